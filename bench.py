@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X backend for zgml's forward-inference path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
-A "step" is one greedy-decode token through the compiled DeviceProgram.
+A "step" is one greedy-decode token through the compiled DeviceProgram. Exactly K steps are timed; a
+stream that reaches the end of the KV cache goes on at position 0. A plain run does only what the
+headline needs (set-up, W warm-up steps, the K timed steps, the result line); every other leg below
+runs with --full. --dump-outputs DIR writes what the timed path computed (N = 1: the K greedy tokens
+and the last step's logits; N > 1: the K tokens) as DIR/<name>.npy, float64 / float32.
 
 N = 1 : BASELINE.json configs[1] — SmolLM-135M, Q4_0 weights, batch 1. `value` is decode tokens/s
         of the device-resident loop (token embedding, causal-mask column, RoPE row, KV position and
-        the argmax all stay in HBM; one hipGraph launch per token). The same JSON line carries
+        the argmax all stay in HBM; one hipGraph launch per token). With --full the JSON line carries
           roofline     : the 4096x4096 Q4_0 mat-vec (the metric's second half) — algorithmic bytes
                          per launch / average launch time, HIP events on the launch stream over a
                          ring of 64 distinct matrices (defeats the 256 MiB Infinity Cache);
@@ -292,11 +296,39 @@ def w8a8_device_leg(be, llama, cpu_us=None, ring=16, chain=64, reps=6):
     return out
 
 
+def resident_stream(sess, first_token, pos, n, max_seq):
+    """n greedy steps of the device-resident loop from `first_token` at position `pos`, in as few calls as the KV cache allows:
+    a stream that reaches max_seq goes on at position 0 (the causal mask then reads only columns this pass has written).
+    Returns (the n tokens, the position after the last step)."""
+    import numpy as np
+    parts, tok = [], first_token
+    while n > 0:
+        if pos >= max_seq:
+            pos = 0
+        m = min(n, max_seq - pos)
+        parts.append(sess.resident_decode(tok, pos, m))
+        tok, pos, n = int(parts[-1][-1]), pos + m, n - m
+    return np.concatenate(parts), pos
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy (float32 / float64 only, 64 MB in all at most)."""
+    import numpy as np
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    log(f"[bench] outputs written to {d}: " + ", ".join(f"{k} {a.dtype} {a.shape}" for k, a in arrays.items()))
+
+
 def bench_single(args):
-    from zgml_amd import Backend, llama
+    import numpy as np
+    from zgml_amd import Backend, capi, llama
     be = Backend(0)
     cfg = llama.preset("smollm-135m")
-    K = min(args.steps, cfg.max_seq_len - args.warmup - 1)
+    K = args.steps
     t0 = time.perf_counter()
     model = llama.Model(cfg, llama.Q4_0, include_dead_f32=False, threads=16)
     sess = llama.Session(model, llama.hip_backend_fns(be))
@@ -304,15 +336,65 @@ def bench_single(args):
     log(f"[bench] SmolLM-135M built+compiled in {time.perf_counter() - t0:.1f}s, {model.program.n_ops} DeviceOps")
 
     # warm-up: W untimed tokens, then EXACTLY K timed tokens continuing the same stream
-    warm = sess.resident_decode(1, 0, max(1, args.warmup))
+    warm, pos = resident_stream(sess, 1, 0, max(1, args.warmup), cfg.max_seq_len)
     be.synchronize()
     t0 = time.perf_counter()
-    toks = sess.resident_decode(int(warm[-1]), max(1, args.warmup), K)
+    toks, _ = resident_stream(sess, int(warm[-1]), pos, K, cfg.max_seq_len)
     be.synchronize()
     dt = time.perf_counter() - t0
     value = K / dt
 
-    extra = {}
+    if args.dump_outputs:
+        # the timed call's tokens and the logits its last step left in the program's logits buffer (their argmax is its last token)
+        logits = np.zeros(cfg.vocab_size, np.float32)
+        io = (capi.ProgramIOC * 1)(capi.ProgramIOC(model.buf("logits"), 0, 0, logits.ctypes.data, logits.nbytes, 0))
+        hip = capi.load_hip()
+        hip.zgml_hip_clear_error(be.ctx)
+        hip.zgml_hip_download_outputs(be.ctx, sess.handle, io, 1)
+        if be.last_error() or int(np.argmax(logits)) != int(toks[-1]):
+            raise RuntimeError(f"logits download: {be.last_error()!r}, argmax {int(np.argmax(logits))} vs token {int(toks[-1])}")
+        dump_outputs(args.dump_outputs, {"tokens": toks.astype(np.float64), "last_logits": logits})
+
+    qb, _ = model.quant_bytes()
+    extra = {"device_ops_per_token": int(model.program.n_ops), "weight_bytes_per_token": qb + cfg.vocab_size * cfg.d_model * 4}
+    roof, cpu, parity_failed = None, None, False
+    if args.full:
+        roof, cpu, parity_failed = full_legs_single(args, be, llama, cfg, model, sess, toks, K, extra)
+    else:
+        sess.close()
+        model.close()
+    be.close()
+
+    def stream_roofline(bytes_per_token, tok_s, what):  # a decode step as a weight stream: bytes every token must read / token time / HBM peak
+        gb = bytes_per_token * tok_s / 1e9
+        return {"bound": "hbm", "achieved": round(gb, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(gb / HBM_PEAK_GBPS, 4),
+                "bytes_per_token": int(bytes_per_token), "tok_s": round(tok_s, 1), "what": what}
+    l7 = extra.get("llama2_7b", {})
+    out = {
+        "metric": "decode_tokens_per_sec", "value": round(value, 1), "unit": "tokens/s", "n_gpus": 1,
+        "steps": K, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
+        "config": {"workload": "SmolLM-135M Q4_0 greedy decode, batch 1, 1xMI355X (BASELINE configs[1])",
+                   "weights": "synthetic Q4_0 (int4 + f16 block scale / 32), tied f32 LM head",
+                   "max_seq": cfg.max_seq_len, "loop": "device-resident (inputs in HBM)", "parallelism": "none"},
+        "roofline": roof, "cpu_baseline": cpu,
+        # (round 5, VERDICT r04 #7: the decode steps' own rooflines and the drop-in path's rate in `parsed`, not only under `extra`)
+        "vtable_tok_s": extra.get("vtable_path_tok_s"),
+        "x_cpu_baseline": round(value / cpu["value"], 2) if cpu and cpu.get("value") else None,
+        "roofline_smollm_decode": stream_roofline(extra["weight_bytes_per_token"], value,
+                                                  "SmolLM-135M token: Q4_0 weights (59.7 MB) + tied f32 LM head (113.2 MB); the whole set fits the 256 MB Infinity Cache, "
+                                                  "so this is a latency figure against an HBM peak, not HBM traffic"),
+        "roofline_llama7b_decode": stream_roofline(l7["q4_0_weight_bytes"], l7["tok_s"], "Llama-2-7B token: 3.716 GB of Q4_0 weights from HBM") if l7.get("tok_s") else None,
+        "extra": extra,
+    }
+    print(json.dumps(out), flush=True)
+    if parity_failed:
+        sys.exit(3)
+
+
+def full_legs_single(args, be, llama, cfg, model, sess, toks, K, extra):
+    """--full at N = 1, after the headline: every other leg of the line, on the headline's context and session (closes both
+    session and model). Fills `extra`; returns (roofline, cpu_baseline, parity_failed)."""
     lc_parity_failed = False
     # long context: the same stream continued at position ~1900 of 2048 (attention reads 1900 KV rows per head;
     # the fused decode attention splits each head over several workgroups there)
@@ -347,9 +429,6 @@ def bench_single(args):
     extra["vtable_path_note"] = "execute_program per token incl. PCIe uploads/logits download (never `value`)"
     prof = be.getRuntimeProfile(sess.handle)
     extra["launches_per_token"] = int(prof.backend_dispatch_count // max(1, prof.call_count))
-    extra["device_ops_per_token"] = int(model.program.n_ops)
-    qb, nw = model.quant_bytes()
-    extra["weight_bytes_per_token"] = qb + cfg.vocab_size * cfg.d_model * 4
     sess.close()
     model.close()
 
@@ -445,33 +524,7 @@ def bench_single(args):
         log("[bench] " + extra["w8a8_device"]["error"])
     except Exception as e:
         extra["w8a8_device"] = {"error": str(e)[:200]}
-    be.close()
-
-    def stream_roofline(bytes_per_token, tok_s, what):  # a decode step as a weight stream: bytes every token must read / token time / HBM peak
-        gb = bytes_per_token * tok_s / 1e9
-        return {"bound": "hbm", "achieved": round(gb, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(gb / HBM_PEAK_GBPS, 4),
-                "bytes_per_token": int(bytes_per_token), "tok_s": round(tok_s, 1), "what": what}
-    l7 = extra.get("llama2_7b", {})
-    out = {
-        "metric": "decode_tokens_per_sec", "value": round(value, 1), "unit": "tokens/s", "n_gpus": 1,
-        "steps": K, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "SmolLM-135M Q4_0 greedy decode, batch 1, 1xMI355X (BASELINE configs[1])",
-                   "weights": "synthetic Q4_0 (int4 + f16 block scale / 32), tied f32 LM head",
-                   "max_seq": cfg.max_seq_len, "loop": "device-resident (inputs in HBM)", "parallelism": "none"},
-        "roofline": roof, "cpu_baseline": cpu,
-        # (round 5, VERDICT r04 #7: the decode steps' own rooflines and the drop-in path's rate in `parsed`, not only under `extra`)
-        "vtable_tok_s": extra.get("vtable_path_tok_s"),
-        "x_cpu_baseline": round(value / cpu["value"], 2) if cpu and cpu.get("value") else None,
-        "roofline_smollm_decode": stream_roofline(extra["weight_bytes_per_token"], value,
-                                                  "SmolLM-135M token: Q4_0 weights (59.7 MB) + tied f32 LM head (113.2 MB); the whole set fits the 256 MB Infinity Cache, "
-                                                  "so this is a latency figure against an HBM peak, not HBM traffic"),
-        "roofline_llama7b_decode": stream_roofline(l7["q4_0_weight_bytes"], l7["tok_s"], "Llama-2-7B token: 3.716 GB of Q4_0 weights from HBM") if l7.get("tok_s") else None,
-        "extra": extra,
-    }
-    print(json.dumps(out), flush=True)
-    if parity_failed:
-        sys.exit(3)
+    return roof, cpu, parity_failed
 
 
 def verify_l7_prefill(be, llama, kind, T=32):
@@ -829,7 +882,7 @@ def bench_sharded(args):
     cfg = llama.preset("llama2-7b", 2048)
     cfg.shard_rank, cfg.shard_world = rank, ws
     model = llama.Model(cfg, llama.Q4_0, threads=max(2, 16 // max(1, ws // 2)))
-    K = min(args.steps, 256)
+    K = args.steps
     W = max(2, args.warmup)
     gold = json.loads((ROOT / "tests" / "golden" / "l7full.json").read_text())["tokens"]
 
@@ -894,9 +947,11 @@ def bench_sharded(args):
     n_chk = min(len(gold), len(toks))
     dist.barrier()
     be.synchronize()
+    timed = []
     t0 = time.perf_counter()
-    for i in range(K):
-        tok = dec.step(tok, W + i)
+    for i in range(K):  # (a stream that reaches the end of the KV cache goes on at position 0)
+        tok = dec.step(tok, (W + i) % cfg.max_seq_len)
+        timed.append(tok)
     be.synchronize()
     dist.barrier()
     dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
@@ -907,7 +962,7 @@ def bench_sharded(args):
     prof = {"step_us": [], "gather_us": []}
     ptok = tok
     for i in range(4):
-        ptok, su, gu = dec.profile_step(ptok, W + K + i)
+        ptok, su, gu = dec.profile_step(ptok, (W + K + i) % cfg.max_seq_len)
         if i:  # (the first eager step after graph replays pays one-off costs)
             prof["step_us"].append(su)
             prof["gather_us"].append(gu)
@@ -920,9 +975,12 @@ def bench_sharded(args):
     eager_us = sum(prof["step_us"]) / max(1, len(prof["step_us"]))
     step_mode = dec.mode
     dec.close()
-    # rank 0: the unsharded model on the same GPU (what the N > 1 value is to be compared with) and the CPU baseline
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        dump_outputs(args.dump_outputs, {"tokens": np.array(timed, np.float64)})
+    # --full, rank 0: the unsharded model on the same GPU (what the N > 1 value is to be compared with) and the CPU baseline
     single, cpu = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             m1 = llama.Model(llama.preset("llama2-7b", 2048), llama.Q4_0, threads=16)
             s1 = llama.Session(m1, llama.hip_backend_fns(be))
@@ -958,7 +1016,7 @@ def bench_sharded(args):
         out = {
             "metric": "decode_tokens_per_sec", "value": round(K / dt, 1), "unit": "tokens/s", "n_gpus": ws,
             "steps": K, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / K, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": f"Llama-2-7B Q4_0 greedy decode, batch 1, weight-row shard over {ws}xMI355X "
                                    "(BASELINE configs[3])",
                        "weights": "synthetic Q4_0", "max_seq": cfg.max_seq_len,
@@ -994,7 +1052,8 @@ def spawn_ranks(args) -> int:
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(Path(__file__).resolve()), "--gpus", str(args.gpus), "--steps", str(args.steps),
-           "--warmup", str(args.warmup)]
+           "--warmup", str(args.warmup)] + (["--full"] if args.full else []) + (["--dump-outputs", str(Path(args.dump_outputs).resolve())] if args.dump_outputs else [])
+    cmd += [f for f, on in (("--skip-cpu", args.skip_cpu), ("--skip-llama7b", args.skip_llama7b), ("--skip-prefill", args.skip_prefill)) if on]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "4")
@@ -1015,12 +1074,17 @@ def spawn_ranks(args) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed decode steps (exactly this many)")
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--skip-cpu", action="store_true", help="omit the cpu_baseline leg")
-    ap.add_argument("--skip-llama7b", action="store_true", help="omit the Llama-2-7B @ 1 GPU extra leg")
-    ap.add_argument("--skip-prefill", action="store_true", help="omit the Llama-2-7B prefill (configs[4]) leg")
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline: roofline, CPU baselines, vtable path, "
+                                                        "long context, int8 KV, W8A8, Llama-2-7B decode / prefill, calibration streams")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed as DIR/<name>.npy")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: omit the cpu_baseline leg")
+    ap.add_argument("--skip-llama7b", action="store_true", help="with --full: omit the Llama-2-7B @ 1 GPU extra leg")
+    ap.add_argument("--skip-prefill", action="store_true", help="with --full: omit the Llama-2-7B prefill (configs[4]) leg")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not (ROOT / "zgml_amd" / "lib" / "libzgml_hip.so").exists():
         import __graft_entry__ as g
         g.build()

@@ -4,7 +4,7 @@ O=gpurun_out/r5; mkdir -p $O
 bash tools/reconcile_chain.sh r5 > $O/reconcile.log 2>&1; tail -3 $O/reconcile.log
 ROUND_DIR=r5 bash tools/prof_decode_by_grid.sh smollm-135m 64 smollm135m_decode_by_grid > /dev/null 2>&1; head -8 $O/smollm135m_decode_by_grid.txt
 ROUND_DIR=r5 bash tools/prof_decode_by_grid.sh llama2-7b 32 llama2_7b_decode_by_grid > /dev/null 2>&1; head -10 $O/llama2_7b_decode_by_grid.txt
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err; python - <<'PY'
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -3 $O/bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r5/bench.json').read().strip().splitlines()[-1])
 print({k: d[k] for k in ('value','vtable_tok_s','x_cpu_baseline','ms_per_step')})

@@ -16,10 +16,13 @@ for san in $KINDS; do
   python3 -c "import __graft_entry__ as g; g.build_host(san='$san')"
   rt=$(gcc -print-file-name=lib$san.so)
   echo "== $san: $TESTS"
-  # detect_leaks=0: the interpreter itself is not leak-clean; the libraries' own errors (overflow, use-after-free, UB, races) abort
-  env LD_PRELOAD="$rt" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+  # detect_leaks=0: the interpreter itself is not leak-clean; the libraries' own errors (overflow, use-after-free, UB, races) abort.
+  # setarch -R (where permitted): this process tree only, without address randomisation — with high-entropy ASLR
+  # (vm.mmap_rnd_bits 32) the interpreter can be mapped outside the application ranges GCC 11's TSan expects ("unexpected memory mapping")
+  NORAND=$(setarch "$(uname -m)" -R true 2>/dev/null && echo "setarch $(uname -m) -R")
+  env LD_PRELOAD="$rt${LD_PRELOAD:+ $LD_PRELOAD}" ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
       TSAN_OPTIONS="halt_on_error=1 report_signal_unsafe=0" \
       ZGML_ORACLE_LIB=$PWD/oracle/_build/$san/libzgml_oracle.so ZGML_HOST_LIB=$PWD/zgml_amd/lib/$san/libzgml_host.so \
-      timeout -k 10 600 python3 -m pytest $TESTS -x -q -m "not gpu" -p no:cacheprovider
+      $NORAND timeout -k 10 600 python3 -m pytest $TESTS -x -q -m "not gpu" -p no:cacheprovider
 done
 echo SANITIZERS_OK
