@@ -1,4 +1,4 @@
-"""The K-split layer launches of short-K models (zgml_amd/csrc/ksplit.hip, runtime.hip: fuse_ksplit) against the oracle.
+"""The K-split layer launches of short-K models (zgml_amd/csrc/ksplit.hip, plan.hip: fuse_ksplit) against the oracle.
 
 A decoder layer of such a model runs as three launches — [deferred vector -> rmsnorm -> gamma -> q / k / v], [attention of each
 head -> that head's partial of the O projection], [O partials + residual -> rmsnorm -> gamma -> gate / up -> SiLU chain,

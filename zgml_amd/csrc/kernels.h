@@ -1,13 +1,22 @@
-// kernels.h — launch interface between the runtime (runtime.hip) and the gfx950 kernels.
+// kernels.h — launch interface between the runtime (runtime.hip, plan.hip) and the gfx950 kernels.
 // All pointers are device pointers; offsets/strides are in f32 elements unless noted.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/zgml_hip.h"
 
 namespace zgml {
+
+// Environment switches (host code): the integer value of `name`, `dflt` when it is not set; env_flag: that value is non-zero.
+// Call sites keep the result in a `static const`, so every switch is read once per process.
+inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
 
 constexpr int kMaxFusedSteps = 8; // Capabilities.hip.max_fused_elementwise_steps
 
@@ -240,7 +249,7 @@ struct QmvPrologue {
 };
 
 // What a launch with a residual-add epilogue (h = y + r) prepares for the rmsnorm -> mul(gamma) -> mat-vec launch that consumes
-// h next (runtime.hip: arm_prenorm): xg_out[n] = h[n] * gamma[n] and ssq_out[n / 16] = sum of h^2 over its 16 columns.
+// h next (plan.hip: arm_prenorm): xg_out[n] = h[n] * gamma[n] and ssq_out[n / 16] = sum of h^2 over its 16 columns.
 struct QmvNextNorm {
     const float* gamma = nullptr;
     float* xg_out = nullptr; // nullptr: nothing to prepare
@@ -259,7 +268,7 @@ struct QmvLaunch {
     QmvPart parts[kMaxQmvParts];
     QmvPrologue pro;
     QmvNextNorm next;
-    // gate / up pair (runtime.hip: arm_pair): parts[0] carries the SiLU chain, parts[1] is plain, both K-on-lanes, same shape;
+    // gate / up pair (plan.hip: arm_pair): parts[0] carries the SiLU chain, parts[1] is plain, both K-on-lanes, same shape;
     // the launch also stores silu(parts[0]) * parts[1] here — the product the NEXT mat-vec's MUL prologue would recompute
     float* pair_out = nullptr;
     uint32_t K = 0;

@@ -1251,7 +1251,7 @@ void launch_fused_elementwise(hipStream_t s, const FusedParams& p) {
 void launch_eltwise_chain(hipStream_t s, const EltChainParams& p) {
     if (p.n == 0) return;
     // ZGML_HIP_ELT_PRELOAD=0: the step-by-step form always
-    static const bool pre_on = !(getenv("ZGML_HIP_ELT_PRELOAD") && atoi(getenv("ZGML_HIP_ELT_PRELOAD")) == 0);
+    static const bool pre_on = env_flag("ZGML_HIP_ELT_PRELOAD", true);
     static const uint32_t vec_min = getenv("ZGML_HIP_ELT_VEC4_MIN") ? (uint32_t)atol(getenv("ZGML_HIP_ELT_VEC4_MIN")) : (1u << 20);
     auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     bool pre = pre_on;
@@ -1294,7 +1294,7 @@ void launch_row_chain(hipStream_t s, const RowChainParams& p, uint32_t rows) {
     if (rows == 0) return;
     // few rows: several workgroups per row share its stores (row_chain_kernel): as many as keep the grid near one workgroup per CU,
     // at most one per 256-column chunk the row really has (ZGML_HIP_ROW_SPLIT=1 switches it off)
-    static const int split_env = getenv("ZGML_HIP_ROW_SPLIT") ? atoi(getenv("ZGML_HIP_ROW_SPLIT")) : 0;
+    static const int split_env = env_int("ZGML_HIP_ROW_SPLIT", 0);
     const uint32_t chunks = cdiv(p.cols, kBlock);
     uint32_t split = 1;
     while (split * 2 <= chunks && rows * split * 2 <= 256 && chunks % (split * 2) == 0) split *= 2;
@@ -1380,7 +1380,7 @@ void launch_attention_decode_batch(hipStream_t s, const AttnDecodeParams* dev_pa
     // d_head 128 (f32 KV): 4-wave workgroups — at short context the chunk needs few waves anyway and a 256-thread workgroup
     // dispatches and merges faster, at long context the splits carry the parallelism: Llama-2-7B 802 -> 812 tok/s, position 1900
     // 605 -> 622 (ZGML_HIP_ATTN_DECODE_BLOCK=1024 / 256 forces either for d_head 64 and 128)
-    static const int block_env = getenv("ZGML_HIP_ATTN_DECODE_BLOCK") ? atoi(getenv("ZGML_HIP_ATTN_DECODE_BLOCK")) : 0;
+    static const int block_env = env_int("ZGML_HIP_ATTN_DECODE_BLOCK", 0);
     const bool small_block = block_env == 256 || (block_env == 0 && d_head == 128);
     if (small_block && (d_head == 64 || d_head == 128)) {
         if (d_head == 64)
@@ -1404,7 +1404,7 @@ void launch_attention_decode_batch(hipStream_t s, const AttnDecodeParams* dev_pa
 void launch_attention_batch(hipStream_t s, const AttentionParams* dev_params, uint32_t n_ops, uint32_t max_seq_q,
                             bool all_dense, uint32_t rows_d_head, const float* zero_word, const AttnPieceSink& sink) {
     if (!n_ops || !max_seq_q) return;
-    static const bool rows_on = !(getenv("ZGML_HIP_ATTN_ROWS") && atoi(getenv("ZGML_HIP_ATTN_ROWS")) == 0);
+    static const bool rows_on = env_flag("ZGML_HIP_ATTN_ROWS", true);
     if (all_dense && rows_d_head && zero_word && rows_on && attention_tiles_applies(max_seq_q, rows_d_head)) {
         launch_attention_tiles(s, dev_params, n_ops, max_seq_q, rows_d_head, zero_word, sink);
         return;

@@ -590,12 +590,12 @@ struct QmvWait {
 };
 
 // PROM: 0 = no prologue, 1 = in-kernel prologue (second vector b, optional rmsnorm), 2 = PRENORM (x-direct launches only): xa_base
-// is the PRODUCER's a * gamma with its partial sums of a^2 right behind it (runtime.hip: arm_prenorm), xb_base the original a;
+// is the PRODUCER's a * gamma with its partial sums of a^2 right behind it (plan.hip: arm_prenorm), xb_base the original a;
 // the finished sums are scaled by 1 / sqrt(mean(a^2) + eps) (the mat-vec is linear in x) and every workgroup stores a 16-element
 // slice of the absorbed ops' outputs — no second vector, no reduction over x and no barrier in front of the first FMA
 __device__ __forceinline__ void kon_pair_finish(const float* red, const QMVArgs& a, float* out0, uint32_t g, uint32_t n_waves, const KonTail& kt, float ones); // (below)
 // PAIR (x-direct launches only; the gate / up launch of a SwiGLU block whose next launch would multiply silu(gate) and up as its
-// prologue — runtime.hip: arm_pair): the workgroup computes the same 16 columns of BOTH matrices (two contiguous parts of equal
+// prologue — plan.hip: arm_pair): the workgroup computes the same 16 columns of BOTH matrices (two contiguous parts of equal
 // shape; x is loaded once) and wave 0 stores the plan's buffers and the product itself (kon_pair_finish), so the down
 // projection streams one vector with no prologue. One workgroup per column group of part 0.
 template <typename ST, bool XVEC, int DEPTH, bool Q4, int PROM, bool GROUPED, bool XD, bool NT, bool CONSUME = false, bool PAIR = false>
@@ -979,7 +979,7 @@ __device__ __forceinline__ void kon_fold_wave(f32x2 (&acc)[8], float T, float* r
 }
 
 // PAIR launches (gate / up): part 0 carries the SiLU chain, part 1 is plain, and the elementwise product silu(gate) * up that
-// the plan's NEXT mat-vec (the down projection) would recompute as its prologue is stored here, `pair_out` (runtime.hip:
+// the plan's NEXT mat-vec (the down projection) would recompute as its prologue is stored here, `pair_out` (plan.hip:
 // arm_pair) — both operands of that product are in this workgroup's registers. Wave 0, behind the barrier.
 __device__ __forceinline__ void kon_pair_finish(const float* red, const QMVArgs& a, float* out0, uint32_t g, uint32_t n_waves, const KonTail& kt, float ones) {
     const uint32_t lane = threadIdx.x & 63, r = lane >> 4, col = lane & 15;
@@ -1199,7 +1199,7 @@ __global__ void __launch_bounds__(512, 4) qmatvec_kon_pair_kernel(QMV_HEAD_PARAM
 // are requested at once and stream while the attention, a 32-workgroup latency chain (record, dynamic words, rope, scores, merges:
 // 3.5 us), runs; behind the counter the projection has its x loads, 4 x 32 weights of FMAs per lane and the fold left. All
 // workgroups are 256 threads and the kernel is held to 128 registers, so four workgroups per CU are admitted; the launch is only
-// built when the whole grid fits three per CU (runtime.hip: fuse_attention_o).
+// built when the whole grid fits three per CU (plan.hip: fuse_attention_o).
 #ifdef ZGML_TRACE // (diagnostics build only: measured slower than two launches; tests load libzgml_hip_trace.so)
 struct AttnOArgs {
     const AttnDecodeParams* params;
@@ -1539,8 +1539,8 @@ bool qweight_packable(uint64_t K, uint64_t N, uint64_t bs) {
 // at least (every workgroup stores a 16-element slice of the absorbed ops' outputs).
 bool qmv_prenorm_ok(const QWeightDev& w, uint32_t K, uint64_t total_cols, uint32_t M) {
     if (w.format == QW_Q4K) return true;
-    static const bool xd_enabled = !(getenv("ZGML_QMV_XDIRECT") && atoi(getenv("ZGML_QMV_XDIRECT")) == 0);
-    static const bool nol = !(getenv("ZGML_HIP_PRENORM_NOL") && atoi(getenv("ZGML_HIP_PRENORM_NOL")) == 0);
+    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
+    static const bool nol = env_flag("ZGML_HIP_PRENORM_NOL", true);
     return nol && xd_enabled && w.format == QW_Q4 && w.scale_f16 && !w.stream_nt && M == 1 && K % 16 == 0 && K <= 4096 && total_cols >= K; // (<= 256 partial sums)
 }
 
@@ -1549,8 +1549,8 @@ bool qmv_prenorm_ok(const QWeightDev& w, uint32_t K, uint64_t total_cols, uint32
 // default cache policy (ZGML_HIP_PAIR_NOL=0 keeps those as a grouped launch + the down projection's MUL prologue).
 bool qmv_pair_ok(const QWeightDev& w) {
     if (w.format == QW_Q4K) return true;
-    static const bool xd_enabled = !(getenv("ZGML_QMV_XDIRECT") && atoi(getenv("ZGML_QMV_XDIRECT")) == 0);
-    static const bool nol = !(getenv("ZGML_HIP_PAIR_NOL") && atoi(getenv("ZGML_HIP_PAIR_NOL")) == 0);
+    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
+    static const bool nol = env_flag("ZGML_HIP_PAIR_NOL", true);
     return nol && xd_enabled && w.format == QW_Q4 && w.scale_f16 && !w.stream_nt;
 }
 
@@ -1574,9 +1574,9 @@ uint32_t qmv_waves(const QWeightDev& w, uint32_t total_blocks = 0) {
     (void)total_blocks;
     const uint32_t U = w.format == QW_Q4 ? w.KC : 2 * w.KC;
     uint32_t waves = cdiv(U, 4);
-    static const int small_cap = getenv("ZGML_QMV_WAVES_SMALLK") ? atoi(getenv("ZGML_QMV_WAVES_SMALLK")) : 16;
+    static const int small_cap = env_int("ZGML_QMV_WAVES_SMALLK", 16);
     uint32_t cap = w.K > 6144 ? 8 : (w.K <= 2048 ? (uint32_t)small_cap : 4); // short K: the launch is one latency chain, more waves shorten it
-    static const int env_cap = getenv("ZGML_QMV_WAVES") ? atoi(getenv("ZGML_QMV_WAVES")) : 0;
+    static const int env_cap = env_int("ZGML_QMV_WAVES", 0);
     if (env_cap > 0) cap = (uint32_t)env_cap;
     if (waves > cap) waves = cap;
     return waves < 1 ? 1 : waves;
@@ -1617,7 +1617,7 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
 // the leading arguments of a single-matrix, prologue-free, x-direct launch with one load step (what the fused O projection
 // needs); false: not that shape
 static bool plain_head_depth1(const QMVArgs& a, const QWeightDev& w0, uint32_t blocks, QmvHead& h) {
-    static const bool xd_enabled = !(getenv("ZGML_QMV_XDIRECT") && atoi(getenv("ZGML_QMV_XDIRECT")) == 0);
+    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
     if (!xd_enabled || a.n_parts != 1 || a.pro.kind != QMV_PRO_NONE || w0.format != QW_Q4 || !w0.scale_f16 || w0.stream_nt) return false;
     const uint32_t waves = qmv_waves(w0, blocks);
     if (cdiv(a.U, waves * 4) != 1 || a.parts[0].NB2 >= (1u << 20)) return false;
@@ -1627,7 +1627,7 @@ static bool plain_head_depth1(const QMVArgs& a, const QWeightDev& w0, uint32_t b
 }
 
 static bool prenorm_late() { // experiments: ZGML_HIP_PRENORM_EARLY=0 folds the prepared norm's partial sums in the kernel's tail (bit 31 of the head flags)
-    static const bool late = getenv("ZGML_HIP_PRENORM_EARLY") && atoi(getenv("ZGML_HIP_PRENORM_EARLY")) == 0;
+    static const bool late = env_int("ZGML_HIP_PRENORM_EARLY", 1) == 0;
     return late;
 }
 // ── the K-on-lanes launches (QW_Q4K) ──
@@ -1636,10 +1636,10 @@ static bool prenorm_late() { // experiments: ZGML_HIP_PRENORM_EARLY=0 folds the 
 // 64 k-pairs up to the cap (the launch is one latency chain inside the decode stream, as for the form above).
 uint32_t kon_waves(const QWeightDev& w) {
     const uint32_t wave_steps = cdiv((w.K + 1) / 2, 64);
-    static const int small_cap = getenv("ZGML_QMV_KON_WAVES_SMALLK") ? atoi(getenv("ZGML_QMV_KON_WAVES_SMALLK")) : 16;
+    static const int small_cap = env_int("ZGML_QMV_KON_WAVES_SMALLK", 16);
     // (in-decode sweep per launch shape, Llama-2-7B, tools/tune_kon.sh: 4 waves for q/k/v, o, gate/up and the LM head, 8 for
     // the down projection's K = 11008: 765 tok/s with 8 everywhere, 792 with 4, 807 with this rule)
-    static const int big_env = getenv("ZGML_QMV_KON_WAVES") ? atoi(getenv("ZGML_QMV_KON_WAVES")) : 0;
+    static const int big_env = env_int("ZGML_QMV_KON_WAVES", 0);
     const int big_cap = big_env > 0 ? big_env : (w.K > 6144 ? 8 : 4);
     const uint32_t cap = (uint32_t)std::max(1, std::min(16, w.K <= 2048 ? small_cap : big_cap));
     return std::max(1u, std::min(wave_steps, cap));
@@ -1688,7 +1688,7 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
             if (q) q++;
         }
     }
-    static const bool contig_ok = !(getenv("ZGML_QMV_CONTIG") && atoi(getenv("ZGML_QMV_CONTIG")) == 0);
+    static const bool contig_ok = env_flag("ZGML_QMV_CONTIG", true);
     bool contig = a.n_parts > 1 && a.n_parts <= 3 && contig_ok;
     for (uint32_t t = 1; t < a.n_parts && contig; t++) {
         const QMVPartDev &pv = a.parts[t - 1], &pt = a.parts[t];
@@ -1766,7 +1766,7 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
                    uint32_t extra_blocks, uint32_t d_head, const FusedO* fo) {
 #ifdef ZGML_TRACE
     { // diagnostics build only: leave out every mat-vec launch of one grid size (wrong results; the token time then drops by that launch's true cost)
-        static const uint32_t skip_blocks = getenv("ZGML_HIP_DEBUG_SKIP_GRID") ? (uint32_t)atoi(getenv("ZGML_HIP_DEBUG_SKIP_GRID")) : 0u;
+        static const uint32_t skip_blocks = (uint32_t)env_int("ZGML_HIP_DEBUG_SKIP_GRID", 0);
         if (skip_blocks && total_blocks == skip_blocks) return true;
     }
 #endif
@@ -1777,11 +1777,11 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
     const bool q4 = w0.format == QW_Q4;
     a.x_vec = xvec ? 1 : 0;
     // x direct (no LDS staging); the rmsnorm prologue reduces the vector while the weights fly
-    static const bool xd_enabled = !(getenv("ZGML_QMV_XDIRECT") && atoi(getenv("ZGML_QMV_XDIRECT")) == 0);
-    static const bool xd_norm = !(getenv("ZGML_QMV_XDIRECT_NORM") && atoi(getenv("ZGML_QMV_XDIRECT_NORM")) == 0);
+    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
+    static const bool xd_norm = env_flag("ZGML_QMV_XDIRECT_NORM", true);
     // (measured: with the rmsnorm prologue the extra per-lane dword loads of x and gamma cost more than the
     // LDS round trip they replace once K is large: Llama-2-7B -5 %, SmolLM-135M +2.7 %)
-    static const uint32_t xd_norm_max_k = getenv("ZGML_QMV_XDNORM_MAXK") ? (uint32_t)atoi(getenv("ZGML_QMV_XDNORM_MAXK")) : 2048u;
+    static const uint32_t xd_norm_max_k = (uint32_t)env_int("ZGML_QMV_XDNORM_MAXK", 2048);
     const bool xd = xd_enabled && (a.pro.kind != QMV_PRO_RMSNORM_MUL || (xd_norm && a.K <= xd_norm_max_k));
     const bool prenorm = a.pro.kind == QMV_PRO_PRENORM;
     if (prenorm && (!qmv_prenorm_ok(w0, a.K, total_blocks * 16, M) || a.pro.ssq != a.pro.xg + a.K)) { // (arm_prenorm asks the same question and lays the partial sums right behind the vector: never reached)
@@ -1792,7 +1792,7 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
     if (!xd && a.pro.kind != QMV_PRO_NONE) // a staged prologue keeps all of x in the register window: 16 floats per thread
         while (waves < (uint32_t)kMaxWaves && waves * 64 * 4 * kXRegs < a.K) waves++;
     // parts back to back in the weight arenas (and <= 4 of them): the kernel needs no argument-block fetch to find them
-    static const bool contig_ok = !(getenv("ZGML_QMV_CONTIG") && atoi(getenv("ZGML_QMV_CONTIG")) == 0);
+    static const bool contig_ok = env_flag("ZGML_QMV_CONTIG", true);
     bool contig = a.n_parts > 1 && a.n_parts <= 3 && contig_ok;
     const size_t sc_elem = (q4 ? 2 : 1) * (w0.scale_f16 ? 2 : 4);
     for (uint32_t t = 1; t < a.n_parts && contig; t++) {
@@ -1919,7 +1919,7 @@ static void build_qmv_args(const QmvLaunch& L, QMVArgs& a, uint32_t& blocks, boo
             const bool silu = pt.n_epi == 5 && st[0].op == ZGML_OP_NEG && !st[0].store && st[1].op == ZGML_OP_EXP && st[1].store &&
                               st[2].op == ZGML_OP_ADD && st[2].operand && st[2].operand != pt.dst && st[2].operand != st[1].store && !st[2].store &&
                               st[3].op == ZGML_OP_RECIP && !st[3].store && st[4].op == ZGML_OP_MUL && st[4].operand == pt.dst && st[4].store;
-            static const bool silu_on = !(getenv("ZGML_QMV_EPI_SILU") && atoi(getenv("ZGML_QMV_EPI_SILU")) == 0);
+            static const bool silu_on = env_flag("ZGML_QMV_EPI_SILU", true);
             const bool residual = pt.n_epi == 1 && st[0].op == ZGML_OP_ADD && st[0].operand && st[0].operand != pt.dst && st[0].store;
             const bool mulvec = pt.n_epi == 1 && st[0].op == ZGML_OP_MUL && st[0].operand && st[0].operand != pt.dst && st[0].store;
             // (the switch is about the SiLU chain only: the residual form also carries the next launch's rmsnorm, arm_prenorm)
@@ -1964,12 +1964,12 @@ bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodePar
     uint32_t shift = 0;
     while ((16u << shift) < d_head) shift++;
 #ifdef ZGML_TRACE // diagnostics build only (tests/handoff_timeout_worker.py loads libzgml_hip_trace.so): one column group never signals
-    static const bool drop_publish = getenv("ZGML_HIP_DEBUG_DROP_PUBLISH") && atoi(getenv("ZGML_HIP_DEBUG_DROP_PUBLISH")) != 0;
+    static const bool drop_publish = env_flag("ZGML_HIP_DEBUG_DROP_PUBLISH", false);
 #else
     constexpr bool drop_publish = false;
 #endif
     f.pub = QmvPublish{counters, {0, n_heads, n_heads + n_kv}, shift, drop_publish ? 1u : 0u};
-    static const uint32_t poll_sleep = getenv("ZGML_HIP_HANDOFF_SLEEP") ? (uint32_t)atoi(getenv("ZGML_HIP_HANDOFF_SLEEP")) : 2u;
+    static const uint32_t poll_sleep = (uint32_t)env_int("ZGML_HIP_HANDOFF_SLEEP", 2);
     f.ho = DecodeHandoff{counters, seen, idx, n_heads, d_head / 16, timeout, poll_sleep, nullptr};
 #ifdef ZGML_TRACE
     if (Lo) { // the O projection rides along (diagnostics build only)
@@ -2053,8 +2053,8 @@ bool launch_attention_o(hipStream_t s, const AttnDecodeParams* dev_params, uint3
     f.n_sp = sp.splits ? sp.splits : 1;
     f.n_attn = n_heads * f.n_sp;
     f.ho = DecodeHandoff{nullptr, nullptr, nullptr, n_heads, d_head / 16, timeout, 2u, out_cnt};
-    static const uint32_t poll_sleep = getenv("ZGML_HIP_ATTN_O_POLL") ? (uint32_t)atoi(getenv("ZGML_HIP_ATTN_O_POLL")) : 10u;
-    static const uint32_t pre_sleep = getenv("ZGML_HIP_ATTN_O_PRESLEEP") ? (uint32_t)atoi(getenv("ZGML_HIP_ATTN_O_PRESLEEP")) : 0u;
+    static const uint32_t poll_sleep = (uint32_t)env_int("ZGML_HIP_ATTN_O_POLL", 10);
+    static const uint32_t pre_sleep = (uint32_t)env_int("ZGML_HIP_ATTN_O_PRESLEEP", 0);
     f.wt = QmvWait{out_cnt, o_seen, n_heads, timeout, poll_sleep, pre_sleep};
     const uint32_t flags = a.parts[0].NB2 | ((waves - 1) << 20) | (1u << 24) | (1u << 30);
     const size_t lds = ((size_t)kMaxWaves * 16 + kMaxWaves) * sizeof(float);

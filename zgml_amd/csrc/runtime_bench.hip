@@ -6,7 +6,7 @@
 extern "C" {
 
 static bool make_synth_weight(zgml_hip_ctx* ctx, uint32_t K, uint32_t N, int q4, uint32_t id, QWeightDev* w, uint32_t M = 1) {
-    static const bool kon_on = !(getenv("ZGML_HIP_QMV_KON") && atoi(getenv("ZGML_HIP_QMV_KON")) == 0);
+    static const bool kon_on = env_flag("ZGML_HIP_QMV_KON", true);
     w->format = q4 ? (M == 1 && kon_on ? QW_Q4K : QW_Q4) : QW_Q8; // (what compile_program picks for a weight that only feeds mat-vecs)
     w->K = K, w->N = N, w->bs = 32;
     w->KC = (K + 31) / 32;

@@ -1,6 +1,6 @@
-// runtime_internal.h — what the translation units of the runtime share (runtime.hip: the C ABI, planner and resident loops;
-// runtime_bench.hip: the measurement entry points; runtime_shard.hip: the row-shard path): the context and program objects and the
-// few internal functions the latter two call. Not part of the boundary (include/zgml_hip.h is).
+// runtime_internal.h — what the translation units of the runtime share (runtime.hip: the C ABI, compile / refresh / execute and the
+// resident loops; plan.hip: the launch planner; runtime_bench.hip: the measurement entry points; runtime_shard.hip: the row-shard
+// path): the context and program objects and the few internal functions they call across files. Not part of the boundary (include/zgml_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -287,21 +287,10 @@ inline hipError_t memset_sync(hipStream_t s, void* dst, int value, size_t bytes)
 } // namespace
 
 namespace zgml_rt {
-// defined in runtime.hip (thin exported forms of its file-local functions)
-void rt_build_plan(zgml_hip_program* p);
-void rt_free_graph(zgml_hip_program* p);
-void rt_run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count);
-bool rt_grow(zgml_hip_ctx* ctx, float** ptr, uint64_t* cap, uint64_t elems);
-uint64_t rt_now_ns();
-void rt_dump_graph(hipGraph_t g, const char* tag);
+// plan.hip
+void build_plan(zgml_hip_program* p);       // p->ops -> p->plan (synchronises the context stream; may run hoisted repeats)
+void free_param_blobs(zgml_hip_program* p); // the device parameter arrays of the plan's launches
+// runtime.hip
+void free_graph(zgml_hip_program* p); // every captured graph of the program
+void dump_graph(hipGraph_t g, const char* tag);
 } // namespace zgml_rt
-#ifndef ZGML_RUNTIME_MAIN // the other translation units call them by the names runtime.hip uses
-namespace {
-inline void build_plan(zgml_hip_program* p) { zgml_rt::rt_build_plan(p); }
-inline void free_graph(zgml_hip_program* p) { zgml_rt::rt_free_graph(p); }
-inline void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count) { zgml_rt::rt_run_plan(p, s, first, count); }
-inline bool grow(zgml_hip_ctx* ctx, float** ptr, uint64_t* cap, uint64_t elems) { return zgml_rt::rt_grow(ctx, ptr, cap, elems); }
-inline uint64_t now_ns() { return zgml_rt::rt_now_ns(); }
-inline void dump_graph(hipGraph_t g, const char* tag) { zgml_rt::rt_dump_graph(g, tag); }
-} // namespace
-#endif
