@@ -1124,6 +1124,28 @@ struct Planner {
             }
         return !members.empty() && !barrier_between(p->barriers, members.front(), last);
     }
+    // ... and among themselves: inside one launch a member's store races with whatever another member reads or writes at ANOTHER
+    // index (delay_legal sees only the non-members, a pass's pattern checks only the chain value). `exempt(x, w, y, s, s_write)`:
+    // the overlap of x's store w with y's span s is one the pass threads through — at the same index by the same lanes, or in
+    // registers. Anything else refuses the fusion.
+    template <typename Exempt>
+    bool members_disjoint(const std::vector<uint32_t>& members, Exempt exempt) const {
+        for (uint32_t x : members)
+            for (const Span& w : access[x].writes)
+                for (uint32_t y : members) {
+                    if (y == x) continue;
+                    for (const Span& s : access[y].reads)
+                        if (spans_overlap(w, s) && !exempt(x, w, y, s, false)) return false;
+                    for (const Span& s : access[y].writes)
+                        if (spans_overlap(w, s) && !exempt(x, w, y, s, true)) return false;
+                }
+        return true;
+    }
+    static bool same_span(const Span& a, const Span& b) { // the same elements (runs as wide as their period are dense)
+        auto dense = [](const Span& x) { return x.period == 0 || x.width == x.period; };
+        return a.buf == b.buf && a.lo == b.lo && a.hi == b.hi &&
+               ((dense(a) && dense(b)) || (a.period == b.period && a.width == b.width));
+    }
     bool free_op(int j) const { return j >= 0 && !in_macro[j] && owner[j] == -1; }
 
     bool exact_dst(uint32_t i, ExactSpan& out) const { // contiguous vector outputs only
@@ -1198,6 +1220,7 @@ struct Planner {
             info.pro.b = buf_at(p, e.src1, e.src1_offset);
             info.pro.store_x = buf_at(p, e.dst, e.dst_offset);
             info.reads.reads = access[P].reads;
+            const ProInfo mul_only = info;
             // rmsnorm feeding one side of the mul?
             for (int side = 0; side < 2; side++) {
                 const ExactSpan sp = side == 0 ? ExactSpan{e.src0, e.src0_offset, e.n} : ExactSpan{e.src1, e.src1_offset, e.n};
@@ -1218,26 +1241,44 @@ struct Planner {
                 info.reads.reads.push_back(side == 0 ? access[P].reads[1] : access[P].reads[0]);
                 break;
             }
-            // the absorbed ops are delayed to the first consumer, and their inputs must survive until the last
-            if (!delay_legal(info.absorbed, info.consumers.front())) continue;
-            // every consumer recomputes the prologue from its inputs, so each input must keep its value
-            // from the op that originally read it (Q for the rmsnorm source, P for the rest) up to the
-            // last consumer
-            bool inputs_live = true;
-            auto live = [&](const Span& r, uint32_t from) {
-                for (uint32_t c = from + 1; c < info.consumers.back() && inputs_live; c++) {
-                    if (std::find(info.absorbed.begin(), info.absorbed.end(), c) != info.absorbed.end()) continue;
-                    for (const Span& w : access[c].writes)
-                        if (spans_overlap(r, w)) inputs_live = false;
+            // the absorbed ops are delayed to the first consumer, and their inputs must survive until the last. A rmsnorm form
+            // that fails falls back to the plain mul form (mul_only) before the prologue is given up.
+            auto legal = [&](const ProInfo& info) {
+                if (!delay_legal(info.absorbed, info.consumers.front())) return false;
+                // every consumer recomputes the prologue from its inputs, so each input must keep its value
+                // from the op that originally read it (Q for the rmsnorm source, P for the rest) up to the
+                // last consumer
+                bool inputs_live = true;
+                auto live = [&](const Span& r, uint32_t from) {
+                    for (uint32_t c = from + 1; c < info.consumers.back() && inputs_live; c++) {
+                        if (std::find(info.absorbed.begin(), info.absorbed.end(), c) != info.absorbed.end()) continue;
+                        for (const Span& w : access[c].writes)
+                            if (spans_overlap(r, w)) inputs_live = false;
+                    }
+                };
+                if (info.pro.kind == QMV_PRO_RMSNORM_MUL) {
+                    live(info.reads.reads[0], info.absorbed.front()); // x, read by the rmsnorm
+                    live(info.reads.reads[1], (uint32_t)P);            // gamma (repeat output), read by the mul
+                } else {
+                    for (const Span& r : info.reads.reads) live(r, (uint32_t)P);
                 }
+                if (!inputs_live || barrier_between(p->barriers, info.absorbed.front(), info.consumers.back())) return false;
+                // in the launch every workgroup reads the prologue's inputs while workgroup 0 stores the absorbed ops' outputs: no
+                // store may meet an input (a gain over the norm's output, x = x * g) or the other store
+                for (uint32_t x : info.absorbed)
+                    for (const Span& w : access[x].writes) {
+                        for (const Span& r : info.reads.reads)
+                            if (spans_overlap(w, r)) return false;
+                        for (uint32_t y : info.absorbed)
+                            for (const Span& w2 : access[y].writes)
+                                if (y != x && spans_overlap(w, w2)) return false;
+                    }
+                return true;
             };
-            if (info.pro.kind == QMV_PRO_RMSNORM_MUL) {
-                live(info.reads.reads[0], info.absorbed.front()); // x, read by the rmsnorm
-                live(info.reads.reads[1], (uint32_t)P);            // gamma (repeat output), read by the mul
-            } else {
-                for (const Span& r : info.reads.reads) live(r, (uint32_t)P);
+            if (!legal(info)) {
+                if (info.pro.kind != QMV_PRO_RMSNORM_MUL || !legal(mul_only)) continue;
+                info = mul_only;
             }
-            if (!inputs_live || barrier_between(p->barriers, info.absorbed.front(), info.consumers.back())) continue;
             const int id = (int)pros.size();
             for (uint32_t c : info.consumers) pro_of[c] = id;
             for (uint32_t x : info.absorbed) owner[x] = -2; // claimed; macro id assigned below
@@ -1288,6 +1329,25 @@ struct Planner {
             }
             m.pro_sig[0] = m.pro.kind, m.pro_sig[1] = (uint64_t)(uintptr_t)m.pro.a, m.pro_sig[2] = (uint64_t)(uintptr_t)m.pro.b;
             m.members.push_back(i);
+            // in the launch every workgroup reads the whole input vector (and the prologue's inputs), workgroup 0 stores the
+            // prologue's outputs (prologues() keeps those apart), and the lanes that own a column run the epilogue on it: an
+            // overlap is legal only as the prologue's output = the anchor's input, or as one span of the anchor's output /
+            // the epilogue met again at the same columns
+            auto exempt = [&](uint32_t x, const Span& w, uint32_t y, const Span& s, bool s_write) {
+                if (x < i && y < i) return true;
+                if (x < i && y == i && !s_write) return same_span(w, s);
+                if (x < i || y < i || (y == i && !s_write)) return false;
+                return same_span(w, s);
+            };
+            // a consumer that recomputes a prologue it does not own reads the prologue's inputs in every workgroup
+            auto shared_inputs_kept = [&](const std::vector<uint32_t>& mem) {
+                if (pro_of[i] < 0 || m.owns_prologue) return true;
+                for (uint32_t x : mem)
+                    for (const Span& w : access[x].writes)
+                        for (const Span& r : pros[pro_of[i]].reads.reads)
+                            if (spans_overlap(w, r)) return false;
+                return true;
+            };
             // epilogue chain
             ExactSpan cur{q.dst, q.dst_offset, q.N};
             uint32_t cur_idx = i;
@@ -1327,7 +1387,7 @@ struct Planner {
                 if (!ok || ns == 0 || m.n_epi + ns > (uint32_t)kMaxEpiSteps) break;
                 std::vector<uint32_t> trial = m.members;
                 trial.push_back((uint32_t)B);
-                if (!delay_legal(trial, (uint32_t)B)) break;
+                if (!delay_legal(trial, (uint32_t)B) || !members_disjoint(trial, exempt) || !shared_inputs_kept(trial)) break;
                 steps[ns - 1].store = buf_at(p, bdst.buf, bdst.off);
                 for (uint32_t t = 0; t < ns; t++) m.epi[m.n_epi++] = steps[t];
                 m.members.push_back((uint32_t)B);
@@ -1336,7 +1396,8 @@ struct Planner {
                 cur = bdst;
                 cur_idx = (uint32_t)B;
             }
-            if (m.members.size() > 1 && !delay_legal(m.members, m.members.back())) { // absorbed prologue + epilogue together
+            if ((m.members.size() > 1 && (!delay_legal(m.members, m.members.back()) || !members_disjoint(m.members, exempt))) ||
+                !shared_inputs_kept(m.members)) { // absorbed prologue + epilogue together
                 // fall back to the bare anchor (keeps correctness trivially)
                 for (uint32_t x : m.members)
                     if (x != i) in_macro[x] = 0;
@@ -1463,6 +1524,27 @@ struct Planner {
             if (std::adjacent_find(m.members.begin(), m.members.end()) != m.members.end()) continue; // an op claimed twice
             m.position = m.members.back();
             if (!delay_legal(m.members, m.position)) continue;
+            // one record per head recomputes the new K / V column from the projections (rope k -> K store -> every head's
+            // attention, V store -> every head's attention) and runs rope q -> attention -> row store: only those edges may meet
+            auto role = [&](uint32_t o) -> int { // 0 rk, 1 sk, 2 sv, 3 + 3h rq, 4 + 3h att, 5 + 3h row store of head h
+                if (o == m.rk) return 0;
+                if (o == m.sk) return 1;
+                if (o == m.sv) return 2;
+                for (size_t h = 0; h < m.heads.size(); h++) {
+                    if (o == m.heads[h].rq) return 3 + 3 * (int)h;
+                    if (o == m.heads[h].att) return 4 + 3 * (int)h;
+                    if ((int)o == m.heads[h].row_store) return 5 + 3 * (int)h;
+                }
+                return -1;
+            };
+            auto exempt = [&](uint32_t x, const Span&, uint32_t y, const Span&, bool s_write) {
+                if (s_write) return false;
+                const int rx = role(x), ry = role(y);
+                if (rx == 0) return ry == 1;
+                if (rx == 1 || rx == 2) return ry >= 4 && (ry - 4) % 3 == 0;
+                return rx >= 3 && (rx - 3) % 3 != 2 && ry == rx + 1;
+            };
+            if (!members_disjoint(m.members, exempt)) continue;
             for (uint32_t x : m.members) {
                 add_access(m.access, access[x]);
                 in_macro[x] = 1;
@@ -1495,7 +1577,12 @@ struct Planner {
                 if (sa.src != out.buf || sa.src_offset != out.off || sa.rows != rows || sa.cols != cols ||
                     sa.src_row_stride != srs || sa.src_col_stride != scs)
                     continue;
-                if (!delay_legal({i, r}, r)) continue;
+                // the anchor stores each element twice (its output, the slice): the slice may meet the anchor's spans only as
+                // the copied output itself
+                if (!delay_legal({i, r}, r) || !members_disjoint({i, r}, [&](uint32_t x, const Span& w, uint32_t y, const Span& s, bool s_write) {
+                        return x == i && y == r && !s_write && same_span(w, s);
+                    }))
+                    continue;
                 Macro m;
                 m.members = {i, r};
                 m.position = r;
@@ -1542,6 +1629,16 @@ struct Planner {
                     if (x >= 0) mem.push_back((uint32_t)x);
                 if (mem.size() < 2 || std::find(t.begin(), t.end(), -1) != t.end()) continue;
                 if (!delay_legal(mem, mem.back())) continue;
+                // the launch reads every input row up front and recomputes the chain values (launch_row_chain keeps ONE workgroup
+                // per row when a store meets a read): members may meet only on the same elements, and a member reads what an
+                // earlier one stored only as the chain value itself (the add's sum as the norm's source, the norm as the mul's side)
+                const int add = t.front() == (int)i ? -1 : t.front(), mul = t.back() == (int)i ? -1 : t.back();
+                auto exempt = [&](uint32_t x, const Span& w, uint32_t y, const Span& s, bool s_write) {
+                    if (!same_span(w, s)) return false;
+                    if (s_write || y < x) return true;
+                    return ((int)x == add && y == i) || (x == i && (int)y == mul);
+                };
+                if (!members_disjoint(mem, exempt)) continue;
                 Macro m;
                 m.chain = true;
                 m.members = mem;
@@ -1617,7 +1714,10 @@ struct Planner {
                     if (!append(trial_p, r, &cur, nxt) || nxt.n != cur.n) continue;
                     std::vector<uint32_t> trial = m.members;
                     trial.push_back(r);
-                    if (!delay_legal(trial, r)) continue;
+                    // thread i runs every step at index i (an operand an earlier step stored keeps the step-by-step reads:
+                    // launch_eltwise_chain): members may meet only on the same elements
+                    if (!delay_legal(trial, r) || !members_disjoint(trial, [](uint32_t, const Span& w, uint32_t, const Span& s, bool) { return same_span(w, s); }))
+                        continue;
                     m.elt = trial_p, m.members = trial, cur = nxt, grown = true;
                     break;
                 }

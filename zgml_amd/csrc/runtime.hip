@@ -375,10 +375,16 @@ bool same_static(const zgml_device_op& a, const zgml_device_op& b) {
         return memcmp(x, y, off) == 0 && memcmp(x + off + flen, y + off + flen, len - off - flen) == 0;
     };
     switch (a.kind) {
+        // a store with patch_stride == 0 is static: its offset / column is not on p->dyn_ops, so a change must rebuild the plan
         case ZGML_DOP_SLICE_ASSIGN:
+            if (a.u.slice_assign.patch_stride == 0 || b.u.slice_assign.patch_stride == 0)
+                return memcmp(&a.u.slice_assign, &b.u.slice_assign, sizeof(a.u.slice_assign)) == 0;
             return except(&a.u.slice_assign, &b.u.slice_assign, sizeof(a.u.slice_assign), offsetof(zgml_op_slice_assign, dst_offset), sizeof(uint32_t));
         case ZGML_DOP_ATTENTION: return except(&a.u.attention, &b.u.attention, sizeof(a.u.attention), offsetof(zgml_op_attention, seq_kv), sizeof(uint32_t));
-        case ZGML_DOP_KVQ_STORE: return except(&a.u.kvq_store, &b.u.kvq_store, sizeof(a.u.kvq_store), offsetof(zgml_op_kvq_store, col), sizeof(uint32_t));
+        case ZGML_DOP_KVQ_STORE:
+            if (a.u.kvq_store.patch_stride == 0 || b.u.kvq_store.patch_stride == 0)
+                return memcmp(&a.u.kvq_store, &b.u.kvq_store, sizeof(a.u.kvq_store)) == 0;
+            return except(&a.u.kvq_store, &b.u.kvq_store, sizeof(a.u.kvq_store), offsetof(zgml_op_kvq_store, col), sizeof(uint32_t));
         case ZGML_DOP_ATTENTION_KVQ:
             return except(&a.u.attention_kvq, &b.u.attention_kvq, sizeof(a.u.attention_kvq), offsetof(zgml_op_attention_kvq, seq_kv), sizeof(uint32_t));
         case ZGML_DOP_FUSED_ELEMENTWISE: {
