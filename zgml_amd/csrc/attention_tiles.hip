@@ -239,8 +239,7 @@ __global__ void __launch_bounds__(kTileWavesMax * 64) attention_tiles_kernel(con
 } // namespace
 
 bool attention_tiles_applies(uint32_t max_seq_q, uint32_t d_head) {
-    static const bool on = env_flag("ZGML_HIP_ATTN_TILES", true);
-    return on && max_seq_q >= 16 && (d_head == 64 || d_head == 128);
+    return sw().hip_attn_tiles && max_seq_q >= 16 && (d_head == 64 || d_head == 128);
 }
 
 // every op dense (q/k/v rows contiguous, 16-byte aligned, strides % 4 == 0 — the planner's `dense`) with this d_head
@@ -248,9 +247,8 @@ void launch_attention_tiles(hipStream_t s, const AttentionParams* dev_params, ui
                             const float* zero_word, const AttnPieceSink& sink) {
     const uint32_t q_tiles = (max_seq_q + 15) / 16;
     const uint64_t units = (uint64_t)q_tiles * n_ops;
-    static const int env_w = env_int("ZGML_HIP_ATTN_TILES_WAVES", 0);
     // enough (query tile, head) workgroups to fill the chip: 4 waves each; few: 8, so a long context is spread over more waves
-    uint32_t waves = env_w > 0 ? (uint32_t)env_w : (units >= 256 ? 4 : kTileWavesMax);
+    uint32_t waves = sw().hip_attn_tiles_waves > 0 ? (uint32_t)sw().hip_attn_tiles_waves : (units >= 256 ? 4 : kTileWavesMax);
     waves = waves < 1 ? 1 : (waves > (uint32_t)kTileWavesMax ? (uint32_t)kTileWavesMax : waves);
     const size_t lds = ((size_t)waves * (d_head / 16) * 4 * 64 + (size_t)waves * 16 * 3 + 16) * sizeof(float);
     const dim3 grid(q_tiles, n_ops);

@@ -677,7 +677,7 @@ void launch_pack_f16(hipStream_t s, const float* b, uint32_t b_rs, uint32_t b_cs
 }
 
 static uint32_t f16_tiles_per_wg(uint32_t M) { // m-tiles a workgroup of the A-pre-laid-out kernel carries
-    static const bool wide = env_flag("ZGML_F16_TILE2_WIDE", true);
+    const bool wide = sw().f16_tile2_wide;
     return M > 64 && wide ? 8 : (M > 32 && wide ? 4 : (M > 16 ? 2 : 1));
 }
 // the pre-laid-out A operand of an M x K matmul has no padding rows / columns (a producer may then write it in place of
@@ -691,19 +691,9 @@ static uint64_t f16_a_bytes(uint32_t M, uint32_t K) { // the pre-laid-out A oper
 }
 // the shared-A form's K split: at most kT3MaxWgs workgroups per launch, one partial tile (8 waves x R x 1 KiB) each
 constexpr uint64_t kT3MaxWgs = 1024;
-static bool f16_tile3_on() { // the shared-A K-split experiment: diagnostics build only, and only on request
-#ifdef ZGML_TRACE
-    static const bool on = env_flag("ZGML_F16_TILE3", false);
-    return on;
-#else
-    return false;
-#endif
-}
-static bool f16_tile4_on();
 uint64_t dense_f16_scratch_bytes(uint32_t M, uint32_t K) {
-    static const bool on = env_flag("ZGML_F16_TILE2", true);
-    if (!on || M <= 1) return 0;
-    return f16_a_bytes(M, K) + (M <= 32 && M > 16 && (f16_tile3_on() || f16_tile4_on()) ? kT3MaxWgs * kT3Waves * 2 * 1024 : 0);
+    if (!sw().f16_tile2 || M <= 1) return 0;
+    return f16_a_bytes(M, K) + (M <= 32 && M > 16 && (sw().f16_tile3 || sw().f16_tile4) ? kT3MaxWgs * kT3Waves * 2 * 1024 : 0);
 }
 
 // M in (16, 32], every part a whole number of 128-column tiles: the shared-A form with a K split. false: not applicable.
@@ -712,7 +702,7 @@ static bool launch_dense_f16_tile3(hipStream_t s, const DenseF16Params* p, uint3
     (void)s, (void)p, (void)n, (void)KC;
     return false;
 #else
-    if (!f16_tile3_on() || p[0].M <= 16 || p[0].M > 32) return false;
+    if (!sw().f16_tile3 || p[0].M <= 16 || p[0].M > 32) return false;
     F16Args3 a{};
     uint32_t tiles = 0;
     for (uint32_t t = 0; t < n; t++) {
@@ -722,9 +712,8 @@ static bool launch_dense_f16_tile3(hipStream_t s, const DenseF16Params* p, uint3
     }
     if ((uint64_t)tiles * sizeof(uint32_t) > kQmmScratchHead) return false; // one counter word per column tile
     // K slices: ~2.5 workgroups per CU, whole stages per slice, at least 4 stages each, no more partial tiles than the scratch holds
-    static const int env_sk = env_int("ZGML_F16_TILE3_SK", 0);
     const uint32_t stages = cdiv(KC, kT3Chunks);
-    uint32_t SK = env_sk > 0 ? (uint32_t)env_sk : std::max(1u, std::min(cdiv(640u, tiles), stages / 4));
+    uint32_t SK = sw().f16_tile3_sk > 0 ? (uint32_t)sw().f16_tile3_sk : std::max(1u, std::min(cdiv(640u, tiles), stages / 4));
     SK = std::max(1u, std::min<uint32_t>(SK, (uint32_t)(kT3MaxWgs / tiles)));
     uint32_t cps = cdiv(stages, SK) * kT3Chunks; // chunks per slice
     SK = cdiv(KC, cps);
@@ -737,29 +726,13 @@ static bool launch_dense_f16_tile3(hipStream_t s, const DenseF16Params* p, uint3
 #endif
 }
 
-static bool f16_tile4_on() { // the A-stationary experiment: diagnostics build only, and only on request
-#ifdef ZGML_TRACE
-    static const bool on = env_flag("ZGML_F16_TILE4", false);
-    return on;
-#else
-    return false;
-#endif
-}
-static uint32_t f16_device_cus() {
-    static const uint32_t n = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        return (uint32_t)cus;
-    }();
-    return n;
-}
 // M in (16, 32]: the A-stationary form. false: not applicable (launch nothing).
 static bool launch_dense_f16_tile4(hipStream_t s, const DenseF16Params* p, uint32_t n, uint32_t KC) {
 #ifndef ZGML_TRACE
     (void)s, (void)p, (void)n, (void)KC;
     return false;
 #else
-    if (!f16_tile4_on() || p[0].M <= 16 || p[0].M > 32) return false;
+    if (!sw().f16_tile4 || p[0].M <= 16 || p[0].M > 32) return false;
     F16Args4 a{};
     uint32_t groups = 0;
     for (uint32_t t = 0; t < n; t++) {
@@ -767,11 +740,10 @@ static bool launch_dense_f16_tile4(hipStream_t s, const DenseF16Params* p, uint3
         groups += p[t].N / 16;
     }
     if ((uint64_t)groups * sizeof(uint32_t) > kQmmScratchHead || groups == 0) return false; // one counter word per column group
-    const uint32_t cus = f16_device_cus();
+    const uint32_t cus = device_cus();
     // K slices: every CU ~10 tasks (column group x slice), a slice of at most 64 chunks (its A: 128 KiB of LDS) and at least 8
-    static const int env_sk = env_int("ZGML_F16_TILE4_SK", 0);
     const uint32_t sk_min = cdiv(KC, (uint32_t)kT4MaxSliceChunks), sk_max = std::max(sk_min, KC / 8);
-    uint32_t SK = env_sk > 0 ? (uint32_t)env_sk : (10u * cus + groups / 2) / groups;
+    uint32_t SK = sw().f16_tile4_sk > 0 ? (uint32_t)sw().f16_tile4_sk : (10u * cus + groups / 2) / groups;
     SK = std::max(sk_min, std::min(SK, sk_max));
     SK = std::min(SK, cus);
     uint32_t cps = cdiv(KC, SK);
@@ -788,8 +760,7 @@ static bool launch_dense_f16_tile4(hipStream_t s, const DenseF16Params* p, uint3
     using Fn4 = void (*)(F16Args4);
     // (round 5) weight loads in flight per wave: a wave walks its task's 64 chunks one after the other, so with 4 in flight and
     // ~1.6 us of loaded latency a chunk costs >= 0.4 us whatever else happens: ZGML_F16_TILE4_DEPTH=8 doubles the ring
-    static const int env_depth = env_int("ZGML_F16_TILE4_DEPTH", 4);
-    const bool deep = env_depth >= 8 && cps % 8 == 0;
+    const bool deep = sw().f16_tile4_depth >= 8 && cps % 8 == 0;
     const Fn4 fn = deep ? (nt ? (Fn4)dense_f16_tile4_kernel<true, 8> : (Fn4)dense_f16_tile4_kernel<false, 8>)
                         : (nt ? (Fn4)dense_f16_tile4_kernel<true, 4> : (Fn4)dense_f16_tile4_kernel<false, 4>);
     static bool attr_set[4] = {false, false, false, false};
@@ -809,13 +780,12 @@ static void launch_dense_f16_tile2(hipStream_t s, const DenseF16Params* p, uint3
     }
     if (R == 2 && tiles == 2 && launch_dense_f16_tile3(s, p, n, KC)) return;
     if (R == 2 && tiles == 2 && launch_dense_f16_tile4(s, p, n, KC)) return;
-    static const int env_w = env_int("ZGML_F16_TILE2_WAVES", 8);
-    const uint32_t waves = std::max(1u, std::min<uint32_t>(KC, (uint32_t)env_w));
+    const uint32_t waves = std::max(1u, std::min<uint32_t>(KC, (uint32_t)sw().f16_tile2_waves));
     // column groups per workgroup (R <= 2 only: the wide-M forms already amortise A over 4 / 8 m-tiles): as many as keep the grid
     // at >= ~1.3 workgroups per CU, every part a whole number of workgroups
     uint32_t total_groups = 0;
     for (uint32_t t = 0; t < n; t++) total_groups += p[t].N / 16;
-    static const int env_cg = env_int("ZGML_F16_TILE2_CG", 0);
+    const int env_cg = sw().f16_tile2_cg;
     uint32_t CG = 1;
     if (R <= 2) {
         // measured at M = 32, K = 4096 (tools/f16_m32_sweep.sh, us per launch incl. the A pack; CG = 1 / 2 / 4): N = 4096 13.6 / 16.8 / 22.9,
@@ -852,7 +822,7 @@ static void launch_dense_f16_tile2(hipStream_t s, const DenseF16Params* p, uint3
                       : ZGML_T2(1);
 #undef ZGML_T2
 #ifdef ZGML_TRACE // the MFMA-sink experiment (wrong results): diagnostics build only
-    static const int sink = env_int("ZGML_F16_SINK", 0);
+    const int sink = sw().f16_sink;
     if (sink && R == 2 && nt) {
         if (CG == 2)
             fn = sink == 2 ? (Fn2)dense_f16_tile2_kernel<2, true, 2, 2> : (Fn2)dense_f16_tile2_kernel<2, true, 2, 1>;
@@ -908,8 +878,7 @@ void launch_dense_f16(hipStream_t s, const DenseF16Params& p) {
     // two column groups per workgroup share the staged x chunk — only worth it when the grid stays several
     // rounds deep (measured at M = 32: N = 32000 75 -> 67 us; N = 11008 neutral, N = 4096 slower); the
     // 8-wave R = 2 form has no room for a second wave set
-    static const int env_g = env_int("ZGML_F16_GROUPS", 0);
-    uint32_t G = env_g ? (uint32_t)env_g : (a.NB2 >= 1536 ? 2u : 1u);
+    uint32_t G = sw().f16_groups ? (uint32_t)sw().f16_groups : (a.NB2 >= 1536 ? 2u : 1u);
     if (waves * G > 8) G = 1;
     size_t lds = 2ull * 16 * R * ((chf + 8) / 2) * sizeof(float);
     const size_t red = (size_t)waves * G * R * 256 * sizeof(float);

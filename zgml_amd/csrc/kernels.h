@@ -7,16 +7,19 @@
 #include <stdlib.h>
 
 #include "../../include/zgml_hip.h"
+#include "switches.h"
 
 namespace zgml {
 
-// Environment switches (host code): the integer value of `name`, `dflt` when it is not set; env_flag: that value is non-zero.
-// Call sites keep the result in a `static const`, so every switch is read once per process.
-inline int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
+// compute units of the current device (host code; looked up once per process, 256 when the query fails)
+inline uint32_t device_cus() {
+    static const uint32_t n = [] {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        return (uint32_t)cus;
+    }();
+    return n;
 }
-inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
 
 constexpr int kMaxFusedSteps = 8; // Capabilities.hip.max_fused_elementwise_steps
 

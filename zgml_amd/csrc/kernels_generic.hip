@@ -1251,11 +1251,9 @@ void launch_fused_elementwise(hipStream_t s, const FusedParams& p) {
 void launch_eltwise_chain(hipStream_t s, const EltChainParams& p) {
     if (p.n == 0) return;
     // ZGML_HIP_ELT_PRELOAD=0: the step-by-step form always
-    static const bool pre_on = env_flag("ZGML_HIP_ELT_PRELOAD", true);
-    static const uint32_t vec_min = getenv("ZGML_HIP_ELT_VEC4_MIN") ? (uint32_t)atol(getenv("ZGML_HIP_ELT_VEC4_MIN")) : (1u << 20);
     auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    bool pre = pre_on;
-    bool vec = p.n >= vec_min && p.n % 4 == 0 && a16(p.src) && (!p.ap || (p.ap_cols % 4 == 0 && a16(p.ap)));
+    bool pre = sw().hip_elt_preload;
+    bool vec = p.n >= sw().hip_elt_vec4_min && p.n % 4 == 0 && a16(p.src) && (!p.ap || (p.ap_cols % 4 == 0 && a16(p.ap)));
     for (uint32_t t = 0; pre && t < p.n_steps; t++) {
         vec = vec && a16(p.steps[t].secondary) && a16(p.steps[t].store);
         for (uint32_t e = 0; pre && p.steps[t].secondary && e < t; e++) // an operand written by an earlier step of this chain: keep the step-by-step reads
@@ -1294,7 +1292,7 @@ void launch_row_chain(hipStream_t s, const RowChainParams& p, uint32_t rows) {
     if (rows == 0) return;
     // few rows: several workgroups per row share its stores (row_chain_kernel): as many as keep the grid near one workgroup per CU,
     // at most one per 256-column chunk the row really has (ZGML_HIP_ROW_SPLIT=1 switches it off)
-    static const int split_env = env_int("ZGML_HIP_ROW_SPLIT", 0);
+    const int split_env = sw().hip_row_split;
     const uint32_t chunks = cdiv(p.cols, kBlock);
     uint32_t split = 1;
     while (split * 2 <= chunks && rows * split * 2 <= 256 && chunks % (split * 2) == 0) split *= 2;
@@ -1380,7 +1378,7 @@ void launch_attention_decode_batch(hipStream_t s, const AttnDecodeParams* dev_pa
     // d_head 128 (f32 KV): 4-wave workgroups — at short context the chunk needs few waves anyway and a 256-thread workgroup
     // dispatches and merges faster, at long context the splits carry the parallelism: Llama-2-7B 802 -> 812 tok/s, position 1900
     // 605 -> 622 (ZGML_HIP_ATTN_DECODE_BLOCK=1024 / 256 forces either for d_head 64 and 128)
-    static const int block_env = env_int("ZGML_HIP_ATTN_DECODE_BLOCK", 0);
+    const int block_env = sw().hip_attn_decode_block;
     const bool small_block = block_env == 256 || (block_env == 0 && d_head == 128);
     if (small_block && (d_head == 64 || d_head == 128)) {
         if (d_head == 64)
@@ -1404,12 +1402,11 @@ void launch_attention_decode_batch(hipStream_t s, const AttnDecodeParams* dev_pa
 void launch_attention_batch(hipStream_t s, const AttentionParams* dev_params, uint32_t n_ops, uint32_t max_seq_q,
                             bool all_dense, uint32_t rows_d_head, const float* zero_word, const AttnPieceSink& sink) {
     if (!n_ops || !max_seq_q) return;
-    static const bool rows_on = env_flag("ZGML_HIP_ATTN_ROWS", true);
-    if (all_dense && rows_d_head && zero_word && rows_on && attention_tiles_applies(max_seq_q, rows_d_head)) {
+    if (all_dense && rows_d_head && zero_word && sw().hip_attn_rows && attention_tiles_applies(max_seq_q, rows_d_head)) {
         launch_attention_tiles(s, dev_params, n_ops, max_seq_q, rows_d_head, zero_word, sink);
         return;
     }
-    if (all_dense && rows_d_head && zero_word && rows_on) { // every op dense with this d_head: the streaming kernel
+    if (all_dense && rows_d_head && zero_word && sw().hip_attn_rows) { // every op dense with this d_head: the streaming kernel
         const dim3 grid(max_seq_q, n_ops);
         // enough (query, head) workgroups to fill the chip: 4 waves each (a 16-wave workgroup whose context needs 2
         // still pays for launching 16); few workgroups: all 16 so a long context is spread over more waves
@@ -1606,7 +1603,7 @@ void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes) {
     uint64_t n4 = bytes / 16;
     if (n4 == 0) return;
     // ZGML_COPY_VARIANT: 0 = the plain loop, else U | NT << 8 | blocks-per-CU << 16 (experiments); default: 8 in flight, nt, 32 blocks per CU (sweep: 4.5-5.1 TB/s over all variants on this part)
-    static const int variant = getenv("ZGML_COPY_VARIANT") ? (int)strtol(getenv("ZGML_COPY_VARIANT"), nullptr, 0) : (8 | 1 << 8 | 32 << 16);
+    const int variant = sw().copy_variant;
     if (variant == 0) {
         copy_f4_kernel<<<2048, kBlock, 0, s>>>((float4*)dst, (const float4*)src, n4);
         return;

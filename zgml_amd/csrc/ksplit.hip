@@ -817,7 +817,7 @@ bool ks_weight_ok(const QWeightDev& w) { return w.format == QW_Q4 && w.scale_f16
 bool ks_norm_ok(const KsNormIn& in) { return ks_vec_aligned(in); }
 
 static uint32_t ks_proj_gp(const KsProjLaunch& L) { // column groups per workgroup: 2 unless a matrix has an odd number of them
-    static const int env = env_int("ZGML_KS_PROJ_GP", 0);
+    const int env = sw().ks_proj_gp;
     uint32_t gp = env == 1 || env == 2 || env == 4 ? (uint32_t)env : 2u;
     for (uint32_t t = 0; t < L.n_parts; t++)
         while (gp > 1 && (L.w[t].N / 16) % gp) gp >>= 1;
@@ -842,7 +842,7 @@ void launch_ks_proj(hipStream_t s, const KsProjLaunch& L) {
         a.wg_begin[t] = wgs;
         if (t < L.n_parts) wgs += (uint32_t)(L.w[t].N / 16) / gp;
     }
-    static const int env_w = env_int("ZGML_KS_PROJ_WAVES", 0);
+    const int env_w = sw().ks_proj_waves;
     uint32_t W = ks_pick_waves(L.in.K, KC * gp); // one unit per row when 4 W / gp >= KC
     if (env_w >= 1 && env_w <= 16 && (uint32_t)env_w * 64 >= L.in.K / 4) W = (uint32_t)env_w;
     const uint32_t n_slots = 4 * W / gp, U = cdiv(KC, n_slots);
@@ -863,7 +863,7 @@ uint32_t ks_mlp_parts(const KsMlpLaunch& L) { return (uint32_t)(L.gate.N / 32); 
 
 static void ks_mlp_shape(const KsMlpLaunch& L, uint32_t& W, uint32_t& UG, uint32_t& UD) {
     const uint32_t KC = L.gate.KC, NB2_d = (uint32_t)(L.down.N / 16);
-    static const int env_w = env_int("ZGML_KS_MLP_WAVES", 0);
+    const int env_w = sw().ks_mlp_waves;
     // rows: the down projection wants one row per column group; gate / up want 4 W rows x UG chunks >= 4 KC: UG <= 2 is the aim
     W = ks_pick_waves(L.in.K, std::max(NB2_d, 2 * KC));
     if (env_w >= 1 && env_w <= 16 && (uint32_t)env_w * 64 >= L.in.K / 4) W = (uint32_t)env_w;
@@ -949,11 +949,9 @@ bool launch_ks_layer_a(hipStream_t s, const KsProjLaunch& PL, const KsAttnOLaunc
     uint32_t shift = 0;
     while ((16u << shift) < AL.d_head) shift++;
     g.pub = KsPublish{counters, {0, AL.n_heads, AL.n_heads + n_kv}, shift};
-    static const uint32_t poll_sleep = (uint32_t)env_int("ZGML_HIP_HANDOFF_SLEEP", 2);
-    g.ho = DecodeHandoff{counters, seen, idx, AL.n_heads, (AL.d_head / 16) / 2, timeout, poll_sleep, nullptr};
+    g.ho = DecodeHandoff{counters, seen, idx, AL.n_heads, (AL.d_head / 16) / 2, timeout, (uint32_t)sw().hip_handoff_sleep, nullptr};
     g.n_proj = wgs, g.n_heads = AL.n_heads;
-    static const uint32_t dbg = (uint32_t)env_int("ZGML_KS_DEBUG_A", 0);
-    g.dbg = dbg;
+    g.dbg = (uint32_t)sw().ks_debug_a;
     using Fn = void (*)(KsLayerAArgs);
     Fn fn = nullptr;
 #define KS_LA2(LPK_, KVQ_, UO_) (U <= 1 ? (Fn)ks_layer_a_kernel<LPK_, KVQ_, UO_, 2, 1> : (Fn)ks_layer_a_kernel<LPK_, KVQ_, UO_, 2, 2>)

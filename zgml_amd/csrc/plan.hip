@@ -32,15 +32,14 @@ const T* upload_params(zgml_hip_program* p, const std::vector<T>& v) {
 // dependent rounds per 128 keys; splitting from 64 keys on gave Llama-2-7B +4 % over positions 200..328 (760 -> 791 tok/s) at no
 // cost at positions 4..132 and 1900 (profiles/r05_split_sweep_7b.txt; 32 is worse again: the merge costs more than a round).
 AttnSplit attn_split_for(zgml_hip_program* p, uint32_t n_heads, uint32_t d_head, uint32_t max_kv, int default_min_keys = 128) {
-    static const int want = env_int("ZGML_HIP_ATTN_SPLIT", 16);
-    static const int min_keys_env = env_int("ZGML_HIP_ATTN_SPLIT_MIN_KEYS", -1);
+    const int want = sw().hip_attn_split;
+    const int min_keys_env = sw().hip_attn_split_min_keys;
     AttnSplit sp;
     const int64_t min_keys = p->ctx->opt_attn_split_min_keys >= 0 ? p->ctx->opt_attn_split_min_keys : (min_keys_env >= 0 ? min_keys_env : default_min_keys);
     if (min_keys == 0 || want <= 1) return sp;
     sp.min_keys = (uint32_t)std::min<int64_t>(std::max<int64_t>(32, min_keys), 1 << 30);
     uint32_t S = std::min<uint32_t>((uint32_t)std::max(want, 1), max_kv / sp.min_keys);
-    static const uint32_t wg_cap = (uint32_t)env_int("ZGML_HIP_ATTN_SPLIT_WGS", 256);
-    S = std::min(S, std::max(1u, wg_cap / std::max(n_heads, 1u))); // about one (1024-thread) workgroup per CU: idle ones still cost dispatch
+    S = std::min(S, std::max(1u, (uint32_t)sw().hip_attn_split_wgs / std::max(n_heads, 1u))); // about one (1024-thread) workgroup per CU: idle ones still cost dispatch
     if (S <= 1) return sp;
     const uint64_t need = (uint64_t)n_heads * S * (d_head + 4);
     if (need > p->split_buf_floats) { // earlier launches keep their (smaller) block: it stays in param_blobs
@@ -156,8 +155,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                     fp.reuse_a = p->split_pos + 1 == pos && p->split_input == dp.a && p->split_M == dp.M && p->split_K == dp.K &&
                                  p->split_in_rs == dp.a_rs && p->split_kind == 2;
                     // ... or the launch that produced the rows wrote the operand itself (as for the quantized split below)
-                    static const bool fuse_pack = env_flag("ZGML_HIP_FUSE_SPLIT", true);
-                    if (!fp.reuse_a && fuse_pack && dense_f16_a_unpadded(dp.M, dp.K) && dp.a_rs == dp.K) {
+                    if (!fp.reuse_a && sw().hip_fuse_split && dense_f16_a_unpadded(dp.M, dp.K) && dp.a_rs == dp.K) {
                         for (size_t back = p->plan.size(); back-- > 0;) {
                             const Launch& prev = p->plan[back];
                             const bool fits = prev.hook && prev.hook->out == dp.a &&
@@ -211,8 +209,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                              p->split_in_rs == qp.in_rs && p->split_kind == 1;
             // ... or finds them written by the launch that produced the rows (a row chain right in front of it, no other
             // splitting launch in between): that launch is armed and this one skips its split_a_kernel launch
-            static const bool fuse_split = env_flag("ZGML_HIP_FUSE_SPLIT", true);
-            if (splits && !qp.reuse_split && fuse_split && qp.M % 16 == 0 && qp.K % 128 == 0 && qp.in_rs == qp.K) {
+            if (splits && !qp.reuse_split && sw().hip_fuse_split && qp.M % 16 == 0 && qp.K % 128 == 0 && qp.in_rs == qp.K) {
                 for (size_t back = p->plan.size(); back-- > 0;) {
                     const Launch& prev = p->plan[back];
                     const bool fits = prev.hook && prev.hook->out == qp.input &&
@@ -221,7 +218,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                         *prev.hook->ap = (uint16_t*)scratch, *prev.hook->ap_S = qp.K / 128;
                         if (prev.hook->ap_cols) *prev.hook->ap_cols = qp.K;
                         qp.reuse_split = 1;
-                        if (getenv("ZGML_HIP_DEBUG_PLAN")) fprintf(stderr, "[zgml_hip] A pieces of op %u (M %u, K %u) written by the launch of kind %u at plan[%zu]\n", (unsigned)i, qp.M, qp.K, prev.kind, back);
+                        if (sw().hip_debug_plan.set) fprintf(stderr, "[zgml_hip] A pieces of op %u (M %u, K %u) written by the launch of kind %u at plan[%zu]\n", (unsigned)i, qp.M, qp.K, prev.kind, back);
                         break;
                     }
                     if (prev.kind == ZGML_DOP_QMATMUL || prev.kind == ZGML_DOP_MATMUL) break; // may own the scratch
@@ -563,8 +560,7 @@ bool anchor_ok(zgml_hip_program* p, uint32_t i) {
 // per-head-slice counters instead of a kernel boundary, and everything the attention can do without them overlaps the
 // projection. Only for the shapes that kernel is built for (short K, Q4_0 with f16 scales, d_head 64 / 128, f32 KV).
 void fuse_qkv_attention(zgml_hip_program* p) {
-    static const bool on = env_flag("ZGML_HIP_FUSE_QKV_ATTN", true);
-    if (!on || p->ctx->fuse_qkv_off || !p->ctx->handoff_flag_dev) return; // (off for good once a hand-off wait has timed out in this context)
+    if (!sw().hip_fuse_qkv_attn || p->ctx->fuse_qkv_off || !p->ctx->handoff_flag_dev) return; // (off for good once a hand-off wait has timed out in this context)
     // Residency: the attention's workgroups spin on counters the projection's workgroups of the SAME grid bump, and HIP
     // promises neither dispatch order nor co-residency. The launch is only built when the whole grid (1024-thread workgroups)
     // fits the device at ONE workgroup per CU — the occupancy query may say two, but it reads one high near a register-file
@@ -579,8 +575,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         const QmvLaunch& L = *qd;
         if (barrier_between_launches(p, i)) continue;
         const bool kon = L.parts[0].w.format == QW_Q4K && L.K > 2048; // the 256-thread form of the launch (qkv_attn_kon_kernel)
-        static const bool kon_on = env_flag("ZGML_HIP_FUSE_QKV_ATTN_KON", true);
-        if (L.n_parts != 3 || (L.K > 2048 && !(kon && kon_on)) || L.pro.kind == QMV_PRO_NONE || (ad->dh != 64 && ad->dh != 128) || L.trace) continue;
+        if (L.n_parts != 3 || (L.K > 2048 && !(kon && sw().hip_fuse_qkv_attn_kon)) || L.pro.kind == QMV_PRO_NONE || (ad->dh != 64 && ad->dh != 128) || L.trace) continue;
         if (kon && L.pro.kind != QMV_PRO_PRENORM) continue; // (an in-kernel rmsnorm prologue runs eight waves: launch_packed_kon)
         const bool kvq = ad->kvq;
         bool ok = true;
@@ -614,8 +609,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
             // workgroups have the lower ids — should fewer be resident than the query says, the attention's workgroups queue behind
             // them instead of spinning beside them (no overlap then, nothing worse); a stranded wait is still bounded and loud.
             const int per_cu = qkv_attn_kon_blocks_per_cu(ad->dh, kvq);
-            static const int eighths = env_int("ZGML_HIP_FUSE_KON_CAP_EIGHTHS", 8); // (experiments)
-            cap = per_cu > 0 ? (uint64_t)per_cu * (uint64_t)std::max(p->ctx->n_cu, 1) * (uint64_t)eighths / 8 : 0;
+            cap = per_cu > 0 ? (uint64_t)per_cu * (uint64_t)std::max(p->ctx->n_cu, 1) * (uint64_t)sw().hip_fuse_kon_cap_eighths / 8 : 0;
         }
         if (n_mv + nh > cap) continue; // not even one attention workgroup per head beside the projection's: two launches
         // (the 256-thread form only with ALL the splits the stand-alone attention would use: with fewer it loses at long contexts —
@@ -631,8 +625,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
             const uint64_t key = ((uint64_t)ad->dh << 40) | ((uint64_t)(kvq ? 1 : 0) << 32) | grid;
             auto it = p->ctx->census.find(key);
             if (it == p->ctx->census.end()) {
-                static const bool census_on = env_flag("ZGML_HIP_FUSE_CENSUS", true);
-                const int r = census_on ? qkv_attn_kon_census(p->ctx->stream, ad->dh, kvq, grid) : -1;
+                const int r = sw().hip_fuse_census ? qkv_attn_kon_census(p->ctx->stream, ad->dh, kvq, grid) : -1;
                 it = p->ctx->census.emplace(key, r).first;
                 if (r == 0) fprintf(stderr, "[zgml_hip] the fused q/k/v + attention launch of %u workgroups is NOT co-resident on this device (census): two launches instead\n", grid);
             }
@@ -644,12 +637,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         // (measured: 93 launches per SmolLM-135M token instead of 123, parity green, and SLOWER — 1714-1734 against 1772 tok/s:
         // this edge is all-to-all (every column group of the projection needs every head), its hand-off costs more than the
         // boundary it replaces. Off unless ZGML_HIP_FUSE_QKV_ATTN_O=1.)
-#ifdef ZGML_TRACE // (diagnostics build only)
-        static const bool with_o = env_flag("ZGML_HIP_FUSE_QKV_ATTN_O", false);
-#else
-        constexpr bool with_o = false;
-#endif
-        bool o_ok = with_o && !kvq && od && od->n_parts == 1 && od->pro.kind == QMV_PRO_NONE && od->K == nh * dh && od->K <= 2048 && !od->trace &&
+        bool o_ok = sw().hip_fuse_qkv_attn_o && !kvq && od && od->n_parts == 1 && od->pro.kind == QMV_PRO_NONE && od->K == nh * dh && od->K <= 2048 && !od->trace &&
                     od->parts[0].w.format == QW_Q4 && od->parts[0].w.scale_f16;
         for (uint32_t r = 0; o_ok && r < nh; r++) {
             const AttnDecodeParams& a = ad->host[r];
@@ -707,8 +695,7 @@ void fuse_attention_o(zgml_hip_program* p) {
     // under 256 workgroups' worth of memory traffic and the all-to-all edge (write-through rows, counter, agent-scope x loads by
     // 256 workgroups) costs more than the boundary it replaces — the round-2 finding for every all-to-all edge, now also with
     // 9.4 MB of prefetch credit on the other side of the scale.
-    static const bool on = env_flag("ZGML_HIP_FUSE_ATTN_O", false);
-    if (!on || p->ctx->fuse_qkv_off || !p->ctx->handoff_flag_dev || p->ctx->opt_fuse_resident_wgs == 0) return;
+    if (!sw().hip_fuse_attn_o || p->ctx->fuse_qkv_off || !p->ctx->handoff_flag_dev || p->ctx->opt_fuse_resident_wgs == 0) return;
     for (size_t i = 0; i + 1 < p->plan.size(); i++) {
         const auto ad = p->plan[i].adec_desc;
         const auto od = p->plan[i + 1].qmv_desc;
@@ -822,9 +809,8 @@ void fuse_ksplit(zgml_hip_program* p) {
     size_t i = 0;
     uint32_t n_fused = 0;
     auto new_trace = [&](const char* what) -> unsigned long long* { // diagnostics build + ZGML_HIP_KS_TRACE=1
-        static const bool want = env_flag("ZGML_HIP_KS_TRACE", false);
         unsigned long long* t = nullptr;
-        if (!want || p->ks_traces.size() >= 24 || !(t = mapped_trace(32))) return nullptr;
+        if (!sw().hip_ks_trace || p->ks_traces.size() >= 24 || !(t = mapped_trace(32))) return nullptr;
         p->ks_traces.push_back({t, what});
         return t;
     };
@@ -872,9 +858,8 @@ void fuse_ksplit(zgml_hip_program* p) {
                 have_pend = false;
                 // ... as ONE launch when the whole grid is resident (the attention's workgroups spin on the projection's: one 768-thread
                 // workgroup per CU is what is counted on; the split count shrinks to fit) and the context's hand-offs have not timed out
-                static const bool fuse_a = env_flag("ZGML_HIP_KSPLIT_FUSE_A", true);
                 bool fused = false;
-                if (fuse_a && !p->ctx->fuse_qkv_off && p->ctx->handoff_flag_dev && ks_layer_a_ok(PL, AL)) {
+                if (sw().hip_ksplit_fuse_a && !p->ctx->fuse_qkv_off && p->ctx->handoff_flag_dev && ks_layer_a_ok(PL, AL)) {
                     const uint32_t nh = A.nh, dh = A.dh;
                     const uint32_t n_kv = (uint32_t)(Q.parts[1].w.N / dh);
                     std::vector<uint32_t> idx(3 * (size_t)nh);
@@ -1001,8 +986,7 @@ void fuse_ksplit(zgml_hip_program* p) {
 // round 4, the x-direct n-on-lanes launches of short-K models (qmv_prenorm_ok: SmolLM-135M's q/k/v and gate/up, whose in-kernel
 // prologue — second vector, sum of squares, barrier — cost 1.1 us of a 2.6 us launch by the stamps).
 void arm_prenorm(zgml_hip_program* p) {
-    static const bool on = env_flag("ZGML_HIP_PRENORM", true);
-    if (!on) return;
+    if (!sw().hip_prenorm) return;
     for (size_t i = 1; i < p->plan.size(); i++) {
         const auto C = p->plan[i].qmv_desc, P = p->plan[i - 1].qmv_desc;
         if (!C || !P || C->pro.kind != QMV_PRO_RMSNORM_MUL) continue;
@@ -1040,8 +1024,7 @@ void arm_prenorm(zgml_hip_program* p) {
 // spent 0.5 us more than the O projection in front of its first load on the second vector).
 void arm_pair(zgml_hip_program* p) {
     // (ZGML_QMV_EPI_SILU=0 asks for the SiLU chain through the generic step interpreter: the pair launch IS a fused SiLU epilogue)
-    static const bool on = env_flag("ZGML_HIP_PAIR", true) && env_flag("ZGML_QMV_EPI_SILU", true);
-    if (!on) return;
+    if (!sw().hip_pair || !sw().qmv_epi_silu) return;
     for (size_t i = 1; i < p->plan.size(); i++) {
         const auto D = p->plan[i].qmv_desc, G = p->plan[i - 1].qmv_desc;
         if (!D || !G || D->pro.kind != QMV_PRO_MUL || !D->pro.store_x || G->n_parts != 2 || G->pair_out) continue;
@@ -1169,10 +1152,9 @@ struct Planner {
 
     // ---- constant repeats (see zgml_hip_program::hoist_op)
     void hoist_constant_repeats() {
-        static const bool hoist_on = env_flag("ZGML_HIP_HOIST_REPEAT", true);
         p->hoist_op.assign(n, 0);
         p->hoist_guard.assign(p->bufs.size(), 0);
-        if (!hoist_on || !p->hoist_ok || !p->barriers.empty()) return;
+        if (!sw().hip_hoist_repeat || !p->hoist_ok || !p->barriers.empty()) return;
         std::vector<uint32_t> writers(p->bufs.size(), 0);
         for (size_t i = 0; i < n; i++) {
             std::vector<uint16_t> seen;
@@ -1426,8 +1408,7 @@ struct Planner {
     // kvq: the same fold over quantised KV caches (extension ops kvq_store / attention_kvq). The fused kernel quantises the new
     // column exactly as storeColumn does and uses the quantised values, so cache bytes and outputs equal the op-by-op plan's.
     void decode_attention(bool kvq) {
-        static const bool on = env_flag("ZGML_HIP_ATTN_DECODE", true), kvq_on = env_flag("ZGML_HIP_ATTN_DECODE_KVQ", true);
-        if (!on || (kvq && !kvq_on)) return;
+        if (!sw().hip_attn_decode || (kvq && !sw().hip_attn_decode_kvq)) return;
         auto aligned4 = [&](uint16_t buf, uint64_t off) { return ((uintptr_t)buf_at(p, buf, off) % 16) == 0; };
         auto rope_ok = [&](int r, uint16_t dst, uint64_t dst_off, uint32_t dh) { // one column of d_head values written to (dst, dst_off)
             if (r < 0 || in_macro[r] || ops[r].kind != ZGML_DOP_ROPE) return false;
@@ -1600,7 +1581,7 @@ struct Planner {
     // ---- [elementwise add ->] rmsnorm [-> elementwise mul] on the same dense rows: one launch instead of three
     // (the M > 1 / prefill form of what the mat-vec prologue does at M = 1; every intermediate is still stored)
     void row_chains() {
-        static const bool enabled = env_flag("ZGML_HIP_ROW_CHAIN", true);
+        const bool enabled = sw().hip_row_chain;
         for (uint32_t i = 0; enabled && i < n; i++) {
             if (!free_op((int)i) || ops[i].kind != ZGML_DOP_RMSNORM) continue;
             const auto& rn = ops[i].u.rmsnorm;
@@ -1659,7 +1640,7 @@ struct Planner {
     // ---- elementwise chains (the SiLU chain and its product with the up projection at M > 1, ...): ops over the same n
     // elements where each consumes its predecessor's output at the same index become one launch
     void elementwise_chains() {
-        static const bool enabled = env_flag("ZGML_HIP_ELT_CHAIN", true);
+        const bool enabled = sw().hip_elt_chain;
         auto is_elt = [&](uint32_t j) { return ops[j].kind == ZGML_DOP_ELEMENTWISE || ops[j].kind == ZGML_DOP_FUSED_ELEMENTWISE; };
         // append op j's steps; `cur` = the chain value's span (nullptr for the first op, which sets src)
         auto append = [&](EltChainParams& c, uint32_t j, const ExactSpan* cur, ExactSpan& out) -> bool {
@@ -1749,7 +1730,6 @@ struct Planner {
 
     // the per-head records of a decode-attention macro, appended to their launch's group (by d_head; int8-KV heads apart)
     void decode_records(const Macro& m, std::map<uint32_t, std::vector<AttnDecodeParams>>& by_dh) {
-        static const bool want_trace = env_flag("ZGML_HIP_ATTN_TRACE", false);
         const auto& kr = ops[m.rk].u.rope;
         bool first_head = true;
         for (const Macro::Head& h : m.heads) {
@@ -1789,7 +1769,7 @@ struct Planner {
             a.k_rot = buf_at(p, kr.dst, kr.dst_off);
             a.dyn_k_off = p->dyn_dev + m.sk, a.dyn_v_off = p->dyn_dev + m.sv; // column indices
             a.owner = first_head ? 1 : 0;
-            if (want_trace && first_head && (a.trace = mapped_trace(8))) p->attn_traces.push_back(a.trace); // one record per launch
+            if (sw().hip_attn_trace && first_head && (a.trace = mapped_trace(8))) p->attn_traces.push_back(a.trace); // one record per launch
             first_head = false;
             by_dh[a.att.d_head | (m.kvq ? 0x10000u : 0u)].push_back(a);
         }
@@ -1879,7 +1859,6 @@ struct Planner {
 
     // mat-vecs of one level that stage the same vector share one launch
     void emit_matvecs(const std::vector<const Macro*>& qmvs) {
-        static const bool want_qmv_trace = env_flag("ZGML_HIP_QMV_TRACE", false);
         std::vector<char> used(qmvs.size(), 0);
         for (size_t i = 0; i < qmvs.size(); i++) {
             if (used[i]) continue;
@@ -1913,7 +1892,7 @@ struct Planner {
                 hi = std::max(hi, c->members.back());
                 n_ops += (uint32_t)c->members.size();
             }
-            if (want_qmv_trace && (L.trace = mapped_trace(16))) // (kind as planned: arm_prenorm / arm_pair may still rewrite it)
+            if (sw().hip_qmv_trace && (L.trace = mapped_trace(16))) // (kind as planned: arm_prenorm / arm_pair may still rewrite it)
                 p->qmv_traces.push_back({L.trace, L.n_parts, L.pro.kind, (uint32_t)w0.K, (uint32_t)w0.N});
             auto desc = std::make_shared<QmvLaunch>(L); // shared with the launch: arm_prenorm may still rewrite it
             Launch QL{ZGML_DOP_QMATMUL, n_ops, lo, hi, [desc](hipStream_t s) { launch_qmatvec_fused(s, *desc); }};
@@ -1990,7 +1969,7 @@ void build_plan(zgml_hip_program* p) {
         for (uint32_t i = 0; i < p->ops.size(); i++) emit_batches(p, {PlanItem{i, -1}});
     }
     p->plan_dirty = false;
-    if (getenv("ZGML_HIP_DEBUG_PLAN")) {
+    if (sw().hip_debug_plan.set) {
         uint64_t by_kind[ZGML_DOP_COUNT] = {0}, ops_by_kind[ZGML_DOP_COUNT] = {0};
         for (const auto& L : p->plan)
             if (L.kind < ZGML_DOP_COUNT) by_kind[L.kind]++, ops_by_kind[L.kind] += L.n_ops;

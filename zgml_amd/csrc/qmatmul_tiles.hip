@@ -1241,12 +1241,8 @@ __global__ void __launch_bounds__(kBlock) qmatmul_raw_kernel(const int8_t* __res
 // Scratch of one M > 1 launch: the pre-split A operand of the second XDL form (split_a_kernel): per
 // 16-row tile and 128-k step 4 * kAPieces KB (4 groups x kAPieces pieces x 64 lanes x 16 B). Launches are serialised on one
 // stream, so one block serves all of a program's quantized matmuls.
-static bool xdl2_enabled() {
-    static const bool on = env_flag("ZGML_QMM_XDL2", true);
-    return on;
-}
 static bool xdl2_applies(const QWeightDev& w, uint32_t M) { // K <= 12288: a wave's weights (<= 12 steps) are preloaded into LDS
-    return M > 1 && w.format == QW_Q4 && w.scale_f16 && xdl2_enabled() && (w.KC + 3) / 4 <= 8 * 12;
+    return M > 1 && w.format == QW_Q4 && w.scale_f16 && sw().qmm_xdl2 && (w.KC + 3) / 4 <= 8 * 12;
 }
 // scratch of an M > 1 launch: [A pieces][split-K partial tiles of the M > 32 form]; the partial region is sized for a
 // grouped launch of kMaxQmmParts weights of this shape (the runtime allocates the maximum over a program's weights, so
@@ -1266,28 +1262,15 @@ static uint64_t xdl4_partial_bytes(const QWeightDev& w, uint32_t M) { // one par
 // M <= 32 (qmatmul_xdl5_kernel): workgroups of the launch = CUs x this; two partial tiles of 8 waves each per workgroup
 constexpr uint32_t kX5Waves = 8;
 static uint32_t xdl5_wgs() {
-    static const int per_cu = std::max(1, env_int("ZGML_QMM_XDL5_WGS_PER_CU", 1));
-    return device_cus() * (uint32_t)per_cu;
-}
-static bool xdl5_enabled() {
-    static const bool on = env_flag("ZGML_QMM_XDL5", true);
-    return on;
+    return device_cus() * (uint32_t)std::max(1, sw().qmm_xdl5_wgs_per_cu);
 }
 static uint64_t xdl5_partial_bytes(uint32_t M) {
-    if (M > 32 || !xdl5_enabled()) return 0;
+    if (M > 32 || !sw().qmm_xdl5) return 0;
     return (uint64_t)xdl5_wgs() * 2 * kX5Waves * (2 * xdl_tile_pad(M) * 256) * sizeof(float);
 }
 // M > 32 (qmatmul_xdl7_kernel, diagnostics build only, opt-in): tile groups x workgroups per group <= max(workgroups of the launch, groups)
-static bool xdl7_enabled() {
-#ifdef ZGML_TRACE
-    static const bool on = env_flag("ZGML_QMM_XDL7", false);
-    return on;
-#else
-    return false;
-#endif
-}
 static uint64_t xdl7_partial_bytes(uint32_t M) {
-    if (M <= 32 || !xdl7_enabled()) return 0;
+    if (M <= 32 || !sw().qmm_xdl7) return 0;
     const uint64_t RT = xdl_tile_pad(M), groups = ((M + 15) / 16 + RT - 1) / RT;
     return std::max<uint64_t>(xdl5_wgs(), groups) * 2 * 8 * (2 * RT * 256) * sizeof(float);
 }
@@ -1307,8 +1290,7 @@ TileFn pick_tile_nt(bool two, bool xvec) {
 template <typename ST, bool Q4>
 TileFn pick_tile(bool two, bool xvec, bool nt) {
 #ifdef ZGML_TRACE // diagnostics build only: ZGML_QMM_XDL=0 keeps the contraction on the f32 MFMA (same results up to rounding order; slower)
-    static const bool xdl = env_flag("ZGML_QMM_XDL", true);
-    if (!xdl) return nt ? pick_tile_nt<ST, Q4, true, false>(two, xvec) : pick_tile_nt<ST, Q4, false, false>(two, xvec);
+    if (!sw().qmm_xdl) return nt ? pick_tile_nt<ST, Q4, true, false>(two, xvec) : pick_tile_nt<ST, Q4, false, false>(two, xvec);
 #endif
     return nt ? pick_tile_nt<ST, Q4, true, true>(two, xvec) : pick_tile_nt<ST, Q4, false, true>(two, xvec);
 }
@@ -1325,12 +1307,6 @@ void launch_xdl2_rg(hipStream_t s, const QMM2Args& a, uint32_t G, dim3 grid, uin
 // read the same rows share one launch (blockIdx.x ranges)
 // M > 32: RT = 4 or 8 m-tiles per workgroup, one scale block-column wide, K split to fill the chip
 void launch_xdl4(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uint32_t n, float* scratch, uint32_t S, uint32_t RT, uint32_t tiles) {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
     QMM4Args a{};
     uint32_t blocks = 0;
     // block-columns per workgroup (kernel template CB): pairing waves on neighbouring block-columns so that the second
@@ -1342,8 +1318,7 @@ void launch_xdl4(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uin
     }
     const uint32_t groups = tiles / RT, KW = kX4Waves / CB;
     // K split: at least one workgroup per CU, at most 4 slices (the scratch regions are sized for 4), whole steps per wave
-    static const int env_sk = env_int("ZGML_QMM_XDL4_SK", 0);
-    uint32_t SK = env_sk > 0 ? (uint32_t)env_sk : cdiv((uint32_t)n_cu, blocks * groups);
+    uint32_t SK = sw().qmm_xdl4_sk > 0 ? (uint32_t)sw().qmm_xdl4_sk : cdiv(device_cus(), blocks * groups);
     SK = std::max(1u, std::min({SK, 4u, cdiv(S, KW)}));
     if ((uint64_t)blocks * groups * sizeof(uint32_t) > kQmmCounterBytes) SK = 1; // one counter word per (tile group, block-column)
     const uint32_t steps_per_slice = cdiv(S, SK);
@@ -1376,11 +1351,9 @@ bool launch_xdl5(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uin
     // narrow outputs stay with qmatmul_xdl2_kernel: every run of a column costs the column's fan-in one more device-scope
     // atomic on one word (measured 2.5 + 0.6 us x runs per column: 12.5 us at 4096 x 4096, 16 runs), and below ~40
     // workgroup-columns (N < 10240) that outweighs the A traffic saved (4096 x 8192: 27.8 against 20.9 us; x 12288: 32.1 against 33.9)
-    static const int min_cols = env_int("ZGML_QMM_XDL5_MIN_COLS", 40);
-    if ((int)wg_cols < min_cols) return false;
-    static const int min_run = std::max(1, env_int("ZGML_QMM_XDL5_MIN_RUN", 2));
+    if ((int)wg_cols < sw().qmm_xdl5_min_cols) return false;
     const uint32_t total = wg_cols * S;
-    const uint32_t run = std::min(S, std::max(cdiv(total, xdl5_wgs()), std::min((uint32_t)min_run, S)));
+    const uint32_t run = std::min(S, std::max(cdiv(total, xdl5_wgs()), std::min((uint32_t)std::max(1, sw().qmm_xdl5_min_run), S)));
     a.ap = (const uint4*)scratch;
     a.partial = (float*)((char*)scratch + xdl_a_bytes(w[0], p[0].M));
     a.counter = (uint32_t*)((char*)scratch - kQmmScratchHead);
@@ -1392,10 +1365,9 @@ bool launch_xdl5(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uin
     const Fn5 fn = RT == 2 ? (nt ? (Fn5)qmatmul_xdl5_kernel<2, kX5Waves, true> : (Fn5)qmatmul_xdl5_kernel<2, kX5Waves, false>)
                            : (nt ? (Fn5)qmatmul_xdl5_kernel<1, kX5Waves, true> : (Fn5)qmatmul_xdl5_kernel<1, kX5Waves, false>);
 #ifdef ZGML_TRACE
-    static const bool tr = env_flag("ZGML_QMM_XDL5_TRACE", false);
     static uint64_t* tbuf = nullptr;
     static uint32_t t_grid, t_cols, t_run, t_units;
-    if (tr) { // every launch stamps into one buffer (graph replays included); the LAST launch's stamps are printed at exit
+    if (sw().qmm_xdl5_trace) { // every launch stamps into one buffer (graph replays included); the LAST launch's stamps are printed at exit
         if (!tbuf) {
             hipHostMalloc((void**)&tbuf, 4096 * 16 * sizeof(uint64_t));
             memset(tbuf, 0, 4096 * 16 * sizeof(uint64_t));
@@ -1441,11 +1413,9 @@ bool launch_xdl7(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uin
     if ((uint64_t)groups * wg_cols * sizeof(uint32_t) > kQmmCounterBytes) return false;
     // narrow outputs: every run of a column costs the fan-in a partial tile of 16 RT KB per wave to write and to read back; below ~40
     // workgroup-columns (N < 10240) there are many runs per column and the K-split kernel wins (as for the M <= 32 form)
-    static const int min_cols = env_int("ZGML_QMM_XDL7_MIN_COLS", 40);
-    if ((int)wg_cols < min_cols) return false;
-    static const int min_run = std::max(1, env_int("ZGML_QMM_XDL7_MIN_RUN", 2));
+    if ((int)wg_cols < sw().qmm_xdl7_min_cols) return false;
     const uint32_t total = wg_cols * S, wgs_g = std::max(1u, xdl5_wgs() / groups);
-    const uint32_t run = std::min(S, std::max(cdiv(total, wgs_g), std::min((uint32_t)min_run, S)));
+    const uint32_t run = std::min(S, std::max(cdiv(total, wgs_g), std::min((uint32_t)std::max(1, sw().qmm_xdl7_min_run), S)));
     a.ap = (const uint4*)scratch;
     a.partial = (float*)((char*)scratch + xdl_a_bytes(w[0], p[0].M));
     a.counter = (uint32_t*)((char*)scratch - kQmmScratchHead);
@@ -1465,20 +1435,19 @@ bool launch_xdl7(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uin
 void launch_xdl2(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uint32_t n, float* scratch) {
     const uint32_t U = w[0].KC, S = cdiv(U, 4), R = xdl_tile_pad(p[0].M), tiles = cdiv(cdiv(p[0].M, 16), R) * R;
     if (!p[0].reuse_split) hipLaunchKernelGGL(split_a_kernel, dim3(S, tiles), dim3(256), 0, s, p[0].input, p[0].M, p[0].K, p[0].in_rs, (uint4*)scratch, S);
-    static const bool xdl4_on = env_flag("ZGML_QMM_XDL4", true);
+    const bool xdl4_on = sw().qmm_xdl4;
 #ifdef ZGML_TRACE
-    if (R >= 4 && xdl7_enabled() && launch_xdl7(s, w, p, n, scratch, S, R, tiles)) return;
+    if (R >= 4 && sw().qmm_xdl7 && launch_xdl7(s, w, p, n, scratch, S, R, tiles)) return;
 #endif
     if (R >= 4 && xdl4_on) {
         launch_xdl4(s, w, p, n, scratch, S, R, tiles);
         return;
     }
-    if (R <= 2 && tiles == R && xdl5_enabled() && launch_xdl5(s, w, p, n, scratch, S, R)) return;
+    if (R <= 2 && tiles == R && sw().qmm_xdl5 && launch_xdl5(s, w, p, n, scratch, S, R)) return;
     // narrow outputs at 17-32 rows: the K-split kernel of the M > 32 form at two m-tiles when it splits K at least two ways with
     // >= 16 steps per slice — a workgroup then pulls half (a quarter) of A instead of all of it and the fan-in has 2-4 arrivals
     // (4096 x 4096: 15.6 -> 14.5 us, 11008 x 4096: 31.8 -> 26.5; 2048 x 2048, one step per wave: 9.9 -> 10.3, hence the floor)
-    static const bool x4_m32 = env_flag("ZGML_QMM_XDL4_M32", true);
-    if (R == 2 && tiles == R && x4_m32 && xdl4_on) {
+    if (R == 2 && tiles == R && sw().qmm_xdl4_m32 && xdl4_on) {
         uint32_t bcs = 0;
         for (uint32_t t = 0; t < n; t++) bcs += p[t].N / 32;
         const uint32_t sk = std::min({cdiv(device_cus(), bcs), 4u, cdiv(S, (uint32_t)kX4Waves)});
@@ -1488,12 +1457,10 @@ void launch_xdl2(hipStream_t s, const QWeightDev* w, const QMatmulParams* p, uin
         }
     }
     const uint32_t R2 = std::min(R, 2u); // (switch off: the M = 32 form over pairs of tiles; the A pieces are laid out per tile)
-    static const int env_g = env_int("ZGML_QMM_XDL2_G", 0);
     uint32_t total_nb2 = 0;
     for (uint32_t t = 0; t < n; t++) total_nb2 += p[t].N / 16;
-    const uint32_t G = env_g ? (uint32_t)env_g : (total_nb2 >= 512 ? 2 : 1);
-    static const int env_w = env_int("ZGML_QMM_WAVES", 8);
-    const uint32_t waves = std::max(std::min<uint32_t>(S, (uint32_t)env_w), cdiv(S, kMaxSpw)), spw_max = cdiv(S, waves); // <= kMaxSpw (xdl2_applies: S <= 96)
+    const uint32_t G = sw().qmm_xdl2_g ? (uint32_t)sw().qmm_xdl2_g : (total_nb2 >= 512 ? 2 : 1);
+    const uint32_t waves = std::max(std::min<uint32_t>(S, (uint32_t)sw().qmm_waves), cdiv(S, kMaxSpw)), spw_max = cdiv(S, waves); // <= kMaxSpw (xdl2_applies: S <= 96)
     // LDS: the waves' weights (spw_max steps x (G KB of nibbles + 256 B of scales) each), reused by the final reduction
     auto b_bytes = [&](uint32_t g) { return (size_t)waves * spw_max * (g * 1024 + 256); };
     uint32_t Gs = G;
@@ -1523,8 +1490,7 @@ void launch_tile(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, boo
     const uint32_t R = two ? 2 : 1, KU = q4 ? 32 : 16;
     QMMArgs a{(const uint4*)w.qs, w.sc, p.input, p.dst, p.M, p.K, q4 ? w.KC : 2 * w.KC, p.in_rs, p.dst_rs, p.N / 16};
     uint32_t waves = cdiv(a.U, 4);
-    static const int env_w = env_int("ZGML_QMM_WAVES", 8);
-    if (waves > (uint32_t)env_w) waves = env_w; // x chunk per step = 16R rows x 4*waves units in LDS
+    if (waves > (uint32_t)sw().qmm_waves) waves = sw().qmm_waves; // x chunk per step = 16R rows x 4*waves units in LDS
     const bool nt = w.stream_nt != 0 && cdiv(p.M, 16 * R) == 1; // several m-tiles re-read the weights: keep them cached
     const TileFn fn = w.scale_f16 ? (q4 ? pick_tile<__half, true>(two, xvec, nt) : pick_tile<__half, false>(two, xvec, nt))
                                   : (q4 ? pick_tile<float, true>(two, xvec, nt) : pick_tile<float, false>(two, xvec, nt));
@@ -1577,8 +1543,7 @@ void launch_qmatmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, 
         return;
     }
     const bool xvec = ((uintptr_t)p.input % 16 == 0) && (p.K % 4 == 0) && (p.M == 1 || p.in_rs % 4 == 0);
-    static const int tile_min_m = env_int("ZGML_QMM_TILE_MIN_M", 2);
-    if (p.M >= (uint32_t)tile_min_m && p.M > 1) {
+    if (p.M >= (uint32_t)sw().qmm_tile_min_m && p.M > 1) {
         launch_tile(s, w, p, xvec, scratch);
         return;
     }

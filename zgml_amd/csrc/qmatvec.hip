@@ -1539,9 +1539,7 @@ bool qweight_packable(uint64_t K, uint64_t N, uint64_t bs) {
 // at least (every workgroup stores a 16-element slice of the absorbed ops' outputs).
 bool qmv_prenorm_ok(const QWeightDev& w, uint32_t K, uint64_t total_cols, uint32_t M) {
     if (w.format == QW_Q4K) return true;
-    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
-    static const bool nol = env_flag("ZGML_HIP_PRENORM_NOL", true);
-    return nol && xd_enabled && w.format == QW_Q4 && w.scale_f16 && !w.stream_nt && M == 1 && K % 16 == 0 && K <= 4096 && total_cols >= K; // (<= 256 partial sums)
+    return sw().hip_prenorm_nol && sw().qmv_xdirect && w.format == QW_Q4 && w.scale_f16 && !w.stream_nt && M == 1 && K % 16 == 0 && K <= 4096 && total_cols >= K; // (<= 256 partial sums)
 }
 
 // Can the gate / up launch over two weights shaped like `w` run as a PAIR launch (one workgroup computes the same 16 columns of both
@@ -1549,9 +1547,7 @@ bool qmv_prenorm_ok(const QWeightDev& w, uint32_t K, uint64_t total_cols, uint32
 // default cache policy (ZGML_HIP_PAIR_NOL=0 keeps those as a grouped launch + the down projection's MUL prologue).
 bool qmv_pair_ok(const QWeightDev& w) {
     if (w.format == QW_Q4K) return true;
-    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
-    static const bool nol = env_flag("ZGML_HIP_PAIR_NOL", true);
-    return nol && xd_enabled && w.format == QW_Q4 && w.scale_f16 && !w.stream_nt;
+    return sw().hip_pair_nol && sw().qmv_xdirect && w.format == QW_Q4 && w.scale_f16 && !w.stream_nt;
 }
 
 bool qmv_can_group(const QWeightDev& a, const QWeightDev& b) {
@@ -1570,14 +1566,11 @@ namespace {
 // wave per 4 units (one load step each, up to 16 waves) shortens it: SmolLM-135M decode +3.8 %
 // (ZGML_QMV_WAVES_SMALLK sweep: 4 -> 1414, 5 -> 1400, 6 -> 1450, 8 -> 1445, 12+ -> 1470 tok/s);
 // for K = 4096 more waves lose in the stream (Llama-2-7B: 8 waves -18 %).
-uint32_t qmv_waves(const QWeightDev& w, uint32_t total_blocks = 0) {
-    (void)total_blocks;
+uint32_t qmv_waves(const QWeightDev& w) {
     const uint32_t U = w.format == QW_Q4 ? w.KC : 2 * w.KC;
     uint32_t waves = cdiv(U, 4);
-    static const int small_cap = env_int("ZGML_QMV_WAVES_SMALLK", 16);
-    uint32_t cap = w.K > 6144 ? 8 : (w.K <= 2048 ? (uint32_t)small_cap : 4); // short K: the launch is one latency chain, more waves shorten it
-    static const int env_cap = env_int("ZGML_QMV_WAVES", 0);
-    if (env_cap > 0) cap = (uint32_t)env_cap;
+    uint32_t cap = w.K > 6144 ? 8 : (w.K <= 2048 ? (uint32_t)sw().qmv_waves_smallk : 4); // short K: the launch is one latency chain, more waves shorten it
+    if (sw().qmv_waves > 0) cap = (uint32_t)sw().qmv_waves;
     if (waves > cap) waves = cap;
     return waves < 1 ? 1 : waves;
 }
@@ -1616,32 +1609,29 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
                    uint32_t extra_blocks = 0, uint32_t d_head = 0, const FusedO* fo = nullptr);
 // the leading arguments of a single-matrix, prologue-free, x-direct launch with one load step (what the fused O projection
 // needs); false: not that shape
+// the leading "flags" word of a mat-vec launch: part 0's column groups, the waves, the parts, and what the kernel's head may assume
+static uint32_t head_flags(const QMVArgs& a, uint32_t waves, bool contig, bool rmsnorm, bool late) {
+    return a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (contig ? 1u << 28 : 0u) | (rmsnorm ? 1u << 29 : 0u) | (a.x_vec ? 1u << 30 : 0u) | (late ? 1u << 31 : 0u);
+}
 static bool plain_head_depth1(const QMVArgs& a, const QWeightDev& w0, uint32_t blocks, QmvHead& h) {
-    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
-    if (!xd_enabled || a.n_parts != 1 || a.pro.kind != QMV_PRO_NONE || w0.format != QW_Q4 || !w0.scale_f16 || w0.stream_nt) return false;
-    const uint32_t waves = qmv_waves(w0, blocks);
+    if (!sw().qmv_xdirect || a.n_parts != 1 || a.pro.kind != QMV_PRO_NONE || w0.format != QW_Q4 || !w0.scale_f16 || w0.stream_nt) return false;
+    const uint32_t waves = qmv_waves(w0);
     if (cdiv(a.U, waves * 4) != 1 || a.parts[0].NB2 >= (1u << 20)) return false;
     h = QmvHead{a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b, a.in_rs, a.K,
-                a.parts[0].NB2 | ((waves - 1) << 20) | (1u << 24) | (a.x_vec ? 1u << 30 : 0u), 0u};
+                head_flags(a, waves, false, false, false), 0u};
     return true;
 }
 
-static bool prenorm_late() { // experiments: ZGML_HIP_PRENORM_EARLY=0 folds the prepared norm's partial sums in the kernel's tail (bit 31 of the head flags)
-    static const bool late = env_int("ZGML_HIP_PRENORM_EARLY", 1) == 0;
-    return late;
-}
 // ── the K-on-lanes launches (QW_Q4K) ──
 // Waves: 8 for K >= 4096 (4096: one load group of 4 items per lane, every load of the workgroup in flight at once;
 // tools/exp/kon.hip sweep, round 3: 4096^2 chain 4.06 us with 8 waves against 4.9 / 4.5 with 4 / 16); short K: one wave per
 // 64 k-pairs up to the cap (the launch is one latency chain inside the decode stream, as for the form above).
 uint32_t kon_waves(const QWeightDev& w) {
     const uint32_t wave_steps = cdiv((w.K + 1) / 2, 64);
-    static const int small_cap = env_int("ZGML_QMV_KON_WAVES_SMALLK", 16);
     // (in-decode sweep per launch shape, Llama-2-7B, tools/tune_kon.sh: 4 waves for q/k/v, o, gate/up and the LM head, 8 for
     // the down projection's K = 11008: 765 tok/s with 8 everywhere, 792 with 4, 807 with this rule)
-    static const int big_env = env_int("ZGML_QMV_KON_WAVES", 0);
-    const int big_cap = big_env > 0 ? big_env : (w.K > 6144 ? 8 : 4);
-    const uint32_t cap = (uint32_t)std::max(1, std::min(16, w.K <= 2048 ? small_cap : big_cap));
+    const int big_cap = sw().qmv_kon_waves > 0 ? sw().qmv_kon_waves : (w.K > 6144 ? 8 : 4);
+    const uint32_t cap = (uint32_t)std::max(1, std::min(16, w.K <= 2048 ? sw().qmv_kon_waves_smallk : big_cap));
     return std::max(1u, std::min(wave_steps, cap));
 }
 
@@ -1676,8 +1666,7 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
     uint32_t waves = kon_waves(w0);
     int tune_depth = 0; // 0: by the step count
     { // experiments: ZGML_QMV_KON_TUNE="<blocks>x<K>:<waves>,..." overrides the wave count of the launches of that grid and K
-        static const char* tune = getenv("ZGML_QMV_KON_TUNE");
-        for (const char* q = tune; q && *q;) {
+        for (const char* q = sw().qmv_kon_tune; q && *q;) {
             unsigned b = 0, k = 0, wv = 0, dp = 0;
             const int got = sscanf(q, "%ux%u:%u:%u", &b, &k, &wv, &dp);
             if (got >= 3 && b == total_blocks && k == a.K && wv >= 1 && wv <= 16) {
@@ -1688,8 +1677,7 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
             if (q) q++;
         }
     }
-    static const bool contig_ok = env_flag("ZGML_QMV_CONTIG", true);
-    bool contig = a.n_parts > 1 && a.n_parts <= 3 && contig_ok;
+    bool contig = a.n_parts > 1 && a.n_parts <= 3 && sw().qmv_contig;
     for (uint32_t t = 1; t < a.n_parts && contig; t++) {
         const QMVPartDev &pv = a.parts[t - 1], &pt = a.parts[t];
         contig = (const char*)pt.qs == (const char*)pv.qs + (size_t)pv.NB2 * P * 16 && (const char*)pt.sc == (const char*)pv.sc + (size_t)(pv.NB2 / 2) * P * 4 &&
@@ -1716,8 +1704,7 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
     // the kernel's leading arguments: PRENORM streams the producer's vector and keeps the original one for the side outputs
     const float* const head_xa = prom == 2 ? a.pro.xg : a.pro.a;
     const float* const head_xb = prom == 2 ? a.pro.a : a.pro.b;
-    const uint32_t flags = a.parts[0].NB2 | ((waves_used - 1) << 20) | (a.n_parts << 24) | (contig ? 1u << 28 : 0u) | (a.pro.kind == QMV_PRO_RMSNORM_MUL ? 1u << 29 : 0u) |
-                           (a.x_vec ? 1u << 30 : 0u) | (prenorm_late() ? 1u << 31 : 0u);
+    const uint32_t flags = head_flags(a, waves_used, contig, a.pro.kind == QMV_PRO_RMSNORM_MUL, sw().hip_prenorm_early == 0);
     if (fused) { // q / k / v + decode attention in one launch of 256-thread workgroups (qkv_attn_kon_kernel)
         using FusedFn = void (*)(const uint4*, const void*, float*, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, QMVArgs, QkvAttnArgs);
         if (!grp || !contig || !xvec || prom == 1 || (d_head != 64 && d_head != 128)) return false;
@@ -1764,12 +1751,8 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
 
 bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t total_blocks, uint32_t M, bool xvec, const QkvAttnArgs* fused,
                    uint32_t extra_blocks, uint32_t d_head, const FusedO* fo) {
-#ifdef ZGML_TRACE
-    { // diagnostics build only: leave out every mat-vec launch of one grid size (wrong results; the token time then drops by that launch's true cost)
-        static const uint32_t skip_blocks = (uint32_t)env_int("ZGML_HIP_DEBUG_SKIP_GRID", 0);
-        if (skip_blocks && total_blocks == skip_blocks) return true;
-    }
-#endif
+    // diagnostics build only: leave out every mat-vec launch of one grid size (wrong results; the token time then drops by that launch's true cost)
+    if (sw().hip_debug_skip_grid && total_blocks == (uint32_t)sw().hip_debug_skip_grid) return true;
     if (w0.format == QW_Q4K) { // (only weights whose every use is an M = 1 mat-vec get this layout: compile_program)
         if (M != 1) return false;
         return launch_packed_kon(s, a, w0, total_blocks, xvec, fused, extra_blocks, d_head, fo);
@@ -1777,23 +1760,19 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
     const bool q4 = w0.format == QW_Q4;
     a.x_vec = xvec ? 1 : 0;
     // x direct (no LDS staging); the rmsnorm prologue reduces the vector while the weights fly
-    static const bool xd_enabled = env_flag("ZGML_QMV_XDIRECT", true);
-    static const bool xd_norm = env_flag("ZGML_QMV_XDIRECT_NORM", true);
     // (measured: with the rmsnorm prologue the extra per-lane dword loads of x and gamma cost more than the
     // LDS round trip they replace once K is large: Llama-2-7B -5 %, SmolLM-135M +2.7 %)
-    static const uint32_t xd_norm_max_k = (uint32_t)env_int("ZGML_QMV_XDNORM_MAXK", 2048);
-    const bool xd = xd_enabled && (a.pro.kind != QMV_PRO_RMSNORM_MUL || (xd_norm && a.K <= xd_norm_max_k));
+    const bool xd = sw().qmv_xdirect && (a.pro.kind != QMV_PRO_RMSNORM_MUL || (sw().qmv_xdirect_norm && a.K <= (uint32_t)sw().qmv_xdnorm_maxk));
     const bool prenorm = a.pro.kind == QMV_PRO_PRENORM;
     if (prenorm && (!qmv_prenorm_ok(w0, a.K, total_blocks * 16, M) || a.pro.ssq != a.pro.xg + a.K)) { // (arm_prenorm asks the same question and lays the partial sums right behind the vector: never reached)
         fprintf(stderr, "[zgml_hip] ERROR: a PRENORM mat-vec launch outside the shapes its kernel is built for: not launched\n");
         return false;
     }
-    uint32_t waves = qmv_waves(w0, total_blocks);
+    uint32_t waves = qmv_waves(w0);
     if (!xd && a.pro.kind != QMV_PRO_NONE) // a staged prologue keeps all of x in the register window: 16 floats per thread
         while (waves < (uint32_t)kMaxWaves && waves * 64 * 4 * kXRegs < a.K) waves++;
     // parts back to back in the weight arenas (and <= 4 of them): the kernel needs no argument-block fetch to find them
-    static const bool contig_ok = env_flag("ZGML_QMV_CONTIG", true);
-    bool contig = a.n_parts > 1 && a.n_parts <= 3 && contig_ok;
+    bool contig = a.n_parts > 1 && a.n_parts <= 3 && sw().qmv_contig;
     const size_t sc_elem = (q4 ? 2 : 1) * (w0.scale_f16 ? 2 : 4);
     for (uint32_t t = 1; t < a.n_parts && contig; t++) {
         const QMVPartDev &pv = a.parts[t - 1], &pt = a.parts[t];
@@ -1810,6 +1789,7 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
     // the kernel's leading arguments: PRENORM streams the producer's vector and keeps the original one for the side outputs
     const float* const head_xa = prenorm ? a.pro.xg : a.pro.a;
     const float* const head_xb = prenorm ? a.pro.a : a.pro.b;
+    const bool rmsnorm = a.pro.kind == QMV_PRO_RMSNORM_MUL, late = sw().hip_prenorm_early == 0; // (late, experiments: the prepared norm's partial sums are folded in the kernel's tail)
     const KernelFn fn = prenorm ? (grp ? (depth_sel == 0 ? qmatvec_prenorm_kernel<1, true> : depth_sel == 1 ? qmatvec_prenorm_kernel<2, true> : qmatvec_prenorm_kernel<4, true>)
                                        : (depth_sel == 0 ? qmatvec_prenorm_kernel<1, false> : depth_sel == 1 ? qmatvec_prenorm_kernel<2, false> : qmatvec_prenorm_kernel<4, false>))
                       : w0.scale_f16 ? pick_kernel<__half>(xvec, q4, pro, grp, depth_sel, xd, nt)
@@ -1828,7 +1808,7 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
                                     : (depth_sel == 0 ? qmatvec_pair_kernel<1, 0> : depth_sel == 1 ? qmatvec_pair_kernel<2, 0> : qmatvec_pair_kernel<4, 0>);
         const size_t lds2 = ((size_t)(2 * kMaxWaves + 1) * 16) * sizeof(float);
         hipLaunchKernelGGL(pf, dim3(a.parts[0].NB2), dim3(waves * 64), lds2, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, head_xa, head_xb, a.in_rs, a.K,
-                           a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (1u << 28) | (a.x_vec ? 1u << 30 : 0u) | (prenorm_late() ? 1u << 31 : 0u), nb2_12, a);
+                           head_flags(a, waves, true, false, late), nb2_12, a);
         return true;
     }
     if (fused) {
@@ -1842,12 +1822,10 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
             const dim3 grid3(total_blocks + extra_blocks + fo->blocks2);
             if (d_head == 64)
                 hipLaunchKernelGGL((qkv_attn_o_kernel<__half, true, 16>), grid3, dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b,
-                                   a.in_rs, a.K, a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (1u << 28) | (a.pro.kind == QMV_PRO_RMSNORM_MUL ? 1u << 29 : 0u) | (a.x_vec ? 1u << 30 : 0u),
-                                   nb2_12, a, g, fo->a2);
+                                   a.in_rs, a.K, head_flags(a, waves, true, rmsnorm, false), nb2_12, a, g, fo->a2);
             else
                 hipLaunchKernelGGL((qkv_attn_o_kernel<__half, true, 32>), grid3, dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b,
-                                   a.in_rs, a.K, a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (1u << 28) | (a.pro.kind == QMV_PRO_RMSNORM_MUL ? 1u << 29 : 0u) | (a.x_vec ? 1u << 30 : 0u),
-                                   nb2_12, a, g, fo->a2);
+                                   a.in_rs, a.K, head_flags(a, waves, true, rmsnorm, false), nb2_12, a, g, fo->a2);
             return true;
         }
 #endif
@@ -1862,15 +1840,11 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
             ff = prenorm ? (fused_kvq ? qkv_attn_kernel<__half, true, 32, true, 2> : qkv_attn_kernel<__half, true, 32, false, 2>)
                          : (fused_kvq ? qkv_attn_kernel<__half, true, 32, true> : qkv_attn_kernel<__half, true, 32, false>);
         hipLaunchKernelGGL(ff, dim3(total_blocks + extra_blocks), dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, head_xa, head_xb, a.in_rs, a.K,
-                           a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (1u << 28) | (a.pro.kind == QMV_PRO_RMSNORM_MUL ? 1u << 29 : 0u) |
-                               (a.x_vec ? 1u << 30 : 0u) | (prenorm_late() ? 1u << 31 : 0u),
-                           nb2_12, a, f);
+                           head_flags(a, waves, true, rmsnorm, late), nb2_12, a, f);
         return true;
     }
     hipLaunchKernelGGL(fn, grid, dim3(waves * 64), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, head_xa, head_xb, a.in_rs, a.K,
-                       a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (contig ? 1u << 28 : 0u) | (a.pro.kind == QMV_PRO_RMSNORM_MUL ? 1u << 29 : 0u) |
-                           (a.x_vec ? 1u << 30 : 0u) | (prenorm_late() ? 1u << 31 : 0u),
-                       nb2_12, a);
+                       head_flags(a, waves, contig, rmsnorm, late), nb2_12, a);
     return true;
 }
 
@@ -1919,11 +1893,10 @@ static void build_qmv_args(const QmvLaunch& L, QMVArgs& a, uint32_t& blocks, boo
             const bool silu = pt.n_epi == 5 && st[0].op == ZGML_OP_NEG && !st[0].store && st[1].op == ZGML_OP_EXP && st[1].store &&
                               st[2].op == ZGML_OP_ADD && st[2].operand && st[2].operand != pt.dst && st[2].operand != st[1].store && !st[2].store &&
                               st[3].op == ZGML_OP_RECIP && !st[3].store && st[4].op == ZGML_OP_MUL && st[4].operand == pt.dst && st[4].store;
-            static const bool silu_on = env_flag("ZGML_QMV_EPI_SILU", true);
             const bool residual = pt.n_epi == 1 && st[0].op == ZGML_OP_ADD && st[0].operand && st[0].operand != pt.dst && st[0].store;
             const bool mulvec = pt.n_epi == 1 && st[0].op == ZGML_OP_MUL && st[0].operand && st[0].operand != pt.dst && st[0].store;
             // (the switch is about the SiLU chain only: the residual form also carries the next launch's rmsnorm, arm_prenorm)
-            d.epi_kind = silu ? (silu_on ? kEpiSilu : kEpiGeneric) : (residual ? kEpiResidual : (mulvec ? kEpiMulVec : kEpiGeneric));
+            d.epi_kind = silu ? (sw().qmv_epi_silu ? kEpiSilu : kEpiGeneric) : (residual ? kEpiResidual : (mulvec ? kEpiMulVec : kEpiGeneric));
         }
         blocks += d.NB2;
     }
@@ -1963,14 +1936,8 @@ bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodePar
     f.n_sp = sp.splits ? sp.splits : 1;
     uint32_t shift = 0;
     while ((16u << shift) < d_head) shift++;
-#ifdef ZGML_TRACE // diagnostics build only (tests/handoff_timeout_worker.py loads libzgml_hip_trace.so): one column group never signals
-    static const bool drop_publish = env_flag("ZGML_HIP_DEBUG_DROP_PUBLISH", false);
-#else
-    constexpr bool drop_publish = false;
-#endif
-    f.pub = QmvPublish{counters, {0, n_heads, n_heads + n_kv}, shift, drop_publish ? 1u : 0u};
-    static const uint32_t poll_sleep = (uint32_t)env_int("ZGML_HIP_HANDOFF_SLEEP", 2);
-    f.ho = DecodeHandoff{counters, seen, idx, n_heads, d_head / 16, timeout, poll_sleep, nullptr};
+    f.pub = QmvPublish{counters, {0, n_heads, n_heads + n_kv}, shift, sw().hip_debug_drop_publish ? 1u : 0u}; // (diagnostics build, tests/handoff_timeout_worker.py: one column group never signals)
+    f.ho = DecodeHandoff{counters, seen, idx, n_heads, d_head / 16, timeout, (uint32_t)sw().hip_handoff_sleep, nullptr};
 #ifdef ZGML_TRACE
     if (Lo) { // the O projection rides along (diagnostics build only)
         FusedO fo;
@@ -2053,9 +2020,7 @@ bool launch_attention_o(hipStream_t s, const AttnDecodeParams* dev_params, uint3
     f.n_sp = sp.splits ? sp.splits : 1;
     f.n_attn = n_heads * f.n_sp;
     f.ho = DecodeHandoff{nullptr, nullptr, nullptr, n_heads, d_head / 16, timeout, 2u, out_cnt};
-    static const uint32_t poll_sleep = (uint32_t)env_int("ZGML_HIP_ATTN_O_POLL", 10);
-    static const uint32_t pre_sleep = (uint32_t)env_int("ZGML_HIP_ATTN_O_PRESLEEP", 0);
-    f.wt = QmvWait{out_cnt, o_seen, n_heads, timeout, poll_sleep, pre_sleep};
+    f.wt = QmvWait{out_cnt, o_seen, n_heads, timeout, (uint32_t)sw().hip_attn_o_poll, (uint32_t)sw().hip_attn_o_presleep};
     const uint32_t flags = a.parts[0].NB2 | ((waves - 1) << 20) | (1u << 24) | (1u << 30);
     const size_t lds = ((size_t)kMaxWaves * 16 + kMaxWaves) * sizeof(float);
     using Fn = void (*)(const uint4*, const void*, float*, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, QMVArgs, AttnOArgs);

@@ -158,15 +158,5 @@ inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b
 
 constexpr size_t kMaxLds = 160 * 1024;
 
-inline uint32_t device_cus() {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-    }
-    return (uint32_t)n_cu;
-}
-
 } // namespace
 } // namespace zgml

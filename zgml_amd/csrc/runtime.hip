@@ -197,7 +197,7 @@ namespace zgml_rt {
 // histogram of every graph the runtime instantiates (how the rocprofv3 crash inside hipGraphLaunch of the per-token
 // graph was narrowed down: DESIGN.md section 5).
 void dump_graph(hipGraph_t g, const char* tag) {
-    const char* dir = getenv("ZGML_HIP_GRAPH_DUMP");
+    const char* dir = sw().hip_graph_dump;
     if (!dir || !g) return;
     size_t n = 0;
     if (hipGraphGetNodes(g, nullptr, &n) != hipSuccess) return;
@@ -413,16 +413,15 @@ void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count) {
 #ifdef ZGML_TRACE
     // diagnostics build only: ZGML_HIP_SKIP_KINDS=<bitmask of DeviceOp tags> drops those launches (timing ablation
     // only; results are garbage)
-    static const unsigned skip = getenv("ZGML_HIP_SKIP_KINDS") ? (unsigned)strtoul(getenv("ZGML_HIP_SKIP_KINDS"), nullptr, 0) : 0u;
     // ZGML_HIP_SKIP_MOD="<period>:<bitmask>" drops launch i >= 1 when bit ((i-1) % period) is set
     static unsigned mod_period = 0, mod_mask = 0;
     static bool mod_init = false;
     if (!mod_init) {
         mod_init = true;
-        if (const char* e = getenv("ZGML_HIP_SKIP_MOD")) sscanf(e, "%u:%x", &mod_period, &mod_mask);
+        if (const char* e = sw().hip_skip_mod) sscanf(e, "%u:%x", &mod_period, &mod_mask);
     }
     for (size_t i = first; i < first + count && i < p->plan.size(); i++) {
-        if (skip & (1u << p->plan[i].kind)) continue;
+        if (sw().hip_skip_kinds & (1u << p->plan[i].kind)) continue;
         if (mod_period && i >= 1 && (mod_mask & (1u << ((i - 1) % mod_period)))) continue;
         p->plan[i].run(s);
     }
@@ -462,7 +461,7 @@ void enqueue(zgml_hip_program* p) {
         }
         hipEventDestroy(e0);
         hipEventDestroy(e1);
-        if (getenv("ZGML_HIP_DEBUG_PLAN") && atoi(getenv("ZGML_HIP_DEBUG_PLAN")) >= 2 && p->plan[0].prof_calls == 8) {
+        if (sw().hip_debug_plan.value >= 2 && p->plan[0].prof_calls == 8) {
             // per-launch table after 8 profiled executions (first 40 launches: one layer and a bit)
             for (size_t i = 0; i < p->plan.size() && i < 40; i++)
                 fprintf(stderr, "[zgml_hip] launch %3zu kind %2u ops %4u [%u..%u]  %.2f us\n", i, p->plan[i].kind, p->plan[i].n_ops,
@@ -474,7 +473,7 @@ void enqueue(zgml_hip_program* p) {
         if (!p->graph_exec) {
             // two graphs (zgml_hip_program::graph_tail): the head holds the first sixth of the launches (at least 8: its device
             // time has to cover the host's submission of the tail), short plans stay one graph
-            static const int split_env = env_int("ZGML_HIP_GRAPH_SPLIT", -1);
+            const int split_env = sw().hip_graph_split;
             size_t head = p->plan.size() >= 48 ? std::max<size_t>(8, p->plan.size() / 6) : p->plan.size();
             if (split_env == 0) head = p->plan.size();
             if (split_env > 0) head = std::min<size_t>((size_t)split_env, p->plan.size());
@@ -610,11 +609,7 @@ zgml_hip_ctx* zgml_hip_create(int device_ordinal) {
     zgml_hip_ctx* ctx = new zgml_hip_ctx();
     ctx->device = device_ordinal;
     // environment overrides of the option defaults (profilers: ZGML_HIP_GRAPH=0 traces eager launches)
-    if (const char* e = getenv("ZGML_HIP_GRAPH")) ctx->opt_graph = atoi(e) != 0;
-    if (const char* e = getenv("ZGML_HIP_FUSION")) ctx->opt_fusion = atoi(e) != 0;
-    if (const char* e = getenv("ZGML_HIP_KSPLIT")) ctx->opt_ksplit = atoi(e) != 0;
-    if (const char* e = getenv("ZGML_HIP_W8A8")) ctx->opt_w8a8 = atoi(e) != 0;
-    if (const char* e = getenv("ZGML_HIP_HOST_PROF")) ctx->host_prof = atoi(e) != 0;
+    read_ctx_switches(*ctx);
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         g_create_error = "hipStreamCreate failed";
         delete ctx;
@@ -936,8 +931,7 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     uint64_t qs_total = 0, sc_total = 0;
     // Q4_0-valued weights with f16 scales that only ever feed M = 1 mat-vecs take the K-on-lanes layout (QW_Q4K, qmatvec.hip);
     // a weight an M > 1 matmul reads keeps the n-on-lanes layout the tile kernels are built for
-    static const bool kon_on = env_flag("ZGML_HIP_QMV_KON", true);
-    std::vector<char> qw_m1(prog->n_qweights, kon_on ? 1 : 0);
+    std::vector<char> qw_m1(prog->n_qweights, sw().hip_qmv_kon ? 1 : 0);
     std::vector<char> qw_m1_all(prog->n_qweights, 1); // every use is a dense M = 1 row (the W8A8 arm's condition, reference.zig:512-516)
     for (const auto& op : p->ops)
         if (op.kind == ZGML_DOP_QMATMUL && op.u.qmatmul.weight_idx < prog->n_qweights) {
@@ -988,15 +982,13 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
         // (short K stays n-on-lanes: those launches are one latency chain inside the decode stream, where the longer fold of
         // the K-on-lanes tail and the hand-over of the norm cost more than the cheaper inner loop saves: SmolLM-135M
         // 1770 tok/s either way without the hand-over, 1680 with it)
-        static const uint32_t kon_min_k = (uint32_t)env_int("ZGML_HIP_QMV_KON_MIN_K", 2049);
-        if (w.format == QW_Q4 && w.scale_f16 && qw_m1[i] && w.K >= kon_min_k) w.format = QW_Q4K;
+        if (w.format == QW_Q4 && w.scale_f16 && qw_m1[i] && w.K >= (uint32_t)sw().hip_qmv_kon_min_k) w.format = QW_Q4K;
         w.KC = (uint32_t)((qw.rows + 31) / 32);
         packed_bytes(w.format, w.scale_f16, w.K, w.N, &w.qs_bytes, &w.sc_bytes);
         qs_total += w.qs_bytes, sc_total += w.sc_bytes;
     }
     char *qs_arena = nullptr, *sc_arena = nullptr;
-    static const bool use_arena = env_flag("ZGML_HIP_WEIGHT_ARENA", true);
-    if (ok && qs_total && use_arena) {
+    if (ok && qs_total && sw().hip_weight_arena) {
         ok = CTX_CHECK(ctx, hipMalloc((void**)&qs_arena, qs_total)) && CTX_CHECK(ctx, hipMalloc((void**)&sc_arena, sc_total ? sc_total : 16));
         if (qs_arena) p->owned.push_back(qs_arena);
         if (sc_arena) p->owned.push_back(sc_arena);
@@ -1005,7 +997,7 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     for (uint64_t i = 0; i < prog->n_qweights; i++) {
         QWeightDev& w = p->qweights[i];
         if (ok && pending[i].raw_a) {
-            if (use_arena) {
+            if (sw().hip_weight_arena) {
                 w.qs = qs_arena + qs_off, w.sc = sc_arena + sc_off;
                 qs_off += w.qs_bytes, sc_off += w.sc_bytes;
             } else { // experiment: one allocation per weight
@@ -1029,10 +1021,9 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     }
     if (flags) hipFree(flags);
     { // weight sets beyond the 256 MB Infinity Cache are streamed with non-temporal loads (see qmatvec.hip: wload)
-        static const uint64_t nt_min = getenv("ZGML_HIP_NT_MIN_BYTES") ? strtoull(getenv("ZGML_HIP_NT_MIN_BYTES"), nullptr, 0) : (192ull << 20);
         uint64_t total = 0;
         for (const QWeightDev& w : p->qweights) total += w.qs_bytes + w.sc_bytes;
-        if (total >= nt_min)
+        if (total >= sw().hip_nt_min_bytes)
             for (QWeightDev& w : p->qweights) w.stream_nt = 1;
     }
 
@@ -1240,8 +1231,7 @@ static bool download_outputs(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
 // inputs or outputs, profiling) — the caller takes the general path.
 static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_program_io* inputs, uint64_t n_inputs,
                              const zgml_program_io* outputs, uint64_t n_outputs, uint64_t t0) {
-    static const bool enabled = env_flag("ZGML_HIP_IO_GRAPH", true);
-    if (!enabled || !ctx->opt_graph || ctx->opt_profile || !n_inputs || !n_outputs || !p->in_plan.word_aligned || !p->out_plan.word_aligned ||
+    if (!sw().hip_io_graph || !ctx->opt_graph || ctx->opt_profile || !n_inputs || !n_outputs || !p->in_plan.word_aligned || !p->out_plan.word_aligned ||
         !p->in_plan.dyn_row || !p->in_plan.table_dev || !p->out_plan.table_dev)
         return false;
     if (p->plan_dirty || p->fuse_epoch != ctx->fuse_epoch) {
@@ -1768,7 +1758,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     // measured SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every workgroup writes the
     // position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838 against 842;
     // profiles/r05_token_tail_ab.txt)
-    static const bool tail_fused = env_flag("ZGML_HIP_TAIL_FUSED", false);
+    const bool tail_fused = sw().hip_tail_fused;
     auto one_token = [&](hipStream_t st) {
         if (!tail_fused) launch_resident_prep(st, a, total);
         // [prep] [plan] [argmax stage 1] [stage 2 + advance]; or, opt-in, [plan] [token tail]: the argmax of the logits, the advance
@@ -1803,7 +1793,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     }
     // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
     // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
-    static const uint32_t per_graph = (uint32_t)env_int("ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH", 1);
+    const uint32_t per_graph = (uint32_t)sw().hip_resident_tokens_per_graph;
     if (ctx->opt_graph && r->graph_exec && per_graph > 1 && n_steps >= per_graph && !r->graph_multi_exec) {
         hipGraph_t g = nullptr;
         if (CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) {

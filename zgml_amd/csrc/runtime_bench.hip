@@ -6,8 +6,7 @@
 extern "C" {
 
 static bool make_synth_weight(zgml_hip_ctx* ctx, uint32_t K, uint32_t N, int q4, uint32_t id, QWeightDev* w, uint32_t M = 1) {
-    static const bool kon_on = env_flag("ZGML_HIP_QMV_KON", true);
-    w->format = q4 ? (M == 1 && kon_on ? QW_Q4K : QW_Q4) : QW_Q8; // (what compile_program picks for a weight that only feeds mat-vecs)
+    w->format = q4 ? (M == 1 && sw().hip_qmv_kon ? QW_Q4K : QW_Q4) : QW_Q8; // (what compile_program picks for a weight that only feeds mat-vecs)
     w->K = K, w->N = N, w->bs = 32;
     w->KC = (K + 31) / 32;
     w->scale_f16 = 1;
@@ -180,7 +179,7 @@ double zgml_hip_qmatvec_chain_bench(zgml_hip_ctx* ctx, uint32_t K, int q4, uint3
     if (ok) {
         // ZGML_HIP_QMV_TRACE=1 (trace build of the library): in-kernel stamps of ONE launch in the middle of the chain, printed below
         unsigned long long* trace = nullptr;
-        if (getenv("ZGML_HIP_QMV_TRACE") && atoi(getenv("ZGML_HIP_QMV_TRACE")) &&
+        if (sw().hip_qmv_trace &&
             hipHostMalloc((void**)&trace, 16 * sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess)
             memset(trace, 0, 16 * sizeof(unsigned long long));
         auto one = [&](uint32_t i) { // launch i: x = (i even ? v0 : v1), y = the other (even ring: the wrap keeps the ping-pong)

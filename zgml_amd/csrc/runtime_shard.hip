@@ -81,8 +81,7 @@ void free_shard_peer(zgml_hip_program* p) {
 extern "C" void shard_peer_release(zgml_hip_program* p) { free_shard_peer(p); }
 namespace {
 uint64_t peer_wait_ticks() { // 100 MHz ticks
-    static const uint64_t ms = (uint64_t)std::max(1, env_int("ZGML_SHARD_PEER_WAIT_MS", 5000));
-    return ms * 100000ull;
+    return (uint64_t)std::max(1, sw().shard_peer_wait_ms) * 100000ull;
 }
 
 // the device side of one sharded step on stream order: op ranges separated by in-place all-gathers
@@ -201,8 +200,7 @@ int zgml_hip_shard_attach(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_sha
     p->shard_pair_argmax = false;
     if (n_points && ctx->shard) {
         const zgml_shard_point& last = points[n_points - 1];
-        static const bool pairs_on = env_flag("ZGML_SHARD_PAIR_ARGMAX", true);
-        p->shard_pair_argmax = pairs_on && last.buf_idx == logits_buf && last.offset == 0 && (uint64_t)world * last.len_per_rank == vocab;
+        p->shard_pair_argmax = sw().shard_pair_argmax && last.buf_idx == logits_buf && last.offset == 0 && (uint64_t)world * last.len_per_rank == vocab;
     }
     if (p->shard_pair_argmax && world > 64) { // (the pair block — device array or the peer block's slots — holds 64 entries, in BOTH gather modes)
         ctx->fail("shard_attach: the (max, index) pair gather of the greedy token holds at most 64 ranks");
@@ -313,8 +311,7 @@ int64_t zgml_hip_shard_step(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_p
         build_plan(p);
     }
     if (zgml_hip_stage_inputs(ctx, p, inputs, n_inputs) != 0) return -1;
-    static const bool want_graph = env_flag("ZGML_SHARD_GRAPH", true);
-    if (want_graph && ctx->opt_graph && !p->shard_graph_exec && !p->shard_capture_failed) {
+    if (sw().shard_graph && ctx->opt_graph && !p->shard_graph_exec && !p->shard_capture_failed) {
         // relaxed capture: RCCL may touch its own (already created) resources while it enqueues
         hipGraph_t g = nullptr;
         bool ok = hipStreamSynchronize(s) == hipSuccess && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
