@@ -430,7 +430,15 @@ enum {
      * dequantise-then-dot arithmetic the default path (and the reference's x86 / GPU backends) computes: results differ by the
      * activations' int8 rounding. Applies to weights of block size 32 with K % 64 == 0, K <= 16384, N % 16 == 0 every use of which
      * is a dense M = 1 row; such ops run unfused. Read at compile_program. */
-    ZGML_HIP_OPT_W8A8 = 10
+    ZGML_HIP_OPT_W8A8 = 10,
+    /* 0 (default) / 1 / 2..8: quantized matmuls of 2 <= M <= bound rows (batched decode: one row per sequence) over Q4_0 weights
+     * with f16 scales and K >= the K-on-lanes threshold take the multi-row K-on-lanes mat-vec (zgml_amd/csrc/qmatvec_rows.hip)
+     * instead of the MFMA tile kernels. 1: bound = 6, the largest M at which that kernel measured faster than the tile kernels at
+     * Llama-2-7B size; 2..8: that bound (the kernel exists up to 8 rows). Such a weight is packed K-on-lanes
+     * when EVERY qmatmul over it has M <= bound (without the option: M = 1), and a later refresh that raises M above the bound over
+     * it is refused. Same results within the mat-vec tolerance. Short-K weights keep the n-on-lanes layout and the tile kernels.
+     * Read at compile_program. */
+    ZGML_HIP_OPT_SMALL_M_MATVEC = 11
 };
 int zgml_hip_set_option(zgml_hip_ctx* ctx, int option, int64_t value);
 /* Drop the cached device copy of host operand `b` (NULL: all of them). */
@@ -565,6 +573,26 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32
  * device. Blocking. Returns the greedy next token (< 0 on error); results equal execute_program on host-patched inputs. */
 int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* tokens, uint32_t n_tokens,
                                   uint32_t start_pos);
+
+/* ── Batched decode: one program step advances n_seqs independent sequences (the host side builds such a program with
+ * build_batch_decode_program, zgml_amd/host/llama_decode.hpp: activations [d, B], per-sequence KV slabs, one decode-shaped
+ * attention section per sequence). Every dynamic op (KV store offset, attention seq_kv) then follows the position of ITS
+ * sequence; set_sequences declares which, once, after compile_program. Every op with a position-dependent field must be
+ * listed (n_seqs <= 32, dyn_op_seq[i] < n_seqs), otherwise the call fails with an error on the context. */
+int zgml_hip_program_set_sequences(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t n_seqs, const uint32_t* dyn_op_indices,
+                                   const uint32_t* dyn_op_seq, uint64_t n_dyn);
+/* zgml_hip_refresh_dynamic per sequence: slice_pos[b] / seq_kv[b] (n_seqs entries each) for the ops of sequence b. Same bounds
+ * check and the same fall-back to program order as refresh_program. Returns 0, or -1 when no sequences are declared. */
+int zgml_hip_refresh_dynamic_batch(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* slice_pos, const uint32_t* seq_kv);
+/* The device-resident greedy loop over a batched program (zgml_hip_resident_setup on a program with sequences declared reads
+ * the T columns of token_input as n_seqs sequences, not T consecutive positions): sequence b starts with first_tokens[b] at
+ * start_pos[b] and produces n_steps[b] <= max_steps tokens, written to tokens_out[b * max_steps + i]. A sequence that has
+ * produced its count is frozen — same token, same position: its later steps recompute and rewrite the same KV column with the
+ * same values — and the rest of its row of tokens_out stays -1. Blocking; one graph launch per step; max(n_steps) steps run.
+ * Out-of-range tokens or positions are refused before anything is enqueued. zgml_hip_resident_decode / _prefill refuse a
+ * batched program, this call a plain one. Returns 0 on success. */
+int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                   const uint32_t* n_steps, uint32_t max_steps, int64_t* tokens_out /* [n_seqs][max_steps] */);
 
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];

@@ -196,6 +196,7 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_prefill", "zgml_hip_shard_unique_id", "zgml_hip_shard_init", "zgml_hip_shard_destroy", "zgml_hip_shard_attach", "zgml_hip_shard_step", "zgml_hip_shard_step_mode",
     "zgml_hip_shard_profile_step", "zgml_hip_shard_last_point_us", "zgml_hip_device_can_access_peer", "zgml_hip_device_count", "zgml_hip_shard_init_peer", "zgml_hip_shard_peer_export", "zgml_hip_shard_peer_import",
     "zgml_hip_program_plan_text", "zgml_hip_program_pin_outputs",
+    "zgml_hip_program_set_sequences", "zgml_hip_refresh_dynamic_batch", "zgml_hip_resident_decode_batch",
 ]
 
 class ShardPointC(C.Structure):
@@ -214,6 +215,7 @@ OPT_ATTN_SPLIT_MIN_KEYS = 7
 OPT_FUSE_RESIDENT_WGS = 8
 OPT_KSPLIT = 9
 OPT_W8A8 = 10
+OPT_SMALL_M_MATVEC = 11
 
 _PKG_DIR = Path(__file__).resolve().parent
 HIP_LIB_PATH = _PKG_DIR / "lib" / "libzgml_hip.so"
@@ -315,6 +317,12 @@ def _bind_hip(lib: C.CDLL) -> None:
     lib.zgml_hip_resident_setup.argtypes = [vp, vp, C.POINTER(ResidentLlamaC)]
     lib.zgml_hip_resident_decode.restype = i32
     lib.zgml_hip_resident_decode.argtypes = [vp, vp, u32, u32, u32, vp]
+    lib.zgml_hip_program_set_sequences.restype = i32
+    lib.zgml_hip_program_set_sequences.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(u32), u64]
+    lib.zgml_hip_refresh_dynamic_batch.restype = i32
+    lib.zgml_hip_refresh_dynamic_batch.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
+    lib.zgml_hip_resident_decode_batch.restype = i32
+    lib.zgml_hip_resident_decode_batch.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, vp]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

@@ -197,7 +197,7 @@ enum QWFormat : uint32_t {
     QW_RAW = 0, // int8 [K*N] + f32 scale per `bs` flat elements (any bs, any N)
     QW_Q4 = 1,  // packed nibbles, lane-tiled (see qmatvec.hip)
     QW_Q8 = 2,  // packed int8, lane-tiled
-    QW_Q4K = 3, // packed offset-binary nibbles, K ON LANES (qmatvec.hip: qmatvec_kon_body): M = 1 mat-vecs only, f16 scales
+    QW_Q4K = 3, // packed offset-binary nibbles, K ON LANES (qmatvec.hip: qmatvec_kon_body): M = 1 mat-vecs (and, opt-in, 2 <= M <= 8: qmatvec_rows.hip), f16 scales
     QW_W8A8 = 4, // the reference's W8A8 arm (w8a8.hip): re-quantised transposed int8 + f32 scale per (column, 32 k); M = 1 only, opt-in
 };
 
@@ -405,6 +405,27 @@ void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t tot
 // the position has reached max_seq). Same (value, index) ordering as launch_argmax: results are identical.
 void launch_argmax_tail(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, uint32_t* cnt, int64_t* out,
                         const ArgmaxAdvance& adv, const ResidentPrepArgs* prep, uint32_t prep_total);
+// ── batched decode (B independent sequences per step): the resident loop's token tail ──
+// Per-sequence state on the device, four words per sequence: state[b] = token, state[B + b] = position, state[2 B + b] = steps
+// left, state[3 B + b] = tokens produced; state[4 B] = the row length of `tokens` in the pick below.
+// The prep: what patch_batch_step (zgml_amd/host/llama_decode.cpp) patches on the host, as one flat index space — B embedding
+// rows, B causal-mask columns, B RoPE columns per layer leaf, and every dynamic word from the position of ITS sequence
+// (dyn_seq[op]): dyn_base + pos * dyn_stride (kind 1) or pos + 1 (kind 2).
+struct ResidentBatchPrepArgs {
+    const float *embed, *cos, *sin;
+    float *tok_in, *mask;
+    float* const* rope_bufs;
+    const uint32_t *dyn_kind, *dyn_base, *dyn_stride, *dyn_seq;
+    uint32_t* dyn;
+    const uint32_t* state;
+    uint32_t d, max_seq, dh, n_rope, n_ops, B;
+};
+void launch_resident_batch_prep(hipStream_t s, const ResidentBatchPrepArgs& a, uint32_t total); // total = B d + B max_seq + n_rope B 2 dh + n_ops
+// The greedy pick of all B rows of the [vocab, B] logits in one stage-1 and one stage-2 launch (blockIdx.y = sequence; first maximum
+// wins per row, as argmax_stage1 / 2). A sequence with steps left records the token at tokens[b * cap + produced] and advances
+// (token, position + 1, left - 1, produced + 1); one without is left as it is (it repeats its step). scratch: B * argmax_batch_blocks(n) pairs.
+int argmax_batch_blocks(uint64_t n);
+void launch_argmax_batch(hipStream_t s, const float* v, uint64_t n, uint32_t B, float* scratch_val, int64_t* scratch_idx, uint32_t* state, int64_t* tokens);
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes);
 void launch_f32_to_f16(hipStream_t s, void* dst, const float* src, uint64_t n);
 
@@ -437,6 +458,13 @@ constexpr uint64_t kQmmScratchHead = 16384;  // (round 4: 4096 counter words —
 constexpr uint64_t kQmmCounterBytes = 4096; // what the Q4_0 tile launchers size their K splits by (unchanged from round 3)
 uint64_t qmatmul_scratch_bytes(const QWeightDev& w, uint32_t M);
 void launch_qmatmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
+// 2 <= M <= kKonRowsMaxM rows over a K-on-lanes weight (qmatvec_rows.hip; ZGML_HIP_OPT_SMALL_M_MATVEC): every weight byte is
+// read once and every nibble converted once for all M rows. false (nothing launched): not that format or row count.
+constexpr uint32_t kKonRowsMaxM = 8;
+// ... and the rows ZGML_HIP_OPT_SMALL_M_MATVEC = 1 routes to it: the largest M at which it beat the tile kernels at Llama-2-7B size by
+// more than the box-to-box spread (+57 % at M = 2, +6.7 % at 6, -3 % at 7, -8 % at 8)
+constexpr uint32_t kKonRowsRoutedM = 6;
+bool launch_qmatvec_kon_rows(hipStream_t s, const QWeightDev& w, const QMatmulParams& p);
 // M > 1: up to qmatmul_max_group() quantized matmuls over the same rows in one launch (qmatmul_can_group pairwise)
 bool qmatmul_can_group(const QWeightDev& a, const QMatmulParams& pa, const QWeightDev& b, const QMatmulParams& pb);
 uint32_t qmatmul_max_group();

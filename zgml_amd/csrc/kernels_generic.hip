@@ -1493,6 +1493,109 @@ __global__ void __launch_bounds__(256) resident_prep_kernel(ResidentPrepArgs a) 
     resident_prep_element(a, blockIdx.x * 256 + threadIdx.x, a.state[1], a.tokens, 0, false);
 }
 
+// the batched form (kernels.h: ResidentBatchPrepArgs): column j / dynamic op i takes token and position of its own sequence
+__global__ void __launch_bounds__(256) resident_batch_prep_kernel(ResidentBatchPrepArgs a) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t* const tok = a.state;
+    const uint32_t* const pos = a.state + a.B;
+    if (i < a.B * a.d) {
+        const uint32_t j = i / a.d, e = i - j * a.d;
+        a.tok_in[i] = a.embed[(uint64_t)tok[j] * a.d + e];
+        return;
+    }
+    i -= a.B * a.d;
+    if (i < a.B * a.max_seq) {
+        const uint32_t j = i / a.max_seq, sidx = i - j * a.max_seq;
+        a.mask[i] = sidx <= pos[j] ? 0.0f : -INFINITY;
+        return;
+    }
+    i -= a.B * a.max_seq;
+    if (i < a.n_rope * a.B * 2 * a.dh) {
+        const uint32_t l = i / (a.B * 2 * a.dh), rem = i - l * (a.B * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
+        a.rope_bufs[l][rem] = e < a.dh ? a.cos[(uint64_t)pos[j] * a.dh + e] : a.sin[(uint64_t)pos[j] * a.dh + e - a.dh];
+        return;
+    }
+    i -= a.n_rope * a.B * 2 * a.dh;
+    if (i < a.n_ops) {
+        const uint32_t kind = a.dyn_kind[i];
+        if (kind == 0) return;
+        const uint32_t ps = pos[a.dyn_seq[i]];
+        a.dyn[i] = kind == 1 ? a.dyn_base[i] + ps * a.dyn_stride[i] : ps + 1;
+    }
+}
+
+// argmax_stage1 / argmax_stage2 over B rows of n values at once: blockIdx.y = row (sequence); same (value, index) ordering
+__global__ void __launch_bounds__(kBlock) argmax_batch_stage1(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    const float* row = v + (uint64_t)blockIdx.y * n;
+    float bv = -INFINITY;
+    int64_t bi = INT64_MAX;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+        float x = row[i];
+        if (x > bv || bi == INT64_MAX) { // strict >: earlier index wins within a thread's ascending walk
+            bv = x;
+            bi = (int64_t)i;
+        }
+    }
+    sv[threadIdx.x] = bv;
+    si[threadIdx.x] = bi;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out_val[blockIdx.y * gridDim.x + blockIdx.x] = sv[0];
+        out_idx[blockIdx.y * gridDim.x + blockIdx.x] = si[0];
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) argmax_batch_stage2(const float* vals, const int64_t* idxs, int nblk, uint32_t* state, int64_t* tokens) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    const uint32_t b = blockIdx.y, B = gridDim.y;
+    vals += (uint64_t)b * nblk, idxs += (uint64_t)b * nblk;
+    float bv = -INFINITY;
+    int64_t bi = INT64_MAX;
+    for (int i = threadIdx.x; i < nblk; i += kBlock)
+        if (idxs[i] != INT64_MAX) {
+            if (bi == INT64_MAX) {
+                bv = vals[i];
+                bi = idxs[i];
+            } else {
+                arg_combine(bv, bi, vals[i], idxs[i]);
+            }
+        }
+    sv[threadIdx.x] = bv;
+    si[threadIdx.x] = bi;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            if (si[threadIdx.x + off] != INT64_MAX) {
+                if (si[threadIdx.x] == INT64_MAX) {
+                    sv[threadIdx.x] = sv[threadIdx.x + off];
+                    si[threadIdx.x] = si[threadIdx.x + off];
+                } else {
+                    arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { // the advance step of sequence b: only while it has steps left (else it repeats the same token at the same position)
+        const int64_t next = si[0] == INT64_MAX ? -1 : si[0];
+        const uint32_t left = state[2 * B + b], produced = state[3 * B + b], cap = state[4 * B];
+        if (left > 0) {
+            if (produced < cap) tokens[(uint64_t)b * cap + produced] = next;
+            state[b] = (uint32_t)next;
+            state[B + b] += 1;
+            state[2 * B + b] = left - 1;
+            state[3 * B + b] = produced + 1;
+        }
+    }
+}
+
 // argmax_stage1 + (last arriver) argmax_stage2 + advance + the next token's prep (kernels.h: launch_argmax_tail)
 __global__ void __launch_bounds__(kBlock) argmax_tail_kernel(const float* __restrict__ v, uint64_t n, float* vals, int64_t* idxs, uint32_t* cnt, int64_t* out,
                                                              ArgmaxAdvance adv, ResidentPrepArgs prep, uint32_t prep_total, uint32_t has_prep) {
@@ -1583,6 +1686,20 @@ __global__ void __launch_bounds__(kBlock) argmax_tail_kernel(const float* __rest
 
 void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t total) {
     if (total) resident_prep_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
+}
+
+void launch_resident_batch_prep(hipStream_t s, const ResidentBatchPrepArgs& a, uint32_t total) {
+    if (total) resident_batch_prep_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
+}
+
+int argmax_batch_blocks(uint64_t n) {
+    const int nblk = (int)(n / (kBlock * 4) + 1);
+    return nblk > kArgBlocks ? kArgBlocks : nblk;
+}
+void launch_argmax_batch(hipStream_t s, const float* v, uint64_t n, uint32_t B, float* scratch_val, int64_t* scratch_idx, uint32_t* state, int64_t* tokens) {
+    const int nblk = argmax_batch_blocks(n);
+    argmax_batch_stage1<<<dim3(nblk, B), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
+    argmax_batch_stage2<<<dim3(1, B), kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, state, tokens);
 }
 
 void launch_argmax_tail(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, uint32_t* cnt, int64_t* out,

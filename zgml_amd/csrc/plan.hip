@@ -236,6 +236,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                 p->split_pos = pos - 1; // the merged launch still sits at the previous plan position
                 return false;
             }
+            if (w.format == QW_Q4K && qp.M >= 2 && qp.M <= p->kon_max_m) L.tag = "qmatvec-kon-rows"; // (launch_qmatmul: the multi-row K-on-lanes mat-vec)
             auto group = std::make_shared<std::vector<std::pair<QWeightDev, QMatmulParams>>>();
             group->push_back({w, qp});
             p->qmm_group = splits ? group : nullptr;
@@ -1947,9 +1948,10 @@ void build_plan(zgml_hip_program* p) {
     p->plan.clear();
     for (size_t i = 0; i < p->ops.size(); i++) { // (refresh_program refuses this already; a launch must never be skipped silently)
         const zgml_device_op& op = p->ops[i];
-        if (op.kind == ZGML_DOP_QMATMUL && op.u.qmatmul.M != 1 && op.u.qmatmul.weight_idx < p->qweights.size() &&
+        if (op.kind == ZGML_DOP_QMATMUL && op.u.qmatmul.M != 1 && op.u.qmatmul.M > p->kon_max_m && op.u.qmatmul.weight_idx < p->qweights.size() &&
             p->qweights[op.u.qmatmul.weight_idx].format == QW_Q4K)
-            p->ctx->fail("build_plan: op " + std::to_string(i) + " is an M > 1 qmatmul over a weight packed for M = 1 mat-vecs (K-on-lanes layout)");
+            p->ctx->fail("build_plan: op " + std::to_string(i) + " is an M > " + std::to_string(p->kon_max_m) + " qmatmul over a weight packed for M <= " +
+                         std::to_string(p->kon_max_m) + " mat-vecs (K-on-lanes layout)");
     }
     free_param_blobs(p);
     for (void* d : p->fuse_owned) hipFree(d); // counters / seen / idx of the previous plan's fused launches

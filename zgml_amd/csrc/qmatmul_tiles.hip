@@ -1538,8 +1538,9 @@ void launch_qmatmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, 
         launch_w8a8_matvec(s, w, p.input, p.dst);
         return;
     }
-    if (w.format == QW_Q4K && p.M != 1) { // compile_program only gives this layout to weights every use of which has M = 1
-        fprintf(stderr, "[zgml_hip] ERROR: an M = %u matmul over a K-on-lanes (mat-vec only) weight: not launched\n", p.M);
+    if (w.format == QW_Q4K && p.M != 1) { // compile_program only gives this layout to weights every use of which has M = 1 (M <= 8 under ZGML_HIP_OPT_SMALL_M_MATVEC)
+        if (!launch_qmatvec_kon_rows(s, w, p))
+            fprintf(stderr, "[zgml_hip] ERROR: an M = %u matmul over a K-on-lanes weight (mat-vecs of M <= %u rows only): not launched\n", p.M, kKonRowsMaxM);
         return;
     }
     const bool xvec = ((uintptr_t)p.input % 16 == 0) && (p.K % 4 == 0) && (p.M == 1 || p.in_rs % 4 == 0);

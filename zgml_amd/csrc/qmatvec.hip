@@ -853,34 +853,7 @@ __global__ void __launch_bounds__(1024) qmatvec_pair_kernel(QMV_HEAD_PARAMS, QMV
 // of the workgroup, so the lanes sum x^2 beside the products and 1 / sqrt(mean + eps) scales the 16 finished sums — no second
 // pass over x, no barrier in front of the first FMA. The absorbed ops' own outputs (x * inv, x * inv * gamma) are stored in
 // slices, 1 / workgroups of the vector each, by the lanes that store the results.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// one dword of an item: 8 nibbles of one k -> four column pairs of the accumulators. ONE asm statement: left to hipcc the
-// converts of all dwords (and items) are hoisted in front of the FMAs, which costs hundreds of live registers (the pair
-// kernel spilled 200 of them); here six temporaries are live and converts and FMAs alternate. `tt.x` = t, broadcast to both
-// halves of the packed FMA by op_sel_hi (tt.y is never read).
-__device__ __forceinline__ void kon_dword(f32x2& a0, f32x2& a1, f32x2& a2, f32x2& a3, uint32_t dw, f32x2 tt) {
-    uint32_t lo, hi;
-    f32x2 c0, c1, c2, c3;
-    asm("v_and_b32_e32 %4, 0xf0f0f0f, %10\n\t"
-        "v_lshrrev_b32_e32 %5, 4, %10\n\t"
-        "v_cvt_pk_f32_fp8_e32 %6, %4\n\t"
-        "v_and_b32_e32 %5, 0xf0f0f0f, %5\n\t"
-        "v_cvt_pk_f32_fp8_sdwa %7, %4 src0_sel:WORD_1\n\t"
-        "v_cvt_pk_f32_fp8_e32 %8, %5\n\t"
-        "v_pk_fma_f32 %0, %6, %11, %0 op_sel_hi:[1,0,1]\n\t"
-        "v_cvt_pk_f32_fp8_sdwa %9, %5 src0_sel:WORD_1\n\t"
-        "v_pk_fma_f32 %1, %7, %11, %1 op_sel_hi:[1,0,1]\n\t"
-        "v_pk_fma_f32 %2, %8, %11, %2 op_sel_hi:[1,0,1]\n\t"
-        "v_pk_fma_f32 %3, %9, %11, %3 op_sel_hi:[1,0,1]"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(lo), "=&v"(hi), "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3)
-        : "v"(dw), "v"(tt));
-}
-__device__ __forceinline__ void kon_dword(f32x2 (&acc)[8], int c, uint32_t dw, float t) {
-    f32x2 tt;
-    tt.x = t, tt.y = t;
-    kon_dword(acc[c], acc[c + 1], acc[c + 2], acc[c + 3], dw, tt);
-}
+// (f32x2, kon_dword and the wave fold kon_fold_wave live in qmv_common.h: qmatvec_rows.hip, the 2 <= M <= 8 form, shares them)
 // PAIR: the same k-pair and columns of a SECOND matrix (same shape, `pair_off` items / scale pairs further on) ride along: x is
 // loaded once and both column sets are accumulated (gate / up: kon_pair_finish)
 template <bool NT, bool PRO, bool XV, bool PAIR>
@@ -946,38 +919,8 @@ struct KonItem { // one lane's share of a step: k = 2p, 2p + 1 x 16 columns
     }
 };
 
-// (a, b) -> lanes 0-31: a summed over lane ^ 32, lanes 32-63: b summed over lane ^ 32
-__device__ __forceinline__ float kon_fold32(float a, float b) {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// rows 0 / 2: a summed over lane ^ 16, rows 1 / 3: b summed over lane ^ 16
-__device__ __forceinline__ float kon_fold16(float a, float b) {
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 // PROM: 0 = no prologue, 1 = in-kernel (x = a * b, optionally the deferred rmsnorm), 2 = PRENORM (xa_base is the producer's a * b,
 // the factor comes from its partial sums of squares)
-// the 16 per-lane column sums of a wave -> red[column] (lanes i < 4 of each row write; see the fold comment in the body)
-__device__ __forceinline__ void kon_fold_wave(f32x2 (&acc)[8], float T, float* red_w, uint32_t r, uint32_t i) {
-    // w = q - 8, per lane, before any cross-lane sum: the sums hold t * q / 512, so acc -= T * 8 / 512. With every q = 8 the
-    // chain acc <- fl(acc + t / 64) equals T / 64 term by term (a power of two commutes with rounding): exactly 0 comes out
-    const f32x2 TT = f32x2{T, T}, m64 = f32x2{-0.015625f, -0.015625f};
-#pragma unroll
-    for (int c = 0; c < 8; c++) acc[c] = __builtin_elementwise_fma(TT, m64, acc[c]);
-    // acc[c] = columns (2c, 2c + 1): after kon_fold32 over column pairs and kon_fold16 over those, register m holds, in row r,
-    // the partial of column 4m + {0, 2, 1, 3}[r]; one row fold finishes it
-    float a8[8];
-#pragma unroll
-    for (int m2 = 0; m2 < 8; m2++) a8[m2] = kon_fold32(acc[m2].x, acc[m2].y);
-    float a4[4];
-#pragma unroll
-    for (int m4 = 0; m4 < 4; m4++) a4[m4] = row16_sum(kon_fold16(a8[2 * m4], a8[2 * m4 + 1]));
-    const float v = (i & 2) ? ((i & 1) ? a4[3] : a4[2]) : ((i & 1) ? a4[1] : a4[0]);
-    if (i < 4) red_w[4 * i + ((r & 1) * 2 + (r >> 1))] = v;
-}
-
 // PAIR launches (gate / up): part 0 carries the SiLU chain, part 1 is plain, and the elementwise product silu(gate) * up that
 // the plan's NEXT mat-vec (the down projection) would recompute as its prologue is stored here, `pair_out` (plan.hip:
 // arm_pair) — both operands of that product are in this workgroup's registers. Wave 0, behind the barrier.

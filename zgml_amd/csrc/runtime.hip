@@ -542,6 +542,15 @@ struct zgml_resident {
     hipGraph_t graph_multi = nullptr; // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
     hipGraphExec_t graph_multi_exec = nullptr;
     uint32_t multi_n = 0;
+    // batched program (zgml_hip_program_set_sequences): per-sequence device state (kernels.h: ResidentBatchPrepArgs), the sequence of
+    // every dynamic op, the pick's scratch (n_seqs rows of partial maxima) and the produced tokens [n_seqs][bcap]
+    uint32_t n_seqs = 0;
+    uint32_t* bstate = nullptr;
+    uint32_t* dyn_seq = nullptr;
+    float* bval = nullptr;
+    int64_t* bidx = nullptr;
+    int64_t* btokens = nullptr;
+    uint64_t btokens_cap = 0; // elements
 };
 using Resident = zgml_resident;
 namespace {
@@ -571,6 +580,11 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->state);
     hipFree(r->tok_dev);
     hipFree(r->tokens);
+    hipFree(r->bstate);
+    hipFree(r->dyn_seq);
+    hipFree(r->bval);
+    hipFree(r->bidx);
+    hipFree(r->btokens);
     delete r;
     p->resident = nullptr;
 }
@@ -683,6 +697,9 @@ int zgml_hip_set_option(zgml_hip_ctx* ctx, int option, int64_t value) {
             return 0;
         case ZGML_HIP_OPT_KSPLIT: ctx->opt_ksplit = value != 0; return 0; // (latched per program at compile_program)
         case ZGML_HIP_OPT_W8A8: ctx->opt_w8a8 = value != 0; return 0;     // (decides the weights' device format at compile_program)
+        case ZGML_HIP_OPT_SMALL_M_MATVEC: // (same) 1: the measured bound; 2..8: that bound
+            ctx->opt_small_m = value <= 0 ? 0 : (value == 1 ? kKonRowsRoutedM : (uint32_t)std::min<int64_t>(value, kKonRowsMaxM));
+            return 0;
         case ZGML_HIP_OPT_DENSE_WEIGHT_CACHE:
             ctx->b_cache_cap = value > 0 ? (uint64_t)value : 0;
             if (!ctx->b_cache_cap) ctx->drop_b_cache();
@@ -930,13 +947,15 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     std::vector<PendingPack> pending(prog->n_qweights);
     uint64_t qs_total = 0, sc_total = 0;
     // Q4_0-valued weights with f16 scales that only ever feed M = 1 mat-vecs take the K-on-lanes layout (QW_Q4K, qmatvec.hip);
-    // a weight an M > 1 matmul reads keeps the n-on-lanes layout the tile kernels are built for
+    // a weight an M > 1 matmul reads keeps the n-on-lanes layout the tile kernels are built for. ZGML_HIP_OPT_SMALL_M_MATVEC moves
+    // the bound up (M <= 6 by default, at most 8): those row counts have a K-on-lanes kernel of their own (qmatvec_rows.hip)
+    p->kon_max_m = ctx->opt_small_m ? ctx->opt_small_m : 1;
     std::vector<char> qw_m1(prog->n_qweights, sw().hip_qmv_kon ? 1 : 0);
     std::vector<char> qw_m1_all(prog->n_qweights, 1); // every use is a dense M = 1 row (the W8A8 arm's condition, reference.zig:512-516)
     for (const auto& op : p->ops)
         if (op.kind == ZGML_DOP_QMATMUL && op.u.qmatmul.weight_idx < prog->n_qweights) {
             const auto& q = op.u.qmatmul;
-            if (q.M != 1) qw_m1[q.weight_idx] = 0;
+            if (q.M < 1 || q.M > p->kon_max_m) qw_m1[q.weight_idx] = 0;
             if (q.M != 1 || (q.input_row_stride != 0 && q.input_row_stride != q.K) || (q.dst_row_stride != 0 && q.dst_row_stride != q.N)) qw_m1_all[q.weight_idx] = 0;
         }
     for (uint64_t i = 0; ok && i < prog->n_qweights; i++) {
@@ -1120,6 +1139,61 @@ int zgml_hip_refresh_dynamic(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t sl
     return 0;
 }
 
+// Batched decode: which sequence each dynamic op follows. Every op on p->dyn_ops must be covered.
+int zgml_hip_program_set_sequences(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t n_seqs, const uint32_t* dyn_op_indices, const uint32_t* dyn_op_seq,
+                                   uint64_t n_dyn) {
+    if (!ctx || !p) return -1;
+    if (n_seqs < 1 || n_seqs > 32 || (n_dyn && (!dyn_op_indices || !dyn_op_seq))) {
+        ctx->fail("set_sequences: n_seqs must be 1..32 and the op lists present");
+        return -1;
+    }
+    std::vector<uint32_t> op_seq(p->ops.size(), UINT32_MAX);
+    for (uint64_t k = 0; k < n_dyn; k++) {
+        if (dyn_op_indices[k] >= p->ops.size() || dyn_op_seq[k] >= n_seqs) {
+            ctx->fail("set_sequences: entry " + std::to_string(k) + " names op " + std::to_string(dyn_op_indices[k]) + " / sequence " +
+                      std::to_string(dyn_op_seq[k]) + " outside the program / the " + std::to_string(n_seqs) + " sequences");
+            return -1;
+        }
+        op_seq[dyn_op_indices[k]] = dyn_op_seq[k];
+    }
+    for (const uint32_t i : p->dyn_ops)
+        if (op_seq[i] == UINT32_MAX) {
+            ctx->fail("set_sequences: op " + std::to_string(i) + " has a position-dependent field but no sequence was declared for it");
+            return -1;
+        }
+    hipSetDevice(ctx->device);
+    free_resident(p); // (a resident set-up reads the declaration: set it up again afterwards)
+    p->n_seqs = n_seqs;
+    p->op_seq = std::move(op_seq);
+    return 0;
+}
+
+// zgml_hip_refresh_dynamic per sequence: the ops of sequence b take slice_pos[b] / seq_kv[b]
+int zgml_hip_refresh_dynamic_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* slice_pos, const uint32_t* seq_kv) {
+    if (!ctx || !p || !slice_pos || !seq_kv) return -1;
+    if (!p->n_seqs) {
+        ctx->fail("refresh_dynamic_batch: no sequences declared for this program (zgml_hip_program_set_sequences)");
+        return -1;
+    }
+    const uint64_t t_prof = ctx->host_prof ? now_ns() : 0;
+    bool in_bounds = true;
+    for (const uint32_t i : p->dyn_ops) {
+        zgml_device_op src = p->ops[i];
+        const uint32_t b = p->op_seq[i];
+        switch (src.kind) {
+            case ZGML_DOP_SLICE_ASSIGN: src.u.slice_assign.dst_offset = src.u.slice_assign.dst_base_offset + slice_pos[b] * src.u.slice_assign.patch_stride; break;
+            case ZGML_DOP_ATTENTION: src.u.attention.seq_kv = seq_kv[b]; break;
+            case ZGML_DOP_KVQ_STORE: src.u.kvq_store.col = src.u.kvq_store.col_base + slice_pos[b] * src.u.kvq_store.patch_stride; break;
+            case ZGML_DOP_ATTENTION_KVQ: src.u.attention_kvq.seq_kv = seq_kv[b]; break;
+            default: break;
+        }
+        in_bounds = apply_dynamic(p, i, src) && in_bounds;
+    }
+    if (p->plan_batched && !in_bounds) p->batching_safe = false, p->plan_dirty = true;
+    if (ctx->host_prof) ctx->prof_ns[0] += now_ns() - t_prof, ctx->prof_calls[0]++;
+    return 0;
+}
+
 void zgml_hip_refresh_program(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_device_op* ops, uint64_t n_ops) {
     if (!ctx || !p || !ops) return;
     const uint64_t t_prof = ctx->host_prof ? now_ns() : 0;
@@ -1149,11 +1223,14 @@ void zgml_hip_refresh_program(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml
         // fed M = 1 mat-vecs was packed K-on-lanes (QW_Q4K), which the M > 1 tile kernels cannot read. Refuse the refresh (the
         // program keeps its previous ops) instead of skipping the launch later: a stale destination must never look like success.
         const zgml_device_op& op = ops[i];
-        if (op.kind == ZGML_DOP_QMATMUL && op.u.qmatmul.M != 1 && op.u.qmatmul.weight_idx < p->qweights.size() &&
-            (p->qweights[op.u.qmatmul.weight_idx].format == QW_Q4K || p->qweights[op.u.qmatmul.weight_idx].format == QW_W8A8)) {
+        if (op.kind != ZGML_DOP_QMATMUL || op.u.qmatmul.weight_idx >= p->qweights.size()) continue;
+        const QWFormat fmt = p->qweights[op.u.qmatmul.weight_idx].format;
+        const uint32_t max_m = fmt == QW_Q4K ? p->kon_max_m : 1; // (W8A8: M = 1 only)
+        if ((fmt == QW_Q4K || fmt == QW_W8A8) && op.u.qmatmul.M != 1 && op.u.qmatmul.M > max_m) {
             ctx->fail("refresh_program: op " + std::to_string(i) + " turns weight " + std::to_string(op.u.qmatmul.weight_idx) +
                       " into the operand of an M = " + std::to_string(op.u.qmatmul.M) +
-                      " qmatmul, but the weight was packed for M = 1 mat-vecs at compile time (K-on-lanes layout): recompile the program");
+                      " qmatmul, but the weight was packed for M <= " + std::to_string(max_m) + " mat-vecs at compile time (" +
+                      (fmt == QW_Q4K ? "K-on-lanes" : "W8A8") + " layout): recompile the program");
             return;
         }
     }
@@ -1161,6 +1238,13 @@ void zgml_hip_refresh_program(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml
     own_ops(p, ops, n_ops);
     set_dyn_from_ops(p);
     p->plan_dirty = true;
+    if (p->n_seqs) // a static refresh may have made another op dynamic: the declaration only survives while it still covers them all
+        for (const uint32_t i : p->dyn_ops)
+            if (i >= p->op_seq.size() || p->op_seq[i] == UINT32_MAX) {
+                free_resident(p);
+                p->n_seqs = 0, p->op_seq.clear();
+                break;
+            }
 }
 
 // inputs: pack -> one H2D -> scatter kernel
@@ -1652,9 +1736,14 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
         ctx->fail("resident_setup: attn_mask / logits smaller than token_len columns / rows");
         return -1;
     }
+    if (p->n_seqs && T != p->n_seqs) {
+        ctx->fail("resident_setup: the program declares " + std::to_string(p->n_seqs) + " sequences but token_input holds " + std::to_string(T) + " columns");
+        return -1;
+    }
     Resident* r = new Resident();
     p->resident = r;
     r->token_len = T;
+    r->n_seqs = p->n_seqs; // > 0: the T columns are T sequences (zgml_hip_resident_decode_batch), not T consecutive positions
     r->vocab = d->vocab, r->d = d->d_model, r->max_seq = d->max_seq, r->dh = d->d_head, r->n_rope = d->n_rope;
     r->tok_in = p->bufs[d->buf_token_input], r->mask = p->bufs[d->buf_attn_mask], r->logits = p->bufs[d->buf_logits];
     const size_t n_ops = p->ops.size();
@@ -1691,6 +1780,14 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
               CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_kind, kind.data(), n_ops * 4)) &&
               CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_base, base.data(), n_ops * 4)) &&
               CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_stride, stride.data(), n_ops * 4));
+    if (ok && r->n_seqs) {
+        std::vector<uint32_t> seq(n_ops + 1, 0);
+        for (size_t i = 0; i < n_ops; i++) seq[i] = kind[i] && i < p->op_seq.size() && p->op_seq[i] != UINT32_MAX ? p->op_seq[i] : 0;
+        const size_t pairs = (size_t)r->n_seqs * argmax_batch_blocks(d->vocab);
+        ok = CTX_CHECK(ctx, hipMalloc((void**)&r->bstate, ((size_t)4 * r->n_seqs + 1) * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_seq, (n_ops + 1) * 4)) &&
+             CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) && CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))) &&
+             CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_seq, seq.data(), n_ops * 4));
+    }
     if (!ok) {
         free_resident(p);
         return -1;
@@ -1709,6 +1806,10 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
                              uint32_t n_steps, int64_t* tokens_out) {
     if (!ctx || !p || !p->resident || !tokens_out) return -1;
     Resident* r = p->resident;
+    if (r->n_seqs) {
+        ctx->fail("resident_decode: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
+        return -1;
+    }
     if (r->token_len != 1) {
         ctx->fail("resident_decode: the program is a token_len > 1 plan (use zgml_hip_resident_prefill)");
         return -1;
@@ -1832,10 +1933,131 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
 }
 
 
+// The resident loop over a batched program: per step [batched prep] [plan] [pick stage 1] [pick stage 2 + advance], one graph launch.
+int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                   const uint32_t* n_steps, uint32_t max_steps, int64_t* tokens_out) {
+    if (!ctx || !p) return -1;
+    Resident* r = p->resident;
+    if (!r || !r->n_seqs || !p->n_seqs) {
+        ctx->fail("resident_decode_batch: not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
+        return -1;
+    }
+    if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
+    const uint32_t B = r->n_seqs;
+    uint32_t steps = 0;
+    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
+    if (steps > max_steps) {
+        ctx->fail("resident_decode_batch: n_steps exceeds max_steps");
+        return -1;
+    }
+    // everything is refused before anything is enqueued. A sequence that stops before the last step repeats its step at the position
+    // BEHIND its last token (it rewrites that KV column with the same values): that column must exist too
+    std::vector<uint32_t> last_pos(B);
+    for (uint32_t b = 0; b < B; b++) {
+        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b]; // position after its last step
+        const bool idles = n_steps[b] < steps;
+        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
+            ctx->fail("resident_decode_batch: token or position out of range (sequence " + std::to_string(b) + ")");
+            return -1;
+        }
+        last_pos[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
+    }
+    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
+    if (!steps) return 0;
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
+        free_graph(p);
+        build_plan(p);
+    }
+    if (p->plan_batched) { // the device patches the dynamic words itself: first and last position of every sequence against the plan's bounds
+        bool ok = true;
+        std::vector<zgml_device_op> probe = p->ops;
+        for (int last = 0; last < 2; last++) {
+            for (const uint32_t i : p->dyn_ops) {
+                auto& o = probe[i];
+                const uint32_t pos = last ? last_pos[p->op_seq[i]] : start_pos[p->op_seq[i]];
+                if (o.kind == ZGML_DOP_SLICE_ASSIGN) o.u.slice_assign.dst_offset = o.u.slice_assign.dst_base_offset + pos * o.u.slice_assign.patch_stride;
+                if (o.kind == ZGML_DOP_ATTENTION) o.u.attention.seq_kv = pos + 1;
+            }
+            ok = ok && dynamic_fields_in_bounds(p->sched, probe);
+        }
+        if (!ok) { // fall back to program order for good, like refresh_program
+            p->batching_safe = false;
+            free_graph(p);
+            build_plan(p);
+        }
+    }
+    if (r->btokens_cap < (uint64_t)B * steps) {
+        hipStreamSynchronize(s);
+        hipFree(r->btokens);
+        r->btokens = nullptr, r->btokens_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->btokens, (size_t)B * steps * 8))) return -1;
+        r->btokens_cap = (uint64_t)B * steps;
+        free_resident_graph(p); // the graph baked the old pointer
+    }
+    const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
+                                  p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
+    const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
+    auto one_step = [&](hipStream_t st) {
+        launch_resident_batch_prep(st, a, total);
+        run_plan(p, st, 0, p->plan.size());
+        launch_argmax_batch(st, r->logits, r->vocab, B, r->bval, r->bidx, r->bstate, r->btokens);
+    };
+    set_dyn_from_ops(p); // static dyn words (the row stores) from the host mirror; the prep kernel rewrites the position-dependent ones
+    p->dyn_dirty = true;
+    flush_dyn(p);
+    std::vector<uint32_t> st0((size_t)4 * B + 1, 0);
+    for (uint32_t b = 0; b < B; b++) st0[b] = first_tokens[b], st0[B + b] = start_pos[b], st0[2 * B + b] = n_steps[b];
+    st0[4 * B] = steps; // row length of the device token table of this call
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
+        return -1;
+    if (ctx->opt_graph && !r->graph_exec) {
+        hipStreamSynchronize(s); // (st0 is read by the copy above: it must not die under a pageable-memory copy in flight)
+        hipGraph_t g = nullptr;
+        if (CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) {
+            one_step(s);
+            if (CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) && g) {
+                dump_graph(g, "resident_batch");
+                if (CTX_CHECK(ctx, hipGraphInstantiate(&r->graph_exec, g, nullptr, nullptr, 0)))
+                    r->graph = g;
+                else
+                    hipGraphDestroy(g);
+            }
+        }
+    }
+    for (uint32_t i = 0; i < steps; i++) {
+        if (r->graph_exec)
+            hipGraphLaunch(r->graph_exec, s);
+        else
+            one_step(s);
+    }
+    std::vector<int64_t> got((size_t)B * steps);
+    hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
+    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    ok = ok && ctx->handoff_ok("resident_decode_batch");
+    for (uint32_t b = 0; ok && b < B; b++)
+        for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
+    // the device rewrote the dyn block behind the host mirror's back: force a re-upload next time
+    memset(p->dyn_host, 0xFF, p->ops.size() * sizeof(uint32_t));
+    set_dyn_from_ops(p);
+    p->dyn_dirty = true;
+    p->profile.call_count += steps;
+    p->profile.backend_op_count += (uint64_t)steps * p->ops.size();
+    p->profile.backend_dispatch_count += (uint64_t)steps * (p->plan.size() + 3);
+    return ok ? 0 : -1;
+}
+
+
 // One execution of a token_len = T plan (a prefill chunk) with everything but the T token ids produced on the device.
 int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* tokens, uint32_t n_tokens, uint32_t start_pos) {
     if (!ctx || !p || !p->resident || !tokens) return -1;
     Resident* r = p->resident;
+    if (r->n_seqs) {
+        ctx->fail("resident_prefill: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
+        return -1;
+    }
     if (n_tokens != r->token_len || (uint64_t)start_pos + n_tokens > r->max_seq) {
         ctx->fail("resident_prefill: n_tokens must equal the plan's token_len and the chunk must fit max_seq");
         return -1;

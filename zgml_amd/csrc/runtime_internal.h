@@ -94,6 +94,7 @@ struct zgml_hip_ctx {
     uint64_t prof_ns[4] = {0, 0, 0, 0}, prof_calls[4] = {0, 0, 0, 0};
     bool opt_ksplit = false; // ZGML_HIP_OPT_KSPLIT (zgml_hip_create takes the default from ZGML_HIP_KSPLIT)
     bool opt_w8a8 = false;   // ZGML_HIP_OPT_W8A8: M = 1 qmatmuls through the reference's W8A8 arm (w8a8.hip); read at compile_program
+    uint32_t opt_small_m = 0; // ZGML_HIP_OPT_SMALL_M_MATVEC: 0 off, else the largest M whose qmatmuls over long-K Q4_0 weights go through qmatvec_rows.hip; read at compile_program
     int64_t opt_attn_split_min_keys = -1; // -1: environment / default (attn_split_for)
     int64_t opt_fuse_resident_wgs = -1;   // -1: one 1024-thread workgroup per CU (fuse_qkv_attention)
     // host dense override scratch
@@ -190,6 +191,10 @@ struct zgml_hip_program {
     std::vector<char> hoist_guard; // per buffer: read or written by a hoisted repeat
     bool hoist_ok = true;
     bool ksplit = false;                 // ZGML_HIP_OPT_KSPLIT as it stood at compile_program
+    uint32_t kon_max_m = 1;              // rows a qmatmul over a K-on-lanes weight of this program may have (ZGML_HIP_OPT_SMALL_M_MATVEC's bound at compile_program)
+    // batched decode (zgml_hip_program_set_sequences): sequences per step (0: none declared) and, per op, the sequence its dynamic field follows
+    uint32_t n_seqs = 0;
+    std::vector<uint32_t> op_seq;
     bool ksplit_off = false;             // fuse_ksplit: off for this program (a caller enqueues op ranges: a deferred vector must not outlive a range)
     bool has_deferred = false;           // the plan holds launches that leave a vector deferred to their successor
     float* prenorm_buf = nullptr;        // arm_prenorm: [x * gamma | partial sums of squares] handed from a residual epilogue to the next prologue

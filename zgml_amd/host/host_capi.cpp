@@ -2,9 +2,11 @@
 // The compute backend is passed in as a function table whose signatures are exactly the
 // zgml_hip_* entry points (ctx first), so the same session code drives the HIP library or — in
 // tests only — the CPU oracle's ctx-taking wrappers.
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <functional>
+#include <string>
 
 #include "llama_decode.hpp"
 
@@ -38,7 +40,7 @@ typedef struct zh_gather_point {
 } zh_gather_point;
 
 struct zh_model {
-    std::unique_ptr<LlamaModel> model;
+    std::shared_ptr<LlamaModel> model; // (shared with the batched twins built from it: zh_model_create_batch_like)
     std::unique_ptr<DecodeProgram> dp;
     std::vector<zgml_qweight_upload> qw_storage;
     zgml_device_program flat;
@@ -52,6 +54,8 @@ struct zh_session {
     // patched ops exactly as the reference does for its wgpu backend (stepDynamicStateFromOps, src/backend/program.zig:7466-7490)
     // and hands over those two numbers instead of the whole op list
     int (*refresh_dynamic)(void* ctx, void* handle, uint32_t slice_pos, uint32_t seq_kv) = nullptr;
+    // ... and its per-sequence form for a batched program (zgml_hip_refresh_dynamic_batch)
+    int (*refresh_dynamic_batch)(void* ctx, void* handle, const uint32_t* slice_pos, const uint32_t* seq_kv) = nullptr;
 };
 
 void zh_preset(const char* name, uint32_t max_seq, zh_config* out) {
@@ -89,6 +93,77 @@ zh_model* zh_model_create_ex(const zh_config* cfg, int weight_kind, int fused_el
     m->dp = build_decode_program(*m->model, fused_elementwise != 0, include_dead_f32 != 0, token_len ? token_len : 1);
     m->flat = m->dp->program.view(m->qw_storage);
     return m;
+}
+
+// The batched decode program of `n_seqs` sequences (build_batch_decode_program). NULL and a text in `err` (cap bytes, NUL-terminated)
+// for what the builder refuses: int8 KV caches, a sharded config, n_seqs outside 1..32.
+zh_model* zh_model_create_batch(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
+                                char* err, uint64_t err_cap) {
+    auto fail = [&](const std::string& why) -> zh_model* {
+        if (err && err_cap) {
+            const size_t n = std::min<size_t>(err_cap - 1, why.size());
+            std::memcpy(err, why.data(), n);
+            err[n] = 0;
+        }
+        return nullptr;
+    };
+    LlamaConfig c;
+    c.vocab_size = cfg->vocab_size, c.d_model = cfg->d_model, c.n_heads = cfg->n_heads, c.n_kv_heads = cfg->n_kv_heads;
+    c.d_ff = cfg->d_ff, c.n_layers = cfg->n_layers, c.max_seq_len = cfg->max_seq_len, c.rope_base = cfg->rope_base;
+    c.rms_norm_eps = cfg->rms_norm_eps, c.tied_lm_head = cfg->tied_lm_head != 0;
+    c.shard_rank = cfg->shard_rank, c.shard_world = cfg->shard_world ? cfg->shard_world : 1;
+    c.kv_quant_block = cfg->kv_quant_block;
+    if (c.n_heads == 0 || c.n_kv_heads == 0 || c.d_model % c.n_heads || c.n_heads % c.n_kv_heads) return fail("invalid LlamaConfig");
+    // the builder's refusals first: they need no weights
+    if (n_seqs < 1 || n_seqs > kMaxBatchSeqs) return fail("build_batch_decode_program: n_seqs must be 1..32");
+    if (c.kv_quant_block != 0) return fail("build_batch_decode_program: int8 KV caches (kv_quant_block != 0) under batching are out of scope");
+    if (c.shard_world != 1) return fail("build_batch_decode_program: the row shard (shard_world != 1) under batching is out of scope");
+    auto* m = new zh_model();
+    m->model = make_synthetic_model(c, (WeightKind)weight_kind, threads);
+    std::string why;
+    m->dp = build_batch_decode_program(*m->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why);
+    if (!m->dp) {
+        delete m;
+        return fail(why);
+    }
+    m->flat = m->dp->program.view(m->qw_storage);
+    return m;
+}
+// ... over the weights of an existing model (shared, not copied): the batched twin of `base` for n_seqs sequences
+zh_model* zh_model_create_batch_like(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, char* err, uint64_t err_cap) {
+    std::string why;
+    auto dp = build_batch_decode_program(*base->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why);
+    if (!dp) {
+        if (err && err_cap) {
+            const size_t n = std::min<size_t>(err_cap - 1, why.size());
+            std::memcpy(err, why.data(), n);
+            err[n] = 0;
+        }
+        return nullptr;
+    }
+    auto* m = new zh_model();
+    m->model = base->model;
+    m->dp = std::move(dp);
+    m->flat = m->dp->program.view(m->qw_storage);
+    return m;
+}
+uint32_t zh_model_n_seqs(zh_model* m) { return m->dp->n_seqs; }
+void zh_model_patch_batch(zh_model* m, const uint32_t* tokens, const uint32_t* pos) { patch_batch_step(*m->model, *m->dp, tokens, pos); }
+// every op with a position-dependent field and the sequence it follows (what zgml_hip_program_set_sequences takes); returns the count
+uint64_t zh_model_dyn_sequences(zh_model* m, uint32_t* op_indices, uint32_t* op_seq, uint64_t cap) {
+    const DecodeProgram& dp = *m->dp;
+    uint64_t n = 0;
+    auto put = [&](uint32_t idx, uint32_t seq) {
+        if (n < cap) op_indices[n] = idx, op_seq[n] = seq;
+        n++;
+    };
+    for (size_t k = 0; k < dp.slice_assign_op_indices.size(); k++) {
+        const auto& op = dp.program.ops[dp.slice_assign_op_indices[k]];
+        const bool dyn = op.kind == ZGML_DOP_KVQ_STORE ? op.u.kvq_store.patch_stride != 0 : op.u.slice_assign.patch_stride != 0;
+        if (dyn) put(dp.slice_assign_op_indices[k], dp.slice_assign_seq[k]);
+    }
+    for (size_t k = 0; k < dp.attention_op_indices.size(); k++) put(dp.attention_op_indices[k], dp.attention_seq[k]);
+    return n;
 }
 
 void zh_model_free(zh_model* m) { delete m; }
@@ -208,6 +283,27 @@ int64_t zh_session_prefill(zh_session* s, const uint32_t* tokens, uint32_t pos, 
                            dp.step_outputs.size());
     if (logits_out) std::memcpy(logits_out, dp.logits_host.data(), dp.logits_host.size() * sizeof(float));
     return LlamaDeviceSession::argmax(dp.logits_host.data(), (uint32_t)dp.logits_host.size());
+}
+
+void zh_session_set_refresh_dynamic_batch(zh_session* s, int (*fn)(void*, void*, const uint32_t*, const uint32_t*)) { s->refresh_dynamic_batch = fn; }
+
+// One step of a batched program: patch the B columns, refresh (per-sequence dynamic refresh when set, else the whole op list),
+// execute. logits_out: [B][vocab] (may be NULL); next_out[B]: each sequence's greedy token.
+int zh_session_step_batch(zh_session* s, const uint32_t* tokens, const uint32_t* pos, float* logits_out, int64_t* next_out) {
+    DecodeProgram& dp = *s->m->dp;
+    const uint32_t B = dp.n_seqs, vocab = s->m->model->cfg.vocab_size;
+    if (!B) return -1;
+    for (uint32_t b = 0; b < B; b++)
+        if (tokens[b] >= vocab || pos[b] >= s->m->model->cfg.max_seq_len) return -1;
+    patch_batch_step(*s->m->model, dp, tokens, pos);
+    uint32_t seq_kv[kMaxBatchSeqs];
+    for (uint32_t b = 0; b < B; b++) seq_kv[b] = pos[b] + 1;
+    if (!(s->refresh_dynamic_batch && s->refresh_dynamic_batch(s->fns.ctx, s->handle, pos, seq_kv) == 0))
+        s->fns.refresh_program(s->fns.ctx, s->handle, dp.program.ops.data(), dp.program.ops.size());
+    s->fns.execute_program(s->fns.ctx, s->handle, dp.step_inputs.data(), dp.step_inputs.size(), dp.step_outputs.data(), dp.step_outputs.size());
+    if (logits_out) std::memcpy(logits_out, dp.logits_host.data(), dp.logits_host.size() * sizeof(float));
+    for (uint32_t b = 0; b < B; b++) next_out[b] = LlamaDeviceSession::argmax(dp.logits_host.data() + (size_t)b * vocab, vocab);
+    return 0;
 }
 
 // the session's greedy pick and the reference's own loop (tests compare them; first maximum wins, src/nn.zig:122-138)

@@ -282,8 +282,11 @@ struct Builder {
 
 } // namespace
 
-std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, bool fused_elementwise,
-                                                    bool include_dead_f32, uint32_t token_len) {
+// n_seqs == 0: the decode (token_len 1) / prefill (token_len N) plan. n_seqs = B >= 1: the batched decode plan — everything but the
+// attention section is the token_len = B plan (activations [d, B]); the attention section is, per sequence b, the token_len = 1
+// plan's op subsequence on column b, over sequence b's slab of the layer's K / V buffers.
+static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, bool fused_elementwise, bool include_dead_f32, uint32_t token_len,
+                                                    uint32_t n_seqs) {
     const LlamaConfig& c = model.cfg;
     auto dpp = std::make_unique<DecodeProgram>();
     DecodeProgram& dp = *dpp;
@@ -298,8 +301,12 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
     const bool rehearse = ws == 1 && token_len <= 1 && !c.tied_lm_head && getenv("ZGML_HOST_SHARD_POINTS_WORLD1") &&
                           atoi(getenv("ZGML_HOST_SHARD_POINTS_WORLD1")) != 0;
     const bool sharded = ws > 1 || rehearse;
-    const uint32_t T = token_len ? token_len : 1; // tokens per execution: 1 = decode plan, N = prefill plan
+    const uint32_t B = n_seqs;
+    const uint32_t T = B ? B : (token_len ? token_len : 1); // tokens per execution: 1 = decode plan, N = prefill plan, B = one token of each sequence
     dp.token_len = T;
+    dp.n_seqs = B;
+    const uint32_t TA = B ? 1 : T;       // columns one pass of the attention section handles
+    const uint32_t n_pass = B ? B : 1;   // ... and its passes (one per sequence)
 
     // quantized weight table (all borrowed from the model), or dense f32 weight leaves
     for (const auto& qw : model.qweights) {
@@ -314,7 +321,7 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
     dp.token_input.assign((size_t)d * T, 0.f);
     dp.attn_mask.assign((size_t)S * T, -std::numeric_limits<float>::infinity()); // [max_seq, T], column per query
     for (uint32_t j = 0; j < T; j++)
-        for (uint32_t s2 = 0; s2 <= j; s2++) dp.attn_mask[(size_t)j * S + s2] = 0.f;
+        for (uint32_t s2 = 0; s2 <= (B ? 0 : j); s2++) dp.attn_mask[(size_t)j * S + s2] = 0.f; // (batched: every sequence at position 0)
     dp.scalar_one.assign(1, 1.0f);
     dp.buf_token_input = b.leaf(dp.token_input);
     dp.buf_attn_mask = b.leaf(dp.attn_mask);
@@ -328,12 +335,14 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
         dp.buf_rope.push_back(rope_cs);
         // consolidated KV caches [d_head, max_seq * n_kv_heads] (this rank's kv heads), zero-initialised:
         // the backend zero-fills every buffer at compile, so no upload is recorded for them
-        const uint16_t k_cache = b.buffer((uint64_t)dh * S * KV_loc), v_cache = b.buffer((uint64_t)dh * S * KV_loc);
+        // (batched: B such slabs back to back, sequence b's at b * kv_slab — the single-sequence plan's whole buffer)
+        const uint64_t kv_slab = (uint64_t)dh * S * KV_loc;
+        const uint16_t k_cache = b.buffer(kv_slab * n_pass), v_cache = b.buffer(kv_slab * n_pass);
         dp.buf_k_cache.push_back(k_cache);
         dp.buf_v_cache.push_back(v_cache);
         if (!c.kv_quant_block) {
-            dp.kv_buffers.push_back({k_cache, (uint64_t)dh * S * KV_loc});
-            dp.kv_buffers.push_back({v_cache, (uint64_t)dh * S * KV_loc});
+            dp.kv_buffers.push_back({k_cache, kv_slab * n_pass});
+            dp.kv_buffers.push_back({v_cache, kv_slab * n_pass});
         }
         if (include_dead_f32 && model.kind != WeightKind::f32_dense) { // f32 master copies: buffers + uploads, never referenced by an op (F8)
             for (int j = 0; j < 7; j++) {
@@ -353,7 +362,6 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
         const uint16_t q_proj = b.buffer((uint64_t)d_loc * T), k_proj = b.buffer((uint64_t)kvd_loc * T),
                        v_proj = b.buffer((uint64_t)kvd_loc * T);
         bool q_done = false;
-        std::vector<char> kv_done(KV_loc, 0);
         bool k_proj_done = false, v_proj_done = false;
         std::vector<uint16_t> attn_out(H_loc);
         const uint32_t kvq = c.kv_quant_block; // quantised KV: one int8 cache buffer per kv head (K and V)
@@ -365,70 +373,77 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
                 dp.kv_buffers.push_back({kq_cache[j], elems});
                 dp.kv_buffers.push_back({vq_cache[j], elems});
             }
-        for (int hl = (int)H_loc - 1; hl >= 0; hl--) {
-            const uint32_t h = h0 + hl, kvh = h / n_rep, kvl = kvh - kv0;
-            if (!q_done) {
-                b.proj(q_proj, norm1, wq, T, d_loc, d, 0, d, 0, d_loc);
-                q_done = true;
-            }
-            const uint16_t q_rot = b.buffer((uint64_t)dh * T);
-            b.op(DeviceOp::rope(q_rot, q_proj, rope_cs, dh / 2, T, hl * dh, 0, 0, 1, d_loc, 2 * dh));
-            if (!kv_done[kvl]) {
-                kv_done[kvl] = 1;
-                if (!k_proj_done) {
-                    b.proj(k_proj, norm1, wk, T, kvd_loc, d, 0, d, 0, kvd_loc);
-                    k_proj_done = true;
+        for (uint32_t sq = 0; sq < n_pass; sq++) { // (batched: sequence sq = column sq of the activations; else one pass over all T columns)
+            std::vector<char> kv_done(KV_loc, 0);
+            const uint32_t seq_slab = sq * (uint32_t)kv_slab; // this sequence's slab of the K / V buffers
+            auto dyn_store = [&](uint32_t seq) { dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size()), dp.slice_assign_seq.push_back(seq); };
+            for (int hl = (int)H_loc - 1; hl >= 0; hl--) {
+                const uint32_t h = h0 + hl, kvh = h / n_rep, kvl = kvh - kv0;
+                if (!q_done) {
+                    b.proj(q_proj, norm1, wq, T, d_loc, d, 0, d, 0, d_loc);
+                    q_done = true;
                 }
-                const uint16_t k_rot = b.buffer((uint64_t)dh * T);
-                b.op(DeviceOp::rope(k_rot, k_proj, rope_cs, dh / 2, T, kvl * dh, 0, 0, 1, kvd_loc, 2 * dh));
-                const uint32_t slab = kvl * S * dh; // k_cache.sliceColumns(kv_h*max_seq, ...)
-                if (kvq) { // k_cache.storeColumn(pos + j, k_rot[:, j]) (llama_inference.zig:300-320)
-                    for (uint32_t j = 0; j < T; j++) {
-                        dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size());
-                        b.op(DeviceOp::kvq_store({kq_cache[kvl], k_rot, dh, kvq, S, j * dh, j, j, 1}));
+                const uint16_t q_rot = b.buffer((uint64_t)dh * TA);
+                b.op(DeviceOp::rope(q_rot, q_proj, rope_cs, dh / 2, TA, sq * d_loc + hl * dh, sq * 2 * dh, 0, 1, d_loc, 2 * dh));
+                if (!kv_done[kvl]) {
+                    kv_done[kvl] = 1;
+                    if (!k_proj_done) {
+                        b.proj(k_proj, norm1, wk, T, kvd_loc, d, 0, d, 0, kvd_loc);
+                        k_proj_done = true;
                     }
-                } else {
-                    dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size());
-                    b.op(DeviceOp::slice_assign(k_cache, k_rot, dh, T, slab, slab, 1, dh, 0, 1, dh, dh));
-                }
-                if (!v_proj_done) {
-                    b.proj(v_proj, norm1, wv, T, kvd_loc, d, 0, d, 0, kvd_loc);
-                    v_proj_done = true;
-                }
-                if (kvq) {
-                    for (uint32_t j = 0; j < T; j++) {
-                        dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size());
-                        b.op(DeviceOp::kvq_store({vq_cache[kvl], v_proj, dh, kvq, S, j * kvd_loc + kvl * dh, j, j, 1}));
+                    const uint16_t k_rot = b.buffer((uint64_t)dh * TA);
+                    b.op(DeviceOp::rope(k_rot, k_proj, rope_cs, dh / 2, TA, sq * kvd_loc + kvl * dh, sq * 2 * dh, 0, 1, kvd_loc, 2 * dh));
+                    const uint32_t slab = seq_slab + kvl * S * dh; // k_cache.sliceColumns(kv_h*max_seq, ...)
+                    if (kvq) { // k_cache.storeColumn(pos + j, k_rot[:, j]) (llama_inference.zig:300-320)
+                        for (uint32_t j = 0; j < T; j++) {
+                            dyn_store(sq);
+                            b.op(DeviceOp::kvq_store({kq_cache[kvl], k_rot, dh, kvq, S, j * dh, j, j, 1}));
+                        }
+                    } else {
+                        dyn_store(sq);
+                        b.op(DeviceOp::slice_assign(k_cache, k_rot, dh, TA, slab, slab, 1, dh, 0, 1, dh, dh));
                     }
-                } else {
-                    dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size());
-                    b.op(DeviceOp::slice_assign(v_cache, v_proj, dh, T, slab, slab, 1, dh, kvl * dh, 1, kvd_loc, dh));
+                    if (!v_proj_done) {
+                        b.proj(v_proj, norm1, wv, T, kvd_loc, d, 0, d, 0, kvd_loc);
+                        v_proj_done = true;
+                    }
+                    if (kvq) {
+                        for (uint32_t j = 0; j < T; j++) {
+                            dyn_store(sq);
+                            b.op(DeviceOp::kvq_store({vq_cache[kvl], v_proj, dh, kvq, S, j * kvd_loc + kvl * dh, j, j, 1}));
+                        }
+                    } else {
+                        dyn_store(sq);
+                        b.op(DeviceOp::slice_assign(v_cache, v_proj, dh, TA, slab, slab, 1, dh, sq * kvd_loc + kvl * dh, 1, kvd_loc, dh));
+                    }
                 }
-            }
-            attn_out[hl] = b.buffer((uint64_t)dh * T);
-            if (kvq) { // attentionQuantized over the kv head's caches
-                zgml_op_attention_kvq a{};
-                a.dst = attn_out[hl], a.q = q_rot, a.k = kq_cache[kvl], a.v = vq_cache[kvl], a.mask = dp.buf_attn_mask, a.has_mask = 1;
-                a.d_head = dh, a.seq_q = T, a.seq_kv = S, a.scale = attn_scale, a.block_size = kvq, a.n_cols = S;
-                a.k_col_start = 0, a.v_col_start = 0, a.q_off = 0, a.q_cs = dh, a.dst_off = 0, a.dst_cs = dh;
-                a.mask_off = 0, a.mask_rs = 1, a.mask_cs = S;
+                attn_out[hl] = b.buffer((uint64_t)dh * TA);
+                if (kvq) { // attentionQuantized over the kv head's caches
+                    zgml_op_attention_kvq a{};
+                    a.dst = attn_out[hl], a.q = q_rot, a.k = kq_cache[kvl], a.v = vq_cache[kvl], a.mask = dp.buf_attn_mask, a.has_mask = 1;
+                    a.d_head = dh, a.seq_q = T, a.seq_kv = S, a.scale = attn_scale, a.block_size = kvq, a.n_cols = S;
+                    a.k_col_start = 0, a.v_col_start = 0, a.q_off = 0, a.q_cs = dh, a.dst_off = 0, a.dst_cs = dh;
+                    a.mask_off = 0, a.mask_rs = 1, a.mask_cs = S;
+                    dp.attention_op_indices.push_back((uint32_t)dp.program.ops.size());
+                    dp.attention_seq.push_back(sq);
+                    b.op(DeviceOp::attention_kvq(a));
+                    continue;
+                }
+                zgml_op_attention a{};
+                a.dst = attn_out[hl], a.q = q_rot, a.k = k_cache, a.v = v_cache, a.mask = dp.buf_attn_mask, a.has_mask = 1;
+                a.d_head = dh, a.seq_q = TA, a.seq_kv = S, a.scale = attn_scale;
+                a.q_off = 0, a.k_off = seq_slab + kvl * S * dh, a.v_off = seq_slab + kvl * S * dh, a.mask_off = sq * S, a.dst_off = 0;
+                a.q_rs = 1, a.q_cs = dh, a.k_rs = 1, a.k_cs = dh, a.v_rs = 1, a.v_cs = dh;
+                a.mask_rs = 1, a.mask_cs = S, a.dst_rs = 1, a.dst_cs = dh;
                 dp.attention_op_indices.push_back((uint32_t)dp.program.ops.size());
-                b.op(DeviceOp::attention_kvq(a));
-                continue;
+                dp.attention_seq.push_back(sq);
+                b.op(DeviceOp::attention(a));
             }
-            zgml_op_attention a{};
-            a.dst = attn_out[hl], a.q = q_rot, a.k = k_cache, a.v = v_cache, a.mask = dp.buf_attn_mask, a.has_mask = 1;
-            a.d_head = dh, a.seq_q = T, a.seq_kv = S, a.scale = attn_scale;
-            a.q_off = 0, a.k_off = kvl * S * dh, a.v_off = kvl * S * dh, a.mask_off = 0, a.dst_off = 0;
-            a.q_rs = 1, a.q_cs = dh, a.k_rs = 1, a.k_cs = dh, a.v_rs = 1, a.v_cs = dh;
-            a.mask_rs = 1, a.mask_cs = S, a.dst_rs = 1, a.dst_cs = dh;
-            dp.attention_op_indices.push_back((uint32_t)dp.program.ops.size());
-            b.op(DeviceOp::attention(a));
-        }
-        for (uint32_t hl = 0; hl < H_loc; hl++) { // sliceAssignRows(attn_out, h*d_head): patch_stride 0
-            const uint32_t row = (h0 + hl) * dh;
-            dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size());
-            b.op(DeviceOp::slice_assign(attn_buf, attn_out[hl], dh, T, 0, row, 1, d, 0, 1, dh, 0));
+            for (uint32_t hl = 0; hl < H_loc; hl++) { // sliceAssignRows(attn_out, h*d_head): patch_stride 0 (batched: into column sq)
+                const uint32_t row = sq * d + (h0 + hl) * dh;
+                dyn_store(sq);
+                b.op(DeviceOp::slice_assign(attn_buf, attn_out[hl], dh, TA, 0, row, 1, d, 0, 1, dh, 0));
+            }
         }
         if (sharded) dp.gather_points.push_back({(uint32_t)dp.program.ops.size(), attn_buf, 0, d_loc});
         const uint16_t attn_proj = b.buffer((uint64_t)d * T), after_attn = b.buffer((uint64_t)d * T);
@@ -498,11 +513,53 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
     dp.step_inputs.push_back(io(dp.buf_attn_mask, dp.attn_mask));
     for (uint32_t l = 0; l < c.n_layers; l++) dp.step_inputs.push_back(io(dp.buf_rope[l], dp.rope_leaf[l]));
     // Last-column logits: [vocab, T] column-major -> last col at offset (T-1)*vocab (llama_inference.zig:463-465)
-    dp.logits_host.assign(c.vocab_size, 0.f);
+    // (batched: every sequence's row, [vocab, B])
+    dp.logits_host.assign((size_t)c.vocab_size * (B ? B : 1), 0.f);
     backend::ProgramIO out_io = io(dp.buf_logits, dp.logits_host);
-    out_io.offset = (uint32_t)((size_t)(T - 1) * c.vocab_size * sizeof(float));
+    out_io.offset = B ? 0 : (uint32_t)((size_t)(T - 1) * c.vocab_size * sizeof(float));
     dp.step_outputs.push_back(out_io);
     return dpp;
+}
+
+std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, bool fused_elementwise, bool include_dead_f32, uint32_t token_len) {
+    return build_program(model, fused_elementwise, include_dead_f32, token_len, 0);
+}
+
+std::unique_ptr<DecodeProgram> build_batch_decode_program(const LlamaModel& model, uint32_t n_seqs, bool fused_elementwise, bool include_dead_f32,
+                                                          std::string* err) {
+    auto refuse = [&](const char* why) {
+        if (err) *err = why;
+        return std::unique_ptr<DecodeProgram>();
+    };
+    if (n_seqs < 1 || n_seqs > kMaxBatchSeqs) return refuse("build_batch_decode_program: n_seqs must be 1..32");
+    if (model.cfg.kv_quant_block != 0) return refuse("build_batch_decode_program: int8 KV caches (kv_quant_block != 0) under batching are out of scope");
+    if (model.cfg.shard_world != 1) return refuse("build_batch_decode_program: the row shard (shard_world != 1) under batching is out of scope");
+    return build_program(model, fused_elementwise, include_dead_f32, n_seqs, n_seqs);
+}
+
+// LlamaInferencePlan.execute steps 1-4, per sequence: column b of token_input / attn_mask / every rope leaf from (tokens[b], pos[b]),
+// and every dynamic op from the position of ITS sequence
+void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t* tokens, const uint32_t* pos) {
+    const LlamaConfig& c = model.cfg;
+    const uint32_t d = c.d_model, dh = c.d_head(), S = c.max_seq_len, B = dp.n_seqs;
+    const float ninf = -std::numeric_limits<float>::infinity();
+    for (uint32_t b = 0; b < B; b++) {
+        std::memcpy(dp.token_input.data() + (size_t)b * d, model.token_embed.data() + (size_t)tokens[b] * d, d * sizeof(float));
+        float* col = dp.attn_mask.data() + (size_t)b * S;
+        const uint32_t valid_upto = pos[b] + 1;
+        std::fill(col, col + valid_upto, 0.f);
+        if (valid_upto < S) std::fill(col + valid_upto, col + S, ninf);
+        for (auto& leaf : dp.rope_leaf) {
+            std::memcpy(leaf.data() + (size_t)b * 2 * dh, model.cos_table.data() + (size_t)pos[b] * dh, dh * sizeof(float));
+            std::memcpy(leaf.data() + (size_t)b * 2 * dh + dh, model.sin_table.data() + (size_t)pos[b] * dh, dh * sizeof(float));
+        }
+    }
+    for (size_t k = 0; k < dp.slice_assign_op_indices.size(); k++) {
+        auto& sa = dp.program.ops[dp.slice_assign_op_indices[k]].u.slice_assign;
+        if (sa.patch_stride != 0) sa.dst_offset = sa.dst_base_offset + pos[dp.slice_assign_seq[k]] * sa.patch_stride;
+    }
+    for (size_t k = 0; k < dp.attention_op_indices.size(); k++)
+        dp.program.ops[dp.attention_op_indices[k]].u.attention.seq_kv = pos[dp.attention_seq[k]] + 1;
 }
 
 void patch_step(const LlamaModel& model, DecodeProgram& dp, uint32_t token, uint32_t pos) { patch_tokens(model, dp, &token, pos); }

@@ -80,7 +80,8 @@ struct DecodeProgram {
     std::vector<std::vector<float>> rope_leaf; // per layer [2*d_head]
     std::vector<std::vector<float>> dead_f32;  // optional f32 master copies (never read by an op)
     std::vector<float> kv_zero;                 // zero initial KV (not uploaded: buffers start zeroed)
-    uint32_t token_len = 1; // tokens per execution (1 = decode plan, N = prefill plan)
+    uint32_t token_len = 1; // tokens per execution (1 = decode plan, N = prefill plan, B = batched decode plan)
+    uint32_t n_seqs = 0;    // batched decode plan (build_batch_decode_program): independent sequences per step, else 0
     uint16_t buf_token_input = 0, buf_attn_mask = 0, buf_logits = 0;
     std::vector<uint16_t> buf_rope, buf_k_cache, buf_v_cache;
     // every KV-cache buffer of the plan, in builder order, with its f32-element count: the consolidated f32 caches
@@ -93,6 +94,8 @@ struct DecodeProgram {
     };
     std::vector<KvBuffer> kv_buffers;
     std::vector<uint32_t> slice_assign_op_indices, attention_op_indices;
+    // per entry of the two lists above: the sequence the op belongs to (0 everywhere outside a batched plan)
+    std::vector<uint32_t> slice_assign_seq, attention_seq;
     std::vector<backend::ProgramIO> step_inputs, step_outputs;
     std::vector<float> logits_host;
     // collective points for the row-sharded variant: after op index `op_end` (exclusive), buffer
@@ -114,6 +117,20 @@ struct DecodeProgram {
 // (LlamaInferencePlan with token_len = N, src/llama_inference.zig:405-466; src/llm/device_prefill.zig).
 std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, bool fused_elementwise,
                                                     bool include_dead_f32, uint32_t token_len = 1);
+
+// Batched decode: one step advances n_seqs (1..kMaxBatchSeqs) independent sequences, each with its own KV slab, position and
+// token. Activations are [d, B] (norms, elementwise ops, projections and the LM head as in a token_len = B plan); token_input is
+// [d, B], attn_mask [max_seq, B] (one causal column per sequence), every rope leaf [2 * d_head, B]. The attention section is, per
+// sequence b, the token_len = 1 plan's op subsequence on column b: seq_len = 1 ropes of column b, K / V stores (patch_stride != 0)
+// into sequence b's slab, attention over that slab and mask column b, row stores into column b. Each layer's K / V buffer holds the
+// B slabs [d_head, max_seq * n_kv] back to back (kv_buffers: same order as the single-sequence plan, B times the elements), so a
+// single-sequence prefill plan hands sequence b its cache by a copy to offset b * slab. int8 KV caches and the row shard are out of
+// scope here: nullptr and a text in *err.
+constexpr uint32_t kMaxBatchSeqs = 32;
+std::unique_ptr<DecodeProgram> build_batch_decode_program(const LlamaModel& model, uint32_t n_seqs, bool fused_elementwise, bool include_dead_f32,
+                                                          std::string* err = nullptr);
+// tokens[B], pos[B]: the B embedding rows, mask columns and rope columns, and each dynamic op from its own sequence's position
+void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t* tokens, const uint32_t* pos);
 
 // Patch the plan's host leaves for (token, pos): embedding row, causal mask column, RoPE row
 // (llama_smollm_bench.zig:299-309), then the dynamic op fields.

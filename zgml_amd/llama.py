@@ -71,6 +71,15 @@ def load_host() -> C.CDLL:
         lib.zh_session_step.argtypes, lib.zh_session_step.restype = [vp, u32, u32, vp], C.c_int64
         lib.zh_session_decode.argtypes, lib.zh_session_decode.restype = [vp, u32, u32, u32, vp], C.c_double
         lib.zh_session_set_refresh_dynamic.argtypes, lib.zh_session_set_refresh_dynamic.restype = [vp, vp], None
+        lib.zh_model_create_batch.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.c_int, u32, C.c_char_p, u64]
+        lib.zh_model_create_batch.restype = vp
+        lib.zh_model_create_batch_like.argtypes = [vp, C.c_int, C.c_int, u32, C.c_char_p, u64]
+        lib.zh_model_create_batch_like.restype = vp
+        lib.zh_model_n_seqs.argtypes, lib.zh_model_n_seqs.restype = [vp], u32
+        lib.zh_model_patch_batch.argtypes, lib.zh_model_patch_batch.restype = [vp, vp, vp], None
+        lib.zh_model_dyn_sequences.argtypes, lib.zh_model_dyn_sequences.restype = [vp, C.POINTER(u32), C.POINTER(u32), u64], u64
+        lib.zh_session_set_refresh_dynamic_batch.argtypes, lib.zh_session_set_refresh_dynamic_batch.restype = [vp, vp], None
+        lib.zh_session_step_batch.argtypes, lib.zh_session_step_batch.restype = [vp, vp, vp, vp, vp], C.c_int
         lib.zh_argmax.argtypes, lib.zh_argmax.restype = [vp, u32], u32
         lib.zh_argmax_reference.argtypes, lib.zh_argmax_reference.restype = [vp, u32], u32
         _lib = lib
@@ -97,11 +106,14 @@ def hip_backend_fns(backend) -> BackendFns:
 class Model:
     """Synthetic LLaMA weights + the decode DeviceProgram (`DeviceInference.init`, token_len = 1)."""
 
+    n_seqs = 0  # (BatchModel: sequences per step)
+
     def __init__(self, cfg: Config, weight_kind: int = Q4_0, fused_elementwise: bool = True,
                  include_dead_f32: bool = False, threads: int = 8, token_len: int = 1):
         self.lib = load_host()
         self.cfg = cfg
         self.token_len = token_len
+        self.build_args = (weight_kind, fused_elementwise, include_dead_f32, threads)
         self.ptr = self.lib.zh_model_create_ex(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32),
                                                threads, token_len)
         if not self.ptr:
@@ -150,6 +162,118 @@ class Model:
         n = C.c_uint64()
         b = self.lib.zh_model_quant_bytes(self.ptr, C.byref(n))
         return int(b), int(n.value)
+
+
+class BatchModel(Model):
+    """Synthetic weights + the BATCHED decode program (`build_batch_decode_program`): one step advances `n_seqs` independent
+    sequences, each with its own KV slab, position and token. ValueError with the builder's text for what it refuses."""
+
+    def __init__(self, cfg: Config, n_seqs: int, weight_kind: int = Q4_0, fused_elementwise: bool = True,
+                 include_dead_f32: bool = False, threads: int = 8, like: Model = None):
+        """`like`: build the batched program over that model's weights (shared, not generated again; cfg / weight_kind come from it)."""
+        self.lib = load_host()
+        self.cfg = like.cfg if like else cfg
+        self.n_seqs = self.token_len = n_seqs
+        err = C.create_string_buffer(256)
+        if like:
+            self.build_args = like.build_args
+            self.ptr = self.lib.zh_model_create_batch_like(like.ptr, int(like.build_args[1]), int(like.build_args[2]), n_seqs, err, len(err))
+        else:
+            self.build_args = (weight_kind, fused_elementwise, include_dead_f32, threads)
+            self.ptr = self.lib.zh_model_create_batch(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32), threads,
+                                                      n_seqs, err, len(err))
+        if not self.ptr:
+            raise ValueError(err.value.decode())
+
+    def patch_batch(self, tokens, positions) -> None:
+        t, p = np.ascontiguousarray(tokens, dtype=np.uint32), np.ascontiguousarray(positions, dtype=np.uint32)
+        assert t.size == self.n_seqs and p.size == self.n_seqs
+        self.lib.zh_model_patch_batch(self.ptr, t.ctypes.data, p.ctypes.data)
+
+    def dyn_sequences(self):
+        """(op indices, sequence of each): every op with a position-dependent field (zgml_hip_program_set_sequences)."""
+        n = self.lib.zh_model_dyn_sequences(self.ptr, None, None, 0)
+        idx, seq = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))()
+        self.lib.zh_model_dyn_sequences(self.ptr, idx, seq, n)
+        return np.array(idx[:n], np.uint32), np.array(seq[:n], np.uint32)
+
+    def kv_slab_elems(self) -> int:
+        """f32 elements of one sequence's slab of a K or V buffer (= the single-sequence plan's whole buffer)."""
+        return self.cfg.d_head * self.cfg.max_seq_len * self.cfg.n_kv_heads
+
+
+class BatchSession:
+    """Batched decode: `step` advances `n_seqs` sequences by one token each through the vtable (refresh + execute). `model` is a
+    BatchModel of `n_seqs` sequences, or any other Model: the session then builds the batched program over that model's weights
+    (shared, so the model must outlive the session). On the HIP backend the program is compiled with
+    ZGML_HIP_OPT_SMALL_M_MATVEC on (`small_m_matvec=False`: the tile kernels; an int: the option's value, e.g. 8 = the row kernel up
+    to its widest form) and its sequences are declared; the oracle
+    takes the same program unchanged."""
+
+    def __init__(self, model: Model, fns: BackendFns, n_seqs: int, small_m_matvec=True):
+        self.lib, self.fns, self.n_seqs = model.lib, fns, n_seqs
+        self._own_model = not (isinstance(model, BatchModel) and model.n_seqs == n_seqs)
+        self.model = BatchModel(model.cfg, n_seqs, like=model) if self._own_model else model
+        self.is_hip = capi.HIP_LIB_PATH.exists() and fns.compile_program == _fn_addr(capi.load_hip(), "zgml_hip_compile_program")
+        hip = capi.load_hip() if self.is_hip else None
+        if self.is_hip:  # (read at compile_program; other programs of the context keep the default)
+            hip.zgml_hip_set_option(fns.ctx, capi.OPT_SMALL_M_MATVEC, int(small_m_matvec))
+        try:
+            self.ptr = self.lib.zh_session_create(self.model.ptr, C.byref(fns))
+        finally:
+            if self.is_hip:
+                hip.zgml_hip_set_option(fns.ctx, capi.OPT_SMALL_M_MATVEC, 0)
+        if not self.ptr:
+            raise RuntimeError("compile_program failed")
+        if self.is_hip:
+            idx, seq = self.model.dyn_sequences()
+            rc = hip.zgml_hip_program_set_sequences(fns.ctx, self.handle, n_seqs, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                    seq.ctypes.data_as(C.POINTER(C.c_uint32)), idx.size)
+            if rc != 0:
+                raise RuntimeError("set_sequences: " + (hip.zgml_hip_last_error(fns.ctx) or b"").decode())
+
+    @property
+    def handle(self):
+        return self.lib.zh_session_handle(self.ptr)
+
+    def use_dynamic_refresh(self, on: bool = True) -> None:
+        """Per step hand over (slice_pos[B], seq_kv[B]) through zgml_hip_refresh_dynamic_batch instead of the whole op list."""
+        self.lib.zh_session_set_refresh_dynamic_batch(self.ptr, _fn_addr(capi.load_hip(), "zgml_hip_refresh_dynamic_batch") if on else None)
+
+    def step(self, tokens, positions):
+        """-> (next_tokens[B], logits[B, vocab])"""
+        t, p = np.ascontiguousarray(tokens, dtype=np.uint32), np.ascontiguousarray(positions, dtype=np.uint32)
+        assert t.size == self.n_seqs and p.size == self.n_seqs
+        logits = np.zeros((self.n_seqs, self.model.cfg.vocab_size), np.float32)
+        nxt = np.zeros(self.n_seqs, np.int64)
+        if self.lib.zh_session_step_batch(self.ptr, t.ctypes.data, p.ctypes.data, logits.ctypes.data, nxt.ctypes.data) != 0:
+            raise ValueError("step: token or position out of range")
+        return nxt, logits
+
+    # ── device-resident loop (HIP backend only; include/zgml_hip.h zgml_hip_resident_decode_batch) ──
+    def resident_setup(self, backend) -> None:
+        Session.resident_setup(self, backend)
+
+    def resident_decode_batch(self, first_tokens, start_pos, n_steps) -> np.ndarray:
+        """-> tokens[B, max(n_steps)]; row b holds n_steps[b] tokens, then -1."""
+        u32p = C.POINTER(C.c_uint32)
+        t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_steps, dtype=np.uint32), (self.n_seqs,)))
+        assert t.size == self.n_seqs and p.size == self.n_seqs
+        max_steps = int(n.max()) if n.size else 0
+        toks = np.full((self.n_seqs, max(1, max_steps)), -1, np.int64)
+        rc = capi.load_hip().zgml_hip_resident_decode_batch(self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p),
+                                                            n.ctypes.data_as(u32p), max_steps, toks.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("resident_decode_batch: " + self._backend.last_error())
+        return toks[:, :max_steps]
+
+    def close(self):
+        if self.ptr:
+            self.lib.zh_session_free(self.ptr)
+            self.ptr = None
+        if self._own_model:
+            self.model.close()
 
 
 class Session:
