@@ -32,6 +32,8 @@ def probe():
     lib.zs_schedule.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, u64, vp]
     lib.zs_schedule.restype = C.c_int
     lib.zs_overlap_matrix.argtypes, lib.zs_overlap_matrix.restype = [vp, u64, vp], None
+    lib.zs_dynamic_field_in_bounds.argtypes, lib.zs_dynamic_field_in_bounds.restype = [vp, u64, vp, u64, vp, vp, vp], None
+    lib.zs_dyn_field.argtypes, lib.zs_dyn_field.restype = [vp, C.c_uint32, vp], None
     _lib = lib
     return lib
 
@@ -204,6 +206,18 @@ def test_random_programs_have_parallel_levels():
 
 # ── 4. dynamic_fields_in_bounds ────────────────────────────────────────────────────────────────────────────────────────
 
+def in_bounds_per_op(ops, sizes, refreshed, seq_kv_bound=None):
+    """dynamic_field_in_bounds for every op of `refreshed` against the schedule of `ops`"""
+    arr, keep = ops_to_c(ops)
+    ref, keep2 = ops_to_c(refreshed)
+    sz = np.array(sizes, np.uint64)
+    bound = np.array(seq_kv_bound, np.uint32) if seq_kv_bound is not None else None
+    out = np.zeros(len(ops), np.uint8)
+    probe().zs_dynamic_field_in_bounds(C.addressof(arr), len(ops), sz.ctypes.data, len(sizes), bound.ctypes.data if bound is not None else None,
+                                       C.addressof(ref), out.ctypes.data)
+    return [bool(v) for v in out]
+
+
 def test_dynamic_fields_in_bounds_at_the_edges():
     from zgml_amd import DeviceOp
     dh, cols = 4, 8
@@ -213,16 +227,69 @@ def test_dynamic_fields_in_bounds_at_the_edges():
     att = DeviceOp.attention(2, 1, 0, 0, 0, False, dh, 1, 3, 0.5, 0, 0, 0, 0, 0, 1, dh, 1, dh, 1, dh, 1, 1, 1, dh)
     ops, sizes = [k0, k1, att], [2 * dh * cols + 4, dh, dh]
     last = dh * cols - dh
-    for refreshed, want in (([k0.with_(dst_offset=last), k1, att], True),            # the last column of slab 0
-                            ([k0.with_(dst_offset=last + 1), k1, att], False),       # one element past it
-                            ([k0, k1.with_(dst_offset=2 * dh * cols), att], True),   # slab 1 runs to the buffer's end
-                            ([k0, k1.with_(dst_offset=2 * dh * cols + 1), att], False),
-                            ([k0, k1, att.with_(seq_kv=3)], True),
-                            ([k0, k1, att.with_(seq_kv=4)], False)):
+    # (refreshed op list, the whole list is in bounds, the op that moved): one below, at and one past each edge
+    for refreshed, want, moved in (([k0.with_(dst_offset=last - 1), k1, att], True, 0),
+                                   ([k0.with_(dst_offset=last), k1, att], True, 0),                # the last column of slab 0
+                                   ([k0.with_(dst_offset=last + 1), k1, att], False, 0),           # one element past it
+                                   ([k0, k1.with_(dst_offset=dh * cols - 1), att], False, 1),      # one below slab 1's base
+                                   ([k0, k1.with_(dst_offset=2 * dh * cols - 1), att], True, 1),
+                                   ([k0, k1.with_(dst_offset=2 * dh * cols), att], True, 1),       # slab 1 runs to the buffer's end
+                                   ([k0, k1.with_(dst_offset=2 * dh * cols + 1), att], False, 1),
+                                   ([k0, k1, att.with_(seq_kv=2)], True, 2),
+                                   ([k0, k1, att.with_(seq_kv=3)], True, 2),
+                                   ([k0, k1, att.with_(seq_kv=4)], False, 2)):
         _, _, ok = schedule(ops, sizes, refreshed=refreshed)
         assert ok is want, refreshed
+        per_op = in_bounds_per_op(ops, sizes, refreshed)  # the per-op function: only the op that moved can be out, and all() is the list's answer
+        assert per_op == [want if i == moved else True for i in range(3)], (refreshed, per_op)
     # with a seq_kv bound above the op's value, the bound is the limit
-    _, _, ok = schedule(ops, sizes, seq_kv_bound=[0, 0, 6], refreshed=[k0, k1, att.with_(seq_kv=6)])
-    assert ok is True
-    _, _, ok = schedule(ops, sizes, seq_kv_bound=[0, 0, 6], refreshed=[k0, k1, att.with_(seq_kv=7)])
-    assert ok is False
+    for kv, want in ((5, True), (6, True), (7, False)):
+        refreshed = [k0, k1, att.with_(seq_kv=kv)]
+        _, _, ok = schedule(ops, sizes, seq_kv_bound=[0, 0, 6], refreshed=refreshed)
+        assert ok is want
+        assert in_bounds_per_op(ops, sizes, refreshed, seq_kv_bound=[0, 0, 6]) == [True, True, want]
+
+
+# ── 5. dyn_field: THE definition of an op's position-dependent word ────────────────────────────────────────────────────
+
+def _dyn_field(op, poke=0xABCD1234):
+    """(role, moves, base, stride, has_word, [at(0,1), at(0,4), at(5,1), at(5,4)], struct bytes before, after the poke, the C op)"""
+    arr, keep = ops_to_c([op])
+    before = bytes(arr[0])
+    out = np.zeros(10, np.uint32)
+    probe().zs_dyn_field(C.addressof(arr), poke, out.ctypes.data)
+    assert out[9] == 1  # the const overload names the same word
+    return int(out[0]), bool(out[1]), int(out[2]), int(out[3]), bool(out[4]), [int(v) for v in out[5:9]], before, bytes(arr[0]), arr[0]
+
+
+@pytest.mark.parametrize("kind", PC.KINDS)
+def test_dyn_field_of_every_kind(kind):
+    """Every DeviceOp kind (the generator's sixteen variants cover the twelve reference kinds and the two quantised-KV extensions):
+    only the two stores and the two attentions have a word; it aliases dst_offset / col / seq_kv; a store moves iff its
+    patch_stride is not 0; at(pos, T) is base + pos * stride for a store and pos + T for an attention."""
+    NONE, OFFSET, SEQ_KV = 0, 1, 2
+    poke = 0xABCD1234
+    op, _ = PC.random_op(np.random.default_rng(PC.KINDS.index(kind)), kind, 4, 128)
+    variants = [op]
+    if op.kind in ("slice_assign", "kvq_store"):  # stride 0 and stride non-zero, whatever the generator drew
+        base = "dst_base_offset" if op.kind == "slice_assign" else "col_base"
+        variants = [op.with_(patch_stride=0, **{base: 7}), op.with_(patch_stride=3, **{base: 7}), op.with_(patch_stride=16, **{base: 0})]
+    for v in variants:
+        role, moves, base, stride, has_word, at, before, after, c = _dyn_field(v, poke)
+        if v.kind in ("slice_assign", "kvq_store"):
+            b = v.dst_base_offset if v.kind == "slice_assign" else v.col_base
+            assert (role, has_word, base, stride) == (OFFSET, True, b, v.patch_stride), v
+            assert moves is (v.patch_stride != 0), v
+            assert at == [b, b, b + 5 * v.patch_stride, b + 5 * v.patch_stride], v  # T plays no part
+            field = c.u.slice_assign.dst_offset if v.kind == "slice_assign" else c.u.kvq_store.col
+        elif v.kind in ("attention", "attention_kvq"):
+            assert (role, has_word, base, stride, moves) == (SEQ_KV, True, 0, 0, True), v
+            assert at == [1, 4, 6, 9], v
+            field = c.u.attention.seq_kv if v.kind == "attention" else c.u.attention_kvq.seq_kv
+        else:
+            assert (role, has_word, base, stride, moves) == (NONE, False, 0, 0, False), v
+            assert after == before, v  # nothing to write through
+            continue
+        assert field == poke, v  # written through the word, read from the field
+        changed = [i for i in range(len(before)) if before[i] != after[i]]
+        assert changed and max(changed) - min(changed) < 4, (v, changed)  # ... and from nothing else

@@ -182,8 +182,6 @@ __global__ void gather_words_wide_kernel(const IoTableDev* table, uint32_t* stag
 
 uint32_t io_grid_y(uint32_t max_row_words) { return std::max<uint32_t>(1, std::min<uint32_t>(64, max_row_words / 1024)); } // workgroups per transfer row
 
-void free_resident_graph(zgml_hip_program* p); // below (zgml_resident is defined there)
-
 void free_io_graph(zgml_hip_program* p) {
     if (p->io_graph_exec) hipGraphExecDestroy(p->io_graph_exec);
     if (p->io_graph) hipGraphDestroy(p->io_graph);
@@ -318,42 +316,22 @@ bool prepare_io(zgml_hip_program* p, IoPlan& plan, const zgml_program_io* ios, u
 }
 
 
-void set_dyn_from_ops(zgml_hip_program* p) {
-    for (size_t i = 0; i < p->ops.size(); i++) {
-        uint32_t v = 0;
-        if (p->ops[i].kind == ZGML_DOP_SLICE_ASSIGN) v = p->ops[i].u.slice_assign.dst_offset;
-        if (p->ops[i].kind == ZGML_DOP_ATTENTION) v = p->ops[i].u.attention.seq_kv;
-        if (p->ops[i].kind == ZGML_DOP_KVQ_STORE) v = p->ops[i].u.kvq_store.col;
-        if (p->ops[i].kind == ZGML_DOP_ATTENTION_KVQ) v = p->ops[i].u.attention_kvq.seq_kv;
-        if (p->dyn_host[i] != v) {
-            p->dyn_host[i] = v;
-            p->dyn_dirty = true;
-        }
-    }
+void note_seq_kv_bounds(zgml_hip_program* p) {
+    p->seq_kv_bound.resize(p->ops.size(), 0);
+    for (size_t i = 0; i < p->ops.size(); i++)
+        if (const DynField f = dyn_field(p->ops[i]); f.role == DynField::SeqKv) p->seq_kv_bound[i] = std::max(p->seq_kv_bound[i], *f.word);
 }
 
 // copy ops (and their fused steps) into program-owned storage
-void note_seq_kv_bounds(zgml_hip_program* p) {
-    p->seq_kv_bound.resize(p->ops.size(), 0);
-    for (size_t i = 0; i < p->ops.size(); i++) {
-        uint32_t v = 0;
-        if (p->ops[i].kind == ZGML_DOP_ATTENTION) v = p->ops[i].u.attention.seq_kv;
-        if (p->ops[i].kind == ZGML_DOP_ATTENTION_KVQ) v = p->ops[i].u.attention_kvq.seq_kv;
-        p->seq_kv_bound[i] = std::max(p->seq_kv_bound[i], v);
-    }
-}
-
 void own_ops(zgml_hip_program* p, const zgml_device_op* ops, uint64_t n_ops) {
     // a static refresh may change an op's kind: bounds of ops that are no longer the same attention start over
     if (p->seq_kv_bound.size() == n_ops && p->ops.size() == n_ops)
         for (uint64_t i = 0; i < n_ops; i++)
             if (p->ops[i].kind != ops[i].kind) p->seq_kv_bound[i] = 0;
     p->ops.assign(ops, ops + n_ops);
-    p->dyn_ops.clear(); // the ops with a dynamic field (what a per-token refresh touches: zgml_hip_refresh_dynamic)
+    p->dyn_ops.clear(); // the ops whose dynamic field moves (what a per-token refresh touches: zgml_hip_refresh_dynamic)
     for (uint64_t i = 0; i < n_ops; i++)
-        if ((ops[i].kind == ZGML_DOP_SLICE_ASSIGN && ops[i].u.slice_assign.patch_stride != 0) || ops[i].kind == ZGML_DOP_ATTENTION ||
-            (ops[i].kind == ZGML_DOP_KVQ_STORE && ops[i].u.kvq_store.patch_stride != 0) || ops[i].kind == ZGML_DOP_ATTENTION_KVQ)
-            p->dyn_ops.push_back((uint32_t)i);
+        if (dyn_field(ops[i]).moves()) p->dyn_ops.push_back((uint32_t)i);
     p->steps.assign(n_ops, {});
     for (uint64_t i = 0; i < n_ops; i++) {
         if (ops[i].kind == ZGML_DOP_FUSED_ELEMENTWISE) {
@@ -365,48 +343,86 @@ void own_ops(zgml_hip_program* p, const zgml_device_op* ops, uint64_t n_ops) {
     note_seq_kv_bounds(p);
 }
 
-// true when the static part of two ops is identical (dynamic fields and step pointers ignored). No copies: the bytes of the
-// ACTIVE union member (the rest may be uninitialised padding) are compared around the member's dynamic field — this runs once per
-// op per token on the drop-in path (refresh_program is called before every execute: src/device_inference.zig:260-263).
-bool same_static(const zgml_device_op& a, const zgml_device_op& b) {
-    if (a.kind != b.kind) return false;
-    auto except = [](const void* pa, const void* pb, size_t len, size_t off, size_t flen) { // equal but for [off, off + flen)
-        const char *x = (const char*)pa, *y = (const char*)pb;
-        return memcmp(x, y, off) == 0 && memcmp(x + off + flen, y + off + flen, len - off - flen) == 0;
-    };
-    switch (a.kind) {
-        // a store with patch_stride == 0 is static: its offset / column is not on p->dyn_ops, so a change must rebuild the plan
-        case ZGML_DOP_SLICE_ASSIGN:
-            if (a.u.slice_assign.patch_stride == 0 || b.u.slice_assign.patch_stride == 0)
-                return memcmp(&a.u.slice_assign, &b.u.slice_assign, sizeof(a.u.slice_assign)) == 0;
-            return except(&a.u.slice_assign, &b.u.slice_assign, sizeof(a.u.slice_assign), offsetof(zgml_op_slice_assign, dst_offset), sizeof(uint32_t));
-        case ZGML_DOP_ATTENTION: return except(&a.u.attention, &b.u.attention, sizeof(a.u.attention), offsetof(zgml_op_attention, seq_kv), sizeof(uint32_t));
-        case ZGML_DOP_KVQ_STORE:
-            if (a.u.kvq_store.patch_stride == 0 || b.u.kvq_store.patch_stride == 0)
-                return memcmp(&a.u.kvq_store, &b.u.kvq_store, sizeof(a.u.kvq_store)) == 0;
-            return except(&a.u.kvq_store, &b.u.kvq_store, sizeof(a.u.kvq_store), offsetof(zgml_op_kvq_store, col), sizeof(uint32_t));
-        case ZGML_DOP_ATTENTION_KVQ:
-            return except(&a.u.attention_kvq, &b.u.attention_kvq, sizeof(a.u.attention_kvq), offsetof(zgml_op_attention_kvq, seq_kv), sizeof(uint32_t));
-        case ZGML_DOP_FUSED_ELEMENTWISE: {
-            const auto &fa = a.u.fused_elementwise, &fb = b.u.fused_elementwise;
-            if (fa.n_steps != fb.n_steps) return false;
-            for (uint32_t s = 0; s < fa.n_steps; s++)
-                if (fa.steps[s].op != fb.steps[s].op || fa.steps[s].is_swapped != fb.steps[s].is_swapped ||
-                    fa.steps[s].secondary_buf != fb.steps[s].secondary_buf || fa.steps[s].secondary_offset != fb.steps[s].secondary_offset)
-                    return false;
-            return except(&fa, &fb, sizeof(fa), offsetof(zgml_op_fused_elementwise, steps), sizeof(fa.steps));
-        }
-        case ZGML_DOP_ELEMENTWISE: return memcmp(&a.u.elementwise, &b.u.elementwise, sizeof(a.u.elementwise)) == 0;
-        case ZGML_DOP_MATMUL: return memcmp(&a.u.matmul, &b.u.matmul, sizeof(a.u.matmul)) == 0;
-        case ZGML_DOP_QMATMUL: return memcmp(&a.u.qmatmul, &b.u.qmatmul, sizeof(a.u.qmatmul)) == 0;
-        case ZGML_DOP_SOFTMAX: return memcmp(&a.u.softmax, &b.u.softmax, sizeof(a.u.softmax)) == 0;
-        case ZGML_DOP_LAYERNORM: return memcmp(&a.u.layernorm, &b.u.layernorm, sizeof(a.u.layernorm)) == 0;
-        case ZGML_DOP_RMSNORM: return memcmp(&a.u.rmsnorm, &b.u.rmsnorm, sizeof(a.u.rmsnorm)) == 0;
-        case ZGML_DOP_REDUCE: return memcmp(&a.u.reduce, &b.u.reduce, sizeof(a.u.reduce)) == 0;
-        case ZGML_DOP_REPEAT: return memcmp(&a.u.repeat, &b.u.repeat, sizeof(a.u.repeat)) == 0;
-        case ZGML_DOP_ROPE: return memcmp(&a.u.rope, &b.u.rope, sizeof(a.u.rope)) == 0;
-        default: return false;
+// bytes of the ACTIVE union member of an op (the rest of the union may be uninitialised padding); 0: unknown kind
+size_t payload_bytes(const zgml_device_op& o) {
+    switch (o.kind) {
+        case ZGML_DOP_ELEMENTWISE: return sizeof(o.u.elementwise);
+        case ZGML_DOP_MATMUL: return sizeof(o.u.matmul);
+        case ZGML_DOP_QMATMUL: return sizeof(o.u.qmatmul);
+        case ZGML_DOP_SOFTMAX:
+        case ZGML_DOP_LAYERNORM:
+        case ZGML_DOP_RMSNORM: return sizeof(o.u.rmsnorm);
+        case ZGML_DOP_REDUCE: return sizeof(o.u.reduce);
+        case ZGML_DOP_REPEAT: return sizeof(o.u.repeat);
+        case ZGML_DOP_SLICE_ASSIGN: return sizeof(o.u.slice_assign);
+        case ZGML_DOP_ROPE: return sizeof(o.u.rope);
+        case ZGML_DOP_ATTENTION: return sizeof(o.u.attention);
+        case ZGML_DOP_FUSED_ELEMENTWISE: return sizeof(o.u.fused_elementwise);
+        case ZGML_DOP_KVQ_STORE: return sizeof(o.u.kvq_store);
+        case ZGML_DOP_ATTENTION_KVQ: return sizeof(o.u.attention_kvq);
+        default: return 0;
     }
+}
+
+// true when the static part of two ops is identical (dynamic fields and step pointers ignored). No copies: the bytes of the
+// active union member are compared around the member's dynamic field — this runs once per op per token on the drop-in path
+// (refresh_program is called before every execute: src/device_inference.zig:260-263).
+bool same_static(const zgml_device_op& a, const zgml_device_op& b) {
+    const size_t len = payload_bytes(a);
+    if (a.kind != b.kind || !len) return false;
+    const char *x = (const char*)&a.u, *y = (const char*)&b.u;
+    size_t off = len, flen = 0; // equal but for [off, off + flen)
+    // a store with patch_stride == 0 is static: its offset / column is not on p->dyn_ops, so a change must rebuild the plan
+    if (const DynField fa = dyn_field(a); fa.moves() && dyn_field(b).moves()) off = (size_t)((const char*)fa.word - x), flen = sizeof(uint32_t);
+    if (a.kind == ZGML_DOP_FUSED_ELEMENTWISE) {
+        const auto &fa = a.u.fused_elementwise, &fb = b.u.fused_elementwise;
+        if (fa.n_steps != fb.n_steps) return false;
+        for (uint32_t s = 0; s < fa.n_steps; s++)
+            if (fa.steps[s].op != fb.steps[s].op || fa.steps[s].is_swapped != fb.steps[s].is_swapped ||
+                fa.steps[s].secondary_buf != fb.steps[s].secondary_buf || fa.steps[s].secondary_offset != fb.steps[s].secondary_offset)
+                return false;
+        off = offsetof(zgml_op_fused_elementwise, steps), flen = sizeof(fa.steps);
+    }
+    return memcmp(x, y, off) == 0 && memcmp(x + off + flen, y + off + flen, len - off - flen) == 0;
+}
+
+} // namespace
+
+namespace zgml_rt {
+
+// the host mirror of the dynamic block from the ops: the word of every op that has one — the stores with patch_stride 0 included,
+// the "static dyn words" the resident loops re-upload from here — and 0 for the rest
+void set_dyn_from_ops(zgml_hip_program* p) {
+    for (size_t i = 0; i < p->ops.size(); i++) {
+        const DynField f = dyn_field(p->ops[i]);
+        const uint32_t v = f.word ? *f.word : 0;
+        if (p->dyn_host[i] != v) p->dyn_host[i] = v, p->dyn_dirty = true;
+    }
+}
+
+// rebuild the plan, dropping every graph captured from the old one, when it is dirty or the context's fuse epoch moved
+void ensure_plan(zgml_hip_program* p) {
+    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
+        free_graph(p);
+        build_plan(p);
+    }
+}
+
+// `work` captured from stream s (thread-local mode) into *g_out and instantiated into *e_out; `tag` names the graph for
+// ZGML_HIP_GRAPH_DUMP (nullptr: not dumped). false, reported on ctx and with nothing left behind, when any step fails.
+bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, hipGraph_t* g_out, hipGraphExec_t* e_out) {
+    hipGraph_t g = nullptr;
+    if (!CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) return false;
+    work();
+    if (!CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) || !g) return false;
+    if (tag) dump_graph(g, tag);
+    hipGraphExec_t ge = nullptr;
+    if (!CTX_CHECK(ctx, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0))) {
+        hipGraphDestroy(g);
+        return false;
+    }
+    *g_out = g, *e_out = ge;
+    return true;
 }
 
 void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count) {
@@ -439,10 +455,7 @@ void flush_dyn(zgml_hip_program* p) {
 // enqueue the whole program on the context stream (graph replay when enabled)
 void enqueue(zgml_hip_program* p) {
     zgml_hip_ctx* ctx = p->ctx;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
+    ensure_plan(p);
     flush_dyn(p);
     if (ctx->opt_profile) {
         hipEvent_t e0, e1;
@@ -478,18 +491,7 @@ void enqueue(zgml_hip_program* p) {
             if (split_env == 0) head = p->plan.size();
             if (split_env > 0) head = std::min<size_t>((size_t)split_env, p->plan.size());
             auto capture = [&](size_t first, size_t count, hipGraph_t* g_out, hipGraphExec_t* e_out, const char* tag) {
-                hipGraph_t g = nullptr;
-                if (!CTX_CHECK(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal))) return false;
-                run_plan(p, ctx->stream, first, count);
-                if (!CTX_CHECK(ctx, hipStreamEndCapture(ctx->stream, &g)) || !g) return false;
-                dump_graph(g, tag);
-                hipGraphExec_t ge = nullptr;
-                if (!CTX_CHECK(ctx, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0))) {
-                    hipGraphDestroy(g);
-                    return false;
-                }
-                *g_out = g, *e_out = ge;
-                return true;
+                return capture_graph(ctx, ctx->stream, tag, [&] { run_plan(p, ctx->stream, first, count); }, g_out, e_out);
             };
             if (capture(0, head, &p->graph, &p->graph_exec, "program") && head < p->plan.size() &&
                 !capture(head, p->plan.size() - head, &p->graph_tail, &p->graph_tail_exec, "program-tail")) {
@@ -505,6 +507,15 @@ void enqueue(zgml_hip_program* p) {
     }
     run_plan(p, ctx->stream, 0, p->plan.size());
 }
+
+// a caller about to touch a buffer some hoisted (run-once) repeat read or wrote: back to running every repeat in the plan
+void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx) {
+    if (p->hoist_ok && buf_idx < p->hoist_guard.size() && p->hoist_guard[buf_idx]) p->hoist_ok = false, p->plan_dirty = true;
+}
+
+} // namespace zgml_rt
+
+namespace {
 
 uint64_t now_ns() {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -522,71 +533,30 @@ bool grow(zgml_hip_ctx* ctx, float** ptr, uint64_t* cap, uint64_t elems) {
     return true;
 }
 
-// ── device-resident LLaMA decode (extension; see include/zgml_hip.h) ─────────────────────────
-} // namespace
-struct zgml_resident {
-    float *embed = nullptr, *cos = nullptr, *sin = nullptr;
-    uint32_t vocab = 0, d = 0, max_seq = 0, dh = 0, n_rope = 0;
-    float *tok_in = nullptr, *mask = nullptr, *logits = nullptr;
-    float** rope_bufs = nullptr;   // device array of n_rope pointers
-    uint32_t* dyn_kind = nullptr;  // per op: 0 static, 1 slice_assign(base,stride), 2 attention
-    uint32_t* dyn_base = nullptr;
-    uint32_t* dyn_stride = nullptr;
-    uint32_t* state = nullptr;     // [0] token, [1] pos, [2] produced count
-    uint32_t token_len = 1;        // T of the plan (token_input holds T rows): 1 = decode, > 1 = prefill chunk
-    uint32_t* tok_dev = nullptr;   // prefill: the chunk's T token ids (the only per-chunk host -> device traffic)
-    int64_t* tokens = nullptr;     // produced tokens (device)
-    uint32_t tokens_cap = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    hipGraph_t graph_multi = nullptr; // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
-    hipGraphExec_t graph_multi_exec = nullptr;
-    uint32_t multi_n = 0;
-    // batched program (zgml_hip_program_set_sequences): per-sequence device state (kernels.h: ResidentBatchPrepArgs), the sequence of
-    // every dynamic op, the pick's scratch (n_seqs rows of partial maxima) and the produced tokens [n_seqs][bcap]
-    uint32_t n_seqs = 0;
-    uint32_t* bstate = nullptr;
-    uint32_t* dyn_seq = nullptr;
-    float* bval = nullptr;
-    int64_t* bidx = nullptr;
-    int64_t* btokens = nullptr;
-    uint64_t btokens_cap = 0; // elements
-};
-using Resident = zgml_resident;
-namespace {
-
-void free_resident_graph(zgml_hip_program* p) {
-    Resident* r = p->resident;
-    if (!r) return;
-    if (r->graph_exec) hipGraphExecDestroy(r->graph_exec);
-    if (r->graph) hipGraphDestroy(r->graph);
-    r->graph_exec = nullptr, r->graph = nullptr;
-    if (r->graph_multi_exec) hipGraphExecDestroy(r->graph_multi_exec);
-    if (r->graph_multi) hipGraphDestroy(r->graph_multi);
-    r->graph_multi_exec = nullptr, r->graph_multi = nullptr, r->multi_n = 0;
+// one op's dynamic field set to `v`: the program's copy, the host mirror of the device word, the attention's compile-time bound;
+// false when the value leaves the span the level schedule assumed (dynamic_field_in_bounds)
+bool apply_dynamic(zgml_hip_program* p, uint32_t i, uint32_t v) {
+    zgml_device_op& op = p->ops[i];
+    const DynField f = dyn_field(op);
+    if (!f.word) return true;
+    *f.word = v;
+    if (f.role == DynField::SeqKv && i < p->seq_kv_bound.size()) p->seq_kv_bound[i] = std::max(p->seq_kv_bound[i], v);
+    if (p->dyn_host[i] != v) p->dyn_host[i] = v, p->dyn_dirty = true;
+    return !p->plan_batched || dynamic_field_in_bounds(p->sched, i, op);
 }
 
-void free_resident(zgml_hip_program* p) {
-    Resident* r = p->resident;
-    if (!r) return;
-    free_resident_graph(p);
-    hipFree(r->embed);
-    hipFree(r->cos);
-    hipFree(r->sin);
-    hipFree(r->rope_bufs);
-    hipFree(r->dyn_kind);
-    hipFree(r->dyn_base);
-    hipFree(r->dyn_stride);
-    hipFree(r->state);
-    hipFree(r->tok_dev);
-    hipFree(r->tokens);
-    hipFree(r->bstate);
-    hipFree(r->dyn_seq);
-    hipFree(r->bval);
-    hipFree(r->bidx);
-    hipFree(r->btokens);
-    delete r;
-    p->resident = nullptr;
+// the loop of the two refresh_dynamic entry points: every op on p->dyn_ops takes pos_kv(i) = {slice_pos, seq_kv} of ITS sequence
+template <class PosKv>
+void refresh_dynamic_ops(zgml_hip_ctx* ctx, zgml_hip_program* p, PosKv pos_kv) {
+    const uint64_t t_prof = ctx->host_prof ? now_ns() : 0;
+    bool in_bounds = true;
+    for (const uint32_t i : p->dyn_ops) {
+        const DynField f = dyn_field(p->ops[i]);
+        const std::pair<uint32_t, uint32_t> at = pos_kv(i);
+        in_bounds = apply_dynamic(p, i, f.role == DynField::SeqKv ? at.second : f.at(at.first, 0)) && in_bounds;
+    }
+    if (p->plan_batched && !in_bounds) p->batching_safe = false, p->plan_dirty = true;
+    if (ctx->host_prof) ctx->prof_ns[0] += now_ns() - t_prof, ctx->prof_calls[0]++;
 }
 
 } // namespace
@@ -1080,62 +1050,13 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     return p;
 }
 
-// one op's dynamic field taken over from `src` (same kind, same static part): the program's copy, the device word, the attention's
-// compile-time bound; false when the value leaves the span the level schedule assumed (dynamic_fields_in_bounds for this op)
-static bool apply_dynamic(zgml_hip_program* p, uint32_t i, const zgml_device_op& src) {
-    auto ext2 = [](uint64_t n0, uint64_t s0, uint64_t n1, uint64_t s1) -> uint64_t { return n0 && n1 ? (n0 - 1) * s0 + (n1 - 1) * s1 + 1 : 0; }; // (schedule.hip's extent of a strided 2-D view)
-    zgml_device_op& op = p->ops[i];
-    uint32_t v = 0;
-    bool ok = true;
-    const DynBound* const b = p->plan_batched && i < p->sched.bounds.size() ? &p->sched.bounds[i] : nullptr;
-    switch (op.kind) {
-        case ZGML_DOP_SLICE_ASSIGN: {
-            auto& sa = op.u.slice_assign;
-            v = sa.dst_offset = src.u.slice_assign.dst_offset;
-            if (b && b->kind == 1) {
-                const uint64_t lo = sa.dst_offset, hi = lo + ext2(sa.rows, sa.dst_row_stride, sa.cols, sa.dst_col_stride);
-                ok = !(lo < b->lo || hi > b->hi);
-            }
-            break;
-        }
-        case ZGML_DOP_ATTENTION:
-            v = op.u.attention.seq_kv = src.u.attention.seq_kv;
-            if (b && b->kind == 2) ok = v <= b->max_seq_kv;
-            if (i < p->seq_kv_bound.size()) p->seq_kv_bound[i] = std::max(p->seq_kv_bound[i], v);
-            break;
-        case ZGML_DOP_KVQ_STORE: v = op.u.kvq_store.col = src.u.kvq_store.col; break;
-        case ZGML_DOP_ATTENTION_KVQ:
-            v = op.u.attention_kvq.seq_kv = src.u.attention_kvq.seq_kv;
-            if (b && b->kind == 3) ok = v <= b->max_seq_kv;
-            if (i < p->seq_kv_bound.size()) p->seq_kv_bound[i] = std::max(p->seq_kv_bound[i], v);
-            break;
-        default: return true;
-    }
-    if (p->dyn_host[i] != v) p->dyn_host[i] = v, p->dyn_dirty = true;
-    return ok;
-}
-
 // The per-token refresh reduced to what it is (src/backend/program.zig:7452-7490 StepDynamicParams, as the reference's wgpu backend
-// applies it — src/backend/wgpu.zig:1162-1169): every KV store goes to column `slice_pos` (dst_offset = dst_base_offset +
-// slice_pos * patch_stride; quantised caches: col = col_base + slice_pos * patch_stride) and every attention reads `seq_kv` keys.
-// O(#dynamic ops); static fields are NOT looked at — a caller that may have changed them calls zgml_hip_refresh_program.
+// applies it — src/backend/wgpu.zig:1162-1169): every KV store goes to column `slice_pos` and every attention reads `seq_kv` keys
+// (schedule.h: dyn_field). O(#dynamic ops); static fields are NOT looked at — a caller that may have changed them calls
+// zgml_hip_refresh_program.
 int zgml_hip_refresh_dynamic(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t slice_pos, uint32_t seq_kv) {
     if (!ctx || !p) return -1;
-    const uint64_t t_prof = ctx->host_prof ? now_ns() : 0;
-    bool in_bounds = true;
-    for (const uint32_t i : p->dyn_ops) {
-        zgml_device_op src = p->ops[i];
-        switch (src.kind) {
-            case ZGML_DOP_SLICE_ASSIGN: src.u.slice_assign.dst_offset = src.u.slice_assign.dst_base_offset + slice_pos * src.u.slice_assign.patch_stride; break;
-            case ZGML_DOP_ATTENTION: src.u.attention.seq_kv = seq_kv; break;
-            case ZGML_DOP_KVQ_STORE: src.u.kvq_store.col = src.u.kvq_store.col_base + slice_pos * src.u.kvq_store.patch_stride; break;
-            case ZGML_DOP_ATTENTION_KVQ: src.u.attention_kvq.seq_kv = seq_kv; break;
-            default: break;
-        }
-        in_bounds = apply_dynamic(p, i, src) && in_bounds;
-    }
-    if (p->plan_batched && !in_bounds) p->batching_safe = false, p->plan_dirty = true;
-    if (ctx->host_prof) ctx->prof_ns[0] += now_ns() - t_prof, ctx->prof_calls[0]++;
+    refresh_dynamic_ops(ctx, p, [&](uint32_t) { return std::make_pair(slice_pos, seq_kv); });
     return 0;
 }
 
@@ -1175,22 +1096,7 @@ int zgml_hip_refresh_dynamic_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
         ctx->fail("refresh_dynamic_batch: no sequences declared for this program (zgml_hip_program_set_sequences)");
         return -1;
     }
-    const uint64_t t_prof = ctx->host_prof ? now_ns() : 0;
-    bool in_bounds = true;
-    for (const uint32_t i : p->dyn_ops) {
-        zgml_device_op src = p->ops[i];
-        const uint32_t b = p->op_seq[i];
-        switch (src.kind) {
-            case ZGML_DOP_SLICE_ASSIGN: src.u.slice_assign.dst_offset = src.u.slice_assign.dst_base_offset + slice_pos[b] * src.u.slice_assign.patch_stride; break;
-            case ZGML_DOP_ATTENTION: src.u.attention.seq_kv = seq_kv[b]; break;
-            case ZGML_DOP_KVQ_STORE: src.u.kvq_store.col = src.u.kvq_store.col_base + slice_pos[b] * src.u.kvq_store.patch_stride; break;
-            case ZGML_DOP_ATTENTION_KVQ: src.u.attention_kvq.seq_kv = seq_kv[b]; break;
-            default: break;
-        }
-        in_bounds = apply_dynamic(p, i, src) && in_bounds;
-    }
-    if (p->plan_batched && !in_bounds) p->batching_safe = false, p->plan_dirty = true;
-    if (ctx->host_prof) ctx->prof_ns[0] += now_ns() - t_prof, ctx->prof_calls[0]++;
+    refresh_dynamic_ops(ctx, p, [&](uint32_t i) { return std::make_pair(slice_pos[p->op_seq[i]], seq_kv[p->op_seq[i]]); });
     return 0;
 }
 
@@ -1202,7 +1108,7 @@ void zgml_hip_refresh_program(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml
     if (static_same) {
         // the common per-token case: only dynamic fields moved — of the ops that have one (p->dyn_ops)
         bool in_bounds = true;
-        for (const uint32_t i : p->dyn_ops) in_bounds = apply_dynamic(p, i, ops[i]) && in_bounds;
+        for (const uint32_t i : p->dyn_ops) in_bounds = apply_dynamic(p, i, *dyn_field(ops[i]).word) && in_bounds;
         if (p->plan_batched && !in_bounds) {
             // a dynamic field left the span the level schedule assumed: the reordered plan is no
             // longer provably equivalent, fall back to program order for good
@@ -1318,10 +1224,7 @@ static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
     if (!sw().hip_io_graph || !ctx->opt_graph || ctx->opt_profile || !n_inputs || !n_outputs || !p->in_plan.word_aligned || !p->out_plan.word_aligned ||
         !p->in_plan.dyn_row || !p->in_plan.table_dev || !p->out_plan.table_dev)
         return false;
-    if (p->plan_dirty || p->fuse_epoch != ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
+    ensure_plan(p);
     if (p->plan.empty()) return false;
     hipStream_t s = ctx->stream;
     { // pack: the inputs, then the dynamic words (always: the graph's scatter launch has a fixed number of rows)
@@ -1381,19 +1284,13 @@ static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
             return false;
         }
         const uint32_t gy = io_grid_y(p->out_plan.max_row_words);
-        hipGraph_t g = nullptr;
-        if (!CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) return false;
-        scatter_words_kernel<<<dim3(in_rows, io_grid_y(p->in_plan.max_row_words)), 256, 0, s>>>(p->in_plan.table_dev, (const uint32_t*)in_dev);
-        run_plan(p, s, 0, p->plan.size());
-        gather_words_wide_kernel<<<dim3(out_rows, gy), 256, 0, s>>>(p->out_plan.table_dev, (uint32_t*)out_dev);
-        if (!CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) || !g) return false;
-        dump_graph(g, "program-io");
-        hipGraphExec_t ge = nullptr;
-        if (!CTX_CHECK(ctx, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0))) {
-            hipGraphDestroy(g);
-            return false;
-        }
-        p->io_graph = g, p->io_graph_exec = ge, p->io_in_rows = in_rows, p->io_out_rows = out_rows, p->io_out_dev = out_dev;
+        const auto work = [&] {
+            scatter_words_kernel<<<dim3(in_rows, io_grid_y(p->in_plan.max_row_words)), 256, 0, s>>>(p->in_plan.table_dev, (const uint32_t*)in_dev);
+            run_plan(p, s, 0, p->plan.size());
+            gather_words_wide_kernel<<<dim3(out_rows, gy), 256, 0, s>>>(p->out_plan.table_dev, (uint32_t*)out_dev);
+        };
+        if (!capture_graph(ctx, s, "program-io", work, &p->io_graph, &p->io_graph_exec)) return false;
+        p->io_in_rows = in_rows, p->io_out_rows = out_rows, p->io_out_dev = out_dev;
     }
     if (!CTX_CHECK(ctx, hipGraphLaunch(p->io_graph_exec, s))) return true; // (reported; nothing ran)
     p->dyn_dirty = false;
@@ -1519,7 +1416,7 @@ void zgml_hip_download_outputs(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgm
     download_outputs(ctx, p, outputs, n_outputs);
 }
 
-void shard_peer_release(zgml_hip_program* p); // (defined with the row-shard path below)
+void shard_peer_release(zgml_hip_program* p); // (runtime_shard.hip)
 void zgml_hip_free_program(zgml_hip_ctx* ctx, zgml_hip_program* p) {
     if (!p) return;
     if (ctx) {
@@ -1605,13 +1502,9 @@ zgml_runtime_profile* zgml_hip_get_runtime_profile(zgml_hip_ctx*, zgml_hip_progr
 
 // ── extensions ──────────────────────────────────────────────────────────────────────────────
 
-// a caller about to touch a buffer some hoisted (run-once) repeat read or wrote: back to running every repeat in the plan
 uint64_t zgml_hip_program_plan_text(zgml_hip_ctx* ctx, zgml_hip_program* p, char* out, uint64_t cap) {
     if (!ctx || !p) return 0;
-    if (p->plan_dirty || p->fuse_epoch != ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
+    ensure_plan(p);
     static const char* const pro_names[4] = {"none", "mul", "rmsnorm", "prenorm"};
     std::string t;
     for (size_t i = 0; i < p->plan.size(); i++) {
@@ -1636,10 +1529,6 @@ uint64_t zgml_hip_program_plan_text(zgml_hip_ctx* ctx, zgml_hip_program* p, char
         out[n] = 0;
     }
     return t.size();
-}
-
-void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx) {
-    if (p->hoist_ok && buf_idx < p->hoist_guard.size() && p->hoist_guard[buf_idx]) p->hoist_ok = false, p->plan_dirty = true;
 }
 
 void* zgml_hip_program_buffer_ptr(zgml_hip_program* p, uint16_t buf_idx) {
@@ -1679,10 +1568,7 @@ void zgml_hip_enqueue_ops(zgml_hip_ctx* ctx, zgml_hip_program* p, uint64_t first
     hipSetDevice(ctx->device);
     if (!p->ksplit_off && !(first == 0 && count >= p->ops.size())) // an op range must leave every buffer written: no deferred vectors in this program's plans
         p->ksplit_off = true, p->plan_dirty = p->plan_dirty || p->has_deferred;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
+    ensure_plan(p);
     flush_dyn(p);
     // a launch belongs to the range when every op it covers does; barriers (set_barriers) make
     // sure batching never straddles the harness's collective points
@@ -1716,402 +1602,6 @@ int64_t zgml_hip_argmax(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     hipMemcpyAsync(ctx->arg_out_host, ctx->arg_out, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
     if (!CTX_CHECK(ctx, hipStreamSynchronize(ctx->stream)) || !ctx->handoff_ok("argmax")) return -1;
     return *ctx->arg_out_host;
-}
-
-
-int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_resident_llama* d) {
-    if (!ctx || !p || !d) return -1;
-    hipSetDevice(ctx->device);
-    free_resident(p);
-    auto live = [&](uint16_t b) { return b < p->bufs.size() && p->bufs[b]; };
-    if (!live(d->buf_token_input) || !live(d->buf_attn_mask) || !live(d->buf_logits) || !d->d_model ||
-        p->sizes[d->buf_token_input] < d->d_model || p->sizes[d->buf_attn_mask] < d->max_seq ||
-        p->sizes[d->buf_logits] < d->vocab) {
-        ctx->fail("resident_setup: bad buffer ids");
-        return -1;
-    }
-    // token_len of the plan: token_input holds T embedding rows (T = 1: decode plan, T > 1: prefill chunk)
-    const uint32_t T = (uint32_t)(p->sizes[d->buf_token_input] / d->d_model);
-    if (T > 1 && (p->sizes[d->buf_attn_mask] < (uint64_t)T * d->max_seq || p->sizes[d->buf_logits] < (uint64_t)T * d->vocab)) {
-        ctx->fail("resident_setup: attn_mask / logits smaller than token_len columns / rows");
-        return -1;
-    }
-    if (p->n_seqs && T != p->n_seqs) {
-        ctx->fail("resident_setup: the program declares " + std::to_string(p->n_seqs) + " sequences but token_input holds " + std::to_string(T) + " columns");
-        return -1;
-    }
-    Resident* r = new Resident();
-    p->resident = r;
-    r->token_len = T;
-    r->n_seqs = p->n_seqs; // > 0: the T columns are T sequences (zgml_hip_resident_decode_batch), not T consecutive positions
-    r->vocab = d->vocab, r->d = d->d_model, r->max_seq = d->max_seq, r->dh = d->d_head, r->n_rope = d->n_rope;
-    r->tok_in = p->bufs[d->buf_token_input], r->mask = p->bufs[d->buf_attn_mask], r->logits = p->bufs[d->buf_logits];
-    const size_t n_ops = p->ops.size();
-    std::vector<float*> ropes(d->n_rope);
-    for (uint32_t l = 0; l < d->n_rope; l++) {
-        if (!live(d->buf_rope[l]) || p->sizes[d->buf_rope[l]] < (uint64_t)T * 2 * d->d_head) {
-            ctx->fail("resident_setup: bad rope buffer");
-            return -1;
-        }
-        ropes[l] = p->bufs[d->buf_rope[l]];
-    }
-    std::vector<uint32_t> kind(n_ops, 0), base(n_ops, 0), stride(n_ops, 0);
-    for (size_t i = 0; i < n_ops; i++) {
-        if (p->ops[i].kind == ZGML_DOP_SLICE_ASSIGN && p->ops[i].u.slice_assign.patch_stride) {
-            kind[i] = 1, base[i] = p->ops[i].u.slice_assign.dst_base_offset, stride[i] = p->ops[i].u.slice_assign.patch_stride;
-        } else if (p->ops[i].kind == ZGML_DOP_ATTENTION || p->ops[i].kind == ZGML_DOP_ATTENTION_KVQ) {
-            kind[i] = 2;
-        } else if (p->ops[i].kind == ZGML_DOP_KVQ_STORE && p->ops[i].u.kvq_store.patch_stride) { // col = col_base + pos * stride
-            kind[i] = 1, base[i] = p->ops[i].u.kvq_store.col_base, stride[i] = p->ops[i].u.kvq_store.patch_stride;
-        }
-    }
-    const size_t tab = (size_t)d->max_seq * d->d_head * 4, emb = (size_t)d->vocab * d->d_model * 4;
-    bool ok = CTX_CHECK(ctx, hipMalloc((void**)&r->embed, emb)) && CTX_CHECK(ctx, hipMalloc((void**)&r->cos, tab)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->sin, tab)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->rope_bufs, (ropes.size() + 1) * sizeof(float*))) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_kind, (n_ops + 1) * 4)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_base, (n_ops + 1) * 4)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_stride, (n_ops + 1) * 4)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->state, 4 * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->tok_dev, (size_t)T * 4)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->embed, d->token_embed, emb)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->cos, d->cos_table, tab)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->sin, d->sin_table, tab)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->rope_bufs, ropes.data(), ropes.size() * sizeof(float*))) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_kind, kind.data(), n_ops * 4)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_base, base.data(), n_ops * 4)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_stride, stride.data(), n_ops * 4));
-    if (ok && r->n_seqs) {
-        std::vector<uint32_t> seq(n_ops + 1, 0);
-        for (size_t i = 0; i < n_ops; i++) seq[i] = kind[i] && i < p->op_seq.size() && p->op_seq[i] != UINT32_MAX ? p->op_seq[i] : 0;
-        const size_t pairs = (size_t)r->n_seqs * argmax_batch_blocks(d->vocab);
-        ok = CTX_CHECK(ctx, hipMalloc((void**)&r->bstate, ((size_t)4 * r->n_seqs + 1) * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_seq, (n_ops + 1) * 4)) &&
-             CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) && CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))) &&
-             CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_seq, seq.data(), n_ops * 4));
-    }
-    if (!ok) {
-        free_resident(p);
-        return -1;
-    }
-    // The resident kernels write token_input, attn_mask and the rope buffers from the device, outside the op list: to the hoist
-    // analysis those buffers look like constants (never written by an op), so a `repeat` that broadcasts one of them would have
-    // been run once at plan build and its stale copy read ever after. Today's LLaMA stream only repeats gamma and the
-    // scalar 1, but the guard must not depend on that: every buffer handed over here leaves the hoisted set.
-    unhoist_if_guarded(p, d->buf_token_input);
-    unhoist_if_guarded(p, d->buf_attn_mask);
-    for (uint32_t l = 0; l < d->n_rope; l++) unhoist_if_guarded(p, d->buf_rope[l]);
-    return 0;
-}
-
-int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos,
-                             uint32_t n_steps, int64_t* tokens_out) {
-    if (!ctx || !p || !p->resident || !tokens_out) return -1;
-    Resident* r = p->resident;
-    if (r->n_seqs) {
-        ctx->fail("resident_decode: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
-        return -1;
-    }
-    if (r->token_len != 1) {
-        ctx->fail("resident_decode: the program is a token_len > 1 plan (use zgml_hip_resident_prefill)");
-        return -1;
-    }
-    if (first_token >= r->vocab || (uint64_t)start_pos + n_steps > r->max_seq) {
-        ctx->fail("resident_decode: token or position out of range");
-        return -1;
-    }
-    hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
-    if (p->plan_batched && n_steps) {
-        // the device patches slice_assign offsets / seq_kv itself (resident_prep_kernel): check the first and
-        // last position of this call against the bounds the batched plan assumed, as refresh_program does
-        bool ok = true;
-        std::vector<zgml_device_op> probe = p->ops;
-        for (uint32_t pos : {start_pos, start_pos + n_steps - 1}) {
-            for (auto& o : probe) {
-                if (o.kind == ZGML_DOP_SLICE_ASSIGN && o.u.slice_assign.patch_stride)
-                    o.u.slice_assign.dst_offset = o.u.slice_assign.dst_base_offset + pos * o.u.slice_assign.patch_stride;
-                if (o.kind == ZGML_DOP_ATTENTION) o.u.attention.seq_kv = pos + 1;
-                if (o.kind == ZGML_DOP_ATTENTION_KVQ) o.u.attention_kvq.seq_kv = pos + 1;
-            }
-            ok = ok && dynamic_fields_in_bounds(p->sched, probe);
-        }
-        if (!ok) { // fall back to program order for good, like refresh_program
-            p->batching_safe = false;
-            free_graph(p);
-            build_plan(p);
-        }
-    }
-    if (r->tokens_cap < n_steps) {
-        hipStreamSynchronize(s);
-        hipFree(r->tokens);
-        r->tokens = nullptr;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_steps * 8))) return -1;
-        r->tokens_cap = n_steps;
-        free_resident_graph(p); // the graph baked the old pointer/cap
-    }
-    ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
-                       p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
-    const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
-    // (off unless ZGML_HIP_TAIL_FUSED=1. First form — the last arriver walks all 8-16 K elements of the next token's patches alone —
-    // measured SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every workgroup writes the
-    // position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838 against 842;
-    // profiles/r05_token_tail_ab.txt)
-    const bool tail_fused = sw().hip_tail_fused;
-    auto one_token = [&](hipStream_t st) {
-        if (!tail_fused) launch_resident_prep(st, a, total);
-        // [prep] [plan] [argmax stage 1] [stage 2 + advance]; or, opt-in, [plan] [token tail]: the argmax of the logits, the advance
-        // of the device state AND the next token's patches in ONE launch (launch_argmax_tail; the first token's patches then
-        // come from a stand-alone prep launch in front of the loop) — two launches fewer per token.
-        run_plan(p, st, 0, p->plan.size());
-        if (tail_fused)
-            launch_argmax_tail(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_cnt, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap}, &a, total);
-        else
-            launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap});
-    };
-    // static dyn words (row stores with patch_stride 0) come from the host mirror; the prep kernel
-    // only rewrites the position-dependent ones
-    set_dyn_from_ops(p);
-    p->dyn_dirty = true;
-    flush_dyn(p);
-    const uint32_t st0[4] = {first_token, start_pos, 0, 0};
-    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return -1;
-    if (tail_fused) launch_resident_prep(s, a, total); // the first token's patches (every later token's come from its predecessor's tail)
-    if (ctx->opt_graph && !r->graph_exec) {
-        hipGraph_t g = nullptr;
-        if (CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) {
-            one_token(s);
-            if (CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) && g) {
-                dump_graph(g, "resident");
-                if (CTX_CHECK(ctx, hipGraphInstantiate(&r->graph_exec, g, nullptr, nullptr, 0)))
-                    r->graph = g;
-                else
-                    hipGraphDestroy(g);
-            }
-        }
-    }
-    // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
-    // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
-    const uint32_t per_graph = (uint32_t)sw().hip_resident_tokens_per_graph;
-    if (ctx->opt_graph && r->graph_exec && per_graph > 1 && n_steps >= per_graph && !r->graph_multi_exec) {
-        hipGraph_t g = nullptr;
-        if (CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) {
-            for (uint32_t t = 0; t < per_graph; t++) one_token(s);
-            if (CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) && g) {
-                if (CTX_CHECK(ctx, hipGraphInstantiate(&r->graph_multi_exec, g, nullptr, nullptr, 0)))
-                    r->graph_multi = g, r->multi_n = per_graph;
-                else
-                    hipGraphDestroy(g);
-            }
-        }
-    }
-    for (uint32_t i = 0; i < n_steps;) {
-        if (r->graph_multi_exec && n_steps - i >= r->multi_n) {
-            hipGraphLaunch(r->graph_multi_exec, s);
-            i += r->multi_n;
-        } else if (r->graph_exec) {
-            hipGraphLaunch(r->graph_exec, s);
-            i++;
-        } else {
-            one_token(s);
-            i++;
-        }
-    }
-    hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
-    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
-    ok = ok && ctx->handoff_ok("resident_decode");
-    // the device rewrote the dyn block behind the host mirror's back: force a re-upload next time
-    memset(p->dyn_host, 0xFF, p->ops.size() * sizeof(uint32_t));
-    set_dyn_from_ops(p);
-    p->dyn_dirty = true;
-    p->profile.call_count += n_steps;
-    p->profile.backend_op_count += (uint64_t)n_steps * p->ops.size();
-    p->profile.backend_dispatch_count += (uint64_t)n_steps * (p->plan.size() + (tail_fused ? 1 : 3));
-    return ok ? 0 : -1;
-}
-
-
-// The resident loop over a batched program: per step [batched prep] [plan] [pick stage 1] [pick stage 2 + advance], one graph launch.
-int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
-                                   const uint32_t* n_steps, uint32_t max_steps, int64_t* tokens_out) {
-    if (!ctx || !p) return -1;
-    Resident* r = p->resident;
-    if (!r || !r->n_seqs || !p->n_seqs) {
-        ctx->fail("resident_decode_batch: not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
-        return -1;
-    }
-    if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
-    const uint32_t B = r->n_seqs;
-    uint32_t steps = 0;
-    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
-    if (steps > max_steps) {
-        ctx->fail("resident_decode_batch: n_steps exceeds max_steps");
-        return -1;
-    }
-    // everything is refused before anything is enqueued. A sequence that stops before the last step repeats its step at the position
-    // BEHIND its last token (it rewrites that KV column with the same values): that column must exist too
-    std::vector<uint32_t> last_pos(B);
-    for (uint32_t b = 0; b < B; b++) {
-        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b]; // position after its last step
-        const bool idles = n_steps[b] < steps;
-        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
-            ctx->fail("resident_decode_batch: token or position out of range (sequence " + std::to_string(b) + ")");
-            return -1;
-        }
-        last_pos[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
-    }
-    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
-    if (!steps) return 0;
-    hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
-    if (p->plan_batched) { // the device patches the dynamic words itself: first and last position of every sequence against the plan's bounds
-        bool ok = true;
-        std::vector<zgml_device_op> probe = p->ops;
-        for (int last = 0; last < 2; last++) {
-            for (const uint32_t i : p->dyn_ops) {
-                auto& o = probe[i];
-                const uint32_t pos = last ? last_pos[p->op_seq[i]] : start_pos[p->op_seq[i]];
-                if (o.kind == ZGML_DOP_SLICE_ASSIGN) o.u.slice_assign.dst_offset = o.u.slice_assign.dst_base_offset + pos * o.u.slice_assign.patch_stride;
-                if (o.kind == ZGML_DOP_ATTENTION) o.u.attention.seq_kv = pos + 1;
-            }
-            ok = ok && dynamic_fields_in_bounds(p->sched, probe);
-        }
-        if (!ok) { // fall back to program order for good, like refresh_program
-            p->batching_safe = false;
-            free_graph(p);
-            build_plan(p);
-        }
-    }
-    if (r->btokens_cap < (uint64_t)B * steps) {
-        hipStreamSynchronize(s);
-        hipFree(r->btokens);
-        r->btokens = nullptr, r->btokens_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->btokens, (size_t)B * steps * 8))) return -1;
-        r->btokens_cap = (uint64_t)B * steps;
-        free_resident_graph(p); // the graph baked the old pointer
-    }
-    const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
-                                  p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
-    const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
-    auto one_step = [&](hipStream_t st) {
-        launch_resident_batch_prep(st, a, total);
-        run_plan(p, st, 0, p->plan.size());
-        launch_argmax_batch(st, r->logits, r->vocab, B, r->bval, r->bidx, r->bstate, r->btokens);
-    };
-    set_dyn_from_ops(p); // static dyn words (the row stores) from the host mirror; the prep kernel rewrites the position-dependent ones
-    p->dyn_dirty = true;
-    flush_dyn(p);
-    std::vector<uint32_t> st0((size_t)4 * B + 1, 0);
-    for (uint32_t b = 0; b < B; b++) st0[b] = first_tokens[b], st0[B + b] = start_pos[b], st0[2 * B + b] = n_steps[b];
-    st0[4 * B] = steps; // row length of the device token table of this call
-    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
-        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
-        return -1;
-    if (ctx->opt_graph && !r->graph_exec) {
-        hipStreamSynchronize(s); // (st0 is read by the copy above: it must not die under a pageable-memory copy in flight)
-        hipGraph_t g = nullptr;
-        if (CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) {
-            one_step(s);
-            if (CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) && g) {
-                dump_graph(g, "resident_batch");
-                if (CTX_CHECK(ctx, hipGraphInstantiate(&r->graph_exec, g, nullptr, nullptr, 0)))
-                    r->graph = g;
-                else
-                    hipGraphDestroy(g);
-            }
-        }
-    }
-    for (uint32_t i = 0; i < steps; i++) {
-        if (r->graph_exec)
-            hipGraphLaunch(r->graph_exec, s);
-        else
-            one_step(s);
-    }
-    std::vector<int64_t> got((size_t)B * steps);
-    hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
-    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
-    ok = ok && ctx->handoff_ok("resident_decode_batch");
-    for (uint32_t b = 0; ok && b < B; b++)
-        for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
-    // the device rewrote the dyn block behind the host mirror's back: force a re-upload next time
-    memset(p->dyn_host, 0xFF, p->ops.size() * sizeof(uint32_t));
-    set_dyn_from_ops(p);
-    p->dyn_dirty = true;
-    p->profile.call_count += steps;
-    p->profile.backend_op_count += (uint64_t)steps * p->ops.size();
-    p->profile.backend_dispatch_count += (uint64_t)steps * (p->plan.size() + 3);
-    return ok ? 0 : -1;
-}
-
-
-// One execution of a token_len = T plan (a prefill chunk) with everything but the T token ids produced on the device.
-int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* tokens, uint32_t n_tokens, uint32_t start_pos) {
-    if (!ctx || !p || !p->resident || !tokens) return -1;
-    Resident* r = p->resident;
-    if (r->n_seqs) {
-        ctx->fail("resident_prefill: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
-        return -1;
-    }
-    if (n_tokens != r->token_len || (uint64_t)start_pos + n_tokens > r->max_seq) {
-        ctx->fail("resident_prefill: n_tokens must equal the plan's token_len and the chunk must fit max_seq");
-        return -1;
-    }
-    for (uint32_t j = 0; j < n_tokens; j++)
-        if (tokens[j] >= r->vocab) {
-            ctx->fail("resident_prefill: token out of range");
-            return -1;
-        }
-    hipSetDevice(ctx->device);
-    hipStream_t s = ctx->stream;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
-    if (p->plan_batched) { // the device patches offsets / seq_kv itself: same bound check as refresh_program
-        std::vector<zgml_device_op> probe = p->ops;
-        for (auto& o : probe) {
-            if (o.kind == ZGML_DOP_SLICE_ASSIGN && o.u.slice_assign.patch_stride)
-                o.u.slice_assign.dst_offset = o.u.slice_assign.dst_base_offset + start_pos * o.u.slice_assign.patch_stride;
-            if (o.kind == ZGML_DOP_ATTENTION) o.u.attention.seq_kv = start_pos + n_tokens;
-            if (o.kind == ZGML_DOP_ATTENTION_KVQ) o.u.attention_kvq.seq_kv = start_pos + n_tokens;
-        }
-        if (!dynamic_fields_in_bounds(p->sched, probe)) {
-            p->batching_safe = false;
-            free_graph(p);
-            build_plan(p);
-        }
-    }
-    set_dyn_from_ops(p); // static dyn words from the host mirror; the prep kernel rewrites the position-dependent ones
-    p->dyn_dirty = true;
-    flush_dyn(p);
-    const uint32_t st0[4] = {0, start_pos, 0, 0};
-    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
-        !CTX_CHECK(ctx, hipMemcpyAsync(r->tok_dev, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, s)))
-        return -1;
-    ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
-                       p->dyn_dev, r->state, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), n_tokens};
-    const uint64_t total = (uint64_t)n_tokens * r->d + (uint64_t)n_tokens * r->max_seq + (uint64_t)r->n_rope * n_tokens * 2 * r->dh + p->ops.size();
-    launch_resident_prep(s, a, (uint32_t)total);
-    p->dyn_dirty = false;
-    enqueue(p); // the plan (graph replay when enabled); flush_dyn is a no-op: the device words are current
-    // the logits buffer holds one row per token: the greedy token comes from the LAST position's row
-    launch_argmax(s, r->logits + (uint64_t)(n_tokens - 1) * r->vocab, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out);
-    hipMemcpyAsync(ctx->arg_out_host, ctx->arg_out, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    const bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s)) && ctx->handoff_ok("resident_prefill");
-    // the device rewrote the dyn block behind the host mirror's back: force a re-upload next time
-    memset(p->dyn_host, 0xFF, p->ops.size() * sizeof(uint32_t));
-    set_dyn_from_ops(p);
-    p->dyn_dirty = true;
-    p->profile.call_count++;
-    p->profile.backend_op_count += p->ops.size();
-    p->profile.backend_dispatch_count += p->plan.size() + 3;
-    return ok ? *ctx->arg_out_host : -1;
 }
 
 } // extern "C"

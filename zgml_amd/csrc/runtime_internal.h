@@ -1,6 +1,7 @@
-// runtime_internal.h — what the translation units of the runtime share (runtime.hip: the C ABI, compile / refresh / execute and the
-// resident loops; plan.hip: the launch planner; runtime_bench.hip: the measurement entry points; runtime_shard.hip: the row-shard
-// path): the context and program objects and the few internal functions they call across files. Not part of the boundary (include/zgml_hip.h is).
+// runtime_internal.h — what the translation units of the runtime share (runtime.hip: the C ABI, compile / refresh / execute;
+// runtime_resident.hip: the device-resident loops; plan.hip: the launch planner; runtime_bench.hip: the measurement entry points;
+// runtime_shard.hip: the row-shard path): the context and program objects and the few internal functions they call across files.
+// Not part of the boundary (include/zgml_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -298,4 +299,15 @@ void free_param_blobs(zgml_hip_program* p); // the device parameter arrays of th
 // runtime.hip
 void free_graph(zgml_hip_program* p); // every captured graph of the program
 void dump_graph(hipGraph_t g, const char* tag);
+void ensure_plan(zgml_hip_program* p);      // build_plan (after free_graph) when the plan is dirty or the context's fuse epoch moved
+// `work` captured from s (thread-local mode) and instantiated; `tag`: dump_graph's, nullptr = not dumped. false: reported, nothing kept
+bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, hipGraph_t* g_out, hipGraphExec_t* e_out);
+void set_dyn_from_ops(zgml_hip_program* p); // ops' dynamic words -> p->dyn_host (sets dyn_dirty on a change)
+void flush_dyn(zgml_hip_program* p);        // p->dyn_host -> p->dyn_dev on the context stream when dirty
+void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count); // launches [first, first + count) of the plan, eagerly
+void enqueue(zgml_hip_program* p);          // the whole program on the context stream (plan ensured, dyn flushed, graph replay when enabled)
+void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx); // a buffer written from outside the op list leaves the hoisted set
+// runtime_resident.hip
+void free_resident_graph(zgml_hip_program* p); // the resident loops' captured graphs (they bake the plan: free_graph calls this)
+void free_resident(zgml_hip_program* p);       // p->resident and everything it owns
 } // namespace zgml_rt

@@ -1,0 +1,403 @@
+// runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up, single-sequence decode,
+// batched decode and the prefill chunk. Everything a step needs (embedding row, mask column, RoPE rows, the dynamic words) is
+// produced on the device from a few state words, so a call is a train of launches (or graph replays) with one copy-out at the
+// end. The three loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_graph), resident_end.
+// No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's in their own files.
+#include "runtime_internal.h"
+
+struct zgml_resident {
+    float *embed = nullptr, *cos = nullptr, *sin = nullptr;
+    uint32_t vocab = 0, d = 0, max_seq = 0, dh = 0, n_rope = 0;
+    float *tok_in = nullptr, *mask = nullptr, *logits = nullptr;
+    float** rope_bufs = nullptr;   // device array of n_rope pointers
+    uint32_t* dyn_kind = nullptr;  // per op: 0 static, 1 store (base + pos * stride), 2 attention (pos + T) — dyn_field's roles, for the prep kernels
+    uint32_t* dyn_base = nullptr;
+    uint32_t* dyn_stride = nullptr;
+    uint32_t* state = nullptr;     // [0] token, [1] pos, [2] produced count
+    uint32_t token_len = 1;        // T of the plan (token_input holds T rows): 1 = decode, > 1 = prefill chunk
+    uint32_t* tok_dev = nullptr;   // prefill: the chunk's T token ids (the only per-chunk host -> device traffic)
+    int64_t* tokens = nullptr;     // produced tokens (device)
+    uint32_t tokens_cap = 0;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    hipGraph_t graph_multi = nullptr; // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
+    hipGraphExec_t graph_multi_exec = nullptr;
+    uint32_t multi_n = 0;
+    // batched program (zgml_hip_program_set_sequences): per-sequence device state (kernels.h: ResidentBatchPrepArgs), the sequence of
+    // every dynamic op, the pick's scratch (n_seqs rows of partial maxima) and the produced tokens [n_seqs][bcap]
+    uint32_t n_seqs = 0;
+    uint32_t* bstate = nullptr;
+    uint32_t* dyn_seq = nullptr;
+    float* bval = nullptr;
+    int64_t* bidx = nullptr;
+    int64_t* btokens = nullptr;
+    uint64_t btokens_cap = 0; // elements
+};
+using Resident = zgml_resident;
+
+namespace zgml_rt {
+
+void free_resident_graph(zgml_hip_program* p) {
+    Resident* r = p->resident;
+    if (!r) return;
+    if (r->graph_exec) hipGraphExecDestroy(r->graph_exec);
+    if (r->graph) hipGraphDestroy(r->graph);
+    r->graph_exec = nullptr, r->graph = nullptr;
+    if (r->graph_multi_exec) hipGraphExecDestroy(r->graph_multi_exec);
+    if (r->graph_multi) hipGraphDestroy(r->graph_multi);
+    r->graph_multi_exec = nullptr, r->graph_multi = nullptr, r->multi_n = 0;
+}
+
+void free_resident(zgml_hip_program* p) {
+    Resident* r = p->resident;
+    if (!r) return;
+    free_resident_graph(p);
+    hipFree(r->embed);
+    hipFree(r->cos);
+    hipFree(r->sin);
+    hipFree(r->rope_bufs);
+    hipFree(r->dyn_kind);
+    hipFree(r->dyn_base);
+    hipFree(r->dyn_stride);
+    hipFree(r->state);
+    hipFree(r->tok_dev);
+    hipFree(r->tokens);
+    hipFree(r->bstate);
+    hipFree(r->dyn_seq);
+    hipFree(r->bval);
+    hipFree(r->bidx);
+    hipFree(r->btokens);
+    delete r;
+    p->resident = nullptr;
+}
+
+} // namespace zgml_rt
+
+namespace {
+
+// would every moving op stay inside the bounds the batched plan assumed with its sequence at position pos_of(op index), T token
+// rows per step? (The device patches the words itself, resident_prep_kernel: nothing else would notice a position outside them.)
+template <class PosOf>
+bool positions_in_bounds(const zgml_hip_program* p, uint32_t T, PosOf pos_of) {
+    for (const uint32_t i : p->dyn_ops) {
+        zgml_device_op o = p->ops[i];
+        const DynField f = dyn_field(o);
+        *f.word = f.at(pos_of(i), T);
+        if (!dynamic_field_in_bounds(p->sched, i, o)) return false;
+    }
+    return true;
+}
+
+// what every loop does before it enqueues anything: the plan is current; when it is a batched plan and `in_bounds()` says this
+// call's positions leave its bounds, program order for good, like refresh_program; then the static dyn words (row stores with
+// patch_stride 0) go up from the host mirror — the prep kernels only rewrite the position-dependent ones
+template <class InBounds>
+void resident_begin(zgml_hip_program* p, InBounds in_bounds) {
+    ensure_plan(p);
+    if (p->plan_batched && !in_bounds()) {
+        p->batching_safe = false;
+        free_graph(p);
+        build_plan(p);
+    }
+    set_dyn_from_ops(p);
+    p->dyn_dirty = true;
+    flush_dyn(p);
+}
+
+// ... and after its last synchronisation: the device rewrote the dyn block behind the host mirror's back, so the mirror is
+// invalidated to force a re-upload next time; `steps` executions of `launches_per_step` launches go into the profile
+void resident_end(zgml_hip_program* p, uint64_t steps, uint64_t launches_per_step) {
+    memset(p->dyn_host, 0xFF, p->ops.size() * sizeof(uint32_t));
+    set_dyn_from_ops(p);
+    p->dyn_dirty = true;
+    p->profile.call_count += steps;
+    p->profile.backend_op_count += steps * p->ops.size();
+    p->profile.backend_dispatch_count += steps * launches_per_step;
+}
+
+} // namespace
+
+extern "C" {
+
+int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_resident_llama* d) {
+    if (!ctx || !p || !d) return -1;
+    hipSetDevice(ctx->device);
+    free_resident(p);
+    auto live = [&](uint16_t b) { return b < p->bufs.size() && p->bufs[b]; };
+    if (!live(d->buf_token_input) || !live(d->buf_attn_mask) || !live(d->buf_logits) || !d->d_model ||
+        p->sizes[d->buf_token_input] < d->d_model || p->sizes[d->buf_attn_mask] < d->max_seq ||
+        p->sizes[d->buf_logits] < d->vocab) {
+        ctx->fail("resident_setup: bad buffer ids");
+        return -1;
+    }
+    // token_len of the plan: token_input holds T embedding rows (T = 1: decode plan, T > 1: prefill chunk)
+    const uint32_t T = (uint32_t)(p->sizes[d->buf_token_input] / d->d_model);
+    if (T > 1 && (p->sizes[d->buf_attn_mask] < (uint64_t)T * d->max_seq || p->sizes[d->buf_logits] < (uint64_t)T * d->vocab)) {
+        ctx->fail("resident_setup: attn_mask / logits smaller than token_len columns / rows");
+        return -1;
+    }
+    if (p->n_seqs && T != p->n_seqs) {
+        ctx->fail("resident_setup: the program declares " + std::to_string(p->n_seqs) + " sequences but token_input holds " + std::to_string(T) + " columns");
+        return -1;
+    }
+    Resident* r = new Resident();
+    p->resident = r;
+    r->token_len = T;
+    r->n_seqs = p->n_seqs; // > 0: the T columns are T sequences (zgml_hip_resident_decode_batch), not T consecutive positions
+    r->vocab = d->vocab, r->d = d->d_model, r->max_seq = d->max_seq, r->dh = d->d_head, r->n_rope = d->n_rope;
+    r->tok_in = p->bufs[d->buf_token_input], r->mask = p->bufs[d->buf_attn_mask], r->logits = p->bufs[d->buf_logits];
+    const size_t n_ops = p->ops.size();
+    std::vector<float*> ropes(d->n_rope);
+    for (uint32_t l = 0; l < d->n_rope; l++) {
+        if (!live(d->buf_rope[l]) || p->sizes[d->buf_rope[l]] < (uint64_t)T * 2 * d->d_head) {
+            ctx->fail("resident_setup: bad rope buffer");
+            return -1;
+        }
+        ropes[l] = p->bufs[d->buf_rope[l]];
+    }
+    std::vector<uint32_t> kind(n_ops, 0), base(n_ops, 0), stride(n_ops, 0);
+    for (size_t i = 0; i < n_ops; i++) // the device's copy of dyn_field for the ops that move (the prep kernels evaluate DynField::at)
+        if (const DynField f = dyn_field(p->ops[i]); f.moves()) kind[i] = f.role == DynField::SeqKv ? 2 : 1, base[i] = f.base, stride[i] = f.stride;
+    const size_t tab = (size_t)d->max_seq * d->d_head * 4, emb = (size_t)d->vocab * d->d_model * 4;
+    bool ok = CTX_CHECK(ctx, hipMalloc((void**)&r->embed, emb)) && CTX_CHECK(ctx, hipMalloc((void**)&r->cos, tab)) &&
+              CTX_CHECK(ctx, hipMalloc((void**)&r->sin, tab)) &&
+              CTX_CHECK(ctx, hipMalloc((void**)&r->rope_bufs, (ropes.size() + 1) * sizeof(float*))) &&
+              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_kind, (n_ops + 1) * 4)) &&
+              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_base, (n_ops + 1) * 4)) &&
+              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_stride, (n_ops + 1) * 4)) &&
+              CTX_CHECK(ctx, hipMalloc((void**)&r->state, 4 * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->tok_dev, (size_t)T * 4)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->embed, d->token_embed, emb)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->cos, d->cos_table, tab)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->sin, d->sin_table, tab)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->rope_bufs, ropes.data(), ropes.size() * sizeof(float*))) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_kind, kind.data(), n_ops * 4)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_base, base.data(), n_ops * 4)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_stride, stride.data(), n_ops * 4));
+    if (ok && r->n_seqs) {
+        std::vector<uint32_t> seq(n_ops + 1, 0);
+        for (size_t i = 0; i < n_ops; i++) seq[i] = kind[i] && i < p->op_seq.size() && p->op_seq[i] != UINT32_MAX ? p->op_seq[i] : 0;
+        const size_t pairs = (size_t)r->n_seqs * argmax_batch_blocks(d->vocab);
+        ok = CTX_CHECK(ctx, hipMalloc((void**)&r->bstate, ((size_t)4 * r->n_seqs + 1) * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_seq, (n_ops + 1) * 4)) &&
+             CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) && CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))) &&
+             CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_seq, seq.data(), n_ops * 4));
+    }
+    if (!ok) {
+        free_resident(p);
+        return -1;
+    }
+    // The resident kernels write token_input, attn_mask and the rope buffers from the device, outside the op list: to the hoist
+    // analysis those buffers look like constants (never written by an op), so a `repeat` that broadcasts one of them would have
+    // been run once at plan build and its stale copy read ever after. Today's LLaMA stream only repeats gamma and the
+    // scalar 1, but the guard must not depend on that: every buffer handed over here leaves the hoisted set.
+    unhoist_if_guarded(p, d->buf_token_input);
+    unhoist_if_guarded(p, d->buf_attn_mask);
+    for (uint32_t l = 0; l < d->n_rope; l++) unhoist_if_guarded(p, d->buf_rope[l]);
+    return 0;
+}
+
+int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos,
+                             uint32_t n_steps, int64_t* tokens_out) {
+    if (!ctx || !p || !p->resident || !tokens_out) return -1;
+    Resident* r = p->resident;
+    if (r->n_seqs) {
+        ctx->fail("resident_decode: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
+        return -1;
+    }
+    if (r->token_len != 1) {
+        ctx->fail("resident_decode: the program is a token_len > 1 plan (use zgml_hip_resident_prefill)");
+        return -1;
+    }
+    if (first_token >= r->vocab || (uint64_t)start_pos + n_steps > r->max_seq) {
+        ctx->fail("resident_decode: token or position out of range");
+        return -1;
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    // the first and the last position of this call; a call of no steps probes nothing (there is no last position)
+    resident_begin(p, [&] {
+        return !n_steps || (positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; }));
+    });
+    if (r->tokens_cap < n_steps) {
+        hipStreamSynchronize(s);
+        hipFree(r->tokens);
+        r->tokens = nullptr;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_steps * 8))) return -1;
+        r->tokens_cap = n_steps;
+        free_resident_graph(p); // the graph baked the old pointer/cap
+    }
+    ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
+                       p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
+    const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
+    // (off unless ZGML_HIP_TAIL_FUSED=1. First form — the last arriver walks all 8-16 K elements of the next token's patches alone —
+    // measured SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every workgroup writes the
+    // position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838 against 842;
+    // profiles/r05_token_tail_ab.txt)
+    const bool tail_fused = sw().hip_tail_fused;
+    auto one_token = [&](hipStream_t st) {
+        if (!tail_fused) launch_resident_prep(st, a, total);
+        // [prep] [plan] [argmax stage 1] [stage 2 + advance]; or, opt-in, [plan] [token tail]: the argmax of the logits, the advance
+        // of the device state AND the next token's patches in ONE launch (launch_argmax_tail; the first token's patches then
+        // come from a stand-alone prep launch in front of the loop) — two launches fewer per token.
+        run_plan(p, st, 0, p->plan.size());
+        if (tail_fused)
+            launch_argmax_tail(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_cnt, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap}, &a, total);
+        else
+            launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap});
+    };
+    const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // (a stack array: no wait before the capture, unlike the batched loop's vector)
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return -1;
+    if (tail_fused) launch_resident_prep(s, a, total); // the first token's patches (every later token's come from its predecessor's tail)
+    if (ctx->opt_graph && !r->graph_exec) capture_graph(ctx, s, "resident", [&] { one_token(s); }, &r->graph, &r->graph_exec); // (failed: eager below)
+    // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
+    // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
+    const uint32_t per_graph = (uint32_t)sw().hip_resident_tokens_per_graph;
+    const auto tokens_of_a_graph = [&] {
+        for (uint32_t t = 0; t < per_graph; t++) one_token(s);
+    };
+    if (ctx->opt_graph && r->graph_exec && per_graph > 1 && n_steps >= per_graph && !r->graph_multi_exec &&
+        capture_graph(ctx, s, nullptr, tokens_of_a_graph, &r->graph_multi, &r->graph_multi_exec))
+        r->multi_n = per_graph;
+    for (uint32_t i = 0; i < n_steps;) {
+        if (r->graph_multi_exec && n_steps - i >= r->multi_n) {
+            hipGraphLaunch(r->graph_multi_exec, s);
+            i += r->multi_n;
+        } else if (r->graph_exec) {
+            hipGraphLaunch(r->graph_exec, s);
+            i++;
+        } else {
+            one_token(s);
+            i++;
+        }
+    }
+    hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
+    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    ok = ok && ctx->handoff_ok("resident_decode");
+    resident_end(p, n_steps, p->plan.size() + (tail_fused ? 1 : 3)); // per token [prep] [plan] [argmax x 2], or [plan] [token tail]
+    return ok ? 0 : -1;
+}
+
+
+// The resident loop over a batched program: per step [batched prep] [plan] [pick stage 1] [pick stage 2 + advance], one graph launch.
+int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                   const uint32_t* n_steps, uint32_t max_steps, int64_t* tokens_out) {
+    if (!ctx || !p) return -1;
+    Resident* r = p->resident;
+    if (!r || !r->n_seqs || !p->n_seqs) {
+        ctx->fail("resident_decode_batch: not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
+        return -1;
+    }
+    if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
+    const uint32_t B = r->n_seqs;
+    uint32_t steps = 0;
+    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
+    if (steps > max_steps) {
+        ctx->fail("resident_decode_batch: n_steps exceeds max_steps");
+        return -1;
+    }
+    // everything is refused before anything is enqueued. A sequence that stops before the last step repeats its step at the position
+    // BEHIND its last token (it rewrites that KV column with the same values): that column must exist too
+    std::vector<uint32_t> last_pos(B);
+    for (uint32_t b = 0; b < B; b++) {
+        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b]; // position after its last step
+        const bool idles = n_steps[b] < steps;
+        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
+            ctx->fail("resident_decode_batch: token or position out of range (sequence " + std::to_string(b) + ")");
+            return -1;
+        }
+        last_pos[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
+    }
+    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
+    if (!steps) return 0;
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    // the first and the last position of every sequence
+    resident_begin(p, [&] {
+        return positions_in_bounds(p, 1, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) && positions_in_bounds(p, 1, [&](uint32_t i) { return last_pos[p->op_seq[i]]; });
+    });
+    if (r->btokens_cap < (uint64_t)B * steps) {
+        hipStreamSynchronize(s);
+        hipFree(r->btokens);
+        r->btokens = nullptr, r->btokens_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->btokens, (size_t)B * steps * 8))) return -1;
+        r->btokens_cap = (uint64_t)B * steps;
+        free_resident_graph(p); // the graph baked the old pointer
+    }
+    const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
+                                  p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
+    const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
+    auto one_step = [&](hipStream_t st) {
+        launch_resident_batch_prep(st, a, total);
+        run_plan(p, st, 0, p->plan.size());
+        launch_argmax_batch(st, r->logits, r->vocab, B, r->bval, r->bidx, r->bstate, r->btokens);
+    };
+    std::vector<uint32_t> st0((size_t)4 * B + 1, 0);
+    for (uint32_t b = 0; b < B; b++) st0[b] = first_tokens[b], st0[B + b] = start_pos[b], st0[2 * B + b] = n_steps[b];
+    st0[4 * B] = steps; // row length of the device token table of this call
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
+        return -1;
+    if (ctx->opt_graph && !r->graph_exec) {
+        // st0, a heap vector, is read by the copy above: it must not die under a pageable-memory copy in flight. (The
+        // single-sequence loop hands over a 16-byte stack array instead and does without the wait.)
+        hipStreamSynchronize(s);
+        capture_graph(ctx, s, "resident_batch", [&] { one_step(s); }, &r->graph, &r->graph_exec); // (failed: eager below)
+    }
+    for (uint32_t i = 0; i < steps; i++) {
+        if (r->graph_exec)
+            hipGraphLaunch(r->graph_exec, s);
+        else
+            one_step(s);
+    }
+    std::vector<int64_t> got((size_t)B * steps);
+    hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
+    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    ok = ok && ctx->handoff_ok("resident_decode_batch");
+    for (uint32_t b = 0; ok && b < B; b++)
+        for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
+    resident_end(p, steps, p->plan.size() + 3); // per step [batched prep] [plan] [pick x 2]
+    return ok ? 0 : -1;
+}
+
+
+// One execution of a token_len = T plan (a prefill chunk) with everything but the T token ids produced on the device.
+int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* tokens, uint32_t n_tokens, uint32_t start_pos) {
+    if (!ctx || !p || !p->resident || !tokens) return -1;
+    Resident* r = p->resident;
+    if (r->n_seqs) {
+        ctx->fail("resident_prefill: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
+        return -1;
+    }
+    if (n_tokens != r->token_len || (uint64_t)start_pos + n_tokens > r->max_seq) {
+        ctx->fail("resident_prefill: n_tokens must equal the plan's token_len and the chunk must fit max_seq");
+        return -1;
+    }
+    for (uint32_t j = 0; j < n_tokens; j++)
+        if (tokens[j] >= r->vocab) {
+            ctx->fail("resident_prefill: token out of range");
+            return -1;
+        }
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    resident_begin(p, [&] { return positions_in_bounds(p, n_tokens, [&](uint32_t) { return start_pos; }); }); // (one execution: one position)
+    const uint32_t st0[4] = {0, start_pos, 0, 0};
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemcpyAsync(r->tok_dev, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, s)))
+        return -1;
+    ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
+                       p->dyn_dev, r->state, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), n_tokens};
+    const uint64_t total = (uint64_t)n_tokens * r->d + (uint64_t)n_tokens * r->max_seq + (uint64_t)r->n_rope * n_tokens * 2 * r->dh + p->ops.size();
+    launch_resident_prep(s, a, (uint32_t)total);
+    // through enqueue, not run_plan: one execution per call, so the program's own graphs (captured once, shared with
+    // execute_program) are what to replay. dyn_dirty is cleared first: the prep launch has just written the device words, and
+    // enqueue's flush_dyn must be a no-op rather than overwrite them with the host mirror
+    p->dyn_dirty = false;
+    enqueue(p);
+    // the logits buffer holds one row per token: the greedy token comes from the LAST position's row
+    launch_argmax(s, r->logits + (uint64_t)(n_tokens - 1) * r->vocab, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out);
+    hipMemcpyAsync(ctx->arg_out_host, ctx->arg_out, sizeof(int64_t), hipMemcpyDeviceToHost, s);
+    const bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s)) && ctx->handoff_ok("resident_prefill");
+    resident_end(p, 1, p->plan.size() + 3); // [prep] [plan] [argmax x 2]
+    return ok ? *ctx->arg_out_host : -1;
+}
+
+} // extern "C"

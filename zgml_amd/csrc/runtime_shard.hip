@@ -306,10 +306,7 @@ int64_t zgml_hip_shard_step(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_p
     if (!ctx || !p || !ctx->shard) return -1;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
+    ensure_plan(p);
     if (zgml_hip_stage_inputs(ctx, p, inputs, n_inputs) != 0) return -1;
     if (sw().shard_graph && ctx->opt_graph && !p->shard_graph_exec && !p->shard_capture_failed) {
         // relaxed capture: RCCL may touch its own (already created) resources while it enqueues
@@ -352,10 +349,7 @@ int64_t zgml_hip_shard_profile_step(zgml_hip_ctx* ctx, zgml_hip_program* p, cons
     if (!ctx || !p || !ctx->shard) return -1;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
-    if (p->plan_dirty || p->fuse_epoch != p->ctx->fuse_epoch) {
-        free_graph(p);
-        build_plan(p);
-    }
+    ensure_plan(p);
     if (zgml_hip_stage_inputs(ctx, p, inputs, n_inputs) != 0) return -1;
     std::vector<hipEvent_t> ev(2 * p->shard_points.size() + 2);
     for (auto& e : ev) hipEventCreate(&e);

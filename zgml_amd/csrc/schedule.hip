@@ -154,13 +154,9 @@ Schedule build_schedule(const std::vector<zgml_device_op>& ops, const std::vecto
             auto it = std::upper_bound(bases.begin(), bases.end(), (uint64_t)sa.dst_base_offset);
             const uint64_t limit = it != bases.end() ? *it : buffer_sizes[sa.dst];
             s.bounds[i] = {1, sa.dst_base_offset, std::max<uint64_t>(limit, (uint64_t)sa.dst_base_offset + 1), 0};
-        } else if (ops[i].kind == ZGML_DOP_ATTENTION) {
-            s.bounds[i].kind = 2;
-            s.bounds[i].max_seq_kv = ops[i].u.attention.seq_kv;
-            if (seq_kv_bound && i < seq_kv_bound->size()) s.bounds[i].max_seq_kv = std::max(s.bounds[i].max_seq_kv, (*seq_kv_bound)[i]);
-        } else if (ops[i].kind == ZGML_DOP_ATTENTION_KVQ) {
-            s.bounds[i].kind = 3;
-            s.bounds[i].max_seq_kv = ops[i].u.attention_kvq.seq_kv;
+        } else if (const DynField f = dyn_field(ops[i]); f.role == DynField::SeqKv) {
+            s.bounds[i].kind = ops[i].kind == ZGML_DOP_ATTENTION ? 2 : 3;
+            s.bounds[i].max_seq_kv = *f.word;
             if (seq_kv_bound && i < seq_kv_bound->size()) s.bounds[i].max_seq_kv = std::max(s.bounds[i].max_seq_kv, (*seq_kv_bound)[i]);
         }
     }
@@ -209,19 +205,21 @@ void levels_from_access(const std::vector<OpAccess>& access, const std::vector<u
     for (size_t i = 0; i < n; i++) levels[level[i]].push_back((uint32_t)i);
 }
 
-bool dynamic_fields_in_bounds(const Schedule& s, const std::vector<zgml_device_op>& ops) {
-    for (size_t i = 0; i < ops.size() && i < s.bounds.size(); i++) {
-        const DynBound& b = s.bounds[i];
-        if (b.kind == 1) {
-            const auto& sa = ops[i].u.slice_assign;
-            const uint64_t lo = sa.dst_offset, hi = lo + ext2(sa.rows, sa.dst_row_stride, sa.cols, sa.dst_col_stride);
-            if (lo < b.lo || hi > b.hi) return false;
-        } else if (b.kind == 2) {
-            if (ops[i].u.attention.seq_kv > b.max_seq_kv) return false;
-        } else if (b.kind == 3) {
-            if (ops[i].u.attention_kvq.seq_kv > b.max_seq_kv) return false;
-        }
+bool dynamic_field_in_bounds(const Schedule& s, size_t i, const zgml_device_op& op) {
+    if (i >= s.bounds.size()) return true;
+    const DynBound& b = s.bounds[i];
+    if (b.kind == 1 && op.kind == ZGML_DOP_SLICE_ASSIGN) {
+        const auto& sa = op.u.slice_assign;
+        const uint64_t lo = sa.dst_offset, hi = lo + ext2(sa.rows, sa.dst_row_stride, sa.cols, sa.dst_col_stride);
+        return lo >= b.lo && hi <= b.hi;
     }
+    if ((b.kind == 2 && op.kind == ZGML_DOP_ATTENTION) || (b.kind == 3 && op.kind == ZGML_DOP_ATTENTION_KVQ)) return *dyn_field(op).word <= b.max_seq_kv;
+    return true; // (a kvq_store's column has no bound: its span is the whole cache)
+}
+
+bool dynamic_fields_in_bounds(const Schedule& s, const std::vector<zgml_device_op>& ops) {
+    for (size_t i = 0; i < ops.size(); i++)
+        if (!dynamic_field_in_bounds(s, i, ops[i])) return false;
     return true;
 }
 
