@@ -594,6 +594,42 @@ int zgml_hip_refresh_dynamic_batch(zgml_hip_ctx* ctx, zgml_hip_program* handle, 
 int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens, const uint32_t* start_pos,
                                    const uint32_t* n_steps, uint32_t max_steps, int64_t* tokens_out /* [n_seqs][max_steps] */);
 
+/* ── Greedy-exact speculative decode of ONE sequence on a token_len = T >= 2 plan (zgml_hip_resident_setup on it first).
+ * A verify step at (tok, pos) — tok the last confirmed token, not yet in the KV cache — runs the plan over the candidates
+ * c[0] = tok, c[j] = the draft for position pos + j (a position without a draft repeats c[j - 1]), exactly as
+ * zgml_hip_resident_prefill would at start_pos = pos. With g[j] the first maximum of logits row j, the step accepts the longest
+ * prefix c[1..a] with c[j] == g[j - 1], emits g[0..a] (cut to the tokens still wanted) and advances by as many positions. Every
+ * emitted token is the greedy token of the plan's own logits over a confirmed context: drafts change how many steps are needed,
+ * never which tokens come out. KV columns written for rejected candidates lie at or behind the new position and are stored
+ * again by the next step before any attention reads them. After the call the caches are valid for positions
+ * < start_pos + n_tokens and unspecified behind that; continue with first_token = tokens_out[n_tokens - 1] at
+ * start_pos + n_tokens and the history extended by first_token and tokens_out[0 .. n_tokens - 2].
+ * Drafts: mode 0 looks the history's last n tokens up in the history itself (n = ngram down to 1, the latest earlier
+ * occurrence of the first n that has one) and proposes what followed it, continuing periodically through its own drafts when the
+ * match overlaps the end; mode 1 reads drafts[i] = the caller's guess for the token at position start_pos + 1 + i (an external
+ * draft model). Everything runs on the device, one graph launch per step; the host launches ceil(remaining / T) steps, reads
+ * the produced count back and repeats until n_tokens are there. */
+typedef struct zgml_spec_decode {
+    const uint32_t* history; /* tokens at positions 0..start_pos-1 (what filled the cache); NULL with n_history = 0: lookup sees only this call's tokens */
+    uint32_t n_history;      /* 0 or start_pos */
+    uint32_t mode;           /* 0 = n-gram lookup, 1 = provided */
+    const uint32_t* drafts;  /* mode 1 */
+    uint32_t n_drafts;
+    uint32_t ngram;          /* mode 0: longest suffix tried, 1..4 (0 = 2) */
+} zgml_spec_decode;
+/* steps: verify steps that emitted something; drafted: real drafts among all candidates (pads are not counted); accepted: the
+ * candidates accepted, summed over the steps, before the cut to n_tokens and pads included. */
+typedef struct zgml_spec_stats {
+    uint32_t steps, drafted, accepted, _pad;
+} zgml_spec_stats;
+/* Blocking. Returns 0 on success. Refused with -1 and an error on the context, before anything is enqueued: a batched or a
+ * token_len = 1 plan, any token (first, history, drafts) >= vocab, n_history neither 0 nor start_pos, mode > 1, ngram > 4,
+ * start_pos + n_tokens + T - 1 > max_seq (the last step may start at start_pos + n_tokens - 1 and stores T columns).
+ * n_tokens = 0 returns 0 and touches nothing. opt = NULL: lookup with ngram 2 and no history. */
+int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t first_token, uint32_t start_pos,
+                                         uint32_t n_tokens, const zgml_spec_decode* opt, int64_t* tokens_out /* [n_tokens] */,
+                                         zgml_spec_stats* stats /* may be NULL */);
+
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];
  * otherwise int8), runs `warmup` + `iters` launches round-robin over the ring and returns the

@@ -174,6 +174,17 @@ class ResidentLlamaC(C.Structure):
                 ("_pad", C.c_uint16), ("buf_rope", C.POINTER(C.c_uint16)), ("n_rope", C.c_uint32), ("_pad2", C.c_uint32)]
 
 
+class SpecDecodeC(C.Structure):
+    """zgml_spec_decode (include/zgml_hip.h): history and draft source of zgml_hip_resident_decode_speculative."""
+    _fields_ = [("history", C.POINTER(C.c_uint32)), ("n_history", C.c_uint32), ("mode", C.c_uint32),
+                ("drafts", C.POINTER(C.c_uint32)), ("n_drafts", C.c_uint32), ("ngram", C.c_uint32)]
+
+
+class SpecStatsC(C.Structure):
+    """zgml_spec_stats (include/zgml_hip.h)."""
+    _fields_ = [("steps", C.c_uint32), ("drafted", C.c_uint32), ("accepted", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class RuntimeProfileC(C.Structure):
     _fields_ = [("time_ns", C.c_uint64 * 12), ("backend_op_count", C.c_uint64),
                 ("fallback_op_count", C.c_uint64), ("backend_dispatch_count", C.c_uint64),
@@ -197,6 +208,7 @@ HIP_SYMBOLS = [
     "zgml_hip_shard_profile_step", "zgml_hip_shard_last_point_us", "zgml_hip_device_can_access_peer", "zgml_hip_device_count", "zgml_hip_shard_init_peer", "zgml_hip_shard_peer_export", "zgml_hip_shard_peer_import",
     "zgml_hip_program_plan_text", "zgml_hip_program_pin_outputs",
     "zgml_hip_program_set_sequences", "zgml_hip_refresh_dynamic_batch", "zgml_hip_resident_decode_batch",
+    "zgml_hip_resident_decode_speculative",
 ]
 
 class ShardPointC(C.Structure):
@@ -323,6 +335,8 @@ def _bind_hip(lib: C.CDLL) -> None:
     lib.zgml_hip_refresh_dynamic_batch.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32)]
     lib.zgml_hip_resident_decode_batch.restype = i32
     lib.zgml_hip_resident_decode_batch.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, vp]
+    lib.zgml_hip_resident_decode_speculative.restype = i32
+    lib.zgml_hip_resident_decode_speculative.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SpecDecodeC), vp, C.POINTER(SpecStatsC)]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

@@ -426,6 +426,40 @@ void launch_resident_batch_prep(hipStream_t s, const ResidentBatchPrepArgs& a, u
 // (token, position + 1, left - 1, produced + 1); one without is left as it is (it repeats its step). scratch: B * argmax_batch_blocks(n) pairs.
 int argmax_batch_blocks(uint64_t n);
 void launch_argmax_batch(hipStream_t s, const float* v, uint64_t n, uint32_t B, float* scratch_val, int64_t* scratch_idx, uint32_t* state, int64_t* tokens);
+// ── speculative decode of ONE sequence (spec_decode.hip; the rules are spec.h's): the serial tails of a verify step ──
+// Stage 1 alone of the pick above over `rows` rows of n values: rows * argmax_batch_blocks(n) partial (value, index) pairs, row-major.
+void launch_argmax_rows_stage1(hipStream_t s, const float* v, uint64_t n, uint32_t rows, float* scratch_val, int64_t* scratch_idx);
+// The loop's device state, one block of words. [kSpecRun, kSpecRun + 3) is laid out like the plain loop's state (token,
+// position, produced): it is what launch_resident_prep reads, and only its position word is ever used.
+enum SpecWord : uint32_t {
+    kSpecTok = 0,  // the last confirmed token (== hist[pos])
+    kSpecPos,      // its position
+    kSpecProduced, // tokens produced so far
+    kSpecWanted,   // n_tokens of the call
+    kSpecMode,     // 0 lookup, 1 provided
+    kSpecNgram,
+    kSpecNDrafts,
+    kSpecStart,    // start_pos of the call
+    kSpecHistLo,   // first position whose token the history knows (0, or start_pos when no history was handed over)
+    kSpecSteps,    // zgml_spec_stats
+    kSpecDrafted,
+    kSpecAccepted,
+    kSpecRun,      // the step's run words: [+1] = the position the verify step runs at (spec_draft_kernel writes it)
+    kSpecRunPos = kSpecRun + 1,
+    kSpecWords = kSpecRun + 4,
+};
+struct SpecArgs {
+    uint32_t* words;        // [kSpecWords]
+    uint32_t* hist;         // [hist_cap] token at every position
+    const uint32_t* drafts; // provided drafts (mode 1)
+    uint32_t* cand;         // [T] the step's candidates: the prep launch's token ids
+    int64_t* tokens;        // [tokens_cap] produced tokens
+    const float* pval;      // stage-1 partials of the T logits rows, [T][nblk]
+    const int64_t* pidx;
+    uint32_t T, nblk, vocab, hist_cap, tokens_cap;
+};
+void launch_spec_draft(hipStream_t s, const SpecArgs& a);
+void launch_spec_accept(hipStream_t s, const SpecArgs& a);
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes);
 void launch_f32_to_f16(hipStream_t s, void* dst, const float* src, uint64_t n);
 

@@ -1702,6 +1702,10 @@ void launch_argmax_batch(hipStream_t s, const float* v, uint64_t n, uint32_t B, 
     argmax_batch_stage2<<<dim3(1, B), kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, state, tokens);
 }
 
+void launch_argmax_rows_stage1(hipStream_t s, const float* v, uint64_t n, uint32_t rows, float* scratch_val, int64_t* scratch_idx) {
+    argmax_batch_stage1<<<dim3(argmax_batch_blocks(n), rows), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
+}
+
 void launch_argmax_tail(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, uint32_t* cnt, int64_t* out,
                         const ArgmaxAdvance& adv, const ResidentPrepArgs* prep, uint32_t prep_total) {
     int nblk = (int)(n / (kBlock * 4) + 1);

@@ -1,9 +1,10 @@
 // runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up, single-sequence decode,
 // batched decode and the prefill chunk. Everything a step needs (embedding row, mask column, RoPE rows, the dynamic words) is
 // produced on the device from a few state words, so a call is a train of launches (or graph replays) with one copy-out at the
-// end. The three loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_graph), resident_end.
+// end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_graph), resident_end.
 // No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's in their own files.
 #include "runtime_internal.h"
+#include "spec.h"
 
 struct zgml_resident {
     float *embed = nullptr, *cos = nullptr, *sin = nullptr;
@@ -32,6 +33,12 @@ struct zgml_resident {
     int64_t* bidx = nullptr;
     int64_t* btokens = nullptr;
     uint64_t btokens_cap = 0; // elements
+    // speculative loop over a token_len > 1 plan (zgml_hip_resident_decode_speculative), allocated by its first call: the state
+    // words (kernels.h: SpecWord), the token at every position, the provided drafts (max_seq words each: a position past max_seq
+    // is never drafted); the T candidates are tok_dev, the rows' partial maxima bval / bidx, the produced tokens `tokens`
+    uint32_t* spec = nullptr;
+    uint32_t* hist = nullptr;
+    uint32_t* drafts = nullptr;
 };
 using Resident = zgml_resident;
 
@@ -67,6 +74,9 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->bval);
     hipFree(r->bidx);
     hipFree(r->btokens);
+    hipFree(r->spec);
+    hipFree(r->hist);
+    hipFree(r->drafts);
     delete r;
     p->resident = nullptr;
 }
@@ -398,6 +408,128 @@ int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const 
     const bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s)) && ctx->handoff_ok("resident_prefill");
     resident_end(p, 1, p->plan.size() + 3); // [prep] [plan] [argmax x 2]
     return ok ? *ctx->arg_out_host : -1;
+}
+
+
+// Greedy-exact speculative decode of one sequence over a token_len = T plan (contract: include/zgml_hip.h; rules: spec.h). Per
+// verify step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance], captured once as one graph.
+int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
+                                         const zgml_spec_decode* opt, int64_t* tokens_out, zgml_spec_stats* stats) {
+    if (!ctx || !p || !p->resident) return -1;
+    Resident* r = p->resident;
+    if (r->n_seqs) {
+        ctx->fail("resident_decode_speculative: the program is a batched plan (speculation under batching is not supported)");
+        return -1;
+    }
+    const uint32_t T = r->token_len;
+    if (T < 2) {
+        ctx->fail("resident_decode_speculative: the program is a token_len = 1 plan (a verify step needs token_len >= 2)");
+        return -1;
+    }
+    if (stats) *stats = zgml_spec_stats{0, 0, 0, 0};
+    if (!n_tokens) return 0;
+    if (!tokens_out) return -1;
+    const zgml_spec_decode none{nullptr, 0, 0, nullptr, 0, 0};
+    const zgml_spec_decode& o = opt ? *opt : none;
+    const uint32_t ngram = o.ngram ? o.ngram : kSpecDefaultNgram;
+    if (o.mode > 1 || ngram > kSpecMaxNgram) {
+        ctx->fail("resident_decode_speculative: mode must be 0 or 1 and ngram at most " + std::to_string(kSpecMaxNgram));
+        return -1;
+    }
+    if ((o.n_history != 0 && o.n_history != start_pos) || (o.n_history && !o.history) || (o.mode == 1 && o.n_drafts && !o.drafts)) {
+        ctx->fail("resident_decode_speculative: n_history must be 0 or start_pos (with the tokens), provided drafts need their array");
+        return -1;
+    }
+    // the last step may start at start_pos + n_tokens - 1 and stores T columns
+    if ((uint64_t)start_pos + n_tokens + T - 1 > r->max_seq) {
+        ctx->fail("resident_decode_speculative: start_pos + n_tokens + token_len - 1 exceeds max_seq");
+        return -1;
+    }
+    const uint32_t n_drafts = o.mode == 1 ? o.n_drafts : 0;
+    bool in_vocab = first_token < r->vocab;
+    for (uint32_t i = 0; in_vocab && i < o.n_history; i++) in_vocab = o.history[i] < r->vocab;
+    for (uint32_t i = 0; in_vocab && i < n_drafts; i++) in_vocab = o.drafts[i] < r->vocab;
+    if (!in_vocab) {
+        ctx->fail("resident_decode_speculative: token out of range (first token, history or drafts)");
+        return -1;
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    // the first start and the last possible start of a verify step
+    resident_begin(p, [&] {
+        return positions_in_bounds(p, T, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, T, [&](uint32_t) { return start_pos + n_tokens - 1; });
+    });
+    const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1;
+    if (!r->spec) {
+        const size_t pairs = (size_t)T * nblk;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->spec, kSpecWords * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->hist, (size_t)hist_cap * 4)) ||
+            !CTX_CHECK(ctx, hipMalloc((void**)&r->drafts, (size_t)r->max_seq * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) ||
+            !CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))))
+            return -1;
+    }
+    if (r->tokens_cap < n_tokens) {
+        hipStreamSynchronize(s);
+        hipFree(r->tokens);
+        r->tokens = nullptr, r->tokens_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_tokens * 8))) return -1;
+        r->tokens_cap = n_tokens;
+        free_resident_graph(p); // the graph baked the old pointer/cap
+    }
+    uint32_t w0[kSpecWords] = {0};
+    w0[kSpecTok] = first_token, w0[kSpecPos] = start_pos, w0[kSpecWanted] = n_tokens, w0[kSpecMode] = o.mode, w0[kSpecNgram] = ngram;
+    w0[kSpecNDrafts] = std::min(n_drafts, r->max_seq), w0[kSpecStart] = start_pos, w0[kSpecHistLo] = o.n_history ? 0 : start_pos;
+    w0[kSpecRunPos] = start_pos;
+    // (the host arrays are the caller's or on this stack, and every copy below is waited for before the call returns)
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->spec, w0, sizeof(w0), hipMemcpyHostToDevice, s)) ||
+        (o.n_history && !CTX_CHECK(ctx, hipMemcpyAsync(r->hist, o.history, (size_t)o.n_history * 4, hipMemcpyHostToDevice, s))) ||
+        !CTX_CHECK(ctx, hipMemcpyAsync(r->hist + start_pos, &first_token, 4, hipMemcpyHostToDevice, s)) ||
+        (w0[kSpecNDrafts] && !CTX_CHECK(ctx, hipMemcpyAsync(r->drafts, o.drafts, (size_t)w0[kSpecNDrafts] * 4, hipMemcpyHostToDevice, s))))
+        return -1;
+    const SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap};
+    // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
+    const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
+                             p->dyn_dev, r->spec + kSpecRun, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), T};
+    const uint64_t total = (uint64_t)T * r->d + (uint64_t)T * r->max_seq + (uint64_t)r->n_rope * T * 2 * r->dh + p->ops.size();
+    // the plan enters the step's graph through run_plan, as in resident_decode: many executions per call, with the dynamic words
+    // written by the prep launch inside the graph (resident_prefill's enqueue replays the program's own graphs and would flush the
+    // host mirror over them unless dyn_dirty is cleared per execution)
+    auto one_step = [&](hipStream_t st) {
+        launch_spec_draft(st, sa);
+        launch_resident_prep(st, a, (uint32_t)total);
+        run_plan(p, st, 0, p->plan.size());
+        launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
+        launch_spec_accept(st, sa);
+    };
+    if (ctx->opt_graph && !r->graph_exec) capture_graph(ctx, s, "resident_spec", [&] { one_step(s); }, &r->graph, &r->graph_exec); // (failed: eager below)
+    // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
+    uint32_t w1[kSpecWords] = {0};
+    uint64_t steps_run = 0;
+    bool ok = true;
+    for (uint32_t produced = 0; ok && produced < n_tokens;) {
+        const uint32_t round = (n_tokens - produced + T - 1) / T;
+        for (uint32_t i = 0; i < round; i++) {
+            if (r->graph_exec)
+                hipGraphLaunch(r->graph_exec, s);
+            else
+                one_step(s);
+        }
+        steps_run += round;
+        hipMemcpyAsync(w1, r->spec, sizeof(w1), hipMemcpyDeviceToHost, s);
+        ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+        if (ok && w1[kSpecProduced] <= produced) { // (every step with tokens left emits at least one)
+            ctx->fail("resident_decode_speculative: a round of verify steps produced nothing");
+            ok = false;
+        }
+        produced = w1[kSpecProduced];
+    }
+    if (ok) {
+        hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_tokens * 8, hipMemcpyDeviceToHost, s);
+        ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    }
+    ok = ok && ctx->handoff_ok("resident_decode_speculative");
+    if (ok && stats) *stats = zgml_spec_stats{w1[kSpecSteps], w1[kSpecDrafted], w1[kSpecAccepted], 0};
+    resident_end(p, steps_run, p->plan.size() + 4); // per step [draft] [prep] [plan] [argmax stage 1] [accept]
+    return ok ? 0 : -1;
 }
 
 } // extern "C"

@@ -1,0 +1,100 @@
+// spec.h — the draft rule and the acceptance rule of greedy-exact speculative decode (zgml_hip_resident_decode_speculative,
+// include/zgml_hip.h), written ONCE: the kernels of spec_decode.hip call these functions and so does the host probe
+// tests/cpp/spec_probe.cpp (tests/test_spec_decode_host.py compares it with a Python model of the same rules). Plain C++,
+// no device intrinsics: the header compiles under g++ as it stands.
+//
+// Vocabulary: hist[0..pos] holds the token at every position, hist[pos] being the last confirmed token (not yet in the KV
+// cache). A verify step runs a token_len = T plan over the candidates c[0..T-1]: c[0] = hist[pos], c[j] the draft for position
+// pos + j, or — a position without a draft — the pad c[j - 1]. g[j] is the greedy token of logits row j: the token at position
+// pos + j + 1 given c[0..j].
+#pragma once
+
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define ZGML_SPEC_FN __host__ __device__ inline
+#else
+#define ZGML_SPEC_FN inline
+#endif
+
+namespace zgml {
+
+constexpr uint32_t kSpecMaxNgram = 4; // longest suffix the lookup tries
+constexpr uint32_t kSpecDefaultNgram = 2;
+
+// does the n-gram that ends at i equal the one that ends at pos? (i - n + 1 >= 0 is the caller's business)
+ZGML_SPEC_FN bool spec_ngram_equal(const uint32_t* hist, uint32_t pos, uint32_t n, uint32_t i) {
+    for (uint32_t k = 0; k < n; k++)
+        if (hist[i - k] != hist[pos - k]) return false;
+    return true;
+}
+
+// the positions a lookup of length n may end at are [n - 1, pos - 1]; none when n > pos (and a suffix of length n does not even
+// exist when n > pos + 1)
+ZGML_SPEC_FN bool spec_ngram_applies(uint32_t pos, uint32_t n) { return n >= 1 && n <= pos; }
+
+// the largest i < pos whose n-gram equals the history's last n tokens; -1: none. (The kernel splits this walk over its threads
+// and keeps the largest hit; the probe walks it alone.)
+ZGML_SPEC_FN int64_t spec_ngram_find(const uint32_t* hist, uint32_t pos, uint32_t n) {
+    if (!spec_ngram_applies(pos, n)) return -1;
+    for (uint32_t i = pos - 1;; i--) {
+        if (spec_ngram_equal(hist, pos, n, i)) return i;
+        if (i == n - 1) return -1;
+    }
+}
+
+// n = ngram down to 1, the first n with a match wins: its match position, -1 when no n has one
+ZGML_SPEC_FN int64_t spec_lookup(const uint32_t* hist, uint32_t pos, uint32_t ngram) {
+    for (uint32_t n = ngram; n >= 1; n--) {
+        const int64_t i = spec_ngram_find(hist, pos, n);
+        if (i >= 0) return i;
+    }
+    return -1;
+}
+
+// the T candidates of a lookup step from the match position i (-1: none, every candidate a pad): d[k] = v[i + 1 + k] with v the
+// history followed by the drafts chosen so far, so a match that overlaps the end of the history continues periodically through
+// its own drafts. Returns the number of real drafts.
+ZGML_SPEC_FN uint32_t spec_candidates_lookup(const uint32_t* hist, uint32_t pos, int64_t i, uint32_t T, uint32_t* c) {
+    c[0] = hist[pos];
+    for (uint32_t j = 1; j < T; j++) {
+        if (i < 0) {
+            c[j] = c[j - 1];
+            continue;
+        }
+        const uint64_t src = (uint64_t)i + j;              // v[src]: i < pos, so src - pos < j is a candidate already chosen
+        c[j] = src <= pos ? hist[src] : c[src - pos];
+    }
+    return i < 0 ? 0 : T - 1;
+}
+
+// ... and of a step with provided drafts: drafts[x] is the caller's guess for position start_pos + 1 + x
+ZGML_SPEC_FN uint32_t spec_candidates_provided(uint32_t tok, uint32_t pos, uint32_t start_pos, const uint32_t* drafts, uint32_t n_drafts,
+                                               uint32_t T, uint32_t* c) {
+    uint32_t real = 0;
+    c[0] = tok;
+    for (uint32_t j = 1; j < T; j++) {
+        const uint64_t x = (uint64_t)pos + j - start_pos - 1; // (pos >= start_pos)
+        if (x < n_drafts)
+            c[j] = drafts[x], real++;
+        else
+            c[j] = c[j - 1];
+    }
+    return real;
+}
+
+// the largest a with c[j] == g[j - 1] for all 1 <= j <= a: the candidates that were the greedy choice of the rows in front of them
+template <class G>
+ZGML_SPEC_FN uint32_t spec_accept(const uint32_t* c, const G* g, uint32_t T) {
+    uint32_t a = 0;
+    while (a + 1 < T && (G)c[a + 1] == g[a]) a++;
+    return a;
+}
+
+// tokens a step emits (g[0..a], cut to what is still wanted); 0: nothing left, the step must change nothing
+ZGML_SPEC_FN uint32_t spec_emit_count(uint32_t a, uint32_t n_tokens, uint32_t produced) {
+    const uint32_t left = produced < n_tokens ? n_tokens - produced : 0;
+    return a + 1 < left ? a + 1 : left;
+}
+
+} // namespace zgml

@@ -1,0 +1,120 @@
+// spec_decode.hip — the two serial tails of a speculative verify step (zgml_hip_resident_decode_speculative, runtime_resident.hip:
+// per step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance]). Both are one workgroup and launches of
+// their own: DESIGN section 0.2 item 5 measured that folding such tails into a neighbouring launch is slower. The rules themselves
+// (which tokens are drafted, how many are accepted) are spec.h's; here is only how a workgroup evaluates them.
+#include "kernels.h"
+#include "spec.h"
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+namespace zgml {
+namespace {
+
+constexpr int kSpecBlock = 256;
+constexpr int kSpecWaves = kSpecBlock / 64;
+
+// The candidates of this step into a.cand (what the prep launch reads as its T token ids) and the position it runs at into the
+// run words. Lookup mode: for n = ngram .. 1 the threads walk the match positions [n - 1, pos - 1] downwards, 256 apart — a
+// thread's first hit is its largest —, the largest hit of the workgroup is folded with wave shuffles and one pass over LDS, and
+// the first n with a hit wins. Provided mode is a table read. Thread 0 writes.
+__global__ void __launch_bounds__(kSpecBlock) spec_draft_kernel(SpecArgs a) {
+    __shared__ int32_t fold[kSpecWaves];
+    uint32_t* const w = a.words;
+    const uint32_t pos = w[kSpecPos], lo = w[kSpecHistLo];
+    if (w[kSpecProduced] >= w[kSpecWanted]) {
+        // nothing left to produce: the step still runs (it is part of a graph the host has already launched), so it repeats the
+        // last confirmed token at its own position — that KV column is rewritten from the same context, everything behind it is
+        // unspecified anyway — and spec_accept_kernel leaves the state alone. (produced >= 1 here: pos - 1 >= start_pos >= lo.)
+        if (threadIdx.x == 0) {
+            const uint32_t at = pos > lo ? pos - 1 : pos;
+            for (uint32_t j = 0; j < a.T; j++) a.cand[j] = a.hist[at];
+            w[kSpecRunPos] = at;
+        }
+        return;
+    }
+    if (w[kSpecMode] == 1) {
+        if (threadIdx.x == 0) {
+            w[kSpecDrafted] += spec_candidates_provided(a.hist[pos], pos, w[kSpecStart], a.drafts, w[kSpecNDrafts], a.T, a.cand);
+            w[kSpecRunPos] = pos;
+        }
+        return;
+    }
+    // the lookup sees positions [lo, pos]: re-based to start at 0
+    const uint32_t* const h = a.hist + lo;
+    const uint32_t p = pos - lo;
+    int32_t best = -1;
+    for (uint32_t n = w[kSpecNgram]; n >= 1 && best < 0; n--) { // (uniform: every thread reads the same fold[])
+        if (!spec_ngram_applies(p, n)) continue;
+        int32_t hit = -1;
+        for (int64_t i = (int64_t)p - 1 - threadIdx.x; i >= (int64_t)n - 1; i -= kSpecBlock)
+            if (spec_ngram_equal(h, p, n, (uint32_t)i)) {
+                hit = (int32_t)i;
+                break;
+            }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) hit = max(hit, __shfl_xor(hit, off, 64));
+        if ((threadIdx.x & 63) == 0) fold[threadIdx.x >> 6] = hit;
+        __syncthreads();
+        best = fold[0];
+#pragma unroll
+        for (int k = 1; k < kSpecWaves; k++) best = max(best, fold[k]);
+        __syncthreads(); // fold[] is rewritten by the next n
+    }
+    if (threadIdx.x == 0) {
+        w[kSpecDrafted] += spec_candidates_lookup(h, p, best, a.T, a.cand);
+        w[kSpecRunPos] = pos;
+    }
+}
+
+// first maximum wins, the order of arg_combine (kernels_generic.hip); a pair with index INT64_MAX is empty
+__device__ __forceinline__ void spec_arg_fold(float& bv, int64_t& bi, float v, int64_t i) {
+    if (i == INT64_MAX) return;
+    if (bi == INT64_MAX || v > bv || (v == bv && i < bi)) bv = v, bi = i;
+}
+
+// g[j] from the nblk stage-1 partials of logits row j (a wave per row, rows kSpecWaves apart), then thread 0: how many
+// candidates were the greedy choice, what is emitted, and the advance of the state, the history and the counters.
+__global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
+    extern __shared__ uint32_t g[]; // [T]
+    uint32_t* const w = a.words;
+    const uint32_t produced = w[kSpecProduced], wanted = w[kSpecWanted];
+    if (produced >= wanted) return; // (uniform) an idle step changes nothing
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t j = threadIdx.x >> 6; j < a.T; j += kSpecWaves) {
+        const float* vals = a.pval + (uint64_t)j * a.nblk;
+        const int64_t* idxs = a.pidx + (uint64_t)j * a.nblk;
+        float bv = -INFINITY;
+        int64_t bi = INT64_MAX;
+        for (uint32_t i = lane; i < a.nblk; i += 64) spec_arg_fold(bv, bi, vals[i], idxs[i]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(bv, off, 64);
+            const int64_t oi = __shfl_xor(bi, off, 64);
+            spec_arg_fold(bv, bi, ov, oi);
+        }
+        if (lane == 0) g[j] = (uint64_t)bi < a.vocab ? (uint32_t)bi : 0u; // (a row always has vocab > 0 entries: the clamp is for the embedding gather's sake)
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const uint32_t pos = w[kSpecPos];
+    const uint32_t acc = spec_accept(a.cand, g, a.T);
+    const uint32_t m = spec_emit_count(acc, wanted, produced);
+    for (uint32_t k = 0; k < m; k++) {
+        if (produced + k < a.tokens_cap) a.tokens[produced + k] = (int64_t)g[k];
+        if (pos + 1 + k < a.hist_cap) a.hist[pos + 1 + k] = g[k];
+    }
+    w[kSpecTok] = g[m - 1];
+    w[kSpecPos] = pos + m;
+    w[kSpecProduced] = produced + m;
+    w[kSpecSteps] += 1;
+    w[kSpecAccepted] += acc;
+}
+
+} // namespace
+
+void launch_spec_draft(hipStream_t s, const SpecArgs& a) { spec_draft_kernel<<<1, kSpecBlock, 0, s>>>(a); }
+
+void launch_spec_accept(hipStream_t s, const SpecArgs& a) { spec_accept_kernel<<<1, kSpecBlock, a.T * sizeof(uint32_t), s>>>(a); }
+
+} // namespace zgml

@@ -351,6 +351,26 @@ class Session:
             raise RuntimeError("resident_prefill: " + self._backend.last_error())
         return nxt
 
+    def resident_decode_speculative(self, first_token: int, start_pos: int, n_tokens: int, history=None, drafts=None, ngram: int = 2):
+        """Greedy-exact speculative decode on a token_len = T >= 2 plan (include/zgml_hip.h: zgml_hip_resident_decode_speculative):
+        -> (tokens[n_tokens], {"steps", "drafted", "accepted"}). `history`: the tokens at positions 0..start_pos-1 (None: the n-gram
+        lookup sees only this call's tokens). `drafts`: guesses for the tokens at positions start_pos+1.. (provided mode); None:
+        n-gram lookup with suffixes of up to `ngram` tokens."""
+        u32p = C.POINTER(C.c_uint32)
+        opt = capi.SpecDecodeC()
+        hist = np.ascontiguousarray([] if history is None else history, dtype=np.uint32)
+        dr = np.ascontiguousarray([] if drafts is None else drafts, dtype=np.uint32)
+        opt.history, opt.n_history = (hist.ctypes.data_as(u32p) if hist.size else None), hist.size
+        opt.mode, opt.ngram = (0 if drafts is None else 1), ngram
+        opt.drafts, opt.n_drafts = (dr.ctypes.data_as(u32p) if dr.size else None), dr.size
+        toks = np.zeros(n_tokens, np.int64)
+        stats = capi.SpecStatsC()
+        rc = capi.load_hip().zgml_hip_resident_decode_speculative(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
+                                                                   toks.ctypes.data, C.byref(stats))
+        if rc != 0:
+            raise RuntimeError("resident_decode_speculative: " + self._backend.last_error())
+        return toks, {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
+
     def close(self):
         if self.ptr:
             self.lib.zh_session_free(self.ptr)
