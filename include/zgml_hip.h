@@ -630,6 +630,54 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* ha
                                          uint32_t n_tokens, const zgml_spec_decode* opt, int64_t* tokens_out /* [n_tokens] */,
                                          zgml_spec_stats* stats /* may be NULL */);
 
+/* ── Seeded top-k / top-p sampling: the token tail of the resident loops with a sampled pick instead of the first maximum.
+ * The rule is written once, in zgml_amd/csrc/sample.h (the kernels and the CPU tests call the same functions):
+ *   candidates: the k = min(top_k, n) largest logits, value descending, the lower index first among equals (-0 == +0, a NaN
+ *     counts as -inf). The set never exceeds the 256 largest logits, also when top_p alone would admit more: the one deliberate
+ *     deviation from textbook nucleus sampling;
+ *   pick: sequential f32 over the candidates: p_j = exp((v_j - v_0) / temperature), top_p < 1 cuts to the smallest prefix whose
+ *     sum reaches top_p of the total, the token is the first whose running sum exceeds u times the kept sum;
+ *   u: Philox4x32-10, key = seed, counter = (position whose logits are sampled, stream, 0, 0); u = (word 0 >> 8) / 2^24.
+ * u depends on (seed, stream, position) alone, so a generation is the same in one call or several, alone or inside a batch, and
+ * a device pick equals the header's pick over the same logits to the bit. top_k = 1 is the greedy token.
+ * Speculative (zgml_hip_resident_decode_speculative) and sharded (zgml_hip_shard_step) decode stay greedy. */
+typedef struct zgml_sampling {
+    float temperature;   /* > 0 */
+    float top_p;         /* (0, 1]; >= 1: no nucleus cut */
+    uint32_t top_k;      /* 1..256, 0 = 256 */
+    uint32_t n_stop;     /* 0..4 */
+    uint32_t stop[4];    /* < vocab */
+    uint32_t stream;     /* Philox counter word 1 */
+    uint64_t seed;
+} zgml_sampling;
+/* The sampling sibling of zgml_hip_argmax over f32 elements [offset, offset + n) of a program buffer, 1 <= n < 2^32; blocking.
+ * `position` is the Philox counter's word 0; stop tokens are not looked at. For vtable-path callers, and for the first token
+ * after zgml_hip_resident_prefill, whose logits rows stay in the buffer. candidates_out (NULL or 256 words) receives the
+ * candidates' indices in order, *n_candidates_out (may be NULL) their number. Returns the token, -1 with an error on the context
+ * for parameters out of range (below) or a range outside the buffer. */
+int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n,
+                        const zgml_sampling* sampling, uint32_t position, uint32_t* candidates_out /* NULL or [256] */,
+                        uint32_t* n_candidates_out);
+/* zgml_hip_resident_decode with the sampled tail: per token [prep] [plan] [select] [merge + pick + advance], the launch count of
+ * the greedy loop, one graph launch per token. The parameters live in a device table uploaded per call, so one captured graph —
+ * a separate one from the greedy loop's: alternating calls on one program invalidate nothing — serves every parameter set.
+ * A sequence that emits one of its stop tokens records it and then freezes as a batched sequence that has used up its count
+ * does (same token, same position: the remaining steps rewrite the KV column behind the stop token with the same values); the
+ * rest of tokens_out is -1 and *n_produced (may be NULL) counts up to and including the stop token. Continue from a stop, or
+ * from the end, with first_token = the last token at start_pos + *n_produced.
+ * Refused with -1 and an error on the context, before anything is enqueued: temperature not > 0 or top_p not in (0, 1] (a NaN
+ * included), top_k > 256, n_stop > 4, a stop token >= vocab, a token_len > 1 or batched plan, and tokens / positions out of range
+ * under the rules of zgml_hip_resident_decode. */
+int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t first_token, uint32_t start_pos,
+                                     uint32_t n_steps, const zgml_sampling* sampling, int64_t* tokens_out /* [n_steps] */,
+                                     uint32_t* n_produced);
+/* zgml_hip_resident_decode_batch with the sampled tail: sequence b samples with per_seq[b] — its own parameters, stream and stop
+ * set — and n_produced[b] (the array may be NULL) counts its tokens. A sequence frozen by a stop token does not affect the
+ * others. Refusals as above per sequence, and those of zgml_hip_resident_decode_batch; a plain plan is refused. */
+int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                           const uint32_t* n_steps, uint32_t max_steps, const zgml_sampling* per_seq /* [n_seqs] */,
+                                           int64_t* tokens_out /* [n_seqs][max_steps] */, uint32_t* n_produced /* [n_seqs] */);
+
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];
  * otherwise int8), runs `warmup` + `iters` launches round-robin over the ring and returns the

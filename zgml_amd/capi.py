@@ -185,6 +185,20 @@ class SpecStatsC(C.Structure):
     _fields_ = [("steps", C.c_uint32), ("drafted", C.c_uint32), ("accepted", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class SamplingC(C.Structure):
+    """zgml_sampling (include/zgml_hip.h): the parameters of the sampled token tail."""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_uint32), ("n_stop", C.c_uint32),
+                ("stop", C.c_uint32 * 4), ("stream", C.c_uint32), ("seed", C.c_uint64)]
+
+    @staticmethod
+    def of(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, stream: int = 0, stop=()) -> "SamplingC":
+        """stop: up to 4 token ids (more: handed over as they are, for the library to refuse)"""
+        s = SamplingC(temperature=temperature, top_p=top_p, top_k=top_k, n_stop=len(stop), stream=stream, seed=seed)
+        for i, t in enumerate(list(stop)[:4]):
+            s.stop[i] = t
+        return s
+
+
 class RuntimeProfileC(C.Structure):
     _fields_ = [("time_ns", C.c_uint64 * 12), ("backend_op_count", C.c_uint64),
                 ("fallback_op_count", C.c_uint64), ("backend_dispatch_count", C.c_uint64),
@@ -209,6 +223,7 @@ HIP_SYMBOLS = [
     "zgml_hip_program_plan_text", "zgml_hip_program_pin_outputs",
     "zgml_hip_program_set_sequences", "zgml_hip_refresh_dynamic_batch", "zgml_hip_resident_decode_batch",
     "zgml_hip_resident_decode_speculative",
+    "zgml_hip_sample", "zgml_hip_resident_decode_sampled", "zgml_hip_resident_decode_batch_sampled",
 ]
 
 class ShardPointC(C.Structure):
@@ -337,6 +352,12 @@ def _bind_hip(lib: C.CDLL) -> None:
     lib.zgml_hip_resident_decode_batch.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, vp]
     lib.zgml_hip_resident_decode_speculative.restype = i32
     lib.zgml_hip_resident_decode_speculative.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SpecDecodeC), vp, C.POINTER(SpecStatsC)]
+    lib.zgml_hip_sample.restype = C.c_int64
+    lib.zgml_hip_sample.argtypes = [vp, vp, C.c_uint16, u64, u64, C.POINTER(SamplingC), u32, C.POINTER(u32), C.POINTER(u32)]
+    lib.zgml_hip_resident_decode_sampled.restype = i32
+    lib.zgml_hip_resident_decode_sampled.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SamplingC), vp, C.POINTER(u32)]
+    lib.zgml_hip_resident_decode_batch_sampled.restype = i32
+    lib.zgml_hip_resident_decode_batch_sampled.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, C.POINTER(SamplingC), vp, C.POINTER(u32)]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

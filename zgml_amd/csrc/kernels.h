@@ -460,6 +460,35 @@ struct SpecArgs {
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
+// ── seeded top-k / top-p sampling (sample.hip; the rule is sample.h's): the sampled token tail, two launches like launch_argmax ──
+// One row's parameters as the kernels read them (uploaded per call: one captured graph serves every parameter set).
+struct SampleParamsDev {
+    float inv_temperature, top_p;
+    uint32_t top_k, n_stop, stop[4], stream, seed_lo, seed_hi;
+};
+// What the second launch does with the token of row b = blockIdx.y:
+//   state == nullptr       the blocking form: out[0] = token, cand[0] = number of candidates, cand[1 + j] = index of candidate j
+//   state, n_seqs == 0     the single-sequence loop: argmax_stage2's advance (state[0] token, [1] position, [2] produced; tokens[cap]),
+//                          nothing once state[3] is set — a stop token sets it behind its own advance
+//   state, n_seqs == B     the batched loop: argmax_batch_stage2's advance; a stop token leaves the sequence no steps
+// The position whose logits are sampled is `position` / state[1] / state[B + b].
+struct SampleAdvance {
+    uint32_t* state = nullptr;
+    int64_t* tokens = nullptr;
+    uint32_t cap = 0, n_seqs = 0, position = 0;
+    int64_t* out = nullptr;
+    uint32_t* cand = nullptr;
+};
+constexpr uint32_t kSampleMaxSlices = 32; // partial candidate lists per row
+constexpr uint32_t kSampleChunk = 1792;   // logits a select workgroup sorts at a time (with the 256 best so far: 2048 keys)
+inline uint32_t sample_slices(uint64_t n) {
+    const uint64_t s = (n + kSampleChunk - 1) / kSampleChunk;
+    return s < 1 ? 1u : s > kSampleMaxSlices ? kSampleMaxSlices : (uint32_t)s;
+}
+inline size_t sample_scratch_keys(uint64_t n, uint32_t rows) { return (size_t)rows * sample_slices(n) * 256; }
+// `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select: sample_slices(n) sorted lists of the 256 largest keys per row]
+// [merge to the row's candidates + pick + advance]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
+void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv);
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes);
 void launch_f32_to_f16(hipStream_t s, void* dst, const float* src, uint64_t n);
 

@@ -635,6 +635,9 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipFree(ctx->arg_cnt);
     hipFree(ctx->arg_out);
     hipHostFree(ctx->arg_out_host);
+    hipFree(ctx->smp_keys);
+    hipFree(ctx->smp_params);
+    hipFree(ctx->smp_out);
     if (ctx->handoff_flag) hipHostFree(ctx->handoff_flag);
     hipStreamDestroy(ctx->stream);
     delete ctx;

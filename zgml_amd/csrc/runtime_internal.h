@@ -119,6 +119,11 @@ struct zgml_hip_ctx {
     uint32_t* arg_cnt = nullptr; // arrival counter of the fused token tail (launch_argmax_tail), re-armed by its last workgroup
     int64_t* arg_out = nullptr;
     int64_t* arg_out_host = nullptr; // pinned
+    // zgml_hip_sample's scratch, allocated by its first call: the select launch's partial lists (kernels.h: sample_scratch_keys of
+    // one row), the parameter row, and [token | candidate count | 256 candidate indices]
+    uint64_t* smp_keys = nullptr;
+    SampleParamsDev* smp_params = nullptr;
+    uint32_t* smp_out = nullptr; // [0, 1]: the token (64 bits); [2]: count; [3, 259): indices
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
     // Fused launches (q/k/v projection + decode attention): ONE host-visible word every bounded in-launch wait sets when it
     // gives up (pinned, device-mapped: the host reads it after any synchronisation without a copy). A set word means the

@@ -4,6 +4,7 @@
 // end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_graph), resident_end.
 // No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's in their own files.
 #include "runtime_internal.h"
+#include "sample.h"
 #include "spec.h"
 
 struct zgml_resident {
@@ -39,6 +40,12 @@ struct zgml_resident {
     uint32_t* spec = nullptr;
     uint32_t* hist = nullptr;
     uint32_t* drafts = nullptr;
+    // sampled tail (zgml_hip_resident_decode_sampled / _batch_sampled), allocated by the first such call: one parameter row and
+    // one set of partial candidate lists per sequence; the loop's own graph (the greedy loop's stays valid beside it)
+    SampleParamsDev* sparams = nullptr;
+    uint64_t* skeys = nullptr;
+    hipGraph_t graph_sampled = nullptr;
+    hipGraphExec_t graph_sampled_exec = nullptr;
 };
 using Resident = zgml_resident;
 
@@ -53,6 +60,9 @@ void free_resident_graph(zgml_hip_program* p) {
     if (r->graph_multi_exec) hipGraphExecDestroy(r->graph_multi_exec);
     if (r->graph_multi) hipGraphDestroy(r->graph_multi);
     r->graph_multi_exec = nullptr, r->graph_multi = nullptr, r->multi_n = 0;
+    if (r->graph_sampled_exec) hipGraphExecDestroy(r->graph_sampled_exec);
+    if (r->graph_sampled) hipGraphDestroy(r->graph_sampled);
+    r->graph_sampled_exec = nullptr, r->graph_sampled = nullptr;
 }
 
 void free_resident(zgml_hip_program* p) {
@@ -77,6 +87,8 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->spec);
     hipFree(r->hist);
     hipFree(r->drafts);
+    hipFree(r->sparams);
+    hipFree(r->skeys);
     delete r;
     p->resident = nullptr;
 }
@@ -123,6 +135,38 @@ void resident_end(zgml_hip_program* p, uint64_t steps, uint64_t launches_per_ste
     p->profile.call_count += steps;
     p->profile.backend_op_count += steps * p->ops.size();
     p->profile.backend_dispatch_count += steps * launches_per_step;
+}
+
+// a caller's zgml_sampling as the kernels read it; false (with the error on the context) for what the header refuses.
+// vocab == 0: the stop tokens are not looked at (zgml_hip_sample)
+bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampling* sp, uint32_t vocab, SampleParamsDev* out) {
+    if (!sp) {
+        ctx->fail(who + ": no sampling parameters");
+        return false;
+    }
+    if (!(sp->temperature > 0.0f) || !(sp->top_p > 0.0f && sp->top_p <= 1.0f)) {
+        ctx->fail(who + ": temperature must be > 0 and top_p in (0, 1]");
+        return false;
+    }
+    if (sp->top_k > kSampleMaxK || sp->n_stop > kSampleMaxStop) {
+        ctx->fail(who + ": top_k must be at most " + std::to_string(kSampleMaxK) + " and n_stop at most " + std::to_string(kSampleMaxStop));
+        return false;
+    }
+    for (uint32_t i = 0; vocab && i < sp->n_stop; i++)
+        if (sp->stop[i] >= vocab) {
+            ctx->fail(who + ": stop token out of range");
+            return false;
+        }
+    *out = SampleParamsDev{1.0f / sp->temperature, sp->top_p, sp->top_k, vocab ? sp->n_stop : 0, {sp->stop[0], sp->stop[1], sp->stop[2], sp->stop[3]},
+                           sp->stream, (uint32_t)sp->seed, (uint32_t)(sp->seed >> 32)};
+    return true;
+}
+
+// the sampled loops' device blocks: `rows` parameter rows and partial candidate lists
+bool ensure_sample_blocks(zgml_hip_ctx* ctx, Resident* r, uint32_t rows) {
+    if (r->sparams) return true;
+    return CTX_CHECK(ctx, hipMalloc((void**)&r->sparams, (size_t)rows * sizeof(SampleParamsDev))) &&
+           CTX_CHECK(ctx, hipMalloc((void**)&r->skeys, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t)));
 }
 
 } // namespace
@@ -365,6 +409,200 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
     for (uint32_t b = 0; ok && b < B; b++)
         for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
     resident_end(p, steps, p->plan.size() + 3); // per step [batched prep] [plan] [pick x 2]
+    return ok ? 0 : -1;
+}
+
+
+// ── the sampled tail (contract: include/zgml_hip.h; rule: sample.h; kernels: sample.hip) ──
+
+int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx, uint64_t offset, uint64_t n, const zgml_sampling* sampling,
+                        uint32_t position, uint32_t* candidates_out, uint32_t* n_candidates_out) {
+    if (!ctx || !p) return -1;
+    if (buf_idx >= p->bufs.size() || !p->bufs[buf_idx] || offset > p->sizes[buf_idx] || n > p->sizes[buf_idx] - offset || !n || n > 0xFFFFFFFFull) {
+        ctx->fail("sample: the range must lie inside the buffer and hold 1 .. 2^32 - 1 elements");
+        return -1;
+    }
+    SampleParamsDev sp;
+    if (!sampling_params(ctx, "sample", sampling, 0, &sp)) return -1;
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    constexpr size_t out_words = 3 + kSampleMaxK;
+    if (!ctx->smp_keys && (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_keys, (size_t)kSampleMaxSlices * kSampleMaxK * sizeof(uint64_t))) ||
+                           !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_params, sizeof(SampleParamsDev))) ||
+                           !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_out, out_words * 4))))
+        return -1;
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
+    SampleAdvance adv;
+    adv.position = position, adv.out = (int64_t*)ctx->smp_out, adv.cand = ctx->smp_out + 2;
+    launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
+    uint32_t got[out_words];
+    hipMemcpyAsync(got, ctx->smp_out, sizeof(got), hipMemcpyDeviceToHost, s);
+    if (!CTX_CHECK(ctx, hipStreamSynchronize(s)) || !ctx->handoff_ok("sample")) return -1;
+    const uint32_t kc = std::min<uint32_t>(got[2], kSampleMaxK);
+    if (n_candidates_out) *n_candidates_out = kc;
+    if (candidates_out) memcpy(candidates_out, got + 3, (size_t)kc * 4);
+    int64_t token;
+    memcpy(&token, got, 8);
+    return token;
+}
+
+// zgml_hip_resident_decode with [select] [merge + pick + advance] in the place of the two argmax stages
+int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_steps,
+                                     const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced) {
+    if (!ctx || !p || !p->resident || (n_steps && !tokens_out)) return -1;
+    Resident* r = p->resident;
+    if (n_produced) *n_produced = 0;
+    if (r->n_seqs) {
+        ctx->fail("resident_decode_sampled: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch_sampled)");
+        return -1;
+    }
+    if (r->token_len != 1) {
+        ctx->fail("resident_decode_sampled: the program is a token_len > 1 plan");
+        return -1;
+    }
+    SampleParamsDev sp;
+    if (!sampling_params(ctx, "resident_decode_sampled", sampling, r->vocab, &sp)) return -1;
+    if (first_token >= r->vocab || (uint64_t)start_pos + n_steps > r->max_seq) {
+        ctx->fail("resident_decode_sampled: token or position out of range");
+        return -1;
+    }
+    if (!n_steps) return 0;
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    resident_begin(p, [&] {
+        return positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; });
+    });
+    if (!ensure_sample_blocks(ctx, r, 1)) return -1;
+    if (r->tokens_cap < n_steps) {
+        hipStreamSynchronize(s);
+        hipFree(r->tokens);
+        r->tokens = nullptr, r->tokens_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_steps * 8))) return -1;
+        r->tokens_cap = n_steps;
+        free_resident_graph(p); // the graphs baked the old pointer/cap
+    }
+    const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
+                             p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
+    const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
+    SampleAdvance adv;
+    adv.state = r->state, adv.tokens = r->tokens, adv.cap = r->tokens_cap;
+    auto one_token = [&](hipStream_t st) {
+        launch_resident_prep(st, a, total);
+        run_plan(p, st, 0, p->plan.size());
+        launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
+    };
+    const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // ([3]: set by a stop token)
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, &sp, sizeof(sp), hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_steps * 8, s))) // (-1: what a stopped sequence leaves behind its stop token)
+        return -1;
+    if (ctx->opt_graph && !r->graph_sampled_exec) {
+        hipStreamSynchronize(s); // (the copies above read this stack frame: none in flight when the capture begins)
+        capture_graph(ctx, s, "resident_sampled", [&] { one_token(s); }, &r->graph_sampled, &r->graph_sampled_exec); // (failed: eager below)
+    }
+    for (uint32_t i = 0; i < n_steps; i++) {
+        if (r->graph_sampled_exec)
+            hipGraphLaunch(r->graph_sampled_exec, s);
+        else
+            one_token(s);
+    }
+    uint32_t st1[4] = {0, 0, 0, 0};
+    hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(st1, r->state, sizeof(st1), hipMemcpyDeviceToHost, s);
+    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    ok = ok && ctx->handoff_ok("resident_decode_sampled");
+    if (ok && n_produced) *n_produced = std::min(st1[2], n_steps);
+    resident_end(p, n_steps, p->plan.size() + 3); // per token [prep] [plan] [select] [merge + pick + advance]
+    return ok ? 0 : -1;
+}
+
+// zgml_hip_resident_decode_batch with the sampled tail, blockIdx.y = sequence in both of its launches
+int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                           const uint32_t* n_steps, uint32_t max_steps, const zgml_sampling* per_seq, int64_t* tokens_out,
+                                           uint32_t* n_produced) {
+    if (!ctx || !p) return -1;
+    Resident* r = p->resident;
+    if (!r || !r->n_seqs || !p->n_seqs) {
+        ctx->fail("resident_decode_batch_sampled: not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
+        return -1;
+    }
+    if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
+    const uint32_t B = r->n_seqs;
+    std::vector<SampleParamsDev> sp(B);
+    for (uint32_t b = 0; b < B; b++)
+        if (!sampling_params(ctx, "resident_decode_batch_sampled (sequence " + std::to_string(b) + ")", per_seq ? per_seq + b : nullptr, r->vocab, &sp[b])) return -1;
+    uint32_t steps = 0;
+    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
+    if (steps > max_steps) {
+        ctx->fail("resident_decode_batch_sampled: n_steps exceeds max_steps");
+        return -1;
+    }
+    // as zgml_hip_resident_decode_batch: a sequence that idles behind its count repeats its step at the position behind its last
+    // token. (One frozen by a stop token idles at a position its own count covers.)
+    std::vector<uint32_t> last_pos(B);
+    for (uint32_t b = 0; b < B; b++) {
+        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b];
+        const bool idles = n_steps[b] < steps;
+        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
+            ctx->fail("resident_decode_batch_sampled: token or position out of range (sequence " + std::to_string(b) + ")");
+            return -1;
+        }
+        last_pos[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
+    }
+    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
+    for (uint32_t b = 0; n_produced && b < B; b++) n_produced[b] = 0;
+    if (!steps) return 0;
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    resident_begin(p, [&] {
+        return positions_in_bounds(p, 1, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) && positions_in_bounds(p, 1, [&](uint32_t i) { return last_pos[p->op_seq[i]]; });
+    });
+    if (!ensure_sample_blocks(ctx, r, B)) return -1;
+    if (r->btokens_cap < (uint64_t)B * steps) {
+        hipStreamSynchronize(s);
+        hipFree(r->btokens);
+        r->btokens = nullptr, r->btokens_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->btokens, (size_t)B * steps * 8))) return -1;
+        r->btokens_cap = (uint64_t)B * steps;
+        free_resident_graph(p); // the graphs baked the old pointer
+    }
+    const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
+                                  p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
+    const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
+    SampleAdvance adv;
+    adv.state = r->bstate, adv.tokens = r->btokens, adv.n_seqs = B;
+    auto one_step = [&](hipStream_t st) {
+        launch_resident_batch_prep(st, a, total);
+        run_plan(p, st, 0, p->plan.size());
+        launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
+    };
+    std::vector<uint32_t> st0((size_t)4 * B + 1, 0), st1((size_t)4 * B + 1, 0);
+    for (uint32_t b = 0; b < B; b++) st0[b] = first_tokens[b], st0[B + b] = start_pos[b], st0[2 * B + b] = n_steps[b];
+    st0[4 * B] = steps; // row length of the device token table of this call
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, sp.data(), sp.size() * sizeof(SampleParamsDev), hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
+        return -1;
+    if (ctx->opt_graph && !r->graph_sampled_exec) {
+        hipStreamSynchronize(s); // (as the greedy batched loop: no pageable copy in flight when the capture begins)
+        capture_graph(ctx, s, "resident_batch_sampled", [&] { one_step(s); }, &r->graph_sampled, &r->graph_sampled_exec); // (failed: eager below)
+    }
+    for (uint32_t i = 0; i < steps; i++) {
+        if (r->graph_sampled_exec)
+            hipGraphLaunch(r->graph_sampled_exec, s);
+        else
+            one_step(s);
+    }
+    std::vector<int64_t> got((size_t)B * steps);
+    hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
+    hipMemcpyAsync(st1.data(), r->bstate, st1.size() * 4, hipMemcpyDeviceToHost, s);
+    bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    ok = ok && ctx->handoff_ok("resident_decode_batch_sampled");
+    for (uint32_t b = 0; ok && b < B; b++) {
+        for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
+        if (n_produced) n_produced[b] = std::min(st1[3 * B + b], n_steps[b]);
+    }
+    resident_end(p, steps, p->plan.size() + 3); // per step [batched prep] [plan] [select] [merge + pick + advance]
     return ok ? 0 : -1;
 }
 

@@ -1,0 +1,156 @@
+// sample.h — the rule of seeded top-k / top-p sampling (zgml_hip_sample, zgml_hip_resident_decode_sampled, _batch_sampled;
+// include/zgml_hip.h), written ONCE: the kernels of sample.hip call these functions and so does the host probe
+// tests/cpp/sample_probe.cpp (tests/test_sample_host.py compares it with a float64 numpy model of the same rule). Plain C++, no
+// device intrinsics: the header compiles under g++ as it stands. Both sides must be built with -ffp-contract=off: every
+// operation below is then one correctly rounded IEEE operation or an explicit fmaf, and device and host agree to the bit.
+//
+// THE CANDIDATES. A logit v at vocabulary index i has the 64-bit key (ordered(v + 0.0f) << 32) | (0xFFFFFFFF - i): `ordered` is
+// the monotone float -> u32 map, + 0.0f makes -0 equal +0 (as the argmax's `>` does), a NaN counts as -inf. The candidates are
+// the k = min(top_k, n) largest keys, descending: value descending, the lower index first among equals. Keys are unique, so the
+// list does not depend on how a search for it is parallelised. top_k is 1..256 (0 = 256).
+//   DEVIATION from textbook nucleus sampling, the one deliberate one: the candidate set never exceeds the 256 largest logits,
+//   also when top_p alone would admit more of them.
+//
+// THE PICK, sequential and in f32 over the ordered candidates v_0 >= v_1 >= ...: p_j = sample_exp((v_j - v_0) * inv_temperature),
+// total = the left-to-right sum; top_p < 1: m = the smallest prefix whose running sum is >= top_p * total, else m = k; the token
+// is the first j < m whose running sum is > u * cum_m (cum_m: the running sum of the m), falling back to m - 1.
+// inv_temperature = 1.0f / temperature is computed once, on the host.
+//   expf / __expf may NOT be used for p_j: the host's libm and the device's expansion differ in the last bits, and one differing
+//   bit in a running sum can move the pick to the neighbouring token. sample_exp is this header's own.
+//
+// THE RANDOM NUMBER. Philox4x32-10, key (seed low word, seed high word), counter (position, stream, 0, 0), where `position` is
+// the position whose logits are sampled; u = (word 0 >> 8) * 2^-24 in [0, 1). u depends on (seed, stream, position) alone: a
+// generation is the same in one call or several, alone or inside a batch.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#define ZGML_SAMPLE_FN __host__ __device__ inline
+#else
+#define ZGML_SAMPLE_FN inline
+#endif
+
+namespace zgml {
+
+constexpr uint32_t kSampleMaxK = 256;   // the candidate set's upper bound
+constexpr uint32_t kSampleMaxStop = 4;  // stop tokens per sequence
+
+ZGML_SAMPLE_FN uint32_t sample_f32_bits(float v) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    return b;
+}
+ZGML_SAMPLE_FN float sample_bits_f32(uint32_t b) {
+    float v;
+    memcpy(&v, &b, 4);
+    return v;
+}
+
+// monotone float -> u32: a < b  <=>  ordered(a) < ordered(b); -0 and +0 map to one word, a NaN to -inf's
+ZGML_SAMPLE_FN uint32_t sample_ordered(float v) {
+    v = v + 0.0f;
+    if (v != v) v = -INFINITY;
+    const uint32_t b = sample_f32_bits(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+ZGML_SAMPLE_FN uint64_t sample_key(float v, uint32_t i) { return ((uint64_t)sample_ordered(v) << 32) | (uint64_t)(0xFFFFFFFFu - i); }
+// (every key of a logit is > 0 — ordered(-inf) is 0x007FFFFF — so 0 pads a list below all of them)
+ZGML_SAMPLE_FN float sample_key_value(uint64_t key) {
+    const uint32_t o = (uint32_t)(key >> 32);
+    return sample_bits_f32((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+ZGML_SAMPLE_FN uint32_t sample_key_index(uint64_t key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+// the number of candidates of a row of n logits
+ZGML_SAMPLE_FN uint32_t sample_top_k(uint32_t top_k, uint64_t n) {
+    const uint32_t k = top_k == 0 || top_k > kSampleMaxK ? kSampleMaxK : top_k;
+    return n < k ? (uint32_t)n : k;
+}
+
+// e^x for x <= 0: n = rint(x / ln 2), r = x - n ln 2 (ln 2 in two parts, two fmaf), a degree-6 Horner polynomial in explicit
+// fmaf, ldexpf. Arguments below -87 (and a NaN) give 0: the smallest result is e^-87 = 1.40 * 2^-126, so no denormal is ever
+// produced. Maximum relative error against exp in float64: 1.9e-7 on [-80, 0].
+ZGML_SAMPLE_FN float sample_exp(float x) {
+    if (!(x >= -87.0f)) return 0.0f;
+    const float n = rintf(x * 1.44269504088896341f);
+    float r = fmaf(n, -0.693145751953125f, x);
+    r = fmaf(n, -1.42860682030941723e-6f, r);
+    float p = 1.0f / 720.0f;
+    p = fmaf(p, r, 1.0f / 120.0f);
+    p = fmaf(p, r, 1.0f / 24.0f);
+    p = fmaf(p, r, 1.0f / 6.0f);
+    p = fmaf(p, r, 0.5f);
+    p = fmaf(p, r, 1.0f);
+    p = fmaf(p, r, 1.0f);
+    return ldexpf(p, (int)n);
+}
+
+// the unnormalised probability of a candidate of value v under the largest candidate v0
+ZGML_SAMPLE_FN float sample_prob(float v, float v0, float inv_temperature) { return sample_exp((v - v0) * inv_temperature); }
+
+// the pick over p[0..k): the candidate's rank j. (The kernel fills p with all its threads — sample_prob is a pure function — and
+// walks this alone; the probe does both alone.)
+ZGML_SAMPLE_FN uint32_t sample_pick_probs(const float* p, uint32_t k, float top_p, float u) {
+    float total = 0.0f;
+    for (uint32_t j = 0; j < k; j++) total = total + p[j];
+    uint32_t m = k;
+    float cum = total;
+    if (top_p < 1.0f) {
+        const float thr = top_p * total;
+        float run = 0.0f;
+        for (uint32_t j = 0; j < k; j++) {
+            run = run + p[j];
+            if (run >= thr) {
+                m = j + 1, cum = run;
+                break;
+            }
+        }
+    }
+    const float t = u * cum;
+    float run = 0.0f;
+    for (uint32_t j = 0; j < m; j++) {
+        run = run + p[j];
+        if (run > t) return j;
+    }
+    return m - 1;
+}
+
+// ... from the ordered candidate keys (k >= 1, k <= kSampleMaxK)
+ZGML_SAMPLE_FN uint32_t sample_pick(const uint64_t* keys, uint32_t k, float inv_temperature, float top_p, float u) {
+    float p[kSampleMaxK];
+    const float v0 = sample_key_value(keys[0]);
+    for (uint32_t j = 0; j < k; j++) p[j] = sample_prob(sample_key_value(keys[j]), v0, inv_temperature);
+    return sample_pick_probs(p, k, top_p, u);
+}
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+ZGML_SAMPLE_FN void sample_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+    for (int round = 0; round < 10; round++) {
+        const uint64_t m0 = (uint64_t)0xD2511F53u * c0, m1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(m1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(m0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)m1, c3 = (uint32_t)m0, c0 = n0, c2 = n2;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+ZGML_SAMPLE_FN float sample_u_of_word(uint32_t word0) { return (float)(word0 >> 8) * 5.9604644775390625e-8f; } // 2^-24: exact
+
+ZGML_SAMPLE_FN float sample_uniform(uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, uint32_t position) {
+    const uint32_t ctr[4] = {position, stream, 0, 0}, key[2] = {seed_lo, seed_hi};
+    uint32_t w[4];
+    sample_philox4x32_10(ctr, key, w);
+    return sample_u_of_word(w[0]);
+}
+
+ZGML_SAMPLE_FN bool sample_is_stop(uint32_t token, uint32_t n_stop, const uint32_t* stop) {
+    for (uint32_t i = 0; i < n_stop && i < kSampleMaxStop; i++)
+        if (stop[i] == token) return true;
+    return false;
+}
+
+} // namespace zgml

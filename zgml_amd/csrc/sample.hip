@@ -1,0 +1,123 @@
+// sample.hip — the sampled token tail (zgml_hip_sample, zgml_hip_resident_decode_sampled / _batch_sampled, runtime_resident.hip):
+// two launches per row of logits, the shape of launch_argmax / launch_argmax_batch. The rule — candidate order, pick, random
+// number — is sample.h's; here is only how workgroups find the candidates. Keys are unique 64-bit words (sample_key), so the
+// largest 256 of a row are one well-defined list whatever the slicing: nothing below depends on arrival order, no workgroup
+// waits for another and there is no last-arriver stage.
+//   [select]  grid (slices, rows), 256 threads: a workgroup walks its slice of the row in chunks of kSampleChunk logits; the 256
+//             best keys so far and the chunk's keys are one 2048-key bitonic sort in LDS (16 KiB); the slice's 256 largest keys,
+//             descending, go to the scratch (0 pads a slice of fewer: every real key is > 0).
+//   [merge + pick + advance]  grid (1, rows), 1024 threads: the slices' lists — at most 32 x 256 keys, 64 KiB of LDS — are loaded
+//             with every second list reversed, which is the state of a bitonic sort after its 256-runs: only the merge stages
+//             from 512 up remain. Then the threads fill p[j] (sample_prob), thread 0 walks sample_pick_probs and advances.
+#include "kernels.h"
+#include "sample.h"
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+namespace zgml {
+namespace {
+
+constexpr uint32_t kSelBlock = 256, kSelKeys = 2048;   // kSelKeys = kSampleMaxK + kSampleChunk
+constexpr uint32_t kMergeBlock = 1024, kMergeKeys = kSampleMaxSlices * kSampleMaxK;
+static_assert(kSelKeys == kSampleMaxK + kSampleChunk, "a select sort holds the best so far and one chunk");
+static_assert(kMergeKeys * sizeof(uint64_t) <= 65536, "the merge's lists must fit the static LDS limit");
+
+// one compare-exchange stage (k, j) of a bitonic sort that ends DESCENDING, over `pairs` = keys / 2 pairs; ends with a barrier
+template <uint32_t kThreads>
+__device__ __forceinline__ void bitonic_stage(uint64_t* s, uint32_t pairs, uint32_t k, uint32_t j) {
+    for (uint32_t t = threadIdx.x; t < pairs; t += kThreads) {
+        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), x = i | j;
+        const uint64_t a = s[i], b = s[x];
+        if ((i & k) == 0 ? a < b : a > b) s[i] = b, s[x] = a;
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(kSelBlock) sample_select_kernel(const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part) {
+    __shared__ uint64_t s[kSelKeys];
+    const float* row = v + (uint64_t)blockIdx.y * n;
+    const uint64_t lo = (uint64_t)blockIdx.x * len, hi = lo + len < n ? lo + len : n; // (lo may lie behind n: an empty slice, all pads)
+    for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) s[t] = 0;
+    for (uint64_t base = lo; base == lo || base < hi; base += kSampleChunk) {
+        for (uint32_t t = threadIdx.x; t < kSampleChunk; t += kSelBlock) {
+            const uint64_t i = base + t;
+            s[kSampleMaxK + t] = i < hi ? sample_key(row[i], (uint32_t)i) : 0;
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= kSelKeys; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) bitonic_stage<kSelBlock>(s, kSelKeys / 2, k, j);
+    }
+    uint64_t* out = part + ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * kSampleMaxK;
+    for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) out[t] = s[t];
+}
+
+__global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const uint64_t* __restrict__ part, uint32_t n, uint32_t slices, uint32_t P,
+                                                                        const SampleParamsDev* __restrict__ params, SampleAdvance adv) {
+    __shared__ uint64_t s[kMergeKeys];
+    const uint32_t b = blockIdx.y;
+    const uint64_t* lists = part + (uint64_t)b * slices * kSampleMaxK;
+    for (uint32_t t = threadIdx.x; t < P; t += kMergeBlock) { // P = the power of two >= slices * 256, <= kMergeKeys
+        const uint32_t l = t >> 8, off = t & 255;
+        s[t] = l < slices ? lists[(uint64_t)l * kSampleMaxK + ((l & 1) ? 255 - off : off)] : 0;
+    }
+    __syncthreads();
+    for (uint32_t k = 2 * kSampleMaxK; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) bitonic_stage<kMergeBlock>(s, P / 2, k, j);
+    // s[0, 256): the row's largest keys, descending
+    const SampleParamsDev& sp = params[b]; // (read in place: a copy with its indexed stop[] would live in scratch)
+    const uint32_t kc = sample_top_k(sp.top_k, n);
+    float* const p = (float*)(s + kSampleMaxK); // (the keys behind the first 256 are done with)
+    const float v0 = sample_key_value(s[0]);
+    if (threadIdx.x < kc) {
+        p[threadIdx.x] = sample_prob(sample_key_value(s[threadIdx.x]), v0, sp.inv_temperature);
+        if (adv.cand) adv.cand[1 + threadIdx.x] = sample_key_index(s[threadIdx.x]);
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (adv.cand) adv.cand[0] = kc;
+    if (!adv.state) {
+        const float u = sample_uniform(sp.seed_lo, sp.seed_hi, sp.stream, adv.position);
+        adv.out[0] = (int64_t)sample_key_index(s[sample_pick_probs(p, kc, sp.top_p, u)]);
+        return;
+    }
+    if (adv.n_seqs == 0) { // argmax_stage2's advance; state[3]: a stop token was emitted, the sequence is frozen
+        uint32_t* const st = adv.state;
+        if (st[3]) return;
+        const float u = sample_uniform(sp.seed_lo, sp.seed_hi, sp.stream, st[1]);
+        const uint32_t next = sample_key_index(s[sample_pick_probs(p, kc, sp.top_p, u)]);
+        const uint32_t produced = st[2];
+        if (produced < adv.cap) adv.tokens[produced] = (int64_t)next;
+        st[0] = next;
+        st[1] += 1;
+        st[2] = produced + 1;
+        if (sample_is_stop(next, sp.n_stop, sp.stop)) st[3] = 1;
+        return;
+    }
+    // argmax_batch_stage2's advance: only while the sequence has steps left (else it repeats the same token at the same position)
+    uint32_t* const st = adv.state;
+    const uint32_t B = adv.n_seqs;
+    const uint32_t left = st[2 * B + b], produced = st[3 * B + b], cap = st[4 * B];
+    if (left == 0) return;
+    const float u = sample_uniform(sp.seed_lo, sp.seed_hi, sp.stream, st[B + b]);
+    const uint32_t next = sample_key_index(s[sample_pick_probs(p, kc, sp.top_p, u)]);
+    if (produced < cap) adv.tokens[(uint64_t)b * cap + produced] = (int64_t)next;
+    st[b] = next;
+    st[B + b] += 1;
+    st[2 * B + b] = sample_is_stop(next, sp.n_stop, sp.stop) ? 0 : left - 1;
+    st[3 * B + b] = produced + 1;
+}
+
+} // namespace
+
+void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv) {
+    if (!n || n > 0xFFFFFFFFull || !rows) return; // (the callers refuse these)
+    const uint32_t slices = sample_slices(n);
+    const uint32_t len = (uint32_t)((n + slices - 1) / slices);
+    uint32_t P = kSampleMaxK;
+    while (P < slices * kSampleMaxK) P <<= 1;
+    sample_select_kernel<<<dim3(slices, rows), kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch);
+    sample_merge_pick_kernel<<<dim3(1, rows), kMergeBlock, 0, s>>>(scratch, (uint32_t)n, slices, P, params, adv);
+}
+
+} // namespace zgml

@@ -268,6 +268,23 @@ class BatchSession:
             raise RuntimeError("resident_decode_batch: " + self._backend.last_error())
         return toks[:, :max_steps]
 
+    def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings):
+        """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
+        -> (tokens[B, max(n_steps)], n_produced[B]); row b holds n_produced[b] tokens, then -1."""
+        u32p = C.POINTER(C.c_uint32)
+        t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_steps, dtype=np.uint32), (self.n_seqs,)))
+        assert t.size == self.n_seqs and p.size == self.n_seqs and len(samplings) == self.n_seqs
+        sp = (capi.SamplingC * self.n_seqs)(*samplings)
+        max_steps = int(n.max()) if n.size else 0
+        toks = np.full((self.n_seqs, max(1, max_steps)), -1, np.int64)
+        produced = np.zeros(self.n_seqs, np.uint32)
+        rc = capi.load_hip().zgml_hip_resident_decode_batch_sampled(self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p),
+                                                                    n.ctypes.data_as(u32p), max_steps, sp, toks.ctypes.data, produced.ctypes.data_as(u32p))
+        if rc != 0:
+            raise RuntimeError("resident_decode_batch_sampled: " + self._backend.last_error())
+        return toks[:, :max_steps], produced
+
     def close(self):
         if self.ptr:
             self.lib.zh_session_free(self.ptr)
@@ -341,6 +358,16 @@ class Session:
         if rc != 0:
             raise RuntimeError("resident_decode: " + self._backend.last_error())
         return toks
+
+    def resident_decode_sampled(self, first_token: int, start_pos: int, n_steps: int, sampling: "capi.SamplingC"):
+        """zgml_hip_resident_decode_sampled -> (tokens[n_steps], n_produced): -1 behind a stop token."""
+        toks = np.full(max(1, n_steps), -1, np.int64)
+        produced = C.c_uint32(0)
+        rc = capi.load_hip().zgml_hip_resident_decode_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_steps, C.byref(sampling),
+                                                              toks.ctypes.data, C.byref(produced))
+        if rc != 0:
+            raise RuntimeError("resident_decode_sampled: " + self._backend.last_error())
+        return toks[:n_steps], int(produced.value)
 
     def resident_prefill(self, tokens, start_pos: int) -> int:
         """One chunk of a token_len = N plan with on-device embedding gather / mask / RoPE rows / argmax."""

@@ -516,6 +516,14 @@ class Backend:
     def argmax(self, handle, buf_idx: int, offset: int, n: int) -> int:
         return int(self._lib.zgml_hip_argmax(self.ctx, handle, buf_idx, offset, n))
 
+    def sample(self, handle, buf_idx: int, offset: int, n: int, sampling: "capi.SamplingC", position: int):
+        """zgml_hip_sample: -> (token, candidate indices in order). RuntimeError for what the library refuses."""
+        cand, kc = (C.c_uint32 * 256)(), C.c_uint32(0)
+        tok = int(self._lib.zgml_hip_sample(self.ctx, handle, buf_idx, offset, n, C.byref(sampling), position, cand, C.byref(kc)))
+        if tok < 0:
+            raise RuntimeError("sample: " + self.last_error())
+        return tok, list(cand[:kc.value])
+
     def synchronize(self) -> None:
         self._lib.zgml_hip_synchronize(self.ctx)
 
