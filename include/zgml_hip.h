@@ -640,7 +640,8 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* ha
  *   u: Philox4x32-10, key = seed, counter = (position whose logits are sampled, stream, 0, 0); u = (word 0 >> 8) / 2^24.
  * u depends on (seed, stream, position) alone, so a generation is the same in one call or several, alone or inside a batch, and
  * a device pick equals the header's pick over the same logits to the bit. top_k = 1 is the greedy token.
- * Speculative (zgml_hip_resident_decode_speculative) and sharded (zgml_hip_shard_step) decode stay greedy. */
+ * Speculative decode samples through zgml_hip_resident_decode_speculative_sampled (below); only sharded decode
+ * (zgml_hip_shard_step) stays greedy. */
 typedef struct zgml_sampling {
     float temperature;   /* > 0 */
     float top_p;         /* (0, 1]; >= 1: no nucleus cut */
@@ -677,6 +678,46 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle
 int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens, const uint32_t* start_pos,
                                            const uint32_t* n_steps, uint32_t max_steps, const zgml_sampling* per_seq /* [n_seqs] */,
                                            int64_t* tokens_out /* [n_seqs][max_steps] */, uint32_t* n_produced /* [n_seqs] */);
+
+/* ── Sampled speculative decode: zgml_hip_resident_decode_speculative with seeded top-k / top-p picks in the verify step.
+ * Verify step. A step at (tok, pos) is that of zgml_hip_resident_decode_speculative with one change: g[j] is the pick of
+ *   zgml_amd/csrc/sample.h over logits row j with u from counter word 0 = pos + j — the position whose logits are sampled, the
+ *   convention of zgml_hip_resident_decode_sampled. The candidates, the pads, the draft modes, the acceptance rule (the longest
+ *   prefix c[1..a] with c[j] == g[j - 1]) and which KV columns are valid afterwards are unchanged. Per step [draft] [prep, T
+ *   tokens] [plan] [select over T rows] [merge + pick over T rows] [accept + advance]: one launch more than the greedy step,
+ *   one graph launch per step, a graph of its own (greedy and sampled speculative calls and zgml_hip_resident_prefill alternate
+ *   on one program and invalidate nothing). All T rows read the one parameter set.
+ * Exactness. u depends on (seed, stream, position) alone and the candidate list of a row is one well-defined list, so the token
+ *   sampled at a position is a deterministic function of that position's logits bits, exactly as the first maximum is. Every
+ *   emitted token is the header's pick over the plan's own logits row over a confirmed context at its own position: drafts change
+ *   how many steps run, and by the rule never which tokens come out; a generation is the same in one call or several. This is
+ *   NOT stochastic (rejection-sampling) acceptance: that would accept more drafts of a stochastic draft model but make the stream
+ *   depend on the drafts; here no draft probabilities exist or are needed.
+ *   What "the plan's own logits" are to the bit: a row's logits depend neither on the tokens of the other rows nor on which row
+ *   of its step it is, but a KV column stored as a later row of a step and the same column stored as row 0 differ in the last
+ *   bit on the device, so how the confirmed context was grouped into steps — which the drafts decide — moves a position's logits
+ *   by about 1e-7 of their range. The same drafts give the same stream, always; other drafts give the same stream unless a pick's
+ *   u lands within that difference of a cumulative boundary (measured: one token of 256 in one of eight SmolLM-135M
+ *   configurations, the streams equal again from the next token; none at Llama-2-7B).
+ *   top_k = 1 gives exactly the tokens (and statistics) of zgml_hip_resident_decode_speculative.
+ *   Against zgml_hip_resident_decode_sampled on a token_len = 1 plan with the same parameters the stream is the same whenever the
+ *   two plans' logits lead to the same picks. The M = T and M = 1 kernels agree to the parity bar only, not to the bit, so a pick
+ *   whose u lands within that difference of a cumulative boundary (or whose candidate order turns on a near-tie) may legitimately
+ *   differ, and the streams part from there: the sampling analogue of the greedy form's tie condition.
+ * Stop tokens (sampling->stop). Among the tokens a step would emit, g[0..m-1] (m after the cut to the tokens still wanted), the
+ *   first stop token cuts the emission behind itself: it is recorded and the call is finished. The rest of tokens_out is -1 and
+ *   *n_produced (may be NULL) counts up to and including the stop token; without a stop it is n_tokens. stats.accepted counts a
+ *   before any cut, as in the greedy form. Continue — from a stop or from the end — with first_token = tokens_out[*n_produced - 1]
+ *   at start_pos + *n_produced; the caches are valid for positions < start_pos + *n_produced.
+ * Blocking. Returns 0 on success. Refused with -1 and an error on the context, before anything is enqueued: everything
+ *   zgml_hip_resident_decode_speculative refuses (a batched or a token_len = 1 plan, any token >= vocab, n_history neither 0 nor
+ *   start_pos, mode > 1, ngram > 4, start_pos + n_tokens + T - 1 > max_seq) and everything zgml_hip_resident_decode_sampled
+ *   refuses of the parameters (temperature not > 0, top_p not in (0, 1], top_k > 256, n_stop > 4, a stop token >= vocab);
+ *   sampling = NULL. n_tokens = 0 returns 0 and touches nothing. opt = NULL: lookup with ngram 2 and no history. */
+int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t first_token, uint32_t start_pos,
+                                                 uint32_t n_tokens, const zgml_spec_decode* opt, const zgml_sampling* sampling,
+                                                 int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
+                                                 zgml_spec_stats* stats /* may be NULL */);
 
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];

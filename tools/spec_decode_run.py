@@ -8,6 +8,14 @@ warm-up of bench.py's resident legs.
     timeout -k 10 300 python tools/spec_decode_run.py smollm-135m && timeout -k 10 900 python tools/spec_decode_run.py llama2-7b
 
     argv: model [T list = 2,3,4,6] [reps = 3] [small-M option list; default 1 for llama2-7b, 0,1 for the others] [prompt = 128] [generate = 256]
+          [sampling = temperature,top_k,top_p,seed; default none]
+
+With a sampling parameter set (say 0.8,40,0.95,1) the sampled entry point (zgml_hip_resident_decode_speculative_sampled) runs
+beside the greedy one on the same program in the same process, its variants alternating with the greedy ones inside every
+repetition: the lines then carry a "sampled" record — ms per sampled verify step, what it costs over the greedy step, and its
+break-even against the plain SAMPLED loop of the decode plan (zgml_hip_resident_decode_sampled, timed beside the plain greedy one)
+— and whether every sampled run gave the untimed n-gram run's tokens ("one_stream_whatever_the_drafts": the same drafts always do;
+other drafts may part at a pick that turns on the last bit of the logits, include/zgml_hip.h).
 
 (llama2-7b: all 32 layers, synthetic Q4_0 weights, max_seq 512.) Each timed run is a blocking call that ends with the tokens on
 the host; the clock is the host's around it. break_even = ms per verify step / ms per token of the plain loop: the tokens a step
@@ -25,6 +33,10 @@ reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 options = [int(o) for o in sys.argv[4].split(",")] if len(sys.argv) > 4 else ([1] if name == "llama2-7b" else [0, 1])
 P = int(sys.argv[5]) if len(sys.argv) > 5 else 128
 G = int(sys.argv[6]) if len(sys.argv) > 6 else 256
+sp = None
+if len(sys.argv) > 7:
+    t_, k_, p_, seed_ = sys.argv[7].split(",")
+    sp = capi.SamplingC.of(float(t_), int(k_), float(p_), seed=int(seed_))
 
 be = Backend(0)
 cfg = llama.preset(name, 512 if name == "llama2-7b" else 2048)
@@ -55,6 +67,18 @@ for _ in range(reps):
 assert not be.last_error(), be.last_error()
 ms_tok = 1e3 * min(single)
 emit(path="single", launches=be.planText(s.handle).count("\n") + 3, ms_per_token=[round(1e3 * t, 4) for t in single], tok_s=[round(1 / t, 1) for t in single])
+ms_tok_sampled = None
+if sp is not None:  # the plain sampled loop of the same plan: what a sampling caller has without speculation
+    s.resident_decode_sampled(first, P, n_ref, sp)  # (untimed: graph capture)
+    single_s = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        s.resident_decode_sampled(first, P, n_ref, sp)
+        single_s.append((time.perf_counter() - t0) / n_ref)
+    assert not be.last_error(), be.last_error()
+    ms_tok_sampled = 1e3 * min(single_s)
+    emit(path="single_sampled", launches=be.planText(s.handle).count("\n") + 3, ms_per_token=[round(1e3 * t, 4) for t in single_s],
+         tok_s=[round(1 / t, 1) for t in single_s])
 s.close()
 
 for T in Ts:
@@ -71,6 +95,14 @@ for T in Ts:
         variants = {"perfect": dict(drafts=stream), "useless": dict(drafts=[(t + 1) % cfg.vocab_size for t in stream]),
                     "ngram": dict(history=prompt)}
         runs = {k: [] for k in variants}
+        variants_s, runs_s = {}, {}
+        if sp is not None:
+            # the sampled stream of THIS plan (its rows are the M = T kernels': the decode plan's stream may part from it) from an
+            # untimed n-gram run, G + T tokens of it so that perfect drafts exist for the last step
+            stream_s = st.resident_decode_speculative_sampled(first, P, G + T, sp, history=prompt)[0].tolist()
+            variants_s = {"perfect": dict(drafts=stream_s), "useless": dict(drafts=[(t + 1) % cfg.vocab_size for t in stream_s]),
+                          "ngram": dict(history=prompt)}
+            runs_s = {k: [] for k in variants_s}
         for rep in range(reps + 1):  # (rep 0: untimed)
             for k, kw in variants.items():
                 t0 = time.perf_counter()
@@ -78,6 +110,12 @@ for T in Ts:
                 dt = time.perf_counter() - t0
                 if rep:
                     runs[k].append((dt, stats, toks.tolist() == stream[:G]))
+                if k in variants_s:
+                    t0 = time.perf_counter()
+                    toks, produced, stats = st.resident_decode_speculative_sampled(first, P, G, sp, **variants_s[k])
+                    dt = time.perf_counter() - t0
+                    if rep:
+                        runs_s[k].append((dt, stats, produced == G and toks.tolist() == stream_s[:G]))
         assert not be.last_error(), be.last_error()
         text = be.planText(st.handle)
         out = {"path": "speculative", "T": T, "option": on, "launches_per_step": text.count("\n") + 4, "rows_kernel_launches": text.count("qmatvec-kon-rows")}
@@ -90,6 +128,17 @@ for T in Ts:
                       "accepted": r[0][1]["accepted"], "tokens_per_step": round(G / r[0][1]["steps"], 3),
                       "ms_per_step": [round(1e3 * dt / st_["steps"], 4) for dt, st_, _ in r], "tok_s": [round(G / dt, 1) for dt, _, _ in r],
                       "vs_plain": round(G / best / (1e3 / ms_tok), 3)}
+        if sp is not None:
+            step_ms_s = min(1e3 * dt / stats["steps"] for dt, stats, _ in runs_s["useless"])
+            rec = {"sampling": sys.argv[7], "launches_per_step": text.count("\n") + 5, "ms_per_verify_step": round(step_ms_s, 4),
+                   "us_per_step_over_greedy": round(1e3 * (step_ms_s - step_ms), 2),
+                   "break_even_tokens_per_step": round(step_ms_s / ms_tok_sampled, 3), "break_even_vs_plain_greedy": round(step_ms_s / ms_tok, 3)}
+            for k, r in runs_s.items():
+                best = min(dt for dt, _, _ in r)
+                rec[k] = {"one_stream_whatever_the_drafts": all(eq for _, _, eq in r), "steps": r[0][1]["steps"], "accepted": r[0][1]["accepted"],
+                          "tokens_per_step": round(G / r[0][1]["steps"], 3), "ms_per_step": [round(1e3 * dt / st_["steps"], 4) for dt, st_, _ in r],
+                          "tok_s": [round(G / dt, 1) for dt, _, _ in r], "vs_plain_sampled": round(G / best / (1e3 / ms_tok_sampled), 3)}
+            out["sampled"] = rec
         emit(**out)
         st.close(), mt.close()
 m.close()

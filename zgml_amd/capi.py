@@ -224,6 +224,7 @@ HIP_SYMBOLS = [
     "zgml_hip_program_set_sequences", "zgml_hip_refresh_dynamic_batch", "zgml_hip_resident_decode_batch",
     "zgml_hip_resident_decode_speculative",
     "zgml_hip_sample", "zgml_hip_resident_decode_sampled", "zgml_hip_resident_decode_batch_sampled",
+    "zgml_hip_resident_decode_speculative_sampled",
 ]
 
 class ShardPointC(C.Structure):
@@ -358,6 +359,9 @@ def _bind_hip(lib: C.CDLL) -> None:
     lib.zgml_hip_resident_decode_sampled.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SamplingC), vp, C.POINTER(u32)]
     lib.zgml_hip_resident_decode_batch_sampled.restype = i32
     lib.zgml_hip_resident_decode_batch_sampled.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, C.POINTER(SamplingC), vp, C.POINTER(u32)]
+    lib.zgml_hip_resident_decode_speculative_sampled.restype = i32
+    lib.zgml_hip_resident_decode_speculative_sampled.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SpecDecodeC), C.POINTER(SamplingC), vp, C.POINTER(u32),
+                                                                 C.POINTER(SpecStatsC)]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

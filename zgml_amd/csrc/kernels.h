@@ -448,6 +448,7 @@ enum SpecWord : uint32_t {
     kSpecRunPos = kSpecRun + 1,
     kSpecWords = kSpecRun + 4,
 };
+struct SampleParamsDev;
 struct SpecArgs {
     uint32_t* words;        // [kSpecWords]
     uint32_t* hist;         // [hist_cap] token at every position
@@ -457,6 +458,10 @@ struct SpecArgs {
     const float* pval;      // stage-1 partials of the T logits rows, [T][nblk]
     const int64_t* pidx;
     uint32_t T, nblk, vocab, hist_cap, tokens_cap;
+    // the sampled form (zgml_hip_resident_decode_speculative_sampled): g[] is picks[0..T) — what the merge + pick launch wrote
+    // for the T rows — instead of the fold of the partials, and sparams[0] holds the stop tokens. nullptr: the greedy form
+    const uint32_t* picks = nullptr;
+    const SampleParamsDev* sparams = nullptr;
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
@@ -471,13 +476,18 @@ struct SampleParamsDev {
 //   state, n_seqs == 0     the single-sequence loop: argmax_stage2's advance (state[0] token, [1] position, [2] produced; tokens[cap]),
 //                          nothing once state[3] is set — a stop token sets it behind its own advance
 //   state, n_seqs == B     the batched loop: argmax_batch_stage2's advance; a stop token leaves the sequence no steps
-// The position whose logits are sampled is `position` / state[1] / state[B + b].
+//   picks                  rows of ONE sequence (a speculative verify step): every row reads the one parameter set params[0] — not
+//                          params[b] —, samples at position *pos_word + b (a device word: the step's position is not known
+//                          when the graph is captured) and stores picks[b] = token. It advances nothing: spec_accept_kernel does
+// The position whose logits are sampled is `position` / state[1] / state[B + b] / *pos_word + b.
 struct SampleAdvance {
     uint32_t* state = nullptr;
     int64_t* tokens = nullptr;
     uint32_t cap = 0, n_seqs = 0, position = 0;
     int64_t* out = nullptr;
     uint32_t* cand = nullptr;
+    uint32_t* picks = nullptr;
+    const uint32_t* pos_word = nullptr;
 };
 constexpr uint32_t kSampleMaxSlices = 32; // partial candidate lists per row
 constexpr uint32_t kSampleChunk = 1792;   // logits a select workgroup sorts at a time (with the 256 best so far: 2048 keys)

@@ -40,8 +40,10 @@ struct zgml_resident {
     uint32_t* spec = nullptr;
     uint32_t* hist = nullptr;
     uint32_t* drafts = nullptr;
-    // sampled tail (zgml_hip_resident_decode_sampled / _batch_sampled), allocated by the first such call: one parameter row and
-    // one set of partial candidate lists per sequence; the loop's own graph (the greedy loop's stays valid beside it)
+    uint32_t* picks = nullptr; // the sampled form's token of every logits row, [T] (zgml_hip_resident_decode_speculative_sampled)
+    // sampled tail (zgml_hip_resident_decode_sampled / _batch_sampled / _speculative_sampled), allocated by the first such call: one
+    // parameter row and one set of partial candidate lists per sequence (per logits row of a token_len > 1 plan, whose verify
+    // step reads parameter row 0 alone); the loop's own graph (the greedy loop's stays valid beside it)
     SampleParamsDev* sparams = nullptr;
     uint64_t* skeys = nullptr;
     hipGraph_t graph_sampled = nullptr;
@@ -87,6 +89,7 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->spec);
     hipFree(r->hist);
     hipFree(r->drafts);
+    hipFree(r->picks);
     hipFree(r->sparams);
     hipFree(r->skeys);
     delete r;
@@ -649,19 +652,27 @@ int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const 
 }
 
 
-// Greedy-exact speculative decode of one sequence over a token_len = T plan (contract: include/zgml_hip.h; rules: spec.h). Per
-// verify step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance], captured once as one graph.
-int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
-                                         const zgml_spec_decode* opt, int64_t* tokens_out, zgml_spec_stats* stats) {
+} // extern "C"
+
+namespace {
+
+// Speculative decode of one sequence over a token_len = T plan (contract: include/zgml_hip.h; rules: spec.h), both forms. Per
+// verify step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance], captured once as one graph; the
+// sampled form (`sampled`: zgml_hip_resident_decode_speculative_sampled) has [select] [merge + pick] over the T rows in the
+// place of the argmax stage — one launch more —, a graph of its own in the slot resident_decode_sampled cannot use on such a plan,
+// and a stop token may end the call early. Everything the greedy form does is what it did before the sampled one existed.
+int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
+                const zgml_spec_decode* opt, bool sampled, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
     if (!ctx || !p || !p->resident) return -1;
     Resident* r = p->resident;
+    if (n_produced) *n_produced = 0;
     if (r->n_seqs) {
-        ctx->fail("resident_decode_speculative: the program is a batched plan (speculation under batching is not supported)");
+        ctx->fail(who + ": the program is a batched plan (speculation under batching is not supported)");
         return -1;
     }
     const uint32_t T = r->token_len;
     if (T < 2) {
-        ctx->fail("resident_decode_speculative: the program is a token_len = 1 plan (a verify step needs token_len >= 2)");
+        ctx->fail(who + ": the program is a token_len = 1 plan (a verify step needs token_len >= 2)");
         return -1;
     }
     if (stats) *stats = zgml_spec_stats{0, 0, 0, 0};
@@ -671,16 +682,16 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p,
     const zgml_spec_decode& o = opt ? *opt : none;
     const uint32_t ngram = o.ngram ? o.ngram : kSpecDefaultNgram;
     if (o.mode > 1 || ngram > kSpecMaxNgram) {
-        ctx->fail("resident_decode_speculative: mode must be 0 or 1 and ngram at most " + std::to_string(kSpecMaxNgram));
+        ctx->fail(who + ": mode must be 0 or 1 and ngram at most " + std::to_string(kSpecMaxNgram));
         return -1;
     }
     if ((o.n_history != 0 && o.n_history != start_pos) || (o.n_history && !o.history) || (o.mode == 1 && o.n_drafts && !o.drafts)) {
-        ctx->fail("resident_decode_speculative: n_history must be 0 or start_pos (with the tokens), provided drafts need their array");
+        ctx->fail(who + ": n_history must be 0 or start_pos (with the tokens), provided drafts need their array");
         return -1;
     }
     // the last step may start at start_pos + n_tokens - 1 and stores T columns
     if ((uint64_t)start_pos + n_tokens + T - 1 > r->max_seq) {
-        ctx->fail("resident_decode_speculative: start_pos + n_tokens + token_len - 1 exceeds max_seq");
+        ctx->fail(who + ": start_pos + n_tokens + token_len - 1 exceeds max_seq");
         return -1;
     }
     const uint32_t n_drafts = o.mode == 1 ? o.n_drafts : 0;
@@ -688,9 +699,11 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p,
     for (uint32_t i = 0; in_vocab && i < o.n_history; i++) in_vocab = o.history[i] < r->vocab;
     for (uint32_t i = 0; in_vocab && i < n_drafts; i++) in_vocab = o.drafts[i] < r->vocab;
     if (!in_vocab) {
-        ctx->fail("resident_decode_speculative: token out of range (first token, history or drafts)");
+        ctx->fail(who + ": token out of range (first token, history or drafts)");
         return -1;
     }
+    SampleParamsDev sp{};
+    if (sampled && !sampling_params(ctx, who, sampling, r->vocab, &sp)) return -1;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     // the first start and the last possible start of a verify step
@@ -705,6 +718,7 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p,
             !CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))))
             return -1;
     }
+    if (sampled && (!ensure_sample_blocks(ctx, r, T) || (!r->picks && !CTX_CHECK(ctx, hipMalloc((void**)&r->picks, (size_t)T * 4))))) return -1;
     if (r->tokens_cap < n_tokens) {
         hipStreamSynchronize(s);
         hipFree(r->tokens);
@@ -723,7 +737,15 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p,
         !CTX_CHECK(ctx, hipMemcpyAsync(r->hist + start_pos, &first_token, 4, hipMemcpyHostToDevice, s)) ||
         (w0[kSpecNDrafts] && !CTX_CHECK(ctx, hipMemcpyAsync(r->drafts, o.drafts, (size_t)w0[kSpecNDrafts] * 4, hipMemcpyHostToDevice, s))))
         return -1;
-    const SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap};
+    if (sampled && (!CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, &sp, sizeof(sp), hipMemcpyHostToDevice, s)) || // (row 0: the one set every row reads)
+                    !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_tokens * 8, s))))                // (-1: what a stop token leaves behind itself)
+        return -1;
+    SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap};
+    SampleAdvance adv; // (sampled form only) rows of one sequence: row j samples at the step's run position + j
+    if (sampled) {
+        sa.picks = r->picks, sa.sparams = r->sparams;
+        adv.picks = r->picks, adv.pos_word = r->spec + kSpecRunPos;
+    }
     // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
     const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
                              p->dyn_dev, r->spec + kSpecRun, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), T};
@@ -735,19 +757,27 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p,
         launch_spec_draft(st, sa);
         launch_resident_prep(st, a, (uint32_t)total);
         run_plan(p, st, 0, p->plan.size());
-        launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
+        if (sampled)
+            launch_sample(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv);
+        else
+            launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
         launch_spec_accept(st, sa);
     };
-    if (ctx->opt_graph && !r->graph_exec) capture_graph(ctx, s, "resident_spec", [&] { one_step(s); }, &r->graph, &r->graph_exec); // (failed: eager below)
+    hipGraphExec_t& exec = sampled ? r->graph_sampled_exec : r->graph_exec;
+    if (ctx->opt_graph && !exec) {
+        if (sampled) hipStreamSynchronize(s); // (as the sampled loops: no copy from this stack frame in flight when the capture begins)
+        capture_graph(ctx, s, sampled ? "resident_spec_sampled" : "resident_spec", [&] { one_step(s); }, sampled ? &r->graph_sampled : &r->graph, &exec); // (failed: eager below)
+    }
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
+    // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)
     uint32_t w1[kSpecWords] = {0};
     uint64_t steps_run = 0;
     bool ok = true;
-    for (uint32_t produced = 0; ok && produced < n_tokens;) {
-        const uint32_t round = (n_tokens - produced + T - 1) / T;
+    for (uint32_t produced = 0, wanted = n_tokens; ok && produced < wanted;) {
+        const uint32_t round = (wanted - produced + T - 1) / T;
         for (uint32_t i = 0; i < round; i++) {
-            if (r->graph_exec)
-                hipGraphLaunch(r->graph_exec, s);
+            if (exec)
+                hipGraphLaunch(exec, s);
             else
                 one_step(s);
         }
@@ -755,19 +785,36 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p,
         hipMemcpyAsync(w1, r->spec, sizeof(w1), hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
         if (ok && w1[kSpecProduced] <= produced) { // (every step with tokens left emits at least one)
-            ctx->fail("resident_decode_speculative: a round of verify steps produced nothing");
+            ctx->fail(who + ": a round of verify steps produced nothing");
             ok = false;
         }
-        produced = w1[kSpecProduced];
+        produced = w1[kSpecProduced], wanted = std::min(w1[kSpecWanted], n_tokens);
     }
     if (ok) {
         hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_tokens * 8, hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     }
-    ok = ok && ctx->handoff_ok("resident_decode_speculative");
+    ok = ok && ctx->handoff_ok(who.c_str());
     if (ok && stats) *stats = zgml_spec_stats{w1[kSpecSteps], w1[kSpecDrafted], w1[kSpecAccepted], 0};
-    resident_end(p, steps_run, p->plan.size() + 4); // per step [draft] [prep] [plan] [argmax stage 1] [accept]
+    if (ok && n_produced) *n_produced = std::min(w1[kSpecProduced], n_tokens);
+    // per step [draft] [prep] [plan] [argmax stage 1] [accept], or [draft] [prep] [plan] [select] [merge + pick] [accept]
+    resident_end(p, steps_run, p->plan.size() + (sampled ? 5 : 4));
     return ok ? 0 : -1;
+}
+
+} // namespace
+
+extern "C" {
+
+int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
+                                         const zgml_spec_decode* opt, int64_t* tokens_out, zgml_spec_stats* stats) {
+    return spec_decode(ctx, p, "resident_decode_speculative", first_token, start_pos, n_tokens, opt, false, nullptr, tokens_out, nullptr, stats);
+}
+
+int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
+                                                 const zgml_spec_decode* opt, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced,
+                                                 zgml_spec_stats* stats) {
+    return spec_decode(ctx, p, "resident_decode_speculative_sampled", first_token, start_pos, n_tokens, opt, true, sampling, tokens_out, n_produced, stats);
 }
 
 } // extern "C"

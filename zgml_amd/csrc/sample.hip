@@ -1,8 +1,9 @@
-// sample.hip — the sampled token tail (zgml_hip_sample, zgml_hip_resident_decode_sampled / _batch_sampled, runtime_resident.hip):
-// two launches per row of logits, the shape of launch_argmax / launch_argmax_batch. The rule — candidate order, pick, random
-// number — is sample.h's; here is only how workgroups find the candidates. Keys are unique 64-bit words (sample_key), so the
-// largest 256 of a row are one well-defined list whatever the slicing: nothing below depends on arrival order, no workgroup
-// waits for another and there is no last-arriver stage.
+// sample.hip — the sampled token tail (zgml_hip_sample, zgml_hip_resident_decode_sampled / _batch_sampled and the T rows of a
+// sampled verify step, zgml_hip_resident_decode_speculative_sampled; runtime_resident.hip): two launches per row of logits, the
+// shape of launch_argmax / launch_argmax_batch. The rule — candidate order, pick, random number — is sample.h's; here is only
+// how workgroups find the candidates. Keys are unique 64-bit words (sample_key), so the largest 256 of a row are one
+// well-defined list whatever the slicing: nothing below depends on arrival order, no workgroup waits for another and there is
+// no last-arriver stage.
 //   [select]  grid (slices, rows), 256 threads: a workgroup walks its slice of the row in chunks of kSampleChunk logits; the 256
 //             best keys so far and the chunk's keys are one 2048-key bitonic sort in LDS (16 KiB); the slice's 256 largest keys,
 //             descending, go to the scratch (0 pads a slice of fewer: every real key is > 0).
@@ -65,7 +66,7 @@ __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const ui
     for (uint32_t k = 2 * kSampleMaxK; k <= P; k <<= 1)
         for (uint32_t j = k >> 1; j > 0; j >>= 1) bitonic_stage<kMergeBlock>(s, P / 2, k, j);
     // s[0, 256): the row's largest keys, descending
-    const SampleParamsDev& sp = params[b]; // (read in place: a copy with its indexed stop[] would live in scratch)
+    const SampleParamsDev& sp = params[adv.picks ? 0 : b]; // (read in place: a copy with its indexed stop[] would live in scratch)
     const uint32_t kc = sample_top_k(sp.top_k, n);
     float* const p = (float*)(s + kSampleMaxK); // (the keys behind the first 256 are done with)
     const float v0 = sample_key_value(s[0]);
@@ -76,6 +77,11 @@ __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const ui
     __syncthreads();
     if (threadIdx.x != 0) return;
     if (adv.cand) adv.cand[0] = kc;
+    if (adv.picks) { // row b of one sequence's verify step: the pick alone, the advance is spec_accept_kernel's
+        const float u = sample_uniform(sp.seed_lo, sp.seed_hi, sp.stream, *adv.pos_word + b);
+        adv.picks[b] = sample_key_index(s[sample_pick_probs(p, kc, sp.top_p, u)]);
+        return;
+    }
     if (!adv.state) {
         const float u = sample_uniform(sp.seed_lo, sp.seed_hi, sp.stream, adv.position);
         adv.out[0] = (int64_t)sample_key_index(s[sample_pick_probs(p, kc, sp.top_p, u)]);

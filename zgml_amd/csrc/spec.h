@@ -1,12 +1,13 @@
-// spec.h — the draft rule and the acceptance rule of greedy-exact speculative decode (zgml_hip_resident_decode_speculative,
-// include/zgml_hip.h), written ONCE: the kernels of spec_decode.hip call these functions and so does the host probe
-// tests/cpp/spec_probe.cpp (tests/test_spec_decode_host.py compares it with a Python model of the same rules). Plain C++,
-// no device intrinsics: the header compiles under g++ as it stands.
+// spec.h — the draft rule and the acceptance rule of greedy-exact speculative decode (zgml_hip_resident_decode_speculative and
+// its sampled form zgml_hip_resident_decode_speculative_sampled, include/zgml_hip.h), written ONCE: the kernels of
+// spec_decode.hip call these functions and so does the host probe tests/cpp/spec_probe.cpp (tests/test_spec_decode_host.py
+// compares it with a Python model of the same rules). Plain C++, no device intrinsics: the header compiles under g++ as it
+// stands.
 //
 // Vocabulary: hist[0..pos] holds the token at every position, hist[pos] being the last confirmed token (not yet in the KV
 // cache). A verify step runs a token_len = T plan over the candidates c[0..T-1]: c[0] = hist[pos], c[j] the draft for position
-// pos + j, or — a position without a draft — the pad c[j - 1]. g[j] is the greedy token of logits row j: the token at position
-// pos + j + 1 given c[0..j].
+// pos + j, or — a position without a draft — the pad c[j - 1]. g[j] is the token of logits row j — its first maximum, or in the
+// sampled form sample.h's pick at position pos + j —: the token at position pos + j + 1 given c[0..j].
 #pragma once
 
 #include <stdint.h>
@@ -95,6 +96,21 @@ ZGML_SPEC_FN uint32_t spec_accept(const uint32_t* c, const G* g, uint32_t T) {
 ZGML_SPEC_FN uint32_t spec_emit_count(uint32_t a, uint32_t n_tokens, uint32_t produced) {
     const uint32_t left = produced < n_tokens ? n_tokens - produced : 0;
     return a + 1 < left ? a + 1 : left;
+}
+
+// the stop cut of the sampled form: among the m tokens g[0..m-1] a step would emit, the first that is one of the n_stop stop
+// tokens ends the emission behind itself. Returns the tokens emitted after the cut (m when none of them stops); *fired: one did
+// — also when it is g[m - 1] and cuts nothing. A stop token behind the m is not looked at.
+template <class G>
+ZGML_SPEC_FN uint32_t spec_stop_cut(const G* g, uint32_t m, uint32_t n_stop, const uint32_t* stop, bool* fired) {
+    *fired = false;
+    for (uint32_t k = 0; k < m; k++)
+        for (uint32_t i = 0; i < n_stop; i++)
+            if (g[k] == (G)stop[i]) {
+                *fired = true;
+                return k + 1;
+            }
+    return m;
 }
 
 } // namespace zgml

@@ -1,5 +1,6 @@
 // spec_decode.hip — the two serial tails of a speculative verify step (zgml_hip_resident_decode_speculative, runtime_resident.hip:
-// per step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance]). Both are one workgroup and launches of
+// per step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance]; the sampled form has sample.hip's
+// [select] [merge + pick] over the T rows in the place of the argmax stage). Both are one workgroup and launches of
 // their own: DESIGN section 0.2 item 5 measured that folding such tails into a neighbouring launch is slower. The rules themselves
 // (which tokens are drafted, how many are accepted) are spec.h's; here is only how a workgroup evaluates them.
 #include "kernels.h"
@@ -73,15 +74,18 @@ __device__ __forceinline__ void spec_arg_fold(float& bv, int64_t& bi, float v, i
     if (bi == INT64_MAX || v > bv || (v == bv && i < bi)) bv = v, bi = i;
 }
 
-// g[j] from the nblk stage-1 partials of logits row j (a wave per row, rows kSpecWaves apart), then thread 0: how many
-// candidates were the greedy choice, what is emitted, and the advance of the state, the history and the counters.
+// g[j] from the nblk stage-1 partials of logits row j (a wave per row, rows kSpecWaves apart) — or, the sampled form, read from
+// a.picks —, then thread 0: how many candidates were the row's choice, what is emitted, and the advance of the state, the history
+// and the counters. The sampled form cuts the emission behind the first stop token and then sets wanted = produced: every later
+// step of the round idles, and the host's round loop ends on the words it reads back.
 __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     extern __shared__ uint32_t g[]; // [T]
     uint32_t* const w = a.words;
     const uint32_t produced = w[kSpecProduced], wanted = w[kSpecWanted];
     if (produced >= wanted) return; // (uniform) an idle step changes nothing
     const uint32_t lane = threadIdx.x & 63;
-    for (uint32_t j = threadIdx.x >> 6; j < a.T; j += kSpecWaves) {
+    for (uint32_t j = threadIdx.x; a.picks && j < a.T; j += kSpecBlock) g[j] = a.picks[j] < a.vocab ? a.picks[j] : 0u; // (a pick is an index of its row: the clamp never acts)
+    for (uint32_t j = threadIdx.x >> 6; !a.picks && j < a.T; j += kSpecWaves) {
         const float* vals = a.pval + (uint64_t)j * a.nblk;
         const int64_t* idxs = a.pidx + (uint64_t)j * a.nblk;
         float bv = -INFINITY;
@@ -99,7 +103,9 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     if (threadIdx.x != 0) return;
     const uint32_t pos = w[kSpecPos];
     const uint32_t acc = spec_accept(a.cand, g, a.T);
-    const uint32_t m = spec_emit_count(acc, wanted, produced);
+    uint32_t m = spec_emit_count(acc, wanted, produced);
+    bool stopped = false;
+    if (a.sparams) m = spec_stop_cut(g, m, a.sparams->n_stop, a.sparams->stop, &stopped); // (read in place, as the merge kernel does)
     for (uint32_t k = 0; k < m; k++) {
         if (produced + k < a.tokens_cap) a.tokens[produced + k] = (int64_t)g[k];
         if (pos + 1 + k < a.hist_cap) a.hist[pos + 1 + k] = g[k];
@@ -107,6 +113,7 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     w[kSpecTok] = g[m - 1];
     w[kSpecPos] = pos + m;
     w[kSpecProduced] = produced + m;
+    if (stopped) w[kSpecWanted] = produced + m; // the call is finished
     w[kSpecSteps] += 1;
     w[kSpecAccepted] += acc;
 }

@@ -378,11 +378,9 @@ class Session:
             raise RuntimeError("resident_prefill: " + self._backend.last_error())
         return nxt
 
-    def resident_decode_speculative(self, first_token: int, start_pos: int, n_tokens: int, history=None, drafts=None, ngram: int = 2):
-        """Greedy-exact speculative decode on a token_len = T >= 2 plan (include/zgml_hip.h: zgml_hip_resident_decode_speculative):
-        -> (tokens[n_tokens], {"steps", "drafted", "accepted"}). `history`: the tokens at positions 0..start_pos-1 (None: the n-gram
-        lookup sees only this call's tokens). `drafts`: guesses for the tokens at positions start_pos+1.. (provided mode); None:
-        n-gram lookup with suffixes of up to `ngram` tokens."""
+    @staticmethod
+    def _spec_opt(history, drafts, ngram: int):
+        """-> (capi.SpecDecodeC, the arrays it points into: keep them alive over the call)"""
         u32p = C.POINTER(C.c_uint32)
         opt = capi.SpecDecodeC()
         hist = np.ascontiguousarray([] if history is None else history, dtype=np.uint32)
@@ -390,13 +388,37 @@ class Session:
         opt.history, opt.n_history = (hist.ctypes.data_as(u32p) if hist.size else None), hist.size
         opt.mode, opt.ngram = (0 if drafts is None else 1), ngram
         opt.drafts, opt.n_drafts = (dr.ctypes.data_as(u32p) if dr.size else None), dr.size
+        return opt, (hist, dr)
+
+    def resident_decode_speculative(self, first_token: int, start_pos: int, n_tokens: int, history=None, drafts=None, ngram: int = 2):
+        """Greedy-exact speculative decode on a token_len = T >= 2 plan (include/zgml_hip.h: zgml_hip_resident_decode_speculative):
+        -> (tokens[n_tokens], {"steps", "drafted", "accepted"}). `history`: the tokens at positions 0..start_pos-1 (None: the n-gram
+        lookup sees only this call's tokens). `drafts`: guesses for the tokens at positions start_pos+1.. (provided mode); None:
+        n-gram lookup with suffixes of up to `ngram` tokens."""
+        opt, keep = self._spec_opt(history, drafts, ngram)
         toks = np.zeros(n_tokens, np.int64)
         stats = capi.SpecStatsC()
         rc = capi.load_hip().zgml_hip_resident_decode_speculative(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
                                                                    toks.ctypes.data, C.byref(stats))
+        del keep
         if rc != 0:
             raise RuntimeError("resident_decode_speculative: " + self._backend.last_error())
         return toks, {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
+
+    def resident_decode_speculative_sampled(self, first_token: int, start_pos: int, n_tokens: int, sampling: "capi.SamplingC", history=None,
+                                            drafts=None, ngram: int = 2):
+        """zgml_hip_resident_decode_speculative_sampled: the verify step's rows are sampled (seeded top-k / top-p) instead of
+        arg-maxed -> (tokens[n_tokens], n_produced, {"steps", "drafted", "accepted"}): -1 behind a stop token. `history`, `drafts`
+        and `ngram` as resident_decode_speculative."""
+        opt, keep = self._spec_opt(history, drafts, ngram)
+        toks = np.full(max(1, n_tokens), -1, np.int64)
+        stats, produced = capi.SpecStatsC(), C.c_uint32(0)
+        rc = capi.load_hip().zgml_hip_resident_decode_speculative_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
+                                                                           C.byref(sampling), toks.ctypes.data, C.byref(produced), C.byref(stats))
+        del keep
+        if rc != 0:
+            raise RuntimeError("resident_decode_speculative_sampled: " + self._backend.last_error())
+        return toks[:n_tokens], int(produced.value), {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
 
     def close(self):
         if self.ptr:
