@@ -41,7 +41,7 @@ def build(dh, bs, n_cols, n_store, seq_q, seq_kv, k_start, rng, masked=False):
     return prog, ce
 
 
-@pytest.mark.parametrize("dh,bs", [(64, 32), (128, 32), (32, 16), (64, 64)])
+@pytest.mark.parametrize("dh,bs", [(64, 32), (128, 32), (32, 16), (64, 64), (16, 16), (256, 32), (256, 64)])
 @pytest.mark.parametrize("seq_q,seq_kv,masked", [(1, 8, False), (1, 37, True), (3, 21, True), (1, 1, False)])
 def test_kvq_store_and_attention_match_oracle(hip_backend, oracle, dh, bs, seq_q, seq_kv, masked):
     rng = np.random.default_rng(dh * 3 + bs + seq_kv)

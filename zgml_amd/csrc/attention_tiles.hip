@@ -17,7 +17,7 @@
 //
 // The waves of a workgroup split the key tiles of one (head, query tile) round-robin and merge their (m, l, O) through
 // LDS in wave order (deterministic). A key tile whose 16 x 16 mask block is entirely -inf (the causal upper triangle) or
-// past seq_kv is skipped before its MFMAs.
+// past seq_kv is skipped before its MFMAs; inside a tile, the V operands of a key that all 16 queries skip reach the PV MFMA as 0.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
@@ -137,6 +137,7 @@ __global__ void __launch_bounds__(kTileWavesMax * 64) attention_tiles_kernel(con
         }
         load_k(nxt); // the K registers are free again
         float pw[4] = {0.f, 0.f, 0.f, 0.f};
+        uint32_t dead_keys = 0; // bit v: key 4 g + v is skipped by all 16 queries of the tile (masked, past seq_kv, non-finite score)
         if (live) {
             float sc[4];
             float bm = -INFINITY;
@@ -144,6 +145,18 @@ __global__ void __launch_bounds__(kTileWavesMax * 64) attention_tiles_kernel(con
             for (int v = 0; v < 4; v++) {
                 sc[v] = key_base + v < seq_kv ? tile_score(s0[v] + s1[v], mk[v], p.scale) : -INFINITY;
                 bm = fmaxf(bm, sc[v]);
+            }
+            // A skipped key's V row is never read by the reference, so it may hold anything, and 0 x NaN = NaN inside the PV
+            // MFMA would reach every query of the tile. The lanes of DPP row g hold key 4 g + v's score for the 16 queries, and
+            // the same lanes supply that key's V operands: one ballot per v tells the row whether any query kept the key.
+            // Wave-uniform test first, so only diagonal / masked / ragged tiles pay for the ballots and the selects.
+            const bool some_dead = !(sc[0] > -INFINITY && sc[1] > -INFINITY && sc[2] > -INFINITY && sc[3] > -INFINITY);
+            if (__builtin_amdgcn_ballot_w64(some_dead) != 0) {
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const uint64_t kept = __builtin_amdgcn_ballot_w64(sc[v] > -INFINITY);
+                    if (((kept >> (16 * g)) & 0xFFFFu) == 0) dead_keys |= 1u << v;
+                }
             }
             bm = rows_max(bm);
             const float nm = fmaxf(m, bm);
@@ -164,6 +177,13 @@ __global__ void __launch_bounds__(kTileWavesMax * 64) attention_tiles_kernel(con
         }
         load_mask(nxt);
         if (live) {
+            if (__builtin_amdgcn_ballot_w64(dead_keys != 0) != 0) { // (the loads stay unconditional: registers are cleared, not reloaded)
+#pragma unroll
+                for (int v = 0; v < 4; v++)
+#pragma unroll
+                    for (int h = 0; h < NH; h++)
+                        if (dead_keys >> v & 1) vv[v][h] = f4{0.f, 0.f, 0.f, 0.f};
+            }
 #pragma unroll
             for (int v = 0; v < 4; v++)
 #pragma unroll

@@ -373,6 +373,11 @@ struct AttnPieceSink {
 };
 void launch_attention_tiles(hipStream_t s, const AttentionParams* dev_params, uint32_t n_ops, uint32_t max_seq_q, uint32_t d_head,
                             const float* zero_word, const AttnPieceSink& sink = AttnPieceSink{});
+// which kernel a level's batched attention launch runs: decided here once, for launch_attention_batch and for the plan text
+// (the switches ZGML_HIP_ATTN_ROWS / ZGML_HIP_ATTN_TILES are read inside)
+enum class AttnRoute { generic, dense, rows, tiles };
+AttnRoute attention_route(bool all_dense, uint32_t rows_d_head, uint32_t max_seq_q, const float* zero_word);
+const char* attention_route_tag(AttnRoute r); // "attention-generic" | "attention-dense" | "attention-rows" | "attention-tiles"
 void launch_attention_batch(hipStream_t s, const AttentionParams* dev_params, uint32_t n_ops, uint32_t max_seq_q, bool all_dense,
                             uint32_t rows_d_head = 0, const float* zero_word = nullptr, const AttnPieceSink& sink = AttnPieceSink{}); // rows_d_head: the common d_head when every op is dense (else 0)
 void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p);

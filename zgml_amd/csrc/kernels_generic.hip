@@ -513,7 +513,7 @@ __global__ void __launch_bounds__(kBlock) attention_kernel(const AttentionParams
         if (new_m == -INFINITY) continue; // uniform: nothing valid so far
         float alpha = (m == -INFINITY) ? 0.0f : expf(m - new_m);
         float w = valid ? expf(score - new_m) : 0.0f;
-        w_s[tid] = w;
+        w_s[tid] = valid ? w : -INFINITY; // a skipped key is marked, not given weight 0: its V row is never read (0 x NaN = NaN)
         float tile_sum = block_sum(w, red); // contains the barrier that publishes w_s
         l = l * alpha + tile_sum;
         m = new_m;
@@ -521,13 +521,17 @@ __global__ void __launch_bounds__(kBlock) attention_kernel(const AttentionParams
         if (v_active) {
             if (grouped) {
                 float a = acc0 * alpha;
-                for (uint32_t t = g; t < tile_n; t += G)
-                    a += w_s[t] * p.v[(uint64_t)r0 * p.v_rs + (uint64_t)(s0 + t) * p.v_cs];
+                for (uint32_t t = g; t < tile_n; t += G) {
+                    const float wt = w_s[t];
+                    if (wt == -INFINITY) continue; // skipped key
+                    a += wt * p.v[(uint64_t)r0 * p.v_rs + (uint64_t)(s0 + t) * p.v_cs];
+                }
                 acc0 = a;
             } else {
                 float a0 = acc0 * alpha, a1 = acc1 * alpha;
                 for (uint32_t t = 0; t < tile_n; t++) {
                     float wt = w_s[t];
+                    if (wt == -INFINITY) continue; // skipped key
                     if (r0 < dh) a0 += wt * p.v[(uint64_t)r0 * p.v_rs + (uint64_t)(s0 + t) * p.v_cs];
                     if (r0 + kBlock < dh)
                         a1 += wt * p.v[(uint64_t)(r0 + kBlock) * p.v_rs + (uint64_t)(s0 + t) * p.v_cs];
@@ -637,7 +641,7 @@ __global__ void __launch_bounds__(kAttnBlock) attention_dense_kernel(const Atten
         for (uint32_t t = tid; t < tn; t += kAttnBlock) {
             const float sc = sc_s[t];
             const float wgt = sc > -INFINITY ? expf(sc - new_m) : 0.0f;
-            sc_s[t] = wgt;
+            if (sc > -INFINITY) sc_s[t] = wgt; // a skipped key keeps its -inf: the marker P.V tests
             tsum += wgt;
         }
         tsum = block_sum_n(tsum, red, NW); // barriers publish the weights
@@ -655,11 +659,13 @@ __global__ void __launch_bounds__(kAttnBlock) attention_dense_kernel(const Atten
 #pragma unroll
             for (int j = 0; j < kAttnUnroll; j++) {
                 const uint32_t t = base + j * keys_per_iter + w * KPW + sub;
-                const float wgt = t < tn ? sc_s[t] : 0.0f;
-                acc.x += wgt * vv[j].x;
-                acc.y += wgt * vv[j].y;
-                acc.z += wgt * vv[j].z;
-                acc.w += wgt * vv[j].w;
+                const float wgt = t < tn ? sc_s[t] : -INFINITY;
+                if (wgt > -INFINITY) { // the row of a skipped key (loaded, clamped) is never used: 0 x NaN = NaN
+                    acc.x += wgt * vv[j].x;
+                    acc.y += wgt * vv[j].y;
+                    acc.z += wgt * vv[j].z;
+                    acc.w += wgt * vv[j].w;
+                }
             }
         }
         __syncthreads(); // sc_s reused by the next tile
@@ -1402,31 +1408,45 @@ void launch_attention_decode_batch(hipStream_t s, const AttnDecodeParams* dev_pa
 void launch_attention_batch(hipStream_t s, const AttentionParams* dev_params, uint32_t n_ops, uint32_t max_seq_q,
                             bool all_dense, uint32_t rows_d_head, const float* zero_word, const AttnPieceSink& sink) {
     if (!n_ops || !max_seq_q) return;
-    if (all_dense && rows_d_head && zero_word && sw().hip_attn_rows && attention_tiles_applies(max_seq_q, rows_d_head)) {
-        launch_attention_tiles(s, dev_params, n_ops, max_seq_q, rows_d_head, zero_word, sink);
-        return;
-    }
-    if (all_dense && rows_d_head && zero_word && sw().hip_attn_rows) { // every op dense with this d_head: the streaming kernel
-        const dim3 grid(max_seq_q, n_ops);
-        // enough (query, head) workgroups to fill the chip: 4 waves each (a 16-wave workgroup whose context needs 2
-        // still pays for launching 16); few workgroups: all 16 so a long context is spread over more waves
-        const uint32_t block = (uint64_t)max_seq_q * n_ops >= 256 ? 256 : kAttnBlock;
+    switch (attention_route(all_dense, rows_d_head, max_seq_q, zero_word)) {
+        case AttnRoute::tiles: launch_attention_tiles(s, dev_params, n_ops, max_seq_q, rows_d_head, zero_word, sink); return;
+        case AttnRoute::rows: { // every op dense with this d_head: the streaming kernel
+            const dim3 grid(max_seq_q, n_ops);
+            // enough (query, head) workgroups to fill the chip: 4 waves each (a 16-wave workgroup whose context needs 2
+            // still pays for launching 16); few workgroups: all 16 so a long context is spread over more waves
+            const uint32_t block = (uint64_t)max_seq_q * n_ops >= 256 ? 256 : kAttnBlock;
 #define AROWS(L) attention_rows_kernel<L><<<grid, block, 0, s>>>(dev_params, zero_word)
-        switch (rows_d_head) {
-            case 8: AROWS(2); return;
-            case 16: AROWS(4); return;
-            case 32: AROWS(8); return;
-            case 64: AROWS(16); return;
-            case 128: AROWS(32); return;
-            case 256: AROWS(64); return;
-            default: break;
-        }
+            switch (rows_d_head) {
+                case 8: AROWS(2); return;
+                case 16: AROWS(4); return;
+                case 32: AROWS(8); return;
+                case 64: AROWS(16); return;
+                case 128: AROWS(32); return;
+                default: AROWS(64); return; // 256 (attention_route admits no other d_head)
+            }
 #undef AROWS
+        }
+        case AttnRoute::dense: attention_dense_kernel<<<dim3(max_seq_q, n_ops), kAttnBlock, 0, s>>>(dev_params); return;
+        case AttnRoute::generic: attention_kernel<<<dim3(max_seq_q, n_ops), kBlock, 0, s>>>(dev_params); return;
     }
-    if (all_dense)
-        attention_dense_kernel<<<dim3(max_seq_q, n_ops), kAttnBlock, 0, s>>>(dev_params);
-    else
-        attention_kernel<<<dim3(max_seq_q, n_ops), kBlock, 0, s>>>(dev_params);
+}
+
+// all_dense: every op passes the planner's attention_op_dense; rows_d_head: their common d_head if it is >= 8, else 0
+AttnRoute attention_route(bool all_dense, uint32_t rows_d_head, uint32_t max_seq_q, const float* zero_word) {
+    if (!all_dense) return AttnRoute::generic;
+    const bool rows_dh = rows_d_head >= 8 && rows_d_head <= 256 && (rows_d_head & (rows_d_head - 1)) == 0; // the instances of attention_rows_kernel
+    if (!(rows_dh && zero_word && sw().hip_attn_rows)) return AttnRoute::dense;
+    return attention_tiles_applies(max_seq_q, rows_d_head) ? AttnRoute::tiles : AttnRoute::rows;
+}
+
+const char* attention_route_tag(AttnRoute r) {
+    switch (r) {
+        case AttnRoute::generic: return "attention-generic";
+        case AttnRoute::dense: return "attention-dense";
+        case AttnRoute::rows: return "attention-rows";
+        case AttnRoute::tiles: return "attention-tiles";
+    }
+    return "attention";
 }
 
 void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p) {

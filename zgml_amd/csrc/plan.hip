@@ -300,6 +300,14 @@ struct PlanItem {
     int store = -1;
 };
 
+// the layout the float4-per-lane attention kernels (dense, rows, tiles) read: unit row strides, d_head a power of two in
+// [4, 256], column strides in whole float4s and 16-byte aligned q / k / v rows. Anything else runs attention_kernel.
+bool attention_op_dense(const AttentionParams& a) {
+    const uint32_t dh = a.d_head;
+    return a.q_rs == 1 && a.k_rs == 1 && a.v_rs == 1 && dh >= 4 && dh <= 256 && (dh & (dh - 1)) == 0 && (a.q_cs % 4) == 0 &&
+           (a.k_cs % 4) == 0 && (a.v_cs % 4) == 0 && ((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0;
+}
+
 // the batchable kinds of one group of mutually independent items -> one "movement" launch (ropes
 // and slice_assigns together), one attention launch, one repeat launch; the rest one by one
 void emit_batches(zgml_hip_program* p, const std::vector<PlanItem>& group) {
@@ -437,12 +445,7 @@ void emit_batches(zgml_hip_program* p, const std::vector<PlanItem>& group) {
     }
     if (!atts.empty()) {
         bool dense = true;
-        for (const AttentionParams& a : atts) {
-            const uint32_t dh = a.d_head;
-            dense = dense && a.q_rs == 1 && a.k_rs == 1 && a.v_rs == 1 && dh >= 4 && dh <= 256 && (dh & (dh - 1)) == 0 &&
-                    (a.q_cs % 4) == 0 && (a.k_cs % 4) == 0 && (a.v_cs % 4) == 0 && ((uintptr_t)a.q % 16) == 0 &&
-                    ((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0;
-        }
+        for (const AttentionParams& a : atts) dense = dense && attention_op_dense(a);
         uint32_t rows_dh = dense ? atts[0].d_head : 0; // the streaming kernel: one d_head >= 8 per launch
         for (const AttentionParams& a : atts)
             if (a.d_head != rows_dh || a.d_head < 8) rows_dh = 0;
@@ -451,9 +454,11 @@ void emit_batches(zgml_hip_program* p, const std::vector<PlanItem>& group) {
         const uint32_t n = (uint32_t)atts.size(), mx = att_max;
         auto sink = std::make_shared<AttnPieceSink>(); // armed by the matmul that reads the heads' row stores, if one follows
         Launch L{ZGML_DOP_ATTENTION, n_att, lo[2], hi[2], [=](hipStream_t s) { launch_attention_batch(s, d, n, mx, dense, rows_dh, zero, *sink); }};
+        const AttnRoute route = attention_route(dense, rows_dh, mx, zero); // the kernel launch_attention_batch will pick
+        L.tag = attention_route_tag(route);
         // every head stores its rows into one dense [seq_q x cols] matrix (d2_rs == 1, a common row stride) and the tile
         // kernel will run: that matrix may be the next quantized matmul's input
-        bool one_matrix = dense && rows_dh && zero && attention_tiles_applies(mx, rows_dh) && atts[0].dst2 && atts[0].d2_rs == 1;
+        bool one_matrix = route == AttnRoute::tiles && atts[0].dst2 && atts[0].d2_rs == 1;
         for (const AttentionParams& a : atts)
             one_matrix = one_matrix && a.dst2 == atts[0].dst2 && a.d2_rs == 1 && a.d2_cs == atts[0].d2_cs && a.seq_q == mx;
         std::vector<int64_t> offs = att_store_off;
