@@ -650,7 +650,39 @@ typedef struct zgml_sampling {
     uint32_t stop[4];    /* < vocab */
     uint32_t stream;     /* Philox counter word 1 */
     uint64_t seed;
+    /* the penalties (below); an all-zero tail: off */
+    float repeat_penalty;    /* 0 or 1: neutral; else finite and > 0 */
+    float presence_penalty;  /* finite; negative values encourage a token */
+    float frequency_penalty; /* finite; likewise */
+    uint32_t penalty_window; /* W: 0..256 */
+    const uint32_t* recent;  /* the tokens before the call (per entry point, below) */
+    uint32_t n_recent;
 } zgml_sampling;
+/* Repetition, presence and frequency penalties (rule: zgml_amd/csrc/sample.h). The pick at position P — over the logits produced
+ *   by feeding the token at P — sees the tokens at positions max(lo, P + 1 - W) .. P, lo the first position whose token the call
+ *   knows; count(t) is the number of occurrences of token t among them. A logit v of a token with count c > 0 becomes
+ *     v1 = v > 0 ? v * (1 / repeat_penalty) : v * repeat_penalty;  v2 = v1 - c * frequency_penalty;  v3 = v2 - presence_penalty
+ *   (one rounded f32 operation each; the multiplication by the reciprocal, computed once on the host, where llama.cpp divides is
+ *   the one deliberate deviation, in the last bit), every other logit stays as it is to the bit, and the candidates, the pick and
+ *   u are those above over the penalised values. The penalties act BEFORE the 256 largest are selected — a penalised token may
+ *   leave the candidates, an encouraged one may enter them from any rank — and before the temperature.
+ *   They are active iff penalty_window > 0 and at least one penalty is not neutral. Inactive: exactly the launches and the tokens
+ *   of a call without the fields. Active: the same number of launches, the select launch in its penalised form; the loops
+ *   replay a captured graph of their own, so calls with and without penalties alternate on one program and invalidate nothing.
+ * Where the window comes from:
+ *   zgml_hip_resident_decode_sampled, _batch_sampled: recent[0, n_recent) are the tokens at positions start_pos - n_recent ..
+ *     start_pos - 1; the library adds first_token at start_pos and every token it emits. lo = start_pos - n_recent; only the last
+ *     W - 1 entries are read. Each batched sequence has its own through per_seq[b], and sequences with penalties off sit
+ *     beside sequences with them on. A sequence frozen by a stop token or by its count adds nothing; continuing it in a later
+ *     call with `recent` re-supplied gives the stream of one uninterrupted call.
+ *   zgml_hip_sample: recent[0, n_recent) are the tokens at positions position + 1 - n_recent .. position, the last one the token
+ *     whose logits these are. The last W entries are read; a token >= n touches no logit and is ignored.
+ *   zgml_hip_resident_decode_speculative_sampled: row j's window is read from the call's own device history and the step's
+ *     candidates (history up to the position the step runs at, the candidates behind it); lo is the first position the history
+ *     knows (0 with opt->history, else start_pos). `recent` must be NULL: the tokens before the call are opt->history.
+ * Refused with -1 and an error on the context, before anything is enqueued: a penalty that is not neutral with
+ *   penalty_window = 0; penalty_window > 256; a penalty that is not finite, or repeat_penalty < 0; recent = NULL with
+ *   n_recent > 0; in the loops a recent token >= vocab and n_recent > start_pos; in the speculative call recent != NULL. */
 /* The sampling sibling of zgml_hip_argmax over f32 elements [offset, offset + n) of a program buffer, 1 <= n < 2^32; blocking.
  * `position` is the Philox counter's word 0; stop tokens are not looked at. For vtable-path callers, and for the first token
  * after zgml_hip_resident_prefill, whose logits rows stay in the buffer. candidates_out (NULL or 256 words) receives the
@@ -699,7 +731,10 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
  *   by about 1e-7 of their range. The same drafts give the same stream, always; other drafts give the same stream unless a pick's
  *   u lands within that difference of a cumulative boundary (measured: one token of 256 in one of eight SmolLM-135M
  *   configurations, the streams equal again from the next token; none at Llama-2-7B).
- *   top_k = 1 gives exactly the tokens (and statistics) of zgml_hip_resident_decode_speculative.
+ *   With penalties the argument carries over: row j's token is a deterministic function of its logits bits AND of its window —
+ *   the confirmed tokens plus the candidates c[1..j]. If row j is used at all, those candidates were accepted, so they are the
+ *   confirmed tokens at their positions: the window of an emitted token never holds a rejected draft.
+ *   top_k = 1 (penalties neutral) gives exactly the tokens (and statistics) of zgml_hip_resident_decode_speculative.
  *   Against zgml_hip_resident_decode_sampled on a token_len = 1 plan with the same parameters the stream is the same whenever the
  *   two plans' logits lead to the same picks. The M = T and M = 1 kernels agree to the parity bar only, not to the bit, so a pick
  *   whose u lands within that difference of a cumulative boundary (or whose candidate order turns on a near-tie) may legitimately

@@ -188,14 +188,27 @@ class SpecStatsC(C.Structure):
 class SamplingC(C.Structure):
     """zgml_sampling (include/zgml_hip.h): the parameters of the sampled token tail."""
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_uint32), ("n_stop", C.c_uint32),
-                ("stop", C.c_uint32 * 4), ("stream", C.c_uint32), ("seed", C.c_uint64)]
+                ("stop", C.c_uint32 * 4), ("stream", C.c_uint32), ("seed", C.c_uint64),
+                ("repeat_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
+                ("penalty_window", C.c_uint32), ("recent", C.POINTER(C.c_uint32)), ("n_recent", C.c_uint32)]
 
     @staticmethod
-    def of(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, stream: int = 0, stop=()) -> "SamplingC":
-        """stop: up to 4 token ids (more: handed over as they are, for the library to refuse)"""
-        s = SamplingC(temperature=temperature, top_p=top_p, top_k=top_k, n_stop=len(stop), stream=stream, seed=seed)
+    def of(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, stream: int = 0, stop=(), repeat_penalty: float = 0.0,
+           presence_penalty: float = 0.0, frequency_penalty: float = 0.0, penalty_window: int = 0, recent=None) -> "SamplingC":
+        """stop: up to 4 token ids (more: handed over as they are, for the library to refuse). The penalties default to off.
+        recent: the tokens before the call, oldest first (None: no array); a longer history is cut to its last penalty_window
+        tokens — all any entry point reads —, and the array lives as long as the structure."""
+        s = SamplingC(temperature=temperature, top_p=top_p, top_k=top_k, n_stop=len(stop), stream=stream, seed=seed, repeat_penalty=repeat_penalty,
+                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window)
         for i, t in enumerate(list(stop)[:4]):
             s.stop[i] = t
+        if recent is not None:
+            keep = [int(t) for t in recent]
+            if 0 < penalty_window <= 256:
+                keep = keep[-penalty_window:]
+            s._recent = (C.c_uint32 * max(len(keep), 1))(*keep)
+            s.recent = C.cast(s._recent, C.POINTER(C.c_uint32))
+            s.n_recent = len(keep)
         return s
 
 

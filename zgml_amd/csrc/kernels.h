@@ -475,6 +475,9 @@ void launch_spec_accept(hipStream_t s, const SpecArgs& a);
 struct SampleParamsDev {
     float inv_temperature, top_p;
     uint32_t top_k, n_stop, stop[4], stream, seed_lo, seed_hi;
+    // the penalties (sample.h), read by the penalised select launch alone: pen_active = 0 leaves the row's logits as they are
+    float repeat, inv_repeat, presence, frequency;
+    uint32_t window, pen_active;
 };
 // What the second launch does with the token of row b = blockIdx.y:
 //   state == nullptr       the blocking form: out[0] = token, cand[0] = number of candidates, cand[1 + j] = index of candidate j
@@ -494,6 +497,24 @@ struct SampleAdvance {
     uint32_t* picks = nullptr;
     const uint32_t* pos_word = nullptr;
 };
+// Where the penalised select launch finds the window of row b (sample.h: positions max(lo, P + 1 - W) .. P); which form holds
+// follows SampleAdvance's:
+//   blocking form          list[0, n_list): the window itself, oldest first (the host has cut it to the last W tokens)
+//   the loops              P = the sequence's position word, the token at P its token word; the token at an earlier position q
+//                          is ring[b * 256 + (q & 255)], lo[b] the first position known. The select launch itself stores the
+//                          token at P into the ring (workgroup 0 of the row; no other workgroup reads that slot in this
+//                          launch: it is the slot of P - 256), so the merge launch is the unpenalised one, untouched
+//   a verify step          P = *pos_word + b; the token at q is hist[q] for q <= *pos_word, cand[q - *pos_word] behind it;
+//                          lo = *lo_word. The rows read parameter row 0
+struct SampleWindow {
+    const uint32_t* list = nullptr;
+    uint32_t n_list = 0;
+    uint32_t* ring = nullptr;
+    const uint32_t* lo = nullptr;
+    const uint32_t* hist = nullptr;
+    const uint32_t* cand = nullptr;
+    const uint32_t* lo_word = nullptr;
+};
 constexpr uint32_t kSampleMaxSlices = 32; // partial candidate lists per row
 constexpr uint32_t kSampleChunk = 1792;   // logits a select workgroup sorts at a time (with the 256 best so far: 2048 keys)
 inline uint32_t sample_slices(uint64_t n) {
@@ -504,6 +525,10 @@ inline size_t sample_scratch_keys(uint64_t n, uint32_t rows) { return (size_t)ro
 // `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select: sample_slices(n) sorted lists of the 256 largest keys per row]
 // [merge to the row's candidates + pick + advance]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
 void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv);
+// ... with the penalties of params[] applied to the logits before the selection: the same two launches, the first in its
+// penalised form (a kernel of its own), the second as it is
+void launch_sample_penalized(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
+                             const SampleAdvance& adv, const SampleWindow& win);
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes);
 void launch_f32_to_f16(hipStream_t s, void* dst, const float* src, uint64_t n);
 

@@ -638,6 +638,7 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipFree(ctx->smp_keys);
     hipFree(ctx->smp_params);
     hipFree(ctx->smp_out);
+    hipFree(ctx->smp_win);
     if (ctx->handoff_flag) hipHostFree(ctx->handoff_flag);
     hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -124,6 +124,7 @@ struct zgml_hip_ctx {
     uint64_t* smp_keys = nullptr;
     SampleParamsDev* smp_params = nullptr;
     uint32_t* smp_out = nullptr; // [0, 1]: the token (64 bits); [2]: count; [3, 259): indices
+    uint32_t* smp_win = nullptr; // the window of a penalised zgml_hip_sample, [256] (allocated by the first such call)
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
     // Fused launches (q/k/v projection + decode attention): ONE host-visible word every bounded in-launch wait sets when it
     // gives up (pinned, device-mapped: the host reads it after any synchronisation without a copy). A set word means the

@@ -5,6 +5,7 @@
 // No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's in their own files.
 #include "runtime_internal.h"
 #include "sample.h"
+#include "sample_params.h"
 #include "spec.h"
 
 struct zgml_resident {
@@ -48,6 +49,12 @@ struct zgml_resident {
     uint64_t* skeys = nullptr;
     hipGraph_t graph_sampled = nullptr;
     hipGraphExec_t graph_sampled_exec = nullptr;
+    // penalised sampled tail (sample.h: the penalties), allocated by the first such call of the single or the batched loop: the
+    // window of every sequence, [n_seqs][256] token words indexed by position & 255, then lo per sequence (the verify step reads
+    // hist / cand instead); the penalised loops' own graph, beside the other two
+    uint32_t* swin = nullptr;
+    hipGraph_t graph_penalized = nullptr;
+    hipGraphExec_t graph_penalized_exec = nullptr;
 };
 using Resident = zgml_resident;
 
@@ -65,6 +72,9 @@ void free_resident_graph(zgml_hip_program* p) {
     if (r->graph_sampled_exec) hipGraphExecDestroy(r->graph_sampled_exec);
     if (r->graph_sampled) hipGraphDestroy(r->graph_sampled);
     r->graph_sampled_exec = nullptr, r->graph_sampled = nullptr;
+    if (r->graph_penalized_exec) hipGraphExecDestroy(r->graph_penalized_exec);
+    if (r->graph_penalized) hipGraphDestroy(r->graph_penalized);
+    r->graph_penalized_exec = nullptr, r->graph_penalized = nullptr;
 }
 
 void free_resident(zgml_hip_program* p) {
@@ -92,6 +102,7 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->picks);
     hipFree(r->sparams);
     hipFree(r->skeys);
+    hipFree(r->swin);
     delete r;
     p->resident = nullptr;
 }
@@ -140,9 +151,13 @@ void resident_end(zgml_hip_program* p, uint64_t steps, uint64_t launches_per_ste
     p->profile.backend_dispatch_count += steps * launches_per_step;
 }
 
+// which entry point's rules the `recent` tokens of a zgml_sampling are held to (include/zgml_hip.h)
+enum class RecentOf { Sample, Loop, Spec };
+
 // a caller's zgml_sampling as the kernels read it; false (with the error on the context) for what the header refuses.
-// vocab == 0: the stop tokens are not looked at (zgml_hip_sample)
-bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampling* sp, uint32_t vocab, SampleParamsDev* out) {
+// vocab == 0: the stop tokens are not looked at (zgml_hip_sample). start_pos: of the sequence, for the loops' n_recent rule
+bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampling* sp, uint32_t vocab, SampleParamsDev* out,
+                     RecentOf form = RecentOf::Sample, uint32_t start_pos = 0) {
     if (!sp) {
         ctx->fail(who + ": no sampling parameters");
         return false;
@@ -160,9 +175,33 @@ bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampl
             ctx->fail(who + ": stop token out of range");
             return false;
         }
+    // the penalties: pure host logic in a header of its own, so that a CPU test can hold it to the list in include/zgml_hip.h
+    float repeat = 1.0f;
+    uint32_t active = 0;
+    if (const char* why = sample_penalty_check(sp, form == RecentOf::Loop ? 1 : form == RecentOf::Spec ? 2 : 0, vocab, start_pos, &repeat, &active)) {
+        ctx->fail(who + ": " + why);
+        return false;
+    }
     *out = SampleParamsDev{1.0f / sp->temperature, sp->top_p, sp->top_k, vocab ? sp->n_stop : 0, {sp->stop[0], sp->stop[1], sp->stop[2], sp->stop[3]},
-                           sp->stream, (uint32_t)sp->seed, (uint32_t)(sp->seed >> 32)};
+                           sp->stream, (uint32_t)sp->seed, (uint32_t)(sp->seed >> 32),
+                           repeat, 1.0f / repeat, sp->presence_penalty, sp->frequency_penalty, sp->penalty_window, active};
     return true;
+}
+
+// the window block of the penalised loops: [rows][256] ring words, then lo per row
+bool ensure_window_block(zgml_hip_ctx* ctx, Resident* r, uint32_t rows) {
+    return r->swin || CTX_CHECK(ctx, hipMalloc((void**)&r->swin, (size_t)rows * (kSamplePenaltyMaxWindow + 1) * 4));
+}
+
+// ... and what a call uploads into it for sequence b of `rows`: the last W - 1 of its recent tokens at their positions' slots
+// (the token at start_pos and every later one is filed by the select launch itself), and lo
+void fill_window_block(std::vector<uint32_t>& block, uint32_t rows, uint32_t b, const zgml_sampling& sp, uint32_t start_pos) {
+    const uint32_t W = sp.penalty_window, take = W ? std::min(sp.n_recent, W - 1) : 0;
+    for (uint32_t i = 0; i < take; i++) {
+        const uint32_t q = start_pos - take + i;
+        block[(size_t)b * kSamplePenaltyMaxWindow + (q & (kSamplePenaltyMaxWindow - 1))] = sp.recent[sp.n_recent - take + i];
+    }
+    block[(size_t)rows * kSamplePenaltyMaxWindow + b] = start_pos - sp.n_recent;
 }
 
 // the sampled loops' device blocks: `rows` parameter rows and partial candidate lists
@@ -437,7 +476,16 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
     SampleAdvance adv;
     adv.position = position, adv.out = (int64_t*)ctx->smp_out, adv.cand = ctx->smp_out + 2;
-    launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
+    if (sp.pen_active) { // the window: the last W of the recent tokens, the token whose logits these are last
+        const uint32_t take = std::min(sampling->n_recent, sp.window);
+        if (!ctx->smp_win && !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_win, kSamplePenaltyMaxWindow * 4))) return -1;
+        if (take && !CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_win, sampling->recent + (sampling->n_recent - take), (size_t)take * 4, hipMemcpyHostToDevice, s))) return -1;
+        SampleWindow win;
+        win.list = ctx->smp_win, win.n_list = take;
+        launch_sample_penalized(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv, win);
+    } else {
+        launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
+    }
     uint32_t got[out_words];
     hipMemcpyAsync(got, ctx->smp_out, sizeof(got), hipMemcpyDeviceToHost, s);
     if (!CTX_CHECK(ctx, hipStreamSynchronize(s)) || !ctx->handoff_ok("sample")) return -1;
@@ -464,7 +512,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         return -1;
     }
     SampleParamsDev sp;
-    if (!sampling_params(ctx, "resident_decode_sampled", sampling, r->vocab, &sp)) return -1;
+    if (!sampling_params(ctx, "resident_decode_sampled", sampling, r->vocab, &sp, RecentOf::Loop, start_pos)) return -1;
     if (first_token >= r->vocab || (uint64_t)start_pos + n_steps > r->max_seq) {
         ctx->fail("resident_decode_sampled: token or position out of range");
         return -1;
@@ -475,7 +523,8 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     resident_begin(p, [&] {
         return positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; });
     });
-    if (!ensure_sample_blocks(ctx, r, 1)) return -1;
+    const bool penalized = sp.pen_active != 0;
+    if (!ensure_sample_blocks(ctx, r, 1) || (penalized && !ensure_window_block(ctx, r, 1))) return -1;
     if (r->tokens_cap < n_steps) {
         hipStreamSynchronize(s);
         hipFree(r->tokens);
@@ -489,23 +538,36 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
     SampleAdvance adv;
     adv.state = r->state, adv.tokens = r->tokens, adv.cap = r->tokens_cap;
+    SampleWindow win;
+    win.ring = r->swin, win.lo = r->swin + kSamplePenaltyMaxWindow;
     auto one_token = [&](hipStream_t st) {
         launch_resident_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
-        launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
+        if (penalized)
+            launch_sample_penalized(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win);
+        else
+            launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
     };
+    std::vector<uint32_t> win0; // (penalised calls only; alive until the call's last synchronisation)
+    if (penalized) {
+        win0.assign(kSamplePenaltyMaxWindow + 1, 0);
+        fill_window_block(win0, 1, 0, *sampling, start_pos);
+        if (!CTX_CHECK(ctx, hipMemcpyAsync(r->swin, win0.data(), win0.size() * 4, hipMemcpyHostToDevice, s))) return -1;
+    }
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // ([3]: set by a stop token)
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, &sp, sizeof(sp), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_steps * 8, s))) // (-1: what a stopped sequence leaves behind its stop token)
         return -1;
-    if (ctx->opt_graph && !r->graph_sampled_exec) {
+    // (a penalised call replays a graph of its own: the two kinds of call alternate on one program and invalidate nothing)
+    hipGraphExec_t& exec = penalized ? r->graph_penalized_exec : r->graph_sampled_exec;
+    if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (the copies above read this stack frame: none in flight when the capture begins)
-        capture_graph(ctx, s, "resident_sampled", [&] { one_token(s); }, &r->graph_sampled, &r->graph_sampled_exec); // (failed: eager below)
+        capture_graph(ctx, s, penalized ? "resident_penalized" : "resident_sampled", [&] { one_token(s); }, penalized ? &r->graph_penalized : &r->graph_sampled, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < n_steps; i++) {
-        if (r->graph_sampled_exec)
-            hipGraphLaunch(r->graph_sampled_exec, s);
+        if (exec)
+            hipGraphLaunch(exec, s);
         else
             one_token(s);
     }
@@ -533,7 +595,7 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     const uint32_t B = r->n_seqs;
     std::vector<SampleParamsDev> sp(B);
     for (uint32_t b = 0; b < B; b++)
-        if (!sampling_params(ctx, "resident_decode_batch_sampled (sequence " + std::to_string(b) + ")", per_seq ? per_seq + b : nullptr, r->vocab, &sp[b])) return -1;
+        if (!sampling_params(ctx, "resident_decode_batch_sampled (sequence " + std::to_string(b) + ")", per_seq ? per_seq + b : nullptr, r->vocab, &sp[b], RecentOf::Loop, start_pos[b])) return -1;
     uint32_t steps = 0;
     for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
     if (steps > max_steps) {
@@ -560,7 +622,9 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     resident_begin(p, [&] {
         return positions_in_bounds(p, 1, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) && positions_in_bounds(p, 1, [&](uint32_t i) { return last_pos[p->op_seq[i]]; });
     });
-    if (!ensure_sample_blocks(ctx, r, B)) return -1;
+    bool penalized = false; // one sequence with penalties: the penalised launch for all (a row without them computes what it did)
+    for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active;
+    if (!ensure_sample_blocks(ctx, r, B) || (penalized && !ensure_window_block(ctx, r, B))) return -1;
     if (r->btokens_cap < (uint64_t)B * steps) {
         hipStreamSynchronize(s);
         hipFree(r->btokens);
@@ -574,11 +638,22 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
     SampleAdvance adv;
     adv.state = r->bstate, adv.tokens = r->btokens, adv.n_seqs = B;
+    SampleWindow win;
+    win.ring = r->swin, win.lo = r->swin + (size_t)B * kSamplePenaltyMaxWindow;
     auto one_step = [&](hipStream_t st) {
         launch_resident_batch_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
-        launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
+        if (penalized)
+            launch_sample_penalized(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win);
+        else
+            launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
     };
+    std::vector<uint32_t> win0;
+    if (penalized) {
+        win0.assign((size_t)B * (kSamplePenaltyMaxWindow + 1), 0);
+        for (uint32_t b = 0; b < B; b++) fill_window_block(win0, B, b, per_seq[b], start_pos[b]);
+        if (!CTX_CHECK(ctx, hipMemcpyAsync(r->swin, win0.data(), win0.size() * 4, hipMemcpyHostToDevice, s))) return -1;
+    }
     std::vector<uint32_t> st0((size_t)4 * B + 1, 0), st1((size_t)4 * B + 1, 0);
     for (uint32_t b = 0; b < B; b++) st0[b] = first_tokens[b], st0[B + b] = start_pos[b], st0[2 * B + b] = n_steps[b];
     st0[4 * B] = steps; // row length of the device token table of this call
@@ -586,13 +661,14 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, sp.data(), sp.size() * sizeof(SampleParamsDev), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
         return -1;
-    if (ctx->opt_graph && !r->graph_sampled_exec) {
+    hipGraphExec_t& exec = penalized ? r->graph_penalized_exec : r->graph_sampled_exec;
+    if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (as the greedy batched loop: no pageable copy in flight when the capture begins)
-        capture_graph(ctx, s, "resident_batch_sampled", [&] { one_step(s); }, &r->graph_sampled, &r->graph_sampled_exec); // (failed: eager below)
+        capture_graph(ctx, s, penalized ? "resident_batch_penalized" : "resident_batch_sampled", [&] { one_step(s); }, penalized ? &r->graph_penalized : &r->graph_sampled, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < steps; i++) {
-        if (r->graph_sampled_exec)
-            hipGraphLaunch(r->graph_sampled_exec, s);
+        if (exec)
+            hipGraphLaunch(exec, s);
         else
             one_step(s);
     }
@@ -703,7 +779,8 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         return -1;
     }
     SampleParamsDev sp{};
-    if (sampled && !sampling_params(ctx, who, sampling, r->vocab, &sp)) return -1;
+    if (sampled && !sampling_params(ctx, who, sampling, r->vocab, &sp, RecentOf::Spec)) return -1;
+    const bool penalized = sp.pen_active != 0; // (sampled form only)
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     // the first start and the last possible start of a verify step
@@ -746,6 +823,8 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         sa.picks = r->picks, sa.sparams = r->sparams;
         adv.picks = r->picks, adv.pos_word = r->spec + kSpecRunPos;
     }
+    SampleWindow win; // (penalised form only) a row's window is the call's history up to the run position and the candidates behind it
+    win.hist = r->hist, win.cand = r->tok_dev, win.lo_word = r->spec + kSpecHistLo;
     // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
     const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
                              p->dyn_dev, r->spec + kSpecRun, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), T};
@@ -757,16 +836,19 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         launch_spec_draft(st, sa);
         launch_resident_prep(st, a, (uint32_t)total);
         run_plan(p, st, 0, p->plan.size());
-        if (sampled)
+        if (penalized)
+            launch_sample_penalized(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv, win);
+        else if (sampled)
             launch_sample(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv);
         else
             launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
         launch_spec_accept(st, sa);
     };
-    hipGraphExec_t& exec = sampled ? r->graph_sampled_exec : r->graph_exec;
+    hipGraphExec_t& exec = penalized ? r->graph_penalized_exec : sampled ? r->graph_sampled_exec : r->graph_exec;
     if (ctx->opt_graph && !exec) {
         if (sampled) hipStreamSynchronize(s); // (as the sampled loops: no copy from this stack frame in flight when the capture begins)
-        capture_graph(ctx, s, sampled ? "resident_spec_sampled" : "resident_spec", [&] { one_step(s); }, sampled ? &r->graph_sampled : &r->graph, &exec); // (failed: eager below)
+        capture_graph(ctx, s, penalized ? "resident_spec_penalized" : sampled ? "resident_spec_sampled" : "resident_spec", [&] { one_step(s); },
+                      penalized ? &r->graph_penalized : sampled ? &r->graph_sampled : &r->graph, &exec); // (failed: eager below)
     }
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)

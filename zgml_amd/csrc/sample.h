@@ -21,6 +21,20 @@
 // THE RANDOM NUMBER. Philox4x32-10, key (seed low word, seed high word), counter (position, stream, 0, 0), where `position` is
 // the position whose logits are sampled; u = (word 0 >> 8) * 2^-24 in [0, 1). u depends on (seed, stream, position) alone: a
 // generation is the same in one call or several, alone or inside a batch.
+//
+// THE PENALTIES (repetition, presence, frequency; off unless zgml_sampling says otherwise). The pick at position P — over the
+// logits produced by feeding the token at P — sees the tokens at positions max(lo, P + 1 - W) .. P: W = penalty_window
+// (1 .. kSamplePenaltyMaxWindow), lo the first position whose token the call knows. count(t) is the number of occurrences of
+// token t among them. A logit v of a token with count c > 0 becomes sample_penalize(v, c, ...):
+//   v1 = v > 0 ? v * inv_repeat : v * repeat;  v2 = v1 - (float)c * frequency;  v3 = v2 - presence
+// — three or four rounded f32 operations —, a logit of a token with count 0 stays as it is to the bit. The candidates, the pick
+// and the random number are then exactly the ones above, computed over the penalised values: penalties come before the
+// selection (a penalised token may leave the 256 largest, an encouraged one may enter them from below) and before the
+// temperature, and the index in a key stays the token's index.
+//   DEVIATION from llama.cpp's sampler, the one deliberate one, in the last bit: a positive logit is MULTIPLIED by
+//   inv_repeat = 1.0f / repeat, computed once on the host as inv_temperature is, where llama.cpp divides by repeat. Host and
+//   device therefore cannot disagree about a division.
+// A NaN or an infinity passes through these operations as IEEE says; sample_ordered then maps a NaN to -inf as ever.
 #pragma once
 
 #include <math.h>
@@ -37,6 +51,7 @@ namespace zgml {
 
 constexpr uint32_t kSampleMaxK = 256;   // the candidate set's upper bound
 constexpr uint32_t kSampleMaxStop = 4;  // stop tokens per sequence
+constexpr uint32_t kSamplePenaltyMaxWindow = 256; // positions a penalty looks back over, the sampled one included
 
 ZGML_SAMPLE_FN uint32_t sample_f32_bits(float v) {
     uint32_t b;
@@ -151,6 +166,40 @@ ZGML_SAMPLE_FN bool sample_is_stop(uint32_t token, uint32_t n_stop, const uint32
     for (uint32_t i = 0; i < n_stop && i < kSampleMaxStop; i++)
         if (stop[i] == token) return true;
     return false;
+}
+
+// ── the penalties ──
+
+// the logit v of a token that occurs `count` times in the window (inv_repeat = 1.0f / repeat, from the host)
+ZGML_SAMPLE_FN float sample_penalize(float v, uint32_t count, float repeat, float inv_repeat, float presence, float frequency) {
+    if (count == 0) return v;
+    const float v1 = v > 0.0f ? v * inv_repeat : v * repeat;
+    const float v2 = v1 - (float)count * frequency;
+    return v2 - presence;
+}
+
+// Entry i of the window win[0, m), m <= kSamplePenaltyMaxWindow: 0 when the token occurred at an earlier entry, else the number
+// of its occurrences in the window. The entries with a result > 0 are the window's distinct tokens, each once, with count(t).
+// O(m) per entry, O(m^2) for a window: the kernel gives every entry a thread, the probe walks them.
+ZGML_SAMPLE_FN uint32_t sample_window_count(const uint32_t* win, uint32_t m, uint32_t i) {
+    const uint32_t t = win[i];
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < m; j++) {
+        if (win[j] != t) continue;
+        if (j < i) return 0;
+        c++;
+    }
+    return c;
+}
+
+// the window of the pick at `position`: its first position and (the return value) its length. lo > position: nothing is known
+ZGML_SAMPLE_FN uint32_t sample_window_span(uint32_t position, uint32_t lo, uint32_t window, uint32_t* first) {
+    *first = position;
+    if (lo > position) return 0;
+    const uint32_t known = position - lo + 1;
+    const uint32_t m = known < window ? known : window;
+    *first = position + 1 - m;
+    return m;
 }
 
 } // namespace zgml

@@ -10,6 +10,11 @@
 //   [merge + pick + advance]  grid (1, rows), 1024 threads: the slices' lists — at most 32 x 256 keys, 64 KiB of LDS — are loaded
 //             with every second list reversed, which is the state of a bitonic sort after its 256-runs: only the merge stages
 //             from 512 up remain. Then the threads fill p[j] (sample_prob), thread 0 walks sample_pick_probs and advances.
+//   [select, penalised]  sample_select_penalized_kernel, a kernel of its own in the place of [select] when a row has penalties
+//             (sample.h): the workgroup loads its row's window — at most 256 token ids, one per thread — into
+//             LDS, every thread counts its entry (sample_window_count), and behind the fill of every chunk each first occurrence
+//             whose token lies in the chunk rewrites that one key with the key of the penalised logit. The cost does not depend
+//             on the vocabulary: there is no table of counts. The merge launch is the same launch either way.
 #include "kernels.h"
 #include "sample.h"
 
@@ -50,6 +55,69 @@ __global__ void __launch_bounds__(kSelBlock) sample_select_kernel(const float* _
             for (uint32_t j = k >> 1; j > 0; j >>= 1) bitonic_stage<kSelBlock>(s, kSelKeys / 2, k, j);
     }
     uint64_t* out = part + ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * kSampleMaxK;
+    for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) out[t] = s[t];
+}
+
+// The penalised form of sample_select_kernel (which stays as it is: a call without penalties launches that one). Row b's window
+// comes from where SampleWindow says (kernels.h); entry t is thread t's. A row whose pen_active is 0 — a batched sequence
+// without penalties beside one with them — takes no branch below and computes what sample_select_kernel computes.
+__global__ void __launch_bounds__(kSelBlock) sample_select_penalized_kernel(const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part,
+                                                                            const SampleParamsDev* __restrict__ params, SampleAdvance adv, SampleWindow w) {
+    __shared__ uint64_t s[kSelKeys];
+    __shared__ uint32_t win[kSamplePenaltyMaxWindow];
+    static_assert(kSelBlock == kSamplePenaltyMaxWindow, "a thread per window entry");
+    const uint32_t b = blockIdx.y;
+    const SampleParamsDev& sp = params[adv.picks ? 0 : b];
+    const bool active = sp.pen_active != 0; // (uniform over the workgroup: the barriers below hang on it)
+    uint32_t tok = 0, count = 0;
+    if (active) {
+        uint32_t m = 0;
+        if (adv.picks) { // row b of a verify step
+            const uint32_t run = *adv.pos_word, P = run + b;
+            uint32_t first;
+            m = sample_window_span(P, *w.lo_word, sp.window, &first);
+            if (threadIdx.x < m) {
+                const uint32_t q = first + threadIdx.x;
+                tok = q <= run ? w.hist[q] : w.cand[q - run];
+            }
+        } else if (!adv.state) { // the blocking form: the list is the window
+            m = w.n_list < sp.window ? w.n_list : sp.window;
+            if (threadIdx.x < m) tok = w.list[w.n_list - m + threadIdx.x];
+        } else { // the loops: the sequence's ring, and the token being fed, which this launch files at its position
+            const uint32_t B = adv.n_seqs;
+            const uint32_t cur = B ? adv.state[b] : adv.state[0], P = B ? adv.state[B + b] : adv.state[1];
+            uint32_t* const ring = w.ring + (uint64_t)b * kSamplePenaltyMaxWindow;
+            uint32_t first;
+            m = sample_window_span(P, w.lo[b], sp.window, &first);
+            if (threadIdx.x < m) {
+                const uint32_t q = first + threadIdx.x;
+                tok = q == P ? cur : ring[q & (kSamplePenaltyMaxWindow - 1)];
+            }
+            if (blockIdx.x == 0 && threadIdx.x == 0) ring[P & (kSamplePenaltyMaxWindow - 1)] = cur; // (the slot of P - 256: outside every window read here)
+        }
+        if (threadIdx.x < m) win[threadIdx.x] = tok;
+        __syncthreads();
+        if (threadIdx.x < m) count = sample_window_count(win, m, threadIdx.x);
+    }
+    const float* row = v + (uint64_t)b * n;
+    const uint64_t lo = (uint64_t)blockIdx.x * len, hi = lo + len < n ? lo + len : n; // (lo may lie behind n: an empty slice, all pads)
+    for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) s[t] = 0;
+    for (uint64_t base = lo; base == lo || base < hi; base += kSampleChunk) {
+        for (uint32_t t = threadIdx.x; t < kSampleChunk; t += kSelBlock) {
+            const uint64_t i = base + t;
+            s[kSampleMaxK + t] = i < hi ? sample_key(row[i], (uint32_t)i) : 0;
+        }
+        if (active) {
+            __syncthreads(); // the slot below was filled by another thread
+            // distinct tokens, distinct slots: no two threads write one key. A token >= n lies in no chunk
+            if (count && tok >= base && tok < hi && tok - base < kSampleChunk)
+                s[kSampleMaxK + (uint32_t)(tok - base)] = sample_key(sample_penalize(row[tok], count, sp.repeat, sp.inv_repeat, sp.presence, sp.frequency), tok);
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= kSelKeys; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) bitonic_stage<kSelBlock>(s, kSelKeys / 2, k, j);
+    }
+    uint64_t* out = part + ((uint64_t)b * gridDim.x + blockIdx.x) * kSampleMaxK;
     for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) out[t] = s[t];
 }
 
@@ -123,6 +191,17 @@ void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uin
     uint32_t P = kSampleMaxK;
     while (P < slices * kSampleMaxK) P <<= 1;
     sample_select_kernel<<<dim3(slices, rows), kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch);
+    sample_merge_pick_kernel<<<dim3(1, rows), kMergeBlock, 0, s>>>(scratch, (uint32_t)n, slices, P, params, adv);
+}
+
+void launch_sample_penalized(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
+                             const SampleAdvance& adv, const SampleWindow& win) {
+    if (!n || n > 0xFFFFFFFFull || !rows) return; // (the callers refuse these)
+    const uint32_t slices = sample_slices(n);
+    const uint32_t len = (uint32_t)((n + slices - 1) / slices);
+    uint32_t P = kSampleMaxK;
+    while (P < slices * kSampleMaxK) P <<= 1;
+    sample_select_penalized_kernel<<<dim3(slices, rows), kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch, params, adv, win);
     sample_merge_pick_kernel<<<dim3(1, rows), kMergeBlock, 0, s>>>(scratch, (uint32_t)n, slices, P, params, adv);
 }
 

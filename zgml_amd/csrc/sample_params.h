@@ -1,0 +1,34 @@
+// sample_params.h — what include/zgml_hip.h refuses of the penalty fields of a zgml_sampling, as pure host logic: the runtime
+// (runtime_resident.hip: sampling_params) and the CPU probe tests/cpp/penalty_probe.cpp compile this one function.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#include "sample.h"
+#include "zgml_hip.h"
+
+namespace zgml {
+
+// The penalty fields of a zgml_sampling against the header's list of refusals: nullptr, or why the call is refused. form: 0
+// zgml_hip_sample, 1 the single and the batched loop (vocab and start_pos are the sequence's), 2 the verify step. *repeat: the
+// factor as the rule reads it (0 means 1); *active: whether the penalised launch is needed at all.
+inline const char* sample_penalty_check(const zgml_sampling* sp, int form, uint32_t vocab, uint32_t start_pos, float* repeat, uint32_t* active) {
+    const float rp = sp->repeat_penalty, pp = sp->presence_penalty, fp = sp->frequency_penalty;
+    if (!isfinite(rp) || !isfinite(pp) || !isfinite(fp) || rp < 0.0f) return "the penalties must be finite and repeat_penalty not negative";
+    if (sp->penalty_window > kSamplePenaltyMaxWindow) return "penalty_window must be at most 256";
+    const bool neutral = (rp == 0.0f || rp == 1.0f) && pp == 0.0f && fp == 0.0f;
+    if (!neutral && sp->penalty_window == 0) return "a penalty that is not neutral needs penalty_window > 0";
+    if (!sp->recent && sp->n_recent) return "n_recent > 0 without the recent tokens";
+    if (form == 2 && sp->recent) return "recent must be NULL (the tokens before a speculative call are opt->history)";
+    if (form == 1) {
+        if (sp->n_recent > start_pos) return "n_recent exceeds start_pos";
+        for (uint32_t i = 0; i < sp->n_recent; i++)
+            if (sp->recent[i] >= vocab) return "recent token out of range";
+    }
+    *repeat = rp == 0.0f ? 1.0f : rp;
+    *active = !neutral && sp->penalty_window > 0;
+    return nullptr;
+}
+
+} // namespace zgml
