@@ -649,6 +649,7 @@ typedef struct zgml_sampling {
     uint32_t n_stop;     /* 0..4 */
     uint32_t stop[4];    /* < vocab */
     uint32_t stream;     /* Philox counter word 1 */
+    uint32_t logprobs;   /* 0: off; else keep the log-probability of every token of the call (below). The word was padding before */
     uint64_t seed;
     /* the penalties (below); an all-zero tail: off */
     float repeat_penalty;    /* 0 or 1: neutral; else finite and > 0 */
@@ -683,14 +684,50 @@ typedef struct zgml_sampling {
  * Refused with -1 and an error on the context, before anything is enqueued: a penalty that is not neutral with
  *   penalty_window = 0; penalty_window > 256; a penalty that is not finite, or repeat_penalty < 0; recent = NULL with
  *   n_recent > 0; in the loops a recent token >= vocab and n_recent > start_pos; in the speculative call recent != NULL. */
+/* The log-probability of every sampled token: the word `logprobs` (rule: zgml_amd/csrc/sample.h, "THE LOG-PROBABILITY"). 0: exactly
+ *   the launches, the graphs and the tokens of a call without it. Not 0: the call also computes, for every token it emits,
+ *   log softmax(row)[token] over the logits row the token was picked from — the WHOLE vocabulary and the RAW logits: before the
+ *   penalties, before the temperature, whatever top_k / top_p are; the model's own distribution, independent of how the token was
+ *   picked (with penalties on, the value of the token the penalised pick chose under the unpenalised row) — and keeps them on the
+ *   context for zgml_hip_logprobs_result (below). A device value equals the header's over the same logits bits, to the bit:
+ *   sample_exp, sample_log and the order of every sum are part of the rule. Against float64 the error is at most
+ *   1e-5 + 2.4e-7 |v_token - max(row)|.
+ *   Why a word and a getter, not an output pointer in the structure: the word takes the four bytes of padding between `stream` and
+ *   `seed`, so no field moves and the structure keeps its size — arrays of it, and callers built against the earlier header, stay
+ *   valid. A caller that never zeroed the structure may have the word set by accident: that costs two launches per step and
+ *   changes no result.
+ *   Layout of the values, that of the call's tokens_out: zgml_hip_resident_decode_sampled [n_steps]; _batch_sampled
+ *   [n_seqs][max_steps], sequences with and without the word side by side (a row of a sequence without it is all NaN);
+ *   _speculative_sampled [n_tokens], entry i the value of tokens_out[i] under the row of the verify step that emitted it;
+ *   zgml_hip_sample one float for the returned token. Entries of tokens that were not produced — behind a stop token, behind a
+ *   sequence's count, behind the cut — are the quiet NaN 0x7FC00000, the analogue of tokens_out's -1. A frozen sequence's later
+ *   steps write nothing. top_k = 1 makes every sampled entry point a greedy loop with log-probabilities: the greedy entry points
+ *   have no twin.
+ *   Cost: two launches more per step ([partial sums: 4096 logits per workgroup] in front of the select, [finish: one wave per
+ *   row] behind the pick), in captured graphs of their own — calls with and without the word, with and without penalties,
+ *   alternate on one program and invalidate nothing. Refused with the word set: a row of more than 2^20 logits.
+ *   Values: a row without an entry above -inf gives -inf; a row holding +inf gives the NaN above; a token whose logit is -inf
+ *   (or NaN, which counts as -inf) gives -inf. */
+/* The values that the context's last call with the `logprobs` word set left behind, in the layout above: copies min(n, their
+ * number) floats to out and returns their number (0 before any such call); a call without the word leaves them as they are.
+ * -1 with an error on the context: out NULL with n > 0. */
+int64_t zgml_hip_logprobs_result(zgml_hip_ctx* ctx, float* out, uint64_t n);
 /* The sampling sibling of zgml_hip_argmax over f32 elements [offset, offset + n) of a program buffer, 1 <= n < 2^32; blocking.
  * `position` is the Philox counter's word 0; stop tokens are not looked at. For vtable-path callers, and for the first token
  * after zgml_hip_resident_prefill, whose logits rows stay in the buffer. candidates_out (NULL or 256 words) receives the
  * candidates' indices in order, *n_candidates_out (may be NULL) their number. Returns the token, -1 with an error on the context
- * for parameters out of range (below) or a range outside the buffer. */
+ * for parameters out of range (below) or a range outside the buffer. sampling->logprobs (above): one float, the returned token's, for zgml_hip_logprobs_result. */
 int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n,
                         const zgml_sampling* sampling, uint32_t position, uint32_t* candidates_out /* NULL or [256] */,
                         uint32_t* n_candidates_out);
+/* The scoring sibling of zgml_hip_sample: logprobs_out[i] = log softmax(row i)[tokens[i]] (the rule above) over `rows` consecutive
+ * rows of n f32 elements each, row i at [offset + i n, offset + (i + 1) n) of a program buffer; blocking; two launches whatever
+ * `rows` is. After zgml_hip_resident_prefill of a T-token chunk at start_pos, row i of the logits buffer with tokens[i] = the
+ * prompt's token at start_pos + i + 1 is that token's log-likelihood: a prompt is scored with T - 1 floats per chunk coming
+ * back instead of T x vocab logits. Returns 0. Refused with -1 and an error on the context, nothing enqueued: n = 0, n > 2^20,
+ * rows = 0, a token >= n, a range outside the buffer, tokens or logprobs_out NULL. */
+int zgml_hip_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n, uint32_t rows,
+                      const uint32_t* tokens /* [rows] */, float* logprobs_out /* [rows] */);
 /* zgml_hip_resident_decode with the sampled tail: per token [prep] [plan] [select] [merge + pick + advance], the launch count of
  * the greedy loop, one graph launch per token. The parameters live in a device table uploaded per call, so one captured graph —
  * a separate one from the greedy loop's: alternating calls on one program invalidate nothing — serves every parameter set.

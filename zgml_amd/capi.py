@@ -188,18 +188,19 @@ class SpecStatsC(C.Structure):
 class SamplingC(C.Structure):
     """zgml_sampling (include/zgml_hip.h): the parameters of the sampled token tail."""
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_uint32), ("n_stop", C.c_uint32),
-                ("stop", C.c_uint32 * 4), ("stream", C.c_uint32), ("seed", C.c_uint64),
+                ("stop", C.c_uint32 * 4), ("stream", C.c_uint32), ("logprobs", C.c_uint32), ("seed", C.c_uint64),
                 ("repeat_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
                 ("penalty_window", C.c_uint32), ("recent", C.POINTER(C.c_uint32)), ("n_recent", C.c_uint32)]
 
     @staticmethod
     def of(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, stream: int = 0, stop=(), repeat_penalty: float = 0.0,
-           presence_penalty: float = 0.0, frequency_penalty: float = 0.0, penalty_window: int = 0, recent=None) -> "SamplingC":
+           presence_penalty: float = 0.0, frequency_penalty: float = 0.0, penalty_window: int = 0, recent=None, logprobs: bool = False) -> "SamplingC":
         """stop: up to 4 token ids (more: handed over as they are, for the library to refuse). The penalties default to off.
         recent: the tokens before the call, oldest first (None: no array); a longer history is cut to its last penalty_window
-        tokens — all any entry point reads —, and the array lives as long as the structure."""
+        tokens — all any entry point reads —, and the array lives as long as the structure. logprobs: the call keeps the
+        log-probability of every token it emits for logprobs_result()."""
         s = SamplingC(temperature=temperature, top_p=top_p, top_k=top_k, n_stop=len(stop), stream=stream, seed=seed, repeat_penalty=repeat_penalty,
-                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window)
+                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window, logprobs=int(bool(logprobs)))
         for i, t in enumerate(list(stop)[:4]):
             s.stop[i] = t
         if recent is not None:
@@ -210,6 +211,24 @@ class SamplingC(C.Structure):
             s.recent = C.cast(s._recent, C.POINTER(C.c_uint32))
             s.n_recent = len(keep)
         return s
+
+
+def with_logprobs(sampling: SamplingC) -> SamplingC:
+    """a copy of `sampling` (which stays as it is, and keeps its `recent` array alive) with the `logprobs` word set"""
+    sp = SamplingC.from_buffer_copy(sampling)
+    sp.logprobs = 1
+    return sp
+
+
+def logprobs_result(ctx, shape):
+    """zgml_hip_logprobs_result: the values the context's last call with the `logprobs` word set left behind, as a float32 array of
+    `shape` (the shape of that call's tokens_out)"""
+    import numpy as np
+    out = np.full(shape, np.nan, np.float32)
+    have = load_hip().zgml_hip_logprobs_result(ctx, out.ctypes.data_as(C.POINTER(C.c_float)), out.size)
+    if have != out.size:
+        raise RuntimeError(f"logprobs_result: the last call with log-probabilities left {have} values, not {out.size}")
+    return out
 
 
 class RuntimeProfileC(C.Structure):
@@ -237,7 +256,7 @@ HIP_SYMBOLS = [
     "zgml_hip_program_set_sequences", "zgml_hip_refresh_dynamic_batch", "zgml_hip_resident_decode_batch",
     "zgml_hip_resident_decode_speculative",
     "zgml_hip_sample", "zgml_hip_resident_decode_sampled", "zgml_hip_resident_decode_batch_sampled",
-    "zgml_hip_resident_decode_speculative_sampled",
+    "zgml_hip_resident_decode_speculative_sampled", "zgml_hip_logprobs", "zgml_hip_logprobs_result",
 ]
 
 class ShardPointC(C.Structure):
@@ -375,6 +394,11 @@ def _bind_hip(lib: C.CDLL) -> None:
     lib.zgml_hip_resident_decode_speculative_sampled.restype = i32
     lib.zgml_hip_resident_decode_speculative_sampled.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SpecDecodeC), C.POINTER(SamplingC), vp, C.POINTER(u32),
                                                                  C.POINTER(SpecStatsC)]
+    if hasattr(lib, "zgml_hip_logprobs"):  # absent from an older build loaded beside this one (tools/logprob_decode_run.py)
+        lib.zgml_hip_logprobs.restype = i32
+        lib.zgml_hip_logprobs.argtypes = [vp, vp, C.c_uint16, u64, u64, u32, C.POINTER(u32), C.POINTER(C.c_float)]
+        lib.zgml_hip_logprobs_result.restype = C.c_int64
+        lib.zgml_hip_logprobs_result.argtypes = [vp, C.POINTER(C.c_float), u64]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

@@ -467,6 +467,11 @@ struct SpecArgs {
     // for the T rows — instead of the fold of the partials, and sparams[0] holds the stop tokens. nullptr: the greedy form
     const uint32_t* picks = nullptr;
     const SampleParamsDev* sparams = nullptr;
+    // the log-probabilities of the sampled form (the `logprobs` field): lp_rows[j] = the value of picks[j] under row j, what the
+    // finish launch of logprob.hip wrote; the emitted prefix — behind the cut and behind spec_stop_cut — is copied to
+    // lp_out[produced ..] next to the tokens ([tokens_cap]). nullptr: none
+    const float* lp_rows = nullptr;
+    float* lp_out = nullptr;
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
@@ -529,6 +534,30 @@ void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uin
 // penalised form (a kernel of its own), the second as it is
 void launch_sample_penalized(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
                              const SampleAdvance& adv, const SampleWindow& win);
+// ── log softmax(row)[token] (logprob.hip; the rule is sample.h's) ──
+// [partial]: (m_b, s_b) of every block of 4096 logits of `rows` rows of n logits (row stride n), 1 <= n <= 2^20, into
+// part[rows][logprob_blocks(n)][2]. It reads the logits alone: it may run before or behind the pick.
+void launch_logprob(hipStream_t s, const float* v, uint64_t n, uint32_t rows, float* part);
+// [finish], one wave per row: the token of row b = blockIdx.y and where its value goes, the first form whose pointer is set:
+//   tokens                 out[b] = the value of tokens[b] (zgml_hip_logprobs)
+//   token64                out[0] = the value of (uint32_t)token64[0], what the merge launch stored (zgml_hip_sample; one row)
+//   picks                  out[b] = the value of picks[b] (a verify step; spec_accept_kernel copies the emitted prefix)
+//   state, n_seqs == 0     the single-sequence loop behind its advance: when state[2] (produced) is above written[0], the token
+//                          emitted[produced - 1] and out[produced - 1], and written[0] = produced
+//   state, n_seqs == B     the batched loop: the same per sequence over state[3 B + b], row length state[4 B], written[b]
+// A frozen sequence (stop token, count used up) produces nothing, so its later steps — whose logits are those of the position
+// BEHIND its last token — write nothing.
+struct LogprobTarget {
+    float* out = nullptr;
+    const uint32_t* tokens = nullptr;
+    const int64_t* token64 = nullptr;
+    const uint32_t* picks = nullptr;
+    const uint32_t* state = nullptr;
+    const int64_t* emitted = nullptr;
+    uint32_t* written = nullptr;
+    uint32_t cap = 0, n_seqs = 0;
+};
+void launch_logprob_finish(hipStream_t s, const float* v, uint64_t n, uint32_t rows, const float* part, const LogprobTarget& t);
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes);
 void launch_f32_to_f16(hipStream_t s, void* dst, const float* src, uint64_t n);
 

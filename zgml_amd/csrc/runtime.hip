@@ -639,6 +639,9 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipFree(ctx->smp_params);
     hipFree(ctx->smp_out);
     hipFree(ctx->smp_win);
+    hipFree(ctx->lp_part);
+    hipFree(ctx->lp_tok);
+    hipFree(ctx->lp_out);
     if (ctx->handoff_flag) hipHostFree(ctx->handoff_flag);
     hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -125,6 +125,13 @@ struct zgml_hip_ctx {
     SampleParamsDev* smp_params = nullptr;
     uint32_t* smp_out = nullptr; // [0, 1]: the token (64 bits); [2]: count; [3, 259): indices
     uint32_t* smp_win = nullptr; // the window of a penalised zgml_hip_sample, [256] (allocated by the first such call)
+    // zgml_hip_logprobs, and zgml_hip_sample with the `logprobs` field: the block pairs [lp_rows][256][2], the tokens and the values
+    // of lp_rows rows (grown by the call that needs more)
+    float* lp_part = nullptr;
+    uint32_t* lp_tok = nullptr;
+    float* lp_out = nullptr;
+    uint32_t lp_rows = 0;
+    std::vector<float> lp_last; // what zgml_hip_logprobs_result hands out: the values of the last call with the `logprobs` word set
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
     // Fused launches (q/k/v projection + decode attention): ONE host-visible word every bounded in-launch wait sets when it
     // gives up (pinned, device-mapped: the host reads it after any synchronisation without a copy). A set word means the

@@ -55,6 +55,15 @@ struct zgml_resident {
     uint32_t* swin = nullptr;
     hipGraph_t graph_penalized = nullptr;
     hipGraphExec_t graph_penalized_exec = nullptr;
+    // log-probabilities of the sampled tail (the `logprobs` field of zgml_sampling; logprob.hip), allocated by the first such call:
+    // the block pairs of every logits row, the values next to the produced tokens ([lp_cap]: the layout of tokens / btokens), the
+    // T row values of a verify step, the "written up to" word of every sequence; the loops' own graphs, plain and penalised,
+    // beside the other four
+    float *lpart = nullptr, *lp = nullptr, *lp_rows = nullptr;
+    uint32_t* lp_written = nullptr;
+    uint64_t lp_cap = 0;
+    hipGraph_t graph_sampled_lp = nullptr, graph_penalized_lp = nullptr;
+    hipGraphExec_t graph_sampled_lp_exec = nullptr, graph_penalized_lp_exec = nullptr;
 };
 using Resident = zgml_resident;
 
@@ -75,6 +84,12 @@ void free_resident_graph(zgml_hip_program* p) {
     if (r->graph_penalized_exec) hipGraphExecDestroy(r->graph_penalized_exec);
     if (r->graph_penalized) hipGraphDestroy(r->graph_penalized);
     r->graph_penalized_exec = nullptr, r->graph_penalized = nullptr;
+    if (r->graph_sampled_lp_exec) hipGraphExecDestroy(r->graph_sampled_lp_exec);
+    if (r->graph_sampled_lp) hipGraphDestroy(r->graph_sampled_lp);
+    r->graph_sampled_lp_exec = nullptr, r->graph_sampled_lp = nullptr;
+    if (r->graph_penalized_lp_exec) hipGraphExecDestroy(r->graph_penalized_lp_exec);
+    if (r->graph_penalized_lp) hipGraphDestroy(r->graph_penalized_lp);
+    r->graph_penalized_lp_exec = nullptr, r->graph_penalized_lp = nullptr;
 }
 
 void free_resident(zgml_hip_program* p) {
@@ -103,6 +118,10 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->sparams);
     hipFree(r->skeys);
     hipFree(r->swin);
+    hipFree(r->lpart);
+    hipFree(r->lp);
+    hipFree(r->lp_rows);
+    hipFree(r->lp_written);
     delete r;
     p->resident = nullptr;
 }
@@ -155,8 +174,9 @@ void resident_end(zgml_hip_program* p, uint64_t steps, uint64_t launches_per_ste
 enum class RecentOf { Sample, Loop, Spec };
 
 // a caller's zgml_sampling as the kernels read it; false (with the error on the context) for what the header refuses.
-// vocab == 0: the stop tokens are not looked at (zgml_hip_sample). start_pos: of the sequence, for the loops' n_recent rule
-bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampling* sp, uint32_t vocab, SampleParamsDev* out,
+// vocab == 0: the stop tokens are not looked at (zgml_hip_sample). start_pos: of the sequence, for the loops' n_recent rule.
+// row_len: the logits of a row, for the `logprobs` field's limit
+bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampling* sp, uint32_t vocab, uint64_t row_len, SampleParamsDev* out,
                      RecentOf form = RecentOf::Sample, uint32_t start_pos = 0) {
     if (!sp) {
         ctx->fail(who + ": no sampling parameters");
@@ -179,6 +199,10 @@ bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampl
     float repeat = 1.0f;
     uint32_t active = 0;
     if (const char* why = sample_penalty_check(sp, form == RecentOf::Loop ? 1 : form == RecentOf::Spec ? 2 : 0, vocab, start_pos, &repeat, &active)) {
+        ctx->fail(who + ": " + why);
+        return false;
+    }
+    if (const char* why = sample_logprobs_check(sp, row_len)) {
         ctx->fail(who + ": " + why);
         return false;
     }
@@ -209,6 +233,44 @@ bool ensure_sample_blocks(zgml_hip_ctx* ctx, Resident* r, uint32_t rows) {
     if (r->sparams) return true;
     return CTX_CHECK(ctx, hipMalloc((void**)&r->sparams, (size_t)rows * sizeof(SampleParamsDev))) &&
            CTX_CHECK(ctx, hipMalloc((void**)&r->skeys, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t)));
+}
+
+// the log-probability blocks of the sampled loops: `rows` logits rows, values for `cap` produced tokens (the capacity of the
+// token table they lie next to). A graph bakes the pointers: growing the values drops the graphs, as growing the tokens does
+bool ensure_logprob_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, uint64_t cap) {
+    Resident* r = p->resident;
+    if (!r->lpart && (!CTX_CHECK(ctx, hipMalloc((void**)&r->lpart, (size_t)rows * logprob_blocks(r->vocab) * 2 * sizeof(float))) ||
+                      !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_rows, (size_t)rows * sizeof(float))) ||
+                      !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_written, (size_t)rows * 4))))
+        return false;
+    if (r->lp_cap < cap) {
+        hipStreamSynchronize(ctx->stream);
+        hipFree(r->lp);
+        r->lp = nullptr, r->lp_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->lp, (size_t)cap * sizeof(float)))) return false;
+        r->lp_cap = cap;
+        free_resident_graph(p);
+    }
+    return true;
+}
+
+// the context's blocks of zgml_hip_logprobs (and of zgml_hip_sample with the field) for `rows` rows
+bool ensure_ctx_logprob(zgml_hip_ctx* ctx, uint32_t rows) {
+    if (ctx->lp_rows >= rows) return true;
+    hipStreamSynchronize(ctx->stream);
+    hipFree(ctx->lp_part), hipFree(ctx->lp_tok), hipFree(ctx->lp_out);
+    ctx->lp_part = nullptr, ctx->lp_tok = nullptr, ctx->lp_out = nullptr, ctx->lp_rows = 0;
+    if (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->lp_part, (size_t)rows * kLogprobMaxBlocks * 2 * sizeof(float))) ||
+        !CTX_CHECK(ctx, hipMalloc((void**)&ctx->lp_tok, (size_t)rows * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&ctx->lp_out, (size_t)rows * sizeof(float))))
+        return false;
+    ctx->lp_rows = rows;
+    return true;
+}
+
+// entries of tokens that were not produced
+void logprob_fill_unproduced(float* out, uint64_t from, uint64_t to) {
+    const float nan = sample_bits_f32(kLogprobNaNBits);
+    for (uint64_t i = from; i < to; i++) out[i] = nan;
 }
 
 } // namespace
@@ -465,7 +527,7 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
         return -1;
     }
     SampleParamsDev sp;
-    if (!sampling_params(ctx, "sample", sampling, 0, &sp)) return -1;
+    if (!sampling_params(ctx, "sample", sampling, 0, n, &sp)) return -1;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     constexpr size_t out_words = 3 + kSampleMaxK;
@@ -473,6 +535,7 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
                            !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_params, sizeof(SampleParamsDev))) ||
                            !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_out, out_words * 4))))
         return -1;
+    if (sampling->logprobs && !ensure_ctx_logprob(ctx, 1)) return -1;
     if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
     SampleAdvance adv;
     adv.position = position, adv.out = (int64_t*)ctx->smp_out, adv.cand = ctx->smp_out + 2;
@@ -486,15 +549,63 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     } else {
         launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
     }
+    float lp = 0.0f;
+    if (sampling->logprobs) { // over the raw row, behind the pick: the token is read where the merge launch stored it
+        LogprobTarget lt;
+        lt.out = ctx->lp_out, lt.token64 = (const int64_t*)ctx->smp_out;
+        launch_logprob(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part);
+        launch_logprob_finish(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, lt);
+        hipMemcpyAsync(&lp, ctx->lp_out, sizeof(lp), hipMemcpyDeviceToHost, s);
+    }
     uint32_t got[out_words];
     hipMemcpyAsync(got, ctx->smp_out, sizeof(got), hipMemcpyDeviceToHost, s);
     if (!CTX_CHECK(ctx, hipStreamSynchronize(s)) || !ctx->handoff_ok("sample")) return -1;
+    if (sampling->logprobs) ctx->lp_last.assign(1, lp);
     const uint32_t kc = std::min<uint32_t>(got[2], kSampleMaxK);
     if (n_candidates_out) *n_candidates_out = kc;
     if (candidates_out) memcpy(candidates_out, got + 3, (size_t)kc * 4);
     int64_t token;
     memcpy(&token, got, 8);
     return token;
+}
+
+// log softmax(row i)[tokens[i]] of `rows` consecutive rows: [partial] [finish], whatever the number of rows
+int zgml_hip_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx, uint64_t offset, uint64_t n, uint32_t rows, const uint32_t* tokens,
+                      float* logprobs_out) {
+    if (!ctx || !p) return -1;
+    const uint64_t buf_size = buf_idx < p->bufs.size() && p->bufs[buf_idx] ? p->sizes[buf_idx] : 0;
+    if (const char* why = logprobs_check(buf_size, offset, n, rows, tokens, logprobs_out)) {
+        ctx->fail(std::string("logprobs: ") + why);
+        return -1;
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    constexpr uint32_t kMaxGridRows = 4096; // rows per pair of launches: the block pairs of that many rows are 8 MiB (a grid's y extent is 65535)
+    if (!ensure_ctx_logprob(ctx, std::min(rows, kMaxGridRows))) return -1;
+    for (uint32_t r0 = 0; r0 < rows; r0 += kMaxGridRows) {
+        const uint32_t nr = std::min(rows - r0, kMaxGridRows);
+        const float* v = p->bufs[buf_idx] + offset + (uint64_t)r0 * n;
+        if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->lp_tok, tokens + r0, (size_t)nr * 4, hipMemcpyHostToDevice, s))) return -1;
+        LogprobTarget lt;
+        lt.out = ctx->lp_out, lt.tokens = ctx->lp_tok;
+        launch_logprob(s, v, n, nr, ctx->lp_part);
+        launch_logprob_finish(s, v, n, nr, ctx->lp_part, lt);
+        hipMemcpyAsync(logprobs_out + r0, ctx->lp_out, (size_t)nr * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (!CTX_CHECK(ctx, hipStreamSynchronize(s))) return -1; // (the caller's arrays are pageable memory: nothing of them in flight on return)
+    }
+    return ctx->handoff_ok("logprobs") ? 0 : -1;
+}
+
+// the values the context's last call with the `logprobs` word set left behind, in the layout of that call's tokens_out
+int64_t zgml_hip_logprobs_result(zgml_hip_ctx* ctx, float* out, uint64_t n) {
+    if (!ctx) return -1;
+    if (!out && n) {
+        ctx->fail("logprobs_result: out must not be NULL");
+        return -1;
+    }
+    const uint64_t have = ctx->lp_last.size();
+    if (const uint64_t take = std::min(n, have)) memcpy(out, ctx->lp_last.data(), take * sizeof(float));
+    return (int64_t)have;
 }
 
 // zgml_hip_resident_decode with [select] [merge + pick + advance] in the place of the two argmax stages
@@ -512,7 +623,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         return -1;
     }
     SampleParamsDev sp;
-    if (!sampling_params(ctx, "resident_decode_sampled", sampling, r->vocab, &sp, RecentOf::Loop, start_pos)) return -1;
+    if (!sampling_params(ctx, "resident_decode_sampled", sampling, r->vocab, r->vocab, &sp, RecentOf::Loop, start_pos)) return -1;
     if (first_token >= r->vocab || (uint64_t)start_pos + n_steps > r->max_seq) {
         ctx->fail("resident_decode_sampled: token or position out of range");
         return -1;
@@ -523,7 +634,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     resident_begin(p, [&] {
         return positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; });
     });
-    const bool penalized = sp.pen_active != 0;
+    const bool penalized = sp.pen_active != 0, lp = sampling->logprobs != 0;
     if (!ensure_sample_blocks(ctx, r, 1) || (penalized && !ensure_window_block(ctx, r, 1))) return -1;
     if (r->tokens_cap < n_steps) {
         hipStreamSynchronize(s);
@@ -533,6 +644,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         r->tokens_cap = n_steps;
         free_resident_graph(p); // the graphs baked the old pointer/cap
     }
+    if (lp && !ensure_logprob_blocks(ctx, p, 1, r->tokens_cap)) return -1;
     const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
                              p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
     const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
@@ -540,13 +652,17 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     adv.state = r->state, adv.tokens = r->tokens, adv.cap = r->tokens_cap;
     SampleWindow win;
     win.ring = r->swin, win.lo = r->swin + kSamplePenaltyMaxWindow;
+    LogprobTarget lt; // (calls with the `logprobs` field only)
+    lt.out = r->lp, lt.state = r->state, lt.emitted = r->tokens, lt.written = r->lp_written, lt.cap = r->tokens_cap;
     auto one_token = [&](hipStream_t st) {
         launch_resident_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
+        if (lp) launch_logprob(st, r->logits, r->vocab, 1, r->lpart); // (the raw row: it depends on the plan alone)
         if (penalized)
             launch_sample_penalized(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win);
         else
             launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
+        if (lp) launch_logprob_finish(st, r->logits, r->vocab, 1, r->lpart, lt); // (behind the advance: it knows whether a token was emitted)
     };
     std::vector<uint32_t> win0; // (penalised calls only; alive until the call's last synchronisation)
     if (penalized) {
@@ -557,13 +673,17 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // ([3]: set by a stop token)
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, &sp, sizeof(sp), hipMemcpyHostToDevice, s)) ||
-        !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_steps * 8, s))) // (-1: what a stopped sequence leaves behind its stop token)
+        !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_steps * 8, s)) || // (-1: what a stopped sequence leaves behind its stop token)
+        (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, 4, s))))
         return -1;
-    // (a penalised call replays a graph of its own: the two kinds of call alternate on one program and invalidate nothing)
-    hipGraphExec_t& exec = penalized ? r->graph_penalized_exec : r->graph_sampled_exec;
+    // (a penalised call replays a graph of its own, and so does a call with log-probabilities: the four kinds of call alternate on
+    // one program and invalidate nothing)
+    hipGraphExec_t& exec = lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
+    hipGraph_t& graph = lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : (penalized ? r->graph_penalized : r->graph_sampled);
     if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (the copies above read this stack frame: none in flight when the capture begins)
-        capture_graph(ctx, s, penalized ? "resident_penalized" : "resident_sampled", [&] { one_token(s); }, penalized ? &r->graph_penalized : &r->graph_sampled, &exec); // (failed: eager below)
+        const char* const names[4] = {"resident_sampled", "resident_penalized", "resident_sampled_logprobs", "resident_penalized_logprobs"};
+        capture_graph(ctx, s, names[2 * lp + penalized], [&] { one_token(s); }, &graph, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < n_steps; i++) {
         if (exec)
@@ -574,10 +694,15 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     uint32_t st1[4] = {0, 0, 0, 0};
     hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(st1, r->state, sizeof(st1), hipMemcpyDeviceToHost, s);
+    if (lp) {
+        ctx->lp_last.assign(n_steps, 0.0f);
+        hipMemcpyAsync(ctx->lp_last.data(), r->lp, (size_t)n_steps * sizeof(float), hipMemcpyDeviceToHost, s);
+    }
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode_sampled");
     if (ok && n_produced) *n_produced = std::min(st1[2], n_steps);
-    resident_end(p, n_steps, p->plan.size() + 3); // per token [prep] [plan] [select] [merge + pick + advance]
+    if (lp) logprob_fill_unproduced(ctx->lp_last.data(), ok ? std::min(st1[2], n_steps) : 0, n_steps);
+    resident_end(p, n_steps, p->plan.size() + (lp ? 5 : 3)); // per token [prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish])
     return ok ? 0 : -1;
 }
 
@@ -595,7 +720,7 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     const uint32_t B = r->n_seqs;
     std::vector<SampleParamsDev> sp(B);
     for (uint32_t b = 0; b < B; b++)
-        if (!sampling_params(ctx, "resident_decode_batch_sampled (sequence " + std::to_string(b) + ")", per_seq ? per_seq + b : nullptr, r->vocab, &sp[b], RecentOf::Loop, start_pos[b])) return -1;
+        if (!sampling_params(ctx, "resident_decode_batch_sampled (sequence " + std::to_string(b) + ")", per_seq ? per_seq + b : nullptr, r->vocab, r->vocab, &sp[b], RecentOf::Loop, start_pos[b])) return -1;
     uint32_t steps = 0;
     for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
     if (steps > max_steps) {
@@ -623,7 +748,8 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         return positions_in_bounds(p, 1, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) && positions_in_bounds(p, 1, [&](uint32_t i) { return last_pos[p->op_seq[i]]; });
     });
     bool penalized = false; // one sequence with penalties: the penalised launch for all (a row without them computes what it did)
-    for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active;
+    bool lp = false; // ... and one with log-probabilities: the two launches for all (a row nobody asked for is not copied out)
+    for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active, lp = lp || per_seq[b].logprobs;
     if (!ensure_sample_blocks(ctx, r, B) || (penalized && !ensure_window_block(ctx, r, B))) return -1;
     if (r->btokens_cap < (uint64_t)B * steps) {
         hipStreamSynchronize(s);
@@ -633,9 +759,12 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         r->btokens_cap = (uint64_t)B * steps;
         free_resident_graph(p); // the graphs baked the old pointer
     }
+    if (lp && !ensure_logprob_blocks(ctx, p, B, r->btokens_cap)) return -1;
     const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
                                   p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
     const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
+    LogprobTarget lt; // (calls with the `logprobs` field only) the values lie as the tokens do: [B][steps]
+    lt.out = r->lp, lt.state = r->bstate, lt.emitted = r->btokens, lt.written = r->lp_written, lt.n_seqs = B;
     SampleAdvance adv;
     adv.state = r->bstate, adv.tokens = r->btokens, adv.n_seqs = B;
     SampleWindow win;
@@ -643,10 +772,12 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     auto one_step = [&](hipStream_t st) {
         launch_resident_batch_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
+        if (lp) launch_logprob(st, r->logits, r->vocab, B, r->lpart);
         if (penalized)
             launch_sample_penalized(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win);
         else
             launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
+        if (lp) launch_logprob_finish(st, r->logits, r->vocab, B, r->lpart, lt);
     };
     std::vector<uint32_t> win0;
     if (penalized) {
@@ -659,12 +790,15 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     st0[4 * B] = steps; // row length of the device token table of this call
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, sp.data(), sp.size() * sizeof(SampleParamsDev), hipMemcpyHostToDevice, s)) ||
-        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
+        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s)) || // (-1: what a sequence leaves behind its count)
+        (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, (size_t)B * 4, s))))
         return -1;
-    hipGraphExec_t& exec = penalized ? r->graph_penalized_exec : r->graph_sampled_exec;
+    hipGraphExec_t& exec = lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
+    hipGraph_t& graph = lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : (penalized ? r->graph_penalized : r->graph_sampled);
     if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (as the greedy batched loop: no pageable copy in flight when the capture begins)
-        capture_graph(ctx, s, penalized ? "resident_batch_penalized" : "resident_batch_sampled", [&] { one_step(s); }, penalized ? &r->graph_penalized : &r->graph_sampled, &exec); // (failed: eager below)
+        const char* const names[4] = {"resident_batch_sampled", "resident_batch_penalized", "resident_batch_sampled_logprobs", "resident_batch_penalized_logprobs"};
+        capture_graph(ctx, s, names[2 * lp + penalized], [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < steps; i++) {
         if (exec)
@@ -675,13 +809,23 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     std::vector<int64_t> got((size_t)B * steps);
     hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(st1.data(), r->bstate, st1.size() * 4, hipMemcpyDeviceToHost, s);
+    std::vector<float> got_lp(lp ? (size_t)B * steps : 0);
+    if (lp) hipMemcpyAsync(got_lp.data(), r->lp, got_lp.size() * sizeof(float), hipMemcpyDeviceToHost, s);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode_batch_sampled");
     for (uint32_t b = 0; ok && b < B; b++) {
         for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
         if (n_produced) n_produced[b] = std::min(st1[3 * B + b], n_steps[b]);
     }
-    resident_end(p, steps, p->plan.size() + 3); // per step [batched prep] [plan] [select] [merge + pick + advance]
+    if (lp) ctx->lp_last.assign((size_t)B * max_steps, sample_bits_f32(kLogprobNaNBits)); // [n_seqs][max_steps], as tokens_out
+    for (uint32_t b = 0; b < B; b++) {
+        if (!per_seq[b].logprobs) continue;
+        float* const out = ctx->lp_last.data() + (size_t)b * max_steps;
+        const uint32_t made = ok ? std::min(st1[3 * B + b], n_steps[b]) : 0;
+        for (uint32_t i = 0; i < made; i++) out[i] = got_lp[(uint64_t)b * steps + i];
+        logprob_fill_unproduced(out, made, max_steps);
+    }
+    resident_end(p, steps, p->plan.size() + (lp ? 5 : 3)); // per step [batched prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish])
     return ok ? 0 : -1;
 }
 
@@ -779,8 +923,8 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         return -1;
     }
     SampleParamsDev sp{};
-    if (sampled && !sampling_params(ctx, who, sampling, r->vocab, &sp, RecentOf::Spec)) return -1;
-    const bool penalized = sp.pen_active != 0; // (sampled form only)
+    if (sampled && !sampling_params(ctx, who, sampling, r->vocab, r->vocab, &sp, RecentOf::Spec)) return -1;
+    const bool penalized = sp.pen_active != 0, lp = sampled && sampling->logprobs; // (sampled form only)
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     // the first start and the last possible start of a verify step
@@ -804,6 +948,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         r->tokens_cap = n_tokens;
         free_resident_graph(p); // the graph baked the old pointer/cap
     }
+    if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens_cap)) return -1;
     uint32_t w0[kSpecWords] = {0};
     w0[kSpecTok] = first_token, w0[kSpecPos] = start_pos, w0[kSpecWanted] = n_tokens, w0[kSpecMode] = o.mode, w0[kSpecNgram] = ngram;
     w0[kSpecNDrafts] = std::min(n_drafts, r->max_seq), w0[kSpecStart] = start_pos, w0[kSpecHistLo] = o.n_history ? 0 : start_pos;
@@ -823,6 +968,9 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         sa.picks = r->picks, sa.sparams = r->sparams;
         adv.picks = r->picks, adv.pos_word = r->spec + kSpecRunPos;
     }
+    LogprobTarget lt; // (the `logprobs` field only) every row's value of its pick; the accept launch copies the emitted prefix
+    lt.out = r->lp_rows, lt.picks = r->picks;
+    if (lp) sa.lp_rows = r->lp_rows, sa.lp_out = r->lp;
     SampleWindow win; // (penalised form only) a row's window is the call's history up to the run position and the candidates behind it
     win.hist = r->hist, win.cand = r->tok_dev, win.lo_word = r->spec + kSpecHistLo;
     // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
@@ -836,19 +984,22 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         launch_spec_draft(st, sa);
         launch_resident_prep(st, a, (uint32_t)total);
         run_plan(p, st, 0, p->plan.size());
+        if (lp) launch_logprob(st, r->logits, r->vocab, T, r->lpart);
         if (penalized)
             launch_sample_penalized(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv, win);
         else if (sampled)
             launch_sample(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv);
         else
             launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
+        if (lp) launch_logprob_finish(st, r->logits, r->vocab, T, r->lpart, lt);
         launch_spec_accept(st, sa);
     };
-    hipGraphExec_t& exec = penalized ? r->graph_penalized_exec : sampled ? r->graph_sampled_exec : r->graph_exec;
+    hipGraphExec_t& exec = lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : penalized ? r->graph_penalized_exec : sampled ? r->graph_sampled_exec : r->graph_exec;
+    hipGraph_t& graph = lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : penalized ? r->graph_penalized : sampled ? r->graph_sampled : r->graph;
     if (ctx->opt_graph && !exec) {
         if (sampled) hipStreamSynchronize(s); // (as the sampled loops: no copy from this stack frame in flight when the capture begins)
-        capture_graph(ctx, s, penalized ? "resident_spec_penalized" : sampled ? "resident_spec_sampled" : "resident_spec", [&] { one_step(s); },
-                      penalized ? &r->graph_penalized : sampled ? &r->graph_sampled : &r->graph, &exec); // (failed: eager below)
+        capture_graph(ctx, s, lp ? (penalized ? "resident_spec_penalized_logprobs" : "resident_spec_sampled_logprobs") : penalized ? "resident_spec_penalized" : sampled ? "resident_spec_sampled" : "resident_spec",
+                      [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
     }
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)
@@ -874,13 +1025,21 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     }
     if (ok) {
         hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_tokens * 8, hipMemcpyDeviceToHost, s);
+        if (lp) {
+            ctx->lp_last.assign(n_tokens, 0.0f);
+            hipMemcpyAsync(ctx->lp_last.data(), r->lp, (size_t)n_tokens * sizeof(float), hipMemcpyDeviceToHost, s);
+        }
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     }
     ok = ok && ctx->handoff_ok(who.c_str());
+    if (lp) {
+        ctx->lp_last.resize(n_tokens);
+        logprob_fill_unproduced(ctx->lp_last.data(), ok ? std::min(w1[kSpecProduced], n_tokens) : 0, n_tokens);
+    }
     if (ok && stats) *stats = zgml_spec_stats{w1[kSpecSteps], w1[kSpecDrafted], w1[kSpecAccepted], 0};
     if (ok && n_produced) *n_produced = std::min(w1[kSpecProduced], n_tokens);
     // per step [draft] [prep] [plan] [argmax stage 1] [accept], or [draft] [prep] [plan] [select] [merge + pick] [accept]
-    resident_end(p, steps_run, p->plan.size() + (sampled ? 5 : 4));
+    resident_end(p, steps_run, p->plan.size() + (lp ? 7 : sampled ? 5 : 4)); // (with log-probabilities: [partial] and [finish] as well)
     return ok ? 0 : -1;
 }
 

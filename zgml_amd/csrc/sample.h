@@ -1,7 +1,8 @@
-// sample.h — the rule of seeded top-k / top-p sampling (zgml_hip_sample, zgml_hip_resident_decode_sampled, _batch_sampled;
-// include/zgml_hip.h), written ONCE: the kernels of sample.hip call these functions and so does the host probe
-// tests/cpp/sample_probe.cpp (tests/test_sample_host.py compares it with a float64 numpy model of the same rule). Plain C++, no
-// device intrinsics: the header compiles under g++ as it stands. Both sides must be built with -ffp-contract=off: every
+// sample.h — the rule of seeded top-k / top-p sampling and of the log-probabilities (zgml_hip_sample, zgml_hip_logprobs,
+// zgml_hip_resident_decode_sampled, _batch_sampled; include/zgml_hip.h), written ONCE: the kernels of sample.hip and logprob.hip
+// call these functions and so do the host probes tests/cpp/sample_probe.cpp and logprob_probe.cpp (tests/test_sample_host.py and
+// tests/test_logprob_host.py compare them with float64 numpy models of the same rule). Plain C++, no device intrinsics: the
+// header compiles under g++ as it stands. Both sides must be built with -ffp-contract=off: every
 // operation below is then one correctly rounded IEEE operation or an explicit fmaf, and device and host agree to the bit.
 //
 // THE CANDIDATES. A logit v at vocabulary index i has the 64-bit key (ordered(v + 0.0f) << 32) | (0xFFFFFFFF - i): `ordered` is
@@ -35,6 +36,25 @@
 //   inv_repeat = 1.0f / repeat, computed once on the host as inv_temperature is, where llama.cpp divides by repeat. Host and
 //   device therefore cannot disagree about a division.
 // A NaN or an infinity passes through these operations as IEEE says; sample_ordered then maps a NaN to -inf as ever.
+//
+// THE LOG-PROBABILITY of token t under a row of n logits (zgml_hip_logprobs, the `logprobs` field of zgml_sampling; kernels:
+// logprob.hip): log softmax(row)[t] over the WHOLE row and over the RAW logits — before penalties, before the temperature, whatever
+// top_k / top_p say: the model's own distribution, independent of how the token was picked. A logit reads as logprob_value(v) =
+// v + 0.0f with a NaN as -inf (sample_ordered's convention: -0 is +0). expf, logf and a free-order sum differ between host and
+// device in the last bits, so the functions (sample_exp, sample_log) and the ORDER of every sum are part of the rule:
+//   blocks:  the row is cut into blocks of kLogprobBlock = 4096 consecutive logits, the last one possibly short. m_b = the block's
+//            largest value (exact, order-free). The block has 1024 accumulators: accumulator j sums sample_exp(v_i - m_b) over the
+//            block's elements i (counted from the block's start) with i mod 1024 == j, ascending i, starting from 0.0f; an element
+//            behind the row's end adds nothing (all terms are >= +0, so adding +0 for it changes no bit). The four accumulators
+//            4l .. 4l + 3 of "thread" l are added left to right, and the 256 thread sums are folded by p[l] += p[l + h] for
+//            h = 128, 64, .., 1: s_b = p[0]. (The layout is what lets a workgroup of 256 threads read the block once, thread l its
+//            k-th 16 bytes at element 1024 k + 4 l, and fold in LDS or with wave shuffles over the same pairs.)
+//   finish:  M = max_b m_b;  S = the sum over b ascending, from 0.0f, of s_b * sample_exp(m_b - M);
+//            logprob(t) = (v_t - M) - sample_log(S).
+//   edges:   M = -inf (no logit above -inf): -inf for every token.  M = +inf: the quiet NaN 0x7FC00000 for every token.  v_t = -inf
+//            (or NaN) under a finite M: -inf.  n = 1 with a finite logit: +0.0f (v - v = +0, S = 1, sample_log(1) = +0).
+// n is at most kLogprobMaxBlocks blocks = 2^20 logits. Against v_t - logsumexp(v) in float64 the error is at most
+// 1e-5 + 2.4e-7 |v_t - M| (the bar of tests/test_logprob_host.py, derived there; measured maximum: 4.5e-7 + the second term).
 #pragma once
 
 #include <math.h>
@@ -200,6 +220,94 @@ ZGML_SAMPLE_FN uint32_t sample_window_span(uint32_t position, uint32_t lo, uint3
     const uint32_t m = known < window ? known : window;
     *first = position + 1 - m;
     return m;
+}
+
+// ── the log-probability ──
+
+constexpr uint32_t kLogprobBlock = 4096;    // logits per block
+constexpr uint32_t kLogprobThreads = 256;   // "threads" of a block: four accumulators each, 16 elements each
+constexpr uint32_t kLogprobMaxBlocks = 256; // blocks per row: n <= 2^20
+constexpr uint64_t kLogprobMaxN = (uint64_t)kLogprobBlock * kLogprobMaxBlocks;
+constexpr uint32_t kLogprobNaNBits = 0x7FC00000u; // M = +inf, and what an entry of a token that was not produced holds
+static_assert(kLogprobBlock == 16 * kLogprobThreads, "a thread reads four times four consecutive elements");
+
+ZGML_SAMPLE_FN uint32_t logprob_blocks(uint64_t n) { return (uint32_t)((n + kLogprobBlock - 1) / kLogprobBlock); }
+
+// ln x for x in [2^-1, 2^32) — all the rule needs: S >= 1, a sum of at most 2^20 terms <= 1 —: frexpf, the mantissa moved to
+// [sqrt 1/2, sqrt 2), t = f - 1 (exact), t - t^2 / 2 + t^3 P(t) with the degree-8 P of Cephes' logf as a Horner chain of explicit
+// fmaf, the exponent's e ln 2 in two parts (0.693359375 is exact in 11 bits: e times it is exact). sample_log(1) = +0.
+// Maximum error against log in float64 on [0.5, 2^32): 7.9e-8 relative where |ln x| >= 1, 4.5e-8 absolute below.
+ZGML_SAMPLE_FN float sample_log(float x) {
+    int e;
+    float f = frexpf(x, &e);
+    if (f < 0.707106781186547524f) f = f + f, e -= 1;
+    const float t = f - 1.0f, z = t * t, fe = (float)e;
+    float p = 7.0376836292e-2f;
+    p = fmaf(p, t, -1.1514610310e-1f);
+    p = fmaf(p, t, 1.1676998740e-1f);
+    p = fmaf(p, t, -1.2420140846e-1f);
+    p = fmaf(p, t, 1.4249322787e-1f);
+    p = fmaf(p, t, -1.6668057665e-1f);
+    p = fmaf(p, t, 2.0000714765e-1f);
+    p = fmaf(p, t, -2.4999993993e-1f);
+    p = fmaf(p, t, 3.3333331174e-1f);
+    float y = (t * z) * p;
+    y = fmaf(fe, -2.12194440e-4f, y);
+    y = fmaf(-0.5f, z, y);
+    return fmaf(fe, 0.693359375f, t + y);
+}
+
+// a logit as the rule reads it: -0 is +0, a NaN is -inf
+ZGML_SAMPLE_FN float logprob_value(float v) {
+    v = v + 0.0f;
+    return v != v ? -INFINITY : v;
+}
+
+// one element's term under its block's maximum (m = +-inf: the difference is a NaN or -inf, the term 0)
+ZGML_SAMPLE_FN float logprob_term(float v, float m) { return sample_exp(logprob_value(v) - m); }
+
+// a thread's sum of its four accumulators
+ZGML_SAMPLE_FN float logprob_thread_sum(const float acc[4]) { return ((acc[0] + acc[1]) + acc[2]) + acc[3]; }
+
+// (m_b, s_b) of the block v[0, len), len <= kLogprobBlock, walked alone (the probe; the kernel gives every "thread" a thread)
+ZGML_SAMPLE_FN void logprob_block(const float* v, uint32_t len, float* m_out, float* s_out) {
+    float m = -INFINITY;
+    for (uint32_t i = 0; i < len; i++) {
+        const float x = logprob_value(v[i]);
+        if (x > m) m = x;
+    }
+    float p[kLogprobThreads];
+    for (uint32_t l = 0; l < kLogprobThreads; l++) {
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (uint32_t k = 0; k < 4; k++)
+            for (uint32_t c = 0; c < 4; c++) {
+                const uint32_t i = k * (4 * kLogprobThreads) + 4 * l + c;
+                if (i < len) acc[c] = acc[c] + logprob_term(v[i], m);
+            }
+        p[l] = logprob_thread_sum(acc);
+    }
+    for (uint32_t h = kLogprobThreads / 2; h > 0; h >>= 1)
+        for (uint32_t l = 0; l < h; l++) p[l] = p[l] + p[l + h];
+    *m_out = m, *s_out = p[0];
+}
+
+// block b's share of S under the row's maximum M
+ZGML_SAMPLE_FN float logprob_block_term(float m_b, float s_b, float M) { return s_b * sample_exp(m_b - M); }
+
+// the value from the row's M and S and the token's logit
+ZGML_SAMPLE_FN float logprob_of(float v_t, float M, float S) {
+    if (M == -INFINITY) return -INFINITY;
+    if (M == INFINITY) return sample_bits_f32(kLogprobNaNBits);
+    return (logprob_value(v_t) - M) - sample_log(S);
+}
+
+// the finish over the nb block pairs: M and S
+ZGML_SAMPLE_FN void logprob_finish(const float* m, const float* s, uint32_t nb, float* M_out, float* S_out) {
+    float M = -INFINITY, S = 0.0f;
+    for (uint32_t b = 0; b < nb; b++)
+        if (m[b] > M) M = m[b];
+    for (uint32_t b = 0; b < nb; b++) S = S + logprob_block_term(m[b], s[b], M);
+    *M_out = M, *S_out = S;
 }
 
 } // namespace zgml

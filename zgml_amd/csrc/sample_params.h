@@ -1,5 +1,6 @@
-// sample_params.h — what include/zgml_hip.h refuses of the penalty fields of a zgml_sampling, as pure host logic: the runtime
-// (runtime_resident.hip: sampling_params) and the CPU probe tests/cpp/penalty_probe.cpp compile this one function.
+// sample_params.h — what include/zgml_hip.h refuses of the penalty fields and of the `logprobs` field of a zgml_sampling, and of the
+// arguments of zgml_hip_logprobs, as pure host logic: the runtime (runtime_resident.hip) and the CPU probes
+// tests/cpp/penalty_probe.cpp and tests/cpp/logprob_probe.cpp compile these functions.
 #pragma once
 
 #include <math.h>
@@ -28,6 +29,23 @@ inline const char* sample_penalty_check(const zgml_sampling* sp, int form, uint3
     }
     *repeat = rp == 0.0f ? 1.0f : rp;
     *active = !neutral && sp->penalty_window > 0;
+    return nullptr;
+}
+
+// What zgml_hip_logprobs refuses: nullptr, or why. buf_size: the elements of the buffer, 0 for one that does not exist.
+inline const char* logprobs_check(uint64_t buf_size, uint64_t offset, uint64_t n, uint32_t rows, const uint32_t* tokens, const float* out) {
+    if (!tokens || !out) return "tokens and logprobs_out must not be NULL";
+    if (!n || n > kLogprobMaxN) return "a row must hold 1 .. 2^20 elements";
+    if (!rows) return "rows must be at least 1";
+    if (!buf_size || offset > buf_size || n * (uint64_t)rows > buf_size - offset) return "the rows must lie inside the buffer";
+    for (uint32_t i = 0; i < rows; i++)
+        if (tokens[i] >= n) return "token out of range";
+    return nullptr;
+}
+
+// ... and what the `logprobs` word of a zgml_sampling asks of the row length of the entry point it is handed to
+inline const char* sample_logprobs_check(const zgml_sampling* sp, uint64_t n) {
+    if (sp->logprobs && n > kLogprobMaxN) return "logprobs needs a row of at most 2^20 elements";
     return nullptr;
 }
 

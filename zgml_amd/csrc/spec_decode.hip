@@ -77,7 +77,8 @@ __device__ __forceinline__ void spec_arg_fold(float& bv, int64_t& bi, float v, i
 // g[j] from the nblk stage-1 partials of logits row j (a wave per row, rows kSpecWaves apart) — or, the sampled form, read from
 // a.picks —, then thread 0: how many candidates were the row's choice, what is emitted, and the advance of the state, the history
 // and the counters. The sampled form cuts the emission behind the first stop token and then sets wanted = produced: every later
-// step of the round idles, and the host's round loop ends on the words it reads back.
+// step of the round idles, and the host's round loop ends on the words it reads back. With a.lp_out the log-probabilities of the
+// emitted tokens go next to them: row k's value of g[k], computed for all T rows behind the pick (logprob.hip).
 __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     extern __shared__ uint32_t g[]; // [T]
     uint32_t* const w = a.words;
@@ -108,6 +109,7 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     if (a.sparams) m = spec_stop_cut(g, m, a.sparams->n_stop, a.sparams->stop, &stopped); // (read in place, as the merge kernel does)
     for (uint32_t k = 0; k < m; k++) {
         if (produced + k < a.tokens_cap) a.tokens[produced + k] = (int64_t)g[k];
+        if (a.lp_out && produced + k < a.tokens_cap) a.lp_out[produced + k] = a.lp_rows[k];
         if (pos + 1 + k < a.hist_cap) a.hist[pos + 1 + k] = g[k];
     }
     w[kSpecTok] = g[m - 1];

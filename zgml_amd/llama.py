@@ -268,9 +268,11 @@ class BatchSession:
             raise RuntimeError("resident_decode_batch: " + self._backend.last_error())
         return toks[:, :max_steps]
 
-    def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings):
+    def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None):
         """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
-        -> (tokens[B, max(n_steps)], n_produced[B]); row b holds n_produced[b] tokens, then -1."""
+        -> (tokens[B, max(n_steps)], n_produced[B]); row b holds n_produced[b] tokens, then -1. logprobs: True, or one flag per
+        sequence: -> (tokens, n_produced, float32[B, max(n_steps)]), row b the log-probabilities of sequence b's tokens — NaN
+        behind them, and all through a row whose flag is off."""
         u32p = C.POINTER(C.c_uint32)
         t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
         n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_steps, dtype=np.uint32), (self.n_seqs,)))
@@ -279,11 +281,18 @@ class BatchSession:
         max_steps = int(n.max()) if n.size else 0
         toks = np.full((self.n_seqs, max(1, max_steps)), -1, np.int64)
         produced = np.zeros(self.n_seqs, np.uint32)
+        flags = [bool(logprobs)] * self.n_seqs if logprobs is None or isinstance(logprobs, bool) else [bool(x) for x in logprobs]
+        for b in range(self.n_seqs):
+            if flags[b]:
+                sp[b].logprobs = 1
         rc = capi.load_hip().zgml_hip_resident_decode_batch_sampled(self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p),
                                                                     n.ctypes.data_as(u32p), max_steps, sp, toks.ctypes.data, produced.ctypes.data_as(u32p))
         if rc != 0:
             raise RuntimeError("resident_decode_batch_sampled: " + self._backend.last_error())
-        return toks[:, :max_steps], produced
+        if logprobs is None:
+            return toks[:, :max_steps], produced
+        lps = capi.logprobs_result(self._backend.ctx, (self.n_seqs, max_steps)) if any(flags) and max_steps else np.full((self.n_seqs, max_steps), np.nan, np.float32)
+        return toks[:, :max_steps], produced, lps
 
     def close(self):
         if self.ptr:
@@ -359,15 +368,20 @@ class Session:
             raise RuntimeError("resident_decode: " + self._backend.last_error())
         return toks
 
-    def resident_decode_sampled(self, first_token: int, start_pos: int, n_steps: int, sampling: "capi.SamplingC"):
-        """zgml_hip_resident_decode_sampled -> (tokens[n_steps], n_produced): -1 behind a stop token."""
+    def resident_decode_sampled(self, first_token: int, start_pos: int, n_steps: int, sampling: "capi.SamplingC", logprobs: bool = False):
+        """zgml_hip_resident_decode_sampled -> (tokens[n_steps], n_produced): -1 behind a stop token. logprobs=True:
+        -> (tokens, n_produced, float32[n_steps]): every token's log-probability, NaN behind a stop token."""
         toks = np.full(max(1, n_steps), -1, np.int64)
         produced = C.c_uint32(0)
+        if logprobs:
+            sampling = capi.with_logprobs(sampling)
         rc = capi.load_hip().zgml_hip_resident_decode_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_steps, C.byref(sampling),
                                                               toks.ctypes.data, C.byref(produced))
         if rc != 0:
             raise RuntimeError("resident_decode_sampled: " + self._backend.last_error())
-        return toks[:n_steps], int(produced.value)
+        if not logprobs:
+            return toks[:n_steps], int(produced.value)
+        return toks[:n_steps], int(produced.value), (capi.logprobs_result(self._backend.ctx, n_steps) if n_steps else np.zeros(0, np.float32))
 
     def resident_prefill(self, tokens, start_pos: int) -> int:
         """One chunk of a token_len = N plan with on-device embedding gather / mask / RoPE rows / argmax."""
@@ -406,19 +420,25 @@ class Session:
         return toks, {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
 
     def resident_decode_speculative_sampled(self, first_token: int, start_pos: int, n_tokens: int, sampling: "capi.SamplingC", history=None,
-                                            drafts=None, ngram: int = 2):
+                                            drafts=None, ngram: int = 2, logprobs: bool = False):
         """zgml_hip_resident_decode_speculative_sampled: the verify step's rows are sampled (seeded top-k / top-p) instead of
         arg-maxed -> (tokens[n_tokens], n_produced, {"steps", "drafted", "accepted"}): -1 behind a stop token. `history`, `drafts`
-        and `ngram` as resident_decode_speculative."""
+        and `ngram` as resident_decode_speculative. logprobs=True: float32[n_tokens] is appended to the result: every emitted
+        token's log-probability, NaN behind a stop token."""
         opt, keep = self._spec_opt(history, drafts, ngram)
         toks = np.full(max(1, n_tokens), -1, np.int64)
+        if logprobs:
+            sampling = capi.with_logprobs(sampling)
         stats, produced = capi.SpecStatsC(), C.c_uint32(0)
         rc = capi.load_hip().zgml_hip_resident_decode_speculative_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
                                                                            C.byref(sampling), toks.ctypes.data, C.byref(produced), C.byref(stats))
         del keep
         if rc != 0:
             raise RuntimeError("resident_decode_speculative_sampled: " + self._backend.last_error())
-        return toks[:n_tokens], int(produced.value), {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
+        st = {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
+        if not logprobs:
+            return toks[:n_tokens], int(produced.value), st
+        return toks[:n_tokens], int(produced.value), st, (capi.logprobs_result(self._backend.ctx, n_tokens) if n_tokens else np.zeros(0, np.float32))
 
     def close(self):
         if self.ptr:

@@ -516,13 +516,27 @@ class Backend:
     def argmax(self, handle, buf_idx: int, offset: int, n: int) -> int:
         return int(self._lib.zgml_hip_argmax(self.ctx, handle, buf_idx, offset, n))
 
-    def sample(self, handle, buf_idx: int, offset: int, n: int, sampling: "capi.SamplingC", position: int):
-        """zgml_hip_sample: -> (token, candidate indices in order). RuntimeError for what the library refuses."""
+    def sample(self, handle, buf_idx: int, offset: int, n: int, sampling: "capi.SamplingC", position: int, logprobs: bool = False):
+        """zgml_hip_sample: -> (token, candidate indices in order), with logprobs=True -> (token, candidates, the token's
+        log-probability as numpy.float32). RuntimeError for what the library refuses."""
         cand, kc = (C.c_uint32 * 256)(), C.c_uint32(0)
+        if logprobs:
+            sampling = capi.with_logprobs(sampling)
         tok = int(self._lib.zgml_hip_sample(self.ctx, handle, buf_idx, offset, n, C.byref(sampling), position, cand, C.byref(kc)))
         if tok < 0:
             raise RuntimeError("sample: " + self.last_error())
-        return tok, list(cand[:kc.value])
+        return (tok, list(cand[:kc.value]), capi.logprobs_result(self.ctx, 1)[0]) if logprobs else (tok, list(cand[:kc.value]))
+
+    def logprobs(self, handle, buf_idx: int, offset: int, n: int, tokens) -> np.ndarray:
+        """zgml_hip_logprobs: float32[rows], entry i = log softmax(row i)[tokens[i]] over the rows of n elements that start at
+        `offset` of the buffer, rows = len(tokens). RuntimeError for what the library refuses."""
+        t = np.ascontiguousarray(tokens, dtype=np.uint32)
+        out = np.zeros(max(1, t.size), np.float32)
+        rc = self._lib.zgml_hip_logprobs(self.ctx, handle, buf_idx, offset, n, t.size, t.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         out.ctypes.data_as(C.POINTER(C.c_float)))
+        if rc != 0:
+            raise RuntimeError("logprobs: " + self.last_error())
+        return out[:t.size]
 
     def synchronize(self) -> None:
         self._lib.zgml_hip_synchronize(self.ctx)
