@@ -658,6 +658,7 @@ typedef struct zgml_sampling {
     uint32_t penalty_window; /* W: 0..256 */
     const uint32_t* recent;  /* the tokens before the call (per entry point, below) */
     uint32_t n_recent;
+    uint32_t top_logprobs;   /* 0: off; else, with logprobs != 0, also keep that many alternatives per token (below). The word was padding before */
 } zgml_sampling;
 /* Repetition, presence and frequency penalties (rule: zgml_amd/csrc/sample.h). The pick at position P — over the logits produced
  *   by feeding the token at P — sees the tokens at positions max(lo, P + 1 - W) .. P, lo the first position whose token the call
@@ -708,6 +709,30 @@ typedef struct zgml_sampling {
  *   alternate on one program and invalidate nothing. Refused with the word set: a row of more than 2^20 logits.
  *   Values: a row without an entry above -inf gives -inf; a row holding +inf gives the NaN above; a token whose logit is -inf
  *   (or NaN, which counts as -inf) gives -inf. */
+/* The alternatives of every sampled token: the word `top_logprobs` (rule: zgml_amd/csrc/sample.h, "THE ALTERNATIVES"). It is read
+ *   ONLY when logprobs != 0. 0: exactly the launches and graphs of a call with `logprobs` alone. a > 0: the call also keeps, for
+ *   every token it emits, the a_eff = min(a, 64, vocab) tokens with the largest logits of the row the token was picked from, in
+ *   the candidate order (value descending, the lower index first among equals), each with its log-probability under the rule
+ *   above: over the RAW row — before the penalties, before the temperature, whatever top_k / top_p are. Entry 0 is the row's first
+ *   maximum; a value equals what zgml_hip_logprobs returns for that token over the same row, to the bit. With penalties on, the
+ *   pick's own candidates are the penalised ones, so they are NOT these.
+ *   The word takes the four bytes of padding behind `n_recent`: no field moves, the structure keeps its size. A value above 64
+ *   is read as 64 and not refused: a caller built against the earlier header that set `logprobs` on a structure it never zeroed
+ *   must not start to see refusals; at worst it pays for alternatives it never fetches.
+ *   Cost: without active penalties none in launches — the finish launch runs in its top form, which merges the heads of the lists
+ *   the select launch left in its scratch —; with active penalties one launch more per step, a select over the raw rows (in a
+ *   batched call as soon as one sequence has penalties active). The count lives in the device parameter table: one captured
+ *   graph per form serves every a >= 1, and calls with and without the word alternate on one program and invalidate nothing.
+ *   The values are fetched with zgml_hip_top_logprobs_result (below). */
+/* The alternatives that the context's last call with logprobs != 0 and top_logprobs != 0 left behind, as
+ *   [entries of that call's tokens_out][width]: width is the largest effective count among the call's sequences (each sequence of
+ *   _batch_sampled has its own; one with a smaller count, or none, is padded), entry (i, j) alternative j of tokens_out[i] — in
+ *   _speculative_sampled of the row of the verify step that emitted it. Padding, and every entry of a token that was not produced
+ *   (behind a stop token, a count, the cut of a speculative step), is token -1 and the quiet NaN 0x7FC00000.
+ *   Copies min(n, entries x width) pairs and returns entries x width (0 before any such call); *width_out (may be NULL) receives
+ *   width. A later call without the word leaves the values as they are. -1 with an error on the context: an output pointer NULL
+ *   with n > 0. */
+int64_t zgml_hip_top_logprobs_result(zgml_hip_ctx* ctx, int64_t* tokens_out, float* logprobs_out, uint64_t n, uint32_t* width_out);
 /* The values that the context's last call with the `logprobs` word set left behind, in the layout above: copies min(n, their
  * number) floats to out and returns their number (0 before any such call); a call without the word leaves them as they are.
  * -1 with an error on the context: out NULL with n > 0. */
@@ -716,7 +741,8 @@ int64_t zgml_hip_logprobs_result(zgml_hip_ctx* ctx, float* out, uint64_t n);
  * `position` is the Philox counter's word 0; stop tokens are not looked at. For vtable-path callers, and for the first token
  * after zgml_hip_resident_prefill, whose logits rows stay in the buffer. candidates_out (NULL or 256 words) receives the
  * candidates' indices in order, *n_candidates_out (may be NULL) their number. Returns the token, -1 with an error on the context
- * for parameters out of range (below) or a range outside the buffer. sampling->logprobs (above): one float, the returned token's, for zgml_hip_logprobs_result. */
+ * for parameters out of range (below) or a range outside the buffer. sampling->logprobs (above): one float, the returned token's, for
+ * zgml_hip_logprobs_result; with sampling->top_logprobs one row of alternatives for zgml_hip_top_logprobs_result. */
 int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n,
                         const zgml_sampling* sampling, uint32_t position, uint32_t* candidates_out /* NULL or [256] */,
                         uint32_t* n_candidates_out);
@@ -728,6 +754,13 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t bu
  * rows = 0, a token >= n, a range outside the buffer, tokens or logprobs_out NULL. */
 int zgml_hip_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n, uint32_t rows,
                       const uint32_t* tokens /* [rows] */, float* logprobs_out /* [rows] */);
+/* The alternatives sibling of zgml_hip_logprobs: row i's min(top_n, n) largest logits as (token, log-probability) pairs, in the
+ * order and under the rule of the `top_logprobs` word above, into tokens_out[i][0 ..] and logprobs_out[i][0 ..]; entries behind
+ * min(top_n, n) are -1 and the quiet NaN. Blocking; three launches ([partial] [select] [finish + top]) whatever `rows` is. Returns
+ * 0. Refused with -1 and an error on the context, nothing enqueued: everything zgml_hip_logprobs refuses of n, rows, the range and
+ * NULL pointers, and top_n outside 1 .. 64 (a new argument: refused, not clamped). */
+int zgml_hip_top_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n, uint32_t rows,
+                          uint32_t top_n, int64_t* tokens_out /* [rows][top_n] */, float* logprobs_out /* [rows][top_n] */);
 /* zgml_hip_resident_decode with the sampled tail: per token [prep] [plan] [select] [merge + pick + advance], the launch count of
  * the greedy loop, one graph launch per token. The parameters live in a device table uploaded per call, so one captured graph —
  * a separate one from the greedy loop's: alternating calls on one program invalidate nothing — serves every parameter set.

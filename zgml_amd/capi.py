@@ -185,6 +185,22 @@ class SpecStatsC(C.Structure):
     _fields_ = [("steps", C.c_uint32), ("drafted", C.c_uint32), ("accepted", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class _TrailingWord:
+    """A 32-bit word in the trailing padding of a ctypes structure, at `offset`: ctypes gives padding no name, and naming it in
+    _fields_ would change the list of fields that callers of the earlier layout iterate over. Read and written in place, so copies
+    of the structure (from_buffer_copy, array elements) carry it."""
+    size = 4
+
+    def __init__(self, offset: int):
+        self.offset = offset
+
+    def __get__(self, obj, cls=None):
+        return self if obj is None else C.c_uint32.from_buffer(obj, self.offset).value
+
+    def __set__(self, obj, value):
+        C.c_uint32.from_buffer(obj, self.offset).value = value
+
+
 class SamplingC(C.Structure):
     """zgml_sampling (include/zgml_hip.h): the parameters of the sampled token tail."""
     _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_uint32), ("n_stop", C.c_uint32),
@@ -192,15 +208,19 @@ class SamplingC(C.Structure):
                 ("repeat_penalty", C.c_float), ("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
                 ("penalty_window", C.c_uint32), ("recent", C.POINTER(C.c_uint32)), ("n_recent", C.c_uint32)]
 
+    top_logprobs = _TrailingWord(76)  # uint32_t top_logprobs: the four bytes of padding behind n_recent (sizeof stays 80)
+
     @staticmethod
     def of(temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, stream: int = 0, stop=(), repeat_penalty: float = 0.0,
-           presence_penalty: float = 0.0, frequency_penalty: float = 0.0, penalty_window: int = 0, recent=None, logprobs: bool = False) -> "SamplingC":
+           presence_penalty: float = 0.0, frequency_penalty: float = 0.0, penalty_window: int = 0, recent=None, logprobs: bool = False, top_logprobs: int = 0) -> "SamplingC":
         """stop: up to 4 token ids (more: handed over as they are, for the library to refuse). The penalties default to off.
         recent: the tokens before the call, oldest first (None: no array); a longer history is cut to its last penalty_window
         tokens — all any entry point reads —, and the array lives as long as the structure. logprobs: the call keeps the
-        log-probability of every token it emits for logprobs_result()."""
+        log-probability of every token it emits for logprobs_result(). top_logprobs: ... and that many alternatives per token for
+        top_logprobs_result() (the library reads the count only with `logprobs` set, so a count sets that word too)."""
         s = SamplingC(temperature=temperature, top_p=top_p, top_k=top_k, n_stop=len(stop), stream=stream, seed=seed, repeat_penalty=repeat_penalty,
-                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window, logprobs=int(bool(logprobs)))
+                      presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window, logprobs=int(bool(logprobs) or top_logprobs > 0))
+        s.top_logprobs = top_logprobs
         for i, t in enumerate(list(stop)[:4]):
             s.stop[i] = t
         if recent is not None:
@@ -213,10 +233,12 @@ class SamplingC(C.Structure):
         return s
 
 
-def with_logprobs(sampling: SamplingC) -> SamplingC:
-    """a copy of `sampling` (which stays as it is, and keeps its `recent` array alive) with the `logprobs` word set"""
+def with_logprobs(sampling: SamplingC, top: int = 0) -> SamplingC:
+    """a copy of `sampling` (which stays as it is, and keeps its `recent` array alive) with the `logprobs` word set, and with
+    `top` alternatives per token (0: none)"""
     sp = SamplingC.from_buffer_copy(sampling)
     sp.logprobs = 1
+    sp.top_logprobs = top
     return sp
 
 
@@ -229,6 +251,22 @@ def logprobs_result(ctx, shape):
     if have != out.size:
         raise RuntimeError(f"logprobs_result: the last call with log-probabilities left {have} values, not {out.size}")
     return out
+
+
+def top_logprobs_result(ctx, entries_shape):
+    """zgml_hip_top_logprobs_result: the alternatives the context's last call with `logprobs` and `top_logprobs` set left behind, as
+    (tokens int64[*entries_shape, width], values float32[*entries_shape, width]); entries_shape is the shape of that call's
+    tokens_out. Padding and entries of tokens that were not produced are -1 / NaN."""
+    import numpy as np
+    lib = load_hip()
+    width = C.c_uint32(0)
+    have = lib.zgml_hip_top_logprobs_result(ctx, None, None, 0, C.byref(width))
+    shape = tuple(np.atleast_1d(entries_shape).tolist()) + (width.value,)
+    tok, val = np.full(shape, -1, np.int64), np.full(shape, np.nan, np.float32)
+    if have != tok.size:
+        raise RuntimeError(f"top_logprobs_result: the last call with alternatives left {have} pairs, not {tok.size}")
+    lib.zgml_hip_top_logprobs_result(ctx, tok.ctypes.data_as(C.POINTER(C.c_int64)), val.ctypes.data_as(C.POINTER(C.c_float)), tok.size, None)
+    return tok, val
 
 
 class RuntimeProfileC(C.Structure):
@@ -257,6 +295,7 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_decode_speculative",
     "zgml_hip_sample", "zgml_hip_resident_decode_sampled", "zgml_hip_resident_decode_batch_sampled",
     "zgml_hip_resident_decode_speculative_sampled", "zgml_hip_logprobs", "zgml_hip_logprobs_result",
+    "zgml_hip_top_logprobs", "zgml_hip_top_logprobs_result",
 ]
 
 class ShardPointC(C.Structure):
@@ -399,6 +438,11 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_logprobs.argtypes = [vp, vp, C.c_uint16, u64, u64, u32, C.POINTER(u32), C.POINTER(C.c_float)]
         lib.zgml_hip_logprobs_result.restype = C.c_int64
         lib.zgml_hip_logprobs_result.argtypes = [vp, C.POINTER(C.c_float), u64]
+    if hasattr(lib, "zgml_hip_top_logprobs"):  # absent from an older build loaded beside this one (tools/top_logprob_decode_run.py)
+        lib.zgml_hip_top_logprobs.restype = i32
+        lib.zgml_hip_top_logprobs.argtypes = [vp, vp, C.c_uint16, u64, u64, u32, u32, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
+        lib.zgml_hip_top_logprobs_result.restype = C.c_int64
+        lib.zgml_hip_top_logprobs_result.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_float), u64, C.POINTER(u32)]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

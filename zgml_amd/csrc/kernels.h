@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "../../include/zgml_hip.h"
+#include "sample.h"
 #include "switches.h"
 
 namespace zgml {
@@ -472,6 +473,11 @@ struct SpecArgs {
     // lp_out[produced ..] next to the tokens ([tokens_cap]). nullptr: none
     const float* lp_rows = nullptr;
     float* lp_out = nullptr;
+    // ... and their alternatives (the `top_logprobs` word): row j's kTopLogprobsMax pairs, copied likewise to entry produced + k
+    const uint32_t* top_rows_tok = nullptr;
+    const float* top_rows_val = nullptr;
+    uint32_t* top_tok_out = nullptr;
+    float* top_val_out = nullptr;
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
@@ -483,6 +489,8 @@ struct SampleParamsDev {
     // the penalties (sample.h), read by the penalised select launch alone: pen_active = 0 leaves the row's logits as they are
     float repeat, inv_repeat, presence, frequency;
     uint32_t window, pen_active;
+    // the alternatives (sample.h), read by the top form of the finish launch alone: 0 .. kTopLogprobsMax per token
+    uint32_t top_logprobs;
 };
 // What the second launch does with the token of row b = blockIdx.y:
 //   state == nullptr       the blocking form: out[0] = token, cand[0] = number of candidates, cand[1 + j] = index of candidate j
@@ -520,12 +528,7 @@ struct SampleWindow {
     const uint32_t* cand = nullptr;
     const uint32_t* lo_word = nullptr;
 };
-constexpr uint32_t kSampleMaxSlices = 32; // partial candidate lists per row
-constexpr uint32_t kSampleChunk = 1792;   // logits a select workgroup sorts at a time (with the 256 best so far: 2048 keys)
-inline uint32_t sample_slices(uint64_t n) {
-    const uint64_t s = (n + kSampleChunk - 1) / kSampleChunk;
-    return s < 1 ? 1u : s > kSampleMaxSlices ? kSampleMaxSlices : (uint32_t)s;
-}
+// (kSampleMaxSlices, kSampleChunk and sample_slices(n): sample.h, where the rule of the alternatives needs them too)
 inline size_t sample_scratch_keys(uint64_t n, uint32_t rows) { return (size_t)rows * sample_slices(n) * 256; }
 // `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select: sample_slices(n) sorted lists of the 256 largest keys per row]
 // [merge to the row's candidates + pick + advance]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
@@ -558,6 +561,23 @@ struct LogprobTarget {
     uint32_t cap = 0, n_seqs = 0;
 };
 void launch_logprob_finish(hipStream_t s, const float* v, uint64_t n, uint32_t rows, const float* part, const LogprobTarget& t);
+// ── the alternatives (top_logprob.hip; the rule is sample.h's) ──
+// [select] alone over the raw rows, the unchanged kernel of launch_sample: what a step with active penalties needs beside its
+// penalised lists. scratch: sample_scratch_keys(n, rows) words, a region of its own.
+void launch_sample_select(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch);
+// [finish + top], in the place of [finish]: the chosen token's value exactly where and when launch_logprob_finish would write it
+// (`chosen`: the same forms, the same guard; all pointers null — zgml_hip_top_logprobs — there is no chosen token and the entry is
+// the row), and beside it — entry e of out at top_tok / top_val[e * kTopLogprobsMax ..] — the row's alternatives from `lists`, the
+// scratch a select launch over the RAW rows left: a lane each, 0xFFFFFFFF and the quiet NaN behind a_eff. The count of row b is
+// params[shared_params ? 0 : b].top_logprobs (device memory: one captured graph serves every count), or top_n without params.
+struct TopLogprobTarget {
+    LogprobTarget chosen;
+    uint32_t* top_tok = nullptr;
+    float* top_val = nullptr;
+    const SampleParamsDev* params = nullptr;
+    uint32_t shared_params = 0, top_n = 0;
+};
+void launch_logprob_finish_top(hipStream_t s, const float* v, uint64_t n, uint32_t rows, const float* part, const uint64_t* lists, const TopLogprobTarget& t);
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes);
 void launch_f32_to_f16(hipStream_t s, void* dst, const float* src, uint64_t n);
 

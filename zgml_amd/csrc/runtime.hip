@@ -642,6 +642,9 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipFree(ctx->lp_part);
     hipFree(ctx->lp_tok);
     hipFree(ctx->lp_out);
+    hipFree(ctx->top_keys);
+    hipFree(ctx->top_tok);
+    hipFree(ctx->top_val);
     if (ctx->handoff_flag) hipHostFree(ctx->handoff_flag);
     hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -132,6 +132,17 @@ struct zgml_hip_ctx {
     float* lp_out = nullptr;
     uint32_t lp_rows = 0;
     std::vector<float> lp_last; // what zgml_hip_logprobs_result hands out: the values of the last call with the `logprobs` word set
+    // the alternatives (zgml_hip_top_logprobs, and zgml_hip_sample with the `top_logprobs` word): the select launch's lists over the raw
+    // rows (top_keys_cap keys), [top_rows][64] tokens and values (grown by the call that needs more); and what
+    // zgml_hip_top_logprobs_result hands out, [entries][top_width_last]
+    uint64_t* top_keys = nullptr;
+    uint64_t top_keys_cap = 0;
+    uint32_t* top_tok = nullptr;
+    float* top_val = nullptr;
+    uint32_t top_rows = 0;
+    std::vector<int64_t> top_tok_last;
+    std::vector<float> top_val_last;
+    uint32_t top_width_last = 0;
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
     // Fused launches (q/k/v projection + decode attention): ONE host-visible word every bounded in-launch wait sets when it
     // gives up (pinned, device-mapped: the host reads it after any synchronisation without a copy). A set word means the

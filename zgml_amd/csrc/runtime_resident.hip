@@ -64,6 +64,16 @@ struct zgml_resident {
     uint64_t lp_cap = 0;
     hipGraph_t graph_sampled_lp = nullptr, graph_penalized_lp = nullptr;
     hipGraphExec_t graph_sampled_lp_exec = nullptr, graph_penalized_lp_exec = nullptr;
+    // the alternatives of the sampled tail (the `top_logprobs` word of zgml_sampling; top_logprob.hip), allocated by the first such
+    // call: the lists of a select over the RAW rows (what a penalised step needs beside skeys, the same size), the pairs next to
+    // the produced tokens ([top_cap][64], the layout of lp), the T rows' pairs of a verify step; the loops' own graphs, "sampled +
+    // top" and "penalised + top", beside the other six
+    uint64_t* skeys_raw = nullptr;
+    uint32_t *top_tok = nullptr, *top_rows_tok = nullptr;
+    float *top_val = nullptr, *top_rows_val = nullptr;
+    uint64_t top_cap = 0;
+    hipGraph_t graph_sampled_top = nullptr, graph_penalized_top = nullptr;
+    hipGraphExec_t graph_sampled_top_exec = nullptr, graph_penalized_top_exec = nullptr;
 };
 using Resident = zgml_resident;
 
@@ -90,6 +100,12 @@ void free_resident_graph(zgml_hip_program* p) {
     if (r->graph_penalized_lp_exec) hipGraphExecDestroy(r->graph_penalized_lp_exec);
     if (r->graph_penalized_lp) hipGraphDestroy(r->graph_penalized_lp);
     r->graph_penalized_lp_exec = nullptr, r->graph_penalized_lp = nullptr;
+    if (r->graph_sampled_top_exec) hipGraphExecDestroy(r->graph_sampled_top_exec);
+    if (r->graph_sampled_top) hipGraphDestroy(r->graph_sampled_top);
+    r->graph_sampled_top_exec = nullptr, r->graph_sampled_top = nullptr;
+    if (r->graph_penalized_top_exec) hipGraphExecDestroy(r->graph_penalized_top_exec);
+    if (r->graph_penalized_top) hipGraphDestroy(r->graph_penalized_top);
+    r->graph_penalized_top_exec = nullptr, r->graph_penalized_top = nullptr;
 }
 
 void free_resident(zgml_hip_program* p) {
@@ -122,6 +138,11 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->lp);
     hipFree(r->lp_rows);
     hipFree(r->lp_written);
+    hipFree(r->skeys_raw);
+    hipFree(r->top_tok);
+    hipFree(r->top_rows_tok);
+    hipFree(r->top_val);
+    hipFree(r->top_rows_val);
     delete r;
     p->resident = nullptr;
 }
@@ -208,7 +229,7 @@ bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampl
     }
     *out = SampleParamsDev{1.0f / sp->temperature, sp->top_p, sp->top_k, vocab ? sp->n_stop : 0, {sp->stop[0], sp->stop[1], sp->stop[2], sp->stop[3]},
                            sp->stream, (uint32_t)sp->seed, (uint32_t)(sp->seed >> 32),
-                           repeat, 1.0f / repeat, sp->presence_penalty, sp->frequency_penalty, sp->penalty_window, active};
+                           repeat, 1.0f / repeat, sp->presence_penalty, sp->frequency_penalty, sp->penalty_window, active, sample_top_logprobs(sp)};
     return true;
 }
 
@@ -265,6 +286,68 @@ bool ensure_ctx_logprob(zgml_hip_ctx* ctx, uint32_t rows) {
         return false;
     ctx->lp_rows = rows;
     return true;
+}
+
+// the blocks of the alternatives of the sampled loops: `rows` logits rows, pairs for `cap` produced tokens (as the values above:
+// growing them drops the graphs)
+bool ensure_top_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, uint64_t cap) {
+    Resident* r = p->resident;
+    if (!r->skeys_raw && (!CTX_CHECK(ctx, hipMalloc((void**)&r->skeys_raw, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t))) ||
+                          !CTX_CHECK(ctx, hipMalloc((void**)&r->top_rows_tok, (size_t)rows * kTopLogprobsMax * 4)) ||
+                          !CTX_CHECK(ctx, hipMalloc((void**)&r->top_rows_val, (size_t)rows * kTopLogprobsMax * sizeof(float)))))
+        return false;
+    if (r->top_cap < cap) {
+        hipStreamSynchronize(ctx->stream);
+        hipFree(r->top_tok), hipFree(r->top_val);
+        r->top_tok = nullptr, r->top_val = nullptr, r->top_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->top_tok, (size_t)cap * kTopLogprobsMax * 4)) ||
+            !CTX_CHECK(ctx, hipMalloc((void**)&r->top_val, (size_t)cap * kTopLogprobsMax * sizeof(float))))
+            return false;
+        r->top_cap = cap;
+        free_resident_graph(p);
+    }
+    return true;
+}
+
+// the context's blocks of zgml_hip_top_logprobs (and of zgml_hip_sample with the word) for `rows` rows and `keys` list words
+bool ensure_ctx_top(zgml_hip_ctx* ctx, uint32_t rows, uint64_t keys) {
+    if (ctx->top_rows >= rows && ctx->top_keys_cap >= keys) return true;
+    hipStreamSynchronize(ctx->stream);
+    if (ctx->top_keys_cap < keys) {
+        hipFree(ctx->top_keys);
+        ctx->top_keys = nullptr, ctx->top_keys_cap = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->top_keys, (size_t)keys * sizeof(uint64_t)))) return false;
+        ctx->top_keys_cap = keys;
+    }
+    if (ctx->top_rows < rows) {
+        hipFree(ctx->top_tok), hipFree(ctx->top_val);
+        ctx->top_tok = nullptr, ctx->top_val = nullptr, ctx->top_rows = 0;
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->top_tok, (size_t)rows * kTopLogprobsMax * 4)) ||
+            !CTX_CHECK(ctx, hipMalloc((void**)&ctx->top_val, (size_t)rows * kTopLogprobsMax * sizeof(float))))
+            return false;
+        ctx->top_rows = rows;
+    }
+    return true;
+}
+
+// What zgml_hip_top_logprobs_result hands out, from a call's downloaded pairs (rows of kTopLogprobsMax, as the device holds
+// them): [entries][width], entry e from row src(e), or padding throughout where src(e) < 0 — a token that was not produced, a
+// sequence without the word
+template <class Src>
+void top_keep(zgml_hip_ctx* ctx, uint64_t entries, uint32_t width, const std::vector<uint32_t>& tok, const std::vector<float>& val, Src src) {
+    ctx->top_width_last = width;
+    ctx->top_tok_last.assign((size_t)entries * width, -1);
+    ctx->top_val_last.assign((size_t)entries * width, sample_bits_f32(kLogprobNaNBits));
+    for (uint64_t e = 0; e < entries; e++) {
+        const int64_t from = src(e);
+        if (from < 0) continue;
+        for (uint32_t j = 0; j < width; j++) {
+            const uint32_t t = tok[(size_t)from * kTopLogprobsMax + j];
+            if (t == 0xFFFFFFFFu) continue; // (behind the row's own count)
+            ctx->top_tok_last[(size_t)e * width + j] = (int64_t)t;
+            ctx->top_val_last[(size_t)e * width + j] = val[(size_t)from * kTopLogprobsMax + j];
+        }
+    }
 }
 
 // entries of tokens that were not produced
@@ -536,6 +619,8 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
                            !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_out, out_words * 4))))
         return -1;
     if (sampling->logprobs && !ensure_ctx_logprob(ctx, 1)) return -1;
+    const uint32_t top = sp.top_logprobs; // (0 without the `logprobs` word)
+    if (top && !ensure_ctx_top(ctx, 1, sample_scratch_keys(n, 1))) return -1;
     if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
     SampleAdvance adv;
     adv.position = position, adv.out = (int64_t*)ctx->smp_out, adv.cand = ctx->smp_out + 2;
@@ -550,17 +635,30 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
         launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
     }
     float lp = 0.0f;
+    std::vector<uint32_t> top_tok;
+    std::vector<float> top_val;
     if (sampling->logprobs) { // over the raw row, behind the pick: the token is read where the merge launch stored it
         LogprobTarget lt;
         lt.out = ctx->lp_out, lt.token64 = (const int64_t*)ctx->smp_out;
         launch_logprob(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part);
-        launch_logprob_finish(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, lt);
+        if (top) { // the alternatives: from the pick's own lists, or — penalties have changed those — from a select over the raw row
+            TopLogprobTarget tt;
+            tt.chosen = lt, tt.top_tok = ctx->top_tok, tt.top_val = ctx->top_val, tt.params = ctx->smp_params;
+            if (sp.pen_active) launch_sample_select(s, p->bufs[buf_idx] + offset, n, 1, ctx->top_keys);
+            launch_logprob_finish_top(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, sp.pen_active ? ctx->top_keys : ctx->smp_keys, tt);
+            top_tok.resize(kTopLogprobsMax), top_val.resize(kTopLogprobsMax);
+            hipMemcpyAsync(top_tok.data(), ctx->top_tok, kTopLogprobsMax * 4, hipMemcpyDeviceToHost, s);
+            hipMemcpyAsync(top_val.data(), ctx->top_val, kTopLogprobsMax * sizeof(float), hipMemcpyDeviceToHost, s);
+        } else {
+            launch_logprob_finish(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, lt);
+        }
         hipMemcpyAsync(&lp, ctx->lp_out, sizeof(lp), hipMemcpyDeviceToHost, s);
     }
     uint32_t got[out_words];
     hipMemcpyAsync(got, ctx->smp_out, sizeof(got), hipMemcpyDeviceToHost, s);
     if (!CTX_CHECK(ctx, hipStreamSynchronize(s)) || !ctx->handoff_ok("sample")) return -1;
     if (sampling->logprobs) ctx->lp_last.assign(1, lp);
+    if (top) top_keep(ctx, 1, top_logprobs_count(top, n), top_tok, top_val, [](uint64_t) { return (int64_t)0; });
     const uint32_t kc = std::min<uint32_t>(got[2], kSampleMaxK);
     if (n_candidates_out) *n_candidates_out = kc;
     if (candidates_out) memcpy(candidates_out, got + 3, (size_t)kc * 4);
@@ -594,6 +692,59 @@ int zgml_hip_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx, 
         if (!CTX_CHECK(ctx, hipStreamSynchronize(s))) return -1; // (the caller's arrays are pageable memory: nothing of them in flight on return)
     }
     return ctx->handoff_ok("logprobs") ? 0 : -1;
+}
+
+// the min(top_n, n) largest logits of `rows` consecutive rows with their log-probabilities: [partial] [select] [finish + top]
+int zgml_hip_top_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx, uint64_t offset, uint64_t n, uint32_t rows, uint32_t top_n,
+                          int64_t* tokens_out, float* logprobs_out) {
+    if (!ctx || !p) return -1;
+    const uint64_t buf_size = buf_idx < p->bufs.size() && p->bufs[buf_idx] ? p->sizes[buf_idx] : 0;
+    if (const char* why = top_logprobs_check(buf_size, offset, n, rows, top_n, tokens_out, logprobs_out)) {
+        ctx->fail(std::string("top_logprobs: ") + why);
+        return -1;
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    constexpr uint32_t kMaxGridRows = 1024; // rows per triple of launches: the lists of that many rows are at most 64 MiB
+    const uint32_t chunk = std::min(rows, kMaxGridRows);
+    if (!ensure_ctx_logprob(ctx, chunk) || !ensure_ctx_top(ctx, chunk, sample_scratch_keys(n, chunk))) return -1;
+    std::vector<uint32_t> tok((size_t)chunk * kTopLogprobsMax);
+    std::vector<float> val((size_t)chunk * kTopLogprobsMax);
+    for (uint32_t r0 = 0; r0 < rows; r0 += kMaxGridRows) {
+        const uint32_t nr = std::min(rows - r0, kMaxGridRows);
+        const float* v = p->bufs[buf_idx] + offset + (uint64_t)r0 * n;
+        TopLogprobTarget tt; // (no chosen token: the entry is the row)
+        tt.top_tok = ctx->top_tok, tt.top_val = ctx->top_val, tt.top_n = top_n;
+        launch_logprob(s, v, n, nr, ctx->lp_part);
+        launch_sample_select(s, v, n, nr, ctx->top_keys);
+        launch_logprob_finish_top(s, v, n, nr, ctx->lp_part, ctx->top_keys, tt);
+        hipMemcpyAsync(tok.data(), ctx->top_tok, (size_t)nr * kTopLogprobsMax * 4, hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(val.data(), ctx->top_val, (size_t)nr * kTopLogprobsMax * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (!CTX_CHECK(ctx, hipStreamSynchronize(s))) return -1;
+        for (uint32_t i = 0; i < nr; i++)
+            for (uint32_t j = 0; j < top_n; j++) { // (behind min(top_n, n) the kernel left 0xFFFFFFFF and the NaN)
+                const uint32_t t = tok[(size_t)i * kTopLogprobsMax + j];
+                tokens_out[(uint64_t)(r0 + i) * top_n + j] = t == 0xFFFFFFFFu ? -1 : (int64_t)t;
+                logprobs_out[(uint64_t)(r0 + i) * top_n + j] = val[(size_t)i * kTopLogprobsMax + j];
+            }
+    }
+    return ctx->handoff_ok("top_logprobs") ? 0 : -1;
+}
+
+// the alternatives the context's last call with `logprobs` and `top_logprobs` set left behind: [entries][width]
+int64_t zgml_hip_top_logprobs_result(zgml_hip_ctx* ctx, int64_t* tokens_out, float* logprobs_out, uint64_t n, uint32_t* width_out) {
+    if (!ctx) return -1;
+    if ((!tokens_out || !logprobs_out) && n) {
+        ctx->fail("top_logprobs_result: tokens_out and logprobs_out must not be NULL");
+        return -1;
+    }
+    const uint64_t have = ctx->top_tok_last.size();
+    if (const uint64_t take = std::min(n, have)) {
+        memcpy(tokens_out, ctx->top_tok_last.data(), take * sizeof(int64_t));
+        memcpy(logprobs_out, ctx->top_val_last.data(), take * sizeof(float));
+    }
+    if (width_out) *width_out = ctx->top_width_last;
+    return (int64_t)have;
 }
 
 // the values the context's last call with the `logprobs` word set left behind, in the layout of that call's tokens_out
@@ -634,7 +785,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     resident_begin(p, [&] {
         return positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; });
     });
-    const bool penalized = sp.pen_active != 0, lp = sampling->logprobs != 0;
+    const bool penalized = sp.pen_active != 0, lp = sampling->logprobs != 0, top = sp.top_logprobs != 0; // (top: only with lp)
     if (!ensure_sample_blocks(ctx, r, 1) || (penalized && !ensure_window_block(ctx, r, 1))) return -1;
     if (r->tokens_cap < n_steps) {
         hipStreamSynchronize(s);
@@ -645,6 +796,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         free_resident_graph(p); // the graphs baked the old pointer/cap
     }
     if (lp && !ensure_logprob_blocks(ctx, p, 1, r->tokens_cap)) return -1;
+    if (top && !ensure_top_blocks(ctx, p, 1, r->tokens_cap)) return -1;
     const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
                              p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
     const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
@@ -654,6 +806,8 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     win.ring = r->swin, win.lo = r->swin + kSamplePenaltyMaxWindow;
     LogprobTarget lt; // (calls with the `logprobs` field only)
     lt.out = r->lp, lt.state = r->state, lt.emitted = r->tokens, lt.written = r->lp_written, lt.cap = r->tokens_cap;
+    TopLogprobTarget tt; // (calls with the `top_logprobs` word only)
+    tt.chosen = lt, tt.top_tok = r->top_tok, tt.top_val = r->top_val, tt.params = r->sparams;
     auto one_token = [&](hipStream_t st) {
         launch_resident_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
@@ -662,7 +816,12 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
             launch_sample_penalized(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win);
         else
             launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
-        if (lp) launch_logprob_finish(st, r->logits, r->vocab, 1, r->lpart, lt); // (behind the advance: it knows whether a token was emitted)
+        if (top) { // [finish + top] in the place of [finish]: the merge launch only read the lists; penalised ones are no use, so a raw select
+            if (penalized) launch_sample_select(st, r->logits, r->vocab, 1, r->skeys_raw);
+            launch_logprob_finish_top(st, r->logits, r->vocab, 1, r->lpart, penalized ? r->skeys_raw : r->skeys, tt);
+        } else if (lp) {
+            launch_logprob_finish(st, r->logits, r->vocab, 1, r->lpart, lt); // (behind the advance: it knows whether a token was emitted)
+        }
     };
     std::vector<uint32_t> win0; // (penalised calls only; alive until the call's last synchronisation)
     if (penalized) {
@@ -678,12 +837,17 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         return -1;
     // (a penalised call replays a graph of its own, and so does a call with log-probabilities: the four kinds of call alternate on
     // one program and invalidate nothing)
-    hipGraphExec_t& exec = lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
-    hipGraph_t& graph = lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : (penalized ? r->graph_penalized : r->graph_sampled);
+    hipGraphExec_t& exec = top  ? (penalized ? r->graph_penalized_top_exec : r->graph_sampled_top_exec)
+                           : lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec)
+                                : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
+    hipGraph_t& graph = top  ? (penalized ? r->graph_penalized_top : r->graph_sampled_top)
+                        : lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp)
+                             : (penalized ? r->graph_penalized : r->graph_sampled);
     if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (the copies above read this stack frame: none in flight when the capture begins)
-        const char* const names[4] = {"resident_sampled", "resident_penalized", "resident_sampled_logprobs", "resident_penalized_logprobs"};
-        capture_graph(ctx, s, names[2 * lp + penalized], [&] { one_token(s); }, &graph, &exec); // (failed: eager below)
+        const char* const names[6] = {"resident_sampled", "resident_penalized", "resident_sampled_logprobs", "resident_penalized_logprobs",
+                                      "resident_sampled_top", "resident_penalized_top"};
+        capture_graph(ctx, s, names[top ? 4 + penalized : 2 * lp + penalized], [&] { one_token(s); }, &graph, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < n_steps; i++) {
         if (exec)
@@ -698,11 +862,20 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         ctx->lp_last.assign(n_steps, 0.0f);
         hipMemcpyAsync(ctx->lp_last.data(), r->lp, (size_t)n_steps * sizeof(float), hipMemcpyDeviceToHost, s);
     }
+    std::vector<uint32_t> top_tok(top ? (size_t)n_steps * kTopLogprobsMax : 0);
+    std::vector<float> top_val(top_tok.size());
+    if (top) {
+        hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+    }
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode_sampled");
     if (ok && n_produced) *n_produced = std::min(st1[2], n_steps);
-    if (lp) logprob_fill_unproduced(ctx->lp_last.data(), ok ? std::min(st1[2], n_steps) : 0, n_steps);
-    resident_end(p, n_steps, p->plan.size() + (lp ? 5 : 3)); // per token [prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish])
+    const uint32_t made = ok ? std::min(st1[2], n_steps) : 0;
+    if (lp) logprob_fill_unproduced(ctx->lp_last.data(), made, n_steps);
+    if (top) top_keep(ctx, n_steps, top_logprobs_count(sp.top_logprobs, r->vocab), top_tok, top_val, [&](uint64_t e) { return e < made ? (int64_t)e : -1; });
+    // per token [prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish], or ([raw select]) [finish + top])
+    resident_end(p, n_steps, p->plan.size() + (top ? 5 + penalized : lp ? 5 : 3));
     return ok ? 0 : -1;
 }
 
@@ -749,7 +922,8 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     });
     bool penalized = false; // one sequence with penalties: the penalised launch for all (a row without them computes what it did)
     bool lp = false; // ... and one with log-probabilities: the two launches for all (a row nobody asked for is not copied out)
-    for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active, lp = lp || per_seq[b].logprobs;
+    bool top = false; // ... and one with alternatives: the top form of the finish for all (a row with the count 0 is all padding)
+    for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active, lp = lp || per_seq[b].logprobs, top = top || sp[b].top_logprobs;
     if (!ensure_sample_blocks(ctx, r, B) || (penalized && !ensure_window_block(ctx, r, B))) return -1;
     if (r->btokens_cap < (uint64_t)B * steps) {
         hipStreamSynchronize(s);
@@ -760,11 +934,14 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         free_resident_graph(p); // the graphs baked the old pointer
     }
     if (lp && !ensure_logprob_blocks(ctx, p, B, r->btokens_cap)) return -1;
+    if (top && !ensure_top_blocks(ctx, p, B, r->btokens_cap)) return -1;
     const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
                                   p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
     const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
     LogprobTarget lt; // (calls with the `logprobs` field only) the values lie as the tokens do: [B][steps]
     lt.out = r->lp, lt.state = r->bstate, lt.emitted = r->btokens, lt.written = r->lp_written, lt.n_seqs = B;
+    TopLogprobTarget tt; // (calls with the `top_logprobs` word only) the pairs lie as the values do
+    tt.chosen = lt, tt.top_tok = r->top_tok, tt.top_val = r->top_val, tt.params = r->sparams;
     SampleAdvance adv;
     adv.state = r->bstate, adv.tokens = r->btokens, adv.n_seqs = B;
     SampleWindow win;
@@ -777,7 +954,12 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
             launch_sample_penalized(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win);
         else
             launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
-        if (lp) launch_logprob_finish(st, r->logits, r->vocab, B, r->lpart, lt);
+        if (top) { // (one sequence with penalties active: the raw select for all rows, so the launches stay uniform)
+            if (penalized) launch_sample_select(st, r->logits, r->vocab, B, r->skeys_raw);
+            launch_logprob_finish_top(st, r->logits, r->vocab, B, r->lpart, penalized ? r->skeys_raw : r->skeys, tt);
+        } else if (lp) {
+            launch_logprob_finish(st, r->logits, r->vocab, B, r->lpart, lt);
+        }
     };
     std::vector<uint32_t> win0;
     if (penalized) {
@@ -793,12 +975,17 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s)) || // (-1: what a sequence leaves behind its count)
         (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, (size_t)B * 4, s))))
         return -1;
-    hipGraphExec_t& exec = lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
-    hipGraph_t& graph = lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : (penalized ? r->graph_penalized : r->graph_sampled);
+    hipGraphExec_t& exec = top  ? (penalized ? r->graph_penalized_top_exec : r->graph_sampled_top_exec)
+                           : lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec)
+                                : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
+    hipGraph_t& graph = top  ? (penalized ? r->graph_penalized_top : r->graph_sampled_top)
+                        : lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp)
+                             : (penalized ? r->graph_penalized : r->graph_sampled);
     if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (as the greedy batched loop: no pageable copy in flight when the capture begins)
-        const char* const names[4] = {"resident_batch_sampled", "resident_batch_penalized", "resident_batch_sampled_logprobs", "resident_batch_penalized_logprobs"};
-        capture_graph(ctx, s, names[2 * lp + penalized], [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
+        const char* const names[6] = {"resident_batch_sampled", "resident_batch_penalized", "resident_batch_sampled_logprobs", "resident_batch_penalized_logprobs",
+                                      "resident_batch_sampled_top", "resident_batch_penalized_top"};
+        capture_graph(ctx, s, names[top ? 4 + penalized : 2 * lp + penalized], [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < steps; i++) {
         if (exec)
@@ -811,6 +998,12 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     hipMemcpyAsync(st1.data(), r->bstate, st1.size() * 4, hipMemcpyDeviceToHost, s);
     std::vector<float> got_lp(lp ? (size_t)B * steps : 0);
     if (lp) hipMemcpyAsync(got_lp.data(), r->lp, got_lp.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+    std::vector<uint32_t> top_tok(top ? (size_t)B * steps * kTopLogprobsMax : 0);
+    std::vector<float> top_val(top_tok.size());
+    if (top) {
+        hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+    }
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode_batch_sampled");
     for (uint32_t b = 0; ok && b < B; b++) {
@@ -825,7 +1018,17 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         for (uint32_t i = 0; i < made; i++) out[i] = got_lp[(uint64_t)b * steps + i];
         logprob_fill_unproduced(out, made, max_steps);
     }
-    resident_end(p, steps, p->plan.size() + (lp ? 5 : 3)); // per step [batched prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish])
+    if (top) { // [n_seqs][max_steps][width]: the largest count among the sequences; a sequence with a smaller one, or none, is padded
+        uint32_t width = 0;
+        for (uint32_t b = 0; b < B; b++) width = std::max(width, top_logprobs_count(sp[b].top_logprobs, r->vocab));
+        top_keep(ctx, (uint64_t)B * max_steps, width, top_tok, top_val, [&](uint64_t e) {
+            const uint32_t b = (uint32_t)(e / max_steps), i = (uint32_t)(e % max_steps);
+            const uint32_t made = ok ? std::min(st1[3 * B + b], n_steps[b]) : 0;
+            return sp[b].top_logprobs && i < made ? (int64_t)((uint64_t)b * steps + i) : -1;
+        });
+    }
+    // per step [batched prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish], or ([raw select]) [finish + top])
+    resident_end(p, steps, p->plan.size() + (top ? 5 + penalized : lp ? 5 : 3));
     return ok ? 0 : -1;
 }
 
@@ -924,7 +1127,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     }
     SampleParamsDev sp{};
     if (sampled && !sampling_params(ctx, who, sampling, r->vocab, r->vocab, &sp, RecentOf::Spec)) return -1;
-    const bool penalized = sp.pen_active != 0, lp = sampled && sampling->logprobs; // (sampled form only)
+    const bool penalized = sp.pen_active != 0, lp = sampled && sampling->logprobs, top = sp.top_logprobs != 0; // (sampled form only; top: only with lp)
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     // the first start and the last possible start of a verify step
@@ -949,6 +1152,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         free_resident_graph(p); // the graph baked the old pointer/cap
     }
     if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens_cap)) return -1;
+    if (top && !ensure_top_blocks(ctx, p, T, r->tokens_cap)) return -1;
     uint32_t w0[kSpecWords] = {0};
     w0[kSpecTok] = first_token, w0[kSpecPos] = start_pos, w0[kSpecWanted] = n_tokens, w0[kSpecMode] = o.mode, w0[kSpecNgram] = ngram;
     w0[kSpecNDrafts] = std::min(n_drafts, r->max_seq), w0[kSpecStart] = start_pos, w0[kSpecHistLo] = o.n_history ? 0 : start_pos;
@@ -971,6 +1175,9 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     LogprobTarget lt; // (the `logprobs` field only) every row's value of its pick; the accept launch copies the emitted prefix
     lt.out = r->lp_rows, lt.picks = r->picks;
     if (lp) sa.lp_rows = r->lp_rows, sa.lp_out = r->lp;
+    TopLogprobTarget tt; // (the `top_logprobs` word only) every row's alternatives, likewise; the rows read parameter row 0
+    tt.chosen = lt, tt.top_tok = r->top_rows_tok, tt.top_val = r->top_rows_val, tt.params = r->sparams, tt.shared_params = 1;
+    if (top) sa.top_rows_tok = r->top_rows_tok, sa.top_rows_val = r->top_rows_val, sa.top_tok_out = r->top_tok, sa.top_val_out = r->top_val;
     SampleWindow win; // (penalised form only) a row's window is the call's history up to the run position and the candidates behind it
     win.hist = r->hist, win.cand = r->tok_dev, win.lo_word = r->spec + kSpecHistLo;
     // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
@@ -991,19 +1198,26 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             launch_sample(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv);
         else
             launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
-        if (lp) launch_logprob_finish(st, r->logits, r->vocab, T, r->lpart, lt);
+        if (top) {
+            if (penalized) launch_sample_select(st, r->logits, r->vocab, T, r->skeys_raw);
+            launch_logprob_finish_top(st, r->logits, r->vocab, T, r->lpart, penalized ? r->skeys_raw : r->skeys, tt);
+        } else if (lp) {
+            launch_logprob_finish(st, r->logits, r->vocab, T, r->lpart, lt);
+        }
         launch_spec_accept(st, sa);
     };
-    hipGraphExec_t& exec = lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : penalized ? r->graph_penalized_exec : sampled ? r->graph_sampled_exec : r->graph_exec;
-    hipGraph_t& graph = lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : penalized ? r->graph_penalized : sampled ? r->graph_sampled : r->graph;
+    hipGraphExec_t& exec = top ? (penalized ? r->graph_penalized_top_exec : r->graph_sampled_top_exec) : lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : penalized ? r->graph_penalized_exec : sampled ? r->graph_sampled_exec : r->graph_exec;
+    hipGraph_t& graph = top ? (penalized ? r->graph_penalized_top : r->graph_sampled_top) : lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : penalized ? r->graph_penalized : sampled ? r->graph_sampled : r->graph;
     if (ctx->opt_graph && !exec) {
         if (sampled) hipStreamSynchronize(s); // (as the sampled loops: no copy from this stack frame in flight when the capture begins)
-        capture_graph(ctx, s, lp ? (penalized ? "resident_spec_penalized_logprobs" : "resident_spec_sampled_logprobs") : penalized ? "resident_spec_penalized" : sampled ? "resident_spec_sampled" : "resident_spec",
+        capture_graph(ctx, s, top ? (penalized ? "resident_spec_penalized_top" : "resident_spec_sampled_top") : lp ? (penalized ? "resident_spec_penalized_logprobs" : "resident_spec_sampled_logprobs") : penalized ? "resident_spec_penalized" : sampled ? "resident_spec_sampled" : "resident_spec",
                       [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
     }
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)
     uint32_t w1[kSpecWords] = {0};
+    std::vector<uint32_t> top_tok;
+    std::vector<float> top_val;
     uint64_t steps_run = 0;
     bool ok = true;
     for (uint32_t produced = 0, wanted = n_tokens; ok && produced < wanted;) {
@@ -1029,6 +1243,11 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             ctx->lp_last.assign(n_tokens, 0.0f);
             hipMemcpyAsync(ctx->lp_last.data(), r->lp, (size_t)n_tokens * sizeof(float), hipMemcpyDeviceToHost, s);
         }
+        if (top) {
+            top_tok.resize((size_t)n_tokens * kTopLogprobsMax), top_val.resize(top_tok.size());
+            hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
+            hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+        }
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     }
     ok = ok && ctx->handoff_ok(who.c_str());
@@ -1036,10 +1255,15 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         ctx->lp_last.resize(n_tokens);
         logprob_fill_unproduced(ctx->lp_last.data(), ok ? std::min(w1[kSpecProduced], n_tokens) : 0, n_tokens);
     }
+    if (top) {
+        const uint32_t made = ok ? std::min(w1[kSpecProduced], n_tokens) : 0;
+        top_keep(ctx, n_tokens, top_logprobs_count(sp.top_logprobs, r->vocab), top_tok, top_val, [&](uint64_t e) { return e < made ? (int64_t)e : -1; });
+    }
     if (ok && stats) *stats = zgml_spec_stats{w1[kSpecSteps], w1[kSpecDrafted], w1[kSpecAccepted], 0};
     if (ok && n_produced) *n_produced = std::min(w1[kSpecProduced], n_tokens);
     // per step [draft] [prep] [plan] [argmax stage 1] [accept], or [draft] [prep] [plan] [select] [merge + pick] [accept]
-    resident_end(p, steps_run, p->plan.size() + (lp ? 7 : sampled ? 5 : 4)); // (with log-probabilities: [partial] and [finish] as well)
+    // (with log-probabilities: [partial] and [finish] as well; with alternatives under penalties: the raw [select] too)
+    resident_end(p, steps_run, p->plan.size() + (top ? 7 + penalized : lp ? 7 : sampled ? 5 : 4));
     return ok ? 0 : -1;
 }
 

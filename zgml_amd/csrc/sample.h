@@ -1,7 +1,8 @@
 // sample.h — the rule of seeded top-k / top-p sampling and of the log-probabilities (zgml_hip_sample, zgml_hip_logprobs,
-// zgml_hip_resident_decode_sampled, _batch_sampled; include/zgml_hip.h), written ONCE: the kernels of sample.hip and logprob.hip
-// call these functions and so do the host probes tests/cpp/sample_probe.cpp and logprob_probe.cpp (tests/test_sample_host.py and
-// tests/test_logprob_host.py compare them with float64 numpy models of the same rule). Plain C++, no device intrinsics: the
+// zgml_hip_resident_decode_sampled, _batch_sampled; include/zgml_hip.h), written ONCE: the kernels of sample.hip, logprob.hip and
+// top_logprob.hip call these functions and so do the host probes tests/cpp/sample_probe.cpp, logprob_probe.cpp and
+// top_logprob_probe.cpp (tests/test_sample_host.py, tests/test_logprob_host.py and tests/test_top_logprob_host.py compare them with
+// float64 numpy models of the same rule). Plain C++, no device intrinsics: the
 // header compiles under g++ as it stands. Both sides must be built with -ffp-contract=off: every
 // operation below is then one correctly rounded IEEE operation or an explicit fmaf, and device and host agree to the bit.
 //
@@ -55,6 +56,15 @@
 //            (or NaN) under a finite M: -inf.  n = 1 with a finite logit: +0.0f (v - v = +0, S = 1, sample_log(1) = +0).
 // n is at most kLogprobMaxBlocks blocks = 2^20 logits. Against v_t - logsumexp(v) in float64 the error is at most
 // 1e-5 + 2.4e-7 |v_t - M| (the bar of tests/test_logprob_host.py, derived there; measured maximum: 4.5e-7 + the second term).
+//
+// THE ALTERNATIVES of a row of n logits for a count a (the `top_logprobs` word of zgml_sampling, zgml_hip_top_logprobs; kernel:
+// top_logprob.hip): a_eff = min(a, kTopLogprobsMax, n) entries (token_j, value_j), the a_eff largest keys sample_key(v_i, i) over the
+// RAW row — before penalties, before the temperature, whatever top_k / top_p say —, descending: the candidate order above.
+// token_j = sample_key_index(key_j); value_j = logprob_of(sample_key_value(key_j), M, S) with the row's M and S of the
+// log-probability rule. sample_key_value(sample_key(v, i)) is logprob_value(v), so value_j is the log-probability of token_j over
+// the same row, to the bit, and entry 0 is the row's first maximum. M = -inf: every value is -inf and the tokens are 0, 1, 2, ..
+// (all keys carry the same value word, the lower index first). M = +inf: every value is the quiet NaN, the tokens still the key
+// order. Entries a_eff .. of a row hold token -1 and the quiet NaN.
 #pragma once
 
 #include <math.h>
@@ -308,6 +318,91 @@ ZGML_SAMPLE_FN void logprob_finish(const float* m, const float* s, uint32_t nb, 
         if (m[b] > M) M = m[b];
     for (uint32_t b = 0; b < nb; b++) S = S + logprob_block_term(m[b], s[b], M);
     *M_out = M, *S_out = S;
+}
+
+// ── the alternatives ──
+
+constexpr uint32_t kTopLogprobsMax = 64; // alternatives per row
+
+// How the select launch cuts a row (sample.hip): sample_slices(n) slices of ceil(n / slices) consecutive logits, a sorted list of
+// the 256 largest keys each
+constexpr uint32_t kSampleMaxSlices = 32; // partial candidate lists per row
+constexpr uint32_t kSampleChunk = 1792;   // logits a select workgroup sorts at a time (with the 256 best so far: 2048 keys)
+ZGML_SAMPLE_FN uint32_t sample_slices(uint64_t n) {
+    const uint64_t s = (n + kSampleChunk - 1) / kSampleChunk;
+    return s < 1 ? 1u : s > kSampleMaxSlices ? kSampleMaxSlices : (uint32_t)s;
+}
+ZGML_SAMPLE_FN uint32_t sample_slice_len(uint64_t n) {
+    const uint32_t slices = sample_slices(n);
+    return (uint32_t)((n + slices - 1) / slices);
+}
+
+// a_eff
+ZGML_SAMPLE_FN uint32_t top_logprobs_count(uint32_t a, uint64_t n) {
+    const uint32_t c = a > kTopLogprobsMax ? kTopLogprobsMax : a;
+    return n < c ? (uint32_t)n : c;
+}
+
+// the `cap` (<= kTopLogprobsMax) largest keys of v[lo, hi), descending, into out[0, cap), 0 behind the last of fewer: the walk
+// keeps the best so far sorted and inserts every key above the last of them
+ZGML_SAMPLE_FN void top_logprobs_walk(const float* v, uint64_t lo, uint64_t hi, uint32_t cap, uint64_t* out) {
+    for (uint32_t j = 0; j < cap; j++) out[j] = 0;
+    if (!cap) return;
+    for (uint64_t i = lo; i < hi; i++) {
+        const uint64_t key = sample_key(v[i], (uint32_t)i);
+        if (key <= out[cap - 1]) continue;
+        uint32_t j = cap - 1;
+        for (; j > 0 && out[j - 1] < key; j--) out[j] = out[j - 1];
+        out[j] = key;
+    }
+}
+
+// the direct form: the a_eff largest keys of the row; returns a_eff
+ZGML_SAMPLE_FN uint32_t top_logprobs_keys(const float* v, uint64_t n, uint32_t a, uint64_t* keys) {
+    const uint32_t ae = top_logprobs_count(a, n);
+    top_logprobs_walk(v, 0, n, ae, keys);
+    return ae;
+}
+
+// The sliced form, what the kernel evaluates. heads: `slices` (<= kSampleMaxSlices) lists of kTopLogprobsMax keys — list l the FIRST
+// 64 keys of the sorted list of slice l, 0 behind the last of a shorter slice. The a_eff largest of all heads, descending, go
+// to keys[0, a_eff).
+//   Why the heads are enough: let x be one of the row's 64 largest keys and l its slice. Every key of slice l above x is a key of
+//   the row above x, and there are at most 63 of those: x is among the first 64 keys of list l. So the row's 64 largest keys all
+//   lie in the heads, they are the 64 largest keys there (the heads hold keys of the row and pads 0, which lie below every
+//   key), and a_eff <= 64 of them are what the direct form finds. Keys are unique: the merge's order of work cannot matter.
+ZGML_SAMPLE_FN uint32_t top_logprobs_merge(const uint64_t* heads, uint32_t slices, uint64_t n, uint32_t a, uint64_t* keys) {
+    const uint32_t ae = top_logprobs_count(a, n);
+    uint32_t at[kSampleMaxSlices];
+    for (uint32_t l = 0; l < slices; l++) at[l] = 0;
+    for (uint32_t j = 0; j < ae; j++) {
+        uint64_t best = 0;
+        uint32_t from = 0;
+        for (uint32_t l = 0; l < slices; l++)
+            if (at[l] < kTopLogprobsMax && heads[l * kTopLogprobsMax + at[l]] > best) best = heads[l * kTopLogprobsMax + at[l]], from = l;
+        keys[j] = best, at[from] += 1; // (best > 0: the heads hold at least min(64, n) keys of the row)
+    }
+    return ae;
+}
+
+// ... over a row cut into `slices` (<= kSampleMaxSlices) slices of `len` logits, slices * len >= n: the heads, then the merge
+ZGML_SAMPLE_FN uint32_t top_logprobs_keys_cut(const float* v, uint64_t n, uint32_t a, uint32_t slices, uint32_t len, uint64_t* keys, uint64_t* heads /* [32 * 64] */) {
+    for (uint32_t l = 0; l < slices; l++) {
+        const uint64_t lo = (uint64_t)l * len, hi = lo + len < n ? lo + len : n;
+        top_logprobs_walk(v, lo < n ? lo : n, hi, kTopLogprobsMax, heads + l * kTopLogprobsMax); // (lo may lie behind n: an empty slice, all pads)
+    }
+    return top_logprobs_merge(heads, slices, n, a, keys);
+}
+
+// ... as the select launch cuts it
+ZGML_SAMPLE_FN uint32_t top_logprobs_keys_sliced(const float* v, uint64_t n, uint32_t a, uint64_t* keys, uint64_t* heads /* [32 * 64] */) {
+    return top_logprobs_keys_cut(v, n, a, sample_slices(n), sample_slice_len(n), keys, heads);
+}
+
+// entry j of a row from its key: the token and its value under the row's M and S
+ZGML_SAMPLE_FN void top_logprobs_entry(uint64_t key, float M, float S, uint32_t* token, float* value) {
+    *token = sample_key_index(key);
+    *value = logprob_of(sample_key_value(key), M, S);
 }
 
 } // namespace zgml

@@ -194,6 +194,12 @@ void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uin
     sample_merge_pick_kernel<<<dim3(1, rows), kMergeBlock, 0, s>>>(scratch, (uint32_t)n, slices, P, params, adv);
 }
 
+void launch_sample_select(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch) {
+    if (!n || n > 0xFFFFFFFFull || !rows) return; // (the callers refuse these)
+    const uint32_t slices = sample_slices(n);
+    sample_select_kernel<<<dim3(slices, rows), kSelBlock, 0, s>>>(v, (uint32_t)n, sample_slice_len(n), scratch);
+}
+
 void launch_sample_penalized(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
                              const SampleAdvance& adv, const SampleWindow& win) {
     if (!n || n > 0xFFFFFFFFull || !rows) return; // (the callers refuse these)

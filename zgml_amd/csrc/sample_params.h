@@ -1,6 +1,7 @@
 // sample_params.h — what include/zgml_hip.h refuses of the penalty fields and of the `logprobs` field of a zgml_sampling, and of the
-// arguments of zgml_hip_logprobs, as pure host logic: the runtime (runtime_resident.hip) and the CPU probes
-// tests/cpp/penalty_probe.cpp and tests/cpp/logprob_probe.cpp compile these functions.
+// arguments of zgml_hip_logprobs and zgml_hip_top_logprobs, and how the `top_logprobs` word is read, as pure host logic: the
+// runtime (runtime_resident.hip) and the CPU probes tests/cpp/penalty_probe.cpp, tests/cpp/logprob_probe.cpp and
+// tests/cpp/top_logprob_probe.cpp compile these functions.
 #pragma once
 
 #include <math.h>
@@ -46,6 +47,24 @@ inline const char* logprobs_check(uint64_t buf_size, uint64_t offset, uint64_t n
 // ... and what the `logprobs` word of a zgml_sampling asks of the row length of the entry point it is handed to
 inline const char* sample_logprobs_check(const zgml_sampling* sp, uint64_t n) {
     if (sp->logprobs && n > kLogprobMaxN) return "logprobs needs a row of at most 2^20 elements";
+    return nullptr;
+}
+
+// the `top_logprobs` word as the kernels read it: only with `logprobs` set, and a value above kTopLogprobsMax as that — the word
+// was padding before, so it is clamped, never refused
+inline uint32_t sample_top_logprobs(const zgml_sampling* sp) {
+    if (!sp->logprobs) return 0;
+    return sp->top_logprobs > kTopLogprobsMax ? kTopLogprobsMax : sp->top_logprobs;
+}
+
+// What zgml_hip_top_logprobs refuses: everything logprobs_check refuses of n, rows, the range and NULL pointers, and — a new
+// argument, so refused, not clamped — top_n outside 1 .. kTopLogprobsMax
+inline const char* top_logprobs_check(uint64_t buf_size, uint64_t offset, uint64_t n, uint32_t rows, uint32_t top_n, const int64_t* tokens_out, const float* out) {
+    if (!tokens_out || !out) return "tokens_out and logprobs_out must not be NULL";
+    if (!n || n > kLogprobMaxN) return "a row must hold 1 .. 2^20 elements";
+    if (!rows) return "rows must be at least 1";
+    if (!buf_size || offset > buf_size || n * (uint64_t)rows > buf_size - offset) return "the rows must lie inside the buffer";
+    if (!top_n || top_n > kTopLogprobsMax) return "top_n must be 1 .. 64";
     return nullptr;
 }
 

@@ -101,23 +101,36 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
         if (lane == 0) g[j] = (uint64_t)bi < a.vocab ? (uint32_t)bi : 0u; // (a row always has vocab > 0 entries: the clamp is for the embedding gather's sake)
     }
     __syncthreads();
-    if (threadIdx.x != 0) return;
-    const uint32_t pos = w[kSpecPos];
-    const uint32_t acc = spec_accept(a.cand, g, a.T);
-    uint32_t m = spec_emit_count(acc, wanted, produced);
-    bool stopped = false;
-    if (a.sparams) m = spec_stop_cut(g, m, a.sparams->n_stop, a.sparams->stop, &stopped); // (read in place, as the merge kernel does)
-    for (uint32_t k = 0; k < m; k++) {
-        if (produced + k < a.tokens_cap) a.tokens[produced + k] = (int64_t)g[k];
-        if (a.lp_out && produced + k < a.tokens_cap) a.lp_out[produced + k] = a.lp_rows[k];
-        if (pos + 1 + k < a.hist_cap) a.hist[pos + 1 + k] = g[k];
+    __shared__ uint32_t emitted; // (the form with alternatives only) m, for the copy below
+    if (threadIdx.x == 0) {
+        const uint32_t pos = w[kSpecPos];
+        const uint32_t acc = spec_accept(a.cand, g, a.T);
+        uint32_t m = spec_emit_count(acc, wanted, produced);
+        bool stopped = false;
+        if (a.sparams) m = spec_stop_cut(g, m, a.sparams->n_stop, a.sparams->stop, &stopped); // (read in place, as the merge kernel does)
+        for (uint32_t k = 0; k < m; k++) {
+            if (produced + k < a.tokens_cap) a.tokens[produced + k] = (int64_t)g[k];
+            if (a.lp_out && produced + k < a.tokens_cap) a.lp_out[produced + k] = a.lp_rows[k];
+            if (pos + 1 + k < a.hist_cap) a.hist[pos + 1 + k] = g[k];
+        }
+        w[kSpecTok] = g[m - 1];
+        w[kSpecPos] = pos + m;
+        w[kSpecProduced] = produced + m;
+        if (stopped) w[kSpecWanted] = produced + m; // the call is finished
+        w[kSpecSteps] += 1;
+        w[kSpecAccepted] += acc;
+        emitted = m;
     }
-    w[kSpecTok] = g[m - 1];
-    w[kSpecPos] = pos + m;
-    w[kSpecProduced] = produced + m;
-    if (stopped) w[kSpecWanted] = produced + m; // the call is finished
-    w[kSpecSteps] += 1;
-    w[kSpecAccepted] += acc;
+    if (!a.top_tok_out) return; // (uniform)
+    // the alternatives of the emitted tokens next to them: row k's 64 pairs to entry produced + k, all threads
+    __syncthreads();
+    const uint32_t m = emitted;
+    for (uint32_t i = threadIdx.x; i < m * kTopLogprobsMax; i += kSpecBlock) {
+        const uint32_t k = i / kTopLogprobsMax, j = i % kTopLogprobsMax;
+        if (produced + k >= a.tokens_cap) continue;
+        a.top_tok_out[(uint64_t)(produced + k) * kTopLogprobsMax + j] = a.top_rows_tok[i];
+        a.top_val_out[(uint64_t)(produced + k) * kTopLogprobsMax + j] = a.top_rows_val[i];
+    }
 }
 
 } // namespace

@@ -268,11 +268,13 @@ class BatchSession:
             raise RuntimeError("resident_decode_batch: " + self._backend.last_error())
         return toks[:, :max_steps]
 
-    def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None):
+    def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None, top_logprobs=None):
         """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
         -> (tokens[B, max(n_steps)], n_produced[B]); row b holds n_produced[b] tokens, then -1. logprobs: True, or one flag per
         sequence: -> (tokens, n_produced, float32[B, max(n_steps)]), row b the log-probabilities of sequence b's tokens — NaN
-        behind them, and all through a row whose flag is off."""
+        behind them, and all through a row whose flag is off. top_logprobs: an int, or one per sequence (a count > 0 sets the
+        sequence's flag too): (int64[B, max(n_steps), width], float32[...]) is appended, the alternatives of every token — width
+        the largest effective count, -1 / NaN as padding and behind the tokens."""
         u32p = C.POINTER(C.c_uint32)
         t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
         n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_steps, dtype=np.uint32), (self.n_seqs,)))
@@ -282,17 +284,28 @@ class BatchSession:
         toks = np.full((self.n_seqs, max(1, max_steps)), -1, np.int64)
         produced = np.zeros(self.n_seqs, np.uint32)
         flags = [bool(logprobs)] * self.n_seqs if logprobs is None or isinstance(logprobs, bool) else [bool(x) for x in logprobs]
+        tops = [0] * self.n_seqs if top_logprobs is None else [int(top_logprobs)] * self.n_seqs if np.isscalar(top_logprobs) else [int(x) for x in top_logprobs]
+        assert len(tops) == self.n_seqs
+        flags = [f or a > 0 for f, a in zip(flags, tops)]
         for b in range(self.n_seqs):
             if flags[b]:
                 sp[b].logprobs = 1
+            if top_logprobs is not None:
+                sp[b].top_logprobs = tops[b]
         rc = capi.load_hip().zgml_hip_resident_decode_batch_sampled(self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p),
                                                                     n.ctypes.data_as(u32p), max_steps, sp, toks.ctypes.data, produced.ctypes.data_as(u32p))
         if rc != 0:
             raise RuntimeError("resident_decode_batch_sampled: " + self._backend.last_error())
-        if logprobs is None:
+        if logprobs is None and top_logprobs is None:
             return toks[:, :max_steps], produced
         lps = capi.logprobs_result(self._backend.ctx, (self.n_seqs, max_steps)) if any(flags) and max_steps else np.full((self.n_seqs, max_steps), np.nan, np.float32)
-        return toks[:, :max_steps], produced, lps
+        if top_logprobs is None:
+            return toks[:, :max_steps], produced, lps
+        if any(tops) and max_steps:
+            alts = capi.top_logprobs_result(self._backend.ctx, (self.n_seqs, max_steps))
+        else:
+            alts = np.full((self.n_seqs, max_steps, 0), -1, np.int64), np.full((self.n_seqs, max_steps, 0), np.nan, np.float32)
+        return toks[:, :max_steps], produced, lps, alts
 
     def close(self):
         if self.ptr:
@@ -368,20 +381,29 @@ class Session:
             raise RuntimeError("resident_decode: " + self._backend.last_error())
         return toks
 
-    def resident_decode_sampled(self, first_token: int, start_pos: int, n_steps: int, sampling: "capi.SamplingC", logprobs: bool = False):
+    def resident_decode_sampled(self, first_token: int, start_pos: int, n_steps: int, sampling: "capi.SamplingC", logprobs: bool = False, top_logprobs: int = 0):
         """zgml_hip_resident_decode_sampled -> (tokens[n_steps], n_produced): -1 behind a stop token. logprobs=True:
-        -> (tokens, n_produced, float32[n_steps]): every token's log-probability, NaN behind a stop token."""
+        -> (tokens, n_produced, float32[n_steps]): every token's log-probability, NaN behind a stop token. top_logprobs=a > 0:
+        (int64[n_steps, min(a, 64, vocab)], float32[...]) is appended: every token's alternatives, -1 / NaN behind a stop token."""
         toks = np.full(max(1, n_steps), -1, np.int64)
         produced = C.c_uint32(0)
-        if logprobs:
-            sampling = capi.with_logprobs(sampling)
+        if logprobs or top_logprobs:
+            sampling = capi.with_logprobs(sampling, top=top_logprobs)
         rc = capi.load_hip().zgml_hip_resident_decode_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_steps, C.byref(sampling),
                                                               toks.ctypes.data, C.byref(produced))
         if rc != 0:
             raise RuntimeError("resident_decode_sampled: " + self._backend.last_error())
-        if not logprobs:
+        if not logprobs and not top_logprobs:
             return toks[:n_steps], int(produced.value)
-        return toks[:n_steps], int(produced.value), (capi.logprobs_result(self._backend.ctx, n_steps) if n_steps else np.zeros(0, np.float32))
+        lps = capi.logprobs_result(self._backend.ctx, n_steps) if n_steps else np.zeros(0, np.float32)
+        if not top_logprobs:
+            return toks[:n_steps], int(produced.value), lps
+        return toks[:n_steps], int(produced.value), lps, self._alternatives(n_steps)
+
+    def _alternatives(self, entries: int):
+        if entries:
+            return capi.top_logprobs_result(self._backend.ctx, entries)
+        return np.zeros((0, 0), np.int64), np.zeros((0, 0), np.float32)
 
     def resident_prefill(self, tokens, start_pos: int) -> int:
         """One chunk of a token_len = N plan with on-device embedding gather / mask / RoPE rows / argmax."""
@@ -420,15 +442,16 @@ class Session:
         return toks, {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
 
     def resident_decode_speculative_sampled(self, first_token: int, start_pos: int, n_tokens: int, sampling: "capi.SamplingC", history=None,
-                                            drafts=None, ngram: int = 2, logprobs: bool = False):
+                                            drafts=None, ngram: int = 2, logprobs: bool = False, top_logprobs: int = 0):
         """zgml_hip_resident_decode_speculative_sampled: the verify step's rows are sampled (seeded top-k / top-p) instead of
         arg-maxed -> (tokens[n_tokens], n_produced, {"steps", "drafted", "accepted"}): -1 behind a stop token. `history`, `drafts`
         and `ngram` as resident_decode_speculative. logprobs=True: float32[n_tokens] is appended to the result: every emitted
-        token's log-probability, NaN behind a stop token."""
+        token's log-probability, NaN behind a stop token. top_logprobs=a > 0: (int64[n_tokens, min(a, 64, vocab)], float32[...]) is
+        appended too: every emitted token's alternatives under the row of the verify step that emitted it."""
         opt, keep = self._spec_opt(history, drafts, ngram)
         toks = np.full(max(1, n_tokens), -1, np.int64)
-        if logprobs:
-            sampling = capi.with_logprobs(sampling)
+        if logprobs or top_logprobs:
+            sampling = capi.with_logprobs(sampling, top=top_logprobs)
         stats, produced = capi.SpecStatsC(), C.c_uint32(0)
         rc = capi.load_hip().zgml_hip_resident_decode_speculative_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
                                                                            C.byref(sampling), toks.ctypes.data, C.byref(produced), C.byref(stats))
@@ -436,9 +459,12 @@ class Session:
         if rc != 0:
             raise RuntimeError("resident_decode_speculative_sampled: " + self._backend.last_error())
         st = {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
-        if not logprobs:
+        if not logprobs and not top_logprobs:
             return toks[:n_tokens], int(produced.value), st
-        return toks[:n_tokens], int(produced.value), st, (capi.logprobs_result(self._backend.ctx, n_tokens) if n_tokens else np.zeros(0, np.float32))
+        lps = capi.logprobs_result(self._backend.ctx, n_tokens) if n_tokens else np.zeros(0, np.float32)
+        if not top_logprobs:
+            return toks[:n_tokens], int(produced.value), st, lps
+        return toks[:n_tokens], int(produced.value), st, lps, self._alternatives(n_tokens)
 
     def close(self):
         if self.ptr:

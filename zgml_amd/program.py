@@ -516,16 +516,31 @@ class Backend:
     def argmax(self, handle, buf_idx: int, offset: int, n: int) -> int:
         return int(self._lib.zgml_hip_argmax(self.ctx, handle, buf_idx, offset, n))
 
-    def sample(self, handle, buf_idx: int, offset: int, n: int, sampling: "capi.SamplingC", position: int, logprobs: bool = False):
+    def sample(self, handle, buf_idx: int, offset: int, n: int, sampling: "capi.SamplingC", position: int, logprobs: bool = False, top_logprobs: int = 0):
         """zgml_hip_sample: -> (token, candidate indices in order), with logprobs=True -> (token, candidates, the token's
-        log-probability as numpy.float32). RuntimeError for what the library refuses."""
+        log-probability as numpy.float32), with top_logprobs=a > 0 -> (token, candidates, log-probability, alternatives' tokens
+        int64[min(a, 64, n)], their log-probabilities float32[...]). RuntimeError for what the library refuses."""
         cand, kc = (C.c_uint32 * 256)(), C.c_uint32(0)
-        if logprobs:
-            sampling = capi.with_logprobs(sampling)
+        if logprobs or top_logprobs:
+            sampling = capi.with_logprobs(sampling, top=top_logprobs)
         tok = int(self._lib.zgml_hip_sample(self.ctx, handle, buf_idx, offset, n, C.byref(sampling), position, cand, C.byref(kc)))
         if tok < 0:
             raise RuntimeError("sample: " + self.last_error())
+        if top_logprobs:
+            alt, val = capi.top_logprobs_result(self.ctx, 1)
+            return tok, list(cand[:kc.value]), capi.logprobs_result(self.ctx, 1)[0], alt[0], val[0]
         return (tok, list(cand[:kc.value]), capi.logprobs_result(self.ctx, 1)[0]) if logprobs else (tok, list(cand[:kc.value]))
+
+    def top_logprobs(self, handle, buf_idx: int, offset: int, n: int, rows: int, top_n: int):
+        """zgml_hip_top_logprobs: (tokens int64[rows, top_n], values float32[rows, top_n]): row i's min(top_n, n) largest logits, value
+        descending, with their log-probabilities; -1 / NaN behind them. RuntimeError for what the library refuses."""
+        tok = np.full((max(1, rows), max(1, top_n)), -1, np.int64)
+        val = np.full(tok.shape, np.nan, np.float32)
+        rc = self._lib.zgml_hip_top_logprobs(self.ctx, handle, buf_idx, offset, n, rows, top_n, tok.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             val.ctypes.data_as(C.POINTER(C.c_float)))
+        if rc != 0:
+            raise RuntimeError("top_logprobs: " + self.last_error())
+        return tok[:rows, :top_n], val[:rows, :top_n]
 
     def logprobs(self, handle, buf_idx: int, offset: int, n: int, tokens) -> np.ndarray:
         """zgml_hip_logprobs: float32[rows], entry i = log softmax(row i)[tokens[i]] over the rows of n elements that start at
