@@ -824,6 +824,50 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
                                                  int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
                                                  zgml_spec_stats* stats /* may be NULL */);
 
+/* ── Constrained decoding: a token automaton masks the sampled picks on the device (rule: zgml_amd/csrc/sample.h, THE CONSTRAINT).
+ * The caller brings the table, in class-compressed form: class_of[i] is the class of token i, next[s][c] the state behind a
+ * token of class c in state s, 0xFFFF where such a token is not allowed in s. There is no grammar compiler here and no additive
+ * logit bias.
+ * Rule. A token that is not allowed in the sequence's current state is no candidate at all: the candidates are the
+ *   min(top_k, number of allowed tokens) largest logits among the allowed ones, the pick and its random number are unchanged, and
+ *   penalties apply to the allowed tokens as ever. top_k = 1 is constrained greedy decoding. Behind every pick the state becomes
+ *   next[state][class_of[token]]; a stop token advances it too. The state lives on the device and persists across calls: two
+ *   calls give the stream of one. A state that allows no token produces nothing: in the loops the sequence freezes as behind a
+ *   stop token (tokens_out keeps -1, *n_produced does not count a token, the state stays); zgml_hip_sample returns -1 with an
+ *   error on the context. Log-probabilities and alternatives (`logprobs`, `top_logprobs`) are over the RAW row, unaffected by the
+ *   constraint exactly as they are unaffected by penalties.
+ * Who honours it. zgml_hip_resident_decode_sampled and _batch_sampled: every batched sequence has its own automaton and state,
+ *   sequences with and without one side by side; a constrained call replays graphs of its own, so calls with and without a
+ *   constraint alternate on one program and invalidate nothing, and a call without one launches exactly what it launched before.
+ *   zgml_hip_sample honours it when n equals the automaton's vocab: it uses sequence 0's state and advances it over the returned
+ *   token (resident prefill, zgml_hip_sample for the first token, then the sampled loop: no host bookkeeping), and
+ *   candidates_out receives the constrained candidates. zgml_hip_resident_prefill is unchanged: the greedy token it returns is
+ *   unconstrained.
+ * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
+ *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled and zgml_hip_shard_step return -1 with an
+ *   error on the context and enqueue nothing: they would pick tokens while ignoring the constraint. (A later change can give row
+ *   j of a verify step the state reached by walking its candidates.) */
+typedef struct zgml_token_dfa {
+    uint32_t n_states, n_classes, vocab, _pad; /* 1 <= n_states <= 65535, 1 <= n_classes <= 8192 */
+    const uint16_t* class_of;                  /* [vocab], every entry < n_classes */
+    const uint16_t* next;                      /* [n_states][n_classes], 0xFFFF: not allowed, else < n_states */
+} zgml_token_dfa;
+typedef struct zgml_hip_constraint zgml_hip_constraint;
+/* Validates the automaton and uploads it once; it may then be attached to any number of sequences of any programs of the
+ * context. NULL with an error on the context, before anything is uploaded: a NULL table, sizes outside the limits, a class
+ * >= n_classes, a next state >= n_states that is not 0xFFFF. */
+zgml_hip_constraint* zgml_hip_constraint_create(zgml_hip_ctx* ctx, const zgml_token_dfa* dfa);
+/* Frees it; a constraint that is still attached to a sequence is refused (an error on the context, nothing freed): detach first.
+ * Freeing a program, or setting it up again, detaches its sequences. */
+void zgml_hip_constraint_free(zgml_hip_ctx* ctx, zgml_hip_constraint* constraint);
+/* Attaches `constraint` to sequence `seq` of a program after zgml_hip_resident_setup (seq 0 of a plain plan) with the sequence's
+ * state set to `state`; constraint = NULL detaches (state is ignored). Blocking. Returns 0; -1 with an error on the context
+ * and nothing changed: no resident set-up, seq >= the number of sequences, a vocab different from the program's,
+ * state >= n_states. */
+int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t seq, zgml_hip_constraint* constraint, uint32_t state);
+/* The sequence's current state (a blocking read); -1: none attached (or seq out of range, no resident set-up). */
+int64_t zgml_hip_program_constraint_state(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t seq);
+
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];
  * otherwise int8), runs `warmup` + `iters` launches round-robin over the ring and returns the

@@ -269,6 +269,26 @@ def top_logprobs_result(ctx, entries_shape):
     return tok, val
 
 
+class TokenDfaC(C.Structure):
+    """zgml_token_dfa (include/zgml_hip.h): a token automaton in class-compressed form."""
+    _fields_ = [("n_states", C.c_uint32), ("n_classes", C.c_uint32), ("vocab", C.c_uint32), ("_pad", C.c_uint32),
+                ("class_of", C.POINTER(C.c_uint16)), ("next", C.POINTER(C.c_uint16))]
+
+    @staticmethod
+    def of(class_of, next_table, n_states: int = None, n_classes: int = None, vocab: int = None) -> "TokenDfaC":
+        """class_of: uint16[vocab]; next_table: uint16[n_states, n_classes], 0xFFFF = not allowed. The sizes default to the
+        arrays' (hand over others for the library to refuse); the arrays live as long as the structure."""
+        import numpy as np
+        cls = np.ascontiguousarray(class_of, np.uint16).reshape(-1)
+        nxt = np.ascontiguousarray(next_table, np.uint16)
+        d = TokenDfaC(n_states=nxt.shape[0] if n_states is None else n_states, n_classes=(nxt.shape[1] if nxt.ndim == 2 else 0) if n_classes is None else n_classes,
+                      vocab=cls.size if vocab is None else vocab)
+        d._keep = (cls, nxt)
+        d.class_of = cls.ctypes.data_as(C.POINTER(C.c_uint16))
+        d.next = nxt.ctypes.data_as(C.POINTER(C.c_uint16))
+        return d
+
+
 class RuntimeProfileC(C.Structure):
     _fields_ = [("time_ns", C.c_uint64 * 12), ("backend_op_count", C.c_uint64),
                 ("fallback_op_count", C.c_uint64), ("backend_dispatch_count", C.c_uint64),
@@ -296,6 +316,7 @@ HIP_SYMBOLS = [
     "zgml_hip_sample", "zgml_hip_resident_decode_sampled", "zgml_hip_resident_decode_batch_sampled",
     "zgml_hip_resident_decode_speculative_sampled", "zgml_hip_logprobs", "zgml_hip_logprobs_result",
     "zgml_hip_top_logprobs", "zgml_hip_top_logprobs_result",
+    "zgml_hip_constraint_create", "zgml_hip_constraint_free", "zgml_hip_program_set_constraint", "zgml_hip_program_constraint_state",
 ]
 
 class ShardPointC(C.Structure):
@@ -443,6 +464,15 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_top_logprobs.argtypes = [vp, vp, C.c_uint16, u64, u64, u32, u32, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
         lib.zgml_hip_top_logprobs_result.restype = C.c_int64
         lib.zgml_hip_top_logprobs_result.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_float), u64, C.POINTER(u32)]
+    if hasattr(lib, "zgml_hip_constraint_create"):  # absent from an older build loaded beside this one (tools/constraint_decode_run.py)
+        lib.zgml_hip_constraint_create.restype = vp
+        lib.zgml_hip_constraint_create.argtypes = [vp, C.POINTER(TokenDfaC)]
+        lib.zgml_hip_constraint_free.restype = None
+        lib.zgml_hip_constraint_free.argtypes = [vp, vp]
+        lib.zgml_hip_program_set_constraint.restype = i32
+        lib.zgml_hip_program_set_constraint.argtypes = [vp, vp, u32, vp, u32]
+        lib.zgml_hip_program_constraint_state.restype = C.c_int64
+        lib.zgml_hip_program_constraint_state.argtypes = [vp, vp, u32]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

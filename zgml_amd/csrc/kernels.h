@@ -528,6 +528,18 @@ struct SampleWindow {
     const uint32_t* cand = nullptr;
     const uint32_t* lo_word = nullptr;
 };
+// The constraint of row b (sample.h: THE CONSTRAINT), read by the constrained select launch and by the advance of the merge
+// launch: a table beside SampleParamsDev's, uploaded when a constraint is attached or detached, and the rows' state words, which
+// live on the device next to the loop's state and are known at replay time only. rows == nullptr: no row has a constraint.
+struct SampleConstraintRow {
+    const uint16_t* class_of; // [vocab]
+    const uint16_t* next;     // [n_states][n_classes]
+    uint32_t n_classes, con_active; // con_active = 0: the row has no constraint (a batched sequence without one beside others)
+};
+struct SampleConstraint {
+    const SampleConstraintRow* rows = nullptr;
+    uint32_t* state = nullptr; // [rows]
+};
 // (kSampleMaxSlices, kSampleChunk and sample_slices(n): sample.h, where the rule of the alternatives needs them too)
 inline size_t sample_scratch_keys(uint64_t n, uint32_t rows) { return (size_t)rows * sample_slices(n) * 256; }
 // `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select: sample_slices(n) sorted lists of the 256 largest keys per row]
@@ -537,6 +549,11 @@ void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uin
 // penalised form (a kernel of its own), the second as it is
 void launch_sample_penalized(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
                              const SampleAdvance& adv, const SampleWindow& win);
+// ... with the rows' constraints as well: the first launch in its constrained form (a kernel of its own, which also serves rows
+// without a constraint and rows with or without penalties), the second as it is, advancing the state words behind the pick.
+// Not for the rows of a verify step (adv.picks)
+void launch_sample_constrained(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
+                               const SampleAdvance& adv, const SampleWindow& win, const SampleConstraint& con);
 // ── log softmax(row)[token] (logprob.hip; the rule is sample.h's) ──
 // [partial]: (m_b, s_b) of every block of 4096 logits of `rows` rows of n logits (row stride n), 1 <= n <= 2^20, into
 // part[rows][logprob_blocks(n)][2]. It reads the logits alone: it may run before or behind the pick.

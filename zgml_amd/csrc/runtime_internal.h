@@ -334,4 +334,5 @@ void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx); // a buffer writ
 // runtime_resident.hip
 void free_resident_graph(zgml_hip_program* p); // the resident loops' captured graphs (they bake the plan: free_graph calls this)
 void free_resident(zgml_hip_program* p);       // p->resident and everything it owns
+bool has_constraint(const zgml_hip_program* p); // a token automaton is attached to one of its sequences (zgml_hip_program_set_constraint)
 } // namespace zgml_rt

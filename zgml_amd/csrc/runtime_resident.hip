@@ -8,6 +8,17 @@
 #include "sample_params.h"
 #include "spec.h"
 
+// the forms of the sampled loops' step: the select launch, and what follows the pick. The constrained select kernel serves rows
+// with and without penalties, so a constrained call has one graph per kind
+enum SampledSel { kSelPlain, kSelPenalized, kSelConstrained, kSampledSels };
+enum SampledKind { kKindPick, kKindLogprobs, kKindTop, kSampledKinds };
+constexpr uint32_t kSampledForms = kSampledSels * kSampledKinds;
+constexpr uint32_t sampled_form(uint32_t sel, uint32_t kind) { return kind * kSampledSels + sel; }
+// the names the graphs are captured under: prefix + one of these
+static const char* const kSampledFormNames[kSampledForms] = {"sampled", "penalized", "constrained", "sampled_logprobs", "penalized_logprobs", "constrained_logprobs",
+                                                             "sampled_top", "penalized_top", "constrained_top"};
+
+struct zgml_hip_constraint;
 struct zgml_resident {
     float *embed = nullptr, *cos = nullptr, *sin = nullptr;
     uint32_t vocab = 0, d = 0, max_seq = 0, dh = 0, n_rope = 0;
@@ -47,14 +58,14 @@ struct zgml_resident {
     // step reads parameter row 0 alone); the loop's own graph (the greedy loop's stays valid beside it)
     SampleParamsDev* sparams = nullptr;
     uint64_t* skeys = nullptr;
-    hipGraph_t graph_sampled = nullptr;
-    hipGraphExec_t graph_sampled_exec = nullptr;
+    // The sampled loops' graphs, one per form — what the select launch is (SampledSel) times what follows the pick (SampledKind):
+    // the forms alternate on one program and invalidate nothing. sampled_form() indexes them
+    hipGraph_t sgraph[kSampledForms] = {};
+    hipGraphExec_t sgraph_exec[kSampledForms] = {};
     // penalised sampled tail (sample.h: the penalties), allocated by the first such call of the single or the batched loop: the
     // window of every sequence, [n_seqs][256] token words indexed by position & 255, then lo per sequence (the verify step reads
     // hist / cand instead); the penalised loops' own graph, beside the other two
     uint32_t* swin = nullptr;
-    hipGraph_t graph_penalized = nullptr;
-    hipGraphExec_t graph_penalized_exec = nullptr;
     // log-probabilities of the sampled tail (the `logprobs` field of zgml_sampling; logprob.hip), allocated by the first such call:
     // the block pairs of every logits row, the values next to the produced tokens ([lp_cap]: the layout of tokens / btokens), the
     // T row values of a verify step, the "written up to" word of every sequence; the loops' own graphs, plain and penalised,
@@ -62,8 +73,6 @@ struct zgml_resident {
     float *lpart = nullptr, *lp = nullptr, *lp_rows = nullptr;
     uint32_t* lp_written = nullptr;
     uint64_t lp_cap = 0;
-    hipGraph_t graph_sampled_lp = nullptr, graph_penalized_lp = nullptr;
-    hipGraphExec_t graph_sampled_lp_exec = nullptr, graph_penalized_lp_exec = nullptr;
     // the alternatives of the sampled tail (the `top_logprobs` word of zgml_sampling; top_logprob.hip), allocated by the first such
     // call: the lists of a select over the RAW rows (what a penalised step needs beside skeys, the same size), the pairs next to
     // the produced tokens ([top_cap][64], the layout of lp), the T rows' pairs of a verify step; the loops' own graphs, "sampled +
@@ -72,10 +81,22 @@ struct zgml_resident {
     uint32_t *top_tok = nullptr, *top_rows_tok = nullptr;
     float *top_val = nullptr, *top_rows_val = nullptr;
     uint64_t top_cap = 0;
-    hipGraph_t graph_sampled_top = nullptr, graph_penalized_top = nullptr;
-    hipGraphExec_t graph_sampled_top_exec = nullptr, graph_penalized_top_exec = nullptr;
+    // constrained sampled tail (sample.h: THE CONSTRAINT; zgml_hip_program_set_constraint), allocated by the first attachment: what
+    // is attached to every sequence (one entry for a plain plan), the device table the kernels read (kernels.h:
+    // SampleConstraintRow, uploaded at every attach / detach) and the sequences' state words, which the merge launch advances
+    std::vector<zgml_hip_constraint*> con;
+    uint32_t n_con = 0; // attached sequences
+    SampleConstraintRow* con_rows = nullptr;
+    uint32_t* con_state = nullptr;
 };
 using Resident = zgml_resident;
+
+// an uploaded token automaton (zgml_hip_constraint_create)
+struct zgml_hip_constraint {
+    uint32_t n_states = 0, n_classes = 0, vocab = 0;
+    uint32_t attached = 0; // sequences it is attached to: it is not freed before that is 0
+    uint16_t *class_of = nullptr, *next = nullptr; // device
+};
 
 namespace zgml_rt {
 
@@ -88,24 +109,11 @@ void free_resident_graph(zgml_hip_program* p) {
     if (r->graph_multi_exec) hipGraphExecDestroy(r->graph_multi_exec);
     if (r->graph_multi) hipGraphDestroy(r->graph_multi);
     r->graph_multi_exec = nullptr, r->graph_multi = nullptr, r->multi_n = 0;
-    if (r->graph_sampled_exec) hipGraphExecDestroy(r->graph_sampled_exec);
-    if (r->graph_sampled) hipGraphDestroy(r->graph_sampled);
-    r->graph_sampled_exec = nullptr, r->graph_sampled = nullptr;
-    if (r->graph_penalized_exec) hipGraphExecDestroy(r->graph_penalized_exec);
-    if (r->graph_penalized) hipGraphDestroy(r->graph_penalized);
-    r->graph_penalized_exec = nullptr, r->graph_penalized = nullptr;
-    if (r->graph_sampled_lp_exec) hipGraphExecDestroy(r->graph_sampled_lp_exec);
-    if (r->graph_sampled_lp) hipGraphDestroy(r->graph_sampled_lp);
-    r->graph_sampled_lp_exec = nullptr, r->graph_sampled_lp = nullptr;
-    if (r->graph_penalized_lp_exec) hipGraphExecDestroy(r->graph_penalized_lp_exec);
-    if (r->graph_penalized_lp) hipGraphDestroy(r->graph_penalized_lp);
-    r->graph_penalized_lp_exec = nullptr, r->graph_penalized_lp = nullptr;
-    if (r->graph_sampled_top_exec) hipGraphExecDestroy(r->graph_sampled_top_exec);
-    if (r->graph_sampled_top) hipGraphDestroy(r->graph_sampled_top);
-    r->graph_sampled_top_exec = nullptr, r->graph_sampled_top = nullptr;
-    if (r->graph_penalized_top_exec) hipGraphExecDestroy(r->graph_penalized_top_exec);
-    if (r->graph_penalized_top) hipGraphDestroy(r->graph_penalized_top);
-    r->graph_penalized_top_exec = nullptr, r->graph_penalized_top = nullptr;
+    for (uint32_t f = 0; f < kSampledForms; f++) {
+        if (r->sgraph_exec[f]) hipGraphExecDestroy(r->sgraph_exec[f]);
+        if (r->sgraph[f]) hipGraphDestroy(r->sgraph[f]);
+        r->sgraph_exec[f] = nullptr, r->sgraph[f] = nullptr;
+    }
 }
 
 void free_resident(zgml_hip_program* p) {
@@ -143,13 +151,33 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->top_rows_tok);
     hipFree(r->top_val);
     hipFree(r->top_rows_val);
+    for (zgml_hip_constraint* c : r->con)
+        if (c) c->attached -= 1; // (a program that goes detaches its sequences)
+    hipFree(r->con_rows);
+    hipFree(r->con_state);
     delete r;
     p->resident = nullptr;
 }
 
+bool has_constraint(const zgml_hip_program* p) { return p && p->resident && p->resident->n_con != 0; }
+
 } // namespace zgml_rt
 
 namespace {
+
+// what the entry points that would pick tokens while ignoring an attached constraint say (include/zgml_hip.h); true: refused
+bool refuse_constrained(zgml_hip_ctx* ctx, const zgml_hip_program* p, const char* who) {
+    if (!has_constraint(p)) return false;
+    ctx->fail(std::string(who) + ": a constraint is attached to the program (only zgml_hip_resident_decode_sampled, _batch_sampled and zgml_hip_sample honour one: detach it first)");
+    return true;
+}
+
+// the constraint arguments of a sampled launch over the program's sequences (none attached: no rows, the other launches)
+SampleConstraint constraint_args(const Resident* r) {
+    SampleConstraint c;
+    if (r->n_con) c.rows = r->con_rows, c.state = r->con_state;
+    return c;
+}
 
 // would every moving op stay inside the bounds the batched plan assumed with its sequence at position pos_of(op index), T token
 // rows per step? (The device patches the words itself, resident_prep_kernel: nothing else would notice a position outside them.)
@@ -440,6 +468,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
                              uint32_t n_steps, int64_t* tokens_out) {
     if (!ctx || !p || !p->resident || !tokens_out) return -1;
     Resident* r = p->resident;
+    if (refuse_constrained(ctx, p, "resident_decode")) return -1;
     if (r->n_seqs) {
         ctx->fail("resident_decode: the program is a batched plan (sequences declared: use zgml_hip_resident_decode_batch)");
         return -1;
@@ -528,6 +557,7 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
         return -1;
     }
     if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
+    if (refuse_constrained(ctx, p, "resident_decode_batch")) return -1;
     const uint32_t B = r->n_seqs;
     uint32_t steps = 0;
     for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
@@ -624,12 +654,20 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
     SampleAdvance adv;
     adv.position = position, adv.out = (int64_t*)ctx->smp_out, adv.cand = ctx->smp_out + 2;
+    // sequence 0's constraint, when the row is a row of the automaton's vocabulary: its state masks the pick and advances over it
+    const Resident* const res = p->resident;
+    const bool constrained = res && res->n_con && res->con[0] && n == res->vocab;
+    const bool raw_select = sp.pen_active || constrained; // (the alternatives: the pick's lists are not the raw row's)
+    SampleWindow win;
     if (sp.pen_active) { // the window: the last W of the recent tokens, the token whose logits these are last
         const uint32_t take = std::min(sampling->n_recent, sp.window);
         if (!ctx->smp_win && !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_win, kSamplePenaltyMaxWindow * 4))) return -1;
         if (take && !CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_win, sampling->recent + (sampling->n_recent - take), (size_t)take * 4, hipMemcpyHostToDevice, s))) return -1;
-        SampleWindow win;
         win.list = ctx->smp_win, win.n_list = take;
+    }
+    if (constrained) {
+        launch_sample_constrained(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv, win, constraint_args(res));
+    } else if (sp.pen_active) {
         launch_sample_penalized(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv, win);
     } else {
         launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
@@ -644,8 +682,8 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
         if (top) { // the alternatives: from the pick's own lists, or — penalties have changed those — from a select over the raw row
             TopLogprobTarget tt;
             tt.chosen = lt, tt.top_tok = ctx->top_tok, tt.top_val = ctx->top_val, tt.params = ctx->smp_params;
-            if (sp.pen_active) launch_sample_select(s, p->bufs[buf_idx] + offset, n, 1, ctx->top_keys);
-            launch_logprob_finish_top(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, sp.pen_active ? ctx->top_keys : ctx->smp_keys, tt);
+            if (raw_select) launch_sample_select(s, p->bufs[buf_idx] + offset, n, 1, ctx->top_keys);
+            launch_logprob_finish_top(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, raw_select ? ctx->top_keys : ctx->smp_keys, tt);
             top_tok.resize(kTopLogprobsMax), top_val.resize(kTopLogprobsMax);
             hipMemcpyAsync(top_tok.data(), ctx->top_tok, kTopLogprobsMax * 4, hipMemcpyDeviceToHost, s);
             hipMemcpyAsync(top_val.data(), ctx->top_val, kTopLogprobsMax * sizeof(float), hipMemcpyDeviceToHost, s);
@@ -664,7 +702,85 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     if (candidates_out) memcpy(candidates_out, got + 3, (size_t)kc * 4);
     int64_t token;
     memcpy(&token, got, 8);
+    if (token < 0) ctx->fail("sample: the constraint's state allows no token");
     return token;
+}
+
+// ── the constraint (contract: include/zgml_hip.h; rule: sample.h; validation: sample_params.h) ──
+
+zgml_hip_constraint* zgml_hip_constraint_create(zgml_hip_ctx* ctx, const zgml_token_dfa* dfa) {
+    if (!ctx) return nullptr;
+    if (const char* why = constraint_check(dfa)) {
+        ctx->fail(std::string("constraint_create: ") + why);
+        return nullptr;
+    }
+    hipSetDevice(ctx->device);
+    zgml_hip_constraint* c = new zgml_hip_constraint();
+    c->n_states = dfa->n_states, c->n_classes = dfa->n_classes, c->vocab = dfa->vocab;
+    const size_t cls = (size_t)dfa->vocab * 2, nxt = (size_t)dfa->n_states * dfa->n_classes * 2;
+    if (!CTX_CHECK(ctx, hipMalloc((void**)&c->class_of, cls)) || !CTX_CHECK(ctx, hipMalloc((void**)&c->next, nxt)) ||
+        !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->class_of, dfa->class_of, cls)) || !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->next, dfa->next, nxt))) {
+        hipFree(c->class_of), hipFree(c->next);
+        delete c;
+        return nullptr;
+    }
+    return c;
+}
+
+void zgml_hip_constraint_free(zgml_hip_ctx* ctx, zgml_hip_constraint* c) {
+    if (!ctx || !c) return;
+    if (c->attached) {
+        ctx->fail("constraint_free: the constraint is still attached to " + std::to_string(c->attached) + " sequence(s) (detach it first)");
+        return;
+    }
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    hipFree(c->class_of), hipFree(c->next);
+    delete c;
+}
+
+int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t seq, zgml_hip_constraint* c, uint32_t state) {
+    if (!ctx || !p) return -1;
+    Resident* r = p->resident;
+    if (!r) {
+        ctx->fail("program_set_constraint: the program has no resident set-up (zgml_hip_resident_setup first)");
+        return -1;
+    }
+    const uint32_t rows = r->n_seqs ? r->n_seqs : 1;
+    if (const char* why = constraint_attach_check(c ? c->vocab : r->vocab, c ? c->n_states : 1, r->vocab, rows, seq, c ? state : 0)) {
+        ctx->fail(std::string("program_set_constraint: ") + why);
+        return -1;
+    }
+    if (!c && (r->con.empty() || !r->con[seq])) return 0; // nothing attached, nothing to detach
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    if (!r->con_rows && (!CTX_CHECK(ctx, hipMalloc((void**)&r->con_rows, (size_t)rows * sizeof(SampleConstraintRow))) ||
+                         !CTX_CHECK(ctx, hipMalloc((void**)&r->con_state, (size_t)rows * 4)) || !CTX_CHECK(ctx, hipMemset(r->con_state, 0, (size_t)rows * 4))))
+        return -1;
+    r->con.resize(rows, nullptr);
+    if (r->con[seq]) r->con[seq]->attached -= 1, r->n_con -= 1;
+    r->con[seq] = c;
+    if (c) c->attached += 1, r->n_con += 1;
+    // the table as the kernels read it, whole (the pointers never move: the graphs bake them, nothing is invalidated)
+    std::vector<SampleConstraintRow> table(rows);
+    for (uint32_t b = 0; b < rows; b++) {
+        const zgml_hip_constraint* const cb = r->con[b];
+        table[b] = cb ? SampleConstraintRow{cb->class_of, cb->next, cb->n_classes, 1} : SampleConstraintRow{nullptr, nullptr, 0, 0};
+    }
+    const uint32_t st = c ? state : 0;
+    const bool ok = CTX_CHECK(ctx, hipMemcpyAsync(r->con_rows, table.data(), table.size() * sizeof(SampleConstraintRow), hipMemcpyHostToDevice, s)) &&
+                    CTX_CHECK(ctx, hipMemcpyAsync(r->con_state + seq, &st, 4, hipMemcpyHostToDevice, s)) && CTX_CHECK(ctx, hipStreamSynchronize(s));
+    return ok ? 0 : -1;
+}
+
+int64_t zgml_hip_program_constraint_state(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t seq) {
+    if (!ctx || !p || !p->resident) return -1;
+    const Resident* r = p->resident;
+    if (seq >= r->con.size() || !r->con[seq]) return -1;
+    hipSetDevice(ctx->device);
+    uint32_t st = 0;
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(&st, r->con_state + seq, 4, hipMemcpyDeviceToHost, ctx->stream)) || !CTX_CHECK(ctx, hipStreamSynchronize(ctx->stream))) return -1;
+    return (int64_t)st;
 }
 
 // log softmax(row i)[tokens[i]] of `rows` consecutive rows: [partial] [finish], whatever the number of rows
@@ -786,7 +902,10 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         return positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; });
     });
     const bool penalized = sp.pen_active != 0, lp = sampling->logprobs != 0, top = sp.top_logprobs != 0; // (top: only with lp)
-    if (!ensure_sample_blocks(ctx, r, 1) || (penalized && !ensure_window_block(ctx, r, 1))) return -1;
+    // a constraint attached: the constrained select launch, which serves penalties on and off (its graph bakes the window block)
+    const bool constrained = r->n_con != 0;
+    const bool raw_select = penalized || constrained; // the pick's lists are not the raw row's: the alternatives need a select of their own
+    if (!ensure_sample_blocks(ctx, r, 1) || ((penalized || constrained) && !ensure_window_block(ctx, r, 1))) return -1;
     if (r->tokens_cap < n_steps) {
         hipStreamSynchronize(s);
         hipFree(r->tokens);
@@ -808,17 +927,20 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     lt.out = r->lp, lt.state = r->state, lt.emitted = r->tokens, lt.written = r->lp_written, lt.cap = r->tokens_cap;
     TopLogprobTarget tt; // (calls with the `top_logprobs` word only)
     tt.chosen = lt, tt.top_tok = r->top_tok, tt.top_val = r->top_val, tt.params = r->sparams;
+    const SampleConstraint con = constraint_args(r);
     auto one_token = [&](hipStream_t st) {
         launch_resident_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
         if (lp) launch_logprob(st, r->logits, r->vocab, 1, r->lpart); // (the raw row: it depends on the plan alone)
-        if (penalized)
+        if (constrained)
+            launch_sample_constrained(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win, con);
+        else if (penalized)
             launch_sample_penalized(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win);
         else
             launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
-        if (top) { // [finish + top] in the place of [finish]: the merge launch only read the lists; penalised ones are no use, so a raw select
-            if (penalized) launch_sample_select(st, r->logits, r->vocab, 1, r->skeys_raw);
-            launch_logprob_finish_top(st, r->logits, r->vocab, 1, r->lpart, penalized ? r->skeys_raw : r->skeys, tt);
+        if (top) { // [finish + top] in the place of [finish]: the merge launch only read the lists; penalised or masked ones are no use, so a raw select
+            if (raw_select) launch_sample_select(st, r->logits, r->vocab, 1, r->skeys_raw);
+            launch_logprob_finish_top(st, r->logits, r->vocab, 1, r->lpart, raw_select ? r->skeys_raw : r->skeys, tt);
         } else if (lp) {
             launch_logprob_finish(st, r->logits, r->vocab, 1, r->lpart, lt); // (behind the advance: it knows whether a token was emitted)
         }
@@ -835,19 +957,14 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_steps * 8, s)) || // (-1: what a stopped sequence leaves behind its stop token)
         (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, 4, s))))
         return -1;
-    // (a penalised call replays a graph of its own, and so does a call with log-probabilities: the four kinds of call alternate on
-    // one program and invalidate nothing)
-    hipGraphExec_t& exec = top  ? (penalized ? r->graph_penalized_top_exec : r->graph_sampled_top_exec)
-                           : lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec)
-                                : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
-    hipGraph_t& graph = top  ? (penalized ? r->graph_penalized_top : r->graph_sampled_top)
-                        : lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp)
-                             : (penalized ? r->graph_penalized : r->graph_sampled);
+    // (a penalised call replays a graph of its own, and so do a constrained call and a call with log-probabilities: the kinds of
+    // call alternate on one program and invalidate nothing)
+    const uint32_t form = sampled_form(constrained ? kSelConstrained : penalized ? kSelPenalized : kSelPlain, top ? kKindTop : lp ? kKindLogprobs : kKindPick);
+    hipGraphExec_t& exec = r->sgraph_exec[form];
+    hipGraph_t& graph = r->sgraph[form];
     if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (the copies above read this stack frame: none in flight when the capture begins)
-        const char* const names[6] = {"resident_sampled", "resident_penalized", "resident_sampled_logprobs", "resident_penalized_logprobs",
-                                      "resident_sampled_top", "resident_penalized_top"};
-        capture_graph(ctx, s, names[top ? 4 + penalized : 2 * lp + penalized], [&] { one_token(s); }, &graph, &exec); // (failed: eager below)
+        capture_graph(ctx, s, (std::string("resident_") + kSampledFormNames[form]).c_str(), [&] { one_token(s); }, &graph, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < n_steps; i++) {
         if (exec)
@@ -875,7 +992,7 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     if (lp) logprob_fill_unproduced(ctx->lp_last.data(), made, n_steps);
     if (top) top_keep(ctx, n_steps, top_logprobs_count(sp.top_logprobs, r->vocab), top_tok, top_val, [&](uint64_t e) { return e < made ? (int64_t)e : -1; });
     // per token [prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish], or ([raw select]) [finish + top])
-    resident_end(p, n_steps, p->plan.size() + (top ? 5 + penalized : lp ? 5 : 3));
+    resident_end(p, n_steps, p->plan.size() + (top ? 5 + raw_select : lp ? 5 : 3));
     return ok ? 0 : -1;
 }
 
@@ -924,7 +1041,9 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     bool lp = false; // ... and one with log-probabilities: the two launches for all (a row nobody asked for is not copied out)
     bool top = false; // ... and one with alternatives: the top form of the finish for all (a row with the count 0 is all padding)
     for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active, lp = lp || per_seq[b].logprobs, top = top || sp[b].top_logprobs;
-    if (!ensure_sample_blocks(ctx, r, B) || (penalized && !ensure_window_block(ctx, r, B))) return -1;
+    const bool constrained = r->n_con != 0; // one sequence with a constraint: the constrained launch for all (a row without one computes what it did)
+    const bool raw_select = penalized || constrained;
+    if (!ensure_sample_blocks(ctx, r, B) || ((penalized || constrained) && !ensure_window_block(ctx, r, B))) return -1;
     if (r->btokens_cap < (uint64_t)B * steps) {
         hipStreamSynchronize(s);
         hipFree(r->btokens);
@@ -946,17 +1065,20 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     adv.state = r->bstate, adv.tokens = r->btokens, adv.n_seqs = B;
     SampleWindow win;
     win.ring = r->swin, win.lo = r->swin + (size_t)B * kSamplePenaltyMaxWindow;
+    const SampleConstraint con = constraint_args(r);
     auto one_step = [&](hipStream_t st) {
         launch_resident_batch_prep(st, a, total);
         run_plan(p, st, 0, p->plan.size());
         if (lp) launch_logprob(st, r->logits, r->vocab, B, r->lpart);
-        if (penalized)
+        if (constrained)
+            launch_sample_constrained(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win, con);
+        else if (penalized)
             launch_sample_penalized(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win);
         else
             launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
-        if (top) { // (one sequence with penalties active: the raw select for all rows, so the launches stay uniform)
-            if (penalized) launch_sample_select(st, r->logits, r->vocab, B, r->skeys_raw);
-            launch_logprob_finish_top(st, r->logits, r->vocab, B, r->lpart, penalized ? r->skeys_raw : r->skeys, tt);
+        if (top) { // (one sequence with penalties active or a constraint: the raw select for all rows, so the launches stay uniform)
+            if (raw_select) launch_sample_select(st, r->logits, r->vocab, B, r->skeys_raw);
+            launch_logprob_finish_top(st, r->logits, r->vocab, B, r->lpart, raw_select ? r->skeys_raw : r->skeys, tt);
         } else if (lp) {
             launch_logprob_finish(st, r->logits, r->vocab, B, r->lpart, lt);
         }
@@ -975,17 +1097,12 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s)) || // (-1: what a sequence leaves behind its count)
         (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, (size_t)B * 4, s))))
         return -1;
-    hipGraphExec_t& exec = top  ? (penalized ? r->graph_penalized_top_exec : r->graph_sampled_top_exec)
-                           : lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec)
-                                : (penalized ? r->graph_penalized_exec : r->graph_sampled_exec);
-    hipGraph_t& graph = top  ? (penalized ? r->graph_penalized_top : r->graph_sampled_top)
-                        : lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp)
-                             : (penalized ? r->graph_penalized : r->graph_sampled);
+    const uint32_t form = sampled_form(constrained ? kSelConstrained : penalized ? kSelPenalized : kSelPlain, top ? kKindTop : lp ? kKindLogprobs : kKindPick);
+    hipGraphExec_t& exec = r->sgraph_exec[form];
+    hipGraph_t& graph = r->sgraph[form];
     if (ctx->opt_graph && !exec) {
         hipStreamSynchronize(s); // (as the greedy batched loop: no pageable copy in flight when the capture begins)
-        const char* const names[6] = {"resident_batch_sampled", "resident_batch_penalized", "resident_batch_sampled_logprobs", "resident_batch_penalized_logprobs",
-                                      "resident_batch_sampled_top", "resident_batch_penalized_top"};
-        capture_graph(ctx, s, names[top ? 4 + penalized : 2 * lp + penalized], [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
+        capture_graph(ctx, s, (std::string("resident_batch_") + kSampledFormNames[form]).c_str(), [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
     }
     for (uint32_t i = 0; i < steps; i++) {
         if (exec)
@@ -1028,7 +1145,7 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         });
     }
     // per step [batched prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish], or ([raw select]) [finish + top])
-    resident_end(p, steps, p->plan.size() + (top ? 5 + penalized : lp ? 5 : 3));
+    resident_end(p, steps, p->plan.size() + (top ? 5 + raw_select : lp ? 5 : 3));
     return ok ? 0 : -1;
 }
 
@@ -1089,6 +1206,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     if (!ctx || !p || !p->resident) return -1;
     Resident* r = p->resident;
     if (n_produced) *n_produced = 0;
+    if (refuse_constrained(ctx, p, who.c_str())) return -1;
     if (r->n_seqs) {
         ctx->fail(who + ": the program is a batched plan (speculation under batching is not supported)");
         return -1;
@@ -1206,12 +1324,13 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         }
         launch_spec_accept(st, sa);
     };
-    hipGraphExec_t& exec = top ? (penalized ? r->graph_penalized_top_exec : r->graph_sampled_top_exec) : lp ? (penalized ? r->graph_penalized_lp_exec : r->graph_sampled_lp_exec) : penalized ? r->graph_penalized_exec : sampled ? r->graph_sampled_exec : r->graph_exec;
-    hipGraph_t& graph = top ? (penalized ? r->graph_penalized_top : r->graph_sampled_top) : lp ? (penalized ? r->graph_penalized_lp : r->graph_sampled_lp) : penalized ? r->graph_penalized : sampled ? r->graph_sampled : r->graph;
+    const uint32_t form = sampled_form(penalized ? kSelPenalized : kSelPlain, top ? kKindTop : lp ? kKindLogprobs : kKindPick); // (sampled form only)
+    hipGraphExec_t& exec = sampled ? r->sgraph_exec[form] : r->graph_exec;
+    hipGraph_t& graph = sampled ? r->sgraph[form] : r->graph;
     if (ctx->opt_graph && !exec) {
         if (sampled) hipStreamSynchronize(s); // (as the sampled loops: no copy from this stack frame in flight when the capture begins)
-        capture_graph(ctx, s, top ? (penalized ? "resident_spec_penalized_top" : "resident_spec_sampled_top") : lp ? (penalized ? "resident_spec_penalized_logprobs" : "resident_spec_sampled_logprobs") : penalized ? "resident_spec_penalized" : sampled ? "resident_spec_sampled" : "resident_spec",
-                      [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
+        const std::string name = sampled ? std::string("resident_spec_") + kSampledFormNames[form] : std::string("resident_spec");
+        capture_graph(ctx, s, name.c_str(), [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
     }
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)

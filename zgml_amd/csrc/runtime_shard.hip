@@ -303,7 +303,12 @@ int zgml_hip_shard_peer_import(zgml_hip_ctx* ctx, zgml_hip_program* p, int peer_
 }
 
 int64_t zgml_hip_shard_step(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_program_io* inputs, uint64_t n_inputs) {
-    if (!ctx || !p || !ctx->shard) return -1;
+    if (!ctx || !p) return -1;
+    if (has_constraint(p)) { // the step's greedy token would ignore it (include/zgml_hip.h); said whether or not the context is sharded
+        ctx->fail("shard_step: a constraint is attached to the program (only zgml_hip_resident_decode_sampled, _batch_sampled and zgml_hip_sample honour one: detach it first)");
+        return -1;
+    }
+    if (!ctx->shard) return -1;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     ensure_plan(p);

@@ -65,6 +65,19 @@
 // the same row, to the bit, and entry 0 is the row's first maximum. M = -inf: every value is -inf and the tokens are 0, 1, 2, ..
 // (all keys carry the same value word, the lower index first). M = +inf: every value is the quiet NaN, the tokens still the key
 // order. Entries a_eff .. of a row hold token -1 and the quiet NaN.
+//
+// THE CONSTRAINT (zgml_token_dfa, zgml_hip_program_set_constraint; kernel: sample_select_constrained_kernel, sample.hip). A token
+// automaton in class-compressed form: class_of[vocab] (u16) gives every token's class in 0 .. n_classes - 1, and
+// next[n_states][n_classes] (u16) the state behind a token of that class, kConstraintForbidden = 0xFFFF where the token is not
+// allowed in the state; 1 <= n_states <= 65535, 1 <= n_classes <= 8192 (a state's row, 16 KiB at most, lies beside the select sort
+// in LDS). A token that is not allowed in the row's current state IS NOT A CANDIDATE AT ALL: its key becomes the pad 0 — not the
+// key of -inf, which has p = 0 and still occupies a rank that the m - 1 fall-back of sample_pick_probs could return. The
+// candidates are the k = min(top_k, number of allowed tokens) largest keys among the allowed ones (sample_real_keys counts them in
+// the merged list); the pick and u are unchanged. An allowed token whose logit is -inf or a NaN stays a candidate with p = 0.
+// Penalties apply to the allowed tokens exactly as above; a masked key is gone, so the order of mask and penalty cannot matter.
+// Behind a pick the state becomes next[state][class_of[token]] (constraint_advance) — stop tokens advance it too. A state that
+// allows no token produces nothing: the loops freeze the sequence as behind a stop token, count no token and leave the state;
+// zgml_hip_sample returns -1. Log-probabilities and alternatives stay what they are above: over the RAW row.
 #pragma once
 
 #include <math.h>
@@ -403,6 +416,32 @@ ZGML_SAMPLE_FN uint32_t top_logprobs_keys_sliced(const float* v, uint64_t n, uin
 ZGML_SAMPLE_FN void top_logprobs_entry(uint64_t key, float M, float S, uint32_t* token, float* value) {
     *token = sample_key_index(key);
     *value = logprob_of(sample_key_value(key), M, S);
+}
+
+// ── the constraint ──
+
+constexpr uint32_t kConstraintMaxStates = 65535;  // states are u16 words, 0xFFFF is taken
+constexpr uint32_t kConstraintMaxClasses = 8192;  // a state's row beside the select sort in LDS: 16 KiB
+constexpr uint16_t kConstraintForbidden = 0xFFFF; // next[state][class]: the token is not allowed
+
+// is `token` allowed in the state whose row of the table — next + state * n_classes — is `row`?
+ZGML_SAMPLE_FN bool constraint_allowed(const uint16_t* row, const uint16_t* class_of, uint32_t token) { return row[class_of[token]] != kConstraintForbidden; }
+
+// the state behind `token` (an allowed one: else kConstraintForbidden comes back)
+ZGML_SAMPLE_FN uint32_t constraint_advance(const uint16_t* next, uint32_t n_classes, const uint16_t* class_of, uint32_t state, uint32_t token) {
+    return next[(uint64_t)state * n_classes + class_of[token]];
+}
+
+// The number of real (non-zero) keys among the first k0 of a descending list whose pads 0 lie behind every key: the k of a row.
+// A row without a constraint has n >= k0 real keys, so the result is k0 and nothing changes for it to the bit.
+ZGML_SAMPLE_FN uint32_t sample_real_keys(const uint64_t* keys, uint32_t k0) {
+    uint32_t lo = 0, hi = k0;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] != 0) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
 }
 
 } // namespace zgml

@@ -1,7 +1,7 @@
 // sample_params.h — what include/zgml_hip.h refuses of the penalty fields and of the `logprobs` field of a zgml_sampling, and of the
-// arguments of zgml_hip_logprobs and zgml_hip_top_logprobs, and how the `top_logprobs` word is read, as pure host logic: the
-// runtime (runtime_resident.hip) and the CPU probes tests/cpp/penalty_probe.cpp, tests/cpp/logprob_probe.cpp and
-// tests/cpp/top_logprob_probe.cpp compile these functions.
+// arguments of zgml_hip_logprobs and zgml_hip_top_logprobs, of a zgml_token_dfa and its attachment, and how the `top_logprobs`
+// word is read, as pure host logic: the runtime (runtime_resident.hip) and the CPU probes tests/cpp/penalty_probe.cpp,
+// tests/cpp/logprob_probe.cpp, tests/cpp/top_logprob_probe.cpp and tests/cpp/constraint_probe.cpp compile these functions.
 #pragma once
 
 #include <math.h>
@@ -65,6 +65,28 @@ inline const char* top_logprobs_check(uint64_t buf_size, uint64_t offset, uint64
     if (!rows) return "rows must be at least 1";
     if (!buf_size || offset > buf_size || n * (uint64_t)rows > buf_size - offset) return "the rows must lie inside the buffer";
     if (!top_n || top_n > kTopLogprobsMax) return "top_n must be 1 .. 64";
+    return nullptr;
+}
+
+// What zgml_hip_constraint_create refuses of a zgml_token_dfa (include/zgml_hip.h), before anything is uploaded: nullptr, or why
+inline const char* constraint_check(const zgml_token_dfa* d) {
+    if (!d || !d->class_of || !d->next) return "the automaton and its two tables must not be NULL";
+    if (d->n_states < 1 || d->n_states > kConstraintMaxStates) return "n_states must be 1 .. 65535";
+    if (d->n_classes < 1 || d->n_classes > kConstraintMaxClasses) return "n_classes must be 1 .. 8192";
+    if (d->vocab < 1) return "vocab must be at least 1";
+    for (uint32_t i = 0; i < d->vocab; i++)
+        if (d->class_of[i] >= d->n_classes) return "a class is not below n_classes";
+    for (uint64_t i = 0; i < (uint64_t)d->n_states * d->n_classes; i++)
+        if (d->next[i] != kConstraintForbidden && d->next[i] >= d->n_states) return "a next state is neither below n_states nor 0xFFFF";
+    return nullptr;
+}
+
+// ... and zgml_hip_program_set_constraint of an attachment: the automaton's vocab and n_states, the program's vocab and number of
+// sequences (1 for a plain plan)
+inline const char* constraint_attach_check(uint32_t dfa_vocab, uint32_t dfa_states, uint32_t program_vocab, uint32_t n_seqs, uint32_t seq, uint32_t state) {
+    if (seq >= n_seqs) return "seq is not below the program's number of sequences";
+    if (dfa_vocab != program_vocab) return "the automaton's vocab differs from the program's";
+    if (state >= dfa_states) return "state is not below n_states";
     return nullptr;
 }
 

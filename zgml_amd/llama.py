@@ -254,6 +254,12 @@ class BatchSession:
     def resident_setup(self, backend) -> None:
         Session.resident_setup(self, backend)
 
+    def set_constraint(self, constraint, state: int = 0, seq: int = 0) -> None:
+        Session.set_constraint(self, constraint, state, seq)
+
+    def constraint_state(self, seq: int = 0) -> int:
+        return Session.constraint_state(self, seq)
+
     def resident_decode_batch(self, first_tokens, start_pos, n_steps) -> np.ndarray:
         """-> tokens[B, max(n_steps)]; row b holds n_steps[b] tokens, then -1."""
         u32p = C.POINTER(C.c_uint32)
@@ -372,6 +378,16 @@ class Session:
         if hip.zgml_hip_resident_setup(backend.ctx, self.handle, C.byref(d)) != 0:
             raise RuntimeError("resident_setup: " + backend.last_error())
         self._backend = backend
+
+    def set_constraint(self, constraint, state: int = 0, seq: int = 0) -> None:
+        """Attach a token automaton (Backend.constraint_create) to sequence `seq` at `state`, after resident_setup; None
+        detaches. resident_decode_sampled / resident_decode_batch_sampled and Backend.sample then pick among the allowed tokens
+        only, and the state advances on the device."""
+        self._backend.set_constraint(self.handle, seq, constraint, state)
+
+    def constraint_state(self, seq: int = 0) -> int:
+        """the sequence's current state (-1: no constraint attached)"""
+        return self._backend.constraint_state(self.handle, seq)
 
     def resident_decode(self, first_token: int, start_pos: int, n_steps: int) -> np.ndarray:
         toks = np.zeros(n_steps, np.int64)

@@ -553,6 +553,34 @@ class Backend:
             raise RuntimeError("logprobs: " + self.last_error())
         return out[:t.size]
 
+    # constrained decoding (include/zgml_hip.h: zgml_token_dfa)
+    def constraint_create(self, class_of, next_table, **sizes):
+        """zgml_hip_constraint_create: validates and uploads a token automaton — class_of uint16[vocab], next_table
+        uint16[n_states, n_classes] with 0xFFFF for "not allowed" — and returns its handle. RuntimeError for what the library
+        refuses."""
+        dfa = capi.TokenDfaC.of(class_of, next_table, **sizes)
+        c = self._lib.zgml_hip_constraint_create(self.ctx, C.byref(dfa))
+        if not c:
+            raise RuntimeError("constraint_create: " + self.last_error())
+        return c
+
+    def constraint_free(self, constraint) -> None:
+        """zgml_hip_constraint_free. RuntimeError while it is still attached to a sequence."""
+        before = self.last_error()
+        self._lib.zgml_hip_constraint_free(self.ctx, constraint)
+        if not before and self.last_error():
+            raise RuntimeError("constraint_free: " + self.last_error())
+
+    def set_constraint(self, handle, seq: int, constraint, state: int = 0) -> None:
+        """zgml_hip_program_set_constraint: attach `constraint` to sequence `seq` of a program with a resident set-up, at `state`;
+        constraint=None detaches."""
+        if self._lib.zgml_hip_program_set_constraint(self.ctx, handle, seq, constraint, state) != 0:
+            raise RuntimeError("set_constraint: " + self.last_error())
+
+    def constraint_state(self, handle, seq: int = 0) -> int:
+        """zgml_hip_program_constraint_state: the sequence's current state, -1 with none attached"""
+        return int(self._lib.zgml_hip_program_constraint_state(self.ctx, handle, seq))
+
     def synchronize(self) -> None:
         self._lib.zgml_hip_synchronize(self.ctx)
 
