@@ -217,6 +217,27 @@ def test_calls_alternate_on_one_program(hip_backend):
     s.close(), m.close()
 
 
+def test_a_longer_call_after_the_graphs_were_captured(hip_backend):
+    """3 steps in each kind, plain and penalised, capture all six graphs over a token table (and values and pairs) of capacity 3;
+    N steps then grow the tables, which every one of the graphs baked: the longer calls must still equal the host loop bit for
+    bit, the short ones its first 3."""
+    kw = dict(seed=1234, stream=0, **PARAMS["k40_p95"])
+    s, m = resident(hip_backend)
+    for n in (3, N):
+        for pen in (None, PEN):
+            want, want_lp, rows = host_loop(hip_backend, kw, pen)
+            want_top = c_tops(rows[:n], 5)
+            sp = S(**kw, **(pen or {}))
+            a, made_a = s.resident_decode_sampled(FIRST, PROMPT_LEN, n, sp)
+            b, made_b, lp_b = s.resident_decode_sampled(FIRST, PROMPT_LEN, n, sp, logprobs=True)
+            c, made_c, lp_c, top_c = s.resident_decode_sampled(FIRST, PROMPT_LEN, n, sp, top_logprobs=5)
+            assert not hip_backend.last_error(), hip_backend.last_error()
+            assert made_a == made_b == made_c == n and a.tolist() == b.tolist() == c.tolist() == want[:n], (pen, n)
+            assert same_bits(lp_b, want_lp[:n]) and same_bits(lp_c, want_lp[:n]), (pen, n)
+            assert top_c[0].shape == (n, 5) and same_top(top_c, want_top), (pen, n)
+    s.close(), m.close()
+
+
 # ── 7. the getter ──────────────────────────────────────────────────────────────────────────────────────────────────────
 
 def test_the_getter(hip_backend):
@@ -245,26 +266,42 @@ def test_the_getter(hip_backend):
 
 # ── 5. batched ─────────────────────────────────────────────────────────────────────────────────────────────────────────
 
+B_FIRSTS, B_STEPS = [90, 292, 22], [12, 5, 12]
+B_KWS = [dict(seed=5, stream=0, **PARAMS["k40_p95"]), dict(seed=5, stream=1, **PARAMS["k256_p1"], **PEN), dict(seed=9, stream=2, **PARAMS["k40_p95"])]
+
+
+def batched_host_plan(be):
+    """B = 3, counts 12 / 5 / 12 from position 0, sequence 1 with penalties beside two without: the batched plan stepped through the
+    vtable, each row sampled on the host; a sequence behind its count repeats its step. -> (every sequence's tokens, float32
+    values, the logits rows). Computed once."""
+    if "batched" not in _host:
+        B, sps = len(B_FIRSTS), [S(**kw) for kw in B_KWS]
+        bm = llama.BatchModel(tiny(), B)
+        host = llama.BatchSession(bm, llama.hip_backend_fns(be), B)
+        tok, pos, want, lps, rows, known = list(B_FIRSTS), [0] * B, [[] for _ in range(B)], [[] for _ in range(B)], [[] for _ in range(B)], [[t] for t in B_FIRSTS]
+        for i in range(max(B_STEPS)):
+            _, logits = host.step(tok, pos)
+            for b in range(B):
+                if i < B_STEPS[b]:
+                    tok[b] = c_sample_penalized(logits[b], sps[b], pos[b], known[b]) if b == 1 else c_sample(logits[b], sps[b], pos[b])
+                    pos[b] += 1
+                    known[b].append(tok[b])
+                    want[b].append(tok[b])
+                    lps[b].append(c_logprob(logits[b], tok[b]))
+                    rows[b].append(np.array(logits[b], f32))
+        host.close(), bm.close()
+        _host["batched"] = (want, [np.array(x, f32) for x in lps], rows)
+    want, lps, rows = _host["batched"]
+    return [list(w) for w in want], [x.copy() for x in lps], [list(r) for r in rows]
+
+
 def test_batched_alternatives_equal_the_host_driven_batched_plan(hip_backend):
-    """B = 3, counts 12 / 5 / 12 from position 0, sequence 1 with penalties beside two without. The reference is the same batched
-    plan stepped through the vtable, each row sampled on the host; a sequence behind its count repeats its step."""
+    """The reference is batched_host_plan: the same batched plan driven from the host."""
     cfg, B = tiny(), 3
-    firsts, steps = [90, 292, 22], [12, 5, 12]
-    kws = [dict(seed=5, stream=0, **PARAMS["k40_p95"]), dict(seed=5, stream=1, **PARAMS["k256_p1"], **PEN), dict(seed=9, stream=2, **PARAMS["k40_p95"])]
+    firsts, steps, kws = B_FIRSTS, B_STEPS, B_KWS
     sps = [S(**kw) for kw in kws]
+    want, _, rows = batched_host_plan(hip_backend)
     bm = llama.BatchModel(cfg, B)
-    host = llama.BatchSession(bm, llama.hip_backend_fns(hip_backend), B)
-    tok, pos, want, rows, known = list(firsts), [0] * B, [[] for _ in range(B)], [[] for _ in range(B)], [[t] for t in firsts]
-    for i in range(max(steps)):
-        _, logits = host.step(tok, pos)
-        for b in range(B):
-            if i < steps[b]:
-                tok[b] = c_sample_penalized(logits[b], sps[b], pos[b], known[b]) if b == 1 else c_sample(logits[b], sps[b], pos[b])
-                pos[b] += 1
-                known[b].append(tok[b])
-                want[b].append(tok[b])
-                rows[b].append(np.array(logits[b], f32))
-    host.close()
     dev = llama.BatchSession(bm, llama.hip_backend_fns(hip_backend), B)
     dev.resident_setup(hip_backend)
     plain, _, lp0 = dev.resident_decode_batch_sampled(firsts, [0] * B, steps, sps, logprobs=True)
@@ -291,6 +328,32 @@ def test_batched_alternatives_equal_the_host_driven_batched_plan(hip_backend):
     assert np.array_equal(got, plain)
     alt, val = capi.top_logprobs_result(hip_backend.ctx, (B, 12))
     assert alt.shape == (B, 12, 5) and same_top((alt[0], val[0]), c_tops(rows[0], 5)) and padding(alt[1:], val[1:])
+    for x in (dev, bm):
+        x.close()
+
+
+def test_a_longer_batched_call_after_the_graphs_were_captured(hip_backend):
+    """as test_a_longer_call_after_the_graphs_were_captured: 3 steps per sequence in each kind, then the counts 12 / 5 / 12"""
+    B = 3
+    sps = [S(**kw) for kw in B_KWS]
+    want, want_lp, rows = batched_host_plan(hip_backend)
+    tops = [c_tops(rows[b], a) for b, a in enumerate((5, 7, 64))]
+    bm = llama.BatchModel(tiny(), B)
+    dev = llama.BatchSession(bm, llama.hip_backend_fns(hip_backend), B)
+    dev.resident_setup(hip_backend)
+    for steps in ([3] * B, B_STEPS):
+        a, made_a = dev.resident_decode_batch_sampled(B_FIRSTS, [0] * B, steps, sps)
+        b, made_b, lp_b = dev.resident_decode_batch_sampled(B_FIRSTS, [0] * B, steps, sps, logprobs=True)
+        c, made_c, lp_c, (alt, val) = dev.resident_decode_batch_sampled(B_FIRSTS, [0] * B, steps, sps, top_logprobs=[5, 7, 64])
+        assert not hip_backend.last_error(), hip_backend.last_error()
+        assert made_a.tolist() == made_b.tolist() == made_c.tolist() == steps and np.array_equal(a, b) and np.array_equal(a, c)
+        assert alt.shape == (B, max(steps), 64)
+        for i, n in enumerate(steps):
+            assert a[i, :n].tolist() == want[i][:n] and np.all(a[i, n:] == -1), (steps, i)
+            assert same_bits(lp_b[i, :n], want_lp[i][:n]) and same_bits(lp_c[i, :n], want_lp[i][:n]), (steps, i)
+            w = tops[i][0].shape[1]
+            assert same_top((alt[i, :n, :w], val[i, :n, :w]), (tops[i][0][:n], tops[i][1][:n])), (steps, i)
+            assert padding(alt[i, :n, w:], val[i, :n, w:]) and padding(alt[i, n:], val[i, n:]), (steps, i)
     for x in (dev, bm):
         x.close()
 

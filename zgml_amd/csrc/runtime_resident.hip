@@ -1,8 +1,11 @@
-// runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up, single-sequence decode,
-// batched decode and the prefill chunk. Everything a step needs (embedding row, mask column, RoPE rows, the dynamic words) is
-// produced on the device from a few state words, so a call is a train of launches (or graph replays) with one copy-out at the
-// end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_graph), resident_end.
-// No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's in their own files.
+// runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up; the greedy loops
+// (single-sequence decode, batched decode, the prefill chunk); their sampled forms and the sampled / greedy speculative verify
+// loop; the blocking calls over one buffer range (zgml_hip_sample, zgml_hip_logprobs, zgml_hip_top_logprobs) with their result
+// getters; the token constraint's create / attach / state. Everything a step needs (embedding row, mask column, RoPE rows, the
+// dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
+// copy-out at the end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_once, then
+// replay), resident_end; what follows the plan in a sampled step is stated once, by SampledTail.
+// No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's and the sampled tail's in their own files.
 #include "runtime_internal.h"
 #include "sample.h"
 #include "sample_params.h"
@@ -30,9 +33,10 @@ struct zgml_resident {
     uint32_t* state = nullptr;     // [0] token, [1] pos, [2] produced count
     uint32_t token_len = 1;        // T of the plan (token_input holds T rows): 1 = decode, > 1 = prefill chunk
     uint32_t* tok_dev = nullptr;   // prefill: the chunk's T token ids (the only per-chunk host -> device traffic)
-    int64_t* tokens = nullptr;     // produced tokens (device)
+    int64_t* tokens = nullptr;     // produced tokens (device), grown by ensure_tokens: the graphs bake pointer and capacity
     uint32_t tokens_cap = 0;
-    hipGraph_t graph = nullptr;
+    uint32_t prep_total = 0;       // the prep launches' flat index space (prep_total(): fixed by the set-up, which checks that it fits)
+    hipGraph_t graph = nullptr;    // the greedy loop's step: single-sequence, batched or verify, whichever the plan is
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph_multi = nullptr; // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
     hipGraphExec_t graph_multi_exec = nullptr;
@@ -55,28 +59,27 @@ struct zgml_resident {
     uint32_t* picks = nullptr; // the sampled form's token of every logits row, [T] (zgml_hip_resident_decode_speculative_sampled)
     // sampled tail (zgml_hip_resident_decode_sampled / _batch_sampled / _speculative_sampled), allocated by the first such call: one
     // parameter row and one set of partial candidate lists per sequence (per logits row of a token_len > 1 plan, whose verify
-    // step reads parameter row 0 alone); the loop's own graph (the greedy loop's stays valid beside it)
+    // step reads parameter row 0 alone)
     SampleParamsDev* sparams = nullptr;
     uint64_t* skeys = nullptr;
     // The sampled loops' graphs, one per form — what the select launch is (SampledSel) times what follows the pick (SampledKind):
-    // the forms alternate on one program and invalidate nothing. sampled_form() indexes them
+    // the forms alternate on one program and invalidate nothing, and the greedy loop's graph stays valid beside them.
+    // SampledTail::form() indexes them
     hipGraph_t sgraph[kSampledForms] = {};
     hipGraphExec_t sgraph_exec[kSampledForms] = {};
-    // penalised sampled tail (sample.h: the penalties), allocated by the first such call of the single or the batched loop: the
-    // window of every sequence, [n_seqs][256] token words indexed by position & 255, then lo per sequence (the verify step reads
-    // hist / cand instead); the penalised loops' own graph, beside the other two
+    // penalised sampled tail (sample.h: the penalties), allocated by the first penalised or constrained call of the single or the
+    // batched loop: the window of every sequence, [n_seqs][256] token words indexed by position & 255, then lo per sequence (the
+    // verify step reads hist / cand instead)
     uint32_t* swin = nullptr;
     // log-probabilities of the sampled tail (the `logprobs` field of zgml_sampling; logprob.hip), allocated by the first such call:
     // the block pairs of every logits row, the values next to the produced tokens ([lp_cap]: the layout of tokens / btokens), the
-    // T row values of a verify step, the "written up to" word of every sequence; the loops' own graphs, plain and penalised,
-    // beside the other four
+    // T row values of a verify step, the "written up to" word of every sequence
     float *lpart = nullptr, *lp = nullptr, *lp_rows = nullptr;
     uint32_t* lp_written = nullptr;
     uint64_t lp_cap = 0;
     // the alternatives of the sampled tail (the `top_logprobs` word of zgml_sampling; top_logprob.hip), allocated by the first such
-    // call: the lists of a select over the RAW rows (what a penalised step needs beside skeys, the same size), the pairs next to
-    // the produced tokens ([top_cap][64], the layout of lp), the T rows' pairs of a verify step; the loops' own graphs, "sampled +
-    // top" and "penalised + top", beside the other six
+    // call: the lists of a select over the RAW rows (what a penalised or constrained step needs beside skeys, the same size), the
+    // pairs next to the produced tokens ([top_cap][64], the layout of lp), the T rows' pairs of a verify step
     uint64_t* skeys_raw = nullptr;
     uint32_t *top_tok = nullptr, *top_rows_tok = nullptr;
     float *top_val = nullptr, *top_rows_val = nullptr;
@@ -384,6 +387,182 @@ void logprob_fill_unproduced(float* out, uint64_t from, uint64_t to) {
     for (uint64_t i = from; i < to; i++) out[i] = nan;
 }
 
+// What follows the plan in a sampled step, over `rows` logits rows:
+//   ([partial]) [select | penalised select | constrained select] [merge + pick] ([finish], or ([raw select]) [finish + top])
+// `sel` and `kind` decide the train, the graph slot and the launch count; the rest is where the launches read and write. The
+// single loop, the batched loop, the sampled verify step and zgml_hip_sample each fill one and call launch().
+struct SampledTail {
+    uint32_t rows = 1;
+    SampledSel sel = kSelPlain;
+    SampledKind kind = kKindPick;
+    uint64_t* keys = nullptr;     // the pick's partial candidate lists
+    uint64_t* keys_raw = nullptr; // ... and those of a select over the raw rows (kKindTop with raw_select())
+    const SampleParamsDev* params = nullptr;
+    float* part = nullptr;        // block pairs of [partial] (kKindLogprobs, kKindTop)
+    SampleAdvance adv;
+    SampleWindow win;     // (kSelPenalized, kSelConstrained)
+    SampleConstraint con; // (kSelConstrained)
+    TopLogprobTarget top; // top.chosen is [finish]'s target (kKindLogprobs, kKindTop); the rest [finish + top]'s (kKindTop)
+
+    static SampledSel sel_of(bool constrained, bool penalized) { return constrained ? kSelConstrained : penalized ? kSelPenalized : kSelPlain; }
+    static SampledKind kind_of(bool lp, bool top) { return top ? kKindTop : lp ? kKindLogprobs : kKindPick; } // (top: only with lp)
+    // penalised or masked lists are not the raw row's: the alternatives then need a select of their own
+    bool raw_select() const { return sel != kSelPlain; }
+    uint32_t form() const { return sampled_form(sel, kind); }
+    // for resident_end: [select] [merge + pick], [partial] and [finish] with log-probabilities, the raw [select] where needed
+    uint32_t launches() const { return 2 + (kind != kKindPick ? 2 : 0) + (kind == kKindTop && raw_select() ? 1 : 0); }
+    void launch(hipStream_t st, const float* logits, uint64_t vocab) const {
+        if (kind != kKindPick) launch_logprob(st, logits, vocab, rows, part); // (the raw row: it depends on the plan alone)
+        if (sel == kSelConstrained)
+            launch_sample_constrained(st, logits, vocab, rows, keys, params, adv, win, con);
+        else if (sel == kSelPenalized)
+            launch_sample_penalized(st, logits, vocab, rows, keys, params, adv, win);
+        else
+            launch_sample(st, logits, vocab, rows, keys, params, adv);
+        if (kind == kKindTop) { // [finish + top] in the place of [finish]: the merge launch only read the lists
+            if (raw_select()) launch_sample_select(st, logits, vocab, rows, keys_raw); // (for all rows, so the launches stay uniform)
+            launch_logprob_finish_top(st, logits, vocab, rows, part, raw_select() ? keys_raw : keys, top);
+        } else if (kind == kKindLogprobs) {
+            launch_logprob_finish(st, logits, vocab, rows, part, top.chosen); // (behind the advance: it knows whether a token was emitted)
+        }
+    }
+};
+
+// the loops' part of a tail over the program's blocks (after the ensure_* calls: the pointers are final); adv / win / top differ
+SampledTail resident_tail(const Resident* r, uint32_t rows, SampledSel sel, SampledKind kind) {
+    SampledTail t;
+    t.rows = rows, t.sel = sel, t.kind = kind;
+    t.keys = r->skeys, t.keys_raw = r->skeys_raw, t.params = r->sparams, t.part = r->lpart;
+    t.con = constraint_args(r);
+    t.top.params = r->sparams;
+    return t;
+}
+
+// The produced-token table of a loop (tokens / btokens) with room for `need` tokens. The graphs baked the old pointer and
+// capacity: growing the table drops them. A failed allocation leaves no table and no capacity
+template <class Cap>
+bool ensure_tokens(zgml_hip_ctx* ctx, zgml_hip_program* p, int64_t*& table, Cap& cap, uint64_t need) {
+    if (cap >= need) return true;
+    hipStreamSynchronize(ctx->stream);
+    hipFree(table);
+    table = nullptr, cap = 0;
+    if (!CTX_CHECK(ctx, hipMalloc((void**)&table, (size_t)need * 8))) return false;
+    cap = (Cap)need;
+    free_resident_graph(p);
+    return true;
+}
+
+// What the two batched loops ask of a request, refused before anything is enqueued: -> the steps of the call (the largest
+// count) and the last position of every sequence. tokens_out (and n_produced) are filled only once nothing is refused.
+// A sequence that stops before the last step repeats its step at the position BEHIND its last token (it rewrites that KV column
+// with the same values): that column must exist too. (One frozen by a stop token idles at a position its own count covers.)
+bool batch_request(zgml_hip_ctx* ctx, const Resident* r, const std::string& who, const uint32_t* first_tokens, const uint32_t* start_pos, const uint32_t* n_steps,
+                   uint32_t max_steps, int64_t* tokens_out, uint32_t* n_produced, uint32_t* steps_out, std::vector<uint32_t>* last_pos) {
+    const uint32_t B = r->n_seqs;
+    uint32_t steps = 0;
+    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
+    if (steps > max_steps) {
+        ctx->fail(who + ": n_steps exceeds max_steps");
+        return false;
+    }
+    last_pos->resize(B);
+    for (uint32_t b = 0; b < B; b++) {
+        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b]; // position after its last step
+        const bool idles = n_steps[b] < steps;
+        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
+            ctx->fail(who + ": token or position out of range (sequence " + std::to_string(b) + ")");
+            return false;
+        }
+        (*last_pos)[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
+    }
+    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
+    for (uint32_t b = 0; n_produced && b < B; b++) n_produced[b] = 0;
+    *steps_out = steps;
+    return true;
+}
+
+// The flat index space of a prep launch (kernels.h): T embedding rows, T mask columns, T RoPE rows per layer leaf, the dynamic
+// words — T the plan's token_len, which is B of a batched plan. The set-up refuses a plan whose total does not fit the
+// launch's 32-bit argument and keeps the value: the op list's length is fixed when the program is created
+// (zgml_hip_refresh_program refuses another), so the n_ops the argument structs read at every call is the one counted here
+uint64_t prep_total(const Resident* r, size_t n_ops) {
+    return (uint64_t)r->token_len * ((uint64_t)r->d + r->max_seq + (uint64_t)r->n_rope * 2 * r->dh) + n_ops;
+}
+
+// the prep launch of a single-sequence plan: position from state[1], the token_len token ids from `tokens`
+struct Prep {
+    ResidentPrepArgs a;
+    uint32_t total;
+};
+Prep prep_args(const zgml_hip_program* p, const uint32_t* state, const uint32_t* tokens) {
+    const Resident* r = p->resident;
+    return {{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
+             p->dyn_dev, state, tokens, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), r->token_len},
+            r->prep_total};
+}
+
+// ... and of a batched plan: everything from bstate
+struct BatchPrep {
+    ResidentBatchPrepArgs a;
+    uint32_t total;
+};
+BatchPrep batch_prep_args(const zgml_hip_program* p) {
+    const Resident* r = p->resident;
+    return {{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
+             p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), r->n_seqs},
+            r->prep_total};
+}
+
+// A loop's step becomes a graph the first time it runs with graphs on (a failed capture leaves the slot empty: eager below).
+// `wait`: host memory that a copy enqueued before this reads must not be in flight when the capture begins
+template <class Step>
+void capture_once(zgml_hip_ctx* ctx, hipStream_t s, const std::string& name, bool wait, Step step, hipGraph_t* graph, hipGraphExec_t* exec) {
+    if (!ctx->opt_graph || *exec) return;
+    if (wait) hipStreamSynchronize(s);
+    capture_graph(ctx, s, name.c_str(), [&] { step(s); }, graph, exec);
+}
+
+// ... and runs n times: the graph, or the step's launches
+template <class Step>
+void replay(hipStream_t s, hipGraphExec_t exec, uint32_t n, Step step) {
+    for (uint32_t i = 0; i < n; i++) {
+        if (exec)
+            hipGraphLaunch(exec, s);
+        else
+            step(s);
+    }
+}
+
+// The copy-out of a sampled loop's values and alternatives: download() enqueues the copies of the first `n` device entries
+// (they lie as the produced tokens do); keep(), behind the synchronisation, leaves what the result getters hand out — `entries`
+// values and [entries][width] pairs, entry e from device entry src(e), or the NaN / padding where src(e) < 0
+struct SampledCopyOut {
+    SampledKind kind;
+    std::vector<float> lp, top_val;
+    std::vector<uint32_t> top_tok;
+    void download(hipStream_t s, const Resident* r, uint64_t n) {
+        if (kind != kKindPick) {
+            lp.resize(n);
+            hipMemcpyAsync(lp.data(), r->lp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s);
+        }
+        if (kind == kKindTop) {
+            top_tok.resize((size_t)n * kTopLogprobsMax), top_val.resize(top_tok.size());
+            hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
+            hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+        }
+    }
+    template <class LpSrc, class TopSrc>
+    void keep(zgml_hip_ctx* ctx, uint64_t entries, uint32_t width, LpSrc lp_src, TopSrc top_src) const {
+        if (kind != kKindPick) {
+            ctx->lp_last.resize(entries);
+            logprob_fill_unproduced(ctx->lp_last.data(), 0, entries);
+            for (uint64_t e = 0; e < entries; e++)
+                if (const int64_t from = lp_src(e); from >= 0) ctx->lp_last[e] = lp[(size_t)from];
+        }
+        if (kind == kKindTop) top_keep(ctx, entries, width, top_tok, top_val, top_src);
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -416,6 +595,12 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
     r->vocab = d->vocab, r->d = d->d_model, r->max_seq = d->max_seq, r->dh = d->d_head, r->n_rope = d->n_rope;
     r->tok_in = p->bufs[d->buf_token_input], r->mask = p->bufs[d->buf_attn_mask], r->logits = p->bufs[d->buf_logits];
     const size_t n_ops = p->ops.size();
+    if (prep_total(r, n_ops) > UINT32_MAX) {
+        ctx->fail("resident_setup: token_len x (d_model + max_seq + 2 n_rope d_head) + ops exceeds 2^32 - 1, the prep launch's index space");
+        free_resident(p);
+        return -1;
+    }
+    r->prep_total = (uint32_t)prep_total(r, n_ops);
     std::vector<float*> ropes(d->n_rope);
     for (uint32_t l = 0; l < d->n_rope; l++) {
         if (!live(d->buf_rope[l]) || p->sizes[d->buf_rope[l]] < (uint64_t)T * 2 * d->d_head) {
@@ -487,37 +672,28 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     resident_begin(p, [&] {
         return !n_steps || (positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; }));
     });
-    if (r->tokens_cap < n_steps) {
-        hipStreamSynchronize(s);
-        hipFree(r->tokens);
-        r->tokens = nullptr;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_steps * 8))) return -1;
-        r->tokens_cap = n_steps;
-        free_resident_graph(p); // the graph baked the old pointer/cap
-    }
-    ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
-                       p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
-    const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
+    if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_steps)) return -1;
+    const Prep prep = prep_args(p, r->state, r->state /* the token is state[0] */);
     // (off unless ZGML_HIP_TAIL_FUSED=1. First form — the last arriver walks all 8-16 K elements of the next token's patches alone —
     // measured SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every workgroup writes the
     // position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838 against 842;
     // profiles/r05_token_tail_ab.txt)
     const bool tail_fused = sw().hip_tail_fused;
     auto one_token = [&](hipStream_t st) {
-        if (!tail_fused) launch_resident_prep(st, a, total);
+        if (!tail_fused) launch_resident_prep(st, prep.a, prep.total);
         // [prep] [plan] [argmax stage 1] [stage 2 + advance]; or, opt-in, [plan] [token tail]: the argmax of the logits, the advance
         // of the device state AND the next token's patches in ONE launch (launch_argmax_tail; the first token's patches then
         // come from a stand-alone prep launch in front of the loop) — two launches fewer per token.
         run_plan(p, st, 0, p->plan.size());
         if (tail_fused)
-            launch_argmax_tail(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_cnt, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap}, &a, total);
+            launch_argmax_tail(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_cnt, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap}, &prep.a, prep.total);
         else
             launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap});
     };
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // (a stack array: no wait before the capture, unlike the batched loop's vector)
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return -1;
-    if (tail_fused) launch_resident_prep(s, a, total); // the first token's patches (every later token's come from its predecessor's tail)
-    if (ctx->opt_graph && !r->graph_exec) capture_graph(ctx, s, "resident", [&] { one_token(s); }, &r->graph, &r->graph_exec); // (failed: eager below)
+    if (tail_fused) launch_resident_prep(s, prep.a, prep.total); // the first token's patches (every later token's come from its predecessor's tail)
+    capture_once(ctx, s, "resident", false, one_token, &r->graph, &r->graph_exec);
     // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
     // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
     const uint32_t per_graph = (uint32_t)sw().hip_resident_tokens_per_graph;
@@ -560,24 +736,8 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
     if (refuse_constrained(ctx, p, "resident_decode_batch")) return -1;
     const uint32_t B = r->n_seqs;
     uint32_t steps = 0;
-    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
-    if (steps > max_steps) {
-        ctx->fail("resident_decode_batch: n_steps exceeds max_steps");
-        return -1;
-    }
-    // everything is refused before anything is enqueued. A sequence that stops before the last step repeats its step at the position
-    // BEHIND its last token (it rewrites that KV column with the same values): that column must exist too
-    std::vector<uint32_t> last_pos(B);
-    for (uint32_t b = 0; b < B; b++) {
-        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b]; // position after its last step
-        const bool idles = n_steps[b] < steps;
-        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
-            ctx->fail("resident_decode_batch: token or position out of range (sequence " + std::to_string(b) + ")");
-            return -1;
-        }
-        last_pos[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
-    }
-    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
+    std::vector<uint32_t> last_pos;
+    if (!batch_request(ctx, r, "resident_decode_batch", first_tokens, start_pos, n_steps, max_steps, tokens_out, nullptr, &steps, &last_pos)) return -1;
     if (!steps) return 0;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
@@ -585,19 +745,10 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
     resident_begin(p, [&] {
         return positions_in_bounds(p, 1, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) && positions_in_bounds(p, 1, [&](uint32_t i) { return last_pos[p->op_seq[i]]; });
     });
-    if (r->btokens_cap < (uint64_t)B * steps) {
-        hipStreamSynchronize(s);
-        hipFree(r->btokens);
-        r->btokens = nullptr, r->btokens_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->btokens, (size_t)B * steps * 8))) return -1;
-        r->btokens_cap = (uint64_t)B * steps;
-        free_resident_graph(p); // the graph baked the old pointer
-    }
-    const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
-                                  p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
-    const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
+    if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * steps)) return -1;
+    const BatchPrep prep = batch_prep_args(p);
     auto one_step = [&](hipStream_t st) {
-        launch_resident_batch_prep(st, a, total);
+        launch_resident_batch_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
         launch_argmax_batch(st, r->logits, r->vocab, B, r->bval, r->bidx, r->bstate, r->btokens);
     };
@@ -607,18 +758,10 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
         return -1;
-    if (ctx->opt_graph && !r->graph_exec) {
-        // st0, a heap vector, is read by the copy above: it must not die under a pageable-memory copy in flight. (The
-        // single-sequence loop hands over a 16-byte stack array instead and does without the wait.)
-        hipStreamSynchronize(s);
-        capture_graph(ctx, s, "resident_batch", [&] { one_step(s); }, &r->graph, &r->graph_exec); // (failed: eager below)
-    }
-    for (uint32_t i = 0; i < steps; i++) {
-        if (r->graph_exec)
-            hipGraphLaunch(r->graph_exec, s);
-        else
-            one_step(s);
-    }
+    // st0, a heap vector, is read by the copy above: it must not die under a pageable-memory copy in flight. (The
+    // single-sequence loop hands over a 16-byte stack array instead and does without the wait.)
+    capture_once(ctx, s, "resident_batch", true, one_step, &r->graph, &r->graph_exec);
+    replay(s, r->graph_exec, steps, one_step);
     std::vector<int64_t> got((size_t)B * steps);
     hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
@@ -652,46 +795,32 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     const uint32_t top = sp.top_logprobs; // (0 without the `logprobs` word)
     if (top && !ensure_ctx_top(ctx, 1, sample_scratch_keys(n, 1))) return -1;
     if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
-    SampleAdvance adv;
-    adv.position = position, adv.out = (int64_t*)ctx->smp_out, adv.cand = ctx->smp_out + 2;
     // sequence 0's constraint, when the row is a row of the automaton's vocabulary: its state masks the pick and advances over it
     const Resident* const res = p->resident;
     const bool constrained = res && res->n_con && res->con[0] && n == res->vocab;
-    const bool raw_select = sp.pen_active || constrained; // (the alternatives: the pick's lists are not the raw row's)
-    SampleWindow win;
+    SampledTail tail;
+    tail.sel = SampledTail::sel_of(constrained, sp.pen_active), tail.kind = SampledTail::kind_of(sampling->logprobs, top);
+    tail.keys = ctx->smp_keys, tail.keys_raw = ctx->top_keys, tail.params = ctx->smp_params, tail.part = ctx->lp_part;
+    tail.adv.position = position, tail.adv.out = (int64_t*)ctx->smp_out, tail.adv.cand = ctx->smp_out + 2;
     if (sp.pen_active) { // the window: the last W of the recent tokens, the token whose logits these are last
         const uint32_t take = std::min(sampling->n_recent, sp.window);
         if (!ctx->smp_win && !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_win, kSamplePenaltyMaxWindow * 4))) return -1;
         if (take && !CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_win, sampling->recent + (sampling->n_recent - take), (size_t)take * 4, hipMemcpyHostToDevice, s))) return -1;
-        win.list = ctx->smp_win, win.n_list = take;
+        tail.win.list = ctx->smp_win, tail.win.n_list = take;
     }
-    if (constrained) {
-        launch_sample_constrained(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv, win, constraint_args(res));
-    } else if (sp.pen_active) {
-        launch_sample_penalized(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv, win);
-    } else {
-        launch_sample(s, p->bufs[buf_idx] + offset, n, 1, ctx->smp_keys, ctx->smp_params, adv);
-    }
+    if (constrained) tail.con = constraint_args(res);
+    // the values over the raw row, behind the pick: the token is read where the merge launch stored it
+    tail.top.chosen.out = ctx->lp_out, tail.top.chosen.token64 = (const int64_t*)ctx->smp_out;
+    tail.top.top_tok = ctx->top_tok, tail.top.top_val = ctx->top_val, tail.top.params = ctx->smp_params;
+    tail.launch(s, p->bufs[buf_idx] + offset, n);
     float lp = 0.0f;
-    std::vector<uint32_t> top_tok;
-    std::vector<float> top_val;
-    if (sampling->logprobs) { // over the raw row, behind the pick: the token is read where the merge launch stored it
-        LogprobTarget lt;
-        lt.out = ctx->lp_out, lt.token64 = (const int64_t*)ctx->smp_out;
-        launch_logprob(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part);
-        if (top) { // the alternatives: from the pick's own lists, or — penalties have changed those — from a select over the raw row
-            TopLogprobTarget tt;
-            tt.chosen = lt, tt.top_tok = ctx->top_tok, tt.top_val = ctx->top_val, tt.params = ctx->smp_params;
-            if (raw_select) launch_sample_select(s, p->bufs[buf_idx] + offset, n, 1, ctx->top_keys);
-            launch_logprob_finish_top(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, raw_select ? ctx->top_keys : ctx->smp_keys, tt);
-            top_tok.resize(kTopLogprobsMax), top_val.resize(kTopLogprobsMax);
-            hipMemcpyAsync(top_tok.data(), ctx->top_tok, kTopLogprobsMax * 4, hipMemcpyDeviceToHost, s);
-            hipMemcpyAsync(top_val.data(), ctx->top_val, kTopLogprobsMax * sizeof(float), hipMemcpyDeviceToHost, s);
-        } else {
-            launch_logprob_finish(s, p->bufs[buf_idx] + offset, n, 1, ctx->lp_part, lt);
-        }
-        hipMemcpyAsync(&lp, ctx->lp_out, sizeof(lp), hipMemcpyDeviceToHost, s);
+    std::vector<uint32_t> top_tok(top ? kTopLogprobsMax : 0);
+    std::vector<float> top_val(top_tok.size());
+    if (top) {
+        hipMemcpyAsync(top_tok.data(), ctx->top_tok, kTopLogprobsMax * 4, hipMemcpyDeviceToHost, s);
+        hipMemcpyAsync(top_val.data(), ctx->top_val, kTopLogprobsMax * sizeof(float), hipMemcpyDeviceToHost, s);
     }
+    if (sampling->logprobs) hipMemcpyAsync(&lp, ctx->lp_out, sizeof(lp), hipMemcpyDeviceToHost, s);
     uint32_t got[out_words];
     hipMemcpyAsync(got, ctx->smp_out, sizeof(got), hipMemcpyDeviceToHost, s);
     if (!CTX_CHECK(ctx, hipStreamSynchronize(s)) || !ctx->handoff_ok("sample")) return -1;
@@ -904,46 +1033,21 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     const bool penalized = sp.pen_active != 0, lp = sampling->logprobs != 0, top = sp.top_logprobs != 0; // (top: only with lp)
     // a constraint attached: the constrained select launch, which serves penalties on and off (its graph bakes the window block)
     const bool constrained = r->n_con != 0;
-    const bool raw_select = penalized || constrained; // the pick's lists are not the raw row's: the alternatives need a select of their own
     if (!ensure_sample_blocks(ctx, r, 1) || ((penalized || constrained) && !ensure_window_block(ctx, r, 1))) return -1;
-    if (r->tokens_cap < n_steps) {
-        hipStreamSynchronize(s);
-        hipFree(r->tokens);
-        r->tokens = nullptr, r->tokens_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_steps * 8))) return -1;
-        r->tokens_cap = n_steps;
-        free_resident_graph(p); // the graphs baked the old pointer/cap
-    }
+    if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_steps)) return -1;
     if (lp && !ensure_logprob_blocks(ctx, p, 1, r->tokens_cap)) return -1;
     if (top && !ensure_top_blocks(ctx, p, 1, r->tokens_cap)) return -1;
-    const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
-                             p->dyn_dev, r->state, r->state /* the token is state[0] */, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), 1};
-    const uint32_t total = r->d + r->max_seq + r->n_rope * 2 * r->dh + (uint32_t)p->ops.size();
-    SampleAdvance adv;
-    adv.state = r->state, adv.tokens = r->tokens, adv.cap = r->tokens_cap;
-    SampleWindow win;
-    win.ring = r->swin, win.lo = r->swin + kSamplePenaltyMaxWindow;
-    LogprobTarget lt; // (calls with the `logprobs` field only)
+    const Prep prep = prep_args(p, r->state, r->state /* the token is state[0] */);
+    SampledTail tail = resident_tail(r, 1, SampledTail::sel_of(constrained, penalized), SampledTail::kind_of(lp, top));
+    tail.adv.state = r->state, tail.adv.tokens = r->tokens, tail.adv.cap = r->tokens_cap;
+    tail.win.ring = r->swin, tail.win.lo = r->swin + kSamplePenaltyMaxWindow;
+    LogprobTarget& lt = tail.top.chosen;
     lt.out = r->lp, lt.state = r->state, lt.emitted = r->tokens, lt.written = r->lp_written, lt.cap = r->tokens_cap;
-    TopLogprobTarget tt; // (calls with the `top_logprobs` word only)
-    tt.chosen = lt, tt.top_tok = r->top_tok, tt.top_val = r->top_val, tt.params = r->sparams;
-    const SampleConstraint con = constraint_args(r);
+    tail.top.top_tok = r->top_tok, tail.top.top_val = r->top_val;
     auto one_token = [&](hipStream_t st) {
-        launch_resident_prep(st, a, total);
+        launch_resident_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
-        if (lp) launch_logprob(st, r->logits, r->vocab, 1, r->lpart); // (the raw row: it depends on the plan alone)
-        if (constrained)
-            launch_sample_constrained(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win, con);
-        else if (penalized)
-            launch_sample_penalized(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv, win);
-        else
-            launch_sample(st, r->logits, r->vocab, 1, r->skeys, r->sparams, adv);
-        if (top) { // [finish + top] in the place of [finish]: the merge launch only read the lists; penalised or masked ones are no use, so a raw select
-            if (raw_select) launch_sample_select(st, r->logits, r->vocab, 1, r->skeys_raw);
-            launch_logprob_finish_top(st, r->logits, r->vocab, 1, r->lpart, raw_select ? r->skeys_raw : r->skeys, tt);
-        } else if (lp) {
-            launch_logprob_finish(st, r->logits, r->vocab, 1, r->lpart, lt); // (behind the advance: it knows whether a token was emitted)
-        }
+        tail.launch(st, r->logits, r->vocab);
     };
     std::vector<uint32_t> win0; // (penalised calls only; alive until the call's last synchronisation)
     if (penalized) {
@@ -959,40 +1063,23 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
         return -1;
     // (a penalised call replays a graph of its own, and so do a constrained call and a call with log-probabilities: the kinds of
     // call alternate on one program and invalidate nothing)
-    const uint32_t form = sampled_form(constrained ? kSelConstrained : penalized ? kSelPenalized : kSelPlain, top ? kKindTop : lp ? kKindLogprobs : kKindPick);
-    hipGraphExec_t& exec = r->sgraph_exec[form];
-    hipGraph_t& graph = r->sgraph[form];
-    if (ctx->opt_graph && !exec) {
-        hipStreamSynchronize(s); // (the copies above read this stack frame: none in flight when the capture begins)
-        capture_graph(ctx, s, (std::string("resident_") + kSampledFormNames[form]).c_str(), [&] { one_token(s); }, &graph, &exec); // (failed: eager below)
-    }
-    for (uint32_t i = 0; i < n_steps; i++) {
-        if (exec)
-            hipGraphLaunch(exec, s);
-        else
-            one_token(s);
-    }
+    hipGraphExec_t& exec = r->sgraph_exec[tail.form()];
+    // (the copies above read this stack frame: none in flight when the capture begins)
+    capture_once(ctx, s, std::string("resident_") + kSampledFormNames[tail.form()], true, one_token, &r->sgraph[tail.form()], &exec);
+    replay(s, exec, n_steps, one_token);
     uint32_t st1[4] = {0, 0, 0, 0};
     hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(st1, r->state, sizeof(st1), hipMemcpyDeviceToHost, s);
-    if (lp) {
-        ctx->lp_last.assign(n_steps, 0.0f);
-        hipMemcpyAsync(ctx->lp_last.data(), r->lp, (size_t)n_steps * sizeof(float), hipMemcpyDeviceToHost, s);
-    }
-    std::vector<uint32_t> top_tok(top ? (size_t)n_steps * kTopLogprobsMax : 0);
-    std::vector<float> top_val(top_tok.size());
-    if (top) {
-        hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
-    }
+    SampledCopyOut out{tail.kind};
+    out.download(s, r, n_steps);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode_sampled");
-    if (ok && n_produced) *n_produced = std::min(st1[2], n_steps);
     const uint32_t made = ok ? std::min(st1[2], n_steps) : 0;
-    if (lp) logprob_fill_unproduced(ctx->lp_last.data(), made, n_steps);
-    if (top) top_keep(ctx, n_steps, top_logprobs_count(sp.top_logprobs, r->vocab), top_tok, top_val, [&](uint64_t e) { return e < made ? (int64_t)e : -1; });
-    // per token [prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish], or ([raw select]) [finish + top])
-    resident_end(p, n_steps, p->plan.size() + (top ? 5 + raw_select : lp ? 5 : 3));
+    if (ok && n_produced) *n_produced = made;
+    const auto produced = [&](uint64_t e) { return e < made ? (int64_t)e : -1; };
+    out.keep(ctx, n_steps, top_logprobs_count(sp.top_logprobs, r->vocab), produced, produced);
+    // per token [prep] [plan] and the sampled tail
+    resident_end(p, n_steps, p->plan.size() + 1 + tail.launches());
     return ok ? 0 : -1;
 }
 
@@ -1012,25 +1099,8 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     for (uint32_t b = 0; b < B; b++)
         if (!sampling_params(ctx, "resident_decode_batch_sampled (sequence " + std::to_string(b) + ")", per_seq ? per_seq + b : nullptr, r->vocab, r->vocab, &sp[b], RecentOf::Loop, start_pos[b])) return -1;
     uint32_t steps = 0;
-    for (uint32_t b = 0; b < B; b++) steps = std::max(steps, n_steps[b]);
-    if (steps > max_steps) {
-        ctx->fail("resident_decode_batch_sampled: n_steps exceeds max_steps");
-        return -1;
-    }
-    // as zgml_hip_resident_decode_batch: a sequence that idles behind its count repeats its step at the position behind its last
-    // token. (One frozen by a stop token idles at a position its own count covers.)
-    std::vector<uint32_t> last_pos(B);
-    for (uint32_t b = 0; b < B; b++) {
-        const uint64_t end = (uint64_t)start_pos[b] + n_steps[b];
-        const bool idles = n_steps[b] < steps;
-        if (first_tokens[b] >= r->vocab || end > r->max_seq || (idles && end >= r->max_seq)) {
-            ctx->fail("resident_decode_batch_sampled: token or position out of range (sequence " + std::to_string(b) + ")");
-            return -1;
-        }
-        last_pos[b] = (uint32_t)(idles ? end : (n_steps[b] ? end - 1 : start_pos[b]));
-    }
-    for (uint64_t i = 0; i < (uint64_t)B * max_steps; i++) tokens_out[i] = -1;
-    for (uint32_t b = 0; n_produced && b < B; b++) n_produced[b] = 0;
+    std::vector<uint32_t> last_pos;
+    if (!batch_request(ctx, r, "resident_decode_batch_sampled", first_tokens, start_pos, n_steps, max_steps, tokens_out, n_produced, &steps, &last_pos)) return -1;
     if (!steps) return 0;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
@@ -1042,46 +1112,21 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     bool top = false; // ... and one with alternatives: the top form of the finish for all (a row with the count 0 is all padding)
     for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active, lp = lp || per_seq[b].logprobs, top = top || sp[b].top_logprobs;
     const bool constrained = r->n_con != 0; // one sequence with a constraint: the constrained launch for all (a row without one computes what it did)
-    const bool raw_select = penalized || constrained;
     if (!ensure_sample_blocks(ctx, r, B) || ((penalized || constrained) && !ensure_window_block(ctx, r, B))) return -1;
-    if (r->btokens_cap < (uint64_t)B * steps) {
-        hipStreamSynchronize(s);
-        hipFree(r->btokens);
-        r->btokens = nullptr, r->btokens_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->btokens, (size_t)B * steps * 8))) return -1;
-        r->btokens_cap = (uint64_t)B * steps;
-        free_resident_graph(p); // the graphs baked the old pointer
-    }
+    if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * steps)) return -1;
     if (lp && !ensure_logprob_blocks(ctx, p, B, r->btokens_cap)) return -1;
     if (top && !ensure_top_blocks(ctx, p, B, r->btokens_cap)) return -1;
-    const ResidentBatchPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
-                                  p->dyn_dev, r->bstate, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B};
-    const uint32_t total = B * r->d + B * r->max_seq + r->n_rope * B * 2 * r->dh + (uint32_t)p->ops.size();
-    LogprobTarget lt; // (calls with the `logprobs` field only) the values lie as the tokens do: [B][steps]
+    const BatchPrep prep = batch_prep_args(p);
+    SampledTail tail = resident_tail(r, B, SampledTail::sel_of(constrained, penalized), SampledTail::kind_of(lp, top));
+    tail.adv.state = r->bstate, tail.adv.tokens = r->btokens, tail.adv.n_seqs = B;
+    tail.win.ring = r->swin, tail.win.lo = r->swin + (size_t)B * kSamplePenaltyMaxWindow;
+    LogprobTarget& lt = tail.top.chosen; // the values lie as the tokens do, [B][steps], and the pairs as the values
     lt.out = r->lp, lt.state = r->bstate, lt.emitted = r->btokens, lt.written = r->lp_written, lt.n_seqs = B;
-    TopLogprobTarget tt; // (calls with the `top_logprobs` word only) the pairs lie as the values do
-    tt.chosen = lt, tt.top_tok = r->top_tok, tt.top_val = r->top_val, tt.params = r->sparams;
-    SampleAdvance adv;
-    adv.state = r->bstate, adv.tokens = r->btokens, adv.n_seqs = B;
-    SampleWindow win;
-    win.ring = r->swin, win.lo = r->swin + (size_t)B * kSamplePenaltyMaxWindow;
-    const SampleConstraint con = constraint_args(r);
+    tail.top.top_tok = r->top_tok, tail.top.top_val = r->top_val;
     auto one_step = [&](hipStream_t st) {
-        launch_resident_batch_prep(st, a, total);
+        launch_resident_batch_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
-        if (lp) launch_logprob(st, r->logits, r->vocab, B, r->lpart);
-        if (constrained)
-            launch_sample_constrained(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win, con);
-        else if (penalized)
-            launch_sample_penalized(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv, win);
-        else
-            launch_sample(st, r->logits, r->vocab, B, r->skeys, r->sparams, adv);
-        if (top) { // (one sequence with penalties active or a constraint: the raw select for all rows, so the launches stay uniform)
-            if (raw_select) launch_sample_select(st, r->logits, r->vocab, B, r->skeys_raw);
-            launch_logprob_finish_top(st, r->logits, r->vocab, B, r->lpart, raw_select ? r->skeys_raw : r->skeys, tt);
-        } else if (lp) {
-            launch_logprob_finish(st, r->logits, r->vocab, B, r->lpart, lt);
-        }
+        tail.launch(st, r->logits, r->vocab);
     };
     std::vector<uint32_t> win0;
     if (penalized) {
@@ -1097,55 +1142,34 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s)) || // (-1: what a sequence leaves behind its count)
         (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, (size_t)B * 4, s))))
         return -1;
-    const uint32_t form = sampled_form(constrained ? kSelConstrained : penalized ? kSelPenalized : kSelPlain, top ? kKindTop : lp ? kKindLogprobs : kKindPick);
-    hipGraphExec_t& exec = r->sgraph_exec[form];
-    hipGraph_t& graph = r->sgraph[form];
-    if (ctx->opt_graph && !exec) {
-        hipStreamSynchronize(s); // (as the greedy batched loop: no pageable copy in flight when the capture begins)
-        capture_graph(ctx, s, (std::string("resident_batch_") + kSampledFormNames[form]).c_str(), [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
-    }
-    for (uint32_t i = 0; i < steps; i++) {
-        if (exec)
-            hipGraphLaunch(exec, s);
-        else
-            one_step(s);
-    }
+    hipGraphExec_t& exec = r->sgraph_exec[tail.form()];
+    // (as the greedy batched loop: no pageable copy in flight when the capture begins)
+    capture_once(ctx, s, std::string("resident_batch_") + kSampledFormNames[tail.form()], true, one_step, &r->sgraph[tail.form()], &exec);
+    replay(s, exec, steps, one_step);
     std::vector<int64_t> got((size_t)B * steps);
     hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(st1.data(), r->bstate, st1.size() * 4, hipMemcpyDeviceToHost, s);
-    std::vector<float> got_lp(lp ? (size_t)B * steps : 0);
-    if (lp) hipMemcpyAsync(got_lp.data(), r->lp, got_lp.size() * sizeof(float), hipMemcpyDeviceToHost, s);
-    std::vector<uint32_t> top_tok(top ? (size_t)B * steps * kTopLogprobsMax : 0);
-    std::vector<float> top_val(top_tok.size());
-    if (top) {
-        hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
-    }
+    SampledCopyOut out{tail.kind};
+    out.download(s, r, (uint64_t)B * steps);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode_batch_sampled");
     for (uint32_t b = 0; ok && b < B; b++) {
         for (uint32_t i = 0; i < steps; i++) tokens_out[(uint64_t)b * max_steps + i] = got[(uint64_t)b * steps + i];
         if (n_produced) n_produced[b] = std::min(st1[3 * B + b], n_steps[b]);
     }
-    if (lp) ctx->lp_last.assign((size_t)B * max_steps, sample_bits_f32(kLogprobNaNBits)); // [n_seqs][max_steps], as tokens_out
-    for (uint32_t b = 0; b < B; b++) {
-        if (!per_seq[b].logprobs) continue;
-        float* const out = ctx->lp_last.data() + (size_t)b * max_steps;
+    // [n_seqs][max_steps] values, as tokens_out, and [n_seqs][max_steps][width] pairs: the largest count among the sequences; a
+    // sequence with a smaller one, or none, is padded, and one that did not ask keeps the NaN
+    uint32_t width = 0;
+    for (uint32_t b = 0; b < B; b++) width = std::max(width, top_logprobs_count(sp[b].top_logprobs, r->vocab));
+    const auto produced = [&](uint64_t e, bool asked) {
+        const uint32_t b = (uint32_t)(e / max_steps), i = (uint32_t)(e % max_steps);
         const uint32_t made = ok ? std::min(st1[3 * B + b], n_steps[b]) : 0;
-        for (uint32_t i = 0; i < made; i++) out[i] = got_lp[(uint64_t)b * steps + i];
-        logprob_fill_unproduced(out, made, max_steps);
-    }
-    if (top) { // [n_seqs][max_steps][width]: the largest count among the sequences; a sequence with a smaller one, or none, is padded
-        uint32_t width = 0;
-        for (uint32_t b = 0; b < B; b++) width = std::max(width, top_logprobs_count(sp[b].top_logprobs, r->vocab));
-        top_keep(ctx, (uint64_t)B * max_steps, width, top_tok, top_val, [&](uint64_t e) {
-            const uint32_t b = (uint32_t)(e / max_steps), i = (uint32_t)(e % max_steps);
-            const uint32_t made = ok ? std::min(st1[3 * B + b], n_steps[b]) : 0;
-            return sp[b].top_logprobs && i < made ? (int64_t)((uint64_t)b * steps + i) : -1;
-        });
-    }
-    // per step [batched prep] [plan] ([partial]) [select] [merge + pick + advance] ([finish], or ([raw select]) [finish + top])
-    resident_end(p, steps, p->plan.size() + (top ? 5 + raw_select : lp ? 5 : 3));
+        return asked && i < made ? (int64_t)((uint64_t)b * steps + i) : -1;
+    };
+    out.keep(ctx, (uint64_t)B * max_steps, width, [&](uint64_t e) { return produced(e, per_seq[e / max_steps].logprobs); },
+             [&](uint64_t e) { return produced(e, sp[e / max_steps].top_logprobs); });
+    // per step [batched prep] [plan] and the sampled tail
+    resident_end(p, steps, p->plan.size() + 1 + tail.launches());
     return ok ? 0 : -1;
 }
 
@@ -1174,10 +1198,8 @@ int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const 
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->tok_dev, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, s)))
         return -1;
-    ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
-                       p->dyn_dev, r->state, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), n_tokens};
-    const uint64_t total = (uint64_t)n_tokens * r->d + (uint64_t)n_tokens * r->max_seq + (uint64_t)r->n_rope * n_tokens * 2 * r->dh + p->ops.size();
-    launch_resident_prep(s, a, (uint32_t)total);
+    const Prep prep = prep_args(p, r->state, r->tok_dev);
+    launch_resident_prep(s, prep.a, prep.total);
     // through enqueue, not run_plan: one execution per call, so the program's own graphs (captured once, shared with
     // execute_program) are what to replay. dyn_dirty is cleared first: the prep launch has just written the device words, and
     // enqueue's flush_dyn must be a no-op rather than overwrite them with the host mirror
@@ -1261,14 +1283,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             return -1;
     }
     if (sampled && (!ensure_sample_blocks(ctx, r, T) || (!r->picks && !CTX_CHECK(ctx, hipMalloc((void**)&r->picks, (size_t)T * 4))))) return -1;
-    if (r->tokens_cap < n_tokens) {
-        hipStreamSynchronize(s);
-        hipFree(r->tokens);
-        r->tokens = nullptr, r->tokens_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->tokens, (size_t)n_tokens * 8))) return -1;
-        r->tokens_cap = n_tokens;
-        free_resident_graph(p); // the graph baked the old pointer/cap
-    }
+    if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_tokens)) return -1;
     if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens_cap)) return -1;
     if (top && !ensure_top_blocks(ctx, p, T, r->tokens_cap)) return -1;
     uint32_t w0[kSpecWords] = {0};
@@ -1285,68 +1300,48 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
                     !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_tokens * 8, s))))                // (-1: what a stop token leaves behind itself)
         return -1;
     SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap};
-    SampleAdvance adv; // (sampled form only) rows of one sequence: row j samples at the step's run position + j
-    if (sampled) {
+    SampledTail tail; // (sampled form only; the greedy form launches none of it)
+    if (sampled) { // rows of one sequence: row j samples at the step's run position + j and reads parameter row 0
+        tail = resident_tail(r, T, SampledTail::sel_of(false, penalized), SampledTail::kind_of(lp, top));
         sa.picks = r->picks, sa.sparams = r->sparams;
-        adv.picks = r->picks, adv.pos_word = r->spec + kSpecRunPos;
+        tail.adv.picks = r->picks, tail.adv.pos_word = r->spec + kSpecRunPos;
+        // (the `logprobs` field only) every row's value of its pick; the accept launch copies the emitted prefix
+        tail.top.chosen.out = r->lp_rows, tail.top.chosen.picks = r->picks;
+        // (the `top_logprobs` word only) every row's alternatives, likewise
+        tail.top.top_tok = r->top_rows_tok, tail.top.top_val = r->top_rows_val, tail.top.shared_params = 1;
+        // (penalised form only) a row's window is the call's history up to the run position and the candidates behind it
+        tail.win.hist = r->hist, tail.win.cand = r->tok_dev, tail.win.lo_word = r->spec + kSpecHistLo;
     }
-    LogprobTarget lt; // (the `logprobs` field only) every row's value of its pick; the accept launch copies the emitted prefix
-    lt.out = r->lp_rows, lt.picks = r->picks;
     if (lp) sa.lp_rows = r->lp_rows, sa.lp_out = r->lp;
-    TopLogprobTarget tt; // (the `top_logprobs` word only) every row's alternatives, likewise; the rows read parameter row 0
-    tt.chosen = lt, tt.top_tok = r->top_rows_tok, tt.top_val = r->top_rows_val, tt.params = r->sparams, tt.shared_params = 1;
     if (top) sa.top_rows_tok = r->top_rows_tok, sa.top_rows_val = r->top_rows_val, sa.top_tok_out = r->top_tok, sa.top_val_out = r->top_val;
-    SampleWindow win; // (penalised form only) a row's window is the call's history up to the run position and the candidates behind it
-    win.hist = r->hist, win.cand = r->tok_dev, win.lo_word = r->spec + kSpecHistLo;
     // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
-    const ResidentPrepArgs a{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride,
-                             p->dyn_dev, r->spec + kSpecRun, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), T};
-    const uint64_t total = (uint64_t)T * r->d + (uint64_t)T * r->max_seq + (uint64_t)r->n_rope * T * 2 * r->dh + p->ops.size();
+    const Prep prep = prep_args(p, r->spec + kSpecRun, r->tok_dev);
     // the plan enters the step's graph through run_plan, as in resident_decode: many executions per call, with the dynamic words
     // written by the prep launch inside the graph (resident_prefill's enqueue replays the program's own graphs and would flush the
     // host mirror over them unless dyn_dirty is cleared per execution)
     auto one_step = [&](hipStream_t st) {
         launch_spec_draft(st, sa);
-        launch_resident_prep(st, a, (uint32_t)total);
+        launch_resident_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
-        if (lp) launch_logprob(st, r->logits, r->vocab, T, r->lpart);
-        if (penalized)
-            launch_sample_penalized(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv, win);
-        else if (sampled)
-            launch_sample(st, r->logits, r->vocab, T, r->skeys, r->sparams, adv);
+        if (sampled)
+            tail.launch(st, r->logits, r->vocab);
         else
             launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
-        if (top) {
-            if (penalized) launch_sample_select(st, r->logits, r->vocab, T, r->skeys_raw);
-            launch_logprob_finish_top(st, r->logits, r->vocab, T, r->lpart, penalized ? r->skeys_raw : r->skeys, tt);
-        } else if (lp) {
-            launch_logprob_finish(st, r->logits, r->vocab, T, r->lpart, lt);
-        }
         launch_spec_accept(st, sa);
     };
-    const uint32_t form = sampled_form(penalized ? kSelPenalized : kSelPlain, top ? kKindTop : lp ? kKindLogprobs : kKindPick); // (sampled form only)
-    hipGraphExec_t& exec = sampled ? r->sgraph_exec[form] : r->graph_exec;
-    hipGraph_t& graph = sampled ? r->sgraph[form] : r->graph;
-    if (ctx->opt_graph && !exec) {
-        if (sampled) hipStreamSynchronize(s); // (as the sampled loops: no copy from this stack frame in flight when the capture begins)
-        const std::string name = sampled ? std::string("resident_spec_") + kSampledFormNames[form] : std::string("resident_spec");
-        capture_graph(ctx, s, name.c_str(), [&] { one_step(s); }, &graph, &exec); // (failed: eager below)
-    }
+    hipGraphExec_t& exec = sampled ? r->sgraph_exec[tail.form()] : r->graph_exec;
+    hipGraph_t& graph = sampled ? r->sgraph[tail.form()] : r->graph;
+    // (the sampled form waits, as the sampled loops: no copy from this stack frame in flight when the capture begins)
+    capture_once(ctx, s, sampled ? std::string("resident_spec_") + kSampledFormNames[tail.form()] : std::string("resident_spec"), sampled, one_step, &graph, &exec);
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)
     uint32_t w1[kSpecWords] = {0};
-    std::vector<uint32_t> top_tok;
-    std::vector<float> top_val;
+    SampledCopyOut out{tail.kind};
     uint64_t steps_run = 0;
     bool ok = true;
     for (uint32_t produced = 0, wanted = n_tokens; ok && produced < wanted;) {
         const uint32_t round = (wanted - produced + T - 1) / T;
-        for (uint32_t i = 0; i < round; i++) {
-            if (exec)
-                hipGraphLaunch(exec, s);
-            else
-                one_step(s);
-        }
+        replay(s, exec, round, one_step);
         steps_run += round;
         hipMemcpyAsync(w1, r->spec, sizeof(w1), hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
@@ -1358,31 +1353,17 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     }
     if (ok) {
         hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_tokens * 8, hipMemcpyDeviceToHost, s);
-        if (lp) {
-            ctx->lp_last.assign(n_tokens, 0.0f);
-            hipMemcpyAsync(ctx->lp_last.data(), r->lp, (size_t)n_tokens * sizeof(float), hipMemcpyDeviceToHost, s);
-        }
-        if (top) {
-            top_tok.resize((size_t)n_tokens * kTopLogprobsMax), top_val.resize(top_tok.size());
-            hipMemcpyAsync(top_tok.data(), r->top_tok, top_tok.size() * 4, hipMemcpyDeviceToHost, s);
-            hipMemcpyAsync(top_val.data(), r->top_val, top_val.size() * sizeof(float), hipMemcpyDeviceToHost, s);
-        }
+        out.download(s, r, n_tokens);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     }
     ok = ok && ctx->handoff_ok(who.c_str());
-    if (lp) {
-        ctx->lp_last.resize(n_tokens);
-        logprob_fill_unproduced(ctx->lp_last.data(), ok ? std::min(w1[kSpecProduced], n_tokens) : 0, n_tokens);
-    }
-    if (top) {
-        const uint32_t made = ok ? std::min(w1[kSpecProduced], n_tokens) : 0;
-        top_keep(ctx, n_tokens, top_logprobs_count(sp.top_logprobs, r->vocab), top_tok, top_val, [&](uint64_t e) { return e < made ? (int64_t)e : -1; });
-    }
+    const uint32_t made = ok ? std::min(w1[kSpecProduced], n_tokens) : 0;
+    const auto produced = [&](uint64_t e) { return e < made ? (int64_t)e : -1; };
+    out.keep(ctx, n_tokens, top_logprobs_count(sp.top_logprobs, r->vocab), produced, produced);
     if (ok && stats) *stats = zgml_spec_stats{w1[kSpecSteps], w1[kSpecDrafted], w1[kSpecAccepted], 0};
-    if (ok && n_produced) *n_produced = std::min(w1[kSpecProduced], n_tokens);
-    // per step [draft] [prep] [plan] [argmax stage 1] [accept], or [draft] [prep] [plan] [select] [merge + pick] [accept]
-    // (with log-probabilities: [partial] and [finish] as well; with alternatives under penalties: the raw [select] too)
-    resident_end(p, steps_run, p->plan.size() + (top ? 7 + penalized : lp ? 7 : sampled ? 5 : 4));
+    if (ok && n_produced) *n_produced = made;
+    // per step [draft] [prep] [plan] [argmax stage 1] [accept], or the sampled tail in the place of the argmax stage
+    resident_end(p, steps_run, p->plan.size() + 3 + (sampled ? tail.launches() : 1));
     return ok ? 0 : -1;
 }
 
