@@ -123,6 +123,17 @@ AttentionParams make_attention(zgml_hip_program* p, const zgml_op_attention& a, 
     return ap;
 }
 
+// The A-operand hand-over (SplitHook): true when an op behind the producing launch's last member and in front of op i (program
+// order) writes into the rows the matmul at op i reads — a slice_assign, an in-place elementwise or softmax, another chain over
+// a different extent. The operand that launch would emit is then stale by the time the matmul runs: the matmul prepares its own.
+// (Spans as the schedule assumes them: a dynamic store counts with its whole slab. Hooks exist in batched plans only.)
+bool rows_rewritten_after(const zgml_hip_program* p, const Launch& producer, size_t i, const Span& rows) {
+    for (size_t j = (size_t)producer.op_hi + 1; j < i && j < p->sched.access.size(); j++)
+        for (const Span& w : p->sched.access[j].writes)
+            if (spans_overlap(w, rows)) return true;
+    return false;
+}
+
 // launch for a single op of a kind that is never batched
 bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
     const zgml_device_op& op = p->ops[i];
@@ -154,6 +165,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                     fp.scratch = p->scratch;
                     fp.reuse_a = p->split_pos + 1 == pos && p->split_input == dp.a && p->split_M == dp.M && p->split_K == dp.K &&
                                  p->split_in_rs == dp.a_rs && p->split_kind == 2;
+                    const bool adjacent = fp.reuse_a; // the launch at split_pos is the plan's last one: only that one can be joined
                     // ... or the launch that produced the rows wrote the operand itself (as for the quantized split below)
                     if (!fp.reuse_a && sw().hip_fuse_split && dense_f16_a_unpadded(dp.M, dp.K) && dp.a_rs == dp.K) {
                         for (size_t back = p->plan.size(); back-- > 0;) {
@@ -161,6 +173,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                             const bool fits = prev.hook && prev.hook->out == dp.a &&
                                               (prev.hook->rows ? prev.hook->rows == dp.M && prev.hook->cols == dp.K : (uint64_t)dp.M * dp.K == prev.hook->n);
                             if (fits) {
+                                if (rows_rewritten_after(p, prev, i, Span{m.a, m.geom.a_offset, m.geom.a_offset + (uint64_t)dp.M * dp.K})) break;
                                 *prev.hook->ap = (uint16_t*)p->scratch, *prev.hook->ap_S = kApF16 | (dp.K / 32);
                                 if (prev.hook->ap_cols) *prev.hook->ap_cols = dp.K;
                                 fp.reuse_a = 1;
@@ -170,7 +183,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                         }
                     }
                     p->split_pos = pos, p->split_input = dp.a, p->split_M = dp.M, p->split_K = dp.K, p->split_in_rs = dp.a_rs, p->split_kind = 2;
-                    bool joins = fp.reuse_a && p->f16_group && p->f16_group->size() < dense_f16_max_group();
+                    bool joins = adjacent && p->f16_group && p->f16_group->size() < dense_f16_max_group();
                     for (size_t t = 0; joins && t < p->f16_group->size(); t++) joins = dense_f16_can_group((*p->f16_group)[t], fp);
                     if (joins) { // same rows, same K (q/k/v, gate/up): one launch
                         p->f16_group->push_back(fp);
@@ -207,14 +220,19 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
             const bool splits = scratch && qmatmul_scratch_bytes(w, qp.M) != 0;
             qp.reuse_split = splits && p->split_pos + 1 == pos && p->split_input == qp.input && p->split_M == qp.M && p->split_K == qp.K &&
                              p->split_in_rs == qp.in_rs && p->split_kind == 1;
-            // ... or finds them written by the launch that produced the rows (a row chain right in front of it, no other
-            // splitting launch in between): that launch is armed and this one skips its split_a_kernel launch
+            // (a matmul armed through a producer's hook below starts a group of its own: the producer's launch stands between it
+            // and the launch at split_pos, which ran before the producer rewrote the rows)
+            const bool adjacent = qp.reuse_split;
+            // ... or finds them written by the launch that produced the rows (a row chain, an elementwise chain or the attention
+            // tile kernel in front of it; no other splitting launch in between, and no op that rewrites the rows after the
+            // producer's last member: rows_rewritten_after): that launch is armed and this one skips its split_a_kernel launch
             if (splits && !qp.reuse_split && sw().hip_fuse_split && qp.M % 16 == 0 && qp.K % 128 == 0 && qp.in_rs == qp.K) {
                 for (size_t back = p->plan.size(); back-- > 0;) {
                     const Launch& prev = p->plan[back];
                     const bool fits = prev.hook && prev.hook->out == qp.input &&
                                       (prev.hook->rows ? prev.hook->rows == qp.M && prev.hook->cols == qp.K : (uint64_t)qp.M * qp.K == prev.hook->n);
                     if (fits) {
+                        if (rows_rewritten_after(p, prev, i, Span{q.input, q.input_offset, q.input_offset + (uint64_t)qp.M * qp.K})) break;
                         *prev.hook->ap = (uint16_t*)scratch, *prev.hook->ap_S = qp.K / 128;
                         if (prev.hook->ap_cols) *prev.hook->ap_cols = qp.K;
                         qp.reuse_split = 1;
@@ -227,7 +245,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
             if (splits)
                 p->split_pos = pos, p->split_input = qp.input, p->split_M = qp.M, p->split_K = qp.K, p->split_in_rs = qp.in_rs, p->split_kind = 1;
             // ... and joins its launch when the kernel can take another part (same rows, same K: q/k/v, gate/up)
-            bool joins = qp.reuse_split && p->qmm_group && p->qmm_group->size() < qmatmul_max_group();
+            bool joins = adjacent && p->qmm_group && p->qmm_group->size() < qmatmul_max_group();
             for (size_t t = 0; joins && t < p->qmm_group->size(); t++) joins = qmatmul_can_group((*p->qmm_group)[t].first, (*p->qmm_group)[t].second, w, qp);
             if (joins) {
                 p->qmm_group->push_back({w, qp});

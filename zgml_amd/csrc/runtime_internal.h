@@ -26,7 +26,9 @@ namespace zgml_rt {
 extern std::string g_create_error; // (defined in runtime.hip)
 
 // A launch that can also emit its result rows as the A pieces of an M > 1 quantized matmul (kernels.h: RowChainParams::ap):
-// the planner arms it when the matmul that consumes exactly these rows follows with no other splitting launch in between.
+// the planner arms it when the matmul that consumes exactly these rows follows with no other splitting launch in between (it
+// may own the scratch) and no op between the launch's last member and the matmul, in program order, writes a span that meets
+// those rows (plan.hip: rows_rewritten_after) — "no other writer", not only "no other splitter".
 struct SplitHook {
     const float* out = nullptr; // the rows the launch produces (dense: row stride == cols)
     uint32_t rows = 0, cols = 0; // rows == 0: a flat launch over `n` elements, any rows x cols = n of dense rows
