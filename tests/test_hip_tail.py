@@ -1,5 +1,5 @@
 """The opt-in one-launch token tail of the device-resident decode loop (ZGML_HIP_TAIL_FUSED=1: argmax stage 1, the last arriver's
-stage 2, the advance of the device state and the NEXT token's patches in one launch — kernels_generic.hip: argmax_tail_kernel)
+stage 2, the advance of the device state and the NEXT token's patches in one launch — greedy_tail.hip: argmax_tail_kernel)
 against the default four-step tail: the same greedy tokens, from position 0, resumed mid-context, and up to the last position of
 the context (where the fused tail must not prepare a position that does not exist). The switch is read once per process, hence
 the worker processes."""

@@ -287,7 +287,7 @@ struct QMatmulParams {
     uint32_t reuse_split = 0; // M > 1: the scratch already holds this input's A pieces (previous launch, same rows)
 };
 
-// generic kernels (kernels_generic.hip)
+// generic kernels (kernels_generic.hip; argmax and the resident loops' prep: greedy_tail.hip)
 void launch_elementwise(hipStream_t s, uint32_t op, float* dst, const float* s0, const float* s1, uint32_t n);
 void launch_fused_elementwise(hipStream_t s, const FusedParams& p);
 void launch_softmax(hipStream_t s, float* dst, const float* src, uint32_t rows, uint32_t cols);
@@ -542,18 +542,21 @@ struct SampleConstraint {
 };
 // (kSampleMaxSlices, kSampleChunk and sample_slices(n): sample.h, where the rule of the alternatives needs them too)
 inline size_t sample_scratch_keys(uint64_t n, uint32_t rows) { return (size_t)rows * sample_slices(n) * 256; }
-// `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select: sample_slices(n) sorted lists of the 256 largest keys per row]
-// [merge to the row's candidates + pick + advance]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
-void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv);
-// ... with the penalties of params[] applied to the logits before the selection: the same two launches, the first in its
-// penalised form (a kernel of its own), the second as it is
-void launch_sample_penalized(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
-                             const SampleAdvance& adv, const SampleWindow& win);
-// ... with the rows' constraints as well: the first launch in its constrained form (a kernel of its own, which also serves rows
-// without a constraint and rows with or without penalties), the second as it is, advancing the state words behind the pick.
-// Not for the rows of a verify step (adv.picks)
-void launch_sample_constrained(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params,
-                               const SampleAdvance& adv, const SampleWindow& win, const SampleConstraint& con);
+// the power of two >= slices * run, >= run: the keys of a merge over the first `run` keys of each of a row's `slices` lists
+inline uint32_t sample_merge_keys(uint32_t slices, uint32_t run) {
+    uint32_t P = run;
+    while (P < slices * run) P <<= 1;
+    return P;
+}
+// The forms of the select launch, ONE body in three instantiations (sample.hip): the plain one; with the penalties of params[]
+// applied to the logits before the selection (`win`); with the rows' constraints as well (`con`) — that one also serves rows
+// without a constraint and rows with or without penalties, but not the rows of a verify step (adv.picks).
+enum SampledSel { kSelPlain, kSelPenalized, kSelConstrained, kSampledSels };
+// `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select in the form `sel`: sample_slices(n) sorted lists of the 256 largest
+// keys per row] [merge to the row's candidates + pick + advance; the same launch behind every form, with kSelConstrained it
+// advances the state words behind the pick]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
+void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv,
+                   SampledSel sel = kSelPlain, const SampleWindow& win = SampleWindow{}, const SampleConstraint& con = SampleConstraint{});
 // ── log softmax(row)[token] (logprob.hip; the rule is sample.h's) ──
 // [partial]: (m_b, s_b) of every block of 4096 logits of `rows` rows of n logits (row stride n), 1 <= n <= 2^20, into
 // part[rows][logprob_blocks(n)][2]. It reads the logits alone: it may run before or behind the pick.
@@ -579,7 +582,7 @@ struct LogprobTarget {
 };
 void launch_logprob_finish(hipStream_t s, const float* v, uint64_t n, uint32_t rows, const float* part, const LogprobTarget& t);
 // ── the alternatives (top_logprob.hip; the rule is sample.h's) ──
-// [select] alone over the raw rows, the unchanged kernel of launch_sample: what a step with active penalties needs beside its
+// [select] alone over the raw rows, the plain kernel of launch_sample: what a step with active penalties needs beside its
 // penalised lists. scratch: sample_scratch_keys(n, rows) words, a region of its own.
 void launch_sample_select(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch);
 // [finish + top], in the place of [finish]: the chosen token's value exactly where and when launch_logprob_finish would write it

@@ -1,6 +1,7 @@
 // kernels_generic.hip — gfx950 kernels for the DeviceOp kinds that are not the quantized
 // mat-vec: elementwise / fused chains / row-wise norms / reduce / repeat / slice_assign / rope /
-// attention / dense matmul / argmax / copy. One launch per op; fused variants live in fused.hip.
+// attention / dense matmul / copy. One launch per op; fused variants live in fused.hip; the greedy
+// pick and the resident loops' prep launches are greedy_tail.hip's.
 //
 // Semantics follow the reference executor src/backend/reference.zig (cited per kernel). These ops
 // are tiny at decode (d_model..d_ff elements): they are latency-bound, so the kernels favour
@@ -1076,86 +1077,6 @@ __global__ void __launch_bounds__(kBlock) dense_strided_kernel(DenseMatmulParams
     p.dst[(uint64_t)m * p.dst_rs + n] = acc;
 }
 
-// ── argmax: first index of the maximum (strict >), nn.zig:122-138 ──────────────────────────
-constexpr int kArgBlocks = 256;
-
-__device__ __forceinline__ void arg_combine(float& bv, int64_t& bi, float v, int64_t i) {
-    if (v > bv || (v == bv && i < bi)) {
-        bv = v;
-        bi = i;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) argmax_stage1(const float* __restrict__ v, uint64_t n, float* out_val,
-                                                        int64_t* out_idx) {
-    __shared__ float sv[kBlock];
-    __shared__ int64_t si[kBlock];
-    float bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        float x = v[i];
-        if (x > bv || bi == INT64_MAX) { // strict >: earlier index wins within a thread's ascending walk
-            bv = x;
-            bi = (int64_t)i;
-        }
-    }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out_val[blockIdx.x] = sv[0];
-        out_idx[blockIdx.x] = si[0];
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) argmax_stage2(const float* vals, const int64_t* idxs, int nblk,
-                                                        int64_t* out, ArgmaxAdvance adv) {
-    __shared__ float sv[kBlock];
-    __shared__ int64_t si[kBlock];
-    float bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    for (int i = threadIdx.x; i < nblk; i += kBlock)
-        if (idxs[i] != INT64_MAX) {
-            if (bi == INT64_MAX) {
-                bv = vals[i];
-                bi = idxs[i];
-            } else {
-                arg_combine(bv, bi, vals[i], idxs[i]);
-            }
-        }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            if (si[threadIdx.x + off] != INT64_MAX) {
-                if (si[threadIdx.x] == INT64_MAX) {
-                    sv[threadIdx.x] = sv[threadIdx.x + off];
-                    si[threadIdx.x] = si[threadIdx.x + off];
-                } else {
-                    arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const int64_t next = si[0] == INT64_MAX ? -1 : si[0];
-        *out = next;
-        if (adv.state) { // the resident loop's advance step
-            const uint32_t n = adv.state[2];
-            if (n < adv.cap) adv.tokens[n] = next;
-            adv.state[0] = (uint32_t)next;
-            adv.state[1] += 1;
-            adv.state[2] = n + 1;
-        }
-    }
-}
-
 __global__ void __launch_bounds__(kBlock) copy_f4_kernel(float4* __restrict__ dst, const float4* __restrict__ src,
                                                          uint64_t n4) {
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * kBlock)
@@ -1481,263 +1402,6 @@ void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p) {
         else
             dense_strided_kernel<float><<<grid, kBlock, 0, s>>>(p);
     }
-}
-
-namespace {
-// one element of the flat prep index space (kernels.h: ResidentPrepArgs) at position `pos` with the chunk's tokens `tokens`
-__device__ __forceinline__ void resident_prep_element(const ResidentPrepArgs& a, uint32_t i, uint32_t pos, const uint32_t* tokens, uint32_t token0, bool use_token0) {
-    if (i < a.T * a.d) {
-        const uint32_t j = i / a.d, e = i - j * a.d;
-        a.tok_in[i] = a.embed[(uint64_t)(use_token0 ? token0 : tokens[j]) * a.d + e];
-        return;
-    }
-    i -= a.T * a.d;
-    if (i < a.T * a.max_seq) {
-        const uint32_t j = i / a.max_seq, sidx = i - j * a.max_seq;
-        a.mask[i] = sidx <= pos + j ? 0.0f : -INFINITY;
-        return;
-    }
-    i -= a.T * a.max_seq;
-    if (i < a.n_rope * a.T * 2 * a.dh) {
-        const uint32_t l = i / (a.T * 2 * a.dh), rem = i - l * (a.T * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
-        a.rope_bufs[l][rem] = e < a.dh ? a.cos[(uint64_t)(pos + j) * a.dh + e] : a.sin[(uint64_t)(pos + j) * a.dh + e - a.dh];
-        return;
-    }
-    i -= a.n_rope * a.T * 2 * a.dh;
-    if (i < a.n_ops) {
-        if (a.dyn_kind[i] == 1) a.dyn[i] = a.dyn_base[i] + pos * a.dyn_stride[i];
-        if (a.dyn_kind[i] == 2) a.dyn[i] = pos + a.T;
-    }
-}
-__global__ void __launch_bounds__(256) resident_prep_kernel(ResidentPrepArgs a) {
-    resident_prep_element(a, blockIdx.x * 256 + threadIdx.x, a.state[1], a.tokens, 0, false);
-}
-
-// the batched form (kernels.h: ResidentBatchPrepArgs): column j / dynamic op i takes token and position of its own sequence
-__global__ void __launch_bounds__(256) resident_batch_prep_kernel(ResidentBatchPrepArgs a) {
-    uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t* const tok = a.state;
-    const uint32_t* const pos = a.state + a.B;
-    if (i < a.B * a.d) {
-        const uint32_t j = i / a.d, e = i - j * a.d;
-        a.tok_in[i] = a.embed[(uint64_t)tok[j] * a.d + e];
-        return;
-    }
-    i -= a.B * a.d;
-    if (i < a.B * a.max_seq) {
-        const uint32_t j = i / a.max_seq, sidx = i - j * a.max_seq;
-        a.mask[i] = sidx <= pos[j] ? 0.0f : -INFINITY;
-        return;
-    }
-    i -= a.B * a.max_seq;
-    if (i < a.n_rope * a.B * 2 * a.dh) {
-        const uint32_t l = i / (a.B * 2 * a.dh), rem = i - l * (a.B * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
-        a.rope_bufs[l][rem] = e < a.dh ? a.cos[(uint64_t)pos[j] * a.dh + e] : a.sin[(uint64_t)pos[j] * a.dh + e - a.dh];
-        return;
-    }
-    i -= a.n_rope * a.B * 2 * a.dh;
-    if (i < a.n_ops) {
-        const uint32_t kind = a.dyn_kind[i];
-        if (kind == 0) return;
-        const uint32_t ps = pos[a.dyn_seq[i]];
-        a.dyn[i] = kind == 1 ? a.dyn_base[i] + ps * a.dyn_stride[i] : ps + 1;
-    }
-}
-
-// argmax_stage1 / argmax_stage2 over B rows of n values at once: blockIdx.y = row (sequence); same (value, index) ordering
-__global__ void __launch_bounds__(kBlock) argmax_batch_stage1(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx) {
-    __shared__ float sv[kBlock];
-    __shared__ int64_t si[kBlock];
-    const float* row = v + (uint64_t)blockIdx.y * n;
-    float bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        float x = row[i];
-        if (x > bv || bi == INT64_MAX) { // strict >: earlier index wins within a thread's ascending walk
-            bv = x;
-            bi = (int64_t)i;
-        }
-    }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out_val[blockIdx.y * gridDim.x + blockIdx.x] = sv[0];
-        out_idx[blockIdx.y * gridDim.x + blockIdx.x] = si[0];
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) argmax_batch_stage2(const float* vals, const int64_t* idxs, int nblk, uint32_t* state, int64_t* tokens) {
-    __shared__ float sv[kBlock];
-    __shared__ int64_t si[kBlock];
-    const uint32_t b = blockIdx.y, B = gridDim.y;
-    vals += (uint64_t)b * nblk, idxs += (uint64_t)b * nblk;
-    float bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    for (int i = threadIdx.x; i < nblk; i += kBlock)
-        if (idxs[i] != INT64_MAX) {
-            if (bi == INT64_MAX) {
-                bv = vals[i];
-                bi = idxs[i];
-            } else {
-                arg_combine(bv, bi, vals[i], idxs[i]);
-            }
-        }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            if (si[threadIdx.x + off] != INT64_MAX) {
-                if (si[threadIdx.x] == INT64_MAX) {
-                    sv[threadIdx.x] = sv[threadIdx.x + off];
-                    si[threadIdx.x] = si[threadIdx.x + off];
-                } else {
-                    arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { // the advance step of sequence b: only while it has steps left (else it repeats the same token at the same position)
-        const int64_t next = si[0] == INT64_MAX ? -1 : si[0];
-        const uint32_t left = state[2 * B + b], produced = state[3 * B + b], cap = state[4 * B];
-        if (left > 0) {
-            if (produced < cap) tokens[(uint64_t)b * cap + produced] = next;
-            state[b] = (uint32_t)next;
-            state[B + b] += 1;
-            state[2 * B + b] = left - 1;
-            state[3 * B + b] = produced + 1;
-        }
-    }
-}
-
-// argmax_stage1 + (last arriver) argmax_stage2 + advance + the next token's prep (kernels.h: launch_argmax_tail)
-__global__ void __launch_bounds__(kBlock) argmax_tail_kernel(const float* __restrict__ v, uint64_t n, float* vals, int64_t* idxs, uint32_t* cnt, int64_t* out,
-                                                             ArgmaxAdvance adv, ResidentPrepArgs prep, uint32_t prep_total, uint32_t has_prep) {
-    __shared__ float sv[kBlock];
-    __shared__ int64_t si[kBlock];
-    __shared__ uint32_t bc[2];
-    using gu32 = __attribute__((address_space(1))) uint32_t;
-    using gu64 = __attribute__((address_space(1))) unsigned long long;
-    // The next token's patches that depend on its POSITION only — mask column, RoPE rows, dynamic words: everything but the
-    // embedding row — are written here by ALL workgroups (the position is known: state[1] + 1, read before this workgroup's
-    // arrival is counted, i.e. before the last arriver advances it; the plan that read the current token's patches has finished).
-    // Round 5's first form left the whole prep to the last arriver: one workgroup walking 8-16 K elements alone was a longer chain
-    // than the two launches it replaced. What is left for the last arriver is the embedding row of the token it has just found.
-    const uint32_t prep_tok = has_prep ? prep.T * prep.d : 0;
-    if (has_prep && adv.state) {
-        const uint32_t pos_next = adv.state[1] + 1;
-        if (pos_next < prep.max_seq)
-            for (uint32_t i = prep_tok + blockIdx.x * kBlock + threadIdx.x; i < prep_total; i += gridDim.x * kBlock) resident_prep_element(prep, i, pos_next, nullptr, 0, true);
-    }
-    float bv = -INFINITY;
-    int64_t bi = INT64_MAX;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) { // (as argmax_stage1)
-        const float x = v[i];
-        if (x > bv || bi == INT64_MAX) {
-            bv = x;
-            bi = (int64_t)i;
-        }
-    }
-    sv[threadIdx.x] = bv, si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { // publish this workgroup's pair write-through, drain, count (the guide's fan-in form: sc1 payload + vmcnt(0) + agent atomic)
-        __hip_atomic_store((gu32*)vals + blockIdx.x, __float_as_uint(sv[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store((gu64*)idxs + blockIdx.x, (unsigned long long)si[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        bc[0] = __hip_atomic_fetch_add((gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!bc[0]) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // compiler only: the agent-scope loads below stay below the count
-    bv = -INFINITY, bi = INT64_MAX; // ---- stage 2 (as argmax_stage2), every pair read with agent-scope loads
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += kBlock) {
-        const int64_t ix = (int64_t)__hip_atomic_load((gu64*)idxs + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float vx = __uint_as_float(__hip_atomic_load((gu32*)vals + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (ix != INT64_MAX) {
-            if (bi == INT64_MAX)
-                bv = vx, bi = ix;
-            else
-                arg_combine(bv, bi, vx, ix);
-        }
-    }
-    sv[threadIdx.x] = bv, si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off && si[threadIdx.x + off] != INT64_MAX) {
-            if (si[threadIdx.x] == INT64_MAX)
-                sv[threadIdx.x] = sv[threadIdx.x + off], si[threadIdx.x] = si[threadIdx.x + off];
-            else
-                arg_combine(sv[threadIdx.x], si[threadIdx.x], sv[threadIdx.x + off], si[threadIdx.x + off]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const int64_t next = si[0] == INT64_MAX ? -1 : si[0];
-        *out = next;
-        uint32_t pos_next = 0;
-        if (adv.state) { // the resident loop's advance step
-            const uint32_t k = adv.state[2];
-            if (k < adv.cap) adv.tokens[k] = next;
-            adv.state[0] = (uint32_t)next;
-            pos_next = adv.state[1] + 1;
-            adv.state[1] = pos_next;
-            adv.state[2] = k + 1;
-        }
-        __hip_atomic_store((gu32*)cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // re-arm
-        bc[0] = (uint32_t)next, bc[1] = pos_next;
-    }
-    __syncthreads();
-    if (!has_prep) return;
-    const uint32_t token = bc[0], pos = bc[1];
-    if (pos >= prep.max_seq || token >= 0x7FFFFFFFu) return; // (the context is full, or no finite logit: nothing to prepare)
-    for (uint32_t i = threadIdx.x; i < prep_tok; i += kBlock) resident_prep_element(prep, i, pos, nullptr, token, true); // the embedding row(s)
-}
-} // namespace
-
-void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t total) {
-    if (total) resident_prep_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
-}
-
-void launch_resident_batch_prep(hipStream_t s, const ResidentBatchPrepArgs& a, uint32_t total) {
-    if (total) resident_batch_prep_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
-}
-
-int argmax_batch_blocks(uint64_t n) {
-    const int nblk = (int)(n / (kBlock * 4) + 1);
-    return nblk > kArgBlocks ? kArgBlocks : nblk;
-}
-void launch_argmax_batch(hipStream_t s, const float* v, uint64_t n, uint32_t B, float* scratch_val, int64_t* scratch_idx, uint32_t* state, int64_t* tokens) {
-    const int nblk = argmax_batch_blocks(n);
-    argmax_batch_stage1<<<dim3(nblk, B), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
-    argmax_batch_stage2<<<dim3(1, B), kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, state, tokens);
-}
-
-void launch_argmax_rows_stage1(hipStream_t s, const float* v, uint64_t n, uint32_t rows, float* scratch_val, int64_t* scratch_idx) {
-    argmax_batch_stage1<<<dim3(argmax_batch_blocks(n), rows), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
-}
-
-void launch_argmax_tail(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, uint32_t* cnt, int64_t* out,
-                        const ArgmaxAdvance& adv, const ResidentPrepArgs* prep, uint32_t prep_total) {
-    int nblk = (int)(n / (kBlock * 4) + 1);
-    if (nblk > kArgBlocks) nblk = kArgBlocks;
-    argmax_tail_kernel<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx, cnt, out, adv, prep ? *prep : ResidentPrepArgs{}, prep_total, prep ? 1u : 0u);
-}
-
-void launch_argmax(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, int64_t* out, const ArgmaxAdvance& adv) {
-    int nblk = (int)(n / (kBlock * 4) + 1);
-    if (nblk > kArgBlocks) nblk = kArgBlocks;
-    argmax_stage1<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
-    argmax_stage2<<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, out, adv);
 }
 
 void launch_copy_f4(hipStream_t s, void* dst, const void* src, uint64_t bytes) {

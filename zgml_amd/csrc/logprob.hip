@@ -9,12 +9,10 @@
 //              h = 128, 64 in LDS, h = 32 .. 1 as shuffles of wave 0. It stores (m_b, s_b).
 //   [finish]   grid (1, rows), one wave: the row's M (order-free), the blocks' terms s_b * sample_exp(m_b - M) with a lane each,
 //              then lane 0 alone: the sum over ascending b, the token's logit, one f32 store. Which token, and where the value
-//              goes, is LogprobTarget's (kernels.h).
+//              goes, is LogprobTarget's (kernels.h). The kernel is four calls of tail_device.h's finish bodies, which the top
+//              form of this launch (top_logprob.hip) calls too.
 #include "kernels.h"
-#include "sample.h"
-
-#include <hip/hip_runtime.h>
-#include <math.h>
+#include "tail_device.h"
 
 namespace zgml {
 namespace {
@@ -82,40 +80,12 @@ __global__ void __launch_bounds__(kLogprobThreads) logprob_partial_kernel(const 
 __global__ void __launch_bounds__(64) logprob_finish_kernel(const float* __restrict__ v, uint32_t n, uint32_t nb, const float* __restrict__ part, LogprobTarget t) {
     __shared__ float term[kLogprobMaxBlocks];
     const uint32_t row = blockIdx.y, lane = threadIdx.x;
-    // which token, and where its value goes (uniform over the wave)
-    uint32_t tok = 0, produced = 0;
-    float* dst = nullptr;
-    if (t.tokens) {
-        tok = t.tokens[row], dst = t.out + row;
-    } else if (t.token64) {
-        tok = (uint32_t)t.token64[0], dst = t.out;
-    } else if (t.picks) {
-        tok = t.picks[row], dst = t.out + row;
-    } else {
-        // the loops: only the step that emitted a token writes its entry. A frozen sequence's produced count stands still, and the
-        // logits of its later steps are those of another position
-        const uint32_t B = t.n_seqs;
-        produced = B ? t.state[3 * B + row] : t.state[2];
-        const uint32_t cap = B ? t.state[4 * B] : t.cap;
-        if (produced <= t.written[row] || produced > cap) return;
-        const uint64_t at = (uint64_t)(B ? row : 0) * cap + (produced - 1);
-        tok = (uint32_t)t.emitted[at], dst = t.out + at;
-    }
-    const float* pr = part + 2 * (uint64_t)row * nb;
-    float M = -INFINITY;
-    for (uint32_t b = lane; b < nb; b += 64) M = pr[2 * b] > M ? pr[2 * b] : M;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(M, off, 64);
-        M = o > M ? o : M;
-    }
-    for (uint32_t b = lane; b < nb; b += 64) term[b] = logprob_block_term(pr[2 * b], pr[2 * b + 1], M);
+    LogprobSlot slot; // which token, and where its value goes (uniform over the wave)
+    if (!logprob_resolve(t, row, slot)) return;
+    const float M = logprob_row_terms(part + 2 * (uint64_t)row * nb, nb, lane, term);
     __syncthreads();
     if (lane != 0) return;
-    float S = 0.0f;
-    for (uint32_t b = 0; b < nb; b++) S = S + term[b];
-    *dst = tok < n ? logprob_of(v[(uint64_t)row * n + tok], M, S) : sample_bits_f32(kLogprobNaNBits); // (a token is an index of its row: the guard never acts)
-    if (t.written) t.written[row] = produced;
+    logprob_store_chosen(t, slot, row, v + (uint64_t)row * n, n, M, logprob_row_sum(term, nb));
 }
 
 } // namespace

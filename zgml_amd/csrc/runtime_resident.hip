@@ -5,15 +5,14 @@
 // dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
 // copy-out at the end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_once, then
 // replay), resident_end; what follows the plan in a sampled step is stated once, by SampledTail.
-// No kernels here: the prep / pick kernels are in kernels_generic.hip, the plan's and the sampled tail's in their own files.
+// No kernels here: the prep / pick kernels are in greedy_tail.hip, the plan's and the sampled tail's in their own files.
 #include "runtime_internal.h"
 #include "sample.h"
 #include "sample_params.h"
 #include "spec.h"
 
-// the forms of the sampled loops' step: the select launch, and what follows the pick. The constrained select kernel serves rows
-// with and without penalties, so a constrained call has one graph per kind
-enum SampledSel { kSelPlain, kSelPenalized, kSelConstrained, kSampledSels };
+// the forms of the sampled loops' step: the select launch (SampledSel, kernels.h), and what follows the pick. The constrained
+// select kernel serves rows with and without penalties, so a constrained call has one graph per kind
 enum SampledKind { kKindPick, kKindLogprobs, kKindTop, kSampledKinds };
 constexpr uint32_t kSampledForms = kSampledSels * kSampledKinds;
 constexpr uint32_t sampled_form(uint32_t sel, uint32_t kind) { return kind * kSampledSels + sel; }
@@ -413,12 +412,7 @@ struct SampledTail {
     uint32_t launches() const { return 2 + (kind != kKindPick ? 2 : 0) + (kind == kKindTop && raw_select() ? 1 : 0); }
     void launch(hipStream_t st, const float* logits, uint64_t vocab) const {
         if (kind != kKindPick) launch_logprob(st, logits, vocab, rows, part); // (the raw row: it depends on the plan alone)
-        if (sel == kSelConstrained)
-            launch_sample_constrained(st, logits, vocab, rows, keys, params, adv, win, con);
-        else if (sel == kSelPenalized)
-            launch_sample_penalized(st, logits, vocab, rows, keys, params, adv, win);
-        else
-            launch_sample(st, logits, vocab, rows, keys, params, adv);
+        launch_sample(st, logits, vocab, rows, keys, params, adv, sel, win, con);
         if (kind == kKindTop) { // [finish + top] in the place of [finish]: the merge launch only read the lists
             if (raw_select()) launch_sample_select(st, logits, vocab, rows, keys_raw); // (for all rows, so the launches stay uniform)
             launch_logprob_finish_top(st, logits, vocab, rows, part, raw_select() ? keys_raw : keys, top);
@@ -884,7 +878,7 @@ int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* p, uint
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     if (!r->con_rows && (!CTX_CHECK(ctx, hipMalloc((void**)&r->con_rows, (size_t)rows * sizeof(SampleConstraintRow))) ||
-                         !CTX_CHECK(ctx, hipMalloc((void**)&r->con_state, (size_t)rows * 4)) || !CTX_CHECK(ctx, hipMemset(r->con_state, 0, (size_t)rows * 4))))
+                         !CTX_CHECK(ctx, hipMalloc((void**)&r->con_state, (size_t)rows * 4)) || !CTX_CHECK(ctx, hipMemsetAsync(r->con_state, 0, (size_t)rows * 4, s)))) // (on the stream of the uploads below: it is a non-blocking one, which a memset on the null stream is not ordered with)
         return -1;
     r->con.resize(rows, nullptr);
     if (r->con[seq]) r->con[seq]->attached -= 1, r->n_con -= 1;

@@ -425,7 +425,9 @@ constexpr uint32_t kConstraintMaxClasses = 8192;  // a state's row beside the se
 constexpr uint16_t kConstraintForbidden = 0xFFFF; // next[state][class]: the token is not allowed
 
 // is `token` allowed in the state whose row of the table — next + state * n_classes — is `row`?
-ZGML_SAMPLE_FN bool constraint_allowed(const uint16_t* row, const uint16_t* class_of, uint32_t token) { return row[class_of[token]] != kConstraintForbidden; }
+// (the test over a class already read: the select kernel reads class_of through a pointer typed for global memory)
+ZGML_SAMPLE_FN bool constraint_row_allows(const uint16_t* row, uint16_t cls) { return row[cls] != kConstraintForbidden; }
+ZGML_SAMPLE_FN bool constraint_allowed(const uint16_t* row, const uint16_t* class_of, uint32_t token) { return constraint_row_allows(row, class_of[token]); }
 
 // the state behind `token` (an allowed one: else kConstraintForbidden comes back)
 ZGML_SAMPLE_FN uint32_t constraint_advance(const uint16_t* next, uint32_t n_classes, const uint16_t* class_of, uint32_t state, uint32_t token) {

@@ -5,9 +5,7 @@
 // (which tokens are drafted, how many are accepted) are spec.h's; here is only how a workgroup evaluates them.
 #include "kernels.h"
 #include "spec.h"
-
-#include <hip/hip_runtime.h>
-#include <math.h>
+#include "tail_device.h"
 
 namespace zgml {
 namespace {
@@ -68,12 +66,6 @@ __global__ void __launch_bounds__(kSpecBlock) spec_draft_kernel(SpecArgs a) {
     }
 }
 
-// first maximum wins, the order of arg_combine (kernels_generic.hip); a pair with index INT64_MAX is empty
-__device__ __forceinline__ void spec_arg_fold(float& bv, int64_t& bi, float v, int64_t i) {
-    if (i == INT64_MAX) return;
-    if (bi == INT64_MAX || v > bv || (v == bv && i < bi)) bv = v, bi = i;
-}
-
 // g[j] from the nblk stage-1 partials of logits row j (a wave per row, rows kSpecWaves apart) — or, the sampled form, read from
 // a.picks —, then thread 0: how many candidates were the row's choice, what is emitted, and the advance of the state, the history
 // and the counters. The sampled form cuts the emission behind the first stop token and then sets wanted = produced: every later
@@ -87,17 +79,9 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t j = threadIdx.x; a.picks && j < a.T; j += kSpecBlock) g[j] = a.picks[j] < a.vocab ? a.picks[j] : 0u; // (a pick is an index of its row: the clamp never acts)
     for (uint32_t j = threadIdx.x >> 6; !a.picks && j < a.T; j += kSpecWaves) {
-        const float* vals = a.pval + (uint64_t)j * a.nblk;
-        const int64_t* idxs = a.pidx + (uint64_t)j * a.nblk;
-        float bv = -INFINITY;
-        int64_t bi = INT64_MAX;
-        for (uint32_t i = lane; i < a.nblk; i += 64) spec_arg_fold(bv, bi, vals[i], idxs[i]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off, 64);
-            const int64_t oi = __shfl_xor(bi, off, 64);
-            spec_arg_fold(bv, bi, ov, oi);
-        }
+        float bv;
+        int64_t bi;
+        arg_wave_fold(a.pval + (uint64_t)j * a.nblk, a.pidx + (uint64_t)j * a.nblk, a.nblk, lane, bv, bi); // (first maximum wins: tail_device.h)
         if (lane == 0) g[j] = (uint64_t)bi < a.vocab ? (uint32_t)bi : 0u; // (a row always has vocab > 0 entries: the clamp is for the embedding gather's sake)
     }
     __syncthreads();
