@@ -438,7 +438,11 @@ enum {
      * when EVERY qmatmul over it has M <= bound (without the option: M = 1), and a later refresh that raises M above the bound over
      * it is refused. Same results within the mat-vec tolerance. Short-K weights keep the n-on-lanes layout and the tile kernels.
      * Read at compile_program. */
-    ZGML_HIP_OPT_SMALL_M_MATVEC = 11
+    ZGML_HIP_OPT_SMALL_M_MATVEC = 11,
+    /* 0 (default) / 1: zgml_hip_kv_move's 16-byte loads (and, in the copying forms, its 16-byte stores) are non-temporal; the
+     * dword path of unaligned lanes and the few dwords behind a chunk's last 16 bytes stay plain. Measured at Llama-2-7B lanes
+     * (DESIGN.md section 4.9): no difference. Read at every call. */
+    ZGML_HIP_OPT_KV_MOVE_NT = 12
 };
 int zgml_hip_set_option(zgml_hip_ctx* ctx, int option, int64_t value);
 /* Drop the cached device copy of host operand `b` (NULL: all of them). */
@@ -453,6 +457,27 @@ void* zgml_hip_program_buffer_ptr(zgml_hip_program* handle, uint16_t buf_idx);
  * which the reference does through host-visible program memory. Returns 0 on success. */
 int zgml_hip_copy_program_buffer(zgml_hip_ctx* ctx, zgml_hip_program* dst, uint16_t dst_buf, uint64_t dst_offset,
                                  zgml_hip_program* src, uint16_t src_buf, uint64_t src_offset, uint64_t n_elems);
+/* KV admission. A lane is the columns of ONE kv head's K or V cache inside a program buffer: f32 columns of d_head floats back to
+ * back from f32 element `offset` (block_size 0: a kv head's region of a consolidated cache or of a batched plan's slab), or a whole
+ * quantised cache in the layout above (block_size 32, offset 0). The host side lists a plan's lanes per (sequence, layer, kv head,
+ * K | V) (DecodeProgram::kv_lanes), so lane i of two plans of one model is the same head. */
+typedef struct zgml_kv_lane {
+    uint16_t buf, _pad;
+    uint32_t d_head, n_cols, block_size; /* block_size 0: f32 columns; 32: the quantised cache layout, offset must be 0 */
+    uint64_t offset;                     /* f32 elements to column 0 (f32 lanes) */
+} zgml_kv_lane;
+/* Columns [src_col, src_col + n) of src lane i -> columns [dst_col, dst_col + n) of dst lane i, i < n_lanes, in ONE launch on the
+ * context stream (stream-ordered, non-blocking, like zgml_hip_copy_program_buffer). dst and src may be the same program (fork);
+ * a lane pair may not overlap itself. Per lane pair: f32 -> f32 copies the floats; int8 -> int8 copies the column bytes and the
+ * column's scales; f32 -> int8 quantises every column as kvq_store does (the bytes and scales are what that op writes for the
+ * column, with ONE exception: an exact zero in a block whose largest magnitude is below 127 / FLT_MAX = 3.7e-37 becomes 127, as in
+ * the reference, where the device's kvq_store writes -127: zgml_amd/csrc/kvq.h); int8 -> f32 is refused. Admission of a prefill plan's caches into a slot of a batched plan and the fork of a slot
+ * are this one call. Returns 0; -1 with an error on the context, before anything is enqueued, for: a dead or elided buffer, a
+ * d_head mismatch, columns beyond either n_cols, a lane extent beyond its buffer, a block_size other than 0 / 32 (or d_head % 32
+ * on an int8 lane, or an int8 lane with an offset), int8 -> f32, overlapping source and destination ranges of one buffer.
+ * n == 0 or n_lanes == 0 does nothing and returns 0. */
+int zgml_hip_kv_move(zgml_hip_ctx* ctx, zgml_hip_program* dst, const zgml_kv_lane* dst_lanes, zgml_hip_program* src,
+                     const zgml_kv_lane* src_lanes, uint64_t n_lanes, uint32_t src_col, uint32_t dst_col, uint32_t n);
 /* The HIP stream (hipStream_t as void*) the context launches on. */
 void* zgml_hip_stream(zgml_hip_ctx* ctx);
 /* Execute without host I/O and without blocking: enqueue the program on the context stream. */

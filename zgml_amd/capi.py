@@ -317,7 +317,14 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_decode_speculative_sampled", "zgml_hip_logprobs", "zgml_hip_logprobs_result",
     "zgml_hip_top_logprobs", "zgml_hip_top_logprobs_result",
     "zgml_hip_constraint_create", "zgml_hip_constraint_free", "zgml_hip_program_set_constraint", "zgml_hip_program_constraint_state",
+    "zgml_hip_kv_move",
 ]
+
+class KvLaneC(C.Structure):
+    """zgml_kv_lane (include/zgml_hip.h): the columns of one kv head's K or V cache inside a program buffer."""
+    _fields_ = [("buf", C.c_uint16), ("_pad", C.c_uint16), ("d_head", C.c_uint32), ("n_cols", C.c_uint32), ("block_size", C.c_uint32),
+                ("offset", C.c_uint64)]
+
 
 class ShardPointC(C.Structure):
     """zgml_shard_point (include/zgml_hip.h)."""
@@ -336,6 +343,7 @@ OPT_FUSE_RESIDENT_WGS = 8
 OPT_KSPLIT = 9
 OPT_W8A8 = 10
 OPT_SMALL_M_MATVEC = 11
+OPT_KV_MOVE_NT = 12
 
 _PKG_DIR = Path(__file__).resolve().parent
 HIP_LIB_PATH = _PKG_DIR / "lib" / "libzgml_hip.so"
@@ -473,6 +481,8 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_program_set_constraint.argtypes = [vp, vp, u32, vp, u32]
         lib.zgml_hip_program_constraint_state.restype = C.c_int64
         lib.zgml_hip_program_constraint_state.argtypes = [vp, vp, u32]
+    lib.zgml_hip_kv_move.restype = i32
+    lib.zgml_hip_kv_move.argtypes = [vp, vp, C.POINTER(KvLaneC), vp, C.POINTER(KvLaneC), u64, u32, u32, u32]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

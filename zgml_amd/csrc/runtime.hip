@@ -627,6 +627,7 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     ctx->drop_b_cache();
+    free_kv_move_pool(ctx);
     hipFree(ctx->mm_a);
     hipFree(ctx->mm_b);
     hipFree(ctx->mm_c);
@@ -680,6 +681,7 @@ int zgml_hip_set_option(zgml_hip_ctx* ctx, int option, int64_t value) {
         case ZGML_HIP_OPT_SMALL_M_MATVEC: // (same) 1: the measured bound; 2..8: that bound
             ctx->opt_small_m = value <= 0 ? 0 : (value == 1 ? kKonRowsRoutedM : (uint32_t)std::min<int64_t>(value, kKonRowsMaxM));
             return 0;
+        case ZGML_HIP_OPT_KV_MOVE_NT: ctx->opt_kv_move_nt = value != 0; return 0;
         case ZGML_HIP_OPT_DENSE_WEIGHT_CACHE:
             ctx->b_cache_cap = value > 0 ? (uint64_t)value : 0;
             if (!ctx->b_cache_cap) ctx->drop_b_cache();
@@ -1528,7 +1530,10 @@ uint64_t zgml_hip_program_plan_text(zgml_hip_ctx* ctx, zgml_hip_program* p, char
                      q.pair_out ? " pair" : "");
             t += line;
         }
-        if (L.adec_desc) t += L.qmv_desc ? " +decode-attention" : " decode-attention";
+        if (L.adec_desc) { // the head records the launch carries, and their form (kvq: int8 KV caches)
+            snprintf(line, sizeof line, "%s heads %u%s", L.qmv_desc ? " +decode-attention" : " decode-attention", L.adec_desc->nh, L.adec_desc->kvq ? " kvq" : "");
+            t += line;
+        }
         if (L.tag) t += std::string(" ") + L.tag;
         if (L.hook && L.hook->ap && *L.hook->ap) t += " writes-A-operand";
         t += "\n";

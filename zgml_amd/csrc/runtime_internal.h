@@ -145,6 +145,10 @@ struct zgml_hip_ctx {
     std::vector<int64_t> top_tok_last;
     std::vector<float> top_val_last;
     uint32_t top_width_last = 0;
+    // zgml_hip_kv_move (kv_move.hip): the lane-record blocks of its launches (pinned host + device, recycled once their launch's
+    // upload has completed) and ZGML_HIP_OPT_KV_MOVE_NT
+    struct KvMovePool* kv_move_pool = nullptr;
+    bool opt_kv_move_nt = false;
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
     // Fused launches (q/k/v projection + decode attention): ONE host-visible word every bounded in-launch wait sets when it
     // gives up (pinned, device-mapped: the host reads it after any synchronisation without a copy). A set word means the
@@ -333,6 +337,8 @@ void flush_dyn(zgml_hip_program* p);        // p->dyn_host -> p->dyn_dev on the 
 void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count); // launches [first, first + count) of the plan, eagerly
 void enqueue(zgml_hip_program* p);          // the whole program on the context stream (plan ensured, dyn flushed, graph replay when enabled)
 void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx); // a buffer written from outside the op list leaves the hoisted set
+// kv_move.hip
+void free_kv_move_pool(zgml_hip_ctx* ctx); // (zgml_hip_destroy, after the stream has drained)
 // runtime_resident.hip
 void free_resident_graph(zgml_hip_program* p); // the resident loops' captured graphs (they bake the plan: free_graph calls this)
 void free_resident(zgml_hip_program* p);       // p->resident and everything it owns

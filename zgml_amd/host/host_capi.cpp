@@ -95,10 +95,22 @@ zh_model* zh_model_create_ex(const zh_config* cfg, int weight_kind, int fused_el
     return m;
 }
 
+// The decode (token_len 1) / T-token plan over the weights of an existing model (shared, not copied): e.g. the f32 prefill plan
+// beside a batched plan of the same model
+zh_model* zh_model_create_like(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t token_len) {
+    if (token_len > 1 && base->model->cfg.shard_world > 1) return nullptr; // the row-shard driver is decode-only
+    auto* m = new zh_model();
+    m->model = base->model;
+    m->dp = build_decode_program(*m->model, fused_elementwise != 0, include_dead_f32 != 0, token_len ? token_len : 1);
+    m->flat = m->dp->program.view(m->qw_storage);
+    return m;
+}
+
 // The batched decode program of `n_seqs` sequences (build_batch_decode_program). NULL and a text in `err` (cap bytes, NUL-terminated)
-// for what the builder refuses: int8 KV caches, a sharded config, n_seqs outside 1..32.
-zh_model* zh_model_create_batch(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
-                                char* err, uint64_t err_cap) {
+// for what the builder refuses: a config with its own int8 KV caches, a sharded config, n_seqs outside 1..32.
+// kv_quant_block: the builder's parameter (0: f32 slabs; 32: per-sequence int8 caches).
+zh_model* zh_model_create_batch_kvq(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
+                                    uint32_t kv_quant_block, char* err, uint64_t err_cap) {
     auto fail = [&](const std::string& why) -> zh_model* {
         if (err && err_cap) {
             const size_t n = std::min<size_t>(err_cap - 1, why.size());
@@ -115,13 +127,11 @@ zh_model* zh_model_create_batch(const zh_config* cfg, int weight_kind, int fused
     c.kv_quant_block = cfg->kv_quant_block;
     if (c.n_heads == 0 || c.n_kv_heads == 0 || c.d_model % c.n_heads || c.n_heads % c.n_kv_heads) return fail("invalid LlamaConfig");
     // the builder's refusals first: they need no weights
-    if (n_seqs < 1 || n_seqs > kMaxBatchSeqs) return fail("build_batch_decode_program: n_seqs must be 1..32");
-    if (c.kv_quant_block != 0) return fail("build_batch_decode_program: int8 KV caches (kv_quant_block != 0) under batching are out of scope");
-    if (c.shard_world != 1) return fail("build_batch_decode_program: the row shard (shard_world != 1) under batching is out of scope");
+    if (const char* why = batch_refusal(c, n_seqs, kv_quant_block)) return fail(why);
     auto* m = new zh_model();
     m->model = make_synthetic_model(c, (WeightKind)weight_kind, threads);
     std::string why;
-    m->dp = build_batch_decode_program(*m->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why);
+    m->dp = build_batch_decode_program(*m->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why, kv_quant_block);
     if (!m->dp) {
         delete m;
         return fail(why);
@@ -129,10 +139,15 @@ zh_model* zh_model_create_batch(const zh_config* cfg, int weight_kind, int fused
     m->flat = m->dp->program.view(m->qw_storage);
     return m;
 }
+zh_model* zh_model_create_batch(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
+                                char* err, uint64_t err_cap) {
+    return zh_model_create_batch_kvq(cfg, weight_kind, fused_elementwise, include_dead_f32, threads, n_seqs, 0, err, err_cap);
+}
 // ... over the weights of an existing model (shared, not copied): the batched twin of `base` for n_seqs sequences
-zh_model* zh_model_create_batch_like(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, char* err, uint64_t err_cap) {
+zh_model* zh_model_create_batch_like_kvq(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, uint32_t kv_quant_block, char* err,
+                                         uint64_t err_cap) {
     std::string why;
-    auto dp = build_batch_decode_program(*base->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why);
+    auto dp = build_batch_decode_program(*base->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why, kv_quant_block);
     if (!dp) {
         if (err && err_cap) {
             const size_t n = std::min<size_t>(err_cap - 1, why.size());
@@ -146,6 +161,9 @@ zh_model* zh_model_create_batch_like(zh_model* base, int fused_elementwise, int 
     m->dp = std::move(dp);
     m->flat = m->dp->program.view(m->qw_storage);
     return m;
+}
+zh_model* zh_model_create_batch_like(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, char* err, uint64_t err_cap) {
+    return zh_model_create_batch_like_kvq(base, fused_elementwise, include_dead_f32, n_seqs, 0, err, err_cap);
 }
 uint32_t zh_model_n_seqs(zh_model* m) { return m->dp->n_seqs; }
 void zh_model_patch_batch(zh_model* m, const uint32_t* tokens, const uint32_t* pos) { patch_batch_step(*m->model, *m->dp, tokens, pos); }
@@ -207,6 +225,12 @@ uint16_t zh_model_buf(zh_model* m, int which, uint32_t layer) {
 uint64_t zh_model_kv_buffers(zh_model* m, uint16_t* bufs, uint64_t* elems, uint64_t cap) {
     const auto& k = m->dp->kv_buffers;
     for (uint64_t i = 0; i < k.size() && i < cap; i++) bufs[i] = k[i].buf, elems[i] = k[i].elems;
+    return k.size();
+}
+// KV lanes of the plan (DecodeProgram::kv_lanes: sequence, layer, kv head, K | V) in the layout of zgml_kv_lane; returns the count
+uint64_t zh_model_kv_lanes(zh_model* m, zgml_kv_lane* out, uint64_t cap) {
+    const auto& k = m->dp->kv_lanes;
+    for (uint64_t i = 0; i < k.size() && i < cap; i++) out[i] = {k[i].buf, 0, k[i].d_head, k[i].n_cols, k[i].block_size, k[i].offset};
     return k.size();
 }
 uint64_t zh_model_gather_points(zh_model* m, zh_gather_point* out, uint64_t cap) {

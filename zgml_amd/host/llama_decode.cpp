@@ -236,7 +236,9 @@ namespace {
 struct Builder {
     DecodeProgram& dp;
     explicit Builder(DecodeProgram& d) : dp(d) {}
+    bool overflow = false; // more buffers than a 16-bit id names
     uint16_t buffer(uint64_t elems) {
+        if (dp.program.buffer_sizes.size() >= 0xFFFF) overflow = true;
         dp.program.buffer_sizes.push_back(std::max<uint64_t>(elems, 1));
         return (uint16_t)(dp.program.buffer_sizes.size() - 1);
     }
@@ -284,9 +286,11 @@ struct Builder {
 
 // n_seqs == 0: the decode (token_len 1) / prefill (token_len N) plan. n_seqs = B >= 1: the batched decode plan — everything but the
 // attention section is the token_len = B plan (activations [d, B]); the attention section is, per sequence b, the token_len = 1
-// plan's op subsequence on column b, over sequence b's slab of the layer's K / V buffers.
+// plan's op subsequence on column b, over sequence b's slab of the layer's K / V buffers — or, with kv_quant (the batched builder's
+// parameter; 0: the model's own cfg.kv_quant_block), over sequence b's own int8 caches, one buffer per (sequence, kv head, K | V).
+// nullptr when the plan needs more buffers than a 16-bit id names.
 static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, bool fused_elementwise, bool include_dead_f32, uint32_t token_len,
-                                                    uint32_t n_seqs) {
+                                                    uint32_t n_seqs, uint32_t kv_quant = 0) {
     const LlamaConfig& c = model.cfg;
     auto dpp = std::make_unique<DecodeProgram>();
     DecodeProgram& dp = *dpp;
@@ -307,6 +311,8 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
     dp.n_seqs = B;
     const uint32_t TA = B ? 1 : T;       // columns one pass of the attention section handles
     const uint32_t n_pass = B ? B : 1;   // ... and its passes (one per sequence)
+    const uint32_t kvq = kv_quant ? kv_quant : c.kv_quant_block; // quantised KV: one int8 cache buffer per (sequence,) kv head (K and V)
+    std::vector<std::vector<DecodeProgram::KvLane>> lanes(n_pass); // per sequence: (layer, kv head, K | V)
 
     // quantized weight table (all borrowed from the model), or dense f32 weight leaves
     for (const auto& qw : model.qweights) {
@@ -337,10 +343,12 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
         // the backend zero-fills every buffer at compile, so no upload is recorded for them
         // (batched: B such slabs back to back, sequence b's at b * kv_slab — the single-sequence plan's whole buffer)
         const uint64_t kv_slab = (uint64_t)dh * S * KV_loc;
-        const uint16_t k_cache = b.buffer(kv_slab * n_pass), v_cache = b.buffer(kv_slab * n_pass);
+        // (batched int8 plan: the two consolidated buffers keep their ids and hold nothing)
+        const uint64_t f32_elems = kvq && B ? 1 : kv_slab * n_pass;
+        const uint16_t k_cache = b.buffer(f32_elems), v_cache = b.buffer(f32_elems);
         dp.buf_k_cache.push_back(k_cache);
         dp.buf_v_cache.push_back(v_cache);
-        if (!c.kv_quant_block) {
+        if (!kvq) {
             dp.kv_buffers.push_back({k_cache, kv_slab * n_pass});
             dp.kv_buffers.push_back({v_cache, kv_slab * n_pass});
         }
@@ -364,18 +372,27 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
         bool q_done = false;
         bool k_proj_done = false, v_proj_done = false;
         std::vector<uint16_t> attn_out(H_loc);
-        const uint32_t kvq = c.kv_quant_block; // quantised KV: one int8 cache buffer per kv head (K and V)
-        std::vector<uint16_t> kq_cache(KV_loc), vq_cache(KV_loc);
+        std::vector<uint16_t> kq_all((size_t)n_pass * KV_loc), vq_all((size_t)n_pass * KV_loc); // [sequence][kv head]
         if (kvq)
-            for (uint32_t j = 0; j < KV_loc; j++) {
+            for (uint32_t j = 0; j < n_pass * KV_loc; j++) {
                 const uint64_t elems = (uint64_t)S * dh / 4 + (uint64_t)S * (dh / kvq);
-                kq_cache[j] = b.buffer(elems), vq_cache[j] = b.buffer(elems);
-                dp.kv_buffers.push_back({kq_cache[j], elems});
-                dp.kv_buffers.push_back({vq_cache[j], elems});
+                kq_all[j] = b.buffer(elems), vq_all[j] = b.buffer(elems);
+                dp.kv_buffers.push_back({kq_all[j], elems});
+                dp.kv_buffers.push_back({vq_all[j], elems});
             }
         for (uint32_t sq = 0; sq < n_pass; sq++) { // (batched: sequence sq = column sq of the activations; else one pass over all T columns)
             std::vector<char> kv_done(KV_loc, 0);
             const uint32_t seq_slab = sq * (uint32_t)kv_slab; // this sequence's slab of the K / V buffers
+            const uint16_t *kq_cache = kq_all.data() + (size_t)sq * KV_loc, *vq_cache = vq_all.data() + (size_t)sq * KV_loc;
+            for (uint32_t j = 0; j < KV_loc; j++) {
+                if (kvq) {
+                    lanes[sq].push_back({kq_cache[j], 0, dh, S, kvq});
+                    lanes[sq].push_back({vq_cache[j], 0, dh, S, kvq});
+                } else {
+                    lanes[sq].push_back({k_cache, (uint64_t)seq_slab + (uint64_t)j * S * dh, dh, S, 0});
+                    lanes[sq].push_back({v_cache, (uint64_t)seq_slab + (uint64_t)j * S * dh, dh, S, 0});
+                }
+            }
             auto dyn_store = [&](uint32_t seq) { dp.slice_assign_op_indices.push_back((uint32_t)dp.program.ops.size()), dp.slice_assign_seq.push_back(seq); };
             for (int hl = (int)H_loc - 1; hl >= 0; hl--) {
                 const uint32_t h = h0 + hl, kvh = h / n_rep, kvl = kvh - kv0;
@@ -395,7 +412,7 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                     b.op(DeviceOp::rope(k_rot, k_proj, rope_cs, dh / 2, TA, sq * kvd_loc + kvl * dh, sq * 2 * dh, 0, 1, kvd_loc, 2 * dh));
                     const uint32_t slab = seq_slab + kvl * S * dh; // k_cache.sliceColumns(kv_h*max_seq, ...)
                     if (kvq) { // k_cache.storeColumn(pos + j, k_rot[:, j]) (llama_inference.zig:300-320)
-                        for (uint32_t j = 0; j < T; j++) {
+                        for (uint32_t j = 0; j < TA; j++) {
                             dyn_store(sq);
                             b.op(DeviceOp::kvq_store({kq_cache[kvl], k_rot, dh, kvq, S, j * dh, j, j, 1}));
                         }
@@ -408,9 +425,9 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                         v_proj_done = true;
                     }
                     if (kvq) {
-                        for (uint32_t j = 0; j < T; j++) {
+                        for (uint32_t j = 0; j < TA; j++) {
                             dyn_store(sq);
-                            b.op(DeviceOp::kvq_store({vq_cache[kvl], v_proj, dh, kvq, S, j * kvd_loc + kvl * dh, j, j, 1}));
+                            b.op(DeviceOp::kvq_store({vq_cache[kvl], v_proj, dh, kvq, S, (sq + j) * kvd_loc + kvl * dh, j, j, 1}));
                         }
                     } else {
                         dyn_store(sq);
@@ -421,9 +438,9 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                 if (kvq) { // attentionQuantized over the kv head's caches
                     zgml_op_attention_kvq a{};
                     a.dst = attn_out[hl], a.q = q_rot, a.k = kq_cache[kvl], a.v = vq_cache[kvl], a.mask = dp.buf_attn_mask, a.has_mask = 1;
-                    a.d_head = dh, a.seq_q = T, a.seq_kv = S, a.scale = attn_scale, a.block_size = kvq, a.n_cols = S;
+                    a.d_head = dh, a.seq_q = TA, a.seq_kv = S, a.scale = attn_scale, a.block_size = kvq, a.n_cols = S;
                     a.k_col_start = 0, a.v_col_start = 0, a.q_off = 0, a.q_cs = dh, a.dst_off = 0, a.dst_cs = dh;
-                    a.mask_off = 0, a.mask_rs = 1, a.mask_cs = S;
+                    a.mask_off = sq * S, a.mask_rs = 1, a.mask_cs = S;
                     dp.attention_op_indices.push_back((uint32_t)dp.program.ops.size());
                     dp.attention_seq.push_back(sq);
                     b.op(DeviceOp::attention_kvq(a));
@@ -501,7 +518,9 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                                sharded ? v_loc : c.vocab_size);
         if (sharded) dp.gather_points.push_back({(uint32_t)dp.program.ops.size(), dp.buf_logits, 0, v_loc});
     }
+    if (b.overflow) return nullptr;
     dp.program.n_buffers = (uint16_t)dp.program.buffer_sizes.size();
+    for (const auto& seq_lanes : lanes) dp.kv_lanes.insert(dp.kv_lanes.end(), seq_lanes.begin(), seq_lanes.end());
 
     // per-step I/O (device_inference.zig:159-177): token_input, attn_mask, every layer's rope leaf
     auto io = [](uint16_t buf, std::vector<float>& v) {
@@ -521,20 +540,31 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
     return dpp;
 }
 
+const char* batch_refusal(const LlamaConfig& c, uint32_t n_seqs, uint32_t kv_quant_block) {
+    if (n_seqs < 1 || n_seqs > kMaxBatchSeqs) return "build_batch_decode_program: n_seqs must be 1..32";
+    if (c.kv_quant_block != 0)
+        return "build_batch_decode_program: int8 KV caches under batching come from the builder's kv_quant_block parameter, not from a model whose own "
+               "cfg.kv_quant_block != 0";
+    if (kv_quant_block != 0 && (kv_quant_block != 32 || c.d_head() % 32 || ((uint64_t)c.max_seq_len * c.d_head()) % 4))
+        return "build_batch_decode_program: kv_quant_block must be 0 or 32 (int8 KV caches need d_head % 32 == 0)";
+    if (c.shard_world != 1) return "build_batch_decode_program: the row shard (shard_world != 1) under batching is out of scope";
+    return nullptr;
+}
+
 std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, bool fused_elementwise, bool include_dead_f32, uint32_t token_len) {
     return build_program(model, fused_elementwise, include_dead_f32, token_len, 0);
 }
 
 std::unique_ptr<DecodeProgram> build_batch_decode_program(const LlamaModel& model, uint32_t n_seqs, bool fused_elementwise, bool include_dead_f32,
-                                                          std::string* err) {
+                                                          std::string* err, uint32_t kv_quant_block) {
     auto refuse = [&](const char* why) {
         if (err) *err = why;
         return std::unique_ptr<DecodeProgram>();
     };
-    if (n_seqs < 1 || n_seqs > kMaxBatchSeqs) return refuse("build_batch_decode_program: n_seqs must be 1..32");
-    if (model.cfg.kv_quant_block != 0) return refuse("build_batch_decode_program: int8 KV caches (kv_quant_block != 0) under batching are out of scope");
-    if (model.cfg.shard_world != 1) return refuse("build_batch_decode_program: the row shard (shard_world != 1) under batching is out of scope");
-    return build_program(model, fused_elementwise, include_dead_f32, n_seqs, n_seqs);
+    if (const char* why = batch_refusal(model.cfg, n_seqs, kv_quant_block)) return refuse(why);
+    auto dp = build_program(model, fused_elementwise, include_dead_f32, n_seqs, n_seqs, kv_quant_block);
+    if (!dp) return refuse("build_batch_decode_program: the plan needs more than 65535 buffers (fewer sequences, or f32 caches)");
+    return dp;
 }
 
 // LlamaInferencePlan.execute steps 1-4, per sequence: column b of token_input / attn_mask / every rope leaf from (tokens[b], pos[b]),
@@ -554,12 +584,22 @@ void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t
             std::memcpy(leaf.data() + (size_t)b * 2 * dh + dh, model.sin_table.data() + (size_t)pos[b] * dh, dh * sizeof(float));
         }
     }
+    // (the dynamic fields as csrc/schedule.h's dyn_field defines them: a store's offset / column is base + pos * patch_stride, an
+    // attention's seq_kv is pos + 1)
     for (size_t k = 0; k < dp.slice_assign_op_indices.size(); k++) {
-        auto& sa = dp.program.ops[dp.slice_assign_op_indices[k]].u.slice_assign;
-        if (sa.patch_stride != 0) sa.dst_offset = sa.dst_base_offset + pos[dp.slice_assign_seq[k]] * sa.patch_stride;
+        auto& op = dp.program.ops[dp.slice_assign_op_indices[k]];
+        const uint32_t at = pos[dp.slice_assign_seq[k]];
+        if (op.kind == ZGML_DOP_KVQ_STORE) {
+            op.u.kvq_store.col = op.u.kvq_store.col_base + at * op.u.kvq_store.patch_stride;
+            continue;
+        }
+        auto& sa = op.u.slice_assign;
+        if (sa.patch_stride != 0) sa.dst_offset = sa.dst_base_offset + at * sa.patch_stride;
     }
-    for (size_t k = 0; k < dp.attention_op_indices.size(); k++)
-        dp.program.ops[dp.attention_op_indices[k]].u.attention.seq_kv = pos[dp.attention_seq[k]] + 1;
+    for (size_t k = 0; k < dp.attention_op_indices.size(); k++) {
+        auto& op = dp.program.ops[dp.attention_op_indices[k]];
+        (op.kind == ZGML_DOP_ATTENTION_KVQ ? op.u.attention_kvq.seq_kv : op.u.attention.seq_kv) = pos[dp.attention_seq[k]] + 1;
+    }
 }
 
 void patch_step(const LlamaModel& model, DecodeProgram& dp, uint32_t token, uint32_t pos) { patch_tokens(model, dp, &token, pos); }

@@ -93,6 +93,17 @@ struct DecodeProgram {
         uint64_t elems;
     };
     std::vector<KvBuffer> kv_buffers;
+    // every KV lane of the plan: the columns of one kv head's K or V cache, one entry per (sequence, layer, kv head, K | V) in that
+    // nesting order (one sequence outside a batched plan). block_size 0: f32 columns of d_head floats back to back from f32 element
+    // `offset` of `buf` (a kv head's region of a slab); 32: `buf` is a quantised cache (include/zgml_hip.h), offset 0. Filled for
+    // every plan the builder makes, so lane i of one plan and lane i of another plan of the same model hold the same head's columns:
+    // what zgml_hip_kv_move takes (prefill plan -> slot of a batched plan, or slot -> slot).
+    struct KvLane {
+        uint16_t buf;
+        uint64_t offset;
+        uint32_t d_head, n_cols, block_size;
+    };
+    std::vector<KvLane> kv_lanes;
     std::vector<uint32_t> slice_assign_op_indices, attention_op_indices;
     // per entry of the two lists above: the sequence the op belongs to (0 everywhere outside a batched plan)
     std::vector<uint32_t> slice_assign_seq, attention_seq;
@@ -124,11 +135,19 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
 // sequence b, the token_len = 1 plan's op subsequence on column b: seq_len = 1 ropes of column b, K / V stores (patch_stride != 0)
 // into sequence b's slab, attention over that slab and mask column b, row stores into column b. Each layer's K / V buffer holds the
 // B slabs [d_head, max_seq * n_kv] back to back (kv_buffers: same order as the single-sequence plan, B times the elements), so a
-// single-sequence prefill plan hands sequence b its cache by a copy to offset b * slab. int8 KV caches and the row shard are out of
-// scope here: nullptr and a text in *err.
+// single-sequence prefill plan hands sequence b its cache by a copy to offset b * slab.
+// kv_quant_block = 32: every sequence owns int8 caches instead, one buffer per (sequence, kv head, K | V) in the layout of
+// include/zgml_hip.h with n_cols = max_seq, written by kvq_store and read by attention_kvq exactly as in the single-sequence int8
+// plan (kv_buffers: layer, sequence, kv head, K | V). An f32 prefill plan hands a sequence its caches through zgml_hip_kv_move over
+// the two plans' kv_lanes.
+// The one wart: the int8 form is asked for by THIS parameter, while the single-sequence builder reads cfg.kv_quant_block. A model
+// whose own cfg.kv_quant_block != 0 stays refused here (a pinned refusal), so one f32-config model serves an f32 prefill plan and
+// an int8 batched plan. The row shard is out of scope. Refusals: nullptr and a text in *err.
 constexpr uint32_t kMaxBatchSeqs = 32;
 std::unique_ptr<DecodeProgram> build_batch_decode_program(const LlamaModel& model, uint32_t n_seqs, bool fused_elementwise, bool include_dead_f32,
-                                                          std::string* err = nullptr);
+                                                          std::string* err = nullptr, uint32_t kv_quant_block = 0);
+// what the batched builder refuses, from the config alone (no weights needed): the text, or nullptr
+const char* batch_refusal(const LlamaConfig& cfg, uint32_t n_seqs, uint32_t kv_quant_block);
 // tokens[B], pos[B]: the B embedding rows, mask columns and rope columns, and each dynamic op from its own sequence's position
 void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t* tokens, const uint32_t* pos);
 

@@ -50,6 +50,7 @@ def load_host() -> C.CDLL:
         lib.zh_model_create.argtypes, lib.zh_model_create.restype = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.c_int], vp
         lib.zh_model_create_ex.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.c_int, u32]
         lib.zh_model_create_ex.restype = vp
+        lib.zh_model_create_like.argtypes, lib.zh_model_create_like.restype = [vp, C.c_int, C.c_int, u32], vp
         lib.zh_model_patch_tokens.argtypes, lib.zh_model_patch_tokens.restype = [vp, vp, u32], None
         lib.zh_session_prefill.argtypes, lib.zh_session_prefill.restype = [vp, vp, u32, vp], C.c_int64
         lib.zh_model_free.argtypes, lib.zh_model_free.restype = [vp], None
@@ -75,6 +76,11 @@ def load_host() -> C.CDLL:
         lib.zh_model_create_batch.restype = vp
         lib.zh_model_create_batch_like.argtypes = [vp, C.c_int, C.c_int, u32, C.c_char_p, u64]
         lib.zh_model_create_batch_like.restype = vp
+        lib.zh_model_create_batch_kvq.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.c_int, u32, u32, C.c_char_p, u64]
+        lib.zh_model_create_batch_kvq.restype = vp
+        lib.zh_model_create_batch_like_kvq.argtypes = [vp, C.c_int, C.c_int, u32, u32, C.c_char_p, u64]
+        lib.zh_model_create_batch_like_kvq.restype = vp
+        lib.zh_model_kv_lanes.argtypes, lib.zh_model_kv_lanes.restype = [vp, C.POINTER(capi.KvLaneC), u64], u64
         lib.zh_model_n_seqs.argtypes, lib.zh_model_n_seqs.restype = [vp], u32
         lib.zh_model_patch_batch.argtypes, lib.zh_model_patch_batch.restype = [vp, vp, vp], None
         lib.zh_model_dyn_sequences.argtypes, lib.zh_model_dyn_sequences.restype = [vp, C.POINTER(u32), C.POINTER(u32), u64], u64
@@ -109,13 +115,19 @@ class Model:
     n_seqs = 0  # (BatchModel: sequences per step)
 
     def __init__(self, cfg: Config, weight_kind: int = Q4_0, fused_elementwise: bool = True,
-                 include_dead_f32: bool = False, threads: int = 8, token_len: int = 1):
+                 include_dead_f32: bool = False, threads: int = 8, token_len: int = 1, like: "Model" = None):
+        """`like`: build the plan over that model's weights (shared, not generated again; cfg / weight_kind come from it, and it
+        must outlive this one's sessions): e.g. the T-token prefill plan beside a decode or batched plan."""
         self.lib = load_host()
-        self.cfg = cfg
+        self.cfg = like.cfg if like else cfg
         self.token_len = token_len
-        self.build_args = (weight_kind, fused_elementwise, include_dead_f32, threads)
-        self.ptr = self.lib.zh_model_create_ex(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32),
-                                               threads, token_len)
+        if like:
+            self.build_args = like.build_args
+            self.ptr = self.lib.zh_model_create_like(like.ptr, int(like.build_args[1]), int(like.build_args[2]), token_len)
+        else:
+            self.build_args = (weight_kind, fused_elementwise, include_dead_f32, threads)
+            self.ptr = self.lib.zh_model_create_ex(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32),
+                                                   threads, token_len)
         if not self.ptr:
             raise ValueError("invalid LlamaConfig / shard spec")
 
@@ -158,6 +170,25 @@ class Model:
         self.lib.zh_model_kv_buffers(self.ptr, bufs, elems, n)
         return [(int(bufs[i]), int(elems[i])) for i in range(n)]
 
+    def kv_lanes(self, seq: int = None):
+        """capi.KvLaneC array of the plan's KV lanes (DecodeProgram::kv_lanes): one per (sequence, layer, kv head, K | V), in that
+        nesting order; `seq`: that sequence's lanes only. Lane i of two plans of one config is the same head's cache, whatever
+        the plans' forms (decode, T-token, batched; f32 or int8): what Backend-level zgml_hip_kv_move takes."""
+        cache = self.__dict__.setdefault("_kv_lanes", {})  # (a plan's lanes never change: built once per sequence asked for)
+        if seq in cache:
+            return cache[seq]
+        n = self.lib.zh_model_kv_lanes(self.ptr, None, 0)
+        arr = (capi.KvLaneC * max(1, n))()
+        self.lib.zh_model_kv_lanes(self.ptr, arr, n)
+        if seq is None:
+            cache[seq] = (capi.KvLaneC * n)(*arr[:n])
+            return cache[seq]
+        per = n // max(1, self.n_seqs)
+        if not 0 <= seq < max(1, self.n_seqs):
+            raise ValueError(f"kv_lanes: sequence {seq} outside the plan's {max(1, self.n_seqs)}")
+        cache[seq] = (capi.KvLaneC * per)(*arr[seq * per:(seq + 1) * per])
+        return cache[seq]
+
     def quant_bytes(self):
         n = C.c_uint64()
         b = self.lib.zh_model_quant_bytes(self.ptr, C.byref(n))
@@ -166,22 +197,26 @@ class Model:
 
 class BatchModel(Model):
     """Synthetic weights + the BATCHED decode program (`build_batch_decode_program`): one step advances `n_seqs` independent
-    sequences, each with its own KV slab, position and token. ValueError with the builder's text for what it refuses."""
+    sequences, each with its own KV slab, position and token. kv_quant_block=32: every sequence owns int8 KV caches instead of a
+    slab (the builder's parameter; a cfg whose own kv_quant_block != 0 stays refused). ValueError with the builder's text for
+    what it refuses."""
 
     def __init__(self, cfg: Config, n_seqs: int, weight_kind: int = Q4_0, fused_elementwise: bool = True,
-                 include_dead_f32: bool = False, threads: int = 8, like: Model = None):
+                 include_dead_f32: bool = False, threads: int = 8, like: Model = None, kv_quant_block: int = 0):
         """`like`: build the batched program over that model's weights (shared, not generated again; cfg / weight_kind come from it)."""
         self.lib = load_host()
         self.cfg = like.cfg if like else cfg
         self.n_seqs = self.token_len = n_seqs
+        self.kv_quant_block = kv_quant_block
         err = C.create_string_buffer(256)
         if like:
             self.build_args = like.build_args
-            self.ptr = self.lib.zh_model_create_batch_like(like.ptr, int(like.build_args[1]), int(like.build_args[2]), n_seqs, err, len(err))
+            self.ptr = self.lib.zh_model_create_batch_like_kvq(like.ptr, int(like.build_args[1]), int(like.build_args[2]), n_seqs, kv_quant_block,
+                                                               err, len(err))
         else:
             self.build_args = (weight_kind, fused_elementwise, include_dead_f32, threads)
-            self.ptr = self.lib.zh_model_create_batch(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32), threads,
-                                                      n_seqs, err, len(err))
+            self.ptr = self.lib.zh_model_create_batch_kvq(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32), threads,
+                                                          n_seqs, kv_quant_block, err, len(err))
         if not self.ptr:
             raise ValueError(err.value.decode())
 
@@ -208,12 +243,12 @@ class BatchSession:
     (shared, so the model must outlive the session). On the HIP backend the program is compiled with
     ZGML_HIP_OPT_SMALL_M_MATVEC on (`small_m_matvec=False`: the tile kernels; an int: the option's value, e.g. 8 = the row kernel up
     to its widest form) and its sequences are declared; the oracle
-    takes the same program unchanged."""
+    takes the same program unchanged. kv_quant_block: for the batched twin the session builds itself (a BatchModel carries its own)."""
 
-    def __init__(self, model: Model, fns: BackendFns, n_seqs: int, small_m_matvec=True):
+    def __init__(self, model: Model, fns: BackendFns, n_seqs: int, small_m_matvec=True, kv_quant_block: int = 0):
         self.lib, self.fns, self.n_seqs = model.lib, fns, n_seqs
         self._own_model = not (isinstance(model, BatchModel) and model.n_seqs == n_seqs)
-        self.model = BatchModel(model.cfg, n_seqs, like=model) if self._own_model else model
+        self.model = BatchModel(model.cfg, n_seqs, like=model, kv_quant_block=kv_quant_block) if self._own_model else model
         self.is_hip = capi.HIP_LIB_PATH.exists() and fns.compile_program == _fn_addr(capi.load_hip(), "zgml_hip_compile_program")
         hip = capi.load_hip() if self.is_hip else None
         if self.is_hip:  # (read at compile_program; other programs of the context keep the default)
@@ -249,6 +284,28 @@ class BatchSession:
         if self.lib.zh_session_step_batch(self.ptr, t.ctypes.data, p.ctypes.data, logits.ctypes.data, nxt.ctypes.data) != 0:
             raise ValueError("step: token or position out of range")
         return nxt, logits
+
+    # ── KV admission (HIP backend only; include/zgml_hip.h zgml_hip_kv_move) ──
+    def _kv_move(self, dst_lanes, src_handle, src_lanes, src_col, dst_col, n_cols) -> None:
+        if not self.is_hip:
+            raise RuntimeError("kv_move: a HIP session is needed")
+        if len(dst_lanes) != len(src_lanes):
+            raise ValueError(f"kv_move: {len(src_lanes)} source lanes for {len(dst_lanes)} destination lanes (plans of different configs)")
+        hip = capi.load_hip()
+        if hip.zgml_hip_kv_move(self.fns.ctx, self.handle, dst_lanes, src_handle, src_lanes, len(dst_lanes), src_col, dst_col, n_cols) != 0:
+            raise RuntimeError("kv_move: " + (hip.zgml_hip_last_error(self.fns.ctx) or b"").decode())
+
+    def admit(self, seq: int, src_session, n_cols: int, src_seq: int = 0) -> None:
+        """Hand sequence `seq` the first n_cols KV columns of every cache of `src_session` (a Session over a decode or T-token plan
+        of the same config on the same context, or a BatchSession and its sequence `src_seq`), in one launch on the context stream:
+        copied, or quantised when this plan's caches are int8 and the source's f32."""
+        self._kv_move(self.model.kv_lanes(seq), src_session.handle, src_session.model.kv_lanes(src_seq), 0, 0, n_cols)
+
+    def fork(self, src_seq: int, dst_seq: int, n_cols: int) -> None:
+        """Sequence dst_seq takes the first n_cols KV columns of sequence src_seq (n completions of one prompt)."""
+        if src_seq == dst_seq:
+            raise ValueError("fork: source and destination are the same sequence")
+        self._kv_move(self.model.kv_lanes(dst_seq), self.handle, self.model.kv_lanes(src_seq), 0, 0, n_cols)
 
     # ── device-resident loop (HIP backend only; include/zgml_hip.h zgml_hip_resident_decode_batch) ──
     def resident_setup(self, backend) -> None:
