@@ -14,9 +14,9 @@ struct FakeCtx { // the fields read_ctx_switches touches, with the defaults of z
 static void rows(const char* tag) {
     const zgml::Switches& s = zgml::sw();
     printf("%s qmv_xdirect=%d qmm_waves=%d hip_nt_min_bytes=%llu copy_variant=%d hip_elt_vec4_min=%u debug_plan_set=%d debug_plan=%d "
-           "f16_tile3=%d hip_debug_skip_grid=%d hip_skip_kinds=%u graph_dump=%s\n",
+           "qmm_xdl5_trace=%d hip_debug_skip_grid=%d hip_skip_kinds=%u graph_dump=%s\n",
            tag, (int)s.qmv_xdirect, s.qmm_waves, (unsigned long long)s.hip_nt_min_bytes, s.copy_variant, s.hip_elt_vec4_min,
-           (int)s.hip_debug_plan.set, s.hip_debug_plan.value, (int)s.f16_tile3, s.hip_debug_skip_grid, s.hip_skip_kinds,
+           (int)s.hip_debug_plan.set, s.hip_debug_plan.value, (int)s.qmm_xdl5_trace, s.hip_debug_skip_grid, s.hip_skip_kinds,
            s.hip_graph_dump ? s.hip_graph_dump : "(null)");
 }
 static void ctx(const char* tag) {

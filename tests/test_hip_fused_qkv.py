@@ -149,22 +149,3 @@ def test_handoff_timeout_is_loud_and_falls_back(model):
     assert out["launches_after"] == out["plain_launches"], out
     assert out["tokens_equal"] and out["resident_equal"], out
     assert out["kv_equal_after_rerun"], out  # re-running the failed step at the same position rewrites its KV column (zgml_hip.h)
-
-
-@pytest.mark.timeout(600)
-def test_attention_plus_o_projection_launch():
-    """The decode attention + O projection in one launch of 256-thread workgroups (attn_o_kon_kernel; measured slower than two
-    launches and therefore off by default): parity at Llama-2-7B dimensions against the oracle fixtures, short and long context."""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-
-    if os.environ.get("ZGML_HIP_QMV_KON") == "0":
-        pytest.skip("the launch is built from the K-on-lanes mat-vec, which the diagnostic switch under test turns off")
-    worker = Path(__file__).parent / "attn_o_worker.py"
-    trace_lib = Path(__file__).resolve().parent.parent / "zgml_amd" / "lib" / "libzgml_hip_trace.so"  # (the kernel is not in the product library)
-    assert trace_lib.exists(), "run __graft_entry__.build(): it builds the diagnostics library too"
-    r = subprocess.run([sys.executable, str(worker)], capture_output=True, text=True, timeout=580,
-                       env=dict(os.environ, ZGML_HIP_FUSE_ATTN_O="1", ZGML_HIP_LIB=str(trace_lib)))
-    assert r.returncode == 0 and "ATTN_O_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

@@ -92,6 +92,23 @@ def test_resident_decode_equals_vtable_stepping(hip_backend, name, kind):
     m.close()
 
 
+def test_resident_decode_resumes_and_reaches_the_last_position(hip_backend):
+    """The resident loop's token tail (prep, plan, argmax + advance): resuming mid-stream on the warm cache reproduces the
+    stream, and decoding up to the context's last position ends without error (no step prepares a position that does not exist)."""
+    for name, max_seq in (("tiny", 64), ("smollm-135m", 256)):
+        m = llama.Model(llama.preset(name, max_seq), llama.Q4_0, threads=8)
+        s = llama.Session(m, llama.hip_backend_fns(hip_backend))
+        s.resident_setup(hip_backend)
+        a = s.resident_decode(5, 0, 24).tolist()
+        b = s.resident_decode(int(a[11]), 12, 12).tolist()  # resume on the warm cache
+        c = s.resident_decode(7, max_seq - 6, 6).tolist()   # up to the context's last position
+        assert not hip_backend.last_error(), (name, hip_backend.last_error())
+        assert a[12:] == b, name
+        assert len(c) == 6, name
+        s.close()
+        m.close()
+
+
 @pytest.mark.parametrize("kvq", [0, 32])
 def test_dynamic_refresh_equals_full_refresh(hip_backend, kvq):
     """The adapter's per-token refresh — (slice_pos, seq_kv) through zgml_hip_refresh_dynamic, as the reference's wgpu backend

@@ -139,25 +139,6 @@ def test_matmul_wide_outputs_above_32_rows_match_oracle(hip_backend, oracle, M, 
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("knobs", [{}, {"ZGML_QMM_XDL7_MIN_COLS": "1", "ZGML_QMM_XDL7_MIN_RUN": "1"}, {"ZGML_QMM_XDL7_MIN_COLS": "1", "ZGML_QMM_XDL7_MIN_RUN": "1000"}])
-def test_shared_a_experiment_kernel_above_32_rows(knobs):
-    """The round-4 experiment kernel (qmatmul_xdl7_kernel: the M <= 32 form's shared-A work list at 4 / 8 m-tiles per workgroup;
-    measured slower than the K-split kernel, so it exists in the diagnostics library only, ZGML_QMM_XDL7=1) stays parity green:
-    the wide M > 32 cases above, then forced onto every M > 32 case of the tile tests and the 128-token prefill chunk (narrow and
-    ragged outputs, grouped launches) with runs of one step and with whole columns only. A process per setting (switches are read once)."""
-    import os
-    import subprocess
-    import sys
-    from pathlib import Path
-    trace_lib = Path(__file__).resolve().parent.parent / "zgml_amd" / "lib" / "libzgml_hip_trace.so"
-    assert trace_lib.exists(), "run __graft_entry__.build(): it builds the diagnostics library too"
-    env = dict(os.environ, ZGML_HIP_LIB=str(trace_lib), ZGML_QMM_XDL7="1", **knobs)
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "tests/test_hip_qmatvec.py", "tests/test_hip_l7dims.py",
-                        "-k", "tile_kernel or wide_outputs_above_32 or chunk128 or worst_case"], capture_output=True, text=True, timeout=880, env=env)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-
-
-@pytest.mark.timeout(900)
 def test_shared_a_kernel_on_narrow_and_ragged_outputs():
     """The same kernel forced onto every M <= 32 case of this file and of the 7B-dimension file (ZGML_QMM_XDL5_MIN_COLS=1:
     outputs narrower than one workgroup-column, block-column counts that do not fill the last workgroup, grouped q/k/v and

@@ -32,7 +32,7 @@ def table_names():
 
 def test_one_declaration_documented():
     names = table_names()
-    assert len(names) == 98, len(names)
+    assert len(names) == 83, len(names)
     dup = sorted({n for n in names if names.count(n) > 1})
     assert not dup, f"declared more than once: {dup}"
     for src in sorted(CSRC.iterdir()):
@@ -48,7 +48,7 @@ def test_one_declaration_documented():
     assert not missing, f"not in INTEGRATION.md: {missing}"
     # a trace-only row is marked as such in the table of section 9
     trace_only = re.findall(r'trace\("(ZGML_[A-Z0-9_]+)"\)', HEADER.read_text())
-    assert len(trace_only) == 19, trace_only
+    assert len(trace_only) == 5, trace_only
     unmarked = [n for n in trace_only if not re.search(rf"`{n}[^`]*` \(trace\)", doc)]
     assert not unmarked, f"trace-only but not marked (trace) in INTEGRATION.md: {unmarked}"
 
@@ -77,7 +77,7 @@ def python_side_names():
 
 def test_no_stray_names():
     found = python_side_names()
-    assert "ZGML_QMM_XDL7" in found and "ZGML_SHARD_PEER_WAIT_MS" in found and "ZGML_HIP_QMV_KON" in found  # (the scan sees all three forms)
+    assert "ZGML_QMM_XDL5_MIN_COLS" in found and "ZGML_SHARD_PEER_WAIT_MS" in found and "ZGML_HIP_QMV_KON" in found  # (the scan sees all three forms)
     known = set(table_names()) | OTHER_COMPONENTS
     stray = {n: sorted(fs) for n, fs in found.items() if n not in known}
     assert not stray, f"names that no component reads (misspelt?): {stray}"
@@ -107,7 +107,7 @@ def test_defaults_when_unset():
     for trace in (False, True):
         o = run(trace=trace)
         assert o["first"] == {"qmv_xdirect": "1", "qmm_waves": "8", "hip_nt_min_bytes": str(192 << 20), "copy_variant": str(8 | 1 << 8 | 32 << 16),
-                              "hip_elt_vec4_min": str(1 << 20), "debug_plan_set": "0", "debug_plan": "0", "f16_tile3": "0",
+                              "hip_elt_vec4_min": str(1 << 20), "debug_plan_set": "0", "debug_plan": "0", "qmm_xdl5_trace": "0",
                               "hip_debug_skip_grid": "0", "hip_skip_kinds": "0", "graph_dump": "(null)"}
         assert o["ctx_first"] == {"graph": "1", "fusion": "1", "ksplit": "0", "w8a8": "0", "host_prof": "0"}
 
@@ -135,11 +135,11 @@ def test_debug_plan_is_set_even_at_zero():
 
 
 def test_trace_only_rows():
-    env = {"ZGML_F16_TILE3": "1", "ZGML_HIP_DEBUG_SKIP_GRID": "36", "ZGML_HIP_SKIP_KINDS": "0x10"}
+    env = {"ZGML_QMM_XDL5_TRACE": "1", "ZGML_HIP_DEBUG_SKIP_GRID": "36", "ZGML_HIP_SKIP_KINDS": "0x10"}
     o = run(env, trace=False)["first"]
-    assert (o["f16_tile3"], o["hip_debug_skip_grid"], o["hip_skip_kinds"]) == ("0", "0", "0")  # the product build does not look
+    assert (o["qmm_xdl5_trace"], o["hip_debug_skip_grid"], o["hip_skip_kinds"]) == ("0", "0", "0")  # the product build does not look
     o = run(env, trace=True)["first"]
-    assert (o["f16_tile3"], o["hip_debug_skip_grid"], o["hip_skip_kinds"]) == ("1", "36", "16")
+    assert (o["qmm_xdl5_trace"], o["hip_debug_skip_grid"], o["hip_skip_kinds"]) == ("1", "36", "16")
 
 
 def test_latched_on_first_use():

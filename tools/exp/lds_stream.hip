@@ -39,15 +39,15 @@ __global__ void __launch_bounds__(512) stream_regs(const u4v* __restrict__ src, 
 }
 
 // LDS-direct: every wave owns DEPTH KiB of LDS; a load instruction lands 64 lanes x 16 B = 1 KiB at M0 + instruction offset.
-// CONSUME: wave pairs — even waves load, odd waves read the even wave's ring behind a workgroup barrier per round.
-template <int DEPTH, bool CONSUME>
+// READ_BACK: wave pairs — even waves load, odd waves read the even wave's ring behind a workgroup barrier per round.
+template <int DEPTH, bool READ_BACK>
 __global__ void __launch_bounds__(512) stream_lds(const u4v* __restrict__ src, uint64_t items_per_wg, uint32_t* out) {
     extern __shared__ __attribute__((aligned(16))) u4v lds[];
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const uint64_t steps = items_per_wg / 64;
     const u4v* p = src + (uint64_t)blockIdx.x * items_per_wg + lane;
     u4v acc = {0, 0, 0, 0};
-    if (!CONSUME) {
+    if (!READ_BACK) {
         u4v* const ring = lds + (uint64_t)w * DEPTH * 64; // this wave's ring
         for (uint64_t s0 = w; s0 < steps; s0 += (uint64_t)DEPTH * nw) {
 #pragma unroll

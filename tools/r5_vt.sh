@@ -7,9 +7,9 @@ ZGML_HIP_SPIN_WAIT_US=0 python tools/decode_vtable_run.py smollm-135m 512 dyn
 python tools/decode_vtable_run.py smollm-135m 512 dyn
 ZGML_HIP_SPIN_WAIT_US=0 python tools/decode_vtable_run.py smollm-135m 512 dyn
 python tools/decode_run.py smollm-135m 512
-ZGML_HIP_TAIL_FUSED=0 python tools/decode_run.py smollm-135m 512
 python tools/decode_run.py smollm-135m 512
-ZGML_HIP_TAIL_FUSED=0 python tools/decode_run.py smollm-135m 512
+python tools/decode_run.py smollm-135m 512
+python tools/decode_run.py smollm-135m 512
 python tools/decode_run.py llama2-7b 128
-ZGML_HIP_TAIL_FUSED=0 python tools/decode_run.py llama2-7b 128
+python tools/decode_run.py llama2-7b 128
 } 2>&1 | tee $O/vtable_prof4.txt

@@ -279,11 +279,9 @@ struct DecodeHandoff {
     uint32_t need;       // column groups per head slice = d_head / 16
     uint32_t* timeout;   // bumped when a wait gives up
     uint32_t poll_sleep; // s_sleep(1) units (64 clocks) between two polls
-    uint32_t* out_cnt;   // optional: bumped once per head when its output rows (dst2) are stored write-through — the O
-                         // projection's workgroups of the same launch wait for it (qmatvec.hip: QmvWait)
 };
 
-// BLOCK: threads of the workgroup that runs the body (1024 stand-alone; 256 inside the launch that also carries the O projection,
+// BLOCK: threads of the workgroup that runs the body (1024 stand-alone; 256 inside the fused launch of K-on-lanes weights,
 // whose workgroups are 4 waves): at most BLOCK / 64 waves work on a chunk of keys, the loop over steps covers the rest
 template <int LPK, bool KVQ, int BLOCK = kAttnBlock>
 __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __restrict__ params, float* split_buf, uint32_t* split_cnt,
@@ -346,8 +344,7 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
     const uint32_t d2_off = p.dst2 ? ldgu(p.dyn_dst2_off) : 0; // scalar, with the other dynamic words
     // (a fused launch reads the projections' outputs only after the hand-off below; `ho` is a literal nullptr in the
     // stand-alone kernel, so nothing here is a run-time branch there)
-    // (round 3) a hand-off record WITHOUT counters: the projections come from an earlier launch (plain loads, no wait); only its
-    // output side is used — the O projection's workgroups of this launch wait for out_cnt
+    // (a hand-off record WITHOUT counters would mean that the projections come from an earlier launch: plain loads, no wait)
     const bool wait_qkv = ho && ho->cnt;
     float4 q_own, q_par, k_own, k_par, v_new;
     if (!wait_qkv) {
@@ -738,22 +735,9 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
             const float o[4] = {r.acc.x * inv_l, r.acc.y * inv_l, r.acc.z * inv_l, r.acc.w * inv_l};
             stg4(p.dst + 4 * lane, make_float4(o[0], o[1], o[2], o[3])); // dst_rs == 1, 16-byte aligned (planner)
             if (p.dst2) {
-                const bool through = ho && ho->out_cnt; // consumers in this launch: write-through (agent scope)
 #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    float* const d = p.dst2 + (uint64_t)d2_off + (uint64_t)(4 * lane + e) * p.d2_rs;
-                    if (through)
-                        __hip_atomic_store((__attribute__((address_space(1))) float*)d, o[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else
-                        stg1(d, o[e]);
-                }
+                for (int e = 0; e < 4; e++) stg1(p.dst2 + (uint64_t)d2_off + (uint64_t)(4 * lane + e) * p.d2_rs, o[e]);
             }
-        }
-        if (ho && ho->out_cnt) { // the head's rows have left this wave: tell the O projection
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-            if (lane == 0) __hip_atomic_fetch_add((gu32*)ho->out_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     ATTN_STAMP(7);

@@ -256,10 +256,12 @@ __global__ void __launch_bounds__(kBlock) pack_a_f16_kernel(const float* __restr
     }
 }
 
-// SINK (diagnostics build, ZGML_F16_SINK=1 / 2): the same kernel with its MFMAs replaced by a vector-ALU sink of the operands
-// (1: xor of every loaded dword into the accumulators) or with the A loads gone as well (2) — WRONG results by construction;
-// separates what the matrix instructions cost the stream from what the memory path costs.
-template <int R, bool NT, int CG = 1, int SINK = 0>
+// What paces this kernel (the sink experiment of round 4, removed since): with its MFMAs replaced by a vector-ALU
+// sink of the operands (an xor of every loaded dword into the accumulators) the stream was UNCHANGED; with the A operand's global
+// loads gone as well it rose to 5.6 TB/s from 3.6-4.4 — not the matrix instructions, the R KiB of L2 hits per KiB of weights
+// through the CU's one vector-memory path. (Taking A out of that path — shared through LDS, or stationary in LDS — was measured
+// no faster all the same; those two forms are removed too.)
+template <int R, bool NT, int CG = 1>
 __global__ void __launch_bounds__(512) dense_f16_tile2_kernel(F16Args2 a) {
     // chunks in flight per wave, (CG + R) x 16 B per lane each (8 measured no faster at R = 2). R = 4 / 8 (prefill chunks of
     // 64 / 128 tokens): all m-tiles in one workgroup, so the weights are read ONCE per matmul instead of once per tile pair
@@ -300,7 +302,7 @@ __global__ void __launch_bounds__(512) dense_f16_tile2_kernel(F16Args2 a) {
             }
         }
 #pragma unroll
-        for (int t = 0; t < R; t++) x.av[t] = SINK == 2 ? make_uint4(cc, 1u, 2u, 3u) : ap[t * tile_stride + (uint64_t)cc * 64];
+        for (int t = 0; t < R; t++) x.av[t] = ap[t * tile_stride + (uint64_t)cc * 64];
     };
     mfma_f4 acc[R][CG];
 #pragma unroll
@@ -322,15 +324,8 @@ __global__ void __launch_bounds__(512) dense_f16_tile2_kernel(F16Args2 a) {
                 for (int j = 0; j < CG; j++) {
                     const half8 bv = __builtin_bit_cast(half8, cur.b[j]);
 #pragma unroll
-                    for (int t = 0; t < R; t++) {
-                        if (SINK) { // four vector-ALU instructions per (tile, column group) instead of one MFMA
-                            const uint4 bq = cur.b[j], aq = cur.av[t];
-                            acc[t][j][0] = __uint_as_float(__float_as_uint(acc[t][j][0]) ^ bq.x ^ aq.x), acc[t][j][1] = __uint_as_float(__float_as_uint(acc[t][j][1]) ^ bq.y ^ aq.y);
-                            acc[t][j][2] = __uint_as_float(__float_as_uint(acc[t][j][2]) ^ bq.z ^ aq.z), acc[t][j][3] = __uint_as_float(__float_as_uint(acc[t][j][3]) ^ bq.w ^ aq.w);
-                        } else {
-                            acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, cur.av[t]), bv, acc[t][j], 0, 0, 0);
-                        }
-                    }
+                    for (int t = 0; t < R; t++)
+                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, cur.av[t]), bv, acc[t][j], 0, 0, 0);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -351,300 +346,6 @@ __global__ void __launch_bounds__(512) dense_f16_tile2_kernel(F16Args2 a) {
         if (m < a.M) P.out[(uint64_t)m * P.out_rs + n] = sum;
     }
 }
-
-constexpr int kT3Chunks = 4; // (the experiment below) 32-k chunks per stage: 512 threads x 16 B = 4 chunks x R = 2 tiles x 1 KiB
-constexpr int kT3Waves = 8;
-#ifdef ZGML_TRACE // diagnostics build only: MEASURED NO FASTER than the form above (tools/f16_m32_sweep.sh)
-// ── M <= 32, third form (round 4 experiment): A SHARED through LDS, K split over workgroups ─────────────────────────────
-// Result: 32 x 4096 x 22016 46.2 us against 42.6 (two column groups per workgroup above), 4096^2 15.5 against 13.2, K = 11008
-// 25.3 against 27.4 at 8 slices: taking seven eighths of the A traffic out of the vector-memory path did NOT raise the stream
-// (4.0-4.5 TB/s either way, a read-only stream of the same access shape does 6.5) — the A re-read is not what paces the launch.
-// The hypothesis it was built on: what paces the form above (3.6 TB/s at 32 x 4096 x 22016) is the A operand:
-// every workgroup (16 columns) re-reads the whole pre-laid-out A from L2 — R KiB per 1 KiB of weights — through the CU's one
-// vector-memory return path. Here a workgroup owns 8 column groups (128 columns: one per wave) and a SLICE of K:
-//   * all eight waves work on the SAME 32-k chunks, so a chunk's A operand (R KiB) is fetched from L2 ONCE per workgroup, by
-//     one 16-byte load per thread for a stage of kT3Chunks chunks, parked in LDS (two stages: one barrier per stage) and read
-//     back by every wave with ds_read_b128: A : B through the vector-memory path drops from R : 1 to R : 8;
-//   * a wave streams only its own column group's weights (1 KiB per chunk, two stages in flight) and owns its 16 x 16R output
-//     tile: no cross-wave fold;
-//   * the grid is (column tiles, K slices): enough workgroups for every CU although a tile is 128 columns wide. A K split
-//     publishes partial tiles (write-through stores, drained, one agent-scope add on the tile's counter); the LAST arriver
-//     sums the slices IN SLICE ORDER (deterministic: two executions agree bit for bit) and stores.
-struct F16Args3 {
-    F16Part2 parts[kMaxF16Parts]; // block_begin in COLUMN TILES (8 column groups)
-    const uint4* ap;              // pack_a_f16_kernel output: [tile][KC][64] uint4
-    float* partial;               // [column tile][slice][wave][R][4][64] floats
-    uint32_t* counter;            // one word per column tile, zero between launches
-    uint32_t n_parts, M, KC, SK, chunks_per_slice;
-};
-template <int R, bool NT>
-__global__ void __launch_bounds__(kT3Waves * 64) dense_f16_tile3_kernel(F16Args3 a) {
-    static_assert(R * kT3Chunks * 64 == kT3Waves * 64, "one 16-byte A load per thread and stage");
-    __shared__ uint4 lds_a[3][kT3Chunks * R * 64]; // three stages: the one being multiplied, the next (already parked), the one after (in flight)
-    __shared__ uint32_t flag;
-    const uint32_t lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t pi = 0;
-#pragma unroll
-    for (uint32_t t = 1; t < (uint32_t)kMaxF16Parts; t++)
-        if (t < a.n_parts && blockIdx.x >= a.parts[t].block_begin) pi = t;
-    const F16Part2& P = a.parts[pi];
-    const uint32_t tile = blockIdx.x - P.block_begin, g = tile * kT3Waves + w, slice = blockIdx.y;
-    const uint32_t c_begin = slice * a.chunks_per_slice, c_end = min(c_begin + a.chunks_per_slice, a.KC), c_last = a.KC - 1;
-    const uint4* const bp = P.bp + (uint64_t)g * a.KC * 64 + lane;
-    // this thread's share of a stage's A: chunk (tid / (R * 64)), tile ((tid / 64) % R), lane
-    const uint32_t a_cc = threadIdx.x / (R * 64), a_t = (threadIdx.x >> 6) % R;
-    const uint4* const ap = a.ap + (uint64_t)a_t * a.KC * 64 + lane;
-    auto load_a = [&](uint32_t c0) { return ap[(uint64_t)min(c0 + a_cc, c_last) * 64]; };
-    struct BStage {
-        uint4 b[kT3Chunks];
-    };
-    auto load_b = [&](BStage& x, uint32_t c0) { // clamped, unconditional; chunks past the slice's end are never multiplied
-#pragma unroll
-        for (int j = 0; j < kT3Chunks; j++) {
-            const uint4* const src = bp + (uint64_t)min(c0 + j, c_last) * 64;
-            if (NT) {
-                typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-                const u4v v = __builtin_nontemporal_load((const u4v*)src);
-                x.b[j] = make_uint4(v.x, v.y, v.z, v.w);
-            } else {
-                x.b[j] = *src;
-            }
-        }
-    };
-    mfma_f4 acc[R];
-#pragma unroll
-    for (int t = 0; t < R; t++) acc[t] = mfma_f4{0.f, 0.f, 0.f, 0.f};
-    // two stages of weights in flight per wave beside the one being multiplied (with one, a workgroup keeps 4 KiB per wave in
-    // flight and the stream starves: Little's law)
-    BStage cur, n1, n2;
-    uint4 a0 = load_a(c_begin);
-    load_b(cur, c_begin);
-    uint4 a1 = load_a(c_begin + kT3Chunks);
-    load_b(n1, c_begin + kT3Chunks);
-    lds_a[0][threadIdx.x] = a0;
-    __syncthreads();
-    uint32_t buf = 0;
-    for (uint32_t c0 = c_begin; c0 < c_end; c0 += kT3Chunks) {
-        const uint4 a2 = load_a(c0 + 2 * kT3Chunks);
-        load_b(n2, c0 + 2 * kT3Chunks);
-        __builtin_amdgcn_sched_barrier(0); // the stage after next is requested before this one is multiplied
-#pragma unroll
-        for (int j = 0; j < kT3Chunks; j++) {
-            if (c0 + j < c_end) { // (scalar: c0, c_end are wave-uniform)
-                const half8 bv = __builtin_bit_cast(half8, cur.b[j]);
-#pragma unroll
-                for (int t = 0; t < R; t++)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, lds_a[buf][(j * R + t) * 64 + lane]), bv, acc[t], 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const uint32_t nb = buf == 2 ? 0 : buf + 1;
-        lds_a[nb][threadIdx.x] = a1; // (that buffer was last read two stages ago: every wave has passed a barrier since)
-        __syncthreads();
-        cur = n1, n1 = n2, a1 = a2;
-        buf = nb;
-    }
-    // D[m = 16 t + 4 (lane / 16) + v][n = 16 g + lane % 16] in acc[t][v]
-    if (a.SK > 1) {
-        using gf32 = __attribute__((address_space(1))) float;
-        using gu32 = __attribute__((address_space(1))) unsigned int;
-        constexpr uint32_t WT = R * 256; // floats of one wave's tile
-        float* const mine = a.partial + (((uint64_t)blockIdx.x * a.SK + slice) * kT3Waves + w) * WT + lane;
-#pragma unroll
-        for (int t = 0; t < R; t++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) __hip_atomic_store((gf32*)(mine + (t * 4 + v) * 64), acc[t][v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave drains before the count
-        __syncthreads();
-        if (threadIdx.x == 0) flag = __hip_atomic_fetch_add((gu32*)(a.counter + blockIdx.x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (flag != a.SK - 1) return; // not the last slice of this column tile
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // compiler only: the loads below stay below the count
-#pragma unroll
-        for (int t = 0; t < R; t++) acc[t] = mfma_f4{0.f, 0.f, 0.f, 0.f};
-        const float* const base = a.partial + (((uint64_t)blockIdx.x * a.SK) * kT3Waves + w) * WT + lane;
-        for (uint32_t s0 = 0; s0 < a.SK; s0 += 4) { // slice order, four slices' loads in flight together
-            float pv[4][R * 4];
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++) {
-                const uint32_t sl = min(s0 + q, a.SK - 1);
-#pragma unroll
-                for (int e = 0; e < R * 4; e++)
-                    pv[q][e] = __hip_atomic_load((gf32*)(base + (uint64_t)sl * kT3Waves * WT + e * 64), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q++)
-#pragma unroll
-                for (int t = 0; t < R; t++)
-#pragma unroll
-                    for (int v = 0; v < 4; v++) acc[t][v] += s0 + q < a.SK ? pv[q][t * 4 + v] : 0.f;
-        }
-        if (threadIdx.x == 0) __hip_atomic_store((gu32*)(a.counter + blockIdx.x), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // re-arm
-    }
-#pragma unroll
-    for (int t = 0; t < R; t++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const uint32_t m = t * 16 + 4 * (lane >> 4) + v, n = g * 16 + (lane & 15);
-            if (m < a.M) P.out[(uint64_t)m * P.out_rs + n] = acc[t][v];
-        }
-}
-
-#endif // ZGML_TRACE
-
-#ifdef ZGML_TRACE // diagnostics build only (ZGML_F16_TILE4=1): parity green, MEASURED within +-5 % of the shipped form on wide outputs and
-                  // 28 % slower at 4096 x 4096 (profiles/r04_f16_m32_tile4.txt) — the A loads it removes are not all that paces the stream
-// ── M <= 32, fourth form (round 4 experiment): A STATIONARY in LDS ──────────────────────────────────────────────────────
-// The sink experiment (tools/f16_sink.sh) says what paces the forms above: not the MFMAs (replaced by a VALU sink: unchanged),
-// the A operand's GLOBAL loads (gone as well: 5.6 TB/s instead of 3.6-4.4) — R KiB of L2 hits per KiB of weights through the CU's
-// one vector-memory path. Here that path carries weights only:
-//   * one workgroup per CU (16 waves; its dynamic LDS is sized to keep a second one out) owns a K SLICE of <= 64 chunks and
-//     loads that slice of the pre-laid-out A (<= 128 KiB) into LDS ONCE; one barrier, then no A load and no barrier again;
-//   * a wave's work is a list of TASKS = (column group, this slice): the column groups cb, cb + n_cwg, ... of the workgroup's
-//     column class are dealt to its waves round-robin; per 32-k chunk a wave issues one 16-byte weight load per lane (1 KiB per
-//     wave-instruction, DEPTH in flight, the ring runs on across task boundaries), reads its two A operands from LDS
-//     (ds_read_b128, lane-contiguous: conflict-free) and issues two MFMAs; it owns its 16 x 32 output tile: no cross-wave fold;
-//   * K slices: as many as give every CU ~10 tasks (the tasks, not the workgroups, carry the parallelism). A split K publishes
-//     each task's partial tile (write-through stores, drained by the storing wave, one agent-scope add on the column group's
-//     counter); the LAST arriver of a column group sums ALL slices in slice order — its own included — so two executions agree
-//     bit for bit, stores, and re-arms the counter.
-#endif
-constexpr int kT4Waves = 16, kT4MaxSliceChunks = 64, kT4Depth = 4;
-#ifdef ZGML_TRACE
-struct F16Args4 {
-    F16Part2 parts[kMaxF16Parts]; // block_begin in COLUMN GROUPS
-    const uint4* ap;              // pack_a_f16_kernel output: [tile][KC][64] uint4
-    float* partial;               // [column group][slice][2][4][64] floats
-    uint32_t* counter;            // one word per column group, zero between launches
-    uint32_t n_parts, M, KC, SK, chunks_per_slice, n_cwg, total_groups;
-};
-template <bool NT, int kT4Depth = 4>
-__global__ void __launch_bounds__(kT4Waves * 64) dense_f16_tile4_kernel(F16Args4 a) {
-    constexpr int R = 2;
-    extern __shared__ uint4 lds_a4[]; // [chunk of the slice][R][64]
-    const uint32_t lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t slice = blockIdx.x % a.SK, cb = blockIdx.x / a.SK;
-    const uint32_t c_begin = slice * a.chunks_per_slice, c_end = min(c_begin + a.chunks_per_slice, a.KC), S = c_end - c_begin;
-    // this wave's tasks: column groups cb + (w + kT4Waves * r) * n_cwg, r = 0, 1, ... (< total_groups)
-    const uint32_t g_first = cb + w * a.n_cwg, g_step = kT4Waves * a.n_cwg;
-    const uint32_t n_tasks = g_first < a.total_groups ? (a.total_groups - 1 - g_first) / g_step + 1 : 0;
-    auto part_of = [&](uint32_t g, uint32_t& gl) -> const F16Part2& { // (<= 3 parts: selects, no loop-carried lookups)
-        uint32_t pi = 0;
-#pragma unroll
-        for (uint32_t t = 1; t < (uint32_t)kMaxF16Parts; t++)
-            if (t < a.n_parts && g >= a.parts[t].block_begin) pi = t;
-        gl = g - a.parts[pi].block_begin;
-        return a.parts[pi];
-    };
-    auto b_src = [&](uint32_t task, uint32_t c) -> const uint4* { // weights of chunk c_begin + c of task `task` (clamped: in bounds)
-        const uint32_t g = min(g_first + task * g_step, a.total_groups - 1);
-        uint32_t gl;
-        const F16Part2& P = part_of(g, gl);
-        return P.bp + ((uint64_t)gl * a.KC + min(c_begin + c, a.KC - 1)) * 64 + lane;
-    };
-    auto wl = [&](const uint4* src) {
-        if (NT) {
-            typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-            const u4v v = __builtin_nontemporal_load((const u4v*)src);
-            return make_uint4(v.x, v.y, v.z, v.w);
-        }
-        return *src;
-    };
-    // the weight ring starts before the A slice is in LDS (its first loads fly while A is fetched)
-    uint4 ring[kT4Depth];
-    uint32_t lt = 0, lc = 0; // (task, chunk) of the next load
-    auto advance = [&](uint32_t& t, uint32_t& c) {
-        if (++c == S) c = 0, t++;
-    };
-    if (n_tasks) {
-#pragma unroll
-        for (int d = 0; d < kT4Depth; d++) {
-            ring[d] = wl(b_src(min(lt, n_tasks - 1), lc));
-            advance(lt, lc);
-        }
-    }
-    // A slice -> LDS: item (c, t, lane) of the slice from ap[t][c_begin + c][lane]
-    for (uint32_t i = threadIdx.x; i < S * R * 64; i += kT4Waves * 64) {
-        const uint32_t l = i & 63, t = (i >> 6) % R, c = i / (R * 64);
-        lds_a4[i] = a.ap[((uint64_t)t * a.KC + c_begin + c) * 64 + l];
-    }
-    __syncthreads();
-    if (!n_tasks) return;
-    using gf32 = __attribute__((address_space(1))) float;
-    using gu32 = __attribute__((address_space(1))) unsigned int;
-    for (uint32_t task = 0; task < n_tasks; task++) {
-        mfma_f4 acc[R] = {mfma_f4{0.f, 0.f, 0.f, 0.f}, mfma_f4{0.f, 0.f, 0.f, 0.f}};
-        for (uint32_t c0 = 0; c0 < S; c0 += kT4Depth) {
-#pragma unroll
-            for (int d = 0; d < kT4Depth; d++) {
-                const uint4 bq = ring[d];
-                ring[d] = wl(b_src(min(lt, n_tasks - 1), lc)); // refill the slot just read (runs on into the next task; clamped past the end)
-                advance(lt, lc);
-                __builtin_amdgcn_sched_barrier(0);
-                if (c0 + d < S) { // (scalar)
-                    const half8 bv = __builtin_bit_cast(half8, bq);
-#pragma unroll
-                    for (int t = 0; t < R; t++)
-                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, lds_a4[((c0 + d) * R + t) * 64 + lane]), bv, acc[t], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // (S need not be a multiple of the depth: the ring slots consumed past S belong to the next task's first chunks — realign)
-        if (S % kT4Depth) { // rare (K / 32 not a multiple of 4 per slice): restart the ring at the next task's first chunk
-            lt = task + 1, lc = 0;
-#pragma unroll
-            for (int d = 0; d < kT4Depth; d++) {
-                ring[d] = wl(b_src(min(lt, n_tasks - 1), lc));
-                advance(lt, lc);
-            }
-        }
-        const uint32_t g = g_first + task * g_step;
-        uint32_t gl;
-        const F16Part2& P = part_of(g, gl);
-        if (a.SK > 1) {
-            constexpr uint32_t WT = R * 256;
-            float* const mine = a.partial + ((uint64_t)g * a.SK + slice) * WT + lane;
-#pragma unroll
-            for (int t = 0; t < R; t++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) __hip_atomic_store((gf32*)(mine + (t * 4 + v) * 64), acc[t][v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's stores have left before it counts itself in
-            uint32_t old = 0;
-            if (lane == 0) old = __hip_atomic_fetch_add((gu32*)(a.counter + g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            old = __builtin_amdgcn_readfirstlane(old);
-            if (old != a.SK - 1) continue; // not the last slice of this column group
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // compiler only: the loads below stay below the count
-            acc[0] = acc[1] = mfma_f4{0.f, 0.f, 0.f, 0.f};
-            const float* const base = a.partial + (uint64_t)g * a.SK * WT + lane;
-            for (uint32_t s0 = 0; s0 < a.SK; s0 += 4) { // slice order; four slices' loads in flight together
-                float pv[4][R * 4];
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++) {
-                    const uint32_t sl = min(s0 + q, a.SK - 1);
-#pragma unroll
-                    for (int e = 0; e < R * 4; e++) pv[q][e] = __hip_atomic_load((gf32*)(base + (uint64_t)sl * WT + e * 64), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < 4; q++)
-#pragma unroll
-                    for (int t = 0; t < R; t++)
-#pragma unroll
-                        for (int v = 0; v < 4; v++) acc[t][v] += s0 + q < a.SK ? pv[q][t * 4 + v] : 0.f;
-            }
-            if (lane == 0) __hip_atomic_store((gu32*)(a.counter + g), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // re-arm
-        }
-#pragma unroll
-        for (int t = 0; t < R; t++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const uint32_t m = t * 16 + 4 * (lane >> 4) + v, n = gl * 16 + (lane & 15);
-                if (m < a.M) P.out[(uint64_t)m * P.out_rs + n] = acc[t][v];
-            }
-    }
-}
-
-#endif // ZGML_TRACE (tile4)
 
 // f32 B (any strides, device memory) -> MFMA-packed f16. One thread per 16-byte item.
 __global__ void __launch_bounds__(kBlock) pack_f16_kernel(const float* __restrict__ b, uint32_t b_rs, uint32_t b_cs,
@@ -689,86 +390,9 @@ static uint64_t f16_a_bytes(uint32_t M, uint32_t K) { // the pre-laid-out A oper
     const uint64_t tiles = (M + 15) / 16, R = f16_tiles_per_wg(M);
     return ((tiles + R - 1) / R * R * ((K + 31) / 32) * 1024 + 255) / 256 * 256;
 }
-// the shared-A form's K split: at most kT3MaxWgs workgroups per launch, one partial tile (8 waves x R x 1 KiB) each
-constexpr uint64_t kT3MaxWgs = 1024;
 uint64_t dense_f16_scratch_bytes(uint32_t M, uint32_t K) {
     if (!sw().f16_tile2 || M <= 1) return 0;
-    return f16_a_bytes(M, K) + (M <= 32 && M > 16 && (sw().f16_tile3 || sw().f16_tile4) ? kT3MaxWgs * kT3Waves * 2 * 1024 : 0);
-}
-
-// M in (16, 32], every part a whole number of 128-column tiles: the shared-A form with a K split. false: not applicable.
-static bool launch_dense_f16_tile3(hipStream_t s, const DenseF16Params* p, uint32_t n, uint32_t KC) {
-#ifndef ZGML_TRACE
-    (void)s, (void)p, (void)n, (void)KC;
-    return false;
-#else
-    if (!sw().f16_tile3 || p[0].M <= 16 || p[0].M > 32) return false;
-    F16Args3 a{};
-    uint32_t tiles = 0;
-    for (uint32_t t = 0; t < n; t++) {
-        if ((p[t].N / 16) % kT3Waves != 0) return false;
-        a.parts[t] = {(const uint4*)p[t].bp, p[t].dst, p[t].dst_rs, tiles};
-        tiles += p[t].N / 16 / kT3Waves;
-    }
-    if ((uint64_t)tiles * sizeof(uint32_t) > kQmmScratchHead) return false; // one counter word per column tile
-    // K slices: ~2.5 workgroups per CU, whole stages per slice, at least 4 stages each, no more partial tiles than the scratch holds
-    const uint32_t stages = cdiv(KC, kT3Chunks);
-    uint32_t SK = sw().f16_tile3_sk > 0 ? (uint32_t)sw().f16_tile3_sk : std::max(1u, std::min(cdiv(640u, tiles), stages / 4));
-    SK = std::max(1u, std::min<uint32_t>(SK, (uint32_t)(kT3MaxWgs / tiles)));
-    uint32_t cps = cdiv(stages, SK) * kT3Chunks; // chunks per slice
-    SK = cdiv(KC, cps);
-    a.ap = (const uint4*)p[0].scratch, a.n_parts = n, a.M = p[0].M, a.KC = KC, a.SK = SK, a.chunks_per_slice = cps;
-    a.partial = (float*)((char*)p[0].scratch + f16_a_bytes(p[0].M, p[0].K));
-    a.counter = (uint32_t*)((char*)p[0].scratch - kQmmScratchHead);
-    const bool nt = p[0].stream_nt != 0;
-    hipLaunchKernelGGL((nt ? dense_f16_tile3_kernel<2, true> : dense_f16_tile3_kernel<2, false>), dim3(tiles, SK), dim3(kT3Waves * 64), 0, s, a);
-    return true;
-#endif
-}
-
-// M in (16, 32]: the A-stationary form. false: not applicable (launch nothing).
-static bool launch_dense_f16_tile4(hipStream_t s, const DenseF16Params* p, uint32_t n, uint32_t KC) {
-#ifndef ZGML_TRACE
-    (void)s, (void)p, (void)n, (void)KC;
-    return false;
-#else
-    if (!sw().f16_tile4 || p[0].M <= 16 || p[0].M > 32) return false;
-    F16Args4 a{};
-    uint32_t groups = 0;
-    for (uint32_t t = 0; t < n; t++) {
-        a.parts[t] = {(const uint4*)p[t].bp, p[t].dst, p[t].dst_rs, groups};
-        groups += p[t].N / 16;
-    }
-    if ((uint64_t)groups * sizeof(uint32_t) > kQmmScratchHead || groups == 0) return false; // one counter word per column group
-    const uint32_t cus = device_cus();
-    // K slices: every CU ~10 tasks (column group x slice), a slice of at most 64 chunks (its A: 128 KiB of LDS) and at least 8
-    const uint32_t sk_min = cdiv(KC, (uint32_t)kT4MaxSliceChunks), sk_max = std::max(sk_min, KC / 8);
-    uint32_t SK = sw().f16_tile4_sk > 0 ? (uint32_t)sw().f16_tile4_sk : (10u * cus + groups / 2) / groups;
-    SK = std::max(sk_min, std::min(SK, sk_max));
-    SK = std::min(SK, cus);
-    uint32_t cps = cdiv(KC, SK);
-    cps = cdiv(cps, (uint32_t)kT4Depth) * kT4Depth; // whole ring rounds per slice (the last slice may be shorter)
-    if (cps > (uint32_t)kT4MaxSliceChunks) cps = kT4MaxSliceChunks;
-    SK = cdiv(KC, cps);
-    if ((uint64_t)groups * SK * 2 * 1024 > kT3MaxWgs * kT3Waves * 2 * 1024) return false; // partial tiles must fit the scratch's partial region
-    a.ap = (const uint4*)p[0].scratch, a.n_parts = n, a.M = p[0].M, a.KC = KC, a.SK = SK, a.chunks_per_slice = cps;
-    a.n_cwg = std::max(1u, cus / SK), a.total_groups = groups;
-    a.partial = (float*)((char*)p[0].scratch + f16_a_bytes(p[0].M, p[0].K));
-    a.counter = (uint32_t*)((char*)p[0].scratch - kQmmScratchHead);
-    const bool nt = p[0].stream_nt != 0;
-    const size_t lds = std::max<size_t>((size_t)cps * 2 * 1024, 96 * 1024); // >= 96 KiB: never two workgroups on one CU
-    using Fn4 = void (*)(F16Args4);
-    // (round 5) weight loads in flight per wave: a wave walks its task's 64 chunks one after the other, so with 4 in flight and
-    // ~1.6 us of loaded latency a chunk costs >= 0.4 us whatever else happens: ZGML_F16_TILE4_DEPTH=8 doubles the ring
-    const bool deep = sw().f16_tile4_depth >= 8 && cps % 8 == 0;
-    const Fn4 fn = deep ? (nt ? (Fn4)dense_f16_tile4_kernel<true, 8> : (Fn4)dense_f16_tile4_kernel<false, 8>)
-                        : (nt ? (Fn4)dense_f16_tile4_kernel<true, 4> : (Fn4)dense_f16_tile4_kernel<false, 4>);
-    static bool attr_set[4] = {false, false, false, false};
-    const int ai = (deep ? 2 : 0) + (nt ? 1 : 0);
-    if (!attr_set[ai]) attr_set[ai] = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    hipLaunchKernelGGL(fn, dim3(a.n_cwg * SK), dim3(kT4Waves * 64), lds, s, a);
-    return true;
-#endif
+    return f16_a_bytes(M, K);
 }
 
 static void launch_dense_f16_tile2(hipStream_t s, const DenseF16Params* p, uint32_t n) {
@@ -778,8 +402,6 @@ static void launch_dense_f16_tile2(hipStream_t s, const DenseF16Params* p, uint3
         pack_a_f16_kernel<<<(uint32_t)std::min<uint64_t>(2048, (items + kBlock - 1) / kBlock), kBlock, 0, s>>>(p[0].a, p[0].M, p[0].K, p[0].a_rs, KC,
                                                                                                              tiles, (uint4*)p[0].scratch);
     }
-    if (R == 2 && tiles == 2 && launch_dense_f16_tile3(s, p, n, KC)) return;
-    if (R == 2 && tiles == 2 && launch_dense_f16_tile4(s, p, n, KC)) return;
     const uint32_t waves = std::max(1u, std::min<uint32_t>(KC, (uint32_t)sw().f16_tile2_waves));
     // column groups per workgroup (R <= 2 only: the wide-M forms already amortise A over 4 / 8 m-tiles): as many as keep the grid
     // at >= ~1.3 workgroups per CU, every part a whole number of workgroups
@@ -788,7 +410,7 @@ static void launch_dense_f16_tile2(hipStream_t s, const DenseF16Params* p, uint3
     const int env_cg = sw().f16_tile2_cg;
     uint32_t CG = 1;
     if (R <= 2) {
-        // measured at M = 32, K = 4096 (tools/f16_m32_sweep.sh, us per launch incl. the A pack; CG = 1 / 2 / 4): N = 4096 13.6 / 16.8 / 22.9,
+        // measured at M = 32, K = 4096 (tools/bench_matvec.py --fmts f16 --M 32 under ZGML_F16_TILE2_CG, us per launch incl. the A pack; CG = 1 / 2 / 4): N = 4096 13.6 / 16.8 / 22.9,
         // N = 12288 29.9 / 30.0 / 28.5, N = 22016 51.3 / 44.0 / 48.4, N = 32000 68.5 / 55.4 / 56.1; K = 11008, N = 4096 27.8 / 35.3 / 47.2:
         // two groups per workgroup once that still leaves >= 2.5 workgroups per CU (CG = 4 runs one workgroup per CU: 142 registers)
         {
@@ -816,20 +438,11 @@ static void launch_dense_f16_tile2(hipStream_t s, const DenseF16Params* p, uint3
 #define ZGML_T2(RV) (CG == 4 ? (nt ? (Fn2)dense_f16_tile2_kernel<RV, true, 4> : (Fn2)dense_f16_tile2_kernel<RV, false, 4>)                    \
                      : CG == 2 ? (nt ? (Fn2)dense_f16_tile2_kernel<RV, true, 2> : (Fn2)dense_f16_tile2_kernel<RV, false, 2>)                 \
                                : (nt ? (Fn2)dense_f16_tile2_kernel<RV, true, 1> : (Fn2)dense_f16_tile2_kernel<RV, false, 1>))
-    Fn2 fn = R == 8   ? (nt ? (Fn2)dense_f16_tile2_kernel<8, true> : (Fn2)dense_f16_tile2_kernel<8, false>)
+    const Fn2 fn = R == 8   ? (nt ? (Fn2)dense_f16_tile2_kernel<8, true> : (Fn2)dense_f16_tile2_kernel<8, false>)
              : R == 4 ? (nt ? (Fn2)dense_f16_tile2_kernel<4, true> : (Fn2)dense_f16_tile2_kernel<4, false>)
              : R == 2 ? ZGML_T2(2)
                       : ZGML_T2(1);
 #undef ZGML_T2
-#ifdef ZGML_TRACE // the MFMA-sink experiment (wrong results): diagnostics build only
-    const int sink = sw().f16_sink;
-    if (sink && R == 2 && nt) {
-        if (CG == 2)
-            fn = sink == 2 ? (Fn2)dense_f16_tile2_kernel<2, true, 2, 2> : (Fn2)dense_f16_tile2_kernel<2, true, 2, 1>;
-        else if (CG == 1)
-            fn = sink == 2 ? (Fn2)dense_f16_tile2_kernel<2, true, 1, 2> : (Fn2)dense_f16_tile2_kernel<2, true, 1, 1>;
-    }
-#endif
     if (lds > 64 * 1024) hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(fn, grid, dim3(waves * 64), lds, s, a);
 }

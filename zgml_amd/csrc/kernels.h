@@ -405,12 +405,6 @@ struct ResidentPrepArgs {
     uint32_t d, max_seq, dh, n_rope, n_ops, T;
 };
 void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t total); // total = T d + T max_seq + n_rope T 2 dh + n_ops
-// The token tail of the device-resident decode loop in ONE launch: the first maximum of v[0, n) (the two stages of launch_argmax:
-// the workgroup whose arrival is the last one on `cnt` — one zeroed word, re-armed here — does the second), the advance of the
-// device state (`adv`) and, by that same workgroup, the NEXT token's patches (`prep`, T = 1, at the advanced position; skipped once
-// the position has reached max_seq). Same (value, index) ordering as launch_argmax: results are identical.
-void launch_argmax_tail(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, uint32_t* cnt, int64_t* out,
-                        const ArgmaxAdvance& adv, const ResidentPrepArgs* prep, uint32_t prep_total);
 // ── batched decode (B independent sequences per step): the resident loop's token tail ──
 // Per-sequence state on the device, four words per sequence: state[b] = token, state[B + b] = position, state[2 B + b] = steps
 // left, state[3 B + b] = tokens produced; state[4 B] = the row length of `tokens` in the pick below.
@@ -656,16 +650,9 @@ void launch_qmatvec_fused(hipStream_t s, const QmvLaunch& L);
 // zero-initialised by the caller. false: not fusable, nothing launched.
 bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t n_kv, uint32_t d_head,
                           const AttnSplit& sp, uint32_t* counters, const uint32_t* idx, uint32_t* seen, uint32_t* timeout,
-                          const QmvLaunch* o_proj = nullptr, uint32_t* out_cnt = nullptr, uint32_t* o_seen = nullptr, bool kvq = false);
-// (round 3) decode attention + the K-on-lanes projection that reads the heads' row stores in one launch of 256-thread workgroups
-// (qmatvec.hip: attn_o_kon_kernel); `out_cnt` one zeroed word, `o_seen` one zeroed word per workgroup of the projection
-bool launch_attention_o(hipStream_t s, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t d_head, const AttnSplit& sp, const QmvLaunch& o_proj,
-                        uint32_t* out_cnt, uint32_t* o_seen, uint32_t* timeout);
-int attn_o_blocks_per_cu(uint32_t d_head);
+                          bool kvq = false);
 int qkv_attn_kon_census(hipStream_t s, uint32_t d_head, bool kvq, uint32_t grid); // 1 = the whole grid of that launch is co-resident (run once, plan-build time), 0 = not, -1 = unknown
 int qkv_attn_kon_blocks_per_cu(uint32_t d_head, bool kvq); // fused q / k / v + attention launch of K-on-lanes weights (256-thread workgroups) // occupancy query of that kernel
-// (o_proj: the single-matrix projection that reads the heads' row stores rides in the same launch; out_cnt: one zeroed
-// word, o_seen: one zeroed word per workgroup of that projection)
 // Deterministic synthetic weights for the roofline micro-benchmark, generated on the device
 // directly in the packed layout (SURVEY §8d generator).
 void launch_synth_packed(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);

@@ -949,7 +949,7 @@ bool launch_ks_layer_a(hipStream_t s, const KsProjLaunch& PL, const KsAttnOLaunc
     uint32_t shift = 0;
     while ((16u << shift) < AL.d_head) shift++;
     g.pub = KsPublish{counters, {0, AL.n_heads, AL.n_heads + n_kv}, shift};
-    g.ho = DecodeHandoff{counters, seen, idx, AL.n_heads, (AL.d_head / 16) / 2, timeout, (uint32_t)sw().hip_handoff_sleep, nullptr};
+    g.ho = DecodeHandoff{counters, seen, idx, AL.n_heads, (AL.d_head / 16) / 2, timeout, (uint32_t)sw().hip_handoff_sleep};
     g.n_proj = wgs, g.n_heads = AL.n_heads;
     g.dbg = (uint32_t)sw().ks_debug_a;
     using Fn = void (*)(KsLayerAArgs);

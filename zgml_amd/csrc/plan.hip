@@ -655,26 +655,11 @@ void fuse_qkv_attention(zgml_hip_program* p) {
             }
             if (it->second == 0) continue;
         }
-        // ... and the single-matrix projection that reads exactly the heads' row stores (the O projection) rides along:
-        // no prologue, K = n_heads * d_head, every head's rows stored at its static offset h * d_head of that input
-        std::shared_ptr<QmvLaunch> od = i + 2 < p->plan.size() ? p->plan[i + 2].qmv_desc : nullptr;
-        // (measured: 93 launches per SmolLM-135M token instead of 123, parity green, and SLOWER — 1714-1734 against 1772 tok/s:
-        // this edge is all-to-all (every column group of the projection needs every head), its hand-off costs more than the
-        // boundary it replaces. Off unless ZGML_HIP_FUSE_QKV_ATTN_O=1.)
-        bool o_ok = sw().hip_fuse_qkv_attn_o && !kvq && od && od->n_parts == 1 && od->pro.kind == QMV_PRO_NONE && od->K == nh * dh && od->K <= 2048 && !od->trace &&
-                    od->parts[0].w.format == QW_Q4 && od->parts[0].w.scale_f16;
-        for (uint32_t r = 0; o_ok && r < nh; r++) {
-            const AttnDecodeParams& a = ad->host[r];
-            o_ok = a.att.dst2 == od->pro.a && a.att.d2_rs == 1 && a.att.dyn_dst2_off >= p->dyn_dev && a.att.dyn_dst2_off < p->dyn_dev + p->ops.size();
-            if (!o_ok) break;
-            const zgml_device_op& so = p->ops[(size_t)(a.att.dyn_dst2_off - p->dyn_dev)];
-            o_ok = so.kind == ZGML_DOP_SLICE_ASSIGN && so.u.slice_assign.patch_stride == 0 && so.u.slice_assign.dst_offset == idx[3 * r] * dh;
-        }
-        if (kon) o_ok = false;
-        if (o_ok && n_mv + (uint64_t)nh * n_sp + od->parts[0].w.N / 16 > resident_cap) o_ok = false;
-        const uint32_t o_blocks = o_ok ? (uint32_t)(od->parts[0].w.N / 16) : 0;
-        const size_t n_cnt = 32 * ((size_t)nh + 2 * n_kv + 1); // one counter per 128 bytes (the last: the heads' outputs)
-        const size_t words = n_cnt + (size_t)nh * n_sp * 3 + 1 + 3 * (size_t)nh + o_blocks;
+        // (The O projection — the single-matrix launch that reads exactly the heads' row stores — does NOT ride along. Measured: 93
+        // launches per SmolLM-135M token instead of 123, parity green, and SLOWER — 1714-1734 against 1772 tok/s: that edge is
+        // all-to-all (every column group of the projection needs every head), its hand-off costs more than the boundary it replaces.)
+        const size_t n_cnt = 32 * ((size_t)nh + 2 * n_kv); // one counter per 128 bytes
+        const size_t words = n_cnt + (size_t)nh * n_sp * 3 + 1 + 3 * (size_t)nh;
         uint32_t* block = nullptr;
         if (hipMalloc((void**)&block, words * 4) != hipSuccess) continue;
         if (memset_sync(p->ctx->stream, block, 0, words * 4) != hipSuccess) {
@@ -687,91 +672,18 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         const AttnDecodeParams* d = ad->dev;
         AttnSplit sp = ad->sp;
         sp.splits = n_sp; // (possibly fewer than the stand-alone launch would use: the residency guard above)
-        uint32_t *out_cnt = counters + 32 * ((size_t)nh + 2 * n_kv), *o_seen = idx_dev + 3 * (size_t)nh;
-        uint32_t n_ops = p->plan[i].n_ops + p->plan[i + 1].n_ops, lo = std::min(p->plan[i].op_lo, p->plan[i + 1].op_lo),
-                 hi = std::max(p->plan[i].op_hi, p->plan[i + 1].op_hi);
-        if (o_ok) n_ops += p->plan[i + 2].n_ops, lo = std::min(lo, p->plan[i + 2].op_lo), hi = std::max(hi, p->plan[i + 2].op_hi);
-        const QmvLaunch Lo = o_ok ? *od : QmvLaunch{};
-        Launch F{ZGML_DOP_QMATMUL, n_ops, lo, hi, [=](hipStream_t s) {
-                     if (o_ok && launch_qkv_attention(s, L, d, nh, n_kv, dh, sp, counters, idx_dev, seen, timeout, &Lo, out_cnt, o_seen)) return;
-                     if (!launch_qkv_attention(s, L, d, nh, n_kv, dh, sp, counters, idx_dev, seen, timeout, nullptr, nullptr, nullptr, kvq)) {
-                         launch_qmatvec_fused(s, L);
-                         launch_attention_decode_batch(s, d, nh, dh, sp, kvq);
-                     }
-                     if (o_ok) launch_qmatvec_fused(s, Lo);
-                 }};
-        p->plan[i] = std::move(F);
-        p->plan.erase(p->plan.begin() + (ptrdiff_t)i + 1, p->plan.begin() + (ptrdiff_t)i + (o_ok ? 3 : 2));
-    }
-}
-
-// The decode-attention launch directly followed by the single-matrix K-on-lanes projection that reads exactly its heads' row
-// stores (the O projection of a Llama-2-7B-class model) becomes ONE launch of 256-thread workgroups (qmatvec.hip:
-// attn_o_kon_kernel): the projection's weights stream while the attention's latency chain runs, the projection's workgroups wait
-// (bounded) for one counter every head bumps. The waiting workgroups spin on workgroups of the same grid, so — like the q/k/v +
-// attention launch above — it is only built when the WHOLE grid is resident: the occupancy query minus one workgroup per CU
-// (the query reads one high near a register-file edge), the attention's split count shrinks to fit, otherwise two launches.
-#ifdef ZGML_TRACE // diagnostics build only: the kernel is not in the product library
-void fuse_attention_o(zgml_hip_program* p) {
-    // MEASURED SLOWER, off unless ZGML_HIP_FUSE_ATTN_O=1 (parity green: tests/test_hip_fused_qkv.py): Llama-2-7B 800 -> 749 tok/s
-    // (766 when the projection's weight loads are delayed until the attention is about done; polling interval and split count
-    // make no difference). The projection's stream does hide under the attention, but the attention's dependent round trips run
-    // under 256 workgroups' worth of memory traffic and the all-to-all edge (write-through rows, counter, agent-scope x loads by
-    // 256 workgroups) costs more than the boundary it replaces — the round-2 finding for every all-to-all edge, now also with
-    // 9.4 MB of prefetch credit on the other side of the scale.
-    if (!sw().hip_fuse_attn_o || p->ctx->fuse_qkv_off || !p->ctx->handoff_flag_dev || p->ctx->opt_fuse_resident_wgs == 0) return;
-    for (size_t i = 0; i + 1 < p->plan.size(); i++) {
-        const auto ad = p->plan[i].adec_desc;
-        const auto od = p->plan[i + 1].qmv_desc;
-        if (!ad || !od || ad->kvq || (ad->dh != 64 && ad->dh != 128)) continue;
-        if (barrier_between_launches(p, i)) continue;
-        const uint32_t nh = ad->nh, dh = ad->dh;
-        bool ok = od->n_parts == 1 && od->pro.kind == QMV_PRO_NONE && od->K == nh * dh && !od->trace && od->parts[0].w.format == QW_Q4K &&
-                  ((uintptr_t)od->pro.a % 16 == 0) && (od->K % 4 == 0);
-        std::vector<char> seen_head(nh, 0);
-        for (uint32_t r = 0; ok && r < nh; r++) { // every head's rows land at a static offset h * d_head of exactly the projection's input
-            const AttnDecodeParams& a = ad->host[r];
-            ok = a.att.dst2 == od->pro.a && a.att.d2_rs == 1 && a.att.dyn_dst2_off >= p->dyn_dev && a.att.dyn_dst2_off < p->dyn_dev + p->ops.size();
-            if (!ok) break;
-            const zgml_device_op& so = p->ops[(size_t)(a.att.dyn_dst2_off - p->dyn_dev)];
-            ok = so.kind == ZGML_DOP_SLICE_ASSIGN && so.u.slice_assign.patch_stride == 0 && so.u.slice_assign.dst_offset % dh == 0 &&
-                 so.u.slice_assign.dst_offset / dh < nh && !seen_head[so.u.slice_assign.dst_offset / dh];
-            if (ok) seen_head[so.u.slice_assign.dst_offset / dh] = 1;
-        }
-        if (!ok) continue;
-        const uint32_t o_blocks = (uint32_t)(od->parts[0].w.N / 16);
-        const int bpc = attn_o_blocks_per_cu(dh);
-        const uint64_t cap = (uint64_t)std::max(bpc - 1, 1) * (uint64_t)std::max(p->ctx->n_cu, 1);
-        if (o_blocks + nh > cap) continue;
-        uint32_t n_sp = ad->sp.splits ? ad->sp.splits : 1;
-        n_sp = (uint32_t)std::min<uint64_t>(n_sp, (cap - o_blocks) / nh);
-        const size_t words = 32 + o_blocks; // the counter on a line of its own, then one `seen` word per projection workgroup
-        uint32_t* block = nullptr;
-        if (hipMalloc((void**)&block, words * 4) != hipSuccess) continue;
-        if (memset_sync(p->ctx->stream, block, 0, words * 4) != hipSuccess) {
-            hipFree(block);
-            continue;
-        }
-        p->fuse_owned.push_back(block);
-        uint32_t *out_cnt = block, *o_seen = block + 32, *timeout = p->ctx->handoff_flag_dev;
-        const AttnDecodeParams* d = ad->dev;
-        AttnSplit sp = ad->sp;
-        sp.splits = n_sp;
-        const AttnSplit sp_plain = ad->sp;
-        const QmvLaunch Lo = *od; // (after arm_prenorm: the residual epilogue's side outputs ride along)
         const uint32_t n_ops = p->plan[i].n_ops + p->plan[i + 1].n_ops, lo = std::min(p->plan[i].op_lo, p->plan[i + 1].op_lo),
                        hi = std::max(p->plan[i].op_hi, p->plan[i + 1].op_hi);
-        Launch F{ZGML_DOP_ATTENTION, n_ops, lo, hi, [=](hipStream_t s) {
-                     if (!launch_attention_o(s, d, nh, dh, sp, Lo, out_cnt, o_seen, timeout)) {
-                         launch_attention_decode_batch(s, d, nh, dh, sp_plain, false);
-                         launch_qmatvec_fused(s, Lo);
+        Launch F{ZGML_DOP_QMATMUL, n_ops, lo, hi, [=](hipStream_t s) {
+                     if (!launch_qkv_attention(s, L, d, nh, n_kv, dh, sp, counters, idx_dev, seen, timeout, kvq)) {
+                         launch_qmatvec_fused(s, L);
+                         launch_attention_decode_batch(s, d, nh, dh, sp, kvq);
                      }
                  }};
         p->plan[i] = std::move(F);
         p->plan.erase(p->plan.begin() + (ptrdiff_t)i + 1);
     }
 }
-#endif
 
 // The decoder layer of a short-K model as launches that end at a K-split (ksplit.hip): in the plan built above a
 // layer is [q/k/v (rmsnorm prologue)] [decode attention] [O (+ residual)] [gate / up (rmsnorm prologue, SiLU chain)] [down (product
@@ -1944,9 +1856,6 @@ void build_fused_plan(zgml_hip_program* p) {
     arm_prenorm(p);
     arm_pair(p);
     fuse_qkv_attention(p);
-#ifdef ZGML_TRACE
-    fuse_attention_o(p);
-#endif
 }
 
 } // namespace

@@ -462,29 +462,20 @@ struct Q4Group {
     uint4 wq[DEPTH];
     Pair<ST> s2[DEPTH];
     float xa[XD ? DEPTH : 1], xb[XD ? DEPTH : 1], ya[XD && PROMUL ? DEPTH : 1], yb[XD && PROMUL ? DEPTH : 1];
-    // WHAT: 0 = weights and x, 1 = weights only, 2 = x only; AGENT: x through agent-scope loads (a consumer of values
-    // stored earlier in the SAME launch: never a stale line of this XCD's L2)
-    template <int WHAT = 0, bool AGENT = false>
+    // WHAT: 0 = weights and x, 1 = weights only
+    template <int WHAT = 0>
     __device__ __forceinline__ void load(const uint4* qs, const Pair<ST>* sc, uint32_t u, uint32_t stride, uint32_t u_last,
                                          const XDirect& xd, uint32_t i) {
-        using gf32 = const __attribute__((address_space(1))) float;
 #pragma unroll
         for (int d = 0; d < DEPTH; d++) { // clamped, unconditional
             const uint32_t ud = min(u + d * stride, u_last);
             if (XD && WHAT != 1) {
                 const uint32_t ka = min(ud * 32 + i, xd.K - 1), kb = min(ud * 32 + 16 + i, xd.K - 1);
-                if (AGENT) {
-                    xa[d] = __hip_atomic_load((gf32*)xd.a + ka, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    xb[d] = __hip_atomic_load((gf32*)xd.a + kb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    xa[d] = xd.a[ka], xb[d] = xd.a[kb];
-                }
+                xa[d] = xd.a[ka], xb[d] = xd.a[kb];
                 if (PROMUL) ya[d] = xd.b[ka], yb[d] = xd.b[kb];
             }
-            if (WHAT != 2) {
-                wq[d] = wload<NT>(qs + (uint64_t)ud * 16);
-                s2[d] = sc[(uint64_t)ud * 16];
-            }
+            wq[d] = wload<NT>(qs + (uint64_t)ud * 16);
+            s2[d] = sc[(uint64_t)ud * 16];
         }
     }
     __device__ __forceinline__ void compute(const float* xs, uint32_t u, uint32_t stride, uint32_t U, uint32_t i,
@@ -522,22 +513,19 @@ struct Q8Group {
     uint4 wq[DEPTH];
     ST s1[DEPTH];
     float xa[XD ? DEPTH : 1], ya[XD && PROMUL ? DEPTH : 1];
-    template <int WHAT = 0, bool AGENT = false>
+    template <int WHAT = 0>
     __device__ __forceinline__ void load(const uint4* qs, const ST* sc, uint32_t u, uint32_t stride, uint32_t u_last,
                                          const XDirect& xd, uint32_t i) {
-        using gf32 = const __attribute__((address_space(1))) float;
 #pragma unroll
         for (int d = 0; d < DEPTH; d++) {
             const uint32_t ud = min(u + d * stride, u_last);
             if (XD && WHAT != 1) {
                 const uint32_t ka = min(ud * 16 + i, xd.K - 1);
-                xa[d] = AGENT ? __hip_atomic_load((gf32*)xd.a + ka, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : xd.a[ka];
+                xa[d] = xd.a[ka];
                 if (PROMUL) ya[d] = xd.b[ka];
             }
-            if (WHAT != 2) {
-                wq[d] = wload<NT>(qs + (uint64_t)ud * 16);
-                s1[d] = sc[(uint64_t)ud * 16];
-            }
+            wq[d] = wload<NT>(qs + (uint64_t)ud * 16);
+            s1[d] = sc[(uint64_t)ud * 16];
         }
     }
     __device__ __forceinline__ void compute(const float* xs, uint32_t u, uint32_t stride, uint32_t U, uint32_t i,
@@ -577,18 +565,6 @@ struct Q8Group {
     const uint4 *__restrict__ qs0, const void *__restrict__ sc0, float *__restrict__ out0, const float *__restrict__ xa_base, \
         const float *__restrict__ xb_base, uint32_t in_rs, uint32_t K, uint32_t nb2_0_flags /* NB2_0 (20 bits) | (waves - 1) << 20 | n_parts << 24 | contiguous << 28 | rmsnorm prologue << 29 | x_vec << 30 */, \
         uint32_t nb2_12 /* NB2_1 | NB2_2 << 16 */
-// The consumer side of an in-launch hand-off (the O projection behind the decode attention, qkv_attn_o_kernel): the
-// weights do not depend on the producers and are requested first; then wave 0 waits (bounded) for the producers' counter
-// to pass this workgroup's private `seen` word + `need`, and x is read with agent-scope loads.
-struct QmvWait {
-    const uint32_t* cnt; // one monotonic counter, bumped once by every producer
-    uint32_t* seen;      // [workgroups of this part]
-    uint32_t need;
-    uint32_t* timeout;
-    uint32_t poll_sleep = 10; // s_sleep units (64 clocks) between two polls
-    uint32_t pre_sleep = 0;   // experiments: s_sleep units before the weights are requested
-};
-
 // PROM: 0 = no prologue, 1 = in-kernel prologue (second vector b, optional rmsnorm), 2 = PRENORM (x-direct launches only): xa_base
 // is the PRODUCER's a * gamma with its partial sums of a^2 right behind it (plan.hip: arm_prenorm), xb_base the original a;
 // the finished sums are scaled by 1 / sqrt(mean(a^2) + eps) (the mat-vec is linear in x) and every workgroup stores a 16-element
@@ -598,11 +574,11 @@ __device__ __forceinline__ void kon_pair_finish(const float* red, const QMVArgs&
 // prologue — plan.hip: arm_pair): the workgroup computes the same 16 columns of BOTH matrices (two contiguous parts of equal
 // shape; x is loaded once) and wave 0 stores the plan's buffers and the product itself (kon_pair_finish), so the down
 // projection streams one vector with no prologue. One workgroup per column group of part 0.
-template <typename ST, bool XVEC, int DEPTH, bool Q4, int PROM, bool GROUPED, bool XD, bool NT, bool CONSUME = false, bool PAIR = false>
-__device__ __forceinline__ void qmatvec_body(QMV_HEAD_PARAMS, const QMVArgs& a, const uint32_t bx, const QmvPublish* pub, const QmvWait* wt = nullptr) {
+template <typename ST, bool XVEC, int DEPTH, bool Q4, int PROM, bool GROUPED, bool XD, bool NT, bool PAIR = false>
+__device__ __forceinline__ void qmatvec_body(QMV_HEAD_PARAMS, const QMVArgs& a, const uint32_t bx, const QmvPublish* pub) {
     constexpr bool PRO = PROM == 1;
-    static_assert(PROM != 2 || (XD && !CONSUME), "PRENORM: x-direct launches only");
-    static_assert(!PAIR || (XD && Q4 && GROUPED && !CONSUME && PROM != 1), "PAIR: x-direct Q4_0 gate / up launches without an in-kernel prologue");
+    static_assert(PROM != 2 || XD, "PRENORM: x-direct launches only");
+    static_assert(!PAIR || (XD && Q4 && GROUPED && PROM != 1), "PAIR: x-direct Q4_0 gate / up launches without an in-kernel prologue");
     constexpr uint32_t UNIT_X = Q4 ? 32 : 16;
     using ScaleT = typename std::conditional<Q4, Pair<ST>, ST>::type;
     using Group = typename std::conditional<Q4, Q4Group<ST, DEPTH, XD, PRO, NT>, Q8Group<ST, DEPTH, XD, PRO, NT>>::type;
@@ -672,37 +648,18 @@ __device__ __forceinline__ void qmatvec_body(QMV_HEAD_PARAMS, const QMVArgs& a, 
     if (XD) {
         SumsqRegs sq;
         if (norm) sq = sumsq_fetch(xa_row, K, x_vec, bdim); // before the weights (in-order vmcnt)
-        if (CONSUME) { // weights first, then the hand-off, then x (QmvWait); no prologue in this mode (planner)
-            cur.template load<1>(qs, sc, u, stride, u_last, xd, i);
-            const uint32_t target = wt->seen[bx] + wt->need;
-            if (w == 0) {
-                uint32_t spins = 0;
-                while ((int32_t)(__hip_atomic_load((const __attribute__((address_space(1))) uint32_t*)wt->cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-                    if (++spins > 400000u) { // bounded: never hang the device; the caller sees the flag
-                        if (threadIdx.x == 0) __hip_atomic_store(wt->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(10); // ~0.3 us between polls (2: 1724, 10: 1741, 40: 1728 tok/s): 36 workgroups polling ONE line back to back starve the line
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // the agent-scope x loads below stay behind the poll
-            if (n_waves > 1) __syncthreads();
-            if (threadIdx.x == 0) wt->seen[bx] = target; // (every wave read it before the barrier)
-            cur.template load<2, true>(qs, sc, u, stride, u_last, xd, i);
-        } else {
-            if (PROM == 2) { // the producer's partial sums of squares (K / 16 <= 256 of them, right behind its vector): BEFORE the weights
-                const uint32_t n_ssq = K >> 4;
-                const float* const ssq = xa_base + K;
+        if (PROM == 2) { // the producer's partial sums of squares (K / 16 <= 256 of them, right behind its vector): BEFORE the weights
+            const uint32_t n_ssq = K >> 4;
+            const float* const ssq = xa_base + K;
 #pragma unroll
-                for (uint32_t j = 0; j < 4; j++) {
-                    const uint32_t q = lane + 64 * j;
-                    const float v = ssq[min(q, n_ssq - 1)];
-                    pn_pp[j] = q < n_ssq ? v : 0.f;
-                }
+            for (uint32_t j = 0; j < 4; j++) {
+                const uint32_t q = lane + 64 * j;
+                const float v = ssq[min(q, n_ssq - 1)];
+                pn_pp[j] = q < n_ssq ? v : 0.f;
             }
-            cur.load(qs, sc, u, stride, u_last, xd, i);
-            if (PAIR) cur_b.template load<1>(qs_b, sc_b, u, stride, u_last, xd, i); // (weights only: x is the other group's)
         }
+        cur.load(qs, sc, u, stride, u_last, xd, i);
+        if (PAIR) cur_b.template load<1>(qs_b, sc_b, u, stride, u_last, xd, i); // (weights only: x is the other group's)
         QMV_STAMP(1); // loads issued
         __builtin_amdgcn_sched_barrier(0); // argument-block reads below wait while the loads above fly
         if (PROM == 2) pn_inv = prenorm_factor(pn_pp, K, a.pro.eps); // (every wave: uniform code, folded while the weights fly)
@@ -782,7 +739,7 @@ __device__ __forceinline__ void qmatvec_body(QMV_HEAD_PARAMS, const QMVArgs& a, 
     };
     for (uint32_t gi = 1; gi < n_groups; gi++) {
         Group nxt, nxt_b;
-        nxt.template load<0, CONSUME>(qs, sc, u + DEPTH * stride, stride, u_last, xd, i);
+        nxt.load(qs, sc, u + DEPTH * stride, stride, u_last, xd, i);
         if (PAIR) nxt_b.template load<1>(qs_b, sc_b, u + DEPTH * stride, stride, u_last, xd, i);
         cur.compute(xs, u, stride, U, i, acc0, acc1, acc2, acc3, xd);
         if (PAIR) {
@@ -830,7 +787,7 @@ __global__ void __launch_bounds__(1024) qmatvec_prenorm_kernel(QMV_HEAD_PARAMS, 
 // gate / up in pairs, n-on-lanes form (SmolLM-class models; LDS: two column sets of wave sums)
 template <int DEPTH, int PROM>
 __global__ void __launch_bounds__(1024) qmatvec_pair_kernel(QMV_HEAD_PARAMS, QMVArgs a) {
-    qmatvec_body<__half, false, DEPTH, true, PROM, true, true, false, false, true>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, nullptr);
+    qmatvec_body<__half, false, DEPTH, true, PROM, true, true, false, true>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, nullptr);
 }
 
 // ── K ON LANES (QW_Q4K, round 3): the M = 1 mat-vec of GGUF-Q4_0-sourced weights ───────────────────────────────────────
@@ -877,18 +834,6 @@ struct KonItem { // one lane's share of a step: k = 2p, 2p + 1 x 16 columns
         if (PAIR) s2_b = sc[pair_s + pd];
         wq = wload<NT>(qs + pd);
         if (PAIR) wq_b = wload<NT>(qs + pair_q + pd);
-    }
-    // the consumer side of an in-launch hand-off (the O projection behind the decode attention): weights and scales do not depend on
-    // the producers and are requested first; x is read afterwards with agent-scope loads (never a stale L1 / L2 line). XV only.
-    __device__ __forceinline__ void load_w(const uint4* qs, const uint32_t* sc, uint32_t p, uint32_t p_last) {
-        const uint32_t pd = min(p, p_last);
-        s2 = sc[pd];
-        wq = wload<NT>(qs + pd);
-    }
-    __device__ __forceinline__ void load_x_agent(const float* a, uint32_t p, uint32_t p_last) {
-        const uint32_t pd = min(p, p_last);
-        const unsigned long long v = __hip_atomic_load((const __attribute__((address_space(1))) unsigned long long*)(a + 2 * pd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        xa = f32x2{__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32))};
     }
     __device__ __forceinline__ void compute(uint32_t pd, uint32_t P, uint32_t K, f32x2 (&acc)[8], f32x2 (&acc_b)[8], float& T, float& T_b, float& SS) const {
         const bool ok0 = pd < P, ok1 = ok0 && (XV || 2 * pd + 1 < K);
@@ -950,11 +895,9 @@ __device__ __forceinline__ void kon_pair_finish(const float* red, const QMVArgs&
     }
 }
 
-template <int DEPTH, int PROM, bool GROUPED, bool XV, bool NT, bool PAIR = false, bool CONSUME = false>
-__device__ __forceinline__ void qmatvec_kon_body(QMV_HEAD_PARAMS, const QMVArgs& a, const uint32_t bx, const uint32_t n_blocks, const QmvPublish* pub,
-                                                 const QmvWait* wt = nullptr) {
+template <int DEPTH, int PROM, bool GROUPED, bool XV, bool NT, bool PAIR = false>
+__device__ __forceinline__ void qmatvec_kon_body(QMV_HEAD_PARAMS, const QMVArgs& a, const uint32_t bx, const uint32_t n_blocks, const QmvPublish* pub) {
     constexpr bool PRO = PROM == 1;
-    static_assert(!CONSUME || (PROM == 0 && !GROUPED && !PAIR && XV), "the consumer form: one matrix, no prologue, aligned x");
     extern __shared__ float smem[];
     float* red = smem; // kMaxWaves * 16 column sums + kMaxWaves sums of squares (PAIR: the second matrix's sums from row kMaxWaves + 1)
 #ifdef ZGML_TRACE
@@ -1001,39 +944,17 @@ __device__ __forceinline__ void qmatvec_kon_body(QMV_HEAD_PARAMS, const QMVArgs&
     const uint64_t pair_q = PAIR ? (uint64_t)NB2_0 * P : 0, pair_s = PAIR ? (uint64_t)(NB2_0 >> 1) * P : 0; // part 1 follows part 0 in the arenas
     KonItem<NT, PRO, XV, PAIR> it[DEPTH];
     float pn_pp[4] = {0.f, 0.f, 0.f, 0.f}; // PRENORM
-    if constexpr (CONSUME) {
-        for (uint32_t z = 0; z < wt->pre_sleep; z++) __builtin_amdgcn_s_sleep(16);
+    if (PROM == 2) { // the producer's partial sums of squares: BEFORE the weights (loads return in order), folded below while those fly
+        const uint32_t n_ssq = K >> 4; // (= a.pro.n_ssq, without the argument-block load)
 #pragma unroll
-        for (int d = 0; d < DEPTH; d++) it[d].load_w(qs, sc, p + d * stride, p_last);
-        const uint32_t target = wt->seen[bx] + wt->need;
-        if (w == 0) { // one wave polls (bounded: never hang the device; the host sees the flag at its next synchronisation)
-            uint32_t spins = 0;
-            while ((int32_t)(__hip_atomic_load((const __attribute__((address_space(1))) uint32_t*)wt->cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-                if (++spins > 400000u) {
-                    if (threadIdx.x == 0) __hip_atomic_store(wt->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                for (uint32_t z = 0; z < wt->poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
-            }
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t q = lane + 64 * j;
+            const float v = (xa_base + K)[min(q, n_ssq - 1)]; // (arm_prenorm lays the partials right behind the vector: no argument-block pointer in front of the first load)
+            pn_pp[j] = q < n_ssq ? v : 0.f;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // the agent-scope x loads below stay behind the poll
-        if (n_waves > 1) __syncthreads();
-        if (threadIdx.x == 0) wt->seen[bx] = target; // (every wave read it before the barrier)
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++) it[d].load_x_agent(xa_base, p + d * stride, p_last);
-    } else {
-        if (PROM == 2) { // the producer's partial sums of squares: BEFORE the weights (loads return in order), folded below while those fly
-            const uint32_t n_ssq = K >> 4; // (= a.pro.n_ssq, without the argument-block load)
-#pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                const uint32_t q = lane + 64 * j;
-                const float v = (xa_base + K)[min(q, n_ssq - 1)]; // (arm_prenorm lays the partials right behind the vector: no argument-block pointer in front of the first load)
-                pn_pp[j] = q < n_ssq ? v : 0.f;
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < DEPTH; d++) it[d].load(qs, sc, xa_base, xb_base, p + d * stride, p_last, K, pair_q, pair_s);
     }
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++) it[d].load(qs, sc, xa_base, xb_base, p + d * stride, p_last, K, pair_q, pair_s);
     // this workgroup's slice of the prologue's side outputs: its inputs are requested now, under the weight stream
     KonTail tail{512.0f, norm, 0.f, K, 0.f, 0.f, 0u, 0u, PROM != 0, PROM == 2, {0.f, 0.f, 0.f, 0.f}};
     if (PROM != 0) { // (PRENORM: xb_base carries the ORIGINAL vector a, a.pro.b the gain: the slices are stored from those)
@@ -1090,12 +1011,7 @@ __device__ __forceinline__ void qmatvec_kon_body(QMV_HEAD_PARAMS, const QMVArgs&
         for (int d = 0; d < DEPTH; d++) {
             compute(it[d], p + d * stride);
             __builtin_amdgcn_sched_barrier(0); // (hipcc otherwise moves the refills to the end of the body)
-            if constexpr (CONSUME) {
-                it[d].load_x_agent(xa_base, p + (DEPTH + d) * stride, p_last);
-                it[d].load_w(qs, sc, p + (DEPTH + d) * stride, p_last);
-            } else {
-                it[d].load(qs, sc, xa_base, xb_base, p + (DEPTH + d) * stride, p_last, K, pair_q, pair_s);
-            }
+            it[d].load(qs, sc, xa_base, xb_base, p + (DEPTH + d) * stride, p_last, K, pair_q, pair_s);
             __builtin_amdgcn_sched_barrier(0);
         }
         p += DEPTH * stride;
@@ -1134,35 +1050,6 @@ template <int DEPTH, int PROM, bool NT>
 __global__ void __launch_bounds__(512, 4) qmatvec_kon_pair_kernel(QMV_HEAD_PARAMS, QMVArgs a) { // (4 waves per SIMD: two workgroups per CU, <= 128 registers)
     qmatvec_kon_body<DEPTH, PROM, true, true, NT, true>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, gridDim.x, nullptr);
 }
-
-// The decode attention and the O projection that consumes it in ONE launch (round 3, Llama-2-7B-class models): workgroups [0, n_attn)
-// run the decode-attention body (4 waves each; head-major, then split), the rest the K-on-lanes mat-vec in its consumer form. The
-// edge is all-to-all (every column group needs every head), so the hand-off is one counter that every head bumps when its output
-// rows are stored write-through — what pays here is not the edge but what overlaps it: the projection's weights (9.4 MB at 4096^2)
-// are requested at once and stream while the attention, a 32-workgroup latency chain (record, dynamic words, rope, scores, merges:
-// 3.5 us), runs; behind the counter the projection has its x loads, 4 x 32 weights of FMAs per lane and the fold left. All
-// workgroups are 256 threads and the kernel is held to 128 registers, so four workgroups per CU are admitted; the launch is only
-// built when the whole grid fits three per CU (plan.hip: fuse_attention_o).
-#ifdef ZGML_TRACE // (diagnostics build only: measured slower than two launches; tests load libzgml_hip_trace.so)
-struct AttnOArgs {
-    const AttnDecodeParams* params;
-    float* split_buf;
-    uint32_t* split_cnt;
-    uint32_t split_min_keys, n_attn, n_sp;
-    DecodeHandoff ho; // cnt == nullptr: q / k / v come from the previous launch; out_cnt: the counter the projection waits on
-    QmvWait wt;
-};
-template <int LPK, int DEPTH, bool NT>
-__global__ void __launch_bounds__(256, 4) attn_o_kon_kernel(QMV_HEAD_PARAMS, QMVArgs a, AttnOArgs f) {
-    if (blockIdx.x < f.n_attn) {
-        const uint32_t n_heads = f.ho.n_heads;
-        attention_decode_body<LPK, false, 256>(f.params, f.split_buf, f.split_cnt, f.split_min_keys, blockIdx.x % n_heads, blockIdx.x / n_heads, f.n_sp, &f.ho);
-    } else {
-        qmatvec_kon_body<DEPTH, 0, false, true, NT, false, true>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x - f.n_attn,
-                                                                  gridDim.x - f.n_attn, nullptr, &f.wt);
-    }
-}
-#endif
 
 // The q / k / v projection and the decode attention that consumes it in ONE launch (DESIGN.md section 8.0,
 // tools/exp/localdep.hip): workgroups [0, n_mv) are the grouped mat-vec's, the rest the attention's (head-major, then
@@ -1227,43 +1114,6 @@ __global__ void __launch_bounds__(256, 4) qkv_attn_kon_kernel(QMV_HEAD_PARAMS, Q
         attention_decode_body<LPK, KVQ, 256>(f.params, f.split_buf, f.split_cnt, f.split_min_keys, b % n_heads, b / n_heads, f.n_sp, &f.ho);
     }
 }
-
-// ... and the O projection behind the attention in the same launch (third range of workgroups): its weights are requested
-// at once, its x (the heads' row stores) is taken over through one counter that every head bumps when its rows are stored.
-struct QmvHead { // the leading arguments of a mat-vec launch (QMV_HEAD_PARAMS) as a value
-    const uint4* qs0;
-    const void* sc0;
-    float* out0;
-    const float* xa_base;
-    const float* xb_base;
-    uint32_t in_rs, K, nb2_0_flags, nb2_12;
-};
-#ifdef ZGML_TRACE // (diagnostics build only: measured slower)
-struct QkvAttnOArgs {
-    QkvAttnArgs f;
-    QmvHead h2;
-    QmvWait wt;
-    uint32_t n_attn; // attention workgroups (heads x splits)
-};
-template <typename ST, bool Q4, int LPK>
-__global__ void __launch_bounds__(1024) qkv_attn_o_kernel(QMV_HEAD_PARAMS, QMVArgs a, QkvAttnOArgs fo, QMVArgs a2) {
-    const QkvAttnArgs& f = fo.f;
-    if (blockIdx.x < f.n_mv) {
-        const uint32_t n_waves = ((nb2_0_flags >> 20) & 0xFu) + 1;
-        if (threadIdx.x >= n_waves * 64) return;
-        qmatvec_body<ST, false, 1, Q4, true, true, true, false>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, &f.pub);
-    } else if (blockIdx.x < f.n_mv + fo.n_attn) {
-        const uint32_t b = blockIdx.x - f.n_mv, n_heads = f.ho.n_heads;
-        attention_decode_body<LPK, false>(f.params, f.split_buf, f.split_cnt, f.split_min_keys, b % n_heads, b / n_heads, f.n_sp, &f.ho);
-    } else {
-        const QmvHead& h = fo.h2;
-        const uint32_t n_waves = ((h.nb2_0_flags >> 20) & 0xFu) + 1;
-        if (threadIdx.x >= n_waves * 64) return;
-        qmatvec_body<ST, false, 1, Q4, false, false, true, false, true>(h.qs0, h.sc0, h.out0, h.xa_base, h.xb_base, h.in_rs, h.K, h.nb2_0_flags, h.nb2_12, a2,
-                                                                       blockIdx.x - f.n_mv - fo.n_attn, nullptr, &fo.wt);
-    }
-}
-#endif
 
 // ── synthetic weights for the roofline ring (SURVEY §8d generator), written in packed form ──
 __device__ __forceinline__ int synth_q4(uint64_t flat, uint32_t id) {
@@ -1542,27 +1392,11 @@ KernelFn pick_kernel(bool xvec, bool q4, bool pro, bool grp, int depth_sel, bool
 
 // `fused` (optional): launch qkv_attn_kernel instead — the grouped mat-vec's workgroups followed by `extra_blocks` of the
 // decode attention. Returns false (nothing launched) when the mat-vec is not one of the shapes that kernel is built for.
-struct FusedO { // the O projection riding in a fused q/k/v + attention launch (qkv_attn_o_kernel)
-    QMVArgs a2;
-    QmvHead h2;
-    QmvWait wt;
-    uint32_t blocks2;
-};
 bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t total_blocks, uint32_t M, bool xvec, const QkvAttnArgs* fused = nullptr,
-                   uint32_t extra_blocks = 0, uint32_t d_head = 0, const FusedO* fo = nullptr);
-// the leading arguments of a single-matrix, prologue-free, x-direct launch with one load step (what the fused O projection
-// needs); false: not that shape
+                   uint32_t extra_blocks = 0, uint32_t d_head = 0);
 // the leading "flags" word of a mat-vec launch: part 0's column groups, the waves, the parts, and what the kernel's head may assume
 static uint32_t head_flags(const QMVArgs& a, uint32_t waves, bool contig, bool rmsnorm, bool late) {
     return a.parts[0].NB2 | ((waves - 1) << 20) | (a.n_parts << 24) | (contig ? 1u << 28 : 0u) | (rmsnorm ? 1u << 29 : 0u) | (a.x_vec ? 1u << 30 : 0u) | (late ? 1u << 31 : 0u);
-}
-static bool plain_head_depth1(const QMVArgs& a, const QWeightDev& w0, uint32_t blocks, QmvHead& h) {
-    if (!sw().qmv_xdirect || a.n_parts != 1 || a.pro.kind != QMV_PRO_NONE || w0.format != QW_Q4 || !w0.scale_f16 || w0.stream_nt) return false;
-    const uint32_t waves = qmv_waves(w0);
-    if (cdiv(a.U, waves * 4) != 1 || a.parts[0].NB2 >= (1u << 20)) return false;
-    h = QmvHead{a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b, a.in_rs, a.K,
-                head_flags(a, waves, false, false, false), 0u};
-    return true;
 }
 
 // ── the K-on-lanes launches (QW_Q4K) ──
@@ -1602,8 +1436,7 @@ KernelFn pick_kon(int prom, bool grp, bool xv, int depth_sel, bool nt) {
 }
 
 bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t total_blocks, bool xvec, const QkvAttnArgs* fused, uint32_t extra_blocks,
-                       uint32_t d_head, const FusedO* fo) {
-    if (fo) return false; // (the O projection riding along is only built for the n-on-lanes form; off by default)
+                       uint32_t d_head) {
     a.x_vec = xvec ? 1 : 0;
     const uint32_t P = (a.K + 1) / 2;
     uint32_t waves = kon_waves(w0);
@@ -1693,12 +1526,12 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
 }
 
 bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t total_blocks, uint32_t M, bool xvec, const QkvAttnArgs* fused,
-                   uint32_t extra_blocks, uint32_t d_head, const FusedO* fo) {
+                   uint32_t extra_blocks, uint32_t d_head) {
     // diagnostics build only: leave out every mat-vec launch of one grid size (wrong results; the token time then drops by that launch's true cost)
     if (sw().hip_debug_skip_grid && total_blocks == (uint32_t)sw().hip_debug_skip_grid) return true;
     if (w0.format == QW_Q4K) { // (only weights whose every use is an M = 1 mat-vec get this layout: compile_program)
         if (M != 1) return false;
-        return launch_packed_kon(s, a, w0, total_blocks, xvec, fused, extra_blocks, d_head, fo);
+        return launch_packed_kon(s, a, w0, total_blocks, xvec, fused, extra_blocks, d_head);
     }
     const bool q4 = w0.format == QW_Q4;
     a.x_vec = xvec ? 1 : 0;
@@ -1759,20 +1592,6 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
         QkvAttnArgs f = *fused;
         f.n_mv = total_blocks;
         const bool fused_kvq = f.kvq != 0;
-#ifdef ZGML_TRACE
-        if (fo && depth_sel == 0 && !fused_kvq) { // ... and the O projection behind the attention (diagnostics build only)
-            QkvAttnOArgs g{f, fo->h2, fo->wt, extra_blocks};
-            const dim3 grid3(total_blocks + extra_blocks + fo->blocks2);
-            if (d_head == 64)
-                hipLaunchKernelGGL((qkv_attn_o_kernel<__half, true, 16>), grid3, dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b,
-                                   a.in_rs, a.K, head_flags(a, waves, true, rmsnorm, false), nb2_12, a, g, fo->a2);
-            else
-                hipLaunchKernelGGL((qkv_attn_o_kernel<__half, true, 32>), grid3, dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b,
-                                   a.in_rs, a.K, head_flags(a, waves, true, rmsnorm, false), nb2_12, a, g, fo->a2);
-            return true;
-        }
-#endif
-        if (fo) return false; // (the caller asked for the triple: let it fall back as a whole)
         if (depth_sel != 0) return false; // (one load step: K <= 2048)
         using FusedFn = void (*)(const uint4*, const void*, float*, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, QMVArgs, QkvAttnArgs);
         FusedFn ff = nullptr;
@@ -1857,13 +1676,13 @@ static void build_qmv_args(const QmvLaunch& L, QMVArgs& a, uint32_t& blocks, boo
     xvec_out = xvec;
 }
 
-static bool launch_qmv(hipStream_t s, const QmvLaunch& L, const QkvAttnArgs* fused, uint32_t extra_blocks, uint32_t d_head, const FusedO* fo = nullptr) {
+static bool launch_qmv(hipStream_t s, const QmvLaunch& L, const QkvAttnArgs* fused, uint32_t extra_blocks, uint32_t d_head) {
     if (L.n_parts == 0) return false;
     QMVArgs a;
     uint32_t blocks = 0;
     bool xvec = false;
     build_qmv_args(L, a, blocks, xvec);
-    return launch_packed(s, a, L.parts[0].w, blocks, 1, xvec, fused, extra_blocks, d_head, fo);
+    return launch_packed(s, a, L.parts[0].w, blocks, 1, xvec, fused, extra_blocks, d_head);
 }
 
 void launch_qmatvec_fused(hipStream_t s, const QmvLaunch& L) { launch_qmv(s, L, nullptr, 0, 0); }
@@ -1871,8 +1690,7 @@ void launch_qmatvec_fused(hipStream_t s, const QmvLaunch& L) { launch_qmv(s, L, 
 // the q / k / v projection + the decode attention of its heads in one launch (qkv_attn_kernel). `n_heads` x `n_sp`
 // attention workgroups follow the mat-vec's; false: shapes the fused kernel is not built for (launch the two separately)
 bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t n_kv, uint32_t d_head,
-                          const AttnSplit& sp, uint32_t* counters, const uint32_t* idx, uint32_t* seen, uint32_t* timeout, const QmvLaunch* Lo,
-                          uint32_t* out_cnt, uint32_t* o_seen, bool kvq) {
+                          const AttnSplit& sp, uint32_t* counters, const uint32_t* idx, uint32_t* seen, uint32_t* timeout, bool kvq) {
     QkvAttnArgs f{};
     f.kvq = kvq ? 1 : 0;
     f.params = dev_params, f.split_buf = sp.buf, f.split_cnt = sp.cnt, f.split_min_keys = sp.min_keys;
@@ -1880,27 +1698,10 @@ bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodePar
     uint32_t shift = 0;
     while ((16u << shift) < d_head) shift++;
     f.pub = QmvPublish{counters, {0, n_heads, n_heads + n_kv}, shift, sw().hip_debug_drop_publish ? 1u : 0u}; // (diagnostics build, tests/handoff_timeout_worker.py: one column group never signals)
-    f.ho = DecodeHandoff{counters, seen, idx, n_heads, d_head / 16, timeout, (uint32_t)sw().hip_handoff_sleep, nullptr};
-#ifdef ZGML_TRACE
-    if (Lo) { // the O projection rides along (diagnostics build only)
-        FusedO fo;
-        bool xvec2 = false;
-        build_qmv_args(*Lo, fo.a2, fo.blocks2, xvec2);
-        fo.a2.x_vec = xvec2 ? 1 : 0;
-        if (!plain_head_depth1(fo.a2, Lo->parts[0].w, fo.blocks2, fo.h2)) return false;
-        fo.wt = QmvWait{out_cnt, o_seen, n_heads, timeout};
-        f.ho.out_cnt = out_cnt;
-        return launch_qmv(s, L, &f, n_heads * f.n_sp, d_head, &fo);
-    }
-#else
-    if (Lo) return false;
-#endif
+    f.ho = DecodeHandoff{counters, seen, idx, n_heads, d_head / 16, timeout, (uint32_t)sw().hip_handoff_sleep};
     return launch_qmv(s, L, &f, n_heads * f.n_sp, d_head);
 }
 
-// the decode attention of `n_heads` heads + the single-matrix K-on-lanes projection that reads their row stores, one launch
-// (attn_o_kon_kernel). `out_cnt`: one zeroed word, `o_seen`: one zeroed word per workgroup of the projection. false: not a shape the
-// kernel is built for (nothing launched). attn_o_blocks_per_cu(): what the occupancy query admits per CU (for the planner's guard).
 // Is a grid of `grid` 256-thread workgroups of the fused K-on-lanes launch co-resident on this device? Runs the kernel's CENSUS
 // instantiation once (synchronises the stream: plan-build time only). 1 = every workgroup saw the whole grid arrive, 0 = some
 // workgroup waited in vain (the launch must not be fused), -1 = the census could not run (the caller falls back to the occupancy query).
@@ -1938,43 +1739,6 @@ int qkv_attn_kon_blocks_per_cu(uint32_t d_head, bool kvq) { // what the occupanc
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, ((size_t)kMaxWaves * 16 + kMaxWaves) * sizeof(float)) != hipSuccess) return 0;
     return nb;
 }
-#ifdef ZGML_TRACE // the attention + O projection launch: diagnostics build only (measured slower)
-int attn_o_blocks_per_cu(uint32_t d_head) {
-    int nb = 0;
-    const void* fn = d_head == 64 ? (const void*)attn_o_kon_kernel<16, 4, true> : (const void*)attn_o_kon_kernel<32, 4, true>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, ((size_t)kMaxWaves * 16 + kMaxWaves) * sizeof(float)) != hipSuccess) return 0;
-    return nb;
-}
-bool launch_attention_o(hipStream_t s, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t d_head, const AttnSplit& sp, const QmvLaunch& Lo,
-                        uint32_t* out_cnt, uint32_t* o_seen, uint32_t* timeout) {
-    QMVArgs a;
-    uint32_t blocks = 0;
-    bool xvec = false;
-    build_qmv_args(Lo, a, blocks, xvec);
-    const QWeightDev& w0 = Lo.parts[0].w;
-    if (w0.format != QW_Q4K || a.n_parts != 1 || a.pro.kind != QMV_PRO_NONE || !xvec || (d_head != 64 && d_head != 128)) return false;
-    a.x_vec = 1;
-    const uint32_t P = (a.K + 1) / 2, waves = 4; // (256-thread workgroups: the kernel's launch bound)
-    const uint32_t n_steps = cdiv(P, waves * 64);
-    const int depth = n_steps >= 4 ? 4 : (n_steps >= 2 ? 2 : 1);
-    const bool nt = w0.stream_nt != 0;
-    AttnOArgs f{};
-    f.params = dev_params, f.split_buf = sp.buf, f.split_cnt = sp.cnt, f.split_min_keys = sp.min_keys;
-    f.n_sp = sp.splits ? sp.splits : 1;
-    f.n_attn = n_heads * f.n_sp;
-    f.ho = DecodeHandoff{nullptr, nullptr, nullptr, n_heads, d_head / 16, timeout, 2u, out_cnt};
-    f.wt = QmvWait{out_cnt, o_seen, n_heads, timeout, (uint32_t)sw().hip_attn_o_poll, (uint32_t)sw().hip_attn_o_presleep};
-    const uint32_t flags = a.parts[0].NB2 | ((waves - 1) << 20) | (1u << 24) | (1u << 30);
-    const size_t lds = ((size_t)kMaxWaves * 16 + kMaxWaves) * sizeof(float);
-    using Fn = void (*)(const uint4*, const void*, float*, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, QMVArgs, AttnOArgs);
-    Fn fn = nullptr;
-#define AO(L) (depth == 4 ? (nt ? (Fn)attn_o_kon_kernel<L, 4, true> : (Fn)attn_o_kon_kernel<L, 4, false>) : depth == 2 ? (Fn)attn_o_kon_kernel<L, 2, false> : (Fn)attn_o_kon_kernel<L, 1, false>)
-    fn = d_head == 64 ? AO(16) : AO(32);
-#undef AO
-    hipLaunchKernelGGL(fn, dim3(f.n_attn + blocks), dim3(256), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, a.pro.a, a.pro.b, a.in_rs, a.K, flags, 0u, a, f);
-    return true;
-}
-#endif
 
 void launch_synth_packed(hipStream_t s, const QWeightDev& w, uint32_t matrix_id) {
     if (w.scale_f16)

@@ -601,8 +601,6 @@ zgml_hip_ctx* zgml_hip_create(int device_ordinal) {
     }
     hipMalloc((void**)&ctx->arg_val, 256 * sizeof(float));
     hipMalloc((void**)&ctx->arg_idx, 256 * sizeof(int64_t));
-    hipMalloc((void**)&ctx->arg_cnt, 128);
-    hipMemset(ctx->arg_cnt, 0, 128);
     hipMalloc((void**)&ctx->arg_out, sizeof(int64_t));
     hipHostMalloc((void**)&ctx->arg_out_host, sizeof(int64_t), hipHostMallocDefault);
     ctx->n_cu = prop.multiProcessorCount;
@@ -633,7 +631,6 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipFree(ctx->mm_c);
     hipFree(ctx->arg_val);
     hipFree(ctx->arg_idx);
-    hipFree(ctx->arg_cnt);
     hipFree(ctx->arg_out);
     hipHostFree(ctx->arg_out_host);
     hipFree(ctx->smp_keys);

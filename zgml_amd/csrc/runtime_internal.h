@@ -118,7 +118,6 @@ struct zgml_hip_ctx {
     // argmax scratch
     float* arg_val = nullptr;
     int64_t* arg_idx = nullptr;
-    uint32_t* arg_cnt = nullptr; // arrival counter of the fused token tail (launch_argmax_tail), re-armed by its last workgroup
     int64_t* arg_out = nullptr;
     int64_t* arg_out_host = nullptr; // pinned
     // zgml_hip_sample's scratch, allocated by its first call: the select launch's partial lists (kernels.h: sample_scratch_keys of

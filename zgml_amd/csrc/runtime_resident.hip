@@ -668,25 +668,18 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     });
     if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_steps)) return -1;
     const Prep prep = prep_args(p, r->state, r->state /* the token is state[0] */);
-    // (off unless ZGML_HIP_TAIL_FUSED=1. First form — the last arriver walks all 8-16 K elements of the next token's patches alone —
-    // measured SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every workgroup writes the
-    // position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838 against 842;
-    // profiles/r05_token_tail_ab.txt)
-    const bool tail_fused = sw().hip_tail_fused;
+    // [prep] [plan] [argmax stage 1] [stage 2 + advance]. (A token tail in ONE launch — the argmax, the advance of the device state
+    // and the next token's patches, two launches fewer per token — was measured and removed. First form — the last arriver walks
+    // all 8-16 K elements of the next token's patches alone — SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against
+    // 817. Second form — every workgroup writes the position-only patches, the last arriver the embedding row — a wash: 1777-1782
+    // against 1768-1780, 838 against 842; profiles/r05_token_tail_ab.txt)
     auto one_token = [&](hipStream_t st) {
-        if (!tail_fused) launch_resident_prep(st, prep.a, prep.total);
-        // [prep] [plan] [argmax stage 1] [stage 2 + advance]; or, opt-in, [plan] [token tail]: the argmax of the logits, the advance
-        // of the device state AND the next token's patches in ONE launch (launch_argmax_tail; the first token's patches then
-        // come from a stand-alone prep launch in front of the loop) — two launches fewer per token.
+        launch_resident_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
-        if (tail_fused)
-            launch_argmax_tail(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_cnt, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap}, &prep.a, prep.total);
-        else
-            launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap});
+        launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap});
     };
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // (a stack array: no wait before the capture, unlike the batched loop's vector)
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return -1;
-    if (tail_fused) launch_resident_prep(s, prep.a, prep.total); // the first token's patches (every later token's come from its predecessor's tail)
     capture_once(ctx, s, "resident", false, one_token, &r->graph, &r->graph_exec);
     // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
     // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
@@ -712,7 +705,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode");
-    resident_end(p, n_steps, p->plan.size() + (tail_fused ? 1 : 3)); // per token [prep] [plan] [argmax x 2], or [plan] [token tail]
+    resident_end(p, n_steps, p->plan.size() + 3); // per token [prep] [plan] [argmax x 2]
     return ok ? 0 : -1;
 }
 

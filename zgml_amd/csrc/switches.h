@@ -33,8 +33,6 @@ struct Switches {
     bool hip_fuse_qkv_attn_kon = env_flag("ZGML_HIP_FUSE_QKV_ATTN_KON", true);        // ... also for K-on-lanes models (K > 2048)
     int hip_fuse_kon_cap_eighths = env_int("ZGML_HIP_FUSE_KON_CAP_EIGHTHS", 8);       // share of the workgroup capacity that launch may fill
     bool hip_fuse_census = env_flag("ZGML_HIP_FUSE_CENSUS", true);                    // co-residency census of the fused K-on-lanes grid
-    bool hip_fuse_qkv_attn_o = env_flag(trace("ZGML_HIP_FUSE_QKV_ATTN_O"), false);    // the O projection rides in the fused launch (measured slower)
-    bool hip_fuse_attn_o = env_flag(trace("ZGML_HIP_FUSE_ATTN_O"), false);            // decode attention + O projection of K > 2048 models as one launch (measured slower)
     bool hip_ksplit_fuse_a = env_flag("ZGML_HIP_KSPLIT_FUSE_A", true);                // K-split layers: projection + attention as one launch
     bool hip_prenorm = env_flag("ZGML_HIP_PRENORM", true);                            // the residual epilogue prepares the next launch's rmsnorm
     bool hip_pair = env_flag("ZGML_HIP_PAIR", true);                                  // gate / up computed in pairs with the SiLU product stored by the launch
@@ -60,7 +58,6 @@ struct Switches {
     bool hip_weight_arena = env_flag("ZGML_HIP_WEIGHT_ARENA", true);                  // a program's packed weights in two allocations, back to back
     uint64_t hip_nt_min_bytes = env_u64_0("ZGML_HIP_NT_MIN_BYTES", 192ull << 20);     // weight sets from this size on are streamed with non-temporal loads
     bool hip_io_graph = env_flag("ZGML_HIP_IO_GRAPH", true);                          // execute_program as one graph that reads / writes pinned host memory
-    bool hip_tail_fused = env_flag("ZGML_HIP_TAIL_FUSED", false);                     // resident loop: argmax stage 2 + next token's prep as one launch (measured slower)
     int hip_resident_tokens_per_graph = env_int("ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH", 1); // tokens held by one graph of the resident loop
     int shard_peer_wait_ms = env_int("ZGML_SHARD_PEER_WAIT_MS", 5000);                // bound of a peer gather's wait (at least 1)
     bool shard_pair_argmax = env_flag("ZGML_SHARD_PAIR_ARGMAX", true);                // sharded greedy token from one (max, index) pair per rank
@@ -91,15 +88,12 @@ struct Switches {
     int hip_handoff_sleep = env_int("ZGML_HIP_HANDOFF_SLEEP", 2);                     // s_sleep argument between polls of a hand-off counter
     int hip_debug_skip_grid = env_int(trace("ZGML_HIP_DEBUG_SKIP_GRID"), 0);          // leave out every mat-vec launch of this many column groups (timing only)
     bool hip_debug_drop_publish = env_flag(trace("ZGML_HIP_DEBUG_DROP_PUBLISH"), false); // one column group of a fused launch never signals (time-out test)
-    int hip_attn_o_poll = env_int(trace("ZGML_HIP_ATTN_O_POLL"), 10);                 // attention + O launch: sleep between polls
-    int hip_attn_o_presleep = env_int(trace("ZGML_HIP_ATTN_O_PRESLEEP"), 0);          // ... and before the first poll
     // ── K-split layers (ksplit.hip) ──
     int ks_proj_gp = env_int("ZGML_KS_PROJ_GP", 0);                                   // 1 | 2 | 4: column groups per workgroup of the projection (else 2)
     int ks_proj_waves = env_int("ZGML_KS_PROJ_WAVES", 0);                             // waves of the projection launch (0: by K)
     int ks_mlp_waves = env_int("ZGML_KS_MLP_WAVES", 0);                               // waves of the MLP launch (0: by K)
     int ks_debug_a = env_int("ZGML_KS_DEBUG_A", 0);                                   // 1: the attention's workgroups exit at once, 2: they skip the wait (timing only)
     // ── quantized tile kernels, M > 1 (qmatmul_tiles.hip) ──
-    bool qmm_xdl = env_flag(trace("ZGML_QMM_XDL"), true);                             // 0: the tile kernel's contraction on the f32 MFMA
     bool qmm_xdl2 = env_flag("ZGML_QMM_XDL2", true);                                  // the split-A forms (pre-laid-out A, B-scaled tiles) for Q4_0 with f16 scales
     int qmm_xdl2_g = env_int("ZGML_QMM_XDL2_G", 0);                                   // column groups per workgroup of qmatmul_xdl2_kernel (0: by N)
     bool qmm_xdl4 = env_flag("ZGML_QMM_XDL4", true);                                  // M > 32: the 4 / 8-m-tile K-split kernel
@@ -110,9 +104,6 @@ struct Switches {
     int qmm_xdl5_min_cols = env_int("ZGML_QMM_XDL5_MIN_COLS", 40);                    // fewest 256-column workgroup-columns it is taken for
     int qmm_xdl5_min_run = env_int("ZGML_QMM_XDL5_MIN_RUN", 2);                       // shortest run of (column, K step) pairs of its work split (at least 1)
     bool qmm_xdl5_trace = env_flag(trace("ZGML_QMM_XDL5_TRACE"), false);              // print the per-phase stamps of its last launch at exit
-    bool qmm_xdl7 = env_flag(trace("ZGML_QMM_XDL7"), false);                          // M > 32: the shared-A kernel (measured slower)
-    int qmm_xdl7_min_cols = env_int(trace("ZGML_QMM_XDL7_MIN_COLS"), 40);             // as for the M <= 32 form
-    int qmm_xdl7_min_run = env_int(trace("ZGML_QMM_XDL7_MIN_RUN"), 2);                // as for the M <= 32 form
     int qmm_waves = env_int("ZGML_QMM_WAVES", 8);                                     // most waves per workgroup of the tile kernels
     int qmm_tile_min_m = env_int("ZGML_QMM_TILE_MIN_M", 2);                           // rows from which a quantized matmul takes the tile kernels
     // ── dense f16 (dense_f16.hip) ──
@@ -120,12 +111,6 @@ struct Switches {
     bool f16_tile2_wide = env_flag("ZGML_F16_TILE2_WIDE", true);                      // ... 4 / 8 m-tiles per workgroup for M > 32 / 64
     int f16_tile2_waves = env_int("ZGML_F16_TILE2_WAVES", 8);                         // ... most waves per workgroup
     int f16_tile2_cg = env_int("ZGML_F16_TILE2_CG", 0);                               // ... 1 | 2 | 4: column groups per workgroup (0: by the grid)
-    bool f16_tile3 = env_flag(trace("ZGML_F16_TILE3"), false);                        // M in (16, 32]: the shared-A K-split experiment
-    int f16_tile3_sk = env_int(trace("ZGML_F16_TILE3_SK"), 0);                        // ... its K slices (0: by the grid)
-    bool f16_tile4 = env_flag(trace("ZGML_F16_TILE4"), false);                        // M in (16, 32]: the A-stationary experiment
-    int f16_tile4_sk = env_int(trace("ZGML_F16_TILE4_SK"), 0);                        // ... its K slices (0: ~10 tasks per CU)
-    int f16_tile4_depth = env_int(trace("ZGML_F16_TILE4_DEPTH"), 4);                  // ... >= 8: eight weight loads in flight per wave
-    int f16_sink = env_int(trace("ZGML_F16_SINK"), 0);                                // the MFMA-sink experiment (wrong results)
     int f16_groups = env_int("ZGML_F16_GROUPS", 0);                                   // column groups per workgroup of the plain dense kernel (0: by N)
 };
 
