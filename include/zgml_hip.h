@@ -655,6 +655,40 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* ha
                                          uint32_t n_tokens, const zgml_spec_decode* opt, int64_t* tokens_out /* [n_tokens] */,
                                          zgml_spec_stats* stats /* may be NULL */);
 
+/* ── Speculative decode under batching: n_seqs sequences on a batched plan with T = tokens_per_seq >= 2 columns per sequence
+ * (build_batch_decode_program's tokens_per_seq; zgml_hip_program_set_sequences, then zgml_hip_resident_setup, which accepts a
+ * token_input of n_seqs * T columns: column b * T + j is candidate j of sequence b). Sequence b runs the loop of
+ * zgml_hip_resident_decode_speculative (same candidates, same acceptance rule, same emission: zgml_amd/csrc/spec.h) from
+ * first_tokens[b] at start_pos[b] until it has n_tokens[b] <= max_tokens tokens, with per_seq[b] (per_seq NULL: every sequence
+ * looks up with ngram 2 and no history; else an entry with the fields of the single-sequence call: its own history, mode,
+ * drafts, ngram). tokens_out[b * max_tokens + i]; the rest of a row stays -1. stats[b] (stats may be NULL) are sequence b's own.
+ * Exactness. Every emitted token of sequence b is the first maximum of the plan's own logits row over b's confirmed context:
+ *   drafts decide how many steps run, never which tokens come out, and the other sequences of the batch change neither a
+ *   sequence's tokens nor its statistics.
+ * Resuming. After the call b's caches are valid for positions < start_pos[b] + n_tokens[b] and unspecified behind that; two
+ *   calls give the stream of one: continue with first_token = tokens_out[b][n_tokens[b] - 1] at start_pos[b] + n_tokens[b] and
+ *   the history extended by first_tokens[b] and tokens_out[b][0 .. n_tokens[b] - 2].
+ * Idling. A sequence that has its count idles: its steps emit nothing and change neither its state, its history nor its
+ *   counters, but they still run its last confirmed token T times from its end position and store T KV columns there (the
+ *   "unspecified" columns). Hence the bound start_pos[b] + n_tokens[b] + T <= max_seq for EVERY b — one column stricter than the
+ *   single-sequence call: the host cannot know which sequence finishes first. n_tokens[b] = 0 is allowed and idles from the
+ *   start.
+ * Launches. One graph launch per step: [draft, n_seqs sequences] [prep, n_seqs * T columns] [plan] [argmax stage 1 over
+ *   n_seqs * T rows] [accept + advance, n_seqs sequences] — the launch count of the single-sequence step, a linear chain, and a
+ *   graph of its own (other calls on the program invalidate nothing). The host launches max_b ceil(left_b / T) steps, reads the
+ *   n_seqs produced counts back and repeats until every sequence is done; a round in which a sequence with tokens left produced
+ *   nothing is an error.
+ * Refused with -1 and an error on the context, before anything is enqueued: a plain plan or a batched plan with one column per
+ *   sequence; a constraint attached to any sequence; per sequence everything zgml_hip_resident_decode_speculative refuses (a
+ *   token — first, history, drafts — >= vocab, n_history neither 0 nor start_pos[b], mode > 1, ngram > 4); the bound above;
+ *   n_tokens[b] > max_tokens; NULL arrays. All n_tokens zero: returns 0 and touches nothing.
+ * zgml_hip_resident_decode_batch and zgml_hip_resident_decode_batch_sampled refuse a plan with more than one column per sequence
+ * (this call is the one that runs it); the single-sequence speculative calls keep refusing every batched plan. Blocking. */
+int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens,
+                                               const uint32_t* start_pos, const uint32_t* n_tokens, uint32_t max_tokens,
+                                               const zgml_spec_decode* per_seq /* [n_seqs] or NULL */,
+                                               int64_t* tokens_out /* [n_seqs][max_tokens] */, zgml_spec_stats* stats /* [n_seqs] or NULL */);
+
 /* ── Seeded top-k / top-p sampling: the token tail of the resident loops with a sampled pick instead of the first maximum.
  * The rule is written once, in zgml_amd/csrc/sample.h (the kernels and the CPU tests call the same functions):
  *   candidates: the k = min(top_k, n) largest logits, value descending, the lower index first among equals (-0 == +0, a NaN

@@ -312,7 +312,7 @@ HIP_SYMBOLS = [
     "zgml_hip_shard_profile_step", "zgml_hip_shard_last_point_us", "zgml_hip_device_can_access_peer", "zgml_hip_device_count", "zgml_hip_shard_init_peer", "zgml_hip_shard_peer_export", "zgml_hip_shard_peer_import",
     "zgml_hip_program_plan_text", "zgml_hip_program_pin_outputs",
     "zgml_hip_program_set_sequences", "zgml_hip_refresh_dynamic_batch", "zgml_hip_resident_decode_batch",
-    "zgml_hip_resident_decode_speculative",
+    "zgml_hip_resident_decode_speculative", "zgml_hip_resident_decode_batch_speculative",
     "zgml_hip_sample", "zgml_hip_resident_decode_sampled", "zgml_hip_resident_decode_batch_sampled",
     "zgml_hip_resident_decode_speculative_sampled", "zgml_hip_logprobs", "zgml_hip_logprobs_result",
     "zgml_hip_top_logprobs", "zgml_hip_top_logprobs_result",
@@ -459,6 +459,10 @@ def _bind_hip(lib: C.CDLL) -> None:
     lib.zgml_hip_resident_decode_sampled.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SamplingC), vp, C.POINTER(u32)]
     lib.zgml_hip_resident_decode_batch_sampled.restype = i32
     lib.zgml_hip_resident_decode_batch_sampled.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, C.POINTER(SamplingC), vp, C.POINTER(u32)]
+    if hasattr(lib, "zgml_hip_resident_decode_batch_speculative"):  # absent from an older build loaded through ZGML_HIP_LIB (A/B runs)
+        lib.zgml_hip_resident_decode_batch_speculative.restype = i32
+        lib.zgml_hip_resident_decode_batch_speculative.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, C.POINTER(SpecDecodeC), vp,
+                                                                   C.POINTER(SpecStatsC)]
     lib.zgml_hip_resident_decode_speculative_sampled.restype = i32
     lib.zgml_hip_resident_decode_speculative_sampled.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SpecDecodeC), C.POINTER(SamplingC), vp, C.POINTER(u32),
                                                                  C.POINTER(SpecStatsC)]

@@ -1,5 +1,5 @@
 // greedy_tail.hip — the greedy token tail of the device-resident loops (runtime_resident.hip) and the stand-alone argmax op: the
-// prep launches that produce a step's patches on the device, and the argmax family — first index of the maximum — in its three
+// prep launches that produce a step's patches on the device (single, batched, batched verify step), and the argmax family — first index of the maximum — in its three
 // shapes, all written over tail_device.h's bodies (a thread's scan, the block reductions, the advances):
 //   launch_argmax               [stage 1: a pair per workgroup] [stage 2: the pairs' fold + the single loop's advance]
 //   launch_argmax_batch         the same two stages over B rows (blockIdx.y = sequence), the batched loop's advance;
@@ -43,35 +43,47 @@ __global__ void __launch_bounds__(256) resident_prep_kernel(ResidentPrepArgs a) 
     resident_prep_element(a, blockIdx.x * 256 + threadIdx.x, a.state[1]);
 }
 
-// the batched form (kernels.h: ResidentBatchPrepArgs): column j / dynamic op i takes token and position of its own sequence
-__global__ void __launch_bounds__(256) resident_batch_prep_kernel(ResidentBatchPrepArgs a) {
-    uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t* const tok = a.state;
-    const uint32_t* const pos = a.state + a.B;
-    if (i < a.B * a.d) {
+// the batched forms (kernels.h: ResidentBatchPrepArgs, ResidentBatchSpecPrepArgs), stated once: `cols` columns, Ts of them per
+// sequence — column c is token j = c % Ts of sequence c / Ts, at that sequence's position + j; dynamic op i takes the position of
+// its own sequence, a SeqKv word pos + Ts. tok_of(column) and pos_of(sequence) read the loop's device state
+template <class A, class TokOf, class PosOf>
+__device__ __forceinline__ void resident_batch_prep_element(const A& a, uint32_t i, uint32_t cols, uint32_t Ts, TokOf tok_of, PosOf pos_of) {
+    if (i < cols * a.d) {
         const uint32_t j = i / a.d, e = i - j * a.d;
-        a.tok_in[i] = a.embed[(uint64_t)tok[j] * a.d + e];
+        a.tok_in[i] = a.embed[(uint64_t)tok_of(j) * a.d + e];
         return;
     }
-    i -= a.B * a.d;
-    if (i < a.B * a.max_seq) {
+    i -= cols * a.d;
+    if (i < cols * a.max_seq) {
         const uint32_t j = i / a.max_seq, sidx = i - j * a.max_seq;
-        a.mask[i] = sidx <= pos[j] ? 0.0f : -INFINITY;
+        a.mask[i] = sidx <= pos_of(j / Ts) + j % Ts ? 0.0f : -INFINITY;
         return;
     }
-    i -= a.B * a.max_seq;
-    if (i < a.n_rope * a.B * 2 * a.dh) {
-        const uint32_t l = i / (a.B * 2 * a.dh), rem = i - l * (a.B * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
-        a.rope_bufs[l][rem] = e < a.dh ? a.cos[(uint64_t)pos[j] * a.dh + e] : a.sin[(uint64_t)pos[j] * a.dh + e - a.dh];
+    i -= cols * a.max_seq;
+    if (i < a.n_rope * cols * 2 * a.dh) {
+        const uint32_t l = i / (cols * 2 * a.dh), rem = i - l * (cols * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
+        const uint64_t at = pos_of(j / Ts) + j % Ts;
+        a.rope_bufs[l][rem] = e < a.dh ? a.cos[at * a.dh + e] : a.sin[at * a.dh + e - a.dh];
         return;
     }
-    i -= a.n_rope * a.B * 2 * a.dh;
+    i -= a.n_rope * cols * 2 * a.dh;
     if (i < a.n_ops) {
         const uint32_t kind = a.dyn_kind[i];
         if (kind == 0) return;
-        const uint32_t ps = pos[a.dyn_seq[i]];
-        a.dyn[i] = kind == 1 ? a.dyn_base[i] + ps * a.dyn_stride[i] : ps + 1;
+        const uint32_t ps = pos_of(a.dyn_seq[i]);
+        a.dyn[i] = kind == 1 ? a.dyn_base[i] + ps * a.dyn_stride[i] : ps + Ts;
     }
+}
+// one column per sequence: token and position from the batched loop's state
+__global__ void __launch_bounds__(256) resident_batch_prep_kernel(ResidentBatchPrepArgs a) {
+    const uint32_t* const tok = a.state;
+    const uint32_t* const pos = a.state + a.B;
+    resident_batch_prep_element(a, blockIdx.x * 256 + threadIdx.x, a.B, 1u, [&](uint32_t j) { return tok[j]; }, [&](uint32_t b) { return pos[b]; });
+}
+// T columns per sequence (a batched verify step): the candidates, from the run position the draft launch chose for the sequence
+__global__ void __launch_bounds__(256) resident_batch_spec_prep_kernel(ResidentBatchSpecPrepArgs a) {
+    resident_batch_prep_element(a, blockIdx.x * 256 + threadIdx.x, a.B * a.T, a.T, [&](uint32_t j) { return a.cand[j]; },
+                                [&](uint32_t b) { return a.words[b * kSpecWords + kSpecRunPos]; });
 }
 
 // stage 1 of row `row` (row stride n): this workgroup's pair to slot row * gridDim.x + blockIdx.x
@@ -135,6 +147,10 @@ void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t tot
 
 void launch_resident_batch_prep(hipStream_t s, const ResidentBatchPrepArgs& a, uint32_t total) {
     if (total) resident_batch_prep_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
+}
+
+void launch_resident_batch_spec_prep(hipStream_t s, const ResidentBatchSpecPrepArgs& a, uint32_t total) {
+    if (total) resident_batch_spec_prep_kernel<<<(total + 255) / 256, 256, 0, s>>>(a);
 }
 
 int argmax_batch_blocks(uint64_t n) {

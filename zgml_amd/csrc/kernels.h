@@ -475,6 +475,32 @@ struct SpecArgs {
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
+// ── speculative decode under batching (zgml_hip_resident_decode_batch_speculative): the same two tails, one workgroup per sequence ──
+// `a` is sequence 0's view and T the columns of ONE sequence; sequence b's view lies at fixed strides behind it: words + b *
+// kSpecWords, hist + b * hist_cap, drafts + b * drafts_stride, cand + b * T, pval / pidx + b * T * nblk, tokens + b * cap with cap =
+// words[n_seqs * kSpecWords], the row length of this call's token table (a device word: the graph serves every max_tokens). A
+// sequence that has its count idles at its END position (the single loop idles one position in front of it): its state, history
+// and counters stay as they are. Greedy form only: picks / sparams / lp_* / top_* stay null.
+struct SpecBatchArgs {
+    SpecArgs a;
+    uint32_t n_seqs, drafts_stride;
+};
+void launch_spec_batch_draft(hipStream_t s, const SpecBatchArgs& a);
+void launch_spec_batch_accept(hipStream_t s, const SpecBatchArgs& a);
+// The prep of that step (cf. ResidentBatchPrepArgs): n_seqs * T columns, column b * T + j from token cand[b * T + j] at position
+// run_pos(b) + j, run_pos(b) = words[b * kSpecWords + kSpecRunPos]; every dynamic word from the run position of ITS sequence: dyn_base
+// + pos * dyn_stride (kind 1) or pos + T (kind 2).
+struct ResidentBatchSpecPrepArgs {
+    const float *embed, *cos, *sin;
+    float *tok_in, *mask;
+    float* const* rope_bufs;
+    const uint32_t *dyn_kind, *dyn_base, *dyn_stride, *dyn_seq;
+    uint32_t* dyn;
+    const uint32_t* words; // [n_seqs][kSpecWords]
+    const uint32_t* cand;  // [n_seqs * T]
+    uint32_t d, max_seq, dh, n_rope, n_ops, B, T;
+};
+void launch_resident_batch_spec_prep(hipStream_t s, const ResidentBatchSpecPrepArgs& a, uint32_t total); // total = B T (d + max_seq + n_rope 2 dh) + n_ops
 // ── seeded top-k / top-p sampling (sample.hip; the rule is sample.h's): the sampled token tail, two launches like launch_argmax ──
 // One row's parameters as the kernels read them (uploaded per call: one captured graph serves every parameter set).
 struct SampleParamsDev {

@@ -1,6 +1,7 @@
 // runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up; the greedy loops
 // (single-sequence decode, batched decode, the prefill chunk); their sampled forms and the sampled / greedy speculative verify
-// loop; the blocking calls over one buffer range (zgml_hip_sample, zgml_hip_logprobs, zgml_hip_top_logprobs) with their result
+// loop, and the greedy verify loop of every sequence of a batched plan; the blocking calls over one buffer range
+// (zgml_hip_sample, zgml_hip_logprobs, zgml_hip_top_logprobs) with their result
 // getters; the token constraint's create / attach / state. Everything a step needs (embedding row, mask column, RoPE rows, the
 // dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
 // copy-out at the end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_once, then
@@ -56,6 +57,17 @@ struct zgml_resident {
     uint32_t* hist = nullptr;
     uint32_t* drafts = nullptr;
     uint32_t* picks = nullptr; // the sampled form's token of every logits row, [T] (zgml_hip_resident_decode_speculative_sampled)
+    // speculative loop over a batched plan with tokens_per_seq = Ts >= 2 columns per sequence (token_len = n_seqs * Ts;
+    // zgml_hip_resident_decode_batch_speculative), allocated by its first call: per sequence the state words, then one word, the row
+    // length of the call's token table (kernels.h: SpecBatchArgs); the history rows [n_seqs][max_seq + 1]; the provided drafts
+    // [n_seqs][max_seq]. The candidates are tok_dev, the rows' partial maxima bval / bidx, the produced tokens btokens. The step's
+    // graph is its own: no other loop runs on such a plan, and no other call's graph is dropped for it
+    uint32_t tokens_per_seq = 1;
+    uint32_t* bspec = nullptr;
+    uint32_t* bhist = nullptr;
+    uint32_t* bdrafts = nullptr;
+    hipGraph_t bspec_graph = nullptr;
+    hipGraphExec_t bspec_graph_exec = nullptr;
     // sampled tail (zgml_hip_resident_decode_sampled / _batch_sampled / _speculative_sampled), allocated by the first such call: one
     // parameter row and one set of partial candidate lists per sequence (per logits row of a token_len > 1 plan, whose verify
     // step reads parameter row 0 alone)
@@ -111,6 +123,9 @@ void free_resident_graph(zgml_hip_program* p) {
     if (r->graph_multi_exec) hipGraphExecDestroy(r->graph_multi_exec);
     if (r->graph_multi) hipGraphDestroy(r->graph_multi);
     r->graph_multi_exec = nullptr, r->graph_multi = nullptr, r->multi_n = 0;
+    if (r->bspec_graph_exec) hipGraphExecDestroy(r->bspec_graph_exec);
+    if (r->bspec_graph) hipGraphDestroy(r->bspec_graph);
+    r->bspec_graph_exec = nullptr, r->bspec_graph = nullptr;
     for (uint32_t f = 0; f < kSampledForms; f++) {
         if (r->sgraph_exec[f]) hipGraphExecDestroy(r->sgraph_exec[f]);
         if (r->sgraph[f]) hipGraphDestroy(r->sgraph[f]);
@@ -141,6 +156,9 @@ void free_resident(zgml_hip_program* p) {
     hipFree(r->hist);
     hipFree(r->drafts);
     hipFree(r->picks);
+    hipFree(r->bspec);
+    hipFree(r->bhist);
+    hipFree(r->bdrafts);
     hipFree(r->sparams);
     hipFree(r->skeys);
     hipFree(r->swin);
@@ -171,6 +189,14 @@ namespace {
 bool refuse_constrained(zgml_hip_ctx* ctx, const zgml_hip_program* p, const char* who) {
     if (!has_constraint(p)) return false;
     ctx->fail(std::string(who) + ": a constraint is attached to the program (only zgml_hip_resident_decode_sampled, _batch_sampled and zgml_hip_sample honour one: detach it first)");
+    return true;
+}
+
+// the batched loops that advance one token per sequence and step, on a plan with several columns per sequence; true: refused
+bool refuse_verify_plan(zgml_hip_ctx* ctx, const Resident* r, const char* who) {
+    if (r->tokens_per_seq <= 1) return false;
+    ctx->fail(std::string(who) + ": the batched plan holds " + std::to_string(r->tokens_per_seq) +
+              " columns per sequence (tokens_per_seq > 1: zgml_hip_resident_decode_batch_speculative runs it)");
     return true;
 }
 
@@ -578,14 +604,18 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
         ctx->fail("resident_setup: attn_mask / logits smaller than token_len columns / rows");
         return -1;
     }
-    if (p->n_seqs && T != p->n_seqs) {
-        ctx->fail("resident_setup: the program declares " + std::to_string(p->n_seqs) + " sequences but token_input holds " + std::to_string(T) + " columns");
+    if (p->n_seqs && (T == 0 || T % p->n_seqs != 0)) {
+        ctx->fail("resident_setup: the program declares " + std::to_string(p->n_seqs) + " sequences but token_input holds " + std::to_string(T) +
+                  " columns (not a multiple of them)");
         return -1;
     }
     Resident* r = new Resident();
     p->resident = r;
     r->token_len = T;
-    r->n_seqs = p->n_seqs; // > 0: the T columns are T sequences (zgml_hip_resident_decode_batch), not T consecutive positions
+    // > 0: the T columns are n_seqs sequences of tokens_per_seq consecutive positions each — one (zgml_hip_resident_decode_batch) or
+    // several (zgml_hip_resident_decode_batch_speculative) —, not T consecutive positions of one
+    r->n_seqs = p->n_seqs;
+    r->tokens_per_seq = p->n_seqs ? T / p->n_seqs : 1;
     r->vocab = d->vocab, r->d = d->d_model, r->max_seq = d->max_seq, r->dh = d->d_head, r->n_rope = d->n_rope;
     r->tok_in = p->bufs[d->buf_token_input], r->mask = p->bufs[d->buf_attn_mask], r->logits = p->bufs[d->buf_logits];
     const size_t n_ops = p->ops.size();
@@ -624,7 +654,7 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
     if (ok && r->n_seqs) {
         std::vector<uint32_t> seq(n_ops + 1, 0);
         for (size_t i = 0; i < n_ops; i++) seq[i] = kind[i] && i < p->op_seq.size() && p->op_seq[i] != UINT32_MAX ? p->op_seq[i] : 0;
-        const size_t pairs = (size_t)r->n_seqs * argmax_batch_blocks(d->vocab);
+        const size_t pairs = (size_t)T * argmax_batch_blocks(d->vocab); // (a row per column: n_seqs, or n_seqs * tokens_per_seq of a verify step)
         ok = CTX_CHECK(ctx, hipMalloc((void**)&r->bstate, ((size_t)4 * r->n_seqs + 1) * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_seq, (n_ops + 1) * 4)) &&
              CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) && CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))) &&
              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_seq, seq.data(), n_ops * 4));
@@ -719,6 +749,7 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
         ctx->fail("resident_decode_batch: not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
         return -1;
     }
+    if (refuse_verify_plan(ctx, r, "resident_decode_batch")) return -1;
     if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
     if (refuse_constrained(ctx, p, "resident_decode_batch")) return -1;
     const uint32_t B = r->n_seqs;
@@ -1080,6 +1111,7 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         ctx->fail("resident_decode_batch_sampled: not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
         return -1;
     }
+    if (refuse_verify_plan(ctx, r, "resident_decode_batch_sampled")) return -1;
     if (!first_tokens || !start_pos || !n_steps || (max_steps && !tokens_out)) return -1;
     const uint32_t B = r->n_seqs;
     std::vector<SampleParamsDev> sp(B);
@@ -1205,6 +1237,42 @@ int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const 
 
 namespace {
 
+// What the speculative loops ask of ONE sequence's request (include/zgml_hip.h), refused before anything is enqueued; -> the
+// options with their defaults filled in. T: the columns of a verify step of the sequence. idle_at_end: the batched loop, whose
+// finished sequences idle at their end position and store T columns there
+struct SpecRequest {
+    zgml_spec_decode o{nullptr, 0, 0, nullptr, 0, 0};
+    uint32_t ngram = kSpecDefaultNgram, n_drafts = 0;
+};
+bool spec_request(zgml_hip_ctx* ctx, const Resident* r, const std::string& who, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens, uint32_t T,
+                  bool idle_at_end, const zgml_spec_decode* opt, SpecRequest* out) {
+    if (opt) out->o = *opt;
+    const zgml_spec_decode& o = out->o;
+    out->ngram = o.ngram ? o.ngram : kSpecDefaultNgram;
+    if (o.mode > 1 || out->ngram > kSpecMaxNgram) {
+        ctx->fail(who + ": mode must be 0 or 1 and ngram at most " + std::to_string(kSpecMaxNgram));
+        return false;
+    }
+    if ((o.n_history != 0 && o.n_history != start_pos) || (o.n_history && !o.history) || (o.mode == 1 && o.n_drafts && !o.drafts)) {
+        ctx->fail(who + ": n_history must be 0 or start_pos (with the tokens), provided drafts need their array");
+        return false;
+    }
+    // the last step may start at start_pos + n_tokens - 1 and stores T columns; an idle step starts one column behind that
+    if ((uint64_t)start_pos + n_tokens + T - (idle_at_end ? 0 : 1) > r->max_seq) {
+        ctx->fail(who + (idle_at_end ? ": start_pos + n_tokens + tokens_per_seq exceeds max_seq" : ": start_pos + n_tokens + token_len - 1 exceeds max_seq"));
+        return false;
+    }
+    out->n_drafts = o.mode == 1 ? o.n_drafts : 0;
+    bool in_vocab = first_token < r->vocab;
+    for (uint32_t i = 0; in_vocab && i < o.n_history; i++) in_vocab = o.history[i] < r->vocab;
+    for (uint32_t i = 0; in_vocab && i < out->n_drafts; i++) in_vocab = o.drafts[i] < r->vocab;
+    if (!in_vocab) {
+        ctx->fail(who + ": token out of range (first token, history or drafts)");
+        return false;
+    }
+    return true;
+}
+
 // Speculative decode of one sequence over a token_len = T plan (contract: include/zgml_hip.h; rules: spec.h), both forms. Per
 // verify step [draft] [prep, T tokens] [plan] [argmax stage 1 over T rows] [accept + advance], captured once as one graph; the
 // sampled form (`sampled`: zgml_hip_resident_decode_speculative_sampled) has [select] [merge + pick] over the T rows in the
@@ -1217,7 +1285,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     if (n_produced) *n_produced = 0;
     if (refuse_constrained(ctx, p, who.c_str())) return -1;
     if (r->n_seqs) {
-        ctx->fail(who + ": the program is a batched plan (speculation under batching is not supported)");
+        ctx->fail(who + ": the program is a batched plan (one sequence only here: zgml_hip_resident_decode_batch_speculative runs a batched plan with tokens_per_seq >= 2)");
         return -1;
     }
     const uint32_t T = r->token_len;
@@ -1228,30 +1296,10 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     if (stats) *stats = zgml_spec_stats{0, 0, 0, 0};
     if (!n_tokens) return 0;
     if (!tokens_out) return -1;
-    const zgml_spec_decode none{nullptr, 0, 0, nullptr, 0, 0};
-    const zgml_spec_decode& o = opt ? *opt : none;
-    const uint32_t ngram = o.ngram ? o.ngram : kSpecDefaultNgram;
-    if (o.mode > 1 || ngram > kSpecMaxNgram) {
-        ctx->fail(who + ": mode must be 0 or 1 and ngram at most " + std::to_string(kSpecMaxNgram));
-        return -1;
-    }
-    if ((o.n_history != 0 && o.n_history != start_pos) || (o.n_history && !o.history) || (o.mode == 1 && o.n_drafts && !o.drafts)) {
-        ctx->fail(who + ": n_history must be 0 or start_pos (with the tokens), provided drafts need their array");
-        return -1;
-    }
-    // the last step may start at start_pos + n_tokens - 1 and stores T columns
-    if ((uint64_t)start_pos + n_tokens + T - 1 > r->max_seq) {
-        ctx->fail(who + ": start_pos + n_tokens + token_len - 1 exceeds max_seq");
-        return -1;
-    }
-    const uint32_t n_drafts = o.mode == 1 ? o.n_drafts : 0;
-    bool in_vocab = first_token < r->vocab;
-    for (uint32_t i = 0; in_vocab && i < o.n_history; i++) in_vocab = o.history[i] < r->vocab;
-    for (uint32_t i = 0; in_vocab && i < n_drafts; i++) in_vocab = o.drafts[i] < r->vocab;
-    if (!in_vocab) {
-        ctx->fail(who + ": token out of range (first token, history or drafts)");
-        return -1;
-    }
+    SpecRequest req;
+    if (!spec_request(ctx, r, who, first_token, start_pos, n_tokens, T, false, opt, &req)) return -1;
+    const zgml_spec_decode& o = req.o;
+    const uint32_t ngram = req.ngram, n_drafts = req.n_drafts;
     SampleParamsDev sp{};
     if (sampled && !sampling_params(ctx, who, sampling, r->vocab, r->vocab, &sp, RecentOf::Spec)) return -1;
     const bool penalized = sp.pen_active != 0, lp = sampled && sampling->logprobs, top = sp.top_logprobs != 0; // (sampled form only; top: only with lp)
@@ -1367,6 +1415,122 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
                                                  const zgml_spec_decode* opt, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced,
                                                  zgml_spec_stats* stats) {
     return spec_decode(ctx, p, "resident_decode_speculative_sampled", first_token, start_pos, n_tokens, opt, true, sampling, tokens_out, n_produced, stats);
+}
+
+// Greedy-exact speculative decode of n_seqs sequences over a batched plan with Ts = tokens_per_seq columns per sequence (contract:
+// include/zgml_hip.h; rules: spec.h). Per step [draft, B sequences] [prep, B Ts columns] [plan] [argmax stage 1 over B Ts rows]
+// [accept + advance, B sequences], one graph of its own; sequence b's device state is spec_decode()'s, at row b of every block.
+int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                               const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, int64_t* tokens_out,
+                                               zgml_spec_stats* stats) {
+    if (!ctx || !p) return -1;
+    const std::string who = "resident_decode_batch_speculative";
+    Resident* r = p->resident;
+    if (!r || !r->n_seqs || !p->n_seqs) {
+        ctx->fail(who + ": not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
+        return -1;
+    }
+    const uint32_t B = r->n_seqs, Ts = r->tokens_per_seq;
+    if (Ts < 2) {
+        ctx->fail(who + ": the batched plan holds one column per sequence (a verify step needs tokens_per_seq >= 2)");
+        return -1;
+    }
+    if (refuse_constrained(ctx, p, who.c_str())) return -1;
+    if (!first_tokens || !start_pos || !n_tokens || (max_tokens && !tokens_out)) {
+        ctx->fail(who + ": NULL array (first_tokens, start_pos, n_tokens, or tokens_out with max_tokens > 0)");
+        return -1;
+    }
+    std::vector<SpecRequest> req(B);
+    uint32_t most = 0;
+    for (uint32_t b = 0; b < B; b++) {
+        const std::string seq = who + " (sequence " + std::to_string(b) + ")";
+        if (n_tokens[b] > max_tokens) {
+            ctx->fail(seq + ": n_tokens exceeds max_tokens");
+            return -1;
+        }
+        if (!spec_request(ctx, r, seq, first_tokens[b], start_pos[b], n_tokens[b], Ts, true, per_seq ? per_seq + b : nullptr, &req[b])) return -1;
+        most = std::max(most, n_tokens[b]);
+    }
+    for (uint64_t i = 0; i < (uint64_t)B * max_tokens; i++) tokens_out[i] = -1;
+    for (uint32_t b = 0; stats && b < B; b++) stats[b] = zgml_spec_stats{0, 0, 0, 0};
+    if (!most) return 0;
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->stream;
+    // every sequence's first start and its last possible one: the position it idles at
+    resident_begin(p, [&] {
+        return positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) &&
+               positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]] + n_tokens[p->op_seq[i]]; });
+    });
+    const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1, n_words = B * kSpecWords + 1;
+    if (!r->bspec && (!CTX_CHECK(ctx, hipMalloc((void**)&r->bspec, (size_t)n_words * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->bhist, (size_t)B * hist_cap * 4)) ||
+                      !CTX_CHECK(ctx, hipMalloc((void**)&r->bdrafts, (size_t)B * r->max_seq * 4))))
+        return -1;
+    if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * max_tokens)) return -1;
+    std::vector<uint32_t> w0(n_words, 0), w1(n_words, 0);
+    w0[(size_t)B * kSpecWords] = max_tokens; // row length of the device token table of this call
+    bool up = true;
+    for (uint32_t b = 0; up && b < B; b++) {
+        uint32_t* w = w0.data() + (size_t)b * kSpecWords;
+        const zgml_spec_decode& o = req[b].o;
+        w[kSpecTok] = first_tokens[b], w[kSpecPos] = start_pos[b], w[kSpecWanted] = n_tokens[b], w[kSpecMode] = o.mode, w[kSpecNgram] = req[b].ngram;
+        w[kSpecNDrafts] = std::min(req[b].n_drafts, r->max_seq), w[kSpecStart] = start_pos[b], w[kSpecHistLo] = o.n_history ? 0 : start_pos[b];
+        w[kSpecRunPos] = start_pos[b];
+        uint32_t* const hist = r->bhist + (size_t)b * hist_cap;
+        // (the host arrays are the caller's or this call's, and every copy below is waited for before the call returns)
+        up = (!o.n_history || CTX_CHECK(ctx, hipMemcpyAsync(hist, o.history, (size_t)o.n_history * 4, hipMemcpyHostToDevice, s))) &&
+             CTX_CHECK(ctx, hipMemcpyAsync(hist + start_pos[b], first_tokens + b, 4, hipMemcpyHostToDevice, s)) &&
+             (!w[kSpecNDrafts] || CTX_CHECK(ctx, hipMemcpyAsync(r->bdrafts + (size_t)b * r->max_seq, o.drafts, (size_t)w[kSpecNDrafts] * 4, hipMemcpyHostToDevice, s)));
+    }
+    if (!up || !CTX_CHECK(ctx, hipMemcpyAsync(r->bspec, w0.data(), w0.size() * 4, hipMemcpyHostToDevice, s)) ||
+        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * max_tokens * 8, s))) { // (-1: what a sequence leaves behind its count)
+        hipStreamSynchronize(s); // (w0 is read by a copy that may be in flight)
+        return -1;
+    }
+    SpecBatchArgs sa{{r->bspec, r->bhist, r->bdrafts, r->tok_dev, r->btokens, r->bval, r->bidx, Ts, nblk, r->vocab, hist_cap, 0 /* the device word */}, B, r->max_seq};
+    const ResidentBatchSpecPrepArgs prep{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
+                                         p->dyn_dev, r->bspec, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B, Ts};
+    auto one_step = [&](hipStream_t st) {
+        launch_spec_batch_draft(st, sa);
+        launch_resident_batch_spec_prep(st, prep, r->prep_total);
+        run_plan(p, st, 0, p->plan.size());
+        launch_argmax_rows_stage1(st, r->logits, r->vocab, B * Ts, r->bval, r->bidx);
+        launch_spec_batch_accept(st, sa);
+    };
+    // (as the batched loops: no pageable copy in flight when the capture begins)
+    capture_once(ctx, s, "resident_batch_spec", true, one_step, &r->bspec_graph, &r->bspec_graph_exec);
+    // the host cannot know how many steps the drafts save: it launches the fewest that can finish the sequence with the most
+    // tokens left, reads the counts back, repeats
+    std::vector<uint32_t> produced(B, 0);
+    uint64_t steps_run = 0;
+    bool ok = true;
+    while (ok) {
+        uint32_t round = 0;
+        for (uint32_t b = 0; b < B; b++) round = std::max(round, (n_tokens[b] - produced[b] + Ts - 1) / Ts);
+        if (!round) break;
+        replay(s, r->bspec_graph_exec, round, one_step);
+        steps_run += round;
+        hipMemcpyAsync(w1.data(), r->bspec, w1.size() * 4, hipMemcpyDeviceToHost, s);
+        ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+        for (uint32_t b = 0; ok && b < B; b++) {
+            const uint32_t now = std::min(w1[(size_t)b * kSpecWords + kSpecProduced], n_tokens[b]);
+            if (produced[b] < n_tokens[b] && now <= produced[b]) { // (every step of a sequence with tokens left emits at least one)
+                ctx->fail(who + ": a round of verify steps produced nothing (sequence " + std::to_string(b) + ")");
+                ok = false;
+            }
+            produced[b] = now;
+        }
+    }
+    if (ok) {
+        hipMemcpyAsync(tokens_out, r->btokens, (size_t)B * max_tokens * 8, hipMemcpyDeviceToHost, s); // (the device rows are max_tokens long too)
+        ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
+    }
+    ok = ok && ctx->handoff_ok(who.c_str());
+    for (uint32_t b = 0; ok && stats && b < B; b++) {
+        const uint32_t* w = w1.data() + (size_t)b * kSpecWords;
+        stats[b] = zgml_spec_stats{w[kSpecSteps], w[kSpecDrafted], w[kSpecAccepted], 0};
+    }
+    resident_end(p, steps_run, p->plan.size() + 4); // per step [draft] [prep] [plan] [argmax stage 1] [accept]
+    return ok ? 0 : -1;
 }
 
 } // extern "C"

@@ -3,6 +3,8 @@
 // [select] [merge + pick] over the T rows in the place of the argmax stage). Both are one workgroup and launches of
 // their own: DESIGN section 0.2 item 5 measured that folding such tails into a neighbouring launch is slower. The rules themselves
 // (which tokens are drafted, how many are accepted) are spec.h's; here is only how a workgroup evaluates them.
+// Each body is stated once, as a device function over ONE sequence's SpecArgs: the single-sequence kernels hand it their
+// arguments, the batched kernels (zgml_hip_resident_decode_batch_speculative; blockIdx.x = sequence) the sequence's view of theirs.
 #include "kernels.h"
 #include "spec.h"
 #include "tail_device.h"
@@ -16,17 +18,20 @@ constexpr int kSpecWaves = kSpecBlock / 64;
 // The candidates of this step into a.cand (what the prep launch reads as its T token ids) and the position it runs at into the
 // run words. Lookup mode: for n = ngram .. 1 the threads walk the match positions [n - 1, pos - 1] downwards, 256 apart — a
 // thread's first hit is its largest —, the largest hit of the workgroup is folded with wave shuffles and one pass over LDS, and
-// the first n with a hit wins. Provided mode is a table read. Thread 0 writes.
-__global__ void __launch_bounds__(kSpecBlock) spec_draft_kernel(SpecArgs a) {
-    __shared__ int32_t fold[kSpecWaves];
+// the first n with a hit wins. Provided mode is a table read. Thread 0 writes. fold: kSpecWaves LDS words.
+// kIdleAtEnd: where a sequence that has its count runs its idle steps (below).
+template <bool kIdleAtEnd>
+__device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold) {
     uint32_t* const w = a.words;
     const uint32_t pos = w[kSpecPos], lo = w[kSpecHistLo];
     if (w[kSpecProduced] >= w[kSpecWanted]) {
         // nothing left to produce: the step still runs (it is part of a graph the host has already launched), so it repeats the
         // last confirmed token at its own position — that KV column is rewritten from the same context, everything behind it is
-        // unspecified anyway — and spec_accept_kernel leaves the state alone. (produced >= 1 here: pos - 1 >= start_pos >= lo.)
+        // unspecified anyway — and the accept launch leaves the state alone. (produced >= 1 here: pos - 1 >= start_pos >= lo.)
+        // kIdleAtEnd, the batched loop, where a sequence may want no token at all and hist[pos - 1] need not exist: the token
+        // that IS confirmed but not yet cached, hist[pos], at pos — the T columns from the sequence's end position are unspecified.
         if (threadIdx.x == 0) {
-            const uint32_t at = pos > lo ? pos - 1 : pos;
+            const uint32_t at = !kIdleAtEnd && pos > lo ? pos - 1 : pos;
             for (uint32_t j = 0; j < a.T; j++) a.cand[j] = a.hist[at];
             w[kSpecRunPos] = at;
         }
@@ -71,8 +76,9 @@ __global__ void __launch_bounds__(kSpecBlock) spec_draft_kernel(SpecArgs a) {
 // and the counters. The sampled form cuts the emission behind the first stop token and then sets wanted = produced: every later
 // step of the round idles, and the host's round loop ends on the words it reads back. With a.lp_out the log-probabilities of the
 // emitted tokens go next to them: row k's value of g[k], computed for all T rows behind the pick (logprob.hip).
-__global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
-    extern __shared__ uint32_t g[]; // [T]
+// g: T LDS words; emitted: one.
+__device__ __forceinline__ void spec_accept_body(const SpecArgs& a, uint32_t* g, uint32_t* emitted_word) {
+    uint32_t& emitted = *emitted_word; // (the form with alternatives only) m, for the copy below
     uint32_t* const w = a.words;
     const uint32_t produced = w[kSpecProduced], wanted = w[kSpecWanted];
     if (produced >= wanted) return; // (uniform) an idle step changes nothing
@@ -85,7 +91,6 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
         if (lane == 0) g[j] = (uint64_t)bi < a.vocab ? (uint32_t)bi : 0u; // (a row always has vocab > 0 entries: the clamp is for the embedding gather's sake)
     }
     __syncthreads();
-    __shared__ uint32_t emitted; // (the form with alternatives only) m, for the copy below
     if (threadIdx.x == 0) {
         const uint32_t pos = w[kSpecPos];
         const uint32_t acc = spec_accept(a.cand, g, a.T);
@@ -117,10 +122,49 @@ __global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
     }
 }
 
+// sequence b's view of a batched launch's arguments (kernels.h: SpecBatchArgs)
+__device__ __forceinline__ SpecArgs spec_seq_view(const SpecBatchArgs& ba, uint32_t b) {
+    SpecArgs v = ba.a;
+    const uint32_t cap = ba.a.words[(uint64_t)ba.n_seqs * kSpecWords]; // row length of this call's token table
+    v.words += (uint64_t)b * kSpecWords;
+    v.hist += (uint64_t)b * v.hist_cap;
+    v.drafts += (uint64_t)b * ba.drafts_stride;
+    v.cand += (uint64_t)b * v.T;
+    v.tokens += (uint64_t)b * cap, v.tokens_cap = cap;
+    v.pval += (uint64_t)b * v.T * v.nblk, v.pidx += (uint64_t)b * v.T * v.nblk;
+    return v;
+}
+
+__global__ void __launch_bounds__(kSpecBlock) spec_draft_kernel(SpecArgs a) {
+    __shared__ int32_t fold[kSpecWaves];
+    spec_draft_body<false>(a, fold);
+}
+__global__ void __launch_bounds__(kSpecBlock) spec_accept_kernel(SpecArgs a) {
+    extern __shared__ uint32_t g[]; // [T]
+    __shared__ uint32_t emitted;
+    spec_accept_body(a, g, &emitted);
+}
+// the batched forms: workgroup b is sequence b
+__global__ void __launch_bounds__(kSpecBlock) spec_batch_draft_kernel(SpecBatchArgs ba) {
+    __shared__ int32_t fold[kSpecWaves];
+    spec_draft_body<true>(spec_seq_view(ba, blockIdx.x), fold);
+}
+__global__ void __launch_bounds__(kSpecBlock) spec_batch_accept_kernel(SpecBatchArgs ba) {
+    extern __shared__ uint32_t g[]; // [T]
+    __shared__ uint32_t emitted;
+    spec_accept_body(spec_seq_view(ba, blockIdx.x), g, &emitted);
+}
+
 } // namespace
 
 void launch_spec_draft(hipStream_t s, const SpecArgs& a) { spec_draft_kernel<<<1, kSpecBlock, 0, s>>>(a); }
 
 void launch_spec_accept(hipStream_t s, const SpecArgs& a) { spec_accept_kernel<<<1, kSpecBlock, a.T * sizeof(uint32_t), s>>>(a); }
+
+void launch_spec_batch_draft(hipStream_t s, const SpecBatchArgs& a) { spec_batch_draft_kernel<<<a.n_seqs, kSpecBlock, 0, s>>>(a); }
+
+void launch_spec_batch_accept(hipStream_t s, const SpecBatchArgs& a) {
+    spec_batch_accept_kernel<<<a.n_seqs, kSpecBlock, a.a.T * sizeof(uint32_t), s>>>(a);
+}
 
 } // namespace zgml

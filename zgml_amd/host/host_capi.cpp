@@ -108,9 +108,10 @@ zh_model* zh_model_create_like(zh_model* base, int fused_elementwise, int includ
 
 // The batched decode program of `n_seqs` sequences (build_batch_decode_program). NULL and a text in `err` (cap bytes, NUL-terminated)
 // for what the builder refuses: a config with its own int8 KV caches, a sharded config, n_seqs outside 1..32.
-// kv_quant_block: the builder's parameter (0: f32 slabs; 32: per-sequence int8 caches).
-zh_model* zh_model_create_batch_kvq(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
-                                    uint32_t kv_quant_block, char* err, uint64_t err_cap) {
+// kv_quant_block: the builder's parameter (0: f32 slabs; 32: per-sequence int8 caches). tokens_per_seq: likewise (1: one column per
+// sequence; 2..16: the B x Ts plan of a batched verify step).
+zh_model* zh_model_create_batch_ts(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
+                                   uint32_t kv_quant_block, uint32_t tokens_per_seq, char* err, uint64_t err_cap) {
     auto fail = [&](const std::string& why) -> zh_model* {
         if (err && err_cap) {
             const size_t n = std::min<size_t>(err_cap - 1, why.size());
@@ -127,11 +128,11 @@ zh_model* zh_model_create_batch_kvq(const zh_config* cfg, int weight_kind, int f
     c.kv_quant_block = cfg->kv_quant_block;
     if (c.n_heads == 0 || c.n_kv_heads == 0 || c.d_model % c.n_heads || c.n_heads % c.n_kv_heads) return fail("invalid LlamaConfig");
     // the builder's refusals first: they need no weights
-    if (const char* why = batch_refusal(c, n_seqs, kv_quant_block)) return fail(why);
+    if (const char* why = batch_refusal(c, n_seqs, kv_quant_block, tokens_per_seq)) return fail(why);
     auto* m = new zh_model();
     m->model = make_synthetic_model(c, (WeightKind)weight_kind, threads);
     std::string why;
-    m->dp = build_batch_decode_program(*m->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why, kv_quant_block);
+    m->dp = build_batch_decode_program(*m->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why, kv_quant_block, tokens_per_seq);
     if (!m->dp) {
         delete m;
         return fail(why);
@@ -139,15 +140,19 @@ zh_model* zh_model_create_batch_kvq(const zh_config* cfg, int weight_kind, int f
     m->flat = m->dp->program.view(m->qw_storage);
     return m;
 }
+zh_model* zh_model_create_batch_kvq(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
+                                    uint32_t kv_quant_block, char* err, uint64_t err_cap) {
+    return zh_model_create_batch_ts(cfg, weight_kind, fused_elementwise, include_dead_f32, threads, n_seqs, kv_quant_block, 1, err, err_cap);
+}
 zh_model* zh_model_create_batch(const zh_config* cfg, int weight_kind, int fused_elementwise, int include_dead_f32, int threads, uint32_t n_seqs,
                                 char* err, uint64_t err_cap) {
     return zh_model_create_batch_kvq(cfg, weight_kind, fused_elementwise, include_dead_f32, threads, n_seqs, 0, err, err_cap);
 }
 // ... over the weights of an existing model (shared, not copied): the batched twin of `base` for n_seqs sequences
-zh_model* zh_model_create_batch_like_kvq(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, uint32_t kv_quant_block, char* err,
-                                         uint64_t err_cap) {
+zh_model* zh_model_create_batch_like_ts(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, uint32_t kv_quant_block,
+                                        uint32_t tokens_per_seq, char* err, uint64_t err_cap) {
     std::string why;
-    auto dp = build_batch_decode_program(*base->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why, kv_quant_block);
+    auto dp = build_batch_decode_program(*base->model, n_seqs, fused_elementwise != 0, include_dead_f32 != 0, &why, kv_quant_block, tokens_per_seq);
     if (!dp) {
         if (err && err_cap) {
             const size_t n = std::min<size_t>(err_cap - 1, why.size());
@@ -162,10 +167,15 @@ zh_model* zh_model_create_batch_like_kvq(zh_model* base, int fused_elementwise, 
     m->flat = m->dp->program.view(m->qw_storage);
     return m;
 }
+zh_model* zh_model_create_batch_like_kvq(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, uint32_t kv_quant_block, char* err,
+                                         uint64_t err_cap) {
+    return zh_model_create_batch_like_ts(base, fused_elementwise, include_dead_f32, n_seqs, kv_quant_block, 1, err, err_cap);
+}
 zh_model* zh_model_create_batch_like(zh_model* base, int fused_elementwise, int include_dead_f32, uint32_t n_seqs, char* err, uint64_t err_cap) {
     return zh_model_create_batch_like_kvq(base, fused_elementwise, include_dead_f32, n_seqs, 0, err, err_cap);
 }
 uint32_t zh_model_n_seqs(zh_model* m) { return m->dp->n_seqs; }
+uint32_t zh_model_tokens_per_seq(zh_model* m) { return m->dp->tokens_per_seq; }
 void zh_model_patch_batch(zh_model* m, const uint32_t* tokens, const uint32_t* pos) { patch_batch_step(*m->model, *m->dp, tokens, pos); }
 // every op with a position-dependent field and the sequence it follows (what zgml_hip_program_set_sequences takes); returns the count
 uint64_t zh_model_dyn_sequences(zh_model* m, uint32_t* op_indices, uint32_t* op_seq, uint64_t cap) {
@@ -311,22 +321,25 @@ int64_t zh_session_prefill(zh_session* s, const uint32_t* tokens, uint32_t pos, 
 
 void zh_session_set_refresh_dynamic_batch(zh_session* s, int (*fn)(void*, void*, const uint32_t*, const uint32_t*)) { s->refresh_dynamic_batch = fn; }
 
-// One step of a batched program: patch the B columns, refresh (per-sequence dynamic refresh when set, else the whole op list),
-// execute. logits_out: [B][vocab] (may be NULL); next_out[B]: each sequence's greedy token.
+// One step of a batched program: patch the B * Ts columns (Ts = tokens_per_seq consecutive positions of every sequence from pos[b]),
+// refresh (per-sequence dynamic refresh when set, else the whole op list), execute. tokens[B * Ts]; logits_out: [B * Ts][vocab] (may
+// be NULL); next_out[B * Ts]: every row's greedy token.
 int zh_session_step_batch(zh_session* s, const uint32_t* tokens, const uint32_t* pos, float* logits_out, int64_t* next_out) {
     DecodeProgram& dp = *s->m->dp;
-    const uint32_t B = dp.n_seqs, vocab = s->m->model->cfg.vocab_size;
+    const uint32_t B = dp.n_seqs, Ts = dp.tokens_per_seq, vocab = s->m->model->cfg.vocab_size;
     if (!B) return -1;
     for (uint32_t b = 0; b < B; b++)
-        if (tokens[b] >= vocab || pos[b] >= s->m->model->cfg.max_seq_len) return -1;
+        if ((uint64_t)pos[b] + Ts > s->m->model->cfg.max_seq_len) return -1;
+    for (uint32_t j = 0; j < B * Ts; j++)
+        if (tokens[j] >= vocab) return -1;
     patch_batch_step(*s->m->model, dp, tokens, pos);
     uint32_t seq_kv[kMaxBatchSeqs];
-    for (uint32_t b = 0; b < B; b++) seq_kv[b] = pos[b] + 1;
+    for (uint32_t b = 0; b < B; b++) seq_kv[b] = pos[b] + Ts;
     if (!(s->refresh_dynamic_batch && s->refresh_dynamic_batch(s->fns.ctx, s->handle, pos, seq_kv) == 0))
         s->fns.refresh_program(s->fns.ctx, s->handle, dp.program.ops.data(), dp.program.ops.size());
     s->fns.execute_program(s->fns.ctx, s->handle, dp.step_inputs.data(), dp.step_inputs.size(), dp.step_outputs.data(), dp.step_outputs.size());
     if (logits_out) std::memcpy(logits_out, dp.logits_host.data(), dp.logits_host.size() * sizeof(float));
-    for (uint32_t b = 0; b < B; b++) next_out[b] = LlamaDeviceSession::argmax(dp.logits_host.data() + (size_t)b * vocab, vocab);
+    for (uint32_t j = 0; j < B * Ts; j++) next_out[j] = LlamaDeviceSession::argmax(dp.logits_host.data() + (size_t)j * vocab, vocab);
     return 0;
 }
 

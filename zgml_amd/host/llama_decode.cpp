@@ -288,9 +288,11 @@ struct Builder {
 // attention section is the token_len = B plan (activations [d, B]); the attention section is, per sequence b, the token_len = 1
 // plan's op subsequence on column b, over sequence b's slab of the layer's K / V buffers — or, with kv_quant (the batched builder's
 // parameter; 0: the model's own cfg.kv_quant_block), over sequence b's own int8 caches, one buffer per (sequence, kv head, K | V).
+// tokens_per_seq = Ts > 1 (batched only): sequence b owns the Ts columns [b * Ts, (b + 1) * Ts) — Ts consecutive positions, the
+// candidates of a verify step — and its pass of the attention section is the token_len = Ts plan's on those columns.
 // nullptr when the plan needs more buffers than a 16-bit id names.
 static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, bool fused_elementwise, bool include_dead_f32, uint32_t token_len,
-                                                    uint32_t n_seqs, uint32_t kv_quant = 0) {
+                                                    uint32_t n_seqs, uint32_t kv_quant = 0, uint32_t tokens_per_seq = 1) {
     const LlamaConfig& c = model.cfg;
     auto dpp = std::make_unique<DecodeProgram>();
     DecodeProgram& dp = *dpp;
@@ -306,10 +308,12 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                           atoi(getenv("ZGML_HOST_SHARD_POINTS_WORLD1")) != 0;
     const bool sharded = ws > 1 || rehearse;
     const uint32_t B = n_seqs;
-    const uint32_t T = B ? B : (token_len ? token_len : 1); // tokens per execution: 1 = decode plan, N = prefill plan, B = one token of each sequence
+    const uint32_t Ts = B ? std::max(1u, tokens_per_seq) : 1;
+    const uint32_t T = B ? B * Ts : (token_len ? token_len : 1); // tokens per execution: 1 = decode plan, N = prefill plan, B * Ts = Ts tokens of each sequence
     dp.token_len = T;
     dp.n_seqs = B;
-    const uint32_t TA = B ? 1 : T;       // columns one pass of the attention section handles
+    dp.tokens_per_seq = Ts;
+    const uint32_t TA = B ? Ts : T;      // columns one pass of the attention section handles
     const uint32_t n_pass = B ? B : 1;   // ... and its passes (one per sequence)
     const uint32_t kvq = kv_quant ? kv_quant : c.kv_quant_block; // quantised KV: one int8 cache buffer per (sequence,) kv head (K and V)
     std::vector<std::vector<DecodeProgram::KvLane>> lanes(n_pass); // per sequence: (layer, kv head, K | V)
@@ -327,7 +331,7 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
     dp.token_input.assign((size_t)d * T, 0.f);
     dp.attn_mask.assign((size_t)S * T, -std::numeric_limits<float>::infinity()); // [max_seq, T], column per query
     for (uint32_t j = 0; j < T; j++)
-        for (uint32_t s2 = 0; s2 <= (B ? 0 : j); s2++) dp.attn_mask[(size_t)j * S + s2] = 0.f; // (batched: every sequence at position 0)
+        for (uint32_t s2 = 0; s2 <= j % TA; s2++) dp.attn_mask[(size_t)j * S + s2] = 0.f; // (batched: every sequence at position 0)
     dp.scalar_one.assign(1, 1.0f);
     dp.buf_token_input = b.leaf(dp.token_input);
     dp.buf_attn_mask = b.leaf(dp.attn_mask);
@@ -401,7 +405,7 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                     q_done = true;
                 }
                 const uint16_t q_rot = b.buffer((uint64_t)dh * TA);
-                b.op(DeviceOp::rope(q_rot, q_proj, rope_cs, dh / 2, TA, sq * d_loc + hl * dh, sq * 2 * dh, 0, 1, d_loc, 2 * dh));
+                b.op(DeviceOp::rope(q_rot, q_proj, rope_cs, dh / 2, TA, sq * TA * d_loc + hl * dh, sq * TA * 2 * dh, 0, 1, d_loc, 2 * dh));
                 if (!kv_done[kvl]) {
                     kv_done[kvl] = 1;
                     if (!k_proj_done) {
@@ -409,7 +413,7 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                         k_proj_done = true;
                     }
                     const uint16_t k_rot = b.buffer((uint64_t)dh * TA);
-                    b.op(DeviceOp::rope(k_rot, k_proj, rope_cs, dh / 2, TA, sq * kvd_loc + kvl * dh, sq * 2 * dh, 0, 1, kvd_loc, 2 * dh));
+                    b.op(DeviceOp::rope(k_rot, k_proj, rope_cs, dh / 2, TA, sq * TA * kvd_loc + kvl * dh, sq * TA * 2 * dh, 0, 1, kvd_loc, 2 * dh));
                     const uint32_t slab = seq_slab + kvl * S * dh; // k_cache.sliceColumns(kv_h*max_seq, ...)
                     if (kvq) { // k_cache.storeColumn(pos + j, k_rot[:, j]) (llama_inference.zig:300-320)
                         for (uint32_t j = 0; j < TA; j++) {
@@ -427,11 +431,11 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                     if (kvq) {
                         for (uint32_t j = 0; j < TA; j++) {
                             dyn_store(sq);
-                            b.op(DeviceOp::kvq_store({vq_cache[kvl], v_proj, dh, kvq, S, (sq + j) * kvd_loc + kvl * dh, j, j, 1}));
+                            b.op(DeviceOp::kvq_store({vq_cache[kvl], v_proj, dh, kvq, S, (sq * TA + j) * kvd_loc + kvl * dh, j, j, 1}));
                         }
                     } else {
                         dyn_store(sq);
-                        b.op(DeviceOp::slice_assign(v_cache, v_proj, dh, TA, slab, slab, 1, dh, sq * kvd_loc + kvl * dh, 1, kvd_loc, dh));
+                        b.op(DeviceOp::slice_assign(v_cache, v_proj, dh, TA, slab, slab, 1, dh, sq * TA * kvd_loc + kvl * dh, 1, kvd_loc, dh));
                     }
                 }
                 attn_out[hl] = b.buffer((uint64_t)dh * TA);
@@ -440,7 +444,7 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                     a.dst = attn_out[hl], a.q = q_rot, a.k = kq_cache[kvl], a.v = vq_cache[kvl], a.mask = dp.buf_attn_mask, a.has_mask = 1;
                     a.d_head = dh, a.seq_q = TA, a.seq_kv = S, a.scale = attn_scale, a.block_size = kvq, a.n_cols = S;
                     a.k_col_start = 0, a.v_col_start = 0, a.q_off = 0, a.q_cs = dh, a.dst_off = 0, a.dst_cs = dh;
-                    a.mask_off = sq * S, a.mask_rs = 1, a.mask_cs = S;
+                    a.mask_off = sq * TA * S, a.mask_rs = 1, a.mask_cs = S;
                     dp.attention_op_indices.push_back((uint32_t)dp.program.ops.size());
                     dp.attention_seq.push_back(sq);
                     b.op(DeviceOp::attention_kvq(a));
@@ -449,15 +453,15 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
                 zgml_op_attention a{};
                 a.dst = attn_out[hl], a.q = q_rot, a.k = k_cache, a.v = v_cache, a.mask = dp.buf_attn_mask, a.has_mask = 1;
                 a.d_head = dh, a.seq_q = TA, a.seq_kv = S, a.scale = attn_scale;
-                a.q_off = 0, a.k_off = seq_slab + kvl * S * dh, a.v_off = seq_slab + kvl * S * dh, a.mask_off = sq * S, a.dst_off = 0;
+                a.q_off = 0, a.k_off = seq_slab + kvl * S * dh, a.v_off = seq_slab + kvl * S * dh, a.mask_off = sq * TA * S, a.dst_off = 0;
                 a.q_rs = 1, a.q_cs = dh, a.k_rs = 1, a.k_cs = dh, a.v_rs = 1, a.v_cs = dh;
                 a.mask_rs = 1, a.mask_cs = S, a.dst_rs = 1, a.dst_cs = dh;
                 dp.attention_op_indices.push_back((uint32_t)dp.program.ops.size());
                 dp.attention_seq.push_back(sq);
                 b.op(DeviceOp::attention(a));
             }
-            for (uint32_t hl = 0; hl < H_loc; hl++) { // sliceAssignRows(attn_out, h*d_head): patch_stride 0 (batched: into column sq)
-                const uint32_t row = sq * d + (h0 + hl) * dh;
+            for (uint32_t hl = 0; hl < H_loc; hl++) { // sliceAssignRows(attn_out, h*d_head): patch_stride 0 (batched: into sequence sq's columns)
+                const uint32_t row = sq * TA * d + (h0 + hl) * dh;
                 dyn_store(sq);
                 b.op(DeviceOp::slice_assign(attn_buf, attn_out[hl], dh, TA, 0, row, 1, d, 0, 1, dh, 0));
             }
@@ -532,16 +536,17 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
     dp.step_inputs.push_back(io(dp.buf_attn_mask, dp.attn_mask));
     for (uint32_t l = 0; l < c.n_layers; l++) dp.step_inputs.push_back(io(dp.buf_rope[l], dp.rope_leaf[l]));
     // Last-column logits: [vocab, T] column-major -> last col at offset (T-1)*vocab (llama_inference.zig:463-465)
-    // (batched: every sequence's row, [vocab, B])
-    dp.logits_host.assign((size_t)c.vocab_size * (B ? B : 1), 0.f);
+    // (batched: every row, [vocab, B * Ts])
+    dp.logits_host.assign((size_t)c.vocab_size * (B ? T : 1), 0.f);
     backend::ProgramIO out_io = io(dp.buf_logits, dp.logits_host);
     out_io.offset = B ? 0 : (uint32_t)((size_t)(T - 1) * c.vocab_size * sizeof(float));
     dp.step_outputs.push_back(out_io);
     return dpp;
 }
 
-const char* batch_refusal(const LlamaConfig& c, uint32_t n_seqs, uint32_t kv_quant_block) {
+const char* batch_refusal(const LlamaConfig& c, uint32_t n_seqs, uint32_t kv_quant_block, uint32_t tokens_per_seq) {
     if (n_seqs < 1 || n_seqs > kMaxBatchSeqs) return "build_batch_decode_program: n_seqs must be 1..32";
+    if (tokens_per_seq < 1 || tokens_per_seq > kMaxBatchTokensPerSeq) return "build_batch_decode_program: tokens_per_seq must be 1..16";
     if (c.kv_quant_block != 0)
         return "build_batch_decode_program: int8 KV caches under batching come from the builder's kv_quant_block parameter, not from a model whose own "
                "cfg.kv_quant_block != 0";
@@ -556,36 +561,37 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
 }
 
 std::unique_ptr<DecodeProgram> build_batch_decode_program(const LlamaModel& model, uint32_t n_seqs, bool fused_elementwise, bool include_dead_f32,
-                                                          std::string* err, uint32_t kv_quant_block) {
+                                                          std::string* err, uint32_t kv_quant_block, uint32_t tokens_per_seq) {
     auto refuse = [&](const char* why) {
         if (err) *err = why;
         return std::unique_ptr<DecodeProgram>();
     };
-    if (const char* why = batch_refusal(model.cfg, n_seqs, kv_quant_block)) return refuse(why);
-    auto dp = build_program(model, fused_elementwise, include_dead_f32, n_seqs, n_seqs, kv_quant_block);
+    if (const char* why = batch_refusal(model.cfg, n_seqs, kv_quant_block, tokens_per_seq)) return refuse(why);
+    auto dp = build_program(model, fused_elementwise, include_dead_f32, n_seqs, n_seqs, kv_quant_block, tokens_per_seq);
     if (!dp) return refuse("build_batch_decode_program: the plan needs more than 65535 buffers (fewer sequences, or f32 caches)");
     return dp;
 }
 
-// LlamaInferencePlan.execute steps 1-4, per sequence: column b of token_input / attn_mask / every rope leaf from (tokens[b], pos[b]),
-// and every dynamic op from the position of ITS sequence
+// LlamaInferencePlan.execute steps 1-4, per sequence: sequence b's Ts columns of token_input / attn_mask / every rope leaf from
+// (tokens[b * Ts + j], pos[b] + j), and every dynamic op from the position of ITS sequence
 void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t* tokens, const uint32_t* pos) {
     const LlamaConfig& c = model.cfg;
-    const uint32_t d = c.d_model, dh = c.d_head(), S = c.max_seq_len, B = dp.n_seqs;
+    const uint32_t d = c.d_model, dh = c.d_head(), S = c.max_seq_len, B = dp.n_seqs, Ts = dp.tokens_per_seq;
     const float ninf = -std::numeric_limits<float>::infinity();
-    for (uint32_t b = 0; b < B; b++) {
-        std::memcpy(dp.token_input.data() + (size_t)b * d, model.token_embed.data() + (size_t)tokens[b] * d, d * sizeof(float));
-        float* col = dp.attn_mask.data() + (size_t)b * S;
-        const uint32_t valid_upto = pos[b] + 1;
-        std::fill(col, col + valid_upto, 0.f);
-        if (valid_upto < S) std::fill(col + valid_upto, col + S, ninf);
+    for (uint32_t col = 0; col < B * Ts; col++) {
+        const uint32_t at = pos[col / Ts] + col % Ts;
+        std::memcpy(dp.token_input.data() + (size_t)col * d, model.token_embed.data() + (size_t)tokens[col] * d, d * sizeof(float));
+        float* m = dp.attn_mask.data() + (size_t)col * S;
+        const uint32_t valid_upto = at + 1;
+        std::fill(m, m + valid_upto, 0.f);
+        if (valid_upto < S) std::fill(m + valid_upto, m + S, ninf);
         for (auto& leaf : dp.rope_leaf) {
-            std::memcpy(leaf.data() + (size_t)b * 2 * dh, model.cos_table.data() + (size_t)pos[b] * dh, dh * sizeof(float));
-            std::memcpy(leaf.data() + (size_t)b * 2 * dh + dh, model.sin_table.data() + (size_t)pos[b] * dh, dh * sizeof(float));
+            std::memcpy(leaf.data() + (size_t)col * 2 * dh, model.cos_table.data() + (size_t)at * dh, dh * sizeof(float));
+            std::memcpy(leaf.data() + (size_t)col * 2 * dh + dh, model.sin_table.data() + (size_t)at * dh, dh * sizeof(float));
         }
     }
     // (the dynamic fields as csrc/schedule.h's dyn_field defines them: a store's offset / column is base + pos * patch_stride, an
-    // attention's seq_kv is pos + 1)
+    // attention's seq_kv is pos + Ts)
     for (size_t k = 0; k < dp.slice_assign_op_indices.size(); k++) {
         auto& op = dp.program.ops[dp.slice_assign_op_indices[k]];
         const uint32_t at = pos[dp.slice_assign_seq[k]];
@@ -598,7 +604,7 @@ void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t
     }
     for (size_t k = 0; k < dp.attention_op_indices.size(); k++) {
         auto& op = dp.program.ops[dp.attention_op_indices[k]];
-        (op.kind == ZGML_DOP_ATTENTION_KVQ ? op.u.attention_kvq.seq_kv : op.u.attention.seq_kv) = pos[dp.attention_seq[k]] + 1;
+        (op.kind == ZGML_DOP_ATTENTION_KVQ ? op.u.attention_kvq.seq_kv : op.u.attention.seq_kv) = pos[dp.attention_seq[k]] + Ts;
     }
 }
 

@@ -82,6 +82,7 @@ struct DecodeProgram {
     std::vector<float> kv_zero;                 // zero initial KV (not uploaded: buffers start zeroed)
     uint32_t token_len = 1; // tokens per execution (1 = decode plan, N = prefill plan, B = batched decode plan)
     uint32_t n_seqs = 0;    // batched decode plan (build_batch_decode_program): independent sequences per step, else 0
+    uint32_t tokens_per_seq = 1; // ... and the consecutive columns each of them owns (token_len = n_seqs * tokens_per_seq)
     uint16_t buf_token_input = 0, buf_attn_mask = 0, buf_logits = 0;
     std::vector<uint16_t> buf_rope, buf_k_cache, buf_v_cache;
     // every KV-cache buffer of the plan, in builder order, with its f32-element count: the consolidated f32 caches
@@ -143,12 +144,20 @@ std::unique_ptr<DecodeProgram> build_decode_program(const LlamaModel& model, boo
 // The one wart: the int8 form is asked for by THIS parameter, while the single-sequence builder reads cfg.kv_quant_block. A model
 // whose own cfg.kv_quant_block != 0 stays refused here (a pinned refusal), so one f32-config model serves an f32 prefill plan and
 // an int8 batched plan. The row shard is out of scope. Refusals: nullptr and a text in *err.
+// tokens_per_seq = Ts in 2..kMaxBatchTokensPerSeq: every sequence runs Ts consecutive positions per step (the verify step of
+// zgml_hip_resident_decode_batch_speculative). Sequence-major: column b * Ts + j is token j of sequence b — activations [d, B * Ts],
+// attn_mask [max_seq, B * Ts], rope leaves [2 * d_head, B * Ts], logits [vocab, B * Ts] — and sequence b's attention section is the
+// token_len = Ts plan's op subsequence on its Ts columns over its own slab (or int8 caches): seq_len = Ts ropes, Ts-column K / V
+// stores (one kvq_store per column), seq_q = Ts attention. Ts = 1 is the program described above, op for op. The cap bounds the
+// rows of a step at 512; it is a limit, not a tuned value.
 constexpr uint32_t kMaxBatchSeqs = 32;
+constexpr uint32_t kMaxBatchTokensPerSeq = 16;
 std::unique_ptr<DecodeProgram> build_batch_decode_program(const LlamaModel& model, uint32_t n_seqs, bool fused_elementwise, bool include_dead_f32,
-                                                          std::string* err = nullptr, uint32_t kv_quant_block = 0);
+                                                          std::string* err = nullptr, uint32_t kv_quant_block = 0, uint32_t tokens_per_seq = 1);
 // what the batched builder refuses, from the config alone (no weights needed): the text, or nullptr
-const char* batch_refusal(const LlamaConfig& cfg, uint32_t n_seqs, uint32_t kv_quant_block);
-// tokens[B], pos[B]: the B embedding rows, mask columns and rope columns, and each dynamic op from its own sequence's position
+const char* batch_refusal(const LlamaConfig& cfg, uint32_t n_seqs, uint32_t kv_quant_block, uint32_t tokens_per_seq = 1);
+// tokens[B * Ts], pos[B]: the embedding rows, mask columns and rope columns of sequence b's Ts columns at positions pos[b] + j, and
+// each dynamic op from its own sequence's position (a store at pos[b], an attention's seq_kv = pos[b] + Ts)
 void patch_batch_step(const LlamaModel& model, DecodeProgram& dp, const uint32_t* tokens, const uint32_t* pos);
 
 // Patch the plan's host leaves for (token, pos): embedding row, causal mask column, RoPE row

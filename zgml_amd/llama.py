@@ -80,6 +80,11 @@ def load_host() -> C.CDLL:
         lib.zh_model_create_batch_kvq.restype = vp
         lib.zh_model_create_batch_like_kvq.argtypes = [vp, C.c_int, C.c_int, u32, u32, C.c_char_p, u64]
         lib.zh_model_create_batch_like_kvq.restype = vp
+        lib.zh_model_create_batch_ts.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.c_int, u32, u32, u32, C.c_char_p, u64]
+        lib.zh_model_create_batch_ts.restype = vp
+        lib.zh_model_create_batch_like_ts.argtypes = [vp, C.c_int, C.c_int, u32, u32, u32, C.c_char_p, u64]
+        lib.zh_model_create_batch_like_ts.restype = vp
+        lib.zh_model_tokens_per_seq.argtypes, lib.zh_model_tokens_per_seq.restype = [vp], u32
         lib.zh_model_kv_lanes.argtypes, lib.zh_model_kv_lanes.restype = [vp, C.POINTER(capi.KvLaneC), u64], u64
         lib.zh_model_n_seqs.argtypes, lib.zh_model_n_seqs.restype = [vp], u32
         lib.zh_model_patch_batch.argtypes, lib.zh_model_patch_batch.restype = [vp, vp, vp], None
@@ -198,31 +203,33 @@ class Model:
 class BatchModel(Model):
     """Synthetic weights + the BATCHED decode program (`build_batch_decode_program`): one step advances `n_seqs` independent
     sequences, each with its own KV slab, position and token. kv_quant_block=32: every sequence owns int8 KV caches instead of a
-    slab (the builder's parameter; a cfg whose own kv_quant_block != 0 stays refused). ValueError with the builder's text for
-    what it refuses."""
+    slab (the builder's parameter; a cfg whose own kv_quant_block != 0 stays refused). tokens_per_seq=Ts in 2..16: every sequence
+    owns Ts consecutive columns per step (column b * Ts + j is token j of sequence b): the plan of a batched verify step
+    (BatchSession.resident_decode_batch_speculative). ValueError with the builder's text for what it refuses."""
 
     def __init__(self, cfg: Config, n_seqs: int, weight_kind: int = Q4_0, fused_elementwise: bool = True,
-                 include_dead_f32: bool = False, threads: int = 8, like: Model = None, kv_quant_block: int = 0):
+                 include_dead_f32: bool = False, threads: int = 8, like: Model = None, kv_quant_block: int = 0, tokens_per_seq: int = 1):
         """`like`: build the batched program over that model's weights (shared, not generated again; cfg / weight_kind come from it)."""
         self.lib = load_host()
         self.cfg = like.cfg if like else cfg
-        self.n_seqs = self.token_len = n_seqs
+        self.n_seqs, self.tokens_per_seq = n_seqs, tokens_per_seq
+        self.token_len = n_seqs * tokens_per_seq
         self.kv_quant_block = kv_quant_block
         err = C.create_string_buffer(256)
         if like:
             self.build_args = like.build_args
-            self.ptr = self.lib.zh_model_create_batch_like_kvq(like.ptr, int(like.build_args[1]), int(like.build_args[2]), n_seqs, kv_quant_block,
-                                                               err, len(err))
+            self.ptr = self.lib.zh_model_create_batch_like_ts(like.ptr, int(like.build_args[1]), int(like.build_args[2]), n_seqs, kv_quant_block,
+                                                              tokens_per_seq, err, len(err))
         else:
             self.build_args = (weight_kind, fused_elementwise, include_dead_f32, threads)
-            self.ptr = self.lib.zh_model_create_batch_kvq(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32), threads,
-                                                          n_seqs, kv_quant_block, err, len(err))
+            self.ptr = self.lib.zh_model_create_batch_ts(C.byref(cfg), weight_kind, int(fused_elementwise), int(include_dead_f32), threads,
+                                                         n_seqs, kv_quant_block, tokens_per_seq, err, len(err))
         if not self.ptr:
             raise ValueError(err.value.decode())
 
     def patch_batch(self, tokens, positions) -> None:
         t, p = np.ascontiguousarray(tokens, dtype=np.uint32), np.ascontiguousarray(positions, dtype=np.uint32)
-        assert t.size == self.n_seqs and p.size == self.n_seqs
+        assert t.size == self.n_seqs * self.tokens_per_seq and p.size == self.n_seqs
         self.lib.zh_model_patch_batch(self.ptr, t.ctypes.data, p.ctypes.data)
 
     def dyn_sequences(self):
@@ -243,12 +250,14 @@ class BatchSession:
     (shared, so the model must outlive the session). On the HIP backend the program is compiled with
     ZGML_HIP_OPT_SMALL_M_MATVEC on (`small_m_matvec=False`: the tile kernels; an int: the option's value, e.g. 8 = the row kernel up
     to its widest form) and its sequences are declared; the oracle
-    takes the same program unchanged. kv_quant_block: for the batched twin the session builds itself (a BatchModel carries its own)."""
+    takes the same program unchanged. kv_quant_block, tokens_per_seq: for the batched twin the session builds itself (a BatchModel
+    carries its own)."""
 
-    def __init__(self, model: Model, fns: BackendFns, n_seqs: int, small_m_matvec=True, kv_quant_block: int = 0):
+    def __init__(self, model: Model, fns: BackendFns, n_seqs: int, small_m_matvec=True, kv_quant_block: int = 0, tokens_per_seq: int = 1):
         self.lib, self.fns, self.n_seqs = model.lib, fns, n_seqs
         self._own_model = not (isinstance(model, BatchModel) and model.n_seqs == n_seqs)
-        self.model = BatchModel(model.cfg, n_seqs, like=model, kv_quant_block=kv_quant_block) if self._own_model else model
+        self.model = BatchModel(model.cfg, n_seqs, like=model, kv_quant_block=kv_quant_block, tokens_per_seq=tokens_per_seq) if self._own_model else model
+        self.tokens_per_seq = self.model.tokens_per_seq
         self.is_hip = capi.HIP_LIB_PATH.exists() and fns.compile_program == _fn_addr(capi.load_hip(), "zgml_hip_compile_program")
         hip = capi.load_hip() if self.is_hip else None
         if self.is_hip:  # (read at compile_program; other programs of the context keep the default)
@@ -276,11 +285,13 @@ class BatchSession:
         self.lib.zh_session_set_refresh_dynamic_batch(self.ptr, _fn_addr(capi.load_hip(), "zgml_hip_refresh_dynamic_batch") if on else None)
 
     def step(self, tokens, positions):
-        """-> (next_tokens[B], logits[B, vocab])"""
-        t, p = np.ascontiguousarray(tokens, dtype=np.uint32), np.ascontiguousarray(positions, dtype=np.uint32)
-        assert t.size == self.n_seqs and p.size == self.n_seqs
-        logits = np.zeros((self.n_seqs, self.model.cfg.vocab_size), np.float32)
-        nxt = np.zeros(self.n_seqs, np.int64)
+        """-> (next_tokens[B], logits[B, vocab]); a tokens_per_seq = Ts plan takes B * Ts tokens (sequence-major) and B positions —
+        sequence b runs its Ts tokens at positions[b] .. positions[b] + Ts - 1 — and returns B * Ts rows"""
+        t, p = np.ascontiguousarray(tokens, dtype=np.uint32).ravel(), np.ascontiguousarray(positions, dtype=np.uint32)
+        rows = self.n_seqs * self.tokens_per_seq
+        assert t.size == rows and p.size == self.n_seqs
+        logits = np.zeros((rows, self.model.cfg.vocab_size), np.float32)
+        nxt = np.zeros(rows, np.int64)
         if self.lib.zh_session_step_batch(self.ptr, t.ctypes.data, p.ctypes.data, logits.ctypes.data, nxt.ctypes.data) != 0:
             raise ValueError("step: token or position out of range")
         return nxt, logits
@@ -330,6 +341,33 @@ class BatchSession:
         if rc != 0:
             raise RuntimeError("resident_decode_batch: " + self._backend.last_error())
         return toks[:, :max_steps]
+
+    def resident_decode_batch_speculative(self, first_tokens, start_pos, n_tokens, histories=None, drafts=None, ngram: int = 2):
+        """Greedy-exact speculative decode of every sequence on a tokens_per_seq >= 2 plan (include/zgml_hip.h:
+        zgml_hip_resident_decode_batch_speculative) -> (tokens[B, max(n_tokens)], [{"steps", "drafted", "accepted"}] per sequence);
+        row b holds n_tokens[b] tokens, then -1. histories / drafts: None, or one entry per sequence as `history` / `drafts` of
+        Session.resident_decode_speculative (an entry None: no history / the n-gram lookup)."""
+        u32p = C.POINTER(C.c_uint32)
+        B = self.n_seqs
+        t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_tokens, dtype=np.uint32), (B,)))
+        assert t.size == B and p.size == B
+        histories = [None] * B if histories is None else list(histories)
+        drafts = [None] * B if drafts is None else list(drafts)
+        assert len(histories) == B and len(drafts) == B
+        opts, keep = (capi.SpecDecodeC * B)(), []
+        for b in range(B):
+            opts[b], arrays = Session._spec_opt(histories[b], drafts[b], ngram)
+            keep.append(arrays)
+        max_tokens = int(n.max()) if n.size else 0
+        toks = np.full((B, max(1, max_tokens)), -1, np.int64)
+        stats = (capi.SpecStatsC * B)()
+        rc = capi.load_hip().zgml_hip_resident_decode_batch_speculative(self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p),
+                                                                        n.ctypes.data_as(u32p), max_tokens, opts, toks.ctypes.data, stats)
+        del keep
+        if rc != 0:
+            raise RuntimeError("resident_decode_batch_speculative: " + self._backend.last_error())
+        return toks[:, :max_tokens], [{"steps": st.steps, "drafted": st.drafted, "accepted": st.accepted} for st in stats]
 
     def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None, top_logprobs=None):
         """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
