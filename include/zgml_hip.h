@@ -820,8 +820,8 @@ int zgml_hip_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_
  * NULL pointers, and top_n outside 1 .. 64 (a new argument: refused, not clamped). */
 int zgml_hip_top_logprobs(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint16_t buf_idx, uint64_t offset, uint64_t n, uint32_t rows,
                           uint32_t top_n, int64_t* tokens_out /* [rows][top_n] */, float* logprobs_out /* [rows][top_n] */);
-/* zgml_hip_resident_decode with the sampled tail: per token [prep] [plan] [select] [merge + pick + advance], the launch count of
- * the greedy loop, one graph launch per token. The parameters live in a device table uploaded per call, so one captured graph —
+/* zgml_hip_resident_decode with the sampled tail: per token [prep] [plan] [select] [merge + pick + advance], three launches
+ * beside the plan's, one graph launch per token. The parameters live in a device table uploaded per call, so one captured graph —
  * a separate one from the greedy loop's: alternating calls on one program invalidate nothing — serves every parameter set.
  * A sequence that emits one of its stop tokens records it and then freezes as a batched sequence that has used up its count
  * does (same token, same position: the remaining steps rewrite the KV column behind the stop token with the same values); the

@@ -1,7 +1,9 @@
 // greedy_tail.hip — the greedy token tail of the device-resident loops (runtime_resident.hip) and the stand-alone argmax op: the
 // prep launches that produce a step's patches on the device (single, batched, batched verify step), and the argmax family — first index of the maximum — in its three
 // shapes, all written over tail_device.h's bodies (a thread's scan, the block reductions, the advances):
-//   launch_argmax               [stage 1: a pair per workgroup] [stage 2: the pairs' fold + the single loop's advance]
+//   launch_argmax               [stage 1: a pair per workgroup] [stage 2: the pairs' fold + the single loop's advance and the
+//                               token's embedding row]; stage 1 may carry the position part of the next step's prep
+//   launch_argmax_fold          its stage 2 alone (the pairs came from the streaming LM head: kernels_generic.hip)
 //   launch_argmax_batch         the same two stages over B rows (blockIdx.y = sequence), the batched loop's advance;
 //   launch_argmax_rows_stage1   its stage 1 alone (a greedy verify step: spec_accept_kernel folds the pairs)
 // Every workgroup has 256 threads and the same two LDS arrays; a row takes n / 1024 + 1 workgroups, at most 256.
@@ -14,30 +16,13 @@ namespace {
 
 constexpr int kBlock = kArgBlock, kArgBlocks = 256;
 
-// one element of the flat prep index space (kernels.h: ResidentPrepArgs) at position `pos` with the chunk's tokens
+// one element of the flat prep index space (kernels.h: ResidentPrepArgs) at position `pos` with the chunk's tokens: the token
+// part, then the position part (tail_device.h)
 __device__ __forceinline__ void resident_prep_element(const ResidentPrepArgs& a, uint32_t i, uint32_t pos) {
-    if (i < a.T * a.d) {
-        const uint32_t j = i / a.d, e = i - j * a.d;
-        a.tok_in[i] = a.embed[(uint64_t)a.tokens[j] * a.d + e];
-        return;
-    }
-    i -= a.T * a.d;
-    if (i < a.T * a.max_seq) {
-        const uint32_t j = i / a.max_seq, sidx = i - j * a.max_seq;
-        a.mask[i] = sidx <= pos + j ? 0.0f : -INFINITY;
-        return;
-    }
-    i -= a.T * a.max_seq;
-    if (i < a.n_rope * a.T * 2 * a.dh) {
-        const uint32_t l = i / (a.T * 2 * a.dh), rem = i - l * (a.T * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
-        a.rope_bufs[l][rem] = e < a.dh ? a.cos[(uint64_t)(pos + j) * a.dh + e] : a.sin[(uint64_t)(pos + j) * a.dh + e - a.dh];
-        return;
-    }
-    i -= a.n_rope * a.T * 2 * a.dh;
-    if (i < a.n_ops) {
-        if (a.dyn_kind[i] == 1) a.dyn[i] = a.dyn_base[i] + pos * a.dyn_stride[i];
-        if (a.dyn_kind[i] == 2) a.dyn[i] = pos + a.T;
-    }
+    if (i < a.T * a.d)
+        resident_prep_token(a, i);
+    else
+        resident_prep_position(a, i - a.T * a.d, pos);
 }
 __global__ void __launch_bounds__(256) resident_prep_kernel(ResidentPrepArgs a) {
     resident_prep_element(a, blockIdx.x * 256 + threadIdx.x, a.state[1]);
@@ -86,23 +71,40 @@ __global__ void __launch_bounds__(256) resident_batch_spec_prep_kernel(ResidentB
                                 [&](uint32_t b) { return a.words[b * kSpecWords + kSpecRunPos]; });
 }
 
-// stage 1 of row `row` (row stride n): this workgroup's pair to slot row * gridDim.x + blockIdx.x
-__device__ __forceinline__ void argmax_stage1_body(float* sv, int64_t* si, uint32_t row, const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx) {
+// stage 1 of row `row` (row stride n), shared by `nblk` workgroups: this workgroup's pair to slot row * nblk + blockIdx.x
+__device__ __forceinline__ void argmax_stage1_body(float* sv, int64_t* si, uint32_t row, const float* __restrict__ v, uint64_t n, uint32_t nblk, float* out_val, int64_t* out_idx) {
     float bv;
     int64_t bi;
-    arg_scan(v + (uint64_t)row * n, n, bv, bi);
+    arg_scan(v + (uint64_t)row * n, n, nblk, bv, bi);
     arg_block_reduce<false>(sv, si, bv, bi);
     if (threadIdx.x == 0) {
-        out_val[row * gridDim.x + blockIdx.x] = sv[0];
-        out_idx[row * gridDim.x + blockIdx.x] = si[0];
+        out_val[row * nblk + blockIdx.x] = sv[0];
+        out_idx[row * nblk + blockIdx.x] = si[0];
     }
 }
-// stage 2 of row `row`: the fold of its nblk pairs, some of them empty; the token in thread 0 (-1: no pair at all)
+// stage 2 of row `row`: the fold of its nblk pairs, some of them empty; the token in every thread (-1: no pair at all).
+// kWide (the pairs of the streaming LM head, at most kArgPairs of them): every thread reads its kWidePairs pairs in ONE memory
+// round trip — clamped loads, a dead one made empty by a select — not one dependent trip per 256 pairs
+constexpr int kWidePairs = (int)kArgPairs / kBlock;
+template <bool kWide = false>
 __device__ __forceinline__ int64_t argmax_stage2_body(float* sv, int64_t* si, uint32_t row, const float* vals, const int64_t* idxs, int nblk) {
     vals += (uint64_t)row * nblk, idxs += (uint64_t)row * nblk;
     float bv = -INFINITY;
     int64_t bi = INT64_MAX;
-    for (int i = threadIdx.x; i < nblk; i += kBlock) arg_fold(bv, bi, vals[i], idxs[i]);
+    if (kWide) {
+        float v[kWidePairs];
+        int64_t ix[kWidePairs];
+#pragma unroll
+        for (int u = 0; u < kWidePairs; u++) {
+            const int i = threadIdx.x + u * kBlock, at = i < nblk ? i : 0;
+            v[u] = vals[at];
+            ix[u] = i < nblk ? idxs[at] : INT64_MAX;
+        }
+#pragma unroll
+        for (int u = 0; u < kWidePairs; u++) arg_fold(bv, bi, v[u], ix[u]);
+    } else {
+        for (int i = threadIdx.x; i < nblk; i += kBlock) arg_fold(bv, bi, vals[i], idxs[i]);
+    }
     arg_block_reduce<true>(sv, si, bv, bi);
     return si[0] == INT64_MAX ? -1 : si[0];
 }
@@ -110,13 +112,30 @@ __device__ __forceinline__ int64_t argmax_stage2_body(float* sv, int64_t* si, ui
 __global__ void __launch_bounds__(kBlock) argmax_stage1(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx) {
     __shared__ float sv[kBlock];
     __shared__ int64_t si[kBlock];
-    argmax_stage1_body(sv, si, 0, v, n, out_val, out_idx);
+    argmax_stage1_body(sv, si, 0, v, n, gridDim.x, out_val, out_idx);
 }
 
+// ... with the position part of the next step's prep in the workgroups behind the row's `nblk` (the resident greedy loop over a
+// head that is not the streaming dense form)
+__global__ void __launch_bounds__(kBlock) argmax_stage1_ahead(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx, uint32_t nblk, ResidentAhead ahead) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    if (blockIdx.x >= nblk) {
+        resident_prep_ahead(ahead, (blockIdx.x - nblk) * kBlock + threadIdx.x);
+        return;
+    }
+    argmax_stage1_body(sv, si, 0, v, n, nblk, out_val, out_idx);
+}
+
+// kWide: the fold launch behind the streaming head (launch_argmax_fold); the stand-alone op and the two-stage tail keep the plain walk
+template <bool kWide>
 __global__ void __launch_bounds__(kBlock) argmax_stage2(const float* vals, const int64_t* idxs, int nblk, int64_t* out, ArgmaxAdvance adv) {
     __shared__ float sv[kBlock];
     __shared__ int64_t si[kBlock];
-    const int64_t next = argmax_stage2_body(sv, si, 0, vals, idxs, nblk);
+    const int64_t next = argmax_stage2_body<kWide>(sv, si, 0, vals, idxs, nblk);
+    // the token part of the next step's prep: its embedding row, by all threads
+    if (adv.embed && next >= 0)
+        for (uint32_t e = threadIdx.x; e < adv.d; e += kBlock) adv.tok_in[e] = adv.embed[(uint64_t)next * adv.d + e];
     if (threadIdx.x != 0) return;
     *out = next;
     if (adv.state) tail_advance_single(adv.state, adv.tokens, adv.cap, next); // the resident loop's advance step
@@ -126,7 +145,7 @@ __global__ void __launch_bounds__(kBlock) argmax_stage2(const float* vals, const
 __global__ void __launch_bounds__(kBlock) argmax_batch_stage1(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx) {
     __shared__ float sv[kBlock];
     __shared__ int64_t si[kBlock];
-    argmax_stage1_body(sv, si, blockIdx.y, v, n, out_val, out_idx);
+    argmax_stage1_body(sv, si, blockIdx.y, v, n, gridDim.x, out_val, out_idx);
 }
 
 __global__ void __launch_bounds__(kBlock) argmax_batch_stage2(const float* vals, const int64_t* idxs, int nblk, uint32_t* state, int64_t* tokens) {
@@ -167,10 +186,18 @@ void launch_argmax_rows_stage1(hipStream_t s, const float* v, uint64_t n, uint32
     argmax_batch_stage1<<<dim3(argmax_batch_blocks(n), rows), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
 }
 
-void launch_argmax(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, int64_t* out, const ArgmaxAdvance& adv) {
+void launch_argmax(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, int64_t* out, const ArgmaxAdvance& adv,
+                   const ResidentAhead* ahead) {
     const int nblk = argmax_batch_blocks(n);
-    argmax_stage1<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
-    argmax_stage2<<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, out, adv);
+    if (ahead && ahead->total)
+        argmax_stage1_ahead<<<nblk + (ahead->total + kBlock - 1) / kBlock, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx, (uint32_t)nblk, *ahead);
+    else
+        argmax_stage1<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
+    argmax_stage2<false><<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, out, adv);
+}
+
+void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* scratch_idx, uint32_t nblk, int64_t* out, const ArgmaxAdvance& adv) {
+    argmax_stage2<true><<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, (int)nblk, out, adv); // (nblk <= kArgPairs: the head's workgroups)
 }
 
 } // namespace zgml

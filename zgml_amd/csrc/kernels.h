@@ -381,16 +381,29 @@ AttnRoute attention_route(bool all_dense, uint32_t rows_d_head, uint32_t max_seq
 const char* attention_route_tag(AttnRoute r); // "attention-generic" | "attention-dense" | "attention-rows" | "attention-tiles"
 void launch_attention_batch(hipStream_t s, const AttentionParams* dev_params, uint32_t n_ops, uint32_t max_seq_q, bool all_dense,
                             uint32_t rows_d_head = 0, const float* zero_word = nullptr, const AttnPieceSink& sink = AttnPieceSink{}); // rows_d_head: the common d_head when every op is dense (else 0)
-void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p);
+// `tail` (the resident greedy loop alone; null for every other caller): what the M = 1, K-contiguous f32 streaming form may carry
+// beside its rows when it produces the WHOLE logits row — dst == tail->logits and N == tail->vocab — (DenseHeadTail, below);
+// tail->pairs says whether it did
+struct DenseHeadTail;
+void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p, DenseHeadTail* tail = nullptr);
 // `adv` (device-resident decode): the final stage also appends the token — state[0] = token, state[1] += 1 (position),
-// tokens[state[2]++] = token — instead of a one-thread launch of its own behind it
+// tokens[state[2]++] = token — instead of a one-thread launch of its own behind it; with `embed`, its 256 threads also copy
+// the token's embedding row (d values) into tok_in, the token part of the next step's prep
 struct ArgmaxAdvance {
     uint32_t* state = nullptr;
     int64_t* tokens = nullptr;
     uint32_t cap = 0;
+    const float* embed = nullptr;
+    float* tok_in = nullptr;
+    uint32_t d = 0;
 };
+struct ResidentAhead;
+// `ahead`: stage 1 also writes the position part of the NEXT step's prep (ResidentAhead, below), in workgroups of its own
 void launch_argmax(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, int64_t* out,
-                   const ArgmaxAdvance& adv = ArgmaxAdvance{});
+                   const ArgmaxAdvance& adv = ArgmaxAdvance{}, const ResidentAhead* ahead = nullptr);
+// stage 2 alone, over nblk pairs another launch left in the scratch (at most kArgPairs; an empty pair's index is INT64_MAX)
+constexpr uint32_t kArgPairs = 1024; // pairs of the context's argmax scratch
+void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* scratch_idx, uint32_t nblk, int64_t* out, const ArgmaxAdvance& adv);
 // Everything LlamaInferencePlan.execute patches on the host per execution (src/llama_inference.zig:405-446; for T > 1
 // patch_tokens of zgml_amd/host/llama_decode.cpp), produced on the device as one flat index space: T embedding rows, T
 // causal-mask columns, T RoPE rows per layer leaf, the dynamic words (KV store offsets at `pos`, seq_kv = pos + T).
@@ -405,6 +418,26 @@ struct ResidentPrepArgs {
     uint32_t d, max_seq, dh, n_rope, n_ops, T;
 };
 void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t total); // total = T d + T max_seq + n_rope T 2 dh + n_ops
+// The position part of that index space (all but the T d embedding elements: it depends on the position alone) written a token
+// AHEAD, for position state[1] + 1, by a launch of the running step that nothing reading those buffers follows: `total` =
+// T max_seq + n_rope T 2 dh + n_ops elements (0: none), 256 to a workgroup. Past the last position nothing is written.
+struct ResidentAhead {
+    ResidentPrepArgs a;
+    uint32_t total = 0;
+};
+// What the resident greedy loop hands through run_plan to the plan's LAST launch (nothing behind it may touch the logits or read
+// the prep's buffers), which takes it up if it is the dense matmul that writes all `vocab` logits (launch_dense_matmul). In:
+// where the workgroups' (value, first index) pairs go, and the prep to write ahead. Out: `pairs`, the pairs written — 0 when
+// the launch did not take it up (the head is another kernel, a part of the row, or not the last launch), and the loop keeps
+// its stage 1.
+struct DenseHeadTail {
+    const float* logits = nullptr;
+    uint32_t vocab = 0;
+    float* pair_val = nullptr;
+    int64_t* pair_idx = nullptr;
+    ResidentAhead ahead;
+    uint32_t pairs = 0;
+};
 // ── batched decode (B independent sequences per step): the resident loop's token tail ──
 // Per-sequence state on the device, four words per sequence: state[b] = token, state[B + b] = position, state[2 B + b] = steps
 // left, state[3 B + b] = tokens produced; state[4 B] = the row length of `tokens` in the pick below.

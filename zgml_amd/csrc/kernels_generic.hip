@@ -1,7 +1,8 @@
 // kernels_generic.hip — gfx950 kernels for the DeviceOp kinds that are not the quantized
 // mat-vec: elementwise / fused chains / row-wise norms / reduce / repeat / slice_assign / rope /
 // attention / dense matmul / copy. One launch per op; fused variants live in fused.hip; the greedy
-// pick and the resident loops' prep launches are greedy_tail.hip's.
+// pick and the resident loops' prep launches are greedy_tail.hip's — but for what the streaming
+// LM head (dense_kcontig_stream_kernel) carries of them in the resident greedy loop.
 //
 // Semantics follow the reference executor src/backend/reference.zig (cited per kernel). These ops
 // are tiny at decode (d_model..d_ff elements): they are latency-bound, so the kernels favour
@@ -13,6 +14,7 @@
 #include <math.h>
 
 #include "attention_decode.h"
+#include "tail_device.h"
 
 namespace zgml {
 
@@ -1066,6 +1068,79 @@ __global__ void __launch_bounds__(kBlock) dense_kcontig_kernel(DenseMatmulParams
     if (lane == 0) p.dst[(uint64_t)m * p.dst_rs + n] = acc;
 }
 
+// The streaming form of dense_kcontig_kernel<float, 4> at M = 1 and K <= kStreamMaxK (the tied LM head). The arithmetic of a row is
+// that kernel's to the bit: lane l accumulates k = 4 l .. 4 l + 3, then + 256, ... with the same fmaf chain, and wave_sum folds the
+// row. What differs is the schedule: a wave owns R rows with independent accumulators, the k loop is unrolled to KI = ceil(K / 256)
+// iterations whose addresses are clamped instead of guarded (a dead lane reads k = 0 of its row, a dead row reads row N - 1), so
+// all R * KI loads of a wave are in flight before its first wait, and x stays in registers across the wave's rows. A dead lane or
+// row keeps its accumulator by a select — never a product with 0: a clamped load may return Inf. Workgroup w takes the blocks
+// of kStreamWgRows rows w, w + head_wgs, ...
+// `pair_val` (the resident greedy loop): the workgroup also folds the rows it produced into one (value, first index) pair, slot
+// blockIdx.x (empty — index INT64_MAX — if it produced none); `ahead`: the workgroups behind the head_wgs of the rows write the
+// position part of the next step's prep (tail_device.h).
+// kStreamRows: rows per wave; kStreamMaxWgs: workgroups of the rows, four per CU — more row blocks than that are strided over, and
+// each workgroup leaves one pair (profiles/r18_token_tail.txt: the sweep over 1-8 rows and 512-4096 workgroups)
+constexpr uint32_t kStreamRows = 2, kStreamWgRows = kStreamRows * (kBlock / 64), kStreamMaxK = 1024, kStreamMaxWgs = 1024;
+static_assert(kStreamMaxWgs <= kArgPairs, "one pair per workgroup of the streaming head must fit the argmax scratch");
+
+template <int R, int KI>
+__global__ void __launch_bounds__(kBlock) dense_kcontig_stream_kernel(DenseMatmulParams p, uint32_t head_wgs, float* pair_val, int64_t* pair_idx, ResidentAhead ahead) {
+    if (blockIdx.x >= head_wgs) {
+        resident_prep_ahead(ahead, (blockIdx.x - head_wgs) * kBlock + threadIdx.x);
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* const b = (const float*)p.b;
+    uint32_t kc[KI];
+    bool live[KI];
+    float4 xv[KI];
+#pragma unroll
+    for (int it = 0; it < KI; it++) {
+        const uint32_t k = lane * 4 + 256 * it;
+        live[it] = k < p.K;
+        kc[it] = live[it] ? k : 0;
+        xv[it] = *(const float4*)(p.a + kc[it]);
+    }
+    float bv = -INFINITY;
+    int64_t bi = INT64_MAX;
+    for (uint64_t row0 = (uint64_t)blockIdx.x * (R * (kBlock / 64)) + wave * R; row0 < p.N; row0 += (uint64_t)head_wgs * (R * (kBlock / 64))) {
+        float4 w[R][KI];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint64_t n = row0 + r < p.N ? row0 + r : p.N - 1;
+#pragma unroll
+            for (int it = 0; it < KI; it++) w[r][it] = *(const float4*)(b + (uint64_t)n * p.b_cs + kc[it]);
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            float acc = 0.f;
+#pragma unroll
+            for (int it = 0; it < KI; it++) {
+                float t = fmaf(xv[it].x, w[r][it].x, acc);
+                t = fmaf(xv[it].y, w[r][it].y, t);
+                t = fmaf(xv[it].z, w[r][it].z, t);
+                t = fmaf(xv[it].w, w[r][it].w, t);
+                acc = live[it] ? t : acc;
+            }
+            acc = wave_sum(acc);
+            if (row0 + r < p.N) { // (wave-uniform)
+                if (lane == 0) p.dst[row0 + r] = acc;
+                arg_fold(bv, bi, acc, (int64_t)(row0 + r));
+            }
+        }
+    }
+    if (!pair_val) return; // (a kernel argument: uniform)
+    __shared__ float sv[kBlock / 64];
+    __shared__ int64_t si[kBlock / 64];
+    if (lane == 0) sv[wave] = bv, si[wave] = bi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w2 = 1; w2 < kBlock / 64; w2++) arg_fold(bv, bi, sv[w2], si[w2]);
+        pair_val[blockIdx.x] = bv, pair_idx[blockIdx.x] = bi;
+    }
+}
+
 template <typename BT>
 __global__ void __launch_bounds__(kBlock) dense_strided_kernel(DenseMatmulParams p) {
     uint32_t n = blockIdx.x * kBlock + threadIdx.x, m = blockIdx.y;
@@ -1370,8 +1445,26 @@ const char* attention_route_tag(AttnRoute r) {
     return "attention";
 }
 
-void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p) {
+// the streaming form (dense_kcontig_stream_kernel): the caller has checked M == 1, f32 B, K <= kStreamMaxK and `vec`
+static void launch_dense_kcontig_stream(hipStream_t s, const DenseMatmulParams& p, DenseHeadTail* tail) {
+    constexpr int R = (int)kStreamRows;
+    const uint32_t blocks = cdiv(p.N, kStreamWgRows), head_wgs = blocks < kStreamMaxWgs ? blocks : kStreamMaxWgs;
+    const ResidentAhead ahead = tail ? tail->ahead : ResidentAhead{};
+    float* const pv = tail ? tail->pair_val : nullptr;
+    int64_t* const pi = tail ? tail->pair_idx : nullptr;
+    const dim3 grid(head_wgs + cdiv(ahead.total, kBlock));
+    switch (cdiv(p.K, 256)) {
+        case 1: dense_kcontig_stream_kernel<R, 1><<<grid, kBlock, 0, s>>>(p, head_wgs, pv, pi, ahead); break;
+        case 2: dense_kcontig_stream_kernel<R, 2><<<grid, kBlock, 0, s>>>(p, head_wgs, pv, pi, ahead); break;
+        case 3: dense_kcontig_stream_kernel<R, 3><<<grid, kBlock, 0, s>>>(p, head_wgs, pv, pi, ahead); break;
+        default: dense_kcontig_stream_kernel<R, 4><<<grid, kBlock, 0, s>>>(p, head_wgs, pv, pi, ahead); break;
+    }
+    if (pv) tail->pairs = head_wgs;
+}
+
+void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p, DenseHeadTail* tail) {
     if (p.M == 0 || p.N == 0) return;
+    if (tail && (tail->logits != p.dst || tail->vocab != p.N)) tail = nullptr; // the rider is for the launch that produces the whole logits row alone
     const bool f16 = p.b_f16 != 0;
     if (p.b_cs == 1 && p.b_rs != 1) {
         dim3 grid(cdiv(p.N, kBlock), p.M);
@@ -1390,7 +1483,9 @@ void launch_dense_matmul(hipStream_t s, const DenseMatmulParams& p) {
             else
                 dense_kcontig_kernel<__half, 1><<<grid, kBlock, 0, s>>>(p);
         } else {
-            if (vec)
+            if (vec && p.M == 1 && p.K <= kStreamMaxK)
+                launch_dense_kcontig_stream(s, p, tail);
+            else if (vec)
                 dense_kcontig_kernel<float, 4><<<grid, kBlock, 0, s>>>(p);
             else
                 dense_kcontig_kernel<float, 1><<<grid, kBlock, 0, s>>>(p);

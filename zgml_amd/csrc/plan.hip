@@ -202,6 +202,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                 return true;
             }
             L.run = [=](hipStream_t s) { launch_dense_matmul(s, dp); };
+            L.run_tail = [=](hipStream_t s, DenseHeadTail* tail) { launch_dense_matmul(s, dp, tail); };
             return true;
         }
         case ZGML_DOP_QMATMUL: {

@@ -425,7 +425,9 @@ bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std:
     return true;
 }
 
-void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count) {
+void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count, DenseHeadTail* tail) {
+    // (the rider goes to the plan's last launch alone: nothing behind it rewrites the logits or reads what it prepares ahead)
+    const auto run = [&](Launch& L) { tail && L.run_tail && &L == &p->plan.back() ? L.run_tail(s, tail) : L.run(s); };
 #ifdef ZGML_TRACE
     // diagnostics build only: ZGML_HIP_SKIP_KINDS=<bitmask of DeviceOp tags> drops those launches (timing ablation
     // only; results are garbage)
@@ -439,10 +441,10 @@ void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count) {
     for (size_t i = first; i < first + count && i < p->plan.size(); i++) {
         if (sw().hip_skip_kinds & (1u << p->plan[i].kind)) continue;
         if (mod_period && i >= 1 && (mod_mask & (1u << ((i - 1) % mod_period)))) continue;
-        p->plan[i].run(s);
+        run(p->plan[i]);
     }
 #else
-    for (size_t i = first; i < first + count && i < p->plan.size(); i++) p->plan[i].run(s);
+    for (size_t i = first; i < first + count && i < p->plan.size(); i++) run(p->plan[i]);
 #endif
 }
 
@@ -599,8 +601,8 @@ zgml_hip_ctx* zgml_hip_create(int device_ordinal) {
         delete ctx;
         return nullptr;
     }
-    hipMalloc((void**)&ctx->arg_val, 256 * sizeof(float));
-    hipMalloc((void**)&ctx->arg_idx, 256 * sizeof(int64_t));
+    hipMalloc((void**)&ctx->arg_val, kArgPairs * sizeof(float));
+    hipMalloc((void**)&ctx->arg_idx, kArgPairs * sizeof(int64_t));
     hipMalloc((void**)&ctx->arg_out, sizeof(int64_t));
     hipHostMalloc((void**)&ctx->arg_out_host, sizeof(int64_t), hipHostMallocDefault);
     ctx->n_cu = prop.multiProcessorCount;

@@ -60,6 +60,9 @@ struct Launch {
     const char* tag = nullptr; // plan text: what a fused launch is
     uint64_t prof_ns = 0;    // ZGML_HIP_OPT_PROFILE: accumulated event time of this launch
     uint32_t prof_calls = 0;
+    // a one-op dense matmul launch: `run` with the resident greedy loop's rider (kernels.h: DenseHeadTail), which run_plan hands
+    // to it at run time when it is the plan's last launch — the plan keeps nothing of it
+    std::function<void(hipStream_t, DenseHeadTail*)> run_tail;
 };
 
 struct IoEntry {
@@ -333,7 +336,8 @@ void ensure_plan(zgml_hip_program* p);      // build_plan (after free_graph) whe
 bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, hipGraph_t* g_out, hipGraphExec_t* e_out);
 void set_dyn_from_ops(zgml_hip_program* p); // ops' dynamic words -> p->dyn_host (sets dyn_dirty on a change)
 void flush_dyn(zgml_hip_program* p);        // p->dyn_host -> p->dyn_dev on the context stream when dirty
-void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count); // launches [first, first + count) of the plan, eagerly
+// launches [first, first + count) of the plan, eagerly; `tail`: the resident greedy loop's rider, handed to the plan's last launch alone
+void run_plan(zgml_hip_program* p, hipStream_t s, size_t first, size_t count, DenseHeadTail* tail = nullptr);
 void enqueue(zgml_hip_program* p);          // the whole program on the context stream (plan ensured, dyn flushed, graph replay when enabled)
 void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx); // a buffer written from outside the op list leaves the hoisted set
 // kv_move.hip

@@ -36,6 +36,7 @@ struct zgml_resident {
     int64_t* tokens = nullptr;     // produced tokens (device), grown by ensure_tokens: the graphs bake pointer and capacity
     uint32_t tokens_cap = 0;
     uint32_t prep_total = 0;       // the prep launches' flat index space (prep_total(): fixed by the set-up, which checks that it fits)
+    uint32_t tail_launches = 0;    // launches behind the plan in a step of the single-sequence greedy loop, as its step last ran (or was captured)
     hipGraph_t graph = nullptr;    // the greedy loop's step: single-sequence, batched or verify, whichever the plan is
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph_multi = nullptr; // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
@@ -698,18 +699,34 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     });
     if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_steps)) return -1;
     const Prep prep = prep_args(p, r->state, r->state /* the token is state[0] */);
-    // [prep] [plan] [argmax stage 1] [stage 2 + advance]. (A token tail in ONE launch — the argmax, the advance of the device state
-    // and the next token's patches, two launches fewer per token — was measured and removed. First form — the last arriver walks
-    // all 8-16 K elements of the next token's patches alone — SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against
-    // 817. Second form — every workgroup writes the position-only patches, the last arriver the embedding row — a wash: 1777-1782
-    // against 1768-1780, 838 against 842; profiles/r05_token_tail_ab.txt)
+    // Per token [plan] [stage 2 + advance + embedding row], one full prep in front of the call's first step. A step's patches
+    // come from the step before it, through ordinary kernel boundaries: the launch that leaves the argmax pairs also writes the
+    // position part of the next step's prep (it depends on the position alone, and nothing behind that launch reads those
+    // buffers), and stage 2, which knows the token, copies its embedding row. The launch with the pairs is the tied LM head in
+    // its streaming form, armed through run_plan with a block that exists for this call only (kernels.h: DenseHeadTail); where
+    // the head is another kernel (a Q4_0 head) nothing takes the block up and the step is [plan] [stage 1 + position part]
+    // [stage 2 + ...]. profiles/r18_token_tail.txt has the measurements.
+    // (A token tail in ONE launch — the argmax, the advance of the device state and the next token's patches behind a
+    // last-arriver count — was measured and removed. First form — the last arriver walks all 8-16 K elements of the next
+    // token's patches alone — SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every
+    // workgroup writes the position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838
+    // against 842; profiles/r05_token_tail_ab.txt. The present form adds no synchronisation inside a launch.)
+    const ArgmaxAdvance adv{r->state, r->tokens, r->tokens_cap, r->embed, r->tok_in, r->d};
+    DenseHeadTail head;
+    head.logits = r->logits, head.vocab = r->vocab, head.pair_val = ctx->arg_val, head.pair_idx = ctx->arg_idx;
+    head.ahead = ResidentAhead{prep.a, prep.total - r->token_len * r->d};
     auto one_token = [&](hipStream_t st) {
-        launch_resident_prep(st, prep.a, prep.total);
-        run_plan(p, st, 0, p->plan.size());
-        launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, ArgmaxAdvance{r->state, r->tokens, r->tokens_cap});
+        head.pairs = 0;
+        run_plan(p, st, 0, p->plan.size(), &head);
+        if (head.pairs)
+            launch_argmax_fold(st, ctx->arg_val, ctx->arg_idx, head.pairs, ctx->arg_out, adv);
+        else
+            launch_argmax(st, r->logits, r->vocab, ctx->arg_val, ctx->arg_idx, ctx->arg_out, adv, &head.ahead);
+        r->tail_launches = head.pairs ? 1 : 2;
     };
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // (a stack array: no wait before the capture, unlike the batched loop's vector)
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return -1;
+    if (n_steps) launch_resident_prep(s, prep.a, prep.total); // the first step's patches, for (first_token, start_pos)
     capture_once(ctx, s, "resident", false, one_token, &r->graph, &r->graph_exec);
     // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
     // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
@@ -735,7 +752,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     ok = ok && ctx->handoff_ok("resident_decode");
-    resident_end(p, n_steps, p->plan.size() + 3); // per token [prep] [plan] [argmax x 2]
+    resident_end(p, n_steps, p->plan.size() + r->tail_launches); // per token [plan] [stage 2], or [plan] [argmax x 2]
     return ok ? 0 : -1;
 }
 

@@ -1,6 +1,7 @@
 // tail_device.h — the device bodies the token tail's kernels share (greedy_tail.hip, sample.hip, logprob.hip, top_logprob.hip,
-// spec_decode.hip), each stated once. Included by .hip files only: threadIdx, barriers and wave shuffles live here, never in
-// sample.h / sample_params.h, the rule headers the CPU tests compile.
+// spec_decode.hip, and kernels_generic.hip's streaming LM head), each stated once. Included by .hip files only: threadIdx,
+// barriers and wave shuffles live here, never in sample.h / sample_params.h, the rule headers the CPU tests compile.
+//   the single-sequence prep     its token part and its position part, and the position part a token ahead
 //   the bitonic stage            sample.hip's select and merge sorts, top_logprob.hip's merge of the lists' heads
 //   the argmax pieces            first maximum wins: a thread's scan, the block reductions, the empty-aware fold, its wave form
 //   the advances                 of the single loop's and of the batched loop's device state, behind a greedy or a sampled pick
@@ -25,6 +26,40 @@ __device__ __forceinline__ void bitonic_stage(uint64_t* s, uint32_t pairs, uint3
     __syncthreads();
 }
 
+// ── the single-sequence prep (kernels.h: ResidentPrepArgs), in its two parts ──
+// the token part: element i < T d of the T embedding rows
+__device__ __forceinline__ void resident_prep_token(const ResidentPrepArgs& a, uint32_t i) {
+    const uint32_t j = i / a.d, e = i - j * a.d;
+    a.tok_in[i] = a.embed[(uint64_t)a.tokens[j] * a.d + e];
+}
+// the position part: element i of its index space (kernels.h: ResidentAhead) — the T mask columns, the T RoPE rows per layer leaf and the dynamic
+// words at position `pos`; it reads no token, so a launch of the token BEFORE may write it (kernels.h: ResidentAhead)
+__device__ __forceinline__ void resident_prep_position(const ResidentPrepArgs& a, uint32_t i, uint32_t pos) {
+    if (i < a.T * a.max_seq) {
+        const uint32_t j = i / a.max_seq, sidx = i - j * a.max_seq;
+        a.mask[i] = sidx <= pos + j ? 0.0f : -INFINITY;
+        return;
+    }
+    i -= a.T * a.max_seq;
+    if (i < a.n_rope * a.T * 2 * a.dh) {
+        const uint32_t l = i / (a.T * 2 * a.dh), rem = i - l * (a.T * 2 * a.dh), j = rem / (2 * a.dh), e = rem - j * 2 * a.dh;
+        a.rope_bufs[l][rem] = e < a.dh ? a.cos[(uint64_t)(pos + j) * a.dh + e] : a.sin[(uint64_t)(pos + j) * a.dh + e - a.dh];
+        return;
+    }
+    i -= a.n_rope * a.T * 2 * a.dh;
+    if (i < a.n_ops) {
+        if (a.dyn_kind[i] == 1) a.dyn[i] = a.dyn_base[i] + pos * a.dyn_stride[i];
+        if (a.dyn_kind[i] == 2) a.dyn[i] = pos + a.T;
+    }
+}
+// ... a token ahead: element i of `total`, for the position behind the one the running step is at. Past the last position there
+// is nothing to prepare (a call's last step may stand there): nothing is written, so no index leaves the mask or the tables
+__device__ __forceinline__ void resident_prep_ahead(const ResidentAhead& h, uint32_t i) {
+    if (i >= h.total) return;
+    const uint32_t pos = h.a.state[1] + 1;
+    if ((uint64_t)pos + h.a.T <= h.a.max_seq) resident_prep_position(h.a, i, pos);
+}
+
 // ── argmax: first index of the maximum (strict >), nn.zig:122-138 ──────────────────────────
 constexpr int kArgBlock = 256; // threads of every argmax workgroup: the reductions below are this wide
 
@@ -43,10 +78,10 @@ __device__ __forceinline__ void arg_fold(float& bv, int64_t& bi, float v, int64_
         arg_combine(bv, bi, v, i);
 }
 
-// this thread's pair over row[0, n): elements blockIdx.x * 256 + threadIdx.x, then a grid of threads apart
-__device__ __forceinline__ void arg_scan(const float* __restrict__ row, uint64_t n, float& bv, int64_t& bi) {
+// this thread's pair over row[0, n), which nblk workgroups share: elements blockIdx.x * 256 + threadIdx.x, then nblk * 256 apart
+__device__ __forceinline__ void arg_scan(const float* __restrict__ row, uint64_t n, uint32_t nblk, float& bv, int64_t& bi) {
     bv = -INFINITY, bi = INT64_MAX;
-    for (uint64_t i = (uint64_t)blockIdx.x * kArgBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kArgBlock) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kArgBlock + threadIdx.x; i < n; i += (uint64_t)nblk * kArgBlock) {
         const float x = row[i];
         if (x > bv || bi == INT64_MAX) { // strict >: earlier index wins within a thread's ascending walk
             bv = x;
