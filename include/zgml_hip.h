@@ -902,10 +902,11 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
  *   token (resident prefill, zgml_hip_sample for the first token, then the sampled loop: no host bookkeeping), and
  *   candidates_out receives the constrained candidates. zgml_hip_resident_prefill is unchanged: the greedy token it returns is
  *   unconstrained.
+ *   zgml_hip_resident_decode_speculative_constrained (below) honours sequence 0's in the verify step of a token_len = T plan.
  * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
- *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled and zgml_hip_shard_step return -1 with an
- *   error on the context and enqueue nothing: they would pick tokens while ignoring the constraint. (A later change can give row
- *   j of a verify step the state reached by walking its candidates.) */
+ *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative
+ *   and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
+ *   constraint. */
 typedef struct zgml_token_dfa {
     uint32_t n_states, n_classes, vocab, _pad; /* 1 <= n_states <= 65535, 1 <= n_classes <= 8192 */
     const uint16_t* class_of;                  /* [vocab], every entry < n_classes */
@@ -926,6 +927,42 @@ void zgml_hip_constraint_free(zgml_hip_ctx* ctx, zgml_hip_constraint* constraint
 int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t seq, zgml_hip_constraint* constraint, uint32_t state);
 /* The sequence's current state (a blocking read); -1: none attached (or seq out of range, no resident set-up). */
 int64_t zgml_hip_program_constraint_state(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t seq);
+
+/* ── Constrained speculative decode: zgml_hip_resident_decode_speculative_sampled whose verify rows walk the token automaton
+ * attached to sequence 0 (rule: zgml_amd/csrc/spec.h, UNDER A CONSTRAINT, and sample.h). With no constraint attached the call IS
+ * zgml_hip_resident_decode_speculative_sampled: same tokens, same launches, same graphs. top_k = 1 is constrained greedy
+ * speculation.
+ * Forced tokens. zgml_hip_constraint_create also computes forced[state]: the single token the state allows when it allows
+ *   exactly one token of the vocabulary (a class without tokens counts as nothing), none otherwise. A forced token needs no draft
+ *   and cannot be rejected: a step inside a run of forced tokens emits T tokens whatever the logits say ("jump-forward").
+ * Candidates. c[0..T-1] and the count of real drafts come from the draft mode as ever. Then one pass runs from s = the sequence's
+ *   state, row_state[0] = s; for j = 1 .. T-1: s dead -> row j is dead and c[j] stays; else forced[s] exists -> c[j] = forced[s],
+ *   also over a real draft (a different draft is certainly wrong); else j behind the real drafts -> the pad is re-evaluated,
+ *   c[j] = c[j - 1]; then s = next[s][class_of[c[j]]], dead when c[j] is not allowed in s, and row_state[j] = s. stats.drafted
+ *   grows by the mode's real drafts plus the forced tokens placed at pad positions.
+ * Picks. g[j] is the constrained pick (above) of logits row j under row_state[j], u from counter word 0 = pos + j, its penalty
+ *   window that of the sampled verify step. A dead row has no candidates; a row without candidates has no pick (internally the
+ *   sentinel 0xFFFFFFFF, which equals no candidate).
+ * Acceptance, emission, state. The acceptance rule is unchanged; a row without a pick matches nothing, so a dead row is never
+ *   reached through accepted candidates. When g[a] has no pick, the reached state allows no token: g[0..a-1] are emitted (possibly
+ *   nothing) and the call is finished as behind a stop token — it returns 0, *n_produced counts what came out, the rest of
+ *   tokens_out is -1. Stop tokens cut as in the sampled form, and a stop token advances the state too. The sequence's state word
+ *   then advances over exactly the emitted tokens; it persists across calls (two calls give the stream of one;
+ *   zgml_hip_program_constraint_state reads it).
+ * Exactness. The contract of the sampled form: every emitted token is the constrained pick over the plan's own logits row, over a
+ *   confirmed context, at its own position and state. Drafts and forced tokens change how many steps run, never which tokens
+ *   come out.
+ * Log-probabilities and alternatives are over the RAW row, unaffected by the constraint; entries behind *n_produced are the quiet
+ *   NaN and -1.
+ * Launches. Those of the sampled verify step — [draft] [prep] [plan] [select] [merge + pick] ([log-probability launches])
+ *   [accept] —: the constraint adds none. Graphs of its own: constrained calls, plain sampled speculative calls (detached) and
+ *   zgml_hip_resident_prefill alternate on one program and invalidate nothing.
+ * Refused with -1 and an error on the context, before anything is enqueued: everything
+ *   zgml_hip_resident_decode_speculative_sampled refuses, sampling->recent != NULL included. */
+int zgml_hip_resident_decode_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip_program* handle, uint32_t first_token, uint32_t start_pos,
+                                                     uint32_t n_tokens, const zgml_spec_decode* opt, const zgml_sampling* sampling,
+                                                     int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
+                                                     zgml_spec_stats* stats /* may be NULL */);
 
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];

@@ -317,6 +317,7 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_decode_speculative_sampled", "zgml_hip_logprobs", "zgml_hip_logprobs_result",
     "zgml_hip_top_logprobs", "zgml_hip_top_logprobs_result",
     "zgml_hip_constraint_create", "zgml_hip_constraint_free", "zgml_hip_program_set_constraint", "zgml_hip_program_constraint_state",
+    "zgml_hip_resident_decode_speculative_constrained",
     "zgml_hip_kv_move",
 ]
 
@@ -485,6 +486,10 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_program_set_constraint.argtypes = [vp, vp, u32, vp, u32]
         lib.zgml_hip_program_constraint_state.restype = C.c_int64
         lib.zgml_hip_program_constraint_state.argtypes = [vp, vp, u32]
+    if hasattr(lib, "zgml_hip_resident_decode_speculative_constrained"):  # absent from an older build loaded beside this one (tools/constraint_spec_run.py)
+        lib.zgml_hip_resident_decode_speculative_constrained.restype = i32
+        lib.zgml_hip_resident_decode_speculative_constrained.argtypes = [vp, vp, u32, u32, u32, C.POINTER(SpecDecodeC), C.POINTER(SamplingC), vp, C.POINTER(u32),
+                                                                         C.POINTER(SpecStatsC)]
     lib.zgml_hip_kv_move.restype = i32
     lib.zgml_hip_kv_move.argtypes = [vp, vp, C.POINTER(KvLaneC), vp, C.POINTER(KvLaneC), u64, u32, u32, u32]
     lib.zgml_hip_copy_bench.restype = C.c_double

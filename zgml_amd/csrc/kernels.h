@@ -482,6 +482,7 @@ enum SpecWord : uint32_t {
     kSpecWords = kSpecRun + 4,
 };
 struct SampleParamsDev;
+struct SampleConstraintRow;
 struct SpecArgs {
     uint32_t* words;        // [kSpecWords]
     uint32_t* hist;         // [hist_cap] token at every position
@@ -505,6 +506,13 @@ struct SpecArgs {
     const float* top_rows_val = nullptr;
     uint32_t* top_tok_out = nullptr;
     float* top_val_out = nullptr;
+    // the constrained form (zgml_hip_resident_decode_speculative_constrained; spec.h: UNDER A CONSTRAINT), over the sampled one:
+    // con_row = the sequence's row of the device table (read at replay time: the graph outlives an attachment), con_state its
+    // state word, row_state[T] the rows' states — the draft launch fills them behind the candidates (all dead in an idle step),
+    // the constrained select launch reads them, the accept launch advances con_state over the emitted tokens. nullptr: none
+    const SampleConstraintRow* con_row = nullptr;
+    uint32_t* con_state = nullptr;
+    uint32_t* row_state = nullptr;
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
@@ -588,6 +596,7 @@ struct SampleConstraintRow {
     const uint16_t* class_of; // [vocab]
     const uint16_t* next;     // [n_states][n_classes]
     uint32_t n_classes, con_active; // con_active = 0: the row has no constraint (a batched sequence without one beside others)
+    const uint32_t* forced;   // [n_states] the state's only allowed token, or kConstraintNoForced (the verify step's draft launch alone)
 };
 struct SampleConstraint {
     const SampleConstraintRow* rows = nullptr;
@@ -601,13 +610,16 @@ inline uint32_t sample_merge_keys(uint32_t slices, uint32_t run) {
     while (P < slices * run) P <<= 1;
     return P;
 }
-// The forms of the select launch, ONE body in three instantiations (sample.hip): the plain one; with the penalties of params[]
+// The forms of the select launch, ONE body in four instantiations (sample.hip): the plain one; with the penalties of params[]
 // applied to the logits before the selection (`win`); with the rows' constraints as well (`con`) — that one also serves rows
-// without a constraint and rows with or without penalties, but not the rows of a verify step (adv.picks).
-enum SampledSel { kSelPlain, kSelPenalized, kSelConstrained, kSampledSels };
+// without a constraint and rows with or without penalties, but not the rows of a verify step (adv.picks). Those have the fourth:
+// kSelConstrainedRows, the T rows of ONE constrained sequence's verify step — con.rows[0] is the automaton of all of them, con.state
+// holds T words, the state of every ROW (SpecArgs::row_state; a dead row writes pads alone), parameter row 0 and the verify
+// step's window serve all rows.
+enum SampledSel { kSelPlain, kSelPenalized, kSelConstrained, kSelConstrainedRows, kSampledSels };
 // `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select in the form `sel`: sample_slices(n) sorted lists of the 256 largest
 // keys per row] [merge to the row's candidates + pick + advance; the same launch behind every form, with kSelConstrained it
-// advances the state words behind the pick]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
+// advances the state words behind the pick; a verify row without a candidate gets picks[b] = kSpecNoPick]. scratch: sample_scratch_keys(n, rows) words of 64 bits.
 void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv,
                    SampledSel sel = kSelPlain, const SampleWindow& win = SampleWindow{}, const SampleConstraint& con = SampleConstraint{});
 // ── log softmax(row)[token] (logprob.hip; the rule is sample.h's) ──

@@ -18,8 +18,9 @@ enum SampledKind { kKindPick, kKindLogprobs, kKindTop, kSampledKinds };
 constexpr uint32_t kSampledForms = kSampledSels * kSampledKinds;
 constexpr uint32_t sampled_form(uint32_t sel, uint32_t kind) { return kind * kSampledSels + sel; }
 // the names the graphs are captured under: prefix + one of these
-static const char* const kSampledFormNames[kSampledForms] = {"sampled", "penalized", "constrained", "sampled_logprobs", "penalized_logprobs", "constrained_logprobs",
-                                                             "sampled_top", "penalized_top", "constrained_top"};
+static const char* const kSampledFormNames[kSampledForms] = {"sampled", "penalized", "constrained", "constrained_rows",
+                                                             "sampled_logprobs", "penalized_logprobs", "constrained_logprobs", "constrained_rows_logprobs",
+                                                             "sampled_top", "penalized_top", "constrained_top", "constrained_rows_top"};
 
 struct zgml_hip_constraint;
 struct zgml_resident {
@@ -103,6 +104,9 @@ struct zgml_resident {
     uint32_t n_con = 0; // attached sequences
     SampleConstraintRow* con_rows = nullptr;
     uint32_t* con_state = nullptr;
+    // constrained verify step (zgml_hip_resident_decode_speculative_constrained), allocated by its first call: the state of every
+    // logits row, [T] (spec.h: UNDER A CONSTRAINT) — the draft launch writes them, the constrained-rows select launch reads them
+    uint32_t* row_state = nullptr;
 };
 using Resident = zgml_resident;
 
@@ -111,6 +115,7 @@ struct zgml_hip_constraint {
     uint32_t n_states = 0, n_classes = 0, vocab = 0;
     uint32_t attached = 0; // sequences it is attached to: it is not freed before that is 0
     uint16_t *class_of = nullptr, *next = nullptr; // device
+    uint32_t* forced = nullptr; // device, [n_states]: the state's only allowed token or kConstraintNoForced (sample.h)
 };
 
 namespace zgml_rt {
@@ -176,6 +181,7 @@ void free_resident(zgml_hip_program* p) {
         if (c) c->attached -= 1; // (a program that goes detaches its sequences)
     hipFree(r->con_rows);
     hipFree(r->con_state);
+    hipFree(r->row_state);
     delete r;
     p->resident = nullptr;
 }
@@ -189,7 +195,7 @@ namespace {
 // what the entry points that would pick tokens while ignoring an attached constraint say (include/zgml_hip.h); true: refused
 bool refuse_constrained(zgml_hip_ctx* ctx, const zgml_hip_program* p, const char* who) {
     if (!has_constraint(p)) return false;
-    ctx->fail(std::string(who) + ": a constraint is attached to the program (only zgml_hip_resident_decode_sampled, _batch_sampled and zgml_hip_sample honour one: detach it first)");
+    ctx->fail(std::string(who) + ": a constraint is attached to the program (only zgml_hip_resident_decode_sampled, _batch_sampled, zgml_hip_resident_decode_speculative_constrained and zgml_hip_sample honour one: detach it first)");
     return true;
 }
 
@@ -881,10 +887,14 @@ zgml_hip_constraint* zgml_hip_constraint_create(zgml_hip_ctx* ctx, const zgml_to
     hipSetDevice(ctx->device);
     zgml_hip_constraint* c = new zgml_hip_constraint();
     c->n_states = dfa->n_states, c->n_classes = dfa->n_classes, c->vocab = dfa->vocab;
-    const size_t cls = (size_t)dfa->vocab * 2, nxt = (size_t)dfa->n_states * dfa->n_classes * 2;
-    if (!CTX_CHECK(ctx, hipMalloc((void**)&c->class_of, cls)) || !CTX_CHECK(ctx, hipMalloc((void**)&c->next, nxt)) ||
-        !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->class_of, dfa->class_of, cls)) || !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->next, dfa->next, nxt))) {
-        hipFree(c->class_of), hipFree(c->next);
+    const size_t cls = (size_t)dfa->vocab * 2, nxt = (size_t)dfa->n_states * dfa->n_classes * 2, frc = (size_t)dfa->n_states * 4;
+    // the forced token of every state, for the verify step under a constraint: once, beside the two tables
+    std::vector<uint32_t> count(dfa->n_classes), first(dfa->n_classes), forced(dfa->n_states);
+    constraint_forced(dfa, count.data(), first.data(), forced.data());
+    if (!CTX_CHECK(ctx, hipMalloc((void**)&c->class_of, cls)) || !CTX_CHECK(ctx, hipMalloc((void**)&c->next, nxt)) || !CTX_CHECK(ctx, hipMalloc((void**)&c->forced, frc)) ||
+        !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->class_of, dfa->class_of, cls)) || !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->next, dfa->next, nxt)) ||
+        !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->forced, forced.data(), frc))) {
+        hipFree(c->class_of), hipFree(c->next), hipFree(c->forced);
         delete c;
         return nullptr;
     }
@@ -899,7 +909,7 @@ void zgml_hip_constraint_free(zgml_hip_ctx* ctx, zgml_hip_constraint* c) {
     }
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    hipFree(c->class_of), hipFree(c->next);
+    hipFree(c->class_of), hipFree(c->next), hipFree(c->forced);
     delete c;
 }
 
@@ -929,7 +939,7 @@ int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* p, uint
     std::vector<SampleConstraintRow> table(rows);
     for (uint32_t b = 0; b < rows; b++) {
         const zgml_hip_constraint* const cb = r->con[b];
-        table[b] = cb ? SampleConstraintRow{cb->class_of, cb->next, cb->n_classes, 1} : SampleConstraintRow{nullptr, nullptr, 0, 0};
+        table[b] = cb ? SampleConstraintRow{cb->class_of, cb->next, cb->n_classes, 1, cb->forced} : SampleConstraintRow{nullptr, nullptr, 0, 0, nullptr};
     }
     const uint32_t st = c ? state : 0;
     const bool ok = CTX_CHECK(ctx, hipMemcpyAsync(r->con_rows, table.data(), table.size() * sizeof(SampleConstraintRow), hipMemcpyHostToDevice, s)) &&
@@ -1295,12 +1305,18 @@ bool spec_request(zgml_hip_ctx* ctx, const Resident* r, const std::string& who, 
 // sampled form (`sampled`: zgml_hip_resident_decode_speculative_sampled) has [select] [merge + pick] over the T rows in the
 // place of the argmax stage — one launch more —, a graph of its own in the slot resident_decode_sampled cannot use on such a plan,
 // and a stop token may end the call early. Everything the greedy form does is what it did before the sampled one existed.
+// `honours_constraint` (zgml_hip_resident_decode_speculative_constrained; spec.h: UNDER A CONSTRAINT): the sampled form, and with
+// a constraint attached to sequence 0 the constrained one — the same launches with the constrained-rows select in the place of
+// the select, the draft and the accept launch also walking the automaton, graphs of their own; a reached state without a token
+// ends the call early as a stop token does. Without a constraint it is the sampled form to the launch.
 int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
-                const zgml_spec_decode* opt, bool sampled, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
+                const zgml_spec_decode* opt, bool sampled, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats,
+                bool honours_constraint = false) {
     if (!ctx || !p || !p->resident) return -1;
     Resident* r = p->resident;
     if (n_produced) *n_produced = 0;
-    if (refuse_constrained(ctx, p, who.c_str())) return -1;
+    if (!honours_constraint && refuse_constrained(ctx, p, who.c_str())) return -1;
+    const bool constrained = honours_constraint && r->n_con != 0;
     if (r->n_seqs) {
         ctx->fail(who + ": the program is a batched plan (one sequence only here: zgml_hip_resident_decode_batch_speculative runs a batched plan with tokens_per_seq >= 2)");
         return -1;
@@ -1335,6 +1351,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             return -1;
     }
     if (sampled && (!ensure_sample_blocks(ctx, r, T) || (!r->picks && !CTX_CHECK(ctx, hipMalloc((void**)&r->picks, (size_t)T * 4))))) return -1;
+    if (constrained && !r->row_state && !CTX_CHECK(ctx, hipMalloc((void**)&r->row_state, (size_t)T * 4))) return -1;
     if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_tokens)) return -1;
     if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens_cap)) return -1;
     if (top && !ensure_top_blocks(ctx, p, T, r->tokens_cap)) return -1;
@@ -1354,7 +1371,13 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap};
     SampledTail tail; // (sampled form only; the greedy form launches none of it)
     if (sampled) { // rows of one sequence: row j samples at the step's run position + j and reads parameter row 0
-        tail = resident_tail(r, T, SampledTail::sel_of(false, penalized), SampledTail::kind_of(lp, top));
+        // (the constrained-rows select serves penalties on and off, as the constrained one does)
+        tail = resident_tail(r, T, constrained ? kSelConstrainedRows : SampledTail::sel_of(false, penalized), SampledTail::kind_of(lp, top));
+        tail.con = SampleConstraint{};
+        if (constrained) { // one automaton — sequence 0's row of the table — and a state per row
+            tail.con.rows = r->con_rows, tail.con.state = r->row_state;
+            sa.con_row = r->con_rows, sa.con_state = r->con_state, sa.row_state = r->row_state;
+        }
         sa.picks = r->picks, sa.sparams = r->sparams;
         tail.adv.picks = r->picks, tail.adv.pos_word = r->spec + kSpecRunPos;
         // (the `logprobs` field only) every row's value of its pick; the accept launch copies the emitted prefix
@@ -1397,7 +1420,9 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         steps_run += round;
         hipMemcpyAsync(w1, r->spec, sizeof(w1), hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
-        if (ok && w1[kSpecProduced] <= produced) { // (every step with tokens left emits at least one)
+        // (every step with tokens left emits at least one — unless the constraint's state allows no token: the call is then
+        // finished, wanted == produced)
+        if (ok && w1[kSpecProduced] <= produced && w1[kSpecWanted] != w1[kSpecProduced]) {
             ctx->fail(who + ": a round of verify steps produced nothing");
             ok = false;
         }
@@ -1432,6 +1457,12 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
                                                  const zgml_spec_decode* opt, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced,
                                                  zgml_spec_stats* stats) {
     return spec_decode(ctx, p, "resident_decode_speculative_sampled", first_token, start_pos, n_tokens, opt, true, sampling, tokens_out, n_produced, stats);
+}
+
+int zgml_hip_resident_decode_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
+                                                     const zgml_spec_decode* opt, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced,
+                                                     zgml_spec_stats* stats) {
+    return spec_decode(ctx, p, "resident_decode_speculative_constrained", first_token, start_pos, n_tokens, opt, true, sampling, tokens_out, n_produced, stats, true);
 }
 
 // Greedy-exact speculative decode of n_seqs sequences over a batched plan with Ts = tokens_per_seq columns per sequence (contract:

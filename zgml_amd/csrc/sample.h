@@ -78,6 +78,9 @@
 // Behind a pick the state becomes next[state][class_of[token]] (constraint_advance) — stop tokens advance it too. A state that
 // allows no token produces nothing: the loops freeze the sequence as behind a stop token, count no token and leave the state;
 // zgml_hip_sample returns -1. Log-probabilities and alternatives stay what they are above: over the RAW row.
+// In a verify step (zgml_hip_resident_decode_speculative_constrained) every logits ROW has a state of its own — the one reached by
+// walking the step's candidates — and is masked by it exactly as above; a state that allows exactly one token FORCES it
+// (forced[], below), which the draft rule uses. The pass, the rows without a pick and the state's advance: spec.h, UNDER A CONSTRAINT.
 #pragma once
 
 #include <math.h>
@@ -432,6 +435,26 @@ ZGML_SAMPLE_FN bool constraint_allowed(const uint16_t* row, const uint16_t* clas
 // the state behind `token` (an allowed one: else kConstraintForbidden comes back)
 ZGML_SAMPLE_FN uint32_t constraint_advance(const uint16_t* next, uint32_t n_classes, const uint16_t* class_of, uint32_t state, uint32_t token) {
     return next[(uint64_t)state * n_classes + class_of[token]];
+}
+
+// ── the constraint under speculation (zgml_hip_resident_decode_speculative_constrained; the pass over a step's candidates is spec.h's) ──
+// A state that allows EXACTLY ONE token of the vocabulary forces it: forced[state] is that token, kConstraintNoForced otherwise
+// (no token, or two and more). A verify row whose state cannot be reached — a candidate in front of it is not allowed — is
+// dead: its state is kConstraintDead, it has no candidates and therefore no pick.
+constexpr uint32_t kConstraintNoForced = 0xFFFFFFFFu;
+constexpr uint32_t kConstraintDead = kConstraintForbidden; // what constraint_advance gives for a token that is not allowed
+
+// forced[] of one state from the per-class token counts: count[c] tokens have class c, first[c] is the lowest of them. A class
+// without tokens counts as nothing, so one allowed singleton class beside allowed empty classes still forces. O(n_classes).
+ZGML_SAMPLE_FN uint32_t constraint_forced_of(const uint16_t* row, uint32_t n_classes, const uint32_t* count, const uint32_t* first) {
+    uint32_t allowed = 0, token = kConstraintNoForced;
+    for (uint32_t c = 0; c < n_classes; c++) {
+        if (!constraint_row_allows(row, (uint16_t)c) || count[c] == 0) continue;
+        allowed += count[c] > 1 ? 2 : 1; // (saturating: only 0, 1 and "more" matter)
+        if (allowed > 1) return kConstraintNoForced;
+        token = first[c];
+    }
+    return token;
 }
 
 // The number of real (non-zero) keys among the first k0 of a descending list whose pads 0 lie behind every key: the k of a row.

@@ -7,7 +7,7 @@
 //   [select]  grid (slices, rows), 256 threads: a workgroup walks its slice of the row in chunks of kSampleChunk logits; the 256
 //             best keys so far and the chunk's keys are one 2048-key bitonic sort in LDS (16 KiB); the slice's 256 largest keys,
 //             descending, go to the scratch (0 pads a slice of fewer: every real key is > 0). ONE body, select_body<form>, and
-//             three kernels that instantiate it (SampledSel, kernels.h); a form only adds to the one before it:
+//             four kernels that instantiate it (SampledSel, kernels.h); a form only adds to the one before it:
 //     sample_select_kernel              the plain form, nothing else.
 //     sample_select_penalized_kernel    when a row has penalties (sample.h): the workgroup loads its row's
 //             window — at most 256 token ids, one per thread — into LDS (select_window), every thread counts its entry
@@ -18,6 +18,10 @@
 //             4.16): the workgroup also stages the row next[state] of its sequence's current state — at most 8192 u16 words,
 //             16 KiB — into LDS, reads class_of[i] beside row[i] when it fills a chunk and writes the pad 0 for a token that is
 //             not allowed: it is no candidate at all; the penalty rewrite acts on the allowed window tokens alone.
+//     sample_select_constrained_rows_kernel  the T rows of a constrained sequence's verify step (spec.h: UNDER A CONSTRAINT;
+//             DESIGN section 4.18): the constrained form with one automaton for all rows and a state word per ROW — every
+//             workgroup stages next[row_state[b]] —, parameter row 0 and the verify step's window. A dead row (no state) writes
+//             its 256 pads and skips the fill.
 //   [merge + pick + advance]  grid (1, rows), 1024 threads, the same launch behind every form: the slices' lists — at most
 //             32 x 256 keys, 64 KiB of LDS — are loaded with every second list reversed, which is the state of a bitonic sort
 //             after its 256-runs: only the merge stages from 512 up remain. Then the threads fill p[j] (sample_prob), thread 0
@@ -25,6 +29,7 @@
 //             sample_pick_probs at the form's position, advances the constraint's state word — it lives on the device — and the
 //             loop's state (tail_device.h).
 #include "kernels.h"
+#include "spec.h"
 #include "tail_device.h"
 
 namespace zgml {
@@ -38,7 +43,7 @@ static_assert(kSelBlock == kSamplePenaltyMaxWindow, "a thread per window entry")
 static_assert(sizeof(uint64_t) * kSelKeys + 4 * kSamplePenaltyMaxWindow + 2 * kConstraintMaxClasses <= 65536, "keys, window and state row must fit the static LDS limit");
 
 // Row b's window from where SampleWindow says (kernels.h): its length m, and entry t < m into thread t's `tok`. kVerifyRows: the
-// rows may be those of a verify step (the constrained form never serves one)
+// rows may be those of a verify step (the constrained form never serves one; the constrained-rows form serves nothing else)
 template <bool kVerifyRows>
 __device__ __forceinline__ uint32_t select_window(const SampleParamsDev& sp, const SampleAdvance& adv, const SampleWindow& w, uint32_t b, uint32_t& tok) {
     uint32_t m, first;
@@ -66,16 +71,22 @@ __device__ __forceinline__ uint32_t select_window(const SampleParamsDev& sp, con
     return m;
 }
 
-// The select launch of row b = blockIdx.y, slice blockIdx.x, in its three forms. s: kSelKeys keys of LDS; win: the window's 256
+// The select launch of row b = blockIdx.y, slice blockIdx.x, in its four forms. s: kSelKeys keys of LDS; win: the window's 256
 // words (from kSelPenalized on); crow: the state row's kConstraintMaxClasses words (kSelConstrained). `active` (the row has
 // penalties) and `constrained` are uniform over the workgroup: the barriers hang on them. A row with neither computes what the
 // plain form computes, a row with penalties alone what the penalised form computes — a batched sequence beside others.
+// kSelConstrainedRows: cr is the one automaton of all rows and con_state[b] the state of ROW b.
 template <SampledSel kForm>
 __device__ __forceinline__ void select_body(uint64_t* s, uint32_t* win, uint16_t* crow, const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part,
                                             const SampleParamsDev* __restrict__ params, const SampleAdvance& adv, const SampleWindow& w, const SampleConstraintRow& cr, const uint32_t* con_state) {
-    constexpr bool kWindow = kForm != kSelPlain, kMask = kForm == kSelConstrained;
+    constexpr bool kRows = kForm == kSelConstrainedRows, kMask = kForm == kSelConstrained || kRows, kWindow = kForm != kSelPlain;
     const uint32_t b = blockIdx.y;
     const bool constrained = kMask && cr.con_active != 0;
+    if (kRows && (!constrained || con_state[b] == kConstraintDead)) { // (uniform, before any barrier) no candidates: all pads
+        uint64_t* out = part + ((uint64_t)b * gridDim.x + blockIdx.x) * kSampleMaxK;
+        for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) out[t] = 0;
+        return;
+    }
     // (cr's pointers were read from a device table, and inside a function the compiler takes such a pointer for a generic one:
     // the type says that they point to global memory, so the loads of the fill loop are global loads, not flat ones)
     using global_u16 = const __attribute__((address_space(1))) uint16_t;
@@ -87,11 +98,11 @@ __device__ __forceinline__ void select_body(uint64_t* s, uint32_t* win, uint16_t
         for (uint32_t t = threadIdx.x; t < cr.n_classes; t += kSelBlock) crow[t] = from[t];
     }
     // (read in place; the plain form has no parameters and reads none)
-    const SampleParamsDev* const sp = kWindow ? params + (!kMask && adv.picks ? 0 : b) : nullptr;
+    const SampleParamsDev* const sp = kWindow ? params + (kRows || (!kMask && adv.picks) ? 0 : b) : nullptr;
     const bool active = kWindow && sp->pen_active != 0;
     uint32_t tok = 0, count = 0;
     if (active) {
-        const uint32_t m = select_window<!kMask>(*sp, adv, w, b, tok);
+        const uint32_t m = select_window<!kMask || kRows>(*sp, adv, w, b, tok);
         if (threadIdx.x < m) win[threadIdx.x] = tok;
         __syncthreads();
         if (threadIdx.x < m) count = sample_window_count(win, m, threadIdx.x);
@@ -143,6 +154,17 @@ __global__ void __launch_bounds__(kSelBlock) sample_select_constrained_kernel(co
     select_body<kSelConstrained>(s, win, crow, v, n, len, part, params, adv, w, cr, con.state);
 }
 
+// the rows of a verify step: the automaton of sequence 0, con.state = the T row states
+__global__ void __launch_bounds__(kSelBlock) sample_select_constrained_rows_kernel(const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part,
+                                                                                   const SampleParamsDev* __restrict__ params, SampleAdvance adv, SampleWindow w,
+                                                                                   SampleConstraint con) {
+    __shared__ uint64_t s[kSelKeys];
+    __shared__ uint32_t win[kSamplePenaltyMaxWindow];
+    __shared__ uint16_t crow[kConstraintMaxClasses];
+    const SampleConstraintRow cr = con.rows[0];
+    select_body<kSelConstrainedRows>(s, win, crow, v, n, len, part, params, adv, w, cr, con.state);
+}
+
 __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const uint64_t* __restrict__ part, uint32_t n, uint32_t slices, uint32_t P,
                                                                         const SampleParamsDev* __restrict__ params, SampleAdvance adv, SampleConstraint con) {
     __shared__ uint64_t s[kMergeKeys];
@@ -177,6 +199,10 @@ __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const ui
     const uint32_t B = adv.n_seqs;
     uint32_t position;
     if (adv.picks) { // row b of one sequence's verify step
+        if (kc == 0) { // (a constrained row alone) no candidate, no pick: nothing walks sample_pick_probs over nothing
+            adv.picks[b] = kSpecNoPick;
+            return;
+        }
         position = *adv.pos_word + b;
     } else if (!st) {
         if (kc == 0) {
@@ -224,9 +250,12 @@ void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uin
                    SampledSel sel, const SampleWindow& win, const SampleConstraint& con) {
     if (!n || n > 0xFFFFFFFFull || !rows) return; // (the callers refuse these)
     if (sel == kSelConstrained && (adv.picks || !con.rows || !con.state)) return;
+    if (sel == kSelConstrainedRows && (!adv.picks || !con.rows || !con.state)) return;
     const uint32_t slices = sample_slices(n), len = sample_slice_len(n);
     const dim3 grid(slices, rows);
-    if (sel == kSelConstrained)
+    if (sel == kSelConstrainedRows)
+        sample_select_constrained_rows_kernel<<<grid, kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch, params, adv, win, con);
+    else if (sel == kSelConstrained)
         sample_select_constrained_kernel<<<grid, kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch, params, adv, win, con);
     else if (sel == kSelPenalized)
         sample_select_penalized_kernel<<<grid, kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch, params, adv, win);

@@ -81,6 +81,18 @@ inline const char* constraint_check(const zgml_token_dfa* d) {
     return nullptr;
 }
 
+// forced[n_states] of a checked automaton (sample.h: the constraint under speculation), what zgml_hip_constraint_create uploads
+// beside the two tables: one pass over class_of for the per-class counts, then constraint_forced_of per state —
+// O(vocab + n_states n_classes). count, first: n_classes words of scratch each
+inline void constraint_forced(const zgml_token_dfa* d, uint32_t* count, uint32_t* first, uint32_t* forced) {
+    for (uint32_t c = 0; c < d->n_classes; c++) count[c] = 0, first[c] = kConstraintNoForced;
+    for (uint32_t i = 0; i < d->vocab; i++) {
+        const uint16_t c = d->class_of[i];
+        if (count[c]++ == 0) first[c] = i;
+    }
+    for (uint32_t s = 0; s < d->n_states; s++) forced[s] = constraint_forced_of(d->next + (uint64_t)s * d->n_classes, d->n_classes, count, first);
+}
+
 // ... and zgml_hip_program_set_constraint of an attachment: the automaton's vocab and n_states, the program's vocab and number of
 // sequences (1 for a plain plan)
 inline const char* constraint_attach_check(uint32_t dfa_vocab, uint32_t dfa_states, uint32_t program_vocab, uint32_t n_seqs, uint32_t seq, uint32_t state) {

@@ -8,9 +8,25 @@
 // cache). A verify step runs a token_len = T plan over the candidates c[0..T-1]: c[0] = hist[pos], c[j] the draft for position
 // pos + j, or — a position without a draft — the pad c[j - 1]. g[j] is the token of logits row j — its first maximum, or in the
 // sampled form sample.h's pick at position pos + j —: the token at position pos + j + 1 given c[0..j].
+//
+// UNDER A CONSTRAINT (zgml_hip_resident_decode_speculative_constrained; sample.h: THE CONSTRAINT). The mode's candidates and its
+// count of real drafts are made as ever; then ONE pass (spec_constrain_candidates) walks the sequence's automaton over them and
+// gives every row its state: row_state[0] = the sequence's state, and for j >= 1, with s the state of row j - 1:
+//   s dead                       row j is dead, c[j] stays
+//   forced[s] exists             c[j] = forced[s] — also over a real draft: a different draft is certainly wrong
+//   j behind the real drafts     the pad is re-evaluated, c[j] = c[j - 1] (it may now follow a forced token)
+//   then row_state[j] = next[s][class_of[c[j]]], dead when c[j] is not allowed in s.
+// `drafted` grows by the mode's real drafts plus the forced tokens placed at pad positions. g[j] is sample.h's constrained pick
+// under row_state[j] at position pos + j; a dead row, and a row whose state allows no token, has no pick: g[j] = kSpecNoPick,
+// which equals no candidate, so spec_accept (unchanged) never walks past it. When g[acc] is kSpecNoPick the reached state allows
+// no token: the emission is cut in front of it (spec_dead_end_cut) and the call is finished. The sequence's state then advances
+// over exactly the emitted tokens (spec_state_advance); an idle step leaves it alone. Every emitted token is the constrained pick
+// over a confirmed context at its own position and state: drafts and forced tokens change how many steps run, never the tokens.
 #pragma once
 
 #include <stdint.h>
+
+#include "sample.h"
 
 #if defined(__HIPCC__)
 #define ZGML_SPEC_FN __host__ __device__ inline
@@ -111,6 +127,47 @@ ZGML_SPEC_FN uint32_t spec_stop_cut(const G* g, uint32_t m, uint32_t n_stop, con
                 return k + 1;
             }
     return m;
+}
+
+// ── under a constraint ──
+
+constexpr uint32_t kSpecNoPick = 0xFFFFFFFFu; // g[j] of a row without candidates: >= 2^31, no token (a token is < vocab <= 2^32 - 1)
+
+// the pass over the mode's candidates c[0..T-1] with `real` real drafts (at c[1..real]) from the sequence's state: rewrites c,
+// fills row_state[0..T-1], returns the forced tokens placed at pad positions (what `drafted` grows by beside `real`)
+ZGML_SPEC_FN uint32_t spec_constrain_candidates(uint32_t* c, uint32_t T, uint32_t real, uint32_t state, const uint16_t* class_of, const uint16_t* next,
+                                                uint32_t n_classes, const uint32_t* forced, uint32_t* row_state) {
+    uint32_t s = state, placed = 0;
+    row_state[0] = s;
+    for (uint32_t j = 1; j < T; j++) {
+        if (s != kConstraintDead) {
+            const uint32_t f = forced[s];
+            if (f != kConstraintNoForced) {
+                c[j] = f;
+                if (j > real) placed++;
+            } else if (j > real) {
+                c[j] = c[j - 1];
+            }
+            s = constraint_advance(next, n_classes, class_of, s, c[j]);
+        }
+        row_state[j] = s;
+    }
+    return placed;
+}
+
+// the dead-end cut: g[acc] without a pick ends the emission in front of itself — at most acc of the m tokens come out — and
+// finishes the call (*dead). m: what spec_emit_count left
+template <class G>
+ZGML_SPEC_FN uint32_t spec_dead_end_cut(const G* g, uint32_t acc, uint32_t m, bool* dead) {
+    *dead = g[acc] == (G)kSpecNoPick;
+    return *dead && acc < m ? acc : m;
+}
+
+// the sequence's state behind the m emitted tokens g[0..m-1] (each the pick of the state reached: always allowed)
+template <class G>
+ZGML_SPEC_FN uint32_t spec_state_advance(const G* g, uint32_t m, uint32_t state, const uint16_t* class_of, const uint16_t* next, uint32_t n_classes) {
+    for (uint32_t k = 0; k < m && state != kConstraintDead; k++) state = constraint_advance(next, n_classes, class_of, state, (uint32_t)g[k]); // (never dead: no row of the table is read behind it)
+    return state;
 }
 
 } // namespace zgml

@@ -15,6 +15,18 @@ namespace {
 constexpr int kSpecBlock = 256;
 constexpr int kSpecWaves = kSpecBlock / 64;
 
+// (thread 0, the constrained form) the pass of spec.h's rule behind the mode's candidates: the candidates a forced token or a
+// re-evaluated pad replaces, the rows' states, and what `drafted` grows by beside the mode's `real`
+__device__ __forceinline__ uint32_t spec_constrain(const SpecArgs& a, uint32_t real) {
+    if (!a.con_row) return 0;
+    const SampleConstraintRow cr = *a.con_row;
+    if (!cr.con_active) { // (nothing attached: the host does not launch this form then) no row has a state
+        for (uint32_t j = 0; j < a.T; j++) a.row_state[j] = kConstraintDead;
+        return 0;
+    }
+    return spec_constrain_candidates(a.cand, a.T, real, *a.con_state, cr.class_of, cr.next, cr.n_classes, cr.forced, a.row_state);
+}
+
 // The candidates of this step into a.cand (what the prep launch reads as its T token ids) and the position it runs at into the
 // run words. Lookup mode: for n = ngram .. 1 the threads walk the match positions [n - 1, pos - 1] downwards, 256 apart — a
 // thread's first hit is its largest —, the largest hit of the workgroup is folded with wave shuffles and one pass over LDS, and
@@ -33,13 +45,15 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
         if (threadIdx.x == 0) {
             const uint32_t at = !kIdleAtEnd && pos > lo ? pos - 1 : pos;
             for (uint32_t j = 0; j < a.T; j++) a.cand[j] = a.hist[at];
+            for (uint32_t j = 0; a.row_state && j < a.T; j++) a.row_state[j] = kConstraintDead; // (no row of an idle step picks)
             w[kSpecRunPos] = at;
         }
         return;
     }
     if (w[kSpecMode] == 1) {
         if (threadIdx.x == 0) {
-            w[kSpecDrafted] += spec_candidates_provided(a.hist[pos], pos, w[kSpecStart], a.drafts, w[kSpecNDrafts], a.T, a.cand);
+            const uint32_t real = spec_candidates_provided(a.hist[pos], pos, w[kSpecStart], a.drafts, w[kSpecNDrafts], a.T, a.cand);
+            w[kSpecDrafted] += real + spec_constrain(a, real);
             w[kSpecRunPos] = pos;
         }
         return;
@@ -66,7 +80,8 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
         __syncthreads(); // fold[] is rewritten by the next n
     }
     if (threadIdx.x == 0) {
-        w[kSpecDrafted] += spec_candidates_lookup(h, p, best, a.T, a.cand);
+        const uint32_t real = spec_candidates_lookup(h, p, best, a.T, a.cand);
+        w[kSpecDrafted] += real + spec_constrain(a, real);
         w[kSpecRunPos] = pos;
     }
 }
@@ -75,7 +90,9 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
 // a.picks —, then thread 0: how many candidates were the row's choice, what is emitted, and the advance of the state, the history
 // and the counters. The sampled form cuts the emission behind the first stop token and then sets wanted = produced: every later
 // step of the round idles, and the host's round loop ends on the words it reads back. With a.lp_out the log-probabilities of the
-// emitted tokens go next to them: row k's value of g[k], computed for all T rows behind the pick (logprob.hip).
+// emitted tokens go next to them: row k's value of g[k], computed for all T rows behind the pick (logprob.hip). The constrained
+// form keeps kSpecNoPick through the clamp, cuts the emission in front of a reached row without a pick — which finishes the call
+// too — and advances the sequence's automaton state over what came out.
 // g: T LDS words; emitted: one.
 __device__ __forceinline__ void spec_accept_body(const SpecArgs& a, uint32_t* g, uint32_t* emitted_word) {
     uint32_t& emitted = *emitted_word; // (the form with alternatives only) m, for the copy below
@@ -83,7 +100,7 @@ __device__ __forceinline__ void spec_accept_body(const SpecArgs& a, uint32_t* g,
     const uint32_t produced = w[kSpecProduced], wanted = w[kSpecWanted];
     if (produced >= wanted) return; // (uniform) an idle step changes nothing
     const uint32_t lane = threadIdx.x & 63;
-    for (uint32_t j = threadIdx.x; a.picks && j < a.T; j += kSpecBlock) g[j] = a.picks[j] < a.vocab ? a.picks[j] : 0u; // (a pick is an index of its row: the clamp never acts)
+    for (uint32_t j = threadIdx.x; a.picks && j < a.T; j += kSpecBlock) g[j] = a.picks[j] < a.vocab || a.picks[j] == kSpecNoPick ? a.picks[j] : 0u; // (a pick is an index of its row or no pick at all: the clamp never acts)
     for (uint32_t j = threadIdx.x >> 6; !a.picks && j < a.T; j += kSpecWaves) {
         float bv;
         int64_t bi;
@@ -95,17 +112,20 @@ __device__ __forceinline__ void spec_accept_body(const SpecArgs& a, uint32_t* g,
         const uint32_t pos = w[kSpecPos];
         const uint32_t acc = spec_accept(a.cand, g, a.T);
         uint32_t m = spec_emit_count(acc, wanted, produced);
-        bool stopped = false;
+        bool stopped = false, dead = false;
+        m = spec_dead_end_cut(g, acc, m, &dead); // (the constrained form alone has rows without a pick) possibly nothing is left
         if (a.sparams) m = spec_stop_cut(g, m, a.sparams->n_stop, a.sparams->stop, &stopped); // (read in place, as the merge kernel does)
         for (uint32_t k = 0; k < m; k++) {
             if (produced + k < a.tokens_cap) a.tokens[produced + k] = (int64_t)g[k];
             if (a.lp_out && produced + k < a.tokens_cap) a.lp_out[produced + k] = a.lp_rows[k];
             if (pos + 1 + k < a.hist_cap) a.hist[pos + 1 + k] = g[k];
         }
-        w[kSpecTok] = g[m - 1];
+        if (m) w[kSpecTok] = g[m - 1];
         w[kSpecPos] = pos + m;
         w[kSpecProduced] = produced + m;
-        if (stopped) w[kSpecWanted] = produced + m; // the call is finished
+        if (stopped || dead) w[kSpecWanted] = produced + m; // the call is finished
+        if (a.con_row && a.con_row->con_active) // the sequence's state, over exactly the emitted tokens (a stop token too)
+            *a.con_state = spec_state_advance(g, m, *a.con_state, a.con_row->class_of, a.con_row->next, a.con_row->n_classes);
         w[kSpecSteps] += 1;
         w[kSpecAccepted] += acc;
         emitted = m;

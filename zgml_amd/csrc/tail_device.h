@@ -192,7 +192,7 @@ __device__ __forceinline__ float logprob_row_sum(const float* term, uint32_t nb)
 }
 // ... and the chosen token's value, by one thread; `row`: the row's n logits
 __device__ __forceinline__ void logprob_store_chosen(const LogprobTarget& t, const LogprobSlot& s, uint32_t row_index, const float* __restrict__ row, uint32_t n, float M, float S) {
-    if (s.dst) *s.dst = s.tok < n ? logprob_of(row[s.tok], M, S) : sample_bits_f32(kLogprobNaNBits); // (a token is an index of its row: the guard never acts)
+    if (s.dst) *s.dst = s.tok < n ? logprob_of(row[s.tok], M, S) : sample_bits_f32(kLogprobNaNBits); // (a token is an index of its row — or, the picks form under a constraint, kSpecNoPick, a row without a pick: the NaN, and nothing indexes the row with it)
     if (t.written) t.written[row_index] = s.produced;
 }
 

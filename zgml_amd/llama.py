@@ -552,8 +552,18 @@ class Session:
             raise RuntimeError("resident_decode_speculative: " + self._backend.last_error())
         return toks, {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
 
+    def resident_decode_speculative_constrained(self, first_token: int, start_pos: int, n_tokens: int, sampling: "capi.SamplingC", history=None,
+                                                drafts=None, ngram: int = 2, logprobs: bool = False, top_logprobs: int = 0):
+        """zgml_hip_resident_decode_speculative_constrained: resident_decode_speculative_sampled whose verify rows walk the automaton
+        attached to the sequence (set_constraint) — forced tokens are drafted for free, every pick is masked by its row's state and
+        the device state advances over the emitted tokens. The same arguments and the same result; n_produced is also short when a
+        reached state allows no token. Without a constraint it is resident_decode_speculative_sampled."""
+        return self.resident_decode_speculative_sampled(first_token, start_pos, n_tokens, sampling, history, drafts, ngram, logprobs, top_logprobs,
+                                                        _entry="zgml_hip_resident_decode_speculative_constrained")
+
     def resident_decode_speculative_sampled(self, first_token: int, start_pos: int, n_tokens: int, sampling: "capi.SamplingC", history=None,
-                                            drafts=None, ngram: int = 2, logprobs: bool = False, top_logprobs: int = 0):
+                                            drafts=None, ngram: int = 2, logprobs: bool = False, top_logprobs: int = 0,
+                                            _entry: str = "zgml_hip_resident_decode_speculative_sampled"):
         """zgml_hip_resident_decode_speculative_sampled: the verify step's rows are sampled (seeded top-k / top-p) instead of
         arg-maxed -> (tokens[n_tokens], n_produced, {"steps", "drafted", "accepted"}): -1 behind a stop token. `history`, `drafts`
         and `ngram` as resident_decode_speculative. logprobs=True: float32[n_tokens] is appended to the result: every emitted
@@ -564,11 +574,11 @@ class Session:
         if logprobs or top_logprobs:
             sampling = capi.with_logprobs(sampling, top=top_logprobs)
         stats, produced = capi.SpecStatsC(), C.c_uint32(0)
-        rc = capi.load_hip().zgml_hip_resident_decode_speculative_sampled(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
-                                                                           C.byref(sampling), toks.ctypes.data, C.byref(produced), C.byref(stats))
+        rc = getattr(capi.load_hip(), _entry)(self._backend.ctx, self.handle, first_token, start_pos, n_tokens, C.byref(opt),
+                                              C.byref(sampling), toks.ctypes.data, C.byref(produced), C.byref(stats))
         del keep
         if rc != 0:
-            raise RuntimeError("resident_decode_speculative_sampled: " + self._backend.last_error())
+            raise RuntimeError(_entry[len("zgml_hip_"):] + ": " + self._backend.last_error())
         st = {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
         if not logprobs and not top_logprobs:
             return toks[:n_tokens], int(produced.value), st
