@@ -683,7 +683,7 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* ha
  *   token — first, history, drafts — >= vocab, n_history neither 0 nor start_pos[b], mode > 1, ngram > 4); the bound above;
  *   n_tokens[b] > max_tokens; NULL arrays. All n_tokens zero: returns 0 and touches nothing.
  * zgml_hip_resident_decode_batch and zgml_hip_resident_decode_batch_sampled refuse a plan with more than one column per sequence
- * (this call is the one that runs it); the single-sequence speculative calls keep refusing every batched plan. Blocking. */
+ * (this call and zgml_hip_resident_decode_batch_speculative_sampled are the ones that run it); the single-sequence speculative calls keep refusing every batched plan. Blocking. */
 int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens,
                                                const uint32_t* start_pos, const uint32_t* n_tokens, uint32_t max_tokens,
                                                const zgml_spec_decode* per_seq /* [n_seqs] or NULL */,
@@ -699,8 +699,9 @@ int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_progr
  *   u: Philox4x32-10, key = seed, counter = (position whose logits are sampled, stream, 0, 0); u = (word 0 >> 8) / 2^24.
  * u depends on (seed, stream, position) alone, so a generation is the same in one call or several, alone or inside a batch, and
  * a device pick equals the header's pick over the same logits to the bit. top_k = 1 is the greedy token.
- * Speculative decode samples through zgml_hip_resident_decode_speculative_sampled (below); only sharded decode
- * (zgml_hip_shard_step) stays greedy. */
+ * Speculative decode samples through zgml_hip_resident_decode_speculative_sampled (one sequence) and
+ * zgml_hip_resident_decode_batch_speculative_sampled (every sequence of a batched plan with its own parameter set), both below;
+ * only sharded decode (zgml_hip_shard_step) stays greedy. */
 typedef struct zgml_sampling {
     float temperature;   /* > 0 */
     float top_p;         /* (0, 1]; >= 1: no nucleus cut */
@@ -883,6 +884,51 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
                                                  int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
                                                  zgml_spec_stats* stats /* may be NULL */);
 
+/* ── Sampled speculative decode under batching: zgml_hip_resident_decode_batch_speculative with seeded picks per sequence.
+ * Sequence b of a batched plan with T = tokens_per_seq >= 2 columns per sequence runs exactly the loop of
+ * zgml_hip_resident_decode_speculative_sampled with sampling[b] and per_seq[b] (per_seq NULL: every sequence looks up with ngram 2
+ * and no history): the same candidates, pads, draft modes and acceptance rule (zgml_amd/csrc/spec.h); g[j] is the pick of
+ * zgml_amd/csrc/sample.h over logits row b * T + j with counter word 0 = the run position of b + j. Every sequence has its own
+ * parameter set, stream, seed and stop set; sequences with different parameters sit side by side. tokens_out[b * max_tokens + i].
+ * Exactness. As in the single-sequence call, per sequence: an emitted token is a deterministic function of its row's logits bits,
+ *   its window and (seed, stream, position); the other sequences of the batch change neither a sequence's tokens nor its
+ *   statistics. top_k = 1 on every sequence (penalties neutral) gives exactly the tokens and statistics of
+ *   zgml_hip_resident_decode_batch_speculative.
+ * Idling and the bound are those of zgml_hip_resident_decode_batch_speculative: a sequence that has its count idles at its end
+ *   position, start_pos[b] + n_tokens[b] + T <= max_seq for every b, n_tokens[b] = 0 is allowed.
+ * Stop tokens (sampling[b].stop). The cut of the single-sequence call, per sequence: the first stop token among the tokens a step
+ *   of b would emit is recorded and finishes b, which idles from there while the others go on. n_produced[b] (n_produced may be
+ *   NULL) counts up to and including the stop token, the rest of the row is -1, stats[b].accepted counts before any cut. The
+ *   host launches max_b ceil((wanted_b - produced_b) / T) steps per round with wanted_b read back from the device, so a stop
+ *   shortens the round; a round in which a sequence with tokens left produced nothing is an error.
+ * Penalties. Row b * T + j's window is sequence b's device history up to its run position plus its candidates c[1..j]; the first
+ *   position known is b's own (0 with a history, else start_pos[b]). sampling[b].recent must be NULL, as in the single-sequence
+ *   call (the tokens before the call are per_seq[b].history). Sequences with penalties on and off sit side by side.
+ * `logprobs` is per sequence; zgml_hip_logprobs_result hands out [n_seqs][max_tokens] values, entry (b, i) the value of
+ *   tokens_out[b][i] under the row of the verify step that emitted it; an entry that was not produced holds the quiet NaN
+ *   0x7FC00000, and so does the whole row of a sequence without the word. Cost: two launches more per step, graphs of their own.
+ * `top_logprobs` is not kept by this call: the word is ignored, not refused (it was padding before), and
+ *   zgml_hip_top_logprobs_result is left as the last call that kept alternatives left it.
+ * Launches. One graph launch per step: [draft, n_seqs sequences] [prep, n_seqs * T columns] [plan] [select, grid (slices, T,
+ *   n_seqs): n_seqs * T rows] [merge + pick, grid (1, T, n_seqs)] [accept + advance, n_seqs sequences] — one launch more than the greedy
+ *   batched step, a linear chain. Graphs of its own, one per form (plain, penalised, each with and without `logprobs`): greedy,
+ *   sampled and penalised batched speculative calls alternate on one program and invalidate nothing.
+ * Resuming. After the call b's caches are valid for positions < start_pos[b] + n_produced[b]; continue with first_token =
+ *   tokens_out[b][n_produced[b] - 1] at start_pos[b] + n_produced[b] and the history extended by first_tokens[b] and the tokens
+ *   before that one.
+ * Blocking. Returns 0 on success. Refused with -1 and an error on the context that names the sequence, before anything is
+ *   enqueued: everything zgml_hip_resident_decode_batch_speculative refuses (a plain plan, one column per sequence, a constraint
+ *   attached to any sequence — constraints under batched speculation are not served —, the per-sequence requests, the bound,
+ *   n_tokens[b] > max_tokens, NULL arrays); per sequence everything zgml_hip_resident_decode_speculative_sampled refuses of the
+ *   parameters, recent != NULL included; sampling = NULL. All n_tokens zero: returns 0 and touches nothing on the device. */
+int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens,
+                                                       const uint32_t* start_pos, const uint32_t* n_tokens, uint32_t max_tokens,
+                                                       const zgml_spec_decode* per_seq /* [n_seqs] or NULL */,
+                                                       const zgml_sampling* sampling /* [n_seqs], never NULL */,
+                                                       int64_t* tokens_out /* [n_seqs][max_tokens] */,
+                                                       uint32_t* n_produced /* [n_seqs] or NULL */,
+                                                       zgml_spec_stats* stats /* [n_seqs] or NULL */);
+
 /* ── Constrained decoding: a token automaton masks the sampled picks on the device (rule: zgml_amd/csrc/sample.h, THE CONSTRAINT).
  * The caller brings the table, in class-compressed form: class_of[i] is the class of token i, next[s][c] the state behind a
  * token of class c in state s, 0xFFFF where such a token is not allowed in s. There is no grammar compiler here and no additive
@@ -904,8 +950,8 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
  *   unconstrained.
  *   zgml_hip_resident_decode_speculative_constrained (below) honours sequence 0's in the verify step of a token_len = T plan.
  * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
- *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative
- *   and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
+ *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative,
+ *   zgml_hip_resident_decode_batch_speculative_sampled and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
  *   constraint. */
 typedef struct zgml_token_dfa {
     uint32_t n_states, n_classes, vocab, _pad; /* 1 <= n_states <= 65535, 1 <= n_classes <= 8192 */

@@ -13,15 +13,22 @@ tokens on the host; the clock is the host's around it, `reps` timed runs after o
 "right" drafts are the tokens of a first run of the same plan with n-gram drafts; where the plan's rows differ between step
 alignments (near-ties of the synthetic LM head) some are rejected, so the line carries the tokens per step that were really emitted.
 
+With --sampled (say --sampled 0.8,40,0.95,1) every run group is followed by its sampled twin on the SAME program, greedy and
+sampled calls alternating repetition by repetition: zgml_hip_resident_decode_batch_sampled beside the one-column greedy loop,
+zgml_hip_resident_decode_batch_speculative_sampled beside the greedy verify loop (sequence b samples with stream + b). The sampled
+drafts are the tokens of a first sampled run of the same plan with n-gram drafts. The table then carries, per (B, Ts, drafts), the
+sampled step next to the greedy one, their difference, and the sampled break-even against the one-column SAMPLED loop.
+
 Positional: model, batches ("2,4,8"), tokens_per_seq values ("2,4"), tokens, start, reps. Flags:
   --max-seq S    context length of the plans (default 512 for llama2-7b, else 2048)
-  --option V     ZGML_HIP_OPT_SMALL_M_MATVEC at compile (default 1: the row kernel up to its measured bound, M <= 6)"""
+  --option V     ZGML_HIP_OPT_SMALL_M_MATVEC at compile (default 1: the row kernel up to its measured bound, M <= 6)
+  --sampled temperature,top_k,top_p,stream   also the sampled calls (seed 1234), alternating with the greedy ones"""
 import json
 import sys
 import time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from zgml_amd import Backend, llama  # noqa: E402
+from zgml_amd import Backend, capi, llama  # noqa: E402
 
 
 def take_flag(args, name):
@@ -36,6 +43,7 @@ def take_flag(args, name):
 args = sys.argv[1:]
 max_seq = int(take_flag(args, "--max-seq") or 0)
 option = int(take_flag(args, "--option") or 1)
+sampled = take_flag(args, "--sampled")
 name = args[0] if len(args) > 0 else "smollm-135m"
 batches = [int(b) for b in args[1].split(",")] if len(args) > 1 else [2, 4, 8]
 widths = [int(t) for t in args[2].split(",")] if len(args) > 2 else [2, 4]
@@ -48,29 +56,51 @@ cfg = llama.preset(name, max_seq or (512 if name == "llama2-7b" else 2048))
 assert start + tokens + max(widths) <= cfg.max_seq_len, "positions beyond --max-seq"
 m = llama.Model(cfg, llama.Q4_0, threads=16)
 fns = llama.hip_backend_fns(be)
-table = []
+table, table_s = [], []
+
+
+def samplings(B):
+    """one parameter set per sequence: the flag's, stream + b"""
+    t, k, p, stream = sampled.split(",")
+    return [capi.SamplingC.of(float(t), int(k), float(p), seed=1234, stream=int(stream) + b) for b in range(B)]
 
 
 def emit(**kw):
     print(json.dumps({"model": name, "positions": [start, start + tokens], "option": option, **kw}), flush=True)
 
 
-def timed(call):
-    call()  # warm-up
-    times, out = [], None
+def timed(call, twin=None):
+    """-> (times, last result) of `call`; with `twin` — the sampled call on the same program — the two alternate repetition by
+    repetition and the twin's (times, last result) follow"""
+    calls = [call] + ([twin] if twin else [])
+    for c in calls:
+        c()  # warm-up
+    times, out = [[] for _ in calls], [None for _ in calls]
     for _ in range(reps):
-        t0 = time.perf_counter()
-        out = call()
-        times.append(time.perf_counter() - t0)
+        for i, c in enumerate(calls):
+            t0 = time.perf_counter()
+            out[i] = c()
+            times[i].append(time.perf_counter() - t0)
     assert not be.last_error(), be.last_error()
-    return times, out
+    return (times[0], out[0], times[1], out[1]) if twin else (times[0], out[0])
 
 
 for B in batches:
     first = [(911 * b + 17) % cfg.vocab_size for b in range(B)]
     bs = llama.BatchSession(m, fns, B, small_m_matvec=option)
     bs.resident_setup(be)
-    times, toks = timed(lambda: bs.resident_decode_batch(first, [start] * B, tokens))
+    base_step_s = None
+    if sampled:
+        sps = samplings(B)
+        times, toks, times_s, (toks_s, made) = timed(lambda: bs.resident_decode_batch(first, [start] * B, tokens),
+                                                     lambda: bs.resident_decode_batch_sampled(first, [start] * B, tokens, sps))
+        assert (toks_s >= 0).all() and (made == tokens).all()
+        base_step_s = min(times_s) / tokens
+        emit(path="batch_sampled", B=B, Ts=1, sampling=sampled, launches=be.planText(bs.handle).count("\n") + 3,
+             ms_per_step=[round(1e3 * t / tokens, 4) for t in times_s], tok_s=[round(B * tokens / t, 1) for t in times_s])
+        table_s.append((B, 1, "batch_sampled", B * tokens / min(times_s), 1e3 * min(times) / tokens, 1e3 * base_step_s, 1.0, None))
+    else:
+        times, toks = timed(lambda: bs.resident_decode_batch(first, [start] * B, tokens))
     assert toks.shape == (B, tokens) and (toks >= 0).all()
     base_step = min(times) / tokens
     emit(path="batch", B=B, Ts=1, launches=be.planText(bs.handle).count("\n") + 3, ms_per_step=[round(1e3 * t / tokens, 4) for t in times],
@@ -85,8 +115,27 @@ for B in batches:
         assert not be.last_error(), be.last_error()
         pad = [[int(t) for t in row] + [int(row[-1])] * Ts for row in stream]
         forms = {"right": pad, "wrong": [[(t + 1) % cfg.vocab_size for t in row] for row in pad]}
+        if sampled:  # the sampled stream of THIS plan, from a sampled run with n-gram drafts
+            stream_s = s.resident_decode_batch_speculative_sampled(first, [start] * B, tokens, sps)[0]
+            assert not be.last_error(), be.last_error()
+            pad_s = [[int(t) for t in row] + [int(row[-1])] * Ts for row in stream_s]
+            forms_s = {"right": pad_s, "wrong": [[(t + 1) % cfg.vocab_size for t in row] for row in pad_s]}
         for form, drafts in forms.items():
-            times, (toks, stats) = timed(lambda: s.resident_decode_batch_speculative(first, [start] * B, tokens, drafts=drafts))
+            if sampled:
+                times, (toks, stats), times_s, (toks_s, made, stats_s) = timed(
+                    lambda: s.resident_decode_batch_speculative(first, [start] * B, tokens, drafts=drafts),
+                    lambda: s.resident_decode_batch_speculative_sampled(first, [start] * B, tokens, sps, drafts=forms_s[form]))
+                assert (made == tokens).all()
+                steps_s = max(st["steps"] for st in stats_s)
+                per_step_s = sum(tokens / st["steps"] for st in stats_s) / B
+                step_ms_s = 1e3 * min(times_s) / steps_s
+                emit(path="batch_spec_sampled", B=B, Ts=Ts, drafts=form, sampling=sampled, launches=text.count("\n") + 5, steps=[st["steps"] for st in stats_s],
+                     tokens_per_step_and_seq=round(per_step_s, 3), same_tokens_as_ngram_run=toks_s.tolist() == stream_s.tolist(),
+                     ms_per_step=[round(1e3 * t / steps_s, 4) for t in times_s], tok_s=[round(B * tokens / t, 1) for t in times_s])
+                greedy_ms = 1e3 * min(times) / max(st["steps"] for st in stats)
+                table_s.append((B, Ts, form, B * tokens / min(times_s), greedy_ms, step_ms_s, step_ms_s / (1e3 * base_step_s), per_step_s))
+            else:
+                times, (toks, stats) = timed(lambda: s.resident_decode_batch_speculative(first, [start] * B, tokens, drafts=drafts))
             assert toks.tolist() == stream.tolist() or form == "right", "the drafts changed the tokens"
             steps = max(st["steps"] for st in stats)  # steps the call ran for its slowest sequence
             per_step = sum(tokens / st["steps"] for st in stats) / B
@@ -101,5 +150,11 @@ print(f"\n{name}: {tokens} tokens per sequence from position {start}, best of {r
 print(f"{'B':>3} {'Ts':>3} {'drafts':>13} {'tok/s':>9} {'ms/step':>9} {'break-even':>11} {'tok/step/seq':>13}")
 for B, Ts, form, tps, ms, be_even, per in table:
     print(f"{B:>3} {Ts:>3} {form:>13} {tps:>9.1f} {ms:>9.4f} {be_even:>11.3f} {'' if per is None else f'{per:>13.3f}'}")
+if sampled:
+    print(f"\n{name}, sampled ({sampled}; seed 1234, stream + b): the sampled step beside the greedy step of the same program, alternating; "
+          "break-even = sampled ms/step over the one-column SAMPLED loop's at the same B")
+    print(f"{'B':>3} {'Ts':>3} {'drafts':>13} {'tok/s':>9} {'greedy ms':>10} {'sampled ms':>11} {'diff us':>8} {'break-even':>11} {'tok/step/seq':>13}")
+    for B, Ts, form, tps, g_ms, s_ms, be_even, per in table_s:
+        print(f"{B:>3} {Ts:>3} {form:>13} {tps:>9.1f} {g_ms:>10.4f} {s_ms:>11.4f} {1e3 * (s_ms - g_ms):>8.1f} {be_even:>11.3f} {'' if per is None else f'{per:>13.3f}'}")
 m.close()
 be.close()

@@ -521,7 +521,8 @@ void launch_spec_accept(hipStream_t s, const SpecArgs& a);
 // kSpecWords, hist + b * hist_cap, drafts + b * drafts_stride, cand + b * T, pval / pidx + b * T * nblk, tokens + b * cap with cap =
 // words[n_seqs * kSpecWords], the row length of this call's token table (a device word: the graph serves every max_tokens). A
 // sequence that has its count idles at its END position (the single loop idles one position in front of it): its state, history
-// and counters stay as they are. Greedy form only: picks / sparams / lp_* / top_* stay null.
+// and counters stay as they are. The sampled form (zgml_hip_resident_decode_batch_speculative_sampled): picks + b * T, sparams + b,
+// lp_rows + b * T and lp_out + b * cap likewise; top_* and con_* stay null.
 struct SpecBatchArgs {
     SpecArgs a;
     uint32_t n_seqs, drafts_stride;
@@ -558,10 +559,16 @@ struct SampleParamsDev {
 //   state, n_seqs == 0     the single-sequence loop: argmax_stage2's advance (state[0] token, [1] position, [2] produced; tokens[cap]),
 //                          nothing once state[3] is set — a stop token sets it behind its own advance
 //   state, n_seqs == B     the batched loop: argmax_batch_stage2's advance; a stop token leaves the sequence no steps
-//   picks                  rows of ONE sequence (a speculative verify step): every row reads the one parameter set params[0] — not
-//                          params[b] —, samples at position *pos_word + b (a device word: the step's position is not known
-//                          when the graph is captured) and stores picks[b] = token. It advances nothing: spec_accept_kernel does
-// The position whose logits are sampled is `position` / state[1] / state[B + b] / *pos_word + b.
+//   picks                  the rows of a verify step, rows_per_seq = T consecutive rows per sequence (ONE sequence: all `rows` of
+//                          the launch; zgml_hip_resident_decode_batch_speculative_sampled: n_seqs * T rows). Row r belongs to
+//                          sequence seq = r / rows_per_seq and is its candidate row cand = r % rows_per_seq. The mapping is
+//                          stated once, by the shape of the two launches: their grids are (.., rows_per_seq, sequences), so a
+//                          workgroup reads (seq, cand) from its block index — SampleRow in sample.hip — and nothing divides. It
+//                          reads that sequence's parameter set params[seq] — not params[r] —, samples at position
+//                          pos_word[seq * pos_stride] + cand (device words: the step's position is not known when the graph is
+//                          captured; pos_stride = kSpecWords, the state words of the sequences lie that far apart) and stores
+//                          picks[r] = token. It advances nothing: the accept launch does
+// The position whose logits are sampled is `position` / state[1] / state[B + b] / pos_word[seq * pos_stride] + cand.
 struct SampleAdvance {
     uint32_t* state = nullptr;
     int64_t* tokens = nullptr;
@@ -570,6 +577,7 @@ struct SampleAdvance {
     uint32_t* cand = nullptr;
     uint32_t* picks = nullptr;
     const uint32_t* pos_word = nullptr;
+    uint32_t rows_per_seq = 1, pos_stride = 0; // (the picks form alone)
 };
 // Where the penalised select launch finds the window of row b (sample.h: positions max(lo, P + 1 - W) .. P); which form holds
 // follows SampleAdvance's:
@@ -578,8 +586,10 @@ struct SampleAdvance {
 //                          is ring[b * 256 + (q & 255)], lo[b] the first position known. The select launch itself stores the
 //                          token at P into the ring (workgroup 0 of the row; no other workgroup reads that slot in this
 //                          launch: it is the slot of P - 256), so the merge launch is the unpenalised one, untouched
-//   a verify step          P = *pos_word + b; the token at q is hist[q] for q <= *pos_word, cand[q - *pos_word] behind it;
-//                          lo = *lo_word. The rows read parameter row 0
+//   a verify step          row r of sequence seq, candidate row j (SampleAdvance's mapping): P = run + j with run = the
+//                          sequence's position word; the token at q is hist[seq * hist_stride + q] for q <= run, the sequence's
+//                          candidate cand[seq * rows_per_seq + q - run] behind it; lo = lo_word[seq * pos_stride]. The rows read
+//                          their sequence's parameter row
 struct SampleWindow {
     const uint32_t* list = nullptr;
     uint32_t n_list = 0;
@@ -588,6 +598,7 @@ struct SampleWindow {
     const uint32_t* hist = nullptr;
     const uint32_t* cand = nullptr;
     const uint32_t* lo_word = nullptr;
+    uint32_t hist_stride = 0; // (a verify step of several sequences) words between two sequences' histories
 };
 // The constraint of row b (sample.h: THE CONSTRAINT), read by the constrained select launch and by the advance of the merge
 // launch: a table beside SampleParamsDev's, uploaded when a constraint is attached or detached, and the rows' state words, which

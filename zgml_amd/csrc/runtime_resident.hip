@@ -1,6 +1,6 @@
 // runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up; the greedy loops
 // (single-sequence decode, batched decode, the prefill chunk); their sampled forms and the sampled / greedy speculative verify
-// loop, and the greedy verify loop of every sequence of a batched plan; the blocking calls over one buffer range
+// loop, and the greedy / sampled verify loop of every sequence of a batched plan; the blocking calls over one buffer range
 // (zgml_hip_sample, zgml_hip_logprobs, zgml_hip_top_logprobs) with their result
 // getters; the token constraint's create / attach / state. Everything a step needs (embedding row, mask column, RoPE rows, the
 // dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
@@ -75,6 +75,7 @@ struct zgml_resident {
     // step reads parameter row 0 alone)
     SampleParamsDev* sparams = nullptr;
     uint64_t* skeys = nullptr;
+    uint32_t sample_rows = 0; // the rows both were allocated for: a call with more is refused on the host, never served short
     // The sampled loops' graphs, one per form — what the select launch is (SampledSel) times what follows the pick (SampledKind):
     // the forms alternate on one program and invalidate nothing, and the greedy loop's graph stays valid beside them.
     // SampledTail::form() indexes them
@@ -90,6 +91,7 @@ struct zgml_resident {
     float *lpart = nullptr, *lp = nullptr, *lp_rows = nullptr;
     uint32_t* lp_written = nullptr;
     uint64_t lp_cap = 0;
+    uint32_t lp_block_rows = 0; // the rows lpart / lp_rows / lp_written were allocated for, as sample_rows
     // the alternatives of the sampled tail (the `top_logprobs` word of zgml_sampling; top_logprob.hip), allocated by the first such
     // call: the lists of a select over the RAW rows (what a penalised or constrained step needs beside skeys, the same size), the
     // pairs next to the produced tokens ([top_cap][64], the layout of lp), the T rows' pairs of a verify step
@@ -312,21 +314,38 @@ void fill_window_block(std::vector<uint32_t>& block, uint32_t rows, uint32_t b, 
     block[(size_t)rows * kSamplePenaltyMaxWindow + b] = start_pos - sp.n_recent;
 }
 
+// A scratch block that exists was sized by the first call that needed it. Every loop of one program asks for the same rows
+// today (the plan fixes them), but a launch over more rows than the block holds would write out of bounds on the device: refused
+// here, on the host
+bool block_holds(zgml_hip_ctx* ctx, const char* what, uint32_t have, uint32_t rows) {
+    if (have >= rows) return true;
+    ctx->fail(std::string(what) + " were allocated for " + std::to_string(have) + " logits rows, this call needs " + std::to_string(rows));
+    return false;
+}
+
 // the sampled loops' device blocks: `rows` parameter rows and partial candidate lists
 bool ensure_sample_blocks(zgml_hip_ctx* ctx, Resident* r, uint32_t rows) {
-    if (r->sparams) return true;
-    return CTX_CHECK(ctx, hipMalloc((void**)&r->sparams, (size_t)rows * sizeof(SampleParamsDev))) &&
-           CTX_CHECK(ctx, hipMalloc((void**)&r->skeys, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t)));
+    if (r->sparams && r->skeys) return block_holds(ctx, "the sampled tail's blocks", r->sample_rows, rows);
+    if (!CTX_CHECK(ctx, hipMalloc((void**)&r->sparams, (size_t)rows * sizeof(SampleParamsDev))) ||
+        !CTX_CHECK(ctx, hipMalloc((void**)&r->skeys, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t))))
+        return false;
+    r->sample_rows = rows;
+    return true;
 }
 
 // the log-probability blocks of the sampled loops: `rows` logits rows, values for `cap` produced tokens (the capacity of the
 // token table they lie next to). A graph bakes the pointers: growing the values drops the graphs, as growing the tokens does
 bool ensure_logprob_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, uint64_t cap) {
     Resident* r = p->resident;
-    if (!r->lpart && (!CTX_CHECK(ctx, hipMalloc((void**)&r->lpart, (size_t)rows * logprob_blocks(r->vocab) * 2 * sizeof(float))) ||
-                      !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_rows, (size_t)rows * sizeof(float))) ||
-                      !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_written, (size_t)rows * 4))))
-        return false;
+    if (r->lpart && r->lp_rows && r->lp_written) {
+        if (!block_holds(ctx, "the log-probability blocks", r->lp_block_rows, rows)) return false;
+    } else {
+        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->lpart, (size_t)rows * logprob_blocks(r->vocab) * 2 * sizeof(float))) ||
+            !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_rows, (size_t)rows * sizeof(float))) ||
+            !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_written, (size_t)rows * 4)))
+            return false;
+        r->lp_block_rows = rows;
+    }
     if (r->lp_cap < cap) {
         hipStreamSynchronize(ctx->stream);
         hipFree(r->lp);
@@ -1379,7 +1398,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             sa.con_row = r->con_rows, sa.con_state = r->con_state, sa.row_state = r->row_state;
         }
         sa.picks = r->picks, sa.sparams = r->sparams;
-        tail.adv.picks = r->picks, tail.adv.pos_word = r->spec + kSpecRunPos;
+        tail.adv.picks = r->picks, tail.adv.pos_word = r->spec + kSpecRunPos, tail.adv.rows_per_seq = T; // (one sequence: all T rows are its)
         // (the `logprobs` field only) every row's value of its pick; the accept launch copies the emitted prefix
         tail.top.chosen.out = r->lp_rows, tail.top.chosen.picks = r->picks;
         // (the `top_logprobs` word only) every row's alternatives, likewise
@@ -1465,14 +1484,22 @@ int zgml_hip_resident_decode_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip
     return spec_decode(ctx, p, "resident_decode_speculative_constrained", first_token, start_pos, n_tokens, opt, true, sampling, tokens_out, n_produced, stats, true);
 }
 
-// Greedy-exact speculative decode of n_seqs sequences over a batched plan with Ts = tokens_per_seq columns per sequence (contract:
-// include/zgml_hip.h; rules: spec.h). Per step [draft, B sequences] [prep, B Ts columns] [plan] [argmax stage 1 over B Ts rows]
-// [accept + advance, B sequences], one graph of its own; sequence b's device state is spec_decode()'s, at row b of every block.
-int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
-                                               const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, int64_t* tokens_out,
-                                               zgml_spec_stats* stats) {
+} // extern "C"
+
+namespace {
+
+// Speculative decode of n_seqs sequences over a batched plan with Ts = tokens_per_seq columns per sequence (contract:
+// include/zgml_hip.h; rules: spec.h), both forms, as spec_decode() serves the single-sequence ones. Per step [draft, B sequences]
+// [prep, B Ts columns] [plan] [argmax stage 1 over B Ts rows] [accept + advance, B sequences], one graph of its own; sequence b's
+// device state is spec_decode()'s, at row b of every block. The sampled form (`sampled`:
+// zgml_hip_resident_decode_batch_speculative_sampled) has [select] [merge + pick] over the B Ts rows in the place of the argmax
+// stage — one launch more; logits row r is candidate row r % Ts of sequence r / Ts (kernels.h: SampleAdvance) and reads that
+// sequence's parameter set —, graphs of its own in the slots no other sampled loop can use on such a plan, and a stop token ends
+// its sequence early: the others go on. Everything the greedy form enqueues is what it enqueued before the sampled one existed.
+int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, const uint32_t* first_tokens, const uint32_t* start_pos,
+                      const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, bool sampled, const zgml_sampling* sampling,
+                      int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
     if (!ctx || !p) return -1;
-    const std::string who = "resident_decode_batch_speculative";
     Resident* r = p->resident;
     if (!r || !r->n_seqs || !p->n_seqs) {
         ctx->fail(who + ": not a batched program with a resident set-up (zgml_hip_program_set_sequences, then zgml_hip_resident_setup)");
@@ -1488,8 +1515,15 @@ int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_progr
         ctx->fail(who + ": NULL array (first_tokens, start_pos, n_tokens, or tokens_out with max_tokens > 0)");
         return -1;
     }
+    if (sampled && !sampling) {
+        ctx->fail(who + ": no sampling parameters (one zgml_sampling per sequence)");
+        return -1;
+    }
     std::vector<SpecRequest> req(B);
+    std::vector<SampleParamsDev> sp(sampled ? B : 0);
     uint32_t most = 0;
+    bool penalized = false; // one sequence with penalties: the penalised select for all (a row without them computes what it did)
+    bool lp = false;        // ... and one with log-probabilities: the two launches for all (a sequence that did not ask is not copied out)
     for (uint32_t b = 0; b < B; b++) {
         const std::string seq = who + " (sequence " + std::to_string(b) + ")";
         if (n_tokens[b] > max_tokens) {
@@ -1497,10 +1531,15 @@ int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_progr
             return -1;
         }
         if (!spec_request(ctx, r, seq, first_tokens[b], start_pos[b], n_tokens[b], Ts, true, per_seq ? per_seq + b : nullptr, &req[b])) return -1;
+        if (sampled) {
+            if (!sampling_params(ctx, seq, sampling + b, r->vocab, r->vocab, &sp[b], RecentOf::Spec)) return -1;
+            penalized = penalized || sp[b].pen_active, lp = lp || sampling[b].logprobs;
+        }
         most = std::max(most, n_tokens[b]);
     }
     for (uint64_t i = 0; i < (uint64_t)B * max_tokens; i++) tokens_out[i] = -1;
     for (uint32_t b = 0; stats && b < B; b++) stats[b] = zgml_spec_stats{0, 0, 0, 0};
+    for (uint32_t b = 0; n_produced && b < B; b++) n_produced[b] = 0;
     if (!most) return 0;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
@@ -1509,11 +1548,15 @@ int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_progr
         return positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) &&
                positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]] + n_tokens[p->op_seq[i]]; });
     });
-    const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1, n_words = B * kSpecWords + 1;
+    const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1, n_words = B * kSpecWords + 1, rows = B * Ts;
     if (!r->bspec && (!CTX_CHECK(ctx, hipMalloc((void**)&r->bspec, (size_t)n_words * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->bhist, (size_t)B * hist_cap * 4)) ||
                       !CTX_CHECK(ctx, hipMalloc((void**)&r->bdrafts, (size_t)B * r->max_seq * 4))))
         return -1;
+    // (sampled form only) every block for B Ts logits rows: the select keys, a parameter row per sequence (the block has one per
+    // logits row), the rows' picks, the rows' values and the block pairs; the emitted values lie as the tokens do
+    if (sampled && (!ensure_sample_blocks(ctx, r, rows) || (!r->picks && !CTX_CHECK(ctx, hipMalloc((void**)&r->picks, (size_t)rows * 4))))) return -1;
     if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * max_tokens)) return -1;
+    if (lp && !ensure_logprob_blocks(ctx, p, rows, r->btokens_cap)) return -1;
     std::vector<uint32_t> w0(n_words, 0), w1(n_words, 0);
     w0[(size_t)B * kSpecWords] = max_tokens; // row length of the device token table of this call
     bool up = true;
@@ -1530,55 +1573,99 @@ int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_progr
              (!w[kSpecNDrafts] || CTX_CHECK(ctx, hipMemcpyAsync(r->bdrafts + (size_t)b * r->max_seq, o.drafts, (size_t)w[kSpecNDrafts] * 4, hipMemcpyHostToDevice, s)));
     }
     if (!up || !CTX_CHECK(ctx, hipMemcpyAsync(r->bspec, w0.data(), w0.size() * 4, hipMemcpyHostToDevice, s)) ||
-        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * max_tokens * 8, s))) { // (-1: what a sequence leaves behind its count)
-        hipStreamSynchronize(s); // (w0 is read by a copy that may be in flight)
+        !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * max_tokens * 8, s)) || // (-1: what a sequence leaves behind its count, or its stop token)
+        (sampled && !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, sp.data(), sp.size() * sizeof(SampleParamsDev), hipMemcpyHostToDevice, s)))) {
+        hipStreamSynchronize(s); // (w0 and sp are read by copies that may be in flight)
         return -1;
     }
     SpecBatchArgs sa{{r->bspec, r->bhist, r->bdrafts, r->tok_dev, r->btokens, r->bval, r->bidx, Ts, nblk, r->vocab, hist_cap, 0 /* the device word */}, B, r->max_seq};
+    SampledTail tail; // (sampled form only; the greedy form launches none of it)
+    if (sampled) { // row b Ts + j: sequence b's parameter row, its run position + j, its history and candidates
+        tail = resident_tail(r, rows, SampledTail::sel_of(false, penalized), SampledTail::kind_of(lp, false)); // (the alternatives are not kept: include/zgml_hip.h)
+        tail.con = SampleConstraint{};
+        sa.a.picks = r->picks, sa.a.sparams = r->sparams;
+        tail.adv.picks = r->picks, tail.adv.pos_word = r->bspec + kSpecRunPos, tail.adv.rows_per_seq = Ts, tail.adv.pos_stride = kSpecWords;
+        // (the `logprobs` field only) every row's value of its pick; the accept launch copies each sequence's emitted prefix
+        tail.top.chosen.out = r->lp_rows, tail.top.chosen.picks = r->picks;
+        // (penalised form only) a row's window is its sequence's history up to the run position and the candidates behind it
+        tail.win.hist = r->bhist, tail.win.hist_stride = hist_cap, tail.win.cand = r->tok_dev, tail.win.lo_word = r->bspec + kSpecHistLo;
+        if (lp) sa.a.lp_rows = r->lp_rows, sa.a.lp_out = r->lp;
+    }
     const ResidentBatchSpecPrepArgs prep{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
                                          p->dyn_dev, r->bspec, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B, Ts};
     auto one_step = [&](hipStream_t st) {
         launch_spec_batch_draft(st, sa);
         launch_resident_batch_spec_prep(st, prep, r->prep_total);
         run_plan(p, st, 0, p->plan.size());
-        launch_argmax_rows_stage1(st, r->logits, r->vocab, B * Ts, r->bval, r->bidx);
+        if (sampled)
+            tail.launch(st, r->logits, r->vocab);
+        else
+            launch_argmax_rows_stage1(st, r->logits, r->vocab, rows, r->bval, r->bidx);
         launch_spec_batch_accept(st, sa);
     };
+    hipGraphExec_t& exec = sampled ? r->sgraph_exec[tail.form()] : r->bspec_graph_exec;
+    hipGraph_t& graph = sampled ? r->sgraph[tail.form()] : r->bspec_graph;
     // (as the batched loops: no pageable copy in flight when the capture begins)
-    capture_once(ctx, s, "resident_batch_spec", true, one_step, &r->bspec_graph, &r->bspec_graph_exec);
+    capture_once(ctx, s, sampled ? std::string("resident_batch_spec_") + kSampledFormNames[tail.form()] : std::string("resident_batch_spec"), true, one_step, &graph, &exec);
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish the sequence with the most
-    // tokens left, reads the counts back, repeats
-    std::vector<uint32_t> produced(B, 0);
+    // tokens left, reads the counts back, repeats. (`wanted` is read back with the words: a stop token of the sampled form sets
+    // its sequence's to the produced count, which shortens the round)
+    std::vector<uint32_t> produced(B, 0), wanted(n_tokens, n_tokens + B);
     uint64_t steps_run = 0;
     bool ok = true;
     while (ok) {
         uint32_t round = 0;
-        for (uint32_t b = 0; b < B; b++) round = std::max(round, (n_tokens[b] - produced[b] + Ts - 1) / Ts);
+        for (uint32_t b = 0; b < B; b++) round = std::max(round, (wanted[b] - produced[b] + Ts - 1) / Ts);
         if (!round) break;
-        replay(s, r->bspec_graph_exec, round, one_step);
+        replay(s, exec, round, one_step);
         steps_run += round;
         hipMemcpyAsync(w1.data(), r->bspec, w1.size() * 4, hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
         for (uint32_t b = 0; ok && b < B; b++) {
             const uint32_t now = std::min(w1[(size_t)b * kSpecWords + kSpecProduced], n_tokens[b]);
-            if (produced[b] < n_tokens[b] && now <= produced[b]) { // (every step of a sequence with tokens left emits at least one)
+            if (produced[b] < wanted[b] && now <= produced[b]) { // (every step of a sequence with tokens left emits at least one)
                 ctx->fail(who + ": a round of verify steps produced nothing (sequence " + std::to_string(b) + ")");
                 ok = false;
             }
-            produced[b] = now;
+            produced[b] = now, wanted[b] = std::max(now, std::min(w1[(size_t)b * kSpecWords + kSpecWanted], n_tokens[b]));
         }
     }
+    SampledCopyOut out{tail.kind};
     if (ok) {
         hipMemcpyAsync(tokens_out, r->btokens, (size_t)B * max_tokens * 8, hipMemcpyDeviceToHost, s); // (the device rows are max_tokens long too)
+        out.download(s, r, (uint64_t)B * max_tokens);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
     }
     ok = ok && ctx->handoff_ok(who.c_str());
-    for (uint32_t b = 0; ok && stats && b < B; b++) {
+    // [n_seqs][max_tokens] values, as tokens_out: a sequence that did not ask, and every entry behind a count, keeps the NaN
+    out.keep(ctx, (uint64_t)B * max_tokens, 0, [&](uint64_t e) {
+        const uint32_t b = (uint32_t)(e / max_tokens), i = (uint32_t)(e % max_tokens);
+        return ok && sampling[b].logprobs && i < produced[b] ? (int64_t)e : -1; }, [](uint64_t) { return (int64_t)-1; });
+    for (uint32_t b = 0; ok && b < B; b++) {
         const uint32_t* w = w1.data() + (size_t)b * kSpecWords;
-        stats[b] = zgml_spec_stats{w[kSpecSteps], w[kSpecDrafted], w[kSpecAccepted], 0};
+        if (stats) stats[b] = zgml_spec_stats{w[kSpecSteps], w[kSpecDrafted], w[kSpecAccepted], 0};
+        if (n_produced) n_produced[b] = produced[b];
     }
-    resident_end(p, steps_run, p->plan.size() + 4); // per step [draft] [prep] [plan] [argmax stage 1] [accept]
+    // per step [draft] [prep] [plan] [argmax stage 1] [accept], or the sampled tail in the place of the argmax stage
+    resident_end(p, steps_run, p->plan.size() + 3 + (sampled ? tail.launches() : 1));
     return ok ? 0 : -1;
+}
+
+} // namespace
+
+extern "C" {
+
+int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                               const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, int64_t* tokens_out,
+                                               zgml_spec_stats* stats) {
+    return spec_decode_batch(ctx, p, "resident_decode_batch_speculative", first_tokens, start_pos, n_tokens, max_tokens, per_seq, false, nullptr, tokens_out, nullptr, stats);
+}
+
+int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                                       const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq,
+                                                       const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
+    return spec_decode_batch(ctx, p, "resident_decode_batch_speculative_sampled", first_tokens, start_pos, n_tokens, max_tokens, per_seq, true, sampling, tokens_out,
+                             n_produced, stats);
 }
 
 } // extern "C"

@@ -1,9 +1,11 @@
-// sample.hip — the sampled token tail (zgml_hip_sample, zgml_hip_resident_decode_sampled / _batch_sampled and the T rows of a
-// sampled verify step, zgml_hip_resident_decode_speculative_sampled; runtime_resident.hip): two launches per row of logits, the
+// sample.hip — the sampled token tail (zgml_hip_sample, zgml_hip_resident_decode_sampled / _batch_sampled and the rows of a
+// sampled verify step — T of one sequence, zgml_hip_resident_decode_speculative_sampled, or T of each of B sequences,
+// zgml_hip_resident_decode_batch_speculative_sampled; runtime_resident.hip): two launches per row of logits, the
 // shape of launch_argmax / launch_argmax_batch. The rule — candidate order, pick, random number — is sample.h's; here is only
 // how workgroups find the candidates. Keys are unique 64-bit words (sample_key), so the largest 256 of a row are one
 // well-defined list whatever the slicing: nothing below depends on arrival order, no workgroup waits for another and there is
 // no last-arriver stage.
+//   (the rows of a verify step lie in grid planes, one per sequence — (.., rows_per_seq, sequences), SampleRow below; everything else is (.., rows))
 //   [select]  grid (slices, rows), 256 threads: a workgroup walks its slice of the row in chunks of kSampleChunk logits; the 256
 //             best keys so far and the chunk's keys are one 2048-key bitonic sort in LDS (16 KiB); the slice's 256 largest keys,
 //             descending, go to the scratch (0 pads a slice of fewer: every real key is > 0). ONE body, select_body<form>, and
@@ -42,17 +44,28 @@ static_assert(kMergeKeys * sizeof(uint64_t) <= 65536, "the merge's lists must fi
 static_assert(kSelBlock == kSamplePenaltyMaxWindow, "a thread per window entry");
 static_assert(sizeof(uint64_t) * kSelKeys + 4 * kSamplePenaltyMaxWindow + 2 * kConstraintMaxClasses <= 65536, "keys, window and state row must fit the static LDS limit");
 
+// The logits row of a workgroup of either launch. The grids are (.., rows, 1) — row = blockIdx.y, as ever — or, the picks form
+// (kernels.h: SampleAdvance), (.., rows_per_seq, sequences): row = seq * rows_per_seq + cand with seq = blockIdx.z, cand = blockIdx.y.
+// One sequence's verify step is the case sequences = 1.
+struct SampleRow {
+    uint32_t row, seq, cand;
+};
+__device__ __forceinline__ SampleRow sample_row() { return {blockIdx.z * gridDim.y + blockIdx.y, blockIdx.z, blockIdx.y}; }
+
 // Row b's window from where SampleWindow says (kernels.h): its length m, and entry t < m into thread t's `tok`. kVerifyRows: the
 // rows may be those of a verify step (the constrained form never serves one; the constrained-rows form serves nothing else)
 template <bool kVerifyRows>
 __device__ __forceinline__ uint32_t select_window(const SampleParamsDev& sp, const SampleAdvance& adv, const SampleWindow& w, uint32_t b, uint32_t& tok) {
     uint32_t m, first;
-    if (kVerifyRows && adv.picks) { // row b of a verify step
-        const uint32_t run = *adv.pos_word, P = run + b;
-        m = sample_window_span(P, *w.lo_word, sp.window, &first);
+    if (kVerifyRows && adv.picks) { // row b of a verify step: candidate row j of its sequence
+        const uint32_t seq = sample_row().seq, j = sample_row().cand;
+        const uint32_t run = adv.pos_word[(uint64_t)seq * adv.pos_stride], P = run + j;
+        const uint32_t* const hist = w.hist + (uint64_t)seq * w.hist_stride;
+        const uint32_t* const cand = w.cand + (uint64_t)seq * adv.rows_per_seq;
+        m = sample_window_span(P, w.lo_word[(uint64_t)seq * adv.pos_stride], sp.window, &first);
         if (threadIdx.x < m) {
             const uint32_t q = first + threadIdx.x;
-            tok = q <= run ? w.hist[q] : w.cand[q - run];
+            tok = q <= run ? hist[q] : cand[q - run];
         }
     } else if (!adv.state) { // the blocking form: the list is the window
         m = w.n_list < sp.window ? w.n_list : sp.window;
@@ -71,7 +84,7 @@ __device__ __forceinline__ uint32_t select_window(const SampleParamsDev& sp, con
     return m;
 }
 
-// The select launch of row b = blockIdx.y, slice blockIdx.x, in its four forms. s: kSelKeys keys of LDS; win: the window's 256
+// The select launch of row b = sample_row().row, slice blockIdx.x, in its four forms. s: kSelKeys keys of LDS; win: the window's 256
 // words (from kSelPenalized on); crow: the state row's kConstraintMaxClasses words (kSelConstrained). `active` (the row has
 // penalties) and `constrained` are uniform over the workgroup: the barriers hang on them. A row with neither computes what the
 // plain form computes, a row with penalties alone what the penalised form computes — a batched sequence beside others.
@@ -80,7 +93,7 @@ template <SampledSel kForm>
 __device__ __forceinline__ void select_body(uint64_t* s, uint32_t* win, uint16_t* crow, const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part,
                                             const SampleParamsDev* __restrict__ params, const SampleAdvance& adv, const SampleWindow& w, const SampleConstraintRow& cr, const uint32_t* con_state) {
     constexpr bool kRows = kForm == kSelConstrainedRows, kMask = kForm == kSelConstrained || kRows, kWindow = kForm != kSelPlain;
-    const uint32_t b = blockIdx.y;
+    const uint32_t b = sample_row().row;
     const bool constrained = kMask && cr.con_active != 0;
     if (kRows && (!constrained || con_state[b] == kConstraintDead)) { // (uniform, before any barrier) no candidates: all pads
         uint64_t* out = part + ((uint64_t)b * gridDim.x + blockIdx.x) * kSampleMaxK;
@@ -98,7 +111,8 @@ __device__ __forceinline__ void select_body(uint64_t* s, uint32_t* win, uint16_t
         for (uint32_t t = threadIdx.x; t < cr.n_classes; t += kSelBlock) crow[t] = from[t];
     }
     // (read in place; the plain form has no parameters and reads none)
-    const SampleParamsDev* const sp = kWindow ? params + (kRows || (!kMask && adv.picks) ? 0 : b) : nullptr;
+    // (a verify row reads its sequence's parameter row; the constrained-rows form has one sequence)
+    const SampleParamsDev* const sp = kWindow ? params + (kRows ? 0 : !kMask && adv.picks ? sample_row().seq : b) : nullptr;
     const bool active = kWindow && sp->pen_active != 0;
     uint32_t tok = 0, count = 0;
     if (active) {
@@ -168,7 +182,7 @@ __global__ void __launch_bounds__(kSelBlock) sample_select_constrained_rows_kern
 __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const uint64_t* __restrict__ part, uint32_t n, uint32_t slices, uint32_t P,
                                                                         const SampleParamsDev* __restrict__ params, SampleAdvance adv, SampleConstraint con) {
     __shared__ uint64_t s[kMergeKeys];
-    const uint32_t b = blockIdx.y;
+    const uint32_t b = sample_row().row;
     const uint64_t* lists = part + (uint64_t)b * slices * kSampleMaxK;
     for (uint32_t t = threadIdx.x; t < P; t += kMergeBlock) { // P = sample_merge_keys(slices, 256), <= kMergeKeys
         const uint32_t l = t >> 8, off = t & 255;
@@ -178,7 +192,7 @@ __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const ui
     for (uint32_t k = 2 * kSampleMaxK; k <= P; k <<= 1)
         for (uint32_t j = k >> 1; j > 0; j >>= 1) bitonic_stage<kMergeBlock>(s, P / 2, k, j);
     // s[0, 256): the row's largest keys, descending
-    const SampleParamsDev& sp = params[adv.picks ? 0 : b]; // (read in place: a copy with its indexed stop[] would live in scratch)
+    const SampleParamsDev& sp = params[adv.picks ? sample_row().seq : b]; // (read in place: a copy with its indexed stop[] would live in scratch)
     // The row's k: the real (non-zero) keys among the first sample_top_k(top_k, n). A row without a constraint has n >= that many
     // real keys — the lists hold the 256 largest of every slice — so for it kc == kc0 and nothing changes to the bit; a constrained
     // row may have fewer allowed tokens than top_k, down to none.
@@ -198,12 +212,12 @@ __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const ui
     uint32_t* const st = adv.state;
     const uint32_t B = adv.n_seqs;
     uint32_t position;
-    if (adv.picks) { // row b of one sequence's verify step
+    if (adv.picks) { // row b of a verify step: candidate row blockIdx.y of sequence blockIdx.z
         if (kc == 0) { // (a constrained row alone) no candidate, no pick: nothing walks sample_pick_probs over nothing
             adv.picks[b] = kSpecNoPick;
             return;
         }
-        position = *adv.pos_word + b;
+        position = adv.pos_word[(uint64_t)sample_row().seq * adv.pos_stride] + sample_row().cand;
     } else if (!st) {
         if (kc == 0) {
             adv.out[0] = -1;
@@ -249,10 +263,13 @@ __global__ void __launch_bounds__(kMergeBlock) sample_merge_pick_kernel(const ui
 void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uint64_t* scratch, const SampleParamsDev* params, const SampleAdvance& adv,
                    SampledSel sel, const SampleWindow& win, const SampleConstraint& con) {
     if (!n || n > 0xFFFFFFFFull || !rows) return; // (the callers refuse these)
+    if (adv.picks && (!adv.rows_per_seq || rows % adv.rows_per_seq)) return; // (whole sequences of verify rows)
     if (sel == kSelConstrained && (adv.picks || !con.rows || !con.state)) return;
     if (sel == kSelConstrainedRows && (!adv.picks || !con.rows || !con.state)) return;
     const uint32_t slices = sample_slices(n), len = sample_slice_len(n);
-    const dim3 grid(slices, rows);
+    // (the picks form: whole sequences of rows_per_seq verify rows, one grid plane per sequence)
+    const dim3 rows_grid = adv.picks ? dim3(1, adv.rows_per_seq, rows / adv.rows_per_seq) : dim3(1, rows, 1);
+    const dim3 grid(slices, rows_grid.y, rows_grid.z);
     if (sel == kSelConstrainedRows)
         sample_select_constrained_rows_kernel<<<grid, kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch, params, adv, win, con);
     else if (sel == kSelConstrained)
@@ -261,7 +278,7 @@ void launch_sample(hipStream_t s, const float* v, uint64_t n, uint32_t rows, uin
         sample_select_penalized_kernel<<<grid, kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch, params, adv, win);
     else
         sample_select_kernel<<<grid, kSelBlock, 0, s>>>(v, (uint32_t)n, len, scratch);
-    sample_merge_pick_kernel<<<dim3(1, rows), kMergeBlock, 0, s>>>(scratch, (uint32_t)n, slices, sample_merge_keys(slices, kSampleMaxK), params, adv,
+    sample_merge_pick_kernel<<<rows_grid, kMergeBlock, 0, s>>>(scratch, (uint32_t)n, slices, sample_merge_keys(slices, kSampleMaxK), params, adv,
                                                                    sel == kSelConstrained ? con : SampleConstraint{});
 }
 

@@ -4,7 +4,8 @@
 // their own: DESIGN section 0.2 item 5 measured that folding such tails into a neighbouring launch is slower. The rules themselves
 // (which tokens are drafted, how many are accepted) are spec.h's; here is only how a workgroup evaluates them.
 // Each body is stated once, as a device function over ONE sequence's SpecArgs: the single-sequence kernels hand it their
-// arguments, the batched kernels (zgml_hip_resident_decode_batch_speculative; blockIdx.x = sequence) the sequence's view of theirs.
+// arguments, the batched kernels (zgml_hip_resident_decode_batch_speculative and its sampled form; blockIdx.x = sequence) the
+// sequence's view of theirs.
 #include "kernels.h"
 #include "spec.h"
 #include "tail_device.h"
@@ -152,6 +153,9 @@ __device__ __forceinline__ SpecArgs spec_seq_view(const SpecBatchArgs& ba, uint3
     v.cand += (uint64_t)b * v.T;
     v.tokens += (uint64_t)b * cap, v.tokens_cap = cap;
     v.pval += (uint64_t)b * v.T * v.nblk, v.pidx += (uint64_t)b * v.T * v.nblk;
+    // the sampled form: the sequence's T picks, its parameter set (the stop tokens), its T row values and its values' row
+    if (v.picks) v.picks += (uint64_t)b * v.T, v.sparams += b;
+    if (v.lp_out) v.lp_rows += (uint64_t)b * v.T, v.lp_out += (uint64_t)b * cap;
     return v;
 }
 

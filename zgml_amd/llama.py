@@ -369,6 +369,49 @@ class BatchSession:
             raise RuntimeError("resident_decode_batch_speculative: " + self._backend.last_error())
         return toks[:, :max_tokens], [{"steps": st.steps, "drafted": st.drafted, "accepted": st.accepted} for st in stats]
 
+    def resident_decode_batch_speculative_sampled(self, first_tokens, start_pos, n_tokens, samplings, histories=None, drafts=None, ngram: int = 2,
+                                                  logprobs=None):
+        """Sampled speculative decode of every sequence on a tokens_per_seq >= 2 plan (include/zgml_hip.h:
+        zgml_hip_resident_decode_batch_speculative_sampled): `samplings` is one capi.SamplingC per sequence, histories / drafts as
+        in resident_decode_batch_speculative. -> (tokens[B, max(n_tokens)], n_produced[B], [{"steps", "drafted", "accepted"}] per
+        sequence); row b holds n_produced[b] tokens — up to and including a stop token —, then -1. logprobs: True, or one flag per
+        sequence: float32[B, max(n_tokens)] is appended, row b the log-probabilities of sequence b's tokens — NaN behind them, and
+        all through a row whose flag is off."""
+        u32p = C.POINTER(C.c_uint32)
+        B = self.n_seqs
+        t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_tokens, dtype=np.uint32), (B,)))
+        assert t.size == B and p.size == B and len(samplings) == B
+        histories = [None] * B if histories is None else list(histories)
+        drafts = [None] * B if drafts is None else list(drafts)
+        assert len(histories) == B and len(drafts) == B
+        opts, keep = (capi.SpecDecodeC * B)(), []
+        for b in range(B):
+            opts[b], arrays = Session._spec_opt(histories[b], drafts[b], ngram)
+            keep.append(arrays)
+        sp = (capi.SamplingC * B)(*samplings)
+        flags = [bool(logprobs)] * B if logprobs is None or isinstance(logprobs, bool) else [bool(x) for x in logprobs]
+        assert len(flags) == B
+        for b in range(B):
+            if flags[b]:
+                sp[b].logprobs = 1
+        max_tokens = int(n.max()) if n.size else 0
+        toks = np.full((B, max(1, max_tokens)), -1, np.int64)
+        produced = np.zeros(B, np.uint32)
+        stats = (capi.SpecStatsC * B)()
+        rc = capi.load_hip().zgml_hip_resident_decode_batch_speculative_sampled(
+            self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p), n.ctypes.data_as(u32p), max_tokens, opts, sp, toks.ctypes.data,
+            produced.ctypes.data_as(u32p), stats)
+        del keep
+        if rc != 0:
+            raise RuntimeError("resident_decode_batch_speculative_sampled: " + self._backend.last_error())
+        out = (toks[:, :max_tokens], produced, [{"steps": st.steps, "drafted": st.drafted, "accepted": st.accepted} for st in stats])
+        if logprobs is None:
+            return out
+        asked = any(bool(sp[b].logprobs) for b in range(B))
+        lps = capi.logprobs_result(self._backend.ctx, (B, max_tokens)) if asked and max_tokens else np.full((B, max_tokens), np.nan, np.float32)
+        return out + (lps,)
+
     def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None, top_logprobs=None):
         """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
         -> (tokens[B, max(n_steps)], n_produced[B]); row b holds n_produced[b] tokens, then -1. logprobs: True, or one flag per
