@@ -30,3 +30,12 @@ def q4_0_blocks_from_int8(data: np.ndarray, scales: np.ndarray) -> np.ndarray:
     nib = (data.astype(np.int16) + 8).astype(np.uint8).reshape(n_blocks, 32)
     out[:, 2:] = nib[:, 0::2] | (nib[:, 1::2] << 4)
     return out.ravel()
+
+
+def q8_0_blocks(data: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """int8 + f16-exact scales in the GGUF Q8_0 byte layout (34-byte blocks: f16 scale, 32 int8)."""
+    nb = scales.size
+    out = np.zeros((nb, 34), np.uint8)
+    out[:, :2] = scales.astype(np.float16).view(np.uint8).reshape(nb, 2)
+    out[:, 2:] = data.reshape(nb, 32).view(np.uint8)
+    return out.ravel()

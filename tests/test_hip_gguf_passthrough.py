@@ -7,18 +7,10 @@ import numpy as np
 import pytest
 
 from zgml_amd import DeviceOp, DeviceProgram, ProgramIO, QuantizedWeightUpload
-from tests.synth import q4_0_blocks_from_int8
+from tests.synth import q4_0_blocks_from_int8, q8_0_blocks
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def q8_0_blocks(data, scales):
-    nb = scales.size
-    out = np.zeros((nb, 34), np.uint8)
-    out[:, :2] = scales.astype(np.float16).view(np.uint8).reshape(nb, 2)
-    out[:, 2:] = data.reshape(nb, 32).view(np.uint8)
-    return out.ravel()
 
 
 def make(kind, K, N, rng):

@@ -242,14 +242,35 @@ def test_tile_kernel_rows_equal_matvec_full_size(hip_backend, oracle, kind):
     hip_backend.freeProgram(h)
 
 
-def _q4_weight(rng, K, N):
-    data = rng.integers(-8, 8, K * N).astype(np.int8)
-    scales = (rng.random(K * N // 32).astype(np.float16) * 0.05 + 0.001).astype(f32)
+def _q4_weight(rng, K, N, values="positive"):
+    """values: "positive" (this file's generator) or a profile of tests/weight_cases.py ("gguf": signed scales over many binades
+    by the Q4_0 rule, at an amplitude that keeps the chains' exp() in range; "negated": every scale negative)"""
+    if values == "positive":
+        data = rng.integers(-8, 8, K * N).astype(np.int8)
+        scales = (rng.random(K * N // 32).astype(np.float16) * 0.05 + 0.001).astype(f32)
+    else:
+        from tests import weight_cases as WC
+        data, scales = WC.make(values, "q4_f16", K, N, rng, amp=0.004)
     return QuantizedWeightUpload(data, scales, K, N, 32)
+
+
+SIGNED = ["gguf", "negated"]  # the value profiles the fused M = 1 builders below also run over (tests/weight_cases.py)
 
 
 @pytest.mark.parametrize("K,N", [(576, 576), (4096, 1024)])
 def test_matvec_prologues_and_epilogue_chains_store_every_intermediate(hip_backend, oracle, K, N):
+    _check_chains(hip_backend, oracle, K, N)
+
+
+@pytest.mark.parametrize("values", SIGNED)
+@pytest.mark.parametrize("K,N", [(576, 576), (2080, 576)])
+def test_matvec_prologues_and_epilogue_chains_over_signed_scales(hip_backend, oracle, K, N, values):
+    """The same chains over GGUF-like and negated weights: 576 is the smallest n-on-lanes shape of the test above, K = 2080 the
+    smallest K that packs K-on-lanes (>= 2049) in whole 32-blocks."""
+    _check_chains(hip_backend, oracle, K, N, values)
+
+
+def _check_chains(hip_backend, oracle, K, N, values="positive"):
     """The planner folds the ops around an M = 1 quantized mat-vec into its launch (prologue: rmsnorm -> mul gamma or a
     plain mul; epilogue: element-wise consumers) and the kernel still writes every intermediate buffer. Chains here:
     the residual add and the SiLU chain exactly as the LLaMA lowering emits them (straight-line fast paths), the SiLU
@@ -292,7 +313,7 @@ def test_matvec_prologues_and_epilogue_chains_store_every_intermediate(hip_backe
     ]
     prog = DeviceProgram(ops=ops, buffer_sizes=sizes,
                          initial_uploads=[ProgramIO(B["x"], x), ProgramIO(B["gamma"], gamma), ProgramIO(B["vec"], vec), ProgramIO(B["one"], one)],
-                         qweights=[_q4_weight(rng, K, N) for _ in range(5)])
+                         qweights=[_q4_weight(rng, K, N, values) for _ in range(5)])
     for name in ("normed", "xg", "gate", "up", "exp_neg", "silu", "y", "resid", "t1", "t2", "t3", "t4", "t5", "g2", "e2", "s2", "s3", "s4"):
         n = sizes[B[name]]
         want = oracle.run_program(prog, B[name], n)
@@ -306,6 +327,18 @@ def test_matvec_prologues_and_epilogue_chains_store_every_intermediate(hip_backe
 
 @pytest.mark.parametrize("K0,K,Ns", [(1536, 576, (576, 192, 192)), (576, 576, (1536, 1536)), (2048, 2048, (2048, 512, 512)), (4096, 4096, (4096, 4096, 4096))])
 def test_prepared_norm_hand_over_stores_every_intermediate(hip_backend, oracle, K0, K, Ns):
+    _check_prenorm(hip_backend, oracle, K0, K, Ns)
+
+
+@pytest.mark.parametrize("values", SIGNED)
+@pytest.mark.parametrize("K0,K,Ns", [(1536, 576, (576, 192, 192)), (2080, 2080, (2080, 512, 512))])
+def test_prepared_norm_hand_over_over_signed_scales(hip_backend, oracle, K0, K, Ns, values):
+    """The same hand-over over GGUF-like and negated weights: the smallest n-on-lanes parametrisation above, and K = 2080 for the
+    K-on-lanes consumer (the plan's text must still say the norm was prepared)."""
+    _check_prenorm(hip_backend, oracle, K0, K, Ns, values)
+
+
+def _check_prenorm(hip_backend, oracle, K0, K, Ns, values="positive"):
     """The tail of one decoder half and the head of the next as the LLaMA lowering emits them (llama_transformer.zig:192-253):
     projection -> residual add -> rmsnorm -> mul(gamma) -> q/k/v (or gate/up) over the result. The planner folds this into TWO
     launches, and the first one PREPARES the second one's norm (h * gamma and the partial sums of h^2: QMV_PRO_PRENORM) so that
@@ -327,7 +360,7 @@ def test_prepared_norm_hand_over_stores_every_intermediate(hip_backend, oracle, 
     ] + [DeviceOp.qmatmul(7 + t, B["xg"], 1 + t, 1, n, K) for t, n in enumerate(Ns)]
     prog = DeviceProgram(ops=ops, buffer_sizes=sizes,
                          initial_uploads=[ProgramIO(B["xin"], xin), ProgramIO(B["resid"], resid), ProgramIO(B["gamma"], gamma)],
-                         qweights=[_q4_weight(rng, K0, K)] + [_q4_weight(rng, K, n) for n in Ns])
+                         qweights=[_q4_weight(rng, K0, K, values)] + [_q4_weight(rng, K, n, values) for n in Ns])
     h = hip_backend.compileProgram(prog)
     assert h
     try:
@@ -353,6 +386,18 @@ def test_prepared_norm_hand_over_stores_every_intermediate(hip_backend, oracle, 
 
 @pytest.mark.parametrize("K,F", [(576, 1536), (2048, 2048), (4096, 11008)])
 def test_gate_up_pair_launch_stores_every_intermediate(hip_backend, oracle, K, F):
+    _check_pair(hip_backend, oracle, K, F)
+
+
+@pytest.mark.parametrize("values", SIGNED)
+@pytest.mark.parametrize("K,F", [(576, 1536), (2080, 2080)])
+def test_gate_up_pair_launch_over_signed_scales(hip_backend, oracle, K, F, values):
+    """The pair launch over GGUF-like and negated weights: the smallest n-on-lanes parametrisation above, and 2080 x 2080 for the
+    K-on-lanes pair kernel (the plan's text must still say a pair ran)."""
+    _check_pair(hip_backend, oracle, K, F, values)
+
+
+def _check_pair(hip_backend, oracle, K, F, values="positive"):
     """The SwiGLU half as the LLaMA lowering emits it (llama_transformer.zig:129-133, silu = nn.zig:38-44): gate and up over the
     same input, the SiLU chain on gate, silu(gate) * up, the down projection over the product. The planner turns the first launch into
     a PAIR launch — one workgroup computes the same 16 columns of gate AND up and stores the product itself — and the down
@@ -374,7 +419,7 @@ def test_gate_up_pair_launch_stores_every_intermediate(hip_backend, oracle, K, F
         DeviceOp.qmatmul(B["down"], B["act"], 2, 1, K, F),
     ]
     prog = DeviceProgram(ops=ops, buffer_sizes=sizes, initial_uploads=[ProgramIO(B["x"], x), ProgramIO(B["one"], one)],
-                         qweights=[_q4_weight(rng, K, F), _q4_weight(rng, K, F), _q4_weight(rng, F, K)])
+                         qweights=[_q4_weight(rng, K, F, values), _q4_weight(rng, K, F, values), _q4_weight(rng, F, K, values)])
     h = hip_backend.compileProgram(prog)
     assert h
     try:
@@ -399,6 +444,18 @@ def test_gate_up_pair_launch_stores_every_intermediate(hip_backend, oracle, K, F
 
 @pytest.mark.parametrize("K0,K,F", [(1536, 576, 1536), (2048, 2048, 1024), (4096, 4096, 11008)])
 def test_swiglu_half_with_prepared_norm_and_pair_stores_every_intermediate(hip_backend, oracle, K0, K, F):
+    _check_swiglu(hip_backend, oracle, K0, K, F)
+
+
+@pytest.mark.parametrize("values", SIGNED)
+@pytest.mark.parametrize("K0,K,F", [(1536, 576, 1536), (2080, 2080, 2080)])
+def test_swiglu_half_over_signed_scales(hip_backend, oracle, K0, K, F, values):
+    """Both hand-overs over GGUF-like and negated weights: the smallest n-on-lanes parametrisation above, and 2080 throughout for
+    the K-on-lanes kernels."""
+    _check_swiglu(hip_backend, oracle, K0, K, F, values)
+
+
+def _check_swiglu(hip_backend, oracle, K0, K, F, values="positive"):
     """Both hand-overs in one chain, as a decoder layer has them: projection -> residual add -> rmsnorm -> mul(gamma) -> gate / up
     -> SiLU chain -> silu * up -> down projection. Three launches: the first prepares the second's norm, the second is a gate / up
     PAIR launch that consumes it (every workgroup also stores a slice of the normalised vector and of its product with gamma), the
@@ -427,7 +484,7 @@ def test_swiglu_half_with_prepared_norm_and_pair_stores_every_intermediate(hip_b
     ]
     prog = DeviceProgram(ops=ops, buffer_sizes=sizes,
                          initial_uploads=[ProgramIO(B["xin"], xin), ProgramIO(B["resid"], resid), ProgramIO(B["gamma"], gamma), ProgramIO(B["one"], one)],
-                         qweights=[_q4_weight(rng, K0, K), _q4_weight(rng, K, F), _q4_weight(rng, K, F), _q4_weight(rng, F, K)])
+                         qweights=[_q4_weight(rng, K0, K, values), _q4_weight(rng, K, F, values), _q4_weight(rng, K, F, values), _q4_weight(rng, F, K, values)])
     h = hip_backend.compileProgram(prog)
     assert h
     try:

@@ -54,6 +54,27 @@ def test_w8a8_matvec_is_bit_identical_to_the_reference_arm(w8a8, oracle, K, N, k
         assert np.array_equal(got2[5:5 + N].view(np.uint32), want.view(np.uint32)) and np.all(got2[:5] == -7)
 
 
+@pytest.mark.parametrize("profile", ["gguf", "negated"])
+@pytest.mark.parametrize("kind", ["q4_f16", "q8_f32"])
+@pytest.mark.parametrize("K,N", [(64, 16), (576, 192)])
+def test_w8a8_matvec_over_signed_scales_is_bit_identical_to_the_reference_arm(w8a8, oracle, K, N, kind, profile):
+    """The arm re-quantises scale * q per (column, 32 k): over GGUF-like weights (scales of either sign over many binades, the
+    stored nibble 0 in every block) and over all-negative scales (tests/weight_cases.py), still array equality with the oracle's
+    arm. tests/test_weight_cases_host.py holds the arm's own sign symmetry and its distance from the exact path on these values."""
+    from tests import weight_cases as WC
+    assert (K, N) in WC.W8A8_SHAPES and kind in WC.W8A8_KINDS and profile in WC.W8A8_PROFILES
+    x = np.random.default_rng(0x8A8 + K + 3 * N).standard_normal(K).astype(f32)
+    data, scales = WC.w8a8_weight(profile, kind, K, N)
+    t_data, t_scales = oracle.prepare_transposed(data, scales, K, N, 32)
+    want = oracle.gemv(t_data, t_scales, x, N, K, 32)
+    got = _run(w8a8, oracle, data, scales, x, N, K)
+    assert not w8a8.last_error(), w8a8.last_error()
+    assert np.array_equal(got[:N].view(np.uint32), want.view(np.uint32)), np.abs(got[:N] - want).max()
+    assert np.all(got[N:] == -7)
+    exact = oracle.qmatmul_exact(data, scales, x, 1, N, K, 32)
+    assert np.any(got[:N] != exact)  # (the arm ran, not the exact mat-vec)
+
+
 def test_w8a8_is_not_the_exact_arithmetic_and_odd_shapes_keep_the_exact_path(w8a8, hip_backend, oracle):
     rng = np.random.default_rng(5)
     K, N = 576, 192
