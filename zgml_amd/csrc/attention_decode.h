@@ -4,7 +4,7 @@
 // translation unit gets its own copy.
 #pragma once
 #include "kernels.h"
-
+#include "handoff_gen.h"
 #include <hip/hip_fp16.h>
 #include <math.h>
 
@@ -265,28 +265,28 @@ __device__ __forceinline__ float slots_all(float v) {
     return v;
 }
 
-// A launch that also holds the workgroups of the q / k / v projection (qmatvec.hip: fused launch) hands the projections
-// over through agent-scope counters instead of a kernel boundary: one counter per 64-column... per head slice of each
-// projection, bumped once by every column group (16 columns) that has stored its outputs with write-through stores. The
-// attention issues everything that does not depend on the projections first, then waits (bounded) for its head's three
-// counters to pass `seen + need`, remembers the new values in its private `seen` words (kv heads have several consumers,
-// so the shared counters are never reset) and reads q / k / v with agent-scope loads.
+// A launch that also holds the workgroups of the q / k / v projection (qmatvec.hip: qkv_attn_kernel, 1024-thread workgroups) hands the
+// projections over as data-tagged granules instead of a kernel boundary: the owning lanes store every output as one 8-byte {value,
+// generation} granule (handoff_gen.h; the data IS the flag: no counter, no drain, no fence). The attention issues all that does not
+// depend on the projections, then ONE wave sweeps the head's 3 d_head granules (bounded) until every tag carries this execution's
+// generation and hands the values on through LDS. The 256-thread launch of K-on-lanes weights keeps counters (CounterHandoff).
 struct DecodeHandoff {
-    const uint32_t* cnt; // [n_heads | n_kv | n_kv] monotonic counters
-    uint32_t* seen;      // [workgroups of the attention part][3]
-    const uint32_t* idx; // [records][3]: the q / k / v counters of each record's head (records need not be in head order)
+    const unsigned long long* gran; // [(n_heads + 2 n_kv) d_head] granules: q, then k, then v columns; zeroed once, never reset
+    uint32_t rel[3];     // a record's slice starts 2 * low32(its pointer) + rel[c] bytes into `gran`, mod 2^32 (derived at launch_qkv_attention)
+    uint32_t* gen;       // [workgroups of the attention part] private generation words, zeroed once
     uint32_t n_heads;
-    uint32_t need;       // column groups per head slice = d_head / 16
-    uint32_t* timeout;   // bumped when a wait gives up
-    uint32_t poll_sleep; // s_sleep(1) units (64 clocks) between two polls
+    uint32_t* timeout;   // set when a wait gives up
+    uint32_t poll_sleep; // s_sleep(1) units (64 clocks) between two sweeps
 };
-
-// BLOCK: threads of the workgroup that runs the body (1024 stand-alone; 256 inside the fused launch of K-on-lanes weights,
-// whose workgroups are 4 waves): at most BLOCK / 64 waves work on a chunk of keys, the loop over steps covers the rest
-template <int LPK, bool KVQ, int BLOCK = kAttnBlock>
+__device__ __forceinline__ void handoff_idle(const DecodeHandoff* ho, uint32_t wg, uint32_t gen) { ho->gen[wg] = gen; } // (an idle split moves its private words on with the producers)
+__device__ __forceinline__ void handoff_idle(const CounterHandoff* ho, uint32_t wg, uint32_t) { for (int c = 0; c < 3; c++) ho->seen[3 * wg + c] += ho->need; }
+__device__ __forceinline__ void handoff_done(const DecodeHandoff* ho, uint32_t wg, uint32_t gen, const uint32_t (&)[3]) { ho->gen[wg] = gen; }
+__device__ __forceinline__ void handoff_done(const CounterHandoff* ho, uint32_t wg, uint32_t, const uint32_t (&t)[3]) { for (int c = 0; c < 3; c++) ho->seen[3 * wg + c] = t[c]; } // (a finished one stores what it waited for)
+// BLOCK: threads of the workgroup that runs the body (1024 stand-alone; 256 inside the fused launch of K-on-lanes weights): at most BLOCK / 64 waves work on a chunk of keys
+template <int LPK, bool KVQ, int BLOCK = kAttnBlock, typename HO = DecodeHandoff> // HO: the hand-off form of a fused launch (nullptr: stand-alone)
 __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __restrict__ params, float* split_buf, uint32_t* split_cnt,
-                                                      uint32_t split_min_keys, const uint32_t hx, const uint32_t sp_in, const uint32_t n_sp,
-                                                      const DecodeHandoff* ho) {
+                                                      uint32_t split_min_keys, const uint32_t hx, const uint32_t sp_in, const uint32_t n_sp, const HO* ho) {
+    constexpr bool COUNTERS = std::is_same<HO, CounterHandoff>::value;
     constexpr int DH = 4 * LPK, HALF = DH / 2;
     // Q16: quantised KV with 16 dims per lane in the key loop (LPKM lanes per key there); KPW4 / LPK stay the mapping of the
     // ropes, the stores, the wave merge and the split merge
@@ -335,6 +335,7 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
     constexpr int COLV = DH / 4 + DH / 32; // Q16: the new K column's words and block scales, then the V column's
     __shared__ __attribute__((aligned(16))) float q16_lds[Q16 ? DH : 4];
     __shared__ __attribute__((aligned(16))) uint32_t col_lds[Q16 ? 2 * COLV : 4];
+    __shared__ __attribute__((aligned(16))) float qkv_lds[3 * DH]; // fused launch: the swept q / k / v slices of this head (unused, and dropped, in the stand-alone kernel)
     const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const uint32_t slot = lane / LPK, li = lane % LPK, d0 = 4 * li, pair = d0 & (HALF - 1);
     const bool is_hi = d0 >= (uint32_t)HALF;
@@ -344,8 +345,7 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
     const uint32_t d2_off = p.dst2 ? ldgu(p.dyn_dst2_off) : 0; // scalar, with the other dynamic words
     // (a fused launch reads the projections' outputs only after the hand-off below; `ho` is a literal nullptr in the
     // stand-alone kernel, so nothing here is a run-time branch there)
-    // (a hand-off record WITHOUT counters would mean that the projections come from an earlier launch: plain loads, no wait)
-    const bool wait_qkv = ho && ho->cnt;
+    const bool wait_qkv = ho != nullptr;
     float4 q_own, q_par, k_own, k_par, v_new;
     if (!wait_qkv) {
         q_own = ldg4(P.q_src + d0), q_par = ldg4(P.q_src + (d0 ^ HALF));
@@ -358,14 +358,14 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
     // this workgroup's keys [k_begin, k_end)
     const uint32_t sp = sp_in;
     uint32_t n_active = 1, k_begin = 0, k_end = seq_kv;
+    // fused launch: the generation this execution's granules carry (the workgroup's private word, written back at the end)
+    uint32_t gen = 0;
+    if constexpr (!COUNTERS) gen = wait_qkv ? handoff_next_gen(ho->gen[hx * n_sp + sp]) : 0;
     if (n_sp > 1) {
         n_active = seq_kv / split_min_keys;
         n_active = n_active < 1 ? 1 : (n_active > n_sp ? n_sp : n_active);
-        if (sp >= n_active) { // (a fused launch: an idle split still moves its private `seen` words with the counters)
-            if (wait_qkv && tid == 0) {
-                uint32_t* const seen = ho->seen + (hx * n_sp + sp) * 3;
-                seen[0] += ho->need, seen[1] += ho->need, seen[2] += ho->need;
-            }
+        if (sp >= n_active) { // (a fused launch: an idle split still moves its private generation with the producers')
+            if (wait_qkv && tid == 0) handoff_idle(ho, hx * n_sp + sp, gen); // (counter form: its `seen` words move with the counters)
             return;
         }
         const uint32_t chunk = (seq_kv + n_active - 1) / n_active;
@@ -439,8 +439,8 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
             mk[j] = ldg1(p.mask + (uint64_t)s * p.mask_rs); // host passes a zero word with stride 0 when there is no mask
         }
     }
-    uint32_t target[3] = {0, 0, 0}; // fused launch: the counter values this execution waits for (written back at the end)
-    if (wait_qkv) { // ---- hand-off: the q / k / v column groups of this head have been stored (DecodeHandoff)
+    uint32_t target[3] = {0, 0, 0}; // counter form: the counter values this execution waits for (written back at the end)
+    if constexpr (COUNTERS) { // ---- hand-off, counter form: the q / k / v column groups of this head have been stored (CounterHandoff)
         const uint32_t ci[3] = {ho->idx[3 * hx], ho->idx[3 * hx + 1], ho->idx[3 * hx + 2]};
         const uint32_t* const seen = ho->seen + (hx * n_sp + sp) * 3;
 #pragma unroll
@@ -471,6 +471,49 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
         q_own = ld_agent4(P.q_src + d0), q_par = ld_agent4(P.q_src + (d0 ^ HALF));
         k_own = ld_agent4(P.k_src + d0), k_par = ld_agent4(P.k_src + (d0 ^ HALF));
         v_new = ld_agent4(P.v_src + d0);
+    } else if (wait_qkv) { // ---- hand-off: the q / k / v granules of this head carry this execution's generation (DecodeHandoff)
+        if (w == 0) { // ONE wave sweeps (16 waves would pull 16 x the granules through this CU's memory path per sweep), the others wait at the barrier
+            constexpr int PER = DH / 64 > 0 ? DH / 64 : 1, NG = 3 * PER; // granules per lane and slice / per lane (the fused launches: d_head 64 / 128)
+            static_assert(DH % 64 == 0 || DH < 64, "a slice is swept by whole waves");
+            // the record's slices from its pointers (records need not be in head order); every access to the granule area is an
+            // agent-scope 8-byte load on the vector path
+            // (addresses: ONE base + a 32-bit byte offset per slice, wave-uniform, + ONE 32-bit byte offset per lane; the offsets are
+            // exact mod 2^32 because the area is far smaller than 4 GB: DecodeHandoff::rel)
+            typedef const __attribute__((address_space(1))) char* gbytes;
+            const gbytes g0 = (gbytes)ho->gran;
+            const gbytes gs[3] = {g0 + (2u * (uint32_t)(uintptr_t)P.q_src + ho->rel[0]), g0 + (2u * (uint32_t)(uintptr_t)P.k_src + ho->rel[1]),
+                                  g0 + (2u * (uint32_t)(uintptr_t)P.v_src + ho->rel[2])};
+            const bool in_slice = DH >= 64 || lane < (uint32_t)DH;
+            const uint32_t lane8 = in_slice ? 8u * lane : 0u;
+            uint32_t spins = 0;
+            for (;;) {
+                bool ok = true;
+#pragma unroll
+                for (int k = 0; k < NG; k++) { // every granule again in every sweep: a value is only taken with its own tag
+                    const unsigned long long x = __hip_atomic_load((const gu64*)(gs[k / PER] + lane8) + 64 * (k % PER), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    // (straight to LDS, sweep after sweep — the last one's values stay: nothing swept is held in registers beside the K / V rows)
+                    if (in_slice) qkv_lds[(k / PER) * DH + 64 * (k % PER) + lane] = __uint_as_float(handoff_granule_value(x));
+                    ok = ok && handoff_granule_gen(x) == gen;
+                }
+                if (__builtin_amdgcn_ballot_w64(!ok) == 0) break; // (wave-uniform)
+                if (++spins > 400000u) { // bounded: never hang the device; the caller sees the flag
+                    if (tid == 0) __hip_atomic_store(ho->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // host-visible word (runtime.hip: handoff_ok)
+                    break;
+                }
+                for (uint32_t z = 0; z < ho->poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        // an LDS-only barrier (__syncthreads() would also wait for the K / V rows in flight); a single wave reads behind its own
+        // writes (the DS operations of a wave complete in order). Waves >= NW have retired and do not count.
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (NW > 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#endif
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        q_own = *(const float4*)&qkv_lds[d0], q_par = *(const float4*)&qkv_lds[d0 ^ HALF];
+        k_own = *(const float4*)&qkv_lds[DH + d0], k_par = *(const float4*)&qkv_lds[DH + (d0 ^ HALF)];
+        v_new = *(const float4*)&qkv_lds[2 * DH + d0];
     }
     ATTN_STAMP(2);
     // ---- ropes; side outputs and the cache stores (one lane group writes each value)
@@ -697,10 +740,7 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
         ATTN_STAMP(6);
     }
     { // wave 0 from here on
-        if (wait_qkv && lane == 0) { // every wave of this workgroup has passed the hand-off (merge barrier above / single wave)
-            uint32_t* const seen = ho->seen + (hx * n_sp + sp) * 3;
-            seen[0] = target[0], seen[1] = target[1], seen[2] = target[2];
-        }
+        if (wait_qkv && lane == 0) handoff_done(ho, hx * n_sp + sp, gen, target); // (also after a give-up: the state stays in step with the producers')
         if (n_active > 1) { // publish this chunk; the last arriver merges all of them
             constexpr uint32_t REC = DH + 4; // m, l, pad, pad, acc[DH]
             float* const head_buf = split_buf + (uint64_t)hx * n_sp * REC;
@@ -747,7 +787,7 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
 template <int LPK, bool KVQ, int BLOCK = kAttnBlock>
 __global__ void __launch_bounds__(BLOCK) attention_decode_kernel(const AttnDecodeParams* __restrict__ params, float* split_buf,
                                                                  uint32_t* split_cnt, uint32_t split_min_keys) {
-    attention_decode_body<LPK, KVQ, BLOCK>(params, split_buf, split_cnt, split_min_keys, blockIdx.x, blockIdx.y, gridDim.y, nullptr);
+    attention_decode_body<LPK, KVQ, BLOCK>(params, split_buf, split_cnt, split_min_keys, blockIdx.x, blockIdx.y, gridDim.y, (const DecodeHandoff*)nullptr);
 }
 
 } // namespace

@@ -726,13 +726,24 @@ bool qmv_can_group(const QWeightDev& a, const QWeightDev& b);
 // Prologue kinds other than NONE keep the whole input in registers: K <= qmv_max_prologue_k(w).
 uint32_t qmv_max_prologue_k(const QWeightDev& w);
 void launch_qmatvec_fused(hipStream_t s, const QmvLaunch& L);
-// q / k / v projection (grouped, rmsnorm prologue, K <= 2048) + the decode attention of its heads in ONE launch; the
-// projection's outputs are handed over through `counters` ([n_heads + 2 n_kv] words; `idx` [n_heads][3] names each record's
-// q / k / v counter) with `seen` ([n_heads * splits * 3]) as the consumers' private progress words; counters and seen
-// zero-initialised by the caller. false: not fusable, nothing launched.
+// q / k / v projection (grouped, rmsnorm prologue) + the decode attention of its heads in ONE launch; the projection's outputs are
+// handed over inside the launch through a block the caller owns, zero-initialised ONCE and never again (its state runs on across
+// executions and graph replays). Two forms, by the kernel the weights select:
+//   granules (n-on-lanes weights, K <= 2048, 1024-thread workgroups): `granules` [(n_heads + 2 n_kv) * d_head] 8-byte {value, generation}
+//     words at the start of a hipMalloc'ed block, so that a column group's 16 are one 128-byte line (q columns, then k, then v), with
+//     `producer_gen` [column groups of the projection] and `consumer_gen` [n_heads * splits] as the two sides' generation words (handoff_gen.h);
+//   counters (K-on-lanes weights, 256-thread workgroups): `counters` [32 * (n_heads + 2 n_kv)] words, `idx` [n_heads][3] naming each record's
+//     q / k / v counter, `seen` [n_heads * splits * 3] as the consumers' private progress words.
+// false: not fusable (or the block is not of the kernel's form), nothing launched.
+struct QkvHandoffBlock {
+    unsigned long long* granules = nullptr;
+    uint32_t *producer_gen = nullptr, *consumer_gen = nullptr;
+    uint32_t* counters = nullptr;
+    const uint32_t* idx = nullptr;
+    uint32_t* seen = nullptr;
+};
 bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t n_kv, uint32_t d_head,
-                          const AttnSplit& sp, uint32_t* counters, const uint32_t* idx, uint32_t* seen, uint32_t* timeout,
-                          bool kvq = false);
+                          const AttnSplit& sp, const QkvHandoffBlock& hb, uint32_t* timeout, bool kvq = false);
 int qkv_attn_kon_census(hipStream_t s, uint32_t d_head, bool kvq, uint32_t grid); // 1 = the whole grid of that launch is co-resident (run once, plan-build time), 0 = not, -1 = unknown
 int qkv_attn_kon_blocks_per_cu(uint32_t d_head, bool kvq); // fused q / k / v + attention launch of K-on-lanes weights (256-thread workgroups) // occupancy query of that kernel
 // Deterministic synthetic weights for the roofline micro-benchmark, generated on the device

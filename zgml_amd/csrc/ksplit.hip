@@ -253,13 +253,14 @@ struct KsProjArgs {
 };
 // The hand-off of a launch that also holds the attention's workgroups (ks_layer_a_kernel): the owning lanes store the outputs
 // write-through (agent scope), the wave drains, lane 0 bumps the counter of the head slice the workgroup's columns belong to
-// (the protocol of qmatvec.hip's QmvPublish / attention_decode.h's DecodeHandoff: monotonic counters, consumers keep private
-// `seen` words, every wait bounded).
+// (monotonic counters, consumers keep private `seen` words, every wait bounded: the counter protocol the fused q / k / v +
+// attention launches of qmatvec.hip used before their data-tagged granules; this opt-in path keeps it).
 struct KsPublish {
     uint32_t* cnt;         // [n_heads | n_kv | n_kv] counters, 32 words apart
     uint32_t base[3];      // first counter of q / k / v
     uint32_t groups_shift; // log2(d_head / 16): column group -> head slice
 };
+using KsHandoff = CounterHandoff; // the consumer's side: the counter form of handoff_gen.h
 template <int GP, int U>
 __device__ __forceinline__ void ks_proj_body(const KsProjArgs& a, float* smem, const KsPublish* pub) {
     const uint32_t T = a.n_threads ? a.n_threads : blockDim.x, W = T >> 6, b = blockIdx.x;
@@ -433,7 +434,7 @@ struct KsAttnArgs {
 };
 constexpr int kKsAttnBlock = 768; // 12 waves: 168 registers per lane hold the attention's double-buffered rows AND the head's W_o units (16 waves: 128, spills)
 template <int LPK, bool KVQ, int UO>
-__device__ __forceinline__ void ks_attn_o_body(const KsAttnArgs& f, const uint32_t hx, const uint32_t sp, const DecodeHandoff* ho) {
+__device__ __forceinline__ void ks_attn_o_body(const KsAttnArgs& f, const uint32_t hx, const uint32_t sp, const KsHandoff* ho) {
     constexpr int DH = 4 * LPK, KPW = 64 / LPK, U = kAttnUnroll, HALF = DH / 2, CH = DH / 32, BLOCK = kKsAttnBlock;
     static_assert(DH % 32 == 0, "the head's rows of W_o are whole 32-k chunks");
     using Row = AttnRow<KVQ>;
@@ -547,7 +548,7 @@ __device__ __forceinline__ void ks_attn_o_body(const KsAttnArgs& f, const uint32
     }
     KS_STAMP(ts, 2); // every load issued
     uint32_t target[3] = {0, 0, 0}; // fused launch: the counter values this execution waits for (written back at the end)
-    if (ho) { // ---- hand-off: the q / k / v column groups of this head have been stored (attention_decode.h: DecodeHandoff)
+    if (ho) { // ---- hand-off: the q / k / v column groups of this head have been stored (KsHandoff)
         const uint32_t ci[3] = {ho->idx[3 * hx], ho->idx[3 * hx + 1], ho->idx[3 * hx + 2]};
         const uint32_t* const seen = ho->seen + (hx * n_sp + sp) * 3;
 #pragma unroll
@@ -772,7 +773,7 @@ struct KsLayerAArgs {
     KsProjArgs pj;
     KsAttnArgs at;
     KsPublish pub;
-    DecodeHandoff ho;
+    KsHandoff ho;
     uint32_t n_proj, n_heads;
     uint32_t dbg; // diagnostics build: 1 = the attention's workgroups exit at once, 2 = they skip the wait (timing only: wrong results)
 };
@@ -949,7 +950,7 @@ bool launch_ks_layer_a(hipStream_t s, const KsProjLaunch& PL, const KsAttnOLaunc
     uint32_t shift = 0;
     while ((16u << shift) < AL.d_head) shift++;
     g.pub = KsPublish{counters, {0, AL.n_heads, AL.n_heads + n_kv}, shift};
-    g.ho = DecodeHandoff{counters, seen, idx, AL.n_heads, (AL.d_head / 16) / 2, timeout, (uint32_t)sw().hip_handoff_sleep};
+    g.ho = KsHandoff{counters, seen, idx, AL.n_heads, (AL.d_head / 16) / 2, timeout, (uint32_t)sw().hip_handoff_sleep};
     g.n_proj = wgs, g.n_heads = AL.n_heads;
     g.dbg = (uint32_t)sw().ks_debug_a;
     using Fn = void (*)(KsLayerAArgs);

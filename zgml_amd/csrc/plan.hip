@@ -581,12 +581,12 @@ bool anchor_ok(zgml_hip_program* p, uint32_t i) {
 }
 
 // A grouped q / k / v projection launch directly followed by the decode-attention launch of exactly its heads becomes ONE
-// launch (qmatvec.hip: qkv_attn_kernel): the projection's outputs reach the attention through
-// per-head-slice counters instead of a kernel boundary, and everything the attention can do without them overlaps the
-// projection. Only for the shapes that kernel is built for (short K, Q4_0 with f16 scales, d_head 64 / 128, f32 KV).
+// launch (qmatvec.hip: qkv_attn_kernel): the projection's outputs reach the attention as data-tagged
+// 8-byte granules (K-on-lanes weights: through per-head-slice counters) instead of through a kernel boundary, and everything the attention can do without them overlaps the
+// projection. Only for the shapes that kernel is built for (short K, Q4_0 with f16 scales, d_head 64 / 128, f32 or int8 KV).
 void fuse_qkv_attention(zgml_hip_program* p) {
     if (!sw().hip_fuse_qkv_attn || p->ctx->fuse_qkv_off || !p->ctx->handoff_flag_dev) return; // (off for good once a hand-off wait has timed out in this context)
-    // Residency: the attention's workgroups spin on counters the projection's workgroups of the SAME grid bump, and HIP
+    // Residency: the attention's workgroups spin on granules (or counters) the projection's workgroups of the SAME grid write, and HIP
     // promises neither dispatch order nor co-residency. The launch is only built when the whole grid (1024-thread workgroups)
     // fits the device at ONE workgroup per CU — the occupancy query may say two, but it reads one high near a register-file
     // edge (guide: residency and cooperative launch) and a stranded producer would mean a time-out, not a slowdown; the
@@ -609,7 +609,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         ok = ok && (uint64_t)nh * dh == L.parts[0].w.N && L.parts[1].w.N == L.parts[2].w.N && L.parts[1].w.N % dh == 0;
         const uint32_t n_kv = ok ? (uint32_t)(L.parts[1].w.N / dh) : 0;
         ok = ok && n_kv != 0 && nh % n_kv == 0;
-        std::vector<uint32_t> idx(3 * (size_t)nh);
+        std::vector<uint32_t> idx(3 * (size_t)nh); // (counter form: each record's q / k / v counter)
         std::vector<char> head_seen(nh, 0);
         for (uint32_t r = 0; ok && r < nh; r++) { // the records are not in head order: each one's head from its pointers
             const AttnDecodeParams& a = ad->host[r];
@@ -619,7 +619,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
             if (!ok) break;
             const uint32_t h = (uint32_t)(qo / dh), kvh = (uint32_t)(ko / dh);
             ok = !head_seen[h] && kvh == h / (nh / n_kv);
-            head_seen[h] = 1;
+            head_seen[h] = 1; // (granule form: the kernel finds the record's granules from the same pointer differences, DecodeHandoff)
             idx[3 * r] = h, idx[3 * r + 1] = nh + kvh, idx[3 * r + 2] = nh + n_kv + kvh;
         }
         if (!ok) continue;
@@ -659,24 +659,37 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         // (The O projection — the single-matrix launch that reads exactly the heads' row stores — does NOT ride along. Measured: 93
         // launches per SmolLM-135M token instead of 123, parity green, and SLOWER — 1714-1734 against 1772 tok/s: that edge is
         // all-to-all (every column group of the projection needs every head), its hand-off costs more than the boundary it replaces.)
-        const size_t n_cnt = 32 * ((size_t)nh + 2 * n_kv); // one counter per 128 bytes
-        const size_t words = n_cnt + (size_t)nh * n_sp * 3 + 1 + 3 * (size_t)nh;
-        uint32_t* block = nullptr;
-        if (hipMalloc((void**)&block, words * 4) != hipSuccess) continue;
-        if (memset_sync(p->ctx->stream, block, 0, words * 4) != hipSuccess) {
+        // the launch's hand-off block, zeroed ONCE (its state runs on across executions and graph replays). Granule form (handoff_gen.h):
+        // [(nh + 2 n_kv) * dh granules of 8 bytes: a column group's 16 are one 128-byte line (hipMalloc aligns to 256)]
+        // [one generation word per projection column group] [one per attention workgroup]
+        // Counter form (the K-on-lanes launch: CounterHandoff): [one counter per 128 bytes] [3 `seen` words per attention workgroup] [idx]
+        const size_t n_gran = ((size_t)nh + 2 * n_kv) * dh, n_cnt = 32 * ((size_t)nh + 2 * n_kv);
+        const size_t bytes = kon ? (n_cnt + (size_t)nh * n_sp * 3 + 1 + idx.size()) * 4 : (n_gran * 8 + (n_mv + (size_t)nh * n_sp) * 4 + 15) / 16 * 16;
+        void* block = nullptr;
+        if (hipMalloc(&block, bytes) != hipSuccess) continue;
+        if (memset_sync(p->ctx->stream, block, 0, bytes) != hipSuccess) {
             hipFree(block);
             continue;
         }
         p->fuse_owned.push_back(block); // (freed by the next build_plan, after its stream sync)
-        uint32_t *counters = block, *seen = block + n_cnt, *timeout = p->ctx->handoff_flag_dev, *idx_dev = seen + (size_t)nh * n_sp * 3 + 1;
-        if (h2d_sync(p->ctx->stream, idx_dev, idx.data(), idx.size() * 4) != hipSuccess) continue;
+        uint32_t* const timeout = p->ctx->handoff_flag_dev;
+        QkvHandoffBlock hb;
+        if (kon) {
+            hb.counters = (uint32_t*)block, hb.seen = hb.counters + n_cnt;
+            uint32_t* const idx_dev = hb.seen + (size_t)nh * n_sp * 3 + 1;
+            if (h2d_sync(p->ctx->stream, idx_dev, idx.data(), idx.size() * 4) != hipSuccess) continue;
+            hb.idx = idx_dev;
+        } else {
+            hb.granules = (unsigned long long*)block;
+            hb.producer_gen = (uint32_t*)(hb.granules + n_gran), hb.consumer_gen = hb.producer_gen + n_mv;
+        }
         const AttnDecodeParams* d = ad->dev;
         AttnSplit sp = ad->sp;
         sp.splits = n_sp; // (possibly fewer than the stand-alone launch would use: the residency guard above)
         const uint32_t n_ops = p->plan[i].n_ops + p->plan[i + 1].n_ops, lo = std::min(p->plan[i].op_lo, p->plan[i + 1].op_lo),
                        hi = std::max(p->plan[i].op_hi, p->plan[i + 1].op_hi);
         Launch F{ZGML_DOP_QMATMUL, n_ops, lo, hi, [=](hipStream_t s) {
-                     if (!launch_qkv_attention(s, L, d, nh, n_kv, dh, sp, counters, idx_dev, seen, timeout, kvq)) {
+                     if (!launch_qkv_attention(s, L, d, nh, n_kv, dh, sp, hb, timeout, kvq)) {
                          launch_qmatvec_fused(s, L);
                          launch_attention_decode_batch(s, d, nh, dh, sp, kvq);
                      }
@@ -1887,7 +1900,7 @@ void build_plan(zgml_hip_program* p) {
                          std::to_string(p->kon_max_m) + " mat-vecs (K-on-lanes layout)");
     }
     free_param_blobs(p);
-    for (void* d : p->fuse_owned) hipFree(d); // counters / seen / idx of the previous plan's fused launches
+    for (void* d : p->fuse_owned) hipFree(d); // hand-off blocks (granules + generation words, or counters / seen / idx) of the previous plan's fused launches
     p->fuse_owned.clear();
     p->fuse_epoch = p->ctx->fuse_epoch;
     p->split_buf = nullptr, p->split_cnt = nullptr, p->split_buf_floats = 0, p->split_cnt_words = 0; // lived in the blobs

@@ -211,9 +211,17 @@ __device__ __forceinline__ void run_epilogue(const QMVPartDev& part, uint32_t n,
 }
 
 // A launch that also holds the decode attention's workgroups (qkv_attn_kernel below) hands the projections over without a
-// kernel boundary: the 16 owning lanes store their outputs write-through (agent scope), the wave drains, and lane 0 bumps
-// the counter of the head slice this column group belongs to (attention_decode.h: DecodeHandoff).
+// kernel boundary: each of the 16 owning lanes stores its output as ONE 8-byte {value, generation} granule (agent scope; a
+// column group's 16 granules are one 128-byte line) next to the plain store into the projection's own buffer — no counter,
+// no drain, no fence: the attention takes a value only with its tag (attention_decode.h: DecodeHandoff, handoff_gen.h).
 struct QmvPublish {
+    unsigned long long* gran; // [all columns of q, k, v] granules
+    uint32_t* gen;            // [column groups of the launch] private generation words: read at kernel start, written back at the end
+    uint32_t drop;            // diagnostics (ZGML_HIP_DEBUG_DROP_PUBLISH=1): column group 0 of part 0 stores no granules — its consumers time out
+};
+// ... and the counter form the 256-thread launch of K-on-lanes weights keeps (handoff_gen.h: CounterHandoff): the 16 owning lanes store
+// their outputs write-through (agent scope), the wave drains, and lane 0 bumps the counter of the head slice the column group belongs to
+struct QmvCountPublish {
     uint32_t* cnt;         // [n_heads | n_kv | n_kv]
     uint32_t base[3];      // first counter of part 0 / 1 / 2 (q, k, v)
     uint32_t groups_shift; // log2(d_head / 16): column group -> head slice
@@ -297,10 +305,10 @@ __device__ __forceinline__ float kon_factor_and_slices(const KonTail& kt, const 
     }
     return inv;
 }
-template <bool GROUPED, bool KON = false>
+template <bool GROUPED, bool KON = false, typename PUB = QmvPublish>
 __device__ __forceinline__ void reduce_store(float acc, float* red, const QMVArgs& a, uint32_t pi, float* out0, uint32_t g, uint32_t m,
-                                             float pre0, bool have_pre0, uint32_t n_waves, const QmvPublish* pub = nullptr, const KonTail* kon = nullptr,
-                                             float pre_g = 0.f) {
+                                             float pre0, bool have_pre0, uint32_t n_waves, const PUB* pub = nullptr, const KonTail* kon = nullptr,
+                                             float pre_g = 0.f, uint32_t pub_cg = 0, uint32_t pub_gen = 0) { // (pub: this workgroup's column group in the launch and this execution's generation)
     const uint32_t lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (!KON) {
         acc = rows_sum4(acc);
@@ -342,10 +350,17 @@ __device__ __forceinline__ void reduce_store(float acc, float* red, const QMVArg
             if (GROUPED) out_rs = pi == 1 ? a.parts[1].out_rs : pi == 2 ? a.parts[2].out_rs : pi == 3 ? a.parts[3].out_rs : out_rs;
             out_row = out + (uint64_t)m * out_rs;
         }
-        if (pub) // (fused launches carry no epilogues on these parts: planner)
-            __hip_atomic_store((__attribute__((address_space(1))) float*)out_row + n, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
+        constexpr bool COUNTERS = std::is_same<PUB, QmvCountPublish>::value;
+        if constexpr (COUNTERS) {
+            if (pub) // (fused launches carry no epilogues on these parts: planner)
+                __hip_atomic_store((__attribute__((address_space(1))) float*)out_row + n, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                out_row[n] = v;
+        } else {
+            if (pub && !(pub->drop && pub_cg == 0)) // the granule first: the attention of this launch waits for it (fused launches carry no epilogues on these parts: planner)
+                __hip_atomic_store((gu64*)pub->gran + (pub_cg * 16 + lane), handoff_granule(__float_as_uint(v), pub_gen), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             out_row[n] = v;
+        }
         if (GROUPED && kind == kEpiSilu) {
             if (pi == 0)
                 run_epilogue_silu(a.parts[0], n, v, ones);
@@ -374,13 +389,17 @@ __device__ __forceinline__ void reduce_store(float acc, float* red, const QMVArg
         else
             run_epilogue(a.parts[3], n, v, out_row);
     }
-    if (pub) {
+    if constexpr (std::is_same<PUB, QmvCountPublish>::value) {
+        if (pub) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the write-through stores of this wave's 16 lanes have left
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the write-through stores of this wave's 16 lanes have left
 #endif
-        if (lane == 0 && !(pub->drop && pi == 0 && g == 0))
-            __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t*)pub->cnt + 32 * (pub->base[pi < 3 ? pi : 2] + (g >> pub->groups_shift)), 1u,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0 && !(pub->drop && pi == 0 && g == 0))
+                __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t*)pub->cnt + 32 * (pub->base[pi < 3 ? pi : 2] + (g >> pub->groups_shift)), 1u,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else {
+        if (pub && lane == 0) pub->gen[pub_cg] = pub_gen; // (a dropped publish too: the generations stay in step with the consumers')
     }
 }
 
@@ -693,6 +712,9 @@ __device__ __forceinline__ void qmatvec_body(QMV_HEAD_PARAMS, const QMVArgs& a, 
     // Llama-2-7B unchanged). Unconditional: under `if (K <= 2048)` the scalar loads sit behind a branch and the counted
     // waits of the whole kernel degrade (-5 %). Fetching the whole descriptor block into SGPRs with three
     // s_load_dwordx16 under the cross-wave fold gave nothing on top of this.
+    // fused launch: this column group's private generation word, requested under the weight stream (no other workgroup writes it)
+    uint32_t pub_gen = 0;
+    if (pub) pub_gen = __hip_atomic_load((gu32*)pub->gen + (block_begin + g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint32_t arg_touch = 0;
 #if defined(__HIP_DEVICE_COMPILE__) // (the builtin's pointer type differs in the host pass)
     {
@@ -766,7 +788,8 @@ __device__ __forceinline__ void qmatvec_body(QMV_HEAD_PARAMS, const QMVArgs& a, 
         __syncthreads();
         if (w == 0) kon_pair_finish(red, a, out0, g, n_waves, ptail, ones);
     } else {
-        reduce_store<GROUPED>((acc0 + acc1) + (acc2 + acc3), red, a, pi, out0, g, m, pre0, have_pre0, n_waves, pub, PROM == 2 ? &ptail : nullptr, pre_g);
+        reduce_store<GROUPED>((acc0 + acc1) + (acc2 + acc3), red, a, pi, out0, g, m, pre0, have_pre0, n_waves, pub, PROM == 2 ? &ptail : nullptr, pre_g,
+                             block_begin + g, handoff_next_gen(pub_gen));
     }
     QMV_STAMP(5);
 #undef QMV_STAMP
@@ -896,7 +919,7 @@ __device__ __forceinline__ void kon_pair_finish(const float* red, const QMVArgs&
 }
 
 template <int DEPTH, int PROM, bool GROUPED, bool XV, bool NT, bool PAIR = false>
-__device__ __forceinline__ void qmatvec_kon_body(QMV_HEAD_PARAMS, const QMVArgs& a, const uint32_t bx, const uint32_t n_blocks, const QmvPublish* pub) {
+__device__ __forceinline__ void qmatvec_kon_body(QMV_HEAD_PARAMS, const QMVArgs& a, const uint32_t bx, const uint32_t n_blocks, const QmvCountPublish* pub) {
     constexpr bool PRO = PROM == 1;
     extern __shared__ float smem[];
     float* red = smem; // kMaxWaves * 16 column sums + kMaxWaves sums of squares (PAIR: the second matrix's sums from row kMaxWaves + 1)
@@ -1054,7 +1077,7 @@ __global__ void __launch_bounds__(512, 4) qmatvec_kon_pair_kernel(QMV_HEAD_PARAM
 // The q / k / v projection and the decode attention that consumes it in ONE launch (DESIGN.md section 8.0,
 // tools/exp/localdep.hip): workgroups [0, n_mv) are the grouped mat-vec's, the rest the attention's (head-major, then
 // split). The attention's record fetch, dynamic words, rope tables and KV rows do not depend on the projection and
-// overlap it; the edge itself is a per-head-slice counter instead of a kernel boundary. 1024 threads per workgroup (the
+// overlap it; the edge itself is a sweep over data-tagged granules (QmvPublish) instead of a kernel boundary. 1024 threads per workgroup (the
 // attention's shape); the mat-vec half uses the waves its preloaded head asks for and retires the rest at once.
 struct QkvAttnArgs {
     const AttnDecodeParams* params;
@@ -1062,8 +1085,10 @@ struct QkvAttnArgs {
     uint32_t* split_cnt;
     uint32_t split_min_keys, n_mv, n_sp;
     uint32_t kvq; // int8 KV caches (the attention half's template variant)
-    QmvPublish pub;
+    QmvPublish pub;   // qkv_attn_kernel: granules
     DecodeHandoff ho;
+    QmvCountPublish cpub; // qkv_attn_kon_kernel: counters (a launch fills the pair its kernel reads)
+    CounterHandoff cho;
     uint32_t* census; // (the CENSUS instantiation of qkv_attn_kon_kernel only) [0] arrivals, [1] set when a workgroup gave up waiting for the grid
 };
 template <typename ST, bool Q4, int LPK, bool KVQ, int PROM = 1>
@@ -1108,10 +1133,10 @@ __global__ void __launch_bounds__(256, 4) qkv_attn_kon_kernel(QMV_HEAD_PARAMS, Q
         return;
     }
     if (blockIdx.x < f.n_mv) {
-        qmatvec_kon_body<DEPTH, PROM, true, true, NT>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, f.n_mv, &f.pub);
+        qmatvec_kon_body<DEPTH, PROM, true, true, NT>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, f.n_mv, &f.cpub);
     } else {
-        const uint32_t b = blockIdx.x - f.n_mv, n_heads = f.ho.n_heads; // head-major: the always-active split 0 of every head first
-        attention_decode_body<LPK, KVQ, 256>(f.params, f.split_buf, f.split_cnt, f.split_min_keys, b % n_heads, b / n_heads, f.n_sp, &f.ho);
+        const uint32_t b = blockIdx.x - f.n_mv, n_heads = f.cho.n_heads; // head-major: the always-active split 0 of every head first
+        attention_decode_body<LPK, KVQ, 256>(f.params, f.split_buf, f.split_cnt, f.split_min_keys, b % n_heads, b / n_heads, f.n_sp, &f.cho);
     }
 }
 
@@ -1483,7 +1508,7 @@ bool launch_packed_kon(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t
     const uint32_t flags = head_flags(a, waves_used, contig, a.pro.kind == QMV_PRO_RMSNORM_MUL, sw().hip_prenorm_early == 0);
     if (fused) { // q / k / v + decode attention in one launch of 256-thread workgroups (qkv_attn_kon_kernel)
         using FusedFn = void (*)(const uint4*, const void*, float*, const float*, const float*, uint32_t, uint32_t, uint32_t, uint32_t, QMVArgs, QkvAttnArgs);
-        if (!grp || !contig || !xvec || prom == 1 || (d_head != 64 && d_head != 128)) return false;
+        if (!grp || !contig || !xvec || prom == 1 || (d_head != 64 && d_head != 128) || !fused->cho.cnt) return false; // (this kernel hands over through counters)
         const uint32_t steps4 = cdiv(P, 4 * 64);
         const bool deep = steps4 >= 4; // four items per lane in flight (K >= 2048 with four waves), else two
         const uint32_t flags4 = (flags & ~(0xFu << 20)) | (3u << 20);
@@ -1588,7 +1613,7 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
         return true;
     }
     if (fused) {
-        if (!(xd && (pro || prenorm) && grp && !nt && q4 && w0.scale_f16 && contig && M == 1 && a.n_parts == 3 && (d_head == 64 || d_head == 128))) return false;
+        if (!(xd && (pro || prenorm) && grp && !nt && q4 && w0.scale_f16 && contig && M == 1 && a.n_parts == 3 && (d_head == 64 || d_head == 128) && fused->ho.gran)) return false; // (this kernel hands over through granules)
         QkvAttnArgs f = *fused;
         f.n_mv = total_blocks;
         const bool fused_kvq = f.kvq != 0;
@@ -1690,15 +1715,31 @@ void launch_qmatvec_fused(hipStream_t s, const QmvLaunch& L) { launch_qmv(s, L, 
 // the q / k / v projection + the decode attention of its heads in one launch (qkv_attn_kernel). `n_heads` x `n_sp`
 // attention workgroups follow the mat-vec's; false: shapes the fused kernel is not built for (launch the two separately)
 bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t n_kv, uint32_t d_head,
-                          const AttnSplit& sp, uint32_t* counters, const uint32_t* idx, uint32_t* seen, uint32_t* timeout, bool kvq) {
+                          const AttnSplit& sp, const QkvHandoffBlock& hb, uint32_t* timeout, bool kvq) {
+    if (L.n_parts != 3) return false;
     QkvAttnArgs f{};
     f.kvq = kvq ? 1 : 0;
     f.params = dev_params, f.split_buf = sp.buf, f.split_cnt = sp.cnt, f.split_min_keys = sp.min_keys;
     f.n_sp = sp.splits ? sp.splits : 1;
-    uint32_t shift = 0;
-    while ((16u << shift) < d_head) shift++;
-    f.pub = QmvPublish{counters, {0, n_heads, n_heads + n_kv}, shift, sw().hip_debug_drop_publish ? 1u : 0u}; // (diagnostics build, tests/handoff_timeout_worker.py: one column group never signals)
-    f.ho = DecodeHandoff{counters, seen, idx, n_heads, d_head / 16, timeout, (uint32_t)sw().hip_handoff_sleep};
+    const uint32_t drop = sw().hip_debug_drop_publish ? 1u : 0u; // (diagnostics build, tests/handoff_timeout_worker.py: one column group never hands over)
+    if (hb.counters) { // counter form (the launcher of K-on-lanes weights takes it; the other refuses it)
+        uint32_t shift = 0;
+        while ((16u << shift) < d_head) shift++;
+        f.cpub = QmvCountPublish{hb.counters, {0, n_heads, n_heads + n_kv}, shift, drop};
+        f.cho = CounterHandoff{hb.counters, hb.seen, hb.idx, n_heads, d_head / 16, timeout, (uint32_t)sw().hip_handoff_sleep};
+        return launch_qmv(s, L, &f, n_heads * f.n_sp, d_head);
+    }
+    if (!hb.granules) return false;
+    unsigned long long* const granules = hb.granules;
+    f.pub = QmvPublish{granules, hb.producer_gen, drop};
+    // Where the attention finds a record's granules. The producer stores column n of part c at granule first[c] + n (column groups
+    // of q, k, v follow each other in the launch). A record names its slices by pointers into the parts' outputs — fuse_qkv_attention
+    // has checked that q_src / k_src / v_src lie inside THESE L.parts[c].dst at multiples of d_head — so the slice's byte offset in
+    // the area is 8 * first[c] + 2 * (src - dst[c] in bytes): 8 bytes of granule per 4 of float. The area is far below 4 GB, so the
+    // kernel forms that offset in 32 bits from the pointer's low word, offset = 2 * low32(src) + rel[c] (mod 2^32).
+    const uint32_t first[3] = {0, n_heads * d_head, (n_heads + n_kv) * d_head};
+    f.ho = DecodeHandoff{granules, {0, 0, 0}, hb.consumer_gen, n_heads, timeout, (uint32_t)sw().hip_handoff_sleep};
+    for (int c = 0; c < 3; c++) f.ho.rel[c] = 8u * first[c] - 2u * (uint32_t)(uintptr_t)L.parts[c].dst;
     return launch_qmv(s, L, &f, n_heads * f.n_sp, d_head);
 }
 

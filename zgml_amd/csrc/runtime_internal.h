@@ -216,7 +216,7 @@ struct zgml_hip_program {
     std::vector<void*> f16_weights; // per buffer: MFMA-packed f16 copy of a promoted matmul B operand (else nullptr)
     std::vector<void*> owned; // other device allocations
     uint64_t fuse_epoch = 0;             // ctx->fuse_epoch the plan was built at (a time-out rebuilds it without the fusion)
-    std::vector<void*> fuse_owned;       // counters / seen / idx blocks of the fused launches: freed with every plan rebuild
+    std::vector<void*> fuse_owned;       // hand-off blocks of the fused launches (granules + generation words, or counters / seen / idx): freed with every plan rebuild
     // repeats of constant data (a weight broadcast to the activation shape: source never written by an op, destination written by
     // this op only) run ONCE when the plan is built instead of in every execution; a host input that ever targets one of the
     // buffers involved switches this off for the program (prepare_io)
