@@ -951,7 +951,8 @@ int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_h
  *   zgml_hip_resident_decode_speculative_constrained (below) honours sequence 0's in the verify step of a token_len = T plan.
  * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
  *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative,
- *   zgml_hip_resident_decode_batch_speculative_sampled and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
+ *   zgml_hip_resident_decode_batch_speculative_sampled, zgml_hip_resident_decode_speculative_model (a constraint on its target or
+ *   on its draft: forced tokens between draft executions are not served) and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
  *   constraint. */
 typedef struct zgml_token_dfa {
     uint32_t n_states, n_classes, vocab, _pad; /* 1 <= n_states <= 65535, 1 <= n_classes <= 8192 */
@@ -1009,6 +1010,47 @@ int zgml_hip_resident_decode_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip
                                                      uint32_t n_tokens, const zgml_spec_decode* opt, const zgml_sampling* sampling,
                                                      int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
                                                      zgml_spec_stats* stats /* may be NULL */);
+
+/* ── Speculative decode with a draft model: a second resident program drafts for the target (rule: zgml_amd/csrc/spec.h, DRAFTS
+ * FROM A MODEL). A sibling of zgml_hip_resident_decode_speculative and _speculative_sampled, not a mode of them: zgml_spec_decode
+ * keeps its layout and those calls keep refusing mode > 1.
+ * Programs. `target` is a plain token_len = T >= 2 plan with a resident set-up, as for zgml_hip_resident_decode_speculative;
+ *   `draft` a plain token_len = 1 plan of the same context with a resident set-up of its own and the target's vocabulary — every
+ *   other dimension, the weight kind and the KV form (f32 or int8) may differ.
+ * Verify step at (hist[pos], pos). c[0] = hist[pos]; for j = 0 .. T-1 the draft executes on c[j] at position pos + j, storing its
+ *   own KV column pos + j; d[j] is the first maximum of its logits row and c[j + 1] = d[j] for j < T - 1. The T-th execution
+ *   exists for its KV column alone (after full acceptance the next step starts at pos + T). Then the target's verify step runs
+ *   over c[0..T-1] as ever: acceptance, emission and the cuts are those of the sibling calls. stats.drafted grows by T - 1 per
+ *   step that emits something; there are no pads. The drafts are the draft's GREEDY tokens, also under a sampled verify step.
+ *   Idle steps (a round already launched, nothing left to produce) execute the draft T times from the token and position the
+ *   target idles at: that column is rewritten with the same values, the columns behind it are unspecified for both programs.
+ * sampling = NULL: the greedy verify step (first maxima; *n_produced = n_tokens). Else the step of
+ *   zgml_hip_resident_decode_speculative_sampled, all of it, from the target's rows: picks, stop tokens, penalties over the call's
+ *   device history, `logprobs`, `top_logprobs` and the result getters; sampling->recent must be NULL. top_k = 1 with neutral
+ *   penalties gives the tokens and statistics of the greedy form.
+ * Caches. On entry both programs' caches are valid for positions < start_pos — fill the draft's as the target's: vtable steps, a
+ *   prefill plan, zgml_hip_kv_move —; on return both are valid for positions < start_pos + *n_produced. Two calls give the token
+ *   stream of one; the second call's statistics are those of a fresh call from that state.
+ * Exactness. The contract of the sibling calls: every emitted token is the target's own greedy token (or pick) over a confirmed
+ *   context. Drafts decide how many steps run, never which tokens come out.
+ * Launches. One graph launch per step, a linear chain: [draft launch] T x { [draft prep] [draft plan] [argmax stage 1] [stage 2 +
+ *   draft advance] } [prep, T columns] [target plan] [argmax stage 1 over T rows | the sampled tail] [accept]. The draft
+ *   executions use the plain form (not the streaming head of zgml_hip_resident_decode). The graphs belong to the (target, draft)
+ *   pair, one per form, apart from every other graph: other calls on either program alternate with this one and invalidate
+ *   nothing; another draft program — or the same one freed, set up again or rebuilt, also a new program at its old address —
+ *   re-captures. Runtime profile: the target counts plan + 3 + tail launches per step, the draft T x (plan + 3).
+ * Blocking. Returns 0. Refused with -1 and an error on the context, before anything is enqueued: everything
+ *   zgml_hip_resident_decode_speculative refuses of the target and of the request (history / n_history as its opt->history), with
+ *   `sampling` everything _speculative_sampled refuses; a sharded target; a draft that is NULL, without a resident set-up, of
+ *   another context, batched, token_len != 1, sharded, the target itself, or of another vocabulary;
+ *   start_pos + n_tokens + T - 1 > the draft's max_seq; a constraint attached to either program (forced tokens would have to be
+ *   placed between the draft executions: not served yet, like a draft model under batching or in front of
+ *   zgml_hip_resident_decode_speculative_constrained). n_tokens = 0 returns 0 and touches nothing. */
+int zgml_hip_resident_decode_speculative_model(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft, uint32_t first_token,
+                                               uint32_t start_pos, uint32_t n_tokens, const uint32_t* history /* [n_history] */,
+                                               uint32_t n_history /* 0 or start_pos */, const zgml_sampling* sampling /* NULL: greedy */,
+                                               int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
+                                               zgml_spec_stats* stats /* may be NULL */);
 
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];

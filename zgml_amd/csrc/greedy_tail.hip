@@ -4,6 +4,8 @@
 //   launch_argmax               [stage 1: a pair per workgroup] [stage 2: the pairs' fold + the single loop's advance and the
 //                               token's embedding row]; stage 1 may carry the position part of the next step's prep
 //   launch_argmax_fold          its stage 2 alone (the pairs came from the streaming LM head: kernels_generic.hip)
+//   launch_argmax_draft         the two stages behind a draft program's execution inside a verify step: stage 2 ends with the
+//                               draft advance (the draft's next token and position, the target's next candidate)
 //   launch_argmax_batch         the same two stages over B rows (blockIdx.y = sequence), the batched loop's advance;
 //   launch_argmax_rows_stage1   its stage 1 alone (a greedy verify step: spec_accept_kernel folds the pairs)
 // Every workgroup has 256 threads and the same two LDS arrays; a row takes n / 1024 + 1 workgroups, at most 256.
@@ -141,6 +143,15 @@ __global__ void __launch_bounds__(kBlock) argmax_stage2(const float* vals, const
     if (adv.state) tail_advance_single(adv.state, adv.tokens, adv.cap, next); // the resident loop's advance step
 }
 
+// stage 2 behind one execution of a draft program inside a verify step: the fold, then the draft advance (tail_device.h). A row
+// has n > 0 entries, so a pair exists and the index is one of the row's: the clamp is for the embedding gather's sake
+__global__ void __launch_bounds__(kBlock) argmax_stage2_draft(const float* vals, const int64_t* idxs, int nblk, uint64_t n, DraftAdvance adv) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    const int64_t next = argmax_stage2_body(sv, si, 0, vals, idxs, nblk);
+    if (threadIdx.x == 0) tail_advance_draft(adv, (uint64_t)next < n ? (uint32_t)next : 0u);
+}
+
 // argmax_stage1 / argmax_stage2 over B rows of n values at once: blockIdx.y = row (sequence); same (value, index) ordering
 __global__ void __launch_bounds__(kBlock) argmax_batch_stage1(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx) {
     __shared__ float sv[kBlock];
@@ -194,6 +205,12 @@ void launch_argmax(hipStream_t s, const float* v, uint64_t n, float* scratch_val
     else
         argmax_stage1<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
     argmax_stage2<false><<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, out, adv);
+}
+
+void launch_argmax_draft(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv) {
+    const int nblk = argmax_batch_blocks(n);
+    argmax_stage1<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
+    argmax_stage2_draft<<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, n, adv);
 }
 
 void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* scratch_idx, uint32_t nblk, int64_t* out, const ArgmaxAdvance& adv) {

@@ -404,6 +404,15 @@ void launch_argmax(hipStream_t s, const float* v, uint64_t n, float* scratch_val
 // stage 2 alone, over nblk pairs another launch left in the scratch (at most kArgPairs; an empty pair's index is INT64_MAX)
 constexpr uint32_t kArgPairs = 1024; // pairs of the context's argmax scratch
 void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* scratch_idx, uint32_t nblk, int64_t* out, const ArgmaxAdvance& adv);
+// The two argmax stages behind ONE execution of a draft program inside a verify step (spec.h: DRAFTS FROM A MODEL): stage 2 ends
+// with the draft advance — state[0] = d, the row's first maximum, state[1] += 1 (the draft program's state words: its next
+// execution's token and position), and with `cand_next` (every execution but the step's last) *cand_next = d, the next
+// candidate of the target's verify step.
+struct DraftAdvance {
+    uint32_t* state = nullptr;
+    uint32_t* cand_next = nullptr;
+};
+void launch_argmax_draft(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv);
 // Everything LlamaInferencePlan.execute patches on the host per execution (src/llama_inference.zig:405-446; for T > 1
 // patch_tokens of zgml_amd/host/llama_decode.cpp), produced on the device as one flat index space: T embedding rows, T
 // causal-mask columns, T RoPE rows per layer leaf, the dynamic words (KV store offsets at `pos`, seq_kv = pos + T).
@@ -469,7 +478,7 @@ enum SpecWord : uint32_t {
     kSpecPos,      // its position
     kSpecProduced, // tokens produced so far
     kSpecWanted,   // n_tokens of the call
-    kSpecMode,     // 0 lookup, 1 provided
+    kSpecMode,     // 0 lookup, 1 provided, 2 a draft model (zgml_hip_resident_decode_speculative_model alone sets it)
     kSpecNgram,
     kSpecNDrafts,
     kSpecStart,    // start_pos of the call
@@ -513,6 +522,10 @@ struct SpecArgs {
     const SampleConstraintRow* con_row = nullptr;
     uint32_t* con_state = nullptr;
     uint32_t* row_state = nullptr;
+    // drafts from a model (zgml_hip_resident_decode_speculative_model; spec.h: DRAFTS FROM A MODEL), mode 2: the state words
+    // (token, position) of the DRAFT program's resident set-up, what its prep launch reads. The draft launch writes c[0] and the
+    // run position there; cand[1..T-1] are written by the draft executions' advances (launch_argmax_draft). nullptr: none
+    uint32_t* draft_state = nullptr;
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);

@@ -1,6 +1,6 @@
 // runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up; the greedy loops
 // (single-sequence decode, batched decode, the prefill chunk); their sampled forms and the sampled / greedy speculative verify
-// loop, and the greedy / sampled verify loop of every sequence of a batched plan; the blocking calls over one buffer range
+// loop — also with a second resident program drafting inside the step (zgml_hip_resident_decode_speculative_model) —, and the greedy / sampled verify loop of every sequence of a batched plan; the blocking calls over one buffer range
 // (zgml_hip_sample, zgml_hip_logprobs, zgml_hip_top_logprobs) with their result
 // getters; the token constraint's create / attach / state. Everything a step needs (embedding row, mask column, RoPE rows, the
 // dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
@@ -8,6 +8,7 @@
 // replay), resident_end; what follows the plan in a sampled step is stated once, by SampledTail.
 // No kernels here: the prep / pick kernels are in greedy_tail.hip, the plan's and the sampled tail's in their own files.
 #include "runtime_internal.h"
+#include <atomic>
 #include "sample.h"
 #include "sample_params.h"
 #include "spec.h"
@@ -109,6 +110,18 @@ struct zgml_resident {
     // constrained verify step (zgml_hip_resident_decode_speculative_constrained), allocated by its first call: the state of every
     // logits row, [T] (spec.h: UNDER A CONSTRAINT) — the draft launch writes them, the constrained-rows select launch reads them
     uint32_t* row_state = nullptr;
+    // speculative decode with a draft model (zgml_hip_resident_decode_speculative_model), on the TARGET's set-up: the step's graphs
+    // hold the launches of two programs, so they belong to the pair — pair_draft and the draft set-up's graph_epoch as it stood at
+    // the capture; another draft, or one whose epoch moved, re-captures —, one per form ([0] greedy, [1 + SampledTail::form()]
+    // the sampled ones) and apart from every other slot: other calls on either program alternate with the pair's and drop nothing
+    zgml_hip_program* pair_draft = nullptr;
+    uint64_t pair_epoch = 0;
+    hipGraph_t pair_graph[1 + kSampledForms] = {};
+    hipGraphExec_t pair_graph_exec[1 + kSampledForms] = {};
+    // what a graph that bakes THIS set-up's launches is valid for: a process-wide count, taken at the set-up and again whenever
+    // its graphs are dropped (free_resident_graph: a plan rebuild, a grown table), so no two states of any program share a value —
+    // a program created at a freed one's address included
+    uint64_t graph_epoch = 0;
 };
 using Resident = zgml_resident;
 
@@ -122,9 +135,23 @@ struct zgml_hip_constraint {
 
 namespace zgml_rt {
 
+static std::atomic<uint64_t> g_graph_epoch{0}; // (Resident::graph_epoch)
+
+// the pair's graphs on the target's set-up (Resident::pair_graph)
+static void free_pair_graphs(Resident* r) {
+    for (uint32_t f = 0; f < 1 + kSampledForms; f++) {
+        if (r->pair_graph_exec[f]) hipGraphExecDestroy(r->pair_graph_exec[f]);
+        if (r->pair_graph[f]) hipGraphDestroy(r->pair_graph[f]);
+        r->pair_graph_exec[f] = nullptr, r->pair_graph[f] = nullptr;
+    }
+    r->pair_draft = nullptr, r->pair_epoch = 0;
+}
+
 void free_resident_graph(zgml_hip_program* p) {
     Resident* r = p->resident;
     if (!r) return;
+    r->graph_epoch = ++g_graph_epoch; // (a pair graph on ANOTHER program that bakes this one as its draft is stale from here on)
+    free_pair_graphs(r);
     if (r->graph_exec) hipGraphExecDestroy(r->graph_exec);
     if (r->graph) hipGraphDestroy(r->graph);
     r->graph_exec = nullptr, r->graph = nullptr;
@@ -637,6 +664,7 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
     }
     Resident* r = new Resident();
     p->resident = r;
+    r->graph_epoch = ++g_graph_epoch;
     r->token_len = T;
     // > 0: the T columns are n_seqs sequences of tokens_per_seq consecutive positions each — one (zgml_hip_resident_decode_batch) or
     // several (zgml_hip_resident_decode_batch_speculative) —, not T consecutive positions of one
@@ -1328,13 +1356,23 @@ bool spec_request(zgml_hip_ctx* ctx, const Resident* r, const std::string& who, 
 // a constraint attached to sequence 0 the constrained one — the same launches with the constrained-rows select in the place of
 // the select, the draft and the accept launch also walking the automaton, graphs of their own; a reached state without a token
 // ends the call early as a stop token does. Without a constraint it is the sampled form to the launch.
+// `model` (zgml_hip_resident_decode_speculative_model; spec.h: DRAFTS FROM A MODEL): the candidates come from `draft`, a plain
+// token_len = 1 program of the same context and vocabulary, executed T times between the draft launch and the prep —
+//   [begin] T x { [draft prep] [draft plan] [argmax stage 1] [stage 2 + draft advance] } [prep] [plan] ... [accept]
+// one graph launch, a linear chain. Either form of the verify step; `opt` carries the history alone. The graphs belong to the
+// pair (Resident::pair_graph); each program's profile counts its own launches. The draft executions are the plain form: the
+// streaming head and the position part written a token ahead (zgml_hip_resident_decode) are not carried over.
 int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
                 const zgml_spec_decode* opt, bool sampled, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats,
-                bool honours_constraint = false) {
+                bool honours_constraint = false, bool model = false, zgml_hip_program* draft = nullptr) {
     if (!ctx || !p || !p->resident) return -1;
     Resident* r = p->resident;
     if (n_produced) *n_produced = 0;
     if (!honours_constraint && refuse_constrained(ctx, p, who.c_str())) return -1;
+    if (model && !p->shard_points.empty()) {
+        ctx->fail(who + ": the target is a sharded program (gather points attached)");
+        return -1;
+    }
     const bool constrained = honours_constraint && r->n_con != 0;
     if (r->n_seqs) {
         ctx->fail(who + ": the program is a batched plan (one sequence only here: zgml_hip_resident_decode_batch_speculative runs a batched plan with tokens_per_seq >= 2)");
@@ -1346,10 +1384,30 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         return -1;
     }
     if (stats) *stats = zgml_spec_stats{0, 0, 0, 0};
+    Resident* const dr = model && draft ? draft->resident : nullptr;
+    if (model) { // what the call asks of the draft program
+        const char* why = !draft ? "no draft program" : draft == p ? "the draft is the target program itself" : draft->ctx != p->ctx ? "the draft belongs to another context"
+                          : !dr ? "the draft has no resident set-up (zgml_hip_resident_setup first)"
+                          : dr->n_seqs ? "the draft is a batched plan" : dr->token_len != 1 ? "the draft must be a token_len = 1 plan"
+                          : !draft->shard_points.empty() ? "the draft is a sharded program (gather points attached)"
+                          : dr->vocab != r->vocab ? "the draft has another vocabulary than the target" : nullptr;
+        if (why) {
+            ctx->fail(who + ": " + why);
+            return -1;
+        }
+        if (has_constraint(draft)) { // (forced tokens would have to be placed between the draft executions: not served)
+            ctx->fail(who + ": a constraint is attached to the draft program (detach it first)");
+            return -1;
+        }
+    }
     if (!n_tokens) return 0;
     if (!tokens_out) return -1;
     SpecRequest req;
     if (!spec_request(ctx, r, who, first_token, start_pos, n_tokens, T, false, opt, &req)) return -1;
+    if (dr && (uint64_t)start_pos + n_tokens + T - 1 > dr->max_seq) { // (the target's bound: the draft stores the same T columns per step)
+        ctx->fail(who + ": start_pos + n_tokens + token_len - 1 exceeds the draft's max_seq");
+        return -1;
+    }
     const zgml_spec_decode& o = req.o;
     const uint32_t ngram = req.ngram, n_drafts = req.n_drafts;
     SampleParamsDev sp{};
@@ -1360,6 +1418,10 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     // the first start and the last possible start of a verify step
     resident_begin(p, [&] {
         return positions_in_bounds(p, T, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, T, [&](uint32_t) { return start_pos + n_tokens - 1; });
+    });
+    // ... and the first and the last possible position of a draft execution
+    if (dr) resident_begin(draft, [&] {
+        return positions_in_bounds(draft, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(draft, 1, [&](uint32_t) { return start_pos + n_tokens + T - 2; });
     });
     const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1;
     if (!r->spec) {
@@ -1375,7 +1437,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens_cap)) return -1;
     if (top && !ensure_top_blocks(ctx, p, T, r->tokens_cap)) return -1;
     uint32_t w0[kSpecWords] = {0};
-    w0[kSpecTok] = first_token, w0[kSpecPos] = start_pos, w0[kSpecWanted] = n_tokens, w0[kSpecMode] = o.mode, w0[kSpecNgram] = ngram;
+    w0[kSpecTok] = first_token, w0[kSpecPos] = start_pos, w0[kSpecWanted] = n_tokens, w0[kSpecMode] = model ? 2 : o.mode, w0[kSpecNgram] = ngram;
     w0[kSpecNDrafts] = std::min(n_drafts, r->max_seq), w0[kSpecStart] = start_pos, w0[kSpecHistLo] = o.n_history ? 0 : start_pos;
     w0[kSpecRunPos] = start_pos;
     // (the host arrays are the caller's or on this stack, and every copy below is waited for before the call returns)
@@ -1410,11 +1472,20 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     if (top) sa.top_rows_tok = r->top_rows_tok, sa.top_rows_val = r->top_rows_val, sa.top_tok_out = r->top_tok, sa.top_val_out = r->top_val;
     // the prep reads its position from the run words (the draft launch decides where the step runs) and its tokens from the candidates
     const Prep prep = prep_args(p, r->spec + kSpecRun, r->tok_dev);
+    // (the model form) the draft's prep reads its own state words, as in zgml_hip_resident_decode: the draft launch and the
+    // executions' advances write them; execution j's advance also writes candidate j + 1
+    const Prep dprep = dr ? prep_args(draft, dr->state, dr->state /* the token is state[0] */) : Prep{};
+    if (dr) sa.draft_state = dr->state;
     // the plan enters the step's graph through run_plan, as in resident_decode: many executions per call, with the dynamic words
     // written by the prep launch inside the graph (resident_prefill's enqueue replays the program's own graphs and would flush the
     // host mirror over them unless dyn_dirty is cleared per execution)
     auto one_step = [&](hipStream_t st) {
         launch_spec_draft(st, sa);
+        for (uint32_t j = 0; dr && j < T; j++) {
+            launch_resident_prep(st, dprep.a, dprep.total);
+            run_plan(draft, st, 0, draft->plan.size());
+            launch_argmax_draft(st, dr->logits, dr->vocab, ctx->arg_val, ctx->arg_idx, DraftAdvance{dr->state, j + 1 < T ? r->tok_dev + j + 1 : nullptr});
+        }
         launch_resident_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
         if (sampled)
@@ -1423,10 +1494,17 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             launch_argmax_rows_stage1(st, r->logits, r->vocab, T, r->bval, r->bidx);
         launch_spec_accept(st, sa);
     };
-    hipGraphExec_t& exec = sampled ? r->sgraph_exec[tail.form()] : r->graph_exec;
-    hipGraph_t& graph = sampled ? r->sgraph[tail.form()] : r->graph;
+    // (the model form) the pair's graphs serve this draft as it stands, and no other
+    if (dr && (r->pair_draft != draft || r->pair_epoch != dr->graph_epoch)) {
+        hipStreamSynchronize(s);
+        free_pair_graphs(r);
+        r->pair_draft = draft, r->pair_epoch = dr->graph_epoch;
+    }
+    const uint32_t pair_slot = sampled ? 1 + tail.form() : 0;
+    hipGraphExec_t& exec = dr ? r->pair_graph_exec[pair_slot] : sampled ? r->sgraph_exec[tail.form()] : r->graph_exec;
+    hipGraph_t& graph = dr ? r->pair_graph[pair_slot] : sampled ? r->sgraph[tail.form()] : r->graph;
     // (the sampled form waits, as the sampled loops: no copy from this stack frame in flight when the capture begins)
-    capture_once(ctx, s, sampled ? std::string("resident_spec_") + kSampledFormNames[tail.form()] : std::string("resident_spec"), sampled, one_step, &graph, &exec);
+    capture_once(ctx, s, std::string(dr ? "resident_spec_model" : "resident_spec") + (sampled ? std::string("_") + kSampledFormNames[tail.form()] : std::string()), sampled, one_step, &graph, &exec);
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)
     uint32_t w1[kSpecWords] = {0};
@@ -1460,12 +1538,21 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     if (ok && n_produced) *n_produced = made;
     // per step [draft] [prep] [plan] [argmax stage 1] [accept], or the sampled tail in the place of the argmax stage
     resident_end(p, steps_run, p->plan.size() + 3 + (sampled ? tail.launches() : 1));
+    if (dr) resident_end(draft, steps_run * T, draft->plan.size() + 3); // per step T x { [prep] [plan] [argmax x 2] }
     return ok ? 0 : -1;
 }
 
 } // namespace
 
 extern "C" {
+
+int zgml_hip_resident_decode_speculative_model(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft, uint32_t first_token, uint32_t start_pos,
+                                               uint32_t n_tokens, const uint32_t* history, uint32_t n_history, const zgml_sampling* sampling, int64_t* tokens_out,
+                                               uint32_t* n_produced, zgml_spec_stats* stats) {
+    const zgml_spec_decode opt{history, n_history, 0, nullptr, 0, 0};
+    return spec_decode(ctx, target, "resident_decode_speculative_model", first_token, start_pos, n_tokens, &opt, sampling != nullptr, sampling, tokens_out, n_produced,
+                       stats, false, true, draft);
+}
 
 int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
                                          const zgml_spec_decode* opt, int64_t* tokens_out, zgml_spec_stats* stats) {

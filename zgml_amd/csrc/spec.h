@@ -6,7 +6,8 @@
 //
 // Vocabulary: hist[0..pos] holds the token at every position, hist[pos] being the last confirmed token (not yet in the KV
 // cache). A verify step runs a token_len = T plan over the candidates c[0..T-1]: c[0] = hist[pos], c[j] the draft for position
-// pos + j, or — a position without a draft — the pad c[j - 1]. g[j] is the token of logits row j — its first maximum, or in the
+// pos + j (from the n-gram lookup, the caller's table, or a draft model: the three candidate rules below), or — a position
+// without a draft — the pad c[j - 1]. g[j] is the token of logits row j — its first maximum, or in the
 // sampled form sample.h's pick at position pos + j —: the token at position pos + j + 1 given c[0..j].
 //
 // UNDER A CONSTRAINT (zgml_hip_resident_decode_speculative_constrained; sample.h: THE CONSTRAINT). The mode's candidates and its
@@ -98,6 +99,24 @@ ZGML_SPEC_FN uint32_t spec_candidates_provided(uint32_t tok, uint32_t pos, uint3
             c[j] = c[j - 1];
     }
     return real;
+}
+
+// ── DRAFTS FROM A MODEL (zgml_hip_resident_decode_speculative_model): a second, token_len = 1 program of the same vocabulary ──
+// A verify step runs at (hist[pos], pos); c[0] = hist[pos]. For j = 0 .. T-1 the draft program executes on token c[j] at position
+// pos + j — each execution stores the DRAFT's KV column pos + j —, d[j] is the first maximum of its logits row, and
+// c[j + 1] = d[j] for j < T - 1. The T-th execution exists for its KV column alone and d[T - 1] is dropped: when all T - 1 drafts
+// are accepted the next step starts at pos + T, and the draft must then already hold column pos + T - 1. `drafted` grows by
+// T - 1 per step that is not idle; there are no pads. The drafts are the draft program's GREEDY tokens, under a sampled verify
+// step too. An idle step executes the draft T times from (hist[at], at), `at` the position the target's idle step runs at:
+// column `at` is rewritten from the same token and context, the columns behind it are unspecified, as the target's are.
+// Why the draft's cache stays in step: with a candidates accepted, the draft's columns pos .. pos + min(a, T - 1) were computed
+// over confirmed tokens — the step emits at most a + 1 —, and every column behind them is stored again, by the next step's
+// executions from its own pos, before any attention of the draft reads it.
+// What the draft launch leaves of this rule: c[0] (the other candidates are written by the executions' advances; until then they
+// repeat c[0]) and the count of drafts.
+ZGML_SPEC_FN uint32_t spec_candidates_model(uint32_t tok, uint32_t T, uint32_t* c) {
+    for (uint32_t j = 0; j < T; j++) c[j] = tok;
+    return T - 1;
 }
 
 // the largest a with c[j] == g[j - 1] for all 1 <= j <= a: the candidates that were the greedy choice of the rows in front of them

@@ -31,7 +31,9 @@ __device__ __forceinline__ uint32_t spec_constrain(const SpecArgs& a, uint32_t r
 // The candidates of this step into a.cand (what the prep launch reads as its T token ids) and the position it runs at into the
 // run words. Lookup mode: for n = ngram .. 1 the threads walk the match positions [n - 1, pos - 1] downwards, 256 apart — a
 // thread's first hit is its largest —, the largest hit of the workgroup is folded with wave shuffles and one pass over LDS, and
-// the first n with a hit wins. Provided mode is a table read. Thread 0 writes. fold: kSpecWaves LDS words.
+// the first n with a hit wins. Provided mode is a table read. The model mode (spec.h: DRAFTS FROM A MODEL) writes c[0] and hands
+// (c[0], position) to the draft program's state words: the draft executions between this launch and the prep fill in the rest.
+// Thread 0 writes. fold: kSpecWaves LDS words.
 // kIdleAtEnd: where a sequence that has its count runs its idle steps (below).
 template <bool kIdleAtEnd>
 __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold) {
@@ -48,6 +50,15 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
             for (uint32_t j = 0; j < a.T; j++) a.cand[j] = a.hist[at];
             for (uint32_t j = 0; a.row_state && j < a.T; j++) a.row_state[j] = kConstraintDead; // (no row of an idle step picks)
             w[kSpecRunPos] = at;
+            if (a.draft_state) a.draft_state[0] = a.hist[at], a.draft_state[1] = at; // (the draft program idles from the same token and position)
+        }
+        return;
+    }
+    if (w[kSpecMode] == 2) { // drafts from a model: c[0] and the draft program's first execution; its advances write c[1..T-1]
+        if (threadIdx.x == 0) {
+            w[kSpecDrafted] += spec_candidates_model(a.hist[pos], a.T, a.cand);
+            w[kSpecRunPos] = pos;
+            a.draft_state[0] = a.hist[pos], a.draft_state[1] = pos;
         }
         return;
     }

@@ -4,7 +4,8 @@
 //   the single-sequence prep     its token part and its position part, and the position part a token ahead
 //   the bitonic stage            sample.hip's select and merge sorts, top_logprob.hip's merge of the lists' heads
 //   the argmax pieces            first maximum wins: a thread's scan, the block reductions, the empty-aware fold, its wave form
-//   the advances                 of the single loop's and of the batched loop's device state, behind a greedy or a sampled pick
+//   the advances                 of the single loop's and of the batched loop's device state, behind a greedy or a sampled pick,
+//                                and of a draft program's state words behind one of its executions inside a verify step
 //   the log-probability finish   which token and where its value goes; M, the blocks' terms and their sum over ascending b
 #pragma once
 #include "kernels.h"
@@ -141,6 +142,15 @@ __device__ __forceinline__ void tail_advance_batched(uint32_t* st, int64_t* toke
     st[B + b] += 1;
     st[2 * B + b] = stop ? 0 : left - 1;
     st[3 * B + b] = produced + 1;
+}
+
+// One execution of the draft program inside a verify step (kernels.h: DraftAdvance; spec.h: DRAFTS FROM A MODEL): the draft's
+// greedy token d becomes the token of its next execution, a position further, and — every execution but the step's last — the
+// next candidate of the target's verify step. No count, no table: what is emitted is the accept launch's business.
+__device__ __forceinline__ void tail_advance_draft(const DraftAdvance& adv, uint32_t d) {
+    adv.state[0] = d;
+    adv.state[1] += 1;
+    if (adv.cand_next) *adv.cand_next = d;
 }
 
 // ── the log-probability finish (the rule: sample.h, THE LOG-PROBABILITY) ──

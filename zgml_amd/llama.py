@@ -630,6 +630,39 @@ class Session:
             return toks[:n_tokens], int(produced.value), st, lps
         return toks[:n_tokens], int(produced.value), st, lps, self._alternatives(n_tokens)
 
+    def resident_decode_speculative_model(self, draft_session: "Session", first_token: int, start_pos: int, n_tokens: int, sampling=None, history=None,
+                                          logprobs: bool = False, top_logprobs: int = 0):
+        """zgml_hip_resident_decode_speculative_model: this session's token_len = T >= 2 plan verifies what `draft_session`'s
+        token_len = 1 plan (same backend, same vocabulary, its own resident_setup) drafts greedily, T - 1 tokens per step, all on
+        the device. Both caches must hold the positions < start_pos; afterwards both hold those < start_pos + the produced count.
+        sampling=None: the greedy verify step -> (tokens[n_tokens], {"steps", "drafted", "accepted"}). With a capi.SamplingC the
+        result is that of resident_decode_speculative_sampled: (tokens, n_produced, stats), then the log-probabilities
+        (logprobs=True) and the alternatives (top_logprobs > 0). `history`: the tokens at positions 0..start_pos-1 (the penalties'
+        window reads them)."""
+        u32p = C.POINTER(C.c_uint32)
+        hist = np.ascontiguousarray([] if history is None else history, dtype=np.uint32)
+        toks = np.full(max(1, n_tokens), -1, np.int64)
+        if sampling is None and (logprobs or top_logprobs):
+            raise ValueError("resident_decode_speculative_model: logprobs / top_logprobs need a sampling parameter set")
+        if logprobs or top_logprobs:
+            sampling = capi.with_logprobs(sampling, top=top_logprobs)
+        stats, produced = capi.SpecStatsC(), C.c_uint32(0)
+        rc = capi.load_hip().zgml_hip_resident_decode_speculative_model(
+            self._backend.ctx, self.handle, draft_session.handle if draft_session is not None else None, first_token, start_pos, n_tokens,
+            hist.ctypes.data_as(u32p) if hist.size else None, hist.size, C.byref(sampling) if sampling is not None else None, toks.ctypes.data,
+            C.byref(produced), C.byref(stats))
+        if rc != 0:
+            raise RuntimeError("resident_decode_speculative_model: " + self._backend.last_error())
+        st = {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
+        if sampling is None:
+            return toks[:n_tokens], st
+        if not logprobs and not top_logprobs:
+            return toks[:n_tokens], int(produced.value), st
+        lps = capi.logprobs_result(self._backend.ctx, n_tokens) if n_tokens else np.zeros(0, np.float32)
+        if not top_logprobs:
+            return toks[:n_tokens], int(produced.value), st, lps
+        return toks[:n_tokens], int(produced.value), st, lps, self._alternatives(n_tokens)
+
     def close(self):
         if self.ptr:
             self.lib.zh_session_free(self.ptr)
