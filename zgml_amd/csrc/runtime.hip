@@ -182,12 +182,6 @@ __global__ void gather_words_wide_kernel(const IoTableDev* table, uint32_t* stag
 
 uint32_t io_grid_y(uint32_t max_row_words) { return std::max<uint32_t>(1, std::min<uint32_t>(64, max_row_words / 1024)); } // workgroups per transfer row
 
-void free_io_graph(zgml_hip_program* p) {
-    if (p->io_graph_exec) hipGraphExecDestroy(p->io_graph_exec);
-    if (p->io_graph) hipGraphDestroy(p->io_graph);
-    p->io_graph_exec = nullptr, p->io_graph = nullptr;
-}
-
 } // namespace
 
 namespace zgml_rt {
@@ -224,17 +218,7 @@ void dump_graph(hipGraph_t g, const char* tag) {
 // Drop every captured graph of the program: both bake the plan's kernel nodes and the device parameter arrays
 // build_plan() is about to free, so a plan rebuild must never leave one behind (the resident graph included).
 void free_graph(zgml_hip_program* p) {
-    free_io_graph(p);
-    if (p->graph_exec) hipGraphExecDestroy(p->graph_exec);
-    if (p->graph) hipGraphDestroy(p->graph);
-    p->graph_exec = nullptr;
-    p->graph = nullptr;
-    if (p->graph_tail_exec) hipGraphExecDestroy(p->graph_tail_exec);
-    if (p->graph_tail) hipGraphDestroy(p->graph_tail);
-    p->graph_tail_exec = nullptr, p->graph_tail = nullptr;
-    if (p->shard_graph_exec) hipGraphExecDestroy(p->shard_graph_exec);
-    if (p->shard_graph) hipGraphDestroy(p->shard_graph);
-    p->shard_graph_exec = nullptr, p->shard_graph = nullptr;
+    for (GraphSlot* g : {&p->io_graph, &p->graph, &p->graph_tail, &p->shard_graph}) g->reset();
     free_resident_graph(p);
 }
 } // namespace zgml_rt
@@ -245,11 +229,12 @@ bool ensure_stage(zgml_hip_program* p, uint64_t bytes) {
     if (bytes <= p->stage_cap) return true;
     zgml_hip_ctx* ctx = p->ctx;
     hipStreamSynchronize(ctx->stream);
-    free_io_graph(p); // (its kernels hold the buffers' addresses)
+    p->io_graph.reset(); // (its kernels hold the buffers' addresses)
     if (p->stage_host) hipHostFree(p->stage_host);
     if (p->stage_out_host) hipHostFree(p->stage_out_host);
     if (p->stage_dev) hipFree(p->stage_dev);
     p->stage_host = p->stage_out_host = p->stage_dev = nullptr;
+    p->stage_cap = 0; // (a failed regrow below leaves no capacity standing over no buffers)
     uint64_t cap = 1 << 16;
     while (cap < bytes) cap <<= 1;
     if (!CTX_CHECK(ctx, hipHostMalloc(&p->stage_host, cap, hipHostMallocMapped))) return false;
@@ -274,7 +259,7 @@ bool prepare_io(zgml_hip_program* p, IoPlan& plan, const zgml_program_io* ios, u
     if (same) return true;
     zgml_hip_ctx* ctx = p->ctx;
     hipStreamSynchronize(ctx->stream);
-    free_io_graph(p); // (captured for the tables that are about to change)
+    p->io_graph.reset(); // (captured for the tables that are about to change)
     plan.entries.clear();
     plan.word_aligned = true;
     plan.total_words = 0, plan.max_row_words = 0;
@@ -408,20 +393,19 @@ void ensure_plan(zgml_hip_program* p) {
     }
 }
 
-// `work` captured from stream s (thread-local mode) into *g_out and instantiated into *e_out; `tag` names the graph for
-// ZGML_HIP_GRAPH_DUMP (nullptr: not dumped). false, reported on ctx and with nothing left behind, when any step fails.
-bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, hipGraph_t* g_out, hipGraphExec_t* e_out) {
-    hipGraph_t g = nullptr;
+// `work` captured from stream s (thread-local mode) and instantiated into the empty `slot`; `tag` names the graph for
+// ZGML_HIP_GRAPH_DUMP (nullptr: not dumped). false, reported on ctx and with the slot left empty, when any step fails.
+bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, GraphSlot* slot) {
     if (!CTX_CHECK(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal))) return false;
     work();
-    if (!CTX_CHECK(ctx, hipStreamEndCapture(s, &g)) || !g) return false;
-    if (tag) dump_graph(g, tag);
+    if (!CTX_CHECK(ctx, hipStreamEndCapture(s, &slot->graph)) || !slot->graph) return false;
+    if (tag) dump_graph(slot->graph, tag);
     hipGraphExec_t ge = nullptr;
-    if (!CTX_CHECK(ctx, hipGraphInstantiate(&ge, g, nullptr, nullptr, 0))) {
-        hipGraphDestroy(g);
+    if (!CTX_CHECK(ctx, hipGraphInstantiate(&ge, slot->graph, nullptr, nullptr, 0))) {
+        slot->reset();
         return false;
     }
-    *g_out = g, *e_out = ge;
+    slot->exec = ge;
     return true;
 }
 
@@ -485,25 +469,22 @@ void enqueue(zgml_hip_program* p) {
         return;
     }
     if (ctx->opt_graph && !p->plan.empty()) {
-        if (!p->graph_exec) {
+        if (!p->graph.exec) {
             // two graphs (zgml_hip_program::graph_tail): the head holds the first sixth of the launches (at least 8: its device
             // time has to cover the host's submission of the tail), short plans stay one graph
             const int split_env = sw().hip_graph_split;
             size_t head = p->plan.size() >= 48 ? std::max<size_t>(8, p->plan.size() / 6) : p->plan.size();
             if (split_env == 0) head = p->plan.size();
             if (split_env > 0) head = std::min<size_t>((size_t)split_env, p->plan.size());
-            auto capture = [&](size_t first, size_t count, hipGraph_t* g_out, hipGraphExec_t* e_out, const char* tag) {
-                return capture_graph(ctx, ctx->stream, tag, [&] { run_plan(p, ctx->stream, first, count); }, g_out, e_out);
+            auto capture = [&](size_t first, size_t count, GraphSlot* slot, const char* tag) {
+                return capture_graph(ctx, ctx->stream, tag, [&] { run_plan(p, ctx->stream, first, count); }, slot);
             };
-            if (capture(0, head, &p->graph, &p->graph_exec, "program") && head < p->plan.size() &&
-                !capture(head, p->plan.size() - head, &p->graph_tail, &p->graph_tail_exec, "program-tail")) {
-                hipGraphExecDestroy(p->graph_exec), hipGraphDestroy(p->graph); // (all or nothing: eager below)
-                p->graph_exec = nullptr, p->graph = nullptr;
-            }
+            if (capture(0, head, &p->graph, "program") && head < p->plan.size() && !capture(head, p->plan.size() - head, &p->graph_tail, "program-tail"))
+                p->graph.reset(); // (all or nothing: eager below)
         }
-        if (p->graph_exec) {
-            CTX_CHECK(ctx, hipGraphLaunch(p->graph_exec, ctx->stream));
-            if (p->graph_tail_exec) CTX_CHECK(ctx, hipGraphLaunch(p->graph_tail_exec, ctx->stream));
+        if (p->graph.exec) {
+            CTX_CHECK(ctx, hipGraphLaunch(p->graph.exec, ctx->stream));
+            if (p->graph_tail.exec) CTX_CHECK(ctx, hipGraphLaunch(p->graph_tail.exec, ctx->stream));
             return;
         }
     }
@@ -635,16 +616,6 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipFree(ctx->arg_idx);
     hipFree(ctx->arg_out);
     hipHostFree(ctx->arg_out_host);
-    hipFree(ctx->smp_keys);
-    hipFree(ctx->smp_params);
-    hipFree(ctx->smp_out);
-    hipFree(ctx->smp_win);
-    hipFree(ctx->lp_part);
-    hipFree(ctx->lp_tok);
-    hipFree(ctx->lp_out);
-    hipFree(ctx->top_keys);
-    hipFree(ctx->top_tok);
-    hipFree(ctx->top_val);
     if (ctx->handoff_flag) hipHostFree(ctx->handoff_flag);
     hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1255,7 +1226,7 @@ static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
         const zgml_program_io& o = outputs[0];
         if (p->pin_host && (p->pin_host != o.host_ptr || p->pin_size != o.size)) { // moved: give the registration up for good
             hipStreamSynchronize(s);
-            free_io_graph(p);
+            p->io_graph.reset();
             (void)hipHostUnregister(p->pin_host);
             p->pin_host = p->pin_dev = nullptr, p->pin_off = true;
         } else if (!p->pin_host) {
@@ -1278,7 +1249,7 @@ static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
         }
     } else if (p->pin_host) {
         hipStreamSynchronize(s);
-        free_io_graph(p);
+        p->io_graph.reset();
         (void)hipHostUnregister(p->pin_host);
         p->pin_host = p->pin_dev = nullptr, p->pin_off = true;
     }
@@ -1287,8 +1258,8 @@ static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
         (void)hipGetLastError();
         return false;
     }
-    if (p->io_graph_exec && (p->io_in_rows != in_rows || p->io_out_rows != out_rows || p->io_out_dev != out_dev)) free_io_graph(p);
-    if (!p->io_graph_exec) {
+    if (p->io_graph.exec && (p->io_in_rows != in_rows || p->io_out_rows != out_rows || p->io_out_dev != out_dev)) p->io_graph.reset();
+    if (!p->io_graph.exec) {
         void* in_dev = nullptr;
         if (hipHostGetDevicePointer(&in_dev, p->stage_host, 0) != hipSuccess) {
             (void)hipGetLastError();
@@ -1300,10 +1271,10 @@ static bool execute_io_graph(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_
             run_plan(p, s, 0, p->plan.size());
             gather_words_wide_kernel<<<dim3(out_rows, gy), 256, 0, s>>>(p->out_plan.table_dev, (uint32_t*)out_dev);
         };
-        if (!capture_graph(ctx, s, "program-io", work, &p->io_graph, &p->io_graph_exec)) return false;
+        if (!capture_graph(ctx, s, "program-io", work, &p->io_graph)) return false;
         p->io_in_rows = in_rows, p->io_out_rows = out_rows, p->io_out_dev = out_dev;
     }
-    if (!CTX_CHECK(ctx, hipGraphLaunch(p->io_graph_exec, s))) return true; // (reported; nothing ran)
+    if (!CTX_CHECK(ctx, hipGraphLaunch(p->io_graph.exec, s))) return true; // (reported; nothing ran)
     p->dyn_dirty = false;
     const uint64_t t2 = ctx->host_prof ? now_ns() : 0;
     const uint64_t ts = now_ns();
@@ -1335,7 +1306,7 @@ int zgml_hip_program_pin_outputs(zgml_hip_ctx* ctx, zgml_hip_program* p, int on)
     hipSetDevice(ctx->device);
     if (!on && p->pin_host) {
         hipStreamSynchronize(ctx->stream);
-        free_io_graph(p);
+        p->io_graph.reset();
         (void)hipHostUnregister(p->pin_host);
         (void)hipGetLastError();
         p->pin_host = p->pin_dev = nullptr;

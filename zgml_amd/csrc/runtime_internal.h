@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_block.h"
 #include "kernels.h"
 #include "schedule.h"
 
@@ -85,6 +86,29 @@ struct IoPlan {
     bool dyn_row = false; // (input plan) the table's last row scatters the program's dynamic words (prepare_io)
 };
 
+// dev_block.h over the HIP allocator: the owner of every device block of the resident state, the constraint tables and the
+// context's sampled scratch
+struct HipMem {
+    static void* alloc(size_t bytes) {
+        void* d = nullptr;
+        return hipMalloc(&d, bytes) == hipSuccess ? d : nullptr;
+    }
+    static void free(void* d) { hipFree(d); }
+};
+template <class T>
+using DevBlock = dev_block<T, HipMem>;
+
+// A captured graph and its instantiation: empty, or both. Every graph of a program and of its resident set-up is one of these
+struct GraphSlot {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    void reset() {
+        if (exec) hipGraphExecDestroy(exec);
+        if (graph) hipGraphDestroy(graph);
+        exec = nullptr, graph = nullptr;
+    }
+};
+
 } // namespace zgml_rt
 using namespace zgml_rt;
 
@@ -125,25 +149,22 @@ struct zgml_hip_ctx {
     int64_t* arg_out_host = nullptr; // pinned
     // zgml_hip_sample's scratch, allocated by its first call: the select launch's partial lists (kernels.h: sample_scratch_keys of
     // one row), the parameter row, and [token | candidate count | 256 candidate indices]
-    uint64_t* smp_keys = nullptr;
-    SampleParamsDev* smp_params = nullptr;
-    uint32_t* smp_out = nullptr; // [0, 1]: the token (64 bits); [2]: count; [3, 259): indices
-    uint32_t* smp_win = nullptr; // the window of a penalised zgml_hip_sample, [256] (allocated by the first such call)
-    // zgml_hip_logprobs, and zgml_hip_sample with the `logprobs` field: the block pairs [lp_rows][256][2], the tokens and the values
-    // of lp_rows rows (grown by the call that needs more)
-    float* lp_part = nullptr;
-    uint32_t* lp_tok = nullptr;
-    float* lp_out = nullptr;
-    uint32_t lp_rows = 0;
+    DevBlock<uint64_t> smp_keys;
+    DevBlock<SampleParamsDev> smp_params;
+    DevBlock<uint32_t> smp_out; // [0, 1]: the token (64 bits); [2]: count; [3, 259): indices
+    DevBlock<uint32_t> smp_win; // the window of a penalised zgml_hip_sample, [256] (allocated by the first such call)
+    // zgml_hip_logprobs, and zgml_hip_sample with the `logprobs` field: the block pairs [rows][256][2], the tokens and the values
+    // of `rows` rows (grown by the call that needs more)
+    DevBlock<float> lp_part;
+    DevBlock<uint32_t> lp_tok;
+    DevBlock<float> lp_out;
     std::vector<float> lp_last; // what zgml_hip_logprobs_result hands out: the values of the last call with the `logprobs` word set
     // the alternatives (zgml_hip_top_logprobs, and zgml_hip_sample with the `top_logprobs` word): the select launch's lists over the raw
-    // rows (top_keys_cap keys), [top_rows][64] tokens and values (grown by the call that needs more); and what
-    // zgml_hip_top_logprobs_result hands out, [entries][top_width_last]
-    uint64_t* top_keys = nullptr;
-    uint64_t top_keys_cap = 0;
-    uint32_t* top_tok = nullptr;
-    float* top_val = nullptr;
-    uint32_t top_rows = 0;
+    // rows, [rows][64] tokens and values (grown by the call that needs more); and what zgml_hip_top_logprobs_result hands out,
+    // [entries][top_width_last]
+    DevBlock<uint64_t> top_keys;
+    DevBlock<uint32_t> top_tok;
+    DevBlock<float> top_val;
     std::vector<int64_t> top_tok_last;
     std::vector<float> top_val_last;
     uint32_t top_width_last = 0;
@@ -255,13 +276,11 @@ struct zgml_hip_program {
     // after a small-seq_kv refresh cannot put a KV store and the attention that reads it on one level.
     std::vector<uint32_t> seq_kv_bound;
     std::vector<void*> param_blobs;  // device parameter arrays of batched launches
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    GraphSlot graph;
     // ... in two pieces: hipGraphLaunch costs the host ~0.36 us per kernel node BEFORE the device sees the first one (45-50 us for a
     // 124-launch SmolLM token, all of it on the critical path of a blocking execute_program); the head piece is short, so the device
     // starts after ~10 us and runs it while the host submits the tail
-    hipGraph_t graph_tail = nullptr;
-    hipGraphExec_t graph_tail_exec = nullptr;
+    GraphSlot graph_tail;
     // host I/O staging
     void* stage_host = nullptr; // pinned
     void* stage_dev = nullptr;
@@ -271,8 +290,7 @@ struct zgml_hip_program {
     // read / write host memory through its device mapping; captured for one (input table, output table) pair, dropped with the
     // plan's graphs, with either table and with the staging buffers.
     void* stage_out_host = nullptr; // pinned, outputs
-    hipGraph_t io_graph = nullptr;
-    hipGraphExec_t io_graph_exec = nullptr;
+    GraphSlot io_graph;
     uint32_t io_in_rows = 0, io_out_rows = 0;
     // zgml_hip_program_pin_outputs (opt-in: the caller promises its output buffer stays allocated): a single output handed over at
     // the same address call after call (DeviceInference's logits slice) is registered with the driver after three such calls and
@@ -295,8 +313,7 @@ struct zgml_hip_program {
     std::vector<zgml_shard_point> shard_points;
     uint16_t shard_logits_buf = 0;
     uint64_t shard_vocab = 0;
-    hipGraph_t shard_graph = nullptr;
-    hipGraphExec_t shard_graph_exec = nullptr;
+    GraphSlot shard_graph;
     bool shard_capture_failed = false;
     std::vector<double> shard_point_us; // per gather point: microseconds in the last zgml_hip_shard_profile_step
     // the greedy token as a (max, index) pair per rank instead of a gather of the logits (the last gather point covers the logits
@@ -332,8 +349,9 @@ void free_param_blobs(zgml_hip_program* p); // the device parameter arrays of th
 void free_graph(zgml_hip_program* p); // every captured graph of the program
 void dump_graph(hipGraph_t g, const char* tag);
 void ensure_plan(zgml_hip_program* p);      // build_plan (after free_graph) when the plan is dirty or the context's fuse epoch moved
-// `work` captured from s (thread-local mode) and instantiated; `tag`: dump_graph's, nullptr = not dumped. false: reported, nothing kept
-bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, hipGraph_t* g_out, hipGraphExec_t* e_out);
+// `work` captured from s (thread-local mode) and instantiated into the (empty) slot; `tag`: dump_graph's, nullptr = not dumped.
+// false: reported, the slot stays empty
+bool capture_graph(zgml_hip_ctx* ctx, hipStream_t s, const char* tag, const std::function<void()>& work, GraphSlot* slot);
 void set_dyn_from_ops(zgml_hip_program* p); // ops' dynamic words -> p->dyn_host (sets dyn_dirty on a change)
 void flush_dyn(zgml_hip_program* p);        // p->dyn_host -> p->dyn_dev on the context stream when dirty
 // launches [first, first + count) of the plan, eagerly; `tail`: the resident greedy loop's rider, handed to the plan's last launch alone

@@ -6,6 +6,9 @@
 // dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
 // copy-out at the end. The loops share one skeleton: resident_begin, the per-step lambda (captured once: capture_once, then
 // replay), resident_end; what follows the plan in a sampled step is stated once, by SampledTail.
+// The state they run over owns itself: every device block is a DevBlock (dev_block.h: pointer + the count it was allocated
+// for, freed by its destructor, allocated in all-or-nothing groups by ensure_blocks / grow_tables below) and every captured
+// graph a GraphSlot (runtime_internal.h), so a new field is declared once and remembered nowhere else.
 // No kernels here: the prep / pick kernels are in greedy_tail.hip, the plan's and the sampled tail's in their own files.
 #include "runtime_internal.h"
 #include <atomic>
@@ -23,101 +26,102 @@ static const char* const kSampledFormNames[kSampledForms] = {"sampled", "penaliz
                                                              "sampled_logprobs", "penalized_logprobs", "constrained_logprobs", "constrained_rows_logprobs",
                                                              "sampled_top", "penalized_top", "constrained_top", "constrained_rows_top"};
 
-struct zgml_hip_constraint;
+// an uploaded token automaton (zgml_hip_constraint_create)
+struct zgml_hip_constraint {
+    uint32_t n_states = 0, n_classes = 0, vocab = 0;
+    uint32_t attached = 0; // sequences it is attached to: it is not freed before that is 0
+    DevBlock<uint16_t> class_of, next;
+    DevBlock<uint32_t> forced; // [n_states]: the state's only allowed token or kConstraintNoForced (sample.h)
+};
+
+// The resident set-up of a program. Every device block below is owned by its field (DevBlock: the count it was allocated for is
+// its capacity, deleting the set-up frees it) and every graph by its slot; what is not allocated by the set-up itself is
+// allocated by the first call that needs it, as one group (ensure_blocks), and a block sized by the rows of that first call
+// refuses a later call with more (block_holds). The tables next to the produced tokens grow (grow_tables), which drops the graphs.
 struct zgml_resident {
-    float *embed = nullptr, *cos = nullptr, *sin = nullptr;
+    DevBlock<float> embed, cos, sin;
     uint32_t vocab = 0, d = 0, max_seq = 0, dh = 0, n_rope = 0;
-    float *tok_in = nullptr, *mask = nullptr, *logits = nullptr;
-    float** rope_bufs = nullptr;   // device array of n_rope pointers
-    uint32_t* dyn_kind = nullptr;  // per op: 0 static, 1 store (base + pos * stride), 2 attention (pos + T) — dyn_field's roles, for the prep kernels
-    uint32_t* dyn_base = nullptr;
-    uint32_t* dyn_stride = nullptr;
-    uint32_t* state = nullptr;     // [0] token, [1] pos, [2] produced count
+    float *tok_in = nullptr, *mask = nullptr, *logits = nullptr; // (the program's buffers: not owned)
+    DevBlock<float*> rope_bufs;   // device array of n_rope pointers
+    DevBlock<uint32_t> dyn_kind;  // per op: 0 static, 1 store (base + pos * stride), 2 attention (pos + T) — dyn_field's roles, for the prep kernels
+    DevBlock<uint32_t> dyn_base;
+    DevBlock<uint32_t> dyn_stride;
+    DevBlock<uint32_t> state;     // [0] token, [1] pos, [2] produced count
     uint32_t token_len = 1;        // T of the plan (token_input holds T rows): 1 = decode, > 1 = prefill chunk
-    uint32_t* tok_dev = nullptr;   // prefill: the chunk's T token ids (the only per-chunk host -> device traffic)
-    int64_t* tokens = nullptr;     // produced tokens (device), grown by ensure_tokens: the graphs bake pointer and capacity
-    uint32_t tokens_cap = 0;
+    DevBlock<uint32_t> tok_dev;   // prefill: the chunk's T token ids (the only per-chunk host -> device traffic)
+    DevBlock<int64_t> tokens;     // produced tokens (device), grown by grow_tables: the graphs bake pointer and capacity (its count)
+    uint32_t tokens_cap() const { return (uint32_t)tokens.count(); }
     uint32_t prep_total = 0;       // the prep launches' flat index space (prep_total(): fixed by the set-up, which checks that it fits)
     uint32_t tail_launches = 0;    // launches behind the plan in a step of the single-sequence greedy loop, as its step last ran (or was captured)
-    hipGraph_t graph = nullptr;    // the greedy loop's step: single-sequence, batched or verify, whichever the plan is
-    hipGraphExec_t graph_exec = nullptr;
-    hipGraph_t graph_multi = nullptr; // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
-    hipGraphExec_t graph_multi_exec = nullptr;
+    GraphSlot graph;               // the greedy loop's step: single-sequence, batched or verify, whichever the plan is
+    GraphSlot graph_multi;         // `multi_n` consecutive tokens as one graph (ZGML_HIP_RESIDENT_TOKENS_PER_GRAPH)
     uint32_t multi_n = 0;
     // batched program (zgml_hip_program_set_sequences): per-sequence device state (kernels.h: ResidentBatchPrepArgs), the sequence of
-    // every dynamic op, the pick's scratch (n_seqs rows of partial maxima) and the produced tokens [n_seqs][bcap]
+    // every dynamic op, the pick's scratch (n_seqs rows of partial maxima) and the produced tokens [n_seqs][steps] (grown as `tokens`)
     uint32_t n_seqs = 0;
-    uint32_t* bstate = nullptr;
-    uint32_t* dyn_seq = nullptr;
-    float* bval = nullptr;
-    int64_t* bidx = nullptr;
-    int64_t* btokens = nullptr;
-    uint64_t btokens_cap = 0; // elements
+    DevBlock<uint32_t> bstate;
+    DevBlock<uint32_t> dyn_seq;
+    DevBlock<float> bval;
+    DevBlock<int64_t> bidx;
+    DevBlock<int64_t> btokens;
     // speculative loop over a token_len > 1 plan (zgml_hip_resident_decode_speculative), allocated by its first call: the state
     // words (kernels.h: SpecWord), the token at every position, the provided drafts (max_seq words each: a position past max_seq
     // is never drafted); the T candidates are tok_dev, the rows' partial maxima bval / bidx, the produced tokens `tokens`
-    uint32_t* spec = nullptr;
-    uint32_t* hist = nullptr;
-    uint32_t* drafts = nullptr;
-    uint32_t* picks = nullptr; // the sampled form's token of every logits row, [T] (zgml_hip_resident_decode_speculative_sampled)
+    DevBlock<uint32_t> spec;
+    DevBlock<uint32_t> hist;
+    DevBlock<uint32_t> drafts;
+    DevBlock<uint32_t> picks; // the sampled form's token of every logits row, [T] (zgml_hip_resident_decode_speculative_sampled)
     // speculative loop over a batched plan with tokens_per_seq = Ts >= 2 columns per sequence (token_len = n_seqs * Ts;
     // zgml_hip_resident_decode_batch_speculative), allocated by its first call: per sequence the state words, then one word, the row
     // length of the call's token table (kernels.h: SpecBatchArgs); the history rows [n_seqs][max_seq + 1]; the provided drafts
     // [n_seqs][max_seq]. The candidates are tok_dev, the rows' partial maxima bval / bidx, the produced tokens btokens. The step's
     // graph is its own: no other loop runs on such a plan, and no other call's graph is dropped for it
     uint32_t tokens_per_seq = 1;
-    uint32_t* bspec = nullptr;
-    uint32_t* bhist = nullptr;
-    uint32_t* bdrafts = nullptr;
-    hipGraph_t bspec_graph = nullptr;
-    hipGraphExec_t bspec_graph_exec = nullptr;
+    DevBlock<uint32_t> bspec;
+    DevBlock<uint32_t> bhist;
+    DevBlock<uint32_t> bdrafts;
+    GraphSlot bspec_graph;
     // sampled tail (zgml_hip_resident_decode_sampled / _batch_sampled / _speculative_sampled), allocated by the first such call: one
     // parameter row and one set of partial candidate lists per sequence (per logits row of a token_len > 1 plan, whose verify
-    // step reads parameter row 0 alone)
-    SampleParamsDev* sparams = nullptr;
-    uint64_t* skeys = nullptr;
-    uint32_t sample_rows = 0; // the rows both were allocated for: a call with more is refused on the host, never served short
+    // step reads parameter row 0 alone). sparams' count is the rows both were allocated for
+    DevBlock<SampleParamsDev> sparams;
+    DevBlock<uint64_t> skeys;
     // The sampled loops' graphs, one per form — what the select launch is (SampledSel) times what follows the pick (SampledKind):
     // the forms alternate on one program and invalidate nothing, and the greedy loop's graph stays valid beside them.
     // SampledTail::form() indexes them
-    hipGraph_t sgraph[kSampledForms] = {};
-    hipGraphExec_t sgraph_exec[kSampledForms] = {};
+    GraphSlot sgraph[kSampledForms];
     // penalised sampled tail (sample.h: the penalties), allocated by the first penalised or constrained call of the single or the
     // batched loop: the window of every sequence, [n_seqs][256] token words indexed by position & 255, then lo per sequence (the
     // verify step reads hist / cand instead)
-    uint32_t* swin = nullptr;
+    DevBlock<uint32_t> swin;
     // log-probabilities of the sampled tail (the `logprobs` field of zgml_sampling; logprob.hip), allocated by the first such call:
-    // the block pairs of every logits row, the values next to the produced tokens ([lp_cap]: the layout of tokens / btokens), the
-    // T row values of a verify step, the "written up to" word of every sequence
-    float *lpart = nullptr, *lp = nullptr, *lp_rows = nullptr;
-    uint32_t* lp_written = nullptr;
-    uint64_t lp_cap = 0;
-    uint32_t lp_block_rows = 0; // the rows lpart / lp_rows / lp_written were allocated for, as sample_rows
+    // the block pairs of every logits row, the values next to the produced tokens (the layout and count of tokens / btokens), the
+    // T row values of a verify step (its count: the rows the three were allocated for), the "written up to" word of every sequence
+    DevBlock<float> lpart, lp, lp_rows;
+    DevBlock<uint32_t> lp_written;
     // the alternatives of the sampled tail (the `top_logprobs` word of zgml_sampling; top_logprob.hip), allocated by the first such
     // call: the lists of a select over the RAW rows (what a penalised or constrained step needs beside skeys, the same size), the
-    // pairs next to the produced tokens ([top_cap][64], the layout of lp), the T rows' pairs of a verify step
-    uint64_t* skeys_raw = nullptr;
-    uint32_t *top_tok = nullptr, *top_rows_tok = nullptr;
-    float *top_val = nullptr, *top_rows_val = nullptr;
-    uint64_t top_cap = 0;
+    // pairs next to the produced tokens ([count of the tokens][64], the layout of lp), the T rows' pairs of a verify step
+    DevBlock<uint64_t> skeys_raw;
+    DevBlock<uint32_t> top_tok, top_rows_tok;
+    DevBlock<float> top_val, top_rows_val;
     // constrained sampled tail (sample.h: THE CONSTRAINT; zgml_hip_program_set_constraint), allocated by the first attachment: what
     // is attached to every sequence (one entry for a plain plan), the device table the kernels read (kernels.h:
     // SampleConstraintRow, uploaded at every attach / detach) and the sequences' state words, which the merge launch advances
     std::vector<zgml_hip_constraint*> con;
     uint32_t n_con = 0; // attached sequences
-    SampleConstraintRow* con_rows = nullptr;
-    uint32_t* con_state = nullptr;
+    DevBlock<SampleConstraintRow> con_rows;
+    DevBlock<uint32_t> con_state;
     // constrained verify step (zgml_hip_resident_decode_speculative_constrained), allocated by its first call: the state of every
     // logits row, [T] (spec.h: UNDER A CONSTRAINT) — the draft launch writes them, the constrained-rows select launch reads them
-    uint32_t* row_state = nullptr;
+    DevBlock<uint32_t> row_state;
     // speculative decode with a draft model (zgml_hip_resident_decode_speculative_model), on the TARGET's set-up: the step's graphs
     // hold the launches of two programs, so they belong to the pair — pair_draft and the draft set-up's graph_epoch as it stood at
     // the capture; another draft, or one whose epoch moved, re-captures —, one per form ([0] greedy, [1 + SampledTail::form()]
     // the sampled ones) and apart from every other slot: other calls on either program alternate with the pair's and drop nothing
     zgml_hip_program* pair_draft = nullptr;
     uint64_t pair_epoch = 0;
-    hipGraph_t pair_graph[1 + kSampledForms] = {};
-    hipGraphExec_t pair_graph_exec[1 + kSampledForms] = {};
+    GraphSlot pair_graph[1 + kSampledForms];
     // what a graph that bakes THIS set-up's launches is valid for: a process-wide count, taken at the set-up and again whenever
     // its graphs are dropped (free_resident_graph: a plan rebuild, a grown table), so no two states of any program share a value —
     // a program created at a freed one's address included
@@ -125,25 +129,13 @@ struct zgml_resident {
 };
 using Resident = zgml_resident;
 
-// an uploaded token automaton (zgml_hip_constraint_create)
-struct zgml_hip_constraint {
-    uint32_t n_states = 0, n_classes = 0, vocab = 0;
-    uint32_t attached = 0; // sequences it is attached to: it is not freed before that is 0
-    uint16_t *class_of = nullptr, *next = nullptr; // device
-    uint32_t* forced = nullptr; // device, [n_states]: the state's only allowed token or kConstraintNoForced (sample.h)
-};
-
 namespace zgml_rt {
 
 static std::atomic<uint64_t> g_graph_epoch{0}; // (Resident::graph_epoch)
 
 // the pair's graphs on the target's set-up (Resident::pair_graph)
 static void free_pair_graphs(Resident* r) {
-    for (uint32_t f = 0; f < 1 + kSampledForms; f++) {
-        if (r->pair_graph_exec[f]) hipGraphExecDestroy(r->pair_graph_exec[f]);
-        if (r->pair_graph[f]) hipGraphDestroy(r->pair_graph[f]);
-        r->pair_graph_exec[f] = nullptr, r->pair_graph[f] = nullptr;
-    }
+    for (GraphSlot& g : r->pair_graph) g.reset();
     r->pair_draft = nullptr, r->pair_epoch = 0;
 }
 
@@ -152,66 +144,17 @@ void free_resident_graph(zgml_hip_program* p) {
     if (!r) return;
     r->graph_epoch = ++g_graph_epoch; // (a pair graph on ANOTHER program that bakes this one as its draft is stale from here on)
     free_pair_graphs(r);
-    if (r->graph_exec) hipGraphExecDestroy(r->graph_exec);
-    if (r->graph) hipGraphDestroy(r->graph);
-    r->graph_exec = nullptr, r->graph = nullptr;
-    if (r->graph_multi_exec) hipGraphExecDestroy(r->graph_multi_exec);
-    if (r->graph_multi) hipGraphDestroy(r->graph_multi);
-    r->graph_multi_exec = nullptr, r->graph_multi = nullptr, r->multi_n = 0;
-    if (r->bspec_graph_exec) hipGraphExecDestroy(r->bspec_graph_exec);
-    if (r->bspec_graph) hipGraphDestroy(r->bspec_graph);
-    r->bspec_graph_exec = nullptr, r->bspec_graph = nullptr;
-    for (uint32_t f = 0; f < kSampledForms; f++) {
-        if (r->sgraph_exec[f]) hipGraphExecDestroy(r->sgraph_exec[f]);
-        if (r->sgraph[f]) hipGraphDestroy(r->sgraph[f]);
-        r->sgraph_exec[f] = nullptr, r->sgraph[f] = nullptr;
-    }
+    r->graph.reset(), r->graph_multi.reset(), r->multi_n = 0, r->bspec_graph.reset();
+    for (GraphSlot& g : r->sgraph) g.reset();
 }
 
 void free_resident(zgml_hip_program* p) {
     Resident* r = p->resident;
     if (!r) return;
     free_resident_graph(p);
-    hipFree(r->embed);
-    hipFree(r->cos);
-    hipFree(r->sin);
-    hipFree(r->rope_bufs);
-    hipFree(r->dyn_kind);
-    hipFree(r->dyn_base);
-    hipFree(r->dyn_stride);
-    hipFree(r->state);
-    hipFree(r->tok_dev);
-    hipFree(r->tokens);
-    hipFree(r->bstate);
-    hipFree(r->dyn_seq);
-    hipFree(r->bval);
-    hipFree(r->bidx);
-    hipFree(r->btokens);
-    hipFree(r->spec);
-    hipFree(r->hist);
-    hipFree(r->drafts);
-    hipFree(r->picks);
-    hipFree(r->bspec);
-    hipFree(r->bhist);
-    hipFree(r->bdrafts);
-    hipFree(r->sparams);
-    hipFree(r->skeys);
-    hipFree(r->swin);
-    hipFree(r->lpart);
-    hipFree(r->lp);
-    hipFree(r->lp_rows);
-    hipFree(r->lp_written);
-    hipFree(r->skeys_raw);
-    hipFree(r->top_tok);
-    hipFree(r->top_rows_tok);
-    hipFree(r->top_val);
-    hipFree(r->top_rows_val);
     for (zgml_hip_constraint* c : r->con)
         if (c) c->attached -= 1; // (a program that goes detaches its sequences)
-    hipFree(r->con_rows);
-    hipFree(r->con_state);
-    hipFree(r->row_state);
-    delete r;
+    delete r; // (every block with it)
     p->resident = nullptr;
 }
 
@@ -325,12 +268,7 @@ bool sampling_params(zgml_hip_ctx* ctx, const std::string& who, const zgml_sampl
     return true;
 }
 
-// the window block of the penalised loops: [rows][256] ring words, then lo per row
-bool ensure_window_block(zgml_hip_ctx* ctx, Resident* r, uint32_t rows) {
-    return r->swin || CTX_CHECK(ctx, hipMalloc((void**)&r->swin, (size_t)rows * (kSamplePenaltyMaxWindow + 1) * 4));
-}
-
-// ... and what a call uploads into it for sequence b of `rows`: the last W - 1 of its recent tokens at their positions' slots
+// what a call uploads into the window block of the penalised loops ([rows][256] ring words, then lo per row) for sequence b of `rows`: the last W - 1 of its recent tokens at their positions' slots
 // (the token at start_pos and every later one is filed by the select launch itself), and lo
 void fill_window_block(std::vector<uint32_t>& block, uint32_t rows, uint32_t b, const zgml_sampling& sp, uint32_t start_pos) {
     const uint32_t W = sp.penalty_window, take = W ? std::min(sp.n_recent, W - 1) : 0;
@@ -341,102 +279,90 @@ void fill_window_block(std::vector<uint32_t>& block, uint32_t rows, uint32_t b, 
     block[(size_t)rows * kSamplePenaltyMaxWindow + b] = start_pos - sp.n_recent;
 }
 
+// The one way the loops and the blocking calls get their device blocks, named as (block, count) pairs. Nothing happens when
+// every block holds its count. Else the stream is waited for — a block about to be freed may still be read, by a graph too —
+// and the group is allocated whole or not at all (dev_block.h: dev_ensure): a failed call leaves every block of it empty, so no
+// later call finds the first and takes the rest for granted. `p`: the program whose resident graphs bake the blocks' pointers
+// (nullptr: the context's scratch, which no graph bakes): they are dropped when the call failed and, with `baked`, when a pointer moved
+template <class... A>
+bool ensure_group(zgml_hip_ctx* ctx, zgml_hip_program* p, bool baked, A&&... a) {
+    if (dev_holds(a...)) return true;
+    hipStreamSynchronize(ctx->stream);
+    bool moved = false;
+    const bool ok = dev_ensure(&moved, a...);
+    if (!ok) ctx->fail(std::string("a device block could not be allocated: ") + hipGetErrorString(hipGetLastError()));
+    if (p && moved && (baked || !ok)) free_resident_graph(p);
+    return ok;
+}
+// blocks allocated by the first call that needs them: no graph of an earlier call can hold their pointers
+template <class... A>
+bool ensure_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, A&&... a) {
+    return ensure_group(ctx, p, false, a...);
+}
+// the tables that lie next to the produced tokens (tokens / btokens, the values, the pairs) with room for this call. The graphs
+// bake pointer and capacity: growing one drops them
+template <class... A>
+bool grow_tables(zgml_hip_ctx* ctx, zgml_hip_program* p, A&&... a) {
+    return ensure_group(ctx, p, true, a...);
+}
+
 // A scratch block that exists was sized by the first call that needed it. Every loop of one program asks for the same rows
 // today (the plan fixes them), but a launch over more rows than the block holds would write out of bounds on the device: refused
 // here, on the host
-bool block_holds(zgml_hip_ctx* ctx, const char* what, uint32_t have, uint32_t rows) {
+bool block_holds(zgml_hip_ctx* ctx, const char* what, size_t have, uint32_t rows) {
     if (have >= rows) return true;
     ctx->fail(std::string(what) + " were allocated for " + std::to_string(have) + " logits rows, this call needs " + std::to_string(rows));
     return false;
 }
-
-// the sampled loops' device blocks: `rows` parameter rows and partial candidate lists
-bool ensure_sample_blocks(zgml_hip_ctx* ctx, Resident* r, uint32_t rows) {
-    if (r->sparams && r->skeys) return block_holds(ctx, "the sampled tail's blocks", r->sample_rows, rows);
-    if (!CTX_CHECK(ctx, hipMalloc((void**)&r->sparams, (size_t)rows * sizeof(SampleParamsDev))) ||
-        !CTX_CHECK(ctx, hipMalloc((void**)&r->skeys, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t))))
-        return false;
-    r->sample_rows = rows;
-    return true;
+// ... so every group sized by rows comes through here: `have`, the rows it holds (0: not allocated yet)
+template <class... A>
+bool ensure_row_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, const char* what, size_t have, uint32_t rows, A&&... a) {
+    return (!have || block_holds(ctx, what, have, rows)) && ensure_blocks(ctx, p, a...);
 }
 
-// the log-probability blocks of the sampled loops: `rows` logits rows, values for `cap` produced tokens (the capacity of the
-// token table they lie next to). A graph bakes the pointers: growing the values drops the graphs, as growing the tokens does
-bool ensure_logprob_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, uint64_t cap) {
+// the window block of the penalised loops: [rows][256] ring words, then lo per row
+bool ensure_window_block(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows) {
     Resident* r = p->resident;
-    if (r->lpart && r->lp_rows && r->lp_written) {
-        if (!block_holds(ctx, "the log-probability blocks", r->lp_block_rows, rows)) return false;
-    } else {
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->lpart, (size_t)rows * logprob_blocks(r->vocab) * 2 * sizeof(float))) ||
-            !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_rows, (size_t)rows * sizeof(float))) ||
-            !CTX_CHECK(ctx, hipMalloc((void**)&r->lp_written, (size_t)rows * 4)))
-            return false;
-        r->lp_block_rows = rows;
-    }
-    if (r->lp_cap < cap) {
-        hipStreamSynchronize(ctx->stream);
-        hipFree(r->lp);
-        r->lp = nullptr, r->lp_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->lp, (size_t)cap * sizeof(float)))) return false;
-        r->lp_cap = cap;
-        free_resident_graph(p);
-    }
-    return true;
+    return ensure_row_blocks(ctx, p, "the penalty windows", r->swin.count() / (kSamplePenaltyMaxWindow + 1), rows, r->swin, (size_t)rows * (kSamplePenaltyMaxWindow + 1));
+}
+
+// the sampled loops' device blocks: `rows` parameter rows and partial candidate lists
+bool ensure_sample_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows) {
+    Resident* r = p->resident;
+    return ensure_row_blocks(ctx, p, "the sampled tail's blocks", r->sparams.count(), rows, r->sparams, rows, r->skeys, sample_scratch_keys(r->vocab, rows));
+}
+
+// the log-probability blocks of the sampled loops: `rows` logits rows, and the values next to the produced tokens of `table`
+bool ensure_logprob_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, const DevBlock<int64_t>& table) {
+    Resident* r = p->resident;
+    return ensure_row_blocks(ctx, p, "the log-probability blocks", r->lp_rows.count(), rows, r->lpart, (size_t)rows * logprob_blocks(r->vocab) * 2, r->lp_rows, rows,
+                             r->lp_written, rows) &&
+           grow_tables(ctx, p, r->lp, table.count());
+}
+
+// the blocks of the alternatives of the sampled loops: `rows` logits rows, and the pairs next to the produced tokens of `table`
+bool ensure_top_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, const DevBlock<int64_t>& table) {
+    Resident* r = p->resident;
+    return ensure_row_blocks(ctx, p, "the alternatives' blocks", r->top_rows_tok.count() / kTopLogprobsMax, rows, r->skeys_raw, sample_scratch_keys(r->vocab, rows),
+                             r->top_rows_tok, (size_t)rows * kTopLogprobsMax, r->top_rows_val, (size_t)rows * kTopLogprobsMax) &&
+           grow_tables(ctx, p, r->top_tok, table.count() * kTopLogprobsMax, r->top_val, table.count() * kTopLogprobsMax);
 }
 
 // the context's blocks of zgml_hip_logprobs (and of zgml_hip_sample with the field) for `rows` rows
 bool ensure_ctx_logprob(zgml_hip_ctx* ctx, uint32_t rows) {
-    if (ctx->lp_rows >= rows) return true;
-    hipStreamSynchronize(ctx->stream);
-    hipFree(ctx->lp_part), hipFree(ctx->lp_tok), hipFree(ctx->lp_out);
-    ctx->lp_part = nullptr, ctx->lp_tok = nullptr, ctx->lp_out = nullptr, ctx->lp_rows = 0;
-    if (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->lp_part, (size_t)rows * kLogprobMaxBlocks * 2 * sizeof(float))) ||
-        !CTX_CHECK(ctx, hipMalloc((void**)&ctx->lp_tok, (size_t)rows * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&ctx->lp_out, (size_t)rows * sizeof(float))))
-        return false;
-    ctx->lp_rows = rows;
-    return true;
-}
-
-// the blocks of the alternatives of the sampled loops: `rows` logits rows, pairs for `cap` produced tokens (as the values above:
-// growing them drops the graphs)
-bool ensure_top_blocks(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t rows, uint64_t cap) {
-    Resident* r = p->resident;
-    if (!r->skeys_raw && (!CTX_CHECK(ctx, hipMalloc((void**)&r->skeys_raw, sample_scratch_keys(r->vocab, rows) * sizeof(uint64_t))) ||
-                          !CTX_CHECK(ctx, hipMalloc((void**)&r->top_rows_tok, (size_t)rows * kTopLogprobsMax * 4)) ||
-                          !CTX_CHECK(ctx, hipMalloc((void**)&r->top_rows_val, (size_t)rows * kTopLogprobsMax * sizeof(float)))))
-        return false;
-    if (r->top_cap < cap) {
-        hipStreamSynchronize(ctx->stream);
-        hipFree(r->top_tok), hipFree(r->top_val);
-        r->top_tok = nullptr, r->top_val = nullptr, r->top_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->top_tok, (size_t)cap * kTopLogprobsMax * 4)) ||
-            !CTX_CHECK(ctx, hipMalloc((void**)&r->top_val, (size_t)cap * kTopLogprobsMax * sizeof(float))))
-            return false;
-        r->top_cap = cap;
-        free_resident_graph(p);
-    }
-    return true;
+    return ensure_blocks(ctx, nullptr, ctx->lp_part, (size_t)rows * kLogprobMaxBlocks * 2, ctx->lp_tok, rows, ctx->lp_out, rows);
 }
 
 // the context's blocks of zgml_hip_top_logprobs (and of zgml_hip_sample with the word) for `rows` rows and `keys` list words
 bool ensure_ctx_top(zgml_hip_ctx* ctx, uint32_t rows, uint64_t keys) {
-    if (ctx->top_rows >= rows && ctx->top_keys_cap >= keys) return true;
-    hipStreamSynchronize(ctx->stream);
-    if (ctx->top_keys_cap < keys) {
-        hipFree(ctx->top_keys);
-        ctx->top_keys = nullptr, ctx->top_keys_cap = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->top_keys, (size_t)keys * sizeof(uint64_t)))) return false;
-        ctx->top_keys_cap = keys;
-    }
-    if (ctx->top_rows < rows) {
-        hipFree(ctx->top_tok), hipFree(ctx->top_val);
-        ctx->top_tok = nullptr, ctx->top_val = nullptr, ctx->top_rows = 0;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->top_tok, (size_t)rows * kTopLogprobsMax * 4)) ||
-            !CTX_CHECK(ctx, hipMalloc((void**)&ctx->top_val, (size_t)rows * kTopLogprobsMax * sizeof(float))))
-            return false;
-        ctx->top_rows = rows;
-    }
-    return true;
+    return ensure_blocks(ctx, nullptr, ctx->top_keys, keys, ctx->top_tok, (size_t)rows * kTopLogprobsMax, ctx->top_val, (size_t)rows * kTopLogprobsMax);
+}
+
+// Once a call has enqueued a copy that reads its own stack or heap memory (the state words, the parameter rows, a window), a
+// failure must not return under it: every loop leaves through here from then on
+int fail_after_copies(hipStream_t s) {
+    hipStreamSynchronize(s);
+    return -1;
 }
 
 // What zgml_hip_top_logprobs_result hands out, from a call's downloaded pairs (rows of kTopLogprobsMax, as the device holds
@@ -511,20 +437,6 @@ SampledTail resident_tail(const Resident* r, uint32_t rows, SampledSel sel, Samp
     return t;
 }
 
-// The produced-token table of a loop (tokens / btokens) with room for `need` tokens. The graphs baked the old pointer and
-// capacity: growing the table drops them. A failed allocation leaves no table and no capacity
-template <class Cap>
-bool ensure_tokens(zgml_hip_ctx* ctx, zgml_hip_program* p, int64_t*& table, Cap& cap, uint64_t need) {
-    if (cap >= need) return true;
-    hipStreamSynchronize(ctx->stream);
-    hipFree(table);
-    table = nullptr, cap = 0;
-    if (!CTX_CHECK(ctx, hipMalloc((void**)&table, (size_t)need * 8))) return false;
-    cap = (Cap)need;
-    free_resident_graph(p);
-    return true;
-}
-
 // What the two batched loops ask of a request, refused before anything is enqueued: -> the steps of the call (the largest
 // count) and the last position of every sequence. tokens_out (and n_produced) are filled only once nothing is refused.
 // A sequence that stops before the last step repeats its step at the position BEHIND its last token (it rewrites that KV column
@@ -589,18 +501,18 @@ BatchPrep batch_prep_args(const zgml_hip_program* p) {
 // A loop's step becomes a graph the first time it runs with graphs on (a failed capture leaves the slot empty: eager below).
 // `wait`: host memory that a copy enqueued before this reads must not be in flight when the capture begins
 template <class Step>
-void capture_once(zgml_hip_ctx* ctx, hipStream_t s, const std::string& name, bool wait, Step step, hipGraph_t* graph, hipGraphExec_t* exec) {
-    if (!ctx->opt_graph || *exec) return;
+void capture_once(zgml_hip_ctx* ctx, hipStream_t s, const std::string& name, bool wait, Step step, GraphSlot& slot) {
+    if (!ctx->opt_graph || slot.exec) return;
     if (wait) hipStreamSynchronize(s);
-    capture_graph(ctx, s, name.c_str(), [&] { step(s); }, graph, exec);
+    capture_graph(ctx, s, name.c_str(), [&] { step(s); }, &slot);
 }
 
 // ... and runs n times: the graph, or the step's launches
 template <class Step>
-void replay(hipStream_t s, hipGraphExec_t exec, uint32_t n, Step step) {
+void replay(hipStream_t s, const GraphSlot& slot, uint32_t n, Step step) {
     for (uint32_t i = 0; i < n; i++) {
-        if (exec)
-            hipGraphLaunch(exec, s);
+        if (slot.exec)
+            hipGraphLaunch(slot.exec, s);
         else
             step(s);
     }
@@ -662,8 +574,9 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
                   " columns (not a multiple of them)");
         return -1;
     }
-    Resident* r = new Resident();
-    p->resident = r;
+    // built here and published only when everything has succeeded: every failure below leaves a program without a set-up
+    std::unique_ptr<Resident> owner(new Resident());
+    Resident* const r = owner.get();
     r->graph_epoch = ++g_graph_epoch;
     r->token_len = T;
     // > 0: the T columns are n_seqs sequences of tokens_per_seq consecutive positions each — one (zgml_hip_resident_decode_batch) or
@@ -675,7 +588,6 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
     const size_t n_ops = p->ops.size();
     if (prep_total(r, n_ops) > UINT32_MAX) {
         ctx->fail("resident_setup: token_len x (d_model + max_seq + 2 n_rope d_head) + ops exceeds 2^32 - 1, the prep launch's index space");
-        free_resident(p);
         return -1;
     }
     r->prep_total = (uint32_t)prep_total(r, n_ops);
@@ -690,17 +602,12 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
     std::vector<uint32_t> kind(n_ops, 0), base(n_ops, 0), stride(n_ops, 0);
     for (size_t i = 0; i < n_ops; i++) // the device's copy of dyn_field for the ops that move (the prep kernels evaluate DynField::at)
         if (const DynField f = dyn_field(p->ops[i]); f.moves()) kind[i] = f.role == DynField::SeqKv ? 2 : 1, base[i] = f.base, stride[i] = f.stride;
-    const size_t tab = (size_t)d->max_seq * d->d_head * 4, emb = (size_t)d->vocab * d->d_model * 4;
-    bool ok = CTX_CHECK(ctx, hipMalloc((void**)&r->embed, emb)) && CTX_CHECK(ctx, hipMalloc((void**)&r->cos, tab)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->sin, tab)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->rope_bufs, (ropes.size() + 1) * sizeof(float*))) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_kind, (n_ops + 1) * 4)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_base, (n_ops + 1) * 4)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_stride, (n_ops + 1) * 4)) &&
-              CTX_CHECK(ctx, hipMalloc((void**)&r->state, 4 * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->tok_dev, (size_t)T * 4)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->embed, d->token_embed, emb)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->cos, d->cos_table, tab)) &&
-              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->sin, d->sin_table, tab)) &&
+    const size_t tab = (size_t)d->max_seq * d->d_head, emb = (size_t)d->vocab * d->d_model; // elements
+    bool ok = ensure_blocks(ctx, nullptr, r->embed, emb, r->cos, tab, r->sin, tab, r->rope_bufs, ropes.size() + 1, r->dyn_kind, n_ops + 1, r->dyn_base, n_ops + 1,
+                            r->dyn_stride, n_ops + 1, r->state, 4, r->tok_dev, T) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->embed, d->token_embed, emb * 4)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->cos, d->cos_table, tab * 4)) &&
+              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->sin, d->sin_table, tab * 4)) &&
               CTX_CHECK(ctx, h2d_sync(ctx->stream, r->rope_bufs, ropes.data(), ropes.size() * sizeof(float*))) &&
               CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_kind, kind.data(), n_ops * 4)) &&
               CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_base, base.data(), n_ops * 4)) &&
@@ -709,14 +616,11 @@ int zgml_hip_resident_setup(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_r
         std::vector<uint32_t> seq(n_ops + 1, 0);
         for (size_t i = 0; i < n_ops; i++) seq[i] = kind[i] && i < p->op_seq.size() && p->op_seq[i] != UINT32_MAX ? p->op_seq[i] : 0;
         const size_t pairs = (size_t)T * argmax_batch_blocks(d->vocab); // (a row per column: n_seqs, or n_seqs * tokens_per_seq of a verify step)
-        ok = CTX_CHECK(ctx, hipMalloc((void**)&r->bstate, ((size_t)4 * r->n_seqs + 1) * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&r->dyn_seq, (n_ops + 1) * 4)) &&
-             CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) && CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))) &&
+        ok = ensure_blocks(ctx, nullptr, r->bstate, (size_t)4 * r->n_seqs + 1, r->dyn_seq, n_ops + 1, r->bval, pairs, r->bidx, pairs) &&
              CTX_CHECK(ctx, h2d_sync(ctx->stream, r->dyn_seq, seq.data(), n_ops * 4));
     }
-    if (!ok) {
-        free_resident(p);
-        return -1;
-    }
+    if (!ok) return -1;
+    p->resident = owner.release();
     // The resident kernels write token_input, attn_mask and the rope buffers from the device, outside the op list: to the hoist
     // analysis those buffers look like constants (never written by an op), so a `repeat` that broadcasts one of them would have
     // been run once at plan build and its stale copy read ever after. Today's LLaMA stream only repeats gamma and the
@@ -750,7 +654,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     resident_begin(p, [&] {
         return !n_steps || (positions_in_bounds(p, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(p, 1, [&](uint32_t) { return start_pos + n_steps - 1; }));
     });
-    if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_steps)) return -1;
+    if (!grow_tables(ctx, p, r->tokens, n_steps)) return -1;
     const Prep prep = prep_args(p, r->state, r->state /* the token is state[0] */);
     // Per token [plan] [stage 2 + advance + embedding row], one full prep in front of the call's first step. A step's patches
     // come from the step before it, through ordinary kernel boundaries: the launch that leaves the argmax pairs also writes the
@@ -764,7 +668,7 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
     // token's patches alone — SLOWER: SmolLM-135M 1756 against 1773 tok/s, Llama-2-7B 790 against 817. Second form — every
     // workgroup writes the position-only patches, the last arriver the embedding row — a wash: 1777-1782 against 1768-1780, 838
     // against 842; profiles/r05_token_tail_ab.txt. The present form adds no synchronisation inside a launch.)
-    const ArgmaxAdvance adv{r->state, r->tokens, r->tokens_cap, r->embed, r->tok_in, r->d};
+    const ArgmaxAdvance adv{r->state, r->tokens, r->tokens_cap(), r->embed, r->tok_in, r->d};
     DenseHeadTail head;
     head.logits = r->logits, head.vocab = r->vocab, head.pair_val = ctx->arg_val, head.pair_idx = ctx->arg_idx;
     head.ahead = ResidentAhead{prep.a, prep.total - r->token_len * r->d};
@@ -778,24 +682,24 @@ int zgml_hip_resident_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t fi
         r->tail_launches = head.pairs ? 1 : 2;
     };
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // (a stack array: no wait before the capture, unlike the batched loop's vector)
-    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return -1;
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s))) return fail_after_copies(s);
     if (n_steps) launch_resident_prep(s, prep.a, prep.total); // the first step's patches, for (first_token, start_pos)
-    capture_once(ctx, s, "resident", false, one_token, &r->graph, &r->graph_exec);
+    capture_once(ctx, s, "resident", false, one_token, r->graph);
     // several tokens per graph launch: everything a token needs is produced on the device from the state words, so a graph may
     // simply hold the launches of G consecutive tokens (experiment: is there a per-graph gap on the device?)
     const uint32_t per_graph = (uint32_t)sw().hip_resident_tokens_per_graph;
     const auto tokens_of_a_graph = [&] {
         for (uint32_t t = 0; t < per_graph; t++) one_token(s);
     };
-    if (ctx->opt_graph && r->graph_exec && per_graph > 1 && n_steps >= per_graph && !r->graph_multi_exec &&
-        capture_graph(ctx, s, nullptr, tokens_of_a_graph, &r->graph_multi, &r->graph_multi_exec))
+    if (ctx->opt_graph && r->graph.exec && per_graph > 1 && n_steps >= per_graph && !r->graph_multi.exec &&
+        capture_graph(ctx, s, nullptr, tokens_of_a_graph, &r->graph_multi))
         r->multi_n = per_graph;
     for (uint32_t i = 0; i < n_steps;) {
-        if (r->graph_multi_exec && n_steps - i >= r->multi_n) {
-            hipGraphLaunch(r->graph_multi_exec, s);
+        if (r->graph_multi.exec && n_steps - i >= r->multi_n) {
+            hipGraphLaunch(r->graph_multi.exec, s);
             i += r->multi_n;
-        } else if (r->graph_exec) {
-            hipGraphLaunch(r->graph_exec, s);
+        } else if (r->graph.exec) {
+            hipGraphLaunch(r->graph.exec, s);
             i++;
         } else {
             one_token(s);
@@ -833,7 +737,7 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
     resident_begin(p, [&] {
         return positions_in_bounds(p, 1, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) && positions_in_bounds(p, 1, [&](uint32_t i) { return last_pos[p->op_seq[i]]; });
     });
-    if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * steps)) return -1;
+    if (!grow_tables(ctx, p, r->btokens, (size_t)B * steps)) return -1;
     const BatchPrep prep = batch_prep_args(p);
     auto one_step = [&](hipStream_t st) {
         launch_resident_batch_prep(st, prep.a, prep.total);
@@ -845,11 +749,11 @@ int zgml_hip_resident_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const
     st0[4 * B] = steps; // row length of the device token table of this call
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->bstate, st0.data(), st0.size() * 4, hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s))) // (-1: what a sequence leaves behind its count)
-        return -1;
+        return fail_after_copies(s);
     // st0, a heap vector, is read by the copy above: it must not die under a pageable-memory copy in flight. (The
     // single-sequence loop hands over a 16-byte stack array instead and does without the wait.)
-    capture_once(ctx, s, "resident_batch", true, one_step, &r->graph, &r->graph_exec);
-    replay(s, r->graph_exec, steps, one_step);
+    capture_once(ctx, s, "resident_batch", true, one_step, r->graph);
+    replay(s, r->graph, steps, one_step);
     std::vector<int64_t> got((size_t)B * steps);
     hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
     bool ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
@@ -875,30 +779,27 @@ int64_t zgml_hip_sample(zgml_hip_ctx* ctx, zgml_hip_program* p, uint16_t buf_idx
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     constexpr size_t out_words = 3 + kSampleMaxK;
-    if (!ctx->smp_keys && (!CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_keys, (size_t)kSampleMaxSlices * kSampleMaxK * sizeof(uint64_t))) ||
-                           !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_params, sizeof(SampleParamsDev))) ||
-                           !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_out, out_words * 4))))
-        return -1;
+    if (!ensure_blocks(ctx, nullptr, ctx->smp_keys, (size_t)kSampleMaxSlices * kSampleMaxK, ctx->smp_params, 1, ctx->smp_out, out_words)) return -1;
     if (sampling->logprobs && !ensure_ctx_logprob(ctx, 1)) return -1;
     const uint32_t top = sp.top_logprobs; // (0 without the `logprobs` word)
     if (top && !ensure_ctx_top(ctx, 1, sample_scratch_keys(n, 1))) return -1;
-    if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return -1;
+    if (sp.pen_active && !ensure_blocks(ctx, nullptr, ctx->smp_win, kSamplePenaltyMaxWindow)) return -1;
+    if (!CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_params, &sp, sizeof(sp), hipMemcpyHostToDevice, s))) return fail_after_copies(s);
     // sequence 0's constraint, when the row is a row of the automaton's vocabulary: its state masks the pick and advances over it
     const Resident* const res = p->resident;
     const bool constrained = res && res->n_con && res->con[0] && n == res->vocab;
     SampledTail tail;
     tail.sel = SampledTail::sel_of(constrained, sp.pen_active), tail.kind = SampledTail::kind_of(sampling->logprobs, top);
     tail.keys = ctx->smp_keys, tail.keys_raw = ctx->top_keys, tail.params = ctx->smp_params, tail.part = ctx->lp_part;
-    tail.adv.position = position, tail.adv.out = (int64_t*)ctx->smp_out, tail.adv.cand = ctx->smp_out + 2;
+    tail.adv.position = position, tail.adv.out = (int64_t*)ctx->smp_out.get(), tail.adv.cand = ctx->smp_out + 2;
     if (sp.pen_active) { // the window: the last W of the recent tokens, the token whose logits these are last
         const uint32_t take = std::min(sampling->n_recent, sp.window);
-        if (!ctx->smp_win && !CTX_CHECK(ctx, hipMalloc((void**)&ctx->smp_win, kSamplePenaltyMaxWindow * 4))) return -1;
-        if (take && !CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_win, sampling->recent + (sampling->n_recent - take), (size_t)take * 4, hipMemcpyHostToDevice, s))) return -1;
+        if (take && !CTX_CHECK(ctx, hipMemcpyAsync(ctx->smp_win, sampling->recent + (sampling->n_recent - take), (size_t)take * 4, hipMemcpyHostToDevice, s))) return fail_after_copies(s);
         tail.win.list = ctx->smp_win, tail.win.n_list = take;
     }
     if (constrained) tail.con = constraint_args(res);
     // the values over the raw row, behind the pick: the token is read where the merge launch stored it
-    tail.top.chosen.out = ctx->lp_out, tail.top.chosen.token64 = (const int64_t*)ctx->smp_out;
+    tail.top.chosen.out = ctx->lp_out, tail.top.chosen.token64 = (const int64_t*)ctx->smp_out.get();
     tail.top.top_tok = ctx->top_tok, tail.top.top_val = ctx->top_val, tail.top.params = ctx->smp_params;
     tail.launch(s, p->bufs[buf_idx] + offset, n);
     float lp = 0.0f;
@@ -938,10 +839,9 @@ zgml_hip_constraint* zgml_hip_constraint_create(zgml_hip_ctx* ctx, const zgml_to
     // the forced token of every state, for the verify step under a constraint: once, beside the two tables
     std::vector<uint32_t> count(dfa->n_classes), first(dfa->n_classes), forced(dfa->n_states);
     constraint_forced(dfa, count.data(), first.data(), forced.data());
-    if (!CTX_CHECK(ctx, hipMalloc((void**)&c->class_of, cls)) || !CTX_CHECK(ctx, hipMalloc((void**)&c->next, nxt)) || !CTX_CHECK(ctx, hipMalloc((void**)&c->forced, frc)) ||
+    if (!ensure_blocks(ctx, nullptr, c->class_of, cls / 2, c->next, nxt / 2, c->forced, frc / 4) ||
         !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->class_of, dfa->class_of, cls)) || !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->next, dfa->next, nxt)) ||
         !CTX_CHECK(ctx, h2d_sync(ctx->stream, c->forced, forced.data(), frc))) {
-        hipFree(c->class_of), hipFree(c->next), hipFree(c->forced);
         delete c;
         return nullptr;
     }
@@ -956,7 +856,6 @@ void zgml_hip_constraint_free(zgml_hip_ctx* ctx, zgml_hip_constraint* c) {
     }
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    hipFree(c->class_of), hipFree(c->next), hipFree(c->forced);
     delete c;
 }
 
@@ -975,8 +874,9 @@ int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* p, uint
     if (!c && (r->con.empty() || !r->con[seq])) return 0; // nothing attached, nothing to detach
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
-    if (!r->con_rows && (!CTX_CHECK(ctx, hipMalloc((void**)&r->con_rows, (size_t)rows * sizeof(SampleConstraintRow))) ||
-                         !CTX_CHECK(ctx, hipMalloc((void**)&r->con_state, (size_t)rows * 4)) || !CTX_CHECK(ctx, hipMemsetAsync(r->con_state, 0, (size_t)rows * 4, s)))) // (on the stream of the uploads below: it is a non-blocking one, which a memset on the null stream is not ordered with)
+    const bool first = !r->con_rows;
+    if (!ensure_row_blocks(ctx, p, "the constraint table", r->con_rows.count(), rows, r->con_rows, rows, r->con_state, rows) ||
+        (first && !CTX_CHECK(ctx, hipMemsetAsync(r->con_state, 0, (size_t)rows * 4, s)))) // (on the stream of the uploads below: it is a non-blocking one, which a memset on the null stream is not ordered with)
         return -1;
     r->con.resize(rows, nullptr);
     if (r->con[seq]) r->con[seq]->attached -= 1, r->n_con -= 1;
@@ -991,7 +891,7 @@ int zgml_hip_program_set_constraint(zgml_hip_ctx* ctx, zgml_hip_program* p, uint
     const uint32_t st = c ? state : 0;
     const bool ok = CTX_CHECK(ctx, hipMemcpyAsync(r->con_rows, table.data(), table.size() * sizeof(SampleConstraintRow), hipMemcpyHostToDevice, s)) &&
                     CTX_CHECK(ctx, hipMemcpyAsync(r->con_state + seq, &st, 4, hipMemcpyHostToDevice, s)) && CTX_CHECK(ctx, hipStreamSynchronize(s));
-    return ok ? 0 : -1;
+    return ok ? 0 : fail_after_copies(s);
 }
 
 int64_t zgml_hip_program_constraint_state(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t seq) {
@@ -1125,16 +1025,16 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     const bool penalized = sp.pen_active != 0, lp = sampling->logprobs != 0, top = sp.top_logprobs != 0; // (top: only with lp)
     // a constraint attached: the constrained select launch, which serves penalties on and off (its graph bakes the window block)
     const bool constrained = r->n_con != 0;
-    if (!ensure_sample_blocks(ctx, r, 1) || ((penalized || constrained) && !ensure_window_block(ctx, r, 1))) return -1;
-    if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_steps)) return -1;
-    if (lp && !ensure_logprob_blocks(ctx, p, 1, r->tokens_cap)) return -1;
-    if (top && !ensure_top_blocks(ctx, p, 1, r->tokens_cap)) return -1;
+    if (!ensure_sample_blocks(ctx, p, 1) || ((penalized || constrained) && !ensure_window_block(ctx, p, 1))) return -1;
+    if (!grow_tables(ctx, p, r->tokens, n_steps)) return -1;
+    if (lp && !ensure_logprob_blocks(ctx, p, 1, r->tokens)) return -1;
+    if (top && !ensure_top_blocks(ctx, p, 1, r->tokens)) return -1;
     const Prep prep = prep_args(p, r->state, r->state /* the token is state[0] */);
     SampledTail tail = resident_tail(r, 1, SampledTail::sel_of(constrained, penalized), SampledTail::kind_of(lp, top));
-    tail.adv.state = r->state, tail.adv.tokens = r->tokens, tail.adv.cap = r->tokens_cap;
+    tail.adv.state = r->state, tail.adv.tokens = r->tokens, tail.adv.cap = r->tokens_cap();
     tail.win.ring = r->swin, tail.win.lo = r->swin + kSamplePenaltyMaxWindow;
     LogprobTarget& lt = tail.top.chosen;
-    lt.out = r->lp, lt.state = r->state, lt.emitted = r->tokens, lt.written = r->lp_written, lt.cap = r->tokens_cap;
+    lt.out = r->lp, lt.state = r->state, lt.emitted = r->tokens, lt.written = r->lp_written, lt.cap = r->tokens_cap();
     tail.top.top_tok = r->top_tok, tail.top.top_val = r->top_val;
     auto one_token = [&](hipStream_t st) {
         launch_resident_prep(st, prep.a, prep.total);
@@ -1145,20 +1045,20 @@ int zgml_hip_resident_decode_sampled(zgml_hip_ctx* ctx, zgml_hip_program* p, uin
     if (penalized) {
         win0.assign(kSamplePenaltyMaxWindow + 1, 0);
         fill_window_block(win0, 1, 0, *sampling, start_pos);
-        if (!CTX_CHECK(ctx, hipMemcpyAsync(r->swin, win0.data(), win0.size() * 4, hipMemcpyHostToDevice, s))) return -1;
+        if (!CTX_CHECK(ctx, hipMemcpyAsync(r->swin, win0.data(), win0.size() * 4, hipMemcpyHostToDevice, s))) return fail_after_copies(s);
     }
     const uint32_t st0[4] = {first_token, start_pos, 0, 0}; // ([3]: set by a stop token)
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, &sp, sizeof(sp), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_steps * 8, s)) || // (-1: what a stopped sequence leaves behind its stop token)
         (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, 4, s))))
-        return -1;
+        return fail_after_copies(s);
     // (a penalised call replays a graph of its own, and so do a constrained call and a call with log-probabilities: the kinds of
     // call alternate on one program and invalidate nothing)
-    hipGraphExec_t& exec = r->sgraph_exec[tail.form()];
+    GraphSlot& slot = r->sgraph[tail.form()];
     // (the copies above read this stack frame: none in flight when the capture begins)
-    capture_once(ctx, s, std::string("resident_") + kSampledFormNames[tail.form()], true, one_token, &r->sgraph[tail.form()], &exec);
-    replay(s, exec, n_steps, one_token);
+    capture_once(ctx, s, std::string("resident_") + kSampledFormNames[tail.form()], true, one_token, slot);
+    replay(s, slot, n_steps, one_token);
     uint32_t st1[4] = {0, 0, 0, 0};
     hipMemcpyAsync(tokens_out, r->tokens, (size_t)n_steps * 8, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(st1, r->state, sizeof(st1), hipMemcpyDeviceToHost, s);
@@ -1205,10 +1105,10 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     bool top = false; // ... and one with alternatives: the top form of the finish for all (a row with the count 0 is all padding)
     for (uint32_t b = 0; b < B; b++) penalized = penalized || sp[b].pen_active, lp = lp || per_seq[b].logprobs, top = top || sp[b].top_logprobs;
     const bool constrained = r->n_con != 0; // one sequence with a constraint: the constrained launch for all (a row without one computes what it did)
-    if (!ensure_sample_blocks(ctx, r, B) || ((penalized || constrained) && !ensure_window_block(ctx, r, B))) return -1;
-    if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * steps)) return -1;
-    if (lp && !ensure_logprob_blocks(ctx, p, B, r->btokens_cap)) return -1;
-    if (top && !ensure_top_blocks(ctx, p, B, r->btokens_cap)) return -1;
+    if (!ensure_sample_blocks(ctx, p, B) || ((penalized || constrained) && !ensure_window_block(ctx, p, B))) return -1;
+    if (!grow_tables(ctx, p, r->btokens, (size_t)B * steps)) return -1;
+    if (lp && !ensure_logprob_blocks(ctx, p, B, r->btokens)) return -1;
+    if (top && !ensure_top_blocks(ctx, p, B, r->btokens)) return -1;
     const BatchPrep prep = batch_prep_args(p);
     SampledTail tail = resident_tail(r, B, SampledTail::sel_of(constrained, penalized), SampledTail::kind_of(lp, top));
     tail.adv.state = r->bstate, tail.adv.tokens = r->btokens, tail.adv.n_seqs = B;
@@ -1225,7 +1125,7 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
     if (penalized) {
         win0.assign((size_t)B * (kSamplePenaltyMaxWindow + 1), 0);
         for (uint32_t b = 0; b < B; b++) fill_window_block(win0, B, b, per_seq[b], start_pos[b]);
-        if (!CTX_CHECK(ctx, hipMemcpyAsync(r->swin, win0.data(), win0.size() * 4, hipMemcpyHostToDevice, s))) return -1;
+        if (!CTX_CHECK(ctx, hipMemcpyAsync(r->swin, win0.data(), win0.size() * 4, hipMemcpyHostToDevice, s))) return fail_after_copies(s);
     }
     std::vector<uint32_t> st0((size_t)4 * B + 1, 0), st1((size_t)4 * B + 1, 0);
     for (uint32_t b = 0; b < B; b++) st0[b] = first_tokens[b], st0[B + b] = start_pos[b], st0[2 * B + b] = n_steps[b];
@@ -1234,11 +1134,11 @@ int zgml_hip_resident_decode_batch_sampled(zgml_hip_ctx* ctx, zgml_hip_program* 
         !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, sp.data(), sp.size() * sizeof(SampleParamsDev), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * steps * 8, s)) || // (-1: what a sequence leaves behind its count)
         (lp && !CTX_CHECK(ctx, hipMemsetAsync(r->lp_written, 0, (size_t)B * 4, s))))
-        return -1;
-    hipGraphExec_t& exec = r->sgraph_exec[tail.form()];
+        return fail_after_copies(s);
+    GraphSlot& slot = r->sgraph[tail.form()];
     // (as the greedy batched loop: no pageable copy in flight when the capture begins)
-    capture_once(ctx, s, std::string("resident_batch_") + kSampledFormNames[tail.form()], true, one_step, &r->sgraph[tail.form()], &exec);
-    replay(s, exec, steps, one_step);
+    capture_once(ctx, s, std::string("resident_batch_") + kSampledFormNames[tail.form()], true, one_step, slot);
+    replay(s, slot, steps, one_step);
     std::vector<int64_t> got((size_t)B * steps);
     hipMemcpyAsync(got.data(), r->btokens, got.size() * 8, hipMemcpyDeviceToHost, s);
     hipMemcpyAsync(st1.data(), r->bstate, st1.size() * 4, hipMemcpyDeviceToHost, s);
@@ -1290,7 +1190,7 @@ int64_t zgml_hip_resident_prefill(zgml_hip_ctx* ctx, zgml_hip_program* p, const 
     const uint32_t st0[4] = {0, start_pos, 0, 0};
     if (!CTX_CHECK(ctx, hipMemcpyAsync(r->state, st0, sizeof(st0), hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->tok_dev, tokens, (size_t)n_tokens * 4, hipMemcpyHostToDevice, s)))
-        return -1;
+        return fail_after_copies(s);
     const Prep prep = prep_args(p, r->state, r->tok_dev);
     launch_resident_prep(s, prep.a, prep.total);
     // through enqueue, not run_plan: one execution per call, so the program's own graphs (captured once, shared with
@@ -1424,18 +1324,14 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         return positions_in_bounds(draft, 1, [&](uint32_t) { return start_pos; }) && positions_in_bounds(draft, 1, [&](uint32_t) { return start_pos + n_tokens + T - 2; });
     });
     const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1;
-    if (!r->spec) {
-        const size_t pairs = (size_t)T * nblk;
-        if (!CTX_CHECK(ctx, hipMalloc((void**)&r->spec, kSpecWords * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->hist, (size_t)hist_cap * 4)) ||
-            !CTX_CHECK(ctx, hipMalloc((void**)&r->drafts, (size_t)r->max_seq * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->bval, pairs * sizeof(float))) ||
-            !CTX_CHECK(ctx, hipMalloc((void**)&r->bidx, pairs * sizeof(int64_t))))
-            return -1;
-    }
-    if (sampled && (!ensure_sample_blocks(ctx, r, T) || (!r->picks && !CTX_CHECK(ctx, hipMalloc((void**)&r->picks, (size_t)T * 4))))) return -1;
-    if (constrained && !r->row_state && !CTX_CHECK(ctx, hipMalloc((void**)&r->row_state, (size_t)T * 4))) return -1;
-    if (!ensure_tokens(ctx, p, r->tokens, r->tokens_cap, n_tokens)) return -1;
-    if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens_cap)) return -1;
-    if (top && !ensure_top_blocks(ctx, p, T, r->tokens_cap)) return -1;
+    if (!ensure_row_blocks(ctx, p, "the verify step's blocks", r->bval.count() / nblk, T, r->spec, kSpecWords, r->hist, hist_cap, r->drafts, r->max_seq,
+                           r->bval, (size_t)T * nblk, r->bidx, (size_t)T * nblk))
+        return -1;
+    if (sampled && (!ensure_sample_blocks(ctx, p, T) || !ensure_row_blocks(ctx, p, "the rows' picks", r->picks.count(), T, r->picks, T))) return -1;
+    if (constrained && !ensure_row_blocks(ctx, p, "the rows' constraint states", r->row_state.count(), T, r->row_state, T)) return -1;
+    if (!grow_tables(ctx, p, r->tokens, n_tokens)) return -1;
+    if (lp && !ensure_logprob_blocks(ctx, p, T, r->tokens)) return -1;
+    if (top && !ensure_top_blocks(ctx, p, T, r->tokens)) return -1;
     uint32_t w0[kSpecWords] = {0};
     w0[kSpecTok] = first_token, w0[kSpecPos] = start_pos, w0[kSpecWanted] = n_tokens, w0[kSpecMode] = model ? 2 : o.mode, w0[kSpecNgram] = ngram;
     w0[kSpecNDrafts] = std::min(n_drafts, r->max_seq), w0[kSpecStart] = start_pos, w0[kSpecHistLo] = o.n_history ? 0 : start_pos;
@@ -1445,11 +1341,11 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         (o.n_history && !CTX_CHECK(ctx, hipMemcpyAsync(r->hist, o.history, (size_t)o.n_history * 4, hipMemcpyHostToDevice, s))) ||
         !CTX_CHECK(ctx, hipMemcpyAsync(r->hist + start_pos, &first_token, 4, hipMemcpyHostToDevice, s)) ||
         (w0[kSpecNDrafts] && !CTX_CHECK(ctx, hipMemcpyAsync(r->drafts, o.drafts, (size_t)w0[kSpecNDrafts] * 4, hipMemcpyHostToDevice, s))))
-        return -1;
+        return fail_after_copies(s);
     if (sampled && (!CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, &sp, sizeof(sp), hipMemcpyHostToDevice, s)) || // (row 0: the one set every row reads)
                     !CTX_CHECK(ctx, hipMemsetAsync(r->tokens, 0xFF, (size_t)n_tokens * 8, s))))                // (-1: what a stop token leaves behind itself)
-        return -1;
-    SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap};
+        return fail_after_copies(s);
+    SpecArgs sa{r->spec, r->hist, r->drafts, r->tok_dev, r->tokens, r->bval, r->bidx, T, nblk, r->vocab, hist_cap, r->tokens_cap()};
     SampledTail tail; // (sampled form only; the greedy form launches none of it)
     if (sampled) { // rows of one sequence: row j samples at the step's run position + j and reads parameter row 0
         // (the constrained-rows select serves penalties on and off, as the constrained one does)
@@ -1501,10 +1397,9 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         r->pair_draft = draft, r->pair_epoch = dr->graph_epoch;
     }
     const uint32_t pair_slot = sampled ? 1 + tail.form() : 0;
-    hipGraphExec_t& exec = dr ? r->pair_graph_exec[pair_slot] : sampled ? r->sgraph_exec[tail.form()] : r->graph_exec;
-    hipGraph_t& graph = dr ? r->pair_graph[pair_slot] : sampled ? r->sgraph[tail.form()] : r->graph;
+    GraphSlot& slot = dr ? r->pair_graph[pair_slot] : sampled ? r->sgraph[tail.form()] : r->graph;
     // (the sampled form waits, as the sampled loops: no copy from this stack frame in flight when the capture begins)
-    capture_once(ctx, s, std::string(dr ? "resident_spec_model" : "resident_spec") + (sampled ? std::string("_") + kSampledFormNames[tail.form()] : std::string()), sampled, one_step, &graph, &exec);
+    capture_once(ctx, s, std::string(dr ? "resident_spec_model" : "resident_spec") + (sampled ? std::string("_") + kSampledFormNames[tail.form()] : std::string()), sampled, one_step, slot);
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish, reads the count back, repeats
     // (`wanted` is read back with the words: a stop token of the sampled form sets it to the produced count, which ends the loop)
     uint32_t w1[kSpecWords] = {0};
@@ -1513,7 +1408,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
     bool ok = true;
     for (uint32_t produced = 0, wanted = n_tokens; ok && produced < wanted;) {
         const uint32_t round = (wanted - produced + T - 1) / T;
-        replay(s, exec, round, one_step);
+        replay(s, slot, round, one_step);
         steps_run += round;
         hipMemcpyAsync(w1, r->spec, sizeof(w1), hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
@@ -1636,14 +1531,14 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
                positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]] + n_tokens[p->op_seq[i]]; });
     });
     const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1, n_words = B * kSpecWords + 1, rows = B * Ts;
-    if (!r->bspec && (!CTX_CHECK(ctx, hipMalloc((void**)&r->bspec, (size_t)n_words * 4)) || !CTX_CHECK(ctx, hipMalloc((void**)&r->bhist, (size_t)B * hist_cap * 4)) ||
-                      !CTX_CHECK(ctx, hipMalloc((void**)&r->bdrafts, (size_t)B * r->max_seq * 4))))
+    if (!ensure_row_blocks(ctx, p, "the batched verify step's blocks", r->bhist.count() / hist_cap * Ts, rows, r->bspec, n_words, r->bhist, (size_t)B * hist_cap,
+                           r->bdrafts, (size_t)B * r->max_seq))
         return -1;
     // (sampled form only) every block for B Ts logits rows: the select keys, a parameter row per sequence (the block has one per
     // logits row), the rows' picks, the rows' values and the block pairs; the emitted values lie as the tokens do
-    if (sampled && (!ensure_sample_blocks(ctx, r, rows) || (!r->picks && !CTX_CHECK(ctx, hipMalloc((void**)&r->picks, (size_t)rows * 4))))) return -1;
-    if (!ensure_tokens(ctx, p, r->btokens, r->btokens_cap, (uint64_t)B * max_tokens)) return -1;
-    if (lp && !ensure_logprob_blocks(ctx, p, rows, r->btokens_cap)) return -1;
+    if (sampled && (!ensure_sample_blocks(ctx, p, rows) || !ensure_row_blocks(ctx, p, "the rows' picks", r->picks.count(), rows, r->picks, rows))) return -1;
+    if (!grow_tables(ctx, p, r->btokens, (size_t)B * max_tokens)) return -1;
+    if (lp && !ensure_logprob_blocks(ctx, p, rows, r->btokens)) return -1;
     std::vector<uint32_t> w0(n_words, 0), w1(n_words, 0);
     w0[(size_t)B * kSpecWords] = max_tokens; // row length of the device token table of this call
     bool up = true;
@@ -1662,8 +1557,7 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     if (!up || !CTX_CHECK(ctx, hipMemcpyAsync(r->bspec, w0.data(), w0.size() * 4, hipMemcpyHostToDevice, s)) ||
         !CTX_CHECK(ctx, hipMemsetAsync(r->btokens, 0xFF, (size_t)B * max_tokens * 8, s)) || // (-1: what a sequence leaves behind its count, or its stop token)
         (sampled && !CTX_CHECK(ctx, hipMemcpyAsync(r->sparams, sp.data(), sp.size() * sizeof(SampleParamsDev), hipMemcpyHostToDevice, s)))) {
-        hipStreamSynchronize(s); // (w0 and sp are read by copies that may be in flight)
-        return -1;
+        return fail_after_copies(s); // (w0 and sp are read by copies that may be in flight)
     }
     SpecBatchArgs sa{{r->bspec, r->bhist, r->bdrafts, r->tok_dev, r->btokens, r->bval, r->bidx, Ts, nblk, r->vocab, hist_cap, 0 /* the device word */}, B, r->max_seq};
     SampledTail tail; // (sampled form only; the greedy form launches none of it)
@@ -1690,10 +1584,9 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
             launch_argmax_rows_stage1(st, r->logits, r->vocab, rows, r->bval, r->bidx);
         launch_spec_batch_accept(st, sa);
     };
-    hipGraphExec_t& exec = sampled ? r->sgraph_exec[tail.form()] : r->bspec_graph_exec;
-    hipGraph_t& graph = sampled ? r->sgraph[tail.form()] : r->bspec_graph;
+    GraphSlot& slot = sampled ? r->sgraph[tail.form()] : r->bspec_graph;
     // (as the batched loops: no pageable copy in flight when the capture begins)
-    capture_once(ctx, s, sampled ? std::string("resident_batch_spec_") + kSampledFormNames[tail.form()] : std::string("resident_batch_spec"), true, one_step, &graph, &exec);
+    capture_once(ctx, s, sampled ? std::string("resident_batch_spec_") + kSampledFormNames[tail.form()] : std::string("resident_batch_spec"), true, one_step, slot);
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish the sequence with the most
     // tokens left, reads the counts back, repeats. (`wanted` is read back with the words: a stop token of the sampled form sets
     // its sequence's to the produced count, which shortens the round)
@@ -1704,7 +1597,7 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
         uint32_t round = 0;
         for (uint32_t b = 0; b < B; b++) round = std::max(round, (wanted[b] - produced[b] + Ts - 1) / Ts);
         if (!round) break;
-        replay(s, exec, round, one_step);
+        replay(s, slot, round, one_step);
         steps_run += round;
         hipMemcpyAsync(w1.data(), r->bspec, w1.size() * 4, hipMemcpyDeviceToHost, s);
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));

@@ -313,29 +313,27 @@ int64_t zgml_hip_shard_step(zgml_hip_ctx* ctx, zgml_hip_program* p, const zgml_p
     hipStream_t s = ctx->stream;
     ensure_plan(p);
     if (zgml_hip_stage_inputs(ctx, p, inputs, n_inputs) != 0) return -1;
-    if (sw().shard_graph && ctx->opt_graph && !p->shard_graph_exec && !p->shard_capture_failed) {
+    if (sw().shard_graph && ctx->opt_graph && !p->shard_graph.exec && !p->shard_capture_failed) {
         // relaxed capture: RCCL may touch its own (already created) resources while it enqueues
-        hipGraph_t g = nullptr;
+        GraphSlot& g = p->shard_graph;
         bool ok = hipStreamSynchronize(s) == hipSuccess && hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
         if (ok) {
             zgml_hip_enqueue_staged(ctx, p);
             const bool seg = shard_segments(ctx, p); // (incl. the greedy token into ctx->arg_out)
             hipMemcpyAsync(ctx->arg_out_host, ctx->arg_out, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-            ok = hipStreamEndCapture(s, &g) == hipSuccess && g && seg;
+            ok = hipStreamEndCapture(s, &g.graph) == hipSuccess && g.graph && seg;
         }
-        if (ok) ok = hipGraphInstantiate(&p->shard_graph_exec, g, nullptr, nullptr, 0) == hipSuccess;
-        if (ok) {
-            p->shard_graph = g;
-        } else {
-            if (g) hipGraphDestroy(g);
-            p->shard_graph_exec = nullptr;
+        if (ok) ok = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) == hipSuccess;
+        if (!ok) {
+            g.exec = nullptr;
+            g.reset();
             p->shard_capture_failed = true; // eager from now on (all ranks decide alike: same program, same runtime)
             (void)hipGetLastError();
             if (!ctx->err.empty()) return -1;
         }
     }
-    if (p->shard_graph_exec) {
-        if (!CTX_CHECK(ctx, hipGraphLaunch(p->shard_graph_exec, s))) return -1;
+    if (p->shard_graph.exec) {
+        if (!CTX_CHECK(ctx, hipGraphLaunch(p->shard_graph.exec, s))) return -1;
     } else {
         zgml_hip_enqueue_staged(ctx, p);
         if (!shard_segments(ctx, p)) return -1;
@@ -400,6 +398,6 @@ int zgml_hip_device_count(void) {
     return n;
 }
 
-int zgml_hip_shard_step_mode(zgml_hip_program* p) { return !p ? -1 : (p->shard_graph_exec ? 1 : 0); } // 1 = one graph per token
+int zgml_hip_shard_step_mode(zgml_hip_program* p) { return !p ? -1 : (p->shard_graph.exec ? 1 : 0); } // 1 = one graph per token
 
 } // extern "C"
