@@ -679,11 +679,11 @@ int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* ha
  *   n_seqs produced counts back and repeats until every sequence is done; a round in which a sequence with tokens left produced
  *   nothing is an error.
  * Refused with -1 and an error on the context, before anything is enqueued: a plain plan or a batched plan with one column per
- *   sequence; a constraint attached to any sequence; per sequence everything zgml_hip_resident_decode_speculative refuses (a
+ *   sequence; a constraint attached to any sequence (zgml_hip_resident_decode_batch_speculative_constrained serves one); per sequence everything zgml_hip_resident_decode_speculative refuses (a
  *   token — first, history, drafts — >= vocab, n_history neither 0 nor start_pos[b], mode > 1, ngram > 4); the bound above;
  *   n_tokens[b] > max_tokens; NULL arrays. All n_tokens zero: returns 0 and touches nothing.
  * zgml_hip_resident_decode_batch and zgml_hip_resident_decode_batch_sampled refuse a plan with more than one column per sequence
- * (this call and zgml_hip_resident_decode_batch_speculative_sampled are the ones that run it); the single-sequence speculative calls keep refusing every batched plan. Blocking. */
+ * (this call, zgml_hip_resident_decode_batch_speculative_sampled and _batch_speculative_constrained are the ones that run it); the single-sequence speculative calls keep refusing every batched plan. Blocking. */
 int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens,
                                                const uint32_t* start_pos, const uint32_t* n_tokens, uint32_t max_tokens,
                                                const zgml_spec_decode* per_seq /* [n_seqs] or NULL */,
@@ -918,7 +918,7 @@ int zgml_hip_resident_decode_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_pro
  *   before that one.
  * Blocking. Returns 0 on success. Refused with -1 and an error on the context that names the sequence, before anything is
  *   enqueued: everything zgml_hip_resident_decode_batch_speculative refuses (a plain plan, one column per sequence, a constraint
- *   attached to any sequence — constraints under batched speculation are not served —, the per-sequence requests, the bound,
+ *   attached to any sequence — zgml_hip_resident_decode_batch_speculative_constrained serves those —, the per-sequence requests, the bound,
  *   n_tokens[b] > max_tokens, NULL arrays); per sequence everything zgml_hip_resident_decode_speculative_sampled refuses of the
  *   parameters, recent != NULL included; sampling = NULL. All n_tokens zero: returns 0 and touches nothing on the device. */
 int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens,
@@ -948,7 +948,9 @@ int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_h
  *   token (resident prefill, zgml_hip_sample for the first token, then the sampled loop: no host bookkeeping), and
  *   candidates_out receives the constrained candidates. zgml_hip_resident_prefill is unchanged: the greedy token it returns is
  *   unconstrained.
- *   zgml_hip_resident_decode_speculative_constrained (below) honours sequence 0's in the verify step of a token_len = T plan.
+ *   zgml_hip_resident_decode_speculative_constrained (below) honours sequence 0's in the verify step of a token_len = T plan,
+ *   zgml_hip_resident_decode_batch_speculative_constrained (below) every sequence's own in the verify step of a batched plan with
+ *   tokens_per_seq >= 2.
  * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
  *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative,
  *   zgml_hip_resident_decode_batch_speculative_sampled, zgml_hip_resident_decode_speculative_model (a constraint on its target or
@@ -1010,6 +1012,43 @@ int zgml_hip_resident_decode_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip
                                                      uint32_t n_tokens, const zgml_spec_decode* opt, const zgml_sampling* sampling,
                                                      int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
                                                      zgml_spec_stats* stats /* may be NULL */);
+
+/* ── Constrained speculative decode under batching: zgml_hip_resident_decode_batch_speculative_sampled whose verify rows walk the
+ * token automata attached to the sequences. Sequence b of a batched plan with T = tokens_per_seq >= 2 columns per sequence runs
+ * exactly the loop of zgml_hip_resident_decode_speculative_constrained with sampling[b], per_seq[b] and the automaton and state
+ * attached to it through zgml_hip_program_set_constraint(.., seq = b, ..). Every sequence may have its own automaton — class
+ * counts and state counts may differ —, and sequences with and without one sit side by side. With no constraint attached to any
+ * sequence the call IS zgml_hip_resident_decode_batch_speculative_sampled: same tokens, same launches, same graphs.
+ * Rule. No new one (zgml_amd/csrc/spec.h, UNDER A CONSTRAINT, and sample.h): per attached sequence the pass over its candidates
+ *   from its state — forced tokens placed, pads re-evaluated, row_state[b * T + j] —, the constrained pick of logits row b * T + j
+ *   under that row's state with sampling[b], u from counter word 0 = the run position of b + j, the dead-end cut, and the advance
+ *   of b's state word over exactly the tokens b emitted, a stop token included.
+ * A sequence without an automaton behaves exactly as in zgml_hip_resident_decode_batch_speculative_sampled: the pass leaves its
+ *   candidates alone, none of its rows is dead, its picks are unmasked, and stats[b].drafted grows by its mode's real drafts alone.
+ * Dead end. A reached state of b without tokens finishes b as a stop token does: n_produced[b] counts what came out (possibly
+ *   nothing), the rest of its row is -1, its state stays; b idles from there, the other sequences go on, and the call returns 0
+ *   with no error on the context. The host's round loop reads b's wanted word back before it judges a round: a sequence whose
+ *   device words say wanted == produced is finished, not failed.
+ * Exactness. Per sequence the contract of the single-sequence call; the other sequences of the batch — their automata, drafts and
+ *   parameters — change neither a sequence's tokens nor its statistics nor its state.
+ * Idling, the bound start_pos[b] + n_tokens[b] + T <= max_seq, resuming (two calls give the stream and the state of one), stop
+ *   tokens, penalties (sampling[b].recent must be NULL) and `logprobs` (over the RAW row, unaffected by the mask; the quiet NaN
+ *   behind n_produced[b] and in the whole row of a sequence without the word) are those of
+ *   zgml_hip_resident_decode_batch_speculative_sampled. `top_logprobs` stays ignored, as there.
+ * Launches. One graph launch per step, no launch more than the sampled batched step: [draft, n_seqs sequences] [prep, n_seqs * T
+ *   columns] [plan] [select, grid (slices, T, n_seqs)] [merge + pick, grid (1, T, n_seqs)] ([log-probability launches]) [accept +
+ *   advance, n_seqs sequences]. The one select serves rows with and without penalties, with and without an automaton. Graphs of
+ *   its own (with and without `logprobs`): constrained calls, detached sampled calls and greedy batched speculative calls
+ *   alternate on one program and invalidate nothing.
+ * Blocking. Returns 0 on success. Refused with -1 and an error on the context, before anything is enqueued: everything
+ *   zgml_hip_resident_decode_batch_speculative_sampled refuses except the attached constraint. */
+int zgml_hip_resident_decode_batch_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip_program* handle, const uint32_t* first_tokens,
+                                                           const uint32_t* start_pos, const uint32_t* n_tokens, uint32_t max_tokens,
+                                                           const zgml_spec_decode* per_seq /* [n_seqs] or NULL */,
+                                                           const zgml_sampling* sampling /* [n_seqs], never NULL */,
+                                                           int64_t* tokens_out /* [n_seqs][max_tokens] */,
+                                                           uint32_t* n_produced /* [n_seqs] or NULL */,
+                                                           zgml_spec_stats* stats /* [n_seqs] or NULL */);
 
 /* ── Speculative decode with a draft model: a second resident program drafts for the target (rule: zgml_amd/csrc/spec.h, DRAFTS
  * FROM A MODEL). A sibling of zgml_hip_resident_decode_speculative and _speculative_sampled, not a mode of them: zgml_spec_decode

@@ -321,6 +321,7 @@ HIP_SYMBOLS = [
     "zgml_hip_kv_move",
     "zgml_hip_resident_decode_batch_speculative_sampled",
     "zgml_hip_resident_decode_speculative_model",
+    "zgml_hip_resident_decode_batch_speculative_constrained",
 ]
 
 class KvLaneC(C.Structure):
@@ -496,6 +497,10 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_resident_decode_batch_speculative_sampled.restype = i32
         lib.zgml_hip_resident_decode_batch_speculative_sampled.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, C.POINTER(SpecDecodeC),
                                                                            C.POINTER(SamplingC), vp, C.POINTER(u32), C.POINTER(SpecStatsC)]
+    if hasattr(lib, "zgml_hip_resident_decode_batch_speculative_constrained"):  # absent from an older build loaded through ZGML_HIP_LIB (A/B runs)
+        lib.zgml_hip_resident_decode_batch_speculative_constrained.restype = i32
+        lib.zgml_hip_resident_decode_batch_speculative_constrained.argtypes = [vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32, C.POINTER(SpecDecodeC),
+                                                                               C.POINTER(SamplingC), vp, C.POINTER(u32), C.POINTER(SpecStatsC)]
     if hasattr(lib, "zgml_hip_resident_decode_speculative_model"):  # absent from an older build loaded through ZGML_HIP_LIB (A/B runs)
         lib.zgml_hip_resident_decode_speculative_model.restype = i32
         lib.zgml_hip_resident_decode_speculative_model.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(SamplingC), vp, C.POINTER(u32),

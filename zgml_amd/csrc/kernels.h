@@ -535,7 +535,9 @@ void launch_spec_accept(hipStream_t s, const SpecArgs& a);
 // words[n_seqs * kSpecWords], the row length of this call's token table (a device word: the graph serves every max_tokens). A
 // sequence that has its count idles at its END position (the single loop idles one position in front of it): its state, history
 // and counters stay as they are. The sampled form (zgml_hip_resident_decode_batch_speculative_sampled): picks + b * T, sparams + b,
-// lp_rows + b * T and lp_out + b * cap likewise; top_* and con_* stay null.
+// lp_rows + b * T and lp_out + b * cap likewise; top_* stay null. The constrained form
+// (zgml_hip_resident_decode_batch_speculative_constrained): con_row + b — the sequence's row of the table, con_active = 0 when nothing
+// is attached to it: its rows are then free (spec.h: kSpecRowFree) —, con_state + b, row_state + b * T.
 struct SpecBatchArgs {
     SpecArgs a;
     uint32_t n_seqs, drafts_stride;
@@ -637,9 +639,10 @@ inline uint32_t sample_merge_keys(uint32_t slices, uint32_t run) {
 // The forms of the select launch, ONE body in four instantiations (sample.hip): the plain one; with the penalties of params[]
 // applied to the logits before the selection (`win`); with the rows' constraints as well (`con`) — that one also serves rows
 // without a constraint and rows with or without penalties, but not the rows of a verify step (adv.picks). Those have the fourth:
-// kSelConstrainedRows, the T rows of ONE constrained sequence's verify step — con.rows[0] is the automaton of all of them, con.state
-// holds T words, the state of every ROW (SpecArgs::row_state; a dead row writes pads alone), parameter row 0 and the verify
-// step's window serve all rows.
+// kSelConstrainedRows, the rows of a constrained verify step, T per sequence (one sequence, or the B of a batched plan) — con.rows[seq]
+// is the automaton of sequence seq's rows (con_active = 0: none, its rows select as the penalised form does), con.state holds a word
+// per ROW, its state (SpecArgs::row_state; a dead row writes pads alone), parameter row seq and the verify step's window of
+// sequence seq serve its rows.
 enum SampledSel { kSelPlain, kSelPenalized, kSelConstrained, kSelConstrainedRows, kSampledSels };
 // `rows` rows of n logits (row stride n), 1 <= n < 2^32: [select in the form `sel`: sample_slices(n) sorted lists of the 256 largest
 // keys per row] [merge to the row's candidates + pick + advance; the same launch behind every form, with kSelConstrained it

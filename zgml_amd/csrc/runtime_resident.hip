@@ -113,7 +113,8 @@ struct zgml_resident {
     DevBlock<SampleConstraintRow> con_rows;
     DevBlock<uint32_t> con_state;
     // constrained verify step (zgml_hip_resident_decode_speculative_constrained), allocated by its first call: the state of every
-    // logits row, [T] (spec.h: UNDER A CONSTRAINT) — the draft launch writes them, the constrained-rows select launch reads them
+    // logits row, [T] (spec.h: UNDER A CONSTRAINT) — the draft launch writes them, the constrained-rows select launch reads them —,
+    // [n_seqs * tokens_per_seq] on a batched plan (zgml_hip_resident_decode_batch_speculative_constrained)
     DevBlock<uint32_t> row_state;
     // speculative decode with a draft model (zgml_hip_resident_decode_speculative_model), on the TARGET's set-up: the step's graphs
     // hold the launches of two programs, so they belong to the pair — pair_draft and the draft set-up's graph_epoch as it stood at
@@ -1478,9 +1479,15 @@ namespace {
 // stage — one launch more; logits row r is candidate row r % Ts of sequence r / Ts (kernels.h: SampleAdvance) and reads that
 // sequence's parameter set —, graphs of its own in the slots no other sampled loop can use on such a plan, and a stop token ends
 // its sequence early: the others go on. Everything the greedy form enqueues is what it enqueued before the sampled one existed.
+// `honours_constraint` (zgml_hip_resident_decode_batch_speculative_constrained; spec.h: UNDER A CONSTRAINT): the sampled form, and
+// with a constraint attached to any sequence the constrained one, as in spec_decode() — the same launches with the constrained-rows
+// select in the place of the select (row b Ts + j: sequence b's automaton, its own state word), the draft and the accept launch
+// of every attached sequence also walking its automaton, graphs of their own; the rows of a sequence without one are free
+// (spec.h: kSpecRowFree). A reached state without a token finishes its sequence as a stop token does: the others go on. With
+// nothing attached it is the sampled form to the launch.
 int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, const uint32_t* first_tokens, const uint32_t* start_pos,
                       const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, bool sampled, const zgml_sampling* sampling,
-                      int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
+                      int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats, bool honours_constraint = false) {
     if (!ctx || !p) return -1;
     Resident* r = p->resident;
     if (!r || !r->n_seqs || !p->n_seqs) {
@@ -1492,7 +1499,8 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
         ctx->fail(who + ": the batched plan holds one column per sequence (a verify step needs tokens_per_seq >= 2)");
         return -1;
     }
-    if (refuse_constrained(ctx, p, who.c_str())) return -1;
+    if (!honours_constraint && refuse_constrained(ctx, p, who.c_str())) return -1;
+    const bool constrained = honours_constraint && r->n_con != 0;
     if (!first_tokens || !start_pos || !n_tokens || (max_tokens && !tokens_out)) {
         ctx->fail(who + ": NULL array (first_tokens, start_pos, n_tokens, or tokens_out with max_tokens > 0)");
         return -1;
@@ -1537,6 +1545,7 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     // (sampled form only) every block for B Ts logits rows: the select keys, a parameter row per sequence (the block has one per
     // logits row), the rows' picks, the rows' values and the block pairs; the emitted values lie as the tokens do
     if (sampled && (!ensure_sample_blocks(ctx, p, rows) || !ensure_row_blocks(ctx, p, "the rows' picks", r->picks.count(), rows, r->picks, rows))) return -1;
+    if (constrained && !ensure_row_blocks(ctx, p, "the rows' constraint states", r->row_state.count(), rows, r->row_state, rows)) return -1;
     if (!grow_tables(ctx, p, r->btokens, (size_t)B * max_tokens)) return -1;
     if (lp && !ensure_logprob_blocks(ctx, p, rows, r->btokens)) return -1;
     std::vector<uint32_t> w0(n_words, 0), w1(n_words, 0);
@@ -1562,8 +1571,13 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     SpecBatchArgs sa{{r->bspec, r->bhist, r->bdrafts, r->tok_dev, r->btokens, r->bval, r->bidx, Ts, nblk, r->vocab, hist_cap, 0 /* the device word */}, B, r->max_seq};
     SampledTail tail; // (sampled form only; the greedy form launches none of it)
     if (sampled) { // row b Ts + j: sequence b's parameter row, its run position + j, its history and candidates
-        tail = resident_tail(r, rows, SampledTail::sel_of(false, penalized), SampledTail::kind_of(lp, false)); // (the alternatives are not kept: include/zgml_hip.h)
+        // (the constrained-rows select serves penalties on and off, as in spec_decode())
+        tail = resident_tail(r, rows, constrained ? kSelConstrainedRows : SampledTail::sel_of(false, penalized), SampledTail::kind_of(lp, false)); // (the alternatives are not kept: include/zgml_hip.h)
         tail.con = SampleConstraint{};
+        if (constrained) { // sequence b's automaton — its row of the table — for its Ts rows, and a state per row
+            tail.con.rows = r->con_rows, tail.con.state = r->row_state;
+            sa.a.con_row = r->con_rows, sa.a.con_state = r->con_state, sa.a.row_state = r->row_state;
+        }
         sa.a.picks = r->picks, sa.a.sparams = r->sparams;
         tail.adv.picks = r->picks, tail.adv.pos_word = r->bspec + kSpecRunPos, tail.adv.rows_per_seq = Ts, tail.adv.pos_stride = kSpecWords;
         // (the `logprobs` field only) every row's value of its pick; the accept launch copies each sequence's emitted prefix
@@ -1603,11 +1617,14 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
         ok = CTX_CHECK(ctx, hipStreamSynchronize(s));
         for (uint32_t b = 0; ok && b < B; b++) {
             const uint32_t now = std::min(w1[(size_t)b * kSpecWords + kSpecProduced], n_tokens[b]);
-            if (produced[b] < wanted[b] && now <= produced[b]) { // (every step of a sequence with tokens left emits at least one)
+            const uint32_t left = std::max(now, std::min(w1[(size_t)b * kSpecWords + kSpecWanted], n_tokens[b])); // (the device's word: a stop token or a dead end has cut it)
+            // (every step of a sequence with tokens left emits at least one — unless its constraint's state allows no token: the
+            // sequence is then finished, wanted == produced on the device, and it idles from here on)
+            if (produced[b] < wanted[b] && now <= produced[b] && left != now) {
                 ctx->fail(who + ": a round of verify steps produced nothing (sequence " + std::to_string(b) + ")");
                 ok = false;
             }
-            produced[b] = now, wanted[b] = std::max(now, std::min(w1[(size_t)b * kSpecWords + kSpecWanted], n_tokens[b]));
+            produced[b] = now, wanted[b] = left;
         }
     }
     SampledCopyOut out{tail.kind};
@@ -1646,6 +1663,13 @@ int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_h
                                                        const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
     return spec_decode_batch(ctx, p, "resident_decode_batch_speculative_sampled", first_tokens, start_pos, n_tokens, max_tokens, per_seq, true, sampling, tokens_out,
                              n_produced, stats);
+}
+
+int zgml_hip_resident_decode_batch_speculative_constrained(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
+                                                           const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq,
+                                                           const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
+    return spec_decode_batch(ctx, p, "resident_decode_batch_speculative_constrained", first_tokens, start_pos, n_tokens, max_tokens, per_seq, true, sampling,
+                             tokens_out, n_produced, stats, true);
 }
 
 } // extern "C"

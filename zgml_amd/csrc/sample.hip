@@ -21,9 +21,11 @@
 //             16 KiB — into LDS, reads class_of[i] beside row[i] when it fills a chunk and writes the pad 0 for a token that is
 //             not allowed: it is no candidate at all; the penalty rewrite acts on the allowed window tokens alone.
 //     sample_select_constrained_rows_kernel  the T rows of a constrained sequence's verify step (spec.h: UNDER A CONSTRAINT;
-//             DESIGN section 4.18): the constrained form with one automaton for all rows and a state word per ROW — every
-//             workgroup stages next[row_state[b]] —, parameter row 0 and the verify step's window. A dead row (no state) writes
-//             its 256 pads and skips the fill.
+//             DESIGN section 4.18), or the T rows of each of B sequences (zgml_hip_resident_decode_batch_speculative_constrained;
+//             DESIGN section 4.21): the constrained form with the automaton of the row's SEQUENCE — the grid plane — and a state
+//             word per ROW — every workgroup stages next[row_state[b]] —, the sequence's parameter row and the verify step's
+//             window. A dead row (no state) writes its 256 pads and skips the fill; the rows of a sequence without an automaton
+//             are free (spec.h) and go through the penalised instantiation of the body inside this kernel.
 //   [merge + pick + advance]  grid (1, rows), 1024 threads, the same launch behind every form: the slices' lists — at most
 //             32 x 256 keys, 64 KiB of LDS — are loaded with every second list reversed, which is the state of a bitonic sort
 //             after its 256-runs: only the merge stages from 512 up remain. Then the threads fill p[j] (sample_prob), thread 0
@@ -88,14 +90,16 @@ __device__ __forceinline__ uint32_t select_window(const SampleParamsDev& sp, con
 // words (from kSelPenalized on); crow: the state row's kConstraintMaxClasses words (kSelConstrained). `active` (the row has
 // penalties) and `constrained` are uniform over the workgroup: the barriers hang on them. A row with neither computes what the
 // plain form computes, a row with penalties alone what the penalised form computes — a batched sequence beside others.
-// kSelConstrainedRows: cr is the one automaton of all rows and con_state[b] the state of ROW b.
+// kSelConstrainedRows: cr is the automaton of the row's SEQUENCE and con_state[b] the state of ROW b (spec.h: dead, or a state of
+// cr). A FREE row — its sequence has no automaton — selects as the penalised or the plain form does: the rows kernel hands it to
+// the penalised instantiation (below), so here `constrained` holds for every row that is not all pads, as in the one-sequence call.
 template <SampledSel kForm>
 __device__ __forceinline__ void select_body(uint64_t* s, uint32_t* win, uint16_t* crow, const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part,
                                             const SampleParamsDev* __restrict__ params, const SampleAdvance& adv, const SampleWindow& w, const SampleConstraintRow& cr, const uint32_t* con_state) {
     constexpr bool kRows = kForm == kSelConstrainedRows, kMask = kForm == kSelConstrained || kRows, kWindow = kForm != kSelPlain;
     const uint32_t b = sample_row().row;
     const bool constrained = kMask && cr.con_active != 0;
-    if (kRows && (!constrained || con_state[b] == kConstraintDead)) { // (uniform, before any barrier) no candidates: all pads
+    if (kRows && (!constrained || !spec_row_selects(con_state[b]))) { // (uniform, before any barrier) a dead row has no candidates: all pads
         uint64_t* out = part + ((uint64_t)b * gridDim.x + blockIdx.x) * kSampleMaxK;
         for (uint32_t t = threadIdx.x; t < kSampleMaxK; t += kSelBlock) out[t] = 0;
         return;
@@ -111,8 +115,8 @@ __device__ __forceinline__ void select_body(uint64_t* s, uint32_t* win, uint16_t
         for (uint32_t t = threadIdx.x; t < cr.n_classes; t += kSelBlock) crow[t] = from[t];
     }
     // (read in place; the plain form has no parameters and reads none)
-    // (a verify row reads its sequence's parameter row; the constrained-rows form has one sequence)
-    const SampleParamsDev* const sp = kWindow ? params + (kRows ? 0 : !kMask && adv.picks ? sample_row().seq : b) : nullptr;
+    // (a verify row reads its sequence's parameter row: the block index, a scalar — nothing divides)
+    const SampleParamsDev* const sp = kWindow ? params + (kRows || (!kMask && adv.picks) ? sample_row().seq : b) : nullptr;
     const bool active = kWindow && sp->pen_active != 0;
     uint32_t tok = 0, count = 0;
     if (active) {
@@ -168,14 +172,19 @@ __global__ void __launch_bounds__(kSelBlock) sample_select_constrained_kernel(co
     select_body<kSelConstrained>(s, win, crow, v, n, len, part, params, adv, w, cr, con.state);
 }
 
-// the rows of a verify step: the automaton of sequence 0, con.state = the T row states
+// the rows of a verify step: plane blockIdx.z holds the rows of sequence blockIdx.z, which walk that sequence's automaton (one
+// plane: the single-sequence call, sequence 0's); con.state = the row states of all planes
 __global__ void __launch_bounds__(kSelBlock) sample_select_constrained_rows_kernel(const float* __restrict__ v, uint32_t n, uint32_t len, uint64_t* __restrict__ part,
                                                                                    const SampleParamsDev* __restrict__ params, SampleAdvance adv, SampleWindow w,
                                                                                    SampleConstraint con) {
     __shared__ uint64_t s[kSelKeys];
     __shared__ uint32_t win[kSamplePenaltyMaxWindow];
     __shared__ uint16_t crow[kConstraintMaxClasses];
-    const SampleConstraintRow cr = con.rows[0];
+    const SampleConstraintRow cr = con.rows[blockIdx.z];
+    if (!cr.con_active && spec_row_selects(con.state[sample_row().row])) { // (uniform) a free row: what the penalised form computes
+        select_body<kSelPenalized>(s, win, nullptr, v, n, len, part, params, adv, w, SampleConstraintRow{}, nullptr);
+        return;
+    }
     select_body<kSelConstrainedRows>(s, win, crow, v, n, len, part, params, adv, w, cr, con.state);
 }
 

@@ -174,6 +174,18 @@ ZGML_SPEC_FN uint32_t spec_constrain_candidates(uint32_t* c, uint32_t T, uint32_
     return placed;
 }
 
+// Under batching (zgml_hip_resident_decode_batch_speculative_constrained) every sequence walks its OWN automaton, and a sequence
+// without one may sit beside sequences with one, in the same launches. Its rows are FREE: the pass leaves its candidates alone,
+// places nothing, and gives every row the state kSpecRowFree — no state of any automaton (those are < 0xFFFF) and not dead —,
+// so the rows select as the rows of the sampled form do and every one of them has a pick. What the select launch asks of a row's
+// state word, whatever its sequence: spec_row_selects — a dead row has no candidates, every other row has its sequence's.
+constexpr uint32_t kSpecRowFree = 0xFFFFFFFEu;
+ZGML_SPEC_FN uint32_t spec_free_rows(uint32_t* row_state, uint32_t T) {
+    for (uint32_t j = 0; j < T; j++) row_state[j] = kSpecRowFree;
+    return 0; // (forced tokens placed: `drafted` grows by the mode's real drafts alone)
+}
+ZGML_SPEC_FN bool spec_row_selects(uint32_t row_state) { return row_state != kConstraintDead; }
+
 // the dead-end cut: g[acc] without a pick ends the emission in front of itself — at most acc of the m tokens come out — and
 // finishes the call (*dead). m: what spec_emit_count left
 template <class G>

@@ -4,8 +4,8 @@
 // their own: DESIGN section 0.2 item 5 measured that folding such tails into a neighbouring launch is slower. The rules themselves
 // (which tokens are drafted, how many are accepted) are spec.h's; here is only how a workgroup evaluates them.
 // Each body is stated once, as a device function over ONE sequence's SpecArgs: the single-sequence kernels hand it their
-// arguments, the batched kernels (zgml_hip_resident_decode_batch_speculative and its sampled form; blockIdx.x = sequence) the
-// sequence's view of theirs.
+// arguments, the batched kernels (zgml_hip_resident_decode_batch_speculative, its sampled and its constrained form; blockIdx.x =
+// sequence) the sequence's view of theirs.
 #include "kernels.h"
 #include "spec.h"
 #include "tail_device.h"
@@ -21,10 +21,7 @@ constexpr int kSpecWaves = kSpecBlock / 64;
 __device__ __forceinline__ uint32_t spec_constrain(const SpecArgs& a, uint32_t real) {
     if (!a.con_row) return 0;
     const SampleConstraintRow cr = *a.con_row;
-    if (!cr.con_active) { // (nothing attached: the host does not launch this form then) no row has a state
-        for (uint32_t j = 0; j < a.T; j++) a.row_state[j] = kConstraintDead;
-        return 0;
-    }
+    if (!cr.con_active) return spec_free_rows(a.row_state, a.T); // (a batched sequence without an automaton beside others: spec.h)
     return spec_constrain_candidates(a.cand, a.T, real, *a.con_state, cr.class_of, cr.next, cr.n_classes, cr.forced, a.row_state);
 }
 
@@ -167,6 +164,8 @@ __device__ __forceinline__ SpecArgs spec_seq_view(const SpecBatchArgs& ba, uint3
     // the sampled form: the sequence's T picks, its parameter set (the stop tokens), its T row values and its values' row
     if (v.picks) v.picks += (uint64_t)b * v.T, v.sparams += b;
     if (v.lp_out) v.lp_rows += (uint64_t)b * v.T, v.lp_out += (uint64_t)b * cap;
+    // the constrained form: the sequence's row of the table (con_active = 0: none attached to it), its state word, its T row states
+    if (v.con_row) v.con_row += b, v.con_state += b, v.row_state += (uint64_t)b * v.T;
     return v;
 }
 

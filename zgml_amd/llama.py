@@ -377,6 +377,11 @@ class BatchSession:
         sequence); row b holds n_produced[b] tokens — up to and including a stop token —, then -1. logprobs: True, or one flag per
         sequence: float32[B, max(n_tokens)] is appended, row b the log-probabilities of sequence b's tokens — NaN behind them, and
         all through a row whose flag is off."""
+        return self._batch_speculative_sampled("resident_decode_batch_speculative_sampled", first_tokens, start_pos, n_tokens, samplings, histories, drafts,
+                                               ngram, logprobs)
+
+    def _batch_speculative_sampled(self, entry, first_tokens, start_pos, n_tokens, samplings, histories, drafts, ngram, logprobs):
+        """the sampled and the constrained batched speculative call: one signature in the library, one marshalling here"""
         u32p = C.POINTER(C.c_uint32)
         B = self.n_seqs
         t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
@@ -399,18 +404,28 @@ class BatchSession:
         toks = np.full((B, max(1, max_tokens)), -1, np.int64)
         produced = np.zeros(B, np.uint32)
         stats = (capi.SpecStatsC * B)()
-        rc = capi.load_hip().zgml_hip_resident_decode_batch_speculative_sampled(
+        rc = getattr(capi.load_hip(), "zgml_hip_" + entry)(
             self._backend.ctx, self.handle, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p), n.ctypes.data_as(u32p), max_tokens, opts, sp, toks.ctypes.data,
             produced.ctypes.data_as(u32p), stats)
         del keep
         if rc != 0:
-            raise RuntimeError("resident_decode_batch_speculative_sampled: " + self._backend.last_error())
+            raise RuntimeError(entry + ": " + self._backend.last_error())
         out = (toks[:, :max_tokens], produced, [{"steps": st.steps, "drafted": st.drafted, "accepted": st.accepted} for st in stats])
         if logprobs is None:
             return out
         asked = any(bool(sp[b].logprobs) for b in range(B))
         lps = capi.logprobs_result(self._backend.ctx, (B, max_tokens)) if asked and max_tokens else np.full((B, max_tokens), np.nan, np.float32)
         return out + (lps,)
+
+    def resident_decode_batch_speculative_constrained(self, first_tokens, start_pos, n_tokens, samplings, histories=None, drafts=None, ngram: int = 2,
+                                                      logprobs=None):
+        """Constrained speculative decode of every sequence on a tokens_per_seq >= 2 plan (include/zgml_hip.h:
+        zgml_hip_resident_decode_batch_speculative_constrained): resident_decode_batch_speculative_sampled whose sequences walk the
+        automata attached through set_constraint(constraint, state, seq) — each its own, sequences with and without one side by
+        side. Arguments and results are the sampled call's; a sequence whose state allows no token ends early, as behind a stop
+        token (n_produced[b] counts what came out; constraint_state(b) reads the state it reached)."""
+        return self._batch_speculative_sampled("resident_decode_batch_speculative_constrained", first_tokens, start_pos, n_tokens, samplings, histories, drafts,
+                                               ngram, logprobs)
 
     def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None, top_logprobs=None):
         """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
