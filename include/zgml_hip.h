@@ -953,8 +953,8 @@ int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_h
  *   tokens_per_seq >= 2.
  * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
  *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative,
- *   zgml_hip_resident_decode_batch_speculative_sampled, zgml_hip_resident_decode_speculative_model (a constraint on its target or
- *   on its draft: forced tokens between draft executions are not served) and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
+ *   zgml_hip_resident_decode_batch_speculative_sampled, zgml_hip_resident_decode_speculative_model and zgml_hip_resident_decode_batch_speculative_model (a constraint on
+ *   the target or on the draft: forced tokens between draft executions are not served) and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
  *   constraint. */
 typedef struct zgml_token_dfa {
     uint32_t n_states, n_classes, vocab, _pad; /* 1 <= n_states <= 65535, 1 <= n_classes <= 8192 */
@@ -1083,13 +1083,52 @@ int zgml_hip_resident_decode_batch_speculative_constrained(zgml_hip_ctx* ctx, zg
  *   `sampling` everything _speculative_sampled refuses; a sharded target; a draft that is NULL, without a resident set-up, of
  *   another context, batched, token_len != 1, sharded, the target itself, or of another vocabulary;
  *   start_pos + n_tokens + T - 1 > the draft's max_seq; a constraint attached to either program (forced tokens would have to be
- *   placed between the draft executions: not served yet, like a draft model under batching or in front of
- *   zgml_hip_resident_decode_speculative_constrained). n_tokens = 0 returns 0 and touches nothing. */
+ *   placed between the draft executions: not served yet, like a draft model in front of
+ *   zgml_hip_resident_decode_speculative_constrained; a draft model under batching is
+ *   zgml_hip_resident_decode_batch_speculative_model). n_tokens = 0 returns 0 and touches nothing. */
 int zgml_hip_resident_decode_speculative_model(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft, uint32_t first_token,
                                                uint32_t start_pos, uint32_t n_tokens, const uint32_t* history /* [n_history] */,
                                                uint32_t n_history /* 0 or start_pos */, const zgml_sampling* sampling /* NULL: greedy */,
                                                int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
                                                zgml_spec_stats* stats /* may be NULL */);
+
+/* ── A draft model under batching: B sequences, one graph. The call above for every sequence of a batched plan, and a sibling of
+ * zgml_hip_resident_decode_batch_speculative and _batch_speculative_sampled, not a mode of them: those keep refusing mode > 1.
+ * Programs. `target` is a batched plan of n_seqs = B sequences with tokens_per_seq = T >= 2 and a resident set-up, as for
+ *   zgml_hip_resident_decode_batch_speculative; `draft` a batched plan of the same context with the same n_seqs, tokens_per_seq =
+ *   1, a resident set-up of its own and the target's vocabulary — every other dimension, the weight kind and the KV form (f32
+ *   slabs or int8 caches) may differ.
+ * Rule. Per sequence that of zgml_hip_resident_decode_speculative_model: at (hist_b[pos_b], pos_b), c[0] = hist_b[pos_b];
+ *   execution j of the draft runs sequence b on c[j] at pos_b + j and stores its KV column; c[j + 1] = d[j], the first maximum
+ *   of the draft's logits row b, for j < T - 1; the T-th execution exists for its column alone. Acceptance, emission, the stop
+ *   cut, the statistics (drafted += T - 1 per emitting step, no pads) and resuming are those of the batched siblings. The other
+ *   sequences change neither a sequence's tokens nor its statistics.
+ * Idling. A sequence that has its count (n_tokens[b] = 0 is allowed) idles at its END position, as in the batched siblings: it
+ *   hands the draft (hist[pos], pos) and the draft idles from there; both programs' T columns from there on are unspecified.
+ *   Hence, for every b and BOTH programs: start_pos[b] + n_tokens[b] + T <= max_seq.
+ * sampling = NULL: the greedy verify step. Else one zgml_sampling per sequence and the step of
+ *   zgml_hip_resident_decode_batch_speculative_sampled, all of it: per-sequence parameters, seeds and stop tokens, penalties over
+ *   the device history, `logprobs` (zgml_hip_logprobs_result: [n_seqs][max_tokens]); `top_logprobs` is ignored, as there. The
+ *   drafts stay the draft's GREEDY tokens. top_k = 1 with neutral penalties gives the tokens and statistics of the greedy form.
+ * Launches. One graph launch per step, a linear chain: [draft launch, B workgroups] T x { [draft batch prep] [draft plan]
+ *   [argmax stage 1, grid (nblk, B)] [stage 2 + draft advance, grid (1, B)] } [prep, B T columns] [target plan] [argmax stage 1
+ *   over B T rows | the sampled tail] [accept, B workgroups] — T draft executions per step whatever B. The graphs belong to the
+ *   (target, draft) pair, one per form, in slots no other call can use on a batched plan: other calls on either program
+ *   alternate with this one and invalidate nothing; another draft — or the same one freed, set up again or rebuilt — re-captures.
+ *   Runtime profile: the target counts plan + 3 + tail launches per step, the draft T x (plan + 3).
+ * Blocking. Returns 0. Refused with -1 and an error on the context that names the sequence where there is one, before anything
+ *   is enqueued: everything zgml_hip_resident_decode_batch_speculative (with `sampling`: _sampled) refuses of the target and the
+ *   requests (histories[b] / n_history[b] as its per_seq[b].history / n_history); a sharded target; a draft that is NULL, the
+ *   target itself, of another context, without a resident set-up, plain, tokens_per_seq != 1, of another n_seqs, sharded or of
+ *   another vocabulary; the bound above on either program; a constraint attached to any sequence of either program. All
+ *   n_tokens zero returns 0 and touches nothing. */
+int zgml_hip_resident_decode_batch_speculative_model(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft,
+                                                     const uint32_t* first_tokens, const uint32_t* start_pos, const uint32_t* n_tokens,
+                                                     uint32_t max_tokens, const uint32_t* const* histories /* [n_seqs] or NULL; entry NULL: none */,
+                                                     const uint32_t* n_history /* [n_seqs]: 0 or start_pos[b] */,
+                                                     const zgml_sampling* sampling /* [n_seqs], or NULL: greedy verify */,
+                                                     int64_t* tokens_out /* [n_seqs][max_tokens] */, uint32_t* n_produced /* [n_seqs] or NULL */,
+                                                     zgml_spec_stats* stats /* [n_seqs] or NULL */);
 
 /* Mat-vec roofline micro-benchmark: builds `n_matrices` distinct K x N quantized
  * matrices on the device from the deterministic synthetic generator (q4: nibbles in [-8,7];

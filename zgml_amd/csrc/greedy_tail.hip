@@ -6,6 +6,7 @@
 //   launch_argmax_fold          its stage 2 alone (the pairs came from the streaming LM head: kernels_generic.hip)
 //   launch_argmax_draft         the two stages behind a draft program's execution inside a verify step: stage 2 ends with the
 //                               draft advance (the draft's next token and position, the target's next candidate)
+//   launch_argmax_batch_draft   ... behind a BATCHED draft program's execution: B rows, sequence b's draft advance
 //   launch_argmax_batch         the same two stages over B rows (blockIdx.y = sequence), the batched loop's advance;
 //   launch_argmax_rows_stage1   its stage 1 alone (a greedy verify step: spec_accept_kernel folds the pairs)
 // Every workgroup has 256 threads and the same two LDS arrays; a row takes n / 1024 + 1 workgroups, at most 256.
@@ -149,7 +150,7 @@ __global__ void __launch_bounds__(kBlock) argmax_stage2_draft(const float* vals,
     __shared__ float sv[kBlock];
     __shared__ int64_t si[kBlock];
     const int64_t next = argmax_stage2_body(sv, si, 0, vals, idxs, nblk);
-    if (threadIdx.x == 0) tail_advance_draft(adv, (uint64_t)next < n ? (uint32_t)next : 0u);
+    if (threadIdx.x == 0) tail_advance_draft(adv, 0, (uint64_t)next < n ? (uint32_t)next : 0u);
 }
 
 // argmax_stage1 / argmax_stage2 over B rows of n values at once: blockIdx.y = row (sequence); same (value, index) ordering
@@ -167,6 +168,16 @@ __global__ void __launch_bounds__(kBlock) argmax_batch_stage2(const float* vals,
     // the advance step of sequence b: only while it has steps left (else it repeats the same token at the same position)
     const uint32_t b = blockIdx.y, B = gridDim.y;
     if (state[2 * B + b] > 0) tail_advance_batched(state, tokens, B, b, next);
+}
+
+// ... behind one execution of a batched draft program: workgroup blockIdx.y folds row b's pairs and advances sequence b's draft
+// state. No gate on the steps-left word and no token table (argmax_batch_stage2 has both): an idling sequence's draft runs on,
+// over columns nobody reads
+__global__ void __launch_bounds__(kBlock) argmax_batch_stage2_draft(const float* vals, const int64_t* idxs, int nblk, uint64_t n, DraftAdvance adv) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    const int64_t next = argmax_stage2_body(sv, si, blockIdx.y, vals, idxs, nblk);
+    if (threadIdx.x == 0) tail_advance_draft(adv, blockIdx.y, (uint64_t)next < n ? (uint32_t)next : 0u);
 }
 
 } // namespace
@@ -211,6 +222,12 @@ void launch_argmax_draft(hipStream_t s, const float* v, uint64_t n, float* scrat
     const int nblk = argmax_batch_blocks(n);
     argmax_stage1<<<nblk, kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
     argmax_stage2_draft<<<1, kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, n, adv);
+}
+
+void launch_argmax_batch_draft(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv) {
+    const int nblk = argmax_batch_blocks(n);
+    argmax_batch_stage1<<<dim3(nblk, adv.n_seqs), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
+    argmax_batch_stage2_draft<<<dim3(1, adv.n_seqs), kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, n, adv);
 }
 
 void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* scratch_idx, uint32_t nblk, int64_t* out, const ArgmaxAdvance& adv) {

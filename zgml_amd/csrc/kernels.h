@@ -408,11 +408,18 @@ void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* 
 // with the draft advance — state[0] = d, the row's first maximum, state[1] += 1 (the draft program's state words: its next
 // execution's token and position), and with `cand_next` (every execution but the step's last) *cand_next = d, the next
 // candidate of the target's verify step.
+// Stated over the batched loop's state layout (below: state[b] token, state[n_seqs + b] position), of which a plain draft's two
+// words are the n_seqs = 1 view: sequence b's candidate is cand_next[b * cand_stride].
 struct DraftAdvance {
     uint32_t* state = nullptr;
     uint32_t* cand_next = nullptr;
+    uint32_t n_seqs = 1, cand_stride = 0;
 };
 void launch_argmax_draft(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv);
+// ... behind one execution of a BATCHED draft program (zgml_hip_resident_decode_batch_speculative_model): the two stages over its
+// adv.n_seqs logits rows (blockIdx.y = sequence), stage 2 ending with sequence b's draft advance. Unlike launch_argmax_batch it
+// reads neither the steps-left nor the produced words and writes no token table. scratch: n_seqs * argmax_batch_blocks(n) pairs.
+void launch_argmax_batch_draft(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv);
 // Everything LlamaInferencePlan.execute patches on the host per execution (src/llama_inference.zig:405-446; for T > 1
 // patch_tokens of zgml_amd/host/llama_decode.cpp), produced on the device as one flat index space: T embedding rows, T
 // causal-mask columns, T RoPE rows per layer leaf, the dynamic words (KV store offsets at `pos`, seq_kv = pos + T).
@@ -478,7 +485,7 @@ enum SpecWord : uint32_t {
     kSpecPos,      // its position
     kSpecProduced, // tokens produced so far
     kSpecWanted,   // n_tokens of the call
-    kSpecMode,     // 0 lookup, 1 provided, 2 a draft model (zgml_hip_resident_decode_speculative_model alone sets it)
+    kSpecMode,     // 0 lookup, 1 provided, 2 a draft model (zgml_hip_resident_decode_speculative_model and its batched sibling alone set it)
     kSpecNgram,
     kSpecNDrafts,
     kSpecStart,    // start_pos of the call
@@ -524,8 +531,11 @@ struct SpecArgs {
     uint32_t* row_state = nullptr;
     // drafts from a model (zgml_hip_resident_decode_speculative_model; spec.h: DRAFTS FROM A MODEL), mode 2: the state words
     // (token, position) of the DRAFT program's resident set-up, what its prep launch reads. The draft launch writes c[0] and the
-    // run position there; cand[1..T-1] are written by the draft executions' advances (launch_argmax_draft). nullptr: none
+    // run position there; cand[1..T-1] are written by the draft executions' advances (launch_argmax_draft). nullptr: none.
+    // The position word lies draft_pos words behind the token word: 1 in a plain draft's state, n_seqs in a batched draft's
+    // (zgml_hip_resident_decode_batch_speculative_model: state[b] token, state[n_seqs + b] position)
     uint32_t* draft_state = nullptr;
+    uint32_t draft_pos = 1;
 };
 void launch_spec_draft(hipStream_t s, const SpecArgs& a);
 void launch_spec_accept(hipStream_t s, const SpecArgs& a);
@@ -537,7 +547,9 @@ void launch_spec_accept(hipStream_t s, const SpecArgs& a);
 // and counters stay as they are. The sampled form (zgml_hip_resident_decode_batch_speculative_sampled): picks + b * T, sparams + b,
 // lp_rows + b * T and lp_out + b * cap likewise; top_* stay null. The constrained form
 // (zgml_hip_resident_decode_batch_speculative_constrained): con_row + b — the sequence's row of the table, con_active = 0 when nothing
-// is attached to it: its rows are then free (spec.h: kSpecRowFree) —, con_state + b, row_state + b * T.
+// is attached to it: its rows are then free (spec.h: kSpecRowFree) —, con_state + b, row_state + b * T. Drafts from a batched
+// draft model (zgml_hip_resident_decode_batch_speculative_model): a.draft_state is the draft set-up's batched state and
+// a.draft_pos = n_seqs; sequence b's token word is draft_state + b, its position word n_seqs behind it.
 struct SpecBatchArgs {
     SpecArgs a;
     uint32_t n_seqs, drafts_stride;

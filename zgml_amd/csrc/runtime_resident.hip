@@ -1,6 +1,7 @@
 // runtime_resident.hip — the device-resident LLaMA loops (extension; see include/zgml_hip.h): set-up; the greedy loops
 // (single-sequence decode, batched decode, the prefill chunk); their sampled forms and the sampled / greedy speculative verify
-// loop — also with a second resident program drafting inside the step (zgml_hip_resident_decode_speculative_model) —, and the greedy / sampled verify loop of every sequence of a batched plan; the blocking calls over one buffer range
+// loop — also with a second resident program drafting inside the step (zgml_hip_resident_decode_speculative_model) —, and the greedy / sampled verify loop of every sequence of a batched plan — also with a batched
+// draft program (zgml_hip_resident_decode_batch_speculative_model) —; the blocking calls over one buffer range
 // (zgml_hip_sample, zgml_hip_logprobs, zgml_hip_top_logprobs) with their result
 // getters; the token constraint's create / attach / state. Everything a step needs (embedding row, mask column, RoPE rows, the
 // dynamic words) is produced on the device from a few state words, so a call is a train of launches (or graph replays) with one
@@ -116,7 +117,8 @@ struct zgml_resident {
     // logits row, [T] (spec.h: UNDER A CONSTRAINT) — the draft launch writes them, the constrained-rows select launch reads them —,
     // [n_seqs * tokens_per_seq] on a batched plan (zgml_hip_resident_decode_batch_speculative_constrained)
     DevBlock<uint32_t> row_state;
-    // speculative decode with a draft model (zgml_hip_resident_decode_speculative_model), on the TARGET's set-up: the step's graphs
+    // speculative decode with a draft model (zgml_hip_resident_decode_speculative_model; on a batched plan
+    // zgml_hip_resident_decode_batch_speculative_model, the only call that can use the slots there), on the TARGET's set-up: the step's graphs
     // hold the launches of two programs, so they belong to the pair — pair_draft and the draft set-up's graph_epoch as it stood at
     // the capture; another draft, or one whose epoch moved, re-captures —, one per form ([0] greedy, [1 + SampledTail::form()]
     // the sampled ones) and apart from every other slot: other calls on either program alternate with the pair's and drop nothing
@@ -1485,9 +1487,19 @@ namespace {
 // of every attached sequence also walking its automaton, graphs of their own; the rows of a sequence without one are free
 // (spec.h: kSpecRowFree). A reached state without a token finishes its sequence as a stop token does: the others go on. With
 // nothing attached it is the sampled form to the launch.
+// `model` (zgml_hip_resident_decode_batch_speculative_model; spec.h: DRAFTS FROM A MODEL): every sequence's candidates come from
+// `draft`, a batched plan of the same context, vocabulary and n_seqs with ONE column per sequence, executed Ts times between the
+// draft launch and the prep —
+//   [begin, B] Ts x { [draft batch prep] [draft plan] [argmax stage 1, (nblk, B)] [stage 2 + draft advance, (1, B)] } [prep] [plan] ... [accept, B]
+// one graph launch, a linear chain, Ts draft executions whatever B. The draft's device state is its batched loop's (token and
+// position rows of bstate), its stage-1 pairs its own bval / bidx. Either form of the verify step; `per_seq` carries the
+// histories alone. The graphs belong to the pair (Resident::pair_graph: spec_decode() cannot use them on a batched plan); each
+// program's profile counts its own launches. A sequence that has its count hands the draft (hist[pos], pos) and the draft idles
+// from there, Ts columns on: both programs need start_pos + n_tokens + Ts <= max_seq.
 int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, const uint32_t* first_tokens, const uint32_t* start_pos,
                       const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, bool sampled, const zgml_sampling* sampling,
-                      int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats, bool honours_constraint = false) {
+                      int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats, bool honours_constraint = false, bool model = false,
+                      zgml_hip_program* draft = nullptr) {
     if (!ctx || !p) return -1;
     Resident* r = p->resident;
     if (!r || !r->n_seqs || !p->n_seqs) {
@@ -1501,6 +1513,25 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     }
     if (!honours_constraint && refuse_constrained(ctx, p, who.c_str())) return -1;
     const bool constrained = honours_constraint && r->n_con != 0;
+    Resident* const dr = model && draft ? draft->resident : nullptr;
+    if (model) { // what the call asks of the two programs beside that
+        const char* why = !p->shard_points.empty() ? "the target is a sharded program (gather points attached)"
+                          : !draft ? "no draft program" : draft == p ? "the draft is the target program itself" : draft->ctx != p->ctx ? "the draft belongs to another context"
+                          : !dr ? "the draft has no resident set-up (zgml_hip_resident_setup first)"
+                          : !dr->n_seqs || !draft->n_seqs ? "the draft is a plain plan (a batched draft is needed: zgml_hip_program_set_sequences)"
+                          : dr->tokens_per_seq != 1 ? "the draft must hold one column per sequence (tokens_per_seq = 1)"
+                          : dr->n_seqs != B ? "the draft has another n_seqs than the target"
+                          : !draft->shard_points.empty() ? "the draft is a sharded program (gather points attached)"
+                          : dr->vocab != r->vocab ? "the draft has another vocabulary than the target" : nullptr;
+        if (why) {
+            ctx->fail(who + ": " + why);
+            return -1;
+        }
+        if (has_constraint(draft)) { // (forced tokens would have to be placed between the draft executions: not served)
+            ctx->fail(who + ": a constraint is attached to the draft program (detach it first)");
+            return -1;
+        }
+    }
     if (!first_tokens || !start_pos || !n_tokens || (max_tokens && !tokens_out)) {
         ctx->fail(who + ": NULL array (first_tokens, start_pos, n_tokens, or tokens_out with max_tokens > 0)");
         return -1;
@@ -1521,6 +1552,10 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
             return -1;
         }
         if (!spec_request(ctx, r, seq, first_tokens[b], start_pos[b], n_tokens[b], Ts, true, per_seq ? per_seq + b : nullptr, &req[b])) return -1;
+        if (dr && (uint64_t)start_pos[b] + n_tokens[b] + Ts > dr->max_seq) { // (the target's bound: the draft stores the same Ts columns per step)
+            ctx->fail(seq + ": start_pos + n_tokens + tokens_per_seq exceeds the draft's max_seq");
+            return -1;
+        }
         if (sampled) {
             if (!sampling_params(ctx, seq, sampling + b, r->vocab, r->vocab, &sp[b], RecentOf::Spec)) return -1;
             penalized = penalized || sp[b].pen_active, lp = lp || sampling[b].logprobs;
@@ -1538,6 +1573,11 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
         return positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]]; }) &&
                positions_in_bounds(p, Ts, [&](uint32_t i) { return start_pos[p->op_seq[i]] + n_tokens[p->op_seq[i]]; });
     });
+    // ... and the first and the last possible position of a draft execution: the Ts-th of a step that idles at the end position
+    if (dr) resident_begin(draft, [&] {
+        return positions_in_bounds(draft, 1, [&](uint32_t i) { return start_pos[draft->op_seq[i]]; }) &&
+               positions_in_bounds(draft, 1, [&](uint32_t i) { return start_pos[draft->op_seq[i]] + n_tokens[draft->op_seq[i]] + Ts - 1; });
+    });
     const uint32_t nblk = (uint32_t)argmax_batch_blocks(r->vocab), hist_cap = r->max_seq + 1, n_words = B * kSpecWords + 1, rows = B * Ts;
     if (!ensure_row_blocks(ctx, p, "the batched verify step's blocks", r->bhist.count() / hist_cap * Ts, rows, r->bspec, n_words, r->bhist, (size_t)B * hist_cap,
                            r->bdrafts, (size_t)B * r->max_seq))
@@ -1554,7 +1594,7 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     for (uint32_t b = 0; up && b < B; b++) {
         uint32_t* w = w0.data() + (size_t)b * kSpecWords;
         const zgml_spec_decode& o = req[b].o;
-        w[kSpecTok] = first_tokens[b], w[kSpecPos] = start_pos[b], w[kSpecWanted] = n_tokens[b], w[kSpecMode] = o.mode, w[kSpecNgram] = req[b].ngram;
+        w[kSpecTok] = first_tokens[b], w[kSpecPos] = start_pos[b], w[kSpecWanted] = n_tokens[b], w[kSpecMode] = model ? 2 : o.mode, w[kSpecNgram] = req[b].ngram;
         w[kSpecNDrafts] = std::min(req[b].n_drafts, r->max_seq), w[kSpecStart] = start_pos[b], w[kSpecHistLo] = o.n_history ? 0 : start_pos[b];
         w[kSpecRunPos] = start_pos[b];
         uint32_t* const hist = r->bhist + (size_t)b * hist_cap;
@@ -1588,8 +1628,18 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     }
     const ResidentBatchSpecPrepArgs prep{r->embed, r->cos, r->sin, r->tok_in, r->mask, r->rope_bufs, r->dyn_kind, r->dyn_base, r->dyn_stride, r->dyn_seq,
                                          p->dyn_dev, r->bspec, r->tok_dev, r->d, r->max_seq, r->dh, r->n_rope, (uint32_t)p->ops.size(), B, Ts};
+    // (the model form) the draft's prep reads the token and position rows of its own batched state, as in
+    // zgml_hip_resident_decode_batch: the draft launch and the executions' advances write them; execution j's advance also writes
+    // candidate j + 1 of every sequence. The stage-1 pairs of its B rows go to the draft's own scratch
+    const BatchPrep dprep = dr ? batch_prep_args(draft) : BatchPrep{};
+    if (dr) sa.a.draft_state = dr->bstate, sa.a.draft_pos = B;
     auto one_step = [&](hipStream_t st) {
         launch_spec_batch_draft(st, sa);
+        for (uint32_t j = 0; dr && j < Ts; j++) {
+            launch_resident_batch_prep(st, dprep.a, dprep.total);
+            run_plan(draft, st, 0, draft->plan.size());
+            launch_argmax_batch_draft(st, dr->logits, dr->vocab, dr->bval, dr->bidx, DraftAdvance{dr->bstate, j + 1 < Ts ? r->tok_dev + j + 1 : nullptr, B, Ts});
+        }
         launch_resident_batch_spec_prep(st, prep, r->prep_total);
         run_plan(p, st, 0, p->plan.size());
         if (sampled)
@@ -1598,9 +1648,16 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
             launch_argmax_rows_stage1(st, r->logits, r->vocab, rows, r->bval, r->bidx);
         launch_spec_batch_accept(st, sa);
     };
-    GraphSlot& slot = sampled ? r->sgraph[tail.form()] : r->bspec_graph;
+    // (the model form) the pair's graphs serve this draft as it stands, and no other
+    if (dr && (r->pair_draft != draft || r->pair_epoch != dr->graph_epoch)) {
+        hipStreamSynchronize(s);
+        free_pair_graphs(r);
+        r->pair_draft = draft, r->pair_epoch = dr->graph_epoch;
+    }
+    GraphSlot& slot = dr ? r->pair_graph[sampled ? 1 + tail.form() : 0] : sampled ? r->sgraph[tail.form()] : r->bspec_graph;
     // (as the batched loops: no pageable copy in flight when the capture begins)
-    capture_once(ctx, s, sampled ? std::string("resident_batch_spec_") + kSampledFormNames[tail.form()] : std::string("resident_batch_spec"), true, one_step, slot);
+    capture_once(ctx, s, std::string(dr ? "resident_batch_spec_model" : "resident_batch_spec") + (sampled ? std::string("_") + kSampledFormNames[tail.form()] : std::string()), true,
+                 one_step, slot);
     // the host cannot know how many steps the drafts save: it launches the fewest that can finish the sequence with the most
     // tokens left, reads the counts back, repeats. (`wanted` is read back with the words: a stop token of the sampled form sets
     // its sequence's to the produced count, which shortens the round)
@@ -1645,12 +1702,24 @@ int spec_decode_batch(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string&
     }
     // per step [draft] [prep] [plan] [argmax stage 1] [accept], or the sampled tail in the place of the argmax stage
     resident_end(p, steps_run, p->plan.size() + 3 + (sampled ? tail.launches() : 1));
+    if (dr) resident_end(draft, steps_run * Ts, draft->plan.size() + 3); // per step Ts x { [batched prep] [plan] [argmax x 2] }
     return ok ? 0 : -1;
 }
 
 } // namespace
 
 extern "C" {
+
+int zgml_hip_resident_decode_batch_speculative_model(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft, const uint32_t* first_tokens,
+                                                     const uint32_t* start_pos, const uint32_t* n_tokens, uint32_t max_tokens, const uint32_t* const* histories,
+                                                     const uint32_t* n_history, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced,
+                                                     zgml_spec_stats* stats) {
+    // the histories as the requests of the batched siblings carry them (mode and drafts are not the caller's here)
+    std::vector<zgml_spec_decode> opt(target && target->resident ? target->resident->n_seqs : 0);
+    for (size_t b = 0; b < opt.size(); b++) opt[b] = zgml_spec_decode{histories ? histories[b] : nullptr, n_history ? n_history[b] : 0, 0, nullptr, 0, 0};
+    return spec_decode_batch(ctx, target, "resident_decode_batch_speculative_model", first_tokens, start_pos, n_tokens, max_tokens, opt.empty() ? nullptr : opt.data(),
+                             sampling != nullptr, sampling, tokens_out, n_produced, stats, false, true, draft);
+}
 
 int zgml_hip_resident_decode_batch_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, const uint32_t* first_tokens, const uint32_t* start_pos,
                                                const uint32_t* n_tokens, uint32_t max_tokens, const zgml_spec_decode* per_seq, int64_t* tokens_out,

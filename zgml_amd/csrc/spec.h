@@ -112,6 +112,10 @@ ZGML_SPEC_FN uint32_t spec_candidates_provided(uint32_t tok, uint32_t pos, uint3
 // Why the draft's cache stays in step: with a candidates accepted, the draft's columns pos .. pos + min(a, T - 1) were computed
 // over confirmed tokens — the step emits at most a + 1 —, and every column behind them is stored again, by the next step's
 // executions from its own pos, before any attention of the draft reads it.
+// Under batching (zgml_hip_resident_decode_batch_speculative_model) this is the rule of every sequence b of a batched target: the
+// draft is a batched one-column plan of the same sequences, execution j runs sequence b on its c[j] at its pos + j, d[j] is the
+// first maximum of the draft's logits ROW b. A sequence that has its count idles at its end position (kIdleAtEnd) and its draft
+// from there.
 // What the draft launch leaves of this rule: c[0] (the other candidates are written by the executions' advances; until then they
 // repeat c[0]) and the count of drafts.
 ZGML_SPEC_FN uint32_t spec_candidates_model(uint32_t tok, uint32_t T, uint32_t* c) {

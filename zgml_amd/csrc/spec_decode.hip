@@ -29,7 +29,8 @@ __device__ __forceinline__ uint32_t spec_constrain(const SpecArgs& a, uint32_t r
 // run words. Lookup mode: for n = ngram .. 1 the threads walk the match positions [n - 1, pos - 1] downwards, 256 apart — a
 // thread's first hit is its largest —, the largest hit of the workgroup is folded with wave shuffles and one pass over LDS, and
 // the first n with a hit wins. Provided mode is a table read. The model mode (spec.h: DRAFTS FROM A MODEL) writes c[0] and hands
-// (c[0], position) to the draft program's state words: the draft executions between this launch and the prep fill in the rest.
+// (c[0], position) to the draft program's state words — token at draft_state[0], position a.draft_pos words behind it: a plain
+// draft's two words, or sequence b's of a batched draft's state —: the draft executions between this launch and the prep fill in the rest.
 // Thread 0 writes. fold: kSpecWaves LDS words.
 // kIdleAtEnd: where a sequence that has its count runs its idle steps (below).
 template <bool kIdleAtEnd>
@@ -47,7 +48,7 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
             for (uint32_t j = 0; j < a.T; j++) a.cand[j] = a.hist[at];
             for (uint32_t j = 0; a.row_state && j < a.T; j++) a.row_state[j] = kConstraintDead; // (no row of an idle step picks)
             w[kSpecRunPos] = at;
-            if (a.draft_state) a.draft_state[0] = a.hist[at], a.draft_state[1] = at; // (the draft program idles from the same token and position)
+            if (a.draft_state) a.draft_state[0] = a.hist[at], a.draft_state[a.draft_pos] = at; // (the draft program idles from the same token and position)
         }
         return;
     }
@@ -55,7 +56,7 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
         if (threadIdx.x == 0) {
             w[kSpecDrafted] += spec_candidates_model(a.hist[pos], a.T, a.cand);
             w[kSpecRunPos] = pos;
-            a.draft_state[0] = a.hist[pos], a.draft_state[1] = pos;
+            a.draft_state[0] = a.hist[pos], a.draft_state[a.draft_pos] = pos;
         }
         return;
     }
@@ -166,6 +167,8 @@ __device__ __forceinline__ SpecArgs spec_seq_view(const SpecBatchArgs& ba, uint3
     if (v.lp_out) v.lp_rows += (uint64_t)b * v.T, v.lp_out += (uint64_t)b * cap;
     // the constrained form: the sequence's row of the table (con_active = 0: none attached to it), its state word, its T row states
     if (v.con_row) v.con_row += b, v.con_state += b, v.row_state += (uint64_t)b * v.T;
+    // drafts from a batched draft model: the sequence's token word of the draft's state (its position word draft_pos = n_seqs behind it)
+    if (v.draft_state) v.draft_state += b;
     return v;
 }
 

@@ -147,10 +147,11 @@ __device__ __forceinline__ void tail_advance_batched(uint32_t* st, int64_t* toke
 // One execution of the draft program inside a verify step (kernels.h: DraftAdvance; spec.h: DRAFTS FROM A MODEL): the draft's
 // greedy token d becomes the token of its next execution, a position further, and — every execution but the step's last — the
 // next candidate of the target's verify step. No count, no table: what is emitted is the accept launch's business.
-__device__ __forceinline__ void tail_advance_draft(const DraftAdvance& adv, uint32_t d) {
-    adv.state[0] = d;
-    adv.state[1] += 1;
-    if (adv.cand_next) *adv.cand_next = d;
+// Sequence b of adv.n_seqs, over the batched loop's first two state rows (token, position); a plain draft is b = 0 of 1.
+__device__ __forceinline__ void tail_advance_draft(const DraftAdvance& adv, uint32_t b, uint32_t d) {
+    adv.state[b] = d;
+    adv.state[adv.n_seqs + b] += 1;
+    if (adv.cand_next) adv.cand_next[(uint64_t)b * adv.cand_stride] = d;
 }
 
 // ── the log-probability finish (the rule: sample.h, THE LOG-PROBABILITY) ──

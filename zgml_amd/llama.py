@@ -427,6 +427,51 @@ class BatchSession:
         return self._batch_speculative_sampled("resident_decode_batch_speculative_constrained", first_tokens, start_pos, n_tokens, samplings, histories, drafts,
                                                ngram, logprobs)
 
+    def resident_decode_batch_speculative_model(self, draft_session: "BatchSession", first_tokens, start_pos, n_tokens, samplings=None, histories=None,
+                                                logprobs=None):
+        """zgml_hip_resident_decode_batch_speculative_model: every sequence of this session's tokens_per_seq = T >= 2 plan verifies
+        what `draft_session`'s batched one-column plan (same backend, n_seqs and vocabulary, its own resident_setup) drafts
+        greedily for it, T - 1 tokens per step, all on the device. Both sessions' caches must hold every sequence's positions <
+        start_pos[b]; afterwards both hold those < start_pos[b] + its produced count. samplings=None: the greedy verify step; else
+        one capi.SamplingC per sequence, as in resident_decode_batch_speculative_sampled. histories: None, or per sequence None /
+        the tokens at positions 0..start_pos[b]-1. -> (tokens[B, max(n_tokens)], n_produced[B], [{"steps", "drafted",
+        "accepted"}] per sequence); logprobs (True, or one flag per sequence; needs samplings): float32[B, max(n_tokens)] is
+        appended, as there."""
+        u32p = C.POINTER(C.c_uint32)
+        B = self.n_seqs
+        t, p = np.ascontiguousarray(first_tokens, dtype=np.uint32), np.ascontiguousarray(start_pos, dtype=np.uint32)
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n_tokens, dtype=np.uint32), (B,)))
+        assert t.size == B and p.size == B and (samplings is None or len(samplings) == B)
+        if samplings is None and logprobs:
+            raise ValueError("resident_decode_batch_speculative_model: logprobs need the sampling parameter sets")
+        hists = [np.ascontiguousarray([] if h is None else h, dtype=np.uint32) for h in ([None] * B if histories is None else histories)]
+        assert len(hists) == B
+        hist_ptrs = (u32p * B)(*[h.ctypes.data_as(u32p) if h.size else None for h in hists])
+        n_hist = np.array([h.size for h in hists], np.uint32)
+        sp = None
+        if samplings is not None:
+            sp = (capi.SamplingC * B)(*samplings)
+            flags = [bool(logprobs)] * B if logprobs is None or isinstance(logprobs, bool) else [bool(x) for x in logprobs]
+            assert len(flags) == B
+            for b in range(B):
+                if flags[b]:
+                    sp[b].logprobs = 1
+        max_tokens = int(n.max()) if n.size else 0
+        toks = np.full((B, max(1, max_tokens)), -1, np.int64)
+        produced = np.zeros(B, np.uint32)
+        stats = (capi.SpecStatsC * B)()
+        rc = capi.load_hip().zgml_hip_resident_decode_batch_speculative_model(
+            self._backend.ctx, self.handle, draft_session.handle if draft_session is not None else None, t.ctypes.data_as(u32p), p.ctypes.data_as(u32p),
+            n.ctypes.data_as(u32p), max_tokens, hist_ptrs, n_hist.ctypes.data_as(u32p), sp, toks.ctypes.data, produced.ctypes.data_as(u32p), stats)
+        if rc != 0:
+            raise RuntimeError("resident_decode_batch_speculative_model: " + self._backend.last_error())
+        out = (toks[:, :max_tokens], produced, [{"steps": st.steps, "drafted": st.drafted, "accepted": st.accepted} for st in stats])
+        if logprobs is None:
+            return out
+        asked = any(bool(sp[b].logprobs) for b in range(B))
+        lps = capi.logprobs_result(self._backend.ctx, (B, max_tokens)) if asked and max_tokens else np.full((B, max_tokens), np.nan, np.float32)
+        return out + (lps,)
+
     def resident_decode_batch_sampled(self, first_tokens, start_pos, n_steps, samplings, logprobs=None, top_logprobs=None):
         """zgml_hip_resident_decode_batch_sampled: `samplings` is one capi.SamplingC per sequence.
         -> (tokens[B, max(n_steps)], n_produced[B]); row b holds n_produced[b] tokens, then -1. logprobs: True, or one flag per
