@@ -119,6 +119,15 @@ __device__ __forceinline__ void soft_merge(SoftState& s, float om, float ol, flo
 // consumer load sc1, no fence.
 using gu64 = __attribute__((address_space(1))) unsigned long long;
 using gu32 = __attribute__((address_space(1))) unsigned int;
+#ifdef ZGML_TRACE // diagnostics build: the XCD this workgroup runs on (0-7)
+__device__ __forceinline__ uint32_t xcc_id() {
+    uint32_t x = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
+#endif
+    return x & 0xFu;
+}
+#endif
 __device__ __forceinline__ void split_put(float* p, float a, float b) {
     const unsigned long long v = (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b) << 32);
     __hip_atomic_store((gu64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -277,6 +286,7 @@ struct DecodeHandoff {
     uint32_t n_heads;
     uint32_t* timeout;   // set when a wait gives up
     uint32_t poll_sleep; // s_sleep(1) units (64 clocks) between two sweeps
+    uint32_t* xcc;       // diagnostics build (ZGML_HIP_ATTN_TRACE=1): [workgroups of the attention part] 1 + the XCC id a live one ran on
 };
 __device__ __forceinline__ void handoff_idle(const DecodeHandoff* ho, uint32_t wg, uint32_t gen) { ho->gen[wg] = gen; } // (an idle split moves its private words on with the producers)
 __device__ __forceinline__ void handoff_idle(const CounterHandoff* ho, uint32_t wg, uint32_t) { for (int c = 0; c < 3; c++) ho->seen[3 * wg + c] += ho->need; }
@@ -705,6 +715,8 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
             if (lane == 0) part_ml[2 * w] = st.m, part_ml[2 * w + 1] = st.l;
         }
         ATTN_STAMP(5);
+        // (measured and NOT kept: the LDS-only barrier of the sweep here, which would not wait for wave 0's q_rot / K / V stores —
+        // the stamps around it read 40-80 ns either way, profiles/r26_qkv_colocate.txt)
         __syncthreads();
         ATTN_STAMP(6);
         if (w != 0) return;
@@ -741,6 +753,11 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
     }
     { // wave 0 from here on
         if (wait_qkv && lane == 0) handoff_done(ho, hx * n_sp + sp, gen, target); // (also after a give-up: the state stays in step with the producers')
+#ifdef ZGML_TRACE
+        if constexpr (!COUNTERS) {
+            if (wait_qkv && ho->xcc && lane == 0) ho->xcc[hx * n_sp + sp] = 1 + xcc_id();
+        }
+#endif
         if (n_active > 1) { // publish this chunk; the last arriver merges all of them
             constexpr uint32_t REC = DH + 4; // m, l, pad, pad, acc[DH]
             float* const head_buf = split_buf + (uint64_t)hx * n_sp * REC;

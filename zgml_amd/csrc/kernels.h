@@ -769,6 +769,8 @@ struct QkvHandoffBlock {
     uint32_t* counters = nullptr;
     const uint32_t* idx = nullptr;
     uint32_t* seen = nullptr;
+    bool group_order = false;       // granule form: record i is a head of kv group i / (n_heads / n_kv) — what the block map assumes (qkv_colocate.h)
+    uint32_t* xcc_trace = nullptr;  // diagnostics (ZGML_HIP_ATTN_TRACE=1): [column groups | attention workgroups] where each ran
 };
 bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodeParams* dev_params, uint32_t n_heads, uint32_t n_kv, uint32_t d_head,
                           const AttnSplit& sp, const QkvHandoffBlock& hb, uint32_t* timeout, bool kvq = false);

@@ -611,6 +611,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         ok = ok && n_kv != 0 && nh % n_kv == 0;
         std::vector<uint32_t> idx(3 * (size_t)nh); // (counter form: each record's q / k / v counter)
         std::vector<char> head_seen(nh, 0);
+        bool group_order = true; // record r is a head of kv group r / (nh / n_kv): the block map's assumption (qkv_colocate.h)
         for (uint32_t r = 0; ok && r < nh; r++) { // the records are not in head order: each one's head from its pointers
             const AttnDecodeParams& a = ad->host[r];
             const ptrdiff_t qo = a.q_src - L.parts[0].dst, ko = a.k_src - L.parts[1].dst, vo = a.v_src - L.parts[2].dst;
@@ -620,6 +621,7 @@ void fuse_qkv_attention(zgml_hip_program* p) {
             const uint32_t h = (uint32_t)(qo / dh), kvh = (uint32_t)(ko / dh);
             ok = !head_seen[h] && kvh == h / (nh / n_kv);
             head_seen[h] = 1; // (granule form: the kernel finds the record's granules from the same pointer differences, DecodeHandoff)
+            group_order = group_order && kvh == r / (nh / n_kv);
             idx[3 * r] = h, idx[3 * r + 1] = nh + kvh, idx[3 * r + 2] = nh + n_kv + kvh;
         }
         if (!ok) continue;
@@ -682,6 +684,10 @@ void fuse_qkv_attention(zgml_hip_program* p) {
         } else {
             hb.granules = (unsigned long long*)block;
             hb.producer_gen = (uint32_t*)(hb.granules + n_gran), hb.consumer_gen = hb.producer_gen + n_mv;
+            hb.group_order = group_order;
+            const size_t n_wg = (size_t)n_mv + (size_t)nh * n_sp;
+            if (sw().hip_attn_trace && (hb.xcc_trace = (uint32_t*)mapped_trace((n_wg + 1) / 2))) // (diagnostics build: where every workgroup of the launch ran)
+                p->xcc_traces.push_back({hb.xcc_trace, (uint32_t)n_mv, nh, n_kv, dh, n_sp});
         }
         const AttnDecodeParams* d = ad->dev;
         AttnSplit sp = ad->sp;

@@ -33,6 +33,7 @@
 // workgroups are placed 8 blocks apart so they share an XCD L2 (speed only, never correctness).
 #include "qmv_common.h"
 #include "attention_decode.h"
+#include "qkv_colocate.h"
 
 #include <hip/hip_fp16.h>
 #include <math.h>
@@ -218,6 +219,7 @@ struct QmvPublish {
     unsigned long long* gran; // [all columns of q, k, v] granules
     uint32_t* gen;            // [column groups of the launch] private generation words: read at kernel start, written back at the end
     uint32_t drop;            // diagnostics (ZGML_HIP_DEBUG_DROP_PUBLISH=1): column group 0 of part 0 stores no granules — its consumers time out
+    uint32_t* xcc;            // diagnostics build (ZGML_HIP_ATTN_TRACE=1): [column groups] 1 + the XCC id of the workgroup that stored the group
 };
 // ... and the counter form the 256-thread launch of K-on-lanes weights keeps (handoff_gen.h: CounterHandoff): the 16 owning lanes store
 // their outputs write-through (agent scope), the wave drains, and lane 0 bumps the counter of the head slice the column group belongs to
@@ -269,9 +271,8 @@ __device__ __forceinline__ float prenorm_factor(const float (&pp)[4], uint32_t K
     const float ss = rows_sum4(row16_sum((pp[0] + pp[1]) + (pp[2] + pp[3])));
     return 1.0f / sqrtf(ss / (float)K + eps); // reference.zig:365
 }
-// wave 0 of a K-on-lanes workgroup, behind the barrier: the deferred rmsnorm factor (1 without a norm) and this workgroup's slice
-// of the prologue's side outputs
-__device__ __forceinline__ float kon_factor_and_slices(const KonTail& kt, const QMVArgs& a, const float* red, uint32_t n_waves, uint32_t lane) {
+// wave 0 of a K-on-lanes workgroup, behind the barrier: the deferred rmsnorm factor (1 without a norm) ...
+__device__ __forceinline__ float kon_factor(const KonTail& kt, const QMVArgs& a, const float* red, uint32_t n_waves, uint32_t lane) {
     const uint32_t col = lane & 15;
     float inv = 1.0f;
     if (kt.inv_known) {
@@ -286,6 +287,10 @@ __device__ __forceinline__ float kon_factor_and_slices(const KonTail& kt, const 
         const float ss = row16_sum(col < n_waves ? sv : 0.f);
         inv = 1.0f / sqrtf(ss / (float)kt.K + kt.eps); // reference.zig:365
     }
+    return inv;
+}
+// ... and this workgroup's slice of the prologue's side outputs
+__device__ __forceinline__ void kon_slices(const KonTail& kt, const QMVArgs& a, float inv, uint32_t lane) {
     if (kt.has_pro && lane < 16) { // this workgroup's slice of the absorbed ops' outputs (mid = a * inv, x = mid * b: reference order)
         const QmvPrologue& pr = a.pro;
         if (kt.slice <= 16) {
@@ -303,6 +308,10 @@ __device__ __forceinline__ float kon_factor_and_slices(const KonTail& kt, const 
             }
         }
     }
+}
+__device__ __forceinline__ float kon_factor_and_slices(const KonTail& kt, const QMVArgs& a, const float* red, uint32_t n_waves, uint32_t lane) {
+    const float inv = kon_factor(kt, a, red, n_waves, lane);
+    kon_slices(kt, a, inv, lane);
     return inv;
 }
 template <bool GROUPED, bool KON = false, typename PUB = QmvPublish>
@@ -337,7 +346,11 @@ __device__ __forceinline__ void reduce_store(float acc, float* red, const QMVArg
     for (uint32_t j = 0; j < 4; j++) v += r + 4 * j < n_waves ? part[j] : 0.f;
     v = rows_sum4(v);
     if (KON) v *= kon->post * kon_factor_and_slices(*kon, a, red, n_waves, lane);
-    if (!KON && kon) v *= kon_factor_and_slices(*kon, a, red, n_waves, lane); // (the n-on-lanes body under PRENORM: the factor and the slices only)
+    // (the n-on-lanes body under PRENORM: the factor and the slices only; a launch that hands over stores the slices behind the
+    // granule, which the attention of the same launch waits for)
+    float pn_inv = 1.0f;
+    const bool slices_last = !KON && kon && pub && !std::is_same<PUB, QmvCountPublish>::value;
+    if (!KON && kon) v *= pn_inv = slices_last ? kon_factor(*kon, a, red, n_waves, lane) : kon_factor_and_slices(*kon, a, red, n_waves, lane);
     if (lane < 16) {
         const uint32_t n = g * 16 + threadIdx.x;
         // part 0's output pointer is a preloaded argument; further parts' come from the argument block
@@ -360,6 +373,7 @@ __device__ __forceinline__ void reduce_store(float acc, float* red, const QMVArg
             if (pub && !(pub->drop && pub_cg == 0)) // the granule first: the attention of this launch waits for it (fused launches carry no epilogues on these parts: planner)
                 __hip_atomic_store((gu64*)pub->gran + (pub_cg * 16 + lane), handoff_granule(__float_as_uint(v), pub_gen), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             out_row[n] = v;
+            if (slices_last) kon_slices(*kon, a, pn_inv, lane);
         }
         if (GROUPED && kind == kEpiSilu) {
             if (pi == 0)
@@ -400,6 +414,9 @@ __device__ __forceinline__ void reduce_store(float acc, float* red, const QMVArg
         }
     } else {
         if (pub && lane == 0) pub->gen[pub_cg] = pub_gen; // (a dropped publish too: the generations stay in step with the consumers')
+#ifdef ZGML_TRACE // where this column group ran (behind everything the attention waits for)
+        if (pub && pub->xcc && lane == 0) pub->xcc[pub_cg] = 1 + xcc_id();
+#endif
     }
 }
 
@@ -1090,16 +1107,32 @@ struct QkvAttnArgs {
     QmvCountPublish cpub; // qkv_attn_kon_kernel: counters (a launch fills the pair its kernel reads)
     CounterHandoff cho;
     uint32_t* census; // (the CENSUS instantiation of qkv_attn_kon_kernel only) [0] arrivals, [1] set when a workgroup gave up waiting for the grid
+    uint32_t colocate; // qkv_attn_kernel: the packed block map (qkv_colocate.h; 0 = identity); the launcher passes it in the head's row-stride slot
 };
+// Which block plays which role comes from qkv_colocate.h: a kv group's projection column groups and split 0 of its heads carry ONE
+// label `blockIdx.x % 8` (blocks of one label share an XCD), so the head-local hand-off stays inside one XCD where the dispatcher
+// deals blocks as observed — and is exactly as correct where it does not (granules: any placement gives the same bits).
+// The launch has one row, so the row-stride slot of the preloaded head (`in_rs`) carries the packed map, and the projection's
+// workgroup count is the sum of its three contiguous parts' (preloaded too): a projection workgroup knows its role with NO
+// argument-block round trip in front of its first load (the comparison with f.n_mv that stood here was one).
 template <typename ST, bool Q4, int LPK, bool KVQ, int PROM = 1>
 __global__ void __launch_bounds__(1024) qkv_attn_kernel(QMV_HEAD_PARAMS, QMVArgs a, QkvAttnArgs f) {
     constexpr int DEPTH = 1; // K <= 2048 with up to 16 waves: one load step
-    if (blockIdx.x < f.n_mv) {
+    const uint32_t NB2_0 = nb2_0_flags & 0xFFFFFu, NB2_1 = nb2_12 & 0xFFFFu, NB2_2 = nb2_12 >> 16, n_mv = NB2_0 + NB2_1 + NB2_2;
+    const QkvColocate co = qkv_colocate_unpack(in_rs);
+    const uint32_t role = qkv_colocate_role(co, blockIdx.x, n_mv, f.ho.n_heads, f.n_sp);
+    if (role < n_mv) {
         const uint32_t n_waves = ((nb2_0_flags >> 20) & 0xFu) + 1;
         if (threadIdx.x >= n_waves * 64) return; // (whole waves: they no longer count at the barriers)
-        qmatvec_body<ST, false, DEPTH, Q4, PROM, true, true, false>(qs0, sc0, out0, xa_base, xb_base, in_rs, K, nb2_0_flags, nb2_12, a, blockIdx.x, &f.pub);
+        uint32_t bx = role;
+        if (co.on) { // the block id the body maps to column group `role` of the launch (column_group inside its part)
+            const uint32_t pi = role < NB2_0 ? 0u : role < NB2_0 + NB2_1 ? 1u : 2u;
+            const uint32_t first = pi == 0 ? 0u : pi == 1 ? NB2_0 : NB2_0 + NB2_1, nb2 = pi == 0 ? NB2_0 : pi == 1 ? NB2_1 : NB2_2;
+            bx = first + column_group_block(role - first, nb2);
+        }
+        qmatvec_body<ST, false, DEPTH, Q4, PROM, true, true, false>(qs0, sc0, out0, xa_base, xb_base, K, K, nb2_0_flags, nb2_12, a, bx, &f.pub);
     } else {
-        const uint32_t b = blockIdx.x - f.n_mv, n_heads = f.ho.n_heads; // head-major: the always-active split 0 of every head first
+        const uint32_t b = role - n_mv, n_heads = f.ho.n_heads; // head-major: the always-active split 0 of every head first
         attention_decode_body<LPK, KVQ>(f.params, f.split_buf, f.split_cnt, f.split_min_keys, b % n_heads, b / n_heads, f.n_sp, &f.ho);
     }
 }
@@ -1626,7 +1659,8 @@ bool launch_packed(hipStream_t s, QMVArgs& a, const QWeightDev& w0, uint32_t tot
         else
             ff = prenorm ? (fused_kvq ? qkv_attn_kernel<__half, true, 32, true, 2> : qkv_attn_kernel<__half, true, 32, false, 2>)
                          : (fused_kvq ? qkv_attn_kernel<__half, true, 32, true> : qkv_attn_kernel<__half, true, 32, false>);
-        hipLaunchKernelGGL(ff, dim3(total_blocks + extra_blocks), dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, head_xa, head_xb, a.in_rs, a.K,
+        // (one row: the row-stride slot carries the packed block map, qkv_attn_kernel)
+        hipLaunchKernelGGL(ff, dim3(total_blocks + extra_blocks), dim3(1024), lds, s, a.parts[0].qs, a.parts[0].sc, a.parts[0].out, head_xa, head_xb, f.colocate, a.K,
                            head_flags(a, waves, true, rmsnorm, late), nb2_12, a, f);
         return true;
     }
@@ -1731,15 +1765,19 @@ bool launch_qkv_attention(hipStream_t s, const QmvLaunch& L, const AttnDecodePar
     }
     if (!hb.granules) return false;
     unsigned long long* const granules = hb.granules;
-    f.pub = QmvPublish{granules, hb.producer_gen, drop};
+    f.pub = QmvPublish{granules, hb.producer_gen, drop, hb.xcc_trace};
     // Where the attention finds a record's granules. The producer stores column n of part c at granule first[c] + n (column groups
     // of q, k, v follow each other in the launch). A record names its slices by pointers into the parts' outputs — fuse_qkv_attention
     // has checked that q_src / k_src / v_src lie inside THESE L.parts[c].dst at multiples of d_head — so the slice's byte offset in
     // the area is 8 * first[c] + 2 * (src - dst[c] in bytes): 8 bytes of granule per 4 of float. The area is far below 4 GB, so the
     // kernel forms that offset in 32 bits from the pointer's low word, offset = 2 * low32(src) + rel[c] (mod 2^32).
     const uint32_t first[3] = {0, n_heads * d_head, (n_heads + n_kv) * d_head};
-    f.ho = DecodeHandoff{granules, {0, 0, 0}, hb.consumer_gen, n_heads, timeout, (uint32_t)sw().hip_handoff_sleep};
+    f.ho = DecodeHandoff{granules, {0, 0, 0}, hb.consumer_gen, n_heads, timeout, (uint32_t)sw().hip_handoff_sleep,
+                         hb.xcc_trace ? hb.xcc_trace + (n_heads + 2 * n_kv) * (d_head / 16) : nullptr};
     for (int c = 0; c < 3; c++) f.ho.rel[c] = 8u * first[c] - 2u * (uint32_t)(uintptr_t)L.parts[c].dst;
+    // a kv group's column groups and split 0 of its heads on one label of block ids (qkv_colocate.h): only where the records are in
+    // kv-group order, and the identity wherever the groups do not fit their labels
+    if (hb.group_order) f.colocate = qkv_colocate_pack(qkv_colocate_plan(n_heads, n_kv, d_head, f.n_sp));
     return launch_qmv(s, L, &f, n_heads * f.n_sp, d_head);
 }
 

@@ -46,6 +46,13 @@ __device__ __forceinline__ uint32_t column_group(uint32_t b, uint32_t NB2) {
     const uint32_t j = (b >> 4) * 8 + (b & 7), half = (b >> 3) & 1;
     return 2 * j + half;
 }
+// ... and its inverse: the block that column_group maps to column group g
+__device__ __forceinline__ uint32_t column_group_block(uint32_t g, uint32_t NB2) {
+    const uint32_t full = NB2 & ~15u;
+    if (g >= full) return g;
+    const uint32_t j = g >> 1, half = g & 1;
+    return (j >> 3) * 16 + half * 8 + (j & 7);
+}
 
 // Weight loads. NT: non-temporal (`global_load … nt`) — for weight sets larger than the 256 MB
 // Infinity Cache every byte is read once per token, and not allocating it in the caches is worth

@@ -1419,6 +1419,26 @@ void zgml_hip_free_program(zgml_hip_ctx* ctx, zgml_hip_program* p) {
         }
         for (auto* t : p->attn_traces) hipHostFree(t);
     }
+    if (!p->xcc_traces.empty()) { // of the last execution: how many (projection column group, consuming head) pairs shared an XCD
+        uint64_t pairs0 = 0, same0 = 0, pairs_n = 0, same_n = 0;
+        for (const auto& x : p->xcc_traces) {
+            const uint32_t pk = x.d_head / 16, hpg = x.n_heads / x.n_kv, nq = x.n_heads * pk, nk = x.n_kv * pk;
+            for (uint32_t r = 0; r < x.n_heads; r++) // (recorded only where record r is a head of kv group r / hpg: fuse_qkv_attention)
+                for (uint32_t sp = 0; sp < x.n_sp; sp++) {
+                    const uint32_t c = x.w[x.n_mv + r * x.n_sp + sp];
+                    if (!c) continue; // an idle split
+                    for (uint32_t i = 0; i < 3 * pk; i++) {
+                        const uint32_t part = i / pk, g = i % pk, cg = part == 0 ? r * pk + g : nq + (part - 1) * nk + (r / hpg) * pk + g;
+                        if (!x.w[cg]) continue;
+                        (sp ? pairs_n : pairs0)++;
+                        if (x.w[cg] == c) (sp ? same_n : same0)++;
+                    }
+                }
+        }
+        fprintf(stderr, "[zgml_hip] fused q/k/v + attention, %zu launches: producer / consumer pairs on one XCD: split 0 %llu of %llu, splits >= 1 %llu of %llu\n",
+                p->xcc_traces.size(), (unsigned long long)same0, (unsigned long long)pairs0, (unsigned long long)same_n, (unsigned long long)pairs_n);
+        for (const auto& x : p->xcc_traces) hipHostFree(x.w);
+    }
     if (!p->ks_traces.empty()) {
         fprintf(stderr, "[zgml_hip] K-split launches, workgroup 0, ns between stamps (gap = since the previous launch's last stamp); ks-proj / ks-mlp: start | loads issued | "
                         "parts summed | vector whole | x staged | FMAs | barrier | folded (mlp: + SiLU) | (mlp: barrier | down partial); ks-attn-o: start | record | loads issued | attention | merged | partial O\n");

@@ -219,6 +219,11 @@ struct zgml_hip_program {
     void* arena = nullptr;
     std::vector<QWeightDev> qweights;
     std::vector<unsigned long long*> attn_traces; // diagnostics (ZGML_HIP_ATTN_TRACE)
+    struct XccTrace { // ... and where the workgroups of each fused q / k / v + attention launch ran: 1 + XCC id (0: not recorded)
+        uint32_t* w;  // [n_mv column groups | n_heads x n_sp attention workgroups, record-major]
+        uint32_t n_mv, n_heads, n_kv, d_head, n_sp;
+    };
+    std::vector<XccTrace> xcc_traces;
     struct QmvTrace {
         unsigned long long* t;
         uint32_t parts, pro, K, N;
