@@ -950,11 +950,12 @@ int zgml_hip_resident_decode_batch_speculative_sampled(zgml_hip_ctx* ctx, zgml_h
  *   unconstrained.
  *   zgml_hip_resident_decode_speculative_constrained (below) honours sequence 0's in the verify step of a token_len = T plan,
  *   zgml_hip_resident_decode_batch_speculative_constrained (below) every sequence's own in the verify step of a batched plan with
- *   tokens_per_seq >= 2.
+ *   tokens_per_seq >= 2, zgml_hip_resident_decode_speculative_model_constrained (below) the TARGET's sequence 0's in the drafts
+ *   of a draft model and in the verify step.
  * Refused. While any constraint is attached to the program, zgml_hip_resident_decode, zgml_hip_resident_decode_batch,
  *   zgml_hip_resident_decode_speculative, zgml_hip_resident_decode_speculative_sampled, zgml_hip_resident_decode_batch_speculative,
  *   zgml_hip_resident_decode_batch_speculative_sampled, zgml_hip_resident_decode_speculative_model and zgml_hip_resident_decode_batch_speculative_model (a constraint on
- *   the target or on the draft: forced tokens between draft executions are not served) and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
+ *   the target or on the draft; zgml_hip_resident_decode_speculative_model_constrained serves one on the target of a single sequence) and zgml_hip_shard_step return -1 with an error on the context and enqueue nothing: they would pick tokens while ignoring the
  *   constraint. */
 typedef struct zgml_token_dfa {
     uint32_t n_states, n_classes, vocab, _pad; /* 1 <= n_states <= 65535, 1 <= n_classes <= 8192 */
@@ -1082,15 +1083,49 @@ int zgml_hip_resident_decode_batch_speculative_constrained(zgml_hip_ctx* ctx, zg
  *   zgml_hip_resident_decode_speculative refuses of the target and of the request (history / n_history as its opt->history), with
  *   `sampling` everything _speculative_sampled refuses; a sharded target; a draft that is NULL, without a resident set-up, of
  *   another context, batched, token_len != 1, sharded, the target itself, or of another vocabulary;
- *   start_pos + n_tokens + T - 1 > the draft's max_seq; a constraint attached to either program (forced tokens would have to be
- *   placed between the draft executions: not served yet, like a draft model in front of
- *   zgml_hip_resident_decode_speculative_constrained; a draft model under batching is
+ *   start_pos + n_tokens + T - 1 > the draft's max_seq; a constraint attached to either program (a draft model under the
+ *   target's constraint is zgml_hip_resident_decode_speculative_model_constrained, below; a draft model under batching is
  *   zgml_hip_resident_decode_batch_speculative_model). n_tokens = 0 returns 0 and touches nothing. */
 int zgml_hip_resident_decode_speculative_model(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft, uint32_t first_token,
                                                uint32_t start_pos, uint32_t n_tokens, const uint32_t* history /* [n_history] */,
                                                uint32_t n_history /* 0 or start_pos */, const zgml_sampling* sampling /* NULL: greedy */,
                                                int64_t* tokens_out /* [n_tokens] */, uint32_t* n_produced /* may be NULL */,
                                                zgml_spec_stats* stats /* may be NULL */);
+
+/* ── Speculative decode with a draft model under a constraint: the draft is masked (rule: zgml_amd/csrc/spec.h, DRAFTS FROM A
+ * MODEL UNDER A CONSTRAINT). A sibling of zgml_hip_resident_decode_speculative_model, not a mode of it: that call keeps refusing
+ * an attached constraint. The constraint is the one attached to the TARGET (zgml_hip_program_set_constraint, sequence 0); the
+ * programs are those of zgml_hip_resident_decode_speculative_model.
+ * Verify step at (hist[pos], pos). c[0] = hist[pos], row_state[0] = the sequence's state. For j = 0 .. T-1 the draft executes on
+ *   c[j] at position pos + j and stores its own KV column. For j < T - 1, with s = row_state[j]: s dead, or s allows no token ->
+ *   there is no draft, c[j + 1] = c[j] and row j + 1 is dead; otherwise c[j + 1] = the first maximum of the draft's logits row
+ *   over the tokens allowed in s (larger value wins, lower index among equals; a forbidden token is no candidate at all, so the
+ *   first allowed token wins over a row of -inf) and row_state[j + 1] = next[s][class_of[c[j + 1]]], never dead. In a state that
+ *   forces a token the masked maximum is that token whatever the logits say: forced runs are drafted without a placing pass.
+ *   stats.drafted grows, per step that emits something, by the rows j in 1 .. T-1 that are not dead; no pads, no forced count.
+ * Behind the drafts the step is zgml_hip_resident_decode_speculative_constrained's, all of it: the constrained picks under
+ *   row_state[j], acceptance, the dead-end cut, stop tokens, penalties over the call's device history, `logprobs`,
+ *   `top_logprobs`, the result getters, the advance of the state word over exactly the emitted tokens. top_k = 1 is the greedy
+ *   form. Idle steps make every row dead; their draft executions repeat one token.
+ * Exactness. Every emitted token is the target's constrained pick over a confirmed context at its own position and state. The
+ *   drafts — masked or not — change how many steps run, never which tokens come out.
+ * With no constraint attached to the target the call IS zgml_hip_resident_decode_speculative_model with `sampling`: same tokens,
+ *   statistics, launches and graphs.
+ * Launches. One graph launch per step: [draft launch] T x { [draft prep] [draft plan] [masked argmax stage 1] [stage 2 +
+ *   constrained draft advance] } [prep, T columns] [target plan] [constrained-rows select] [merge + pick] ([log-probability
+ *   launches]) [accept] — no launch more than zgml_hip_resident_decode_speculative_model with `sampling`. The graphs belong to the
+ *   (target, draft) pair, one per form; the automaton's pointers and the state live in the target's device table, so attaching
+ *   another automaton, or none, between calls re-captures nothing, and other calls on either program alternate with this one.
+ *   Runtime profile: the target counts plan + 3 + tail launches per step, the draft T x (plan + 3).
+ * Blocking. Returns 0. Refused with -1 and an error on the context, before anything is enqueued: sampling == NULL; everything
+ *   zgml_hip_resident_decode_speculative_model with `sampling` refuses except the target's constraint — a constraint attached to
+ *   the DRAFT stays refused. The state on entry is what zgml_hip_program_set_constraint accepted or an earlier call left.
+ *   n_tokens = 0 returns 0 and touches nothing. */
+int zgml_hip_resident_decode_speculative_model_constrained(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft,
+                                                           uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
+                                                           const uint32_t* history /* [n_history] */, uint32_t n_history /* 0 or start_pos */,
+                                                           const zgml_sampling* sampling /* not NULL */, int64_t* tokens_out /* [n_tokens] */,
+                                                           uint32_t* n_produced /* may be NULL */, zgml_spec_stats* stats /* may be NULL */);
 
 /* ── A draft model under batching: B sequences, one graph. The call above for every sequence of a batched plan, and a sibling of
  * zgml_hip_resident_decode_batch_speculative and _batch_speculative_sampled, not a mode of them: those keep refusing mode > 1.

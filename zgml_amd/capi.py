@@ -323,6 +323,7 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_decode_speculative_model",
     "zgml_hip_resident_decode_batch_speculative_constrained",
     "zgml_hip_resident_decode_batch_speculative_model",
+    "zgml_hip_resident_decode_speculative_model_constrained",
 ]
 
 class KvLaneC(C.Structure):
@@ -511,6 +512,10 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_resident_decode_batch_speculative_model.argtypes = [vp, vp, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), u32,
                                                                          C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(SamplingC), vp, C.POINTER(u32),
                                                                          C.POINTER(SpecStatsC)]
+    if hasattr(lib, "zgml_hip_resident_decode_speculative_model_constrained"):  # absent from an older build loaded through ZGML_HIP_LIB (A/B runs)
+        lib.zgml_hip_resident_decode_speculative_model_constrained.restype = i32
+        lib.zgml_hip_resident_decode_speculative_model_constrained.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(SamplingC), vp,
+                                                                               C.POINTER(u32), C.POINTER(SpecStatsC)]
     lib.zgml_hip_kv_move.restype = i32
     lib.zgml_hip_kv_move.argtypes = [vp, vp, C.POINTER(KvLaneC), vp, C.POINTER(KvLaneC), u64, u32, u32, u32]
     lib.zgml_hip_copy_bench.restype = C.c_double

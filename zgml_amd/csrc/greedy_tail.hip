@@ -7,6 +7,7 @@
 //   launch_argmax_draft         the two stages behind a draft program's execution inside a verify step: stage 2 ends with the
 //                               draft advance (the draft's next token and position, the target's next candidate)
 //   launch_argmax_batch_draft   ... behind a BATCHED draft program's execution: B rows, sequence b's draft advance
+//   launch_argmax_draft_constrained  ... under the target's constraint: stage 1 masked by the walk's state, the constrained draft advance
 //   launch_argmax_batch         the same two stages over B rows (blockIdx.y = sequence), the batched loop's advance;
 //   launch_argmax_rows_stage1   its stage 1 alone (a greedy verify step: spec_accept_kernel folds the pairs)
 // Every workgroup has 256 threads and the same two LDS arrays; a row takes n / 1024 + 1 workgroups, at most 256.
@@ -180,6 +181,57 @@ __global__ void __launch_bounds__(kBlock) argmax_batch_stage2_draft(const float*
     if (threadIdx.x == 0) tail_advance_draft(adv, blockIdx.y, (uint64_t)next < n ? (uint32_t)next : 0u);
 }
 
+// ... behind one execution of a draft program under the target's constraint (kernels.h: DraftConstraint): workgroup (x, b) scans
+// its share of row b over the tokens that the walk's state allows. The state word is read here, at run time. A dead state leaves
+// in front of any barrier and any table read — next + s * n_classes is never formed with it —, its pair empty; the row
+// next[s] is staged as sample.hip's select_body stages it (global loads: the pointers come from a device table). A sequence
+// without an automaton scans the plain way.
+// LDS: 3 KiB of pairs, at most 16 KiB of state row
+__global__ void __launch_bounds__(kBlock) argmax_batch_stage1_masked(const float* __restrict__ v, uint64_t n, float* out_val, int64_t* out_idx, DraftConstraint dc) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    __shared__ uint16_t crow[kConstraintMaxClasses];
+    const uint32_t b = blockIdx.y, nblk = gridDim.x;
+    const SampleConstraintRow cr = dc.rows[b];
+    if (!cr.con_active) { // (uniform)
+        argmax_stage1_body(sv, si, b, v, n, nblk, out_val, out_idx);
+        return;
+    }
+    const uint32_t s = dc.row_state[(uint64_t)b * dc.stride];
+    if (s == kConstraintDead) { // (uniform) no draft: the advance does not look at the pairs, they are empty all the same
+        if (threadIdx.x == 0) out_val[b * nblk + blockIdx.x] = -INFINITY, out_idx[b * nblk + blockIdx.x] = INT64_MAX;
+        return;
+    }
+    using global_u16 = const __attribute__((address_space(1))) uint16_t;
+    global_u16* const class_of = (global_u16*)cr.class_of;
+    global_u16* const from = (global_u16*)cr.next + (uint64_t)s * cr.n_classes;
+    for (uint32_t t = threadIdx.x; t < cr.n_classes; t += kBlock) crow[t] = from[t];
+    __syncthreads(); // crow is whole before the scan reads it
+    float bv;
+    int64_t bi;
+    arg_scan_masked(v + (uint64_t)b * n, n, nblk, crow, class_of, bv, bi);
+    arg_block_reduce<true>(sv, si, bv, bi);
+    if (threadIdx.x == 0) {
+        out_val[b * nblk + blockIdx.x] = sv[0];
+        out_idx[b * nblk + blockIdx.x] = si[0];
+    }
+}
+
+// ... and its stage 2: the empty-aware fold, then the constrained draft advance (tail_device.h). An empty fold, or an index that
+// is not one of the row's, is "no draft"
+__global__ void __launch_bounds__(kBlock) argmax_batch_stage2_draft_constrained(const float* vals, const int64_t* idxs, int nblk, uint64_t n, DraftAdvance adv, DraftConstraint dc) {
+    __shared__ float sv[kBlock];
+    __shared__ int64_t si[kBlock];
+    const int64_t next = argmax_stage2_body(sv, si, blockIdx.y, vals, idxs, nblk);
+    if (threadIdx.x != 0) return;
+    const uint32_t b = blockIdx.y;
+    const SampleConstraintRow cr = dc.rows[b];
+    if (!cr.con_active)
+        tail_advance_draft(adv, b, (uint64_t)next < n ? (uint32_t)next : 0u);
+    else
+        tail_advance_draft_constrained(adv, dc, cr, b, (uint64_t)next < n ? next : -1);
+}
+
 } // namespace
 
 void launch_resident_prep(hipStream_t s, const ResidentPrepArgs& a, uint32_t total) {
@@ -228,6 +280,13 @@ void launch_argmax_batch_draft(hipStream_t s, const float* v, uint64_t n, float*
     const int nblk = argmax_batch_blocks(n);
     argmax_batch_stage1<<<dim3(nblk, adv.n_seqs), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx);
     argmax_batch_stage2_draft<<<dim3(1, adv.n_seqs), kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, n, adv);
+}
+
+void launch_argmax_draft_constrained(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv,
+                                     const DraftConstraint& dc) {
+    const int nblk = argmax_batch_blocks(n);
+    argmax_batch_stage1_masked<<<dim3(nblk, adv.n_seqs), kBlock, 0, s>>>(v, n, scratch_val, scratch_idx, dc);
+    argmax_batch_stage2_draft_constrained<<<dim3(1, adv.n_seqs), kBlock, 0, s>>>(scratch_val, scratch_idx, nblk, n, adv, dc);
 }
 
 void launch_argmax_fold(hipStream_t s, const float* scratch_val, const int64_t* scratch_idx, uint32_t nblk, int64_t* out, const ArgmaxAdvance& adv) {

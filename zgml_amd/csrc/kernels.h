@@ -420,6 +420,23 @@ void launch_argmax_draft(hipStream_t s, const float* v, uint64_t n, float* scrat
 // adv.n_seqs logits rows (blockIdx.y = sequence), stage 2 ending with sequence b's draft advance. Unlike launch_argmax_batch it
 // reads neither the steps-left nor the produced words and writes no token table. scratch: n_seqs * argmax_batch_blocks(n) pairs.
 void launch_argmax_batch_draft(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv);
+// ... behind execution j of a draft program UNDER THE TARGET'S CONSTRAINT (zgml_hip_resident_decode_speculative_model_constrained;
+// spec.h: DRAFTS FROM A MODEL UNDER A CONSTRAINT): stage 1 is masked by the state the walk has reached, stage 2 folds pairs that
+// may all be empty and ends with the constrained draft advance. Over the batched layout (blockIdx.y = sequence, adv.n_seqs of
+// them), of which the single-sequence call is the one-plane view: rows[b] is sequence b's row of the target's device table
+// (con_active = 0: its draft is the plain one), and the walk's state word IS the row state — execution j is handed
+// row_state = the target's row_state + j, reads row_state[b * stride] (at run time: the draft launch and the advances in front
+// wrote it) and, with adv.cand_next, writes row_state[b * stride + 1] and adds to drafted[b * drafted_stride].
+struct SampleConstraintRow;
+struct DraftConstraint {
+    const SampleConstraintRow* rows = nullptr;
+    uint32_t* row_state = nullptr;
+    uint32_t stride = 0;
+    uint32_t* drafted = nullptr;
+    uint32_t drafted_stride = 0;
+};
+void launch_argmax_draft_constrained(hipStream_t s, const float* v, uint64_t n, float* scratch_val, int64_t* scratch_idx, const DraftAdvance& adv,
+                                     const DraftConstraint& dc);
 // Everything LlamaInferencePlan.execute patches on the host per execution (src/llama_inference.zig:405-446; for T > 1
 // patch_tokens of zgml_amd/host/llama_decode.cpp), produced on the device as one flat index space: T embedding rows, T
 // causal-mask columns, T RoPE rows per layer leaf, the dynamic words (KV store offsets at `pos`, seq_kv = pos + T).
@@ -485,7 +502,7 @@ enum SpecWord : uint32_t {
     kSpecPos,      // its position
     kSpecProduced, // tokens produced so far
     kSpecWanted,   // n_tokens of the call
-    kSpecMode,     // 0 lookup, 1 provided, 2 a draft model (zgml_hip_resident_decode_speculative_model and its batched sibling alone set it)
+    kSpecMode,     // 0 lookup, 1 provided, 2 a draft model (zgml_hip_resident_decode_speculative_model, its constrained and its batched sibling alone set it)
     kSpecNgram,
     kSpecNDrafts,
     kSpecStart,    // start_pos of the call
@@ -525,7 +542,9 @@ struct SpecArgs {
     // the constrained form (zgml_hip_resident_decode_speculative_constrained; spec.h: UNDER A CONSTRAINT), over the sampled one:
     // con_row = the sequence's row of the device table (read at replay time: the graph outlives an attachment), con_state its
     // state word, row_state[T] the rows' states — the draft launch fills them behind the candidates (all dead in an idle step),
-    // the constrained select launch reads them, the accept launch advances con_state over the emitted tokens. nullptr: none
+    // the constrained select launch reads them, the accept launch advances con_state over the emitted tokens. nullptr: none.
+    // With drafts from a model (mode 2; zgml_hip_resident_decode_speculative_model_constrained) the draft launch fills
+    // row_state[0] alone: the masked draft executions write the rows behind it (DraftConstraint, above)
     const SampleConstraintRow* con_row = nullptr;
     uint32_t* con_state = nullptr;
     uint32_t* row_state = nullptr;

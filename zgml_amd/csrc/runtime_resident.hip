@@ -1265,6 +1265,10 @@ bool spec_request(zgml_hip_ctx* ctx, const Resident* r, const std::string& who, 
 // one graph launch, a linear chain. Either form of the verify step; `opt` carries the history alone. The graphs belong to the
 // pair (Resident::pair_graph); each program's profile counts its own launches. The draft executions are the plain form: the
 // streaming head and the position part written a token ahead (zgml_hip_resident_decode) are not carried over.
+// `model` and `honours_constraint` (zgml_hip_resident_decode_speculative_model_constrained; spec.h: DRAFTS FROM A MODEL UNDER A
+// CONSTRAINT): with a constraint attached to the target the two argmax launches of every draft execution are the masked ones
+// (launch_argmax_draft_constrained) — execution j reads row j's state and writes row j + 1's — in front of the constrained verify
+// step; launch for launch the chain above, in the pair's constrained-rows slots. Without a constraint it is the `model` form.
 int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,
                 const zgml_spec_decode* opt, bool sampled, const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats,
                 bool honours_constraint = false, bool model = false, zgml_hip_program* draft = nullptr) {
@@ -1298,7 +1302,7 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
             ctx->fail(who + ": " + why);
             return -1;
         }
-        if (has_constraint(draft)) { // (forced tokens would have to be placed between the draft executions: not served)
+        if (has_constraint(draft)) { // (the automaton that masks the drafts is the TARGET's: zgml_hip_resident_decode_speculative_model_constrained)
             ctx->fail(who + ": a constraint is attached to the draft program (detach it first)");
             return -1;
         }
@@ -1383,7 +1387,11 @@ int spec_decode(zgml_hip_ctx* ctx, zgml_hip_program* p, const std::string& who, 
         for (uint32_t j = 0; dr && j < T; j++) {
             launch_resident_prep(st, dprep.a, dprep.total);
             run_plan(draft, st, 0, draft->plan.size());
-            launch_argmax_draft(st, dr->logits, dr->vocab, ctx->arg_val, ctx->arg_idx, DraftAdvance{dr->state, j + 1 < T ? r->tok_dev + j + 1 : nullptr});
+            const DraftAdvance adv{dr->state, j + 1 < T ? r->tok_dev + j + 1 : nullptr};
+            if (constrained) // the walk stands at row j's state; the advance writes row j + 1's and counts the draft
+                launch_argmax_draft_constrained(st, dr->logits, dr->vocab, ctx->arg_val, ctx->arg_idx, adv, DraftConstraint{r->con_rows, r->row_state + j, T, r->spec + kSpecDrafted, kSpecWords});
+            else
+                launch_argmax_draft(st, dr->logits, dr->vocab, ctx->arg_val, ctx->arg_idx, adv);
         }
         launch_resident_prep(st, prep.a, prep.total);
         run_plan(p, st, 0, p->plan.size());
@@ -1450,6 +1458,20 @@ int zgml_hip_resident_decode_speculative_model(zgml_hip_ctx* ctx, zgml_hip_progr
     const zgml_spec_decode opt{history, n_history, 0, nullptr, 0, 0};
     return spec_decode(ctx, target, "resident_decode_speculative_model", first_token, start_pos, n_tokens, &opt, sampling != nullptr, sampling, tokens_out, n_produced,
                        stats, false, true, draft);
+}
+
+int zgml_hip_resident_decode_speculative_model_constrained(zgml_hip_ctx* ctx, zgml_hip_program* target, zgml_hip_program* draft, uint32_t first_token,
+                                                           uint32_t start_pos, uint32_t n_tokens, const uint32_t* history, uint32_t n_history,
+                                                           const zgml_sampling* sampling, int64_t* tokens_out, uint32_t* n_produced, zgml_spec_stats* stats) {
+    if (!ctx) return -1;
+    if (!sampling) { // (the verify step is the constrained one, which is a sampled one: top_k = 1 is its greedy form)
+        if (n_produced) *n_produced = 0;
+        ctx->fail("resident_decode_speculative_model_constrained: sampling is NULL (the constrained verify step is a sampled one: top_k = 1 is the greedy form)");
+        return -1;
+    }
+    const zgml_spec_decode opt{history, n_history, 0, nullptr, 0, 0};
+    return spec_decode(ctx, target, "resident_decode_speculative_model_constrained", first_token, start_pos, n_tokens, &opt, true, sampling, tokens_out, n_produced,
+                       stats, true, true, draft);
 }
 
 int zgml_hip_resident_decode_speculative(zgml_hip_ctx* ctx, zgml_hip_program* p, uint32_t first_token, uint32_t start_pos, uint32_t n_tokens,

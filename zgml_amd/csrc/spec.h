@@ -190,6 +190,63 @@ ZGML_SPEC_FN uint32_t spec_free_rows(uint32_t* row_state, uint32_t T) {
 }
 ZGML_SPEC_FN bool spec_row_selects(uint32_t row_state) { return row_state != kConstraintDead; }
 
+// ── DRAFTS FROM A MODEL UNDER A CONSTRAINT (zgml_hip_resident_decode_speculative_model_constrained): the draft is masked ──
+// DRAFTS FROM A MODEL with the TARGET's automaton walked between the draft executions. A verify step runs at (hist[pos], pos);
+// c[0] = hist[pos], row_state[0] = the sequence's state. For j = 0 .. T-1 the draft program executes on c[j] at pos + j and
+// stores its own KV column, as without a constraint. For j < T - 1, with s = row_state[j]:
+//   s dead, or s allows no token   there is no draft: c[j + 1] = c[j] (a valid token: the draft's next execution and the target's
+//                                  prep stay in range) and row_state[j + 1] = kConstraintDead
+//   otherwise                      c[j + 1] = the first maximum of the draft's logits row over the tokens ALLOWED in s
+//                                  (constraint_row_allows(next[s], class_of[t])), in the order of the plain first maximum: larger
+//                                  value wins, lower index among equals; a forbidden token contributes nothing, so the first allowed
+//                                  token wins when nothing beats it (a row of -inf). row_state[j + 1] = next[s][class_of[c[j + 1]]],
+//                                  never dead.
+// The T-th execution exists for its KV column alone; its maximum is dropped. `drafted` grows, per step that is not idle, by the
+// number of j in 1 .. T-1 with row_state[j] != kConstraintDead: no pads are counted and there is no separate count of forced
+// tokens. An idle step makes every row dead (so its draft executions repeat one token). Everything behind the drafts is UNDER A
+// CONSTRAINT's: g[j] the constrained pick under row_state[j] or kSpecNoPick, spec_accept, spec_emit_count, spec_dead_end_cut,
+// spec_stop_cut, spec_state_advance. Every emitted token is the target's constrained pick over a confirmed context at its own
+// position and state: the drafts change how many steps run, never the tokens.
+// A consequence: in a state with forced[s] != kConstraintNoForced exactly one token is allowed, so the masked first maximum IS
+// forced[s] whatever the logits are — the draft rule serves forced tokens without a forced[] lookup and without a placing pass.
+// What the draft launch leaves of this rule: c[0] (spec_candidates_model) and row_state[0]; the executions' advances write the rest.
+
+// the first maximum of row[0, vocab) over the tokens allowed by the state row `srow` = next[s]; -1: s allows no token
+ZGML_SPEC_FN int64_t spec_masked_first_max(const float* row, uint32_t vocab, const uint16_t* srow, const uint16_t* class_of) {
+    int64_t best = -1;
+    for (uint32_t t = 0; t < vocab; t++)
+        if (constraint_row_allows(srow, class_of[t]) && (best < 0 || row[t] > row[best])) best = t; // strict >: the lower index wins among equals
+    return best;
+}
+
+// behind execution j < T - 1: d = the masked first maximum under s = row_state[j] (anything when s is dead; -1: none), c_prev =
+// c[j] -> c[j + 1], row_state[j + 1]; returns what `drafted` grows by
+ZGML_SPEC_FN uint32_t spec_draft_advance_constrained(uint32_t c_prev, uint32_t s, int64_t d, const uint16_t* class_of, const uint16_t* next, uint32_t n_classes,
+                                                     uint32_t* c_next, uint32_t* s_next) {
+    if (s == kConstraintDead || d < 0) {
+        *c_next = c_prev, *s_next = kConstraintDead;
+        return 0;
+    }
+    *c_next = (uint32_t)d, *s_next = constraint_advance(next, n_classes, class_of, s, (uint32_t)d); // (d is allowed in s: never dead)
+    return 1;
+}
+
+// the whole rule of a step, for the host probe (the kernels evaluate it one execution at a time): draft_row(j, c) is the logits
+// row of the draft's execution j given c[0..j]; behind a dead state it is not asked for. Returns what `drafted` grows by
+template <class RowOf>
+ZGML_SPEC_FN uint32_t spec_candidates_model_constrained(uint32_t tok, uint32_t T, uint32_t vocab, uint32_t state, const uint16_t* class_of, const uint16_t* next,
+                                                        uint32_t n_classes, RowOf draft_row, uint32_t* c, uint32_t* row_state) {
+    uint32_t drafted = 0;
+    spec_candidates_model(tok, T, c);
+    row_state[0] = state;
+    for (uint32_t j = 0; j + 1 < T; j++) {
+        const uint32_t s = row_state[j];
+        const int64_t d = s == kConstraintDead ? -1 : spec_masked_first_max(draft_row(j, c), vocab, next + (uint64_t)s * n_classes, class_of);
+        drafted += spec_draft_advance_constrained(c[j], s, d, class_of, next, n_classes, &c[j + 1], &row_state[j + 1]);
+    }
+    return drafted;
+}
+
 // the dead-end cut: g[acc] without a pick ends the emission in front of itself — at most acc of the m tokens come out — and
 // finishes the call (*dead). m: what spec_emit_count left
 template <class G>

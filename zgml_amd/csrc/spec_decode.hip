@@ -25,12 +25,24 @@ __device__ __forceinline__ uint32_t spec_constrain(const SpecArgs& a, uint32_t r
     return spec_constrain_candidates(a.cand, a.T, real, *a.con_state, cr.class_of, cr.next, cr.n_classes, cr.forced, a.row_state);
 }
 
+// (thread 0, the model mode) what the draft launch leaves of the rows' states, and what `drafted` grows by up front. Without a
+// constraint: nothing, and the mode's T - 1. Under one (spec.h: DRAFTS FROM A MODEL UNDER A CONSTRAINT) row 0 gets the sequence's
+// state — the walk starts there; the masked draft executions write the rows behind it and count their own drafts —, and nothing
+// is counted here
+__device__ __forceinline__ uint32_t spec_model_rows(const SpecArgs& a, uint32_t real) {
+    if (!a.con_row) return real;
+    if (!a.con_row->con_active) return real + spec_free_rows(a.row_state, a.T);
+    a.row_state[0] = *a.con_state;
+    return 0;
+}
+
 // The candidates of this step into a.cand (what the prep launch reads as its T token ids) and the position it runs at into the
 // run words. Lookup mode: for n = ngram .. 1 the threads walk the match positions [n - 1, pos - 1] downwards, 256 apart — a
 // thread's first hit is its largest —, the largest hit of the workgroup is folded with wave shuffles and one pass over LDS, and
 // the first n with a hit wins. Provided mode is a table read. The model mode (spec.h: DRAFTS FROM A MODEL) writes c[0] and hands
 // (c[0], position) to the draft program's state words — token at draft_state[0], position a.draft_pos words behind it: a plain
 // draft's two words, or sequence b's of a batched draft's state —: the draft executions between this launch and the prep fill in the rest.
+// Under the target's constraint it also hands the walk its first state, row_state[0] (spec_model_rows).
 // Thread 0 writes. fold: kSpecWaves LDS words.
 // kIdleAtEnd: where a sequence that has its count runs its idle steps (below).
 template <bool kIdleAtEnd>
@@ -54,7 +66,8 @@ __device__ __forceinline__ void spec_draft_body(const SpecArgs& a, int32_t* fold
     }
     if (w[kSpecMode] == 2) { // drafts from a model: c[0] and the draft program's first execution; its advances write c[1..T-1]
         if (threadIdx.x == 0) {
-            w[kSpecDrafted] += spec_candidates_model(a.hist[pos], a.T, a.cand);
+            const uint32_t real = spec_candidates_model(a.hist[pos], a.T, a.cand);
+            w[kSpecDrafted] += spec_model_rows(a, real);
             w[kSpecRunPos] = pos;
             a.draft_state[0] = a.hist[pos], a.draft_state[a.draft_pos] = pos;
         }

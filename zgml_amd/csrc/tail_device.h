@@ -5,11 +5,13 @@
 //   the bitonic stage            sample.hip's select and merge sorts, top_logprob.hip's merge of the lists' heads
 //   the argmax pieces            first maximum wins: a thread's scan, the block reductions, the empty-aware fold, its wave form
 //   the advances                 of the single loop's and of the batched loop's device state, behind a greedy or a sampled pick,
-//                                and of a draft program's state words behind one of its executions inside a verify step
+//                                and of a draft program's state words behind one of its executions inside a verify step, plain
+//                                and under the target's constraint; the masked form of a thread's scan goes with the latter
 //   the log-probability finish   which token and where its value goes; M, the blocks' terms and their sum over ascending b
 #pragma once
 #include "kernels.h"
 #include "sample.h"
+#include "spec.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -91,6 +93,22 @@ __device__ __forceinline__ void arg_scan(const float* __restrict__ row, uint64_t
     }
 }
 
+// ... over the tokens a state row allows (spec.h: DRAFTS FROM A MODEL UNDER A CONSTRAINT): crow = next[s], staged in LDS, class_of
+// a global-address-space pointer (sample.hip: select_body). Both loads stand in front of the test; a thread that saw no allowed
+// token keeps the empty pair, and an allowed -inf is taken while the pair is empty: the first allowed token wins when nothing beats it
+template <class ClassOf>
+__device__ __forceinline__ void arg_scan_masked(const float* __restrict__ row, uint64_t n, uint32_t nblk, const uint16_t* crow, ClassOf class_of, float& bv, int64_t& bi) {
+    bv = -INFINITY, bi = INT64_MAX;
+    for (uint64_t i = (uint64_t)blockIdx.x * kArgBlock + threadIdx.x; i < n; i += (uint64_t)nblk * kArgBlock) {
+        const float x = row[i];
+        const uint16_t cls = class_of[i];
+        if (constraint_row_allows(crow, cls) && (x > bv || bi == INT64_MAX)) {
+            bv = x;
+            bi = (int64_t)i;
+        }
+    }
+}
+
 // the workgroup's pair from its 256 threads' into sv[0], si[0] (two LDS arrays of 256); kEmptyAware: with arg_fold, for pairs
 // that may be empty. Ends with a barrier
 template <bool kEmptyAware>
@@ -152,6 +170,18 @@ __device__ __forceinline__ void tail_advance_draft(const DraftAdvance& adv, uint
     adv.state[b] = d;
     adv.state[adv.n_seqs + b] += 1;
     if (adv.cand_next) adv.cand_next[(uint64_t)b * adv.cand_stride] = d;
+}
+
+// ... under the target's constraint (kernels.h: DraftConstraint; spec.h: DRAFTS FROM A MODEL UNDER A CONSTRAINT): d is the masked
+// first maximum under the row state the walk stands at, -1 when the fold was empty. No draft — a dead state, or one that allows
+// no token — repeats the draft's token and makes the next row dead. The step's last execution (no cand_next) writes no row state
+// and counts nothing
+__device__ __forceinline__ void tail_advance_draft_constrained(const DraftAdvance& adv, const DraftConstraint& dc, const SampleConstraintRow& cr, uint32_t b, int64_t d) {
+    uint32_t* const rs = dc.row_state + (uint64_t)b * dc.stride;
+    uint32_t c_next, s_next;
+    const uint32_t placed = spec_draft_advance_constrained(adv.state[b], rs[0], d, cr.class_of, cr.next, cr.n_classes, &c_next, &s_next);
+    tail_advance_draft(adv, b, c_next);
+    if (adv.cand_next) rs[1] = s_next, dc.drafted[(uint64_t)b * dc.drafted_stride] += placed;
 }
 
 // ── the log-probability finish (the rule: sample.h, THE LOG-PROBABILITY) ──

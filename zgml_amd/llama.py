@@ -690,8 +690,21 @@ class Session:
             return toks[:n_tokens], int(produced.value), st, lps
         return toks[:n_tokens], int(produced.value), st, lps, self._alternatives(n_tokens)
 
+    def resident_decode_speculative_model_constrained(self, draft_session: "Session", first_token: int, start_pos: int, n_tokens: int,
+                                                      sampling: "capi.SamplingC", history=None, logprobs: bool = False, top_logprobs: int = 0):
+        """zgml_hip_resident_decode_speculative_model_constrained: resident_decode_speculative_model under the automaton attached to
+        THIS session (set_constraint) — every draft is the draft model's first maximum over the tokens the walk's state allows, so
+        forced tokens are drafted as they are and no verify row is spent on a forbidden one; the verify step is that of
+        resident_decode_speculative_constrained. `sampling` is required (top_k = 1: greedy). The result is that of
+        resident_decode_speculative_model with a sampling set; n_produced is also short when a reached state allows no token.
+        Without a constraint it is resident_decode_speculative_model with `sampling`."""
+        if sampling is None:
+            raise ValueError("resident_decode_speculative_model_constrained: a sampling parameter set is required (top_k = 1 is the greedy form)")
+        return self.resident_decode_speculative_model(draft_session, first_token, start_pos, n_tokens, sampling, history, logprobs, top_logprobs,
+                                                      _entry="zgml_hip_resident_decode_speculative_model_constrained")
+
     def resident_decode_speculative_model(self, draft_session: "Session", first_token: int, start_pos: int, n_tokens: int, sampling=None, history=None,
-                                          logprobs: bool = False, top_logprobs: int = 0):
+                                          logprobs: bool = False, top_logprobs: int = 0, _entry: str = "zgml_hip_resident_decode_speculative_model"):
         """zgml_hip_resident_decode_speculative_model: this session's token_len = T >= 2 plan verifies what `draft_session`'s
         token_len = 1 plan (same backend, same vocabulary, its own resident_setup) drafts greedily, T - 1 tokens per step, all on
         the device. Both caches must hold the positions < start_pos; afterwards both hold those < start_pos + the produced count.
@@ -707,12 +720,12 @@ class Session:
         if logprobs or top_logprobs:
             sampling = capi.with_logprobs(sampling, top=top_logprobs)
         stats, produced = capi.SpecStatsC(), C.c_uint32(0)
-        rc = capi.load_hip().zgml_hip_resident_decode_speculative_model(
+        rc = getattr(capi.load_hip(), _entry)(
             self._backend.ctx, self.handle, draft_session.handle if draft_session is not None else None, first_token, start_pos, n_tokens,
             hist.ctypes.data_as(u32p) if hist.size else None, hist.size, C.byref(sampling) if sampling is not None else None, toks.ctypes.data,
             C.byref(produced), C.byref(stats))
         if rc != 0:
-            raise RuntimeError("resident_decode_speculative_model: " + self._backend.last_error())
+            raise RuntimeError(_entry[len("zgml_hip_"):] + ": " + self._backend.last_error())
         st = {"steps": stats.steps, "drafted": stats.drafted, "accepted": stats.accepted}
         if sampling is None:
             return toks[:n_tokens], st
