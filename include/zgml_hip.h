@@ -475,9 +475,32 @@ typedef struct zgml_kv_lane {
  * are this one call. Returns 0; -1 with an error on the context, before anything is enqueued, for: a dead or elided buffer, a
  * d_head mismatch, columns beyond either n_cols, a lane extent beyond its buffer, a block_size other than 0 / 32 (or d_head % 32
  * on an int8 lane, or an int8 lane with an offset), int8 -> f32, overlapping source and destination ranges of one buffer.
- * n == 0 or n_lanes == 0 does nothing and returns 0. */
+ * n == 0 or n_lanes == 0 does nothing and returns 0. (Moving columns down INSIDE a lane — a context shift — is zgml_hip_kv_shift
+ * below: this call refuses a lane pair that overlaps itself and does no arithmetic besides quantisation.) */
 int zgml_hip_kv_move(zgml_hip_ctx* ctx, zgml_hip_program* dst, const zgml_kv_lane* dst_lanes, zgml_hip_program* src,
                      const zgml_kv_lane* src_lanes, uint64_t n_lanes, uint32_t src_col, uint32_t dst_col, uint32_t n);
+/* Context shift. With n_filled columns of every lane in use, columns [keep + discard, n_filled) of every lane move down to
+ * [keep, n_filled - discard), in place, in ONE launch on the context stream (stream-ordered, non-blocking); the first `keep`
+ * columns (BOS / system prompt) stay, the next `discard` are dropped, and every other byte of every lane keeps its value, the stale
+ * tail [n_filled - discard, n_cols) included. rotate[i] = 1 marks lane i as a K lane: its caches hold keys already turned by RoPE,
+ * and every MOVED key is turned back by `discard` positions — pairs (i, i + d_head / 2) as the rope op's, with cos_row[i], sin_row[i]
+ * (host, d_head / 2 floats each: the first half of row `discard` of the model's own tables), every product and sum rounded to f32
+ * on its own (zgml_amd/csrc/kv_shift.h states the rule; device columns equal it to the bit). An int8 K column is dequantised, turned
+ * and requantised as a whole with the column rule of kvq.h — every shift therefore costs an int8 key up to one quantisation unit,
+ * shrinking it: shift rarely and by much —; V lanes are copied. Afterwards positions equal column indices again: decoding goes
+ * on at position n_filled - discard with the same plan, masks and loops; no forward pass. The shifted cache is NOT a re-prefilled
+ * one: kept values and keys still carry the attention of the dropped tokens (llama.cpp's context-shift semantics).
+ * All lanes of a call share one d_head. Returns 0; -1 with an error on the context that starts with "kv_shift:", before anything
+ * is enqueued, for: every lane check zgml_hip_kv_move makes (dead or elided buffer, block_size, d_head / n_cols 0, extent, int8
+ * d_head % 32 and offset), an odd d_head, differing d_head, an int8 K lane whose d_head is neither 32 nor a multiple of 64, d_head > 2048,
+ * keep + discard > n_filled, n_filled > n_cols, a NULL row or lane table, two lanes whose extents meet. discard == 0,
+ * n_lanes == 0 or keep + discard == n_filled does nothing and returns 0. Not for sharded (zgml_hip_shard_*) programs. */
+int zgml_hip_kv_shift(zgml_hip_ctx* ctx, zgml_hip_program* program, const zgml_kv_lane* lanes, const uint8_t* rotate /* [n_lanes]: 1 = a K lane */,
+                      uint64_t n_lanes, uint32_t keep, uint32_t discard, uint32_t n_filled,
+                      const float* cos_row /* host, d_head / 2 */, const float* sin_row /* host, d_head / 2 */);
+/* What one round of the shift's kernel carries (it walks a lane in ascending rounds: kv_shift.hip): values of a K lane, bytes of
+ * a V lane. For tests and tools that size a lane to the kernel's loop. */
+void zgml_hip_kv_shift_rounds(uint32_t* rotate_values, uint32_t* copy_bytes);
 /* The HIP stream (hipStream_t as void*) the context launches on. */
 void* zgml_hip_stream(zgml_hip_ctx* ctx);
 /* Execute without host I/O and without blocking: enqueue the program on the context stream. */

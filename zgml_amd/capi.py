@@ -324,6 +324,7 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_decode_batch_speculative_constrained",
     "zgml_hip_resident_decode_batch_speculative_model",
     "zgml_hip_resident_decode_speculative_model_constrained",
+    "zgml_hip_kv_shift", "zgml_hip_kv_shift_rounds",
 ]
 
 class KvLaneC(C.Structure):
@@ -518,6 +519,11 @@ def _bind_hip(lib: C.CDLL) -> None:
                                                                                C.POINTER(u32), C.POINTER(SpecStatsC)]
     lib.zgml_hip_kv_move.restype = i32
     lib.zgml_hip_kv_move.argtypes = [vp, vp, C.POINTER(KvLaneC), vp, C.POINTER(KvLaneC), u64, u32, u32, u32]
+    if hasattr(lib, "zgml_hip_kv_shift"):  # absent from an older build loaded through ZGML_HIP_LIB (A/B runs)
+        lib.zgml_hip_kv_shift.restype = i32
+        lib.zgml_hip_kv_shift.argtypes = [vp, vp, C.POINTER(KvLaneC), C.POINTER(C.c_uint8), u64, u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.zgml_hip_kv_shift_rounds.restype = None
+        lib.zgml_hip_kv_shift_rounds.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

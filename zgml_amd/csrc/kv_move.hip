@@ -25,12 +25,7 @@ struct KvMoveLane {
 };
 
 struct KvMovePool {
-    struct Block {
-        KvMoveLane *host = nullptr, *dev = nullptr;
-        uint64_t cap = 0;
-        hipEvent_t uploaded = nullptr; // recorded behind the block's last upload: the host side is free again once it has passed
-    };
-    std::vector<Block> blocks;
+    std::vector<zgml_rt::KvPoolBlock> blocks; // (uploaded: recorded behind the block's last upload: the host side is free again once it has passed)
 };
 
 namespace zgml_rt {
@@ -136,17 +131,19 @@ __global__ void __launch_bounds__(kKvmBlock) kv_move_kernel(const KvMoveLane* __
     }
 }
 
-// a free block of the pool with room for n records (its last upload has completed), or a new one
-KvMovePool::Block* kvm_block(zgml_hip_ctx* ctx, uint64_t n) {
+} // namespace
+
+// a free block of the pool with room for `bytes` (its last upload has completed), or a new one
+KvPoolBlock* kv_pool_block(zgml_hip_ctx* ctx, uint64_t bytes) {
     if (!ctx->kv_move_pool) ctx->kv_move_pool = new KvMovePool();
     auto& blocks = ctx->kv_move_pool->blocks;
     for (auto& b : blocks)
-        if (b.cap >= n && hipEventQuery(b.uploaded) == hipSuccess) return &b;
+        if (b.cap >= bytes && hipEventQuery(b.uploaded) == hipSuccess) return &b;
     (void)hipGetLastError(); // (hipErrorNotReady of a busy block is not an error of the call)
-    KvMovePool::Block b;
-    b.cap = std::max<uint64_t>(n, 256);
-    if (!CTX_CHECK(ctx, hipHostMalloc((void**)&b.host, b.cap * sizeof(KvMoveLane), hipHostMallocDefault)) ||
-        !CTX_CHECK(ctx, hipMalloc((void**)&b.dev, b.cap * sizeof(KvMoveLane))) || !CTX_CHECK(ctx, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming))) {
+    KvPoolBlock b;
+    b.cap = std::max<uint64_t>(bytes, 256 * sizeof(KvMoveLane));
+    if (!CTX_CHECK(ctx, hipHostMalloc((void**)&b.host, b.cap, hipHostMallocDefault)) || !CTX_CHECK(ctx, hipMalloc((void**)&b.dev, b.cap)) ||
+        !CTX_CHECK(ctx, hipEventCreateWithFlags(&b.uploaded, hipEventDisableTiming))) {
         (void)hipHostFree(b.host);
         (void)hipFree(b.dev);
         if (b.uploaded) (void)hipEventDestroy(b.uploaded);
@@ -156,7 +153,30 @@ KvMovePool::Block* kvm_block(zgml_hip_ctx* ctx, uint64_t n) {
     return &blocks.back();
 }
 
-} // namespace
+bool kv_pool_upload(zgml_hip_ctx* ctx, KvPoolBlock* blk, uint64_t bytes) {
+    return CTX_CHECK(ctx, hipMemcpyAsync(blk->dev, blk->host, bytes, hipMemcpyHostToDevice, ctx->stream)) && CTX_CHECK(ctx, hipEventRecord(blk->uploaded, ctx->stream));
+}
+
+bool kv_lane_base(zgml_hip_program* p, const zgml_kv_lane& l, uint64_t col_end, const char** why, char** data, float** scales) {
+    *data = nullptr, *scales = nullptr;
+    if (l.buf >= p->bufs.size() || !p->bufs[l.buf]) return *why = "no such live buffer (dead or elided)", false;
+    if (l.block_size != 0 && l.block_size != 32) return *why = "block_size must be 0 (f32 columns) or 32 (the quantised cache layout)", false;
+    if (!l.d_head || !l.n_cols) return *why = "d_head and n_cols must not be 0", false;
+    if (col_end > l.n_cols) return *why = "columns beyond the lane's n_cols", false;
+    const uint64_t vals = (uint64_t)l.n_cols * l.d_head;
+    if (l.block_size == 0) {
+        if (l.offset > p->sizes[l.buf] || vals > p->sizes[l.buf] - l.offset) return *why = "the lane's extent exceeds its buffer", false;
+        *data = (char*)(p->bufs[l.buf] + l.offset);
+        return true;
+    }
+    if (l.d_head % 32) return *why = "an int8 lane needs d_head % 32 == 0", false;
+    if (l.offset) return *why = "an int8 lane is a whole cache buffer: offset must be 0", false;
+    if (vals % 4 || vals / 4 + vals / 32 > p->sizes[l.buf]) return *why = "the lane's extent exceeds its buffer", false;
+    *data = (char*)p->bufs[l.buf];
+    *scales = p->bufs[l.buf] + vals / 4;
+    return true;
+}
+
 } // namespace zgml_rt
 
 extern "C" {
@@ -179,32 +199,12 @@ int zgml_hip_kv_move(zgml_hip_ctx* ctx, zgml_hip_program* dst, const zgml_kv_lan
     std::vector<Range> ranges;
     ranges.reserve(n_lanes * 4);
     uint64_t max_elems = 0;
-    // a lane's checks; -> the address of column 0's values and (int8) of column 0's scales
-    auto lane_base = [&](zgml_hip_program* p, const zgml_kv_lane& l, uint32_t col, const char** why, char** data, float** scales) {
-        *data = nullptr, *scales = nullptr;
-        if (l.buf >= p->bufs.size() || !p->bufs[l.buf]) return *why = "no such live buffer (dead or elided)", false;
-        if (l.block_size != 0 && l.block_size != 32) return *why = "block_size must be 0 (f32 columns) or 32 (the quantised cache layout)", false;
-        if (!l.d_head || !l.n_cols) return *why = "d_head and n_cols must not be 0", false;
-        if ((uint64_t)col + n > l.n_cols) return *why = "columns beyond the lane's n_cols", false;
-        const uint64_t vals = (uint64_t)l.n_cols * l.d_head;
-        if (l.block_size == 0) {
-            if (l.offset > p->sizes[l.buf] || vals > p->sizes[l.buf] - l.offset) return *why = "the lane's extent exceeds its buffer", false;
-            *data = (char*)(p->bufs[l.buf] + l.offset);
-            return true;
-        }
-        if (l.d_head % 32) return *why = "an int8 lane needs d_head % 32 == 0", false;
-        if (l.offset) return *why = "an int8 lane is a whole cache buffer: offset must be 0", false;
-        if (vals % 4 || vals / 4 + vals / 32 > p->sizes[l.buf]) return *why = "the lane's extent exceeds its buffer", false;
-        *data = (char*)p->bufs[l.buf];
-        *scales = p->bufs[l.buf] + vals / 4;
-        return true;
-    };
     for (uint64_t i = 0; i < n_lanes; i++) {
         const zgml_kv_lane &d = dst_lanes[i], &s = src_lanes[i];
         const char* why = nullptr;
         char *dp, *sp;
         float *dsc, *ssc;
-        if (!lane_base(dst, d, dst_col, &why, &dp, &dsc) || !lane_base(src, s, src_col, &why, &sp, &ssc)) return refuse(i, why);
+        if (!kv_lane_base(dst, d, (uint64_t)dst_col + n, &why, &dp, &dsc) || !kv_lane_base(src, s, (uint64_t)src_col + n, &why, &sp, &ssc)) return refuse(i, why);
         if (d.d_head != s.d_head) return refuse(i, "d_head of the source and the destination differ");
         if (s.block_size && !d.block_size) return refuse(i, "int8 -> f32 is not a move (a quantised column has no f32 original)");
         KvMoveLane& r = recs[i];
@@ -235,18 +235,16 @@ int zgml_hip_kv_move(zgml_hip_ctx* ctx, zgml_hip_program* dst, const zgml_kv_lan
     if (chunk < kKvmChunk || chunk > (1u << 29)) return refuse(0, "more values per lane than one launch carries"); // (a chunk's byte count stays a 32-bit number)
 
     (void)hipSetDevice(ctx->device);
-    KvMovePool::Block* blk = kvm_block(ctx, n_lanes);
+    KvPoolBlock* blk = kv_pool_block(ctx, n_lanes * sizeof(KvMoveLane));
     if (!blk) return -1;
     for (uint64_t i = 0; i < n_lanes; i++) unhoist_if_guarded(dst, dst_lanes[i].buf);
     memcpy(blk->host, recs.data(), n_lanes * sizeof(KvMoveLane));
-    if (!CTX_CHECK(ctx, hipMemcpyAsync(blk->dev, blk->host, n_lanes * sizeof(KvMoveLane), hipMemcpyHostToDevice, ctx->stream)) ||
-        !CTX_CHECK(ctx, hipEventRecord(blk->uploaded, ctx->stream)))
-        return -1;
+    if (!kv_pool_upload(ctx, blk, n_lanes * sizeof(KvMoveLane))) return -1;
     const dim3 grid((uint32_t)n_lanes, (uint32_t)((max_elems + chunk - 1) / chunk));
     if (ctx->opt_kv_move_nt)
-        kv_move_kernel<true><<<grid, kKvmBlock, 0, ctx->stream>>>(blk->dev, chunk);
+        kv_move_kernel<true><<<grid, kKvmBlock, 0, ctx->stream>>>((const KvMoveLane*)blk->dev, chunk);
     else
-        kv_move_kernel<false><<<grid, kKvmBlock, 0, ctx->stream>>>(blk->dev, chunk);
+        kv_move_kernel<false><<<grid, kKvmBlock, 0, ctx->stream>>>((const KvMoveLane*)blk->dev, chunk);
     return CTX_CHECK(ctx, hipGetLastError()) ? 0 : -1;
 }
 

@@ -168,8 +168,8 @@ struct zgml_hip_ctx {
     std::vector<int64_t> top_tok_last;
     std::vector<float> top_val_last;
     uint32_t top_width_last = 0;
-    // zgml_hip_kv_move (kv_move.hip): the lane-record blocks of its launches (pinned host + device, recycled once their launch's
-    // upload has completed) and ZGML_HIP_OPT_KV_MOVE_NT
+    // zgml_hip_kv_move / zgml_hip_kv_shift (kv_move.hip, kv_shift.hip): the record blocks of their launches (pinned host + device,
+    // recycled once their launch's upload has completed) and ZGML_HIP_OPT_KV_MOVE_NT
     struct KvMovePool* kv_move_pool = nullptr;
     bool opt_kv_move_nt = false;
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
@@ -365,6 +365,18 @@ void enqueue(zgml_hip_program* p);          // the whole program on the context 
 void unhoist_if_guarded(zgml_hip_program* p, uint16_t buf_idx); // a buffer written from outside the op list leaves the hoisted set
 // kv_move.hip
 void free_kv_move_pool(zgml_hip_ctx* ctx); // (zgml_hip_destroy, after the stream has drained)
+// One upload of a lane call's records: a pinned host block and its device twin of at least `bytes` bytes (16-byte aligned), free
+// again once `uploaded` has passed. kv_upload copies bytes host -> dev on the context stream and records the event.
+struct KvPoolBlock {
+    char *host = nullptr, *dev = nullptr;
+    uint64_t cap = 0; // bytes
+    hipEvent_t uploaded = nullptr;
+};
+KvPoolBlock* kv_pool_block(zgml_hip_ctx* ctx, uint64_t bytes); // nullptr: reported on the context
+bool kv_pool_upload(zgml_hip_ctx* ctx, KvPoolBlock* blk, uint64_t bytes);
+// The checks of one zgml_kv_lane of program p whose columns [0, col_end) a call touches; -> the address of column 0's values and
+// (int8) of column 0's scales. false: *why says what is wrong with the lane.
+bool kv_lane_base(zgml_hip_program* p, const zgml_kv_lane& l, uint64_t col_end, const char** why, char** data, float** scales);
 // runtime_resident.hip
 void free_resident_graph(zgml_hip_program* p); // the resident loops' captured graphs (they bake the plan: free_graph calls this)
 void free_resident(zgml_hip_program* p);       // p->resident and everything it owns

@@ -244,6 +244,31 @@ class BatchModel(Model):
         return self.cfg.d_head * self.cfg.max_seq_len * self.cfg.n_kv_heads
 
 
+def _kv_shift(session, lanes, keep: int, discard: int, n_filled: int) -> int:
+    """zgml_hip_kv_shift over `lanes` of the session's program -> the new position. The lane order is (layer, kv head, K | V)
+    with K | V innermost (DecodeProgram::kv_lanes), so every even lane is a K lane: those are the ones whose moved columns are
+    turned back. The rows are the first half of row `discard` of the model's own RoPE tables."""
+    cfg = session.model.cfg
+    is_hip = capi.HIP_LIB_PATH.exists() and session.fns.compile_program == _fn_addr(capi.load_hip(), "zgml_hip_compile_program")
+    if not is_hip:
+        raise RuntimeError("kv_shift: a HIP session is needed")
+    keep, discard, n_filled = int(keep), int(discard), int(n_filled)
+    if keep < 0 or discard < 0 or keep + discard > n_filled or n_filled > cfg.max_seq_len:
+        raise ValueError(f"kv_shift: keep {keep} + discard {discard} <= n_filled {n_filled} <= max_seq_len {cfg.max_seq_len} must hold")
+    if discard == 0 or keep + discard == n_filled:
+        return n_filled - discard  # (nothing moves)
+    hd = cfg.d_head // 2
+    cos, sin = session.model.rope_tables()
+    c, s = np.ascontiguousarray(cos[discard, :hd], np.float32), np.ascontiguousarray(sin[discard, :hd], np.float32)
+    rotate = (C.c_uint8 * len(lanes))(*[1 - i % 2 for i in range(len(lanes))])
+    f32p = C.POINTER(C.c_float)
+    hip = capi.load_hip()
+    if hip.zgml_hip_kv_shift(session.fns.ctx, session.handle, lanes, rotate, len(lanes), keep, discard, n_filled, c.ctypes.data_as(f32p),
+                             s.ctypes.data_as(f32p)) != 0:
+        raise RuntimeError((hip.zgml_hip_last_error(session.fns.ctx) or b"").decode())
+    return n_filled - discard
+
+
 class BatchSession:
     """Batched decode: `step` advances `n_seqs` sequences by one token each through the vtable (refresh + execute). `model` is a
     BatchModel of `n_seqs` sequences, or any other Model: the session then builds the batched program over that model's weights
@@ -317,6 +342,14 @@ class BatchSession:
         if src_seq == dst_seq:
             raise ValueError("fork: source and destination are the same sequence")
         self._kv_move(self.model.kv_lanes(dst_seq), self.handle, self.model.kv_lanes(src_seq), 0, 0, n_cols)
+
+    def shift(self, seq: int, keep: int, discard: int, n_filled: int) -> int:
+        """Context shift of sequence `seq` alone (Session.shift; include/zgml_hip.h zgml_hip_kv_shift): of its n_filled columns the
+        first `keep` stay, the next `discard` are dropped, the rest move down with their keys turned back -> the sequence's new
+        position n_filled - discard. The other sequences' caches are not touched. The caller drops the same tokens from whatever
+        it keeps per sequence (`history` of the speculative loops, the penalties' window) and shifts a batched draft session's
+        sequence too; an attached constraint needs nothing."""
+        return _kv_shift(self, self.model.kv_lanes(seq), keep, discard, n_filled)
 
     # ── device-resident loop (HIP backend only; include/zgml_hip.h zgml_hip_resident_decode_batch) ──
     def resident_setup(self, backend) -> None:
@@ -559,6 +592,19 @@ class Session:
         toks = np.zeros(n_steps, np.int64)
         secs = self.lib.zh_session_decode(self.ptr, first_token, start_pos, n_steps, toks.ctypes.data)
         return toks, secs
+
+    def shift(self, keep: int, discard: int, n_filled: int) -> int:
+        """Context shift (HIP sessions only, like BatchSession.admit / fork; include/zgml_hip.h zgml_hip_kv_shift): with n_filled
+        KV columns in use, keep the first `keep` (BOS / system prompt), drop the next `discard`, move the rest down and turn every
+        moved key back by `discard` positions of RoPE — one stream-ordered launch, no forward pass -> the new position
+        n_filled - discard, where step / resident_decode* go on (generation past max_seq_len). What the caller owns: drop tokens
+        [keep, keep + discard) from the `history` it hands the speculative loops (and from a penalty window it tracks), and shift
+        a draft model's session with the same arguments (a draft pair is shifted by shifting both sessions). Constraint state
+        needs nothing: it depends on tokens, not positions. int8 caches are requantised on every shift (truncation shrinks the
+        keys a little each time): shift rarely and by much — at half the window a column is requantised at most twice. The
+        shifted cache is not a re-prefilled one: kept columns still carry the attention of the dropped tokens (llama.cpp's
+        semantics)."""
+        return _kv_shift(self, self.model.kv_lanes(), keep, discard, n_filled)
 
     # ── device-resident loop (HIP backend only; include/zgml_hip.h zgml_hip_resident_*) ──
     def resident_setup(self, backend) -> None:
