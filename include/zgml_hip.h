@@ -501,6 +501,35 @@ int zgml_hip_kv_shift(zgml_hip_ctx* ctx, zgml_hip_program* program, const zgml_k
 /* What one round of the shift's kernel carries (it walks a lane in ascending rounds: kv_shift.hip): values of a K lane, bytes of
  * a V lane. For tests and tools that size a lane to the kernel's loop. */
 void zgml_hip_kv_shift_rounds(uint32_t* rotate_values, uint32_t* copy_bytes);
+/* Park and resume. zgml_hip_kv_park writes columns [col, col + n) of every lane into the caller's HOST blob: one pack launch into
+ * a device staging block the context owns (grown on demand), then one device-to-host copy; it blocks until the blob is complete.
+ * zgml_hip_kv_resume writes a blob's n columns into columns [col, col + n) of every lane — any col, not only the park's —: one
+ * host-to-device copy into staging, then one unpack launch on the context stream; it returns once the blob has been consumed (the
+ * caller may free it) and the launch is stream-ordered like zgml_hip_kv_move. The blob outlives its program: a prompt prefilled
+ * once can be handed to any slot of any plan of the same model later (prompt cache), a running sequence can leave its slot and
+ * come back (preemption), and an application can keep the bytes (persistence). Token history, penalty window, constraint state
+ * and position are the caller's to keep beside it.
+ * The blob is self-describing (zgml_amd/csrc/kv_park.h states the layout): a 32-byte header — magic, version, n_lanes, n, flags,
+ * total bytes —, a directory of one 16-byte record per lane — d_head, the run's form (f32 | int8), the data offset —, and per lane
+ * a data run and, for int8, a scale run of n * d_head / 32 floats, every run on a 16-byte boundary of the blob. The host writes
+ * header and directory, the device the payload. zgml_hip_kv_park_bytes is the size of that blob for a lane table; 0 for a table
+ * a park would refuse by the records alone.
+ * flags bit 0 (ZGML_KV_PARK_INT8): f32 lanes are stored quantised with the column rule of kvq.h (0.28x the bytes at d_head 128);
+ * refused for an f32 lane whose d_head % 32 != 0, no effect on int8 lanes. Per lane a resume copies (f32 run -> f32 lane; int8 run
+ * -> int8 lane: bytes and scales) or quantises (f32 run -> int8 lane: exactly the bytes zgml_hip_kv_move writes for f32 -> int8);
+ * an int8 run into an f32 lane is refused.
+ * Both return 0; -1 with an error on the context that starts with "kv_park:" / "kv_resume:", before anything is enqueued, for:
+ * every lane check zgml_hip_kv_move makes, columns beyond n_cols, cap below the size, the flag on a lane that cannot take it, a
+ * NULL blob or lane table; on resume also a bad magic or version, bytes different from the header's total (or a directory that is
+ * not the layout's), n_lanes or a lane's d_head different from the destination's, int8 -> f32, two destination lanes whose
+ * written ranges meet. n == 0 or n_lanes == 0 does nothing and returns 0 (a park writes a valid empty blob: the bare header).
+ * Not for sharded (zgml_hip_shard_*) programs. */
+#define ZGML_KV_PARK_INT8 1u
+uint64_t zgml_hip_kv_park_bytes(const zgml_kv_lane* lanes, uint64_t n_lanes, uint32_t n, uint32_t flags);
+int zgml_hip_kv_park(zgml_hip_ctx* ctx, zgml_hip_program* program, const zgml_kv_lane* lanes, uint64_t n_lanes, uint32_t col, uint32_t n,
+                     uint32_t flags, void* blob, uint64_t cap);
+int zgml_hip_kv_resume(zgml_hip_ctx* ctx, zgml_hip_program* program, const zgml_kv_lane* lanes, uint64_t n_lanes, uint32_t col, const void* blob,
+                       uint64_t bytes);
 /* The HIP stream (hipStream_t as void*) the context launches on. */
 void* zgml_hip_stream(zgml_hip_ctx* ctx);
 /* Execute without host I/O and without blocking: enqueue the program on the context stream. */

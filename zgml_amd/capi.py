@@ -325,7 +325,10 @@ HIP_SYMBOLS = [
     "zgml_hip_resident_decode_batch_speculative_model",
     "zgml_hip_resident_decode_speculative_model_constrained",
     "zgml_hip_kv_shift", "zgml_hip_kv_shift_rounds",
+    "zgml_hip_kv_park_bytes", "zgml_hip_kv_park", "zgml_hip_kv_resume",
 ]
+
+KV_PARK_INT8 = 1  # ZGML_KV_PARK_INT8: zgml_hip_kv_park stores f32 lanes quantised (the column rule of kvq.h)
 
 class KvLaneC(C.Structure):
     """zgml_kv_lane (include/zgml_hip.h): the columns of one kv head's K or V cache inside a program buffer."""
@@ -524,6 +527,13 @@ def _bind_hip(lib: C.CDLL) -> None:
         lib.zgml_hip_kv_shift.argtypes = [vp, vp, C.POINTER(KvLaneC), C.POINTER(C.c_uint8), u64, u32, u32, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.zgml_hip_kv_shift_rounds.restype = None
         lib.zgml_hip_kv_shift_rounds.argtypes = [C.POINTER(u32), C.POINTER(u32)]
+    if hasattr(lib, "zgml_hip_kv_park"):  # (as above)
+        lib.zgml_hip_kv_park_bytes.restype = u64
+        lib.zgml_hip_kv_park_bytes.argtypes = [C.POINTER(KvLaneC), u64, u32, u32]
+        lib.zgml_hip_kv_park.restype = i32
+        lib.zgml_hip_kv_park.argtypes = [vp, vp, C.POINTER(KvLaneC), u64, u32, u32, u32, vp, u64]
+        lib.zgml_hip_kv_resume.restype = i32
+        lib.zgml_hip_kv_resume.argtypes = [vp, vp, C.POINTER(KvLaneC), u64, u32, vp, u64]
     lib.zgml_hip_copy_bench.restype = C.c_double
     lib.zgml_hip_copy_bench.argtypes = [vp, u64, u32, u32]
 

@@ -3,26 +3,11 @@
 // lane pair the columns are copied (f32 -> f32; int8 -> int8: bytes and scales) or quantised (f32 -> int8) exactly as kvq_store
 // does (kvq.h states the rule).
 //
-// Shape: in every form the moved columns of a lane are ONE contiguous run of n * d_head values on either side (columns lie back to
-// back in both layouts), and the scales of an int8 lane a second run of n * d_head / 32 floats. The grid is (lane, chunk): a
-// workgroup takes `chunk` values of its lane's run — 16-byte loads and stores where both addresses allow, dwords otherwise. In the
-// quantising form a lane of a wave takes 4 dims, so 8 adjacent lanes hold a block of 32 and a wave 8 blocks; the block maximum
-// is a shuffle-xor reduction within those 8 lanes (a maximum has no rounding: any order gives kvq_store_kernel's wave_max). No
-// workgroup reads what another writes: there is no cross-workgroup ordering, hand-off or loop over work items, and the host
-// refuses a call whose destination ranges meet another destination or any source range.
+// The copy and the quantising body of a workgroup's chunk, the record of a lane pair and the chunk size are kv_copy.h's (shared
+// with kv_park.hip); this file adds the lane checks, the range check and the pool of record blocks that the lane calls share.
 #include "runtime_internal.h"
 
-#include "kvq.h"
-
-enum KvMoveMode : uint32_t { KVM_F32 = 0, KVM_I8 = 1, KVM_QUANT = 2 };
-struct KvMoveLane {
-    const void* src;         // first moved value of the source (f32: floats; int8: bytes)
-    void* dst;               // ... of the destination
-    const float* src_scales; // int8 source: scale of the first moved block
-    float* dst_scales;       // int8 destination
-    uint64_t elems;          // n * d_head values
-    uint32_t mode, _pad;
-};
+#include "kv_copy.h"
 
 struct KvMovePool {
     std::vector<zgml_rt::KvPoolBlock> blocks; // (uploaded: recorded behind the block's last upload: the host side is free again once it has passed)
@@ -43,92 +28,9 @@ void free_kv_move_pool(zgml_hip_ctx* ctx) {
 
 namespace {
 
-constexpr int kKvmBlock = 256;
-constexpr uint32_t kKvmChunk = 8192; // values per workgroup: 32 KB of f32 — 8 16-byte loads per lane; a multiple of 4 * kKvmBlock
-
-typedef uint32_t kvm_u4 __attribute__((ext_vector_type(4)));
-typedef float kvm_f4 __attribute__((ext_vector_type(4)));
-
-// `bytes` (a multiple of 4) from s to d, the workgroup's threads side by side
-template <bool NT>
-__device__ __forceinline__ void kvm_copy(char* d, const char* s, uint32_t bytes) {
-    const uint32_t tid = threadIdx.x;
-    if ((((uintptr_t)d | (uintptr_t)s) & 15) == 0) {
-        const uint32_t n16 = bytes / 16;
-        const kvm_u4* s4 = (const kvm_u4*)s;
-        kvm_u4* d4 = (kvm_u4*)d;
-        constexpr int U = 8; // (a 32 KB chunk is one round: every load of the chunk in flight before the first store)
-        uint32_t i = tid;
-        for (; i + (U - 1) * kKvmBlock < n16; i += U * kKvmBlock) {
-            kvm_u4 v[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) v[u] = NT ? __builtin_nontemporal_load(s4 + i + u * kKvmBlock) : s4[i + u * kKvmBlock];
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                if (NT)
-                    __builtin_nontemporal_store(v[u], d4 + i + u * kKvmBlock);
-                else
-                    d4[i + u * kKvmBlock] = v[u];
-            }
-        }
-        for (; i < n16; i += kKvmBlock) d4[i] = s4[i];
-        const uint32_t done = n16 * 16;
-        for (uint32_t b = done + 4 * tid; b < bytes; b += 4 * kKvmBlock) *(uint32_t*)(d + b) = *(const uint32_t*)(s + b);
-        return;
-    }
-    for (uint32_t b = 4 * tid; b < bytes; b += 4 * kKvmBlock) *(uint32_t*)(d + b) = *(const uint32_t*)(s + b);
-}
-
 template <bool NT>
 __global__ void __launch_bounds__(kKvmBlock) kv_move_kernel(const KvMoveLane* __restrict__ lanes, uint32_t chunk) {
-    const KvMoveLane& L = lanes[blockIdx.x];
-    const uint64_t lo = (uint64_t)blockIdx.y * chunk;
-    if (lo >= L.elems) return;
-    const uint32_t cnt = (uint32_t)(L.elems - lo < chunk ? L.elems - lo : chunk);
-    if (L.mode == KVM_F32) {
-        kvm_copy<NT>((char*)L.dst + lo * 4, (const char*)L.src + lo * 4, cnt * 4);
-        return;
-    }
-    if (L.mode == KVM_I8) { // (d_head % 32 == 0: lo and cnt are whole blocks)
-        kvm_copy<NT>((char*)L.dst + lo, (const char*)L.src + lo, cnt);
-        kvm_copy<NT>((char*)(L.dst_scales + lo / 32), (const char*)(L.src_scales + lo / 32), cnt / 32 * 4);
-        return;
-    }
-    // f32 -> int8: 4 dims per lane, a block of 32 dims on 8 adjacent lanes; cnt is a multiple of 32, so a group of 8 lanes is live or
-    // idle as a whole and the loop's trip count is the same for every lane of the workgroup
-    const float* src = (const float*)L.src + lo;
-    uint32_t* dst = (uint32_t*)((int8_t*)L.dst + lo);
-    float* sc = L.dst_scales + lo / 32;
-    const bool vec = ((uintptr_t)src & 15) == 0;
-    constexpr int QU = 8; // 16-byte loads in flight per lane: a 32 KB chunk is one round (a lone load per round left the kernel latency-bound)
-    for (uint32_t base = 0; base < cnt; base += QU * 4 * kKvmBlock) {
-        kvm_f4 v[QU];
-#pragma unroll
-        for (int u = 0; u < QU; u++) {
-            const uint32_t e = base + (u * kKvmBlock + threadIdx.x) * 4;
-            v[u] = kvm_f4{0.f, 0.f, 0.f, 0.f};
-            if (e < cnt) {
-                if (vec)
-                    v[u] = NT ? __builtin_nontemporal_load((const kvm_f4*)(src + e)) : *(const kvm_f4*)(src + e);
-                else
-                    v[u] = kvm_f4{src[e], src[e + 1], src[e + 2], src[e + 3]};
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < QU; u++) {
-            const uint32_t e = base + (u * kKvmBlock + threadIdx.x) * 4;
-            float mx = fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w)));
-#pragma unroll
-            for (int off = 4; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-            const KvqScale s = kvq_block_scale(mx);
-            const uint32_t w = (uint32_t)(uint8_t)kvq_quantise(v[u].x, s.inv) | (uint32_t)(uint8_t)kvq_quantise(v[u].y, s.inv) << 8 |
-                               (uint32_t)(uint8_t)kvq_quantise(v[u].z, s.inv) << 16 | (uint32_t)(uint8_t)kvq_quantise(v[u].w, s.inv) << 24;
-            if (e < cnt) {
-                dst[e / 4] = w;
-                if ((threadIdx.x & 7) == 0) sc[e / 32] = s.scale;
-            }
-        }
-    }
+    kvm_lane_chunk<NT>(lanes, chunk);
 }
 
 } // namespace
@@ -155,6 +57,17 @@ KvPoolBlock* kv_pool_block(zgml_hip_ctx* ctx, uint64_t bytes) {
 
 bool kv_pool_upload(zgml_hip_ctx* ctx, KvPoolBlock* blk, uint64_t bytes) {
     return CTX_CHECK(ctx, hipMemcpyAsync(blk->dev, blk->host, bytes, hipMemcpyHostToDevice, ctx->stream)) && CTX_CHECK(ctx, hipEventRecord(blk->uploaded, ctx->stream));
+}
+
+// no written range may meet another written range or a read range (a lane pair that overlaps itself, or two pairs that meet)
+bool kv_ranges_clash(std::vector<KvRange>& ranges) {
+    std::sort(ranges.begin(), ranges.end(), [](const KvRange& a, const KvRange& b) { return a.lo < b.lo; });
+    uintptr_t hi_written = 0, hi_read = 0;
+    for (const KvRange& r : ranges) {
+        if (r.lo < hi_written || (r.written && r.lo < hi_read)) return true;
+        (r.written ? hi_written : hi_read) = std::max(r.written ? hi_written : hi_read, r.hi);
+    }
+    return false;
 }
 
 bool kv_lane_base(zgml_hip_program* p, const zgml_kv_lane& l, uint64_t col_end, const char** why, char** data, float** scales) {
@@ -191,12 +104,8 @@ int zgml_hip_kv_move(zgml_hip_ctx* ctx, zgml_hip_program* dst, const zgml_kv_lan
     };
     if (!dst_lanes || !src_lanes) return refuse(0, "no lane records");
     if (n_lanes > 0x7FFFFFFFull) return refuse(0, "more lanes than one launch carries");
-    struct Range {
-        uintptr_t lo, hi;
-        bool written;
-    };
     std::vector<KvMoveLane> recs(n_lanes);
-    std::vector<Range> ranges;
+    std::vector<KvRange> ranges;
     ranges.reserve(n_lanes * 4);
     uint64_t max_elems = 0;
     for (uint64_t i = 0; i < n_lanes; i++) {
@@ -220,19 +129,12 @@ int zgml_hip_kv_move(zgml_hip_ctx* ctx, zgml_hip_program* dst, const zgml_kv_lan
         if (r.dst_scales) ranges.push_back({(uintptr_t)r.dst_scales, (uintptr_t)(r.dst_scales + (uint64_t)n * bpc), true});
         max_elems = std::max(max_elems, elems);
     }
-    // no written range may meet another written range or a read range (a lane pair that overlaps itself, or two pairs that meet)
-    std::sort(ranges.begin(), ranges.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
-    uintptr_t hi_written = 0, hi_read = 0;
-    for (const Range& r : ranges) {
-        if (r.lo < hi_written || (r.written && r.lo < hi_read)) {
-            ctx->fail("kv_move: overlapping source and destination ranges of one buffer (a lane pair may not overlap itself, and no pair may write what another reads or writes)");
-            return -1;
-        }
-        (r.written ? hi_written : hi_read) = std::max(r.written ? hi_written : hi_read, r.hi);
+    if (kv_ranges_clash(ranges)) {
+        ctx->fail("kv_move: overlapping source and destination ranges of one buffer (a lane pair may not overlap itself, and no pair may write what another reads or writes)");
+        return -1;
     }
-    uint32_t chunk = kKvmChunk;
-    while ((max_elems + chunk - 1) / chunk > 65535) chunk *= 2;
-    if (chunk < kKvmChunk || chunk > (1u << 29)) return refuse(0, "more values per lane than one launch carries"); // (a chunk's byte count stays a 32-bit number)
+    const uint32_t chunk = kvm_chunk_for(max_elems);
+    if (!chunk) return refuse(0, "more values per lane than one launch carries");
 
     (void)hipSetDevice(ctx->device);
     KvPoolBlock* blk = kv_pool_block(ctx, n_lanes * sizeof(KvMoveLane));

@@ -609,6 +609,7 @@ void zgml_hip_destroy(zgml_hip_ctx* ctx) {
     hipStreamSynchronize(ctx->stream);
     ctx->drop_b_cache();
     free_kv_move_pool(ctx);
+    free_kv_park_stage(ctx);
     hipFree(ctx->mm_a);
     hipFree(ctx->mm_b);
     hipFree(ctx->mm_c);

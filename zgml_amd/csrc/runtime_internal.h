@@ -168,10 +168,12 @@ struct zgml_hip_ctx {
     std::vector<int64_t> top_tok_last;
     std::vector<float> top_val_last;
     uint32_t top_width_last = 0;
-    // zgml_hip_kv_move / zgml_hip_kv_shift (kv_move.hip, kv_shift.hip): the record blocks of their launches (pinned host + device,
+    // zgml_hip_kv_move / zgml_hip_kv_shift / zgml_hip_kv_park / zgml_hip_kv_resume: the record blocks of their launches (pinned host + device,
     // recycled once their launch's upload has completed) and ZGML_HIP_OPT_KV_MOVE_NT
     struct KvMovePool* kv_move_pool = nullptr;
     bool opt_kv_move_nt = false;
+    // zgml_hip_kv_park / zgml_hip_kv_resume (kv_park.hip): the device staging block of a blob's payload, grown on demand
+    struct KvParkStage* kv_park_stage = nullptr;
     struct ShardState* shard = nullptr; // RCCL communicator of the row-shard path (zgml_hip_shard_*), else nullptr
     // Fused launches (q/k/v projection + decode attention): ONE host-visible word every bounded in-launch wait sets when it
     // gives up (pinned, device-mapped: the host reads it after any synchronisation without a copy). A set word means the
@@ -377,6 +379,14 @@ bool kv_pool_upload(zgml_hip_ctx* ctx, KvPoolBlock* blk, uint64_t bytes);
 // The checks of one zgml_kv_lane of program p whose columns [0, col_end) a call touches; -> the address of column 0's values and
 // (int8) of column 0's scales. false: *why says what is wrong with the lane.
 bool kv_lane_base(zgml_hip_program* p, const zgml_kv_lane& l, uint64_t col_end, const char** why, char** data, float** scales);
+// The byte ranges a lane call reads and writes. true: a written range meets another written range or a read range (sorts `ranges`).
+struct KvRange {
+    uintptr_t lo, hi;
+    bool written;
+};
+bool kv_ranges_clash(std::vector<KvRange>& ranges);
+// kv_park.hip
+void free_kv_park_stage(zgml_hip_ctx* ctx); // (zgml_hip_destroy, after the stream has drained)
 // runtime_resident.hip
 void free_resident_graph(zgml_hip_program* p); // the resident loops' captured graphs (they bake the plan: free_graph calls this)
 void free_resident(zgml_hip_program* p);       // p->resident and everything it owns

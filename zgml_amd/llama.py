@@ -269,6 +269,36 @@ def _kv_shift(session, lanes, keep: int, discard: int, n_filled: int) -> int:
     return n_filled - discard
 
 
+def _is_hip(session) -> bool:
+    return capi.HIP_LIB_PATH.exists() and session.fns.compile_program == _fn_addr(capi.load_hip(), "zgml_hip_compile_program")
+
+
+def _kv_park(session, lanes, n_cols: int, col: int, int8: bool) -> np.ndarray:
+    """zgml_hip_kv_park over `lanes` of the session's program -> the blob (uint8; zgml_amd/csrc/kv_park.h states its layout)"""
+    if not _is_hip(session):
+        raise RuntimeError("kv_park: a HIP session is needed")
+    n_cols, col, flags = int(n_cols), int(col), capi.KV_PARK_INT8 if int8 else 0
+    if n_cols < 0 or col < 0:
+        raise ValueError(f"kv_park: n_cols {n_cols} and col {col} must not be negative")
+    hip = capi.load_hip()
+    size = hip.zgml_hip_kv_park_bytes(lanes, len(lanes), n_cols, flags)
+    blob = np.zeros(size, np.uint8)  # (size 0: a lane table the call refuses — it says why)
+    if hip.zgml_hip_kv_park(session.fns.ctx, session.handle, lanes, len(lanes), col, n_cols, flags, blob.ctypes.data, size) != 0:
+        raise RuntimeError((hip.zgml_hip_last_error(session.fns.ctx) or b"").decode())
+    return blob
+
+
+def _kv_resume(session, lanes, blob, col: int) -> None:
+    if not _is_hip(session):
+        raise RuntimeError("kv_resume: a HIP session is needed")
+    if int(col) < 0:
+        raise ValueError(f"kv_resume: col {col} must not be negative")
+    blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8)
+    hip = capi.load_hip()
+    if hip.zgml_hip_kv_resume(session.fns.ctx, session.handle, lanes, len(lanes), int(col), blob.ctypes.data, blob.size) != 0:
+        raise RuntimeError((hip.zgml_hip_last_error(session.fns.ctx) or b"").decode())
+
+
 class BatchSession:
     """Batched decode: `step` advances `n_seqs` sequences by one token each through the vtable (refresh + execute). `model` is a
     BatchModel of `n_seqs` sequences, or any other Model: the session then builds the batched program over that model's weights
@@ -350,6 +380,20 @@ class BatchSession:
         it keeps per sequence (`history` of the speculative loops, the penalties' window) and shifts a batched draft session's
         sequence too; an attached constraint needs nothing."""
         return _kv_shift(self, self.model.kv_lanes(seq), keep, discard, n_filled)
+
+    def park(self, seq: int, n_cols: int, col: int = 0, int8: bool = False) -> np.ndarray:
+        """KV columns [col, col + n_cols) of sequence `seq` -> a host blob (Session.park: the same call over this slot's lanes).
+        The slot is free for another sequence afterwards (preemption); the other sequences' caches are not touched. What the
+        caller keeps beside the blob, per sequence: its token history, the penalties' window, the constraint's state
+        (constraint_state) and its position."""
+        return _kv_park(self, self.model.kv_lanes(seq), n_cols, col, int8)
+
+    def resume(self, seq: int, blob, col: int = 0) -> None:
+        """The blob's columns -> columns [col, col + n) of sequence `seq` (Session.resume): any slot of any batched plan of the
+        blob's model, f32 or int8, on any context — a prompt parked once can be resumed into many slots. Stream-ordered: the next
+        step or resident loop sees the columns. The caller puts back what it kept beside the blob (history, penalty window,
+        set_constraint with the saved state) and decodes on at the saved position."""
+        _kv_resume(self, self.model.kv_lanes(seq), blob, col)
 
     # ── device-resident loop (HIP backend only; include/zgml_hip.h zgml_hip_resident_decode_batch) ──
     def resident_setup(self, backend) -> None:
@@ -605,6 +649,23 @@ class Session:
         shifted cache is not a re-prefilled one: kept columns still carry the attention of the dropped tokens (llama.cpp's
         semantics)."""
         return _kv_shift(self, self.model.kv_lanes(), keep, discard, n_filled)
+
+    def park(self, n_cols: int, col: int = 0, int8: bool = False) -> np.ndarray:
+        """KV columns [col, col + n_cols) of every cache -> a host blob (uint8 array; HIP sessions only; include/zgml_hip.h
+        zgml_hip_kv_park): one pack launch and one device-to-host copy, complete on return. The blob outlives the session, the
+        model's plan and the backend: keep it as a prompt cache, to make room for a more urgent request, or across a restart
+        (it is self-describing: zgml_amd/csrc/kv_park.h; writing it to a file is the caller's). int8=True stores f32 caches
+        quantised with the cache's own column rule (0.28x the bytes at d_head 128); such a blob resumes into int8 plans only.
+        What the caller still owns per sequence, because none of it lives in the caches: the token history, the penalties'
+        window, the constraint's state and the position to decode on at."""
+        return _kv_park(self, self.model.kv_lanes(), n_cols, col, int8)
+
+    def resume(self, blob, col: int = 0) -> None:
+        """The blob's columns -> columns [col, col + n) of every cache (zgml_hip_kv_resume): one host-to-device copy and one
+        stream-ordered unpack launch; the blob may be dropped on return. f32 columns are quantised on the way into an int8 plan
+        exactly as admission does; an int8 blob into an f32 plan is refused. `col` need not be the park's. History, penalty
+        window, constraint state and position are put back by the caller."""
+        _kv_resume(self, self.model.kv_lanes(), blob, col)
 
     # ── device-resident loop (HIP backend only; include/zgml_hip.h zgml_hip_resident_*) ──
     def resident_setup(self, backend) -> None:
