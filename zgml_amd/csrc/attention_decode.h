@@ -5,6 +5,7 @@
 #pragma once
 #include "kernels.h"
 #include "handoff_gen.h"
+#include "sweep_ring.h"
 #include <hip/hip_fp16.h>
 #include <math.h>
 
@@ -28,6 +29,25 @@ __device__ __forceinline__ void stgu(uint32_t* p, uint32_t v) { *(__attribute__(
 
 constexpr int kAttnBlock = 1024;
 constexpr int kAttnUnroll = 4;
+// The granule hand-off's wait (fused launch, DecodeHandoff): sweeps the sweeping wave keeps in flight (sweep_ring.h; a slot is 6
+// registers at d_head 64 and 12 at d_head 128) and, for depths above 1, the s_sleep units (64 clocks each) one round trip is taken
+// for (the first issues are kSweepRtt / depth apart). ONE is kept: what pays is that a sweep's loads are issued TOGETHER and
+// checked behind one round trip (the loop this replaces staged each granule in LDS behind its own load: three dependent round
+// trips per sweep). Two and four in flight measured slower than one (profiles/r30_sweep_ring.txt: as hipcc builds the ring its
+// header waits for every outstanding load, and the sweeps still in flight when one matches must land before this wave may
+// re-use their registers). d_head 128 keeps two for a static reason alone: with one, three of its four instantiations spill two
+// SGPRs, with two none does; nothing here times those kernels. Overridable for A / B builds (tools/build_variant.py).
+#ifndef ZGML_SWEEP_DEPTH_64
+#define ZGML_SWEEP_DEPTH_64 1
+#endif
+#ifndef ZGML_SWEEP_DEPTH_128
+#define ZGML_SWEEP_DEPTH_128 2
+#endif
+#ifndef ZGML_SWEEP_RTT_UNITS
+#define ZGML_SWEEP_RTT_UNITS 28
+#endif
+constexpr int kSweepDepth64 = ZGML_SWEEP_DEPTH_64, kSweepDepth128 = ZGML_SWEEP_DEPTH_128;
+constexpr int kSweepRtt = ZGML_SWEEP_RTT_UNITS;
 
 // rope of 4 consecutive dims [d0, d0+4) of a head vector (reference.zig:457-478, DeviceOp
 // convention: sin at cs + pair + half_d); `own` = x[d0..], `par` = x[(d0 ^ half)..]. Same
@@ -482,7 +502,9 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
         k_own = ld_agent4(P.k_src + d0), k_par = ld_agent4(P.k_src + (d0 ^ HALF));
         v_new = ld_agent4(P.v_src + d0);
     } else if (wait_qkv) { // ---- hand-off: the q / k / v granules of this head carry this execution's generation (DecodeHandoff)
-        if (w == 0) { // ONE wave sweeps (16 waves would pull 16 x the granules through this CU's memory path per sweep), the others wait at the barrier
+        // ONE wave sweeps (16 waves would pull 16 x the granules through this CU's memory path per sweep), the others wait at the barrier
+        // (the wave index as a scalar: the ring's loop stands behind a scalar branch, not under an exec mask)
+        if (__builtin_amdgcn_readfirstlane(w) == 0) {
             constexpr int PER = DH / 64 > 0 ? DH / 64 : 1, NG = 3 * PER; // granules per lane and slice / per lane (the fused launches: d_head 64 / 128)
             static_assert(DH % 64 == 0 || DH < 64, "a slice is swept by whole waves");
             // the record's slices from its pointers (records need not be in head order); every access to the granule area is an
@@ -495,23 +517,61 @@ __device__ __forceinline__ void attention_decode_body(const AttnDecodeParams* __
                                   g0 + (2u * (uint32_t)(uintptr_t)P.v_src + ho->rel[2])};
             const bool in_slice = DH >= 64 || lane < (uint32_t)DH;
             const uint32_t lane8 = in_slice ? 8u * lane : 0u;
-            uint32_t spins = 0;
-            for (;;) {
+            // The wait as sweep_ring.h states it, with D sweeps in flight (d_head 64: 1, d_head 128: 2, see above): a sweep loads every granule
+            // again, ALL its loads issued back to back, and a value is only taken with its own tag.
+            // Every CHECKED sweep is staged in LDS, as the loop this replaces did, and the wait ends on the first whose tags all
+            // match: what the other waves read behind the barrier is that sweep and no other. (For D > 1: staging only the matching
+            // sweep makes its values leave the loop by D exits; hipcc then keeps slots in scratch memory or copies slots in flight
+            // behind vmcnt(0): profiles/r30_sweep_ring.txt section 2.)
+            constexpr int D = DH >= 128 ? kSweepDepth128 : kSweepDepth64;
+            static_assert(D >= 1 && kSweepRtt / D <= 127, "s_sleep takes 7 bits");
+            struct Sweep { unsigned long long g[NG]; };
+#ifdef ZGML_TRACE // diagnostics build: the round trip of the first sweep (the K / V rows in front of it included) and the sweeps of this wait
+            unsigned long long sweep_t0 = 0, sweep_rtt = 0;
+            bool sweep_first = trace != nullptr;
+#endif
+            auto issue = [&]() {
+                Sweep s;
+#ifdef ZGML_TRACE
+                if (sweep_first && !sweep_t0) sweep_t0 = wall_clock64();
+#endif
+#pragma unroll
+                for (int k = 0; k < NG; k++)
+                    s.g[k] = __hip_atomic_load((const gu64*)(gs[k / PER] + lane8) + 64 * (k % PER), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return s;
+            };
+            auto stage_and_match = [&](const Sweep& s) {
                 bool ok = true;
 #pragma unroll
-                for (int k = 0; k < NG; k++) { // every granule again in every sweep: a value is only taken with its own tag
-                    const unsigned long long x = __hip_atomic_load((const gu64*)(gs[k / PER] + lane8) + 64 * (k % PER), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    // (straight to LDS, sweep after sweep — the last one's values stay: nothing swept is held in registers beside the K / V rows)
-                    if (in_slice) qkv_lds[(k / PER) * DH + 64 * (k % PER) + lane] = __uint_as_float(handoff_granule_value(x));
-                    ok = ok && handoff_granule_gen(x) == gen;
+                for (int k = 0; k < NG; k++) {
+                    ok = ok && handoff_granule_gen(s.g[k]) == gen;
+                    if (in_slice) qkv_lds[(k / PER) * DH + 64 * (k % PER) + lane] = __uint_as_float(handoff_granule_value(s.g[k]));
                 }
-                if (__builtin_amdgcn_ballot_w64(!ok) == 0) break; // (wave-uniform)
-                if (++spins > 400000u) { // bounded: never hang the device; the caller sees the flag
-                    if (tid == 0) __hip_atomic_store(ho->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // host-visible word (runtime.hip: handoff_ok)
-                    break;
+                const bool all = __builtin_amdgcn_ballot_w64(!ok) == 0; // (wave-uniform)
+#ifdef ZGML_TRACE
+                if (sweep_first) { // (the clock is not ordered against the compiler's own wait: wait for the first sweep's loads here)
+#if defined(__HIP_DEVICE_COMPILE__)
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sweep_ring_in_flight(D, NG)) : "memory");
+#endif
+                    sweep_rtt = wall_clock64() - sweep_t0, sweep_first = false;
                 }
-                for (uint32_t z = 0; z < ho->poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
-            }
+#endif
+                return all;
+            };
+            auto accept = [](const Sweep&) {}; // (already staged)
+            auto pause = [&](SweepPause what) {
+                if (what == kSweepStagger)
+                    __builtin_amdgcn_s_sleep(kSweepRtt / D);
+                else // (the switch's sleep, as between two sequential sweeps: its slot is re-issued behind it)
+                    for (uint32_t z = 0; z < ho->poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
+            };
+            const SweepResult swept = sweep_ring<D, Sweep>(issue, stage_and_match, accept, pause);
+            // bounded: never hang the device; the caller sees the flag (the sweep staged last did not match: the fallback runs the
+            // step again). Every lane of the wave stores the same word: no branch on the lane beside the ring's loop.
+            if (!swept.accepted) __hip_atomic_store(ho->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); // host-visible word (runtime.hip: handoff_ok)
+#ifdef ZGML_TRACE
+            if (trace) trace[8] = swept.checked, trace[9] = sweep_rtt; // (sweeps checked | first round trip, wall-clock ticks; wave-uniform values)
+#endif
         }
         // an LDS-only barrier (__syncthreads() would also wait for the K / V rows in flight); a single wave reads behind its own
         // writes (the DS operations of a wave complete in order). Waves >= NW have retired and do not count.

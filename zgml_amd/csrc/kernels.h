@@ -118,6 +118,7 @@ struct AttentionParams {
 // attention itself and (via att.dst2) the head-output row store. Heads that share a kv head each
 // recompute the new key/value from the projections; `owner` marks the one that writes the cache
 // and the k_rot side output. The new column is taken from registers, never re-read from memory.
+constexpr int kAttnTraceWords = 10; // a launch's diagnostics record: stamps 0-7 | sweeps of the granule hand-off wait | its first sweep's round trip
 struct AttnDecodeParams {
     AttentionParams att;      // att.q = q_rot (side output), att.k / att.v = the kv head's slabs
     float* q_rot;             // == att.q, writable
@@ -137,7 +138,7 @@ struct AttnDecodeParams {
     // quantised KV caches (kvq_store + attention_kvq folded in): block size (32; 0 = f32 caches) and columns per cache;
     // k_cache / v_cache are then the cache buffers (int8 rows, f32 block scales behind them), the dynamic words columns
     uint32_t kvq_block = 0, kvq_cols = 0;
-    unsigned long long* trace; // diagnostics (ZGML_HIP_ATTN_TRACE=1): 8 wall-clock stamps, else nullptr
+    unsigned long long* trace; // diagnostics (ZGML_HIP_ATTN_TRACE=1): 8 wall-clock stamps, then the hand-off wait's sweep count and first round trip (kAttnTraceWords), else nullptr
 };
 
 // quantised KV cache (extension ops; layout in include/zgml_hip.h)

@@ -1725,7 +1725,7 @@ struct Planner {
             a.k_rot = buf_at(p, kr.dst, kr.dst_off);
             a.dyn_k_off = p->dyn_dev + m.sk, a.dyn_v_off = p->dyn_dev + m.sv; // column indices
             a.owner = first_head ? 1 : 0;
-            if (sw().hip_attn_trace && first_head && (a.trace = mapped_trace(8))) p->attn_traces.push_back(a.trace); // one record per launch
+            if (sw().hip_attn_trace && first_head && (a.trace = mapped_trace(kAttnTraceWords))) p->attn_traces.push_back(a.trace); // one record per launch
             first_head = false;
             by_dh[a.att.d_head | (m.kvq ? 0x10000u : 0u)].push_back(a);
         }

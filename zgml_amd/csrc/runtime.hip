@@ -1415,6 +1415,7 @@ void zgml_hip_free_program(zgml_hip_ctx* ctx, zgml_hip_program* p) {
             const unsigned long long* t = p->attn_traces[i];
             fprintf(stderr, "  L%02zu gap %6lld |", i, prev_end ? (long long)(t[0] - prev_end) * 10 : -1);
             for (int k = 1; k < 8; k++) fprintf(stderr, " %5lld", (long long)(t[k] - t[k - 1]) * 10);
+            if (t[8]) fprintf(stderr, " | sweeps %3llu first-rtt %5llu", t[8], t[9] * 10); // (the granule hand-off's wait: attention_decode.h)
             fprintf(stderr, "\n");
             prev_end = t[7];
         }
