@@ -255,9 +255,19 @@ typedef struct zgml_program_io {
  *     data_len == rows*cols/32 * 34  ->  Q8_0 blocks {f16 scale, 32 int8}
  * i.e. what quantizedWeightFromInfo (src/models/gguf_loader.zig:99-154) expands on the host; here the
  * expansion and the re-pack happen on the device and half (Q4_0) of the bytes cross PCIe.
- * Requires rows*cols % 32 == 0 and cols % 32 == 0. */
+ * Requires rows*cols % 32 == 0 and cols % 32 == 0.
+ *
+ * With `scales == NULL && scales_len == 0 && block_size == 256`, `data` holds GGUF Q4_K super-blocks — block b covers flat
+ * elements [256b, 256b+256), i.e. 256 consecutive columns of one row —
+ *     data_len == rows*cols/256 * 144 -> {f16 d, f16 dmin, scales[12], qs[128]}: eight 6-bit (scale, min) pairs, one per 32
+ *                                        elements; element 64i+l is the low nibble of qs[32i+l], element 64i+32+l the high one;
+ *                                        value = (d*sc)*nibble - dmin*m (GGUF's own definition; zgml_amd/csrc/q4k.h states it)
+ * Requires cols % 256 == 0 (a tensor with another width travels in another type, as GGUF writers do). rows*cols/256*144 equals
+ * rows*cols/32*18, so `block_size` alone tells Q4_K from Q4_0. The blocks stay 4.5 bit/weight on the device and are read by
+ * kernels of their own for every M; such a weight is never fused, grouped or sharded. */
 #define ZGML_QW_GGUF_Q4_0_BLOCK_BYTES 18
 #define ZGML_QW_GGUF_Q8_0_BLOCK_BYTES 34
+#define ZGML_QW_GGUF_Q4_K_BLOCK_BYTES 144
 typedef struct zgml_qweight_upload {
     const int8_t* data;
     uint64_t data_len;

@@ -1,0 +1,46 @@
+"""GGUF Q4_K (q4k.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes kernel and the
+M = 32 matmul against the tile kernel, at 4096^2, 4096 x 11008 and 4096 x 32000. Both formats stream 4.5 bit/weight, so the
+bytes per launch are equal and the times compare directly. A ring of distinct matrices larger than the 256 MiB Infinity Cache
+stands for a model; device-event time per launch over replays of a captured graph (zgml_hip_qmatmul_bench); the two formats
+alternate within each repeat and every repeat is printed, so the spread shows next to the difference."""
+import argparse
+import ctypes as C
+import json
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from zgml_amd import Backend  # noqa: E402
+
+FMT = {"q4_0": 1, "q4_k": 2}  # the `q4` argument of zgml_hip_qmatmul_bench
+
+
+def run(be, fmt, M, K, N, ring, iters):
+    nbytes = C.c_uint64()
+    us = be._lib.zgml_hip_qmatmul_bench(be.ctx, M, K, N, FMT[fmt], ring, 20, iters, C.byref(nbytes))
+    if us <= 0:
+        raise RuntimeError(be.last_error() or "bench refused the shape")
+    return us, nbytes.value
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--shapes", default="4096x4096,4096x11008,4096x32000")
+    a = ap.parse_args()
+    be = Backend(0)
+    for shp in a.shapes.split(","):
+        K, N = map(int, shp.split("x"))
+        ring = max(2, min(64, int(40e9 // (K * N))))
+        for M in (1, 32):
+            us = {f: [] for f in FMT}
+            for _ in range(a.repeats):
+                for f in FMT:
+                    t, nbytes = run(be, f, M, K, N, ring, a.iters if M == 1 else max(64, a.iters // 8))
+                    us[f].append(round(t, 3))
+            best = {f: min(v) for f, v in us.items()}
+            print(json.dumps({"K": K, "N": N, "M": M, "ring": ring, "bytes": nbytes, "us": us,
+                              "GBps": {f: round(nbytes / best[f] / 1e3, 1) for f in FMT},
+                              "q4_k_over_q4_0": round(best["q4_k"] / best["q4_0"], 3)}), flush=True)
+    be.close()

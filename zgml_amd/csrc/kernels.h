@@ -201,6 +201,9 @@ enum QWFormat : uint32_t {
     QW_Q8 = 2,  // packed int8, lane-tiled
     QW_Q4K = 3, // packed offset-binary nibbles, K ON LANES (qmatvec.hip: qmatvec_kon_body): M = 1 mat-vecs (and, opt-in, 2 <= M <= 8: qmatvec_rows.hip), f16 scales
     QW_W8A8 = 4, // the reference's W8A8 arm (w8a8.hip): re-quantised transposed int8 + f32 scale per (column, 32 k); M = 1 only, opt-in
+    // GGUF Q4_K ("super-block 4-bit", q4k.hip): 16-byte items of one sub-block column at one k + the file's 16-byte headers; any M, its
+    // own launcher, never fused, grouped or sharded. NOT QW_Q4K above, which is Q4_0 with K on lanes and has nothing to do with Q4_K.
+    QW_SB4 = 5,
 };
 
 struct QWeightDev {
@@ -743,6 +746,15 @@ bool w8a8_applies(uint64_t K, uint64_t N, uint64_t bs);
 void w8a8_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
 void launch_pack_w8a8(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);
 void launch_w8a8_matvec(hipStream_t s, const QWeightDev& w, const float* x, float* dst);
+// GGUF Q4_K arm (q4k.hip; format: q4k.h): shapes it takes (N a multiple of 256), sizes of its packed image (4.5 bit/weight), the
+// device re-pack of the file's 144-byte super-blocks, the scratch an M = 1 launch splits K through (the same block and counter
+// head as qmatmul_scratch_bytes describes below) and the launch for any M (M = 1: the streaming mat-vec, M > 1: bf16 matrix cores)
+bool sb4_applies(uint64_t K, uint64_t N);
+void sb4_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
+void launch_pack_sb4(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
+void launch_synth_sb4(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
+uint64_t sb4_scratch_bytes(const QWeightDev& w, uint32_t M);
+void launch_sb4_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
 void packed_bytes(QWFormat format, uint32_t scale_f16, uint64_t K, uint64_t N, uint64_t* qs_bytes,
                   uint64_t* sc_bytes);
 void launch_pack_qweight(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);

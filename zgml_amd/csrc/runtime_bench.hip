@@ -5,8 +5,17 @@
 
 extern "C" {
 
+// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K (q4k.hip)
 static bool make_synth_weight(zgml_hip_ctx* ctx, uint32_t K, uint32_t N, int q4, uint32_t id, QWeightDev* w, uint32_t M = 1) {
-    w->format = q4 ? (M == 1 && sw().hip_qmv_kon ? QW_Q4K : QW_Q4) : QW_Q8; // (what compile_program picks for a weight that only feeds mat-vecs)
+    if (q4 == 2) {
+        if (!sb4_applies(K, N)) return false;
+        w->format = QW_SB4, w->K = K, w->N = N, w->bs = 256, w->KC = (K + 31) / 32, w->scale_f16 = 1;
+        sb4_packed_bytes(K, N, &w->qs_bytes, &w->sc_bytes);
+        if (!CTX_CHECK(ctx, hipMalloc(&w->qs, w->qs_bytes)) || !CTX_CHECK(ctx, hipMalloc(&w->sc, w->sc_bytes))) return false;
+        launch_synth_sb4(ctx->stream, *w, id);
+        return true;
+    }
+    w->format = q4 ?(M == 1 && sw().hip_qmv_kon ? QW_Q4K : QW_Q4) : QW_Q8; // (what compile_program picks for a weight that only feeds mat-vecs)
     w->K = K, w->N = N, w->bs = 32;
     w->KC = (K + 31) / 32;
     w->scale_f16 = 1;

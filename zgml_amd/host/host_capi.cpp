@@ -85,7 +85,7 @@ zh_model* zh_model_create_ex(const zh_config* cfg, int weight_kind, int fused_el
                               (c.d_ff / c.shard_world) % 32 || (c.vocab_size / c.shard_world) % 32 || c.d_ff % c.shard_world ||
                               c.vocab_size % c.shard_world))
         return nullptr; // shard slices must stay whole 32-column scale blocks
-    if (((WeightKind)weight_kind == WeightKind::f32_dense || (WeightKind)weight_kind == WeightKind::q4_0_gguf) && c.shard_world > 1)
+    if ((is_dense((WeightKind)weight_kind) || is_gguf((WeightKind)weight_kind)) && c.shard_world > 1)
         return nullptr; // shard slices are cut from the int8 form
     if (token_len > 1 && c.shard_world > 1) return nullptr; // the row-shard driver is decode-only
     auto* m = new zh_model();
@@ -252,8 +252,11 @@ uint64_t zh_model_quant_bytes(zh_model* m, uint64_t* n_weights) { // Q4_0/Q8_0 f
     uint64_t elems = 0;
     for (const auto& q : m->model->qweights) elems += q.K * q.N;
     if (n_weights) *n_weights = elems;
-    if (m->model->kind == WeightKind::f32_dense) return elems * 2; // f16-promoted bytes
-    return elems / 32 * (m->model->kind == WeightKind::q8_0 ? 34 : 18);
+    if (is_dense(m->model->kind)) return elems * 2; // f16-promoted bytes
+    uint64_t bytes = 0; // (Q4_K: 144 B per 256 elements, the same 4.5 bit/weight as Q4_0's 18 B per 32)
+    for (const auto& q : m->model->qweights)
+        bytes += q.gguf_block == 256 ? q.K * q.N / 256 * 144 : q.K * q.N / 32 * (m->model->kind == WeightKind::q8_0 ? 34 : 18);
+    return bytes;
 }
 
 zh_session* zh_session_create(zh_model* m, const zh_backend_fns* fns) {

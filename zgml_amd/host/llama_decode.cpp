@@ -4,6 +4,8 @@
 #endif
 #include "llama_decode.hpp"
 
+#include "../csrc/q4k.h"
+
 #include <cstdlib>
 
 #include <algorithm>
@@ -88,6 +90,22 @@ inline float synth_scale(uint64_t block, uint32_t id, WeightKind kind) {
     return f16_round(base * (1.0f + (float)((block + id) % 7) * 0.125f));
 }
 
+// Q4_K super-block `sb` of weight `id` (csrc/q4k.h): d and dmin of both signs in the normal f16 range, the twelve scale bytes and the
+// 128 nibble bytes hashed, so sc and m run over 0..63 and q over 0..15. |w| stays below 0.2, mostly far below.
+inline uint32_t mix32(uint32_t x) {
+    x ^= x >> 16, x *= 0x7feb352du;
+    x ^= x >> 15, x *= 0x846ca68bu;
+    return x ^ (x >> 16);
+}
+void synth_q4k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
+    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0x85EBCA6Bu);
+    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -14) * ((s >> 3) & 1 ? -1.0f : 1.0f);
+    const float dmin = std::ldexp(1.0f + (float)((s >> 4) & 7) * 0.125f, -11) * ((s >> 7) & 1 ? -1.0f : 1.0f);
+    const uint16_t hd = f32_to_f16_bits(d), hm = f32_to_f16_bits(dmin);
+    blk[0] = (uint8_t)(hd & 0xFF), blk[1] = (uint8_t)(hd >> 8), blk[2] = (uint8_t)(hm & 0xFF), blk[3] = (uint8_t)(hm >> 8);
+    for (uint32_t i = 0; i < 140; i++) blk[4 + i] = (uint8_t)(mix32(s + 1 + i) >> 11);
+}
+
 void parallel_rows(size_t n, int threads, const std::function<void(size_t, size_t)>& fn) {
     threads = std::max(1, threads);
     if (threads == 1 || n < 64) {
@@ -166,8 +184,23 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
         auto [n0, nl] = shard(cfg.vocab_size);
         m->qweights.push_back(make_qweight(d, cfg.vocab_size, n0, nl, cfg.n_layers * 8, kind, threads));
     }
-    if (kind == WeightKind::q4_0_gguf) { // the same model as 18-byte file blocks (gguf_loader.zig:118-141, interleaved nibbles)
+    const bool sb_model = kind == WeightKind::q4_k_gguf || kind == WeightKind::q4_k_dense;
+    if (sb_model) // N % 256 == 0: Q4_K super-blocks of their own generator (the Q4_0 values are dropped); else Q4_0 file blocks below
+        for (size_t wi = 0; wi < m->qweights.size(); wi++) {
+            auto& q = m->qweights[wi];
+            if (q.N % zgml::kQ4kBlock) continue;
+            const uint32_t id = (uint32_t)(wi / 7 * 8 + wi % 7);
+            q.gguf_block = zgml::kQ4kBlock;
+            q.gguf.resize(q.K * q.N / zgml::kQ4kBlock * zgml::kQ4kBytes);
+            parallel_rows(q.K * q.N / zgml::kQ4kBlock, threads, [&](size_t b0, size_t b1) {
+                for (size_t b = b0; b < b1; b++) synth_q4k_block(b, id, q.gguf.data() + b * zgml::kQ4kBytes);
+            });
+            std::vector<int8_t>().swap(q.data);
+            std::vector<float>().swap(q.scales);
+        }
+    if (kind == WeightKind::q4_0_gguf || sb_model) { // the same model as 18-byte file blocks (gguf_loader.zig:118-141, interleaved nibbles)
         for (auto& q : m->qweights) {
+            if (!q.gguf.empty()) continue;
             const size_t nb = q.K * q.N / 32;
             q.gguf.resize(nb * 18);
             parallel_rows(nb, threads, [&](size_t b0, size_t b1) {
@@ -181,6 +214,26 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
             });
             std::vector<int8_t>().swap(q.data);
             std::vector<float>().swap(q.scales);
+        }
+    }
+    if (kind == WeightKind::q4_k_dense) { // the q4_k_gguf model, dequantised by the format's own rule (csrc/q4k.h); file blocks dropped
+        for (auto& q : m->qweights) {
+            std::vector<float> w(q.K * q.N);
+            const uint8_t* g = q.gguf.data();
+            const bool sb = q.gguf_block == zgml::kQ4kBlock;
+            parallel_rows(q.K, threads, [&](size_t k0, size_t k1) {
+                for (size_t i = k0 * q.N; i < k1 * q.N; i++) {
+                    if (sb) {
+                        w[i] = zgml::q4k_value(g + i / zgml::kQ4kBlock * zgml::kQ4kBytes, (uint32_t)(i % zgml::kQ4kBlock));
+                    } else { // Q4_0 block: f16 scale, element e in the low (e even) / high nibble of byte e / 2, value = nibble - 8
+                        const uint8_t* blk = g + i / 32 * 18;
+                        const uint32_t e = (uint32_t)(i % 32);
+                        w[i] = (float)((int)((blk[2 + e / 2] >> (4 * (e & 1))) & 15) - 8) * zgml::q4k_f16((uint16_t)(blk[0] | blk[1] << 8));
+                    }
+                }
+            });
+            m->dense.push_back(std::move(w));
+            std::vector<uint8_t>().swap(q.gguf);
         }
     }
     if (kind == WeightKind::f32_dense) { // the same model, dequantised: f32 [K, N] per weight; int8 form dropped
@@ -320,12 +373,14 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
 
     // quantized weight table (all borrowed from the model), or dense f32 weight leaves
     for (const auto& qw : model.qweights) {
-        if (model.kind == WeightKind::q4_0_gguf)
+        if (is_gguf(model.kind) && qw.gguf_block == zgml::kQ4kBlock)
+            dp.program.qweights.push_back(backend::QuantizedWeightUpload::ggufSuperBlocks(qw.gguf.data(), qw.gguf.size(), qw.K, qw.N));
+        else if (is_gguf(model.kind))
             dp.program.qweights.push_back(backend::QuantizedWeightUpload::ggufBlocks(qw.gguf.data(), qw.gguf.size(), qw.K, qw.N));
-        else if (model.kind != WeightKind::f32_dense)
+        else if (!is_dense(model.kind))
             dp.program.qweights.push_back({qw.data.data(), qw.data.size(), qw.scales.data(), qw.scales.size(), qw.K, qw.N, 32});
     }
-    if (model.kind == WeightKind::f32_dense)
+    if (is_dense(model.kind))
         for (const auto& w : model.dense) b.dense_buf.push_back(b.leaf(w));
 
     dp.token_input.assign((size_t)d * T, 0.f);
@@ -356,7 +411,7 @@ static std::unique_ptr<DecodeProgram> build_program(const LlamaModel& model, boo
             dp.kv_buffers.push_back({k_cache, kv_slab * n_pass});
             dp.kv_buffers.push_back({v_cache, kv_slab * n_pass});
         }
-        if (include_dead_f32 && model.kind != WeightKind::f32_dense) { // f32 master copies: buffers + uploads, never referenced by an op (F8)
+        if (include_dead_f32 && !is_dense(model.kind) && !is_gguf(model.kind)) { // f32 master copies: buffers + uploads, never referenced by an op (F8); file-block models keep no int8 form to expand
             for (int j = 0; j < 7; j++) {
                 const auto& qw = model.qweights[l * 7 + j];
                 dp.dead_f32.emplace_back(qw.K * qw.N);

@@ -12,6 +12,8 @@ import numpy as np
 from . import capi
 
 Q4_0, Q8_0, F32_DENSE, Q4_0_GGUF = 0, 1, 2, 3
+# GGUF Q4_K super-blocks wherever a projection's N % 256 == 0 (Q4_0 file blocks elsewhere), and the same values as f32 matmuls
+Q4_K_GGUF, Q4_K_DENSE = 4, 5
 
 
 class Config(C.Structure):

@@ -261,9 +261,13 @@ class QuantizedWeightUpload:
 
     @staticmethod
     def from_gguf_blocks(raw: np.ndarray, rows: int, cols: int, kind: str) -> "QuantizedWeightUpload":
-        assert kind in ("q4_0", "q8_0") and (rows * cols) % 32 == 0
+        """kind "q4_0" / "q8_0": 18 / 34-byte blocks of 32 flat elements; "q4_k": 144-byte super-blocks of 256 (cols % 256 == 0)."""
+        assert kind in ("q4_0", "q8_0", "q4_k")
         raw = np.ascontiguousarray(raw, dtype=np.uint8).ravel()
-        assert raw.size == rows * cols // 32 * (18 if kind == "q4_0" else 34)
+        if kind == "q4_k":
+            assert cols % 256 == 0 and raw.size == rows * cols // 256 * 144
+            return QuantizedWeightUpload(raw, np.zeros(0, np.float32), rows, cols, 256, gguf=kind)
+        assert (rows * cols) % 32 == 0 and raw.size == rows * cols // 32 * (18 if kind == "q4_0" else 34)
         return QuantizedWeightUpload(raw, np.zeros(0, np.float32), rows, cols, 32, gguf=kind)
 
 
@@ -395,7 +399,10 @@ class DeviceProgram:
                 n_elems = op.K * op.N
                 n_blocks = (n_elems + qw.block_size - 1) // qw.block_size
                 if qw.gguf is not None:
-                    if n_elems % 32 or op.N % 32 or qw.block_size != 32:
+                    if qw.block_size == 256:  # Q4_K super-blocks
+                        if op.N % 256 or qw.data.size != n_elems // 256 * 144:
+                            return False
+                    elif n_elems % 32 or op.N % 32 or qw.block_size != 32:
                         return False
                     continue
                 if qw.data.size < n_elems or qw.scales.size < n_blocks:
