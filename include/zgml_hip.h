@@ -264,10 +264,17 @@ typedef struct zgml_program_io {
  *                                        value = (d*sc)*nibble - dmin*m (GGUF's own definition; zgml_amd/csrc/q4k.h states it)
  * Requires cols % 256 == 0 (a tensor with another width travels in another type, as GGUF writers do). rows*cols/256*144 equals
  * rows*cols/32*18, so `block_size` alone tells Q4_K from Q4_0. The blocks stay 4.5 bit/weight on the device and are read by
- * kernels of their own for every M; such a weight is never fused, grouped or sharded. */
+ * kernels of their own for every M; such a weight is never fused, grouped or sharded.
+ *     data_len == rows*cols/256 * 210 -> Q6_K {ql[128], qh[64], int8 scales[16], f16 d}, the type a Q4_K_M file keeps output.weight
+ *                                        and part of attn_v / ffn_down in: element 128h+32g+l has the low nibble
+ *                                        (ql[64h+32(g&1)+l] >> 4(g>>1)) & 15 and the high bits (qh[32h+l] >> 2g) & 3;
+ *                                        value = (d*scales[e/16])*(q-32) (zgml_amd/csrc/q6k.h states it)
+ * Under block_size 256 `data_len` tells the two apart; the same shape rule holds, and Q6_K stays 6.5625 bit/weight on the device
+ * with kernels of its own, launched as Q4_K is. A file block is only 2-byte aligned; `data` needs no more than that. */
 #define ZGML_QW_GGUF_Q4_0_BLOCK_BYTES 18
 #define ZGML_QW_GGUF_Q8_0_BLOCK_BYTES 34
 #define ZGML_QW_GGUF_Q4_K_BLOCK_BYTES 144
+#define ZGML_QW_GGUF_Q6_K_BLOCK_BYTES 210
 typedef struct zgml_qweight_upload {
     const int8_t* data;
     uint64_t data_len;

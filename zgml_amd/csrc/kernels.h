@@ -204,7 +204,12 @@ enum QWFormat : uint32_t {
     // GGUF Q4_K ("super-block 4-bit", q4k.hip): 16-byte items of one sub-block column at one k + the file's 16-byte headers; any M, its
     // own launcher, never fused, grouped or sharded. NOT QW_Q4K above, which is Q4_0 with K on lanes and has nothing to do with Q4_K.
     QW_SB4 = 5,
+    // GGUF Q6_K ("super-block 6-bit", q6k.hip): 16 + 8-byte items of 32 columns at one k in two planes + the file's 16 int8 scales and f16 d
+    // per (k, 256 columns) in planes of their own; launched as QW_SB4 is
+    QW_SB6 = 6,
 };
+// the GGUF super-block formats: plain launches of their own kernels for every M
+inline bool qw_super_block(QWFormat f) { return f == QW_SB4 || f == QW_SB6; }
 
 struct QWeightDev {
     QWFormat format = QW_RAW;
@@ -755,6 +760,13 @@ void launch_pack_sb4(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev&
 void launch_synth_sb4(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
 uint64_t sb4_scratch_bytes(const QWeightDev& w, uint32_t M);
 void launch_sb4_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
+// GGUF Q6_K arm (q6k.hip; format: q6k.h): the same set for the 210-byte super-blocks (6.5625 bit/weight packed)
+bool sb6_applies(uint64_t K, uint64_t N);
+void sb6_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
+void launch_pack_sb6(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
+void launch_synth_sb6(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
+uint64_t sb6_scratch_bytes(const QWeightDev& w, uint32_t M);
+void launch_sb6_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
 void packed_bytes(QWFormat format, uint32_t scale_f16, uint64_t K, uint64_t N, uint64_t* qs_bytes,
                   uint64_t* sc_bytes);
 void launch_pack_qweight(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);

@@ -16,7 +16,7 @@
 // the same headers, so HBM sees each once —, one x). A lane carries 32 column sums and one min sum: one multiply, 32 FMAs and one
 // FMA per item. The sums are folded over the lanes by row swaps and DPP row sums in a fixed tree. With fewer sub-block columns than
 // the part has wave slots the K range is split over blockIdx.y; every part stores its 256 partial outputs and the LAST part to
-// arrive (an integer counter; no float atomics) adds them in part order, so the bytes do not depend on arrival order.
+// arrive (an integer counter; no float atomics) adds them in part order, so the bytes do not depend on arrival order (sb_combine.h).
 //
 // M > 1 (sb4_matmul_kernel): a workgroup of 4 waves owns one sub-block column (32 output columns = two 16-column tiles) and 16
 // rows; the waves deal the 64-k chunks round-robin. Per chunk a wave loads 64 items coalesced, turns them through its own LDS
@@ -25,7 +25,7 @@
 // pieces (t = h1 + h2 + h3 up to 2^-26 |t|), contracted by v_mfma_f32_16x16x32_bf16 with f32 accumulation: six MFMAs per 32 k.
 // The min term is 8 VALU FMAs per 32 k beside them, folded over the four lane rows at the end. Waves are folded in wave order.
 #include "q4k.h"
-#include "qmv_common.h"
+#include "sb_combine.h"
 
 namespace zgml {
 namespace {
@@ -34,11 +34,8 @@ constexpr uint32_t kSbWaves = 8;           // M = 1: waves of a workgroup = sub-
 constexpr uint32_t kSbSweep = 64;          // k per wave sweep (one per lane)
 constexpr uint32_t kSbShareMinSweeps = 4;  // a part's K share is at least this many sweeps (the fold costs about one sweep)
 constexpr uint32_t kSbTargetWaves = 2048;  // 256 CUs x 8 waves: split K until the grid has this many waves
-constexpr uint32_t kSbCombineBatch = 8;    // partial sums the combining workgroup loads before it adds them
 constexpr uint32_t kSbMmWaves = 4;        // M > 1: waves of a workgroup, dealing the 64-k chunks
 
-using gf32 = __attribute__((address_space(1))) float;
-using gu32 = __attribute__((address_space(1))) unsigned int;
 typedef float sb4_f4 __attribute__((ext_vector_type(4)));
 typedef __bf16 sb4_bf8 __attribute__((ext_vector_type(8)));
 
@@ -146,27 +143,7 @@ __global__ void __launch_bounds__(kSbWaves * 64) sb4_matvec_kernel(Sb4MvArgs a) 
 
     const uint32_t n = nsb * kQ4kBlock + threadIdx.x; // threads 0..255: one column each
     float y = threadIdx.x < kQ4kBlock ? red[threadIdx.x >> 5][threadIdx.x & 31] : 0.f;
-    if (a.parts > 1) {
-        if (threadIdx.x < kQ4kBlock) __hip_atomic_store((gf32*)(a.partial + (uint64_t)part * a.N + n), y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // every storing wave drains before the count
-        __syncthreads();
-        uint32_t* const cnt = a.counter + nsb;
-        if (threadIdx.x == 0) flag = __hip_atomic_fetch_add((gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (flag != a.parts - 1) return; // not the last part of this super-block column
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // compiler only: the loads below stay below the count
-        y = 0.f;
-        if (threadIdx.x < kQ4kBlock)
-            for (uint32_t p0 = 0; p0 < a.parts; p0 += kSbCombineBatch) { // part order, not arrival order; a batch of loads in flight at once
-                float pv[kSbCombineBatch];                               // (one dependent load per part cost 1.4 us each)
-#pragma unroll
-                for (uint32_t q = 0; q < kSbCombineBatch; q++) // (past the end: the last part again, dropped below)
-                    pv[q] = __hip_atomic_load((gf32*)(a.partial + (uint64_t)min(p0 + q, a.parts - 1) * a.N + n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (uint32_t q = 0; q < kSbCombineBatch; q++) y += p0 + q < a.parts ? pv[q] : 0.f;
-            }
-        if (threadIdx.x == 0) __hip_atomic_store((gu32*)cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // re-arm
-    }
+    if (a.parts > 1 && !sb_combine(y, threadIdx.x < kQ4kBlock, a.partial, a.counter + nsb, part, a.parts, a.N, n, &flag)) return;
     if (threadIdx.x < kQ4kBlock) a.dst[n] = y;
 }
 

@@ -14,6 +14,8 @@ from . import capi
 Q4_0, Q8_0, F32_DENSE, Q4_0_GGUF = 0, 1, 2, 3
 # GGUF Q4_K super-blocks wherever a projection's N % 256 == 0 (Q4_0 file blocks elsewhere), and the same values as f32 matmuls
 Q4_K_GGUF, Q4_K_DENSE = 4, 5
+# the Q4_K_M mix: Q6_K super-blocks for the untied LM head and the wv / w_down of the "more bits" layers, Q4_K elsewhere; and its f32 twin
+Q4_K_M_GGUF, Q4_K_M_DENSE = 6, 7
 
 
 class Config(C.Structure):
