@@ -269,11 +269,16 @@ typedef struct zgml_program_io {
  *                                        and part of attn_v / ffn_down in: element 128h+32g+l has the low nibble
  *                                        (ql[64h+32(g&1)+l] >> 4(g>>1)) & 15 and the high bits (qh[32h+l] >> 2g) & 3;
  *                                        value = (d*scales[e/16])*(q-32) (zgml_amd/csrc/q6k.h states it)
- * Under block_size 256 `data_len` tells the two apart; the same shape rule holds, and Q6_K stays 6.5625 bit/weight on the device
- * with kernels of its own, launched as Q4_K is. A file block is only 2-byte aligned; `data` needs no more than that. */
+ *     data_len == rows*cols/256 * 176 -> Q5_K {f16 d, f16 dmin, scales[12] as Q4_K, qh[32], qs[128]}, the bulk type of a Q5_K_M / Q5_K_S
+ *                                        file: element 32j+l has the nibble (qs[32(j>>1)+l] >> 4(j&1)) & 15 and the high bit
+ *                                        (qh[l] >> j) & 1; value = (d*sc_j)*q - dmin*m_j (zgml_amd/csrc/q5k.h states it)
+ * Under block_size 256 `data_len` tells the three apart (144 / 176 / 210); the same shape rule holds, and Q6_K stays 6.5625 and
+ * Q5_K 5.5 bit/weight on the device with kernels of their own, launched as Q4_K is. A file block is only 2-byte aligned; `data`
+ * needs no more than that. */
 #define ZGML_QW_GGUF_Q4_0_BLOCK_BYTES 18
 #define ZGML_QW_GGUF_Q8_0_BLOCK_BYTES 34
 #define ZGML_QW_GGUF_Q4_K_BLOCK_BYTES 144
+#define ZGML_QW_GGUF_Q5_K_BLOCK_BYTES 176
 #define ZGML_QW_GGUF_Q6_K_BLOCK_BYTES 210
 typedef struct zgml_qweight_upload {
     const int8_t* data;

@@ -1,6 +1,6 @@
-"""GGUF Q4_K (q4k.hip) and Q6_K (q6k.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes
+"""GGUF Q4_K (q4k.hip), Q5_K (q5k.hip) and Q6_K (q6k.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes
 kernel and the M = 32 matmul against the tile kernel, at 4096^2, 4096 x 11008 and 4096 x 32000. Q4_0 and Q4_K stream 4.5 bit/weight,
-so their bytes per launch are equal and the times compare directly; Q6_K streams 210/144 of that, so its GB/s is printed too. A ring of distinct matrices larger than the 256 MiB Infinity Cache
+so their bytes per launch are equal and the times compare directly; Q5_K streams 176/144 and Q6_K 210/144 of that, so the GB/s are printed too. A ring of distinct matrices larger than the 256 MiB Infinity Cache
 stands for a model; device-event time per launch over replays of a captured graph (zgml_hip_qmatmul_bench); the formats
 alternate within each repeat and every repeat is printed, so the spread shows next to the difference."""
 import argparse
@@ -12,7 +12,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from zgml_amd import Backend  # noqa: E402
 
-FMT = {"q4_0": 1, "q4_k": 2, "q6_k": 3}  # the `q4` argument of zgml_hip_qmatmul_bench
+FMT = {"q4_0": 1, "q4_k": 2, "q5_k": 4, "q6_k": 3}  # the `q4` argument of zgml_hip_qmatmul_bench
 
 
 def run(be, fmt, M, K, N, ring, iters):
@@ -43,5 +43,7 @@ if __name__ == "__main__":
             print(json.dumps({"K": K, "N": N, "M": M, "ring": ring, "bytes": nbytes, "us": us,
                               "GBps": {f: round(nbytes[f] / best[f] / 1e3, 1) for f in FMT},
                               "q4_k_over_q4_0": round(best["q4_k"] / best["q4_0"], 3),
-                              "q6_k_over_q4_k": round(best["q6_k"] / best["q4_k"], 3)}), flush=True)
+                              "q6_k_over_q4_k": round(best["q6_k"] / best["q4_k"], 3),
+                              "q5_k_over_q4_k": round(best["q5_k"] / best["q4_k"], 3),
+                              "q5_k_over_q6_k": round(best["q5_k"] / best["q6_k"], 3)}), flush=True)
     be.close()

@@ -207,9 +207,12 @@ enum QWFormat : uint32_t {
     // GGUF Q6_K ("super-block 6-bit", q6k.hip): 16 + 8-byte items of 32 columns at one k in two planes + the file's 16 int8 scales and f16 d
     // per (k, 256 columns) in planes of their own; launched as QW_SB4 is
     QW_SB6 = 6,
+    // GGUF Q5_K ("super-block 5-bit", q5k.hip): 16 + 4-byte items of 32 columns at one k in two planes + the file's 16-byte headers per
+    // (k, 256 columns); launched as QW_SB4 is
+    QW_SB5 = 7,
 };
 // the GGUF super-block formats: plain launches of their own kernels for every M
-inline bool qw_super_block(QWFormat f) { return f == QW_SB4 || f == QW_SB6; }
+inline bool qw_super_block(QWFormat f) { return f == QW_SB4 || f == QW_SB6 || f == QW_SB5; }
 
 struct QWeightDev {
     QWFormat format = QW_RAW;
@@ -767,6 +770,13 @@ void launch_pack_sb6(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev&
 void launch_synth_sb6(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
 uint64_t sb6_scratch_bytes(const QWeightDev& w, uint32_t M);
 void launch_sb6_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
+// GGUF Q5_K arm (q5k.hip; format: q5k.h): the same set for the 176-byte super-blocks (5.5 bit/weight packed)
+bool sb5_applies(uint64_t K, uint64_t N);
+void sb5_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
+void launch_pack_sb5(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
+void launch_synth_sb5(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
+uint64_t sb5_scratch_bytes(const QWeightDev& w, uint32_t M);
+void launch_sb5_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
 void packed_bytes(QWFormat format, uint32_t scale_f16, uint64_t K, uint64_t N, uint64_t* qs_bytes,
                   uint64_t* sc_bytes);
 void launch_pack_qweight(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);

@@ -218,7 +218,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
             // q/k/v and gate/up read the same rows: the launch right after one that split the same input
             // (adjacent in the plan, so nothing rewrote the rows or the scratch in between) reuses its A pieces
             const uint64_t pos = p->plan.size();
-            // (a Q4_K / Q6_K launch splits no A pieces: what it keeps in the scratch is its own K-split partials, nothing a neighbour reuses)
+            // (a Q4_K / Q5_K / Q6_K launch splits no A pieces: what it keeps in the scratch is its own K-split partials, nothing a neighbour reuses)
             const bool splits = scratch && !qw_super_block(w.format) && qmatmul_scratch_bytes(w, qp.M) != 0;
             qp.reuse_split = splits && p->split_pos + 1 == pos && p->split_input == qp.input && p->split_M == qp.M && p->split_K == qp.K &&
                              p->split_in_rs == qp.in_rs && p->split_kind == 1;
@@ -258,6 +258,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
             }
             if (w.format == QW_SB4) L.tag = qp.M == 1 ? "q4k-matvec" : "q4k-matmul";
             if (w.format == QW_SB6) L.tag = qp.M == 1 ? "q6k-matvec" : "q6k-matmul";
+            if (w.format == QW_SB5) L.tag = qp.M == 1 ? "q5k-matvec" : "q5k-matmul";
             if (w.format == QW_Q4K && qp.M >= 2 && qp.M <= p->kon_max_m) L.tag = "qmatvec-kon-rows"; // (launch_qmatmul: the multi-row K-on-lanes mat-vec)
             auto group = std::make_shared<std::vector<std::pair<QWeightDev, QMatmulParams>>>();
             group->push_back({w, qp});
@@ -580,7 +581,7 @@ bool anchor_ok(zgml_hip_program* p, uint32_t i) {
     const zgml_device_op& op = p->ops[i];
     if (op.kind != ZGML_DOP_QMATMUL || op.u.qmatmul.M != 1) return false;
     const QWeightDev& w = p->qweights[op.u.qmatmul.weight_idx];
-    // (W8A8: the reference's arm, and Q4_K / Q6_K: launched as they are — no prologue / epilogue fusion, no grouping)
+    // (W8A8: the reference's arm, and Q4_K / Q5_K / Q6_K: launched as they are — no prologue / epilogue fusion, no grouping)
     return w.format != QW_RAW && w.format != QW_W8A8 && !qw_super_block(w.format) && (op.u.qmatmul.input_offset % 4) == 0;
 }
 

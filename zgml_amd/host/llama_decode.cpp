@@ -5,6 +5,7 @@
 #include "llama_decode.hpp"
 
 #include "../csrc/q4k.h"
+#include "../csrc/q5k.h"
 #include "../csrc/q6k.h"
 
 #include <cstdlib>
@@ -107,6 +108,17 @@ void synth_q4k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
     for (uint32_t i = 0; i < 140; i++) blk[4 + i] = (uint8_t)(mix32(s + 1 + i) >> 11);
 }
 
+// Q5_K super-block `sb` of weight `id` (csrc/q5k.h): Q4_K's header at half the d (q runs over 0..31), qh and qs hashed. |w| stays below
+// 0.2, mostly far below.
+void synth_q5k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
+    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0x27D4EB2Fu);
+    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -15) * ((s >> 3) & 1 ? -1.0f : 1.0f);
+    const float dmin = std::ldexp(1.0f + (float)((s >> 4) & 7) * 0.125f, -11) * ((s >> 7) & 1 ? -1.0f : 1.0f);
+    const uint16_t hd = f32_to_f16_bits(d), hm = f32_to_f16_bits(dmin);
+    blk[0] = (uint8_t)(hd & 0xFF), blk[1] = (uint8_t)(hd >> 8), blk[2] = (uint8_t)(hm & 0xFF), blk[3] = (uint8_t)(hm >> 8);
+    for (uint32_t i = 4; i < zgml::kQ5kBytes; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
+}
+
 // Q6_K super-block `sb` of weight `id` (csrc/q6k.h): d of both signs in the normal f16 range, ql, qh and the sixteen scale bytes
 // hashed, so the scales run over the whole int8 range and q over 0..63. |w| stays below 0.47, mostly far below.
 void synth_q6k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
@@ -116,7 +128,7 @@ void synth_q6k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
     for (uint32_t i = 0; i < zgml::kQ6kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
     blk[zgml::kQ6kDOffset] = (uint8_t)(hd & 0xFF), blk[zgml::kQ6kDOffset + 1] = (uint8_t)(hd >> 8);
 }
-// the Q4_K_M mix GGUF writers use: does weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) take Q6_K?
+// the Q4_K_M / Q5_K_M mix GGUF writers use: does weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) take Q6_K?
 bool q4_k_m_takes_q6k(size_t wi, uint32_t n_layers) {
     const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7), e = n_layers / 8;
     if (l >= n_layers) return true;        // output.weight
@@ -202,19 +214,20 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
         auto [n0, nl] = shard(cfg.vocab_size);
         m->qweights.push_back(make_qweight(d, cfg.vocab_size, n0, nl, cfg.n_layers * 8, kind, threads));
     }
-    const bool mix_model = kind == WeightKind::q4_k_m_gguf || kind == WeightKind::q4_k_m_dense;
+    const bool five = kind == WeightKind::q5_k_m_gguf || kind == WeightKind::q5_k_m_dense; // the base type of the mix: Q5_K, else Q4_K
+    const bool mix_model = kind == WeightKind::q4_k_m_gguf || kind == WeightKind::q4_k_m_dense || five;
     const bool sb_model = kind == WeightKind::q4_k_gguf || kind == WeightKind::q4_k_dense || mix_model;
-    if (sb_model) // N % 256 == 0: Q4_K (in the mix: or Q6_K) super-blocks of their own generators (the Q4_0 values are dropped); else Q4_0 file blocks below
+    if (sb_model) // N % 256 == 0: Q4_K / Q5_K (in the mixes: or Q6_K) super-blocks of their own generators (the Q4_0 values are dropped); else Q4_0 file blocks below
         for (size_t wi = 0; wi < m->qweights.size(); wi++) {
             auto& q = m->qweights[wi];
             if (q.N % zgml::kQ4kBlock) continue;
             const uint32_t id = (uint32_t)(wi / 7 * 8 + wi % 7);
             const bool six = mix_model && q4_k_m_takes_q6k(wi, cfg.n_layers);
             q.gguf_block = zgml::kQ4kBlock;
-            q.gguf_block_bytes = six ? zgml::kQ6kBytes : zgml::kQ4kBytes;
+            q.gguf_block_bytes = six ? zgml::kQ6kBytes : five ? zgml::kQ5kBytes : zgml::kQ4kBytes;
             q.gguf.resize(q.K * q.N / zgml::kQ4kBlock * q.gguf_block_bytes);
             parallel_rows(q.K * q.N / zgml::kQ4kBlock, threads, [&](size_t b0, size_t b1) {
-                for (size_t b = b0; b < b1; b++) (six ? synth_q6k_block : synth_q4k_block)(b, id, q.gguf.data() + b * q.gguf_block_bytes);
+                for (size_t b = b0; b < b1; b++) (six ? synth_q6k_block : five ? synth_q5k_block : synth_q4k_block)(b, id, q.gguf.data() + b * q.gguf_block_bytes);
             });
             std::vector<int8_t>().swap(q.data);
             std::vector<float>().swap(q.scales);
@@ -237,7 +250,7 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
             std::vector<float>().swap(q.scales);
         }
     }
-    if (kind == WeightKind::q4_k_dense || kind == WeightKind::q4_k_m_dense) { // the gguf twin, dequantised by the formats' own rules (csrc/q4k.h, q6k.h); file blocks dropped
+    if (kind == WeightKind::q4_k_dense || kind == WeightKind::q4_k_m_dense || kind == WeightKind::q5_k_m_dense) { // the gguf twin, dequantised by the formats' own rules (csrc/q4k.h, q5k.h, q6k.h); file blocks dropped
         for (auto& q : m->qweights) {
             std::vector<float> w(q.K * q.N);
             const uint8_t* g = q.gguf.data();
@@ -246,6 +259,8 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
                 for (size_t i = k0 * q.N; i < k1 * q.N; i++) {
                     if (sb && q.gguf_block_bytes == zgml::kQ6kBytes) {
                         w[i] = zgml::q6k_value(g + i / zgml::kQ6kBlock * zgml::kQ6kBytes, (uint32_t)(i % zgml::kQ6kBlock));
+                    } else if (sb && q.gguf_block_bytes == zgml::kQ5kBytes) {
+                        w[i] = zgml::q5k_value(g + i / zgml::kQ5kBlock * zgml::kQ5kBytes, (uint32_t)(i % zgml::kQ5kBlock));
                     } else if (sb) {
                         w[i] = zgml::q4k_value(g + i / zgml::kQ4kBlock * zgml::kQ4kBytes, (uint32_t)(i % zgml::kQ4kBlock));
                     } else { // Q4_0 block: f16 scale, element e in the low (e even) / high nibble of byte e / 2, value = nibble - 8

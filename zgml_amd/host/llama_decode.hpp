@@ -52,16 +52,19 @@ LlamaConfig tiny_test();                 // small GQA config for parity tests
 // q4_k_m_gguf: the Q4_K_M mix GGUF writers use: where N % 256 == 0 the untied LM head and the wv / w_down of layer i with
 //            i < L/8 || i >= 7L/8 || (i - L/8) % 3 == 2 are Q6_K super-blocks (210 B; csrc/q6k.h), everything else as q4_k_gguf
 // q4_k_m_dense: the q4_k_m_gguf model dequantised to f32 `matmul` weights
-enum class WeightKind : int { q4_0 = 0, q8_0 = 1, f32_dense = 2, q4_0_gguf = 3, q4_k_gguf = 4, q4_k_dense = 5, q4_k_m_gguf = 6, q4_k_m_dense = 7 };
-inline bool is_dense(WeightKind k) { return k == WeightKind::f32_dense || k == WeightKind::q4_k_dense || k == WeightKind::q4_k_m_dense; }
-inline bool is_gguf(WeightKind k) { return k == WeightKind::q4_0_gguf || k == WeightKind::q4_k_gguf || k == WeightKind::q4_k_m_gguf; }
+// q5_k_m_gguf / q5_k_m_dense: the Q5_K_M mix and its f32 twin: the same layout rule with Q5_K super-blocks (176 B; csrc/q5k.h) as the
+//            base type in place of Q4_K (another model again: its own generator)
+enum class WeightKind : int { q4_0 = 0, q8_0 = 1, f32_dense = 2, q4_0_gguf = 3, q4_k_gguf = 4, q4_k_dense = 5, q4_k_m_gguf = 6, q4_k_m_dense = 7,
+                              q5_k_m_gguf = 8, q5_k_m_dense = 9 };
+inline bool is_dense(WeightKind k) { return k == WeightKind::f32_dense || k == WeightKind::q4_k_dense || k == WeightKind::q4_k_m_dense || k == WeightKind::q5_k_m_dense; }
+inline bool is_gguf(WeightKind k) { return k == WeightKind::q4_0_gguf || k == WeightKind::q4_k_gguf || k == WeightKind::q4_k_m_gguf || k == WeightKind::q5_k_m_gguf; }
 
 struct QWeightHost {
     std::vector<int8_t> data;
     std::vector<float> scales;
-    std::vector<uint8_t> gguf; // q4_0_gguf / q4_k_gguf / q4_k_m_gguf: the file blocks (data / scales dropped)
-    uint32_t gguf_block = 32;  // ... their elements: 32 (Q4_0) or 256 (Q4_K, Q6_K)
-    uint32_t gguf_block_bytes = 18; // ... and their bytes, which say the form: 18 (Q4_0), 144 (Q4_K) or 210 (Q6_K)
+    std::vector<uint8_t> gguf; // q4_0_gguf / q4_k_gguf / q4_k_m_gguf / q5_k_m_gguf: the file blocks (data / scales dropped)
+    uint32_t gguf_block = 32;  // ... their elements: 32 (Q4_0) or 256 (Q4_K, Q5_K, Q6_K)
+    uint32_t gguf_block_bytes = 18; // ... and their bytes, which say the form: 18 (Q4_0), 144 (Q4_K), 176 (Q5_K) or 210 (Q6_K)
     size_t K = 0, N = 0; // rows, cols
 };
 
@@ -73,7 +76,7 @@ struct LlamaModel {
     std::vector<float> gamma_f;
     // per layer: q,k,v,o,gate,up,down; then (untied) the LM head
     std::vector<QWeightHost> qweights;
-    // kind == f32_dense / q4_k_dense / q4_k_m_dense: the same weights dequantised to f32 [K, N] (qweights keep only K and N)
+    // kind == f32_dense / q4_k_dense / q4_k_m_dense / q5_k_m_dense: the same weights dequantised to f32 [K, N] (qweights keep only K and N)
     std::vector<std::vector<float>> dense;
     std::vector<float> cos_table, sin_table; // [max_seq][d_head], RoPE.init src/nn.zig:286-311
     size_t lm_head_index() const { return (size_t)cfg.n_layers * 7; }

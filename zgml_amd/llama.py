@@ -16,6 +16,8 @@ Q4_0, Q8_0, F32_DENSE, Q4_0_GGUF = 0, 1, 2, 3
 Q4_K_GGUF, Q4_K_DENSE = 4, 5
 # the Q4_K_M mix: Q6_K super-blocks for the untied LM head and the wv / w_down of the "more bits" layers, Q4_K elsewhere; and its f32 twin
 Q4_K_M_GGUF, Q4_K_M_DENSE = 6, 7
+# the Q5_K_M mix: the same layout rule with Q5_K super-blocks as the base type; and its f32 twin
+Q5_K_M_GGUF, Q5_K_M_DENSE = 8, 9
 
 
 class Config(C.Structure):
