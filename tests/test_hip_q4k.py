@@ -1,4 +1,4 @@
-"""GGUF Q4_K weights on the MI355X (zgml_amd/csrc/q4k.hip) against float64 over the dequantised weights (tests/q4k_cases.py).
+"""GGUF Q4_K weights on the MI355X (zgml_amd/csrc/sb_kernels.hip) against float64 over the dequantised weights (tests/q4k_cases.py).
 Per output |y - ref| <= 2e-5 * sum_k |x[k]| * (|d sc q| + |dmin m|) + 1e-30: the project's mat-vec bound, its magnitude over BOTH
 terms (the kernels sum them apart, and they cancel in w)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""GGUF Q5_K weights on the MI355X (zgml_amd/csrc/q5k.hip) against float64 over the dequantised weights (tests/q5k_cases.py). Per output
+"""GGUF Q5_K weights on the MI355X (zgml_amd/csrc/sb_kernels.hip) against float64 over the dequantised weights (tests/q5k_cases.py). Per output
 |y - ref| <= 2e-5 * sum_k |x[k]| * (|d sc q| + |dmin m|) + 1e-30: Q4_K's bound, over BOTH terms (summed apart, they cancel in w)."""
 import numpy as np
 import pytest
@@ -15,7 +15,7 @@ F16_MAX = 65504.0  # w <= 63 * 32 d: every f16 keeps the f32 sums of these shape
 
 PINS = {None: {}, "max": dict(d=F16_MAX, dmin=-F16_MAX, scale_byte=0xFF, ql_byte=0xFF, qh_byte=0xFF),
         "high only": dict(ql_byte=0, qh_byte=0xFF), "zero": dict(scale_byte=0)}
-# M = 1 (kS5Round = 256 k, kS5Sweep = 64, kS5MaxParts = 16): one column block and one k; K odd, below a sweep; K one past a one-round
+# M = 1 (kSbRound = 256 k, kSbSweep = 64, kSbRoundMaxParts = 16): one column block and one k; K odd, below a sweep; K one past a one-round
 # share (two parts, the last of one k); 16 rounds over two column blocks (16 parts of one round: the cap); three column blocks, K no
 # multiple of the sweep; K one past 16 rounds (the cap makes parts of two rounds). M > 1 (row tile 16, two per workgroup over M = 16;
 # chunk 64 k dealt to 8 waves): K of 1.5 chunks; K no multiple of 8 over two column blocks (16 chunks: two per wave); strides and

@@ -1,4 +1,4 @@
-"""GGUF Q6_K weights on the MI355X (zgml_amd/csrc/q6k.hip) against float64 over the dequantised weights (tests/q6k_cases.py).
+"""GGUF Q6_K weights on the MI355X (zgml_amd/csrc/sb_kernels.hip) against float64 over the dequantised weights (tests/q6k_cases.py).
 Per output |y - ref| <= 2e-5 * sum_k |x[k]| |w[k, n]| + 1e-30: the project's mat-vec bound as it is, which is zero where w is."""
 import numpy as np
 import pytest

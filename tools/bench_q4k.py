@@ -1,4 +1,4 @@
-"""GGUF Q4_K (q4k.hip), Q5_K (q5k.hip) and Q6_K (q6k.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes
+"""GGUF Q4_K, Q5_K and Q6_K (sb_kernels.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes
 kernel and the M = 32 matmul against the tile kernel, at 4096^2, 4096 x 11008 and 4096 x 32000. Q4_0 and Q4_K stream 4.5 bit/weight,
 so their bytes per launch are equal and the times compare directly; Q5_K streams 176/144 and Q6_K 210/144 of that, so the GB/s are printed too. A ring of distinct matrices larger than the 256 MiB Infinity Cache
 stands for a model; device-event time per launch over replays of a captured graph (zgml_hip_qmatmul_bench); the formats

@@ -201,18 +201,40 @@ enum QWFormat : uint32_t {
     QW_Q8 = 2,  // packed int8, lane-tiled
     QW_Q4K = 3, // packed offset-binary nibbles, K ON LANES (qmatvec.hip: qmatvec_kon_body): M = 1 mat-vecs (and, opt-in, 2 <= M <= 8: qmatvec_rows.hip), f16 scales
     QW_W8A8 = 4, // the reference's W8A8 arm (w8a8.hip): re-quantised transposed int8 + f32 scale per (column, 32 k); M = 1 only, opt-in
-    // GGUF Q4_K ("super-block 4-bit", q4k.hip): 16-byte items of one sub-block column at one k + the file's 16-byte headers; any M, its
-    // own launcher, never fused, grouped or sharded. NOT QW_Q4K above, which is Q4_0 with K on lanes and has nothing to do with Q4_K.
+    // GGUF Q4_K / Q6_K / Q5_K ("super-block 4 / 6 / 5-bit", sb_kernels.h): 16-byte items of 32 columns at one k, a plane of 8- / 4-byte
+    // high bits beside them (Q6_K / Q5_K), and the file's headers (Q6_K: int8 scales and f16 d) per (k, 256 columns); any M, their own
+    // launcher, never fused, grouped or sharded. QW_SB4 is NOT QW_Q4K above, which is Q4_0 with K on lanes and has nothing to do
+    // with Q4_K.
     QW_SB4 = 5,
-    // GGUF Q6_K ("super-block 6-bit", q6k.hip): 16 + 8-byte items of 32 columns at one k in two planes + the file's 16 int8 scales and f16 d
-    // per (k, 256 columns) in planes of their own; launched as QW_SB4 is
     QW_SB6 = 6,
-    // GGUF Q5_K ("super-block 5-bit", q5k.hip): 16 + 4-byte items of 32 columns at one k in two planes + the file's 16-byte headers per
-    // (k, 256 columns); launched as QW_SB4 is
     QW_SB5 = 7,
 };
-// the GGUF super-block formats: plain launches of their own kernels for every M
-inline bool qw_super_block(QWFormat f) { return f == QW_SB4 || f == QW_SB6 || f == QW_SB5; }
+// the GGUF super-block formats: plain launches of their own kernels for every M. What the callers need to know of each, once: the
+// pass-through form number (runtime.hip: gguf_form), the bytes of a 256-element file block, the code of the measurement entry
+// points (runtime_bench.hip) and the launch tags of the plan
+struct SbFormatRow {
+    QWFormat format;
+    int form;
+    uint32_t block_bytes;
+    int bench_code;
+    const char *matvec_tag, *matmul_tag;
+};
+constexpr SbFormatRow kSbFormats[] = {
+    {QW_SB4, 3, ZGML_QW_GGUF_Q4_K_BLOCK_BYTES, 2, "q4k-matvec", "q4k-matmul"},
+    {QW_SB6, 4, ZGML_QW_GGUF_Q6_K_BLOCK_BYTES, 3, "q6k-matvec", "q6k-matmul"},
+    {QW_SB5, 5, ZGML_QW_GGUF_Q5_K_BLOCK_BYTES, 4, "q5k-matvec", "q5k-matmul"},
+};
+// the row with pick(row) true, or nullptr
+template <class Pick>
+inline const SbFormatRow* sb_format_row(Pick pick) {
+    for (const SbFormatRow& row : kSbFormats)
+        if (pick(row)) return &row;
+    return nullptr;
+}
+inline const SbFormatRow* sb_format_row(QWFormat f) {
+    return sb_format_row([f](const SbFormatRow& row) { return row.format == f; });
+}
+inline bool qw_super_block(QWFormat f) { return sb_format_row(f) != nullptr; }
 
 struct QWeightDev {
     QWFormat format = QW_RAW;
@@ -754,29 +776,17 @@ bool w8a8_applies(uint64_t K, uint64_t N, uint64_t bs);
 void w8a8_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
 void launch_pack_w8a8(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);
 void launch_w8a8_matvec(hipStream_t s, const QWeightDev& w, const float* x, float* dst);
-// GGUF Q4_K arm (q4k.hip; format: q4k.h): shapes it takes (N a multiple of 256), sizes of its packed image (4.5 bit/weight), the
-// device re-pack of the file's 144-byte super-blocks, the scratch an M = 1 launch splits K through (the same block and counter
-// head as qmatmul_scratch_bytes describes below) and the launch for any M (M = 1: the streaming mat-vec, M > 1: bf16 matrix cores)
-bool sb4_applies(uint64_t K, uint64_t N);
-void sb4_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
-void launch_pack_sb4(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
-void launch_synth_sb4(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
-uint64_t sb4_scratch_bytes(const QWeightDev& w, uint32_t M);
-void launch_sb4_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
-// GGUF Q6_K arm (q6k.hip; format: q6k.h): the same set for the 210-byte super-blocks (6.5625 bit/weight packed)
-bool sb6_applies(uint64_t K, uint64_t N);
-void sb6_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
-void launch_pack_sb6(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
-void launch_synth_sb6(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
-uint64_t sb6_scratch_bytes(const QWeightDev& w, uint32_t M);
-void launch_sb6_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
-// GGUF Q5_K arm (q5k.hip; format: q5k.h): the same set for the 176-byte super-blocks (5.5 bit/weight packed)
-bool sb5_applies(uint64_t K, uint64_t N);
-void sb5_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
-void launch_pack_sb5(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
-void launch_synth_sb5(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
-uint64_t sb5_scratch_bytes(const QWeightDev& w, uint32_t M);
-void launch_sb5_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
+// GGUF super-block arm (Q4_K / Q5_K / Q6_K: sb_kernels.hip; formats: q4k.h, q5k.h, q6k.h): shapes it takes (N a multiple of 256, the
+// same set for all three), sizes of a format's packed image (4.5 / 5.5 / 6.5625 bit/weight like the file), the device re-pack of
+// the file's super-blocks and the micro-benchmark's synthetic weights (out.format / w.format selects which), the scratch an M = 1
+// launch splits K through (the same block and counter head as qmatmul_scratch_bytes describes below) and the launch for any M
+// (M = 1: the streaming mat-vec, M > 1: bf16 matrix cores)
+bool sb_applies(uint64_t K, uint64_t N);
+void sb_packed_bytes(QWFormat format, uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
+void launch_pack_sb(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
+void launch_synth_sb(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
+uint64_t sb_scratch_bytes(const QWeightDev& w, uint32_t M);
+void launch_sb_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
 void packed_bytes(QWFormat format, uint32_t scale_f16, uint64_t K, uint64_t N, uint64_t* qs_bytes,
                   uint64_t* sc_bytes);
 void launch_pack_qweight(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);

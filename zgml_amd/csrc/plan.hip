@@ -256,9 +256,7 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                 p->split_pos = pos - 1; // the merged launch still sits at the previous plan position
                 return false;
             }
-            if (w.format == QW_SB4) L.tag = qp.M == 1 ? "q4k-matvec" : "q4k-matmul";
-            if (w.format == QW_SB6) L.tag = qp.M == 1 ? "q6k-matvec" : "q6k-matmul";
-            if (w.format == QW_SB5) L.tag = qp.M == 1 ? "q5k-matvec" : "q5k-matmul";
+            if (const SbFormatRow* sb = sb_format_row(w.format)) L.tag = qp.M == 1 ? sb->matvec_tag : sb->matmul_tag;
             if (w.format == QW_Q4K && qp.M >= 2 && qp.M <= p->kon_max_m) L.tag = "qmatvec-kon-rows"; // (launch_qmatmul: the multi-row K-on-lanes mat-vec)
             auto group = std::make_shared<std::vector<std::pair<QWeightDev, QMatmulParams>>>();
             group->push_back({w, qp});

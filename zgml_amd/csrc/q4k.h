@@ -5,7 +5,7 @@
 //   64 i + 32 + l the high nibble (i = 0..3, l = 0..31)
 //   w = (d * sc_j) * q - (dmin * m_j),   q the nibble itself in 0..15
 // d * sc_j and dmin * m_j are products of an f16 and a 6-bit integer: exact in f32, in general not representable in f16. The
-// device kernels (q4k.hip) never form w: they sum (x * d * sc_j) * q and x * dmin * m_j apart, the second once per 32 columns.
+// device kernels (sb_kernels.hip) never form w: they sum (x * d * sc_j) * q and x * dmin * m_j apart, the second once per 32 columns.
 // Plain C++ besides the host / device marks, so the host model builder (host/llama_decode.cpp) compiles it too.
 #pragma once
 #include <stdint.h>

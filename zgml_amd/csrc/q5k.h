@@ -5,7 +5,7 @@
 //   element e = 32 j + l (j in 0..7, l in 0..31):
 //     nibble = (qs[32 (j >> 1) + l] >> 4 (j & 1)) & 15 (Q4_K's rule),  high bit = (qh[l] >> j) & 1,
 //     q = nibble | high << 4 in 0..31,   w = (d * sc_j) * q - dmin * m_j
-// d * sc_j and dmin * m_j are exact in f32 (q4k.h). The device kernels (q5k.hip) never form w: they sum (x * d * sc_j) * q and
+// d * sc_j and dmin * m_j are exact in f32 (q4k.h). The device kernels (sb_kernels.hip) never form w: they sum (x * d * sc_j) * q and
 // x * dmin * m_j apart, the second once per 32 columns, as Q4_K's do.
 // Plain C++ besides the host / device marks, so the host model builder (host/llama_decode.cpp) compiles it too.
 #pragma once

@@ -5,7 +5,7 @@
 //     low nibble = (ql[64 h + 32 (g & 1) + l] >> 4 (g >> 1)) & 15,  high bits = (qh[32 h + l] >> 2 g) & 3,
 //     q = low | high << 4 in 0..63,   w = (d * scales[e >> 4]) * (q - 32)
 // d * scale is an f16 times an int8: exact in f32. q - 32 is an exact small integer in f32 and in bf16, so w in f32 carries one
-// rounding. The -32 is NOT part of a second sum (as Q4_K's min is): the device kernels (q6k.hip) multiply by the signed integer.
+// rounding. The -32 is NOT part of a second sum (as Q4_K's min is): the device kernels (sb_kernels.hip) multiply by the signed integer.
 // Plain C++ besides the host / device marks, so the host model builder (host/llama_decode.cpp) compiles it too.
 #pragma once
 #include "q4k.h" // q4k_f16: every f16 to f32, exactly

@@ -951,9 +951,7 @@ static uint64_t xdl5_partial_bytes(uint32_t M) {
     return (uint64_t)xdl5_wgs() * 2 * kX5Waves * (2 * xdl_tile_pad(M) * 256) * sizeof(float);
 }
 uint64_t qmatmul_scratch_bytes(const QWeightDev& w, uint32_t M) {
-    if (w.format == QW_SB4) return sb4_scratch_bytes(w, M);
-    if (w.format == QW_SB6) return sb6_scratch_bytes(w, M);
-    if (w.format == QW_SB5) return sb5_scratch_bytes(w, M);
+    if (qw_super_block(w.format)) return sb_scratch_bytes(w, M);
     if (!xdl2_applies(w, M)) return 0;
     return xdl_a_bytes(w, M) + std::max((uint64_t)kMaxQmmParts * xdl4_partial_bytes(w, M), xdl5_partial_bytes(M));
 }
@@ -1179,16 +1177,8 @@ void launch_qmatmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, 
         launch_w8a8_matvec(s, w, p.input, p.dst);
         return;
     }
-    if (w.format == QW_SB4) { // GGUF Q4_K: its own kernels for every M (q4k.hip)
-        launch_sb4_matmul(s, w, p, scratch);
-        return;
-    }
-    if (w.format == QW_SB6) { // GGUF Q6_K: likewise (q6k.hip)
-        launch_sb6_matmul(s, w, p, scratch);
-        return;
-    }
-    if (w.format == QW_SB5) { // GGUF Q5_K: likewise (q5k.hip)
-        launch_sb5_matmul(s, w, p, scratch);
+    if (qw_super_block(w.format)) { // GGUF Q4_K / Q5_K / Q6_K: their own kernels for every M (sb_kernels.hip)
+        launch_sb_matmul(s, w, p, scratch);
         return;
     }
     if (w.format == QW_Q4K && p.M != 1) { // compile_program only gives this layout to weights every use of which has M = 1 (M <= 8 under ZGML_HIP_OPT_SMALL_M_MATVEC)

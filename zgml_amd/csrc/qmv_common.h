@@ -67,6 +67,20 @@ __device__ __forceinline__ uint4 wload(const uint4* p) {
     }
     return *p;
 }
+// ... and the 8- and 4-byte forms (the high planes of the super-block formats, sb_kernels.h)
+template <bool NT>
+__device__ __forceinline__ uint2 wload2(const uint2* p) {
+    if (NT) {
+        typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+        const u2v v = __builtin_nontemporal_load((const u2v*)p);
+        return make_uint2(v.x, v.y);
+    }
+    return *p;
+}
+template <bool NT>
+__device__ __forceinline__ uint32_t wload1(const uint32_t* p) {
+    return NT ? __builtin_nontemporal_load(p) : *p;
+}
 
 // ── inline-asm helpers ──────────────────────────────────────────────────────────────────────
 // The per-weight work is two VALU instructions: an SDWA convert (nibble or byte -> f32) and a

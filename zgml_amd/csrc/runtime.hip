@@ -47,15 +47,15 @@ void fill_caps(zgml_capabilities* c) {
 }
 
 // packed-GGUF pass-through (include/zgml_hip.h): 0 = reference form, 1 = Q4_0 blocks, 2 = Q8_0 blocks, 3 = Q4_K, 4 = Q6_K and 5 = Q5_K
-// super-blocks (block_size tells Q4_K from Q4_0: 144 B per 256 elements and 18 B per 32 are the same data_len; data_len tells
-// the three super-block types apart: 144 / 176 / 210 B per 256 elements)
+// super-blocks (kSbFormats; block_size tells Q4_K from Q4_0: 144 B per 256 elements and 18 B per 32 are the same data_len; data_len
+// tells the three super-block types apart: 144 / 176 / 210 B per 256 elements)
 int gguf_form(const zgml_qweight_upload& qw) {
     if (qw.scales || qw.scales_len || !qw.data) return 0;
     const uint64_t n = qw.rows * qw.cols;
     if (qw.block_size == 256) {
-        if (!sb4_applies(qw.rows, qw.cols)) return 0; // (sb5_applies and sb6_applies are the same set)
-        return qw.data_len == n / 256 * ZGML_QW_GGUF_Q4_K_BLOCK_BYTES ? 3 : qw.data_len == n / 256 * ZGML_QW_GGUF_Q6_K_BLOCK_BYTES ? 4 :
-               qw.data_len == n / 256 * ZGML_QW_GGUF_Q5_K_BLOCK_BYTES ? 5 : 0;
+        if (!sb_applies(qw.rows, qw.cols)) return 0;
+        const SbFormatRow* row = sb_format_row([&](const SbFormatRow& f) { return qw.data_len == n / 256 * f.block_bytes; });
+        return row ? row->form : 0;
     }
     if (qw.block_size != 32) return 0;
     if (!n || n % 32 || qw.cols % 32 || !qweight_packable(qw.rows, qw.cols, 32)) return 0;
@@ -927,14 +927,15 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
         const uint64_t n_elems = qw.rows * qw.cols;
         const uint64_t n_blocks = (n_elems + qw.block_size - 1) / qw.block_size;
         if (const int form = gguf_form(qw)) { // file blocks straight to the device, unpacked + re-packed there
-            w.format = form == 1 ? QW_Q4 : form == 2 ? QW_Q8 : form == 3 ? QW_SB4 : form == 4 ? QW_SB6 : QW_SB5;
+            const SbFormatRow* sb = sb_format_row([&](const SbFormatRow& f) { return f.form == form; });
+            w.format = form == 1 ? QW_Q4 : form == 2 ? QW_Q8 : sb->format;
             w.scale_f16 = 1;
             pending[i].gguf = true;
             ok = CTX_CHECK(ctx, hipMalloc(&pending[i].raw_a, qw.data_len)) &&
                  CTX_CHECK(ctx, hipMemcpyAsync(pending[i].raw_a, qw.data, qw.data_len, hipMemcpyHostToDevice, ctx->stream));
-            if (ok && form >= 3) { // Q4_K / Q6_K / Q5_K: their own layouts and launchers (q4k.hip, q6k.hip, q5k.hip), whatever M their ops have
+            if (ok && sb) { // Q4_K / Q6_K / Q5_K: their own layouts and launchers (sb_kernels.hip), whatever M their ops have
                 w.KC = (uint32_t)((qw.rows + 31) / 32);
-                (form == 3 ? sb4_packed_bytes : form == 4 ? sb6_packed_bytes : sb5_packed_bytes)(qw.rows, qw.cols, &w.qs_bytes, &w.sc_bytes);
+                sb_packed_bytes(w.format, qw.rows, qw.cols, &w.qs_bytes, &w.sc_bytes);
                 qs_total += w.qs_bytes + 15, sc_total += w.sc_bytes + 15; // (its items and headers are read as dwordx4: room to align them)
                 continue;
             }
@@ -993,12 +994,8 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
                 p->owned.push_back(w.qs);
                 p->owned.push_back(w.sc);
             }
-            if (w.format == QW_SB4)
-                launch_pack_sb4(ctx->stream, (const uint8_t*)pending[i].raw_a, w);
-            else if (w.format == QW_SB6)
-                launch_pack_sb6(ctx->stream, (const uint8_t*)pending[i].raw_a, w);
-            else if (w.format == QW_SB5)
-                launch_pack_sb5(ctx->stream, (const uint8_t*)pending[i].raw_a, w);
+            if (qw_super_block(w.format))
+                launch_pack_sb(ctx->stream, (const uint8_t*)pending[i].raw_a, w);
             else if (pending[i].gguf)
                 launch_pack_gguf(ctx->stream, (const uint8_t*)pending[i].raw_a, w);
             else if (w.format == QW_W8A8)

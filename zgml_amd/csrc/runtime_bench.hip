@@ -5,14 +5,14 @@
 
 extern "C" {
 
-// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K (q4k.hip), 3 = GGUF Q6_K (q6k.hip), 4 = GGUF Q5_K (q5k.hip)
+// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K, 3 = GGUF Q6_K, 4 = GGUF Q5_K (kSbFormats' bench codes; sb_kernels.hip)
 static bool make_synth_weight(zgml_hip_ctx* ctx, uint32_t K, uint32_t N, int q4, uint32_t id, QWeightDev* w, uint32_t M = 1) {
-    if (q4 >= 2 && q4 <= 4) {
-        if (!sb4_applies(K, N)) return false;
-        w->format = q4 == 2 ? QW_SB4 : q4 == 3 ? QW_SB6 : QW_SB5, w->K = K, w->N = N, w->bs = 256, w->KC = (K + 31) / 32, w->scale_f16 = 1;
-        (q4 == 2 ? sb4_packed_bytes : q4 == 3 ? sb6_packed_bytes : sb5_packed_bytes)(K, N, &w->qs_bytes, &w->sc_bytes);
+    if (const SbFormatRow* sb = sb_format_row([&](const SbFormatRow& f) { return f.bench_code == q4; })) {
+        if (!sb_applies(K, N)) return false;
+        w->format = sb->format, w->K = K, w->N = N, w->bs = 256, w->KC = (K + 31) / 32, w->scale_f16 = 1;
+        sb_packed_bytes(w->format, K, N, &w->qs_bytes, &w->sc_bytes);
         if (!CTX_CHECK(ctx, hipMalloc(&w->qs, w->qs_bytes)) || !CTX_CHECK(ctx, hipMalloc(&w->sc, w->sc_bytes))) return false;
-        (q4 == 2 ? launch_synth_sb4 : q4 == 3 ? launch_synth_sb6 : launch_synth_sb5)(ctx->stream, *w, id);
+        launch_synth_sb(ctx->stream, *w, id);
         return true;
     }
     w->format = q4 ?(M == 1 && sw().hip_qmv_kon ? QW_Q4K : QW_Q4) : QW_Q8; // (what compile_program picks for a weight that only feeds mat-vecs)

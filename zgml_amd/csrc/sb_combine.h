@@ -1,4 +1,4 @@
-// sb_combine.h — the K-split fan-in of the super-block mat-vecs (q4k.hip, q6k.hip): every part of one super-block column stores
+// sb_combine.h — the K-split fan-in of the super-block mat-vecs (sb_kernels.hip): every part of one super-block column stores
 // its partial outputs, counts itself on an integer word in the scratch head, and the LAST part to arrive adds the partials in
 // PART order (not arrival order; no float atomics), so two launches give the same bytes. The word is re-armed for the next launch.
 #pragma once
