@@ -272,11 +272,20 @@ typedef struct zgml_program_io {
  *     data_len == rows*cols/256 * 176 -> Q5_K {f16 d, f16 dmin, scales[12] as Q4_K, qh[32], qs[128]}, the bulk type of a Q5_K_M / Q5_K_S
  *                                        file: element 32j+l has the nibble (qs[32(j>>1)+l] >> 4(j&1)) & 15 and the high bit
  *                                        (qh[l] >> j) & 1; value = (d*sc_j)*q - dmin*m_j (zgml_amd/csrc/q5k.h states it)
- * Under block_size 256 `data_len` tells the three apart (144 / 176 / 210); the same shape rule holds, and Q6_K stays 6.5625 and
- * Q5_K 5.5 bit/weight on the device with kernels of their own, launched as Q4_K is. A file block is only 2-byte aligned; `data`
- * needs no more than that. */
+ *     data_len == rows*cols/256 * 110 -> Q3_K {hmask[32], qs[64], scales[12], f16 d}, the bulk type of a Q3_K_S / _M / _L file:
+ *                                        element e has the low bits (qs[32(e>>7)+(e&31)] >> 2((e>>5)&3)) & 3 and the high bit
+ *                                        (hmask[e&31] >> (e>>5)) & 1, q = low + 4 high - 4; sub-block s = e/16 has the 6-bit scale
+ *                                        (s < 8 ? scales[s] & 15 : scales[s-8] >> 4) | ((scales[8+(s&3)] >> 2(s>>2)) & 3) << 4;
+ *                                        value = d*(sc_s-32)*q (zgml_amd/csrc/q3k.h states it)
+ *     data_len == rows*cols/256 * 84  -> Q2_K {scales[16], qs[64], f16 d, f16 dmin}, the bulk type of a Q2_K file: q is Q3_K's low
+ *                                        rule, value = d*(scales[e/16] & 15)*q - dmin*(scales[e/16] >> 4) (zgml_amd/csrc/q2k.h)
+ * Under block_size 256 `data_len` tells the five apart (84 / 110 / 144 / 176 / 210: for one block count no two coincide); the same
+ * shape rule holds, and each type keeps the file's bits per weight on the device (Q6_K 6.5625, Q5_K 5.5, Q3_K 3.4375, Q2_K 2.625)
+ * with kernels of its own, launched as Q4_K is. A file block is only 2-byte aligned; `data` needs no more than that. */
 #define ZGML_QW_GGUF_Q4_0_BLOCK_BYTES 18
 #define ZGML_QW_GGUF_Q8_0_BLOCK_BYTES 34
+#define ZGML_QW_GGUF_Q2_K_BLOCK_BYTES 84
+#define ZGML_QW_GGUF_Q3_K_BLOCK_BYTES 110
 #define ZGML_QW_GGUF_Q4_K_BLOCK_BYTES 144
 #define ZGML_QW_GGUF_Q5_K_BLOCK_BYTES 176
 #define ZGML_QW_GGUF_Q6_K_BLOCK_BYTES 210

@@ -46,9 +46,9 @@ void fill_caps(zgml_capabilities* c) {
     c->attention_max_d_head = 512;
 }
 
-// packed-GGUF pass-through (include/zgml_hip.h): 0 = reference form, 1 = Q4_0 blocks, 2 = Q8_0 blocks, 3 = Q4_K, 4 = Q6_K and 5 = Q5_K
-// super-blocks (kSbFormats; block_size tells Q4_K from Q4_0: 144 B per 256 elements and 18 B per 32 are the same data_len; data_len
-// tells the three super-block types apart: 144 / 176 / 210 B per 256 elements)
+// packed-GGUF pass-through (include/zgml_hip.h): 0 = reference form, 1 = Q4_0 blocks, 2 = Q8_0 blocks, 3 = Q4_K, 4 = Q6_K, 5 = Q5_K,
+// 6 = Q3_K and 7 = Q2_K super-blocks (kSbFormats; block_size tells Q4_K from Q4_0: 144 B per 256 elements and 18 B per 32 are the same
+// data_len; data_len tells the five super-block types apart: 84 / 110 / 144 / 176 / 210 B per 256 elements)
 int gguf_form(const zgml_qweight_upload& qw) {
     if (qw.scales || qw.scales_len || !qw.data) return 0;
     const uint64_t n = qw.rows * qw.cols;
@@ -933,10 +933,10 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
             pending[i].gguf = true;
             ok = CTX_CHECK(ctx, hipMalloc(&pending[i].raw_a, qw.data_len)) &&
                  CTX_CHECK(ctx, hipMemcpyAsync(pending[i].raw_a, qw.data, qw.data_len, hipMemcpyHostToDevice, ctx->stream));
-            if (ok && sb) { // Q4_K / Q6_K / Q5_K: their own layouts and launchers (sb_kernels.hip), whatever M their ops have
+            if (ok && sb) { // the super-block types: their own layouts and launchers (sb_kernels.hip), whatever M their ops have
                 w.KC = (uint32_t)((qw.rows + 31) / 32);
                 sb_packed_bytes(w.format, qw.rows, qw.cols, &w.qs_bytes, &w.sc_bytes);
-                qs_total += w.qs_bytes + 15, sc_total += w.sc_bytes + 15; // (its items and headers are read as dwordx4: room to align them)
+                qs_total += w.qs_bytes + 15, sc_total += w.sc_bytes + 15; // (its items and headers are read as up to dwordx4: room to align them)
                 continue;
             }
         } else {

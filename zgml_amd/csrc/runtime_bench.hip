@@ -5,7 +5,7 @@
 
 extern "C" {
 
-// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K, 3 = GGUF Q6_K, 4 = GGUF Q5_K (kSbFormats' bench codes; sb_kernels.hip)
+// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K, 3 = GGUF Q6_K, 4 = GGUF Q5_K, 5 = GGUF Q3_K, 6 = GGUF Q2_K (kSbFormats' bench codes; sb_kernels.hip)
 static bool make_synth_weight(zgml_hip_ctx* ctx, uint32_t K, uint32_t N, int q4, uint32_t id, QWeightDev* w, uint32_t M = 1) {
     if (const SbFormatRow* sb = sb_format_row([&](const SbFormatRow& f) { return f.bench_code == q4; })) {
         if (!sb_applies(K, N)) return false;
@@ -152,7 +152,8 @@ double zgml_hip_qmatmul_bench(zgml_hip_ctx* ctx, uint32_t M, uint32_t K, uint32_
         if (ge) hipGraphExecDestroy(ge);
         if (g) hipGraphDestroy(g);
     }
-    if (bytes_per_launch) *bytes_per_launch = (q4 >= 3 ? (uint64_t)K * N / 256 * (q4 == 3 ? 210 : 176) : (uint64_t)K * N / 32 * (q4 ? 18 : 34)) + 4ull * M * K + 4ull * M * N;
+    const SbFormatRow* row = sb_format_row([&](const SbFormatRow& f) { return f.bench_code == q4; });
+    if (bytes_per_launch) *bytes_per_launch = (row ? (uint64_t)K * N / 256 * row->block_bytes : (uint64_t)K * N / 32 * (q4 ? 18 : 34)) + 4ull * M * K + 4ull * M * N;
     for (auto& w : ring) {
         hipFree(w.qs);
         hipFree(w.sc);

@@ -1,26 +1,32 @@
-// sb_kernels.h — the GGUF super-block weights on the device (QW_SB4 / QW_SB5 / QW_SB6 = Q4_K / Q5_K / Q6_K; q4k.h, q5k.h and
-// q6k.h state the file formats): what each format states, once, and the device functions every super-block kernel is built
-// from. The kernels and their launchers are sb_kernels.hip.
+// sb_kernels.h — the GGUF super-block weights on the device (QW_SB4 / QW_SB5 / QW_SB6 / QW_SB3 / QW_SB2 = Q4_K / Q5_K / Q6_K / Q3_K /
+// Q2_K; q4k.h, q5k.h, q6k.h, q3k.h and q2k.h state the file formats): what each format states, once, and the device functions every
+// super-block kernel is built from. The kernels and their launchers are sb_kernels.hip.
 //
 // COMMON DEVICE LAYOUT. A weight is cut into ITEMS [N / 32][K]: item (j, k) holds the 32 q of columns 32 j .. 32 j + 31 at row k,
 // so 64 consecutive k of one j are contiguous and a wave (lane = k) streams them coalesced. QWeightDev::qs holds the item planes:
 //   lo plane, 16 B per item: byte b = low nibble of column b | low nibble of column b + 16 << 4
 //   hi plane (Q5_K: 4 B, Q6_K: 8 B per item; Q4_K: none): the bits above the nibble, laid out so that the four q of columns
 //   16 h + 4 s .. + 3 (h = 0..1, s = 0..3) come out as ONE dword of bytes by a shift, a mask and an OR (sb_quants)
+// Q3_K / Q2_K have a 2-BIT low plane instead, 8 B per item: dword h = columns 16 h .. + 15, bits 2 s .. 2 s + 1 of byte b = column
+// 16 h + 4 s + b (Q6_K's high-pair layout), so the four q of a dword come out by one shift and one AND; Q3_K's third bit is a
+// 4-byte high plane in Q5_K's layout (sb_quants2).
 // QWeightDev::sc holds the FACTOR planes [N / 256][K], one entry per (k, super-block column): Q4_K / Q5_K the file's 16-byte header
-// {d, dmin, scales[12]} as it is (Q4kHeader dwords); Q6_K the file's 16 int8 scales (16 B), then a plane of its f16 d (2 B).
+// {d, dmin, scales[12]} as it is (Q4kHeader dwords); Q6_K the file's 16 int8 scales (16 B), then a plane of its f16 d (2 B); Q3_K
+// the file's twelve scale bytes as they are (12 B), then a plane of d; Q2_K the file's 16 scale bytes, then a plane of d | dmin << 16.
 //
 // ARITHMETIC. y[n] = sum_k (x[k] * d * sc) * (q - bias)  [ -  sum_k x[k] * dmin * m ]. d * sc and dmin * m are formed in f32
 // (exact), never rounded to f16. Q4_K / Q5_K: one (d * sc, dmin * m) pair per item, bias 0, the min sum kept apart and formed once
 // per 32 columns. Q6_K: two d * sc per item (one per 16 columns), the signed integer q - 32 as the operand (a weight of q = 32
-// contributes an exact zero) and nothing summed apart.
+// contributes an exact zero) and nothing summed apart. Q3_K: as Q6_K with q - 4 and d * (sc - 32). Q2_K: two (d * sc, dmin * m)
+// pairs per item, bias 0, and TWO min sums per item, one per 16 columns.
 //
-// A FORMAT (Sb4, Sb5, Sb6 below) is a plain struct of constants and static functions, no more: the file block bytes, its planes
+// A FORMAT (Sb4, Sb5, Sb6, Sb3, Sb2 below) is a plain struct of constants and static functions, no more: the file block bytes, its planes
 // and how qs / sc are cut into them, the high-plane load, quants(), how many d * sc an item has, whether a min sum exists, the
 // operand bias, where its factors come from (per 64-k chunk for M > 1, per 256-k round for M = 1), its pack rule, its synth
 // pattern and its name. Everything else here is shared: the lane fold, the M = 1 tail through sb_combine, byte -> f32 / bf16 with
 // the bias, the three-piece bf16 split, the [column][k] turn and the wave-order fold and store.
 #pragma once
+#include "q2k.h"
 #include "q5k.h"
 #include "q6k.h"
 #include "sb_combine.h"
@@ -35,6 +41,7 @@ constexpr uint32_t kSbSweep = 64;  // k per wave sweep (one per lane)
 constexpr uint32_t kSbSweeps = 4;  // sweeps of a round (Q5_K, Q6_K): all loaded before the first is consumed
 constexpr uint32_t kSbRound = kSbSweep * kSbSweeps; // k of a round = rows of the factors in LDS
 static_assert(kQ4kBlock == kSbBlock && kQ5kBlock == kSbBlock && kQ6kBlock == kSbBlock && kQ4kSub == kSbItem && kQ5kSub == kSbItem && 2 * kQ6kSub == kSbItem, "");
+static_assert(kQ3kBlock == kSbBlock && kQ2kBlock == kSbBlock && 2 * kQ3kSub == kSbItem && 2 * kQ2kSub == kSbItem, "");
 static_assert(kSbWaves * kSbItem == kSbBlock && kSbWaves * 64 == 2 * kSbRound, "the factor duty of a round: one k and half of its factors per thread");
 
 typedef float sb_f4 __attribute__((ext_vector_type(4)));
@@ -57,6 +64,18 @@ __device__ __forceinline__ void sb_quants(uint4 lo, uint32_t hi0, uint32_t hi1, 
         }
     }
 }
+// the 2-bit low plane: the same eight dwords from 8 bytes. dword 4 h + s = (lo_h >> 2 s) & 3 per byte; HIGH: bit 4 h + s of byte b of
+// `hi` is the third bit of column 16 h + 4 s + b, moved to bit 2 by one shift and taken in by one AND-OR. 14 (+ 16) VALU per item
+template <bool HIGH>
+__device__ __forceinline__ void sb_quants2(uint2 lo, uint32_t hi, uint32_t (&q)[8]) {
+    const uint32_t l[2] = {lo.x, lo.y};
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        q[d] = (l[d >> 2] >> (2 * (d & 3))) & 0x03030303u;
+        if constexpr (HIGH) q[d] |= (d >= 2 ? hi >> (d - 2) : hi << (2 - d)) & 0x04040404u;
+        asm("" : "+v"(q[d])); // keep the dword of four bytes: left to itself hipcc takes every 2-bit field out of `lo` on its own (one v_bfe per weight)
+    }
+}
 // the Q4_K / Q5_K header of one (k, super-block column) -> (d * sc, dmin * m) of sub-block j
 __device__ __forceinline__ Q4kFactors sb_header_factors(uint4 h, uint32_t j) { return q4k_factors(Q4kHeader{{h.x, h.y, h.z, h.w}}, j); }
 
@@ -70,9 +89,9 @@ __device__ __forceinline__ float sb_operand(uint32_t dword, int b) {
 
 // M = 1: the 32 per-lane column sums of wave w -> red[column] (red = the wave's row): halves (16 registers, half h holds column
 // 2 m + h), rows (8 registers, row r holds column 4 n + 2 (r & 1) + (r >> 1)), then the 16 lanes of a row; MIN: less the min
-// sum over all 64 lanes
-template <bool MIN>
-__device__ __forceinline__ void sb_fold_lanes(const float (&acc)[32], float macc, float (&red)[kSbItem], uint32_t r, uint32_t i) {
+// sum over all 64 lanes — one per item (NS = 1) or one per column half (NS = 2: columns 16 h .. + 15 are registers i = 4 h .. + 3)
+template <bool MIN, int NS>
+__device__ __forceinline__ void sb_fold_lanes(const float (&acc)[32], const float (&macc)[NS], float (&red)[kSbItem], uint32_t r, uint32_t i) {
     float b16[16];
 #pragma unroll
     for (int m = 0; m < 16; m++) b16[m] = kon_fold32(acc[2 * m], acc[2 * m + 1]);
@@ -80,7 +99,11 @@ __device__ __forceinline__ void sb_fold_lanes(const float (&acc)[32], float macc
 #pragma unroll
     for (int n = 0; n < 8; n++) c8[n] = row16_sum(kon_fold16(b16[2 * n], b16[2 * n + 1]));
     float mins = 0.f;
-    if constexpr (MIN) mins = rows_sum4(row16_sum(macc));
+    if constexpr (MIN) mins = rows_sum4(row16_sum(macc[0]));
+    if constexpr (MIN && NS == 2) {
+        const float mins1 = rows_sum4(row16_sum(macc[1]));
+        mins = i >= 4 ? mins1 : mins;
+    }
     float v = c8[0];
 #pragma unroll
     for (int n = 1; n < 8; n++) v = i == (uint32_t)n ? c8[n] : v;
@@ -147,10 +170,11 @@ __device__ __forceinline__ sb_f4 sb_mfma3(sb_bf8 h1, sb_bf8 h2, sb_bf8 h3, sb_bf
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(h3, qv, acc, 0, 0, 0);
 }
 // M > 1, the end of a workgroup of WAVES waves that owns item column j and RT row tiles from row m0: D[m = 4 r + v][n = i] of
-// tile t = 2 rt + ct is in acc[rt][ct][v]; MIN: the min sum of row i over the four lane rows; then the waves in wave order
-template <uint32_t WAVES, int RT, bool MIN, class Args>
-__device__ __forceinline__ void sb_fold_waves(const Args& a, float (&fold)[WAVES][RT * 2][4][64], float (&mins)[WAVES][RT][16], const sb_f4 (&acc)[RT][2],
-                                              const float (&macc)[RT], uint32_t j, uint32_t m0) {
+// tile t = 2 rt + ct is in acc[rt][ct][v]; MIN: the min sum of row i over the four lane rows — one per row tile (NS = 1) or one
+// per (row tile, column tile) (NS = 2: a column tile is a scale sub-block with a min of its own); then the waves in wave order
+template <uint32_t WAVES, int RT, bool MIN, int NS, class Args>
+__device__ __forceinline__ void sb_fold_waves(const Args& a, float (&fold)[WAVES][RT * 2][4][64], float (&mins)[WAVES][RT * NS][16], const sb_f4 (&acc)[RT][2],
+                                              const float (&macc)[RT][NS], uint32_t j, uint32_t m0) {
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int t = 0; t < RT * 2; t++)
@@ -158,19 +182,22 @@ __device__ __forceinline__ void sb_fold_waves(const Args& a, float (&fold)[WAVES
         for (int v = 0; v < 4; v++) fold[w][t][v][lane] = acc[t >> 1][t & 1][v];
     if constexpr (MIN) {
 #pragma unroll
-        for (int rt = 0; rt < RT; rt++) {
-            const float mrow = rows_sum4(macc[rt]);
-            if (lane >> 4 == 0) mins[w][rt][lane & 15] = mrow;
-        }
+        for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+            for (int h = 0; h < NS; h++) {
+                const float mrow = rows_sum4(macc[rt][h]);
+                if (lane >> 4 == 0) mins[w][rt * NS + h][lane & 15] = mrow;
+            }
     }
     __syncthreads();
     for (uint32_t idx = threadIdx.x; idx < RT * 2 * 256; idx += WAVES * 64) {
         const uint32_t t = idx >> 8, rt = RT > 1 ? t >> 1 : 0, v = (idx >> 6) & 3, l = idx & 63, ml = 4 * (l >> 4) + v;
+        const uint32_t rn = NS == 2 ? t : rt; // (t = 2 rt + ct)
         float sum = fold[0][t][v][l], mn = 0.f;
-        if constexpr (MIN) mn = mins[0][rt][ml];
+        if constexpr (MIN) mn = mins[0][rn][ml];
         for (uint32_t ww = 1; ww < WAVES; ww++) {
             sum += fold[ww][t][v][l];
-            if constexpr (MIN) mn += mins[ww][rt][ml];
+            if constexpr (MIN) mn += mins[ww][rn][ml];
         }
         const uint32_t m = m0 + 16 * rt + ml, n = j * kSbItem + (t & 1) * 16 + (l & 15);
         if (m < a.M) a.dst[(uint64_t)m * a.dst_rs + n] = MIN ? sum - mn : sum;
@@ -184,10 +211,11 @@ __device__ __forceinline__ void sb_fold_waves(const Args& a, float (&fold)[WAVES
 // stream the weights non-temporally (beyond it several workgroup rows re-read them: keep them cached).
 // pack_item() / pack_factors(): item `idx` = (sub-block js, k) / the factor entry `fidx` from file block `blk`. synth(): the
 // deterministic pattern of the micro-benchmark, in the packed layout (every q; sc and m over their ranges; d = 2^-10).
-// chunk_factors(): the item's two factor rows at row k, {d * sc, dmin * m} or {d * sc of columns 0..15, of 16..31}.
-// Round kernels only: Hi + load_hi(); RoundLds: the round's factors in LDS; round_load() / round_store(): the duty of thread
+// chunk_factors(): the item's factor rows at row k: f[kScales] = d * sc (of the item, or of columns 0..15 and 16..31), mn[kScales] =
+// dmin * m beside each (kMin).
+// Round kernels only: Lo / Hi + load_lo() / load_hi(): an item's low and high plane entries (Hi = SbNoHi: none); RoundLds: the round's factors in LDS; round_load() / round_store(): the duty of thread
 // (kl, half) — one k of the round, half of its factors — from memory to LDS; item_factors(): the t = x * d * sc of wave w's
-// item at row kl (and its FMA into the min sum).
+// item at row kl (and its FMAs into the kScales min sums).
 struct Sb4 {
     static constexpr QWFormat kFormat = QW_SB4;
     static constexpr const char* kName = "Q4_K";
@@ -236,14 +264,19 @@ struct Sb5 {
         return {lo, (Hi*)(lo + (uint64_t)w.K * (w.N / kSbItem)), (uint4*)w.sc};
     }
     __device__ static __forceinline__ Planes at(Planes p, uint64_t item, uint64_t factor) { return {p.lo + item, p.hi + item, p.hdr + factor}; }
+    using Lo = uint4;
     template <bool NT>
-    __device__ static __forceinline__ Hi load_hi(const Hi* p) {
-        return wload1<NT>(p);
+    __device__ static __forceinline__ Lo load_lo(const Planes& c, uint32_t k) {
+        return wload<NT>(c.lo + k);
+    }
+    template <bool NT>
+    __device__ static __forceinline__ Hi load_hi(const Planes& c, uint32_t k) {
+        return wload1<NT>(c.hi + k);
     }
     __device__ static __forceinline__ void quants(uint4 lo, Hi hi, uint32_t (&q)[8]) { sb_quants<1>(lo, hi, hi >> 4, q); }
-    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float& f0, float& f1) {
-        const Q4kFactors f = sb_header_factors(c.hdr[k], js);
-        f0 = f.scale, f1 = f.min;
+    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float (&f)[1], float (&mn)[1]) {
+        const Q4kFactors hf = sb_header_factors(c.hdr[k], js);
+        f[0] = hf.scale, mn[0] = hf.min;
     }
     // [sub-block][k] of 8-byte (d * sc, dmin * m) pairs: a wave reads its own sub-block's pair of 64 k as one conflict-free 8-byte
     // read per lane. A thread turns four of its k's eight sub-blocks
@@ -265,10 +298,10 @@ struct Sb5 {
             }
         }
     }
-    __device__ static __forceinline__ void item_factors(const RoundLds& fac, uint32_t w, uint32_t kl, float x, float (&t)[1], float& macc) {
+    __device__ static __forceinline__ void item_factors(const RoundLds& fac, uint32_t w, uint32_t kl, float x, float (&t)[1], float (&macc)[1]) {
         const float2 f = fac[w][kl];
         t[0] = x * f.x;
-        macc = __builtin_fmaf(x, f.y, macc);
+        macc[0] = __builtin_fmaf(x, f.y, macc[0]);
     }
     // the file block is read by bytes (only 2-byte aligned) through q5k.h's own rule
     __device__ static __forceinline__ void pack_item(const uint8_t* blk, uint32_t js, const Planes& o, uint64_t idx) {
@@ -315,16 +348,21 @@ struct Sb6 {
         return {lo, (Hi*)(lo + (uint64_t)w.K * (w.N / kSbItem)), sc, (uint16_t*)(sc + (uint64_t)w.K * (w.N / kSbBlock))};
     }
     __device__ static __forceinline__ Planes at(Planes p, uint64_t item, uint64_t factor) { return {p.lo + item, p.hi + item, p.sc + factor, p.d + factor}; }
+    using Lo = uint4;
     template <bool NT>
-    __device__ static __forceinline__ Hi load_hi(const Hi* p) {
-        return wload2<NT>(p);
+    __device__ static __forceinline__ Lo load_lo(const Planes& c, uint32_t k) {
+        return wload<NT>(c.lo + k);
+    }
+    template <bool NT>
+    __device__ static __forceinline__ Hi load_hi(const Planes& c, uint32_t k) {
+        return wload2<NT>(c.hi + k);
     }
     __device__ static __forceinline__ void quants(uint4 lo, Hi hi, uint32_t (&q)[8]) { sb_quants<2>(lo, hi.x, hi.y, q); }
     __device__ static __forceinline__ float product(float d, uint32_t scale_byte) { return d * (float)(int)(int8_t)scale_byte; }
-    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float& f0, float& f1) {
+    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float (&f)[2], float (&)[2]) {
         const uint32_t sc2 = ((const uint16_t*)(c.sc + k))[js]; // the scales of columns 32 js .. + 15 and + 16 .. + 31
         const float d = q4k_f16(c.d[k]);
-        f0 = product(d, sc2 & 255u), f1 = product(d, sc2 >> 8);
+        f[0] = product(d, sc2 & 255u), f[1] = product(d, sc2 >> 8);
     }
     // [scale][k] of d * sc, so a wave reads its two scales of 64 k without a bank conflict. A thread turns eight of its k's sixteen
     // scale bytes
@@ -342,7 +380,7 @@ struct Sb6 {
             ds[half * 8 + e][kl] = live ? ds_e : 0.f;
         }
     }
-    __device__ static __forceinline__ void item_factors(const RoundLds& ds, uint32_t w, uint32_t kl, float x, float (&t)[2], float&) {
+    __device__ static __forceinline__ void item_factors(const RoundLds& ds, uint32_t w, uint32_t kl, float x, float (&t)[2], float (&)[2]) {
         t[0] = x * ds[2 * w][kl];
         t[1] = x * ds[2 * w + 1][kl];
     }
@@ -371,6 +409,181 @@ struct Sb6 {
         if (factors) {
             o.sc[idx] = make_uint4(a * 23u, a * 11u, a * 13u, a * 29u);
             o.d[idx] = 0x1400;
+        }
+    }
+};
+
+// the 2-bit-plane formats. Their item is 8 (+ 4) bytes, so a 256-k round holds 2 / 3.25 KiB per wave in flight
+struct SbNoHi {}; // Q2_K: no high plane, nothing loaded
+// an 8-byte low-plane entry from the 32 two-bit fields `low(c)` of an item's columns
+template <class Low>
+__device__ __forceinline__ uint2 sb_pack_lo2(Low low) {
+    uint32_t lo[2] = {0, 0};
+#pragma unroll
+    for (uint32_t c = 0; c < 32; c++) lo[c >> 4] |= low(c) << (8 * (c & 3) + 2 * ((c >> 2) & 3));
+    return make_uint2(lo[0], lo[1]);
+}
+
+struct Sb3 {
+    static constexpr QWFormat kFormat = QW_SB3;
+    static constexpr const char* kName = "Q3_K";
+    static constexpr uint32_t kFileBytes = kQ3kBytes, kItemBytes = 8 + 4, kFactorBytes = 12 + 2; // 3.4375 bit/weight like the file
+    static constexpr uint32_t kScales = 2, kNtMaxM = 32;
+    static constexpr bool kMin = false, kRound = true;
+    static constexpr int kBias = 4;
+    using Lo = uint2;
+    using Hi = uint32_t; // bit 4 h + s of byte b = third bit of column 16 h + 4 s + b (Q5_K's layout)
+    struct Sc12 {       // the file's twelve scale bytes
+        uint32_t x, y, z;
+    };
+    struct Planes {
+        Lo* lo;
+        Hi* hi;
+        Sc12* sc;
+        uint16_t* d;
+    };
+    static Planes planes(const QWeightDev& w) {
+        Lo* lo = (Lo*)w.qs;
+        Sc12* sc = (Sc12*)w.sc;
+        return {lo, (Hi*)(lo + (uint64_t)w.K * (w.N / kSbItem)), sc, (uint16_t*)(sc + (uint64_t)w.K * (w.N / kSbBlock))};
+    }
+    __device__ static __forceinline__ Planes at(Planes p, uint64_t item, uint64_t factor) { return {p.lo + item, p.hi + item, p.sc + factor, p.d + factor}; }
+    template <bool NT>
+    __device__ static __forceinline__ Lo load_lo(const Planes& c, uint32_t k) {
+        return wload2<NT>(c.lo + k);
+    }
+    template <bool NT>
+    __device__ static __forceinline__ Hi load_hi(const Planes& c, uint32_t k) {
+        return wload1<NT>(c.hi + k);
+    }
+    __device__ static __forceinline__ void quants(Lo lo, Hi hi, uint32_t (&q)[8]) { sb_quants2<true>(lo, hi, q); }
+    __device__ static __forceinline__ float product(float d, uint32_t sc) { return d * (float)((int)sc - 32); }
+    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float (&f)[2], float (&)[2]) {
+        const uint32_t* r = (const uint32_t*)(c.sc + k); // bytes 0..7 as one 64-bit value, 8..11 as a dword: shifts, nothing indexed
+        const uint64_t r8 = r[0] | (uint64_t)r[1] << 32;
+        const uint32_t r4 = r[2];
+        const float d = q4k_f16(c.d[k]);
+        const auto byte = [&](uint32_t i) { return (i < 8 ? (uint32_t)(r8 >> (8 * i)) : r4 >> (8 * (i & 3))) & 255u; };
+        f[0] = product(d, q3k_scale(byte, 2 * js)), f[1] = product(d, q3k_scale(byte, 2 * js + 1));
+    }
+    // [scale][k] of d * (sc - 32), as Q6_K. A thread turns eight of its k's sixteen scales: the eight 6-bit values of its half
+    // come out of the twelve bytes as two dwords of bytes by 4 shifts, 4 ANDs and 2 shift-ORs, ten VALU in all
+    using RoundLds = float[16][kSbRound];
+    struct RoundRaw {
+        Sc12 s;
+        uint32_t dbits;
+    };
+    __device__ static __forceinline__ RoundRaw round_load(const Planes& c, uint32_t k, uint32_t) { return {c.sc[k], c.d[k]}; }
+    __device__ static __forceinline__ void round_store(RoundLds& ds, const RoundRaw& raw, uint32_t kl, uint32_t half, bool live) {
+        const float d = q4k_f16((uint16_t)raw.dbits);
+        const uint32_t sh = 4 * half; // scales 8 half + e: nibble `half` of byte e, top bits 4 half + 2 (e >> 2) of byte 8 + (e & 3)
+        const uint32_t sc[2] = {((raw.s.x >> sh) & 0x0f0f0f0fu) | (((raw.s.z >> sh) & 0x03030303u) << 4),
+                                ((raw.s.y >> sh) & 0x0f0f0f0fu) | (((raw.s.z >> (sh + 2)) & 0x03030303u) << 4)};
+#pragma unroll
+        for (uint32_t e = 0; e < 8; e++) {
+            const float ds_e = product(d, (sc[e >> 2] >> (8 * (e & 3))) & 255u);
+            ds[half * 8 + e][kl] = live ? ds_e : 0.f;
+        }
+    }
+    __device__ static __forceinline__ void item_factors(const RoundLds& ds, uint32_t w, uint32_t kl, float x, float (&t)[2], float (&)[2]) {
+        t[0] = x * ds[2 * w][kl];
+        t[1] = x * ds[2 * w + 1][kl];
+    }
+    // the file block is read by bytes (only 2-byte aligned) through q3k.h's own rule
+    __device__ static __forceinline__ void pack_item(const uint8_t* blk, uint32_t js, const Planes& o, uint64_t idx) {
+        uint32_t hi = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < 32; c++) hi |= q3k_high(blk, 32 * js + c) << (8 * (c & 3) + 4 * (c >> 4) + ((c >> 2) & 3));
+        o.lo[idx] = sb_pack_lo2([&](uint32_t c) { return q3k_low(blk, 32 * js + c); });
+        o.hi[idx] = hi;
+    }
+    __device__ static __forceinline__ void pack_factors(const uint8_t* blk, const Planes& o, uint64_t fidx) {
+        uint32_t s[3] = {0, 0, 0};
+#pragma unroll
+        for (uint32_t e = 0; e < 12; e++) s[e >> 2] |= (uint32_t)blk[kQ3kScaleOffset + e] << (8 * (e & 3));
+        o.sc[fidx] = Sc12{s[0], s[1], s[2]};
+        o.d[fidx] = (uint16_t)(blk[kQ3kDOffset] | blk[kQ3kDOffset + 1] << 8);
+    }
+    __device__ static __forceinline__ void synth(const Planes& o, uint64_t idx, uint32_t a, bool factors) {
+        o.lo[idx] = make_uint2(a, a * 3u + 1u);
+        o.hi[idx] = a * 17u + 4u;
+        if (factors) {
+            o.sc[idx] = Sc12{a * 23u, a * 11u, a * 13u};
+            o.d[idx] = 0x1400;
+        }
+    }
+};
+
+struct Sb2 {
+    static constexpr QWFormat kFormat = QW_SB2;
+    static constexpr const char* kName = "Q2_K";
+    static constexpr uint32_t kFileBytes = kQ2kBytes, kItemBytes = 8, kFactorBytes = 16 + 4; // 2.625 bit/weight like the file
+    static constexpr uint32_t kScales = 2, kNtMaxM = 32;
+    static constexpr bool kMin = true, kRound = true;
+    static constexpr int kBias = 0;
+    using Lo = uint2;
+    using Hi = SbNoHi;
+    struct Planes {
+        Lo* lo;
+        uint4* sc;    // the file's sixteen (scale, min) nibble pairs
+        uint32_t* dm; // d | dmin << 16
+    };
+    static Planes planes(const QWeightDev& w) {
+        uint4* sc = (uint4*)w.sc;
+        return {(Lo*)w.qs, sc, (uint32_t*)(sc + (uint64_t)w.K * (w.N / kSbBlock))};
+    }
+    __device__ static __forceinline__ Planes at(Planes p, uint64_t item, uint64_t factor) { return {p.lo + item, p.sc + factor, p.dm + factor}; }
+    template <bool NT>
+    __device__ static __forceinline__ Lo load_lo(const Planes& c, uint32_t k) {
+        return wload2<NT>(c.lo + k);
+    }
+    template <bool NT>
+    __device__ static __forceinline__ Hi load_hi(const Planes&, uint32_t) {
+        return {};
+    }
+    __device__ static __forceinline__ void quants(Lo lo, Hi, uint32_t (&q)[8]) { sb_quants2<false>(lo, 0, q); }
+    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float (&f)[2], float (&mn)[2]) {
+        const uint32_t sc2 = ((const uint16_t*)(c.sc + k))[js], dm = c.dm[k]; // the pairs of columns 32 js .. + 15 and + 16 .. + 31
+        const Q4kFactors f0 = q2k_factors(sc2 & 255u, dm), f1 = q2k_factors(sc2 >> 8, dm);
+        f[0] = f0.scale, f[1] = f1.scale, mn[0] = f0.min, mn[1] = f1.min;
+    }
+    // [scale][k] of 8-byte (d * sc, dmin * m) pairs: a wave reads the two pairs of its item over 64 k as two conflict-free 8-byte
+    // reads per lane. A thread turns eight of its k's sixteen scale bytes
+    using RoundLds = float2[16][kSbRound];
+    struct RoundRaw {
+        uint2 sbytes;
+        uint32_t dm;
+    };
+    __device__ static __forceinline__ RoundRaw round_load(const Planes& c, uint32_t k, uint32_t half) { return {((const uint2*)(c.sc + k))[half], c.dm[k]}; }
+    __device__ static __forceinline__ void round_store(RoundLds& fac, const RoundRaw& raw, uint32_t kl, uint32_t half, bool live) {
+#pragma unroll
+        for (uint32_t e = 0; e < 8; e++) {
+            const Q4kFactors f = q2k_factors(((e < 4 ? raw.sbytes.x : raw.sbytes.y) >> (8 * (e & 3))) & 255u, raw.dm);
+            fac[half * 8 + e][kl] = live ? make_float2(f.scale, f.min) : make_float2(0.f, 0.f);
+        }
+    }
+    __device__ static __forceinline__ void item_factors(const RoundLds& fac, uint32_t w, uint32_t kl, float x, float (&t)[2], float (&macc)[2]) {
+#pragma unroll
+        for (uint32_t h = 0; h < 2; h++) {
+            const float2 f = fac[2 * w + h][kl];
+            t[h] = x * f.x;
+            macc[h] = __builtin_fmaf(x, f.y, macc[h]);
+        }
+    }
+    // (84 = 21 * 4: every file block is 4-byte aligned; the items go through q2k.h's own rule)
+    __device__ static __forceinline__ void pack_item(const uint8_t* blk, uint32_t js, const Planes& o, uint64_t idx) {
+        o.lo[idx] = sb_pack_lo2([&](uint32_t c) { return q2k_quant(blk, 32 * js + c); });
+    }
+    __device__ static __forceinline__ void pack_factors(const uint8_t* blk, const Planes& o, uint64_t fidx) {
+        const uint32_t* src = (const uint32_t*)blk;
+        o.sc[fidx] = make_uint4(src[0], src[1], src[2], src[3]);
+        o.dm[fidx] = src[kQ2kDOffset / 4];
+    }
+    __device__ static __forceinline__ void synth(const Planes& o, uint64_t idx, uint32_t a, bool factors) {
+        o.lo[idx] = make_uint2(a, a * 3u + 1u);
+        if (factors) {
+            o.sc[idx] = make_uint4(a * 23u, a * 11u, a * 13u, a * 29u);
+            o.dm[idx] = 0x90001400u; // d = 2^-10, dmin = -2^-11
         }
     }
 };

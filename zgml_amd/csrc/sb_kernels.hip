@@ -1,15 +1,15 @@
-// sb_kernels.hip — the kernels and launchers of the GGUF super-block weights (Q4_K / Q5_K / Q6_K); sb_kernels.h states the
-// layout, the arithmetic, the three formats and the device functions the kernels below are built from. Nothing here is shared
+// sb_kernels.hip — the kernels and launchers of the GGUF super-block weights (Q4_K / Q5_K / Q6_K / Q3_K / Q2_K); sb_kernels.h states the
+// layout, the arithmetic, the five formats and the device functions the kernels below are built from. Nothing here is shared
 // with the 32-block formats (and QW_Q4K, "Q4_0 with K on lanes", is none of these).
 //
 // M = 1. A workgroup of 8 waves owns one super-block column and one K share; wave w streams item column w, lane = k. A lane
-// carries 32 column sums (and one min sum), folded over the lanes by row swaps and DPP row sums in a fixed tree. With fewer item
+// carries 32 column sums (and one min sum; Q2_K: two, one per 16 columns), folded over the lanes by row swaps and DPP row sums in a fixed tree. With fewer item
 // columns than the part has wave slots the K range is split over blockIdx.y; every part stores its 256 partial outputs and the
 // LAST part to arrive (an integer counter; no float atomics) adds them in part order, so the bytes do not depend on arrival order
 // (sb_combine.h).
-//   Q5_K, Q6_K (sb_round_matvec_kernel): the share is walked in ROUNDS of four 64-k sweeps, and a round issues every load it has
+//   Q5_K, Q6_K, Q3_K, Q2_K (sb_round_matvec_kernel): the share is walked in ROUNDS of four 64-k sweeps, and a round issues every load it has
 //   — the workgroup's factors first, then per wave four lo items, four hi items and four x — before anything is consumed: 5.25 /
-//   6 KiB in flight per wave. While the items fly the 512 threads turn the round's 256 factor entries into f32 products in LDS,
+//   6 / 3.25 / 2.25 KiB in flight per wave. While the items fly the 512 threads turn the round's 256 factor entries into f32 products in LDS,
 //   once per workgroup. K is split into parts of whole rounds until the grid has about two workgroups per CU (at most 16 parts).
 //   Q4_K (sb4_matvec_kernel): sweep by sweep with a one-sweep look-ahead (one dwordx4 of nibbles, one dwordx4 of header — the 8
 //   waves of the workgroup read the same headers, so HBM sees each once —, one x), the header unpacked per item.
@@ -19,9 +19,10 @@
 // chunk's two factor rows beside them. B = q - bias, exact in bf16; A = t = x * (d * sc) in f32, split into three bf16 pieces,
 // contracted by v_mfma_f32_16x16x32_bf16 with f32 accumulation: three MFMAs per tile and 32 k. The min term is 8 VALU FMAs per
 // (row tile, 32 k) beside them, folded over the four lane rows at the end. Waves are folded in wave order.
-//   Q5_K, Q6_K (sb_matmul_kernel<F, RT>): 8 waves, RT = 1 or 2 row tiles of 16; the turned bytes are the assembled q. The B of a
+//   Q5_K, Q6_K, Q3_K, Q2_K (sb_matmul_kernel<F, RT>): 8 waves, RT = 1 or 2 row tiles of 16; the turned bytes are the assembled q. The B of a
 //   column tile serves both row tiles. With ONE d * sc per item (Q5_K) A is formed once per (row tile, 32 k) and feeds both
-//   column tiles; with two (Q6_K: a column tile is exactly one scale sub-block) A is per (row tile, column tile).
+//   column tiles; with two (Q6_K, Q3_K, Q2_K: a column tile is exactly one scale sub-block) A is per (row tile, column tile), and
+//   Q2_K's min sum is per (row tile, column tile) as well.
 //   Q4_K (sb4_matmul_kernel): 4 waves, one row tile; the turned byte keeps the nibble pair (columns i and i + 16), so the two
 //   column tiles are ONE 8-byte LDS read.
 #include "sb_kernels.h"
@@ -79,19 +80,21 @@ __global__ void __launch_bounds__(kSbWaves * 64) sb_round_matvec_kernel(SbMvArgs
     float acc[32];
 #pragma unroll
     for (int n = 0; n < 32; n++) acc[n] = 0.f;
-    float macc = 0.f;
+    float macc[F::kScales];
+#pragma unroll
+    for (uint32_t h = 0; h < F::kScales; h++) macc[h] = 0.f;
     for (uint32_t k0 = k_lo; k0 < k_hi; k0 += kSbRound) {
         // every load of the round, the factors first (their wait then leaves the items in flight); past the share: a live
         // address again, with x = 0 and every factor 0
         const typename F::RoundRaw raw = F::round_load(c, min(k0 + fkl, k_hi - 1), fhalf);
-        uint4 ql[kSbSweeps];
+        typename F::Lo ql[kSbSweeps];
         typename F::Hi qh[kSbSweeps];
         float xs[kSbSweeps];
 #pragma unroll
         for (uint32_t s = 0; s < kSbSweeps; s++) {
             const uint32_t k = k0 + s * kSbSweep + lane, kc = min(k, k_hi - 1);
-            ql[s] = wload<NT>(c.lo + kc);
-            qh[s] = F::template load_hi<NT>(c.hi + kc);
+            ql[s] = F::template load_lo<NT>(c, kc);
+            qh[s] = F::template load_hi<NT>(c, kc);
             xs[s] = k < k_hi ? a.x[kc] : 0.f;
         }
         F::round_store(fac, raw, fkl, fhalf, k0 + fkl < k_hi);
@@ -110,7 +113,7 @@ __global__ void __launch_bounds__(kSbWaves * 64) sb_round_matvec_kernel(SbMvArgs
         }
         __syncthreads(); // the next round rewrites fac
     }
-    sb_fold_lanes<F::kMin>(acc, macc, red[w], r, i);
+    sb_fold_lanes<F::kMin, (int)F::kScales>(acc, macc, red[w], r, i);
     sb_matvec_tail(a, red, &flag, nsb, part);
 }
 
@@ -138,11 +141,11 @@ __global__ void __launch_bounds__(kSbWaves * 64) sb4_matvec_kernel(SbMvArgs<Sb4>
     float acc[32];
 #pragma unroll
     for (int n = 0; n < 32; n++) acc[n] = 0.f;
-    float macc = 0.f;
+    float macc[1] = {0.f};
     auto consume = [&](const Item& it) {
         const Q4kFactors f = sb_header_factors(it.h, w);
         const float t = it.x * f.scale;
-        macc = __builtin_fmaf(it.x, f.min, macc);
+        macc[0] = __builtin_fmaf(it.x, f.min, macc[0]);
         uint32_t q[8];
         Sb4::quants(it.q, q);
 #pragma unroll
@@ -160,7 +163,7 @@ __global__ void __launch_bounds__(kSbWaves * 64) sb4_matvec_kernel(SbMvArgs<Sb4>
         cur = nxt;
     }
     consume(cur);
-    sb_fold_lanes<true>(acc, macc, red[w], r, i);
+    sb_fold_lanes<true, 1>(acc, macc, red[w], r, i);
     sb_matvec_tail(a, red, &flag, nsb, part);
 }
 
@@ -199,33 +202,34 @@ template <class F, int RT, bool XVEC, bool NT>
 __global__ void __launch_bounds__(kSbMmWaves * 64) sb_matmul_kernel(SbMmArgs<F> a) {
     __shared__ __attribute__((aligned(16))) uint8_t turned[kSbMmWaves][32 * 64]; // per wave: the chunk's q bytes, [column][k]
     __shared__ __attribute__((aligned(16))) float fs[kSbMmWaves][F::kScales][64]; // ... and its d * sc: one row, or one per column tile
-    __shared__ __attribute__((aligned(16))) float fm[kSbMmWaves][64];             // ... and its dmin * m (F::kMin)
+    __shared__ __attribute__((aligned(16))) float fm[kSbMmWaves][F::kScales][64]; // ... and its dmin * m beside each (F::kMin)
     __shared__ float fold[kSbMmWaves][RT * 2][4][64];
-    __shared__ float mins[kSbMmWaves][RT][16];
+    __shared__ float mins[kSbMmWaves][RT * F::kScales][16];
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane >> 4, i = lane & 15;
     const uint32_t j = blockIdx.x, nsb = j >> 3, js = j & 7, m0 = blockIdx.y * 16 * RT;
     const typename F::Planes c = F::at(a.w, (uint64_t)j * a.K, (uint64_t)nsb * a.K);
     const float* xrow[RT]; // A operand: lane (r, i) holds row i, k = 8 r .. 8 r + 7 of a 32-k step
     sb_f4 acc[RT][2];
-    float macc[RT];
+    float macc[RT][F::kScales]; // the min sums: per row tile, or per (row tile, column tile)
 #pragma unroll
     for (int rt = 0; rt < RT; rt++) {
         xrow[rt] = a.x + (uint64_t)min(m0 + 16 * rt + i, a.M - 1) * a.in_rs;
         acc[rt][0] = acc[rt][1] = sb_f4{0.f, 0.f, 0.f, 0.f};
-        macc[rt] = 0.f;
+#pragma unroll
+        for (uint32_t h = 0; h < F::kScales; h++) macc[rt][h] = 0.f;
     }
     const uint32_t chunks = (a.K + 63) / 64;
     for (uint32_t ch = w; ch < chunks; ch += kSbMmWaves) {
         const uint32_t k = ch * 64 + lane, kc = min(k, a.K - 1);
-        const uint4 lo = wload<NT>(c.lo + kc);
-        const typename F::Hi hi = F::template load_hi<NT>(c.hi + kc);
-        float f0, f1;
-        F::chunk_factors(c, kc, js, f0, f1);
-        fs[w][0][lane] = k < a.K ? f0 : 0.f; // rows past K: t = 0 and no min
-        if constexpr (F::kMin)
-            fm[w][lane] = k < a.K ? f1 : 0.f;
-        else
-            fs[w][1][lane] = k < a.K ? f1 : 0.f;
+        const typename F::Lo lo = F::template load_lo<NT>(c, kc);
+        const typename F::Hi hi = F::template load_hi<NT>(c, kc);
+        float f[F::kScales], mn[F::kScales];
+        F::chunk_factors(c, kc, js, f, mn);
+#pragma unroll
+        for (uint32_t h = 0; h < F::kScales; h++) {
+            fs[w][h][lane] = k < a.K ? f[h] : 0.f; // rows past K: t = 0 and no min
+            if constexpr (F::kMin) fm[w][h][lane] = k < a.K ? mn[h] : 0.f;
+        }
         uint32_t q[8];
         F::quants(lo, hi, q);
         sb_turn(turned[w], q, lane);
@@ -236,7 +240,7 @@ __global__ void __launch_bounds__(kSbMmWaves * 64) sb_matmul_kernel(SbMmArgs<F> 
             if constexpr (F::kScales == 1) { // one A per row tile, for both column tiles
                 float sv[8], mv[8];
                 sb_read8(&fs[w][0][kl], sv);
-                sb_read8(&fm[w][kl], mv);
+                sb_read8(&fm[w][0][kl], mv);
                 sb_bf8 qv[2]; // B of the two column tiles: column 16 ct + i
 #pragma unroll
                 for (int ct = 0; ct < 2; ct++) qv[ct] = sb_fragment<F::kBias>(sb_turned8(turned[w], 16 * ct + i, kl));
@@ -248,7 +252,7 @@ __global__ void __launch_bounds__(kSbMmWaves * 64) sb_matmul_kernel(SbMmArgs<F> 
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
                         const float t = xv[e] * sv[e];
-                        if constexpr (F::kMin) macc[rt] = __builtin_fmaf(xv[e], mv[e], macc[rt]);
+                        if constexpr (F::kMin) macc[rt][0] = __builtin_fmaf(xv[e], mv[e], macc[rt][0]);
                         sb_split3(t, h1, h2, h3, e);
                     }
 #pragma unroll
@@ -261,14 +265,18 @@ __global__ void __launch_bounds__(kSbMmWaves * 64) sb_matmul_kernel(SbMmArgs<F> 
 #pragma unroll
                 for (int ct = 0; ct < 2; ct++) {
                     const uint2 bb = sb_turned8(turned[w], 16 * ct + i, kl);
-                    float sv[8];
+                    float sv[8], mv[8];
                     sb_read8(&fs[w][ct][kl], sv);
+                    if constexpr (F::kMin) sb_read8(&fm[w][ct][kl], mv); // the column tile's own dmin * m
                     const sb_bf8 qv = sb_fragment<F::kBias>(bb);
 #pragma unroll
                     for (int rt = 0; rt < RT; rt++) {
                         sb_bf8 h1, h2, h3;
 #pragma unroll
-                        for (int e = 0; e < 8; e++) sb_split3(xv[rt][e] * sv[e], h1, h2, h3, e);
+                        for (int e = 0; e < 8; e++) {
+                            if constexpr (F::kMin) macc[rt][ct] = __builtin_fmaf(xv[rt][e], mv[e], macc[rt][ct]);
+                            sb_split3(xv[rt][e] * sv[e], h1, h2, h3, e);
+                        }
                         acc[rt][ct] = sb_mfma3(h1, h2, h3, qv, acc[rt][ct]);
                     }
                 }
@@ -276,7 +284,7 @@ __global__ void __launch_bounds__(kSbMmWaves * 64) sb_matmul_kernel(SbMmArgs<F> 
         }
         sb_wave_lds_fence(); // the reads above stay above the next chunk's writes
     }
-    sb_fold_waves<kSbMmWaves, RT, F::kMin>(a, fold, mins, acc, macc, j, m0);
+    sb_fold_waves<kSbMmWaves, RT, F::kMin, (int)F::kScales>(a, fold, mins, acc, macc, j, m0);
 }
 
 template <bool XVEC, bool NT>
@@ -290,7 +298,7 @@ __global__ void __launch_bounds__(kSb4MmWaves * 64) sb4_matmul_kernel(SbMmArgs<S
     const Sb4::Planes c = Sb4::at(a.w, (uint64_t)j * a.K, (uint64_t)nsb * a.K);
     const float* xrow = a.x + (uint64_t)min(m0 + i, a.M - 1) * a.in_rs; // A operand: lane (r, i) holds row i, k = 8 r .. 8 r + 7 of a 32-k step
     sb_f4 acc[1][2] = {{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}};
-    float macc[1] = {0.f};
+    float macc[1][1] = {{0.f}};
     const uint32_t chunks = (a.K + 63) / 64;
     for (uint32_t ch = w; ch < chunks; ch += kSb4MmWaves) {
         const uint32_t k = ch * 64 + lane, kc = min(k, a.K - 1);
@@ -314,7 +322,7 @@ __global__ void __launch_bounds__(kSb4MmWaves * 64) sb4_matmul_kernel(SbMmArgs<S
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 const float t = xv[e] * sv[e];
-                macc[0] = __builtin_fmaf(xv[e], mv[e], macc[0]);
+                macc[0][0] = __builtin_fmaf(xv[e], mv[e], macc[0][0]);
                 sb_split3(t, h1, h2, h3, e);
                 const uint32_t byte = (bw[e >> 2] >> (8 * (e & 3))) & 255u;
                 q0[e] = (__bf16)(float)(byte & 15u); // column i
@@ -329,7 +337,7 @@ __global__ void __launch_bounds__(kSb4MmWaves * 64) sb4_matmul_kernel(SbMmArgs<S
         }
         sb_wave_lds_fence(); // the reads above stay above the next chunk's writes
     }
-    sb_fold_waves<kSb4MmWaves, 1, true>(a, fold, mins, acc, macc, j, m0);
+    sb_fold_waves<kSb4MmWaves, 1, true, 1>(a, fold, mins, acc, macc, j, m0);
 }
 
 // ── launches ──
@@ -384,6 +392,8 @@ auto sb_dispatch(QWFormat format, Fn fn) {
     case Sb4::kFormat: return fn(Sb4{});
     case Sb5::kFormat: return fn(Sb5{});
     case Sb6::kFormat: return fn(Sb6{});
+    case Sb3::kFormat: return fn(Sb3{});
+    case Sb2::kFormat: return fn(Sb2{});
     default: break;
     }
     fprintf(stderr, "[zgml_hip] ERROR: weight format %u is no super-block format\n", (uint32_t)format);

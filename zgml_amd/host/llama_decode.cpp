@@ -4,6 +4,8 @@
 #endif
 #include "llama_decode.hpp"
 
+#include "../csrc/q2k.h"
+#include "../csrc/q3k.h"
 #include "../csrc/q4k.h"
 #include "../csrc/q5k.h"
 #include "../csrc/q6k.h"
@@ -128,12 +130,74 @@ void synth_q6k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
     for (uint32_t i = 0; i < zgml::kQ6kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
     blk[zgml::kQ6kDOffset] = (uint8_t)(hd & 0xFF), blk[zgml::kQ6kDOffset + 1] = (uint8_t)(hd >> 8);
 }
+// Q3_K super-block `sb` of weight `id` (csrc/q3k.h): d of both signs in the normal f16 range, hmask, qs and the twelve scale bytes
+// hashed, so sc - 32 runs over -32..31 and q over -4..3. |w| stays below 0.12, mostly far below.
+void synth_q3k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
+    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0x165667B1u);
+    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -11) * ((s >> 3) & 1 ? -1.0f : 1.0f);
+    const uint16_t hd = f32_to_f16_bits(d);
+    for (uint32_t i = 0; i < zgml::kQ3kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
+    blk[zgml::kQ3kDOffset] = (uint8_t)(hd & 0xFF), blk[zgml::kQ3kDOffset + 1] = (uint8_t)(hd >> 8);
+}
+// Q2_K super-block `sb` of weight `id` (csrc/q2k.h): d and dmin of both signs, the sixteen (scale, min) bytes and qs hashed, so sc
+// and m run over 0..15 and q over 0..3. |w| stays below 0.14, mostly far below.
+void synth_q2k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
+    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0xD3A2646Cu);
+    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -10) * ((s >> 3) & 1 ? -1.0f : 1.0f);
+    const float dmin = std::ldexp(1.0f + (float)((s >> 4) & 7) * 0.125f, -9) * ((s >> 7) & 1 ? -1.0f : 1.0f);
+    const uint16_t hd = f32_to_f16_bits(d), hm = f32_to_f16_bits(dmin);
+    for (uint32_t i = 0; i < zgml::kQ2kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
+    blk[80] = (uint8_t)(hd & 0xFF), blk[81] = (uint8_t)(hd >> 8), blk[82] = (uint8_t)(hm & 0xFF), blk[83] = (uint8_t)(hm >> 8);
+}
 // the Q4_K_M / Q5_K_M mix GGUF writers use: does weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) take Q6_K?
 bool q4_k_m_takes_q6k(size_t wi, uint32_t n_layers) {
     const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7), e = n_layers / 8;
     if (l >= n_layers) return true;        // output.weight
     if (slot != 2 && slot != 6) return false; // attn_v and ffn_down of the "more bits" layers
     return l < e || l >= 7 * n_layers / 8 || (l - e) % 3 == 2;
+}
+
+// the file block bytes (= the type) of weight `wi` in the super-block model kinds: the layout rules of GGUF writers for the LLaMA
+// architecture (llama_decode.hpp states them per kind)
+uint32_t sb_block_bytes(WeightKind kind, size_t wi, uint32_t n_layers) {
+    const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7); // slot: q, k, v, o, gate, up, down
+    switch (kind) {
+    case WeightKind::q4_k_m_gguf:
+    case WeightKind::q4_k_m_dense: return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ4kBytes;
+    case WeightKind::q5_k_m_gguf:
+    case WeightKind::q5_k_m_dense: return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ5kBytes;
+    case WeightKind::q3_k_m_gguf:
+    case WeightKind::q3_k_m_dense:
+        if (l >= n_layers) return zgml::kQ6kBytes;
+        if (slot == 2) return l < 2 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
+        if (slot == 6) return l < n_layers / 16 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
+        return slot == 3 ? zgml::kQ4kBytes : zgml::kQ3kBytes;
+    case WeightKind::q2_k_gguf:
+    case WeightKind::q2_k_dense:
+        if (l >= n_layers) return zgml::kQ6kBytes;
+        if (slot == 6 && l < n_layers / 8) return zgml::kQ4kBytes;
+        return slot == 2 || slot == 3 || slot == 6 ? zgml::kQ3kBytes : zgml::kQ2kBytes;
+    default: return zgml::kQ4kBytes;
+    }
+}
+// ... and the generator / the value rule of a type
+void synth_sb_block(uint32_t block_bytes, uint64_t sb, uint32_t id, uint8_t* blk) {
+    switch (block_bytes) {
+    case zgml::kQ2kBytes: return synth_q2k_block(sb, id, blk);
+    case zgml::kQ3kBytes: return synth_q3k_block(sb, id, blk);
+    case zgml::kQ5kBytes: return synth_q5k_block(sb, id, blk);
+    case zgml::kQ6kBytes: return synth_q6k_block(sb, id, blk);
+    default: return synth_q4k_block(sb, id, blk);
+    }
+}
+float sb_value(uint32_t block_bytes, const uint8_t* blk, uint32_t e) {
+    switch (block_bytes) {
+    case zgml::kQ2kBytes: return zgml::q2k_value(blk, e);
+    case zgml::kQ3kBytes: return zgml::q3k_value(blk, e);
+    case zgml::kQ5kBytes: return zgml::q5k_value(blk, e);
+    case zgml::kQ6kBytes: return zgml::q6k_value(blk, e);
+    default: return zgml::q4k_value(blk, e);
+    }
 }
 
 void parallel_rows(size_t n, int threads, const std::function<void(size_t, size_t)>& fn) {
@@ -214,20 +278,17 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
         auto [n0, nl] = shard(cfg.vocab_size);
         m->qweights.push_back(make_qweight(d, cfg.vocab_size, n0, nl, cfg.n_layers * 8, kind, threads));
     }
-    const bool five = kind == WeightKind::q5_k_m_gguf || kind == WeightKind::q5_k_m_dense; // the base type of the mix: Q5_K, else Q4_K
-    const bool mix_model = kind == WeightKind::q4_k_m_gguf || kind == WeightKind::q4_k_m_dense || five;
-    const bool sb_model = kind == WeightKind::q4_k_gguf || kind == WeightKind::q4_k_dense || mix_model;
-    if (sb_model) // N % 256 == 0: Q4_K / Q5_K (in the mixes: or Q6_K) super-blocks of their own generators (the Q4_0 values are dropped); else Q4_0 file blocks below
+    const bool sb_model = (int)kind >= (int)WeightKind::q4_k_gguf; // every kind from q4_k_gguf on
+    if (sb_model) // N % 256 == 0: super-blocks of the type the kind's layout rule gives, from their own generators (the Q4_0 values are dropped); else Q4_0 file blocks below
         for (size_t wi = 0; wi < m->qweights.size(); wi++) {
             auto& q = m->qweights[wi];
             if (q.N % zgml::kQ4kBlock) continue;
             const uint32_t id = (uint32_t)(wi / 7 * 8 + wi % 7);
-            const bool six = mix_model && q4_k_m_takes_q6k(wi, cfg.n_layers);
             q.gguf_block = zgml::kQ4kBlock;
-            q.gguf_block_bytes = six ? zgml::kQ6kBytes : five ? zgml::kQ5kBytes : zgml::kQ4kBytes;
+            q.gguf_block_bytes = sb_block_bytes(kind, wi, cfg.n_layers);
             q.gguf.resize(q.K * q.N / zgml::kQ4kBlock * q.gguf_block_bytes);
             parallel_rows(q.K * q.N / zgml::kQ4kBlock, threads, [&](size_t b0, size_t b1) {
-                for (size_t b = b0; b < b1; b++) (six ? synth_q6k_block : five ? synth_q5k_block : synth_q4k_block)(b, id, q.gguf.data() + b * q.gguf_block_bytes);
+                for (size_t b = b0; b < b1; b++) synth_sb_block(q.gguf_block_bytes, b, id, q.gguf.data() + b * q.gguf_block_bytes);
             });
             std::vector<int8_t>().swap(q.data);
             std::vector<float>().swap(q.scales);
@@ -250,19 +311,15 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
             std::vector<float>().swap(q.scales);
         }
     }
-    if (kind == WeightKind::q4_k_dense || kind == WeightKind::q4_k_m_dense || kind == WeightKind::q5_k_m_dense) { // the gguf twin, dequantised by the formats' own rules (csrc/q4k.h, q5k.h, q6k.h); file blocks dropped
+    if (sb_model && is_dense(kind)) { // the gguf twin, dequantised by the formats' own rules (csrc/q2k.h .. q6k.h); file blocks dropped
         for (auto& q : m->qweights) {
             std::vector<float> w(q.K * q.N);
             const uint8_t* g = q.gguf.data();
             const bool sb = q.gguf_block == zgml::kQ4kBlock;
             parallel_rows(q.K, threads, [&](size_t k0, size_t k1) {
                 for (size_t i = k0 * q.N; i < k1 * q.N; i++) {
-                    if (sb && q.gguf_block_bytes == zgml::kQ6kBytes) {
-                        w[i] = zgml::q6k_value(g + i / zgml::kQ6kBlock * zgml::kQ6kBytes, (uint32_t)(i % zgml::kQ6kBlock));
-                    } else if (sb && q.gguf_block_bytes == zgml::kQ5kBytes) {
-                        w[i] = zgml::q5k_value(g + i / zgml::kQ5kBlock * zgml::kQ5kBytes, (uint32_t)(i % zgml::kQ5kBlock));
-                    } else if (sb) {
-                        w[i] = zgml::q4k_value(g + i / zgml::kQ4kBlock * zgml::kQ4kBytes, (uint32_t)(i % zgml::kQ4kBlock));
+                    if (sb) {
+                        w[i] = sb_value(q.gguf_block_bytes, g + i / zgml::kQ4kBlock * q.gguf_block_bytes, (uint32_t)(i % zgml::kQ4kBlock));
                     } else { // Q4_0 block: f16 scale, element e in the low (e even) / high nibble of byte e / 2, value = nibble - 8
                         const uint8_t* blk = g + i / 32 * 18;
                         const uint32_t e = (uint32_t)(i % 32);

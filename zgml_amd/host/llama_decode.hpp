@@ -54,17 +54,28 @@ LlamaConfig tiny_test();                 // small GQA config for parity tests
 // q4_k_m_dense: the q4_k_m_gguf model dequantised to f32 `matmul` weights
 // q5_k_m_gguf / q5_k_m_dense: the Q5_K_M mix and its f32 twin: the same layout rule with Q5_K super-blocks (176 B; csrc/q5k.h) as the
 //            base type in place of Q4_K (another model again: its own generator)
+// q3_k_m_gguf / q3_k_m_dense: the Q3_K_M mix GGUF writers use for the LLaMA architecture and its f32 twin: the head Q6_K, attn_v
+//            Q5_K in layers 0-1 and Q4_K after, ffn_down Q5_K in layers < L/16 and Q4_K after, attn_output Q4_K, the rest Q3_K
+//            super-blocks (110 B; csrc/q3k.h)
+// q2_k_gguf / q2_k_dense: the Q2_K mix and its f32 twin: the head Q6_K, attn_v, attn_output and ffn_down Q3_K (ffn_down of layers
+//            < L/8: Q4_K), the rest Q2_K super-blocks (84 B; csrc/q2k.h)
 enum class WeightKind : int { q4_0 = 0, q8_0 = 1, f32_dense = 2, q4_0_gguf = 3, q4_k_gguf = 4, q4_k_dense = 5, q4_k_m_gguf = 6, q4_k_m_dense = 7,
-                              q5_k_m_gguf = 8, q5_k_m_dense = 9 };
-inline bool is_dense(WeightKind k) { return k == WeightKind::f32_dense || k == WeightKind::q4_k_dense || k == WeightKind::q4_k_m_dense || k == WeightKind::q5_k_m_dense; }
-inline bool is_gguf(WeightKind k) { return k == WeightKind::q4_0_gguf || k == WeightKind::q4_k_gguf || k == WeightKind::q4_k_m_gguf || k == WeightKind::q5_k_m_gguf; }
+                              q5_k_m_gguf = 8, q5_k_m_dense = 9, q3_k_m_gguf = 10, q3_k_m_dense = 11, q2_k_gguf = 12, q2_k_dense = 13 };
+inline bool is_dense(WeightKind k) {
+    return k == WeightKind::f32_dense || k == WeightKind::q4_k_dense || k == WeightKind::q4_k_m_dense || k == WeightKind::q5_k_m_dense || k == WeightKind::q3_k_m_dense ||
+           k == WeightKind::q2_k_dense;
+}
+inline bool is_gguf(WeightKind k) {
+    return k == WeightKind::q4_0_gguf || k == WeightKind::q4_k_gguf || k == WeightKind::q4_k_m_gguf || k == WeightKind::q5_k_m_gguf || k == WeightKind::q3_k_m_gguf ||
+           k == WeightKind::q2_k_gguf;
+}
 
 struct QWeightHost {
     std::vector<int8_t> data;
     std::vector<float> scales;
-    std::vector<uint8_t> gguf; // q4_0_gguf / q4_k_gguf / q4_k_m_gguf / q5_k_m_gguf: the file blocks (data / scales dropped)
-    uint32_t gguf_block = 32;  // ... their elements: 32 (Q4_0) or 256 (Q4_K, Q5_K, Q6_K)
-    uint32_t gguf_block_bytes = 18; // ... and their bytes, which say the form: 18 (Q4_0), 144 (Q4_K), 176 (Q5_K) or 210 (Q6_K)
+    std::vector<uint8_t> gguf; // the *_gguf kinds: the file blocks (data / scales dropped)
+    uint32_t gguf_block = 32;  // ... their elements: 32 (Q4_0) or 256 (the k-quants)
+    uint32_t gguf_block_bytes = 18; // ... and their bytes, which say the form: 18 (Q4_0), 84 (Q2_K), 110 (Q3_K), 144 (Q4_K), 176 (Q5_K) or 210 (Q6_K)
     size_t K = 0, N = 0; // rows, cols
 };
 
@@ -76,7 +87,7 @@ struct LlamaModel {
     std::vector<float> gamma_f;
     // per layer: q,k,v,o,gate,up,down; then (untied) the LM head
     std::vector<QWeightHost> qweights;
-    // kind == f32_dense / q4_k_dense / q4_k_m_dense / q5_k_m_dense: the same weights dequantised to f32 [K, N] (qweights keep only K and N)
+    // is_dense(kind): the same weights dequantised to f32 [K, N] (qweights keep only K and N)
     std::vector<std::vector<float>> dense;
     std::vector<float> cos_table, sin_table; // [max_seq][d_head], RoPE.init src/nn.zig:286-311
     size_t lm_head_index() const { return (size_t)cfg.n_layers * 7; }

@@ -18,6 +18,10 @@ Q4_K_GGUF, Q4_K_DENSE = 4, 5
 Q4_K_M_GGUF, Q4_K_M_DENSE = 6, 7
 # the Q5_K_M mix: the same layout rule with Q5_K super-blocks as the base type; and its f32 twin
 Q5_K_M_GGUF, Q5_K_M_DENSE = 8, 9
+# the Q3_K_M mix (Q3_K bulk; Q4_K / Q5_K for attn_v, attn_output and ffn_down; Q6_K head) and the Q2_K mix (Q2_K bulk; Q3_K / Q4_K for
+# attn_v, attn_output and ffn_down; Q6_K head), each with its f32 twin
+Q3_K_M_GGUF, Q3_K_M_DENSE = 10, 11
+Q2_K_GGUF, Q2_K_DENSE = 12, 13
 
 
 class Config(C.Structure):
