@@ -226,14 +226,21 @@ struct QuantizedWeightUpload {
     static QuantizedWeightUpload ggufSuperBlocks(const uint8_t* blocks, size_t n_bytes, size_t rows, size_t cols) {
         return {reinterpret_cast<const int8_t*>(blocks), n_bytes, nullptr, 0, rows, cols, 256};
     }
+    // the super-block forms: {form, bytes of a 256-element file block}. The device's table is kSbFormats (csrc/kernels.h, which the
+    // host build does not see): the same rows in the same order, and a new format is a row in both.
+    static constexpr struct {
+        int form;
+        size_t block_bytes;
+    } kSbForms[] = {{3, ZGML_QW_GGUF_Q4_K_BLOCK_BYTES}, {4, ZGML_QW_GGUF_Q6_K_BLOCK_BYTES}, {5, ZGML_QW_GGUF_Q5_K_BLOCK_BYTES},
+                    {6, ZGML_QW_GGUF_Q3_K_BLOCK_BYTES}, {7, ZGML_QW_GGUF_Q2_K_BLOCK_BYTES}};
     int ggufForm() const { // 1 = Q4_0, 2 = Q8_0, 3 = Q4_K, 4 = Q6_K, 5 = Q5_K, 6 = Q3_K, 7 = Q2_K
         if (scales || scales_len || !data) return 0;
         const size_t n = rows * cols;
         if (block_size == 256) {
             if (!n || cols % 256) return 0;
-            return data_len == n / 256 * ZGML_QW_GGUF_Q4_K_BLOCK_BYTES ? 3 : data_len == n / 256 * ZGML_QW_GGUF_Q6_K_BLOCK_BYTES ? 4 :
-                   data_len == n / 256 * ZGML_QW_GGUF_Q5_K_BLOCK_BYTES ? 5 : data_len == n / 256 * ZGML_QW_GGUF_Q3_K_BLOCK_BYTES ? 6 :
-                   data_len == n / 256 * ZGML_QW_GGUF_Q2_K_BLOCK_BYTES ? 7 : 0;
+            for (const auto& sb : kSbForms)
+                if (data_len == n / 256 * sb.block_bytes) return sb.form;
+            return 0;
         }
         if (block_size != 32) return 0;
         if (!n || n % 32 || cols % 32) return 0;

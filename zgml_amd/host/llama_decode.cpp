@@ -94,111 +94,81 @@ inline float synth_scale(uint64_t block, uint32_t id, WeightKind kind) {
     return f16_round(base * (1.0f + (float)((block + id) % 7) * 0.125f));
 }
 
-// Q4_K super-block `sb` of weight `id` (csrc/q4k.h): d and dmin of both signs in the normal f16 range, the twelve scale bytes and the
-// 128 nibble bytes hashed, so sc and m run over 0..63 and q over 0..15. |w| stays below 0.2, mostly far below.
 inline uint32_t mix32(uint32_t x) {
     x ^= x >> 16, x *= 0x7feb352du;
     x ^= x >> 15, x *= 0x846ca68bu;
     return x ^ (x >> 16);
 }
-void synth_q4k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
-    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0x85EBCA6Bu);
-    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -14) * ((s >> 3) & 1 ? -1.0f : 1.0f);
-    const float dmin = std::ldexp(1.0f + (float)((s >> 4) & 7) * 0.125f, -11) * ((s >> 7) & 1 ? -1.0f : 1.0f);
-    const uint16_t hd = f32_to_f16_bits(d), hm = f32_to_f16_bits(dmin);
-    blk[0] = (uint8_t)(hd & 0xFF), blk[1] = (uint8_t)(hd >> 8), blk[2] = (uint8_t)(hm & 0xFF), blk[3] = (uint8_t)(hm >> 8);
-    for (uint32_t i = 0; i < 140; i++) blk[4 + i] = (uint8_t)(mix32(s + 1 + i) >> 11);
+
+// The super-block types, one row each: the file block bytes (which name the type: QWeightHost::gguf_block_bytes), the value rule of
+// element e of a block, and what the generator below needs. A new type is its csrc/q?k.h and a row here.
+constexpr int kNoDmin = std::numeric_limits<int>::min();
+struct SbTypeRow {
+    uint32_t block_bytes;
+    float (*value)(const uint8_t* block, uint32_t e);
+    uint32_t id_salt;                     // weight `id` enters the block's seed as id * id_salt: every type is a model of its own
+    int d_exp, dmin_exp;                  // d = +-[1, 2) * 2^d_exp and dmin likewise (kNoDmin: the type has none)
+    uint32_t d_offset, dmin_offset;       // where the f16 fields sit
+    uint32_t hash_begin, hash_end, hash_base; // bytes [hash_begin, hash_end) are hashed: byte i takes hash number i - hash_base
+};
+// d, dmin in the normal f16 range; every other byte hashed, so the scales (sc, m) and q run over all their values:
+//   Q2_K sc, m 0..15, q 0..3, |w| < 0.14;  Q3_K sc - 32 -32..31, q -4..3, |w| < 0.12;  Q4_K sc, m 0..63, q 0..15, |w| < 0.2;
+//   Q5_K Q4_K's header at half the d (q 0..31), |w| < 0.2;  Q6_K int8 scales, q - 32 -32..31, |w| < 0.47;  all mostly far below.
+// Q4_K's hash numbers start at its byte 4 (hash_base 4); the later types number the hashes by the byte.
+constexpr SbTypeRow kSbTypes[] = {
+    {zgml::kQ2kBytes, zgml::q2k_value, 0xD3A2646Cu, -10, -9, zgml::kQ2kDOffset, zgml::kQ2kDOffset + 2, 0, zgml::kQ2kDOffset, 0},
+    {zgml::kQ3kBytes, zgml::q3k_value, 0x165667B1u, -11, kNoDmin, zgml::kQ3kDOffset, 0, 0, zgml::kQ3kDOffset, 0},
+    {zgml::kQ4kBytes, zgml::q4k_value, 0x85EBCA6Bu, -14, -11, 0, 2, 4, zgml::kQ4kBytes, 4},
+    {zgml::kQ5kBytes, zgml::q5k_value, 0x27D4EB2Fu, -15, -11, 0, 2, 4, zgml::kQ5kBytes, 0},
+    {zgml::kQ6kBytes, zgml::q6k_value, 0xC2B2AE35u, -14, kNoDmin, zgml::kQ6kDOffset, 0, 0, zgml::kQ6kDOffset, 0},
+};
+const SbTypeRow& sb_type(uint32_t block_bytes) {
+    for (const SbTypeRow& t : kSbTypes)
+        if (t.block_bytes == block_bytes) return t;
+    std::abort(); // a layout rule named a type that has no row
 }
 
-// Q5_K super-block `sb` of weight `id` (csrc/q5k.h): Q4_K's header at half the d (q runs over 0..31), qh and qs hashed. |w| stays below
-// 0.2, mostly far below.
-void synth_q5k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
-    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0x27D4EB2Fu);
-    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -15) * ((s >> 3) & 1 ? -1.0f : 1.0f);
-    const float dmin = std::ldexp(1.0f + (float)((s >> 4) & 7) * 0.125f, -11) * ((s >> 7) & 1 ? -1.0f : 1.0f);
-    const uint16_t hd = f32_to_f16_bits(d), hm = f32_to_f16_bits(dmin);
-    blk[0] = (uint8_t)(hd & 0xFF), blk[1] = (uint8_t)(hd >> 8), blk[2] = (uint8_t)(hm & 0xFF), blk[3] = (uint8_t)(hm >> 8);
-    for (uint32_t i = 4; i < zgml::kQ5kBytes; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
+// super-block `sb` of weight `id` in type t
+void synth_sb_block(const SbTypeRow& t, uint64_t sb, uint32_t id, uint8_t* blk) {
+    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * t.id_salt);
+    for (uint32_t i = t.hash_begin; i < t.hash_end; i++) blk[i] = (uint8_t)(mix32(s + 1 + i - t.hash_base) >> 11);
+    const auto put_f16 = [&](uint32_t at, uint32_t bits, int exp) { // mantissa bits 0-2 and the sign bit 3 of `bits`
+        const uint16_t h = f32_to_f16_bits(std::ldexp(1.0f + (float)(bits & 7) * 0.125f, exp) * ((bits >> 3) & 1 ? -1.0f : 1.0f));
+        blk[at] = (uint8_t)(h & 0xFF), blk[at + 1] = (uint8_t)(h >> 8);
+    };
+    put_f16(t.d_offset, s, t.d_exp);
+    if (t.dmin_exp != kNoDmin) put_f16(t.dmin_offset, s >> 4, t.dmin_exp);
 }
 
-// Q6_K super-block `sb` of weight `id` (csrc/q6k.h): d of both signs in the normal f16 range, ql, qh and the sixteen scale bytes
-// hashed, so the scales run over the whole int8 range and q over 0..63. |w| stays below 0.47, mostly far below.
-void synth_q6k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
-    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0xC2B2AE35u);
-    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -14) * ((s >> 3) & 1 ? -1.0f : 1.0f);
-    const uint16_t hd = f32_to_f16_bits(d);
-    for (uint32_t i = 0; i < zgml::kQ6kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
-    blk[zgml::kQ6kDOffset] = (uint8_t)(hd & 0xFF), blk[zgml::kQ6kDOffset + 1] = (uint8_t)(hd >> 8);
-}
-// Q3_K super-block `sb` of weight `id` (csrc/q3k.h): d of both signs in the normal f16 range, hmask, qs and the twelve scale bytes
-// hashed, so sc - 32 runs over -32..31 and q over -4..3. |w| stays below 0.12, mostly far below.
-void synth_q3k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
-    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0x165667B1u);
-    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -11) * ((s >> 3) & 1 ? -1.0f : 1.0f);
-    const uint16_t hd = f32_to_f16_bits(d);
-    for (uint32_t i = 0; i < zgml::kQ3kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
-    blk[zgml::kQ3kDOffset] = (uint8_t)(hd & 0xFF), blk[zgml::kQ3kDOffset + 1] = (uint8_t)(hd >> 8);
-}
-// Q2_K super-block `sb` of weight `id` (csrc/q2k.h): d and dmin of both signs, the sixteen (scale, min) bytes and qs hashed, so sc
-// and m run over 0..15 and q over 0..3. |w| stays below 0.14, mostly far below.
-void synth_q2k_block(uint64_t sb, uint32_t id, uint8_t* blk) {
-    const uint32_t s = mix32((uint32_t)sb * 0x9E3779B9u + (uint32_t)(sb >> 32) + id * 0xD3A2646Cu);
-    const float d = std::ldexp(1.0f + (float)(s & 7) * 0.125f, -10) * ((s >> 3) & 1 ? -1.0f : 1.0f);
-    const float dmin = std::ldexp(1.0f + (float)((s >> 4) & 7) * 0.125f, -9) * ((s >> 7) & 1 ? -1.0f : 1.0f);
-    const uint16_t hd = f32_to_f16_bits(d), hm = f32_to_f16_bits(dmin);
-    for (uint32_t i = 0; i < zgml::kQ2kDOffset; i++) blk[i] = (uint8_t)(mix32(s + 1 + i) >> 11);
-    blk[80] = (uint8_t)(hd & 0xFF), blk[81] = (uint8_t)(hd >> 8), blk[82] = (uint8_t)(hm & 0xFF), blk[83] = (uint8_t)(hm >> 8);
-}
-// the Q4_K_M / Q5_K_M mix GGUF writers use: does weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) take Q6_K?
+// The layout rules of GGUF writers for the LLaMA architecture (llama_decode.hpp states them per kind): the type of weight `wi`
+uint32_t all_q4k(size_t, uint32_t) { return zgml::kQ4kBytes; }
+// Q4_K_M / Q5_K_M: does `wi` take Q6_K?
 bool q4_k_m_takes_q6k(size_t wi, uint32_t n_layers) {
     const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7), e = n_layers / 8;
     if (l >= n_layers) return true;        // output.weight
     if (slot != 2 && slot != 6) return false; // attn_v and ffn_down of the "more bits" layers
     return l < e || l >= 7 * n_layers / 8 || (l - e) % 3 == 2;
 }
-
-// the file block bytes (= the type) of weight `wi` in the super-block model kinds: the layout rules of GGUF writers for the LLaMA
-// architecture (llama_decode.hpp states them per kind)
-uint32_t sb_block_bytes(WeightKind kind, size_t wi, uint32_t n_layers) {
+uint32_t q4_k_m(size_t wi, uint32_t n_layers) { return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ4kBytes; }
+uint32_t q5_k_m(size_t wi, uint32_t n_layers) { return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ5kBytes; }
+uint32_t q3_k_m(size_t wi, uint32_t n_layers) {
     const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7); // slot: q, k, v, o, gate, up, down
-    switch (kind) {
-    case WeightKind::q4_k_m_gguf:
-    case WeightKind::q4_k_m_dense: return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ4kBytes;
-    case WeightKind::q5_k_m_gguf:
-    case WeightKind::q5_k_m_dense: return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ5kBytes;
-    case WeightKind::q3_k_m_gguf:
-    case WeightKind::q3_k_m_dense:
-        if (l >= n_layers) return zgml::kQ6kBytes;
-        if (slot == 2) return l < 2 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
-        if (slot == 6) return l < n_layers / 16 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
-        return slot == 3 ? zgml::kQ4kBytes : zgml::kQ3kBytes;
-    case WeightKind::q2_k_gguf:
-    case WeightKind::q2_k_dense:
-        if (l >= n_layers) return zgml::kQ6kBytes;
-        if (slot == 6 && l < n_layers / 8) return zgml::kQ4kBytes;
-        return slot == 2 || slot == 3 || slot == 6 ? zgml::kQ3kBytes : zgml::kQ2kBytes;
-    default: return zgml::kQ4kBytes;
-    }
+    if (l >= n_layers) return zgml::kQ6kBytes;
+    if (slot == 2) return l < 2 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
+    if (slot == 6) return l < n_layers / 16 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
+    return slot == 3 ? zgml::kQ4kBytes : zgml::kQ3kBytes;
 }
-// ... and the generator / the value rule of a type
-void synth_sb_block(uint32_t block_bytes, uint64_t sb, uint32_t id, uint8_t* blk) {
-    switch (block_bytes) {
-    case zgml::kQ2kBytes: return synth_q2k_block(sb, id, blk);
-    case zgml::kQ3kBytes: return synth_q3k_block(sb, id, blk);
-    case zgml::kQ5kBytes: return synth_q5k_block(sb, id, blk);
-    case zgml::kQ6kBytes: return synth_q6k_block(sb, id, blk);
-    default: return synth_q4k_block(sb, id, blk);
-    }
+uint32_t q2_k(size_t wi, uint32_t n_layers) {
+    const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7);
+    if (l >= n_layers) return zgml::kQ6kBytes;
+    if (slot == 6 && l < n_layers / 8) return zgml::kQ4kBytes;
+    return slot == 2 || slot == 3 || slot == 6 ? zgml::kQ3kBytes : zgml::kQ2kBytes;
 }
-float sb_value(uint32_t block_bytes, const uint8_t* blk, uint32_t e) {
-    switch (block_bytes) {
-    case zgml::kQ2kBytes: return zgml::q2k_value(blk, e);
-    case zgml::kQ3kBytes: return zgml::q3k_value(blk, e);
-    case zgml::kQ5kBytes: return zgml::q5k_value(blk, e);
-    case zgml::kQ6kBytes: return zgml::q6k_value(blk, e);
-    default: return zgml::q4k_value(blk, e);
-    }
-}
+constexpr SbMixRow kSbMixes[] = {
+    {WeightKind::q4_k_gguf, WeightKind::q4_k_dense, all_q4k},   {WeightKind::q4_k_m_gguf, WeightKind::q4_k_m_dense, q4_k_m},
+    {WeightKind::q5_k_m_gguf, WeightKind::q5_k_m_dense, q5_k_m}, {WeightKind::q3_k_m_gguf, WeightKind::q3_k_m_dense, q3_k_m},
+    {WeightKind::q2_k_gguf, WeightKind::q2_k_dense, q2_k},
+};
 
 void parallel_rows(size_t n, int threads, const std::function<void(size_t, size_t)>& fn) {
     threads = std::max(1, threads);
@@ -234,6 +204,12 @@ QWeightHost make_qweight(size_t K, size_t N_full, size_t n0, size_t N_loc, uint3
 }
 
 } // namespace
+
+const SbMixRow* sb_mix(WeightKind k) {
+    for (const SbMixRow& mix : kSbMixes)
+        if (mix.gguf == k || mix.dense == k) return &mix;
+    return nullptr;
+}
 
 std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightKind kind, int threads) {
     auto m = std::make_unique<LlamaModel>();
@@ -278,17 +254,18 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
         auto [n0, nl] = shard(cfg.vocab_size);
         m->qweights.push_back(make_qweight(d, cfg.vocab_size, n0, nl, cfg.n_layers * 8, kind, threads));
     }
-    const bool sb_model = (int)kind >= (int)WeightKind::q4_k_gguf; // every kind from q4_k_gguf on
+    const SbMixRow* sb_model = sb_mix(kind);
     if (sb_model) // N % 256 == 0: super-blocks of the type the kind's layout rule gives, from their own generators (the Q4_0 values are dropped); else Q4_0 file blocks below
         for (size_t wi = 0; wi < m->qweights.size(); wi++) {
             auto& q = m->qweights[wi];
             if (q.N % zgml::kQ4kBlock) continue;
             const uint32_t id = (uint32_t)(wi / 7 * 8 + wi % 7);
             q.gguf_block = zgml::kQ4kBlock;
-            q.gguf_block_bytes = sb_block_bytes(kind, wi, cfg.n_layers);
+            const SbTypeRow& type = sb_type(sb_model->block_bytes(wi, cfg.n_layers));
+            q.gguf_block_bytes = type.block_bytes;
             q.gguf.resize(q.K * q.N / zgml::kQ4kBlock * q.gguf_block_bytes);
             parallel_rows(q.K * q.N / zgml::kQ4kBlock, threads, [&](size_t b0, size_t b1) {
-                for (size_t b = b0; b < b1; b++) synth_sb_block(q.gguf_block_bytes, b, id, q.gguf.data() + b * q.gguf_block_bytes);
+                for (size_t b = b0; b < b1; b++) synth_sb_block(type, b, id, q.gguf.data() + b * q.gguf_block_bytes);
             });
             std::vector<int8_t>().swap(q.data);
             std::vector<float>().swap(q.scales);
@@ -315,11 +292,11 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
         for (auto& q : m->qweights) {
             std::vector<float> w(q.K * q.N);
             const uint8_t* g = q.gguf.data();
-            const bool sb = q.gguf_block == zgml::kQ4kBlock;
+            const SbTypeRow* type = q.gguf_block == zgml::kQ4kBlock ? &sb_type(q.gguf_block_bytes) : nullptr;
             parallel_rows(q.K, threads, [&](size_t k0, size_t k1) {
                 for (size_t i = k0 * q.N; i < k1 * q.N; i++) {
-                    if (sb) {
-                        w[i] = sb_value(q.gguf_block_bytes, g + i / zgml::kQ4kBlock * q.gguf_block_bytes, (uint32_t)(i % zgml::kQ4kBlock));
+                    if (type) {
+                        w[i] = type->value(g + i / zgml::kQ4kBlock * q.gguf_block_bytes, (uint32_t)(i % zgml::kQ4kBlock));
                     } else { // Q4_0 block: f16 scale, element e in the low (e even) / high nibble of byte e / 2, value = nibble - 8
                         const uint8_t* blk = g + i / 32 * 18;
                         const uint32_t e = (uint32_t)(i % 32);

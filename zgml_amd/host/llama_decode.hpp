@@ -61,13 +61,21 @@ LlamaConfig tiny_test();                 // small GQA config for parity tests
 //            < L/8: Q4_K), the rest Q2_K super-blocks (84 B; csrc/q2k.h)
 enum class WeightKind : int { q4_0 = 0, q8_0 = 1, f32_dense = 2, q4_0_gguf = 3, q4_k_gguf = 4, q4_k_dense = 5, q4_k_m_gguf = 6, q4_k_m_dense = 7,
                               q5_k_m_gguf = 8, q5_k_m_dense = 9, q3_k_m_gguf = 10, q3_k_m_dense = 11, q2_k_gguf = 12, q2_k_dense = 13 };
+// The super-block mixes, one row each (llama_decode.cpp: kSbMixes): the gguf kind, its dense twin and the layout rule that gives the
+// file block bytes (= the type) of weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) in a model of n_layers.
+// A new mix is a pair of enumerators, a row there and its pair in llama.py's DENSE_TWIN.
+struct SbMixRow {
+    WeightKind gguf, dense;
+    uint32_t (*block_bytes)(size_t wi, uint32_t n_layers);
+};
+const SbMixRow* sb_mix(WeightKind k); // the row whose gguf or dense kind is k, or nullptr (the kinds before q4_k_gguf)
 inline bool is_dense(WeightKind k) {
-    return k == WeightKind::f32_dense || k == WeightKind::q4_k_dense || k == WeightKind::q4_k_m_dense || k == WeightKind::q5_k_m_dense || k == WeightKind::q3_k_m_dense ||
-           k == WeightKind::q2_k_dense;
+    const SbMixRow* mix = sb_mix(k);
+    return k == WeightKind::f32_dense || (mix && mix->dense == k);
 }
 inline bool is_gguf(WeightKind k) {
-    return k == WeightKind::q4_0_gguf || k == WeightKind::q4_k_gguf || k == WeightKind::q4_k_m_gguf || k == WeightKind::q5_k_m_gguf || k == WeightKind::q3_k_m_gguf ||
-           k == WeightKind::q2_k_gguf;
+    const SbMixRow* mix = sb_mix(k);
+    return k == WeightKind::q4_0_gguf || (mix && mix->gguf == k);
 }
 
 struct QWeightHost {
