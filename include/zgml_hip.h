@@ -279,13 +279,18 @@ typedef struct zgml_program_io {
  *                                        value = d*(sc_s-32)*q (zgml_amd/csrc/q3k.h states it)
  *     data_len == rows*cols/256 * 84  -> Q2_K {scales[16], qs[64], f16 d, f16 dmin}, the bulk type of a Q2_K file: q is Q3_K's low
  *                                        rule, value = d*(scales[e/16] & 15)*q - dmin*(scales[e/16] >> 4) (zgml_amd/csrc/q2k.h)
- * Under block_size 256 `data_len` tells the five apart (84 / 110 / 144 / 176 / 210: for one block count no two coincide); the same
- * shape rule holds, and each type keeps the file's bits per weight on the device (Q6_K 6.5625, Q5_K 5.5, Q3_K 3.4375, Q2_K 2.625)
+ *     data_len == rows*cols/256 * 136 -> IQ4_XS {f16 d, u16 scales_h, scales_l[4], qs[128]}, the bulk type of an IQ4_XS file: element
+ *                                        32ib+j has the 6-bit scale ls = ((scales_l[ib>>1] >> 4(ib&1)) & 15) | ((scales_h >> 2ib) & 3) << 4
+ *                                        and the table index (qs[16ib+(j&15)] >> 4(j>>4)) & 15; value = d*(ls-32)*kvalues[index] with
+ *                                        the sixteen signed bytes kvalues of zgml_amd/csrc/iq4xs.h (a non-linear 4-bit quant)
+ * Under block_size 256 `data_len` tells the six apart (84 / 110 / 136 / 144 / 176 / 210: for one block count no two coincide); the same
+ * shape rule holds, and each type keeps the file's bits per weight on the device (Q6_K 6.5625, Q5_K 5.5, IQ4_XS 4.25, Q3_K 3.4375, Q2_K 2.625)
  * with kernels of its own, launched as Q4_K is. A file block is only 2-byte aligned; `data` needs no more than that. */
 #define ZGML_QW_GGUF_Q4_0_BLOCK_BYTES 18
 #define ZGML_QW_GGUF_Q8_0_BLOCK_BYTES 34
 #define ZGML_QW_GGUF_Q2_K_BLOCK_BYTES 84
 #define ZGML_QW_GGUF_Q3_K_BLOCK_BYTES 110
+#define ZGML_QW_GGUF_IQ4_XS_BLOCK_BYTES 136
 #define ZGML_QW_GGUF_Q4_K_BLOCK_BYTES 144
 #define ZGML_QW_GGUF_Q5_K_BLOCK_BYTES 176
 #define ZGML_QW_GGUF_Q6_K_BLOCK_BYTES 210

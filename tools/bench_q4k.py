@@ -1,6 +1,6 @@
-"""GGUF Q4_K, Q5_K, Q6_K, Q3_K and Q2_K (sb_kernels.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes
+"""GGUF Q4_K, Q5_K, Q6_K, Q3_K, Q2_K and IQ4_XS (sb_kernels.hip) next to Q4_0 on the same box in the same run: the M = 1 mat-vec against the K-on-lanes
 kernel and the M = 32 matmul against the tile kernel, at 4096^2, 4096 x 11008 and 4096 x 32000. Q4_0 and Q4_K stream 4.5 bit/weight,
-so their bytes per launch are equal and the times compare directly; Q5_K streams 176/144, Q6_K 210/144, Q3_K 110/144 and Q2_K 84/144 of that, so the GB/s are printed too. A ring of distinct matrices larger than the 256 MiB Infinity Cache
+so their bytes per launch are equal and the times compare directly; Q5_K streams 176/144, Q6_K 210/144, Q3_K 110/144, Q2_K 84/144 and IQ4_XS 136/144 of that, so the GB/s are printed too. A ring of distinct matrices larger than the 256 MiB Infinity Cache
 stands for a model; device-event time per launch over replays of a captured graph (zgml_hip_qmatmul_bench); the formats
 alternate within each repeat and every repeat is printed, so the spread shows next to the difference."""
 import argparse
@@ -12,7 +12,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from zgml_amd import Backend  # noqa: E402
 
-FMT = {"q4_0": 1, "q4_k": 2, "q5_k": 4, "q6_k": 3, "q3_k": 5, "q2_k": 6}  # the `q4` argument of zgml_hip_qmatmul_bench
+FMT = {"q4_0": 1, "q4_k": 2, "q5_k": 4, "q6_k": 3, "q3_k": 5, "q2_k": 6, "iq4_xs": 7}  # the `q4` argument of zgml_hip_qmatmul_bench
 
 
 def run(be, fmt, M, K, N, ring, iters):
@@ -47,5 +47,7 @@ if __name__ == "__main__":
                               "q5_k_over_q4_k": round(best["q5_k"] / best["q4_k"], 3),
                               "q5_k_over_q6_k": round(best["q5_k"] / best["q6_k"], 3),
                               "q3_k_over_q5_k": round(best["q3_k"] / best["q5_k"], 3),
-                              "q2_k_over_q5_k": round(best["q2_k"] / best["q5_k"], 3)}), flush=True)
+                              "q2_k_over_q5_k": round(best["q2_k"] / best["q5_k"], 3),
+                              "iq4_xs_over_q4_k": round(best["iq4_xs"] / best["q4_k"], 3),
+                              "iq4_xs_over_q5_k": round(best["iq4_xs"] / best["q5_k"], 3)}), flush=True)
     be.close()

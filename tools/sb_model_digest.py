@@ -1,4 +1,4 @@
-"""SHA-256 of every weight the host model builder makes for the file-block kinds (3-13): the qweight bytes of a gguf kind, the f32
+"""SHA-256 of every weight the host model builder makes for the file-block kinds (3-15): the qweight bytes of a gguf kind, the f32
 weight uploads of a dense kind, on preset("tiny") and on the all-256 config of the super-block tests. Two builds of the host
 library that print the same lines build the same synthetic models. No GPU."""
 import ctypes as C
@@ -17,7 +17,7 @@ def all_256():
 
 
 for name, cfg in (("tiny", llama.preset("tiny")), ("all-256", all_256())):
-    for kind in range(3, 14):
+    for kind in range(3, 16):
         m = llama.Model(cfg, kind)
         p, n = m.program, 7 * cfg.n_layers + (not cfg.tied_lm_head)
         blobs = [(q.data, q.data_len) for q in p.qweights[:p.n_qweights]] or [(u.host_ptr, u.size) for u in p.initial_uploads[:n]]

@@ -205,12 +205,14 @@ enum QWFormat : uint32_t {
     // high bits beside them (Q6_K / Q5_K), and the file's headers (Q6_K: int8 scales and f16 d) per (k, 256 columns); any M, their own
     // launcher, never fused, grouped or sharded. QW_SB4 is NOT QW_Q4K above, which is Q4_0 with K on lanes and has nothing to do
     // with Q4_K. Q3_K / Q2_K ("super-block 3 / 2-bit"): 8-byte items of 2-bit fields (Q3_K: a 4-byte plane of third bits beside them)
-    // and the file's scale bytes, d (and dmin) per (k, 256 columns), in the same cut.
+    // and the file's scale bytes, d (and dmin) per (k, 256 columns), in the same cut. IQ4_XS ("super-block 4-bit, indexed"): Q4_K's
+    // 16-byte items, whose nibbles index a table of sixteen signed bytes, and the file's 8-byte header per (k, 256 columns).
     QW_SB4 = 5,
     QW_SB6 = 6,
     QW_SB5 = 7,
     QW_SB3 = 8,
     QW_SB2 = 9,
+    QW_SB4X = 10,
 };
 // the GGUF super-block formats: plain launches of their own kernels for every M. What the callers need to know of each, once: the
 // pass-through form number (runtime.hip: gguf_form), the bytes of a 256-element file block, the code of the measurement entry
@@ -228,6 +230,7 @@ constexpr SbFormatRow kSbFormats[] = {
     {QW_SB5, 5, ZGML_QW_GGUF_Q5_K_BLOCK_BYTES, 4, "q5k-matvec", "q5k-matmul"},
     {QW_SB3, 6, ZGML_QW_GGUF_Q3_K_BLOCK_BYTES, 5, "q3k-matvec", "q3k-matmul"},
     {QW_SB2, 7, ZGML_QW_GGUF_Q2_K_BLOCK_BYTES, 6, "q2k-matvec", "q2k-matmul"},
+    {QW_SB4X, 8, ZGML_QW_GGUF_IQ4_XS_BLOCK_BYTES, 7, "iq4xs-matvec", "iq4xs-matmul"},
 };
 // the row with pick(row) true, or nullptr
 template <class Pick>
@@ -781,7 +784,7 @@ bool w8a8_applies(uint64_t K, uint64_t N, uint64_t bs);
 void w8a8_packed_bytes(uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
 void launch_pack_w8a8(hipStream_t s, const int8_t* raw_data, const float* raw_scales, const QWeightDev& out);
 void launch_w8a8_matvec(hipStream_t s, const QWeightDev& w, const float* x, float* dst);
-// GGUF super-block arm (Q4_K / Q5_K / Q6_K / Q3_K / Q2_K: sb_kernels.hip; formats: q4k.h, q5k.h, q6k.h, q3k.h, q2k.h): shapes it takes (N a multiple of 256, the
+// GGUF super-block arm (Q4_K / Q5_K / Q6_K / Q3_K / Q2_K / IQ4_XS: sb_kernels.hip; formats: q4k.h, q5k.h, q6k.h, q3k.h, q2k.h, iq4xs.h): shapes it takes (N a multiple of 256, the
 // same set for all three), sizes of a format's packed image (4.5 / 5.5 / 6.5625 bit/weight like the file), the device re-pack of
 // the file's super-blocks and the micro-benchmark's synthetic weights (out.format / w.format selects which), the scratch an M = 1
 // launch splits K through (the same block and counter head as qmatmul_scratch_bytes describes below) and the launch for any M

@@ -47,8 +47,8 @@ void fill_caps(zgml_capabilities* c) {
 }
 
 // packed-GGUF pass-through (include/zgml_hip.h): 0 = reference form, 1 = Q4_0 blocks, 2 = Q8_0 blocks, 3 = Q4_K, 4 = Q6_K, 5 = Q5_K,
-// 6 = Q3_K and 7 = Q2_K super-blocks (kSbFormats; block_size tells Q4_K from Q4_0: 144 B per 256 elements and 18 B per 32 are the same
-// data_len; data_len tells the five super-block types apart: 84 / 110 / 144 / 176 / 210 B per 256 elements)
+// 6 = Q3_K, 7 = Q2_K and 8 = IQ4_XS super-blocks (kSbFormats; block_size tells Q4_K from Q4_0: 144 B per 256 elements and 18 B per 32 are
+// the same data_len; data_len tells the six super-block types apart: 84 / 110 / 136 / 144 / 176 / 210 B per 256 elements)
 int gguf_form(const zgml_qweight_upload& qw) {
     if (qw.scales || qw.scales_len || !qw.data) return 0;
     const uint64_t n = qw.rows * qw.cols;

@@ -5,7 +5,7 @@
 
 extern "C" {
 
-// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K, 3 = GGUF Q6_K, 4 = GGUF Q5_K, 5 = GGUF Q3_K, 6 = GGUF Q2_K (kSbFormats' bench codes; sb_kernels.hip)
+// q4: 0 = Q8_0, 1 = Q4_0, 2 = GGUF Q4_K, 3 = GGUF Q6_K, 4 = GGUF Q5_K, 5 = GGUF Q3_K, 6 = GGUF Q2_K, 7 = GGUF IQ4_XS (kSbFormats' bench codes; sb_kernels.hip)
 static bool make_synth_weight(zgml_hip_ctx* ctx, uint32_t K, uint32_t N, int q4, uint32_t id, QWeightDev* w, uint32_t M = 1) {
     if (const SbFormatRow* sb = sb_format_row([&](const SbFormatRow& f) { return f.bench_code == q4; })) {
         if (!sb_applies(K, N)) return false;

@@ -1,6 +1,6 @@
-// sb_kernels.h — the GGUF super-block weights on the device (QW_SB4 / QW_SB5 / QW_SB6 / QW_SB3 / QW_SB2 = Q4_K / Q5_K / Q6_K / Q3_K /
-// Q2_K; q4k.h, q5k.h, q6k.h, q3k.h and q2k.h state the file formats): what each format states, once, and the device functions every
-// super-block kernel is built from. The kernels and their launchers are sb_kernels.hip.
+// sb_kernels.h — the GGUF super-block weights on the device (QW_SB4 / QW_SB5 / QW_SB6 / QW_SB3 / QW_SB2 / QW_SB4X = Q4_K / Q5_K / Q6_K /
+// Q3_K / Q2_K / IQ4_XS; q4k.h, q5k.h, q6k.h, q3k.h, q2k.h and iq4xs.h state the file formats): what each format states, once, and the
+// device functions every super-block kernel is built from. The kernels and their launchers are sb_kernels.hip.
 //
 // COMMON DEVICE LAYOUT. A weight is cut into ITEMS [N / 32][K]: item (j, k) holds the 32 q of columns 32 j .. 32 j + 31 at row k,
 // so 64 consecutive k of one j are contiguous and a wave (lane = k) streams them coalesced. QWeightDev::qs holds the item planes:
@@ -10,22 +10,27 @@
 // Q3_K / Q2_K have a 2-BIT low plane instead, 8 B per item: dword h = columns 16 h .. + 15, bits 2 s .. 2 s + 1 of byte b = column
 // 16 h + 4 s + b (Q6_K's high-pair layout), so the four q of a dword come out by one shift and one AND; Q3_K's third bit is a
 // 4-byte high plane in Q5_K's layout (sb_quants2).
+// IQ4_XS has the 16-byte low plane alone, and its nibbles are INDICES into a table of sixteen signed bytes: the file's 16 qs bytes of a
+// sub-block already are the low-plane entry, and sb_codebook4 turns a dword of four indices into a dword of four table bytes in registers.
 // QWeightDev::sc holds the FACTOR planes [N / 256][K], one entry per (k, super-block column): Q4_K / Q5_K the file's 16-byte header
 // {d, dmin, scales[12]} as it is (Q4kHeader dwords); Q6_K the file's 16 int8 scales (16 B), then a plane of its f16 d (2 B); Q3_K
-// the file's twelve scale bytes as they are (12 B), then a plane of d; Q2_K the file's 16 scale bytes, then a plane of d | dmin << 16.
+// the file's twelve scale bytes as they are (12 B), then a plane of d; Q2_K the file's 16 scale bytes, then a plane of d | dmin << 16;
+// IQ4_XS the file's 8-byte header {d, scales_h, scales_l[4]} as it is.
 //
 // ARITHMETIC. y[n] = sum_k (x[k] * d * sc) * (q - bias)  [ -  sum_k x[k] * dmin * m ]. d * sc and dmin * m are formed in f32
 // (exact), never rounded to f16. Q4_K / Q5_K: one (d * sc, dmin * m) pair per item, bias 0, the min sum kept apart and formed once
 // per 32 columns. Q6_K: two d * sc per item (one per 16 columns), the signed integer q - 32 as the operand (a weight of q = 32
 // contributes an exact zero) and nothing summed apart. Q3_K: as Q6_K with q - 4 and d * (sc - 32). Q2_K: two (d * sc, dmin * m)
-// pairs per item, bias 0, and TWO min sums per item, one per 16 columns.
+// pairs per item, bias 0, and TWO min sums per item, one per 16 columns. IQ4_XS: ONE d * (ls - 32) per item and no min; the operand is
+// the signed table byte itself (kSbSigned), converted by one sign-extending byte convert.
 //
-// A FORMAT (Sb4, Sb5, Sb6, Sb3, Sb2 below) is a plain struct of constants and static functions, no more: the file block bytes, its planes
+// A FORMAT (Sb4, Sb5, Sb6, Sb3, Sb2, Sb4x below) is a plain struct of constants and static functions, no more: the file block bytes, its planes
 // and how qs / sc are cut into them, the high-plane load, quants(), how many d * sc an item has, whether a min sum exists, the
 // operand bias, where its factors come from (per 64-k chunk for M > 1, per 256-k round for M = 1), its pack rule, its synth
 // pattern and its name. Everything else here is shared: the lane fold, the M = 1 tail through sb_combine, byte -> f32 / bf16 with
 // the bias, the three-piece bf16 split, the [column][k] turn and the wave-order fold and store.
 #pragma once
+#include "iq4xs.h"
 #include "q2k.h"
 #include "q5k.h"
 #include "q6k.h"
@@ -42,6 +47,7 @@ constexpr uint32_t kSbSweeps = 4;  // sweeps of a round (Q5_K, Q6_K): all loaded
 constexpr uint32_t kSbRound = kSbSweep * kSbSweeps; // k of a round = rows of the factors in LDS
 static_assert(kQ4kBlock == kSbBlock && kQ5kBlock == kSbBlock && kQ6kBlock == kSbBlock && kQ4kSub == kSbItem && kQ5kSub == kSbItem && 2 * kQ6kSub == kSbItem, "");
 static_assert(kQ3kBlock == kSbBlock && kQ2kBlock == kSbBlock && 2 * kQ3kSub == kSbItem && 2 * kQ2kSub == kSbItem, "");
+static_assert(kIq4xsBlock == kSbBlock && kIq4xsSub == kSbItem, "");
 static_assert(kSbWaves * kSbItem == kSbBlock && kSbWaves * 64 == 2 * kSbRound, "the factor duty of a round: one k and half of its factors per thread");
 
 typedef float sb_f4 __attribute__((ext_vector_type(4)));
@@ -79,9 +85,24 @@ __device__ __forceinline__ void sb_quants2(uint2 lo, uint32_t hi, uint32_t (&q)[
 // the Q4_K / Q5_K header of one (k, super-block column) -> (d * sc, dmin * m) of sub-block j
 __device__ __forceinline__ Q4kFactors sb_header_factors(uint4 h, uint32_t j) { return q4k_factors(Q4kHeader{{h.x, h.y, h.z, h.w}}, j); }
 
-// byte b of a quant dword as the f32 operand q - BIAS
+// IQ4_XS: a dword of four table indices (0..15 each, as sb_quants<0> leaves them) -> the dword of their four signed table bytes.
+// The table is four dword constants; v_perm_b32 picks any byte of a register pair by a selector byte 0..7 (larger selectors mean
+// other things to the instruction, hence idx & 7): one perm over entries 0..7, one over 8..15, and a third perm takes byte b from the
+// second where bit 3 of index b is set (selector b or 4 + b). Six VALU per four weights, no LDS table, no per-weight lookup. (The third
+// perm stands where a bit-field insert under a byte mask would: its selector is a shift and an AND-OR, the mask a shift, an AND, a
+// shift and a subtraction.)
+__device__ __forceinline__ uint32_t sb_codebook4(uint32_t idx) {
+    constexpr uint32_t t0 = iq4xs_table_dword(0), t1 = iq4xs_table_dword(1), t2 = iq4xs_table_dword(2), t3 = iq4xs_table_dword(3);
+    const uint32_t sel = idx & 0x07070707u;
+    const uint32_t low = __builtin_amdgcn_perm(t1, t0, sel), high = __builtin_amdgcn_perm(t3, t2, sel);
+    return __builtin_amdgcn_perm(high, low, ((idx >> 1) & 0x04040404u) | 0x03020100u);
+}
+
+// byte b of a quant dword as the f32 operand q - BIAS; BIAS = kSbSigned: the byte is a signed value itself
+constexpr int kSbSigned = -1;
 template <int BIAS>
 __device__ __forceinline__ float sb_operand(uint32_t dword, int b) {
+    if constexpr (BIAS == kSbSigned) return (float)(int)(int8_t)(dword >> (8 * b));
     const float q = (float)((dword >> (8 * b)) & 255u);
     if constexpr (BIAS != 0) return q - (float)BIAS;
     return q;
@@ -585,6 +606,69 @@ struct Sb2 {
             o.sc[idx] = make_uint4(a * 23u, a * 11u, a * 13u, a * 29u);
             o.dm[idx] = 0x90001400u; // d = 2^-10, dmin = -2^-11
         }
+    }
+};
+
+// IQ4_XS: Q4_K's bytes per item, the codebook in place of the nibble's own value, one scale per item and no min
+struct Sb4x {
+    static constexpr QWFormat kFormat = QW_SB4X;
+    static constexpr const char* kName = "IQ4_XS";
+    static constexpr uint32_t kFileBytes = kIq4xsBytes, kItemBytes = 16, kFactorBytes = kIq4xsHeaderBytes; // 4.25 bit/weight like the file
+    static constexpr uint32_t kScales = 1, kNtMaxM = 32;
+    static constexpr bool kMin = false, kRound = true;
+    static constexpr int kBias = kSbSigned;
+    using Lo = uint4;
+    using Hi = SbNoHi;
+    struct Planes {
+        Lo* lo;
+        uint2* hdr; // d | scales_h << 16, scales_l[4]
+    };
+    static Planes planes(const QWeightDev& w) { return {(Lo*)w.qs, (uint2*)w.sc}; }
+    __device__ static __forceinline__ Planes at(Planes p, uint64_t item, uint64_t factor) { return {p.lo + item, p.hdr + factor}; }
+    template <bool NT>
+    __device__ static __forceinline__ Lo load_lo(const Planes& c, uint32_t k) {
+        return wload<NT>(c.lo + k);
+    }
+    template <bool NT>
+    __device__ static __forceinline__ Hi load_hi(const Planes&, uint32_t) {
+        return {};
+    }
+    // the indices, then the table bytes: what the FMAs convert and what the turn leaves in LDS are table values
+    __device__ static __forceinline__ void quants(Lo lo, Hi, uint32_t (&q)[8]) {
+        sb_quants<0>(lo, 0, 0, q);
+#pragma unroll
+        for (int d = 0; d < 8; d++) q[d] = sb_codebook4(q[d]);
+    }
+    __device__ static __forceinline__ void chunk_factors(const Planes& c, uint32_t k, uint32_t js, float (&f)[1], float (&)[1]) {
+        const uint2 h = c.hdr[k];
+        f[0] = iq4xs_factor(h.x, h.y, js);
+    }
+    // [sub-block][k] of d * (ls - 32): a wave reads its own sub-block's factor of 64 k as one conflict-free read per lane. A thread turns
+    // the four scales of its half: the header shifted once by the half, then constant fields
+    using RoundLds = float[kSbWaves][kSbRound];
+    using RoundRaw = uint2; // the header
+    __device__ static __forceinline__ RoundRaw round_load(const Planes& c, uint32_t k, uint32_t) { return c.hdr[k]; }
+    __device__ static __forceinline__ void round_store(RoundLds& ds, const RoundRaw& raw, uint32_t kl, uint32_t half, bool live) {
+        const float d = q4k_f16((uint16_t)(raw.x & 0xFFFFu));
+        const uint32_t h0 = raw.x >> (8 * half), h1 = raw.y >> (16 * half); // sub-block 4 half + e: iq4xs_scale's fields of e
+#pragma unroll
+        for (uint32_t e = 0; e < 4; e++) {
+            const float ds_e = d * (float)iq4xs_scale(h0, h1, e);
+            ds[half * 4 + e][kl] = live ? ds_e : 0.f;
+        }
+    }
+    __device__ static __forceinline__ void item_factors(const RoundLds& ds, uint32_t w, uint32_t kl, float x, float (&t)[1], float (&)[1]) { t[0] = x * ds[w][kl]; }
+    // (136 = 17 * 8: every file block is 8-byte aligned.) The file's 16 qs bytes of sub-block js are the low-plane entry as it is: byte
+    // b = index of column b | index of column b + 16 << 4
+    __device__ static __forceinline__ void pack_item(const uint8_t* blk, uint32_t js, const Planes& o, uint64_t idx) {
+        const uint2* src = (const uint2*)(blk + kIq4xsQsOffset + 16 * js);
+        const uint2 a = src[0], b = src[1];
+        o.lo[idx] = make_uint4(a.x, a.y, b.x, b.y);
+    }
+    __device__ static __forceinline__ void pack_factors(const uint8_t* blk, const Planes& o, uint64_t fidx) { o.hdr[fidx] = *(const uint2*)blk; }
+    __device__ static __forceinline__ void synth(const Planes& o, uint64_t idx, uint32_t a, bool factors) { // (every index; ls over its range)
+        o.lo[idx] = make_uint4(a, a * 3u + 1u, a * 5u + 2u, a * 7u + 3u);
+        if (factors) o.hdr[idx] = make_uint2(0x1400u /* d = 2^-10 */ | (a * 23u << 16), a * 11u);
     }
 };
 

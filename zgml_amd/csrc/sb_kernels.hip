@@ -1,5 +1,5 @@
-// sb_kernels.hip — the kernels and launchers of the GGUF super-block weights (Q4_K / Q5_K / Q6_K / Q3_K / Q2_K); sb_kernels.h states the
-// layout, the arithmetic, the five formats and the device functions the kernels below are built from. Nothing here is shared
+// sb_kernels.hip — the kernels and launchers of the GGUF super-block weights (Q4_K / Q5_K / Q6_K / Q3_K / Q2_K / IQ4_XS); sb_kernels.h states the
+// layout, the arithmetic, the six formats and the device functions the kernels below are built from. Nothing here is shared
 // with the 32-block formats (and QW_Q4K, "Q4_0 with K on lanes", is none of these).
 //
 // M = 1. A workgroup of 8 waves owns one super-block column and one K share; wave w streams item column w, lane = k. A lane
@@ -7,7 +7,7 @@
 // columns than the part has wave slots the K range is split over blockIdx.y; every part stores its 256 partial outputs and the
 // LAST part to arrive (an integer counter; no float atomics) adds them in part order, so the bytes do not depend on arrival order
 // (sb_combine.h).
-//   Q5_K, Q6_K, Q3_K, Q2_K (sb_round_matvec_kernel): the share is walked in ROUNDS of four 64-k sweeps, and a round issues every load it has
+//   Q5_K, Q6_K, Q3_K, Q2_K, IQ4_XS (sb_round_matvec_kernel): the share is walked in ROUNDS of four 64-k sweeps, and a round issues every load it has
 //   — the workgroup's factors first, then per wave four lo items, four hi items and four x — before anything is consumed: 5.25 /
 //   6 / 3.25 / 2.25 KiB in flight per wave. While the items fly the 512 threads turn the round's 256 factor entries into f32 products in LDS,
 //   once per workgroup. K is split into parts of whole rounds until the grid has about two workgroups per CU (at most 16 parts).
@@ -19,8 +19,9 @@
 // chunk's two factor rows beside them. B = q - bias, exact in bf16; A = t = x * (d * sc) in f32, split into three bf16 pieces,
 // contracted by v_mfma_f32_16x16x32_bf16 with f32 accumulation: three MFMAs per tile and 32 k. The min term is 8 VALU FMAs per
 // (row tile, 32 k) beside them, folded over the four lane rows at the end. Waves are folded in wave order.
-//   Q5_K, Q6_K, Q3_K, Q2_K (sb_matmul_kernel<F, RT>): 8 waves, RT = 1 or 2 row tiles of 16; the turned bytes are the assembled q. The B of a
-//   column tile serves both row tiles. With ONE d * sc per item (Q5_K) A is formed once per (row tile, 32 k) and feeds both
+//   Q5_K, Q6_K, Q3_K, Q2_K, IQ4_XS (sb_matmul_kernel<F, RT>): 8 waves, RT = 1 or 2 row tiles of 16; the turned bytes are the assembled q
+//   (IQ4_XS: the table values, looked up once per chunk in front of the turn). The B of a
+//   column tile serves both row tiles. With ONE d * sc per item (Q5_K, IQ4_XS) A is formed once per (row tile, 32 k) and feeds both
 //   column tiles; with two (Q6_K, Q3_K, Q2_K: a column tile is exactly one scale sub-block) A is per (row tile, column tile), and
 //   Q2_K's min sum is per (row tile, column tile) as well.
 //   Q4_K (sb4_matmul_kernel): 4 waves, one row tile; the turned byte keeps the nibble pair (columns i and i + 16), so the two
@@ -240,7 +241,7 @@ __global__ void __launch_bounds__(kSbMmWaves * 64) sb_matmul_kernel(SbMmArgs<F> 
             if constexpr (F::kScales == 1) { // one A per row tile, for both column tiles
                 float sv[8], mv[8];
                 sb_read8(&fs[w][0][kl], sv);
-                sb_read8(&fm[w][0][kl], mv);
+                if constexpr (F::kMin) sb_read8(&fm[w][0][kl], mv); // (IQ4_XS: one scale and no min row)
                 sb_bf8 qv[2]; // B of the two column tiles: column 16 ct + i
 #pragma unroll
                 for (int ct = 0; ct < 2; ct++) qv[ct] = sb_fragment<F::kBias>(sb_turned8(turned[w], 16 * ct + i, kl));
@@ -394,6 +395,7 @@ auto sb_dispatch(QWFormat format, Fn fn) {
     case Sb6::kFormat: return fn(Sb6{});
     case Sb3::kFormat: return fn(Sb3{});
     case Sb2::kFormat: return fn(Sb2{});
+    case Sb4x::kFormat: return fn(Sb4x{});
     default: break;
     }
     fprintf(stderr, "[zgml_hip] ERROR: weight format %u is no super-block format\n", (uint32_t)format);

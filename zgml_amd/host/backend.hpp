@@ -221,8 +221,8 @@ struct QuantizedWeightUpload {
     static QuantizedWeightUpload ggufBlocks(const uint8_t* blocks, size_t n_bytes, size_t rows, size_t cols) {
         return {reinterpret_cast<const int8_t*>(blocks), n_bytes, nullptr, 0, rows, cols, 32};
     }
-    // ... or its Q2_K (84-byte) / Q3_K (110-byte) / Q4_K (144-byte) / Q5_K (176-byte) / Q6_K (210-byte) super-blocks, 256 consecutive
-    // columns of a row each: block_size 256 tells Q4_K from Q4_0, n_bytes the five super-block types apart
+    // ... or its Q2_K (84-byte) / Q3_K (110-byte) / IQ4_XS (136-byte) / Q4_K (144-byte) / Q5_K (176-byte) / Q6_K (210-byte) super-blocks, 256
+    // consecutive columns of a row each: block_size 256 tells Q4_K from Q4_0, n_bytes the six super-block types apart
     static QuantizedWeightUpload ggufSuperBlocks(const uint8_t* blocks, size_t n_bytes, size_t rows, size_t cols) {
         return {reinterpret_cast<const int8_t*>(blocks), n_bytes, nullptr, 0, rows, cols, 256};
     }
@@ -232,8 +232,8 @@ struct QuantizedWeightUpload {
         int form;
         size_t block_bytes;
     } kSbForms[] = {{3, ZGML_QW_GGUF_Q4_K_BLOCK_BYTES}, {4, ZGML_QW_GGUF_Q6_K_BLOCK_BYTES}, {5, ZGML_QW_GGUF_Q5_K_BLOCK_BYTES},
-                    {6, ZGML_QW_GGUF_Q3_K_BLOCK_BYTES}, {7, ZGML_QW_GGUF_Q2_K_BLOCK_BYTES}};
-    int ggufForm() const { // 1 = Q4_0, 2 = Q8_0, 3 = Q4_K, 4 = Q6_K, 5 = Q5_K, 6 = Q3_K, 7 = Q2_K
+                    {6, ZGML_QW_GGUF_Q3_K_BLOCK_BYTES}, {7, ZGML_QW_GGUF_Q2_K_BLOCK_BYTES}, {8, ZGML_QW_GGUF_IQ4_XS_BLOCK_BYTES}};
+    int ggufForm() const { // 1 = Q4_0, 2 = Q8_0, 3 = Q4_K, 4 = Q6_K, 5 = Q5_K, 6 = Q3_K, 7 = Q2_K, 8 = IQ4_XS
         if (scales || scales_len || !data) return 0;
         const size_t n = rows * cols;
         if (block_size == 256) {

@@ -253,7 +253,7 @@ uint64_t zh_model_quant_bytes(zh_model* m, uint64_t* n_weights) { // Q4_0/Q8_0 f
     for (const auto& q : m->model->qweights) elems += q.K * q.N;
     if (n_weights) *n_weights = elems;
     if (is_dense(m->model->kind)) return elems * 2; // f16-promoted bytes
-    uint64_t bytes = 0; // (Q4_K: 144 B per 256 elements, the same 4.5 bit/weight as Q4_0's 18 B per 32; Q2_K: 84, Q3_K: 110, Q5_K: 176, Q6_K: 210 B per 256)
+    uint64_t bytes = 0; // (Q4_K: 144 B per 256 elements, the same 4.5 bit/weight as Q4_0's 18 B per 32; Q2_K: 84, Q3_K: 110, IQ4_XS: 136, Q5_K: 176, Q6_K: 210 B per 256)
     for (const auto& q : m->model->qweights)
         bytes += q.gguf_block == 256 ? q.K * q.N / 256 * q.gguf_block_bytes : q.K * q.N / 32 * (m->model->kind == WeightKind::q8_0 ? 34 : 18);
     return bytes;

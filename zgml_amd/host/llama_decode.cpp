@@ -4,6 +4,7 @@
 #endif
 #include "llama_decode.hpp"
 
+#include "../csrc/iq4xs.h"
 #include "../csrc/q2k.h"
 #include "../csrc/q3k.h"
 #include "../csrc/q4k.h"
@@ -113,7 +114,8 @@ struct SbTypeRow {
 };
 // d, dmin in the normal f16 range; every other byte hashed, so the scales (sc, m) and q run over all their values:
 //   Q2_K sc, m 0..15, q 0..3, |w| < 0.14;  Q3_K sc - 32 -32..31, q -4..3, |w| < 0.12;  Q4_K sc, m 0..63, q 0..15, |w| < 0.2;
-//   Q5_K Q4_K's header at half the d (q 0..31), |w| < 0.2;  Q6_K int8 scales, q - 32 -32..31, |w| < 0.47;  all mostly far below.
+//   Q5_K Q4_K's header at half the d (q 0..31), |w| < 0.2;  Q6_K int8 scales, q - 32 -32..31, |w| < 0.47;  IQ4_XS ls - 32 -32..31, table
+//   values -127..113, |w| <= 4064 |d| < 0.25;  all mostly far below.
 // Q4_K's hash numbers start at its byte 4 (hash_base 4); the later types number the hashes by the byte.
 constexpr SbTypeRow kSbTypes[] = {
     {zgml::kQ2kBytes, zgml::q2k_value, 0xD3A2646Cu, -10, -9, zgml::kQ2kDOffset, zgml::kQ2kDOffset + 2, 0, zgml::kQ2kDOffset, 0},
@@ -121,6 +123,7 @@ constexpr SbTypeRow kSbTypes[] = {
     {zgml::kQ4kBytes, zgml::q4k_value, 0x85EBCA6Bu, -14, -11, 0, 2, 4, zgml::kQ4kBytes, 4},
     {zgml::kQ5kBytes, zgml::q5k_value, 0x27D4EB2Fu, -15, -11, 0, 2, 4, zgml::kQ5kBytes, 0},
     {zgml::kQ6kBytes, zgml::q6k_value, 0xC2B2AE35u, -14, kNoDmin, zgml::kQ6kDOffset, 0, 0, zgml::kQ6kDOffset, 0},
+    {zgml::kIq4xsBytes, zgml::iq4xs_value, 0x9E3779B1u, -15, kNoDmin, 0, 0, 2, zgml::kIq4xsBytes, 0},
 };
 const SbTypeRow& sb_type(uint32_t block_bytes) {
     for (const SbTypeRow& t : kSbTypes)
@@ -141,7 +144,7 @@ void synth_sb_block(const SbTypeRow& t, uint64_t sb, uint32_t id, uint8_t* blk) 
 }
 
 // The layout rules of GGUF writers for the LLaMA architecture (llama_decode.hpp states them per kind): the type of weight `wi`
-uint32_t all_q4k(size_t, uint32_t) { return zgml::kQ4kBytes; }
+uint32_t all_q4k(size_t, const LlamaConfig&) { return zgml::kQ4kBytes; }
 // Q4_K_M / Q5_K_M: does `wi` take Q6_K?
 bool q4_k_m_takes_q6k(size_t wi, uint32_t n_layers) {
     const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7), e = n_layers / 8;
@@ -149,25 +152,32 @@ bool q4_k_m_takes_q6k(size_t wi, uint32_t n_layers) {
     if (slot != 2 && slot != 6) return false; // attn_v and ffn_down of the "more bits" layers
     return l < e || l >= 7 * n_layers / 8 || (l - e) % 3 == 2;
 }
-uint32_t q4_k_m(size_t wi, uint32_t n_layers) { return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ4kBytes; }
-uint32_t q5_k_m(size_t wi, uint32_t n_layers) { return q4_k_m_takes_q6k(wi, n_layers) ? zgml::kQ6kBytes : zgml::kQ5kBytes; }
-uint32_t q3_k_m(size_t wi, uint32_t n_layers) {
-    const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7); // slot: q, k, v, o, gate, up, down
+uint32_t q4_k_m(size_t wi, const LlamaConfig& cfg) { return q4_k_m_takes_q6k(wi, cfg.n_layers) ? zgml::kQ6kBytes : zgml::kQ4kBytes; }
+uint32_t q5_k_m(size_t wi, const LlamaConfig& cfg) { return q4_k_m_takes_q6k(wi, cfg.n_layers) ? zgml::kQ6kBytes : zgml::kQ5kBytes; }
+uint32_t q3_k_m(size_t wi, const LlamaConfig& cfg) {
+    const uint32_t n_layers = cfg.n_layers, l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7); // slot: q, k, v, o, gate, up, down
     if (l >= n_layers) return zgml::kQ6kBytes;
     if (slot == 2) return l < 2 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
     if (slot == 6) return l < n_layers / 16 ? zgml::kQ5kBytes : zgml::kQ4kBytes;
     return slot == 3 ? zgml::kQ4kBytes : zgml::kQ3kBytes;
 }
-uint32_t q2_k(size_t wi, uint32_t n_layers) {
-    const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7);
+uint32_t q2_k(size_t wi, const LlamaConfig& cfg) {
+    const uint32_t n_layers = cfg.n_layers, l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7);
     if (l >= n_layers) return zgml::kQ6kBytes;
     if (slot == 6 && l < n_layers / 8) return zgml::kQ4kBytes;
     return slot == 2 || slot == 3 || slot == 6 ? zgml::kQ3kBytes : zgml::kQ2kBytes;
 }
+uint32_t iq4_xs(size_t wi, const LlamaConfig& cfg) {
+    const uint32_t l = (uint32_t)(wi / 7), slot = (uint32_t)(wi % 7);
+    if (l >= cfg.n_layers) return zgml::kQ6kBytes;
+    if (slot == 2 && cfg.n_heads / cfg.n_kv_heads >= 4) return zgml::kQ5kBytes;
+    if (slot == 6 && l < cfg.n_layers / 8) return zgml::kQ5kBytes;
+    return zgml::kIq4xsBytes;
+}
 constexpr SbMixRow kSbMixes[] = {
     {WeightKind::q4_k_gguf, WeightKind::q4_k_dense, all_q4k},   {WeightKind::q4_k_m_gguf, WeightKind::q4_k_m_dense, q4_k_m},
     {WeightKind::q5_k_m_gguf, WeightKind::q5_k_m_dense, q5_k_m}, {WeightKind::q3_k_m_gguf, WeightKind::q3_k_m_dense, q3_k_m},
-    {WeightKind::q2_k_gguf, WeightKind::q2_k_dense, q2_k},
+    {WeightKind::q2_k_gguf, WeightKind::q2_k_dense, q2_k},       {WeightKind::iq4_xs_gguf, WeightKind::iq4_xs_dense, iq4_xs},
 };
 
 void parallel_rows(size_t n, int threads, const std::function<void(size_t, size_t)>& fn) {
@@ -261,7 +271,7 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
             if (q.N % zgml::kQ4kBlock) continue;
             const uint32_t id = (uint32_t)(wi / 7 * 8 + wi % 7);
             q.gguf_block = zgml::kQ4kBlock;
-            const SbTypeRow& type = sb_type(sb_model->block_bytes(wi, cfg.n_layers));
+            const SbTypeRow& type = sb_type(sb_model->block_bytes(wi, cfg));
             q.gguf_block_bytes = type.block_bytes;
             q.gguf.resize(q.K * q.N / zgml::kQ4kBlock * q.gguf_block_bytes);
             parallel_rows(q.K * q.N / zgml::kQ4kBlock, threads, [&](size_t b0, size_t b1) {
@@ -288,7 +298,7 @@ std::unique_ptr<LlamaModel> make_synthetic_model(const LlamaConfig& cfg, WeightK
             std::vector<float>().swap(q.scales);
         }
     }
-    if (sb_model && is_dense(kind)) { // the gguf twin, dequantised by the formats' own rules (csrc/q2k.h .. q6k.h); file blocks dropped
+    if (sb_model && is_dense(kind)) { // the gguf twin, dequantised by the formats' own rules (csrc/q2k.h .. q6k.h, iq4xs.h); file blocks dropped
         for (auto& q : m->qweights) {
             std::vector<float> w(q.K * q.N);
             const uint8_t* g = q.gguf.data();

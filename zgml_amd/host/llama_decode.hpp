@@ -59,14 +59,19 @@ LlamaConfig tiny_test();                 // small GQA config for parity tests
 //            super-blocks (110 B; csrc/q3k.h)
 // q2_k_gguf / q2_k_dense: the Q2_K mix and its f32 twin: the head Q6_K, attn_v, attn_output and ffn_down Q3_K (ffn_down of layers
 //            < L/8: Q4_K), the rest Q2_K super-blocks (84 B; csrc/q2k.h)
+// iq4_xs_gguf / iq4_xs_dense: the IQ4_XS mix and its f32 twin: the head Q6_K, attn_v Q5_K when n_heads / n_kv_heads >= 4, ffn_down Q5_K in
+//            layers < L/8, the rest IQ4_XS super-blocks (136 B; csrc/iq4xs.h). These promotions are written from memory of the public
+//            writer's rules and nothing here checks them against a file; a real file does not depend on them, because each tensor is
+//            recognised by its own data_len
 enum class WeightKind : int { q4_0 = 0, q8_0 = 1, f32_dense = 2, q4_0_gguf = 3, q4_k_gguf = 4, q4_k_dense = 5, q4_k_m_gguf = 6, q4_k_m_dense = 7,
-                              q5_k_m_gguf = 8, q5_k_m_dense = 9, q3_k_m_gguf = 10, q3_k_m_dense = 11, q2_k_gguf = 12, q2_k_dense = 13 };
+                              q5_k_m_gguf = 8, q5_k_m_dense = 9, q3_k_m_gguf = 10, q3_k_m_dense = 11, q2_k_gguf = 12, q2_k_dense = 13,
+                              iq4_xs_gguf = 14, iq4_xs_dense = 15 };
 // The super-block mixes, one row each (llama_decode.cpp: kSbMixes): the gguf kind, its dense twin and the layout rule that gives the
-// file block bytes (= the type) of weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) in a model of n_layers.
+// file block bytes (= the type) of weight `wi` (per layer q, k, v, o, gate, up, down; then the untied LM head) in a model of config cfg.
 // A new mix is a pair of enumerators, a row there and its pair in llama.py's DENSE_TWIN.
 struct SbMixRow {
     WeightKind gguf, dense;
-    uint32_t (*block_bytes)(size_t wi, uint32_t n_layers);
+    uint32_t (*block_bytes)(size_t wi, const LlamaConfig& cfg);
 };
 const SbMixRow* sb_mix(WeightKind k); // the row whose gguf or dense kind is k, or nullptr (the kinds before q4_k_gguf)
 inline bool is_dense(WeightKind k) {
@@ -83,7 +88,7 @@ struct QWeightHost {
     std::vector<float> scales;
     std::vector<uint8_t> gguf; // the *_gguf kinds: the file blocks (data / scales dropped)
     uint32_t gguf_block = 32;  // ... their elements: 32 (Q4_0) or 256 (the k-quants)
-    uint32_t gguf_block_bytes = 18; // ... and their bytes, which say the form: 18 (Q4_0), 84 (Q2_K), 110 (Q3_K), 144 (Q4_K), 176 (Q5_K) or 210 (Q6_K)
+    uint32_t gguf_block_bytes = 18; // ... and their bytes, which say the form: 18 (Q4_0), 84 (Q2_K), 110 (Q3_K), 136 (IQ4_XS), 144 (Q4_K), 176 (Q5_K) or 210 (Q6_K)
     size_t K = 0, N = 0; // rows, cols
 };
 

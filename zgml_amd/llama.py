@@ -22,8 +22,11 @@ Q5_K_M_GGUF, Q5_K_M_DENSE = 8, 9
 # attn_v, attn_output and ffn_down; Q6_K head), each with its f32 twin
 Q3_K_M_GGUF, Q3_K_M_DENSE = 10, 11
 Q2_K_GGUF, Q2_K_DENSE = 12, 13
+# the IQ4_XS mix (IQ4_XS bulk; Q5_K for attn_v under grouped-query attention and for the first ffn_down; Q6_K head) and its f32 twin
+IQ4_XS_GGUF, IQ4_XS_DENSE = 14, 15
 # gguf kind -> the same values as f32 matmuls (llama_decode.cpp: kSbMixes)
-DENSE_TWIN = {Q4_K_GGUF: Q4_K_DENSE, Q4_K_M_GGUF: Q4_K_M_DENSE, Q5_K_M_GGUF: Q5_K_M_DENSE, Q3_K_M_GGUF: Q3_K_M_DENSE, Q2_K_GGUF: Q2_K_DENSE}
+DENSE_TWIN = {Q4_K_GGUF: Q4_K_DENSE, Q4_K_M_GGUF: Q4_K_M_DENSE, Q5_K_M_GGUF: Q5_K_M_DENSE, Q3_K_M_GGUF: Q3_K_M_DENSE, Q2_K_GGUF: Q2_K_DENSE,
+              IQ4_XS_GGUF: IQ4_XS_DENSE}
 
 
 class Config(C.Structure):

@@ -248,7 +248,7 @@ def ios_to_c(ios: Sequence[ProgramIO]):
     return arr
 
 
-SUPER_BLOCK_BYTES = {"q2_k": 84, "q3_k": 110, "q4_k": 144, "q5_k": 176, "q6_k": 210}  # GGUF super-blocks of 256 flat elements
+SUPER_BLOCK_BYTES = {"q2_k": 84, "q3_k": 110, "iq4_xs": 136, "q4_k": 144, "q5_k": 176, "q6_k": 210}  # GGUF super-blocks of 256 flat elements
 
 
 @dataclass
@@ -259,14 +259,14 @@ class QuantizedWeightUpload:
     cols: int           # N
     block_size: int = 32
     # packed-GGUF pass-through (include/zgml_hip.h): `data` holds the raw uint8 file
-    # blocks (18 B Q4_0 / 34 B Q8_0 per 32 flat elements, 84 B Q2_K / 110 B Q3_K / 144 B Q4_K / 176 B Q5_K / 210 B Q6_K per 256) and `scales` is empty
+    # blocks (18 B Q4_0 / 34 B Q8_0 per 32 flat elements, 84 B Q2_K / 110 B Q3_K / 136 B IQ4_XS / 144 B Q4_K / 176 B Q5_K / 210 B Q6_K per 256) and `scales` is empty
     gguf: Optional[str] = None
 
     @staticmethod
     def from_gguf_blocks(raw: np.ndarray, rows: int, cols: int, kind: str) -> "QuantizedWeightUpload":
-        """kind "q4_0" / "q8_0": 18 / 34-byte blocks of 32 flat elements; "q2_k" / "q3_k" / "q4_k" / "q5_k" / "q6_k": 84 / 110 / 144 / 176 / 210-byte super-blocks of 256
+        """kind "q4_0" / "q8_0": 18 / 34-byte blocks of 32 flat elements; "q2_k" / "q3_k" / "iq4_xs" / "q4_k" / "q5_k" / "q6_k": 84 / 110 / 136 / 144 / 176 / 210-byte super-blocks of 256
         (cols % 256 == 0)."""
-        assert kind in ("q4_0", "q8_0", "q2_k", "q3_k", "q4_k", "q5_k", "q6_k")
+        assert kind in ("q4_0", "q8_0", "q2_k", "q3_k", "iq4_xs", "q4_k", "q5_k", "q6_k")
         raw = np.ascontiguousarray(raw, dtype=np.uint8).ravel()
         if kind in SUPER_BLOCK_BYTES:
             assert cols % 256 == 0 and raw.size == rows * cols // 256 * SUPER_BLOCK_BYTES[kind]
@@ -403,7 +403,7 @@ class DeviceProgram:
                 n_elems = op.K * op.N
                 n_blocks = (n_elems + qw.block_size - 1) // qw.block_size
                 if qw.gguf is not None:
-                    if qw.block_size == 256:  # Q2_K .. Q6_K super-blocks: the byte count says which
+                    if qw.block_size == 256:  # Q2_K .. Q6_K and IQ4_XS super-blocks: the byte count says which
                         if op.N % 256 or qw.data.size not in [n_elems // 256 * b for b in SUPER_BLOCK_BYTES.values()]:
                             return False
                     elif n_elems % 32 or op.N % 32 or qw.block_size != 32 or qw.data.size not in (n_elems // 32 * 18, n_elems // 32 * 34):
