@@ -473,6 +473,10 @@ enum {
      * Llama-2-7B size; 2..8: that bound (the kernel exists up to 8 rows). Such a weight is packed K-on-lanes
      * when EVERY qmatmul over it has M <= bound (without the option: M = 1), and a later refresh that raises M above the bound over
      * it is refused. Same results within the mat-vec tolerance. Short-K weights keep the n-on-lanes layout and the tile kernels.
+     * GGUF super-block weights (Q4_K / Q5_K / Q6_K / Q3_K / Q2_K / IQ4_XS): qmatmuls of 2 <= M <= bound rows take the multi-row
+     * mat-vecs of zgml_amd/csrc/sb_kernels.hip instead of the matrix-core kernel; row m of such a launch is bit-identical to the
+     * M = 1 launch over that row. 1: the bound is per format, measured (3 / 4 / 4 / 4 / 6 / 3); 2..8: that
+     * bound. Their layout does not depend on the option: a refresh above the bound runs the matrix-core kernel, nothing is refused.
      * Read at compile_program. */
     ZGML_HIP_OPT_SMALL_M_MATVEC = 11,
     /* 0 (default) / 1: zgml_hip_kv_move's 16-byte loads (and, in the copying forms, its 16-byte stores) are non-temporal; the

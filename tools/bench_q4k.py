@@ -2,7 +2,9 @@
 kernel and the M = 32 matmul against the tile kernel, at 4096^2, 4096 x 11008 and 4096 x 32000. Q4_0 and Q4_K stream 4.5 bit/weight,
 so their bytes per launch are equal and the times compare directly; Q5_K streams 176/144, Q6_K 210/144, Q3_K 110/144, Q2_K 84/144 and IQ4_XS 136/144 of that, so the GB/s are printed too. A ring of distinct matrices larger than the 256 MiB Infinity Cache
 stands for a model; device-event time per launch over replays of a captured graph (zgml_hip_qmatmul_bench); the formats
-alternate within each repeat and every repeat is printed, so the spread shows next to the difference."""
+alternate within each repeat and every repeat is printed, so the spread shows next to the difference.
+--rows: the super-block formats at M = 2..8 with ZGML_HIP_OPT_SMALL_M_MATVEC at 8 (the multi-row mat-vecs) and at 0 (the matrix-core
+kernel), alternating within each repeat: what the formats' kRowsRoutedM are set by."""
 import argparse
 import ctypes as C
 import json
@@ -10,7 +12,7 @@ import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-from zgml_amd import Backend  # noqa: E402
+from zgml_amd import Backend, capi  # noqa: E402
 
 FMT = {"q4_0": 1, "q4_k": 2, "q5_k": 4, "q6_k": 3, "q3_k": 5, "q2_k": 6, "iq4_xs": 7}  # the `q4` argument of zgml_hip_qmatmul_bench
 
@@ -28,12 +30,25 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--shapes", default="4096x4096,4096x11008,4096x32000")
+    ap.add_argument("--rows", action="store_true")
     a = ap.parse_args()
     be = Backend(0)
     for shp in a.shapes.split(","):
         K, N = map(int, shp.split("x"))
         ring = max(2, min(64, int(40e9 // (K * N))))
-        for M in (1, 32):
+        for M in range(2, 9) if a.rows else ():
+            for f in (f for f in FMT if f != "q4_0"):
+                us = {"rows": [], "matmul": []}
+                for _ in range(a.repeats):
+                    for route, value in (("rows", 8), ("matmul", 0)):
+                        be.set_option(capi.OPT_SMALL_M_MATVEC, value)
+                        try:
+                            us[route].append(round(run(be, f, M, K, N, ring, max(64, a.iters // 8))[0], 3))
+                        finally:
+                            be.set_option(capi.OPT_SMALL_M_MATVEC, 0)
+                print(json.dumps({"K": K, "N": N, "M": M, "format": f, "ring": ring, "us": us,
+                                  "rows_over_matmul": round(min(us["rows"]) / min(us["matmul"]), 3)}), flush=True)
+        for M in () if a.rows else (1, 32):
             us, nbytes = {f: [] for f in FMT}, {}
             for _ in range(a.repeats):
                 for f in FMT:

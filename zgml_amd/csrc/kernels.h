@@ -222,15 +222,15 @@ struct SbFormatRow {
     int form;
     uint32_t block_bytes;
     int bench_code;
-    const char *matvec_tag, *matmul_tag;
+    const char *matvec_tag, *matmul_tag, *rows_tag; // M = 1, the matrix-core kernel, the multi-row mat-vec (2 <= M <= 8, opt-in)
 };
 constexpr SbFormatRow kSbFormats[] = {
-    {QW_SB4, 3, ZGML_QW_GGUF_Q4_K_BLOCK_BYTES, 2, "q4k-matvec", "q4k-matmul"},
-    {QW_SB6, 4, ZGML_QW_GGUF_Q6_K_BLOCK_BYTES, 3, "q6k-matvec", "q6k-matmul"},
-    {QW_SB5, 5, ZGML_QW_GGUF_Q5_K_BLOCK_BYTES, 4, "q5k-matvec", "q5k-matmul"},
-    {QW_SB3, 6, ZGML_QW_GGUF_Q3_K_BLOCK_BYTES, 5, "q3k-matvec", "q3k-matmul"},
-    {QW_SB2, 7, ZGML_QW_GGUF_Q2_K_BLOCK_BYTES, 6, "q2k-matvec", "q2k-matmul"},
-    {QW_SB4X, 8, ZGML_QW_GGUF_IQ4_XS_BLOCK_BYTES, 7, "iq4xs-matvec", "iq4xs-matmul"},
+    {QW_SB4, 3, ZGML_QW_GGUF_Q4_K_BLOCK_BYTES, 2, "q4k-matvec", "q4k-matmul", "q4k-rows"},
+    {QW_SB6, 4, ZGML_QW_GGUF_Q6_K_BLOCK_BYTES, 3, "q6k-matvec", "q6k-matmul", "q6k-rows"},
+    {QW_SB5, 5, ZGML_QW_GGUF_Q5_K_BLOCK_BYTES, 4, "q5k-matvec", "q5k-matmul", "q5k-rows"},
+    {QW_SB3, 6, ZGML_QW_GGUF_Q3_K_BLOCK_BYTES, 5, "q3k-matvec", "q3k-matmul", "q3k-rows"},
+    {QW_SB2, 7, ZGML_QW_GGUF_Q2_K_BLOCK_BYTES, 6, "q2k-matvec", "q2k-matmul", "q2k-rows"},
+    {QW_SB4X, 8, ZGML_QW_GGUF_IQ4_XS_BLOCK_BYTES, 7, "iq4xs-matvec", "iq4xs-matmul", "iq4xs-rows"},
 };
 // the row with pick(row) true, or nullptr
 template <class Pick>
@@ -327,6 +327,7 @@ struct QMatmulParams {
     uint32_t M, N, K;
     uint32_t in_rs, dst_rs;
     uint32_t reuse_split = 0; // M > 1: the scratch already holds this input's A pieces (previous launch, same rows)
+    uint32_t sb_rows_m = 0;   // super-block weights: 2 <= M <= this takes the multi-row mat-vecs (sb_rows_bound; 0: the matmul kernel)
 };
 
 // generic kernels (kernels_generic.hip; argmax and the resident loops' prep: greedy_tail.hip)
@@ -788,12 +789,18 @@ void launch_w8a8_matvec(hipStream_t s, const QWeightDev& w, const float* x, floa
 // same set for all three), sizes of a format's packed image (4.5 / 5.5 / 6.5625 bit/weight like the file), the device re-pack of
 // the file's super-blocks and the micro-benchmark's synthetic weights (out.format / w.format selects which), the scratch an M = 1
 // launch splits K through (the same block and counter head as qmatmul_scratch_bytes describes below) and the launch for any M
-// (M = 1: the streaming mat-vec, M > 1: bf16 matrix cores)
+// (M = 1: the streaming mat-vec, M > 1: bf16 matrix cores; 2 <= M <= QMatmulParams::sb_rows_m <= 8: the multi-row mat-vecs, whose
+// [parts][M][N] partials sb_scratch_bytes counts for such an M)
 bool sb_applies(uint64_t K, uint64_t N);
 void sb_packed_bytes(QWFormat format, uint64_t K, uint64_t N, uint64_t* qs_bytes, uint64_t* sc_bytes);
 void launch_pack_sb(hipStream_t s, const uint8_t* raw_blocks, const QWeightDev& out);
 void launch_synth_sb(hipStream_t s, const QWeightDev& w, uint32_t matrix_id);
 uint64_t sb_scratch_bytes(const QWeightDev& w, uint32_t M);
+// 2 <= M <= 8 rows through the M = 1 kernels' own arithmetic, R rows per weight pass (ZGML_HIP_OPT_SMALL_M_MATVEC): the bound a
+// program's option value (0 off, 1 the format's measured bound, 2..8) gives a format, and whether an M-row launch over w takes the
+// row kernels under a bound (QMatmulParams::sb_rows_m): the one predicate of the launcher, the plan text and the scratch size
+uint32_t sb_rows_bound(QWFormat format, uint32_t option);
+bool sb_rows_routed(const QWeightDev& w, uint32_t M, uint32_t max_m);
 void launch_sb_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch);
 void packed_bytes(QWFormat format, uint32_t scale_f16, uint64_t K, uint64_t N, uint64_t* qs_bytes,
                   uint64_t* sc_bytes);

@@ -256,7 +256,10 @@ bool make_single(zgml_hip_program* p, size_t i, Launch& L) {
                 p->split_pos = pos - 1; // the merged launch still sits at the previous plan position
                 return false;
             }
-            if (const SbFormatRow* sb = sb_format_row(w.format)) L.tag = qp.M == 1 ? sb->matvec_tag : sb->matmul_tag;
+            if (const SbFormatRow* sb = sb_format_row(w.format)) {
+                qp.sb_rows_m = sb_rows_bound(w.format, p->sb_rows_opt);
+                L.tag = qp.M == 1 ? sb->matvec_tag : sb_rows_routed(w, qp.M, qp.sb_rows_m) ? sb->rows_tag : sb->matmul_tag; // (the launcher's own predicate)
+            }
             if (w.format == QW_Q4K && qp.M >= 2 && qp.M <= p->kon_max_m) L.tag = "qmatvec-kon-rows"; // (launch_qmatmul: the multi-row K-on-lanes mat-vec)
             auto group = std::make_shared<std::vector<std::pair<QWeightDev, QMatmulParams>>>();
             group->push_back({w, qp});

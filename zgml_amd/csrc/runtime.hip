@@ -659,6 +659,7 @@ int zgml_hip_set_option(zgml_hip_ctx* ctx, int option, int64_t value) {
         case ZGML_HIP_OPT_W8A8: ctx->opt_w8a8 = value != 0; return 0;     // (decides the weights' device format at compile_program)
         case ZGML_HIP_OPT_SMALL_M_MATVEC: // (same) 1: the measured bound; 2..8: that bound
             ctx->opt_small_m = value <= 0 ? 0 : (value == 1 ? kKonRowsRoutedM : (uint32_t)std::min<int64_t>(value, kKonRowsMaxM));
+            ctx->opt_sb_rows = value <= 0 ? 0 : (uint32_t)std::min<int64_t>(value, kKonRowsMaxM); // (the super-block formats keep a measured bound each)
             return 0;
         case ZGML_HIP_OPT_KV_MOVE_NT: ctx->opt_kv_move_nt = value != 0; return 0;
         case ZGML_HIP_OPT_DENSE_WEIGHT_CACHE:
@@ -911,6 +912,7 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     // a weight an M > 1 matmul reads keeps the n-on-lanes layout the tile kernels are built for. ZGML_HIP_OPT_SMALL_M_MATVEC moves
     // the bound up (M <= 6 by default, at most 8): those row counts have a K-on-lanes kernel of their own (qmatvec_rows.hip)
     p->kon_max_m = ctx->opt_small_m ? ctx->opt_small_m : 1;
+    p->sb_rows_opt = ctx->opt_sb_rows; // (the super-block weights keep their layout: the option only routes their 2 <= M <= bound launches, sb_kernels.hip)
     std::vector<char> qw_m1(prog->n_qweights, sw().hip_qmv_kon ? 1 : 0);
     std::vector<char> qw_m1_all(prog->n_qweights, 1); // every use is a dense M = 1 row (the W8A8 arm's condition, reference.zig:512-516)
     for (const auto& op : p->ops)
@@ -1021,8 +1023,11 @@ zgml_hip_program* zgml_hip_compile_program(zgml_hip_ctx* ctx, const zgml_device_
     for (const auto& op : p->ops)
         if (op.kind == ZGML_DOP_QMATMUL) {
             const QWeightDev& w = p->qweights[op.u.qmatmul.weight_idx];
-            // (a Q4_K / Q5_K / Q6_K weight takes any M after a refresh, and only its M = 1 launch wants scratch: sized for that one)
+            // (a super-block weight takes any M after a refresh, and its M = 1 launch and the row launches up to the program's bound
+            // want scratch: sized for all of those, so a refresh to any M has what its launch needs)
             uint64_t b = qmatmul_scratch_bytes(w, qw_super_block(w.format) ? 1 : op.u.qmatmul.M);
+            if (qw_super_block(w.format))
+                for (uint32_t m = 2; m <= sb_rows_bound(w.format, p->sb_rows_opt); m++) b = std::max(b, qmatmul_scratch_bytes(w, m));
             if (b > p->scratch_bytes) p->scratch_bytes = b;
         } else if (op.kind == ZGML_DOP_MATMUL && op.u.matmul.b < p->f16_weights.size() && p->f16_weights[op.u.matmul.b]) {
             uint64_t b = dense_f16_scratch_bytes((uint32_t)op.u.matmul.geom.M, (uint32_t)op.u.matmul.geom.K); // pre-rounded A operand

@@ -112,7 +112,9 @@ double zgml_hip_qmatmul_bench(zgml_hip_ctx* ctx, uint32_t M, uint32_t K, uint32_
     char* scratch_base = nullptr;
     std::vector<float> xh((size_t)M * K);
     for (size_t i = 0; i < xh.size(); i++) xh[i] = ((int)(i % 17) - 8) * 0.03125f;
-    uint64_t sb = ok ? qmatmul_scratch_bytes(ring[0], M) : 0;
+    // (a super-block launch of M > 1 rows that the context's ZGML_HIP_OPT_SMALL_M_MATVEC does not route runs the matrix-core kernel: no scratch)
+    const uint32_t sb_rows_m = ok && qw_super_block(ring[0].format) ? sb_rows_bound(ring[0].format, ctx->opt_sb_rows) : 0;
+    uint64_t sb = ok && !(qw_super_block(ring[0].format) && M > 1 && !sb_rows_routed(ring[0], M, sb_rows_m)) ? qmatmul_scratch_bytes(ring[0], M) : 0;
     ok = ok && CTX_CHECK(ctx, hipMalloc((void**)&x, xh.size() * 4)) && CTX_CHECK(ctx, hipMalloc((void**)&y, (size_t)M * N * 4)) &&
          (!sb || (CTX_CHECK(ctx, hipMalloc((void**)&scratch_base, kQmmScratchHead + sb)) && CTX_CHECK(ctx, hipMemsetAsync(scratch_base, 0, kQmmScratchHead, ctx->stream)))) &&
          CTX_CHECK(ctx, hipMemcpy(x, xh.data(), xh.size() * 4, hipMemcpyHostToDevice));
@@ -120,6 +122,7 @@ double zgml_hip_qmatmul_bench(zgml_hip_ctx* ctx, uint32_t M, uint32_t K, uint32_
     double us = -1.0;
     if (ok) {
         QMatmulParams qp{y, x, M, N, K, K, N};
+        qp.sb_rows_m = sb_rows_m; // (the context's ZGML_HIP_OPT_SMALL_M_MATVEC, as compile_program reads it)
         for (uint32_t i = 0; i < warmup; i++) launch_qmatmul(ctx->stream, ring[i % n_matrices], qp, scratch);
         // One pass over the ring is captured into a hipGraph and replayed: back-to-back eager
         // launches are host-bound below ~3 us per kernel on this platform, a graph is not.

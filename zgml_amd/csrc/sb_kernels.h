@@ -45,6 +45,7 @@ constexpr uint32_t kSbWaves = 8;   // M = 1: waves of a workgroup = item columns
 constexpr uint32_t kSbSweep = 64;  // k per wave sweep (one per lane)
 constexpr uint32_t kSbSweeps = 4;  // sweeps of a round (Q5_K, Q6_K): all loaded before the first is consumed
 constexpr uint32_t kSbRound = kSbSweep * kSbSweeps; // k of a round = rows of the factors in LDS
+constexpr uint32_t kSbRowsPerGroup = 4; // 2 <= M <= 8: rows of a row group (128 of a wave's 256 VGPRs are its accumulators)
 static_assert(kQ4kBlock == kSbBlock && kQ5kBlock == kSbBlock && kQ6kBlock == kSbBlock && kQ4kSub == kSbItem && kQ5kSub == kSbItem && 2 * kQ6kSub == kSbItem, "");
 static_assert(kQ3kBlock == kSbBlock && kQ2kBlock == kSbBlock && 2 * kQ3kSub == kSbItem && 2 * kQ2kSub == kSbItem, "");
 static_assert(kIq4xsBlock == kSbBlock && kIq4xsSub == kSbItem, "");
@@ -141,6 +142,23 @@ __device__ __forceinline__ void sb_matvec_tail(const Args& a, const float (&red)
     if (a.parts > 1 && !sb_combine(y, threadIdx.x < kSbBlock, a.partial, a.counter + nsb, part, a.parts, a.N, n, flag)) return;
     if (threadIdx.x < kSbBlock) a.dst[n] = y;
 }
+// 2 <= M <= 8 rows: the same tail over the R rows of a row group that starts at row m0 (`rows` of them live). red[rr] is row rr's
+// M = 1 red; the 512 threads take one column and every second row each, and the group's parts meet on the group's own counter word
+template <int R, class Args>
+__device__ __forceinline__ void sb_rows_tail(const Args& a, const float (&red)[R][kSbWaves][kSbItem], uint32_t* flag, uint32_t nsb, uint32_t part, uint32_t m0,
+                                             uint32_t rows) {
+    __syncthreads();
+    const uint32_t col = threadIdx.x & (kSbBlock - 1), odd = threadIdx.x >> 8, n = nsb * kSbBlock + col;
+    float y[R];
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) y[rr] = red[rr][col >> 5][col & 31];
+    if (a.parts > 1 && !sb_combine_rows<R>(y, odd, rows, a.partial + (uint64_t)m0 * a.N, (uint64_t)a.M * a.N, a.counter + blockIdx.z * (a.N / kSbBlock) + nsb, part,
+                                           a.parts, a.N, n, flag))
+        return;
+#pragma unroll
+    for (int rr = 0; rr < R; rr++)
+        if ((rr & 1) == (int)odd && rr < (int)rows) a.dst[(uint64_t)(m0 + rr) * a.dst_rs + n] = y[rr];
+}
 
 // M > 1: a wave's own LDS slice: its DS operations run in order, so a wave barrier is all that a write -> read (or read -> next
 // write) hand-over needs
@@ -232,6 +250,7 @@ __device__ __forceinline__ void sb_fold_waves(const Args& a, float (&fold)[WAVES
 // stream the weights non-temporally (beyond it several workgroup rows re-read them: keep them cached).
 // pack_item() / pack_factors(): item `idx` = (sub-block js, k) / the factor entry `fidx` from file block `blk`. synth(): the
 // deterministic pattern of the micro-benchmark, in the packed layout (every q; sc and m over their ranges; d = 2^-10).
+// kRowsRoutedM: the largest M ZGML_HIP_OPT_SMALL_M_MATVEC = 1 routes to the row kernels (measured per format).
 // chunk_factors(): the item's factor rows at row k: f[kScales] = d * sc (of the item, or of columns 0..15 and 16..31), mn[kScales] =
 // dmin * m beside each (kMin).
 // Round kernels only: Lo / Hi + load_lo() / load_hi(): an item's low and high plane entries (Hi = SbNoHi: none); RoundLds: the round's factors in LDS; round_load() / round_store(): the duty of thread
@@ -242,6 +261,7 @@ struct Sb4 {
     static constexpr const char* kName = "Q4_K";
     static constexpr uint32_t kFileBytes = kQ4kBytes, kItemBytes = 16, kFactorBytes = kQ4kHeaderBytes; // 4.5 bit/weight like the file
     static constexpr uint32_t kScales = 1, kNtMaxM = 16;
+    static constexpr uint32_t kRowsRoutedM = 3;
     static constexpr bool kMin = true, kRound = false;
     static constexpr int kBias = 0;
     struct Planes {
@@ -272,6 +292,7 @@ struct Sb5 {
     static constexpr const char* kName = "Q5_K";
     static constexpr uint32_t kFileBytes = kQ5kBytes, kItemBytes = 16 + 4, kFactorBytes = kQ4kHeaderBytes; // 5.5 bit/weight like the file
     static constexpr uint32_t kScales = 1, kNtMaxM = 32;
+    static constexpr uint32_t kRowsRoutedM = 4;
     static constexpr bool kMin = true, kRound = true;
     static constexpr int kBias = 0;
     using Hi = uint32_t; // bit 4 h + s of byte b = high bit of column 16 h + 4 s + b
@@ -354,6 +375,7 @@ struct Sb6 {
     static constexpr const char* kName = "Q6_K";
     static constexpr uint32_t kFileBytes = kQ6kBytes, kItemBytes = 16 + 8, kFactorBytes = 16 + 2; // 6.5625 bit/weight like the file
     static constexpr uint32_t kScales = 2, kNtMaxM = 32;
+    static constexpr uint32_t kRowsRoutedM = 4;
     static constexpr bool kMin = false, kRound = true;
     static constexpr int kBias = 32;
     using Hi = uint2; // dword h (columns 16 h .. 16 h + 15), byte b, bits 2 s .. 2 s + 1 = high pair of column 16 h + 4 s + b
@@ -450,6 +472,7 @@ struct Sb3 {
     static constexpr const char* kName = "Q3_K";
     static constexpr uint32_t kFileBytes = kQ3kBytes, kItemBytes = 8 + 4, kFactorBytes = 12 + 2; // 3.4375 bit/weight like the file
     static constexpr uint32_t kScales = 2, kNtMaxM = 32;
+    static constexpr uint32_t kRowsRoutedM = 4;
     static constexpr bool kMin = false, kRound = true;
     static constexpr int kBias = 4;
     using Lo = uint2;
@@ -540,6 +563,7 @@ struct Sb2 {
     static constexpr const char* kName = "Q2_K";
     static constexpr uint32_t kFileBytes = kQ2kBytes, kItemBytes = 8, kFactorBytes = 16 + 4; // 2.625 bit/weight like the file
     static constexpr uint32_t kScales = 2, kNtMaxM = 32;
+    static constexpr uint32_t kRowsRoutedM = 6;
     static constexpr bool kMin = true, kRound = true;
     static constexpr int kBias = 0;
     using Lo = uint2;
@@ -615,6 +639,7 @@ struct Sb4x {
     static constexpr const char* kName = "IQ4_XS";
     static constexpr uint32_t kFileBytes = kIq4xsBytes, kItemBytes = 16, kFactorBytes = kIq4xsHeaderBytes; // 4.25 bit/weight like the file
     static constexpr uint32_t kScales = 1, kNtMaxM = 32;
+    static constexpr uint32_t kRowsRoutedM = 3;
     static constexpr bool kMin = false, kRound = true;
     static constexpr int kBias = kSbSigned;
     using Lo = uint4;

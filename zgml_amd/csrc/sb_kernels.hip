@@ -14,6 +14,12 @@
 //   Q4_K (sb4_matvec_kernel): sweep by sweep with a one-sweep look-ahead (one dwordx4 of nibbles, one dwordx4 of header — the 8
 //   waves of the workgroup read the same headers, so HBM sees each once —, one x), the header unpacked per item.
 //
+// 2 <= M <= 8, opt-in (ZGML_HIP_OPT_SMALL_M_MATVEC -> QMatmulParams::sb_rows_m). sb_round_rows_kernel<F, R> / sb4_rows_kernel<R>: the
+// M = 1 kernels over the R = 2..4 rows of a row group (blockIdx.z; M = 5..8: two groups of cdiv(M, 2) and M / 2 rows, each streaming the
+// weights): the quants of a sweep are unpacked once and every weight converted once for R FMAs, the factors in LDS serve all rows. A
+// row keeps the M = 1 launch's K split, FMA order, lane fold and part-order combine ([parts][M][N] partials, one counter word per (row
+// group, super-block column)), so row m is bit-identical to the M = 1 launch over x[m].
+//
 // M > 1. A workgroup owns one item column (32 output columns = two 16-column MFMA tiles) and its waves deal the 64-k chunks. Per
 // chunk a wave loads 64 items coalesced, turns their bytes ONCE through its own LDS slice into [column][k] order and leaves the
 // chunk's two factor rows beside them. B = q - bias, exact in bf16; A = t = x * (d * sc) in f32, split into three bf16 pieces,
@@ -188,6 +194,147 @@ SbSplit sb_round_split(uint32_t K, uint32_t N, bool split) {
 template <class F>
 SbSplit sb_split(uint32_t K, uint32_t N, bool split) {
     return F::kRound ? sb_round_split(K, N, split) : sb4_split(K, N, split);
+}
+
+// ── 2 <= M <= 8: the M = 1 kernels over R rows at once ──
+// A row group of R rows (blockIdx.z) streams the weights once: per sweep the quants are unpacked once and every weight converted
+// once, and the conversion feeds R FMAs. Every row keeps the M = 1 kernel's own split, FMA order, lane fold and part-order
+// combine, so row m of the launch is bit-identical to the M = 1 launch over x[m].
+template <class F>
+struct SbRowsArgs {
+    typename F::Planes w;
+    const float* x;
+    float* dst;
+    float* partial;    // [parts][M][N] (parts > 1)
+    uint32_t* counter; // [row groups][N / 256] fan-in words, zero between launches
+    uint32_t M, K, N, in_rs, dst_rs, share, parts;
+};
+
+template <class F, int R, bool NT>
+__global__ void __launch_bounds__(kSbWaves * 64) sb_round_rows_kernel(SbRowsArgs<F> a) {
+    __shared__ typename F::RoundLds fac; // the round's factors, shared by the rows
+    __shared__ float red[R][kSbWaves][kSbItem];
+    __shared__ uint32_t flag;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane >> 4, i = lane & 15;
+    const uint32_t nsb = blockIdx.x, part = blockIdx.y, m0 = blockIdx.z * R, rows = min((uint32_t)R, a.M - m0);
+    const uint32_t k_lo = part * a.share, k_hi = min(a.K, k_lo + a.share); // k_lo < K: the host sizes `parts` so
+    const typename F::Planes c = F::at(a.w, (uint64_t)(nsb * kSbWaves + w) * a.K, (uint64_t)nsb * a.K);
+    const uint32_t fkl = threadIdx.x & (kSbRound - 1), fhalf = threadIdx.x >> 8;
+    const float* xr[R]; // (a row past the group's last: the last row of the launch again, never stored)
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) xr[rr] = a.x + (uint64_t)min(m0 + rr, a.M - 1) * a.in_rs;
+
+    float acc[R][32], macc[R][F::kScales];
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) {
+#pragma unroll
+        for (int n = 0; n < 32; n++) acc[rr][n] = 0.f;
+#pragma unroll
+        for (uint32_t h = 0; h < F::kScales; h++) macc[rr][h] = 0.f;
+    }
+    for (uint32_t k0 = k_lo; k0 < k_hi; k0 += kSbRound) {
+        const typename F::RoundRaw raw = F::round_load(c, min(k0 + fkl, k_hi - 1), fhalf);
+        typename F::Lo ql[kSbSweeps];
+        typename F::Hi qh[kSbSweeps];
+        float xs[kSbSweeps][R];
+#pragma unroll
+        for (uint32_t s = 0; s < kSbSweeps; s++) {
+            const uint32_t k = k0 + s * kSbSweep + lane, kc = min(k, k_hi - 1);
+            ql[s] = F::template load_lo<NT>(c, kc);
+            qh[s] = F::template load_hi<NT>(c, kc);
+#pragma unroll
+            for (int rr = 0; rr < R; rr++) xs[s][rr] = k < k_hi ? xr[rr][kc] : 0.f;
+        }
+        F::round_store(fac, raw, fkl, fhalf, k0 + fkl < k_hi);
+        __syncthreads();
+#pragma unroll
+        for (uint32_t s = 0; s < kSbSweeps; s++) {
+            if (k0 + s * kSbSweep >= k_hi) break; // (the same for the whole workgroup)
+            float t[R][F::kScales];
+#pragma unroll
+            for (int rr = 0; rr < R; rr++) F::item_factors(fac, w, s * kSbSweep + lane, xs[s][rr], t[rr], macc[rr]);
+            uint32_t q[8];
+            F::quants(ql[s], qh[s], q);
+#pragma unroll
+            for (int dd = 0; dd < 8; dd++)
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const float v = sb_operand<F::kBias>(q[dd], b); // one conversion, R FMAs
+#pragma unroll
+                    for (int rr = 0; rr < R; rr++) acc[rr][4 * dd + b] = __builtin_fmaf(t[rr][F::kScales == 2 ? dd >> 2 : 0], v, acc[rr][4 * dd + b]);
+                }
+        }
+        __syncthreads(); // the next round rewrites fac
+    }
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) sb_fold_lanes<F::kMin, (int)F::kScales>(acc[rr], macc[rr], red[rr][w], r, i);
+    sb_rows_tail<R>(a, red, &flag, nsb, part, m0, rows);
+}
+
+template <int R, bool NT>
+__global__ void __launch_bounds__(kSbWaves * 64) sb4_rows_kernel(SbRowsArgs<Sb4> a) {
+    __shared__ float red[R][kSbWaves][kSbItem];
+    __shared__ uint32_t flag;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane >> 4, i = lane & 15;
+    const uint32_t nsb = blockIdx.x, part = blockIdx.y, m0 = blockIdx.z * R, rows = min((uint32_t)R, a.M - m0);
+    const uint32_t k_lo = part * a.share, k_hi = min(a.K, k_lo + a.share); // k_lo < K: the host sizes `parts` so
+    const Sb4::Planes c = Sb4::at(a.w, (uint64_t)(nsb * kSbWaves + w) * a.K, (uint64_t)nsb * a.K);
+    const float* xr[R];
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) xr[rr] = a.x + (uint64_t)min(m0 + rr, a.M - 1) * a.in_rs;
+
+    struct Item {
+        uint4 q, h;
+        float x[R];
+    };
+    auto load = [&](uint32_t k0) {
+        const uint32_t k = k0 + lane, kc = min(k, k_hi - 1); // past the share: a live item again, with x = 0
+        Item it;
+        it.q = wload<NT>(c.lo + kc);
+        it.h = c.hdr[kc];
+#pragma unroll
+        for (int rr = 0; rr < R; rr++) it.x[rr] = k < k_hi ? xr[rr][kc] : 0.f;
+        return it;
+    };
+    float acc[R][32], macc[R][1];
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) {
+#pragma unroll
+        for (int n = 0; n < 32; n++) acc[rr][n] = 0.f;
+        macc[rr][0] = 0.f;
+    }
+    auto consume = [&](const Item& it) {
+        const Q4kFactors f = sb_header_factors(it.h, w); // the header unpacked once for the rows
+        float t[R];
+#pragma unroll
+        for (int rr = 0; rr < R; rr++) {
+            t[rr] = it.x[rr] * f.scale;
+            macc[rr][0] = __builtin_fmaf(it.x[rr], f.min, macc[rr][0]);
+        }
+        uint32_t q[8];
+        Sb4::quants(it.q, q);
+#pragma unroll
+        for (int dd = 0; dd < 4; dd++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const float v0 = sb_operand<0>(q[dd], b), v1 = sb_operand<0>(q[4 + dd], b);
+#pragma unroll
+                for (int rr = 0; rr < R; rr++) {
+                    acc[rr][4 * dd + b] = __builtin_fmaf(t[rr], v0, acc[rr][4 * dd + b]);
+                    acc[rr][16 + 4 * dd + b] = __builtin_fmaf(t[rr], v1, acc[rr][16 + 4 * dd + b]);
+                }
+            }
+    };
+    Item cur = load(k_lo);
+    for (uint32_t k0 = k_lo + kSbSweep; k0 < k_hi; k0 += kSbSweep) { // the next sweep's loads fly while this one is consumed
+        const Item nxt = load(k0);
+        consume(cur);
+        cur = nxt;
+    }
+    consume(cur);
+#pragma unroll
+    for (int rr = 0; rr < R; rr++) sb_fold_lanes<true, 1>(acc[rr], macc[rr], red[rr][w], r, i);
+    sb_rows_tail<R>(a, red, &flag, nsb, part, m0, rows);
 }
 
 // ── M > 1 ──
@@ -366,11 +513,46 @@ void launch_mm(hipStream_t s, const SbMmArgs<F>& a, bool xvec, bool nt) {
         nt ? launch_mm<F, RT, false, true>(s, a) : launch_mm<F, RT, false, false>(s, a);
 }
 
+// the row groups of an M-row launch: one of M rows up to kSbRowsPerGroup, else two of cdiv(M, 2) and M / 2 (blockIdx.z)
+constexpr uint32_t sb_row_groups(uint32_t M) { return M > kSbRowsPerGroup ? 2 : 1; }
+template <class F, int R, bool NT>
+void launch_rows(hipStream_t s, const SbRowsArgs<F>& a) {
+    const dim3 grid(a.N / kSbBlock, a.parts, sb_row_groups(a.M));
+    if constexpr (F::kRound)
+        sb_round_rows_kernel<F, R, NT><<<grid, kSbWaves * 64, 0, s>>>(a);
+    else
+        sb4_rows_kernel<R, NT><<<grid, kSbWaves * 64, 0, s>>>(a);
+}
+template <class F, int R>
+void launch_rows(hipStream_t s, const SbRowsArgs<F>& a, bool nt) {
+    nt ? launch_rows<F, R, true>(s, a) : launch_rows<F, R, false>(s, a);
+}
+
+// does an M-row launch over a K x N weight take the row kernels under the bound `max_m`? One counter word per (row group,
+// super-block column) has to fit the head — the condition under which the M = 1 launch splits K, times the groups —, so a
+// routed row always has its M = 1 split
+bool sb_rows_take(uint32_t N, uint32_t M, uint32_t max_m) {
+    return M >= 2 && M <= std::min(max_m, 2 * kSbRowsPerGroup) && (uint64_t)sb_row_groups(M) * (N / kSbBlock) <= kQmmCounterBytes / 4;
+}
+
 template <class F>
 void launch_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch) {
     if (p.K != w.K || p.N != w.N) {
         fprintf(stderr, "[zgml_hip] ERROR: a %u x %u matmul over a %u x %u %s weight: not launched\n", p.K, p.N, w.K, w.N, F::kName);
         return;
+    }
+    if (sb_rows_take(w.N, p.M, p.sb_rows_m)) {
+        const SbSplit sp = sb_split<F>(w.K, w.N, true); // the M = 1 launch's own split
+        if (sp.parts > 1 && !scratch) {
+            fprintf(stderr, "[zgml_hip] ERROR: a %u-row %s launch that splits K has no scratch: not launched\n", p.M, F::kName);
+            return;
+        }
+        const SbRowsArgs<F> a{F::planes(w), p.input, p.dst, scratch, scratch ? (uint32_t*)((char*)scratch - kQmmScratchHead) : nullptr, p.M, w.K, w.N, p.in_rs, p.dst_rs, sp.share, sp.parts};
+        switch (cdiv(p.M, sb_row_groups(p.M))) { // rows of the (first) group
+        case 2: return launch_rows<F, 2>(s, a, w.stream_nt != 0);
+        case 3: return launch_rows<F, 3>(s, a, w.stream_nt != 0);
+        default: return launch_rows<F, 4>(s, a, w.stream_nt != 0);
+        }
     }
     if (p.M == 1) {
         const SbSplit sp = sb_split<F>(w.K, w.N, scratch != nullptr);
@@ -421,10 +603,17 @@ void launch_synth_sb(hipStream_t s, const QWeightDev& w, uint32_t matrix_id) {
     sb_dispatch(w.format, [&](auto f) { synth_sb_kernel<decltype(f)><<<2048, kBlock, 0, s>>>(f.planes(w), w.K, w.N, matrix_id); });
 }
 
+uint32_t sb_rows_bound(QWFormat format, uint32_t option) {
+    if (option != 1) return std::min(option, 2 * kSbRowsPerGroup);
+    return sb_dispatch(format, [](auto f) { return f.kRowsRoutedM; });
+}
+
+bool sb_rows_routed(const QWeightDev& w, uint32_t M, uint32_t max_m) { return sb_rows_take(w.N, M, max_m); }
+
 uint64_t sb_scratch_bytes(const QWeightDev& w, uint32_t M) {
-    if (M != 1) return 0;
+    if (M != 1 && !sb_rows_routed(w, M, M)) return 0; // (the partials of M rows under a bound >= M: a caller with a smaller bound asks for its bound's rows, or for none)
     const SbSplit sp = sb_dispatch(w.format, [&](auto f) { return sb_split<decltype(f)>(w.K, w.N, true); });
-    return sp.parts > 1 ? (uint64_t)sp.parts * w.N * sizeof(float) : 0;
+    return sp.parts > 1 ? (uint64_t)sp.parts * M * w.N * sizeof(float) : 0;
 }
 
 void launch_sb_matmul(hipStream_t s, const QWeightDev& w, const QMatmulParams& p, float* scratch) {
